@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — constraint projections / second of the MI355X projector (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode fd|analytic] [--obj NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode fd|analytic] [--obj NAME] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic samples per GPU:
 project B uniform joint samples of config Wine_Bottle onto the closed-chain manifold
@@ -10,8 +11,10 @@ CPU oracle), compact the valid states, and — for N > 1 — all-gather them ove
 fixed-capacity collective, no host synchronisation inside the step).  Inputs are generated on the
 device before the timed region (resident in HBM).  Default workload is BASELINE.json configs[2]
 (Wine_Bottle, B = 262144, "HBM-roofline run"), which is also the per-GPU shard of the 8-GPU config
-(2097152 / 8); configs[1] (B = 4096), configs[3] (stefan, both tolerance sets) and the extend step
-are timed as secondary figures, each with an in-run bitwise check against the det oracle.
+(2097152 / 8).  With --full, configs[1] (B = 4096), configs[3] (stefan, both tolerance sets) and the
+extend step are timed as secondary figures, each with an in-run bitwise check against the det oracle.
+A plain run (no --full) sets up, warms up, times the steps, writes --dump-outputs if asked and
+prints the line: nothing else.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (fresh child processes, one per GPU, rendezvous on 127.0.0.1) and relays rank 0's line; under
@@ -21,8 +24,14 @@ Prints ONE JSON line on rank 0.  `value` is whole-job projections/s (all ranks' 
 ranks time).  `roofline` prices the dominant kernel against HBM as the metric asks (225 algorithmic
 bytes per projection); the path is FP64-VALU bound, so the honest efficiency figure
 `fp64` (2.4 kflop per Newton iteration x iterations / kernel time vs 78.6 TFLOP/s) sits beside it.
-`cpu_baseline` times the CPU oracle (glibc build = what the reference would call) on this box's
-host cores — the count actually usable, not the count the OS reports — rank 0, N = 1 only.
+`cpu_baseline` (--full) times the CPU oracle (glibc build = what the reference would call) on the
+host's cores — the count actually usable, not the count the OS reports — rank 0, N = 1 only.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's): projected.npy
+(B, 14) float64, ok.npy and iterations.npy (B,) float32, valid_states.npy (the compacted valid states;
+for N > 1 the all-gathered ones of every rank) float64.  Above DUMP_BYTES in all, every array keeps
+the same fixed, seeded sample of its rows, and <name>_rows.npy says which.  The inputs are a pure
+function of the arguments, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -41,6 +50,7 @@ BYTES_PER_PROJECTION = 225      # 112 B in + 112 B out + 1 B flag (SURVEY.md §8
 FLOP_PER_NEWTON_ITER = 2400.0   # analytic formulation = algorithmic minimum
 SEEDS = {4096: 0xC2, 262144: 0xC3}
 GATHER_CAPACITY = 0.5           # gather block = this fraction of the shard (about 22 % of uniform samples are valid)
+DUMP_BYTES = 64_000_000         # --dump-outputs: at most this many bytes in all
 
 
 def parse():
@@ -53,8 +63,13 @@ def parse():
     ap.add_argument("--obj", default="Wine_Bottle")
     ap.add_argument("--waves-per-cu", type=int, default=0)
     ap.add_argument("--tol", default="", help="tolerance1,tolerance2 (default: the reference's 1e-3,5e-3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline, the secondary configurations and the one-process forms, and run the in-run "
+                         "parity checks (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary figures and the one-process forms")
     ap.add_argument("--backend", default="nccl", help="rehearsal only: gloo lets several ranks share one GPU")
     ap.add_argument("--force-device", type=int, default=-1, help="rehearsal only: every rank uses this GPU")
     ap.add_argument("--one-process", type=int, default=0,
@@ -63,7 +78,10 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, rendezvous over gloo on the CPU, print the launch facts and exit (no GPU work: "
                          "checks the launcher on a box without GPUs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---- N ranks from one command ------------------------------------------------------------------------------------------
@@ -485,9 +503,14 @@ def main():
     sum_iters = float(it.to(torch.float64).sum().item())
     ok_frac = float(ok.to(torch.float64).mean().item())
     gathered = None
+    outputs = None
+    if args.dump_outputs and rank == 0:  # what the last timed step handed its caller, downloaded after the timed region
+        outputs = {"projected": q_out.cpu().numpy(), "ok": ok.cpu().numpy(), "iterations": it.cpu().numpy()}
     if vg is not None:
         counts = vg.counts()  # after the timed region: what the host tree would read when it consumes the states
         n_valid = counts[rank]
+        if outputs is not None:
+            outputs["valid_states"] = vg.unpack()[0].cpu().numpy()  # the last step's all-gather, before the probe reuses the blocks
         # what a first multi-GPU run is diagnosed by: every rank's own kernel time and wall clock, and how long the last
         # step's collective ran past the last projector kernel (one small all-gather, after the timed region)
         mine = torch.tensor([kms, local_elapsed * 1e3 / args.steps, kernel_ms[-1][1].elapsed_time(e_done)], dtype=torch.float64, device="cuda")
@@ -502,9 +525,11 @@ def main():
                     "step_ms_per_rank": [float(v) for v in per_rank[:, 1]],
                     "last_kernel_to_gather_done_ms_per_rank": [float(v) for v in per_rank[:, 2]],
                     "last_kernel_to_gather_done_ms_max": float(per_rank[:, 2].max()),
-                    "probe": gather_probe(c, vg, rank, world, torch, dist)}
+                    "probe": gather_probe(c, vg, rank, world, torch, dist) if args.full else None}
     else:
         n_valid = int(cnt.item())
+        if outputs is not None:
+            outputs["valid_states"] = q_valid[:n_valid].cpu().numpy()
     rccl_ranks = dist.get_world_size() if (world > 1 and args.backend == "nccl") else (1 if world == 1 else 0)
 
     if world > 1:
@@ -575,10 +600,13 @@ def main():
         "stats": {"ok_fraction": ok_frac, "mean_newton_iters": sum_iters / B, "valid_states_rank0": n_valid, "gather": gathered},
     }
 
-    if world == 1 and not args.no_secondary:
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+
+    if world == 1 and args.full and not args.no_secondary:
         line["secondary"] = secondary(args, c, ctx, B, torch, cfg_path)
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             gpu_check = None
             if args.mode == "fd" and not args.tol:
@@ -590,7 +618,7 @@ def main():
             line["cpu_baseline"] = {"error": repr(e)}
     if world > 1:
         dist.destroy_process_group()
-    if not args.no_secondary and args.mode == "fd":
+    if args.full and not args.no_secondary and args.mode == "fd":
         # the other multi-GPU form SURVEY.md section 8(e) names: ONE process driving all the GPUs through the C ABI (a fresh child,
         # started when every rank is done; with a deadline, and never allowed to take this line down with it)
         if world > 1:
@@ -602,6 +630,24 @@ def main():
         line.setdefault("secondary", {})["one_process"] = one
     flatten_for_the_driver(line, B)
     print(json.dumps(line), flush=True)
+
+
+def dump_outputs(d, arrays):
+    """{name: numpy array} -> d/<name>.npy: float64 stays float64, flags and counts become float32.  Above DUMP_BYTES in all,
+    every array keeps the same share of its rows, a sample drawn with a fixed seed, and d/<name>_rows.npy holds their numbers."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    budget = DUMP_BYTES - 2048 * len(arrays)  # room for the .npy headers
+    total = sum(v.nbytes for v in arrays.values())
+    share = 1.0 if total <= budget else budget / (total + sum(8 * len(v) for v in arrays.values()))  # the row numbers count too
+    for k, v in arrays.items():
+        if share < 1.0:
+            rows = np.sort(np.random.default_rng(0xD5).choice(len(v), int(len(v) * share), replace=False))
+            np.save(os.path.join(d, k + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def flatten_for_the_driver(line, B):

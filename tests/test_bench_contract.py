@@ -15,12 +15,13 @@ REQUIRED = {"metric": str, "value": float, "unit": str, "n_gpus": int, "steps": 
 def test_bench_help_needs_no_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
 
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16384"],
-                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16384",
+                          "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -171,6 +172,70 @@ def test_flat_keys_are_first_level_scalars():
     assert bare["roofline"]["fp64_executed_frac"] is None and "det_bit_identical" not in bare["cpu_baseline"]
 
 
+@pytest.mark.gpu
+def test_plain_bench_times_the_headline_only_and_dumps_its_last_step(gpu_ctx, oracle_det, tmp_path):
+    """A plain run (no --full) carries the headline and nothing that needs runs of its own; --steps is the number of timed steps;
+    --dump-outputs holds what the last timed step returned: the projections of the bench's own seeded samples (the det oracle's,
+    bit for bit, on a leading slice), their flags and iteration counts, and the compacted valid states in order."""
+    import numpy as np
+
+    from conftest import NCPU, config_path
+    from closed_chain_motion_planner_amd import KinematicChainConstraint
+
+    B = 16384
+    out = _run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B), "--dump-outputs", str(tmp_path / "out"))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    j = json.loads(lines[0])
+    for k, t in REQUIRED.items():
+        assert isinstance(j[k], t) or (t is float and isinstance(j[k], int)), (k, type(j[k]))
+    assert j["steps"] == 3 and len(j["roofline"]["kernel_ms_per_step"]) == 3 and j["ms_per_step"] > 0
+    assert "secondary" not in j and "cpu_baseline" not in j
+    d = tmp_path / "out"
+    q, ok, it, valid = (np.load(d / (n + ".npy")) for n in ("projected", "ok", "iterations", "valid_states"))
+    assert q.dtype == np.float64 and valid.dtype == np.float64 and ok.dtype == np.float32 and it.dtype == np.float32
+    assert q.shape == (B, 14) and ok.shape == (B,) and it.shape == (B,) and not list(d.glob("*_rows.npy"))
+    assert set(np.unique(ok)) <= {0.0, 1.0} and valid.shape == (j["stats"]["valid_states_rank0"], 14)
+    assert np.array_equal(valid.view(np.uint64), q[ok == 1].view(np.uint64))
+    c = KinematicChainConstraint.from_yaml(config_path("Wine_Bottle"), ctx=gpu_ctx)
+    P = oracle_det.checker_problem(config_path("Wine_Bottle"), c.problem)
+    m = 512
+    q_in = c.ambient_uniform_batch(0xC3, 0, m).cpu().numpy()  # bench.SEEDS: 0xC3 for any batch but 4096
+    qd, okd, itd = oracle_det.project_batch(P, q_in, NCPU)
+    assert np.array_equal(q[:m].view(np.uint64), qd.view(np.uint64))
+    assert np.array_equal(ok[:m], okd.astype(np.float32)) and np.array_equal(it[:m], itd.astype(np.float32))
+
+
+def test_dump_outputs_keeps_one_seeded_sample_of_rows_under_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs (no GPU needed): arrays under the limit are written whole, float64 as float64 and everything else as
+    float32; above it every array keeps the same seeded share of its rows, the row numbers are written beside, and the whole
+    stays under the limit"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(1)
+    arrays = {"projected": rng.standard_normal((5000, 14)), "ok": rng.integers(0, 2, 5000).astype(np.uint8),
+              "iterations": rng.integers(0, 250, 5000).astype(np.int16)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    w = {n: np.load(tmp_path / "whole" / (n + ".npy")) for n in arrays}
+    assert w["projected"].dtype == np.float64 and w["ok"].dtype == np.float32 and w["iterations"].dtype == np.float32
+    assert all(np.array_equal(w[n], arrays[n]) for n in arrays) and not list((tmp_path / "whole").glob("*_rows.npy"))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    d = tmp_path / "a"
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 200_000
+    rows = np.load(d / "projected_rows.npy")
+    assert 0 < len(rows) < 5000 and np.array_equal(rows, np.unique(rows))
+    for n in arrays:
+        assert np.array_equal(np.load(d / (n + "_rows.npy")), rows)
+        assert np.array_equal(np.load(d / (n + ".npy")), arrays[n][rows.astype(np.int64)].astype(w[n].dtype))
+        assert (d / (n + ".npy")).read_bytes() == (tmp_path / "b" / (n + ".npy")).read_bytes()
+
+
 def _run_bench(*argv, env=None, timeout=600):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
@@ -195,10 +260,11 @@ def test_bench_starts_its_own_ranks(ccmp_built):
 
 
 @pytest.mark.gpu
-def test_bench_two_ranks_from_the_bare_command():
+def test_bench_two_ranks_from_the_bare_command(tmp_path):
     """the N > 1 step for real — projection, capped compaction into the gather block, one all-gather per step — as two
     self-launched ranks sharing this box's one GPU over gloo (RCCL refuses two ranks on one device)"""
-    out = _run_bench("--gpus", "2", "--backend", "gloo", "--force-device", "0", "--steps", "1", "--warmup", "1", "--batch", "32768")
+    out = _run_bench("--gpus", "2", "--backend", "gloo", "--force-device", "0", "--steps", "1", "--warmup", "1", "--batch", "32768", "--full",
+                     "--dump-outputs", str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -212,6 +278,12 @@ def test_bench_two_ranks_from_the_bare_command():
     assert len(g["kernel_ms_per_rank"]) == 2 and g["kernel_ms_min"] <= g["kernel_ms_max"] and len(g["step_ms_per_rank"]) == 2
     assert len(g["last_kernel_to_gather_done_ms_per_rank"]) == 2 and g["bytes_sent_per_rank"] == 16385 * 112
     assert g["bytes_received_per_rank"] == 2 * g["bytes_sent_per_rank"]
+    # --dump-outputs on N ranks: rank 0's own projections, and the valid states of every rank as the all-gather delivered them
+    import numpy as np
+
+    q, ok, valid = (np.load(tmp_path / (n + ".npy")) for n in ("projected", "ok", "valid_states"))
+    assert q.shape == (32768, 14) and valid.shape == (g["valid_states_all_ranks"], 14)
+    assert np.array_equal(valid[: int(ok.sum())].view(np.uint64), q[ok == 1].view(np.uint64))
     pr = g["probe"]
     assert pr["samples"] == 4096 and pr["bit_identical_to_one_gpu"] is True and sum(pr["valid_per_rank"]) == pr["valid_states"] > 500
     # the other multi-GPU form of SURVEY.md section 8(e), in the same line: ONE process driving the GPUs through the C ABI's sharded

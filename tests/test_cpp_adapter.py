@@ -236,7 +236,6 @@ def test_part2_control_flow_matches_oracle(ccmp_built, oracle_det):
 # ---- the drop-in recipe of INTEGRATION.md section 2, compiled: both replacement headers, two translation units --------------
 OVERLAY = os.path.join(ROOT, "include", "reference_overlay")
 DROPIN_EXE = os.path.join(ROOT, "tests", "cpp", "dropin_check")
-REFERENCE = "/root/reference"
 
 
 def _build_dropin(ccmp_built, tmp):
@@ -275,37 +274,62 @@ def test_dropin_headers_compile_in_two_translation_units_and_link(ccmp_built, tm
         assert "#include <ccmp_ompl_adapter.hpp>" in code and "class " not in code  # no class body left behind
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference checkout is not on this box")
-def test_overlay_matches_the_reference_it_replaces(tmp_path):
-    """With the reference at hand: (1) CMakeLists.diff applies to its CMakeLists.txt and takes jy_ProjectedStateSpace.cpp out
-    of SOURCES; (2) each replacement header keeps every #include and the namespace / using line of the header it replaces —
-    what the reference's other sources get through them; (3) the classes the adapter defines are exactly those the two
-    original headers define, and the dropped source file defines members of no other class."""
-    import shutil
-
-    cm = tmp_path / "CMakeLists.txt"
-    shutil.copy(os.path.join(REFERENCE, "CMakeLists.txt"), cm)
-    subprocess.run(["patch", "-s", "-p1", str(cm)], stdin=open(os.path.join(OVERLAY, "CMakeLists.diff")), check=True, cwd=tmp_path)
-    patched = cm.read_text()
-    assert "src/base/jy_ProjectedStateSpace.cpp" not in patched and "${CCMP_LIB}" in patched and "CCMP_ROOT}/include" in patched
+def _hunks(diff_text):
+    """[(old start line, old-side lines, new-side lines)] of the hunks of a unified diff"""
     import re
 
+    hunks = []
+    for ln in diff_text.split("\n"):
+        m = re.match(r"@@ -(\d+)(?:,\d+)? \+\d+(?:,\d+)? @@", ln)
+        if m:
+            hunks.append((int(m.group(1)), [], []))
+        elif hunks and ln[:1] in (" ", "-", "+"):
+            if ln[0] != "+":
+                hunks[-1][1].append(ln[1:])
+            if ln[0] != "-":
+                hunks[-1][2].append(ln[1:])
+    return hunks
+
+
+def test_overlay_matches_the_reference_it_replaces():
+    """Against what tests/golden/overlay_facts.json records of the reference (tests/golden/make_overlay_facts.py): (1)
+    CMakeLists.diff applies to its CMakeLists.txt — every hunk's old side is those very lines at those very places — and takes
+    jy_ProjectedStateSpace.cpp out of SOURCES; (2) each replacement header keeps every #include and the namespace / using line
+    of the header it replaces — what the reference's other sources get through them; (3) the classes the adapter defines are
+    exactly those the two original headers define, and the dropped source file defines members of no other class."""
+    import hashlib
+    import json
+    import re
+
+    facts = json.load(open(os.path.join(ROOT, "tests", "golden", "overlay_facts.json")))
+    cm = facts["cmakelists"]
+    hunks = _hunks(open(os.path.join(OVERLAY, "CMakeLists.diff")).read())
+    assert len(hunks) == 3
+    removed = set()
+    for start, old, new in hunks:
+        assert start + len(old) - 1 <= cm["lines"], (start, len(old))
+        assert [hashlib.sha256(ln.encode()).hexdigest() for ln in old] == cm["line_sha256"][start - 1: start - 1 + len(old)], start
+        removed |= {start + k for k, ln in enumerate(old) if ln not in new}
+    added = [ln for _, old, new in hunks for ln in new if ln not in old]
+    assert cm["lines_naming_dropped_source"] and set(cm["lines_naming_dropped_source"]) <= removed
+    assert not any("src/base/jy_ProjectedStateSpace.cpp" in ln for ln in added)
+    assert any("${CCMP_LIB}" in ln for ln in added) and any("CCMP_ROOT}/include" in ln for ln in added)
     inc = re.compile(r'^\s*#\s*include\s*[<"]([^>"]+)[>"]', re.M)
+    originals = set()
     for hdr, keep in (("closed_chain_motion_planner/base/constraints/ConstraintFunction.h", "using namespace std;"),
                       ("closed_chain_motion_planner/base/jy_ProjectedStateSpace.h", "namespace ob = ompl::base;")):
-        orig = open(os.path.join(REFERENCE, "include", hdr)).read()
+        orig = facts["headers"][hdr]
         ours = open(os.path.join(OVERLAY, hdr)).read()
-        assert set(inc.findall(orig)) <= set(inc.findall(ours)), (hdr, set(inc.findall(orig)) - set(inc.findall(ours)))
-        assert keep in orig and keep in ours
+        assert set(orig["includes"]) <= set(inc.findall(ours)), (hdr, set(orig["includes"]) - set(inc.findall(ours)))
+        assert orig["keep"] == keep and orig["has_keep"] and keep in ours
+        originals |= set(orig["classes"])
+    assert {"KinematicChainConstraint", "jy_ProjectedStateSampler", "jy_ProjectedStateSpace"} <= originals
     cls = re.compile(r"^\s*class\s+(\w+)\s*:", re.M)
-    originals = set()
-    for hdr in ("closed_chain_motion_planner/base/constraints/ConstraintFunction.h", "closed_chain_motion_planner/base/jy_ProjectedStateSpace.h"):
-        originals |= set(cls.findall(open(os.path.join(REFERENCE, "include", hdr)).read()))
     adapter = open(os.path.join(ROOT, "include", "ccmp_ompl_adapter.hpp")).read()
     part2 = adapter[adapter.index("#ifdef CCMP_WITH_OMPL"):]
     assert originals <= set(cls.findall(part2)), originals - set(cls.findall(part2))
-    members = set(re.findall(r"^\w[\w:<> \*&]*?\b(\w+)::\w+\(", open(os.path.join(REFERENCE, "src", "base", "jy_ProjectedStateSpace.cpp")).read(), re.M))
-    assert members <= {"jy_ProjectedStateSampler", "jy_ProjectedStateSpace"}, members
+    members = set(facts["dropped_source"]["member_classes"])
+    assert members and members <= {"jy_ProjectedStateSampler", "jy_ProjectedStateSpace"}, members
 
 
 @pytest.mark.gpu
