@@ -77,7 +77,7 @@ EXPORTS = [
 
 _lib = None
 # include/ccmp_debug.h: exported by lib/libccmp_debug.so only (the same sources with -DCCMP_DEBUG_HOOKS; select it with CCMP_LIBRARY)
-DEBUG_EXPORTS = ["ccmp_detmath_probe", "ccmp_ctx_set_order_experimental", "ccmp_ctx_debug_lpt_pred", "ccmp_debug_fail_calls"]
+DEBUG_EXPORTS = ["ccmp_detmath_probe", "ccmp_detmath_div_probe", "ccmp_ctx_set_order_experimental", "ccmp_ctx_debug_lpt_pred", "ccmp_debug_fail_calls"]
 DEBUG_LIBPATH = os.path.join(os.path.dirname(LIBPATH), "libccmp_debug.so")
 
 
@@ -176,6 +176,7 @@ def lib():
         "ccmp_ctx_set_order_experimental": ([vp, vp], C.c_int),
         "ccmp_ctx_debug_lpt_pred": ([vp, vp, C.c_size_t], C.c_int),
         "ccmp_detmath_probe": ([vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
+        "ccmp_detmath_div_probe": ([vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
         "ccmp_debug_fail_calls": ([vp, C.c_int], C.c_int),
     }
     for name, (args, res) in debug_sig.items():  # present in the debug build only (include/ccmp_debug.h)

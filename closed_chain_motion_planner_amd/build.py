@@ -32,7 +32,7 @@ LIBPATH = os.environ.get("CCMP_LIBRARY") or os.path.join(LIBDIR, "libccmp.so")
 # the same sources with the test / tool hooks of include/ccmp_debug.h (-DCCMP_DEBUG_HOOKS on the two host units that carry them)
 DEBUG_LIBPATH = os.path.join(LIBDIR, "libccmp_debug.so")
 _DEBUG_UNITS = ("ccmp_api.cpp", "ccmp_policy.cpp")
-_DEBUG_ONLY_UNITS = [("ccmp_kernels_debug.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-mllvm", "-disable-machine-licm"])]  # the device probe of ccmp_detmath.h
+_DEBUG_ONLY_UNITS = [("ccmp_kernels_debug.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-DCCMP_LEAN_DIV", "-mllvm", "-disable-machine-licm"])]  # the device probe of ccmp_detmath.h
 ARCH = "gfx950"
 
 _UNITS = [
@@ -41,7 +41,11 @@ _UNITS = [
     # throughput kernel needed 133 VGPRs and no scratch (measured +3.3 %, in-process A/B; today's kernel: 167, no scratch,
     # three wavefronts per SIMD).  The wave kernels are
     # 2.7 % slower with the option, hence their own unit.
-    ("ccmp_kernels_fd.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+    # the residual's tail (DESIGN_experiments.md §5.6, in-process A/B each): CCMP_ATAN_UNIFORM atan's first interval without its
+    # division when the whole wavefront is in it (-2.0 %), CCMP_FD_TI_HOIST arm 1's term of the residual once per round (-0.4 %);
+    # CCMP_LEAN_DIV (quotients without scaling and fixup) measured +1.0 % here and stays off
+    ("ccmp_kernels_fd.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-DCCMP_ATAN_UNIFORM", "-DCCMP_FD_TI_HOIST",
+                             "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
      + os.environ.get("CCMP_FD_EXTRA_FLAGS", "").split()),
     ("ccmp_kernels_wave.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA"]),
     # max-ilp scheduling: -0.6 % (throughput kernel) ... -1.5 % (latency kernel, single state), in-process A/B

@@ -98,6 +98,7 @@ hipError_t ccmp_launch_geodesic_scout_order(const ccmp_consts *K, const double *
                                             int max_states, int round_cap, uint16_t *pred, unsigned int *hist, unsigned int *order, int pairs,
                                             const ccmp_split_req *split, hipStream_t st);
 hipError_t ccmp_launch_detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
+hipError_t ccmp_launch_div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);
 hipError_t ccmp_launch_compact(const double *q, const uint8_t *ok, size_t B, double *out, size_t capacity,
                                unsigned int *block_counts, unsigned long long *total, hipStream_t st);
 }
@@ -787,6 +788,17 @@ int ccmp_detmath_probe(ccmp_ctx *ctx, const double *x_dev, const double *y_dev, 
   hipStream_t st = (hipStream_t)hip_stream;
   if (n == 0) return CCMP_OK;
   HIP_TRY(ccmp_launch_detmath_probe(x_dev, y_dev, out_dev, n, st));
+  return CCMP_OK;
+}
+
+int ccmp_detmath_div_probe(ccmp_ctx *ctx, const double *n_dev, const double *d_dev, double *out_dev, size_t count, void *hip_stream)
+{
+  if (!ctx || !n_dev || !d_dev || !out_dev) return CCMP_EINVAL;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (count == 0) return CCMP_OK;
+  HIP_TRY(ccmp_launch_div_probe(n_dev, d_dev, out_dev, count, st));
   return CCMP_OK;
 }
 #endif

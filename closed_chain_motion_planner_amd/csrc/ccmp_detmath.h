@@ -83,6 +83,42 @@ static __device__ __forceinline__ double ccmp_sqrt(double x)
 #else
 CCMP_HD double ccmp_sqrt(double x) { return __builtin_sqrt(x); }
 #endif
+
+/* IEEE correctly rounded quotient on both sides.  On gfx950 the compiler expands n / d into v_div_scale (x2), v_rcp_f64, four
+ * fused steps, a multiply, v_div_fmas and v_div_fixup.  The scalings of v_div_scale act only when an operand, the reciprocal or
+ * the quotient is near the ends of the exponent range (or an operand is zero), v_div_fmas without a scaling is a plain FMA, and
+ * v_div_fixup returns its input unless an operand is zero, infinite or NaN or the quotient leaves the range.  With both
+ * operands in 2^-300 <= |v| < 2^300 none of this happens: ccmp_div_steps runs the remaining operations on the same values, hence
+ * the same bits.  CCMP_LEAN_DIV: ccmp_div_lean takes that sequence when every lane of the wavefront qualifies (wave-uniform test),
+ * the compiler's expansion otherwise; without it (and on the host) both are n / d. */
+#if defined(__HIP_DEVICE_COMPILE__) && defined(CCMP_LEAN_DIV) && defined(CCMP_USE_FMA)
+static __device__ __forceinline__ double ccmp_div_steps(double n, double d)
+{
+  const double r0 = __builtin_amdgcn_rcp(d);
+  const double e0 = CCMP_FMA(-d, r0, 1.0);
+  const double r1 = CCMP_FMA(r0, e0, r0);
+  const double e1 = CCMP_FMA(-d, r1, 1.0);
+  const double r2 = CCMP_FMA(r1, e1, r1);
+  const double m = n * r2;
+  const double rem = CCMP_FMA(-d, m, n);
+  return CCMP_FMA(rem, r2, m);
+}
+static __device__ __forceinline__ bool ccmp_div_operand_plain(double v)
+{
+  /* 2^-300 <= |v| < 2^300  <=>  0x2d300000 <= high dword without its sign < 0x52b00000 */
+  const unsigned hi = (unsigned)__double2hiint(v) & 0x7fffffffu;
+  return (hi - 0x2d300000u) < (0x52b00000u - 0x2d300000u);
+}
+static __device__ __forceinline__ double ccmp_div_lean(double n, double d)
+{
+  if (__builtin_amdgcn_ballot_w64(!(ccmp_div_operand_plain(n) && ccmp_div_operand_plain(d))) == 0ull) return ccmp_div_steps(n, d);
+  return n / d;
+}
+#else
+CCMP_HD double ccmp_div_steps(double n, double d) { return n / d; }
+CCMP_HD double ccmp_div_lean(double n, double d) { return n / d; }
+#endif
+
 CCMP_HD double ccmp_abs(double x) { return __builtin_fabs(x); }
 
 /* sin(x+y) and cos(x+y), |x| <= pi/4 (+ a hair), y the tail of the reduced argument. */
@@ -174,6 +210,28 @@ CCMP_HD double ccmp_atan(double x)
                a6 = CCMP_K(30, 6.66107313738753120669e-02), a7 = CCMP_K(31, -5.83357013379057348645e-02),
                a8 = CCMP_K(32, 4.97687799461593236017e-02), a9 = CCMP_K(33, -3.65315727442169155270e-02),
                a10 = CCMP_K(34, 1.62858201153657823623e-02);
+#if defined(__HIP_DEVICE_COMPILE__) && defined(CCMP_ATAN_UNIFORM)
+  /* every lane of the wavefront in the first interval (|x| < 7/16: the residual's angular error under ~47 degrees): the
+   * quotient below would be |x| / 1.0 = |x| exactly — no division, no interval selects (wave-uniform test; NaN fails it) */
+  if (__builtin_amdgcn_ballot_w64(!(ccmp_abs(x) < 0.4375)) == 0ull) {
+    const double t = ccmp_abs(x);
+    double z = t * t;
+    double w = z * z;
+    double s1 = CCMP_FMA(w, a10, a8);
+    s1 = CCMP_FMA(w, s1, a6);
+    s1 = CCMP_FMA(w, s1, a4);
+    s1 = CCMP_FMA(w, s1, a2);
+    s1 = CCMP_FMA(w, s1, a0);
+    s1 = z * s1;
+    double s2 = CCMP_FMA(w, a9, a7);
+    s2 = CCMP_FMA(w, s2, a5);
+    s2 = CCMP_FMA(w, s2, a3);
+    s2 = CCMP_FMA(w, s2, a1);
+    s2 = w * s2;
+    const double res = CCMP_FMA(-t, s1 + s2, t);
+    return x < 0.0 ? -res : res;
+  }
+#endif
   int neg = x < 0.0;
   double ax = ccmp_abs(x);
   if (ax >= 7.378697629483821e19) { /* 2^66: atan saturates (also catches +-inf) */
@@ -194,7 +252,7 @@ CCMP_HD double ccmp_atan(double x)
   } else { /* also the NaN path: every comparison above is false */
     num = -1.0; den = ax; hi = hi3; lo = lo3;
   }
-  double t = num / den;
+  double t = ccmp_div_lean(num, den);
   double z = t * t;
   double w = z * z;
   double s1 = CCMP_FMA(w, a10, a8);
@@ -263,7 +321,7 @@ CCMP_HD void ccmp_fill_ktab(double *t)
 CCMP_HD double ccmp_atan2_nn(double y, double x)
 {
   if (x == 0.0 && y == 0.0) return 0.0;
-  return ccmp_atan(y / x); /* x == 0 < y gives +inf -> pi/2 */
+  return ccmp_atan(ccmp_div_lean(y, x)); /* x == 0 < y gives +inf -> pi/2 */
 }
 
 /* Natural logarithm for finite normal x > 0 (the only use: Box-Muller on u in (0,1]).  fdlibm scheme:

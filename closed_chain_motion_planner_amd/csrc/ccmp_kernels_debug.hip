@@ -20,10 +20,27 @@ __global__ void detmath_probe_kernel(const double *__restrict__ x, const double 
   out[5 * i + 4] = x[i] / y[i];
 }
 
+// ccmp_div_lean's two paths (the unit is built with -DCCMP_LEAN_DIV): the lean sequence forced on every lane, the wave-uniform
+// choice, and the compiler's division
+__global__ void div_probe_kernel(const double *__restrict__ num, const double *__restrict__ den, double *__restrict__ out, size_t n)
+{
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[3 * i + 0] = ccmp_div_steps(num[i], den[i]);
+  out[3 * i + 1] = ccmp_div_lean(num[i], den[i]);
+  out[3 * i + 2] = num[i] / den[i];
+}
+
 } // namespace
 
 extern "C" hipError_t ccmp_launch_detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st)
 {
   hipLaunchKernelGGL(detmath_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, out, n);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ccmp_launch_div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st)
+{
+  hipLaunchKernelGGL(div_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, num, den, out, n);
   return hipGetLastError();
 }

@@ -205,6 +205,15 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
   double To[12]; // the other arm's (unperturbed) tool pose: 24 VGPRs that save 12 LDS reads per column (-6.5 %, A/B)
 #pragma unroll
   for (int k = 0; k < 12; k++) To[k] = rec[kEE + (1 - ARM) * 12 + k];
+#ifdef CCMP_FD_TI_HOIST
+  // arm 0's columns: chain_residual's ti = R2^T p2 is arm 1's alone — once here, in place of p2 (no register added)
+  if (ARM == 0) {
+    double ti[3];
+    mulTvec(&To[0], &To[9], ti);
+#pragma unroll
+    for (int k = 0; k < 3; k++) To[9 + k] = ti[k];
+  }
+#endif
   for (int j = 0; j < 7; j++) {
     const double xj = rec[kX + ARM * 7 + j];
     const double axj = ccmp_abs(xj);
@@ -305,7 +314,11 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
 #endif
     double Tw[12], t[2];
     tool_pose_t<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
+#ifdef CCMP_FD_TI_HOIST
+    if (ARM == 0) chain_residual_ti(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
+#else
     if (ARM == 0) chain_residual(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
+#endif
     else chain_residual(K, &To[0], &To[9], &Tw[0], &Tw[9], t, nullptr, nullptr);
     // park this evaluation in the prefix slot the group has just consumed (12 doubles = 6 lanes x (f0, f1));
     // the stencil is combined after the arm's 7 columns (stencil_combine) instead of through two dependent

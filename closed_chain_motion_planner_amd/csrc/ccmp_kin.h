@@ -231,6 +231,7 @@ CCMP_HD void fk_arm(const ccmp_consts &K, int arm, const double *q, double *Rw, 
  * differences/sums are scaled by 0.5/sqrt, so the operands are selected and sqrt/divide run once.
  * Every output is produced by the same operation on the same operands as in the branchy form below
  * (bit-identical; in-process A/B on MI355X, tools/ab.py: 1.4 % faster than the branchy form). */
+
 CCMP_HD void quat_of(const double *m, double *q)
 {
   const double tr = (m[0] + m[4]) + m[8];
@@ -245,7 +246,7 @@ CCMP_HD void quat_of(const double *m, double *q)
   const double arg = kase == 3 ? a3 : (kase == 0 ? a0 : (kase == 1 ? a1 : a2));
   const double t = ccmp_sqrt(arg);
   const double h = 0.5 * t;
-  const double k = 0.5 / t;
+  const double k = ccmp_div_lean(0.5, t);
   const double d1 = (m[7] - m[5]) * k, d2 = (m[2] - m[6]) * k, d3 = (m[3] - m[1]) * k;
   const double s1 = (m[3] + m[1]) * k, s2 = (m[6] + m[2]) * k, s3 = (m[7] + m[5]) * k;
   q[0] = kase == 3 ? d1 : (kase == 0 ? h : (kase == 1 ? s1 : s2));
@@ -298,13 +299,16 @@ CCMP_HD void quat_of(const double *m, double *q)
 
 /* current_chain = t_w72.inverse() * t_w71, then (|dp|, angularDistance) against init_chain_
  * (ConstraintFunction.h:92-101).  dq (nullable) receives q_c * conj(q_0) as (x,y,z,w) and pc
- * (nullable) the chain translation — the analytic Jacobian needs both. */
-CCMP_HD void chain_residual(const ccmp_consts &K, const double *R1, const double *p1, const double *R2,
-                            const double *p2, double *f, double *dq, double *pc_out)
+ * (nullable) the chain translation — the analytic Jacobian needs both.  chain_residual_ti takes ti = R2^T p2 from the caller
+ * (a term of arm 1 alone: arm 0's Jacobian columns compute it once per round instead of once per stencil point). */
+template <bool TI>
+CCMP_HD void chain_residual_t(const ccmp_consts &K, const double *R1, const double *p1, const double *R2,
+                              const double *p2_or_ti, double *f, double *dq, double *pc_out)
 {
   double Rc[9], ti[3], pc[3], qc[4];
   mulT33(R2, R1, Rc);
-  mulTvec(R2, p2, ti);
+  if (TI) { ti[0] = p2_or_ti[0]; ti[1] = p2_or_ti[1]; ti[2] = p2_or_ti[2]; }
+  else mulTvec(R2, p2_or_ti, ti);
   mulTvec(R2, p1, pc);
 #pragma unroll
   for (int k = 0; k < 3; k++) pc[k] = pc[k] + (-ti[k]);
@@ -321,6 +325,16 @@ CCMP_HD void chain_residual(const ccmp_consts &K, const double *R1, const double
   f[0] = ccmp_sqrt(dot3(e0, e0, e1, e1, e2, e2));
   if (dq) { dq[0] = dx; dq[1] = dy; dq[2] = dz; dq[3] = dw; }
   if (pc_out) { pc_out[0] = pc[0]; pc_out[1] = pc[1]; pc_out[2] = pc[2]; }
+}
+CCMP_HD void chain_residual(const ccmp_consts &K, const double *R1, const double *p1, const double *R2,
+                            const double *p2, double *f, double *dq, double *pc_out)
+{
+  chain_residual_t<false>(K, R1, p1, R2, p2, f, dq, pc_out);
+}
+CCMP_HD void chain_residual_ti(const ccmp_consts &K, const double *R1, const double *p1, const double *R2,
+                               const double *ti, double *f, double *dq, double *pc_out)
+{
+  chain_residual_t<true>(K, R1, p1, R2, ti, f, dq, pc_out);
 }
 
 /* KinematicChainConstraint::function for one state. */

@@ -18,6 +18,10 @@ extern "C" {
 /* runs ccmp_detmath.h's sincos / atan2 / sqrt / div on the device: out[i] = {sin, cos, atan2_nn(|x|, |y|), sqrt(|x|), x / y} —
  * how the tests prove the device arithmetic bit-identical to the host's */
 int ccmp_detmath_probe(ccmp_ctx *ctx, const double *x_dev, const double *y_dev, double *out_dev, size_t n, void *hip_stream);
+/* the quotient n / d three ways on the device: out[i] = {ccmp_div_steps (the lean sequence, forced), ccmp_div_lean (wave-uniform
+ * choice), the compiler's n / d} — the lean sequence must equal n / d wherever both operands are in 2^-300 <= |v| < 2^300, and
+ * ccmp_div_lean everywhere */
+int ccmp_detmath_div_probe(ccmp_ctx *ctx, const double *n_dev, const double *d_dev, double *out_dev, size_t count, void *hip_stream);
 /* an externally supplied processing order for the reference-arithmetic projector (device array of B sample indices, NULL = none) */
 int ccmp_ctx_set_order_experimental(ccmp_ctx *ctx, const unsigned int *order_dev);
 /* a copy of the FP32 scout's predicted iteration counts of the last call that ran one */
