@@ -190,7 +190,7 @@ def lib():
     return L
 
 
-CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GEODESIC_BUDGET = range(5)  # ccmp.h: CCMP_CALL_*
+CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GEODESIC_BUDGET, CALL_GEODESIC_ANALYTIC = range(6)  # ccmp.h: CCMP_CALL_*
 
 
 def option_table():

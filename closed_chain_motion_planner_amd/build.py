@@ -15,7 +15,7 @@ Translation units with deliberately different flags:
   ccmp_kernels_resident.hip -ffp-contract=off -DCCMP_USE_FMA  ... its device side, on the latency flavour's Newton routine
   ccmp_host_io.cpp                                          *_host conveniences (staging, pinned block, page-locked caller buffers), sharded host calls
   ccmp_comm.cpp                                             one process / several GPUs: RCCL communicator and sharded entry points
-  ccmp_kernels_fast.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   analytic fast mode (one sample per lane pair), bit-identical to the oracle's analytic mode
+  ccmp_kernels_fast.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   analytic fast mode (lane-pair and row16 projectors, the row16 extend step), bit-identical to the oracle's analytic mode
   ccmp_kernels_scout.hip -ffast-math                        FP32 iteration-count predictor + ordering (never touches results)
   ccmp_kernels_scene.hip -ffp-contract=off -DCCMP_USE_FMA   proxy-geometry clearance (pre-filter ahead of the host's MoveIt test)
   ccmp_scene.cpp                                            proxy scenes: validation, pair list, launches
@@ -111,6 +111,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_group_kernel|resident_service_kernel)<(\d+, )?true>", 0),
     (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_group_kernel|resident_service_kernel)<(\d+, )?false>", 136),
     (r"project_pair_kernel|project_row16_kernel", 0),  # analytic mode, every instantiation (stock twin arms, stock, calibrated)
+    (r"geodesic_row16_kernel", 0),  # analytic mode's extend step, both instantiations (diagonal and general base frames)
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

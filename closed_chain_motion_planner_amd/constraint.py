@@ -62,7 +62,7 @@ class Context:
 
     def describe(self, call_kind, n):
         """ccmp_ctx_describe: which kernels and thresholds the policy takes for a call of n samples / edges (call_kind:
-        _lib.CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GEODESIC_BUDGET)"""
+        _lib.CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GEODESIC_BUDGET, CALL_GEODESIC_ANALYTIC)"""
         return _lib.describe(self._h, call_kind, n)
 
     def set_lpt(self, mode=1, min_batch=None):

@@ -52,7 +52,8 @@ constexpr size_t kGeoGroupLateHandoverFrom = 32768; // bulk extend calls: the gr
 constexpr size_t kGeoGroupHigherCut = 65536;        // ... and 56 from here on (profiles/r05_low_cut_sweep.log: 65 536 edges -1.7 %, 131 072 -2.1 % against 48)
 constexpr int kGeoPoolDoubles = 40;                // = kGeoPoolEntry (ccmp_fd_common.h): one handed-over edge of the extend step's bulk form
 constexpr int kAnalyticWords = 64 + 2;            // ctx->queue + 8: 64 ticket words of the analytic mode's lane-pair kernel, the hand-over pool's fill count, the latency kernel's ticket word
-constexpr int kGeoGroupWords = 8 + kAnalyticWords + 1; // ctx->queue: first of the 8 words of the extend step's bulk form (behind the analytic kernel's)
+constexpr int kGeoAnalyticWord = 8 + kAnalyticWords;  // ctx->queue: the ticket word of the extend step in analytic mode (geodesic_row16_kernel)
+constexpr int kGeoGroupWords = kGeoAnalyticWord + 1;  // ctx->queue: first of the 8 words of the extend step's bulk form (behind the analytic kernels')
 constexpr size_t kDefaultLatencyOrderMin = 2049;   // latency kernel alone: FP32 scout order as soon as the blocks take tickets (more samples than blocks)
 constexpr size_t kDefaultLptMinBatch = 16384;      // throughput kernel: the scout's order pays from here on
 constexpr size_t kOccupancyHandoverBelow = 53248;  // below: the throughput kernel hands over by occupancy, from here on at once
@@ -75,8 +76,6 @@ struct ccmp_ctx {
   size_t lpt_cap = 0;                  // in samples
   double *geo_pool = nullptr;          // bulk extend hand-over: kGeoPoolDoubles per edge
   size_t geo_pool_cap = 0;
-  void *geo_an = nullptr;              // the analytic-mode extend step's per-edge state (ccmp_kernels_fast.hip: geo_an_ws) + target flags
-  size_t geo_an_cap = 0;               // in edges
   unsigned int *scan = nullptr;        // compaction block counts
   size_t scan_cap = 0;
   void *stage = nullptr;               // device staging of the *_host conveniences

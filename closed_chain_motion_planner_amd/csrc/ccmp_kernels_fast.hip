@@ -20,8 +20,9 @@
 // Lanes whose sample is done are refilled from ticket queues while their neighbours keep iterating (iteration counts
 // spread 15..250); when the queues are dry a wavefront that is mostly empty hands its live samples over (x, index,
 // counters, at the loop top) to a pool that the LATENCY kernel below — sixteen lanes per sample, 2.7 us per Newton round
-// where this layout needs 4 — finishes; that kernel also takes small batches alone.  The extend step in this mode is a step
-// loop around these projectors (end of the file).
+// where this layout needs 4 — finishes; that kernel also takes small batches alone.  The extend step in this mode is a traversal
+// kernel on the latency kernel's layout and Newton round (geodesic_row16_kernel, end of the file): one launch per call, four edges
+// per wavefront, the round budget, carry-in / carry-out and isSatisfied(to) inside.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -464,77 +465,7 @@ __global__ __launch_bounds__(64, 2) void project_row16_kernel(const ccmp_consts 
     }
     if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
 
-    // ---- function(x).  Joint lanes: sine, cosine, joint rotation (lanes 14, 15 shadow lane 13: same values, same words) ------
-    {
-      double s, c, Rj[9];
-      ccmp_sincos(x, &s, &c);
-      rot_sc(ax, ap, s, c, Rj);
-#pragma unroll
-      for (int k = 0; k < 9; k++) rec[qRJ + 9 * lj + k] = Rj[k];
-    }
-    // ---- chain lanes: one row of the arm's frame through the seven joints, then one row of the hand pose ---------------------
-    {
-      double R0 = rc == 0 ? 1.0 : 0.0, R1 = rc == 1 ? 1.0 : 0.0, R2 = rc == 2 ? 1.0 : 0.0, o = 0.0;
-      // the arm's joint rotations in two batches (four joints, then three): two LDS latencies instead of seven
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        constexpr int kFirst[2] = {0, 4}, kCount[2] = {4, 3};
-        double Rj[4][9];
-#pragma unroll
-        for (int i = 0; i < kCount[h]; i++)
-#pragma unroll
-          for (int k = 0; k < 9; k++) Rj[i][k] = rec[qRJ + 9 * (ac * 7 + kFirst[h] + i) + k];
-#pragma unroll
-        for (int ii = 0; ii < kCount[h]; ii++) {
-          const int i = kFirst[h] + ii;
-          const double *off = K.offset[ac][i], *a = K.axis[ac][i];
-          o = dot3acc(o, R0, off[0], R1, off[1], R2, off[2]);
-          const double zr = dot3(R0, a[0], R1, a[1], R2, a[2]);
-          rec[qZO + (ac * 7 + i) * 6 + rc] = zr;
-          rec[qZO + (ac * 7 + i) * 6 + 3 + rc] = o;
-          const double n0 = dot3(R0, Rj[ii][0], R1, Rj[ii][3], R2, Rj[ii][6]);
-          const double n1 = dot3(R0, Rj[ii][1], R1, Rj[ii][4], R2, Rj[ii][7]);
-          const double n2 = dot3(R0, Rj[ii][2], R1, Rj[ii][5], R2, Rj[ii][8]);
-          R0 = n0; R1 = n1; R2 = n2;
-        }
-      }
-      // the hand frame in the arm's base frame (getTranslation / getRotation), one row
-      const double pf = dot3acc(o, R0, cee[0], R1, cee[1], R2, cee[2]);
-      const double f0 = dot3(R0, cRt[0], R1, cRt[3], R2, cRt[6]);
-      const double f1 = dot3(R0, cRt[1], R1, cRt[4], R2, cRt[7]);
-      const double f2 = dot3(R0, cRt[2], R1, cRt[5], R2, cRt[8]);
-      double *T = rec + qT + 12 * ac;
-      if (DIAG) { // t_wb * T with t_wb.linear() = diag(d): d_r * Rf[r][c], fma(d_r, pf[r], base_p[r]) (the general product adds exact zeros)
-        T[3 * rc] = cd * f0;
-        T[3 * rc + 1] = cd * f1;
-        T[3 * rc + 2] = cd * f2;
-        T[9 + rc] = CCMP_FMA(cd, pf, cbp);
-      } else {
-        T[3 * rc] = f0;
-        T[3 * rc + 1] = f1;
-        T[3 * rc + 2] = f2;
-        T[9 + rc] = pf;
-      }
-    }
-    // ---- all lanes: the two world poses, the residual, the loop condition ------------------------------------------------------
-    double T0[12], T1[12], f[2], dq[4], pc[3];
-    if (DIAG) {
-#pragma unroll
-      for (int k = 0; k < 12; k++) { T0[k] = rec[qT + k]; T1[k] = rec[qT + 12 + k]; }
-    } else {
-#pragma unroll
-      for (int arm = 0; arm < 2; arm++) {
-        double Rf[9], pf[3], *Tw = arm ? T1 : T0;
-#pragma unroll
-        for (int k = 0; k < 9; k++) Rf[k] = rec[qT + 12 * arm + k];
-#pragma unroll
-        for (int k = 0; k < 3; k++) pf[k] = rec[qT + 12 * arm + 9 + k];
-        mul33(K.base_R[arm], Rf, Tw);
-        Tw[9] = K.base_p[arm][0]; Tw[10] = K.base_p[arm][1]; Tw[11] = K.base_p[arm][2];
-        mulvec_acc(K.base_R[arm], pf, Tw + 9);
-      }
-    }
-    chain_residual(K, &T0[0], &T0[9], &T1[0], &T1[9], f, dq, pc);
+#include "ccmp_row16_eval.inc"
     bool cont = false;
     if (active) { // ConstraintFunction.h:68, quirks included; the sixteen lanes of a row decide alike
       const bool c1 = f[0] > K.tol_pos;
@@ -560,203 +491,213 @@ __global__ __launch_bounds__(64, 2) void project_row16_kernel(const ccmp_consts 
       if (fin) active = false;
     }
     if (__builtin_amdgcn_ballot_w64(cont) == 0ull) continue;
-    // ---- analytic Jacobian: probes (every lane, its joint's arm), then this lane's column --------------------------------------
-    double J0, J1;
-    {
-      double u[3] = {0, 0, 0}, n[3] = {0, 0, 0}, aw[3], bw[3];
-      if (f[0] > 0.0) {
-        const double inv = 1.0 / f[0];
-#pragma unroll
-        for (int k = 0; k < 3; k++) u[k] = (pc[k] - K.init_p[k]) * inv;
-      }
-      const double vn = ccmp_sqrt(dot3(dq[0], dq[0], dq[1], dq[1], dq[2], dq[2]));
-      if (vn > 0.0) {
-        const double sg = (dq[3] < 0.0 ? -1.0 : 1.0) / vn;
-#pragma unroll
-        for (int k = 0; k < 3; k++) n[k] = dq[k] * sg;
-      }
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        aw[k] = dot3(T1[3 * k], u[0], T1[3 * k + 1], u[1], T1[3 * k + 2], u[2]);
-        bw[k] = dot3(T1[3 * k], n[0], T1[3 * k + 1], n[1], T1[3 * k + 2], n[2]);
-      }
-      double al[3], bl[3], pl[3], dp[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) dp[k] = T0[9 + k] - K.base_p[aj][k];
-      mulTvec(K.base_R[aj], aw, al);
-      mulTvec(K.base_R[aj], bw, bl);
-      mulTvec(K.base_R[aj], dp, pl);
-      const double *zo = rec + qZO + 6 * lj;
-      const double z0 = zo[0], z1 = zo[1], z2 = zo[2];
-      const double r0 = pl[0] - zo[3], r1 = pl[1] - zo[4], r2 = pl[2] - zo[5];
-      const double cx = CCMP_FMA(z1, r2, -(z2 * r1));
-      const double cy = CCMP_FMA(z2, r0, -(z0 * r2));
-      const double cz = CCMP_FMA(z0, r1, -(z1 * r0));
-      J0 = sgn * dot3(al[0], cx, al[1], cy, al[2], cz);
-      J1 = sgn * dot3(bl[0], z0, bl[1], z1, bl[2], z2);
-      rec[qJ + lj] = J0;
-      rec[qJ + 14 + lj] = J1;
-    }
-    // ---- Newton update on the Gram matrix (orc_solve_gram): every lane the three sums, its own component of the step ----------
-    {
-      double Jr[28], a, d, b, y0, y1;
-#pragma unroll
-      for (int k = 0; k < 28; k++) Jr[k] = rec[qJ + k];
-      gram_sums(Jr, a, d, b);
-      const bool well = gram_coeffs(a, d, b, f[0], f[1], y0, y1);
-      double dx = CCMP_FMA(y1, J1, y0 * J0);
-      if (__builtin_amdgcn_ballot_w64(cont && !well) != 0ull) { // nearly parallel rows (or a NaN): the SVD-equivalent solve, through LDS
-        double dxf[14];
-        solve_minnorm(Jr, f[0], f[1], dxf);
-        if (l == 0) {
-#pragma unroll
-          for (int k = 0; k < 14; k++) rec[qDX + k] = dxf[k];
-        }
-        const double own = rec[qDX + lj];
-        if (!well) dx = own;
-      }
-      if (cont) {
-        x = CCMP_FMA(-K.step, dx, x);
-        updates++;
-      }
-    }
+#include "ccmp_row16_step.inc"
   }
 }
 
 
 // ------------------------------------------------------------------------------------------------------------------------
-// The extend step in analytic mode (round 6): jy_ProjectedStateSpace::discreteGeodesic (src/base/jy_ProjectedStateSpace.cpp:32-96)
-// as a STEP LOOP around the batched projector — per step one launch that writes every live edge's interpolated state, the
-// analytic-mode projection of all of them (the kernels above, whatever the policy picks for E states), one launch that does
-// the reference's bookkeeping between two projections (the four break tests, the state list, the running lengths) — instead
-// of a traversal kernel of its own.  max_states steps at most (an edge appends one state per step), no host synchronisation:
-// an edge that has ended projects a state that is already on the manifold (the problem's start_joint: zero iterations).
-// Operation for operation oracle/ccmp_oracle.c: orc_discrete_geodesic_ex with interpolate = true (the host truncates the list
-// at the first state its StateValidityChecker rejects — where the reference's loop breaks), resumable through carry_in /
-// carry_out like the reference-arithmetic kernel; a round budget is not enforced in this mode (ok is never 2).
-struct geo_an_ws { // the step loop's per-edge state (device workspace of the context)
-  double *prev, *scr, *dtm; // [E][14] last accepted state, [E][14] the state under projection, [E][3] dist / total / max
-  uint16_t *itp;            // [E] iterations of the step's projection
-  uint8_t *okp, *live;      // [E] its result; is the edge still under way
-};
+// The extend step in analytic mode: jy_ProjectedStateSpace::discreteGeodesic (src/base/jy_ProjectedStateSpace.cpp:32-96) as a
+// TRAVERSAL KERNEL on the latency kernel's layout — sixteen lanes (one DPP row) per edge, four edges per wavefront, one wavefront
+// per block, persistent wavefronts that take edges from a ticket word; the rows of a wavefront run independently, driven by
+// ballots.  Per edge exactly the order of ccmp_geo_edge_body.inc and oracle/ccmp_oracle.c: orc_discrete_geodesic_ex with
+// interpolate = true (the host truncates the list at the first state its StateValidityChecker rejects): `from` as row 0,
+// isSatisfied(to) with check_target (one function evaluation), the entry test, then per state the interpolation (lane l < 14:
+// joint l), the projection (the Newton round of project_row16_kernel, ccmp_row16_eval.inc / ccmp_row16_step.inc: the same bits),
+// jointValid, step and newDist as serial sums over the row's LDS record, the four break tests, the list-full rule, the round
+// budget (ok = 2 between two states), carry_in / carry_out.  An edge that has ended does no further work: its row takes the next
+// ticket between two Newton rounds.
+constexpr int gX = qRec, gPrev = qRec + 14, gTo = qRec + 28, gRec = qRec + 42; // + the projected state, previous, the target; odd stride
 
-__device__ __forceinline__ double geo_distance(const double *a, const double *b)
-{ // RealVectorStateSpace::distance: sqrt of the squares summed left to right (oracle: orc_distance)
-  double d = 0.0;
-#pragma unroll
-  for (int i = 0; i < 14; i++) {
-    const double diff = a[i] - b[i];
-    d = CCMP_FMA(diff, diff, d);
-  }
-  return ccmp_sqrt(d);
-}
-
-__global__ void geo_an_init_kernel(const double delta, const double lambda, const double *__restrict__ from, const double *__restrict__ to,
-                                   unsigned long long E, int max_states, double *__restrict__ states, int32_t *__restrict__ n_states,
-                                   uint8_t *__restrict__ ok, int32_t *__restrict__ newton_iters, const double *__restrict__ carry_in,
-                                   double *__restrict__ carry_out, const uint8_t *__restrict__ target_ok, geo_an_ws W)
+template <bool DIAG>
+__global__ __launch_bounds__(64, 2) void geodesic_row16_kernel(const ccmp_consts K_arg, const double delta, const double lambda,
+                                                               const double *__restrict__ from, const double *__restrict__ to,
+                                                               unsigned long long E, int max_states, double *__restrict__ states,
+                                                               int32_t *__restrict__ n_states, uint8_t *__restrict__ ok_out,
+                                                               int32_t *__restrict__ newton_iters, const double *__restrict__ carry_in,
+                                                               double *__restrict__ carry_out, int round_budget, int check_target,
+                                                               unsigned long long *queue)
 {
-  const unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  double a[14], b[14];
-#pragma unroll
-  for (int i = 0; i < 14; i++) { a[i] = from[e * 14 + i]; b[i] = to[e * 14 + i]; }
-  if (max_states > 0) {
-#pragma unroll
-    for (int i = 0; i < 14; i++) states[e * (unsigned long long)max_states * 14 + i] = a[i];
+  __shared__ double ktab[kConstsDoubles + 1];
+  __shared__ double lds[4 * gRec];
+  {
+    const double *srcp = reinterpret_cast<const double *>(&K_arg);
+    for (int k = threadIdx.x; k < kConstsDoubles; k += 64) ktab[k] = srcp[k];
   }
-  const double dist = geo_distance(a, b);
-  double total = 0.0, mx = dist * lambda;
-  if (carry_in) { total = carry_in[2 * e]; mx = carry_in[2 * e + 1]; }
-  if (carry_out) { carry_out[2 * e] = total; carry_out[2 * e + 1] = mx; }
-  newton_iters[e] = 0;
-  n_states[e] = 1;
-  bool live = true;
-  if (target_ok && !target_ok[e]) { ok[e] = 0; live = false; } // checkMotion: isSatisfied(to) failed — false, only `from` in the list
-  else if (carry_in ? !(dist >= delta) : dist <= delta) { ok[e] = (uint8_t)(dist <= delta); live = false; }
-  W.live[e] = live ? 1 : 0;
-  W.dtm[3 * e] = dist; W.dtm[3 * e + 1] = total; W.dtm[3 * e + 2] = mx;
+  __syncthreads();
+  const ccmp_consts &K = *reinterpret_cast<const ccmp_consts *>(ktab);
+  const int lane = threadIdx.x, l = lane & 15;
+  double *const rec = lds + (lane >> 4) * gRec;
+  // joint role (lanes 14, 15 shadow joint 13 and never store), chain role: as project_row16_kernel
+  const bool jl = l < 14;
+  const int lj = jl ? l : 13;
+  const int aj = lj >= 7 ? 1 : 0, ij = lj - 7 * aj;
+  double ax[3], ap[6];
 #pragma unroll
-  for (int i = 0; i < 14; i++) W.prev[e * 14 + i] = a[i];
-}
-
-struct geo_an_start { double q[14]; };
-
-// the next state of every live edge: WrapperStateSpace::interpolate(previous, to, delta / dist) (KinematicChain.h:145-171; oracle:
-// orc_interpolate); an edge that has ended gets the problem's start state (f = 0 exactly: the projector leaves at once)
-__global__ void geo_an_prepare_kernel(const double delta, const double *__restrict__ to, unsigned long long E, const geo_an_start S, geo_an_ws W)
-{
-  const unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
+  for (int k = 0; k < 3; k++) ax[k] = K.axis[aj][ij][k];
+#pragma unroll
+  for (int k = 0; k < 6; k++) ap[k] = K.aprod[aj][ij][k];
+  const double sgn = aj ? -1.0 : 1.0;
+  const int ac = (l / 3) & 1, rc = l % 3;
+  double cee[3], cRt[9];
+#pragma unroll
+  for (int k = 0; k < 3; k++) cee[k] = K.ee[ac][k];
+#pragma unroll
+  for (int k = 0; k < 9; k++) cRt[k] = K.R_tool[ac][k];
+  const double cd = K.base_R[ac][4 * rc], cbp = K.base_p[ac][rc];
   const double pi = 3.14159265358979323846;
-  if (!W.live[e]) {
-#pragma unroll
-    for (int i = 0; i < 14; i++) W.scr[e * 14 + i] = S.q[i];
-    return;
-  }
-  const double t = delta / W.dtm[3 * e];
-#pragma unroll
-  for (int i = 0; i < 14; i++) {
-    const double f = W.prev[e * 14 + i];
-    double diff = to[e * 14 + i] - f, v;
-    if (ccmp_abs(diff) <= pi) v = CCMP_FMA(diff, t, f);
-    else {
-      if (diff > 0.0) diff = 2.0 * pi - diff;
-      else diff = -2.0 * pi - diff;
-      v = CCMP_FMA(-diff, t, f);
-      if (v > pi) v -= 2.0 * pi;
-      else if (v < -pi) v += 2.0 * pi;
-    }
-    W.scr[e * 14 + i] = v;
-  }
-}
 
-// between two projections: jy_ProjectedStateSpace.cpp:65-92 (the break tests, the list, the running lengths)
-__global__ void geo_an_book_kernel(const double delta, const double lambda, const double *__restrict__ to, unsigned long long E, int max_states,
-                                   double *__restrict__ states, int32_t *__restrict__ n_states, uint8_t *__restrict__ ok,
-                                   int32_t *__restrict__ newton_iters, double *__restrict__ carry_out, geo_an_ws W)
-{
-  const unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E || !W.live[e]) return;
-  double prev[14], sc[14], tg[14];
+  // What the row does next (the sixteen lanes of a row hold the same stage and counters; lane l < 14 also joint l of the iterate x,
+  // of `previous` and of the target in registers, and the row's LDS record holds all fourteen of each for the serial sums)
+  enum { kIdle, kTarget, kProject, kEnter, kBook, kNext, kDone };
+  int stage = kIdle;
+  bool drained = false, target_ok = true, fits = true, suspended = false;
+  unsigned long long t = 0;
+  double x = 0.0, prv = 0.0, tgt = 0.0, dist = 0.0, total = 0.0, maxd = 0.0, norm1 = 0.0, norm2 = 0.0;
+  int n = 0, its = 0, rounds = 0, iter = 0, updates = 0;
+
+  for (;;) {
+    // ---- between two Newton rounds: bookkeeping, ended edges, new edges — until every row projects or the tickets are gone -----
+    for (;;) {
+      if (stage == kBook) { // a projection has ended: jy_ProjectedStateSpace.cpp:65-92
+        its += updates;
+        rounds += updates + 1;
+        if (jl) rec[gX + lj] = x;
+        asm volatile("" ::: "memory"); // written before the row reads it (one wavefront per block: the LDS queue keeps the order)
+        // jointValid(x), step = |previous - x| and newDist = |x - to| side by side, the canonical order each (ccmp_geo_edge_body.inc)
+        bool jv = true;
+        double s_acc = 0.0, d_acc = 0.0;
 #pragma unroll
-  for (int i = 0; i < 14; i++) { prev[i] = W.prev[e * 14 + i]; sc[i] = W.scr[e * 14 + i]; tg[i] = to[e * 14 + i]; }
-  double dist = W.dtm[3 * e], total = W.dtm[3 * e + 1];
-  const double mx = W.dtm[3 * e + 2];
-  const int it = (int)W.itp[e];
-  int its = newton_iters[e] + it, n = n_states[e];
-  bool go_on = W.okp[e] != 0; // !project(scratch) -> break (interpolate = true: no validity test on the device)
-  double step = 0.0;
-  if (go_on) { step = geo_distance(prev, sc); go_on = !(step > lambda * delta); }
-  const double total_before = total;
-  if (go_on) { total += step; go_on = !(total > mx); }
-  double new_dist = dist;
-  if (go_on) { new_dist = geo_distance(sc, tg); go_on = !(new_dist >= dist); }
-  if (go_on && n >= max_states) { // the accepted state finds the list full: the continuation projects it again
-    n_states[e] = max_states + 1;
-    newton_iters[e] = its - it;
-    if (carry_out) { carry_out[2 * e] = total_before; carry_out[2 * e + 1] = mx; }
-    ok[e] = 0;
-    W.live[e] = 0;
-    return;
-  }
-  if (go_on) {
-    dist = new_dist;
+        for (int i = 0; i < 14; i++) {
+          const double xi = rec[gX + i];
+          const int jj = i < 7 ? i : i - 7;
+          if (xi < K.lbe[jj]) jv = false;
+          if (xi > K.ube[jj]) jv = false;
+          const double ds = rec[gPrev + i] - xi, dd = xi - rec[gTo + i];
+          s_acc = CCMP_FMA(ds, ds, s_acc);
+          d_acc = CCMP_FMA(dd, dd, d_acc);
+        }
+        const bool conv = (norm1 < K.tol_pos) && (norm2 < K.tol_rot); // project()'s return value (project_row16_kernel's ok without jointValid)
+        stage = kDone;
+        if (conv && jv) {                                   // else: not on manifold
+          const double step = ccmp_sqrt(s_acc), newDist = ccmp_sqrt(d_acc);
+          const double total_before = total;
+          if (!(step > lambda * delta)) {                   // else: deviated
+            total += step;
+            if (!(total > maxd) && !(newDist >= dist)) {    // else: wandered too far / no closer than before
+              if (n >= max_states) { // the accepted state finds the list full: the continuation projects it again
+                fits = false;
+                n = max_states + 1;
+                total = total_before;
+                its -= updates;
+              } else {
+                dist = newDist;
+                prv = x;
+                if (jl) {
+                  rec[gPrev + lj] = x;
+                  states[(t * (unsigned long long)max_states + (unsigned long long)n) * 14ull + lj] = x;
+                }
+                n++;
+                // } while (dist >= tolerance); then the call's bound on the serial work spent on one edge: past round_budget
+                // Newton rounds the edge stops between two states and reports ok = 2 (ccmp_geo_edge_body.inc)
+                if (dist >= delta) {
+                  if (round_budget > 0 && rounds >= round_budget) suspended = true;
+                  else stage = kNext;
+                }
+              }
+            }
+          }
+        }
+      }
+      // ---- rows without an edge take the next ticket --------------------------------------------------------------------------
+      {
+        const bool want = stage == kIdle && !drained;
+        unsigned long long tk = 0;
+        if (want && l == 0) tk = atomicAdd(queue, 1ull);
+        tk = __shfl(tk, lane & ~15);
+        if (want) {
+          if (tk < E) {
+            t = tk;
+            prv = from[t * 14 + lj];
+            tgt = to[t * 14 + lj];
+            if (jl) {
+              rec[gPrev + lj] = prv;
+              rec[gTo + lj] = tgt;
+              states[t * (unsigned long long)max_states * 14ull + lj] = prv; // geodesic->push_back(cloneState(from))
+            }
+            n = 1; its = 0; rounds = 0;
+            target_ok = true; fits = true; suspended = false;
+            total = 0.0;
+            // ConstrainedMotionValidator::checkMotion (src/planner/stefanBiPRM.cpp:397-398): isSatisfied(to) first, one evaluation
+            if (check_target) { x = tgt; stage = kTarget; }
+            else stage = kEnter;
+          } else drained = true;
+        }
+      }
+      if (stage == kEnter) {
+        asm volatile("" ::: "memory");
+        double d = 0.0;
 #pragma unroll
-    for (int i = 0; i < 14; i++) {
-      W.prev[e * 14 + i] = sc[i];
-      states[(e * (unsigned long long)max_states + (unsigned long long)n) * 14 + i] = sc[i];
+        for (int i = 0; i < 14; i++) {
+          const double diff = rec[gPrev + i] - rec[gTo + i];
+          d = CCMP_FMA(diff, diff, d);
+        }
+        dist = ccmp_sqrt(d);
+        maxd = dist * lambda;
+        // a continuation is in the middle of the reference's do-while: it re-enters on the loop's own condition (dist >= delta)
+        // with the running length and the bound of the first call
+        bool enter = dist > delta;
+        if (carry_in) {
+          total = carry_in[2 * t];
+          maxd = carry_in[2 * t + 1];
+          enter = dist >= delta;
+        }
+        stage = (target_ok && enter) ? kNext : kDone;
+      }
+      if (stage == kNext) { // WrapperStateSpace::interpolate(previous, to, delta_ / dist, scratch) (KinematicChain.h:145-171; orc_interpolate)
+        const double tt = delta / dist;
+        double diff = tgt - prv, v;
+        if (ccmp_abs(diff) <= pi) v = CCMP_FMA(diff, tt, prv);
+        else {
+          if (diff > 0.0) diff = 2.0 * pi - diff;
+          else diff = -2.0 * pi - diff;
+          v = CCMP_FMA(-diff, tt, prv);
+          if (v > pi) v -= 2.0 * pi;
+          else if (v < -pi) v += 2.0 * pi;
+        }
+        x = v;
+        iter = 0; updates = 0; norm1 = 0.0; norm2 = 0.0;
+        stage = kProject;
+      }
+      if (stage == kDone) {
+        if (l == 0) {
+          n_states[t] = n;
+          ok_out[t] = suspended ? (uint8_t)2 : (uint8_t)(target_ok && fits && dist <= delta);
+          if (newton_iters) newton_iters[t] = its;
+          if (carry_out) { carry_out[2 * t] = total; carry_out[2 * t + 1] = maxd; }
+        }
+        stage = kIdle;
+      }
+      if (__builtin_amdgcn_ballot_w64(stage == kIdle && !drained) == 0ull) break;
     }
-    n++;
-    go_on = dist >= delta; // } while (dist >= tolerance)
-  }
-  n_states[e] = n;
-  newton_iters[e] = its;
-  W.dtm[3 * e] = dist; W.dtm[3 * e + 1] = total;
-  if (!go_on) {
-    if (carry_out) { carry_out[2 * e] = total; carry_out[2 * e + 1] = mx; }
-    ok[e] = (uint8_t)(dist <= delta);
-    W.live[e] = 0;
+    if (__builtin_amdgcn_ballot_w64(stage != kIdle) == 0ull) break;
+
+    // ---- one Newton round of every row that projects (or evaluates its target) ------------------------------------------------
+#include "ccmp_row16_eval.inc"
+    bool cont = false;
+    if (stage == kTarget) { // KinematicChainConstraint::isSatisfied (ConstraintFunction.h:114-120): finite, f0 <= tol1, f1 <= tol2
+      target_ok = (f[0] - f[0] == 0.0) && (f[1] - f[1] == 0.0) && f[0] <= K.tol_pos && f[1] <= K.tol_rot;
+      stage = kEnter;
+    } else if (stage == kProject) { // ConstraintFunction.h:68, quirks included
+      const bool c1 = f[0] > K.tol_pos;
+      norm1 = c1 ? 1.0 : 0.0;
+      bool resid = c1;
+      if (!c1) { norm2 = f[1]; resid = f[1] > K.tol_rot; }
+      if (resid) { cont = iter < K.max_iter; iter++; }
+      if (!cont) stage = kBook;
+    }
+    if (__builtin_amdgcn_ballot_w64(cont) == 0ull) continue;
+#include "ccmp_row16_step.inc"
   }
 }
 
@@ -802,24 +743,21 @@ extern "C" hipError_t ccmp_launch_project_analytic(const ccmp_consts *K, int mod
   return hipGetLastError();
 }
 
-// the extend step's step loop in analytic mode: which = 0 init, 1 prepare, 2 bookkeeping (ws: seven device pointers of the
-// context's workspace — prev, scr, dtm, itp, okp, live; start14: the problem's start_joint)
-extern "C" hipError_t ccmp_launch_geodesic_analytic_step(int which, double delta, double lambda, const double *from, const double *to, size_t E,
-                                                         int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters,
-                                                         const double *carry_in, double *carry_out, const uint8_t *target_ok, void *const *ws,
-                                                         const double *start14, hipStream_t st)
+// The extend step in analytic mode, one call on one stream: the ticket word cleared (a kernel, so that a stream capture replays it),
+// then geodesic_row16_kernel with `blocks` wavefronts (four edges each at a time).
+extern "C" hipError_t ccmp_launch_geodesic_analytic(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to, size_t E,
+                                                    int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters,
+                                                    const double *carry_in, double *carry_out, int round_budget, int check_target, int blocks,
+                                                    unsigned long long *queue, hipStream_t st)
 {
-  geo_an_ws W{(double *)ws[0], (double *)ws[1], (double *)ws[2], (uint16_t *)ws[3], (uint8_t *)ws[4], (uint8_t *)ws[5]};
-  const dim3 grid((unsigned)((E + 127) / 128)), block(128);
-  if (which == 0)
-    hipLaunchKernelGGL(geo_an_init_kernel, grid, block, 0, st, delta, lambda, from, to, (unsigned long long)E, max_states, states, n_states, ok,
-                       newton_iters, carry_in, carry_out, target_ok, W);
-  else if (which == 1) {
-    geo_an_start S;
-    for (int i = 0; i < 14; i++) S.q[i] = start14[i];
-    hipLaunchKernelGGL(geo_an_prepare_kernel, grid, block, 0, st, delta, to, (unsigned long long)E, S, W);
-  } else
-    hipLaunchKernelGGL(geo_an_book_kernel, grid, block, 0, st, delta, lambda, to, (unsigned long long)E, max_states, states, n_states, ok,
-                       newton_iters, carry_out, W);
+  if (blocks <= 0) return hipErrorInvalidValue;
+  hipError_t e = ccmp_launch_clear_words(queue, 2, st);
+  if (e != hipSuccess) return e;
+#define CCMP_LAUNCH_GEO_ROW16(DIAG)                                                                                                     \
+  hipLaunchKernelGGL((geodesic_row16_kernel<DIAG>), dim3(blocks), dim3(64), 0, st, *K, delta, lambda, from, to, (unsigned long long)E, \
+                     max_states, states, n_states, ok, newton_iters, carry_in, carry_out, round_budget, check_target, queue)
+  if (K->base_diag == 3) CCMP_LAUNCH_GEO_ROW16(true);
+  else CCMP_LAUNCH_GEO_ROW16(false);
+#undef CCMP_LAUNCH_GEO_ROW16
   return hipGetLastError();
 }

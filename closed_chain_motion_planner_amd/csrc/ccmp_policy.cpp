@@ -229,6 +229,14 @@ AnalyticPlan plan_analytic_batch(const ccmp_ctx *ctx, size_t B)
   return pl;
 }
 
+// Analytic mode's extend step: one persistent wavefront per four edges, at most two per SIMD (the kernel's occupancy); rows take edges
+// from a ticket word, so the grid only bounds how many edges are under way at once
+int plan_geodesic_analytic(const ccmp_ctx *ctx, size_t E)
+{
+  const size_t want = (E + 3) / 4, resident = (size_t)ctx->num_cus * (size_t)kGeoAnalyticWavesPerCu;
+  return (int)(want < resident ? want : resident);
+}
+
 // The extend step.  One 128-thread block per edge.  Up to the resident capacity every edge has its block at once and the
 // hardware dispatcher is the queue.  Beyond it the blocks are persistent and take tickets from an atomic word, handed out
 // through a long-edges-first order when the batch is large enough for the ordering pass to pay.  Two builds of the kernel: a
@@ -399,6 +407,10 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
             ctx->geodesic_group_min, kGeoGroupHighCut, kGeoGroupHigherCut, kGeoGroupLateHandoverFrom);
       break;
     }
+    case CCMP_CALL_GEODESIC_ANALYTIC:
+      L.add("geodesic (analytic mode) E=%zu: geodesic_row16_kernel x %d wavefronts (four edges per wavefront, ticket queue; at most %d per CU)", n,
+            plan_geodesic_analytic(ctx, n), kGeoAnalyticWavesPerCu);
+      break;
     default: return CCMP_EINVAL;
   }
   // without a context the plan is the built-in policy on an ASSUMED device: say so (block counts and the thresholds that mark

@@ -57,6 +57,10 @@ struct GeoPlan {
 };
 GeoPlan plan_geodesic(const ccmp_ctx *ctx, size_t E, int round_budget, bool continuation);
 
+/* the extend step in analytic mode: wavefronts of geodesic_row16_kernel (four edges each at a time) */
+constexpr int kGeoAnalyticWavesPerCu = 8; // two per SIMD at occupancy 2
+int plan_geodesic_analytic(const ccmp_ctx *ctx, size_t E);
+
 /* a context-shaped default for calls that have none at hand (ccmp_ctx_get_option / ccmp_ctx_describe with ctx == NULL):
  * the built-in settings on a 256-CU device */
 const ccmp_ctx &default_ctx();

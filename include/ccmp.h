@@ -235,7 +235,8 @@ enum {
   CCMP_CALL_SAMPLE_PROJECT = 1,   /* ccmp_sample_project_batch                         */
   CCMP_CALL_PROJECT_ANALYTIC = 2, /* ccmp_project_batch with CCMP_JAC_ANALYTIC         */
   CCMP_CALL_GEODESIC = 3,         /* ccmp_geodesic_batch / _ex without a round budget  */
-  CCMP_CALL_GEODESIC_BUDGET = 4   /* ccmp_geodesic_batch_ex with round_budget > 0      */
+  CCMP_CALL_GEODESIC_BUDGET = 4,  /* ccmp_geodesic_batch_ex with round_budget > 0      */
+  CCMP_CALL_GEODESIC_ANALYTIC = 5 /* ccmp_geodesic_batch / _ex with CCMP_JAC_ANALYTIC  */
 };
 int ccmp_ctx_describe(const ccmp_ctx *ctx, int call_kind, size_t n, char *buf, size_t cap);
 int ccmp_ctx_device(const ccmp_ctx *ctx);
@@ -286,10 +287,9 @@ int ccmp_compute_t_wo_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *
  * Python mirror do) — a creeping edge (observed: 952 accepted states, each a hair closer to the target) must not hold
  * a whole launch, and a cut list must never look complete.  Runs as the reference does with interpolate == true; for
  * interpolate == false the host truncates at the first state its StateValidityChecker rejects.
- * With jacobian_mode = CCMP_JAC_ANALYTIC the traversal is a step loop around the batched analytic projector (at most max_states steps of
- * three launches each, no host synchronisation): the same lists, counts, flags and carries as the analytic mode's CPU restatement, bit for
- * bit; newton_iters must be given, a round budget (ccmp_geodesic_batch_ex) is not enforced in that mode (ok is never 2), the resident
- * service does not serve it. */
+ * With jacobian_mode = CCMP_JAC_ANALYTIC the traversal is one launch of a traversal kernel on the analytic projector's Newton round (four
+ * edges per wavefront, no host synchronisation): the same lists, counts, flags and carries as the analytic mode's CPU restatement, bit for
+ * bit, the round budget of ccmp_geodesic_batch_ex included; the resident service does not serve it. */
 int ccmp_geodesic_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *from, const double *to, size_t E, int max_states,
                         double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, void *hip_stream);
 /* The same, resumable.  carry_out (nullable, [E][2]) receives what a continuation needs: the running length and the

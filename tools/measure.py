@@ -4,7 +4,8 @@
     python tools/measure.py sizes   [obj] [--schedules]    run time against batch size (1 .. 1048576), default policy;
                                                            --schedules adds latency-kernel-only and throughput-only columns
     python tools/measure.py single                          latency of the reference-signature single-state calls
-    python tools/measure.py geodesic [E ...]                batched discreteGeodesic (near-neighbour edges)
+    python tools/measure.py geodesic [E ...] [--analytic]   batched discreteGeodesic (near-neighbour edges); --analytic: in analytic mode,
+                                                           lists of 16 with and without the round budget, lists of 64
     python tools/measure.py analytic                        analytic mode against batch size and waves per CU
     python tools/measure.py host                            PCIe-inclusive rate of ccmp_project_host (pageable / pinned)
     python tools/measure.py sharded [n_gpus [B]]            one process, n GPUs, RCCL all-gather inside the C ABI: per-GPU stream times
@@ -13,7 +14,8 @@
     python tools/measure.py soak_resident [N]               N states as single calls through the resident service kernel against the batched kernels
     python tools/measure.py scout                           FP32 scout's predictions against the true iteration counts
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
-                                                           c3 | flat4096 | mid<B> | flat1 | geodesic | analytic[<B>] | stefan | stefan_tight | calibrated | clearance
+                                                           c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
+                                                           stefan_tight | calibrated | clearance
 """
 import ctypes as C
 import sys
@@ -106,11 +108,16 @@ def geodesic(argv):
     operation (continuation of those edges until every list is whole)"""
     ctx = Context(0)
     c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
-    for E in [int(a) for a in argv] or [5, 64, 1024, 16384]:
+    analytic = "--analytic" in argv
+    shapes = ((16, 128), (64, 0))  # bench.py's first pass: lists of 16 states, 128 Newton rounds per edge; lists of 64
+    if analytic:  # the edges are drawn in the default mode (the same edges as without the switch), then traversed in analytic mode
+        shapes = ((16, 128), (16, 0), (64, 0))
+    for E in [int(a) for a in argv if not a.startswith("--")] or [5, 64, 1024, 16384]:
         frm, to = near_edges(c, E)
+        if analytic:
+            c.setJacobianMode(1)
         row = []
-        for cap in (16, 64):
-            budget = 128 if cap == 16 else 0  # bench.py's first pass: lists of 16 states, 128 Newton rounds per edge
+        for cap, budget in shapes:
             ms = timed(lambda: c.discrete_geodesic_batch(frm, to, cap, want_carry=True, round_budget=budget), reps=3)
             st, n, okg, its, carry = c.discrete_geodesic_batch(frm, to, cap, want_carry=True, round_budget=budget)
             over = int(((n > cap) | (okg == 2)).sum())
@@ -120,10 +127,15 @@ def geodesic(argv):
             whole = c.continue_geodesics(to, r[0], r[1], r[2], r[3], r[4], cap, round_budget=budget)
             torch.cuda.synchronize()
             ms_all = (time.perf_counter() - t0) * 1e3
-            row.append("lists of %d: %.3f ms, %d edges did not fit, %.3e complete edges/s; everything continued to the end: %.2f ms"
-                       % (cap, ms, over, (E - over) / ms * 1e3, ms_all))
-        print("E=%-6d %s | mean states %.2f (first %d), reached %.3f, Newton iterations per edge %.1f"
-              % (E, "; ".join(row), n.clamp(max=cap).float().mean().item(), cap, (okg == 1).float().mean().item(), its.float().mean().item()), flush=True)
+            # Newton rounds of the longest edge's serial chain in this call: its updates plus one per projection (its stored states
+            # after `from`, and the state that ended it)
+            rounds = int((its + n.clamp(max=cap)).max().item())
+            row.append("lists of %d, budget %d: %.3f ms, %d edges did not fit, %.3e complete edges/s, longest edge %d rounds; "
+                       "everything continued to the end: %.2f ms" % (cap, budget, ms, over, (E - over) / ms * 1e3, rounds, ms_all))
+        print("E=%-6d %s%s | mean states %.2f (first %d), reached %.3f, Newton iterations per edge %.1f"
+              % (E, "analytic mode: " if analytic else "", "; ".join(row), n.clamp(max=cap).float().mean().item(), cap, (okg == 1).float().mean().item(),
+                 its.float().mean().item()), flush=True)
+        c.setJacobianMode(0)
 
 
 _ANALYTIC = ("analytic_small_batch", "analytic_waves_per_cu", "analytic_handover")
@@ -432,6 +444,10 @@ def run(argv):
     elif what == "flat1":
         x = c.ambient_uniform_batch(0xC1, 0, 64).cpu().numpy()
         fn = lambda: [c.project(x[i].copy()) for i in range(64)]
+    elif what.startswith("geodesic_analytic"):  # the same first pass in analytic mode (geodesic_row16_kernel)
+        frm, to = near_edges(c, int(what[17:] or 16384))
+        c.setJacobianMode(1)
+        fn = lambda: c.discrete_geodesic_batch(frm, to, 16, want_carry=True, round_budget=128)
     elif what.startswith("geodesic"):  # geodesic (16384 edges: bench.py's first pass), geodesic65536 (a bulk call) ...
         frm, to = near_edges(c, int(what[8:] or 16384))
         fn = lambda: c.discrete_geodesic_batch(frm, to, 16, want_carry=True, round_budget=128)  # bench.py's first pass
