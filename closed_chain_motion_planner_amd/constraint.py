@@ -52,8 +52,9 @@ class Context:
 
     def set_option(self, name, value):
         """tuning knobs of include/ccmp.h (ccmp_ctx_set_option): "handover_threshold", "flat_kernel", "stock_kernels",
-        "analytic_cap" / "analytic_small_batch" / "analytic_handover_max", "analytic_split" (+ "_min", "_max", "_pred",
-        "_front", "_cap"), "clearance_per_state_max"; results never change"""
+        "fd_split" (+ "_min", "_max", "_pred", "_front", "_samples", "_group_cut"), "analytic_small_batch" /
+        "analytic_waves_per_cu" / "analytic_handover", "geodesic_*", "clearance_per_state_max", "resident" — every one with its
+        range in _lib.option_table(); results never change"""
         check(_lib.lib().ccmp_ctx_set_option(self._h, name.encode(), int(value)), "ccmp_ctx_set_option(%s)" % name)
 
     def get_option(self, name):

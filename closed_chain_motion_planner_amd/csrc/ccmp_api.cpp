@@ -15,110 +15,18 @@
 #include "../../include/ccmp.h"
 #include "ccmp_ctx.h"
 #include "ccmp_host.h"
+#include "ccmp_launch.h"
 #include "ccmp_policy.h"
 #include "ccmp_resident.h"
-#include "ccmp_split.h"
-#include "ccmp_kin.h"
 
-using ccmp_host::AnalyticPlan;
-using ccmp_host::DeviceGuard;
-using ccmp_host::FdPlan;
-using ccmp_host::GeoPlan;
-using ccmp_host::g_hip_err;
-using ccmp_host::hip_fail;
-using ccmp_host::kPinData;
+using namespace ccmp_host;
+using namespace ccmp_launch; // the queue words, the call-wide argument structs
 
 namespace ccmp_host {
 thread_local char g_hip_err[256] = "";
 }  // namespace ccmp_host
 
-extern "C" int ccmp_policy_set_option(ccmp_ctx *ctx, const char *name, long value); // ccmp_policy.cpp: the option table
-
-extern "C" {
-hipError_t ccmp_launch_clear_words(void *words, size_t n_u32, hipStream_t st);
-hipError_t ccmp_launch_project_group(const ccmp_consts *K, int mode, const double *q_in, double *q_out, uint8_t *ok,
-                                     uint16_t *iters, double *q_ambient, size_t B, unsigned long long *queue,
-                                     unsigned long long seed, unsigned long long first, int nblocks, double *pool,
-                                     int dump_threshold, const unsigned int *order, const uint16_t *pred, int long_remaining,
-                                     size_t pool_records, hipStream_t st);
-hipError_t ccmp_launch_project_wave(const ccmp_consts *K, int src, const double *q_in, double *q_out, uint8_t *ok,
-                                    uint16_t *iters, double *q_ambient, size_t B, unsigned long long *queue_head,
-                                    unsigned long long seed, unsigned long long first, const double *pool,
-                                    const unsigned long long *pool_count, int wrap_output, int nblocks, hipStream_t st);
-hipError_t ccmp_launch_project_flat(const ccmp_consts *K, int src, const double *q_in, double *q_out, uint8_t *ok,
-                                    uint16_t *iters, double *q_ambient, size_t B, unsigned long long *queue_head,
-                                    unsigned long long seed, unsigned long long first, const double *pool,
-                                    const unsigned long long *pool_count, int wrap_output, int nblocks, unsigned int *done_flag,
-                                    unsigned int done_seq, size_t pool_records, const unsigned int *order,
-                                    const unsigned long long *total_ptr, hipStream_t st);
-hipError_t ccmp_launch_fd_split(const unsigned int *hist, int pred_min, unsigned int limit, unsigned long long *queue, hipStream_t st);
-hipError_t ccmp_launch_geo_split(const unsigned int *hist, int p_min, int p_max, int permille, unsigned long long *queue, hipStream_t st);
-hipError_t ccmp_launch_split_count(const unsigned int *hist, int pred_min, unsigned int limit, unsigned int *out, hipStream_t st);
-hipError_t ccmp_launch_geodesic_analytic(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to, size_t E,
-                                         int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters,
-                                         const double *carry_in, double *carry_out, int round_budget, int check_target, int blocks,
-                                         unsigned long long *queue, hipStream_t st);
-hipError_t ccmp_launch_project_analytic(const ccmp_consts *K, int mode, const double *q_in, double *q_out, uint8_t *ok, uint16_t *iters,
-                                        double *q_ambient, size_t B, unsigned long long *queue, unsigned long long seed,
-                                        unsigned long long first, int pair_blocks, int dump_below, int latency_blocks, double *pool,
-                                        hipStream_t st);
-hipError_t ccmp_launch_scout_order(const ccmp_consts *K, int mode, const double *q_in, size_t B, uint16_t *pred,
-                                   unsigned int *hist, unsigned int *order, unsigned long long *queue,
-                                   unsigned long long seed, unsigned long long first, int nblocks, int pair_max_blocks,
-                                   const ccmp_split_req *split, hipStream_t st);
-hipError_t ccmp_launch_function(const ccmp_consts *K, const double *q, double *f, size_t B, unsigned int *done_flag,
-                                unsigned int done_seq, hipStream_t st);
-hipError_t ccmp_launch_is_satisfied(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag,
-                                    unsigned int done_seq, hipStream_t st);
-hipError_t ccmp_launch_joint_valid(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag,
-                                   unsigned int done_seq, hipStream_t st);
-hipError_t ccmp_launch_ambient_uniform(const ccmp_consts *K, unsigned long long seed, unsigned long long first,
-                                       double *q, size_t B, hipStream_t st);
-hipError_t ccmp_launch_enforce_bounds(double *q, size_t B, hipStream_t st);
-hipError_t ccmp_launch_ambient_ref(const ccmp_consts *K, int kind, unsigned long long seed, unsigned long long first,
-                                   const double *ref, int ref_stride, double param, double *q, size_t B, hipStream_t st);
-hipError_t ccmp_launch_t_wo(const ccmp_consts *K, const double *q, int q_stride, double *out, size_t B, hipStream_t st);
-hipError_t ccmp_launch_geodesic(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to,
-                                size_t E, int max_states, double *states, int *n_states, uint8_t *ok, int *newton_iters,
-                                int check_target, int nblocks, unsigned long long *queue, const unsigned int *order,
-                                const double *carry_in, double *carry_out, int round_budget, const unsigned long long *total_ptr,
-                                const double *pool, const unsigned long long *pool_count, hipStream_t st);
-hipError_t ccmp_launch_geodesic_lat(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to,
-                                    size_t E, int max_states, double *states, int *n_states, uint8_t *ok, int *newton_iters,
-                                    int check_target, int nblocks, unsigned long long *queue, const unsigned int *order,
-                                    const double *carry_in, double *carry_out, int round_budget, const unsigned long long *total_ptr,
-                                    const double *pool, const unsigned long long *pool_count, hipStream_t st);
-hipError_t ccmp_launch_geodesic_group(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to, size_t E,
-                                      int max_states, double *states, int *n_states, uint8_t *ok, int *newton_iters, int nblocks,
-                                      unsigned long long *queue, const unsigned int *order, double *carry_out, int round_budget,
-                                      double *pool, unsigned long long *pool_count, int handover_pct, const uint8_t *target_ok, hipStream_t st);
-hipError_t ccmp_launch_geodesic_order(const double *from, const double *to, size_t E, double long_dist, unsigned int *counters,
-                                      unsigned int *order, hipStream_t st);
-hipError_t ccmp_launch_geodesic_scout_order(const ccmp_consts *K, const double *from, const double *to, size_t E, double delta, double lambda,
-                                            int max_states, int round_cap, uint16_t *pred, unsigned int *hist, unsigned int *order, int pairs,
-                                            const ccmp_split_req *split, hipStream_t st);
-hipError_t ccmp_launch_detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
-hipError_t ccmp_launch_div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);
-hipError_t ccmp_launch_compact(const double *q, const uint8_t *ok, size_t B, double *out, size_t capacity,
-                               unsigned int *block_counts, unsigned long long *total, hipStream_t st);
-}
-
-
-
 namespace {
-
-
-
-
-// single-state calls from the host entry points: the kernel publishes ctx->done_seq in the pinned block behind its
-// result and HostIO::finish polls that word (NULL = this launch does not publish)
-unsigned int *arm_done_word(ccmp_ctx *ctx, size_t B)
-{
-  if (!ctx->want_done || B != 1 || !ctx->pin_dev) return nullptr;
-  ctx->done_seq++;
-  ctx->done_armed = true;
-  return (unsigned int *)((char *)ctx->pin_dev + kPinData);
-}
 
 // A launch sequence that puts part of a call on the context's side stream.  fork() orders the side stream behind what the
 // caller's stream holds; step() launches and remembers the FIRST failure instead of returning (later steps are skipped);
@@ -158,9 +66,9 @@ struct ForkJoin {
   }
 };
 
-#define FJ_STEP(fj, call)                                  \
-  do {                                                     \
-    if ((fj).err == hipSuccess) (fj).fail((call), #call);  \
+#define FJ_STEP(fj, ...)                                                 \
+  do {                                                                   \
+    if ((fj).err == hipSuccess) (fj).fail((__VA_ARGS__), #__VA_ARGS__);  \
   } while (0)
 
 int check_problem(const ccmp_problem *p)
@@ -229,7 +137,7 @@ int ccmp_ctx_create(int device, ccmp_ctx **out)
   ctx->num_cus = prop.multiProcessorCount;
   e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete ctx; return hip_fail(e, "hipStreamCreate"); }
-  e = hipMalloc((void **)&ctx->queue, (kGeoGroupWords + 8) * sizeof(unsigned long long)); // 8 words: reference-arithmetic kernels; kAnalyticWords: analytic kernel; 1: analytic extend step; 8: bulk extend
+  e = hipMalloc((void **)&ctx->queue, kQueueWords * sizeof(unsigned long long));
   if (e != hipSuccess) { (void)hipStreamDestroy(ctx->stream); delete ctx; return hip_fail(e, "hipMalloc(queue)"); }
   // side stream of the analytic mode's split launches (latency kernel beside the throughput kernel) and the two events
   // that order it against the caller's stream
@@ -292,7 +200,7 @@ int ccmp_ctx_set_option(ccmp_ctx *ctx, const char *name, long value)
 {
   if (!ctx || !name) return CCMP_EINVAL;
   if (!strcmp(name, "resident")) return ccmp_host::resident_set(ctx, value); // starts / stops the service kernel (ccmp_resident.cpp)
-  return ccmp_policy_set_option(ctx, name, value); // the option table: ccmp_policy.cpp
+  return ccmp_host::policy_set_option(ctx, name, value); // the option table: ccmp_policy.cpp
 }
 int ccmp_ctx_set_lpt(ccmp_ctx *ctx, int mode, size_t min_batch)
 {
@@ -351,32 +259,27 @@ int ccmp_function_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *q, d
   if (B == 0) return CCMP_OK;
   if (!q || !f) return CCMP_EINVAL;
   unsigned int *flag = arm_done_word(ctx, B);
-  HIP_TRY(ccmp_launch_function(&K, q, f, B, flag, ctx->done_seq, st));
+  HIP_TRY(ccmp_launch::function(&K, q, f, B, flag, ctx->done_seq, st));
   return CCMP_OK;
 }
 
-// workspaces owned by the context; they grow outside any stream capture (the first call at a size is never captured)
-static int ensure_pool(ccmp_ctx *ctx, size_t records)
+// workspaces owned by the context: below n units (*cap) *buf is replaced by `bytes` new bytes.  They grow outside any stream
+// capture (the first call at a size is never captured) and after a resident service kernel has left (hipFree waits for it)
+static int grow(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes)
 {
-  if (ctx->pool_cap >= records) return CCMP_OK;
-  ccmp_host::quiesce(ctx); // (hipFree waits for the whole device: a resident service kernel must be gone first)
-  if (ctx->pool) (void)hipFree(ctx->pool);
-  ctx->pool = nullptr;
-  ctx->pool_cap = 0;
-  HIP_TRY(hipMalloc((void **)&ctx->pool, records * 18 * sizeof(double)));
-  ctx->pool_cap = records;
+  if (*cap >= n) return CCMP_OK;
+  ccmp_host::quiesce(ctx);
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr;
+  *cap = 0;
+  HIP_TRY(hipMalloc(buf, bytes));
+  *cap = n;
   return CCMP_OK;
 }
-static int ensure_lpt_buffers(ccmp_ctx *ctx, size_t B)
+static int ensure_pool(ccmp_ctx *ctx, size_t records) { return grow(ctx, (void **)&ctx->pool, &ctx->pool_cap, records, records * kPoolEntry * sizeof(double)); }
+static int ensure_lpt_buffers(ccmp_ctx *ctx, size_t B) // pred u16 | hist 1024 x u32 | order u32 | flags u8 (bulk checkMotion)
 {
-  if (ctx->lpt_cap >= B) return CCMP_OK;
-  ccmp_host::quiesce(ctx);
-  if (ctx->lpt_buf) (void)hipFree(ctx->lpt_buf);
-  ctx->lpt_buf = nullptr;
-  ctx->lpt_cap = 0;
-  HIP_TRY(hipMalloc(&ctx->lpt_buf, ((B * 2 + 255) & ~(size_t)255) + 4096 + B * 4 + B)); // pred u16 | hist 1024 x u32 | order u32 | flags u8 (bulk checkMotion)
-  ctx->lpt_cap = B;
-  return CCMP_OK;
+  return grow(ctx, &ctx->lpt_buf, &ctx->lpt_cap, B, ((B * 2 + 255) & ~(size_t)255) + 4096 + B * 4 + B);
 }
 
 // the scout's workspace inside ctx->lpt_buf: pred (u16 x cap) | hist (u32 x 1024) | order (u32 x cap) | flags (u8 x cap)
@@ -400,15 +303,15 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
   if (B == 0) return CCMP_OK;
   if (!q_out || !ok || (mode == 0 && !q_in)) return CCMP_EINVAL;
   if ((((uintptr_t)q_in) | ((uintptr_t)q_out)) & 15u) return CCMP_EINVAL; // rows are moved in 16-byte pieces
-  const int scout_pair_blocks = ctx->scout_pairs ? ctx->num_cus * ctx->scout_pair_blocks_per_cu : 0;
+  const ProjectCall c{&K, mode, q_in, q_out, ok, iters, q_ambient, B, seed, first};
+  const int scout_pair_blocks = ctx->scout_pairs ? ctx->num_cus * kScoutPairBlocksPerCu : 0;
   if (p->jacobian_mode != CCMP_JAC_FD) { // analytic mode: the plan is ccmp_policy.cpp's plan_analytic_batch
     const AnalyticPlan pl = ccmp_host::plan_analytic_batch(ctx, B);
     if (pl.pool_records > 0) {
       int rc = ensure_pool(ctx, pl.pool_records); // sized before anything of the call is in flight
       if (rc != CCMP_OK) return rc;
     }
-    HIP_TRY(ccmp_launch_project_analytic(&K, mode, q_in, q_out, ok, iters, q_ambient, B, ctx->queue + 8, seed, first, pl.pair_blocks, pl.dump,
-                                         pl.latency_blocks, ctx->pool, st));
+    HIP_TRY(ccmp_launch::project_analytic(c, pl.pair_blocks, pl.dump, pl.latency_blocks, ctx->pool, ctx->queue + kQAnalytic, st));
     return CCMP_OK;
   }
   // Reference arithmetic.  sampleUniform on arms WITHOUT the stock structure (calibrated arms, tilted bases) is not fused: the
@@ -417,10 +320,10 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
   // spilled 2.3 KB per lane (its sampler prologue and the general chain's pose arrays overlap) and was removed in round 6.
   if (mode == 1 && !(K.stock && K.twin_arms)) {
     double *amb = q_ambient ? q_ambient : q_out;
-    HIP_TRY(ccmp_launch_ambient_uniform(&K, seed, first, amb, B, st));
+    HIP_TRY(ccmp_launch::ambient_uniform(&K, seed, first, amb, B, st));
     const int rc = project_common(ctx, p, 0, amb, q_out, ok, iters, nullptr, B, seed, first, hip_stream);
     if (rc != CCMP_OK) return rc;
-    HIP_TRY(ccmp_launch_enforce_bounds(q_out, B, st));
+    HIP_TRY(ccmp_launch::enforce_bounds(q_out, B, st));
     return CCMP_OK;
   }
   // the plan is ccmp_policy.cpp's plan_fd_batch (what ccmp_ctx_describe prints)
@@ -434,9 +337,8 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
     int rc = ensure_pool(ctx, (size_t)pl.group_blocks * 10);
     if (rc != CCMP_OK) return rc;
   }
-  // queue[0]: sample queue of the throughput kernel; queue[1]: pool fill count; queue[2]: read head of the latency kernel
-  unsigned long long *const q_group = ctx->queue, *const q_pool_count = ctx->queue + 1, *const q_latency = ctx->queue + 2;
-  if (!pl.latency_static) HIP_TRY(ccmp_launch_clear_words(ctx->queue, 16, st)); // the eight 64-bit words of this path (6: pool count from the back)
+  unsigned long long *const q_pool_count = ctx->queue + kQPool, *const q_latency = ctx->queue + kQLatency;
+  if (!pl.latency_static) HIP_TRY(ccmp_launch::clear_words(ctx->queue, 16, st)); // the projector's eight queue words
 
   if (pl.group_blocks == 0) { // small batches and single states
     if (ctx->flat_kernel) {
@@ -448,15 +350,14 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
       // the scout — profiles/r06_head_start_ab.log.)
       if (pl.latency_order) { // longest-predicted-first on the latency kernel alone
         const ScoutBuffers sb(ctx);
-        HIP_TRY(ccmp_launch_scout_order(&K, mode, q_in, B, sb.pred, sb.hist, sb.order, ctx->queue + 5, seed, first, ctx->num_cus, scout_pair_blocks, nullptr, st));
+        HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, ctx->queue + kQScout, ctx->num_cus, scout_pair_blocks, nullptr, st));
         lat_order = sb.order;
       }
-      HIP_TRY(ccmp_launch_project_flat(&K, mode, q_in, q_out, ok, iters, q_ambient, B, pl.latency_static ? nullptr : q_latency, seed, first,
-                                       ctx->pool, q_pool_count, mode, pl.latency_blocks, flag, ctx->done_seq, 0, lat_order, nullptr, st));
+      HIP_TRY(ccmp_launch::project_flat(c, {.blocks = pl.latency_blocks, .queue = pl.latency_static ? nullptr : q_latency, .pool = ctx->pool,
+                                            .pool_count = q_pool_count, .order = lat_order, .done_flag = flag, .done_seq = ctx->done_seq}, st));
     }
     else
-      HIP_TRY(ccmp_launch_project_wave(&K, mode, q_in, q_out, ok, iters, q_ambient, B, q_latency, seed, first, ctx->pool, q_pool_count,
-                                       mode, pl.latency_blocks, st));
+      HIP_TRY(ccmp_launch::project_wave(c, false, pl.latency_blocks, q_latency, ctx->pool, q_pool_count, st));
     return CCMP_OK;
   }
 
@@ -466,10 +367,9 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
   if (pl.scout) { // FP32 scout pass -> predicted iteration counts -> descending counting sort -> processing order
     const ScoutBuffers sb(ctx);
     // one 256-thread block per CU, 4 samples per lane at 262144: more lanes only lengthen the per-wave maximum
-    // (a split launch's cut of the order — fd_split_kernel's rule — is decided by the sort's own kernel: ccmp_split.h)
+    // (a split launch's cut of the order — fd_split_kernel's rule — is decided by the sort's own kernel: ccmp_launch.h, ccmp_split_req)
     const ccmp_split_req cut{ctx->queue, 1, pl.shape.pred, 0, 0, pl.shape.samples, 0};
-    HIP_TRY(ccmp_launch_scout_order(&K, mode, q_in, B, sb.pred, sb.hist, sb.order, ctx->queue + 5, seed, first, ctx->num_cus, scout_pair_blocks,
-                                    pl.split ? &cut : nullptr, st));
+    HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, ctx->queue + kQScout, ctx->num_cus, scout_pair_blocks, pl.split ? &cut : nullptr, st));
     order = sb.order;
     // hand-over in two classes (scout's prediction minus the iterations done): the pool is filled from both ends and the
     // latency kernel takes the long samples first
@@ -482,22 +382,21 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
     if (pl.split) {
       fj.fork();
       CCMP_FAIL_AFTER_FORK(fj, 1);
-      FJ_STEP(fj, ccmp_launch_project_flat(&K, mode, q_in, q_out, ok, iters, q_ambient, B, ctx->queue + 7, seed, first, ctx->pool, q_pool_count, mode,
-                                           pl.shape.blocks, nullptr, 0, 0, sb.order, ctx->queue + 4, ctx->side));
+      FJ_STEP(fj, ccmp_launch::project_flat(c, {.blocks = pl.shape.blocks, .queue = ctx->queue + kQFront, .pool = ctx->pool, .pool_count = q_pool_count,
+                                                .order = sb.order, .total = ctx->queue + kQFrontLen}, ctx->side));
       fj.side_done();
       CCMP_FAIL_AFTER_FORK(fj, 2);
     }
   }
   const size_t pool_records = pred ? (size_t)pl.group_blocks * 10 : 0;
-  FJ_STEP(fj, ccmp_launch_project_group(&K, mode, q_in, q_out, ok, iters, q_ambient, B, q_group, seed, first, pl.group_blocks,
-                                        pl.handover ? ctx->pool : nullptr, pl.dump_threshold, order, pred, ctx->pool_long_remaining, pool_records, st));
+  FJ_STEP(fj, ccmp_launch::project_group(c, pl.group_blocks, ctx->queue, pl.handover ? ctx->pool : nullptr, pl.dump_threshold, order, pred,
+                                         kPoolLongRemaining, pool_records, st));
   if (pl.handover) { // the pool's fill count is read on the device: the latency kernel's surplus blocks exit at once
     if (ctx->flat_kernel)
-      FJ_STEP(fj, ccmp_launch_project_flat(&K, 2, q_in, q_out, ok, iters, q_ambient, B, q_latency, seed, first, ctx->pool, q_pool_count, mode,
-                                           pl.latency_blocks, nullptr, 0, pool_records, nullptr, nullptr, st));
+      FJ_STEP(fj, ccmp_launch::project_flat(c, {.blocks = pl.latency_blocks, .queue = q_latency, .from_pool = true, .pool = ctx->pool,
+                                                .pool_count = q_pool_count, .pool_records = pool_records}, st));
     else
-      FJ_STEP(fj, ccmp_launch_project_wave(&K, 2, q_in, q_out, ok, iters, q_ambient, B, q_latency, seed, first, ctx->pool, q_pool_count, mode,
-                                           pl.latency_blocks, st));
+      FJ_STEP(fj, ccmp_launch::project_wave(c, true, pl.latency_blocks, q_latency, ctx->pool, q_pool_count, st));
   }
   return fj.join(); // the call is complete on `st` when the front is
 }
@@ -523,7 +422,7 @@ static int sample_ref_common(ccmp_ctx *ctx, const ccmp_problem *p, int kind, uin
   if (!ref || !q_out || !ok || (ref_stride != 0 && ref_stride != 14) || !(param >= 0)) return CCMP_EINVAL;
   {
     CCMP_PROLOGUE();
-    HIP_TRY(ccmp_launch_ambient_ref(&K, kind, seed, first_index, ref, ref_stride, param, q_out, B, st));
+    HIP_TRY(ccmp_launch::ambient_ref(&K, kind, seed, first_index, ref, ref_stride, param, q_out, B, st));
     if (q_ambient) HIP_TRY(hipMemcpyAsync(q_ambient, q_out, B * 14 * sizeof(double), hipMemcpyDeviceToDevice, st));
   }
   int rc = ccmp_project_batch(ctx, p, q_out, q_out, ok, iters, B, hip_stream);
@@ -551,7 +450,7 @@ int ccmp_compute_t_wo_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *
   CCMP_PROLOGUE();
   if (B == 0) return CCMP_OK;
   if (!q || !t_wo || q_stride < 7) return CCMP_EINVAL;
-  HIP_TRY(ccmp_launch_t_wo(&K, q, q_stride, t_wo, B, st));
+  HIP_TRY(ccmp_launch::t_wo(&K, q, q_stride, t_wo, B, st));
   return CCMP_OK;
 }
 
@@ -568,12 +467,12 @@ static int geodesic_common(ccmp_ctx *ctx, const ccmp_problem *p, const double *f
   // a resumable call needs room for one state besides `from`: with a one-entry list the first accepted state already reports
   // max_states + 1 with `from` as its last stored state, and a caller following the protocol would continue from `from` for ever
   if ((carry_in || carry_out || round_budget > 0) && max_states < 2) return CCMP_EINVAL;
+  const GeoCall g{&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok, newton_iters, carry_in, carry_out, round_budget, check_target};
   if (p->jacobian_mode != CCMP_JAC_FD) {
     // Analytic mode: one launch of the traversal kernel on the analytic latency kernel's layout (ccmp_kernels_fast.hip:
     // geodesic_row16_kernel — four edges per wavefront, ticket queue, isSatisfied(to), the round budget and the carries inside);
     // no workspace, no host synchronisation, capturable.  ccmp_policy.cpp: plan_geodesic_analytic — what ccmp_ctx_describe prints.
-    HIP_TRY(ccmp_launch_geodesic_analytic(&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok, newton_iters, carry_in, carry_out,
-                                          round_budget, check_target, ccmp_host::plan_geodesic_analytic(ctx, E), ctx->queue + kGeoAnalyticWord, st));
+    HIP_TRY(ccmp_launch::geodesic_analytic(g, ccmp_host::plan_geodesic_analytic(ctx, E), ctx->queue + kQGeoAnalytic, st));
     return CCMP_OK;
   }
   // what the call is going to launch is decided (ccmp_policy.cpp: plan_geodesic — what ccmp_ctx_describe prints) and every workspace
@@ -585,29 +484,25 @@ static int geodesic_common(ccmp_ctx *ctx, const ccmp_problem *p, const double *f
     int rc = ensure_lpt_buffers(ctx, E);
     if (rc != CCMP_OK) return rc;
   }
-  if (pl.bulk && pl.handover_pct > 0 && ctx->geo_pool_cap < pl.group_waves * 10) { // (grows outside any stream capture: the first call at a size is never captured)
-    ccmp_host::quiesce(ctx);
-    if (ctx->geo_pool) (void)hipFree(ctx->geo_pool);
-    ctx->geo_pool = nullptr;
-    ctx->geo_pool_cap = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->geo_pool, pl.group_waves * 10 * kGeoPoolDoubles * sizeof(double)));
-    ctx->geo_pool_cap = pl.group_waves * 10;
+  if (pl.bulk && pl.handover_pct > 0) {
+    int rc = grow(ctx, (void **)&ctx->geo_pool, &ctx->geo_pool_cap, pl.group_waves * 10, pl.group_waves * 10 * kGeoPoolEntry * sizeof(double));
+    if (rc != CCMP_OK) return rc;
   }
   if (pl.queued) {
-    queue = ctx->queue + 3; // word 3: ticket; word 4: the two counters of the ordering pass
-    HIP_TRY(ccmp_launch_clear_words(queue, 4, st));
+    queue = ctx->queue + kQGeoTicket;
+    HIP_TRY(ccmp_launch::clear_words(queue, 4, st)); // the ticket and the ordering pass's counters
     if (pl.ordered) {
       const ScoutBuffers sb(ctx);
       if (pl.scouted) {
         // FP32 scout of every edge (the traversal in single precision with the exact Jacobian, one edge per lane, rounds
         // capped) -> predicted Newton rounds -> descending counting sort: longest-predicted-first
         // (a bulk call's default cut of the order — apply_split's kind 2, ccmp_kernels_scout.hip — is decided, and the launch's block of queue words
-        // cleared, by the sort's own kernel: ccmp_split.h)
-        const ccmp_split_req cut{ctx->queue + kGeoGroupWords, 2, pl.low_cut, 64, ctx->geodesic_group_heavy_permille, 0u, 8};
-        HIP_TRY(ccmp_launch_geodesic_scout_order(&K, from, to, E, p->delta, p->lambda, max_states, ctx->geodesic_scout_rounds, sb.pred, sb.hist,
-                                                 sb.order, pl.scout_pairs, pl.bulk && pl.default_cut ? &cut : nullptr, st));
+        // cleared, by the sort's own kernel: ccmp_launch.h, ccmp_split_req)
+        const ccmp_split_req cut{ctx->queue + kQBulk, 2, pl.low_cut, 64, kGeoGroupHeavyPermille, 0u, 8};
+        HIP_TRY(ccmp_launch::geodesic_scout_order(g, ctx->geodesic_scout_rounds, sb.pred, sb.hist, sb.order, pl.scout_pairs,
+                                                  pl.bulk && pl.default_cut ? &cut : nullptr, st));
       } else {
-        HIP_TRY(ccmp_launch_geodesic_order(from, to, E, ctx->geodesic_long_steps * p->delta, (unsigned int *)(ctx->queue + 4), sb.order, st));
+        HIP_TRY(ccmp_launch::geodesic_order(from, to, E, ctx->geodesic_long_steps * p->delta, (unsigned int *)(ctx->queue + kQGeoOrder), sb.order, st));
       }
       order = sb.order;
     }
@@ -616,43 +511,44 @@ static int geodesic_common(ccmp_ctx *ctx, const ccmp_problem *p, const double *f
   // wavefront, geodesic_group_kernel, less than half the instructions per Newton round — and the front of the order on this
   // kernel's blocks on the side stream, both from the start.
   if (pl.bulk) {
-    unsigned long long *gq = ctx->queue + kGeoGroupWords; // [0] group kernel's ticket (starts behind the front), [3] finished edges, [4] front length, [5] front's ticket, [6] pool count, [7] pool ticket
+    unsigned long long *gq = ctx->queue + kQBulk; // words: BulkWord
     const ScoutBuffers sb(ctx);
     const int pct = pl.handover_pct;
-    if (!pl.default_cut) HIP_TRY(ccmp_launch_clear_words(gq, 16, st));
+    if (!pl.default_cut) HIP_TRY(ccmp_launch::clear_words(gq, 16, st));
     // checkMotion: isSatisfied(to) of every edge up front (one lane per edge) for the group kernel; the front's blocks test their own
     uint8_t *target_ok = nullptr;
     if (check_target) {
       target_ok = (uint8_t *)sb.hist + 4096 + ctx->lpt_cap * 4;
-      HIP_TRY(ccmp_launch_is_satisfied(&K, to, target_ok, E, nullptr, 0, st));
+      HIP_TRY(ccmp_launch::is_satisfied(&K, to, target_ok, E, nullptr, 0, st));
     }
     // the cut of the order: by default one of two, by what the batch looks like — at the scout's cap where the edges beyond it carry
     // a tenth of the predicted work (stefan, dumbbell), lower where they do not (Wine_Bottle) — decided by the sort's kernel above;
     // the options that fix it themselves get a launch of their own
     if (ctx->geodesic_group_permille > 0)
-      HIP_TRY(ccmp_launch_geo_split(sb.hist, 8, ctx->geodesic_group_pred > 0 ? ctx->geodesic_group_pred : 64, ctx->geodesic_group_permille, gq, st));
+      HIP_TRY(ccmp_launch::geo_split(sb.hist, 8, ctx->geodesic_group_pred > 0 ? ctx->geodesic_group_pred : 64, ctx->geodesic_group_permille, gq, st));
     else if (ctx->geodesic_group_pred > 0)
-      HIP_TRY(ccmp_launch_fd_split(sb.hist, ctx->geodesic_group_pred, 0xffffffffu, gq, st));
+      HIP_TRY(ccmp_launch::fd_split(sb.hist, ctx->geodesic_group_pred, 0xffffffffu, gq, st));
     // Fork.  From here on a failure no longer returns at once: whatever was queued on the side stream is joined back into the
     // caller's stream first (an early return left the side stream's kernels writing the caller's buffers unordered against
     // `st`), then the first error is reported.
     ForkJoin fj(ctx, st);
     fj.fork();
     CCMP_FAIL_AFTER_FORK(fj, 1);
-    FJ_STEP(fj, ccmp_launch_geodesic(&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok, newton_iters, check_target,
-                                     pl.front_blocks, gq + 5, order, carry_in, carry_out, round_budget, gq + 4, nullptr, nullptr, ctx->side));
+    FJ_STEP(fj, ccmp_launch::geodesic(g, {.blocks = pl.front_blocks, .queue = gq + kBFront, .order = order, .total = gq + kBFrontLen}, ctx->side));
     fj.side_done();
     CCMP_FAIL_AFTER_FORK(fj, 2);
-    FJ_STEP(fj, ccmp_launch_geodesic_group(&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok, newton_iters, (int)pl.group_waves, gq,
-                                           order, carry_out, round_budget, pct > 0 ? ctx->geo_pool : nullptr, gq + 6, pct, target_ok, st));
-    if (pct > 0) // the handed-over edges: latency blocks behind the group kernel; the pool's fill count is read on the device
-      FJ_STEP(fj, ccmp_launch_geodesic(&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok, newton_iters, 0, pl.drain_blocks, gq + 7,
-                                       nullptr, nullptr, carry_out, round_budget, nullptr, ctx->geo_pool, gq + 6, st));
+    FJ_STEP(fj, ccmp_launch::geodesic_group(g, (int)pl.group_waves, gq + kBTicket, order, pct > 0 ? ctx->geo_pool : nullptr, gq + kBPool, pct,
+                                            target_ok, st));
+    if (pct > 0) { // the handed-over edges: latency blocks behind the group kernel; the pool's fill count is read on the device
+      GeoCall drain = g; // the pool's records: not the call's targets to test, order or carries to read
+      drain.check_target = 0;
+      drain.carry_in = nullptr;
+      FJ_STEP(fj, ccmp_launch::geodesic(drain, {.blocks = pl.drain_blocks, .queue = gq + kBDrain, .order = nullptr, .pool = ctx->geo_pool,
+                                                .pool_count = gq + kBPool}, st));
+    }
     return fj.join();
   }
-  HIP_TRY((pl.latency_flavour ? ccmp_launch_geodesic_lat : ccmp_launch_geodesic)(&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok,
-                                                                                newton_iters, check_target, (int)pl.blocks, queue, order, carry_in,
-                                                                                carry_out, round_budget, nullptr, nullptr, nullptr, st));
+  HIP_TRY((pl.latency_flavour ? ccmp_launch::geodesic_lat : ccmp_launch::geodesic)(g, {.blocks = (int)pl.blocks, .queue = queue, .order = order}, st));
   return CCMP_OK;
 }
 
@@ -682,7 +578,7 @@ int ccmp_is_satisfied_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *
   if (B == 0) return CCMP_OK;
   if (!q || !ok) return CCMP_EINVAL;
   unsigned int *flag = arm_done_word(ctx, B);
-  HIP_TRY(ccmp_launch_is_satisfied(&K, q, ok, B, flag, ctx->done_seq, st));
+  HIP_TRY(ccmp_launch::is_satisfied(&K, q, ok, B, flag, ctx->done_seq, st));
   return CCMP_OK;
 }
 
@@ -692,7 +588,7 @@ int ccmp_joint_valid_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *q
   if (B == 0) return CCMP_OK;
   if (!q || !ok) return CCMP_EINVAL;
   unsigned int *flag = arm_done_word(ctx, B);
-  HIP_TRY(ccmp_launch_joint_valid(&K, q, ok, B, flag, ctx->done_seq, st));
+  HIP_TRY(ccmp_launch::joint_valid(&K, q, ok, B, flag, ctx->done_seq, st));
   return CCMP_OK;
 }
 
@@ -702,7 +598,7 @@ int ccmp_ambient_uniform_batch(ccmp_ctx *ctx, const ccmp_problem *p, uint64_t se
   CCMP_PROLOGUE();
   if (B == 0) return CCMP_OK;
   if (!q_out) return CCMP_EINVAL;
-  HIP_TRY(ccmp_launch_ambient_uniform(&K, seed, first_index, q_out, B, st));
+  HIP_TRY(ccmp_launch::ambient_uniform(&K, seed, first_index, q_out, B, st));
   return CCMP_OK;
 }
 
@@ -714,7 +610,7 @@ int ccmp_enforce_bounds_batch(ccmp_ctx *ctx, double *q, size_t B, void *hip_stre
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
-  HIP_TRY(ccmp_launch_enforce_bounds(q, B, st));
+  HIP_TRY(ccmp_launch::enforce_bounds(q, B, st));
   return CCMP_OK;
 }
 
@@ -732,21 +628,16 @@ int ccmp_compact_valid_capped(ccmp_ctx *ctx, const double *q, const uint8_t *ok,
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
   if (B == 0) {
-    HIP_TRY(ccmp_launch_clear_words(count_dev, 2, st));
+    HIP_TRY(ccmp_launch::clear_words(count_dev, 2, st));
     return CCMP_OK;
   }
   if (!q || !ok || !q_valid) return CCMP_EINVAL;
   const size_t nblocks = (B + 255) / 256;
-  if (ctx->scan_cap < nblocks) {
-    // growth happens outside any capture: callers that capture graphs call once un-captured first
-    ccmp_host::quiesce(ctx);
-    if (ctx->scan) (void)hipFree(ctx->scan);
-    ctx->scan = nullptr;
-    ctx->scan_cap = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->scan, nblocks * sizeof(unsigned int)));
-    ctx->scan_cap = nblocks;
+  {
+    int rc = grow(ctx, (void **)&ctx->scan, &ctx->scan_cap, nblocks, nblocks * sizeof(unsigned int)); // callers that capture graphs call once un-captured first
+    if (rc != CCMP_OK) return rc;
   }
-  HIP_TRY(ccmp_launch_compact(q, ok, B, q_valid, capacity, ctx->scan, (unsigned long long *)count_dev, st));
+  HIP_TRY(ccmp_launch::compact(q, ok, B, q_valid, capacity, ctx->scan, (unsigned long long *)count_dev, st));
   return CCMP_OK;
 }
 
@@ -758,7 +649,7 @@ int ccmp_detmath_probe(ccmp_ctx *ctx, const double *x_dev, const double *y_dev, 
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
   if (n == 0) return CCMP_OK;
-  HIP_TRY(ccmp_launch_detmath_probe(x_dev, y_dev, out_dev, n, st));
+  HIP_TRY(ccmp_launch::detmath_probe(x_dev, y_dev, out_dev, n, st));
   return CCMP_OK;
 }
 
@@ -769,7 +660,7 @@ int ccmp_detmath_div_probe(ccmp_ctx *ctx, const double *n_dev, const double *d_d
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
   if (count == 0) return CCMP_OK;
-  HIP_TRY(ccmp_launch_div_probe(n_dev, d_dev, out_dev, count, st));
+  HIP_TRY(ccmp_launch::div_probe(n_dev, d_dev, out_dev, count, st));
   return CCMP_OK;
 }
 #endif

@@ -19,10 +19,10 @@ inline int hip_fail(hipError_t e, const char *what)
   snprintf(g_hip_err, sizeof g_hip_err, "%s: %s", what, hipGetErrorString(e));
   return CCMP_EHIP;
 }
-#define HIP_TRY(call)                                            \
-  do {                                                           \
-    hipError_t e_ = (call);                                      \
-    if (e_ != hipSuccess) return ccmp_host::hip_fail(e_, #call); \
+#define HIP_TRY(...)                                                    \
+  do {                                                                  \
+    hipError_t e_ = (__VA_ARGS__);                                      \
+    if (e_ != hipSuccess) return ccmp_host::hip_fail(e_, #__VA_ARGS__); \
   } while (0)
 
 /* makes `dev` current for the lifetime of the guard and restores the previous device */
@@ -50,15 +50,20 @@ constexpr size_t kSplitWideMax = 24576;            // split launch: up to here t
 constexpr size_t kGeoGroupHighCut = 20480;         // bulk extend calls: the low cut of the order is 40 rounds below this many edges, 48 from here on ...
 constexpr size_t kGeoGroupLateHandoverFrom = 32768; // bulk extend calls: the group kernel hands over below 50 % occupancy up to here, below 80 % from here on (profiles/r05_bulk_handover_sweep.log)
 constexpr size_t kGeoGroupHigherCut = 65536;        // ... and 56 from here on (profiles/r05_low_cut_sweep.log: 65 536 edges -1.7 %, 131 072 -2.1 % against 48)
-constexpr int kGeoPoolDoubles = 40;                // = kGeoPoolEntry (ccmp_fd_common.h): one handed-over edge of the extend step's bulk form
-constexpr int kAnalyticWords = 64 + 2;            // ctx->queue + 8: 64 ticket words of the analytic mode's lane-pair kernel, the hand-over pool's fill count, the latency kernel's ticket word
-constexpr int kGeoAnalyticWord = 8 + kAnalyticWords;  // ctx->queue: the ticket word of the extend step in analytic mode (geodesic_row16_kernel)
-constexpr int kGeoGroupWords = kGeoAnalyticWord + 1;  // ctx->queue: first of the 8 words of the extend step's bulk form (behind the analytic kernels')
 constexpr size_t kDefaultLatencyOrderMin = 2049;   // latency kernel alone: FP32 scout order as soon as the blocks take tickets (more samples than blocks)
 constexpr size_t kDefaultLptMinBatch = 16384;      // throughput kernel: the scout's order pays from here on
 constexpr size_t kOccupancyHandoverBelow = 53248;  // below: the throughput kernel hands over by occupancy, from here on at once
 constexpr int kOccupancyHandoverValue = 10 + 70;   // "handover_threshold" encoding of that rule: 10 + per cent of the group slots (70 %)
 constexpr size_t kNoHandoverFrom = 131072;         // ordered batches of this size or more end on their shortest samples: no hand-over
+// fixed since round 6 (no option sets them any more)
+constexpr int kPoolLongRemaining = 24;             // two-class hand-over: samples with at least this many predicted iterations left go first
+constexpr int kLatencyBlocksPerCu = 8;             // the projector's latency kernel (and the extend step's throughput flavour): blocks per CU
+constexpr int kScoutPairBlocksPerCu = 1;           // the scout's two-lanes-per-sample form while every sample gets its pair at once
+constexpr size_t kScoutPairMaxEdges = 131072;      // extend step: the scout's two-lanes-per-edge form up to this many edges
+constexpr int kGeoBlocksPerCu = 4;                 // the extend step's latency flavour: blocks per CU
+constexpr int kGeoGroupHeavyPermille = 100;        // bulk extend calls: the front is the edges beyond the scout's cap if they carry this much of the work
+constexpr int kGeoGroupFrontPerCu = 8;             // bulk extend calls: latency blocks of the front per CU ...
+constexpr int kGeoGroupWavesPerCu = 8;             // ... and wavefronts of geodesic_group_kernel per CU
 
 // One execution context (include/ccmp.h).  The tuning members are reached by name through the option table of ccmp_policy.cpp
 // (ccmp_ctx_set_option / ccmp_ctx_get_option / ccmp_ctx_option_info), which also holds their ranges and one-line meanings; their
@@ -69,12 +74,12 @@ struct ccmp_ctx {
   hipStream_t stream = nullptr;        // internal stream of the *_host entry points
   hipStream_t side = nullptr;          // side stream of split launches (highest priority: a hardware queue of its own)
   hipEvent_t fork = nullptr, join = nullptr;
-  unsigned long long *queue = nullptr; // work-queue words: 0-2, 6-7 projector kernels, 3-4 extend step, 5 scout, 8.. analytic kernels, kGeoGroupWords.. bulk extend
+  unsigned long long *queue = nullptr; // work-queue words: ccmp_launch.h (QueueWord)
   double *pool = nullptr;              // straggler hand-over records (throughput kernel -> latency kernel)
   size_t pool_cap = 0;                 // in records
   void *lpt_buf = nullptr;             // pred (u16 x B) | hist (u32 x 1024) | order (u32 x B) | flags (u8 x B, bulk checkMotion)
   size_t lpt_cap = 0;                  // in samples
-  double *geo_pool = nullptr;          // bulk extend hand-over: kGeoPoolDoubles per edge
+  double *geo_pool = nullptr;          // bulk extend hand-over: kGeoPoolEntry doubles per edge
   size_t geo_pool_cap = 0;
   unsigned int *scan = nullptr;        // compaction block counts
   size_t scan_cap = 0;
@@ -105,8 +110,6 @@ struct ccmp_ctx {
   size_t lpt_min_batch = kDefaultLptMinBatch;
   size_t latency_order_min = kDefaultLatencyOrderMin;
   int dump_threshold = -1;             // "handover_threshold"
-  int pool_long_remaining = 24;
-  int latency_blocks_per_cu = 8;
   int fd_split = 1;
   size_t fd_split_min = 0, fd_split_max = 90112;
   int fd_split_pred = -1, fd_split_front = -1, fd_split_group_cut = -1;
@@ -114,16 +117,14 @@ struct ccmp_ctx {
   size_t analytic_small_batch = 8192;  // analytic mode: at or below, the sixteen-lanes-per-sample latency kernel alone
   int analytic_waves_per_cu = 12;      // ... persistent wavefronts of the lane-pair kernel per CU (142 registers, 13 KB of LDS: three per SIMD)
   int analytic_handover = 8;           // ... one of them hands over to the latency kernel once its tickets are gone and it holds at most this many samples (0: never)
-  int scout_pairs = 1, scout_pair_blocks_per_cu = 1;
-  size_t scout_pair_max_edges = 131072;
-  int geodesic_blocks_per_cu = 4, geodesic_flavour = 0, geodesic_order = 2;
+  int scout_pairs = 1;
+  int geodesic_flavour = 0, geodesic_order = 2;
   size_t geodesic_order_min = 2049, geodesic_scout_min = 2049; // (4096 / 6144 until round 5: the scout's order pays as soon as the blocks take tickets — tools/policy_check.py)
   int geodesic_scout_rounds = 64;
   double geodesic_long_steps = 12.0;
   int geodesic_group = 1;
   size_t geodesic_group_min = 13312;  // (16384 until round 5: tools/policy_check.py found the bulk form 10-12 % ahead at 15872 edges; crossover at 13312, profiles/r05_bulk_crossover.log)
-  int geodesic_group_pred = -1, geodesic_group_low_cut = -1, geodesic_group_heavy_permille = 100, geodesic_group_permille = 0;
-  int geodesic_group_front_per_cu = 8, geodesic_group_waves_per_cu = 8, geodesic_group_handover_pct = -1;
+  int geodesic_group_pred = -1, geodesic_group_low_cut = -1, geodesic_group_permille = 0, geodesic_group_handover_pct = -1;
   size_t clearance_per_state_max = 8192;
   int host_zero_copy = 2;
   int resident_idle_ms = 10;           // the resident service kernel leaves by itself after this long without a request
@@ -135,6 +136,15 @@ namespace ccmp_host {
 /* the pinned, device-mapped block of the small *_host calls: its last 64 bytes hold the completion word */
 constexpr size_t kPinBytes = 64 * 1024;
 constexpr size_t kPinData = kPinBytes - 64;
+/* single-state calls from the host entry points: the kernel publishes ctx->done_seq in the pinned block behind its result and
+ * HostIO::finish polls that word (nullptr: this launch does not publish) */
+inline unsigned int *arm_done_word(ccmp_ctx *ctx, size_t B)
+{
+  if (!ctx->want_done || B != 1 || !ctx->pin_dev) return nullptr;
+  ctx->done_seq++;
+  ctx->done_armed = true;
+  return (unsigned int *)((char *)ctx->pin_dev + kPinData);
+}
 /* device staging of the *_host conveniences, grown on demand */
 int ensure_stage(ccmp_ctx *ctx, size_t bytes);
 /* the device-visible alias of a caller's host range if all of it is page-locked and mapped (hipHostMalloc,

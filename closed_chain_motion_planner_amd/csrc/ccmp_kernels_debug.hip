@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ccmp_detmath.h"
+#include "ccmp_launch.h"
 
 namespace {
 
@@ -33,13 +34,13 @@ __global__ void div_probe_kernel(const double *__restrict__ num, const double *_
 
 } // namespace
 
-extern "C" hipError_t ccmp_launch_detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st)
+hipError_t ccmp_launch::detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st)
 {
   hipLaunchKernelGGL(detmath_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, out, n);
   return hipGetLastError();
 }
 
-extern "C" hipError_t ccmp_launch_div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st)
+hipError_t ccmp_launch::div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st)
 {
   hipLaunchKernelGGL(div_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, num, den, out, n);
   return hipGetLastError();

@@ -27,15 +27,16 @@
 #include <stdint.h>
 
 #include "ccmp_kin.h"
+#include "ccmp_launch.h"
 #include "ccmp_solve.h"
 
 using namespace ccmp;
+using ccmp_launch::kFastQueues; // ticket words of the lane-pair kernel
+using ccmp_launch::kPoolEntry;  // hand-over record
 
 namespace {
 
 constexpr int kConstsDoubles = (int)((sizeof(ccmp_consts) + 7) / 8);
-constexpr int kFastQueues = 64; // ticket words of the lane-pair kernel: one per lane of a wavefront (ccmp_ctx.h: kAnalyticWords)
-constexpr int kPoolEntry = 18;  // hand-over record: x[14], idx, (iter, updates), norm1, norm2 (as ccmp_fd_common.h)
 
 // value of the pair's even (arm 0) / odd (arm 1) lane in both lanes; the partner's value
 __device__ __forceinline__ double pair_even(double v)
@@ -703,27 +704,26 @@ __global__ __launch_bounds__(64, 2) void geodesic_row16_kernel(const ccmp_consts
 
 } // namespace
 
-extern "C" hipError_t ccmp_launch_clear_words(void *words, size_t n_u32, hipStream_t st); // ccmp_kernels_fd.hip
+namespace ccmp_launch {
 
 // One call of the analytic mode on one stream: the lane-pair kernel with pair_blocks wavefronts (0: none) and behind it, or
 // alone, the latency kernel with latency_blocks wavefronts (0: none).  With both, a wavefront of the lane-pair kernel whose
 // tickets are used up and that holds at most dump_below samples hands them over through `pool` (kPoolEntry doubles per
 // sample; the fill count is read on the device: surplus wavefronts of the latency kernel exit at once).  queue: kFastQueues
 // ticket words of the lane-pair kernel, the pool's fill count, the ticket word of the latency kernel.
-extern "C" hipError_t ccmp_launch_project_analytic(const ccmp_consts *K, int mode, const double *q_in, double *q_out, uint8_t *ok,
-                                                   uint16_t *iters, double *q_ambient, size_t B, unsigned long long *queue,
-                                                   unsigned long long seed, unsigned long long first, int pair_blocks, int dump_below,
-                                                   int latency_blocks, double *pool, hipStream_t st)
+hipError_t project_analytic(const ProjectCall &c, int pair_blocks, int dump_below, int latency_blocks, double *pool,
+                            unsigned long long *queue, hipStream_t st)
 {
   if (pair_blocks <= 0 && latency_blocks <= 0) return hipErrorInvalidValue;
-  hipError_t e = ccmp_launch_clear_words(queue, (kFastQueues + 2) * 2, st); // a kernel, so that a stream capture replays it
+  hipError_t e = clear_words(queue, (kFastQueues + 2) * 2, st); // a kernel, so that a stream capture replays it
   if (e != hipSuccess) return e;
+  const ccmp_consts *K = c.K;
   unsigned long long *count = queue + kFastQueues, *lat_tickets = queue + kFastQueues + 1;
   const bool both = pair_blocks > 0 && latency_blocks > 0;
   if (pair_blocks > 0) {
 #define CCMP_LAUNCH_PAIR(STOCK, TWIN)                                                                                                  \
-  hipLaunchKernelGGL((project_pair_kernel<STOCK, TWIN>), dim3(pair_blocks), dim3(64), 0, st, *K, mode | (mode << 4), q_in, q_out, ok, iters, \
-                     q_ambient, (unsigned long long)B, queue, seed, first, both ? pool : nullptr, count, dump_below)
+  hipLaunchKernelGGL((project_pair_kernel<STOCK, TWIN>), dim3(pair_blocks), dim3(64), 0, st, *K, c.mode | (c.mode << 4), c.q_in, c.q_out, c.ok, \
+                     c.iters, c.q_ambient, (unsigned long long)c.B, queue, c.seed, c.first, both ? pool : nullptr, count, dump_below)
     if (K->twin_arms) CCMP_LAUNCH_PAIR(true, true);
     else if (K->stock) CCMP_LAUNCH_PAIR(true, false);
     else CCMP_LAUNCH_PAIR(false, false);
@@ -732,32 +732,31 @@ extern "C" hipError_t ccmp_launch_project_analytic(const ccmp_consts *K, int mod
   if (latency_blocks > 0) {
     // srcmode: low nibble = where the samples come from (2: the pool), high nibble = the call's mode (a sample of a fused
     // sampleUniform is wrapped by whichever kernel finishes it)
-    const int srcmode = (both ? 2 : mode) | (mode << 4);
+    const int srcmode = (both ? 2 : c.mode) | (c.mode << 4);
     if (K->base_diag == 3)
-      hipLaunchKernelGGL((project_row16_kernel<true>), dim3(latency_blocks), dim3(64), 0, st, *K, srcmode, q_in, q_out, ok, iters, q_ambient,
-                         (unsigned long long)B, lat_tickets, seed, first, pool, count);
+      hipLaunchKernelGGL((project_row16_kernel<true>), dim3(latency_blocks), dim3(64), 0, st, *K, srcmode, c.q_in, c.q_out, c.ok, c.iters,
+                         c.q_ambient, (unsigned long long)c.B, lat_tickets, c.seed, c.first, pool, count);
     else
-      hipLaunchKernelGGL((project_row16_kernel<false>), dim3(latency_blocks), dim3(64), 0, st, *K, srcmode, q_in, q_out, ok, iters, q_ambient,
-                         (unsigned long long)B, lat_tickets, seed, first, pool, count);
+      hipLaunchKernelGGL((project_row16_kernel<false>), dim3(latency_blocks), dim3(64), 0, st, *K, srcmode, c.q_in, c.q_out, c.ok, c.iters,
+                         c.q_ambient, (unsigned long long)c.B, lat_tickets, c.seed, c.first, pool, count);
   }
   return hipGetLastError();
 }
 
 // The extend step in analytic mode, one call on one stream: the ticket word cleared (a kernel, so that a stream capture replays it),
 // then geodesic_row16_kernel with `blocks` wavefronts (four edges each at a time).
-extern "C" hipError_t ccmp_launch_geodesic_analytic(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to, size_t E,
-                                                    int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters,
-                                                    const double *carry_in, double *carry_out, int round_budget, int check_target, int blocks,
-                                                    unsigned long long *queue, hipStream_t st)
+hipError_t geodesic_analytic(const GeoCall &g, int blocks, unsigned long long *queue, hipStream_t st)
 {
   if (blocks <= 0) return hipErrorInvalidValue;
-  hipError_t e = ccmp_launch_clear_words(queue, 2, st);
+  hipError_t e = clear_words(queue, 2, st);
   if (e != hipSuccess) return e;
-#define CCMP_LAUNCH_GEO_ROW16(DIAG)                                                                                                     \
-  hipLaunchKernelGGL((geodesic_row16_kernel<DIAG>), dim3(blocks), dim3(64), 0, st, *K, delta, lambda, from, to, (unsigned long long)E, \
-                     max_states, states, n_states, ok, newton_iters, carry_in, carry_out, round_budget, check_target, queue)
-  if (K->base_diag == 3) CCMP_LAUNCH_GEO_ROW16(true);
+#define CCMP_LAUNCH_GEO_ROW16(DIAG)                                                                                                       \
+  hipLaunchKernelGGL((geodesic_row16_kernel<DIAG>), dim3(blocks), dim3(64), 0, st, *g.K, g.delta, g.lambda, g.from, g.to, (unsigned long long)g.E, \
+                     g.max_states, g.states, g.n_states, g.ok, g.newton_iters, g.carry_in, g.carry_out, g.round_budget, g.check_target, queue)
+  if (g.K->base_diag == 3) CCMP_LAUNCH_GEO_ROW16(true);
   else CCMP_LAUNCH_GEO_ROW16(false);
 #undef CCMP_LAUNCH_GEO_ROW16
   return hipGetLastError();
 }
+
+}  // namespace ccmp_launch

@@ -979,46 +979,41 @@ __global__ void compact_scatter_kernel(const double *__restrict__ q, const uint8
 
 } // namespace
 
-// ---- launchers (called from ccmp_api.cpp) --------------------------------------------------------
-extern "C" {
+// ---- launchers (ccmp_launch.h) ---------------------------------------------------------------------------------------------
+namespace ccmp_launch {
 
 // the extend step's short edges on the throughput layout (geodesic_group_kernel): one-wavefront workgroups, ten edges each
-hipError_t ccmp_launch_geodesic_group(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to, size_t E,
-                                      int max_states, double *states, int *n_states, uint8_t *ok, int *newton_iters, int nblocks,
-                                      unsigned long long *queue, const unsigned int *order, double *carry_out, int round_budget,
-                                      double *pool, unsigned long long *pool_count, int handover_pct, const uint8_t *target_ok, hipStream_t st)
+hipError_t geodesic_group(const GeoCall &g, int blocks, unsigned long long *queue, const unsigned int *order, double *pool,
+                          unsigned long long *pool_count, int handover_pct, const uint8_t *target_ok, hipStream_t st)
 {
-  if (K->stock && K->twin_arms) // the STOCK instantiation also assumes twin arms on diag(+-1) base frames (chain_rows), like project_fd_kernel's
-    hipLaunchKernelGGL(geodesic_group_kernel<true>, dim3(nblocks), dim3(64), 0, st, *K, delta, lambda, from, to, (unsigned long long)E,
-                       max_states, states, n_states, ok, newton_iters, queue, order, carry_out, round_budget, pool, pool_count, handover_pct, target_ok);
+  if (g.K->stock && g.K->twin_arms) // the STOCK instantiation also assumes twin arms on diag(+-1) base frames (chain_rows), like project_fd_kernel's
+    hipLaunchKernelGGL(geodesic_group_kernel<true>, dim3(blocks), dim3(64), 0, st, *g.K, g.delta, g.lambda, g.from, g.to, (unsigned long long)g.E,
+                       g.max_states, g.states, g.n_states, g.ok, g.newton_iters, queue, order, g.carry_out, g.round_budget, pool, pool_count, handover_pct, target_ok);
   else
-    hipLaunchKernelGGL(geodesic_group_kernel<false>, dim3(nblocks), dim3(64), 0, st, *K, delta, lambda, from, to, (unsigned long long)E,
-                       max_states, states, n_states, ok, newton_iters, queue, order, carry_out, round_budget, pool, pool_count, handover_pct, target_ok);
+    hipLaunchKernelGGL(geodesic_group_kernel<false>, dim3(blocks), dim3(64), 0, st, *g.K, g.delta, g.lambda, g.from, g.to, (unsigned long long)g.E,
+                       g.max_states, g.states, g.n_states, g.ok, g.newton_iters, queue, order, g.carry_out, g.round_budget, pool, pool_count, handover_pct, target_ok);
   return hipGetLastError();
 }
 
-hipError_t ccmp_launch_clear_words(void *words, size_t n_u32, hipStream_t st)
+hipError_t clear_words(void *words, size_t n_u32, hipStream_t st)
 {
   hipLaunchKernelGGL(clear_words_kernel, dim3((unsigned)((n_u32 + 255) / 256)), dim3(256), 0, st, (unsigned int *)words, (unsigned int)n_u32);
   return hipGetLastError();
 }
 
-hipError_t ccmp_launch_project_group(const ccmp_consts *K, int mode, const double *q_in, double *q_out, uint8_t *ok,
-                                     uint16_t *iters, double *q_ambient, size_t B, unsigned long long *queue,
-                                     unsigned long long seed, unsigned long long first, int nblocks, double *pool,
-                                     int dump_threshold, const unsigned int *order, const uint16_t *pred, int long_remaining,
-                                     size_t pool_records, hipStream_t st)
+// queue: the projector's block of queue words (kQTicket: this kernel's samples, kQPool: the pool's fill count)
+hipError_t project_group(const ProjectCall &c, int blocks, unsigned long long *queue, double *pool, int dump_threshold,
+                         const unsigned int *order, const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st)
 {
-  // queue[0]: sample queue of this kernel; queue[1]: pool fill count (front); queue[6]: pool fill count from the back
-#define CCMP_LAUNCH_GROUP(MODE, STOCK)                                                                                        \
-  hipLaunchKernelGGL((project_fd_kernel<MODE, STOCK>), dim3(nblocks), dim3(64), 0, st, *K, q_in, q_out, ok, iters, q_ambient, \
-                     (unsigned long long)B, queue, seed, first, pool, queue + 1, dump_threshold, order, pred, long_remaining, \
-                     (unsigned long long)pool_records)
-  if (mode == 0) {
-    if (K->stock && K->twin_arms) CCMP_LAUNCH_GROUP(0, true);
+#define CCMP_LAUNCH_GROUP(MODE, STOCK)                                                                                                    \
+  hipLaunchKernelGGL((project_fd_kernel<MODE, STOCK>), dim3(blocks), dim3(64), 0, st, *c.K, c.q_in, c.q_out, c.ok, c.iters, c.q_ambient, \
+                     (unsigned long long)c.B, queue + kQTicket, c.seed, c.first, pool, queue + kQPool, dump_threshold, order, pred,       \
+                     long_remaining, (unsigned long long)pool_records)
+  if (c.mode == 0) {
+    if (c.K->stock && c.K->twin_arms) CCMP_LAUNCH_GROUP(0, true);
     else CCMP_LAUNCH_GROUP(0, false);
   } else {
-    if (!(K->stock && K->twin_arms)) return hipErrorInvalidValue; // the fused sampler exists for the stock structure only (ccmp_api.cpp: project_common)
+    if (!(c.K->stock && c.K->twin_arms)) return hipErrorInvalidValue; // the fused sampler exists for the stock structure only (ccmp_api.cpp: project_common)
     CCMP_LAUNCH_GROUP(1, true);
   }
 #undef CCMP_LAUNCH_GROUP
@@ -1026,36 +1021,34 @@ hipError_t ccmp_launch_project_group(const ccmp_consts *K, int mode, const doubl
 }
 
 // done_flag (nullable) is honoured for B == 1 only: the single working thread publishes done_seq behind its result
-hipError_t ccmp_launch_function(const ccmp_consts *K, const double *q, double *f, size_t B, unsigned int *done_flag,
-                                unsigned int done_seq, hipStream_t st)
+hipError_t function(const ccmp_consts *K, const double *q, double *f, size_t B, unsigned int *done_flag, unsigned int done_seq, hipStream_t st)
 {
   if (B != 1) done_flag = nullptr;
   hipLaunchKernelGGL(function_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, *K, q, f, B, done_flag, done_seq);
   return hipGetLastError();
 }
-hipError_t ccmp_launch_is_satisfied(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag,
-                                    unsigned int done_seq, hipStream_t st)
+hipError_t is_satisfied(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag, unsigned int done_seq,
+                        hipStream_t st)
 {
   if (B != 1) done_flag = nullptr;
   hipLaunchKernelGGL(is_satisfied_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, *K, q, ok, B, done_flag, done_seq);
   return hipGetLastError();
 }
-hipError_t ccmp_launch_joint_valid(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag,
-                                   unsigned int done_seq, hipStream_t st)
+hipError_t joint_valid(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag, unsigned int done_seq,
+                       hipStream_t st)
 {
   if (B != 1) done_flag = nullptr;
   hipLaunchKernelGGL(joint_valid_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, *K, q, ok, B, done_flag, done_seq);
   return hipGetLastError();
 }
-hipError_t ccmp_launch_ambient_uniform(const ccmp_consts *K, unsigned long long seed, unsigned long long first,
-                                       double *q, size_t B, hipStream_t st)
+hipError_t ambient_uniform(const ccmp_consts *K, unsigned long long seed, unsigned long long first, double *q, size_t B, hipStream_t st)
 {
   size_t n = B * 14;
   hipLaunchKernelGGL(ambient_uniform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *K, seed, first, q, n);
   return hipGetLastError();
 }
-hipError_t ccmp_launch_ambient_ref(const ccmp_consts *K, int kind, unsigned long long seed, unsigned long long first,
-                                   const double *ref, int ref_stride, double param, double *q, size_t B, hipStream_t st)
+hipError_t ambient_ref(const ccmp_consts *K, int kind, unsigned long long seed, unsigned long long first, const double *ref, int ref_stride,
+                       double param, double *q, size_t B, hipStream_t st)
 {
   size_t n = B * 14;
   if (kind == 0)
@@ -1066,19 +1059,19 @@ hipError_t ccmp_launch_ambient_ref(const ccmp_consts *K, int kind, unsigned long
                        ref_stride, param, q, n);
   return hipGetLastError();
 }
-hipError_t ccmp_launch_t_wo(const ccmp_consts *K, const double *q, int q_stride, double *out, size_t B, hipStream_t st)
+hipError_t t_wo(const ccmp_consts *K, const double *q, int q_stride, double *out, size_t B, hipStream_t st)
 {
   hipLaunchKernelGGL(t_wo_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, *K, q, q_stride, out, B);
   return hipGetLastError();
 }
-hipError_t ccmp_launch_enforce_bounds(double *q, size_t B, hipStream_t st)
+hipError_t enforce_bounds(double *q, size_t B, hipStream_t st)
 {
   size_t n = B * 14;
   hipLaunchKernelGGL(enforce_bounds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, n);
   return hipGetLastError();
 }
-hipError_t ccmp_launch_compact(const double *q, const uint8_t *ok, size_t B, double *out, size_t capacity,
-                               unsigned int *block_counts, unsigned long long *total, hipStream_t st)
+hipError_t compact(const double *q, const uint8_t *ok, size_t B, double *out, size_t capacity, unsigned int *block_counts,
+                   unsigned long long *total, hipStream_t st)
 {
   const size_t nblocks = (B + 255) / 256;
   hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, ok, B, block_counts);
@@ -1087,4 +1080,4 @@ hipError_t ccmp_launch_compact(const double *q, const uint8_t *ok, size_t B, dou
   return hipGetLastError();
 }
 
-} // extern "C"
+}  // namespace ccmp_launch

@@ -108,37 +108,36 @@ __global__ __launch_bounds__(128, CCMP_FLAT_MIN_WAVES) void project_fd_flat_kern
 
 } // namespace
 
-extern "C" {
+namespace ccmp_launch {
 
-
-// one sample per 128-thread block, all evaluations of an iteration in one round; queue_head may be NULL (static striding)
-hipError_t ccmp_launch_project_flat(const ccmp_consts *K, int src, const double *q_in, double *q_out, uint8_t *ok,
-                                    uint16_t *iters, double *q_ambient, size_t B, unsigned long long *queue_head,
-                                    unsigned long long seed, unsigned long long first, const double *pool,
-                                    const unsigned long long *pool_count, int wrap_output, int nblocks, unsigned int *done_flag,
-                                    unsigned int done_seq, size_t pool_records, const unsigned int *order,
-                                    const unsigned long long *total_ptr, hipStream_t st)
+// one sample per 128-thread block, all evaluations of an iteration in one round
+hipError_t project_flat(const ProjectCall &c, const FlatLaunch &l, hipStream_t st)
 {
+  const int src = l.from_pool ? 2 : c.mode;
   // the latency kernel alone (no pool, no front of a split launch): the whole grid is resident at once — static first tickets
-  const int static_first = (src != 2 && total_ptr == nullptr) ? 1 : 0;
-  if (nblocks != 1) done_flag = nullptr; // the completion word is written by the one block of a single-state call
-#define CCMP_LAUNCH_FLAT(SRC, STOCK)                                                                                             \
-  hipLaunchKernelGGL((project_fd_flat_kernel<SRC, STOCK>), dim3(nblocks), dim3(128), 0, st, *K, q_in, q_out, ok, iters, q_ambient, \
-                     (unsigned long long)B, queue_head, seed, first, pool, pool_count, wrap_output, done_flag, done_seq, \
-                     (unsigned long long)pool_records, order, total_ptr, static_first)
+  const int static_first = (src != 2 && l.total == nullptr) ? 1 : 0;
+  unsigned int *const done_flag = l.blocks == 1 ? l.done_flag : nullptr; // the completion word is written by the one block of a single-state call
+#define CCMP_LAUNCH_FLAT(SRC, STOCK)                                                                                                    \
+  hipLaunchKernelGGL((project_fd_flat_kernel<SRC, STOCK>), dim3(l.blocks), dim3(128), 0, st, *c.K, c.q_in, c.q_out, c.ok, c.iters, c.q_ambient, \
+                     (unsigned long long)c.B, l.queue, c.seed, c.first, l.pool, l.pool_count, c.mode, done_flag, l.done_seq,             \
+                     (unsigned long long)l.pool_records, l.order, l.total, static_first)
   if (src == 0) {
-    if (K->stock) CCMP_LAUNCH_FLAT(0, true);
+    if (c.K->stock) CCMP_LAUNCH_FLAT(0, true);
     else CCMP_LAUNCH_FLAT(0, false);
   } else if (src == 1) {
-    if (!K->stock) return hipErrorInvalidValue; // the fused sampler exists for the stock structure only (ccmp_api.cpp: project_common)
+    if (!c.K->stock) return hipErrorInvalidValue; // the fused sampler exists for the stock structure only (ccmp_api.cpp: project_common)
     CCMP_LAUNCH_FLAT(1, true);
   } else {
-    if (K->stock) CCMP_LAUNCH_FLAT(2, true);
+    if (c.K->stock) CCMP_LAUNCH_FLAT(2, true);
     else CCMP_LAUNCH_FLAT(2, false);
   }
 #undef CCMP_LAUNCH_FLAT
   return hipGetLastError();
 }
+
+}  // namespace ccmp_launch
+
+extern "C" {
 
 #ifdef CCMP_GEO_TRACE
 hipError_t ccmp_debug_flat_trace(unsigned long long *out, size_t n_edges)

@@ -1,9 +1,9 @@
 // ccmp_kernels_geo.hip — the extend step (jy_ProjectedStateSpace::discreteGeodesic) on the latency kernels' Newton
 // routine (ccmp_flat_newton.h).  One source, two objects (build.py):
-//  * throughput flavour (ccmp_launch_geodesic) — the projector's latency kernel's flags: 128 registers, eight blocks per
+//  * throughput flavour (ccmp_launch::geodesic) — the projector's latency kernel's flags: 128 registers, eight blocks per
 //    CU.  For calls that bound the Newton rounds per edge (ccmp_geodesic_batch_ex, round_budget > 0): such a launch is
 //    bound by how many rounds the chip turns over, and occupancy is what buys that.
-//  * latency flavour (-DCCMP_GEO_LATENCY: ccmp_launch_geodesic_lat) — machine LICM on and a 256-register budget, four
+//  * latency flavour (-DCCMP_GEO_LATENCY: ccmp_launch::geodesic_lat) — machine LICM on and a 256-register budget, four
 //    blocks per CU: the ~60 FP64 literals of a Newton round live in registers instead of being re-materialised every round
 //    (two moves each; 8 % fewer instructions per round).  For calls that end on ONE edge's serial chain — no round
 //    budget, or no more edges than blocks.  In-process A/B, 16 384 near-neighbour edges, lists of 16: without a budget
@@ -125,40 +125,38 @@ __global__ void geodesic_order_kernel(const double *__restrict__ from, const dou
 
 } // namespace
 
-extern "C" {
+namespace ccmp_launch {
 
 #ifdef CCMP_GEO_LATENCY
-#define CCMP_LAUNCH_GEODESIC ccmp_launch_geodesic_lat
+hipError_t geodesic_lat(const GeoCall &g, const GeoLaunch &l, hipStream_t st)
 #else
-#define CCMP_LAUNCH_GEODESIC ccmp_launch_geodesic
+hipError_t geodesic(const GeoCall &g, const GeoLaunch &l, hipStream_t st)
 #endif
-hipError_t CCMP_LAUNCH_GEODESIC(const ccmp_consts *K, double delta, double lambda, const double *from, const double *to,
-                                size_t E, int max_states, double *states, int *n_states, uint8_t *ok, int *newton_iters,
-                                int check_target, int nblocks, unsigned long long *queue, const unsigned int *order,
-                                const double *carry_in, double *carry_out, int round_budget, const unsigned long long *total_ptr,
-                                const double *pool, const unsigned long long *pool_count, hipStream_t st)
 {
-  const int static_first = (pool == nullptr && total_ptr == nullptr) ? 1 : 0; // alone on the chip: neither front nor hand-over of a bulk call
-  if (K->stock)
-    hipLaunchKernelGGL(geodesic_flat_kernel<true>, dim3(nblocks), dim3(128), 0, st, *K, delta, lambda, from, to, (unsigned long long)E,
-                       max_states, states, n_states, ok, newton_iters, check_target, queue, order, carry_in, carry_out, round_budget, total_ptr, pool, pool_count, static_first);
+  const int static_first = (l.pool == nullptr && l.total == nullptr) ? 1 : 0; // alone on the chip: neither front nor hand-over of a bulk call
+  if (g.K->stock)
+    hipLaunchKernelGGL(geodesic_flat_kernel<true>, dim3(l.blocks), dim3(128), 0, st, *g.K, g.delta, g.lambda, g.from, g.to, (unsigned long long)g.E,
+                       g.max_states, g.states, g.n_states, g.ok, g.newton_iters, g.check_target, l.queue, l.order, g.carry_in, g.carry_out, g.round_budget, l.total, l.pool, l.pool_count, static_first);
   else
-    hipLaunchKernelGGL(geodesic_flat_kernel<false>, dim3(nblocks), dim3(128), 0, st, *K, delta, lambda, from, to, (unsigned long long)E,
-                       max_states, states, n_states, ok, newton_iters, check_target, queue, order, carry_in, carry_out, round_budget, total_ptr, pool, pool_count, static_first);
+    hipLaunchKernelGGL(geodesic_flat_kernel<false>, dim3(l.blocks), dim3(128), 0, st, *g.K, g.delta, g.lambda, g.from, g.to, (unsigned long long)g.E,
+                       g.max_states, g.states, g.n_states, g.ok, g.newton_iters, g.check_target, l.queue, l.order, g.carry_in, g.carry_out, g.round_budget, l.total, l.pool, l.pool_count, static_first);
   return hipGetLastError();
 }
 
 #ifndef CCMP_GEO_LATENCY
 // counters: two zeroed words; order: E words
-hipError_t ccmp_launch_geodesic_order(const double *from, const double *to, size_t E, double long_dist, unsigned int *counters,
-                                      unsigned int *order, hipStream_t st)
+hipError_t geodesic_order(const double *from, const double *to, size_t E, double long_dist, unsigned int *counters, unsigned int *order,
+                          hipStream_t st)
 {
   hipLaunchKernelGGL(geodesic_order_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, from, to, (unsigned long long)E,
                      long_dist * long_dist, counters, order);
   return hipGetLastError();
 }
-
 #endif
+
+}  // namespace ccmp_launch
+
+extern "C" {
 
 #ifdef CCMP_GEO_TRACE
 #ifdef CCMP_GEO_LATENCY

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(128, 1) void resident_service_kernel(unsigned long 
 
 } // namespace
 
-extern "C" hipError_t ccmp_launch_resident(int stock, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st)
+hipError_t ccmp_launch::resident(int stock, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st)
 {
   if (stock)
     hipLaunchKernelGGL(resident_service_kernel<true>, dim3(1), dim3(128), 0, st, (unsigned long long *)box_dev, last_tag, idle_ticks);

@@ -341,17 +341,17 @@ __global__ __launch_bounds__(256) void clearance_state_kernel(const ccmp_consts 
 
 } // namespace
 
-extern "C" {
+namespace ccmp_launch {
 
-size_t ccmp_clearance_lds_bytes(int n_spheres)
+size_t clearance_lds_bytes(int n_spheres)
 {
   return (size_t)n_spheres * 3 * kTile * sizeof(double) + kTileWaves * kTile * sizeof(double) + 2 * kTileWaves * kTile * sizeof(int);
 }
 
 // per_state != 0: one block per state (small batches, nblocks <= B); done_flag (nullable) is honoured for B == 1 only
-hipError_t ccmp_launch_clearance(const ccmp_consts *K, const scene_dev *scene_dev_ptr, int n_spheres, int n_pairs, const double *q, const uint8_t *ok_in,
-                                 size_t B, double margin, double *clearance, int32_t *pair, uint8_t *free_out, int nblocks, int per_state,
-                                 unsigned int *done_flag, unsigned int done_seq, hipStream_t st)
+hipError_t clearance(const ccmp_consts *K, const scene_dev *scene_dev_ptr, int n_spheres, int n_pairs, const double *q, const uint8_t *ok_in,
+                     size_t B, double margin, double *clearance, int32_t *pair, uint8_t *free_out, int nblocks, int per_state,
+                     unsigned int *done_flag, unsigned int done_seq, hipStream_t st)
 {
   if (per_state) {
     if (B != 1) done_flag = nullptr;
@@ -359,7 +359,7 @@ hipError_t ccmp_launch_clearance(const ccmp_consts *K, const scene_dev *scene_de
                        clearance, pair, free_out, done_flag, done_seq);
     return hipGetLastError();
   }
-  const size_t lds = ccmp_clearance_lds_bytes(n_spheres);
+  const size_t lds = clearance_lds_bytes(n_spheres);
   if (lds > 64 * 1024) { // per device and function; cheap, but not free: asked once per size class and thread
     static thread_local size_t granted = 0;
     static thread_local int granted_dev = -1;
@@ -383,4 +383,4 @@ hipError_t ccmp_launch_clearance(const ccmp_consts *K, const scene_dev *scene_de
   return hipGetLastError();
 }
 
-} // extern "C"
+}  // namespace ccmp_launch

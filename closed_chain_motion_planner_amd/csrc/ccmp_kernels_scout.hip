@@ -14,7 +14,7 @@
 #include <stdint.h>
 
 #include "ccmp_kin.h" // ccmp_consts, ambient_uniform (double, so that MODE 1 sees the same samples)
-#include "ccmp_split.h"
+#include "ccmp_launch.h"
 
 namespace {
 
@@ -692,7 +692,7 @@ __global__ void hist_kernel(const uint16_t *__restrict__ pred, unsigned long lon
     if (h[k]) atomicAdd(&hist[k], h[k]);
 }
 
-// The cut of the order for a split launch (ccmp_split.h), by ONE wavefront of the sort's own kernel: ge[k] = number of keys >= k for
+// The cut of the order for a split launch (ccmp_launch.h: ccmp_split_req), by ONE wavefront of the sort's own kernel: ge[k] = number of keys >= k for
 // every k < kBins (LDS).  Kind 1 is fd_split_kernel's rule (below: it remains for the option sets that fix the
 // cut themselves), kind 2 the extend step's default (described at geo_split_kernel).
 __device__ __forceinline__ void apply_split(const unsigned int *ge, const ccmp_split_req &req, int lane)
@@ -838,16 +838,6 @@ __global__ __launch_bounds__(1024) void sort_fused_kernel(const uint16_t *__rest
 }
 static_assert(kBins == 1024, "sort_fused_kernel: one thread per bin");
 
-// after scatter_kernel the cursor array holds, at k, the number of samples predicted >= k iterations: the front of
-// the order that a split launch gives to the latency kernel = those predicted >= pred_min, at most `limit`
-__global__ void split_kernel(const unsigned int *__restrict__ hist, int pred_min, unsigned int limit, unsigned int *__restrict__ out)
-{
-  if (threadIdx.x == 0) {
-    const unsigned int n = hist[pred_min < kBins ? pred_min : kBins - 1];
-    *out = n < limit ? n : limit;
-  }
-}
-
 // The split launch of the reference-arithmetic path (mid-size batches, ccmp_api.cpp): the front of the descending order — the
 // samples predicted >= pred_min iterations, at most `limit` — goes to latency blocks BESIDE the throughput kernel.  queue[4]:
 // the front's length (the latency blocks' ticket limit); queue[0]: the throughput kernel's queue starts behind the front;
@@ -901,26 +891,6 @@ __global__ __launch_bounds__(64) void geo_split_kernel(const unsigned int *__res
 
 } // namespace
 
-extern "C" hipError_t ccmp_launch_clear_words(void *words, size_t n_u32, hipStream_t st); // ccmp_kernels_fd.hip
-
-extern "C" hipError_t ccmp_launch_geo_split(const unsigned int *hist, int p_min, int p_max, int permille, unsigned long long *queue, hipStream_t st)
-{
-  hipLaunchKernelGGL(geo_split_kernel, dim3(1), dim3(64), 0, st, hist, p_min, p_max, permille, queue);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ccmp_launch_fd_split(const unsigned int *hist, int pred_min, unsigned int limit, unsigned long long *queue, hipStream_t st)
-{
-  hipLaunchKernelGGL(fd_split_kernel, dim3(1), dim3(64), 0, st, hist, pred_min, limit, queue);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ccmp_launch_split_count(const unsigned int *hist, int pred_min, unsigned int limit, unsigned int *out, hipStream_t st)
-{
-  hipLaunchKernelGGL(split_kernel, dim3(1), dim3(64), 0, st, hist, pred_min, limit, out);
-  return hipGetLastError();
-}
-
 // single-precision copy of the kernel constants; *stock = the model looks like the stock Panda to single precision (axes
 // on coordinate axes, the expected zero offsets, block-diagonal tool rotation, diagonal base rotation) — only the
 // prediction depends on it
@@ -959,11 +929,25 @@ static void make_consts_f(const ccmp_consts *K, consts_f &F, bool *stock_out)
   *stock_out = stock;
 }
 
-extern "C" hipError_t ccmp_launch_scout_order(const ccmp_consts *K, int mode, const double *q_in, size_t B, uint16_t *pred,
-                                              unsigned int *hist, unsigned int *order, unsigned long long *queue,
-                                              unsigned long long seed, unsigned long long first, int nblocks, int pair_max_blocks,
-                                              const ccmp_split_req *split, hipStream_t st)
+namespace ccmp_launch {
+
+hipError_t geo_split(const unsigned int *hist, int p_min, int p_max, int permille, unsigned long long *queue, hipStream_t st)
 {
+  hipLaunchKernelGGL(geo_split_kernel, dim3(1), dim3(64), 0, st, hist, p_min, p_max, permille, queue);
+  return hipGetLastError();
+}
+
+hipError_t fd_split(const unsigned int *hist, int pred_min, unsigned int limit, unsigned long long *queue, hipStream_t st)
+{
+  hipLaunchKernelGGL(fd_split_kernel, dim3(1), dim3(64), 0, st, hist, pred_min, limit, queue);
+  return hipGetLastError();
+}
+
+hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist, unsigned int *order, unsigned long long *queue, int blocks,
+                       int pair_max_blocks, const ccmp_split_req *split, hipStream_t st)
+{
+  const ccmp_consts *K = c.K;
+  const size_t B = c.B;
   const ccmp_split_req sr = split ? *split : ccmp_split_req{nullptr, 0, 0, 0, 0, 0u, 0};
   consts_f F;
   bool stock;
@@ -971,23 +955,23 @@ extern "C" hipError_t ccmp_launch_scout_order(const ccmp_consts *K, int mode, co
   const bool fused = B <= (size_t)kSortFusedMax; // the fused sort writes every bin itself: nothing to clear
   hipError_t e = hipSuccess;
 #ifdef CCMP_SCOUT_ATOMIC_QUEUE
-  e = ccmp_launch_clear_words(queue, 2, st); // kernels, so that a stream capture replays them
+  e = clear_words(queue, 2, st); // kernels, so that a stream capture replays them
   if (e != hipSuccess) return e;
 #endif
   if (!fused) {
-    e = ccmp_launch_clear_words(hist, kBins, st);
+    e = clear_words(hist, kBins, st);
     if (e != hipSuccess) return e;
   }
 #define CCMP_LAUNCH_SCOUT(MODE, STOCK) \
-  hipLaunchKernelGGL((scout_kernel<MODE, STOCK>), dim3(nblocks), dim3(256), 0, st, F, *K, q_in, pred, (unsigned long long)B, queue, seed, first)
+  hipLaunchKernelGGL((scout_kernel<MODE, STOCK>), dim3(blocks), dim3(256), 0, st, F, *K, c.q_in, pred, (unsigned long long)B, queue, c.seed, c.first)
   // two lanes per sample while every sample still gets its pair at once (pair_max_blocks blocks of 128 pairs); larger batches
   // keep one lane per sample, several samples per lane
   const size_t pair_blocks = (2 * B + 255) / 256;
   if (stock && K->twin_arms && pair_max_blocks > 0 && pair_blocks <= (size_t)pair_max_blocks) {
-    if (mode == 0) hipLaunchKernelGGL(scout_pair_kernel<0>, dim3((unsigned)pair_blocks), dim3(256), 0, st, F, *K, q_in, pred, (unsigned long long)B, seed, first);
-    else hipLaunchKernelGGL(scout_pair_kernel<1>, dim3((unsigned)pair_blocks), dim3(256), 0, st, F, *K, q_in, pred, (unsigned long long)B, seed, first);
+    if (c.mode == 0) hipLaunchKernelGGL(scout_pair_kernel<0>, dim3((unsigned)pair_blocks), dim3(256), 0, st, F, *K, c.q_in, pred, (unsigned long long)B, c.seed, c.first);
+    else hipLaunchKernelGGL(scout_pair_kernel<1>, dim3((unsigned)pair_blocks), dim3(256), 0, st, F, *K, c.q_in, pred, (unsigned long long)B, c.seed, c.first);
   } else
-  if (mode == 0) {
+  if (c.mode == 0) {
     if (stock) CCMP_LAUNCH_SCOUT(0, true);
     else CCMP_LAUNCH_SCOUT(0, false);
   } else {
@@ -1007,10 +991,11 @@ extern "C" hipError_t ccmp_launch_scout_order(const ccmp_consts *K, int mode, co
 }
 
 // extend-step order: FP32 scout of every edge (rounds capped at round_cap < 1024), then the descending counting sort
-extern "C" hipError_t ccmp_launch_geodesic_scout_order(const ccmp_consts *K, const double *from, const double *to, size_t E, double delta,
-                                                        double lambda, int max_states, int round_cap, uint16_t *pred, unsigned int *hist,
-                                                        unsigned int *order, int pairs, const ccmp_split_req *split, hipStream_t st)
+hipError_t geodesic_scout_order(const GeoCall &g, int round_cap, uint16_t *pred, unsigned int *hist, unsigned int *order, int pairs,
+                                const ccmp_split_req *split, hipStream_t st)
 {
+  const ccmp_consts *K = g.K;
+  const size_t E = g.E;
   const ccmp_split_req sr = split ? *split : ccmp_split_req{nullptr, 0, 0, 0, 0, 0u, 0};
   consts_f F;
   bool stock;
@@ -1023,19 +1008,19 @@ extern "C" hipError_t ccmp_launch_geodesic_scout_order(const ccmp_consts *K, con
   if (!fused) {
     // every bin, not only the nbins this sort fills: the split rules sum the histogram over all kBins, and the bins above were
     // whatever the context's last sort left there (a projector batch's counts up to its cap of 96: a cut decided on them)
-    e = ccmp_launch_clear_words(hist, (size_t)kBins, st);
+    e = clear_words(hist, (size_t)kBins, st);
     if (e != hipSuccess) return e;
   }
   const unsigned blocks = (unsigned)((E + 63) / 64);
   if (stock && K->twin_arms && pairs)
-    hipLaunchKernelGGL(scout_geodesic_pair_kernel, dim3((unsigned)((2 * E + 63) / 64)), dim3(64), 0, st, F, from, to, (unsigned long long)E,
-                       (float)delta, (float)lambda, max_states, round_cap, pred);
+    hipLaunchKernelGGL(scout_geodesic_pair_kernel, dim3((unsigned)((2 * E + 63) / 64)), dim3(64), 0, st, F, g.from, g.to, (unsigned long long)E,
+                       (float)g.delta, (float)g.lambda, g.max_states, round_cap, pred);
   else if (stock)
-    hipLaunchKernelGGL(scout_geodesic_kernel<true>, dim3(blocks), dim3(64), 0, st, F, from, to, (unsigned long long)E, (float)delta,
-                       (float)lambda, max_states, round_cap, pred);
+    hipLaunchKernelGGL(scout_geodesic_kernel<true>, dim3(blocks), dim3(64), 0, st, F, g.from, g.to, (unsigned long long)E, (float)g.delta,
+                       (float)g.lambda, g.max_states, round_cap, pred);
   else
-    hipLaunchKernelGGL(scout_geodesic_kernel<false>, dim3(blocks), dim3(64), 0, st, F, from, to, (unsigned long long)E, (float)delta,
-                       (float)lambda, max_states, round_cap, pred);
+    hipLaunchKernelGGL(scout_geodesic_kernel<false>, dim3(blocks), dim3(64), 0, st, F, g.from, g.to, (unsigned long long)E, (float)g.delta,
+                       (float)g.lambda, g.max_states, round_cap, pred);
   if (fused) {
     hipLaunchKernelGGL(sort_fused_kernel, dim3(1), dim3(1024), 0, st, pred, (unsigned int)E, hist, order, sr);
     return hipGetLastError();
@@ -1046,3 +1031,5 @@ extern "C" hipError_t ccmp_launch_geodesic_scout_order(const ccmp_consts *K, con
                      (unsigned long long)E, hist, order);
   return hipGetLastError();
 }
+
+}  // namespace ccmp_launch

@@ -244,24 +244,21 @@ __global__ __launch_bounds__(64, CCMP_WAVE_WAVES_PER_SIMD) void project_fd_wave_
 
 } // namespace
 
-extern "C" {
+namespace ccmp_launch {
 
-// src 0: q_in, 1: ambient sampler, 2: straggler pool (count read from *pool_count on the device)
-hipError_t ccmp_launch_project_wave(const ccmp_consts *K, int src, const double *q_in, double *q_out, uint8_t *ok,
-                                    uint16_t *iters, double *q_ambient, size_t B, unsigned long long *queue_head,
-                                    unsigned long long seed, unsigned long long first, const double *pool,
-                                    const unsigned long long *pool_count, int wrap_output, int nblocks, hipStream_t st)
+// the call's samples (its mode) or the straggler pool's (count read from *pool_count on the device)
+hipError_t project_wave(const ProjectCall &c, bool from_pool, int blocks, unsigned long long *queue, const double *pool,
+                        const unsigned long long *pool_count, hipStream_t st)
 {
-  if (src == 0)
-    hipLaunchKernelGGL(project_fd_wave_kernel<0>, dim3(nblocks), dim3(64), 0, st, *K, q_in, q_out, ok, iters, q_ambient,
-                       (unsigned long long)B, queue_head, seed, first, pool, pool_count, wrap_output);
-  else if (src == 1)
-    hipLaunchKernelGGL(project_fd_wave_kernel<1>, dim3(nblocks), dim3(64), 0, st, *K, q_in, q_out, ok, iters, q_ambient,
-                       (unsigned long long)B, queue_head, seed, first, pool, pool_count, wrap_output);
-  else
-    hipLaunchKernelGGL(project_fd_wave_kernel<2>, dim3(nblocks), dim3(64), 0, st, *K, q_in, q_out, ok, iters, q_ambient,
-                       (unsigned long long)B, queue_head, seed, first, pool, pool_count, wrap_output);
+  const int src = from_pool ? 2 : c.mode;
+#define CCMP_LAUNCH_WAVE(SRC)                                                                                                           \
+  hipLaunchKernelGGL(project_fd_wave_kernel<SRC>, dim3(blocks), dim3(64), 0, st, *c.K, c.q_in, c.q_out, c.ok, c.iters, c.q_ambient, \
+                     (unsigned long long)c.B, queue, c.seed, c.first, pool, pool_count, c.mode)
+  if (src == 0) CCMP_LAUNCH_WAVE(0);
+  else if (src == 1) CCMP_LAUNCH_WAVE(1);
+  else CCMP_LAUNCH_WAVE(2);
+#undef CCMP_LAUNCH_WAVE
   return hipGetLastError();
 }
 
-} // extern "C"
+}  // namespace ccmp_launch

@@ -1,0 +1,144 @@
+/* ccmp_launch.h — the kernel launchers of libccmp (defined in the ccmp_kernels_*.hip units, called by the host units): the one
+ * declaration of each, with C++ linkage (a definition that drifts from it does not compile) and hidden visibility (not exported).
+ * Also the layout facts that host and kernels share: the work-queue words, the hand-over record sizes, a split launch's cut. */
+#ifndef CCMP_LAUNCH_H
+#define CCMP_LAUNCH_H
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+struct ccmp_consts;
+namespace ccmp { struct scene_dev; }
+
+/* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
+ * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
+ * the block (QueueWord, BulkWord).  Until round 5 two launches of their own: two of the five kernel boundaries before the fork. */
+struct ccmp_split_req {
+  unsigned long long *queue; /* the block of queue words; nullptr: no split */
+  int kind;                  /* 1: the units predicted >= p_low, at most `limit` (projector: fd_split_kernel's rule);
+                                2: >= p_high where those carry permille / 1000 of the predicted work, else >= p_low (extend step: geo_split2_kernel's) */
+  int p_low, p_high, permille;
+  unsigned int limit;
+  int clear;                 /* this many 64-bit words from queue[0] on are zeroed first (the others of the launch's block) */
+};
+
+namespace ccmp_launch {
+
+constexpr int kPoolEntry = 18;    // projector hand-over record, in doubles: x[14], idx, (iter, updates), norm1, norm2
+constexpr int kGeoPoolEntry = 40; // extend-step hand-over of an edge in the middle of a projection: x[14], previous[14], dist, total,
+                                  // maxd, edge, (n, its), (rounds, iter), updates, norm1, norm2 (geodesic_group_kernel -> geodesic_flat_kernel)
+constexpr int kFastQueues = 64;   // ticket words of the analytic mode's lane-pair kernel: one per lane of a wavefront
+
+/* ctx->queue, in 64-bit words; each launch sequence clears the words it uses */
+enum QueueWord : int {
+  kQTicket = 0,                                 // projector: throughput kernel's ticket (split launch: starts behind the front)
+  kQPool = 1,                                   // projector: hand-over pool's fill count (the kernels count from the back at kQPool + 5)
+  kQLatency = 2,                                // projector: latency kernel's ticket
+  kQFinished = 3,                               // projector: throughput kernel's finished samples (its occupancy hand-over)
+  kQFrontLen = 4,                               // projector, split launch: the front's length
+  kQScout = 5,                                  // projector: the scout pass's queue
+  kQFront = 7,                                  // projector, split launch: the front's ticket
+  kQGeoTicket = 3,                              // extend step: ticket (the projector's words: a call runs one or the other)
+  kQGeoOrder = 4,                               // extend step: the ordering pass's two 32-bit counters
+  kQAnalytic = 8,                               // analytic projector: kFastQueues lane-pair tickets, pool fill count, latency kernel's ticket
+  kQGeoAnalytic = kQAnalytic + kFastQueues + 2, // extend step in analytic mode: ticket
+  kQBulk = kQGeoAnalytic + 1,                   // bulk extend step: a block of eight (BulkWord)
+  kQueueWords = kQBulk + 8,
+};
+/* the bulk extend step's block: the group kernel's ticket (starts behind the front) and finished edges (its hand-over rule), the
+ * front's length and ticket, the hand-over pool's fill count, the ticket of the launch that drains the pool */
+enum BulkWord : int { kBTicket = 0, kBFinished = 3, kBFrontLen = 4, kBFront = 5, kBPool = 6, kBDrain = 7 };
+
+/* what every launch of one projector call shares */
+struct ProjectCall {
+  const ccmp_consts *K;
+  int mode;                       // 0: project q_in, 1: fused sampleUniform
+  const double *q_in;
+  double *q_out;
+  uint8_t *ok;
+  uint16_t *iters;                // nullable
+  double *q_ambient;              // nullable: the fused sampler's ambient samples
+  size_t B;
+  unsigned long long seed, first; // the sampler's stream
+};
+
+/* what every launch of one extend-step call shares */
+struct GeoCall {
+  const ccmp_consts *K;
+  double delta, lambda;
+  const double *from, *to;
+  size_t E;
+  int max_states;
+  double *states;
+  int32_t *n_states;
+  uint8_t *ok;
+  int32_t *newton_iters;
+  const double *carry_in; // nullable: a continuation's carries
+  double *carry_out;      // nullable
+  int round_budget;       // 0: none
+  int check_target;       // checkMotion: isSatisfied(to) of every edge
+};
+
+/* one launch of project_fd_flat_kernel, the projector's latency kernel */
+struct FlatLaunch {
+  int blocks = 0;
+  unsigned long long *queue = nullptr;                                      // ticket word; nullptr: one block per sample, static striding
+  bool from_pool = false;                                                   // the samples handed over through the pool, else the call's
+  const double *pool = nullptr; const unsigned long long *pool_count = nullptr; // the pool and its fill count
+  size_t pool_records = 0;                                                  // two-class pool: its capacity (0: filled from the front only)
+  const unsigned int *order = nullptr;                                      // processing order ...
+  const unsigned long long *total = nullptr;                                // ... of which a split launch's front takes the first *total
+  unsigned int *done_flag = nullptr, done_seq = 0;                          // single-state call: completion word (one block only), value
+};
+
+/* one launch of geodesic_flat_kernel, the extend step's latency kernel */
+struct GeoLaunch {
+  int blocks = 0;
+  unsigned long long *queue = nullptr;                                     // ticket word; nullptr: one block per edge, static striding
+  const unsigned int *order = nullptr;                                     // processing order ...
+  const unsigned long long *total = nullptr;                               // ... of which a bulk call's front takes the first *total
+  const double *pool = nullptr; const unsigned long long *pool_count = nullptr; // drain of a bulk call: the edges handed over, their count
+};
+
+#pragma GCC visibility push(hidden)
+hipError_t clear_words(void *words, size_t n_u32, hipStream_t st);
+hipError_t project_group(const ProjectCall &c, int blocks, unsigned long long *queue, double *pool, int dump_threshold, const unsigned int *order,
+                         const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st);
+hipError_t project_wave(const ProjectCall &c, bool from_pool, int blocks, unsigned long long *queue, const double *pool,
+                        const unsigned long long *pool_count, hipStream_t st);
+hipError_t project_flat(const ProjectCall &c, const FlatLaunch &l, hipStream_t st);
+hipError_t project_analytic(const ProjectCall &c, int pair_blocks, int dump_below, int latency_blocks, double *pool, unsigned long long *queue, hipStream_t st);
+hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist, unsigned int *order, unsigned long long *queue, int blocks,
+                       int pair_max_blocks, const ccmp_split_req *split, hipStream_t st);
+hipError_t fd_split(const unsigned int *hist, int pred_min, unsigned int limit, unsigned long long *queue, hipStream_t st);
+hipError_t geo_split(const unsigned int *hist, int p_min, int p_max, int permille, unsigned long long *queue, hipStream_t st);
+hipError_t geodesic(const GeoCall &g, const GeoLaunch &l, hipStream_t st);
+hipError_t geodesic_lat(const GeoCall &g, const GeoLaunch &l, hipStream_t st);
+hipError_t geodesic_group(const GeoCall &g, int blocks, unsigned long long *queue, const unsigned int *order, double *pool,
+                          unsigned long long *pool_count, int handover_pct, const uint8_t *target_ok, hipStream_t st);
+hipError_t geodesic_analytic(const GeoCall &g, int blocks, unsigned long long *queue, hipStream_t st);
+hipError_t geodesic_scout_order(const GeoCall &g, int round_cap, uint16_t *pred, unsigned int *hist, unsigned int *order, int pairs,
+                                const ccmp_split_req *split, hipStream_t st);
+hipError_t geodesic_order(const double *from, const double *to, size_t E, double long_dist, unsigned int *counters, unsigned int *order, hipStream_t st);
+hipError_t function(const ccmp_consts *K, const double *q, double *f, size_t B, unsigned int *done_flag, unsigned int done_seq, hipStream_t st);
+hipError_t is_satisfied(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag, unsigned int done_seq, hipStream_t st);
+hipError_t joint_valid(const ccmp_consts *K, const double *q, uint8_t *ok, size_t B, unsigned int *done_flag, unsigned int done_seq, hipStream_t st);
+hipError_t ambient_uniform(const ccmp_consts *K, unsigned long long seed, unsigned long long first, double *q, size_t B, hipStream_t st);
+hipError_t ambient_ref(const ccmp_consts *K, int kind, unsigned long long seed, unsigned long long first, const double *ref, int ref_stride,
+                       double param, double *q, size_t B, hipStream_t st);
+hipError_t t_wo(const ccmp_consts *K, const double *q, int q_stride, double *out, size_t B, hipStream_t st);
+hipError_t enforce_bounds(double *q, size_t B, hipStream_t st);
+hipError_t compact(const double *q, const uint8_t *ok, size_t B, double *out, size_t capacity, unsigned int *block_counts, unsigned long long *total, hipStream_t st);
+size_t clearance_lds_bytes(int n_spheres);
+hipError_t clearance(const ccmp_consts *K, const ccmp::scene_dev *scene, int n_spheres, int n_pairs, const double *q, const uint8_t *ok_in, size_t B,
+                     double margin, double *clearance, int32_t *pair, uint8_t *free_out, int blocks, int per_state, unsigned int *done_flag,
+                     unsigned int done_seq, hipStream_t st);
+hipError_t resident(int stock, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st);
+// lib/libccmp_debug.so only (ccmp_kernels_debug.hip)
+hipError_t detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
+hipError_t div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);
+#pragma GCC visibility pop
+
+}  // namespace ccmp_launch
+
+#endif /* CCMP_LAUNCH_H */

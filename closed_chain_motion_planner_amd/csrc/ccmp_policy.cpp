@@ -159,7 +159,7 @@ FdPlan plan_fd_batch(const ccmp_ctx *ctx, size_t B, bool external_order)
   FdPlan pl;
   const int wpc = ctx->waves_per_cu > 0 ? ctx->waves_per_cu : 12;
   // latency kernels: the flat kernel runs 8 blocks of 128 threads per CU (16 waves), the one-wave kernel wpc waves
-  const size_t lat_cap = ctx->flat_kernel ? (size_t)ctx->num_cus * (size_t)ctx->latency_blocks_per_cu : (size_t)ctx->num_cus * (size_t)wpc;
+  const size_t lat_cap = ctx->flat_kernel ? (size_t)ctx->num_cus * kLatencyBlocksPerCu : (size_t)ctx->num_cus * (size_t)wpc;
   const bool latency_only = ctx->wave_kernel == 2 || (ctx->wave_kernel == 1 && B <= ctx->small_batch);
   if (latency_only) {
     pl.latency_blocks = (int)(B < lat_cap ? B : lat_cap);
@@ -185,7 +185,7 @@ FdPlan plan_fd_batch(const ccmp_ctx *ctx, size_t B, bool external_order)
     const size_t in_flight = (size_t)pl.group_blocks * 10;
     pl.latency_blocks = (int)(in_flight < lat_cap ? in_flight : lat_cap);
   }
-  pl.two_class_pool = pl.scout && pl.handover && ctx->flat_kernel && ctx->pool_long_remaining > 0;
+  pl.two_class_pool = pl.scout && pl.handover && ctx->flat_kernel;
   // Split launch.  Decided HERE, before anything of the call is launched: it needs the scout's predictions, the hand-over's
   // latency kernel, a front of at least one block, and at least one throughput wavefront per CU left beside it (a cut that
   // reaches waves_per_cu — both are options — once left a grid of 0 or fewer blocks behind a front that was already running).
@@ -247,28 +247,28 @@ int plan_geodesic_analytic(const ccmp_ctx *ctx, size_t E)
 GeoPlan plan_geodesic(const ccmp_ctx *ctx, size_t E, int round_budget, bool continuation)
 {
   GeoPlan pl;
-  const size_t lat_resident = (size_t)ctx->num_cus * (size_t)ctx->geodesic_blocks_per_cu;
+  const size_t lat_resident = (size_t)ctx->num_cus * kGeoBlocksPerCu;
   pl.latency_flavour = ctx->geodesic_flavour == 2 || (ctx->geodesic_flavour == 0 && (round_budget == 0 || E <= lat_resident));
-  const size_t resident = pl.latency_flavour ? lat_resident : (size_t)ctx->num_cus * (size_t)ctx->latency_blocks_per_cu;
+  const size_t resident = pl.latency_flavour ? lat_resident : (size_t)ctx->num_cus * kLatencyBlocksPerCu;
   pl.blocks = E;
   if (E > resident) {
     pl.blocks = resident;
     pl.queued = true;
     pl.ordered = ctx->geodesic_order && E >= ctx->geodesic_order_min && E < 0xffffffffull;
     pl.scouted = pl.ordered && ctx->geodesic_order == 2 && E >= ctx->geodesic_scout_min && !continuation;
-    pl.scout_pairs = pl.scouted && ctx->scout_pairs && E <= ctx->scout_pair_max_edges;
+    pl.scout_pairs = pl.scouted && ctx->scout_pairs && E <= kScoutPairMaxEdges;
   }
   pl.bulk = pl.scouted && round_budget > 0 && ctx->geodesic_group && E >= ctx->geodesic_group_min;
   if (pl.bulk) {
     pl.group_waves = (E + 9) / 10;
-    const size_t cap = (size_t)ctx->num_cus * (size_t)ctx->geodesic_group_waves_per_cu;
+    const size_t cap = (size_t)ctx->num_cus * kGeoGroupWavesPerCu;
     if (pl.group_waves > cap) pl.group_waves = cap;
-    pl.front_blocks = ctx->num_cus * (ctx->geodesic_group_front_per_cu > 0 ? ctx->geodesic_group_front_per_cu : 8);
+    pl.front_blocks = ctx->num_cus * kGeoGroupFrontPerCu;
     pl.low_cut = ctx->geodesic_group_low_cut > 0 ? ctx->geodesic_group_low_cut : (E < kGeoGroupHighCut ? 40 : (E < kGeoGroupHigherCut ? 48 : 56));
     pl.default_cut = ctx->geodesic_group_permille <= 0 && ctx->geodesic_group_pred <= 0;
     pl.handover_pct = ctx->geodesic_group_handover_pct >= 0 ? ctx->geodesic_group_handover_pct : (E < kGeoGroupLateHandoverFrom ? 50 : 80);
     if (pl.handover_pct > 0) {
-      const size_t lat = (size_t)ctx->num_cus * (size_t)ctx->latency_blocks_per_cu;
+      const size_t lat = (size_t)ctx->num_cus * kLatencyBlocksPerCu;
       pl.drain_blocks = (int)(pl.group_waves * 10 < lat ? pl.group_waves * 10 : lat);
     }
   }
@@ -297,6 +297,17 @@ struct Line {
 };
 
 }  // namespace
+
+int ccmp_host::policy_set_option(ccmp_ctx *ctx, const char *name, long value)
+{
+  if (!ctx || !name) return CCMP_EINVAL;
+  const OptionDesc *o = find_option(name);
+  if (!o) return CCMP_EINVAL;
+  if (value < o->lo || value > o->hi) return CCMP_EINVAL;
+  if ((o->flags & kNotZero) && value == 0) return CCMP_EINVAL;
+  write_option(ctx, *o, value);
+  return CCMP_OK;
+}
 
 extern "C" {
 
@@ -331,16 +342,6 @@ int ccmp_ctx_get_option(const ccmp_ctx *ctx, const char *name, long *value)
   return CCMP_OK;
 }
 
-int ccmp_policy_set_option(ccmp_ctx *ctx, const char *name, long value) // (behind ccmp_ctx_set_option: ccmp_api.cpp handles "resident")
-{
-  if (!ctx || !name) return CCMP_EINVAL;
-  const OptionDesc *o = find_option(name);
-  if (!o) return CCMP_EINVAL;
-  if (value < o->lo || value > o->hi) return CCMP_EINVAL;
-  if ((o->flags & kNotZero) && value == 0) return CCMP_EINVAL;
-  write_option(ctx, *o, value);
-  return CCMP_OK;
-}
 
 int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf, size_t cap)
 {
@@ -370,7 +371,7 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
         if (pl.dump_threshold > 10) L.add("; hand-over below %d %% occupancy", pl.dump_threshold - 10);
         else L.add("; hand-over per wavefront at <= %d busy groups", pl.dump_threshold);
         L.add(" to %d %s blocks", pl.latency_blocks, ctx->flat_kernel ? "project_fd_flat_kernel" : "project_fd_wave_kernel");
-        if (pl.two_class_pool) L.add(" in two classes (>= %d predicted iterations left first)", ctx->pool_long_remaining);
+        if (pl.two_class_pool) L.add(" in two classes (>= %d predicted iterations left first)", kPoolLongRemaining);
       } else L.add("; no hand-over");
       L.add(" [small_batch=%zu lpt_min_batch=%zu fd_split=%d:%zu..%zu wide<=%zu occupancy_rule<%zu no_handover>=%zu]", ctx->small_batch,
             ctx->lpt_min_batch, ctx->fd_split, ctx->fd_split_min, ctx->fd_split_max, kSplitWideMax, kOccupancyHandoverBelow, kNoHandoverFrom);
@@ -396,7 +397,7 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
       if (pl.bulk) {
         L.add("bulk form: front (predicted >= 64 rounds if those edges carry %d permille of the work, else >= %d) on %d geodesic_flat_kernel blocks on the side stream, "
               "beside geodesic_group_kernel x %zu wavefronts",
-              ctx->geodesic_group_heavy_permille, pl.low_cut, pl.front_blocks, pl.group_waves);
+              kGeoGroupHeavyPermille, pl.low_cut, pl.front_blocks, pl.group_waves);
         if (ctx->geodesic_group_pred > 0) L.add(" (cut fixed at %d)", ctx->geodesic_group_pred);
         if (pl.handover_pct > 0)
           L.add("; hand-over below %d %% occupancy to %d blocks behind it", pl.handover_pct, pl.drain_blocks);

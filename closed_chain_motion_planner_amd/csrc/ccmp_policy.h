@@ -61,6 +61,8 @@ GeoPlan plan_geodesic(const ccmp_ctx *ctx, size_t E, int round_budget, bool cont
 constexpr int kGeoAnalyticWavesPerCu = 8; // two per SIMD at occupancy 2
 int plan_geodesic_analytic(const ccmp_ctx *ctx, size_t E);
 
+/* ccmp_ctx_set_option behind the options ccmp_api.cpp handles itself ("resident"): the option table */
+__attribute__((visibility("hidden"))) int policy_set_option(ccmp_ctx *ctx, const char *name, long value);
 /* a context-shaped default for calls that have none at hand (ccmp_ctx_get_option / ccmp_ctx_describe with ctx == NULL):
  * the built-in settings on a 256-CU device */
 const ccmp_ctx &default_ctx();

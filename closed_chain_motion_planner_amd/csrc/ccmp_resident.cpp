@@ -10,11 +10,10 @@
 
 #include "ccmp_ctx.h"
 #include "ccmp_host.h"
+#include "ccmp_launch.h"
 
 using ccmp_host::DeviceGuard;
 using ccmp_host::hip_fail;
-
-extern "C" hipError_t ccmp_launch_resident(int stock, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st);
 
 struct ccmp_resident {
   char *box = nullptr;      // pinned, device-mapped, coherent
@@ -111,7 +110,7 @@ int start(ccmp_ctx *ctx, ccmp_resident *r, int stock)
   drain(r); // (a kernel that left by itself)
   __atomic_store_n(word(r, kResStateOff), (unsigned long long)kResStarting, __ATOMIC_RELEASE);
   const unsigned long long idle_ticks = (unsigned long long)ctx->resident_idle_ms * 100000ull; // wall_clock64: 100 MHz
-  HIP_TRY(ccmp_launch_resident(stock, r->box_dev, r->tag, idle_ticks, r->stream));
+  HIP_TRY(ccmp_launch::resident(stock, r->box_dev, r->tag, idle_ticks, r->stream));
   r->launched = true;
   r->stock = stock;
   // The kernel reports itself running with its first instructions (~20 us behind the launch).  If it does not within 5 ms — two

@@ -6,19 +6,13 @@
 
 #include "ccmp_ctx.h"
 #include "ccmp_host.h"
+#include "ccmp_launch.h"
 #include "ccmp_resident.h"
 #include "ccmp_scene.h"
 
 using namespace ccmp_host;
 using ccmp::kSceneSlots;
 using ccmp::scene_dev;
-
-extern "C" {
-hipError_t ccmp_launch_clearance(const ccmp_consts *K, const scene_dev *scene_dev_ptr, int n_spheres, int n_pairs, const double *q, const uint8_t *ok_in,
-                                 size_t B, double margin, double *clearance, int32_t *pair, uint8_t *free_out, int nblocks, int per_state,
-                                 unsigned int *done_flag, unsigned int done_seq, hipStream_t st);
-size_t ccmp_clearance_lds_bytes(int n_spheres);
-}
 
 namespace {
 
@@ -150,27 +144,22 @@ int ccmp_clearance_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene 
     size_t blocks = B;
     const size_t cap = (size_t)ctx->num_cus * 8;
     if (blocks > cap) blocks = cap;
-    unsigned int *flag = nullptr;
-    if (ctx->want_done && B == 1 && ctx->pin_dev) {
-      ctx->done_seq++;
-      ctx->done_armed = true;
-      flag = (unsigned int *)((char *)ctx->pin_dev + ccmp_host::kPinData);
-    }
-    HIP_TRY(ccmp_launch_clearance(&K, scene->dev, scene->host.n_spheres, scene->host.n_pairs, q, ok_in, B, margin, clearance, pair, free_out, (int)blocks, 1,
-                                  flag, ctx->done_seq, (hipStream_t)hip_stream));
+    unsigned int *flag = arm_done_word(ctx, B);
+    HIP_TRY(ccmp_launch::clearance(&K, scene->dev, scene->host.n_spheres, scene->host.n_pairs, q, ok_in, B, margin, clearance, pair, free_out, (int)blocks, 1,
+                                   flag, ctx->done_seq, (hipStream_t)hip_stream));
     return CCMP_OK;
   }
   // one 256-thread block per tile of 64 states; the centres of a tile take 1.5 KB of LDS per sphere, so a CU holds
   // 160 KB / that many blocks (and at most eight: 2048 threads)
-  const size_t lds = ccmp_clearance_lds_bytes(scene->host.n_spheres);
+  const size_t lds = ccmp_launch::clearance_lds_bytes(scene->host.n_spheres);
   size_t per_cu = (160 * 1024) / lds;
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 8) per_cu = 8;
   size_t blocks = (B + 63) / 64;
   const size_t cap = (size_t)ctx->num_cus * per_cu;
   if (blocks > cap) blocks = cap;
-  HIP_TRY(ccmp_launch_clearance(&K, scene->dev, scene->host.n_spheres, scene->host.n_pairs, q, ok_in, B, margin, clearance, pair, free_out, (int)blocks, 0,
-                                nullptr, 0, (hipStream_t)hip_stream));
+  HIP_TRY(ccmp_launch::clearance(&K, scene->dev, scene->host.n_spheres, scene->host.n_pairs, q, ok_in, B, margin, clearance, pair, free_out, (int)blocks, 0,
+                                 nullptr, 0, (hipStream_t)hip_stream));
   return CCMP_OK;
 }
 

@@ -37,7 +37,10 @@ def test_exports_every_declared_symbol(L, ccmp_built):
     syms = lambda path: set(re.findall(r" T (\w+)", subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout))
     default_syms, debug_syms = syms(ccmp_built), syms(_lib.DEBUG_LIBPATH)
     assert not [n for n in default_syms if re.search(r"debug|probe|experimental", n)], default_syms
-    assert dbg_declared <= debug_syms and declared <= debug_syms and declared <= default_syms
+    # and nothing else unmangled: the kernel launchers and the other internals have C++ linkage and hidden visibility
+    c_abi = lambda names: {n for n in names if n.startswith("ccmp_")}
+    assert c_abi(default_syms) == declared, c_abi(default_syms) ^ declared
+    assert c_abi(debug_syms) == declared | dbg_declared, c_abi(debug_syms) ^ (declared | dbg_declared)
     assert all(o["name"] != "fail_after_fork" and not o["doc"].startswith("debug") for o in _lib.option_table())
 
 
