@@ -71,6 +71,7 @@ EXPORTS = [
     "ccmp_project_host", "ccmp_function_host", "ccmp_is_satisfied_host", "ccmp_joint_valid_host", "ccmp_sample_project_host", "ccmp_sample_ref_project_host", "ccmp_geodesic_host", "ccmp_project_sharded_host", "ccmp_sample_project_sharded_host", "ccmp_sharded_host_last_timing",
     "ccmp_comm_create", "ccmp_comm_destroy", "ccmp_comm_last_timing", "ccmp_project_sharded", "ccmp_sample_project_sharded",
     "ccmp_scene_create", "ccmp_scene_destroy", "ccmp_scene_num_pairs", "ccmp_clearance_batch", "ccmp_clearance_host",
+    "ccmp_geodesic_scene_batch", "ccmp_geodesic_scene_host",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -163,6 +164,10 @@ def lib():
         "ccmp_scene_num_pairs": ([vp], C.c_int),
         "ccmp_clearance_batch": ([vp, pp, vp, vp, vp, C.c_size_t, C.c_double, vp, vp, vp, vp], C.c_int),
         "ccmp_clearance_host": ([vp, pp, vp, dp, C.c_size_t, C.c_double, dp, C.POINTER(C.c_int32), u8p], C.c_int),
+        "ccmp_geodesic_scene_batch": ([vp, pp, vp, C.c_double, vp, vp, C.c_size_t, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+                                      C.c_int),
+        "ccmp_geodesic_scene_host": ([vp, pp, vp, C.c_double, dp, dp, C.c_size_t, C.c_int, dp, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int32), u8p,
+                                      dp, dp, dp, C.c_int, C.c_int], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),

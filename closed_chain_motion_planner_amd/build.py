@@ -8,6 +8,7 @@ Translation units with deliberately different flags:
   ccmp_kernels_geo.hip   -ffp-contract=off -DCCMP_USE_FMA   the extend step on the same Newton routine (ccmp_flat_newton.h), built twice:
                          like the flat unit (throughput flavour) and -DCCMP_GEO_LATENCY with machine LICM and a 256-register
                          budget (latency flavour)
+  ccmp_kernels_geo_scene.hip  the latency flavour's flags   the extend step with a proxy scene's clearance test (geodesic_scene_kernel)
   ccmp_problem.cpp       -ffp-contract=off -DCCMP_USE_FMA   host set-up (problem, constants) in the same rounding model
   ccmp_api.cpp           -ffp-contract=off -DCCMP_USE_FMA   context, launches            } compiled a second time with -DCCMP_DEBUG_HOOKS for
   ccmp_policy.cpp                                           option table, plans, describe } lib/libccmp_debug.so (include/ccmp_debug.h)
@@ -57,6 +58,8 @@ _UNITS = [
     ("ccmp_kernels_geo.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
     ("ccmp_kernels_geo.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_GEO_LATENCY", "-DCCMP_SUMS_IN_LANE", "-DCCMP_FLAT_MIN_WAVES=2", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
      "ccmp_kernels_geo_lat.hip.o"),
+    # the extend step with a proxy scene (FD mode): the latency flavour's flags — its 256-register budget holds the clearance without scratch
+    ("ccmp_kernels_geo_scene.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_SUMS_IN_LANE", "-DCCMP_FLAT_MIN_WAVES=2", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
     # the resident service kernel: one block alone on its SIMDs — the latency flavour's flags (registers are free, fewest instructions per round)
     ("ccmp_kernels_resident.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_SUMS_IN_LANE", "-DCCMP_FLAT_MIN_WAVES=2", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
     # the analytic mode's lane-pair kernel: without machine LICM (the ~35 FP64 literals of sincos / atan would be held in
@@ -72,7 +75,7 @@ _UNITS = [
     ("ccmp_kernels_scene.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     ("ccmp_scene.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -108,10 +111,10 @@ def _stale(target, sources):
 #     calibrated arms runs unfused (ccmp_api.cpp: project_common);
 #   * everything else (scouts, small per-lane kernels, analytic mode, scene): at most 64 B unless listed.
 _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
-    (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_group_kernel|resident_service_kernel)<(\d+, )?true>", 0),
-    (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_group_kernel|resident_service_kernel)<(\d+, )?false>", 136),
+    (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_scene_kernel|geodesic_group_kernel|resident_service_kernel)<(\d+, )?true>", 0),
+    (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_scene_kernel|geodesic_group_kernel|resident_service_kernel)<(\d+, )?false>", 136),
     (r"project_pair_kernel|project_row16_kernel", 0),  # analytic mode, every instantiation (stock twin arms, stock, calibrated)
-    (r"geodesic_row16_kernel", 0),  # analytic mode's extend step, both instantiations (diagonal and general base frames)
+    (r"geodesic_row16_(scene_)?kernel", 0),  # analytic mode's extend step and its scene variant, both instantiations (diagonal and general base frames)
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

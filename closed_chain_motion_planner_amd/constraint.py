@@ -356,12 +356,53 @@ class KinematicChainConstraint:
                                                 1 if check_target else 0, _stream_handle(stream)), "ccmp_geodesic_batch_ex")
         return (states, n, ok, its, carry) if want_carry else (states, n, ok, its)
 
-    def continue_geodesics(self, to, states, n, ok, its, carry, max_states, round_budget=0, max_calls=1 << 20, cont_states=None):
+    def discrete_geodesic_scene_batch(self, frm, to, scene, margin, max_states=64, stream=None, check_target=False, carry_in=None,
+                                      want_clearance=False, want_carry=False, round_budget=0):
+        """`discrete_geodesic_batch` with interpolate == false and a proxy scene's validity test on the device
+        (ccmp_geodesic_scene_batch): a projected state is valid when its clearance in `scene` (a ProxyScene of this
+        constraint's context) exceeds `margin` — the rule of ProxyValidityChecker.isValid — and the traversal breaks at the
+        first state that is not, as the reference's loop does.  Returns (states, n_states, ok, newton_iters, blocked (E,)
+        uint8) and then, with want_clearance, clearance (E,max_states) float64 (entry k: listed state k, 1 <= k <
+        min(n_states, max_states); the rest NaN), with want_carry carry (E,2).  blocked[e] = 1: the edge ended at a state
+        the scene refused (final: not to be continued)."""
+        self._need_problem()
+        self._check_q(frm)
+        self._check_q(to)
+        torch = _torch()
+        E = frm.shape[0]
+        states = torch.empty((E, max_states, 14), dtype=torch.float64, device=frm.device)
+        n = torch.empty(E, dtype=torch.int32, device=frm.device)
+        ok = torch.empty(E, dtype=torch.uint8, device=frm.device)
+        its = torch.empty(E, dtype=torch.int32, device=frm.device)
+        blocked = torch.empty(E, dtype=torch.uint8, device=frm.device)
+        if carry_in is not None and not (isinstance(carry_in, torch.Tensor) and carry_in.is_cuda and carry_in.dtype == torch.float64
+                                         and carry_in.is_contiguous() and tuple(carry_in.shape) == (E, 2)):
+            raise ValueError("carry_in: contiguous (E,2) float64 CUDA tensor")
+        if round_budget and not want_carry:
+            raise ValueError("round_budget needs want_carry=True: a suspended edge is continued from its carry")
+        carry = torch.empty((E, 2), dtype=torch.float64, device=frm.device) if want_carry else None
+        clr = torch.full((E, max_states), float("nan"), dtype=torch.float64, device=frm.device) if want_clearance else None
+        check(_lib.lib().ccmp_geodesic_scene_batch(self.ctx.handle, C.byref(self.problem), scene._h, float(margin), frm.data_ptr(),
+                                                   to.data_ptr(), E, int(max_states), states.data_ptr(), n.data_ptr(), ok.data_ptr(),
+                                                   its.data_ptr(), blocked.data_ptr(), clr.data_ptr() if clr is not None else None,
+                                                   carry_in.data_ptr() if carry_in is not None else None,
+                                                   carry.data_ptr() if carry is not None else None, int(round_budget),
+                                                   1 if check_target else 0, _stream_handle(stream)), "ccmp_geodesic_scene_batch")
+        out = (states, n, ok, its, blocked)
+        if want_clearance:
+            out += (clr,)
+        if want_carry:
+            out += (carry,)
+        return out
+
+    def continue_geodesics(self, to, states, n, ok, its, carry, max_states, round_budget=0, max_calls=1 << 20, cont_states=None,
+                           scene=None, margin=None):
         """Finishes the edges of a `discrete_geodesic_batch(..., want_carry=True)` result that did not reach their end
         (list full: n == max_states + 1; round budget spent: ok == 2), each from its last stored state.  Returns {edge index:
         (states (m,14) numpy, ok, newton iterations)} with the complete list of every such edge — what one uninterrupted
         traversal produces, bit for bit.  `max_states` is the list length of the result passed in, `cont_states` (default:
-        the same) the one the continuation calls use."""
+        the same) the one the continuation calls use.  With `scene` and `margin` (a `discrete_geodesic_scene_batch` result,
+        continued with the same scene and margin) the values are (states, ok, newton iterations, blocked)."""
         torch = _torch()
         cs = max_states if cont_states is None else int(cont_states)
         if max_states < 2 or cs < 2:
@@ -379,9 +420,16 @@ class KinematicChainConstraint:
         cur_from = states[long][rows, (stored - 1).long()].contiguous()
         cur_to = to[long].contiguous()
         cur_carry = carry[long].contiguous()
+        if scene is not None and margin is None:
+            raise ValueError("scene needs its margin")
         for _ in range(max_calls):
-            s2, n2, ok2, it2, c2 = self.discrete_geodesic_batch(cur_from, cur_to, cs, carry_in=cur_carry, want_carry=True,
-                                                                round_budget=round_budget)
+            if scene is None:
+                s2, n2, ok2, it2, c2 = self.discrete_geodesic_batch(cur_from, cur_to, cs, carry_in=cur_carry, want_carry=True,
+                                                                    round_budget=round_budget)
+            else:
+                s2, n2, ok2, it2, bl2, c2 = self.discrete_geodesic_scene_batch(cur_from, cur_to, scene, margin, cs, carry_in=cur_carry,
+                                                                               want_carry=True, round_budget=round_budget)
+                bl2c = bl2.cpu().numpy()
             n2c, ok2c, it2c = n2.cpu().numpy(), ok2.cpu().numpy(), it2.cpu().numpy()
             s2h = s2.cpu().numpy()
             again = []
@@ -393,6 +441,8 @@ class KinematicChainConstraint:
                     again.append(k)
                 else:
                     out[e] = (np.concatenate(parts[e], axis=0), int(ok2c[k]), total_its[e])
+                    if scene is not None:
+                        out[e] += (int(bl2c[k]),)
             if not again:
                 break
             sel = torch.as_tensor(again, device=to.device)

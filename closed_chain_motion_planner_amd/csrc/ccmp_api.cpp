@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -18,6 +19,7 @@
 #include "ccmp_launch.h"
 #include "ccmp_policy.h"
 #include "ccmp_resident.h"
+#include "ccmp_scene.h"
 
 using namespace ccmp_host;
 using namespace ccmp_launch; // the queue words, the call-wide argument structs
@@ -454,12 +456,10 @@ int ccmp_compute_t_wo_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *
   return CCMP_OK;
 }
 
-static int geodesic_common(ccmp_ctx *ctx, const ccmp_problem *p, const double *from, const double *to, size_t E, int max_states,
-                           double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, const double *carry_in,
-                           double *carry_out, int round_budget, int check_target, void *hip_stream)
+// the arguments of an extend-step call (E > 0) that every form of it checks
+static int geodesic_args(const ccmp_problem *p, const double *from, const double *to, int max_states, double *states, int32_t *n_states,
+                         uint8_t *ok, const double *carry_in, double *carry_out, int round_budget, int check_target)
 {
-  CCMP_PROLOGUE();
-  if (E == 0) return CCMP_OK;
   if (!from || !to || !states || !n_states || !ok || max_states < 1 || round_budget < 0) return CCMP_EINVAL;
   if (!(p->delta > 0) || !(p->lambda > 0)) return CCMP_EINVAL;
   if (carry_in && check_target) return CCMP_EINVAL;        // a continuation's target was tested by the call it continues
@@ -467,6 +467,16 @@ static int geodesic_common(ccmp_ctx *ctx, const ccmp_problem *p, const double *f
   // a resumable call needs room for one state besides `from`: with a one-entry list the first accepted state already reports
   // max_states + 1 with `from` as its last stored state, and a caller following the protocol would continue from `from` for ever
   if ((carry_in || carry_out || round_budget > 0) && max_states < 2) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+static int geodesic_common(ccmp_ctx *ctx, const ccmp_problem *p, const double *from, const double *to, size_t E, int max_states,
+                           double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, const double *carry_in,
+                           double *carry_out, int round_budget, int check_target, void *hip_stream)
+{
+  CCMP_PROLOGUE();
+  if (E == 0) return CCMP_OK;
+  { const int rc = geodesic_args(p, from, to, max_states, states, n_states, ok, carry_in, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; }
   const GeoCall g{&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok, newton_iters, carry_in, carry_out, round_budget, check_target};
   if (p->jacobian_mode != CCMP_JAC_FD) {
     // Analytic mode: one launch of the traversal kernel on the analytic latency kernel's layout (ccmp_kernels_fast.hip:
@@ -570,6 +580,25 @@ int ccmp_geodesic_batch_ex(ccmp_ctx *ctx, const ccmp_problem *p, const double *f
 {
   return geodesic_common(ctx, p, from, to, E, max_states, states, n_states, ok, newton_iters, carry_in, carry_out, round_budget,
                          check_target, hip_stream);
+}
+
+// The extend step with the StateValidityChecker's proxy pre-filter on the device: one launch of the scene variant of the mode's
+// traversal kernel (FD: geodesic_scene_kernel, the latency build's persistent blocks on a ticket; analytic: geodesic_row16_scene_kernel).
+// Never the bulk form, never the resident service.  ccmp_policy.cpp: plan_geodesic_scene — what ccmp_ctx_describe prints.
+int ccmp_geodesic_scene_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *from, const double *to,
+                              size_t E, int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                              double *clearance, const double *carry_in, double *carry_out, int round_budget, int check_target, void *hip_stream)
+{
+  CCMP_PROLOGUE();
+  if (!scene || scene->device != ctx->device || std::isnan(margin)) return CCMP_EINVAL;
+  if (E == 0) return CCMP_OK;
+  { const int rc = geodesic_args(p, from, to, max_states, states, n_states, ok, carry_in, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; }
+  const GeoCall g{&K, p->delta, p->lambda, from, to, E, max_states, states, n_states, ok, newton_iters, carry_in, carry_out, round_budget, check_target};
+  const ccmp_launch::GeoScene sg{scene->dev, margin, blocked, clearance};
+  const int blocks = ccmp_host::plan_geodesic_scene(ctx, E, p->jacobian_mode != CCMP_JAC_FD);
+  if (p->jacobian_mode != CCMP_JAC_FD) HIP_TRY(ccmp_launch::geodesic_analytic_scene(g, sg, blocks, ctx->queue + kQGeoAnalytic, st));
+  else HIP_TRY(ccmp_launch::geodesic_scene(g, sg, blocks, ctx->queue + kQGeoTicket, st));
+  return CCMP_OK;
 }
 
 int ccmp_is_satisfied_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *q, uint8_t *ok, size_t B, void *hip_stream)

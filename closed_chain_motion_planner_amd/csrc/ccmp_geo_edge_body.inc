@@ -5,6 +5,10 @@
 // the same place).  The including scope provides: K (constants for scalar tests), KL (their LDS copy), steptab, rec, tid, pi, delta,
 // lambda, t (edge index), from, to, states, max_states, n_states, ok_out, newton_iters, carry_in, carry_out, round_budget,
 // check_target, ent (pool entry of a handed-over edge, or nullptr).
+// With CCMP_GEO_SCENE defined (geodesic_scene_kernel only; every other includer leaves it undefined and compiles the text it compiled
+// before) the reference's svc->isValid runs on the device: after a successful projection and before the step test, the proxy scene's
+// clearance of the state (ccmp_clearance.h) must exceed `margin`, else the edge ends there, blocked.  The scope then also provides
+// scene, margin, clr_ws (LDS), lane, blocked_out and clearance_out (nullable).
     double *out = states + t * (unsigned long long)max_states * 14ull;
     if (tid < 14) {
       if (ent) {
@@ -23,6 +27,10 @@
     bool suspended = false; // the edge used up the call's budget of Newton rounds: it stops between two states (ok = 2)
     bool fits = true; // false: an accepted state found the list full — the edge stops there and reports max_states + 1
     bool target_ok = true;
+#ifdef CCMP_GEO_SCENE
+    bool blocked = false; // the traversal ended at a state the scene refused
+    double clr = 0.0;     // the clearance of the state being booked
+#endif
     if (check_target) {
       // ConstrainedMotionValidator::checkMotion (src/planner/stefanBiPRM.cpp:397-398): isSatisfied(s2) first —
       // function(to) through one evaluation pass of the Newton routine (iteration cap 0: no update), then
@@ -103,6 +111,10 @@
           d_acc = CCMP_FMA(dd, dd, d_acc); // distance(scratch, to)
         }
         if (!(conv && jv)) break;                        // not on manifold
+#ifdef CCMP_GEO_SCENE
+        clr = state_clearance<128>(KL, scene, rec + fX, clr_ws, clr_ws + kClrFrames, clr_ws + kClrFrames + kClrCentres, tid, lane);
+        if (!(clr > margin)) { blocked = true; break; }  // svc->isValid(scratch): refused (before the list-full rule)
+#endif
         const double step = ccmp_sqrt(s_acc), newDist = ccmp_sqrt(d_acc);
         if (step > lambda * delta) break;                // deviated
         total_before = total;
@@ -118,6 +130,9 @@
           x_own = rec[fX + tid];
           out[(unsigned long long)n * 14ull + tid] = x_own;
         }
+#ifdef CCMP_GEO_SCENE
+        if (tid == 0 && clearance_out) clearance_out[t * (unsigned long long)max_states + (unsigned long long)n] = clr;
+#endif
         n++;
         if (!(dist >= delta)) break;
         // A call bounds the serial work it spends on one edge: past round_budget Newton rounds the edge stops HERE — between
@@ -134,6 +149,9 @@
       ok_out[t] = suspended ? (uint8_t)2 : (uint8_t)(target_ok && fits && dist <= delta);
       if (newton_iters) newton_iters[t] = its;
       if (carry_out) { carry_out[2 * t] = total; carry_out[2 * t + 1] = maxd; }
+#ifdef CCMP_GEO_SCENE
+      if (blocked_out) blocked_out[t] = blocked ? (uint8_t)1 : (uint8_t)0;
+#endif
 #ifdef CCMP_GEO_TRACE
       if (t < 65536) g_geo_trace[3 * t + 1] = wall_clock64();
 #endif

@@ -8,6 +8,7 @@
 #include <thread>
 #include <vector>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +16,7 @@
 #include "../../include/ccmp.h"
 #include "ccmp_ctx.h"
 #include "ccmp_resident.h"
+#include "ccmp_scene.h"
 
 using ccmp_host::DeviceGuard;
 using ccmp_host::ensure_stage;
@@ -98,7 +100,7 @@ struct HostIO {
   ccmp_ctx *ctx;
   char *dev = nullptr;  // what the kernels get
   char *host = nullptr; // pinned alias (small calls) or nullptr
-  struct Out { void *dst; size_t off, n; } outs[4];
+  struct Out { void *dst; size_t off, n; } outs[8]; // the most any entry point downloads: ccmp_geodesic_scene_host's seven
   int n_outs = 0;
   // every *_host call starts with the completion-word machinery off: a flag left over from a call that returned early
   // (an argument error behind want_done = true) must never make a later launch arm, or a later finish() poll, a word
@@ -130,7 +132,11 @@ struct HostIO {
   }
   int out(void *dst, size_t off, size_t n)
   {
-    if (host) { outs[n_outs++] = Out{dst, off, n}; return CCMP_OK; }
+    if (host) {
+      if (n_outs == (int)(sizeof outs / sizeof outs[0])) return CCMP_EINVAL; // (never: every caller stays within the table)
+      outs[n_outs++] = Out{dst, off, n};
+      return CCMP_OK;
+    }
     HIP_TRY(hipMemcpyAsync(dst, dev + off, n, hipMemcpyDeviceToHost, ctx->stream));
     return CCMP_OK;
   }
@@ -459,6 +465,56 @@ int ccmp_geodesic_host_ex(ccmp_ctx *ctx, const ccmp_problem *p, const double *fr
   if (carry_in && check_target) return CCMP_EINVAL;
   if (round_budget > 0 && !carry_out) return CCMP_EINVAL; // a suspended edge is useless without what its continuation needs
   return geodesic_host_common(ctx, p, from, to, E, max_states, states, n_states, ok, carry_in, carry_out, round_budget, check_target);
+}
+
+// the extend step with a proxy scene on host buffers: staged through the pinned block like geodesic_host_common (never the resident service)
+int ccmp_geodesic_scene_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *from, const double *to,
+                             size_t E, int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                             double *clearance, const double *carry_in, double *carry_out, int round_budget, int check_target)
+{
+  if (!ctx || !p) return CCMP_EINVAL;
+  // as ccmp_geodesic_scene_batch: the scene and the margin are checked before an empty batch returns
+  if (!scene || scene->device != ctx->device || std::isnan(margin)) return CCMP_EINVAL;
+  if (E == 0) return CCMP_OK;
+  if (!from || !to || !states || !n_states || !ok || max_states < 1) return CCMP_EINVAL;
+  if ((carry_in || carry_out || round_budget > 0) && max_states < 2) return CCMP_EINVAL; // as geodesic_common: before any buffer is touched
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  const size_t eb = E * 14 * sizeof(double);
+  const size_t sb = E * (size_t)max_states * 14 * sizeof(double);
+  const size_t cb = E * 2 * sizeof(double);
+  const size_t clb = E * (size_t)max_states * sizeof(double);
+  const size_t off_to = (eb + 255) & ~(size_t)255;
+  const size_t off_st = (off_to + eb + 255) & ~(size_t)255;
+  const size_t off_n = (off_st + sb + 255) & ~(size_t)255;
+  const size_t off_ok = (off_n + E * sizeof(int32_t) + 255) & ~(size_t)255;
+  const size_t off_ci = (off_ok + E + 255) & ~(size_t)255;
+  const size_t off_co = (off_ci + cb + 255) & ~(size_t)255;
+  const size_t off_it = (off_co + cb + 255) & ~(size_t)255;
+  const size_t off_bl = (off_it + E * sizeof(int32_t) + 255) & ~(size_t)255;
+  const size_t off_cl = (off_bl + E + 255) & ~(size_t)255;
+  HostIO io(ctx);
+  int rc = io.begin(off_cl + (clearance ? clb : 0));
+  if (rc != CCMP_OK) return rc;
+  if ((rc = io.in(0, from, eb)) != CCMP_OK) return rc;
+  if ((rc = io.in(off_to, to, eb)) != CCMP_OK) return rc;
+  if (carry_in && (rc = io.in(off_ci, carry_in, cb)) != CCMP_OK) return rc;
+  // entries the kernel does not write (entry 0, past the list) keep the caller's values
+  if (clearance && (rc = io.in(off_cl, clearance, clb)) != CCMP_OK) return rc;
+  rc = ccmp_geodesic_scene_batch(ctx, p, scene, margin, (const double *)io.dev, (const double *)(io.dev + off_to), E, max_states,
+                                 (double *)(io.dev + off_st), (int32_t *)(io.dev + off_n), (uint8_t *)(io.dev + off_ok),
+                                 newton_iters ? (int32_t *)(io.dev + off_it) : nullptr, blocked ? (uint8_t *)(io.dev + off_bl) : nullptr,
+                                 clearance ? (double *)(io.dev + off_cl) : nullptr, carry_in ? (const double *)(io.dev + off_ci) : nullptr,
+                                 carry_out ? (double *)(io.dev + off_co) : nullptr, round_budget, check_target, ctx->stream);
+  if (rc != CCMP_OK) return rc;
+  if ((rc = io.out(states, off_st, sb)) != CCMP_OK) return io.abandon(rc);
+  if ((rc = io.out(n_states, off_n, E * sizeof(int32_t))) != CCMP_OK) return io.abandon(rc);
+  if ((rc = io.out(ok, off_ok, E)) != CCMP_OK) return io.abandon(rc);
+  if (carry_out && (rc = io.out(carry_out, off_co, cb)) != CCMP_OK) return io.abandon(rc);
+  if (newton_iters && (rc = io.out(newton_iters, off_it, E * sizeof(int32_t))) != CCMP_OK) return io.abandon(rc);
+  if (blocked && (rc = io.out(blocked, off_bl, E)) != CCMP_OK) return io.abandon(rc);
+  if (clearance && (rc = io.out(clearance, off_cl, clb)) != CCMP_OK) return io.abandon(rc);
+  return io.finish();
 }
 
 // One shard of ccmp_*_sharded_host, on its context's device and stream: upload (mode 0), project, download, wait.  Runs

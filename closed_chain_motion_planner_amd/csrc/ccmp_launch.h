@@ -79,6 +79,14 @@ struct GeoCall {
   int check_target;       // checkMotion: isSatisfied(to) of every edge
 };
 
+/* what an extend-step call with a proxy scene adds (ccmp_geodesic_scene_batch) */
+struct GeoScene {
+  const ccmp::scene_dev *scene;
+  double margin;     // a state is valid when its clearance exceeds this
+  uint8_t *blocked;  // nullable, [E]
+  double *clearance; // nullable, [E][max_states]
+};
+
 /* one launch of project_fd_flat_kernel, the projector's latency kernel */
 struct FlatLaunch {
   int blocks = 0;
@@ -117,6 +125,8 @@ hipError_t geodesic_lat(const GeoCall &g, const GeoLaunch &l, hipStream_t st);
 hipError_t geodesic_group(const GeoCall &g, int blocks, unsigned long long *queue, const unsigned int *order, double *pool,
                           unsigned long long *pool_count, int handover_pct, const uint8_t *target_ok, hipStream_t st);
 hipError_t geodesic_analytic(const GeoCall &g, int blocks, unsigned long long *queue, hipStream_t st);
+hipError_t geodesic_scene(const GeoCall &g, const GeoScene &s, int blocks, unsigned long long *queue, hipStream_t st);
+hipError_t geodesic_analytic_scene(const GeoCall &g, const GeoScene &s, int blocks, unsigned long long *queue, hipStream_t st);
 hipError_t geodesic_scout_order(const GeoCall &g, int round_cap, uint16_t *pred, unsigned int *hist, unsigned int *order, int pairs,
                                 const ccmp_split_req *split, hipStream_t st);
 hipError_t geodesic_order(const double *from, const double *to, size_t E, double long_dist, unsigned int *counters, unsigned int *order, hipStream_t st);

@@ -237,6 +237,13 @@ int plan_geodesic_analytic(const ccmp_ctx *ctx, size_t E)
   return (int)(want < resident ? want : resident);
 }
 
+int plan_geodesic_scene(const ccmp_ctx *ctx, size_t E, bool analytic)
+{
+  if (analytic) return plan_geodesic_analytic(ctx, E);
+  const size_t resident = (size_t)ctx->num_cus * kGeoBlocksPerCu;
+  return (int)(E < resident ? E : resident);
+}
+
 // The extend step.  One 128-thread block per edge.  Up to the resident capacity every edge has its block at once and the
 // hardware dispatcher is the queue.  Beyond it the blocks are persistent and take tickets from an atomic word, handed out
 // through a long-edges-first order when the batch is large enough for the ordering pass to pay.  Two builds of the kernel: a
@@ -412,6 +419,12 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
       L.add("geodesic (analytic mode) E=%zu: geodesic_row16_kernel x %d wavefronts (four edges per wavefront, ticket queue; at most %d per CU)", n,
             plan_geodesic_analytic(ctx, n), kGeoAnalyticWavesPerCu);
       break;
+    case CCMP_CALL_GEODESIC_SCENE: {
+      const int fd = plan_geodesic_scene(ctx, n, false), an = plan_geodesic_scene(ctx, n, true);
+      L.add("geodesic with a proxy scene E=%zu: geodesic_scene_kernel x %d blocks (one edge per 128-thread block, ticket queue); analytic mode: "
+            "geodesic_row16_scene_kernel x %d wavefronts (four edges per wavefront, ticket queue; at most %d per CU)", n, fd, an, kGeoAnalyticWavesPerCu);
+      break;
+    }
     default: return CCMP_EINVAL;
   }
   // without a context the plan is the built-in policy on an ASSUMED device: say so (block counts and the thresholds that mark

@@ -61,6 +61,10 @@ GeoPlan plan_geodesic(const ccmp_ctx *ctx, size_t E, int round_budget, bool cont
 constexpr int kGeoAnalyticWavesPerCu = 8; // two per SIMD at occupancy 2
 int plan_geodesic_analytic(const ccmp_ctx *ctx, size_t E);
 
+/* the extend step with a proxy scene (ccmp_geodesic_scene_batch): analytic mode as plan_geodesic_analytic (geodesic_row16_scene_kernel),
+ * FD mode geodesic_scene_kernel's blocks (one per edge up to the latency build's resident blocks, persistent on a ticket beyond) */
+int plan_geodesic_scene(const ccmp_ctx *ctx, size_t E, bool analytic);
+
 /* ccmp_ctx_set_option behind the options ccmp_api.cpp handles itself ("resident"): the option table */
 __attribute__((visibility("hidden"))) int policy_set_option(ccmp_ctx *ctx, const char *name, long value);
 /* a context-shaped default for calls that have none at hand (ccmp_ctx_get_option / ccmp_ctx_describe with ctx == NULL):

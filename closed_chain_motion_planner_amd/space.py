@@ -150,16 +150,29 @@ class jy_ProjectedStateSpace:
         # a continuation starts from a stored state other than `from`: lists hold at least two states (the C++ adapter clamps
         # the same way); max_states = 1 therefore behaves like 2 — nothing is ever cut, edges that need more are continued
         cap = max(2, min(self.max_states, 16) if big else self.max_states)
-        states, n, ok, its, carry = self.constraint_.discrete_geodesic_batch(f, t, cap, check_target=check_target, want_carry=True,
-                                                                             round_budget=128 if big else 0)
+        # isValid = a ProxyValidityChecker's isValid on this constraint, interpolate == False: the proxy test runs on the device
+        # inside the traversal (discrete_geodesic_scene_batch) and only the checker's exact `inner` is asked here, about the
+        # listed states in order — the lists and bools of the host loop below, without one clearance launch per state
+        from .scene import ProxyValidityChecker
+
+        chk = getattr(self.isValid, "__self__", None)
+        pre = (not interpolate and isinstance(chk, ProxyValidityChecker) and chk.constraint is self.constraint_
+               and getattr(self.isValid, "__func__", None) is ProxyValidityChecker.isValid)
+        if pre:
+            states, n, ok, its, _, carry = self.constraint_.discrete_geodesic_scene_batch(
+                f, t, chk.scene, chk.margin, cap, check_target=check_target, want_carry=True, round_budget=128 if big else 0)
+        else:
+            states, n, ok, its, carry = self.constraint_.discrete_geodesic_batch(f, t, cap, check_target=check_target, want_carry=True,
+                                                                                 round_budget=128 if big else 0)
         # n_states == cap + 1: these lists did not fit and the traversal stopped there (ok == 2: the edge had spent the
         # call's Newton rounds).  Continue them from their last stored state until they are whole (ccmp_geodesic_batch_ex:
         # the same states as one uninterrupted traversal) — a cut list must never reach the validity test or the caller
         # as if it were complete.
-        whole = self.constraint_.continue_geodesics(t, states, n, ok, its, carry, cap, cont_states=max(self.max_states, 2))
+        whole = self.constraint_.continue_geodesics(t, states, n, ok, its, carry, cap, cont_states=max(self.max_states, 2),
+                                                    scene=chk.scene if pre else None, margin=chk.margin if pre else None)
         n, ok = n.cpu().numpy(), ok.cpu().numpy()
         rows = [None] * len(n)
-        for e, (st_e, ok_e, _) in whole.items():
+        for e, (st_e, ok_e, *_) in whole.items():
             rows[e], n[e], ok[e] = st_e, st_e.shape[0], ok_e
         left = [e for e in range(len(n)) if rows[e] is None and (n[e] > cap or ok[e] == 2)]
         if left:  # a truncated or suspended edge must never be reported as reached (ok == 2 is not a bool)
@@ -170,9 +183,10 @@ class jy_ProjectedStateSpace:
         for e in range(states.shape[0]):
             st = rows[e] if rows[e] is not None else states[e, : n[e]]
             good = bool(ok[e])
-            if not interpolate and self.isValid is not None:
+            valid = (chk.inner if pre else self.isValid) if not interpolate else None
+            if valid is not None:
                 for k in range(1, st.shape[0]):
-                    if not self.isValid(st[k]):
+                    if not valid(st[k]):
                         st = st[:k]
                         good = self.distance(st[-1], to[e]) <= delta  # the loop broke before dist was updated
                         break

@@ -236,7 +236,8 @@ enum {
   CCMP_CALL_PROJECT_ANALYTIC = 2, /* ccmp_project_batch with CCMP_JAC_ANALYTIC         */
   CCMP_CALL_GEODESIC = 3,         /* ccmp_geodesic_batch / _ex without a round budget  */
   CCMP_CALL_GEODESIC_BUDGET = 4,  /* ccmp_geodesic_batch_ex with round_budget > 0      */
-  CCMP_CALL_GEODESIC_ANALYTIC = 5 /* ccmp_geodesic_batch / _ex with CCMP_JAC_ANALYTIC  */
+  CCMP_CALL_GEODESIC_ANALYTIC = 5, /* ccmp_geodesic_batch / _ex with CCMP_JAC_ANALYTIC */
+  CCMP_CALL_GEODESIC_SCENE = 6     /* ccmp_geodesic_scene_batch, both Jacobian modes    */
 };
 int ccmp_ctx_describe(const ccmp_ctx *ctx, int call_kind, size_t n, char *buf, size_t cap);
 int ccmp_ctx_device(const ccmp_ctx *ctx);
@@ -286,7 +287,8 @@ int ccmp_compute_t_wo_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *
  * max_states + 1 (ok[e] = 0): repeat it with a larger buffer before anything is concluded from it (the adapter and the
  * Python mirror do) — a creeping edge (observed: 952 accepted states, each a hair closer to the target) must not hold
  * a whole launch, and a cut list must never look complete.  Runs as the reference does with interpolate == true; for
- * interpolate == false the host truncates at the first state its StateValidityChecker rejects.
+ * interpolate == false the host truncates at the first state its StateValidityChecker rejects, or, for a
+ * proxy scene's pre-filter, ccmp_geodesic_scene_batch applies it on the device.
  * With jacobian_mode = CCMP_JAC_ANALYTIC the traversal is one launch of a traversal kernel on the analytic projector's Newton round (four
  * edges per wavefront, no host synchronisation): the same lists, counts, flags and carries as the analytic mode's CPU restatement, bit for
  * bit, the round budget of ccmp_geodesic_batch_ex included; the resident service does not serve it. */
@@ -452,6 +454,38 @@ int ccmp_clearance_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene 
 /* the same on host buffers (a single state: what a StateValidityChecker wrapper calls before MoveIt) */
 int ccmp_clearance_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, const double *q, size_t B, double margin,
                         double *clearance, int32_t *pair, uint8_t *free_out);
+/* The extend step with the proxy pre-filter on the device: jy_ProjectedStateSpace::discreteGeodesic with interpolate == false
+ * (src/base/jy_ProjectedStateSpace.cpp:65-68, what growTree and checkMotion run) where svc->isValid(x) is
+ * "ccmp_clearance_batch's clearance of x > margin" (the rule of its free_out).  Per edge the result equals, bit for bit and in
+ * both Jacobian modes, the reference's loop with that validity test (the CPU checker oracle/ccmp_oracle.c: its resumable
+ * discrete geodesic with a validity callback that asks its clearance): states, n_states, ok, newton_iters, carry_out.  Arguments, outputs, carries, the round budget (ok = 2) and check_target as
+ * ccmp_geodesic_batch_ex; in addition:
+ *   - where the test runs: after a successful projection (converged and jointValid), before the step test — the reference's
+ *     order, so the clearances evaluated are exactly the oracle's valid() calls;
+ *   - a refusal beats "list full": a refused state that finds the list full ends the edge with n_states = the states stored
+ *     and blocked set, not max_states + 1;
+ *   - never tested: row 0 (`from`, or the first state of a continuation) and the target under check_target (checkMotion does
+ *     not call isValid(s2));
+ *   - a refused edge ends as the reference's break: ok = (distance of the last accepted state to the target) <= delta, and its
+ *     Newton count includes the refused state's projection;
+ *   - blocked (nullable, uint8[E]) = 1 exactly when the traversal ended at a state the scene refused (the oracle's last valid()
+ *     call returned 0).  A blocked edge is final: do not continue it;
+ *   - clearance (nullable, double[E][max_states]): entry k = the clearance of listed state k, 1 <= k < min(n_states, max_states);
+ *     entry 0 and entries past the list are not written.  Bit-identical to ccmp_clearance_batch of that state;
+ *   - continuations keep their meaning: pass the same scene and margin, and first call + continuations give one uninterrupted
+ *     traversal;
+ *   - margin = -inf: the results of ccmp_geodesic_batch_ex, blocked all 0; margin = +inf: every edge that enters the loop stops
+ *     at its first projected state with n_states = 1, blocked = 1 if that projection succeeded (0 if it failed).
+ * CCMP_EINVAL besides ccmp_geodesic_batch_ex's cases: scene NULL, a scene of another device than ctx's, margin NaN.  One launch
+ * (FD: geodesic_scene_kernel, one 128-thread block per edge; analytic: geodesic_row16_scene_kernel, sixteen lanes per edge), no
+ * host synchronisation, capturable; never the bulk form of the FD extend step, never the resident service. */
+int ccmp_geodesic_scene_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *from, const double *to,
+                              size_t E, int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                              double *clearance, const double *carry_in, double *carry_out, int round_budget, int check_target, void *hip_stream);
+/* the same on host buffers, synchronous */
+int ccmp_geodesic_scene_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *from, const double *to,
+                             size_t E, int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                             double *clearance, const double *carry_in, double *carry_out, int round_budget, int check_target);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

@@ -482,6 +482,7 @@ public:
     check(ccmp_clearance_host(proj_.ctx(), &proj_.problem(), scene_, q, B, margin, clearance, pair, free_out), "ccmp_clearance_host");
   }
   const ccmp_scene *handle() const { return scene_; }
+  const Projector &projector() const { return proj_; }
 
   // AllowedCollisionMatrix::setEntry(g, h, true) on a 32-word matrix
   static void allow(uint32_t *allowed32, int g, int h)
@@ -505,6 +506,90 @@ private:
   const Projector &proj_;
   ccmp_scene *scene_ = nullptr;
 };
+
+// discreteGeodesicBatch with the proxy pre-filter ON THE DEVICE (ccmp_geodesic_scene_host): with interpolate == false the
+// traversal itself refuses a state whose clearance in `scene` does not exceed `margin` — before the step test, where the
+// reference's loop asks its StateValidityChecker — and `exact` (the checker behind the proxies: MoveIt in the reference) is then
+// asked only about the listed states, in order, an edge stopping at its first refusal as above.  (*blocked)[e] (nullable) = 1:
+// the edge ended at a state the proxies refused (the exact checker had accepted everything before it).  scene == nullptr or
+// interpolate: the overload above with `exact` as the checker.  The scene must belong to proj's context.
+template <class ValidFn>
+inline void discreteGeodesicBatch(const Projector &proj, const double *from, const double *to, size_t E, bool interpolate, ValidFn exact,
+                                  std::vector<std::vector<std::vector<double>>> *geodesics, std::vector<char> *reached, int max_states,
+                                  bool check_target, double delta, double lambda, const ProxyScene *scene, double margin,
+                                  std::vector<char> *blocked = nullptr)
+{
+  if (blocked) blocked->assign(E, 0);
+  if (!scene || interpolate) {
+    discreteGeodesicBatch(proj, from, to, E, interpolate, exact, geodesics, reached, max_states, check_target, delta, lambda);
+    return;
+  }
+  if (reached) reached->assign(E, 0);
+  if (geodesics) geodesics->assign(E, {});
+  if (E == 0) return;
+  if (max_states < 2) max_states = 2;
+  const bool big = E >= 1024; // the first pass's shape as above
+  const int first_cap = big && max_states > 16 ? 16 : max_states;
+  const int first_budget = big ? 128 : 0;
+  ccmp_problem pb;
+  std::vector<double> states(E * (size_t)first_cap * 14), carry(E * 2);
+  std::vector<int32_t> n(E);
+  std::vector<uint8_t> ok(E), bl(E);
+  {
+    std::lock_guard<std::mutex> hold(proj.mutex());
+    pb = proj.problem();
+    if (delta > 0) pb.delta = delta;
+    if (lambda > 0) pb.lambda = lambda;
+    check(ccmp_geodesic_scene_host(proj.ctx(), &pb, scene->handle(), margin, from, to, E, first_cap, states.data(), n.data(), ok.data(), nullptr,
+                                   bl.data(), nullptr, nullptr, carry.data(), first_budget, check_target ? 1 : 0),
+          "ccmp_geodesic_scene_host");
+  }
+  std::vector<double> more((size_t)max_states * 14);
+  for (size_t e = 0; e < E; ++e) {
+    std::vector<std::vector<double>> list;
+    const double *st = &states[e * (size_t)first_cap * 14];
+    const double *to_e = to + 14 * e;
+    double cr[2] = {carry[2 * e], carry[2 * e + 1]};
+    int32_t ne = n[e];
+    uint8_t oke = ok[e], ble = bl[e];
+    bool good = false, cut = false;
+    std::vector<double> last(14);
+    int first = 0;
+    int cap = first_cap;
+    for (;;) {
+      const int have = ne > cap ? cap : ne;
+      for (int k = first; k < have && !cut; ++k) {
+        const double *row = st + (size_t)k * 14;
+        if (!(list.empty() && k == 0) && !exact(row)) {
+          double d = 0;
+          for (int i = 0; i < 14; ++i) { const double df = last[i] - to_e[i]; d += df * df; }
+          good = std::sqrt(d) <= pb.delta;
+          cut = true;
+          break;
+        }
+        last.assign(row, row + 14);
+        list.emplace_back(row, row + 14);
+      }
+      if (cut) break;
+      // a blocked edge is final (the traversal's ok is the reference's answer behind the break); else as above
+      if (ne <= cap && oke != 2) { good = oke != 0; if (blocked) (*blocked)[e] = (char)ble; break; }
+      double cr_out[2];
+      {
+        std::lock_guard<std::mutex> hold(proj.mutex());
+        check(ccmp_geodesic_scene_host(proj.ctx(), &pb, scene->handle(), margin, last.data(), to_e, 1, max_states, more.data(), &ne, &oke, nullptr,
+                                       &ble, nullptr, cr, cr_out, 0, 0),
+              "ccmp_geodesic_scene_host(continue)");
+      }
+      cr[0] = cr_out[0];
+      cr[1] = cr_out[1];
+      st = more.data();
+      cap = max_states;
+      first = 1;
+    }
+    if (reached) (*reached)[e] = good ? 1 : 0;
+    if (geodesics) (*geodesics)[e] = std::move(list);
+  }
+}
 
 // ---- dump formats of the reference's planner run ----------------------------------------------------------------------
 // PathGeometric::printAsMatrix as ConstrainedProblem::solveOnce writes `<obj>_path.txt`
@@ -698,6 +783,45 @@ private:
 };
 typedef std::shared_ptr<KinematicChainConstraint> ChainConstraintPtr;
 
+// A StateValidityChecker that asks the proxy scene first and the exact checker (the reference's
+// KinematicChainValidityChecker, i.e. MoveIt) only for states the proxies do not already refuse:
+//   si->setStateValidityChecker(std::make_shared<PrefilteredValidityChecker>(si, scene, valid_checker_));
+// `reject_below` = 0 with inscribed proxies; the answer for every state MoveIt is asked about is MoveIt's.
+class PrefilteredValidityChecker : public ompl::base::StateValidityChecker {
+public:
+  PrefilteredValidityChecker(const ompl::base::SpaceInformationPtr &si, std::shared_ptr<ccmp::ProxyScene> scene,
+                             ompl::base::StateValidityCheckerPtr exact, double reject_below = 0.0)
+    : ompl::base::StateValidityChecker(si), scene_(std::move(scene)), exact_(std::move(exact)), reject_below_(reject_below)
+  {
+  }
+  bool isValid(const ompl::base::State *state) const override
+  {
+    const auto &q = *state->as<ompl::base::ConstrainedStateSpace::StateType>();  // an Eigen::Map over the 14 joints, as in
+    const double clr = scene_->clearance(&q[0]);                                 // KinematicChain.cpp:94-99
+    if (!(clr > reject_below_)) { rejected_++; return false; }
+    asked_++;
+    return exact_ ? exact_->isValid(state) : true;
+  }
+  uint64_t rejectedByProxies() const { return rejected_.load(); }
+  uint64_t askedExact() const { return asked_.load(); }
+  // what jy_ProjectedStateSpace's device path uses (the proxies then run inside the traversal, ccmp_geodesic_scene_host):
+  // the scene, the threshold, the exact checker alone — counted as isValid counts a state the proxies passed — and the count
+  // of a state the proxies refused
+  const std::shared_ptr<ccmp::ProxyScene> &scene() const { return scene_; }
+  double rejectBelow() const { return reject_below_; }
+  bool isValidExact(const ompl::base::State *state) const
+  {
+    asked_++;
+    return exact_ ? exact_->isValid(state) : true;
+  }
+  void countRejected() const { rejected_++; }
+
+private:
+  std::shared_ptr<ccmp::ProxyScene> scene_;
+  ompl::base::StateValidityCheckerPtr exact_;
+  double reject_below_;
+  mutable std::atomic<uint64_t> rejected_{0}, asked_{0};
+};
 // jy_ProjectedStateSampler (include/closed_chain_motion_planner/base/jy_ProjectedStateSpace.h:18-29): same
 // name, same overrides; all three draw from the GPU's counter-based samplers through refill-on-empty buffers
 // (sampleUniform: `batch` samples per launch; Near / Gaussian: a look-ahead around the current reference state).
@@ -790,16 +914,31 @@ public:
     auto &&svc = si_->getStateValidityChecker();
     std::vector<std::vector<std::vector<double>>> lists;
     ompl::base::State *scratch = allocState();
+    const PrefilteredValidityChecker *pre = devicePrefilter(svc.get(), interpolate);
+    std::vector<char> blocked;
     const bool done = chain_->guarded([&] {
-      ccmp::discreteGeodesicBatch(proj, a.data(), b.data(), E, interpolate,
-                                  [&](const double *q) {
-                                    auto &x = *scratch->as<StateType>();
-                                    for (int i = 0; i < 14; ++i) x[i] = q[i];
-                                    return svc->isValid(scratch);
-                                  },
-                                  geodesics ? &lists : nullptr, reached, 64, false, delta_, lambda_); // setDelta / setLambda of the base class
+      if (pre)  // the proxies inside the traversal, the exact checker on the listed states
+        ccmp::discreteGeodesicBatch(proj, a.data(), b.data(), E, false,
+                                    [&](const double *q) {
+                                      auto &x = *scratch->as<StateType>();
+                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
+                                      return pre->isValidExact(scratch);
+                                    },
+                                    geodesics ? &lists : nullptr, reached, 64, false, delta_, lambda_, pre->scene().get(), pre->rejectBelow(),
+                                    &blocked);
+      else
+        ccmp::discreteGeodesicBatch(proj, a.data(), b.data(), E, interpolate,
+                                    [&](const double *q) {
+                                      auto &x = *scratch->as<StateType>();
+                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
+                                      return svc->isValid(scratch);
+                                    },
+                                    geodesics ? &lists : nullptr, reached, 64, false, delta_, lambda_); // setDelta / setLambda of the base class
     });
     freeState(scratch);
+    if (pre && done)
+      for (size_t e = 0; e < E; ++e)
+        if (blocked[e]) pre->countRejected();
     if (!done) {  // the GPU call failed (KinematicChainConstraint::lastError()): no edge was extended
       if (geodesics) geodesics->assign(E, {});
       if (reached) reached->assign(E, 0);
@@ -830,17 +969,35 @@ private:
     std::vector<std::vector<double>> states;
     ompl::base::State *scratch = allocState();
     bool ok = false;
+    const PrefilteredValidityChecker *pre = devicePrefilter(svc.get(), interpolate);
+    std::vector<char> blocked;
     const bool done = chain_->guarded([&] {
-      ok = ccmp::discreteGeodesic(proj, a, b, interpolate,
-                                  [&](const double *q) {
-                                    auto &x = *scratch->as<StateType>();
-                                    for (int i = 0; i < 14; ++i) x[i] = q[i];
-                                    return svc->isValid(scratch);
-                                  },
-                                  geodesic ? &states : nullptr, 64, check_target, delta_,
-                                  lambda_);  // setDelta / setLambda of the base class stay the source of truth
+      if (pre) {  // the proxies inside the traversal, the exact checker on the listed states
+        std::vector<std::vector<std::vector<double>>> lists;
+        std::vector<char> reached;
+        ccmp::discreteGeodesicBatch(proj, a, b, 1, false,
+                                    [&](const double *q) {
+                                      auto &x = *scratch->as<StateType>();
+                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
+                                      return pre->isValidExact(scratch);
+                                    },
+                                    geodesic ? &lists : nullptr, &reached, 64, check_target, delta_, lambda_, pre->scene().get(),
+                                    pre->rejectBelow(), &blocked);
+        ok = reached[0] != 0;
+        if (geodesic) states = std::move(lists[0]);
+      } else {
+        ok = ccmp::discreteGeodesic(proj, a, b, interpolate,
+                                    [&](const double *q) {
+                                      auto &x = *scratch->as<StateType>();
+                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
+                                      return svc->isValid(scratch);
+                                    },
+                                    geodesic ? &states : nullptr, 64, check_target, delta_,
+                                    lambda_);  // setDelta / setLambda of the base class stay the source of truth
+      }
     });
     freeState(scratch);
+    if (pre && done && blocked[0]) pre->countRejected();
     if (!done) {  // the GPU call failed (KinematicChainConstraint::lastError()): "not reached", no states
       if (geodesic) geodesic->clear();
       return false;
@@ -855,6 +1012,17 @@ private:
       }
     }
     return ok;
+  }
+
+  // the space information's checker when the extend step can run its proxies on the device: a PrefilteredValidityChecker whose
+  // scene lives on this space's context, and interpolate == false (the checker is asked at all).  Its counters then count what
+  // the reference's order counts: per listed state one exact question, one proxy refusal for an edge that ended at one.
+  const PrefilteredValidityChecker *devicePrefilter(const ompl::base::StateValidityChecker *svc, bool interpolate) const
+  {
+    if (interpolate) return nullptr;
+    const auto *pre = dynamic_cast<const PrefilteredValidityChecker *>(svc);
+    if (!pre || !pre->scene() || pre->scene()->projector().ctx() != chain_->impl().ctx()) return nullptr;
+    return pre;
   }
 
   std::shared_ptr<KinematicChainConstraint> chain_;
@@ -889,34 +1057,6 @@ inline jy_ProjectedStateSampler::jy_ProjectedStateSampler(const jy_ProjectedStat
 {
 }
 
-// A StateValidityChecker that asks the proxy scene first and the exact checker (the reference's
-// KinematicChainValidityChecker, i.e. MoveIt) only for states the proxies do not already refuse:
-//   si->setStateValidityChecker(std::make_shared<PrefilteredValidityChecker>(si, scene, valid_checker_));
-// `reject_below` = 0 with inscribed proxies; the answer for every state MoveIt is asked about is MoveIt's.
-class PrefilteredValidityChecker : public ompl::base::StateValidityChecker {
-public:
-  PrefilteredValidityChecker(const ompl::base::SpaceInformationPtr &si, std::shared_ptr<ccmp::ProxyScene> scene,
-                             ompl::base::StateValidityCheckerPtr exact, double reject_below = 0.0)
-    : ompl::base::StateValidityChecker(si), scene_(std::move(scene)), exact_(std::move(exact)), reject_below_(reject_below)
-  {
-  }
-  bool isValid(const ompl::base::State *state) const override
-  {
-    const auto &q = *state->as<ompl::base::ConstrainedStateSpace::StateType>();  // an Eigen::Map over the 14 joints, as in
-    const double clr = scene_->clearance(&q[0]);                                 // KinematicChain.cpp:94-99
-    if (!(clr > reject_below_)) { rejected_++; return false; }
-    asked_++;
-    return exact_ ? exact_->isValid(state) : true;
-  }
-  uint64_t rejectedByProxies() const { return rejected_.load(); }
-  uint64_t askedExact() const { return asked_.load(); }
-
-private:
-  std::shared_ptr<ccmp::ProxyScene> scene_;
-  ompl::base::StateValidityCheckerPtr exact_;
-  double reject_below_;
-  mutable std::atomic<uint64_t> rejected_{0}, asked_{0};
-};
 #endif  // CCMP_WITH_OMPL
 
 #endif  // CCMP_OMPL_ADAPTER_HPP

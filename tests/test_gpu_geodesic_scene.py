@@ -1,0 +1,437 @@
+"""The extend step with a proxy scene's validity test on the device (ccmp_geodesic_scene_batch / _host): the reference's loop with
+interpolate == false, svc->isValid(x) = "clearance(x) > margin".  Compared bit for bit with the oracle's
+orc_discrete_geodesic_ex(interpolate = 0) behind a validity callback that calls orc_clearance, in both Jacobian modes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from conftest import load_roadmap
+from oracle_binding import pack_proxies
+from test_gpu_analytic_extend import _edges, _tilt
+from test_gpu_parity import _constraint, _oracle_problem
+
+pytestmark = pytest.mark.gpu
+
+dp = C.POINTER(C.c_double)
+VALID_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_void_p)
+
+
+def _random_scene(c, seed=0x5CE1):
+    """64 spheres on every kind of frame, 8 boxes (turned ones among them), a random allowed-pair matrix (test_gpu_scene.py)"""
+    from closed_chain_motion_planner_amd import scene as S
+
+    rng = np.random.default_rng(seed)
+    frames = [S.FRAME_WORLD] + list(range(18))
+    sph = [(int(rng.choice(frames)), int(rng.integers(0, 32)), tuple(rng.uniform(-0.15, 0.15, 3)), float(rng.uniform(0.0, 0.08)))
+           for _ in range(64)]
+    sph[5] = (S.FRAME_WORLD, 3, (0.4, 0.0, 1.5), 0.2)
+    boxes = []
+    for b in range(8):
+        Q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+        boxes.append((int(rng.integers(0, 32)), tuple(rng.uniform([-0.2, -0.8, 0.6], [0.9, 0.8, 1.8])), np.eye(3) if b < 2 else Q,
+                      tuple(rng.uniform(0.0, 0.3, 3))))
+    allowed = [int(v) for v in rng.integers(0, 2 ** 32, 32, dtype=np.uint64) & rng.integers(0, 2 ** 32, 32, dtype=np.uint64)]
+    return S.ProxyScene(c, sph, boxes, allowed)
+
+
+class OracleScene:
+    """orc_discrete_geodesic_ex with valid(x) = orc_clearance(x) > margin; records every valid() answer"""
+
+    def __init__(self, oracle, P, sc, margin):
+        self.o, self.P, self.margin = oracle, P, float(margin)
+        self.packed = pack_proxies(sc.spheres, sc.boxes, sc.allowed)
+        self.answers, self.clr = [], []
+
+        def valid(x, _user):
+            sa, ns, ba, nb, al = self.packed
+            clr, pair = C.c_double(0.0), C.c_int32(0)
+            self.o.lib.orc_clearance(C.byref(self.P), sa, ns, ba, nb, al, x, C.byref(clr), C.byref(pair))
+            self.clr.append(clr.value)
+            self.answers.append(1 if clr.value > self.margin else 0)
+            return self.answers[-1]
+
+        self.fn = VALID_FN(valid)
+
+    def edge(self, a, b, max_states, carry_in=None):
+        """-> ok, states (min(n, max_states), 14), n, its, carry (2,), blocked, clearances of the accepted states"""
+        self.answers, self.clr = [], []
+        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+        out = np.zeros((max_states, 14)); n = C.c_int(0); its = C.c_int64(0); cout = np.zeros(2)
+        cin = None if carry_in is None else np.ascontiguousarray(carry_in, dtype=np.float64)
+        ok = self.o.lib.orc_discrete_geodesic_ex(C.byref(self.P), a.ctypes.data_as(dp), b.ctypes.data_as(dp), 0,
+                                                 C.cast(self.fn, C.c_void_p), None, out.ctypes.data_as(dp), max_states, C.byref(n),
+                                                 C.byref(its), cin.ctypes.data_as(dp) if cin is not None else None, cout.ctypes.data_as(dp))
+        blocked = 1 if (self.answers and self.answers[-1] == 0) else 0
+        return int(ok), out[: min(n.value, max_states)].copy(), n.value, its.value, cout, blocked, list(self.clr)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _pick_margin(c, sc, frm, to, ms):
+    """a margin from the clearance distribution of the unfiltered traversal: the median of each edge's smallest clearance"""
+    st, n, ok, _ = c.discrete_geodesic_batch(frm, to, ms)
+    clr = sc.clearance_batch(st.reshape(-1, 14).contiguous(), 0.0, want_pair=False)[0].reshape(n.shape[0], ms).cpu().numpy()
+    n = n.cpu().numpy()
+    mins = [clr[e, 1:min(n[e], ms)].min() for e in range(len(n)) if min(n[e], ms) >= 2]
+    return float(np.median(mins)), clr, n
+
+
+def _check_against_oracle(c, P, oracle, sc, margin, frm, to, ms, need_blocked=True):
+    got = c.discrete_geodesic_scene_batch(frm, to, sc, margin, ms, want_clearance=True, want_carry=True)
+    st, n, ok, its, bl, clr, carry = [x.cpu().numpy() for x in got]
+    orc = OracleScene(oracle, P, sc, margin)
+    f, t = frm.cpu().numpy(), to.cpu().numpy()
+    first_blocked = 0
+    for e in range(f.shape[0]):
+        ok_o, st_o, n_o, its_o, c_o, bl_o, clr_o = orc.edge(f[e], t[e], ms)
+        assert n[e] == n_o and ok[e] == ok_o and its[e] == its_o and bl[e] == bl_o, (e, n[e], n_o, ok[e], ok_o, its[e], its_o, bl[e], bl_o)
+        m = min(n_o, ms)
+        assert np.array_equal(_bits(st[e, :m]), _bits(st_o)), e
+        assert np.array_equal(_bits(carry[e]), _bits(c_o)), e
+        # the clearances of the listed states: the oracle's valid() calls in order, those of the accepted ones
+        assert np.array_equal(_bits(clr[e, 1:m]), _bits(clr_o[: m - 1])), e
+        assert np.isnan(clr[e, 0]) and np.isnan(clr[e, m:]).all(), e
+        first_blocked += int(bl_o and n_o == 1)
+    frac = bl.mean()
+    if need_blocked:
+        assert 0.2 <= frac <= 0.8, frac
+        assert first_blocked >= 1
+    return bl
+
+
+@pytest.mark.parametrize("obj", ["Wine_Bottle", "stefan"])
+def test_fd_bitwise_against_oracle(gpu_ctx, oracle_det, obj):
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint(obj, gpu_ctx)
+    P = _oracle_problem(oracle_det, c)
+    sc = S.ProxyValidityChecker(c).scene if obj == "Wine_Bottle" else _random_scene(c)
+    E, ms = 64, 64
+    frm, to = _edges(c, E, 0x5C0 + len(obj))
+    margin, _, _ = _pick_margin(c, sc, frm, to, ms)
+    _check_against_oracle(c, P, oracle_det, sc, margin, frm, to, ms)
+
+
+def test_fd_recorded_roadmap_edges(gpu_ctx, oracle_det):
+    import torch
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx)
+    P = _oracle_problem(oracle_det, c)
+    sc = S.ProxyValidityChecker(c).scene
+    nodes, edges = load_roadmap("Wine_Bottle")
+    edges = edges[:48]
+    frm = torch.as_tensor(np.array([nodes[e[0]] for e in edges])).cuda().contiguous()
+    to = torch.as_tensor(np.array([nodes[e[1]] for e in edges])).cuda().contiguous()
+    _check_against_oracle(c, P, oracle_det, sc, -0.03, frm, to, 32, need_blocked=False)
+
+
+@pytest.mark.parametrize("variant", ["diagonal", "tilted"])
+def test_analytic_bitwise_against_oracle(gpu_ctx, oracle_det, variant):
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx, mode=1)
+    if variant == "tilted":
+        _tilt(c)
+    P = _oracle_problem(oracle_det, c)
+    assert P.jacobian_mode == 1
+    sc = S.ProxyValidityChecker(c).scene
+    E, ms = 48, 64
+    frm, to = _edges(c, E, 0x5C1)
+    margin, _, _ = _pick_margin(c, sc, frm, to, ms)
+    _check_against_oracle(c, P, oracle_det, sc, margin, frm, to, ms)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_refusal_on_a_full_list(gpu_ctx, oracle_det, mode):
+    """a refused state that finds the list full: n = max_states and blocked, not max_states + 1"""
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx, mode=mode)
+    P = _oracle_problem(oracle_det, c)
+    sc = S.ProxyValidityChecker(c).scene
+    frm, to = _edges(c, 64, 0x5C2)
+    _, clr, n = _pick_margin(c, sc, frm, to, 64)
+    ms = 3
+    cand = [e for e in range(len(n)) if n[e] > ms + 1 and clr[e, ms] < min(clr[e, 1], clr[e, 2])]
+    assert cand
+    orc = OracleScene(oracle_det, P, sc, 0.0)
+    for e in cand[:4]:
+        margin = float(clr[e, ms])  # refuses listed state `ms` exactly (clearance == margin), accepts the ones before
+        st, nn, ok, its, bl = [x.cpu().numpy() for x in c.discrete_geodesic_scene_batch(frm[e:e + 1], to[e:e + 1], sc, margin, ms)]
+        assert nn[0] == ms and bl[0] == 1 and ok[0] == 0
+        orc.margin = margin
+        ok_o, st_o, n_o, its_o, _, bl_o, _ = orc.edge(frm[e].cpu().numpy(), to[e].cpu().numpy(), ms)
+        assert (n_o, ok_o, its_o, bl_o) == (nn[0], ok[0], its[0], bl[0])
+        assert np.array_equal(_bits(st[0]), _bits(st_o))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_round_budget_and_continuation(gpu_ctx, oracle_det, mode):
+    """budget + continuations with the same scene and margin = one uninterrupted traversal"""
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx, mode=mode)
+    sc = S.ProxyValidityChecker(c).scene
+    E, ms = 256, 16
+    frm, to = _edges(c, E, 0x5C3)
+    margin, _, _ = _pick_margin(c, sc, frm, to, 64)
+    whole = [x.cpu().numpy() for x in c.discrete_geodesic_scene_batch(frm, to, sc, margin, 256)]
+    st, n, ok, its, bl, carry = c.discrete_geodesic_scene_batch(frm, to, sc, margin, ms, want_carry=True, round_budget=8)
+    assert int((ok == 2).sum()) > 0 and int((n > ms).sum()) >= 0
+    cont = c.continue_geodesics(to, st, n, ok, its, carry, ms, round_budget=8, scene=sc, margin=margin)
+    st_h, n_h, ok_h, its_h, bl_h = [x.cpu().numpy() for x in (st, n, ok, its, bl)]
+    for e in range(E):
+        if e in cont:
+            s_e, ok_e, its_e, bl_e = cont[e]
+            n_e = s_e.shape[0]
+        else:
+            n_e, ok_e, its_e, bl_e = n_h[e], ok_h[e], its_h[e], bl_h[e]
+            s_e = st_h[e, :n_e]
+        assert (n_e, ok_e, its_e, bl_e) == (whole[1][e], whole[2][e], whole[3][e], whole[4][e]), e
+        assert np.array_equal(_bits(s_e), _bits(whole[0][e, :n_e])), e
+    assert whole[4].any() and not whole[4].all()
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_check_target_and_margin_limits(gpu_ctx, oracle_det, mode):
+    import torch
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx, mode=mode)
+    sc = S.ProxyValidityChecker(c).scene
+    E, ms = 128, 32
+    frm, to = _edges(c, E, 0x5C4)
+    # check_target with a target off the manifold, under a margin that refuses every state it is asked about: the target is never
+    # scene-tested — n = 1, ok = 0, blocked = 0
+    bad = to.clone()
+    bad[:, 3] += 0.3
+    st, n, ok, its, bl = c.discrete_geodesic_scene_batch(frm, bad, sc, float("inf"), ms, check_target=True)
+    sat = c.is_satisfied_batch(bad)
+    off = sat == 0
+    assert int(off.sum()) > 0
+    assert (n[off] == 1).all() and (ok[off] == 0).all() and (bl[off] == 0).all()
+    # margin = -inf: ccmp_geodesic_batch_ex bit for bit, nothing blocked — also where the plain call takes its bulk form
+    # (round budget, geodesic_group_min edges or more)
+    group_min = int(gpu_ctx.get_option("geodesic_group_min"))
+    for EE, budget in ((E, 0), (E, 16), (max(group_min - 64, 1), 128), (group_min + 64, 128)):
+        f2, t2 = (frm, to) if EE == E else _edges(c, EE, 0x5C9)
+        ref = c.discrete_geodesic_batch(f2, t2, ms, want_carry=True, round_budget=budget)
+        got = c.discrete_geodesic_scene_batch(f2, t2, sc, float("-inf"), ms, want_carry=True, round_budget=budget)
+        live = torch.arange(ms, device=f2.device)[None, :] < ref[1].clamp(max=ms)[:, None]
+        for k in (1, 2, 3):
+            assert torch.equal(got[k], ref[k]), (EE, budget)
+        assert torch.equal(got[0][live].view(torch.int64), ref[0][live].view(torch.int64)), (EE, budget)
+        assert torch.equal(got[5].view(torch.int64), ref[4].view(torch.int64)), (EE, budget)
+        assert int(got[4].sum()) == 0
+    # margin = +inf: every edge that enters the loop stops at its first projected state
+    st, n, ok, its, bl = c.discrete_geodesic_scene_batch(frm, to, sc, float("inf"), ms)
+    ref = c.discrete_geodesic_batch(frm, to, ms)
+    moved = ref[1] > 1  # the first projection succeeded (and passed the step tests): the plain traversal stored it
+    assert (n == 1).all()
+    assert (bl[moved] == 1).all()
+    assert int(moved.sum()) > E // 2
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_infinite_margin_blocks_exactly_the_successful_first_projections(gpu_ctx, oracle_det, mode):
+    """margin = +inf with an iteration cap that makes many first projections fail: blocked = 1 exactly where the projection
+    succeeded (the oracle's valid() was called), 0 where it failed"""
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx, mode=mode)
+    sc = S.ProxyValidityChecker(c).scene
+    E, ms = 48, 8
+    frm, to = _edges(c, E, 0x5CA)
+    c.problem.max_iter = 3
+    P = _oracle_problem(oracle_det, c)
+    st, n, ok, its, bl = [x.cpu().numpy() for x in c.discrete_geodesic_scene_batch(frm, to, sc, float("inf"), ms)]
+    orc = OracleScene(oracle_det, P, sc, float("inf"))
+    f, t = frm.cpu().numpy(), to.cpu().numpy()
+    for e in range(E):
+        ok_o, st_o, n_o, its_o, _, bl_o, _ = orc.edge(f[e], t[e], ms)
+        assert (n[e], ok[e], its[e], bl[e]) == (n_o, ok_o, its_o, bl_o), e
+        assert n[e] == 1
+    assert 0 < int(bl.sum()) < E
+
+
+def test_argument_errors(gpu_ctx):
+    import torch
+    from closed_chain_motion_planner_amd import _lib
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx)
+    sc = S.ProxyValidityChecker(c).scene
+    frm, to = _edges(c, 4, 0x5C5)
+    ms = 8
+    st = torch.empty((4, ms, 14), dtype=torch.float64, device="cuda")
+    n = torch.empty(4, dtype=torch.int32, device="cuda")
+    ok = torch.empty(4, dtype=torch.uint8, device="cuda")
+    L = _lib.lib()
+
+    def call(scene, margin, **kw):
+        a = dict(max_states=ms, states=st.data_ptr(), carry_in=None, carry_out=None, budget=0, check_target=0)
+        a.update(kw)
+        return L.ccmp_geodesic_scene_batch(gpu_ctx.handle, C.byref(c.problem), scene, margin, frm.data_ptr(), to.data_ptr(), 4, a["max_states"],
+                                           a["states"], n.data_ptr(), ok.data_ptr(), None, None, None, a["carry_in"], a["carry_out"],
+                                           a["budget"], a["check_target"], None)
+
+    EINVAL = -1
+    assert call(None, 0.0) == EINVAL
+    assert call(sc._h, float("nan")) == EINVAL
+    assert call(sc._h, 0.0, states=None) == EINVAL
+    assert call(sc._h, 0.0, max_states=0) == EINVAL
+    assert call(sc._h, 0.0, budget=4) == EINVAL  # a round budget without carry_out
+    assert call(sc._h, 0.0) == 0
+    torch.cuda.synchronize()
+
+
+def test_stream_capture(gpu_ctx, oracle_det):
+    import torch
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx)
+    sc = S.ProxyValidityChecker(c).scene
+    E, ms = 512, 16
+    frm, to = _edges(c, E, 0x5C6)
+    eager = c.discrete_geodesic_scene_batch(frm, to, sc, -0.03, ms, want_carry=True, round_budget=32)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        c.discrete_geodesic_scene_batch(frm, to, sc, -0.03, ms, want_carry=True, round_budget=32)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        cap = c.discrete_geodesic_scene_batch(frm, to, sc, -0.03, ms, want_carry=True, round_budget=32)
+    for _ in range(2):
+        for x in cap:
+            x.fill_(0)
+        g.replay()
+        torch.cuda.synchronize()
+        live = torch.arange(ms, device=frm.device)[None, :] < eager[1].clamp(max=ms)[:, None]
+        for k in (1, 2, 3, 4):
+            assert torch.equal(cap[k], eager[k])
+        assert torch.equal(cap[5].view(torch.int64), eager[5].view(torch.int64))
+        assert torch.equal(cap[0][live].view(torch.int64), eager[0][live].view(torch.int64))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_large_call_against_composition(gpu_ctx, oracle_det, mode):
+    """16 384 edges, lists of 16, budget 128: scene call (+ continuations) = plain call (+ continuations) cut at the first state
+    ccmp_clearance_batch refuses; the full oracle contract on a fixed sample"""
+    import torch
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx, mode=mode)
+    P = _oracle_problem(oracle_det, c)
+    sc = S.ProxyValidityChecker(c).scene
+    E, ms, budget, margin = 16384, 16, 128, -0.03
+    frm, to = _edges(c, E, 0x5C7)
+    sres = c.discrete_geodesic_scene_batch(frm, to, sc, margin, ms, want_carry=True, round_budget=budget)
+    pres = c.discrete_geodesic_batch(frm, to, ms, want_carry=True, round_budget=budget)
+    scont = c.continue_geodesics(to, sres[0], sres[1], sres[2], sres[3], sres[5], ms, round_budget=budget, scene=sc, margin=margin)
+    pcont = c.continue_geodesics(to, pres[0], pres[1], pres[2], pres[3], pres[4], ms, round_budget=budget)
+
+    def lists(res, cont, k_bl=None):
+        st, n = res[0].cpu().numpy(), res[1].cpu().numpy()
+        bl = res[4].cpu().numpy() if k_bl else None
+        out = []
+        for e in range(E):
+            if e in cont:
+                out.append((cont[e][0], cont[e][3] if k_bl else 0))
+            else:
+                out.append((st[e, :n[e]], int(bl[e]) if k_bl else 0))
+        return out
+
+    sl, pl = lists(sres, scont, True), lists(pres, pcont)
+    allst = np.concatenate([p[0][1:] for p in pl if p[0].shape[0] > 1])
+    clr = sc.clearance_batch(torch.as_tensor(allst).cuda(), margin, want_pair=False)[2].cpu().numpy()
+    pos, n_blocked = 0, 0
+    for e in range(E):
+        ps = pl[e][0]
+        free = clr[pos:pos + ps.shape[0] - 1]
+        pos += ps.shape[0] - 1
+        refused = np.nonzero(free == 0)[0]
+        if refused.size:
+            cut = ps[: refused[0] + 1]
+            assert sl[e][1] == 1, e
+            n_blocked += 1
+        else:
+            cut = ps
+            # the plain traversal accepted every state; the scene call may only differ by having been refused at the state
+            # where the plain one broke (never listed): then its list is the whole plain list
+        assert np.array_equal(_bits(sl[e][0]), _bits(cut)), e
+    assert 0 < n_blocked < E
+    # the oracle contract on a fixed sample (fresh calls without a budget, lists of 64)
+    idx = torch.arange(0, E, E // 64, device=frm.device)
+    _check_against_oracle(c, P, oracle_det, sc, margin, frm[idx].contiguous(), to[idx].contiguous(), 64, need_blocked=False)
+
+
+def test_host_entry_and_resident_service(gpu_ctx, oracle_det):
+    """ccmp_geodesic_scene_host = the device call; with the resident service on, scene calls take the launch path (same bits)"""
+    from closed_chain_motion_planner_amd import _lib
+    from closed_chain_motion_planner_amd import scene as S
+
+    c = _constraint("Wine_Bottle", gpu_ctx)
+    sc = S.ProxyValidityChecker(c).scene
+    E, ms = 16, 32
+    frm, to = _edges(c, E, 0x5C8)
+    ref = [x.cpu().numpy() for x in c.discrete_geodesic_scene_batch(frm, to, sc, -0.03, ms, want_clearance=True)]
+    f, t = frm.cpu().numpy(), to.cpu().numpy()
+    L = _lib.lib()
+    i32 = C.POINTER(C.c_int32)
+    u8 = C.POINTER(C.c_uint8)
+    try:
+        for resident in (False, True):
+            c.setResident(resident)
+            for e in (0, 5):  # single edges, as the planner asks for them
+                st = np.zeros((1, ms, 14)); n = np.zeros(1, np.int32); ok = np.zeros(1, np.uint8); its = np.zeros(1, np.int32)
+                bl = np.zeros(1, np.uint8); clr = np.full((1, ms), np.nan)
+                rc = L.ccmp_geodesic_scene_host(gpu_ctx.handle, C.byref(c.problem), sc._h, -0.03, f[e].ctypes.data_as(dp), t[e].ctypes.data_as(dp),
+                                                1, ms, st.ctypes.data_as(dp), n.ctypes.data_as(i32), ok.ctypes.data_as(u8), its.ctypes.data_as(i32),
+                                                bl.ctypes.data_as(u8), clr.ctypes.data_as(dp), None, None, 0, 0)
+                assert rc == 0
+                m = min(n[0], ms)
+                assert (n[0], ok[0], its[0], bl[0]) == (ref[1][e], ref[2][e], ref[3][e], ref[4][e])
+                assert np.array_equal(_bits(st[0, :m]), _bits(ref[0][e, :m]))
+                assert np.array_equal(_bits(clr[0]), _bits(ref[5][e]))  # both start as the same NaN: unwritten entries too
+    finally:
+        c.setResident(False)
+
+
+def test_mirror_runs_the_proxies_on_the_device(gpu_ctx, oracle_det):
+    """space.jy_ProjectedStateSpace with isValid = a ProxyValidityChecker's isValid: the same lists and bools as the host loop
+    (forced by hiding the bound method in a lambda), and `inner` asked about the same states in the same order"""
+    from closed_chain_motion_planner_amd import scene as S
+    from closed_chain_motion_planner_amd.space import jy_ProjectedStateSpace
+
+    c = _constraint("Wine_Bottle", gpu_ctx)
+    asked = []
+
+    def inner(x):
+        asked.append(np.asarray(x, dtype=np.float64).copy())
+        return (abs(float(x[3])) * 1000.0) % 11.0 >= 1.0  # refuses about one state in eleven
+
+    chk = S.ProxyValidityChecker(c, inner=inner)
+    frm, to = _edges(c, 48, 0x5CB)
+    f, t = frm.cpu().numpy(), to.cpu().numpy()
+    results = []
+    for valid in (chk.isValid, lambda x: chk.isValid(x)):
+        asked.clear()
+        sp = jy_ProjectedStateSpace(c, isValid=valid)
+        out = sp.discreteGeodesicBatch(f, t, False) + sp.discreteGeodesicBatch(f, t, False, check_target=True)
+        out += [(sp.discreteGeodesic(f[e], t[e]), None) for e in range(4)]
+        results.append((out, np.array(asked)))
+    (dev, asked_dev), (host, asked_host) = results
+    assert len(dev) == len(host)
+    for (g1, s1), (g2, s2) in zip(dev, host):
+        assert g1 == g2
+        if s1 is not None:
+            assert np.array_equal(_bits(s1), _bits(s2))
+    assert np.array_equal(_bits(asked_dev), _bits(asked_host)) and len(asked_dev) > 50
+    assert any(not g for g, _ in dev) and any(g for g, _ in dev)

@@ -6,6 +6,9 @@
     python tools/measure.py single                          latency of the reference-signature single-state calls
     python tools/measure.py geodesic [E ...] [--analytic]   batched discreteGeodesic (near-neighbour edges); --analytic: in analytic mode,
                                                            lists of 16 with and without the round budget, lists of 64
+    python tools/measure.py geodesic --scene [--analytic] [E ...]   the same with the default skeleton scene's pre-filter (margin -3 cm):
+                                                           the mirror's host loop (one clearance call per listed state) against its
+                                                           device path, and the plain call against the scene call (lists of 16, budget 128)
     python tools/measure.py analytic                        analytic mode against batch size and waves per CU
     python tools/measure.py host                            PCIe-inclusive rate of ccmp_project_host (pageable / pinned)
     python tools/measure.py sharded [n_gpus [B]]            one process, n GPUs, RCCL all-gather inside the C ABI: per-GPU stream times
@@ -109,6 +112,8 @@ def geodesic(argv):
     ctx = Context(0)
     c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
     analytic = "--analytic" in argv
+    if "--scene" in argv:
+        return geodesic_scene(c, analytic, [int(a) for a in argv if not a.startswith("--")] or [5, 16384])
     shapes = ((16, 128), (64, 0))  # bench.py's first pass: lists of 16 states, 128 Newton rounds per edge; lists of 64
     if analytic:  # the edges are drawn in the default mode (the same edges as without the switch), then traversed in analytic mode
         shapes = ((16, 128), (16, 0), (64, 0))
@@ -135,6 +140,41 @@ def geodesic(argv):
         print("E=%-6d %s%s | mean states %.2f (first %d), reached %.3f, Newton iterations per edge %.1f"
               % (E, "analytic mode: " if analytic else "", "; ".join(row), n.clamp(max=cap).float().mean().item(), cap, (okg == 1).float().mean().item(),
                  its.float().mean().item()), flush=True)
+        c.setJacobianMode(0)
+
+
+def geodesic_scene(c, analytic, sizes_):
+    """the extend step with the proxy pre-filter (default skeleton scene, margin -3 cm): up to 64 edges through the mirror
+    (space.jy_ProjectedStateSpace, lists of 64) — host loop (isValid hidden in a lambda: the unfiltered traversal, then one
+    ccmp_clearance_host per listed state) against the device path (isValid = the checker's bound isValid: the scene call) — and
+    for every size the device calls alone, lists of 16 and a budget of 128 rounds: plain against scene"""
+    from closed_chain_motion_planner_amd.scene import ProxyValidityChecker
+    from closed_chain_motion_planner_amd.space import jy_ProjectedStateSpace
+
+    for E in sizes_:
+        frm, to = near_edges(c, E)
+        if analytic:
+            c.setJacobianMode(1)
+        chk = ProxyValidityChecker(c)
+        row = []
+        if E <= 64:
+            f, t = frm.cpu().numpy(), to.cpu().numpy()
+            for name, valid in (("host loop", lambda x: chk.isValid(x)), ("device path", chk.isValid)):
+                sp = jy_ProjectedStateSpace(c, isValid=valid)
+                sp.discreteGeodesicBatch(f, t, False)
+                ts = []
+                for _ in range(30):
+                    t0 = time.perf_counter()
+                    sp.discreteGeodesicBatch(f, t, False)
+                    ts.append(time.perf_counter() - t0)
+                row.append("mirror %s %.3f ms" % (name, np.median(ts) * 1e3))
+        plain = timed(lambda: c.discrete_geodesic_batch(frm, to, 16, want_carry=True, round_budget=128), reps=7)
+        scene = timed(lambda: c.discrete_geodesic_scene_batch(frm, to, chk.scene, chk.margin, 16, want_carry=True, round_budget=128), reps=7)
+        st, n, ok, its, bl, carry = c.discrete_geodesic_scene_batch(frm, to, chk.scene, chk.margin, 16, want_carry=True, round_budget=128)
+        tested = int((n.clamp(max=16) - 1).sum().item() + bl.sum().item())
+        row.append("device call, lists of 16, budget 128: plain %.3f ms, scene %.3f ms (%d states tested, %d edges blocked)"
+                   % (plain, scene, tested, int(bl.sum().item())))
+        print("E=%-6d %s%s" % (E, "analytic mode: " if analytic else "", "; ".join(row)), flush=True)
         c.setJacobianMode(0)
 
 
