@@ -4,14 +4,24 @@
 // cannot drift apart bit-wise, and — being the same tokens in the same place as before — the register allocation of neither
 // changed (shared through FUNCTIONS, the general instantiations of both kernels came out with 2.3 KB of scratch: the allocator lost
 // the scoping of the pose arrays).  The including loop provides: K, rec, live, writer, r, arm_l, row_l, d_lane, CCMP_FD_BP (the lane's
-// base-frame offset: a register in the projector, an LDS slot in the extend step), active, iter, norm1, norm2; it declares
-// `bool cont; double f0, f1;` behind which this text continues.
+// base-frame offset: a register in the projector, an LDS slot in the extend step), CCMP_FD_X0_ROWS (1: the chains by rows take the
+// short rotation too; 0 in the extend step, which spilled with both copies), active, iter, norm1, norm2; it declares
+// `bool x0, cont; double f0, f1;` behind which this text continues.
     // ---- phase 1: function(x) — sines/cosines, both chains, residual ---------------------------
+    bool x0_off = false; // some joint of the group sits too close to a multiple of 2 pi for rot_sc_x0 (ccmp_kin.h: rot_x0_round_ok)
     for (int e = r; e < 14; e += kGroup) {
       double s, c;
-      ccmp_sincos(rec[kX + e], &s, &c);
+      const double xe = rec[kX + e];
+      ccmp_sincos(xe, &s, &c);
       if (live) { rec[kSC + 2 * e] = s; rec[kSC + 2 * e + 1] = c; }
+      x0_off = x0_off || !rot_x0_round_ok(xe, c);
     }
+    // wave-uniform, for the whole round: the short form of the general joints' rotations, at x and at every stencil point
+    // (groups without a sample have no say)
+    bool x0 = false;
+#ifdef CCMP_FD_ROT_X0
+    if constexpr (STOCK) x0 = K.rot_x0 != 0 && __builtin_amdgcn_ballot_w64(active && x0_off) == 0ull;
+#endif
     __syncthreads();
     bool cont = false;
     double f0, f1;
@@ -19,7 +29,8 @@
       double T0[12], T1[12], f[2];
       if constexpr (STOCK && CCMP_FD_ROWS) {
         // both chains and both tool poses, one matrix row per lane; arm 0's prefix frames stay in LDS for its columns
-        chain_rows<true>(K, rec, arm_l, row_l, live, 0, d_lane, CCMP_FD_BP);
+        if (CCMP_FD_X0_ROWS && x0) chain_rows<true, true>(K, rec, arm_l, row_l, live, 0, d_lane, CCMP_FD_BP);
+        else chain_rows<true, false>(K, rec, arm_l, row_l, live, 0, d_lane, CCMP_FD_BP);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 12; k++) { T0[k] = rec[kEE + k]; T1[k] = rec[kEE + 12 + k]; }

@@ -103,6 +103,22 @@ __device__ __forceinline__ void chain_at_x(const ccmp_consts &K, double *rec, bo
   tool_pose_t<STOCK>(K, ARM, R, o, &T[0], &T[9]);
 }
 
+// A general joint (1, 3, 5, 6) of the stock Panda in the STOCK instantiations: Rn = R * Rot(axis_i, angle).  X0: the short form
+// rot_sc_x0 (7 operations for rot_sc's 13, the same bits: ccmp_kin.h).  It is exact only away from angle 0, so the choice is made
+// ONCE per Newton round and wavefront (ccmp_fd_newton_phase1.inc: rot_x0_round_ok on every joint of every sample the wavefront
+// iterates on — the test covers the six stencil points of each column as well) and selects between two copies of the round's
+// kinematics, piece by piece (ccmp_fd_newton_phase2.inc).  Measured: a test and a scalar branch at every rotation instead cost
+// more than the short form saved (+2.2 %: the branches cut the scheduler's regions where a rotation overlaps the product in
+// front of it); the two copies pay -2.7 % (DESIGN_experiments.md §5.6).
+template <bool X0>
+__device__ __forceinline__ void stock_rot_mul(const ccmp_consts &K, int i, double s, double c, const double *R, double *Rn)
+{
+  double Rj[9];
+  if constexpr (X0) rot_sc_x0(K.axis[0][i], K.aprod[0][i], s, c, Rj);
+  else rot_sc(K.axis[0][i], K.aprod[0][i], s, c, Rj);
+  mul33(R, Rj, Rn);
+}
+
 // ---- the chains at x, one matrix ROW per lane (STOCK instantiation: twin arms, diag(+-1) base frames) ---------------
 // Row r of (R * Rj) needs row r of R only, and o[r] += R[r,:] * offset likewise: lane `row` of an arm's three lanes
 // carries one row of the running frame (3 + 1 doubles) and does a third of every product — per element the same
@@ -112,7 +128,7 @@ __device__ __forceinline__ void chain_at_x(const ccmp_consts &K, double *rec, bo
 // and tool poses instead of 2 x (343 + 48) when every lane ran both chains whole.  The lanes of arm `store_arm` keep
 // the frame in front of every joint in LDS (R row before the joint's rotation, o including the joint's offset) for
 // that arm's Jacobian columns; with TOOL every lane also leaves its row of the arm's world tool pose in LDS.
-template <bool TOOL, int I>
+template <bool TOOL, bool X0, int I>
 __device__ __forceinline__ void chain_rows_from(const ccmp_consts &K, double *rec, const double *sc, int row, bool store,
                                                 double &R0, double &R1, double &R2, double &o)
 {
@@ -136,23 +152,24 @@ __device__ __forceinline__ void chain_rows_from(const ccmp_consts &K, double *re
       n0 = CCMP_FMA(R1, s, R0 * c);
       n1 = CCMP_FMA(R1, c, R0 * ns);
       n2 = R2 * w;
-    } else { // rot_sc + one row of mul33
+    } else { // rot_sc (X0: its short form, see stock_rot_mul) + one row of mul33
       double Rj[9];
-      rot_sc(K.axis[0][I], K.aprod[0][I], s, c, Rj);
+      if constexpr (X0) rot_sc_x0(K.axis[0][I], K.aprod[0][I], s, c, Rj);
+      else rot_sc(K.axis[0][I], K.aprod[0][I], s, c, Rj);
       n0 = dot3(R0, Rj[0], R1, Rj[3], R2, Rj[6]);
       n1 = dot3(R0, Rj[1], R1, Rj[4], R2, Rj[7]);
       n2 = dot3(R0, Rj[2], R1, Rj[5], R2, Rj[8]);
     }
     R0 = n0; R1 = n1; R2 = n2;
-    chain_rows_from<TOOL, I + 1>(K, rec, sc, row, store, R0, R1, R2, o);
+    chain_rows_from<TOOL, X0, I + 1>(K, rec, sc, row, store, R0, R1, R2, o);
   }
 }
-template <bool TOOL>
+template <bool TOOL, bool X0>
 __device__ __forceinline__ void chain_rows(const ccmp_consts &K, double *rec, int arm, int row, bool live, int store_arm,
                                            double d_lane, double bp_lane)
 {
   double R0 = row == 0 ? 1.0 : 0.0, R1 = row == 1 ? 1.0 : 0.0, R2 = row == 2 ? 1.0 : 0.0, o = 0.0;
-  chain_rows_from<TOOL, 0>(K, rec, rec + kSC + 14 * arm, row, live && arm == store_arm, R0, R1, R2, o);
+  chain_rows_from<TOOL, X0, 0>(K, rec, rec + kSC + 14 * arm, row, live && arm == store_arm, R0, R1, R2, o);
   if constexpr (TOOL) { // tool_pose_t<true>, diag(+-1) base frame, one row
     double pf = o;
     if (kStockEe & 1) pf = CCMP_FMA(R0, K.ee[0][0], pf);
@@ -187,19 +204,19 @@ __device__ __forceinline__ void stock_z_step(const ccmp_consts &K, int i, double
   for (int r = 0; r < 3; r++) o[r] = CCMP_FMA(R[3 * r + 2], oz, CCMP_FMA(R[3 * r], ox, o[r]));
   mul_zrot(R, s, c, Rn);
 }
+template <bool X0>
 __device__ __forceinline__ void stock_g_step(const ccmp_consts &K, int i, double s, double c, const double *R, double *Rn, double *o)
 {
   const double ox = K.offset[0][i][0];
 #pragma unroll
   for (int r = 0; r < 3; r++) o[r] = CCMP_FMA(R[3 * r], ox, o[r]);
-  double Rj[9];
-  rot_sc(K.axis[0][i], K.aprod[0][i], s, c, Rj);
-  mul33(R, Rj, Rn);
+  stock_rot_mul<X0>(K, i, s, c, R, Rn);
 }
 
 // OMPL's default Constraint::jacobian, evaluation part, for the 7 columns of one arm: each lane evaluates
-// its stencil point of column j from the cached prefix frame and parks the residual pair in LDS.
-template <int ARM, bool STOCK>
+// its stencil point of column j from the cached prefix frame and parks the residual pair in LDS.  X0 (STOCK only): the general
+// joints' rotations in their short form (stock_rot_mul).
+template <int ARM, bool STOCK, bool X0 = false>
 __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *rec, bool live, int r, bool plus, int nstep)
 {
   double To[12]; // the other arm's (unperturbed) tool pose: 24 VGPRs that save 12 LDS reads per column (-6.5 %, A/B)
@@ -213,6 +230,17 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
 #pragma unroll
     for (int k = 0; k < 3; k++) To[9 + k] = ti[k];
   }
+  constexpr bool kOtherP = ARM == 1; // arm 0's columns hold ti in place of the other arm's translation
+#else
+  constexpr bool kOtherP = true;
+#endif
+#ifdef CCMP_FD_BASE_FOLD
+  // STOCK: twin arms on diag(+-1) base frames (launchers).  This arm's +-1 factors go into the other arm's pose once, here,
+  // instead of into this arm's nine rotation entries at every stencil point (ccmp_kin.h: tool_pose_fold)
+  constexpr bool kFold = STOCK;
+  if constexpr (kFold) fold_other_pose<kOtherP>(K, ARM, To);
+#else
+  constexpr bool kFold = false;
 #endif
   for (int j = 0; j < 7; j++) {
     const double xj = rec[kX + ARM * 7 + j];
@@ -246,12 +274,10 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
           R[3 * rr + 2] = R[3 * rr + 2] * w;
         }
       } else {
-        double Rj[9];
-        rot_sc(K.axis[0][j], K.aprod[0][j], s, c, Rj);
-        mul33(R, Rj, Rn);
+        stock_rot_mul<X0>(K, j, s, c, R, Rn);
         if (j < 6) { // j = 1, 3, 5: the next joint (2, 4 or 6) takes the frame back to R
           if (i < 6) stock_z_step(K, i, sc[2 * i], sc[2 * i + 1], Rn, R, o);
-          else stock_g_step(K, 6, sc[12], sc[13], Rn, R, o);
+          else stock_g_step<X0>(K, 6, sc[12], sc[13], Rn, R, o);
           i++;
         } else { // j = 6: no suffix
 #pragma unroll
@@ -259,14 +285,12 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
         }
       }
       for (; i < 5; i += 2) { // (1, 2), (3, 4): general step then z step, R -> Rn -> R
-        stock_g_step(K, i, sc[2 * i], sc[2 * i + 1], R, Rn, o);
+        stock_g_step<X0>(K, i, sc[2 * i], sc[2 * i + 1], R, Rn, o);
         stock_z_step(K, i + 1, sc[2 * i + 2], sc[2 * i + 3], Rn, R, o);
       }
       if (i == 5) { // (5, 6): joint 5 has no offset at all
-        double Rj[9];
-        rot_sc(K.axis[0][5], K.aprod[0][5], sc[10], sc[11], Rj);
-        mul33(R, Rj, Rn);
-        stock_g_step(K, 6, sc[12], sc[13], Rn, R, o);
+        stock_rot_mul<X0>(K, 5, sc[10], sc[11], R, Rn);
+        stock_g_step<X0>(K, 6, sc[12], sc[13], Rn, R, o);
       }
     } else {
       {
@@ -313,7 +337,8 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
     }
 #endif
     double Tw[12], t[2];
-    tool_pose_t<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
+    if constexpr (kFold) tool_pose_fold<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
+    else tool_pose_t<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
 #ifdef CCMP_FD_TI_HOIST
     if (ARM == 0) chain_residual_ti(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
 #else
@@ -489,6 +514,7 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
     }
 
 #define CCMP_FD_BP bp_lane
+#define CCMP_FD_X0_ROWS 1
 #include "ccmp_fd_newton_phase1.inc"
     // ---- finished groups: jointValid, write-back --------------------------------------------
     {
@@ -532,6 +558,7 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
 
 #include "ccmp_fd_newton_phase2.inc"
 #undef CCMP_FD_BP
+#undef CCMP_FD_X0_ROWS
   }
 }
 
@@ -714,6 +741,7 @@ __global__ __launch_bounds__(64, CCMP_GEO_GROUP_WAVES_PER_SIMD) void geodesic_gr
     }
 
 #define CCMP_FD_BP lane_bp[lane_opaque(lane)]
+#define CCMP_FD_X0_ROWS 0
 #include "ccmp_fd_newton_phase1.inc"
     // ---- a projection has ended: the reference's bookkeeping between two projections (jy_ProjectedStateSpace.cpp:65-90) --
     {
@@ -797,6 +825,7 @@ __global__ __launch_bounds__(64, CCMP_GEO_GROUP_WAVES_PER_SIMD) void geodesic_gr
 
 #include "ccmp_fd_newton_phase2.inc"
 #undef CCMP_FD_BP
+#undef CCMP_FD_X0_ROWS
   }
 }
 

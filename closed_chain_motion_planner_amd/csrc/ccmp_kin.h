@@ -42,6 +42,9 @@ struct ccmp_consts {
   int32_t stock;     /* both arms carry the stock Panda structure (see kStockZ below): launchers pick the STOCK kernels */
   int32_t twin_arms; /* stock, both arms have bit-identical chain constants (axis, offset, ee, R_tool) and both t_wb are
                         diag(+-1): the throughput kernel's STOCK instantiation reads arm 0's constants for either arm */
+  int32_t rot_x0;    /* twin_arms, and every joint axis has an x component of exactly 0 with y, z components of the general
+                        joints (1, 3, 5, 6) at least 2^-64 in magnitude: rot_sc_x0 may stand in for rot_sc (see there) */
+  double base_dp[2][3]; /* base_R[a][r][r] * base_p[a][r] (exact: the factor is +-1); meaningful under base_diag only */
 };
 
 namespace ccmp {
@@ -102,6 +105,39 @@ CCMP_HD void rot_sc(const double *a, const double *ap, double s, double c, doubl
   R[5] = CCMP_FMA(ap[4], t, -a0s);
   R[6] = CCMP_FMA(ap[2], t, -a1s);
   R[7] = CCMP_FMA(ap[4], t, a0s);
+  R[8] = CCMP_FMA(ap[5], t, c);
+}
+
+/* rot_sc for an axis whose x component is exactly zero (every joint of the stock Panda: the general joints 1, 3, 5, 6 have
+ * axes (0, +-1, 6.1e-17) and (0, -1.2e-16, -1)), 7 operations instead of 13.  With a0 = 0 the products ap[0] t, ap[1] t,
+ * ap[2] t and a0 s are exact zeros of either sign, and
+ *   R[0] = 0 t + c = c                      (c is a cosine: never -0)
+ *   R[1], R[2], R[3], R[6] = +-0 + (+-a_k s) = +-a_k s   as long as a_k s is not itself a zero,
+ *   R[5], R[7] = fma(ap[4], t, -+0) = ap[4] t            as long as ap[4] t is not itself a zero
+ * (a sum of two zeros takes its sign from both, so there the short form could give -0 for +0).  rot_x0_admits(c) is the
+ * guard: c < 1, that is t = 1 - c > 0, means |angle| > ~1e-8, hence |s| > ~1e-8 and neither a_k s (|a_k| >= 2^-64, ccmp_consts::rot_x0)
+ * nor ap[4] t (>= 2^-128 2^-53) is zero or underflows; NaN fails it.  Where the guard holds the nine results are rot_sc's
+ * bit for bit (tests/test_rot_x0_host.py runs both over the four general axes); where it does not — an angle within
+ * 1e-8 of zero — the caller takes rot_sc.  a[0], ap[0..2] are not read. */
+CCMP_HD bool rot_x0_admits(double c) { return c < 1.0; } /* <=> 1 - c > 0: the difference of two doubles is zero only if they are equal */
+/* The same for a whole Newton round of the finite-difference projector, asked once of the round's iterate x_j (cosine c): the six
+ * stencil points y = x_j +- k h, k <= 3, h = sqrt(eps) max(1, |x_j|), must admit the short form too.  c < 1 - 2^-30 puts x_j more
+ * than 4.3e-5 from every multiple of 2 pi, |x_j| <= 512 keeps 3 h below 2.3e-5: every y stays 2e-5 away from them, a thousand
+ * times what rot_x0_admits needs.  NaN fails. */
+CCMP_HD bool rot_x0_round_ok(double x, double c) { return c < 1.0 - 0x1p-30 && ccmp_abs(x) <= 512.0; }
+CCMP_HD void rot_sc_x0(const double *a, const double *ap, double s, double c, double *R)
+{
+  const double t = 1.0 - c;
+  const double a1s = a[1] * s, a2s = a[2] * s;
+  const double m = ap[4] * t;
+  R[0] = c;
+  R[1] = -a2s;
+  R[2] = a1s;
+  R[3] = a2s;
+  R[4] = CCMP_FMA(ap[3], t, c);
+  R[5] = m;
+  R[6] = -a1s;
+  R[7] = m;
   R[8] = CCMP_FMA(ap[5], t, c);
 }
 
@@ -210,6 +246,40 @@ CCMP_HD void tool_pose_t(const ccmp_consts &K, int arm, const double *R, const d
 CCMP_HD void tool_pose(const ccmp_consts &K, int arm, const double *R, const double *o, double *Rw, double *pw)
 {
   tool_pose_t<false>(K, arm, R, o, Rw, pw);
+}
+
+/* ---- the diag(+-1) base frame folded into the OTHER arm's pose (K.base_diag has the arm's bit) -------------------------
+ * With d = diag(t_wb.linear()) tool_pose_t gives Rw = d (.) Rf (nine products with +-1) and pw = fma(d, pf, bp) =
+ * d (.) (pf + d (.) bp): a product with +-1 is exact and rounding is symmetric in sign.  chain_residual only ever multiplies
+ * Rw[r][.] and pw[r] with row r of the other arm's pose To, or with each other, and (d x) y == x (d y) bit for bit, so a
+ * caller that evaluates one arm many times against a fixed To scales To's rows by d ONCE (fold_other_pose) and hands
+ * chain_residual the unscaled pair (Rf, pf + d (.) bp) of tool_pose_fold:
+ *   this arm first  (R1 = Rw, p1 = pw, R2 = To):  Rc = To^T Rw, pc = To^T pw - ti     rows of To's rotation scaled; ti from
+ *                                                                                      the UNSCALED To (chain_residual_ti)
+ *   this arm second (R1 = To, p1 = po, R2 = Rw):  Rc = Rw^T To, ti = Rw^T pw, pc = Rw^T po - ti   rows of To's rotation
+ *                                                  and translation scaled; in ti the two factors d_r cancel
+ * Only the sign of a zero pf + d bp can differ from d fma(d, pf, bp)'s, and it can reach nothing but the sign of a zero
+ * component of pc, which the residual squares.  Both residual components are the same bits (tests/test_rot_x0_host.py). */
+template <bool STOCK>
+CCMP_HD void tool_pose_fold(const ccmp_consts &K, int arm, const double *R, const double *o, double *Rf, double *pl)
+{
+  double pf[3] = {o[0], o[1], o[2]};
+  mulvec_acc_nz<STOCK ? kStockEe : 7>(R, K.ee[arm], pf);
+  mul33(R, K.R_tool[arm], Rf);
+#pragma unroll
+  for (int r = 0; r < 3; r++) pl[r] = pf[r] + K.base_dp[arm][r];
+}
+/* To = (R(9), p(3)) of the arm that is NOT `arm`: rows of R — and of p with WITH_P — times `arm`'s d */
+template <bool WITH_P>
+CCMP_HD void fold_other_pose(const ccmp_consts &K, int arm, double *To)
+{
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const double d = K.base_R[arm][4 * r];
+#pragma unroll
+    for (int c = 0; c < 3; c++) To[3 * r + c] = d * To[3 * r + c];
+    if (WITH_P) To[9 + r] = d * To[9 + r];
+  }
 }
 
 /* Full FK of one arm (world pose of its hand frame). */

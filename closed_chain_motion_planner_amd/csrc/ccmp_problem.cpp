@@ -135,6 +135,18 @@ void make_consts_impl(const ccmp_problem &P, ccmp_consts &K)
                  memcmp(P.offset[0], P.offset[1], sizeof P.offset[0]) == 0 && memcmp(P.ee[0], P.ee[1], sizeof P.ee[0]) == 0 &&
                  memcmp(P.R_tool[0], P.R_tool[1], sizeof P.R_tool[0]) == 0)
                     ? 1 : 0;
+  // rot_sc_x0 (ccmp_kin.h) in the STOCK throughput kernels: every axis without an x component (exactly), and the general
+  // joints' y, z components far enough from zero that their products with a sine above 1e-8 cannot vanish
+  bool x0 = K.twin_arms != 0;
+  for (int a = 0; a < 2; a++)
+    for (int i = 0; i < 7; i++) {
+      const double *ax = P.axis[a][i];
+      x0 = x0 && ax[0] == 0.0;
+      if (!ccmp::kStockZ[i]) x0 = x0 && __builtin_fabs(ax[1]) >= 0x1p-64 && __builtin_fabs(ax[2]) >= 0x1p-64;
+    }
+  K.rot_x0 = x0 ? 1 : 0;
+  for (int a = 0; a < 2; a++)
+    for (int k = 0; k < 3; k++) K.base_dp[a][k] = P.base_R[a][4 * k] * P.base_p[a][k];
   for (int k = 0; k < 3; k++) K.init_p[k] = P.init_p[k];
   ccmp::quat_of(P.init_R, K.init_q);
   for (int i = 0; i < 7; i++) {

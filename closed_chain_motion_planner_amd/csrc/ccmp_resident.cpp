@@ -222,7 +222,7 @@ int resident_call(ccmp_ctx *ctx, const ccmp_problem *p, const ResidentCall &call
     if (!(p->tol_pos > 0) || !(p->tol_rot > 0) || p->max_iter < 0 || p->max_iter > 65535) return CCMP_EINVAL;
     ccmp_consts K;
     make_consts(*p, K);
-    if (!ctx->stock_kernels) K.stock = K.twin_arms = 0;
+    if (!ctx->stock_kernels) K.stock = K.twin_arms = K.rot_x0 = 0;
     if (r->launched && r->stock != (K.stock ? 1 : 0)) stop(r); // the other instantiation of the kernel
     static_assert(sizeof(ccmp_consts) <= kResStateOff, "the constants fit in front of the state word");
     if (!r->box) { // (first use: the mailbox comes with the first start)
