@@ -14,10 +14,11 @@ Translation units with deliberately different flags:
   ccmp_api.cpp           -ffp-contract=off -DCCMP_USE_FMA   context, launches            } compiled a second time with -DCCMP_DEBUG_HOOKS for
   ccmp_policy.cpp                                           option table, plans, describe } lib/libccmp_debug.so (include/ccmp_debug.h)
   ccmp_resident.cpp                                         opt-in resident service kernel for single-state calls (host side)
-  ccmp_kernels_resident.hip -ffp-contract=off -DCCMP_USE_FMA  ... its device side, on the latency flavour's Newton routine
+  ccmp_kernels_resident.hip -ffp-contract=off -DCCMP_USE_FMA  ... its device side for the reference arithmetic, on the latency flavour's Newton routine
+                         (its device side for analytic mode, resident_row16_kernel, is part of ccmp_kernels_fast.hip: the same flags, the same bits)
   ccmp_host_io.cpp                                          *_host conveniences (staging, pinned block, page-locked caller buffers), sharded host calls
   ccmp_comm.cpp                                             one process / several GPUs: RCCL communicator and sharded entry points
-  ccmp_kernels_fast.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   analytic fast mode (lane-pair and row16 projectors, the row16 extend step), bit-identical to the oracle's analytic mode
+  ccmp_kernels_fast.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   analytic fast mode (lane-pair and row16 projectors, the row16 extend step, the row16 resident service kernel), bit-identical to the oracle's analytic mode
   ccmp_kernels_scout.hip -ffast-math                        FP32 iteration-count predictor + ordering (never touches results)
   ccmp_kernels_scene.hip -ffp-contract=off -DCCMP_USE_FMA   proxy-geometry clearance (pre-filter ahead of the host's MoveIt test)
   ccmp_scene.cpp                                            proxy scenes: validation, pair list, launches
@@ -80,7 +81,7 @@ _UNITS = [
     ("ccmp_kernels_scene.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     ("ccmp_scene.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -119,6 +120,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_scene_kernel|geodesic_group_kernel|resident_service_kernel)<(\d+, )?true>", 0),
     (r"(project_fd_kernel|project_fd_flat_kernel|project_fd_wave_kernel|geodesic_flat_kernel(_lat)?|geodesic_scene_kernel|geodesic_group_kernel|resident_service_kernel)<(\d+, )?false>", 136),
     (r"project_pair_kernel|project_row16_kernel", 0),  # analytic mode, every instantiation (stock twin arms, stock, calibrated)
+    (r"resident_row16_kernel", 0),  # the resident service kernel of analytic mode, both instantiations
     (r"geodesic_row16_(scene_)?kernel", 0),  # analytic mode's extend step and its scene variant, both instantiations (diagonal and general base frames)
     (r"scout_|clearance", 400),
     (r".", 64),

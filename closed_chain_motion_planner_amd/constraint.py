@@ -58,7 +58,7 @@ class Context:
         check(_lib.lib().ccmp_ctx_set_option(self._h, name.encode(), int(value)), "ccmp_ctx_set_option(%s)" % name)
 
     def get_option(self, name):
-        """ccmp_ctx_get_option: the value in force (also "num_cus", "side_stream_busy", "resident")"""
+        """ccmp_ctx_get_option: the value in force (also "num_cus", "side_stream_busy", "resident", "resident_gave_up", "resident_served")"""
         return _lib.get_option(self._h, name)
 
     def describe(self, call_kind, n):
@@ -519,7 +519,9 @@ class KinematicChainConstraint:
     def setResident(self, on=True):
         """The adapter's `KinematicChainConstraint::setResident` (include/ccmp_ompl_adapter.hpp): the single-state calls below and
         single-edge calls from host buffers go through the context's resident service kernel (option "resident", include/ccmp.h) —
-        no launch on the call path, the same bits.  Off by default."""
+        no launch on the call path, the same bits.  After setJacobianMode(1) it serves host-buffer extend-step calls of up to eight
+        edges, continuation calls with carry_in included; ctx.get_option("resident_served") counts the served requests.  Off by
+        default."""
         self.ctx.set_option("resident", 1 if on else 0)
 
     def project(self, x):

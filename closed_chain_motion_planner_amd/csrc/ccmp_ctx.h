@@ -98,6 +98,7 @@ struct ccmp_ctx {
   // resident service kernel (opt-in, option "resident"; ccmp_resident.h)
   struct ccmp_resident *resident = nullptr;
   int resident_on = 0;
+  long resident_served = 0;            // requests the service kernel has answered for this context (read-only option "resident_served")
   int resident_gave_up = 0;            // how often a start of the service kernel gave up (it did not get to run within 5 ms: that ONE call took the launch path; ccmp_resident.cpp)
 
   // ---- tuning (option table: ccmp_policy.cpp) ----------------------------------------------------------------------------

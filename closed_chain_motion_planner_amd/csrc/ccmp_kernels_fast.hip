@@ -29,6 +29,7 @@
 #include "ccmp_fd_common.h"
 #include "ccmp_kin.h"
 #include "ccmp_launch.h"
+#include "ccmp_resident.h" // the resident service kernel for analytic mode, at the end of the file
 #include "ccmp_solve.h"
 
 using namespace ccmp;
@@ -544,6 +545,243 @@ __global__ __launch_bounds__(64, 2) void geodesic_row16_scene_kernel(const ccmp_
 #undef CCMP_ROW16_SCENE
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// resident_row16_kernel — the resident service kernel (ccmp_resident.h: what it is for, the mailbox, what keeps it from hanging
+// anything) for a problem in analytic mode.  One persistent 128-thread block like resident_service_kernel (ccmp_kernels_resident.hip),
+// polling the same request header on the same stream, but on this unit's latency layout: two wavefronts, EIGHT rows of sixteen lanes.
+//   kResProject                 one state on row 0 of wavefront 0: project_row16_kernel's sequence with source 0 and no wrap (the same
+//                               text: ccmp_row16_eval.inc / ccmp_row16_step.inc, the same flags: the same bits)
+//   kResFunction / IsSatisfied  one evaluation (ccmp_row16_eval.inc), as the traversal's isSatisfied(to)
+//   kResJointValid              the bounds test of project_row16_kernel
+//   kResGeodesicMulti           1..8 edges of discreteGeodesic / checkMotion, each on its own row through the text of
+//                               geodesic_row16_kernel (ccmp_row16_geo_body.inc, included without its prologue).  The ticket word is an
+//                               LDS word; from / to / carry_in are staged from the mailbox into LDS once and verified
+//                               (ccmp_resident_proto.h); state rows and per-edge results go to the mailbox as the body writes them.
+//                               The two wavefronts run the body independently — it has no barrier — and meet at block barriers
+//                               before and after the request only.
+// Every loop is bounded: the idle poll by idle_ticks, the read-it-again loop by kResRereads (then the request is answered with
+// kResErrTorn), a projection by max_iter, a traversal by max_states and the reference's own break tests.
+__device__ __forceinline__ unsigned long long res_load(const unsigned long long *p)
+{
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ void res_store(unsigned long long *p, unsigned long long v)
+{
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ unsigned long long res_lane_word(unsigned long long v, int src_lane) // wave-uniform broadcast of one lane's word
+{
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(v & 0xffffffffull), src_lane);
+  const unsigned int hi = (unsigned int)__builtin_amdgcn_readlane((int)(v >> 32), src_lane);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+template <bool DIAG>
+__global__ __launch_bounds__(128, 1) void resident_row16_kernel(unsigned long long *box, unsigned long long last_tag,
+                                                               unsigned long long idle_ticks /* of the 100 MHz wall clock */)
+{
+  __shared__ double ktab[kConstsDoubles + 1];
+  __shared__ double lds[8 * gRec];                                   // one record per row
+  __shared__ unsigned long long s_multi[ccmp_res::kMultiMaxWords];   // a several-edge request as read from the mailbox
+  __shared__ double edge_from[8 * 14], edge_to[8 * 14], edge_carry[8 * 2];
+  __shared__ double s_x[14];                                         // the state of a single-state command
+  __shared__ unsigned long long s_tag, s_ticket;
+  __shared__ int s_cmd, s_edges, s_bad;
+  __shared__ unsigned int s_consts;
+  __shared__ ccmp_res::MultiParams s_mp;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, l = lane & 15; // (lane: within the wavefront — what the row16 texts' ballots and shuffles index)
+  const unsigned long long *consts = box + kResConstsOff / 8;
+  const unsigned long long *req = box + kResReqOff / 8;
+  const unsigned long long *mreq = box + kResMultiReqOff / 8;
+  unsigned long long *resp = box + kResRespOff / 8;
+  unsigned long long *mresp = box + kResMultiRespOff / 8;
+  unsigned long long *state = box + kResStateOff / 8;
+  const ccmp_consts &K = *reinterpret_cast<const ccmp_consts *>(ktab);
+  double *const rec = lds + (tid >> 4) * gRec;
+  unsigned int my_consts = ~0u; // nothing loaded yet: the first request brings its constants
+  if (tid == 0) res_store(state, (unsigned long long)kResRunning);
+  unsigned long long idle_since = wall_clock64();
+
+  for (;;) {
+    // ---- wait for a request: the header's five lines, 40 words in one load by wavefront 0 (resident_service_kernel's poll) -------
+    if (tid < 64) {
+      unsigned long long w = 0;
+      if (tid < kResReqWords) w = res_load(req + tid);
+      const int col = tid & 7;
+      unsigned long long h = 0;
+      if (col < 7) { const int r = 7 * col + 1; h = (w << r) | (w >> (64 - r)); }
+      h ^= __shfl_xor(h, 1);
+      h ^= __shfl_xor(h, 2);
+      h ^= __shfl_xor(h, 4); // every lane of a line holds the line's checksum
+      const bool torn = col == 7 && tid < kResReqWords && (unsigned int)(w >> 32) != (unsigned int)(h ^ (h >> 32));
+      const bool clean = __builtin_amdgcn_ballot_w64(torn) == 0ull;
+      const unsigned int ta = (unsigned int)res_lane_word(w, 7), tb = (unsigned int)res_lane_word(w, 15), tc = (unsigned int)res_lane_word(w, 23),
+                         td = (unsigned int)res_lane_word(w, 31), te = (unsigned int)res_lane_word(w, 39);
+      const bool fresh = clean && ta == tb && tb == tc && tc == td && td == te && te != (unsigned int)last_tag;
+      if (fresh) {
+        if (col < 7 && tid < 16) s_x[7 * (tid >> 3) + col] = __longlong_as_double((long long)w); // lines A, B: the state
+        if (tid == 0) {
+          const unsigned long long head = res_lane_word(w, 32);
+          s_cmd = (int)(head & 0xffffffffull);
+          s_consts = (unsigned int)(head >> 32);
+          s_edges = (int)(unsigned int)(res_lane_word(w, 37) & 0xffffffffull); // kResGeodesicMulti: how many edges' lines to read
+          s_tag = (unsigned long long)te;
+        }
+        last_tag = te;
+      } else if (tid == 0) {
+        s_cmd = (wall_clock64() - idle_since > idle_ticks) ? kResStop : kResNone; // nobody has asked for a while: leave by itself
+      }
+    }
+    __syncthreads();
+    const int cmd = s_cmd;
+    if (cmd == kResNone) {
+      __syncthreads(); // (s_cmd is rewritten at the top)
+      continue;
+    }
+    if (cmd == kResStop) break;
+    if (tid >= 64) last_tag = s_tag;
+    // ---- the problem in force: its constants are reloaded when the host says they changed ----------------------------------------
+    if (s_consts != my_consts) {
+      __syncthreads();
+      for (int k = tid; k < kConstsDoubles; k += 128) ktab[k] = __longlong_as_double((long long)res_load(consts + k));
+      my_consts = s_consts;
+      __syncthreads();
+    }
+    unsigned long long flags = 0ull;
+    if (cmd == kResGeodesicMulti) {
+      // ---- the edges' lines: staged into LDS, then verified (ccmp_res::line_ok on one thread per line, multi_unpack on thread 0 —
+      // the two functions ccmp_res::multi_accept is made of); lines that do not agree are read again, kResRereads times at most
+      const int hdr_edges = s_edges < 1 ? 1 : (s_edges > ccmp_res::kMultiMaxEdges ? ccmp_res::kMultiMaxEdges : s_edges);
+      const int lines = ccmp_res::multi_lines(hdr_edges);
+      bool accepted = false;
+      for (int attempt = 0; attempt < kResRereads && !accepted; attempt++) {
+        for (int w = tid; w < 8 * lines; w += 128) s_multi[w] = res_load(mreq + w);
+        if (tid == 0) s_bad = 0;
+        __syncthreads();
+        if (tid < lines && !ccmp_res::line_ok((unsigned int)s_tag, s_multi + 8 * tid)) s_bad = 1;
+        if (tid == 127) {
+          ccmp_res::MultiParams m;
+          const bool good = ccmp_res::multi_unpack(s_multi, &m);
+          s_mp = m;
+          // (the bounds of everything the traversal indexes: rows of the states area, words of the per-edge response)
+          if (!good || m.E != s_edges || m.max_states < 1 || m.max_states > kResMaxStates) s_bad = 1;
+        }
+        __syncthreads();
+        accepted = s_bad == 0;
+        __syncthreads(); // (s_bad and s_multi are rewritten by the next attempt)
+      }
+      if (!accepted) flags = kResErrTorn;
+      else {
+        const int n_edges = s_mp.E;
+        if (tid < 14 * n_edges) {
+          const int e = tid / 14, i = tid - 14 * e;
+          edge_from[tid] = __longlong_as_double((long long)s_multi[ccmp_res::multi_from_word(e, i)]);
+          edge_to[tid] = __longlong_as_double((long long)s_multi[ccmp_res::multi_to_word(e, i)]);
+        }
+        if (tid < 2 * n_edges) edge_carry[tid] = __longlong_as_double((long long)s_multi[ccmp_res::multi_carry_word(tid >> 1, tid & 1)]);
+        if (tid == 0) s_ticket = 0ull;
+        __syncthreads();
+        {
+          // geodesic_row16_kernel's arguments, pointed at LDS (inputs, the ticket word) and at the mailbox (outputs)
+          const unsigned long long E = (unsigned long long)n_edges;
+          const int max_states = s_mp.max_states, round_budget = s_mp.round_budget, check_target = s_mp.check_target;
+          const double delta = __longlong_as_double((long long)s_mp.delta_bits), lambda = __longlong_as_double((long long)s_mp.lambda_bits);
+          const double *from = edge_from, *to = edge_to, *carry_in = s_mp.has_carry ? edge_carry : nullptr;
+          double *states = reinterpret_cast<double *>(box + kResMultiStatesOff / 8);
+          int32_t *n_states = reinterpret_cast<int32_t *>(mresp + kResMultiRespN), *newton_iters = reinterpret_cast<int32_t *>(mresp + kResMultiRespIts);
+          uint8_t *ok_out = reinterpret_cast<uint8_t *>(mresp + kResMultiRespOk);
+          double *carry_out = reinterpret_cast<double *>(mresp + kResMultiRespCarry);
+          unsigned long long *queue = &s_ticket;
+#define CCMP_ROW16_NO_PROLOGUE
+#include "ccmp_row16_geo_body.inc"
+#undef CCMP_ROW16_NO_PROLOGUE
+        }
+      }
+    } else if (cmd == kResProject || cmd == kResFunction || cmd == kResIsSatisfied || cmd == kResJointValid) {
+      if (tid < 64) { // wavefront 0; its row 0 carries the state, rows 1..3 stay without one (as rows of project_row16_kernel past the batch)
+        // joint role and chain role: as project_row16_kernel
+        const bool jl = l < 14;
+        const int lj = jl ? l : 13;
+        const int aj = lj >= 7 ? 1 : 0, ij = lj - 7 * aj;
+        double ax[3], ap[6];
+#pragma unroll
+        for (int k = 0; k < 3; k++) ax[k] = K.axis[aj][ij][k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) ap[k] = K.aprod[aj][ij][k];
+        const double lbe = K.lbe[ij], ube = K.ube[ij];
+        const double sgn = aj ? -1.0 : 1.0;
+        const int ac = (l / 3) & 1, rc = l % 3;
+        double cee[3], cRt[9];
+#pragma unroll
+        for (int k = 0; k < 3; k++) cee[k] = K.ee[ac][k];
+#pragma unroll
+        for (int k = 0; k < 9; k++) cRt[k] = K.R_tool[ac][k];
+        const double cd = K.base_R[ac][4 * rc], cbp = K.base_p[ac][rc];
+        const bool row0 = lane < 16;
+        double x = row0 ? s_x[lj] : 0.0;
+        int iter = 0, updates = 0;
+        double norm1 = 0.0, norm2 = 0.0;
+        bool ok = false;
+        if (cmd == kResJointValid) { // ConstraintFunction.h:43-55
+          const bool bad = row0 && jl && (x < lbe || x > ube);
+          ok = (__builtin_amdgcn_ballot_w64(bad) & 0xFFFFull) == 0ull;
+        } else if (cmd == kResProject) { // KinematicChainConstraint::project (ConstraintFunction.h:57-82): project_row16_kernel's sequence
+          bool active = row0;
+          for (;;) {
+            if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
+#include "ccmp_row16_eval.inc"
+            bool cont = false;
+            if (active) { // ConstraintFunction.h:68, quirks included
+              const bool c1 = f[0] > K.tol_pos;
+              norm1 = c1 ? 1.0 : 0.0;
+              bool resid = c1;
+              if (!c1) { norm2 = f[1]; resid = f[1] > K.tol_rot; }
+              if (resid) { cont = iter < K.max_iter; iter++; }
+            }
+            {
+              const bool fin = active && !cont;
+              bool bad = false;
+              if (fin && jl) {
+                if (x < lbe) bad = true;
+                if (x > ube) bad = true;
+                res_store(resp + kResRespQ + lj, (unsigned long long)__double_as_longlong(x));
+              }
+              const unsigned long long badmask = __builtin_amdgcn_ballot_w64(bad);
+              if (fin) {
+                ok = ((badmask & 0xFFFFull) == 0ull) && (norm1 < K.tol_pos) && (norm2 < K.tol_rot);
+                active = false;
+              }
+            }
+            if (__builtin_amdgcn_ballot_w64(cont) == 0ull) continue;
+#include "ccmp_row16_step.inc"
+          }
+        } else { // function(x): one evaluation; KinematicChainConstraint::isSatisfied's test on it (ConstraintFunction.h:114-120)
+#include "ccmp_row16_eval.inc"
+          ok = (f[0] - f[0] == 0.0) && (f[1] - f[1] == 0.0) && f[0] <= K.tol_pos && f[1] <= K.tol_rot;
+          if (tid < 2) res_store(resp + kResRespF + tid, (unsigned long long)__double_as_longlong(tid ? f[1] : f[0]));
+        }
+        if (tid == 0) flags = (unsigned long long)(ok ? 1u : 0u) | ((unsigned long long)(unsigned int)updates << 32);
+      }
+    } else {
+      flags = kResErrTorn; // a command this kernel does not serve (the host never sends one): answered, refused
+    }
+    if (tid == 0) res_store(resp + kResRespFlags, flags);
+    // every wavefront's result words are on their way before the tag is: system fence, block barrier, then the tag
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) {
+      __hip_atomic_store(resp + kResRespDone, s_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      idle_since = wall_clock64();
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    __threadfence_system();
+    __hip_atomic_store(state, (unsigned long long)kResExited, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 } // namespace
 
 namespace ccmp_launch {
@@ -614,6 +852,16 @@ hipError_t geodesic_analytic_scene(const GeoCall &g, const GeoScene &s, int bloc
   if (g.K->base_diag == 3) CCMP_LAUNCH_GEO_ROW16_SCENE(true);
   else CCMP_LAUNCH_GEO_ROW16_SCENE(false);
 #undef CCMP_LAUNCH_GEO_ROW16_SCENE
+  return hipGetLastError();
+}
+
+// The resident service kernel for a problem in analytic mode (ccmp_resident.cpp starts it on the service's own stream).
+hipError_t resident_row16(int diag, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st)
+{
+  if (diag)
+    hipLaunchKernelGGL(resident_row16_kernel<true>, dim3(1), dim3(128), 0, st, (unsigned long long *)box_dev, last_tag, idle_ticks);
+  else
+    hipLaunchKernelGGL(resident_row16_kernel<false>, dim3(1), dim3(128), 0, st, (unsigned long long *)box_dev, last_tag, idle_ticks);
   return hipGetLastError();
 }
 

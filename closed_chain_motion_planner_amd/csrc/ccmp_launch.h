@@ -144,6 +144,7 @@ hipError_t clearance(const ccmp_consts *K, const ccmp::scene_dev *scene, int n_s
                      double margin, double *clearance, int32_t *pair, uint8_t *free_out, int blocks, int per_state, unsigned int *done_flag,
                      unsigned int done_seq, hipStream_t st);
 hipError_t resident(int stock, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st);
+hipError_t resident_row16(int diag, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st);
 // lib/libccmp_debug.so only (ccmp_kernels_debug.hip)
 hipError_t detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
 hipError_t div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);

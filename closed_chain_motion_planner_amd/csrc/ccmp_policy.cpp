@@ -342,6 +342,7 @@ int ccmp_ctx_get_option(const ccmp_ctx *ctx, const char *name, long *value)
     return CCMP_OK;
   }
   if (!strcmp(name, "resident")) { *value = ctx ? ctx->resident_on : 0; return CCMP_OK; }
+  if (!strcmp(name, "resident_served")) { *value = ctx ? ctx->resident_served : 0; return CCMP_OK; } // requests the service has answered (a served call and a fallen-back one give the same bits: only this tells them apart)
   if (!strcmp(name, "resident_gave_up")) { *value = ctx ? ctx->resident_gave_up : 0; return CCMP_OK; } // how often a start gave up (that call took the launch path; the option stays on)
   const OptionDesc *o = find_option(name);
   if (!o) return CCMP_EINVAL;

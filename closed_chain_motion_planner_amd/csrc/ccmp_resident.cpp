@@ -23,7 +23,7 @@ struct ccmp_resident {
   bool abandoned = false;   // ... and did not get to run within the start bound: told to stop, not waited for (it leaves as soon as it runs)
   bool broken = false;      // a request was not answered within its bound: the service is not used again by this context
   double retry_after_ms = 0, backoff_ms = 0; // no new start before this time (steady clock); doubled by every start that gave up
-  int stock = -1;           // which instantiation runs
+  int stock = -1;           // which kernel runs: 0 / 1 resident_service_kernel<false / true> (FD), 2 / 3 resident_row16_kernel<false / true> (analytic)
   unsigned int tag = 0;     // sequence number of the last request
   unsigned int consts_seq = 0;
   bool have_problem = false;
@@ -40,23 +40,9 @@ double now_ms()
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// a request line's tag: the request's sequence number (low half) and a checksum of the line's seven payload words (high half) — the
-// device accepts a line only when the two belong together (ccmp_kernels_resident.hip)
-unsigned long long line_tag(unsigned int seq, const volatile unsigned long long *w7)
-{
-  unsigned long long h = 0;
-  for (int i = 0; i < 7; i++) {
-    const unsigned long long v = w7[i];
-    const int r = 7 * i + 1;
-    h ^= (v << r) | (v >> (64 - r));
-  }
-  return (unsigned long long)seq | ((unsigned long long)(unsigned int)(h ^ (h >> 32)) << 32);
-}
-// payloads are in place: the five tags, last
-void post(volatile unsigned long long *req, unsigned int seq)
-{
-  for (int line = 0; line < 5; line++) __atomic_store_n(&req[8 * line + 7], line_tag(seq, req + 8 * line), __ATOMIC_RELEASE);
-}
+// a request line's tag and the posting of a request: ccmp_resident_proto.h (one text for this side, the analytic service kernel and a
+// host-only test).  The header's five lines:
+void post(volatile unsigned long long *req, unsigned int seq) { ccmp_res::post(req, 5, seq); }
 
 // waits for the kernel on the service's stream to be gone (it has been told to stop, or stopped by itself)
 void drain(ccmp_resident *r)
@@ -110,7 +96,8 @@ int start(ccmp_ctx *ctx, ccmp_resident *r, int stock)
   drain(r); // (a kernel that left by itself)
   __atomic_store_n(word(r, kResStateOff), (unsigned long long)kResStarting, __ATOMIC_RELEASE);
   const unsigned long long idle_ticks = (unsigned long long)ctx->resident_idle_ms * 100000ull; // wall_clock64: 100 MHz
-  HIP_TRY(ccmp_launch::resident(stock, r->box_dev, r->tag, idle_ticks, r->stream));
+  HIP_TRY(stock >= 2 ? ccmp_launch::resident_row16(stock - 2, r->box_dev, r->tag, idle_ticks, r->stream)
+                     : ccmp_launch::resident(stock, r->box_dev, r->tag, idle_ticks, r->stream));
   r->launched = true;
   r->stock = stock;
   // The kernel reports itself running with its first instructions (~20 us behind the launch).  If it does not within 5 ms — two
@@ -210,12 +197,19 @@ int resident_set(ccmp_ctx *ctx, long on)
 int resident_call(ccmp_ctx *ctx, const ccmp_problem *p, const ResidentCall &call)
 {
   ccmp_resident *r = ctx->resident;
-  if (!ctx->resident_on || !r || !p || p->jacobian_mode != CCMP_JAC_FD) return kResidentFallBack; // reference arithmetic only
+  if (!ctx->resident_on || !r || !p || (p->jacobian_mode != CCMP_JAC_FD && p->jacobian_mode != CCMP_JAC_ANALYTIC)) return kResidentFallBack;
+  const bool analytic = p->jacobian_mode == CCMP_JAC_ANALYTIC;
+  // each kernel serves its own extend-step command: the FD kernel one edge, the analytic kernel up to eight with carry_in
+  if ((call.cmd == kResGeodesic && analytic) || (call.cmd == kResGeodesicMulti && (!analytic || call.E < 1 || call.E > ccmp_res::kMultiMaxEdges)))
+    return kResidentFallBack;
   if (r->broken) return kResidentFallBack;
   if (r->abandoned && !may_start(r)) return kResidentFallBack; // an abandoned kernel is still queued, or the back-off has not passed
   // a request whose worst case (max_iter rounds for each of max_states states, ~20 us each under load) exceeds what the answer is
-  // waited for goes to the launch path instead of timing out spuriously
-  const double worst_ms = 0.02 * (double)p->max_iter * (double)(call.cmd == kResGeodesic ? (call.max_states > 0 ? call.max_states : 1) : 1);
+  // waited for goes to the launch path instead of timing out spuriously.  The same formula for the analytic kernel, where it is
+  // conservative: a round of the row16 layout is ~2.7 us (ccmp_kernels_fast.hip), the edges of a request run side by side, and even
+  // all eight taken by ONE row one after the other (8 x 2.7 us per round) stay at the figure the formula charges for one.
+  const bool is_geo = call.cmd == kResGeodesic || call.cmd == kResGeodesicMulti;
+  const double worst_ms = 0.02 * (double)p->max_iter * (double)(is_geo ? (call.max_states > 0 ? call.max_states : 1) : 1);
   if (worst_ms > 1500.0) return kResidentFallBack;
   // the problem in force: its kernel constants go into the mailbox when it changes (a planner sets its problem up once)
   if (!r->have_problem || r->stock_kernels != ctx->stock_kernels || memcmp(&r->problem, p, sizeof *p) != 0) {
@@ -223,11 +217,13 @@ int resident_call(ccmp_ctx *ctx, const ccmp_problem *p, const ResidentCall &call
     ccmp_consts K;
     make_consts(*p, K);
     if (!ctx->stock_kernels) K.stock = K.twin_arms = K.rot_x0 = 0;
-    if (r->launched && r->stock != (K.stock ? 1 : 0)) stop(r); // the other instantiation of the kernel
+    // which kernel serves this problem; another one running is stopped first and the right one started below: one launch
+    const int variant = analytic ? 2 + (K.base_diag == 3 ? 1 : 0) : (K.stock ? 1 : 0);
+    if (r->launched && r->stock != variant) stop(r);
     static_assert(sizeof(ccmp_consts) <= kResStateOff, "the constants fit in front of the state word");
     if (!r->box) { // (first use: the mailbox comes with the first start)
       if (!may_start(r)) return kResidentFallBack;
-      int rc = start(ctx, r, K.stock ? 1 : 0);
+      int rc = start(ctx, r, variant);
       if (rc != CCMP_OK) return rc; // (kResidentFallBack: the service could not get a queue of its own)
     }
     memcpy(r->box + kResConstsOff, &K, sizeof K);
@@ -235,7 +231,7 @@ int resident_call(ccmp_ctx *ctx, const ccmp_problem *p, const ResidentCall &call
     r->problem = *p;
     r->have_problem = true;
     r->stock_kernels = ctx->stock_kernels;
-    if (!r->launched) r->stock = K.stock ? 1 : 0;
+    if (!r->launched) r->stock = variant;
   }
   // (re)start: never started, stopped by quiesce(), or left by itself after its idle time
   if (!r->launched || __atomic_load_n(word(r, kResStateOff), __ATOMIC_ACQUIRE) == (unsigned long long)kResExited) {
@@ -255,6 +251,22 @@ int resident_call(ccmp_ctx *ctx, const ccmp_problem *p, const ResidentCall &call
     req[8 + i] = b;
   }
   req[32] = (unsigned long long)(unsigned int)call.cmd | ((unsigned long long)r->consts_seq << 32);
+  if (call.cmd == kResGeodesicMulti) {
+    // the edges' lines and their tags FIRST (x86 stores become visible in program order): when the kernel sees the header's fresh
+    // tags, these are in place; it reads them only then.  The header's spare word 5 tells it how many edges' lines to read.
+    volatile unsigned long long *area = word(r, kResMultiReqOff);
+    ccmp_res::MultiParams m;
+    m.E = call.E;
+    m.has_carry = call.carry_in ? 1 : 0;
+    m.max_states = call.max_states;
+    m.round_budget = call.round_budget;
+    m.check_target = call.check_target;
+    m.delta_bits = ccmp_res::bits_of(p->delta);
+    m.lambda_bits = ccmp_res::bits_of(p->lambda);
+    ccmp_res::multi_pack(area, m, call.x, call.to, call.carry_in);
+    ccmp_res::post(area, ccmp_res::multi_lines(call.E), tag);
+    req[37] = (unsigned long long)(unsigned int)call.E;
+  } else req[37] = 0;
   if (call.cmd == kResGeodesic) {
     for (int i = 0; i < 7; i++) {
       unsigned long long a, b;
@@ -303,6 +315,22 @@ int resident_call(ccmp_ctx *ctx, const ccmp_problem *p, const ResidentCall &call
     return CCMP_EHIP;
   }
   const unsigned long long flags = resp[kResRespFlags];
+  if (analytic && (flags & kResErrTorn)) return kResidentFallBack; // the kernel refused the request (its lines never agreed): this call takes the launch path
+  ctx->resident_served++;
+  if (call.cmd == kResGeodesicMulti) {
+    const unsigned long long *mresp = reinterpret_cast<const unsigned long long *>(r->box + kResMultiRespOff);
+    const double *box_states = reinterpret_cast<const double *>(r->box + kResMultiStatesOff);
+    for (int e = 0; e < call.E; e++) {
+      int32_t n;
+      memcpy(&n, reinterpret_cast<const char *>(mresp + kResMultiRespN) + 4 * e, 4);
+      call.n_states[e] = n;
+      call.ok[e] = *(reinterpret_cast<const uint8_t *>(mresp + kResMultiRespOk) + e); // 0 / 1 / 2 (round budget spent)
+      const int rows = n > call.max_states ? call.max_states : (n < 0 ? 0 : n);
+      memcpy(call.states + (size_t)e * call.max_states * 14, box_states + (size_t)e * call.max_states * 14, (size_t)rows * 14 * sizeof(double));
+      if (call.carry_out) memcpy(call.carry_out + 2 * e, mresp + kResMultiRespCarry + 2 * e, 2 * sizeof(double));
+    }
+    return CCMP_OK;
+  }
   if (call.cmd == kResGeodesic) {
     const unsigned long long nw = resp[kResRespN];
     int32_t n;

@@ -4,6 +4,11 @@
 // the reference's svc->isValid runs on the device: in kBook, after a successful projection and before the step test, the row computes
 // the proxy scene's clearance of the state (ccmp_clearance.h, sixteen lanes) and a state whose clearance does not exceed `margin` ends
 // the edge, blocked.  The including kernel then also provides scene, margin, blocked_out and clearance_out (nullable).
+// With CCMP_ROW16_NO_PROLOGUE defined (the analytic resident service kernel, resident_row16_kernel: the text runs once per request
+// inside a kernel that never ends) the including scope provides what the prologue would: K (the constants, in LDS), lane (within
+// the wavefront), l, rec (the row's record) — besides the kernel's arguments from, to, E, max_states, states, n_states, ok_out,
+// newton_iters, carry_in, carry_out, round_budget, check_target, queue (there: a ticket word in LDS), delta and lambda.
+#ifndef CCMP_ROW16_NO_PROLOGUE
   __shared__ double ktab[kConstsDoubles + 1];
   __shared__ double lds[4 * gRec];
   {
@@ -14,6 +19,7 @@
   const ccmp_consts &K = *reinterpret_cast<const ccmp_consts *>(ktab);
   const int lane = threadIdx.x, l = lane & 15;
   double *const rec = lds + (lane >> 4) * gRec;
+#endif
 #ifdef CCMP_ROW16_SCENE
   // the row's proxy centres; its frames go to the front of its record (the Newton round's workspace, dead between two projections)
   __shared__ double clr_cen[4 * kClrCentres];

@@ -141,7 +141,7 @@ int ccmp_ctx_set_lpt(ccmp_ctx *ctx, int mode, size_t min_batch);
 /* Tuning options, by name.  NONE of them changes a result bit: they choose which kernels a call runs on and where the regimes
  * meet.  ccmp_ctx_set_option: CCMP_EINVAL for an unknown name or a value outside the range.  ccmp_ctx_get_option: the value in
  * force; with ctx == NULL the built-in default (no device needed); besides the table it answers "num_cus", "resident",
- * "resident_gave_up" and "side_stream_busy" (1 while the context's side stream still holds unfinished work).  ccmp_ctx_option_info enumerates the table
+ * "resident_gave_up", "resident_served" and "side_stream_busy" (1 while the context's side stream still holds unfinished work).  ccmp_ctx_option_info enumerates the table
  * (index 0 .. until CCMP_EINVAL; any out-pointer may be NULL).  The table below is GENERATED from the library's
  * (tools/gen_option_docs.py) and compared with it by the CPU test suite, so a default stated here is the default in the code.
  * "resident" (0 / 1, default 0; not in the table: it starts and stops something) — see "resident service kernel" below. */
@@ -210,12 +210,24 @@ int ccmp_ctx_option_info(int index, const char **name, long *dflt, long *lo, lon
  *   "resident_idle_ms"              10        1..10000      the resident service kernel (option "resident") leaves by itself after this many
  *                                                           milliseconds without a request
  * END OPTION TABLE */
-/* Resident service kernel (option "resident", 0 / 1, default 0): with it on, the one-at-a-time calls the unchanged planner makes —
- * ccmp_project_host, ccmp_function_host, ccmp_is_satisfied_host, ccmp_joint_valid_host with B == 1, and ccmp_geodesic_host /
- * ccmp_geodesic_host_ex / ccmp_check_motion_host with E == 1 (no carry_in, max_states <= 64), reference arithmetic: the reference's
- * project(State*) / isSatisfied(State*) / discreteGeodesic and checkMotion of one pair, src/base/jy_ProjectedStateSpace.cpp:13,20,27,
- * 32-96, src/planner/stefanBiPRM.cpp:315-318,397-398 — are served by ONE persistent 128-thread block that waits on a mailbox in pinned host memory, instead of a kernel launch
- * and a completion poll each: the same bits, ~10-13 us less per call.  Started by the first such call, never under stream capture.
+/* Resident service kernel (option "resident", 0 / 1, default 0): with it on, the calls the unchanged planner makes one at a time or
+ * a handful at a time are served by ONE persistent 128-thread block that waits on a mailbox in pinned host memory, instead of a
+ * kernel launch and a completion poll each: the same bits, no launch on the call path.  What is served:
+ *   both modes      ccmp_project_host, ccmp_function_host, ccmp_is_satisfied_host, ccmp_joint_valid_host with B == 1 — the reference's
+ *                   project(State*) / isSatisfied(State*), src/base/jy_ProjectedStateSpace.cpp:13,20,27,65;
+ *   CCMP_JAC_FD     ccmp_geodesic_host / ccmp_geodesic_host_ex / ccmp_check_motion_host with E == 1, without carry_in, max_states <= 64 —
+ *                   discreteGeodesic and checkMotion of one pair, src/planner/stefanBiPRM.cpp:315-318,397-398 (one state needs the
+ *                   whole block in this mode: several edges would only run one after the other);
+ *   CCMP_JAC_ANALYTIC  the same three entry points with 1 <= E <= 8 (growTree's five neighbours in one request: the edges traverse
+ *                   side by side, one row of sixteen lanes each), WITH or without carry_in (continuation calls), max_states <= 64.
+ * Everything else — larger E, longer lists, ccmp_geodesic_scene_host, every *_batch entry point — takes the launch path as before.
+ * Each mode has its own kernel and one runs at a time: a call whose problem is of the other mode (or of the other instantiation
+ * within a mode: stock / calibrated arms, diagonal / general base frames) stops the running kernel and starts the right one, which
+ * costs ONE launch.  A planner that sets its mode once pays that once; one that alternates modes call by call pays it every time
+ * and is better off without the option.  Started by the first served call, never under stream capture.
+ * ccmp_ctx_get_option(ctx, "resident_served") is the number of requests the service has answered for this context (0 with
+ * ctx == NULL; read-only, not in the table): a served call and one that fell back to the launch path give the same bits, and only
+ * this count tells them apart.
  * What a kernel that stays on the device asks of the caller: the LIBRARY stops it before every hipFree / hipMalloc / device-wide
  * synchronise of its own and in ccmp_ctx_destroy (and takes the launch path while it is stopped), so every entry point of this
  * header can be mixed with resident calls; the APPLICATION's own hipDeviceSynchronize / hipFree waits until the service leaves by
@@ -223,9 +235,10 @@ int ccmp_ctx_option_info(int index, const char **name, long *dflt, long *lo, lon
  * stream has the lowest priority (a hardware queue of its own); should the kernel not get to run within 5 ms of a start — its queue
  * is shared with something that does not end soon, e.g. another context's service — THAT CALL takes the launch path, the kernel is
  * told to stop and abandoned (never waited for), and a later call starts the service again behind a back-off (10 ms, doubling up
- * to 1 s; "resident_gave_up" counts the occasions; setting "resident" to 1 again clears both).  Every host-side wait is bounded:
- * a request whose worst case exceeds 1.5 s goes to the launch path, CCMP_EHIP after 2 s without an answer (the service is then not
- * used again by the context). */
+ * to 1 s; "resident_gave_up" counts the occasions; setting "resident" to 1 again clears both).  Every wait is bounded, on both
+ * sides: a request whose worst case exceeds 1.5 s goes to the launch path, CCMP_EHIP after 2 s without an answer (the service is
+ * then not used again by the context); a several-edge request whose lines the kernel cannot read consistently within its bound is
+ * answered with a refusal and that call takes the launch path. */
 /* What the policy does with a call: writes ONE line into buf (NUL-terminated, truncated to cap) naming the kernels a call of
  * kind call_kind over n samples / edges runs on under the context's present settings, and the thresholds that delimit that
  * regime — computed by the same functions the launches use (csrc/ccmp_policy.cpp), so it cannot disagree with them.  ctx == NULL:

@@ -119,7 +119,10 @@ public:
   // The unchanged planner calls the constraint one state at a time (project(State*), isSatisfied(State*):
   // src/base/jy_ProjectedStateSpace.cpp:13,20,27,65, src/planner/stefanBiPRM.cpp:397-398), and each such call is a kernel launch
   // plus a completion poll.  setResident(true) turns on the context's resident service kernel (include/ccmp.h, option "resident"):
-  // the same calls, the same bits, no launch on the call path (project(x) ~10 us less, isSatisfied 21 -> 9 us).  Opt-in because a
+  // the same calls, the same bits, no launch on the call path (project(x) ~10 us less, isSatisfied 21 -> 9 us).  In the reference
+  // arithmetic it also serves discreteGeodesic / checkMotion of ONE pair; after setJacobianMode(1) it serves discreteGeodesicBatch
+  // of up to eight edges (growTree's five) and the continuation calls below, which carry carry_in — they reach it through
+  // ccmp_geodesic_host_ex by themselves.  ccmp_ctx_get_option(ctx(), "resident_served", &n) counts the served requests.  Opt-in because a
   // kernel that stays on the device makes a device-wide synchronise of the APPLICATION's own (hipDeviceSynchronize, hipFree) wait
   // until the service has idled out ("resident_idle_ms", default 10 ms); the library's own calls stop it first.
   void setResident(bool on)
@@ -685,7 +688,8 @@ public:
     impl_->setInitialPosition(q.data());
   }
   // opt-in (not part of the reference's class): the context's resident service kernel for the one-state-at-a-time calls below
-  // — same results, ~10 us less per call; see ccmp::Projector::setResident for what it asks of the application
+  // and, in analytic mode, for discreteGeodesics of up to eight edges and their continuations — same results, ~10 us less per call;
+  // see ccmp::Projector::setResident for what it asks of the application
   void setResident(bool on) { impl_->setResident(on); }
   void setTolerance(const double tolerance1, const double tolerance2)
   {

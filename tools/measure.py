@@ -14,7 +14,8 @@
     python tools/measure.py sharded [n_gpus [B]]            one process, n GPUs, RCCL all-gather inside the C ABI: per-GPU stream times
     python tools/measure.py sampler                         project_batch vs the fused sampler
     python tools/measure.py soak                            25 repeats of the default policy, outputs compared bit for bit
-    python tools/measure.py soak_resident [N]               N states as single calls through the resident service kernel against the batched kernels
+    python tools/measure.py soak_resident [N] [--analytic]  N states as single calls through the resident service kernel against the batched kernels
+                                                            (--analytic: analytic mode, and five checkMotion edges per request instead of one)
     python tools/measure.py scout                           FP32 scout's predictions against the true iteration counts
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
@@ -104,6 +105,27 @@ def single(argv):
         c.project(x)
         ts.append(time.perf_counter() - t0)
     print("project near the manifold: median %.1f us" % (np.median(np.array(ts[4:])) * 1e6))
+    # analytic mode, launched against the resident service (option "resident"): interleaved passes, median per pass, minimum of the passes
+    c.setJacobianMode(1)
+    ctx.set_option("resident_idle_ms", 200)
+    near = np.array([x0 + 0.02 * np.sin(np.arange(14) + i) for i in range(64)])
+    res = {}
+    for on in (0, 1, 0, 1):
+        ctx.set_option("resident", on)
+        for name, xs, fn in (("project(uniform)", q, c.project), ("project(near)", near, c.project), ("function", near, c.function),
+                             ("isSatisfied", near, c.isSatisfied), ("jointValid", near, c.jointValid)):
+            ts = []
+            for x in xs:
+                y = x.copy()
+                t0 = time.perf_counter()
+                fn(y)
+                ts.append(time.perf_counter() - t0)
+            res.setdefault((name, on), []).append(float(np.median(ts[8:]) * 1e6))
+    print("analytic mode, served by the resident service: %d requests" % ctx.get_option("resident_served"))
+    ctx.set_option("resident", 0)
+    c.setJacobianMode(0)
+    for name in ("project(uniform)", "project(near)", "function", "isSatisfied", "jointValid"):
+        print("analytic %-17s launched %6.1f us   resident %6.1f us" % (name, min(res[(name, 0)]), min(res[(name, 1)])))
 
 
 def geodesic(argv):
@@ -140,6 +162,23 @@ def geodesic(argv):
         print("E=%-6d %s%s | mean states %.2f (first %d), reached %.3f, Newton iterations per edge %.1f"
               % (E, "analytic mode: " if analytic else "", "; ".join(row), n.clamp(max=cap).float().mean().item(), cap, (okg == 1).float().mean().item(),
                  its.float().mean().item()), flush=True)
+        if analytic and E <= 8:  # the host ABI on these edges (growTree's shape), launched against the resident service
+            L, dp = _lib.lib(), C.POINTER(C.c_double)
+            fh, th = np.ascontiguousarray(frm.cpu().numpy()), np.ascontiguousarray(to.cpu().numpy())
+            st, nn, okb, cr = np.zeros((E, 64, 14)), (C.c_int32 * E)(), (C.c_uint8 * E)(), np.zeros((E, 2))
+            ctx.set_option("resident_idle_ms", 200)
+            res = {}
+            for on in (0, 1, 0, 1):
+                ctx.set_option("resident", on)
+                ts = []
+                for _ in range(72):
+                    t0 = time.perf_counter()
+                    L.ccmp_geodesic_host_ex(ctx.handle, C.byref(c.problem), fh.ctypes.data_as(dp), th.ctypes.data_as(dp), E, 64, st.ctypes.data_as(dp), nn, okb,
+                                            None, cr.ctypes.data_as(dp), 0, 1)
+                    ts.append(time.perf_counter() - t0)
+                res.setdefault(on, []).append(float(np.median(ts[8:]) * 1e6))
+            ctx.set_option("resident", 0)
+            print("E=%-6d analytic mode, ccmp_geodesic_host_ex (lists of 64, checkMotion): launched %.1f us   resident %.1f us" % (E, min(res[0]), min(res[1])), flush=True)
         c.setJacobianMode(0)
 
 
@@ -353,13 +392,18 @@ def soak_resident(argv):
     """the resident service kernel under a long run: N distinct states, each through project / function / isSatisfied / jointValid as
     single calls on the service, against the BATCHED kernels' results on the same states (both are bit-identical to the oracle, so
     they must be to each other) — with idle exits (the service leaves after 2 ms here and restarts), batch launches and workspace
-    growth on the same context in between, and every 64th state a single checkMotion edge towards the next one"""
+    growth on the same context in between, and every 64th state a single checkMotion edge towards the next one.  --analytic: the
+    same in analytic mode (the row16 service kernel), with FIVE edges per request at every 64th state"""
     import time
 
+    analytic = "--analytic" in argv
+    argv = [a for a in argv if a != "--analytic"]
+    per_req = 5 if analytic else 1
     N = int(argv[0]) if argv else 20000
     ctx = Context(0)
     for obj in ("Wine_Bottle", "stefan"):
         c = KinematicChainConstraint.from_yaml(CFG % obj, ctx=ctx)
+        c.setJacobianMode(1 if analytic else 0)
         far = c.ambient_uniform_batch(0x50C, 0, N)
         qp, okp, _ = c.project_batch(c.ambient_uniform_batch(0x50D, 0, 4 * N))
         near = qp[okp == 1][: N // 2] + 0.04 * (torch.rand((min(N // 2, int((okp == 1).sum())), 14), dtype=torch.float64, device=qp.device) - 0.5)
@@ -379,6 +423,7 @@ def soak_resident(argv):
         L, dp = _lib.lib(), C.POINTER(C.c_double)
         ctx.set_option("resident_idle_ms", 2)
         ctx.set_option("resident", 1)
+        served0 = ctx.get_option("resident_served")
         bad = restarts = 0
         grow = 30000
         t0 = time.perf_counter()
@@ -391,13 +436,16 @@ def soak_resident(argv):
                     and bool(ok) == bool(okb_h[k]) and np.array_equal(np.isnan(f), np.isnan(fb_h[k])) and np.array_equal(f[~np.isnan(f)].view(np.uint64), fb_h[k][~np.isnan(f)].view(np.uint64))
                     and bool(c.isSatisfied(x)) == bool(sb_h[k]) and bool(c.jointValid(x)) == bool(jb_h[k]))
             if k % 64 == 0 and k // 64 < len(edges):
-                e = k // 64
-                # one edge from host buffers, as the unchanged planner asks for it: through the service
-                st, n1, ok1 = np.zeros((16, 14)), (C.c_int32 * 1)(), (C.c_uint8 * 1)()
-                rc = L.ccmp_geodesic_host_ex(ctx.handle, C.byref(c.problem), frm_h[e].ctypes.data_as(dp), to_h[e].ctypes.data_as(dp), 1, 16,
+                # one edge (analytic mode: five) from host buffers, as the unchanged planner asks for them: through the service
+                es = [(k // 64 + j) % len(edges) for j in range(per_req)]
+                fa, ta = np.ascontiguousarray(frm_h[es]), np.ascontiguousarray(to_h[es])
+                st, n1, ok1 = np.zeros((per_req, 16, 14)), (C.c_int32 * per_req)(), (C.c_uint8 * per_req)()
+                rc = L.ccmp_geodesic_host_ex(ctx.handle, C.byref(c.problem), fa.ctypes.data_as(dp), ta.ctypes.data_as(dp), per_req, 16,
                                              st.ctypes.data_as(dp), n1, ok1, None, None, 0, 1)
-                n = min(int(exp_n[e]), 16)
-                same = same and rc == 0 and int(n1[0]) == int(exp_n[e]) and int(ok1[0]) == int(exp_ok[e]) and st[:n].tobytes() == exp_st[e, :n].tobytes()
+                same = same and rc == 0
+                for j, e in enumerate(es):
+                    n = min(int(exp_n[e]), 16)
+                    same = same and int(n1[j]) == int(exp_n[e]) and int(ok1[j]) == int(exp_ok[e]) and st[j, :n].tobytes() == exp_st[e, :n].tobytes()
             bad += not same
             if k % 997 == 0:
                 time.sleep(0.004)  # idle exit: the next call starts the service again
@@ -406,11 +454,11 @@ def soak_resident(argv):
                 grow += 7000
                 c.project_batch(c.ambient_uniform_batch(0x50E, k, grow))
         dt = time.perf_counter() - t0
-        gave_up = ctx.get_option("resident_gave_up")
+        gave_up, served = ctx.get_option("resident_gave_up"), ctx.get_option("resident_served") - served0
         ctx.set_option("resident", 0)
-        print("%s: %d states x (project, function, isSatisfied, jointValid) + %d single checkMotion edges through the resident service, %d idle exits, "
-              "%d batch calls in between: differing from the batched kernels %d; gave up %d; %.1f s" %
-              (obj, xs_h.shape[0], len(edges), restarts, xs_h.shape[0] // 4001 + 1, bad, gave_up, dt), flush=True)
+        print("%s%s: %d states x (project, function, isSatisfied, jointValid) + %d checkMotion requests of %d edge(s) through the resident service "
+              "(%d requests served), %d idle exits, %d batch calls in between: differing from the batched kernels %d; gave up %d; %.1f s" %
+              (obj, " (analytic)" if analytic else "", xs_h.shape[0], len(edges), per_req, served, restarts, xs_h.shape[0] // 4001 + 1, bad, gave_up, dt), flush=True)
         assert bad == 0 and gave_up == 0
 
 
