@@ -3,7 +3,8 @@
 Translation units with deliberately different flags:
   ccmp_kernels_fd.hip    -ffp-contract=off -DCCMP_USE_FMA   canonical, bit-reproducible arithmetic (throughput kernel);
                          -DCCMP_LEAN_SQRT: ccmp_detmath.h's wave-uniform fast path of the IEEE square root (same bits, -1.9 %);
-                         -DCCMP_FD_ROT_X0 -DCCMP_FD_BASE_FOLD: the stock structure's short rotation and folded base frame (same bits, -5.9 %)
+                         -DCCMP_FD_ROT_X0 -DCCMP_FD_BASE_FOLD: the stock structure's short rotation and folded base frame (same bits, -5.9 %);
+                         -DCCMP_FD_GROUP_SOLVE: the minimum-norm solve spread over a group's six lanes, one solve per sample (same bits)
   ccmp_kernels_wave.hip  -ffp-contract=off -DCCMP_USE_FMA   same arithmetic, one-wave-per-sample kernels
   ccmp_kernels_flat.hip  -ffp-contract=off -DCCMP_USE_FMA   same arithmetic, one 128-thread block per sample (latency kernel)
   ccmp_kernels_geo.hip   -ffp-contract=off -DCCMP_USE_FMA   the extend step on the same Newton routine (ccmp_flat_newton.h), built twice:
@@ -50,8 +51,11 @@ _UNITS = [
     # FP64 work fixed by the stock Panda's structure (STOCK instantiations only, same bits): CCMP_FD_ROT_X0 general joints'
     # rotation in 7 operations for 13 where no angle of the round is within 1e-8 of a multiple of 2 pi (-2.7 %), CCMP_FD_BASE_FOLD the
     # diag(+-1) base frame folded into the other arm's pose once per arm instead of nine products per stencil point (-2.4 %); together -5.9 %
+    # CCMP_FD_GROUP_SOLVE (ccmp_fd_newton_phase2.inc, every instantiation, same bits): the 2x14 minimum-norm solve once per sample — lane r of
+    # a group rotates and updates columns r, r + 6, r + 12, each serial Gram sum is one chain in one lane — instead of whole in each of the
+    # six lanes: -262 VALU / -191 FP64 instructions per round (static count of project_fd_kernel<0, true>; the solve is straight-line code)
     ("ccmp_kernels_fd.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-DCCMP_ATAN_UNIFORM", "-DCCMP_FD_TI_HOIST",
-                             "-DCCMP_FD_ROT_X0", "-DCCMP_FD_BASE_FOLD",
+                             "-DCCMP_FD_ROT_X0", "-DCCMP_FD_BASE_FOLD", "-DCCMP_FD_GROUP_SOLVE",
                              "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
      + os.environ.get("CCMP_FD_EXTRA_FLAGS", "").split()),
     ("ccmp_kernels_wave.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA"]),
