@@ -3,8 +3,7 @@
 Translation units with deliberately different flags:
   ccmp_kernels_fd.hip    -ffp-contract=off -DCCMP_USE_FMA   canonical, bit-reproducible arithmetic (throughput kernel);
                          -DCCMP_LEAN_SQRT: ccmp_detmath.h's wave-uniform fast path of the IEEE square root (same bits, -1.9 %);
-                         -DCCMP_FD_ROT_X0 -DCCMP_FD_BASE_FOLD: the stock structure's short rotation and folded base frame (same bits, -5.9 %);
-                         -DCCMP_FD_GROUP_SOLVE: the minimum-norm solve spread over a group's six lanes, one solve per sample (same bits)
+                         -DCCMP_ATAN_UNIFORM: atan's first interval without its division when the whole wavefront is in it (same bits, -2.0 %)
   ccmp_kernels_wave.hip  -ffp-contract=off -DCCMP_USE_FMA   same arithmetic, one-wave-per-sample kernels
   ccmp_kernels_flat.hip  -ffp-contract=off -DCCMP_USE_FMA   same arithmetic, one 128-thread block per sample (latency kernel)
   ccmp_kernels_geo.hip   -ffp-contract=off -DCCMP_USE_FMA   the extend step on the same Newton routine (ccmp_flat_newton.h), built twice:
@@ -45,17 +44,10 @@ _UNITS = [
     # throughput kernel needed 133 VGPRs and no scratch (measured +3.3 %, in-process A/B; today's kernel: 167, no scratch,
     # three wavefronts per SIMD).  The wave kernels are
     # 2.7 % slower with the option, hence their own unit.
-    # the residual's tail (DESIGN_experiments.md §5.6, in-process A/B each): CCMP_ATAN_UNIFORM atan's first interval without its
-    # division when the whole wavefront is in it (-2.0 %), CCMP_FD_TI_HOIST arm 1's term of the residual once per round (-0.4 %);
-    # CCMP_LEAN_DIV (quotients without scaling and fixup) measured +1.0 % here and stays off
-    # FP64 work fixed by the stock Panda's structure (STOCK instantiations only, same bits): CCMP_FD_ROT_X0 general joints'
-    # rotation in 7 operations for 13 where no angle of the round is within 1e-8 of a multiple of 2 pi (-2.7 %), CCMP_FD_BASE_FOLD the
-    # diag(+-1) base frame folded into the other arm's pose once per arm instead of nine products per stencil point (-2.4 %); together -5.9 %
-    # CCMP_FD_GROUP_SOLVE (ccmp_fd_newton_phase2.inc, every instantiation, same bits): the 2x14 minimum-norm solve once per sample — lane r of
-    # a group rotates and updates columns r, r + 6, r + 12, each serial Gram sum is one chain in one lane — instead of whole in each of the
-    # six lanes: -262 VALU / -191 FP64 instructions per round (static count of project_fd_kernel<0, true>; the solve is straight-line code)
-    ("ccmp_kernels_fd.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-DCCMP_ATAN_UNIFORM", "-DCCMP_FD_TI_HOIST",
-                             "-DCCMP_FD_ROT_X0", "-DCCMP_FD_BASE_FOLD", "-DCCMP_FD_GROUP_SOLVE",
+    # the two detmath flavours of this unit: CCMP_ATAN_UNIFORM (-2.0 %, in-process A/B) and CCMP_LEAN_SQRT; CCMP_LEAN_DIV (quotients
+    # without scaling and fixup) measured +1.0 % here and stays off.  What the kernel's own text does for the stock Panda's structure
+    # and how each piece measured: DESIGN.md §5.1, DESIGN_experiments.md §5.6
+    ("ccmp_kernels_fd.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-DCCMP_ATAN_UNIFORM",
                              "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
      + os.environ.get("CCMP_FD_EXTRA_FLAGS", "").split()),
     ("ccmp_kernels_wave.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA"]),

@@ -19,15 +19,13 @@
     // wave-uniform, for the whole round: the short form of the general joints' rotations, at x and at every stencil point
     // (groups without a sample have no say)
     bool x0 = false;
-#ifdef CCMP_FD_ROT_X0
     if constexpr (STOCK) x0 = K.rot_x0 != 0 && __builtin_amdgcn_ballot_w64(active && x0_off) == 0ull;
-#endif
     __syncthreads();
     bool cont = false;
     double f0, f1;
     {
       double T0[12], T1[12], f[2];
-      if constexpr (STOCK && CCMP_FD_ROWS) {
+      if constexpr (STOCK) {
         // both chains and both tool poses, one matrix row per lane; arm 0's prefix frames stay in LDS for its columns
         if (CCMP_FD_X0_ROWS && x0) chain_rows<true, true>(K, rec, arm_l, row_l, live, 0, d_lane, CCMP_FD_BP);
         else chain_rows<true, false>(K, rec, arm_l, row_l, live, 0, d_lane, CCMP_FD_BP);
@@ -35,12 +33,12 @@
 #pragma unroll
         for (int k = 0; k < 12; k++) { T0[k] = rec[kEE + k]; T1[k] = rec[kEE + 12 + k]; }
       } else {
-        chain_at_x<1, false, STOCK>(K, rec, writer, T1);
+        chain_at_x<1, false>(K, rec, writer, T1);
         if (writer) {
 #pragma unroll
           for (int k = 0; k < 12; k++) rec[kEE + 12 + k] = T1[k];
         }
-        chain_at_x<0, true, STOCK>(K, rec, writer, T0); // arm 0's prefix frames stay in LDS for its columns
+        chain_at_x<0, true>(K, rec, writer, T0); // arm 0's prefix frames stay in LDS for its columns
         if (writer) {
 #pragma unroll
           for (int k = 0; k < 12; k++) rec[kEE + k] = T0[k];

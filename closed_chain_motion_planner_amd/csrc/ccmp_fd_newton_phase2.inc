@@ -12,12 +12,12 @@
     __syncthreads();
     stencil_combine<0>(rec, r, live);
     __syncthreads();
-    if constexpr (STOCK && CCMP_FD_ROWS) { // re-run by rows: arm 1's lanes stage ITS prefix frames
+    if constexpr (STOCK) { // re-run by rows: arm 1's lanes stage ITS prefix frames
       if (CCMP_FD_X0_ROWS && x0) chain_rows<false, true>(K, rec, arm_l, row_l, live, 1, d_lane, CCMP_FD_BP);
       else chain_rows<false, false>(K, rec, arm_l, row_l, live, 1, d_lane, CCMP_FD_BP);
     } else {
       double T1[12];
-      chain_at_x<1, true, STOCK>(K, rec, writer, T1); // re-run arm 1's chain to stage ITS prefix frames
+      chain_at_x<1, true>(K, rec, writer, T1); // re-run arm 1's chain to stage ITS prefix frames
     }
     __syncthreads();
     if constexpr (STOCK) {
@@ -29,7 +29,6 @@
     __syncthreads();
 
     // ---- Newton update: x -= 0.30 * J.jacobiSvd().solve(f) --------------------------------------
-#ifdef CCMP_FD_GROUP_SOLVE
     // solve_minnorm (ccmp_solve.h) spread over the group's six lanes instead of run whole by each of them — its operations on
     // its operands in its order (the pieces are ccmp_solve.h's minnorm_*), hence its bits.  Lane r owns columns r, r + 6, r + 12
     // (< 14), the entries of x it updates: it keeps their (row 0, row 1) pairs in registers through both sweeps, rotates them, and
@@ -87,23 +86,4 @@
         }
       }
     }
-#else
-    {
-      double Jr[28], dx[14];
-#pragma unroll
-      for (int j = 0; j < 7; j++) {
-        Jr[j] = rec[kJ0 + 2 * j];
-        Jr[14 + j] = rec[kJ0 + 2 * j + 1];
-        Jr[7 + j] = rec[kSC + 2 * j];
-        Jr[21 + j] = rec[kSC + 2 * j + 1];
-      }
-      solve_minnorm(Jr, f0, f1, dx);
-      if (cont) {
-#pragma unroll
-        for (int e = 0; e < 14; e++)
-          if (e % kGroup == r) rec[kX + e] = CCMP_FMA(-K.step, dx[e], rec[kX + e]);
-        updates++;
-      }
-    }
-#endif
     __syncthreads();

@@ -7,11 +7,10 @@
 #define CCMP_FLAT_NEWTON_H
 // The FP64 literals of sine/cosine and arctangent come from an LDS table in these units (ccmp_detmath.h: CCMP_K): the
 // compiler re-materialises a literal with two move instructions per use (machine LICM is off here, and hoisting them
-// costs the registers that eight blocks per CU live on), one 16-byte LDS read brings two.  -DCCMP_FLAT_LITERALS: as before.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(CCMP_FLAT_LITERALS)
+// costs the registers that eight blocks per CU live on), one 16-byte LDS read brings two.
+#ifdef __HIP_DEVICE_COMPILE__
 static __shared__ __attribute__((aligned(16))) double ccmp_ktab[36]; // internal linkage: three translation units include this header
 #define CCMP_K(i, v) (ccmp_ktab[i])
-#define CCMP_KTAB_IN_LDS 1
 #endif
 #include "ccmp_fd_common.h"
 
@@ -20,11 +19,6 @@ using namespace ccmp;
 namespace {
 
 constexpr int kConstsDoubles = (int)((sizeof(ccmp_consts) + 7) / 8);
-#ifdef CCMP_GEO_TRACE
-// per-edge / per-sample timeline of one launch (tools/exp_r3.py geo_trace, flat_trace; never defined in the product build):
-// start, end (100 MHz wall clock), block << 32 | ticket
-__device__ unsigned long long g_geo_trace[3 * 65536];
-#endif
 #ifndef CCMP_FLAT_MIN_WAVES
 #define CCMP_FLAT_MIN_WAVES 4 // waves per SIMD the register budget must allow (A/B: -DCCMP_FLAT_MIN_WAVES=2)
 #endif
@@ -54,21 +48,6 @@ __device__ unsigned long long g_geo_trace[3 * 65536];
 // is: tools/ubench/), so the routine is written to keep moves, selects, exec-mask regions and branches out of the
 // round: lanes find "their" joint, their (sin, cos) slot and every joint's (sin, cos) through per-lane LDS addresses
 // computed once; literals of the elementary functions come from an LDS table (CCMP_K).
-#ifdef CCMP_FLAT_TIMING
-// phase timing of thread 0 of block 0 (tools/exp_r3.py phases; never defined in the product build)
-__device__ unsigned long long g_flat_timing[8];
-__device__ __forceinline__ void flat_tick(int k, unsigned long long &prev)
-{
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const unsigned long long now = __builtin_readcyclecounter();
-    g_flat_timing[k] += now - prev;
-    prev = now;
-  }
-}
-#define FLAT_TICK(k) flat_tick(k, tprev)
-#else
-#define FLAT_TICK(k) do { } while (0)
-#endif
 
 // record of one sample in LDS (doubles): x 14 | joint rotations at x 14 x 12 | tool poses at x 24 | f(x) 2 | J | flag |
 // one joint-rotation slot per evaluation lane (its own perturbed joint).
@@ -117,10 +96,7 @@ __device__ __forceinline__ double column_sum(const double *jx)
   for (int k = 0; k < 14; k++) acc = CCMP_FMA(uv[k].x, uv[k].y, acc);
   return acc;
 }
-// the value lane N of the row holds, in every lane of the row (the three sums are formed in lanes 0, 1, 2 of EVERY row, so
-// all 64 lanes end up with the same numbers).  By readlane into a scalar pair, or — CCMP_SUM_BCAST_DPP, the build with
-// machine LICM, whose scalar registers are spilled already — by a DPP row broadcast that stays in vector registers.
-// all three in every lane (CCMP_SUMS_IN_LANE: the build with machine LICM measured 5 % slower with the split sums)
+// all three sums in every lane (CCMP_SUMS_IN_LANE: the build with machine LICM measured 5 % slower with the split sums)
 __device__ __forceinline__ void column_sums(const double *jbase, double &a, double &d, double &b)
 {
   a = 0.0; d = 0.0; b = 0.0;
@@ -136,17 +112,12 @@ __device__ __forceinline__ void column_sums(const double *jbase, double &a, doub
     b = CCMP_FMA(p.x, p.y, b);
   }
 }
+// the value lane N holds, in every lane, by readlane into a scalar pair (the three split sums are formed in lanes 0, 1, 2 of
+// EVERY 16-lane row, so any row's copy serves)
 template <int N>
 __device__ __forceinline__ double lane_value(double v)
 {
-#ifdef CCMP_SUM_BCAST_DPP
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, 0x150 + N, 0xf, 0xf, false); // row_newbcast:N
-  hi = __builtin_amdgcn_update_dpp(hi, hi, 0x150 + N, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-#else
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), N), __builtin_amdgcn_readlane(__double2loint(v), N));
-#endif
 }
 constexpr int kXLane = 54, kScLane0 = 55; // chain at x; first sine/cosine lane
 
@@ -174,7 +145,7 @@ constexpr int kStepDoubles = 14, kStepAxis = 4, kStepTab = 2 * 7 * kStepDoubles;
 
 __device__ __forceinline__ void stage_step_table(const ccmp_consts &K, double *tab, int tid)
 {
-#ifdef CCMP_KTAB_IN_LDS
+#ifdef __HIP_DEVICE_COMPILE__ // the host pass has no table
   if (tid == 64) ccmp_fill_ktab(ccmp_ktab); // one thread of wave 1; the caller's barrier publishes it
 #endif
   for (int k = tid; k < kStepTab; k += 128) {
@@ -268,14 +239,11 @@ __device__ __forceinline__ void flat_residual_stencil(const ccmp_consts &K, doub
 
 template <int W, bool STOCK>
 __device__ __forceinline__ void flat_chain_and_residual(const ccmp_consts &K, const ccmp_consts &KC, const double *steptab,
-                                                        double *rec, int lane, int j, int own, bool head, double y,
-                                                        unsigned long long &tprev)
+                                                        double *rec, int lane, int j, int own, bool head, double y)
 {
-  (void)tprev; // only the -DCCMP_FLAT_TIMING build ticks it
   double Tw[12];
   flat_chain_pose<W, STOCK>(KC, steptab, rec, lane, j, own, Tw);
   __syncthreads();
-  FLAT_TICK(1);
   flat_residual_stencil<W, STOCK>(K, rec, lane, j, head, y, Tw);
 }
 
@@ -349,16 +317,18 @@ __device__ __forceinline__ bool flat_newton(const ccmp_consts &K, const ccmp_con
   const FlatLane L = flat_lane(w, lane);
   const int j = L.j, own = L.own;
   const bool head = L.head;
-  unsigned long long tprev = __builtin_readcyclecounter();
+  // A dead read of the cycle counter (one s_memtime + s_waitcnt lgkmcnt(0) per entry), left from a retired phase-timing hook.
+  // Deleting it is not neutral: with no scalar load in flight the compiler turns full LDS waits of the first round into counted
+  // ones in the extend step's and the resident kernel's units — a code change that wants timings of its own
+  // (DESIGN_experiments.md §5.6).
+  (void)__builtin_readcyclecounter();
   for (;;) {
     const double y = flat_angles(steptab, rec, L);
     // an arm's sines and cosines are written and read by the arm's own wave: no block barrier
     wave_lds_fence();
-    FLAT_TICK(0);
-    if (w == 0) flat_chain_and_residual<0, STOCK>(K, KC, steptab, rec, lane, j, own, head, y, tprev);
-    else flat_chain_and_residual<1, STOCK>(K, KC, steptab, rec, lane, j, own, head, y, tprev);
+    if (w == 0) flat_chain_and_residual<0, STOCK>(K, KC, steptab, rec, lane, j, own, head, y);
+    else flat_chain_and_residual<1, STOCK>(K, KC, steptab, rec, lane, j, own, head, y);
     __syncthreads();
-    FLAT_TICK(2);
     const double f0 = rec[fF], f1 = rec[fF + 1];
     // ---- loop condition of ConstraintFunction.h:68 (block-uniform) ------------------------------------------
     // (norm1 = f0 > tol1) || (norm2 = f1) > tol2: norm2 is assigned only when the first test fails; iter++ only when the
@@ -374,9 +344,6 @@ __device__ __forceinline__ bool flat_newton(const ccmp_consts &K, const ccmp_con
     // owning column c.  A second wave repeating it would only take issue slots from other blocks; wave 1 waits at the
     // barrier below.
     if (w == 0) {
-#ifdef CCMP_FLAT_SOLVE_PRIO
-      __builtin_amdgcn_s_setprio(CCMP_FLAT_SOLVE_PRIO); // the serial solve is every block's critical path: first in line on its SIMD
-#endif
       // lanes 0, 1 and 2+ of every 16-lane row form sum J0c^2, sum J1c^2 and sum J0c J1c; lane_value hands them round
 #ifndef CCMP_SUMS_IN_LANE
       const double *jx = rec + fJ + 2 * (rl < 2 ? rl : 2);
@@ -431,29 +398,9 @@ __device__ __forceinline__ bool flat_newton(const ccmp_consts &K, const ccmp_con
 #endif
       const double dxm = CCMP_FMA(k1, mine.y, k0 * mine.x);
       if (lane < 14) rec[fX + lane] = CCMP_FMA(-K.step, dxm, rec[fX + lane]);
-#ifdef CCMP_FLAT_SOLVE_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
     }
-#ifdef CCMP_FLAT_PROBE_DUMMY
-    // probe (never in the product): wave 1 burns CCMP_FLAT_PROBE_DUMMY dependent-free FP64 instructions while it would wait
-    // for the solve — issue load without any effect on the block's critical path.  If the loaded throughput falls, the
-    // kernel is bound by issue slots; if it does not, by the latency of the rounds.
-    else {
-      // eight independent accumulators, multiplier and addend in registers: nothing but v_fma_f64, 4 cycles each
-      double a0 = f0, a1 = f1, a2 = f0 + 1.0, a3 = f1 + 1.0, a4 = f0 + 2.0, a5 = f1 + 2.0, a6 = f0 + 3.0, a7 = f1 + 3.0;
-      const double m = 1.0 + f0 * 1e-9, c0 = f1 * 1e-9;
-#pragma unroll
-      for (int k = 0; k < CCMP_FLAT_PROBE_DUMMY / 8; k++) {
-        a0 = CCMP_FMA(a0, m, c0); a1 = CCMP_FMA(a1, m, c0); a2 = CCMP_FMA(a2, m, c0); a3 = CCMP_FMA(a3, m, c0);
-        a4 = CCMP_FMA(a4, m, c0); a5 = CCMP_FMA(a5, m, c0); a6 = CCMP_FMA(a6, m, c0); a7 = CCMP_FMA(a7, m, c0);
-      }
-      if (((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)) == 12345.678) rec[fV] = a0; // keeps the chain alive; never true
-    }
-#endif
     updates++;
     __syncthreads();
-    FLAT_TICK(4);
   }
 }
 

@@ -152,8 +152,5 @@
 #ifdef CCMP_GEO_SCENE
       if (blocked_out) blocked_out[t] = blocked ? (uint8_t)1 : (uint8_t)0;
 #endif
-#ifdef CCMP_GEO_TRACE
-      if (t < 65536) g_geo_trace[3 * t + 1] = wall_clock64();
-#endif
     }
     __syncthreads();

@@ -49,58 +49,29 @@ constexpr int kRec = 165;             // 164 used; odd stride keeps the 10 group
 #ifndef CCMP_FD_WAVES_PER_SIMD
 #define CCMP_FD_WAVES_PER_SIMD 3
 #endif
-#ifndef CCMP_FD_STOCK_COLUMNS
-#define CCMP_FD_STOCK_COLUMNS 1 // STOCK instantiation: Jacobian columns skip the products with the stock Panda's exact zeros
-#endif
-#ifndef CCMP_FD_ROWS
-#define CCMP_FD_ROWS 1 // STOCK instantiation: the chains at x by matrix rows, three lanes per arm (0 = every lane runs both chains whole)
-#endif
 
-// One arm's chain at x (sines/cosines from LDS), joint indices at compile time (the STOCK instantiation skips the
-// products with the stock Panda's exact zeros, ccmp_kin.h).  With STORE the writer lane keeps the frame in front of
-// every joint (R before the joint's rotation, o including the joint's offset) in LDS.
-template <int ARM, bool STORE, bool STOCK, int I>
-__device__ __forceinline__ void chain_at_x_from(const ccmp_consts &K, double *rec, bool writer, double *R, double *o)
-{
-  if constexpr (I < 7) {
-    double Rn[9];
-    mulvec_acc_nz<STOCK ? kStockOff[I] : 7>(R, K.offset[ARM][I], o);
-    if (STORE && writer) {
-#pragma unroll
-      for (int k = 0; k < 9; k++) rec[kPre + I * 12 + k] = R[k];
-#pragma unroll
-      for (int k = 0; k < 3; k++) rec[kPre + I * 12 + 9 + k] = o[k];
-    }
-    chain_rot<I, STOCK>(K.axis[ARM][I], K.aprod[ARM][I], rec[kSC + 2 * (ARM * 7 + I)], rec[kSC + 2 * (ARM * 7 + I) + 1], R, Rn);
-#pragma unroll
-    for (int k = 0; k < 9; k++) R[k] = Rn[k];
-    chain_at_x_from<ARM, STORE, STOCK, I + 1>(K, rec, writer, R, o);
-  }
-}
-template <int ARM, bool STORE, bool STOCK>
+// One arm's chain at x (sines/cosines from LDS) in the general instantiations (calibrated arms, tilted bases), whole in every
+// lane; the STOCK instantiations run chain_rows below instead.  With STORE the writer lane keeps the frame in front of every
+// joint (R before the joint's rotation, o including the joint's offset) in LDS.  A loop: unrolled, the general formulas spill.
+template <int ARM, bool STORE>
 __device__ __forceinline__ void chain_at_x(const ccmp_consts &K, double *rec, bool writer, double *T)
 {
   double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
-  if constexpr (STOCK) {
-    // unrolled: 5.6 k instructions in all, 135 VGPRs (the general formulas unrolled the same way spill)
-    chain_at_x_from<ARM, STORE, true, 0>(K, rec, writer, R, o);
-  } else {
-    for (int i = 0; i < 7; i++) {
-      double Rj[9], Rn[9];
-      mulvec_acc(R, K.offset[ARM][i], o);
-      if (STORE && writer) {
+  for (int i = 0; i < 7; i++) {
+    double Rj[9], Rn[9];
+    mulvec_acc(R, K.offset[ARM][i], o);
+    if (STORE && writer) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) rec[kPre + i * 12 + k] = R[k];
+      for (int k = 0; k < 9; k++) rec[kPre + i * 12 + k] = R[k];
 #pragma unroll
-        for (int k = 0; k < 3; k++) rec[kPre + i * 12 + 9 + k] = o[k];
-      }
-      rot_sc(K.axis[ARM][i], K.aprod[ARM][i], rec[kSC + 2 * (ARM * 7 + i)], rec[kSC + 2 * (ARM * 7 + i) + 1], Rj);
-      mul33(R, Rj, Rn);
-#pragma unroll
-      for (int k = 0; k < 9; k++) R[k] = Rn[k];
+      for (int k = 0; k < 3; k++) rec[kPre + i * 12 + 9 + k] = o[k];
     }
+    rot_sc(K.axis[ARM][i], K.aprod[ARM][i], rec[kSC + 2 * (ARM * 7 + i)], rec[kSC + 2 * (ARM * 7 + i) + 1], Rj);
+    mul33(R, Rj, Rn);
+#pragma unroll
+    for (int k = 0; k < 9; k++) R[k] = Rn[k];
   }
-  tool_pose_t<STOCK>(K, ARM, R, o, &T[0], &T[9]);
+  tool_pose_t<false>(K, ARM, R, o, &T[0], &T[9]);
 }
 
 // A general joint (1, 3, 5, 6) of the stock Panda in the STOCK instantiations: Rn = R * Rot(axis_i, angle).  X0: the short form
@@ -222,7 +193,6 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
   double To[12]; // the other arm's (unperturbed) tool pose: 24 VGPRs that save 12 LDS reads per column (-6.5 %, A/B)
 #pragma unroll
   for (int k = 0; k < 12; k++) To[k] = rec[kEE + (1 - ARM) * 12 + k];
-#ifdef CCMP_FD_TI_HOIST
   // arm 0's columns: chain_residual's ti = R2^T p2 is arm 1's alone — once here, in place of p2 (no register added)
   if (ARM == 0) {
     double ti[3];
@@ -231,17 +201,9 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
     for (int k = 0; k < 3; k++) To[9 + k] = ti[k];
   }
   constexpr bool kOtherP = ARM == 1; // arm 0's columns hold ti in place of the other arm's translation
-#else
-  constexpr bool kOtherP = true;
-#endif
-#ifdef CCMP_FD_BASE_FOLD
   // STOCK: twin arms on diag(+-1) base frames (launchers).  This arm's +-1 factors go into the other arm's pose once, here,
   // instead of into this arm's nine rotation entries at every stencil point (ccmp_kin.h: tool_pose_fold)
-  constexpr bool kFold = STOCK;
-  if constexpr (kFold) fold_other_pose<kOtherP>(K, ARM, To);
-#else
-  constexpr bool kFold = false;
-#endif
+  if constexpr (STOCK) fold_other_pose<kOtherP>(K, ARM, To);
   for (int j = 0; j < 7; j++) {
     const double xj = rec[kX + ARM * 7 + j];
     const double axj = ccmp_abs(xj);
@@ -257,7 +219,7 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
     for (int k = 0; k < 3; k++) o[k] = rec[kPre + j * 12 + 9 + k];
     ccmp_sincos(y, &s, &c);
     const double *sc = rec + kSC + 2 * ARM * 7;
-    if constexpr (STOCK && CCMP_FD_STOCK_COLUMNS) {
+    if constexpr (STOCK) {
       // twin arms: arm 0's constants serve both.  Joint indices are wave-uniform scalars; the branches are scalar.
       // The frame ends every step in R (R -> Rn -> R, or in place): no register copies between steps.
       double Rn[9];
@@ -319,31 +281,10 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
         }
       }
     }
-#if defined(CCMP_FD_PROBE_MOV) || defined(CCMP_FD_PROBE_FMA)
-    // probe (never in the product; tools/ab.py): what one more instruction per stencil evaluation costs THIS kernel at its
-    // occupancy — N independent 32-bit moves or N independent FP64 FMAs beside the evaluation's own stream
-    {
-      int pv = j;
-      double pa = xj, pb = xj;
-#ifdef CCMP_FD_PROBE_MOV
-#pragma unroll
-      for (int k = 0; k < CCMP_FD_PROBE_MOV; k++) asm volatile("v_mov_b32 %0, 0x12345678" : "=v"(pv));
-#endif
-#ifdef CCMP_FD_PROBE_FMA
-#pragma unroll
-      for (int k = 0; k < CCMP_FD_PROBE_FMA / 2; k++) asm volatile("v_fma_f64 %0, %0, %2, %2\n v_fma_f64 %1, %1, %2, %2" : "+v"(pa), "+v"(pb) : "v"(h));
-#endif
-      if (pv == 0x7fffffff || pa + pb == 12345.678) rec[kX] = pa; // never true: keeps the probe alive
-    }
-#endif
     double Tw[12], t[2];
-    if constexpr (kFold) tool_pose_fold<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
+    if constexpr (STOCK) tool_pose_fold<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
     else tool_pose_t<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
-#ifdef CCMP_FD_TI_HOIST
     if (ARM == 0) chain_residual_ti(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
-#else
-    if (ARM == 0) chain_residual(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
-#endif
     else chain_residual(K, &To[0], &To[9], &Tw[0], &Tw[9], t, nullptr, nullptr);
     // park this evaluation in the prefix slot the group has just consumed (12 doubles = 6 lanes x (f0, f1));
     // the stencil is combined after the arm's 7 columns (stencil_combine) instead of through two dependent
@@ -633,13 +574,8 @@ __global__ __launch_bounds__(64, CCMP_GEO_GROUP_WAVES_PER_SIMD) void geodesic_gr
   // Newton loop: under the bound of three wavefronts per SIMD the allocator parked them in scratch.  They are recomputed where they
   // are used — once per edge or projection — from a lane index the optimiser cannot see through, which keeps it from hoisting them
   // back out of the loop.
-#ifndef CCMP_GEO_GROUP_OPAQUE
-#define CCMP_GEO_GROUP_OPAQUE 1
-#endif
   auto lane_opaque = [](int v) {
-#if CCMP_GEO_GROUP_OPAQUE
     asm volatile("" : "+v"(v));
-#endif
     return v;
   };
 

@@ -78,14 +78,7 @@ __global__ __launch_bounds__(128, CCMP_FLAT_MIN_WAVES) void project_fd_flat_kern
       }
     }
     __syncthreads();
-#ifdef CCMP_GEO_TRACE
-    const int updates_in = updates;
-    if (tid == 0 && t < 65536) { g_geo_trace[3 * t] = wall_clock64(); g_geo_trace[3 * t + 2] = ((unsigned long long)blockIdx.x << 32) | (unsigned)updates_in; }
-#endif
     const bool conv = flat_newton<STOCK>(K, KL, steptab, rec, tid, iter, updates, norm1, norm2, K.max_iter);
-#ifdef CCMP_GEO_TRACE
-    if (tid == 0 && t < 65536) { g_geo_trace[3 * t + 1] = wall_clock64(); g_geo_trace[3 * t + 2] |= (unsigned long long)(unsigned)(updates - updates_in) << 16; }
-#endif
     const bool jv = flat_joint_valid(KL, rec, tid);
     if (tid < 14) {
       const double v = rec[fX + tid];
@@ -136,26 +129,3 @@ hipError_t project_flat(const ProjectCall &c, const FlatLaunch &l, hipStream_t s
 }
 
 }  // namespace ccmp_launch
-
-extern "C" {
-
-#ifdef CCMP_GEO_TRACE
-hipError_t ccmp_debug_flat_trace(unsigned long long *out, size_t n_edges)
-{
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_geo_trace), 3 * n_edges * sizeof(unsigned long long));
-}
-#endif
-
-#ifdef CCMP_FLAT_TIMING
-hipError_t ccmp_debug_flat_timing(unsigned long long *out8, int reset)
-{
-  hipError_t e = hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_flat_timing), 8 * sizeof(unsigned long long));
-  if (e == hipSuccess && reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_flat_timing), z, sizeof z);
-  }
-  return e;
-}
-#endif
-
-} // extern "C"

@@ -80,9 +80,6 @@ __global__ __launch_bounds__(128, (STOCK || CCMP_FLAT_MIN_WAVES < 4) ? CCMP_FLAT
                                    (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)tk);
     const double *ent = pool ? pool + tks * (unsigned long long)kGeoPoolEntry : nullptr;
     const unsigned long long t = ent ? (unsigned long long)__double_as_longlong(ent[31]) : (order ? (unsigned long long)order[tk] : tk);
-#ifdef CCMP_GEO_TRACE
-    if (tid == 0 && t < 65536) { g_geo_trace[3 * t] = wall_clock64(); g_geo_trace[3 * t + 2] = ((unsigned long long)blockIdx.x << 32) | tk; }
-#endif
 #include "ccmp_geo_edge_body.inc"
     if (!queue) tk += gridDim.x;
   }
@@ -155,17 +152,3 @@ hipError_t geodesic_order(const double *from, const double *to, size_t E, double
 #endif
 
 }  // namespace ccmp_launch
-
-extern "C" {
-
-#ifdef CCMP_GEO_TRACE
-#ifdef CCMP_GEO_LATENCY
-#define ccmp_debug_geo_trace ccmp_debug_geo_trace_lat
-#endif
-hipError_t ccmp_debug_geo_trace(unsigned long long *out, size_t n_edges)
-{
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_geo_trace), 3 * n_edges * sizeof(unsigned long long));
-}
-#endif
-
-} // extern "C"

@@ -266,14 +266,10 @@ __global__ __launch_bounds__(256) void scout_kernel(const consts_f K, const ccmp
   (void)queue;
   for (;;) {
     if (!active && !drained) {
-#ifdef CCMP_SCOUT_ATOMIC_QUEUE
-      const unsigned long long t = atomicAdd(queue, 1ull);
-#else
       // static striding instead of a shared queue head: 262144 single-lane dequeues on one word cost more than
       // the whole scout (one word saturates at ~88 dequeues/us); the imbalance of a few samples per lane is small
       const unsigned long long t = next;
       next += (unsigned long long)gridDim.x * blockDim.x;
-#endif
       if (t < B) {
         idx = t; active = true; iter = 0;
 #pragma unroll
@@ -954,10 +950,6 @@ hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist,
   make_consts_f(K, F, &stock);
   const bool fused = B <= (size_t)kSortFusedMax; // the fused sort writes every bin itself: nothing to clear
   hipError_t e = hipSuccess;
-#ifdef CCMP_SCOUT_ATOMIC_QUEUE
-  e = clear_words(queue, 2, st); // kernels, so that a stream capture replays them
-  if (e != hipSuccess) return e;
-#endif
   if (!fused) {
     e = clear_words(hist, kBins, st);
     if (e != hipSuccess) return e;

@@ -224,7 +224,6 @@ CCMP_HD void tool_pose_t(const ccmp_consts &K, int arm, const double *R, const d
   double pf[3] = {o[0], o[1], o[2]}, Rf[9];
   mulvec_acc_nz<STOCK ? kStockEe : 7>(R, K.ee[arm], pf);
   mul33(R, K.R_tool[arm], Rf);
-#ifndef CCMP_NO_BASE_DIAG
   if ((K.base_diag >> arm) & 1) {
     /* t_wb.linear() = diag(+-1): the general product below adds exact zeros to d_r * Rf[r][c] and to
      * fma(d_r, pf[r], base_p[r]) — the same bits for a third of the operations */
@@ -237,7 +236,6 @@ CCMP_HD void tool_pose_t(const ccmp_consts &K, int arm, const double *R, const d
     }
     return;
   }
-#endif
   mul33(K.base_R[arm], Rf, Rw);
   pw[0] = K.base_p[arm][0]; pw[1] = K.base_p[arm][1]; pw[2] = K.base_p[arm][2];
   mulvec_acc(K.base_R[arm], pf, pw);
@@ -295,13 +293,11 @@ CCMP_HD void fk_arm(const ccmp_consts &K, int arm, const double *q, double *Rw, 
   tool_pose(K, arm, R, o, Rw, pw);
 }
 
-#ifndef CCMP_QUAT_BRANCHY
-/* Eigen Quaterniond(Matrix3d) — trace / major-diagonal branches; out (x,y,z,w) — in branch-free form:
- * the four branches of Eigen's conversion differ only in WHICH sum feeds the one square root and which
- * differences/sums are scaled by 0.5/sqrt, so the operands are selected and sqrt/divide run once.
- * Every output is produced by the same operation on the same operands as in the branchy form below
- * (bit-identical; in-process A/B on MI355X, tools/ab.py: 1.4 % faster than the branchy form). */
-
+/* Eigen Quaterniond(Matrix3d); out (x,y,z,w) — in branch-free form.  Eigen branches on the trace (positive: w from
+ * sqrt(trace + 1)) and otherwise on the largest diagonal entry (x, y or z from sqrt of that entry minus the other two, plus 1);
+ * the four branches differ only in WHICH sum feeds the one square root and which differences/sums are scaled by 0.5/sqrt,
+ * so the operands are selected and sqrt/divide run once.  Every output is produced by the same operation on the same
+ * operands as in Eigen's branch (bit-identical; in-process A/B on MI355X, tools/ab.py: 1.4 % faster than a branchy copy). */
 CCMP_HD void quat_of(const double *m, double *q)
 {
   const double tr = (m[0] + m[4]) + m[8];
@@ -324,48 +320,6 @@ CCMP_HD void quat_of(const double *m, double *q)
   q[2] = kase == 3 ? d3 : (kase == 0 ? s2 : (kase == 1 ? s3 : h));
   q[3] = kase == 3 ? h : (kase == 0 ? d1 : (kase == 1 ? d2 : d3));
 }
-#else
-/* Eigen Quaterniond(Matrix3d) — trace / major-diagonal branches; out (x,y,z,w). */
-CCMP_HD void quat_of(const double *m, double *q)
-{
-  double t = (m[0] + m[4]) + m[8];
-  if (t > 0.0) {
-    t = ccmp_sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (m[7] - m[5]) * t;
-    q[1] = (m[2] - m[6]) * t;
-    q[2] = (m[3] - m[1]) * t;
-  } else {
-    int i = (m[4] > m[0]) ? 1 : 0;
-    double mii = i ? m[4] : m[0];
-    if (m[8] > mii) i = 2;
-    if (i == 0) { /* j=1, k=2 */
-      t = ccmp_sqrt(((m[0] - m[4]) - m[8]) + 1.0);
-      q[0] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[7] - m[5]) * t;
-      q[1] = (m[3] + m[1]) * t;
-      q[2] = (m[6] + m[2]) * t;
-    } else if (i == 1) { /* j=2, k=0 */
-      t = ccmp_sqrt(((m[4] - m[8]) - m[0]) + 1.0);
-      q[1] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[2] - m[6]) * t;
-      q[2] = (m[7] + m[5]) * t;
-      q[0] = (m[1] + m[3]) * t;
-    } else { /* i=2, j=0, k=1 */
-      t = ccmp_sqrt(((m[8] - m[0]) - m[4]) + 1.0);
-      q[2] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[3] - m[1]) * t;
-      q[0] = (m[2] + m[6]) * t;
-      q[1] = (m[5] + m[7]) * t;
-    }
-  }
-}
-
-#endif
 
 /* current_chain = t_w72.inverse() * t_w71, then (|dp|, angularDistance) against init_chain_
  * (ConstraintFunction.h:92-101).  dq (nullable) receives q_c * conj(q_0) as (x,y,z,w) and pc

@@ -1,5 +1,5 @@
-// group_solve_check.cpp — host check of the throughput layout's minimum-norm solve (ccmp_fd_newton_phase2.inc, build flag
-// CCMP_FD_GROUP_SOLVE): the pieces of ccmp_solve.h (minnorm_sum_step, minnorm_sweep_coeffs, minnorm_rotate, minnorm_final_coeffs,
+// group_solve_check.cpp — host check of the throughput layout's minimum-norm solve (ccmp_fd_newton_phase2.inc):
+// the pieces of ccmp_solve.h (minnorm_sum_step, minnorm_sweep_coeffs, minnorm_rotate, minnorm_final_coeffs,
 // minnorm_dx, minnorm_group_slot) composed as the kernels compose them — six virtual lanes on one group record, lane r owning
 // columns r, r + 6, r + 12, lanes 0..2 (and again 3..5) forming one serial sum each from the record, the sums published in the
 // record, every lane running the scalar part, the rotated columns written back in place — against the one-lane solve_minnorm, in

@@ -1,4 +1,4 @@
-"""The two cuts of the throughput kernel's STOCK instantiations (CCMP_FD_ROT_X0, CCMP_FD_BASE_FOLD; closed_chain_motion_planner_amd/build.py)
+"""The two cuts of the throughput kernel's STOCK instantiations (the short rotation and the folded base frame)
 against the det oracle, bit for bit — joints, flags, iteration counts — at throughput-kernel size (> 10 240 samples):
 
   * the short rotation of the general joints is taken only by wavefronts none of whose samples holds a joint within 1e-8 of

@@ -1,5 +1,4 @@
-"""The minimum-norm solve spread over a group's six lanes (CCMP_FD_GROUP_SOLVE; closed_chain_motion_planner_amd/build.py,
-ccmp_fd_newton_phase2.inc) against the det oracle, bit for bit — joints, flags, iteration counts — at throughput-kernel size
+"""The minimum-norm solve spread over a group's six lanes (closed_chain_motion_planner_amd/csrc/ccmp_fd_newton_phase2.inc) against the det oracle, bit for bit — joints, flags, iteration counts — at throughput-kernel size
 (> 10 240 samples, so that every group slot of a wavefront refills while its neighbours are in the middle of a projection):
 
   * the throughput kernel alone (schedule 0) and the default policy; Wine_Bottle, stefan and dumbbell; the reference's tolerances

@@ -1,5 +1,5 @@
-"""The wave-uniform fast paths of the residual's tail (CCMP_ATAN_UNIFORM and CCMP_FD_TI_HOIST in the throughput kernel, the opt-in
-CCMP_LEAN_DIV; closed_chain_motion_planner_amd/build.py): a wavefront takes the lean sequence only when every lane qualifies, the general code
+"""The wave-uniform fast paths of the residual's tail (in the throughput kernel CCMP_ATAN_UNIFORM and arm 1's term of the residual
+once per round, the opt-in CCMP_LEAN_DIV; closed_chain_motion_planner_amd/build.py): a wavefront takes the lean sequence only when every lane qualifies, the general code
 otherwise, and both must give the det oracle's bits.  Batches at throughput-kernel size (> 10 240 samples) in which waves are
 mixed — samples far from the manifold (atan off its first interval, several quaternion cases) interleaved with near-manifold
 ones — and batches of near-manifold samples only; plus the device's lean quotient against the compiler's over the whole

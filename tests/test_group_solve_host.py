@@ -1,5 +1,4 @@
-"""The throughput layout's minimum-norm solve, spread over a group's six lanes (ccmp_fd_newton_phase2.inc, build flag
-CCMP_FD_GROUP_SOLVE), checked on the host.  tests/cpp/group_solve_check.cpp composes the pieces of ccmp_solve.h as the kernels do —
+"""The throughput layout's minimum-norm solve, spread over a group's six lanes (ccmp_fd_newton_phase2.inc), checked on the host.  tests/cpp/group_solve_check.cpp composes the pieces of ccmp_solve.h as the kernels do —
 six virtual lanes on one group record: lane r owns columns r, r + 6, r + 12, one serial sum per lane read from the record, the
 sums published in the record, the scalar part in every lane, rotated columns written back in place — and runs the one-lane
 solve_minnorm beside it, compiled with the det oracle's flags.  All 14 entries of both must be the bits of the oracle's

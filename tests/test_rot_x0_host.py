@@ -1,5 +1,5 @@
 """The two cuts of the throughput kernel's STOCK instantiations, checked on the host against the functions they replace
-(closed_chain_motion_planner_amd/csrc/ccmp_kin.h; build flags CCMP_FD_ROT_X0 and CCMP_FD_BASE_FOLD).  tests/cpp/rot_x0_check.cpp is compiled
+(closed_chain_motion_planner_amd/csrc/ccmp_kin.h: rot_sc_x0, tool_pose_fold).  tests/cpp/rot_x0_check.cpp is compiled
 with the det oracle's flags (-ffp-contract=off -DCCMP_USE_FMA, hardware FMA where the host has it) against ccmp_kin.h and takes
 the stock constants from libccmp's own set-up code:
 
