@@ -72,6 +72,7 @@ EXPORTS = [
     "ccmp_comm_create", "ccmp_comm_destroy", "ccmp_comm_last_timing", "ccmp_project_sharded", "ccmp_sample_project_sharded",
     "ccmp_scene_create", "ccmp_scene_destroy", "ccmp_scene_num_pairs", "ccmp_clearance_batch", "ccmp_clearance_host",
     "ccmp_geodesic_scene_batch", "ccmp_geodesic_scene_host",
+    "ccmp_knn_batch", "ccmp_knn_host", "ccmp_connect_batch", "ccmp_connect_host",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -168,6 +169,12 @@ def lib():
                                       C.c_int),
         "ccmp_geodesic_scene_host": ([vp, pp, vp, C.c_double, dp, dp, C.c_size_t, C.c_int, dp, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int32), u8p,
                                       dp, dp, dp, C.c_int, C.c_int], C.c_int),
+        "ccmp_knn_batch": ([vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, vp, vp, vp], C.c_int),
+        "ccmp_knn_host": ([vp, dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int32), dp], C.c_int),
+        "ccmp_connect_batch": ([vp, pp, vp, C.c_double, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_connect_host": ([vp, pp, vp, C.c_double, dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                               C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int32), u8p, dp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -196,6 +203,9 @@ def lib():
 
 
 CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GEODESIC_BUDGET, CALL_GEODESIC_ANALYTIC = range(6)  # ccmp.h: CCMP_CALL_*
+CALL_GEODESIC_SCENE, CALL_KNN, CALL_CONNECT = 6, 7, 8
+KNN_ALL, KNN_NOT_SELF, KNN_EARLIER = 0, 1, 2  # ccmp.h: CCMP_KNN_*
+KNN_MAX_K = 16
 
 
 def option_table():

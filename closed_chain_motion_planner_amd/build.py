@@ -22,6 +22,7 @@ Translation units with deliberately different flags:
   ccmp_kernels_scout.hip -ffast-math                        FP32 iteration-count predictor + ordering (never touches results)
   ccmp_kernels_scene.hip -ffp-contract=off -DCCMP_USE_FMA   proxy-geometry clearance (pre-filter ahead of the host's MoveIt test)
   ccmp_scene.cpp                                            proxy scenes: validation, pair list, launches
+  ccmp_kernels_knn.hip   -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the connection step: FP64 brute-force k nearest neighbours, the gather of ccmp_connect_batch
 """
 import os
 import shutil
@@ -75,6 +76,8 @@ _UNITS = [
     ("ccmp_host_io.cpp", ["-O2", "-x", "hip"]),
     ("ccmp_comm.cpp", ["-O2", "-x", "hip"]),
     ("ccmp_kernels_scene.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # the connection step (k nearest neighbours, gather): the scene unit's flags; its lists live in registers and LDS, never in scratch
+    ("ccmp_kernels_knn.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     ("ccmp_scene.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
 _HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
@@ -118,6 +121,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"project_pair_kernel|project_row16_kernel", 0),  # analytic mode, every instantiation (stock twin arms, stock, calibrated)
     (r"resident_row16_kernel", 0),  # the resident service kernel of analytic mode, both instantiations
     (r"geodesic_row16_(scene_)?kernel", 0),  # analytic mode's extend step and its scene variant, both instantiations (diagonal and general base frames)
+    (r"knn_|connect_(gather|fix)_kernel", 0),  # the connection step: per-thread lists of up to 16 (distance, index) pairs in registers, every instantiation
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

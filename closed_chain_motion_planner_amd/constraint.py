@@ -395,6 +395,57 @@ class KinematicChainConstraint:
             out += (carry,)
         return out
 
+    def nearest_k_batch(self, nodes, queries, k, mode=0, self_base=0, want_dist=True, stream=None):
+        """The connection step's choice of pairs (ccmp_knn_batch): the k nearest of `nodes` (N,14) for every row of `queries`
+        (Q,14) under the joint distance of `KinematicChainSpace::distance` (the oracle's orc_distance), ranked by (distance,
+        node index).  mode: _lib.KNN_ALL, KNN_NOT_SELF (query q is node self_base + q, left out) or KNN_EARLIER (only nodes
+        below self_base + q).  Returns (nbr_idx (Q,k) int32, nbr_dist (Q,k) float64 or None); a slot without an eligible node
+        holds idx = -1, dist = +inf."""
+        torch = _torch()
+        self._check_q(queries)
+        if nodes.shape[0] > 0:
+            self._check_q(nodes)
+        N, Q = nodes.shape[0], queries.shape[0]
+        idx = torch.empty((Q, int(k)), dtype=torch.int32, device=queries.device)
+        dist = torch.empty((Q, int(k)), dtype=torch.float64, device=queries.device) if want_dist else None
+        check(_lib.lib().ccmp_knn_batch(self.ctx.handle, nodes.data_ptr() if N else None, N, queries.data_ptr(), Q, int(k), int(mode),
+                                        int(self_base), idx.data_ptr(), dist.data_ptr() if dist is not None else None,
+                                        _stream_handle(stream)), "ccmp_knn_batch")
+        return idx, dist
+
+    def connect_batch(self, nodes, queries, k, mode=0, self_base=0, check_target=True, max_states=64, round_budget=0, scene=None,
+                      margin=None, stream=None):
+        """Neighbours and their traversals in one call on one stream (ccmp_connect_batch): edge e = q * k + r runs from
+        nodes[nbr_idx[q, r]] to queries[q] — checkMotion(n, m) with check_target, discreteGeodesic(n -> m) without — exactly as
+        `discrete_geodesic_batch` (or, with a ProxyScene and a margin, `discrete_geodesic_scene_batch`) would on the gathered
+        pairs.  Returns a dict: nbr_idx, nbr_dist (Q,k); states (Q*k,max_states,14); n_states, ok, newton_iters, blocked (Q*k,);
+        carry (Q*k,2).  Empty slots (idx = -1): ok = 0, n_states = 0, newton_iters = 0, blocked = 0, carry = 0.  Edges that
+        stopped short (ok == 2, n_states == max_states + 1) continue through `continue_geodesics` with to = the query."""
+        self._need_problem()
+        torch = _torch()
+        self._check_q(queries)
+        if nodes.shape[0] > 0:
+            self._check_q(nodes)
+        N, Q, k = nodes.shape[0], queries.shape[0], int(k)
+        E, dev = Q * k, queries.device
+        out = {
+            "nbr_idx": torch.empty((Q, k), dtype=torch.int32, device=dev),
+            "nbr_dist": torch.empty((Q, k), dtype=torch.float64, device=dev),
+            "states": torch.empty((E, int(max_states), 14), dtype=torch.float64, device=dev),
+            "n_states": torch.empty(E, dtype=torch.int32, device=dev),
+            "ok": torch.empty(E, dtype=torch.uint8, device=dev),
+            "newton_iters": torch.empty(E, dtype=torch.int32, device=dev),
+            "blocked": torch.empty(E, dtype=torch.uint8, device=dev),
+            "carry": torch.empty((E, 2), dtype=torch.float64, device=dev),
+        }
+        check(_lib.lib().ccmp_connect_batch(self.ctx.handle, C.byref(self.problem), scene._h if scene is not None else None,
+                                            float(margin) if scene is not None else 0.0, nodes.data_ptr() if N else None, N,
+                                            queries.data_ptr(), Q, k, int(mode), int(self_base), 1 if check_target else 0, int(max_states),
+                                            int(round_budget), out["nbr_idx"].data_ptr(), out["nbr_dist"].data_ptr(), out["states"].data_ptr(),
+                                            out["n_states"].data_ptr(), out["ok"].data_ptr(), out["newton_iters"].data_ptr(),
+                                            out["blocked"].data_ptr(), out["carry"].data_ptr(), _stream_handle(stream)), "ccmp_connect_batch")
+        return out
+
     def continue_geodesics(self, to, states, n, ok, its, carry, max_states, round_budget=0, max_calls=1 << 20, cont_states=None,
                            scene=None, margin=None):
         """Finishes the edges of a `discrete_geodesic_batch(..., want_carry=True)` result that did not reach their end

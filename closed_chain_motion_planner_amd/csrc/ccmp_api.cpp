@@ -171,6 +171,8 @@ void ccmp_ctx_destroy(ccmp_ctx *ctx)
   ccmp_host::resident_destroy(ctx); // first: hipFree below waits for the whole device, a resident kernel included
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->geo_pool) (void)hipFree(ctx->geo_pool);
+  if (ctx->knn_ws) (void)hipFree(ctx->knn_ws);
+  if (ctx->connect_ws) (void)hipFree(ctx->connect_ws);
   if (ctx->queue) (void)hipFree(ctx->queue);
   if (ctx->pool) (void)hipFree(ctx->pool);
   if (ctx->lpt_buf) (void)hipFree(ctx->lpt_buf);
@@ -598,6 +600,75 @@ int ccmp_geodesic_scene_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_s
   const int blocks = ccmp_host::plan_geodesic_scene(ctx, E, p->jacobian_mode != CCMP_JAC_FD);
   if (p->jacobian_mode != CCMP_JAC_FD) HIP_TRY(ccmp_launch::geodesic_analytic_scene(g, sg, blocks, ctx->queue + kQGeoAnalytic, st));
   else HIP_TRY(ccmp_launch::geodesic_scene(g, sg, blocks, ctx->queue + kQGeoTicket, st));
+  return CCMP_OK;
+}
+
+// ---- the connection step -------------------------------------------------------------------------------
+// what every form of a k-NN call checks (Q > 0 behind it)
+static int knn_args(const double *nodes, size_t N, const double *queries, size_t Q, int k, int mode, const int32_t *nbr_idx)
+{
+  if (k < 1 || k > CCMP_KNN_MAX_K || mode < CCMP_KNN_ALL || mode > CCMP_KNN_EARLIER) return CCMP_EINVAL;
+  if (N >= ((size_t)1 << 31) || Q >= ((size_t)1 << 31)) return CCMP_EINVAL; // indices are int32; one merge block per query
+  if (Q > 0 && (!queries || !nbr_idx || (N > 0 && !nodes))) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+// the launches of a k-NN call whose arguments are checked and whose workspace has its size (ccmp_policy.cpp: plan_knn)
+static int knn_launches(ccmp_ctx *ctx, const KnnCall &c, const KnnShape &s, hipStream_t st)
+{
+  HIP_TRY(ccmp_launch::knn(c, s, ctx->knn_ws, st));
+  return CCMP_OK;
+}
+
+int ccmp_knn_batch(ccmp_ctx *ctx, const double *nodes, size_t N, const double *queries, size_t Q, int k, int mode, size_t self_base,
+                   int32_t *nbr_idx, double *nbr_dist, void *hip_stream)
+{
+  if (!ctx) return CCMP_EINVAL;
+  CCMP_DEBUG_FAIL_POINT()
+  { const int rc = knn_args(nodes, N, queries, Q, k, mode, nbr_idx); if (rc != CCMP_OK) return rc; }
+  if (Q == 0) return CCMP_OK;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  const KnnShape s = ccmp_host::plan_knn(ctx, Q, N, k);
+  { const int rc = grow(ctx, &ctx->knn_ws, &ctx->knn_ws_cap, s.workspace_bytes, s.workspace_bytes); if (rc != CCMP_OK) return rc; }
+  return knn_launches(ctx, KnnCall{nodes, N, queries, Q, k, mode, self_base, nbr_idx, nbr_dist}, s, (hipStream_t)hip_stream);
+}
+
+// k-NN, gather, the traversal the caller would have run on the gathered pairs (geodesic_common, or the scene variant's entry point,
+// both unchanged), then the empty slots' values.  One stream, no host synchronisation; both workspaces of its own have their size
+// before the first launch.
+int ccmp_connect_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, size_t N,
+                       const double *queries, size_t Q, int k, int mode, size_t self_base, int check_target, int max_states, int round_budget,
+                       int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                       double *carry_out, void *hip_stream)
+{
+  if (!ctx) return CCMP_EINVAL;
+  CCMP_DEBUG_FAIL_POINT()
+  { const int rc = check_problem(p); if (rc != CCMP_OK) return rc; }
+  { const int rc = knn_args(nodes, N, queries, Q, k, mode, nbr_idx); if (rc != CCMP_OK) return rc; }
+  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  if (Q == 0) return CCMP_OK;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t E = Q * (size_t)k;
+  const KnnShape s = ccmp_host::plan_knn(ctx, Q, N, k);
+  { const int rc = grow(ctx, &ctx->knn_ws, &ctx->knn_ws_cap, s.workspace_bytes, s.workspace_bytes); if (rc != CCMP_OK) return rc; }
+  { const int rc = grow(ctx, (void **)&ctx->connect_ws, &ctx->connect_ws_cap, E, E * 28 * sizeof(double)); if (rc != CCMP_OK) return rc; }
+  double *from = ctx->connect_ws, *to = ctx->connect_ws + E * 14;
+  { const int rc = geodesic_args(p, from, to, max_states, states, n_states, ok, nullptr, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; }
+  { const int rc = knn_launches(ctx, KnnCall{nodes, N, queries, Q, k, mode, self_base, nbr_idx, nbr_dist}, s, st); if (rc != CCMP_OK) return rc; }
+  HIP_TRY(ccmp_launch::connect_gather(nodes, queries, nbr_idx, E, k, from, to, st));
+  int rc;
+  if (scene)
+    rc = ccmp_geodesic_scene_batch(ctx, p, scene, margin, from, to, E, max_states, states, n_states, ok, newton_iters, blocked, nullptr, nullptr,
+                                   carry_out, round_budget, check_target, hip_stream);
+  else {
+    rc = geodesic_common(ctx, p, from, to, E, max_states, states, n_states, ok, newton_iters, nullptr, carry_out, round_budget, check_target, hip_stream);
+    if (rc == CCMP_OK && blocked) HIP_TRY(hipMemsetAsync(blocked, 0, E, st)); // no scene refuses anything
+  }
+  if (rc != CCMP_OK) return rc;
+  HIP_TRY(ccmp_launch::connect_fix(nbr_idx, E, n_states, ok, newton_iters, blocked, carry_out, st));
   return CCMP_OK;
 }
 

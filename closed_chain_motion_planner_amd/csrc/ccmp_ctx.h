@@ -83,6 +83,10 @@ struct ccmp_ctx {
   size_t geo_pool_cap = 0;
   unsigned int *scan = nullptr;        // compaction block counts
   size_t scan_cap = 0;
+  void *knn_ws = nullptr;              // k-NN: the partitions' lists (ccmp_launch.h: KnnShape)
+  size_t knn_ws_cap = 0;               // in bytes
+  double *connect_ws = nullptr;        // ccmp_connect_batch: the gathered endpoints, from [E][14] then to [E][14]
+  size_t connect_ws_cap = 0;           // in edges
   void *stage = nullptr;               // device staging of the *_host conveniences
   size_t stage_cap = 0;
   void *pin = nullptr;                 // pinned, device-mapped host block for small *_host calls (single states of the reference signature)

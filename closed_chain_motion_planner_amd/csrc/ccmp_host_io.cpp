@@ -522,6 +522,79 @@ int ccmp_geodesic_scene_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sc
   return io.finish();
 }
 
+// the connection step on host buffers: nodes and queries are uploaded per call (there is no device-resident node store)
+int ccmp_knn_host(ccmp_ctx *ctx, const double *nodes, size_t N, const double *queries, size_t Q, int k, int mode, size_t self_base,
+                  int32_t *nbr_idx, double *nbr_dist)
+{
+  if (!ctx) return CCMP_EINVAL;
+  if (k < 1 || k > CCMP_KNN_MAX_K || mode < CCMP_KNN_ALL || mode > CCMP_KNN_EARLIER || N >= ((size_t)1 << 31) || Q >= ((size_t)1 << 31)) return CCMP_EINVAL;
+  if (Q == 0) return CCMP_OK;
+  if (!queries || !nbr_idx || (N > 0 && !nodes)) return CCMP_EINVAL;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  const size_t nb = N * 14 * sizeof(double), qb = Q * 14 * sizeof(double), S = Q * (size_t)k;
+  const size_t off_q = (nb + 255) & ~(size_t)255;
+  const size_t off_i = (off_q + qb + 255) & ~(size_t)255;
+  const size_t off_d = (off_i + S * sizeof(int32_t) + 255) & ~(size_t)255;
+  HostIO io(ctx);
+  int rc = io.begin(off_d + S * sizeof(double));
+  if (rc != CCMP_OK) return rc;
+  if (N > 0 && (rc = io.in(0, nodes, nb)) != CCMP_OK) return rc;
+  if ((rc = io.in(off_q, queries, qb)) != CCMP_OK) return rc;
+  rc = ccmp_knn_batch(ctx, (const double *)io.dev, N, (const double *)(io.dev + off_q), Q, k, mode, self_base, (int32_t *)(io.dev + off_i),
+                      nbr_dist ? (double *)(io.dev + off_d) : nullptr, ctx->stream);
+  if (rc != CCMP_OK) return rc;
+  if ((rc = io.out(nbr_idx, off_i, S * sizeof(int32_t))) != CCMP_OK) return io.abandon(rc);
+  if (nbr_dist && (rc = io.out(nbr_dist, off_d, S * sizeof(double))) != CCMP_OK) return io.abandon(rc);
+  return io.finish();
+}
+
+int ccmp_connect_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, size_t N,
+                      const double *queries, size_t Q, int k, int mode, size_t self_base, int check_target, int max_states, int round_budget,
+                      int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                      double *carry_out)
+{
+  if (!ctx || !p) return CCMP_EINVAL;
+  if (k < 1 || k > CCMP_KNN_MAX_K || mode < CCMP_KNN_ALL || mode > CCMP_KNN_EARLIER || N >= ((size_t)1 << 31) || Q >= ((size_t)1 << 31)) return CCMP_EINVAL;
+  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  if (Q == 0) return CCMP_OK;
+  if (!queries || !nbr_idx || (N > 0 && !nodes) || !states || !n_states || !ok || max_states < 1) return CCMP_EINVAL;
+  if (round_budget < 0 || (round_budget > 0 && !carry_out) || ((carry_out || round_budget > 0) && max_states < 2)) return CCMP_EINVAL; // as geodesic_args: before any buffer is touched
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  const size_t E = Q * (size_t)k;
+  const size_t nb = N * 14 * sizeof(double), qb = Q * 14 * sizeof(double), sb = E * (size_t)max_states * 14 * sizeof(double), cb = E * 2 * sizeof(double);
+  const size_t off_q = (nb + 255) & ~(size_t)255;
+  const size_t off_i = (off_q + qb + 255) & ~(size_t)255;
+  const size_t off_d = (off_i + E * sizeof(int32_t) + 255) & ~(size_t)255;
+  const size_t off_st = (off_d + E * sizeof(double) + 255) & ~(size_t)255;
+  const size_t off_n = (off_st + sb + 255) & ~(size_t)255;
+  const size_t off_ok = (off_n + E * sizeof(int32_t) + 255) & ~(size_t)255;
+  const size_t off_it = (off_ok + E + 255) & ~(size_t)255;
+  const size_t off_bl = (off_it + E * sizeof(int32_t) + 255) & ~(size_t)255;
+  const size_t off_co = (off_bl + E + 255) & ~(size_t)255;
+  HostIO io(ctx);
+  int rc = io.begin(off_co + cb);
+  if (rc != CCMP_OK) return rc;
+  if (N > 0 && (rc = io.in(0, nodes, nb)) != CCMP_OK) return rc;
+  if ((rc = io.in(off_q, queries, qb)) != CCMP_OK) return rc;
+  rc = ccmp_connect_batch(ctx, p, scene, margin, (const double *)io.dev, N, (const double *)(io.dev + off_q), Q, k, mode, self_base, check_target,
+                          max_states, round_budget, (int32_t *)(io.dev + off_i), nbr_dist ? (double *)(io.dev + off_d) : nullptr,
+                          (double *)(io.dev + off_st), (int32_t *)(io.dev + off_n), (uint8_t *)(io.dev + off_ok),
+                          newton_iters ? (int32_t *)(io.dev + off_it) : nullptr, blocked ? (uint8_t *)(io.dev + off_bl) : nullptr,
+                          carry_out ? (double *)(io.dev + off_co) : nullptr, ctx->stream);
+  if (rc != CCMP_OK) return rc;
+  if ((rc = io.out(nbr_idx, off_i, E * sizeof(int32_t))) != CCMP_OK) return io.abandon(rc);
+  if (nbr_dist && (rc = io.out(nbr_dist, off_d, E * sizeof(double))) != CCMP_OK) return io.abandon(rc);
+  if ((rc = io.out(states, off_st, sb)) != CCMP_OK) return io.abandon(rc);
+  if ((rc = io.out(n_states, off_n, E * sizeof(int32_t))) != CCMP_OK) return io.abandon(rc);
+  if ((rc = io.out(ok, off_ok, E)) != CCMP_OK) return io.abandon(rc);
+  if (newton_iters && (rc = io.out(newton_iters, off_it, E * sizeof(int32_t))) != CCMP_OK) return io.abandon(rc);
+  if (blocked && (rc = io.out(blocked, off_bl, E)) != CCMP_OK) return io.abandon(rc);
+  if (carry_out && (rc = io.out(carry_out, off_co, cb)) != CCMP_OK) return io.abandon(rc);
+  return io.finish();
+}
+
 // One shard of ccmp_*_sharded_host, on its context's device and stream: upload (mode 0), project, download, wait.  Runs
 // on its own thread when there are several (for_each_shard): a copy from pageable memory returns only when the data is
 // staged and a copy into pageable memory only when it has arrived, so shards driven from ONE thread start and finish one

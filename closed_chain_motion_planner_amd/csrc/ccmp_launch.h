@@ -108,7 +108,33 @@ struct GeoLaunch {
   const double *pool = nullptr; const unsigned long long *pool_count = nullptr; // drain of a bulk call: the edges handed over, their count
 };
 
+/* one k-nearest-neighbour call (ccmp_knn_batch) ... */
+struct KnnCall {
+  const double *nodes; size_t N;
+  const double *queries; size_t Q;
+  int k, mode;
+  size_t self_base;
+  int32_t *nbr_idx;  // [Q][k]
+  double *nbr_dist;  // [Q][k], nullable
+};
+/* ... and its launch shape (ccmp_policy.cpp: plan_knn).  No field changes a result bit. */
+constexpr int kKnnThreads = 256; // threads per block of every k-NN kernel; queries per block of the many-query kernel
+constexpr int kKnnTile = 256;    // nodes per LDS tile of the many-query kernel (28 KB)
+constexpr int kKnnMaxPartitions = 256; // the merge kernel holds one partition's list per thread
+struct KnnShape {
+  bool few = false;            // knn_few_kernel: one block per (partition, query), else knn_many_kernel: one query per thread
+  unsigned int groups = 0;     // many-query kernel: blocks of kKnnThreads queries
+  unsigned int partitions = 1; // cuts of the node range; > 1: partial lists in the workspace + knn_merge_kernel
+  unsigned int part = 0;       // nodes per partition (a multiple of kKnnTile)
+  int kc = 0;                  // list capacity the kernels are instantiated for: 1, 4, 8 or 16 (>= k)
+  size_t workspace_bytes = 0;  // Q * partitions * kc * 12, 0 with one partition
+};
+
 #pragma GCC visibility push(hidden)
+hipError_t knn(const KnnCall &c, const KnnShape &s, void *workspace, hipStream_t st);
+hipError_t connect_gather(const double *nodes, const double *queries, const int32_t *nbr_idx, size_t E, int k, double *from, double *to, hipStream_t st);
+hipError_t connect_fix(const int32_t *nbr_idx, size_t E, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out,
+                       hipStream_t st);
 hipError_t clear_words(void *words, size_t n_u32, hipStream_t st);
 hipError_t project_group(const ProjectCall &c, int blocks, unsigned long long *queue, double *pool, int dump_threshold, const unsigned int *order,
                          const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st);

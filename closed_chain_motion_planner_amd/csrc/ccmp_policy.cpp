@@ -282,6 +282,30 @@ GeoPlan plan_geodesic(const ccmp_ctx *ctx, size_t E, int round_budget, bool cont
   return pl;
 }
 
+// The k nearest neighbours.  Up to kKnnFewMax queries (the planner inserting a milestone): one block per (partition, query), the
+// threads striding over the partition's nodes — a single query over 10^5 nodes is on every CU.  More queries: one query per thread,
+// 256 per block, the partition's nodes through LDS tiles.  Either way the node range is cut so that the call has about two blocks
+// per CU, into at most kKnnMaxPartitions partitions of at least kKnnMinPart nodes; with more than one partition the lists go through
+// the context's workspace and knn_merge_kernel.  The (distance, index) key makes the result the same for every cut.
+ccmp_launch::KnnShape plan_knn(const ccmp_ctx *ctx, size_t Q, size_t N, int k)
+{
+  ccmp_launch::KnnShape s;
+  s.kc = k <= 1 ? 1 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16));
+  s.few = Q <= kKnnFewMax;
+  const size_t units = s.few ? Q : (Q + ccmp_launch::kKnnThreads - 1) / ccmp_launch::kKnnThreads; // blocks per partition
+  s.groups = (unsigned int)units;
+  size_t want = units ? ((size_t)ctx->num_cus * 2 + units - 1) / units : 1;
+  if (want < 1) want = 1;
+  if (want > (size_t)ccmp_launch::kKnnMaxPartitions) want = ccmp_launch::kKnnMaxPartitions;
+  size_t part = (N + want - 1) / want;
+  part = (part + ccmp_launch::kKnnTile - 1) / ccmp_launch::kKnnTile * ccmp_launch::kKnnTile;
+  if (part < kKnnMinPart) part = kKnnMinPart;
+  s.part = (unsigned int)part;
+  s.partitions = N ? (unsigned int)((N + part - 1) / part) : 1u;
+  s.workspace_bytes = s.partitions > 1 ? Q * (size_t)s.partitions * (size_t)s.kc * (sizeof(double) + sizeof(int32_t)) : 0;
+  return s;
+}
+
 }  // namespace ccmp_host
 
 namespace {
@@ -424,6 +448,35 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
       const int fd = plan_geodesic_scene(ctx, n, false), an = plan_geodesic_scene(ctx, n, true);
       L.add("geodesic with a proxy scene E=%zu: geodesic_scene_kernel x %d blocks (one edge per 128-thread block, ticket queue); analytic mode: "
             "geodesic_row16_scene_kernel x %d wavefronts (four edges per wavefront, ticket queue; at most %d per CU)", n, fd, an, kGeoAnalyticWavesPerCu);
+      break;
+    }
+    case CCMP_CALL_KNN:
+    case CCMP_CALL_CONNECT: {
+      // n = the queries; the node count and k are not arguments of this function: a roadmap of kKnnDescribeNodes nodes and the
+      // reference's five neighbours are assumed (the shape follows Q, N and the CU count only)
+      constexpr size_t kKnnDescribeNodes = 65536;
+      const ccmp_launch::KnnShape s = plan_knn(ctx, n, kKnnDescribeNodes, kConnectDescribeK);
+      L.add("%s Q=%zu (N=%zu, k=%d assumed): ", call_kind == CCMP_CALL_KNN ? "knn" : "connect", n, kKnnDescribeNodes, kConnectDescribeK);
+      if (s.few)
+        L.add("partitioned form: knn_few_kernel x %zu blocks (one per partition and query, %d threads striding over %u nodes)", (size_t)s.partitions * s.groups,
+              ccmp_launch::kKnnThreads, s.part);
+      else
+        L.add("knn_many_kernel x %zu blocks (one query per thread, %d per block; LDS tiles of %d nodes)", (size_t)s.partitions * s.groups,
+              ccmp_launch::kKnnThreads, ccmp_launch::kKnnTile);
+      L.add(", %u partitions of %u nodes", s.partitions, s.part);
+      if (s.partitions > 1) L.add(", then knn_merge_kernel x %zu blocks (workspace %zu bytes)", n, s.workspace_bytes);
+      L.add(", lists of %d [few_queries<=%zu min_partition=%u max_partitions=%d]", s.kc, kKnnFewMax, kKnnMinPart, ccmp_launch::kKnnMaxPartitions);
+      if (call_kind == CCMP_CALL_CONNECT) {
+        L.add("; connect_gather_kernel; then, for %zu edges, ", n * kConnectDescribeK);
+        const int m = ccmp_ctx_describe(ctx_in, CCMP_CALL_GEODESIC, n * kConnectDescribeK, nullptr, 0);
+        if (m > 0) {
+          char sub[2048];
+          (void)ccmp_ctx_describe(ctx_in, CCMP_CALL_GEODESIC, n * kConnectDescribeK, sub, sizeof sub);
+          for (size_t at = 0, len = strlen(sub); at < len; at += 256) L.add("%.256s", sub + at);
+        }
+        L.add("; connect_fix_kernel (empty slots)");
+        return (int)L.len; // (the traversal's line already says whether a context was given)
+      }
       break;
     }
     default: return CCMP_EINVAL;

@@ -4,6 +4,7 @@
 #ifndef CCMP_POLICY_H
 #define CCMP_POLICY_H
 #include "ccmp_ctx.h"
+#include "ccmp_launch.h"
 
 namespace ccmp_host {
 
@@ -64,6 +65,13 @@ int plan_geodesic_analytic(const ccmp_ctx *ctx, size_t E);
 /* the extend step with a proxy scene (ccmp_geodesic_scene_batch): analytic mode as plan_geodesic_analytic (geodesic_row16_scene_kernel),
  * FD mode geodesic_scene_kernel's blocks (one per edge up to the latency build's resident blocks, persistent on a ticket beyond) */
 int plan_geodesic_scene(const ccmp_ctx *ctx, size_t E, bool analytic);
+
+/* the k nearest neighbours of Q queries among N nodes (ccmp_knn_batch, and the first part of ccmp_connect_batch): which kernel, how
+ * the node range is cut.  A function of Q, N, k and the CU count alone: there is no option. */
+constexpr size_t kKnnFewMax = 8;          // up to this many queries: one block per (partition, query)
+constexpr unsigned int kKnnMinPart = 1024; // nodes per partition at least (four tiles)
+ccmp_launch::KnnShape plan_knn(const ccmp_ctx *ctx, size_t Q, size_t N, int k);
+constexpr int kConnectDescribeK = 5;      // ccmp_ctx_describe(CCMP_CALL_CONNECT): the reference's DEFAULT_NEAREST_NEIGHBORS
 
 /* ccmp_ctx_set_option behind the options ccmp_api.cpp handles itself ("resident"): the option table */
 __attribute__((visibility("hidden"))) int policy_set_option(ccmp_ctx *ctx, const char *name, long value);

@@ -193,6 +193,43 @@ class jy_ProjectedStateSpace:
             out.append((good, st.copy()))
         return out
 
+    def nearestK(self, nodes, state_or_states, k):
+        """The reference's connectionStrategy_(m) (a KStrategy over tree_, src/planner/stefanBiPRM.cpp:292,390,457) on the joint
+        distance: numpy nodes (N,14) and one state (14,) or several (Q,14) -> neighbour indices (k,) or (Q,k), nearest first,
+        ties to the lower index, -1 where fewer than k nodes exist.  The joint term only: the compound space's SE3 term is not
+        part of it."""
+        torch = _torch()
+        dev = "cuda:%d" % self.constraint_.ctx.device
+        q = np.ascontiguousarray(state_or_states, dtype=np.float64)
+        single = q.ndim == 1
+        nd = torch.as_tensor(np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 14)).to(dev)
+        idx, _ = self.constraint_.nearest_k_batch(nd, torch.as_tensor(q.reshape(-1, 14)).to(dev), k, want_dist=False)
+        idx = idx.cpu().numpy()
+        return idx[0] if single else idx
+
+    def connectMilestones(self, nodes, new_states, k, check_target=True):
+        """addMilestone's neighbour loop for a batch of new states (src/planner/stefanBiPRM.cpp:390-409): the k nearest nodes
+        of each, then checkMotion(neighbour, new) — discreteGeodesic(neighbour, new) with check_target=False, growTree's — through
+        `discreteGeodesicBatch`, so cut lists are re-run and the validity test applies exactly as there.  Returns (nbr_idx (Q,k),
+        reached (Q,k) bool, lists: Q lists of k state arrays); a slot without a neighbour (-1) is not reached and has an empty
+        list."""
+        torch = _torch()
+        dev = "cuda:%d" % self.constraint_.ctx.device
+        nd = torch.as_tensor(np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 14)).to(dev)
+        qs = torch.as_tensor(np.ascontiguousarray(new_states, dtype=np.float64).reshape(-1, 14)).to(dev)
+        idx, _ = self.constraint_.nearest_k_batch(nd, qs, k, want_dist=False)
+        Q, k = idx.shape
+        flat = idx.reshape(-1).long()
+        have = flat >= 0
+        frm = nd[flat[have]] if nd.shape[0] else nd
+        to = qs.repeat_interleave(k, dim=0)[have]
+        res = self.discreteGeodesicBatch(frm.cpu().numpy(), to.cpu().numpy(), False, check_target) if frm.shape[0] else []
+        reached = np.zeros(Q * k, dtype=bool)
+        lists = [np.zeros((0, 14))] * (Q * k)
+        for e, (good, st) in zip(np.flatnonzero(have.cpu().numpy()), res):
+            reached[e], lists[e] = good, st
+        return idx.cpu().numpy(), reached.reshape(Q, k), [lists[q * k:(q + 1) * k] for q in range(Q)]
+
     def discreteGeodesic(self, frm, to, interpolate=False, geodesic=None, check_target=False):
         good, st = self.discreteGeodesicBatch(np.asarray(frm).reshape(1, 14), np.asarray(to).reshape(1, 14), interpolate,
                                               check_target)[0]

@@ -250,7 +250,9 @@ enum {
   CCMP_CALL_GEODESIC = 3,         /* ccmp_geodesic_batch / _ex without a round budget  */
   CCMP_CALL_GEODESIC_BUDGET = 4,  /* ccmp_geodesic_batch_ex with round_budget > 0      */
   CCMP_CALL_GEODESIC_ANALYTIC = 5, /* ccmp_geodesic_batch / _ex with CCMP_JAC_ANALYTIC */
-  CCMP_CALL_GEODESIC_SCENE = 6     /* ccmp_geodesic_scene_batch, both Jacobian modes    */
+  CCMP_CALL_GEODESIC_SCENE = 6,    /* ccmp_geodesic_scene_batch, both Jacobian modes    */
+  CCMP_CALL_KNN = 7,               /* ccmp_knn_batch: n = the queries; 65536 nodes and k = 5 assumed (the shape follows Q, N and the CU count) */
+  CCMP_CALL_CONNECT = 8            /* ccmp_connect_batch: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
 };
 int ccmp_ctx_describe(const ccmp_ctx *ctx, int call_kind, size_t n, char *buf, size_t cap);
 int ccmp_ctx_device(const ccmp_ctx *ctx);
@@ -499,6 +501,54 @@ int ccmp_geodesic_scene_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_s
 int ccmp_geodesic_scene_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *from, const double *to,
                              size_t E, int max_states, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
                              double *clearance, const double *carry_in, double *carry_out, int round_budget, int check_target);
+
+/* ---- the connection step: k nearest neighbours, and neighbours + checkMotion in one call ------------------------------------------ */
+/* The reference chooses the pairs it tries with connectionStrategy_(m): a KStrategy over tree_ with DEFAULT_NEAREST_NEIGHBORS = 5
+ * (src/planner/stefanBiPRM.cpp:292,390,457; stefanBiPRM.h:35), followed by checkMotion(neighbour, new) per neighbour in addMilestone /
+ * startgoalMilestone (:392-409, :458-475) or discreteGeodesic(neighbour, new) in growTree (:307-351).
+ * Distance: RealVectorStateSpace::distance over the 14 joints exactly as oracle/ccmp_oracle.c: orc_distance states it — the chain
+ * dist = fma(diff_i, diff_i, dist), i = 0..13, diff_i = a[i] - b[i], then the correctly rounded square root; not wrap-aware.  THE
+ * JOINT TERM ONLY: the reference's tree metric is the compound space's, this distance plus the object's SE3 distance
+ * (ConstrainedPlanningCommon.cpp:66-67); the SE3 term is not part of this library.
+ * Ranking of the eligible nodes of a query: ascending by (distance as returned, i.e. after the square root; node index) — equal
+ * distances go to the lower index, also where two different squared sums round to one distance.  Eligible: a node whose distance
+ * to the query is not NaN (a NaN on either side: never a neighbour), and by mode
+ *   CCMP_KNN_ALL       every node;
+ *   CCMP_KNN_NOT_SELF  query q IS node self_base + q, which is left out;
+ *   CCMP_KNN_EARLIER   only nodes j < self_base + q: a batch inserted in order, each node seeing the ones before it — the
+ *                      sequential addMilestone order.
+ * nbr_idx[q][r] / nbr_dist[q][r] (nullable), r = 0..k-1: the r-th neighbour; fewer than k eligible nodes leave the remaining slots
+ * idx = -1, dist = +inf.  1 <= k <= CCMP_KNN_MAX_K, N < 2^31 (N == 0 is allowed: every slot empty), Q < 2^31; Q == 0 returns CCMP_OK and
+ * touches nothing.  The result is a function of the arguments alone: the launch shape (csrc/ccmp_policy.cpp: plan_knn, from Q, N and
+ * the CU count; no option) never changes it.  `nodes` is read per call: there is no device-resident, appendable node store, and the
+ * host form uploads the nodes every time.  Device pointers, asynchronous on hip_stream, capturable (after one eager call at that
+ * size); the resident service does not serve these calls. */
+#define CCMP_KNN_MAX_K 16
+enum { CCMP_KNN_ALL = 0, CCMP_KNN_NOT_SELF = 1, CCMP_KNN_EARLIER = 2 };
+int ccmp_knn_batch(ccmp_ctx *ctx, const double *nodes, size_t N, const double *queries, size_t Q, int k, int mode, size_t self_base,
+                   int32_t *nbr_idx, double *nbr_dist, void *hip_stream);
+/* the same on host buffers, synchronous */
+int ccmp_knn_host(ccmp_ctx *ctx, const double *nodes, size_t N, const double *queries, size_t Q, int k, int mode, size_t self_base,
+                  int32_t *nbr_idx, double *nbr_dist);
+/* Neighbours and their traversals in ONE call on one stream, without a host synchronisation: ccmp_knn_batch, then edge e = q * k + r
+ * with from = nodes[nbr_idx[q][r]] and to = queries[q] — the reference's direction, checkMotion(n, m) / discreteGeodesic(n -> t) —
+ * through the extend step exactly as ccmp_geodesic_batch_ex runs it (scene == NULL; blocked, if given, is all 0) or as
+ * ccmp_geodesic_scene_batch runs it (scene, margin; no clearance output).  check_target = 1: addMilestone's checkMotion; 0: growTree's
+ * discreteGeodesic.  states [Q*k][max_states][14], n_states / ok / newton_iters (nullable) / blocked (nullable) [Q*k], carry_out
+ * [Q*k][2] (nullable unless round_budget > 0).  Every occupied slot reports, bit for bit, what that entry point reports for the pair;
+ * an empty slot (idx = -1) costs no Newton work and reports ok = 0, n_states = 0, newton_iters = 0, blocked = 0, carry_out = {0, 0}
+ * (its rows of `states` are unspecified).  A suspended (ok = 2) or full-list (n_states = max_states + 1) edge is continued through
+ * ccmp_geodesic_batch_ex / ccmp_geodesic_scene_batch as documented there: from = its last stored state, to = queries[q], carry_in =
+ * its carry_out.  CCMP_EINVAL: the k-NN's and ccmp_geodesic_batch_ex's cases, and with a scene ccmp_geodesic_scene_batch's. */
+int ccmp_connect_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, size_t N,
+                       const double *queries, size_t Q, int k, int mode, size_t self_base, int check_target, int max_states, int round_budget,
+                       int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                       double *carry_out, void *hip_stream);
+/* the same on host buffers, synchronous */
+int ccmp_connect_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, size_t N,
+                      const double *queries, size_t Q, int k, int mode, size_t self_base, int check_target, int max_states, int round_budget,
+                      int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                      double *carry_out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

@@ -375,6 +375,17 @@ inline bool discreteGeodesic(const Projector &proj, const double *from14, const 
   return reached[0] != 0;
 }
 
+// The reference's connectionStrategy_(m) — a KStrategy over tree_ (src/planner/stefanBiPRM.cpp:292,390,457) — on the joint distance
+// (ccmp_knn_host): the k nearest of N host states for one state, nearest first, ties to the lower index; idx has k entries, -1
+// where fewer than k nodes exist.  The joint term only: the compound space's SE3 term is not part of it.  The
+// nodes are uploaded with every call.
+inline void nearestK(const Projector &proj, const double *nodes, size_t N, const double *q14, unsigned k, std::vector<int32_t> *idx)
+{
+  idx->assign(k, -1);
+  std::lock_guard<std::mutex> hold(proj.mutex());
+  check(ccmp_knn_host(proj.ctx(), nodes, N, q14, 1, (int)k, CCMP_KNN_ALL, 0, idx->data(), nullptr), "ccmp_knn_host");
+}
+
 // One planner process, several GPUs (the reference's shape: src/main.cpp is one process): one context per device and an
 // RCCL communicator over them.  sampleProjectSharded / projectSharded spread a batch over the GPUs in contiguous shards,
 // every GPU compacts its valid states into a fixed-capacity block and ONE all-gather brings them together; the valid
@@ -907,6 +918,50 @@ public:
   void discreteGeodesics(const std::vector<const ompl::base::State *> &from, const ompl::base::State *to, bool interpolate,
                          std::vector<std::vector<ompl::base::State *>> *geodesics, std::vector<char> *reached) const
   {
+    traverseMany(from, to, interpolate, geodesics, reached, false);
+  }
+
+  // connectionStrategy_(m) of the reference's planner (a KStrategy over tree_, src/planner/stefanBiPRM.cpp:292,390,457) on the joint
+  // distance: the indices into `nodes` of the k nearest to s, nearest first, ties to the lower index; fewer when there are fewer
+  // nodes.  The compound space's SE3 term is not part of the ranking.  false (and *out empty) when the GPU call
+  // failed: KinematicChainConstraint::lastError().
+  bool nearestK(const std::vector<const ompl::base::State *> &nodes, const ompl::base::State *s, unsigned k, std::vector<unsigned> *out) const
+  {
+    out->clear();
+    if (k == 0 || nodes.empty()) return true;
+    std::vector<double> a(nodes.size() * 14);
+    double b[14];
+    for (size_t j = 0; j < nodes.size(); ++j) {
+      const auto &x = *nodes[j]->as<StateType>();
+      for (int i = 0; i < 14; ++i) a[14 * j + i] = x[i];
+    }
+    const auto &sb = *s->as<StateType>();
+    for (int i = 0; i < 14; ++i) b[i] = sb[i];
+    std::vector<int32_t> idx;
+    if (!chain_->guarded([&] { ccmp::nearestK(chain_->impl(), a.data(), nodes.size(), b, k, &idx); })) return false;
+    for (int32_t j : idx)
+      if (j >= 0) out->push_back((unsigned)j);
+    return true;
+  }
+
+  // addMilestone's neighbour loop (src/planner/stefanBiPRM.cpp:390-409) in two calls: nearestK, then checkMotion(nodes[n], s) for
+  // every neighbour n in one launch — (*reached)[r] is the bool of the reference's call for (*neighbours)[r], (*geodesics)[r]
+  // (nullable) its list.  The StateValidityChecker is asked about the same states in the same order as by that loop.
+  void connectMilestone(const std::vector<const ompl::base::State *> &nodes, const ompl::base::State *s, unsigned k, std::vector<unsigned> *neighbours,
+                        std::vector<char> *reached, std::vector<std::vector<ompl::base::State *>> *geodesics) const
+  {
+    if (reached) reached->clear();
+    if (geodesics) geodesics->clear();
+    if (!nearestK(nodes, s, k, neighbours)) return;
+    std::vector<const ompl::base::State *> from;
+    for (unsigned j : *neighbours) from.push_back(nodes[j]);
+    traverseMany(from, s, false, geodesics, reached, true);
+  }
+
+private:
+  void traverseMany(const std::vector<const ompl::base::State *> &from, const ompl::base::State *to, bool interpolate,
+                    std::vector<std::vector<ompl::base::State *>> *geodesics, std::vector<char> *reached, bool check_target) const
+  {
     const size_t E = from.size();
     std::vector<double> a(E * 14), b(E * 14);
     const auto &tb = *to->as<StateType>();
@@ -928,7 +983,7 @@ public:
                                       for (int i = 0; i < 14; ++i) x[i] = q[i];
                                       return pre->isValidExact(scratch);
                                     },
-                                    geodesics ? &lists : nullptr, reached, 64, false, delta_, lambda_, pre->scene().get(), pre->rejectBelow(),
+                                    geodesics ? &lists : nullptr, reached, 64, check_target, delta_, lambda_, pre->scene().get(), pre->rejectBelow(),
                                     &blocked);
       else
         ccmp::discreteGeodesicBatch(proj, a.data(), b.data(), E, interpolate,
@@ -937,7 +992,7 @@ public:
                                       for (int i = 0; i < 14; ++i) x[i] = q[i];
                                       return svc->isValid(scratch);
                                     },
-                                    geodesics ? &lists : nullptr, reached, 64, false, delta_, lambda_); // setDelta / setLambda of the base class
+                                    geodesics ? &lists : nullptr, reached, 64, check_target, delta_, lambda_); // setDelta / setLambda of the base class
     });
     freeState(scratch);
     if (pre && done)
@@ -960,7 +1015,6 @@ public:
     }
   }
 
-private:
   bool traverse(const ompl::base::State *from, const ompl::base::State *to, bool interpolate, std::vector<ompl::base::State *> *geodesic,
                 bool check_target) const
   {

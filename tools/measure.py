@@ -17,6 +17,9 @@
     python tools/measure.py soak_resident [N] [--analytic]  N states as single calls through the resident service kernel against the batched kernels
                                                             (--analytic: analytic mode, and five checkMotion edges per request instead of one)
     python tools/measure.py scout                           FP32 scout's predictions against the true iteration counts
+    python tools/measure.py connect [reps]                  the connection step: ccmp_knn_batch against FP64 torch distances + torch.topk (throughput shape and
+                                                           single queries), ccmp_connect_batch against torch k-NN + gather + ccmp_geodesic_batch_ex, both
+                                                           contenders alternating in one process, device events, medians with their spread
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -508,6 +511,121 @@ def clearance(argv):
     print("single-state host call: median %.1f us" % (np.median(ts[20:]) * 1e6))
 
 
+def valid_states(c, n, seed=0x4E4E):
+    """n valid projected states (sampleUniform, the rows project() accepted)"""
+    rows, have, first = [], 0, 0
+    while have < n:
+        B = min(1 << 20, max(4 * (n - have), 4096))
+        q, ok, _, _ = c.sample_project_batch(seed, first, B, want_iters=False)
+        rows.append(q[ok != 0])
+        have += rows[-1].shape[0]
+        first += B
+    return torch.cat(rows)[:n].contiguous()
+
+
+def torch_knn_mm(nodes, queries, k):
+    """the fastest thing torch offers: |q|^2 + |n|^2 - 2 q n^T through the FP64 matrix product, then topk (inexact distances)"""
+    d2 = (queries * queries).sum(1)[:, None] + (nodes * nodes).sum(1)[None, :] - 2.0 * (queries @ nodes.T)
+    return torch.topk(d2, k, dim=1, largest=False, sorted=True)
+
+
+def torch_knn_diff(nodes, queries, k, chunk=256):
+    """squared differences summed per pair (the distance's own operations), in chunks of queries, then topk"""
+    vals, idxs = [], []
+    for s in range(0, queries.shape[0], chunk):
+        d2 = torch.cdist(queries[s: s + chunk], nodes, compute_mode="donot_use_mm_for_euclid_dist")
+        v, i = torch.topk(d2, k, dim=1, largest=False, sorted=True)
+        vals.append(v)
+        idxs.append(i)
+    return torch.cat(vals), torch.cat(idxs)
+
+
+def alternate(fns, reps):
+    """{name: [ms per call]} — every contender warmed up, then `reps` rounds in which each runs once, device events around each call"""
+    for fn in fns.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    out = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[name].append(e0.elapsed_time(e1))
+    return out
+
+
+def _stat(ms):
+    a = np.sort(np.asarray(ms))
+    return "median %.4f ms (min %.4f, max %.4f, n %d)" % (np.median(a), a[0], a[-1], len(a))
+
+
+def connect(argv):
+    """the connection step against what a user does without it; every line states the median and the spread of both contenders"""
+    reps = max(20, int(argv[0])) if argv else 20
+    ctx = Context(0)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    big = valid_states(c, (1 << 20) + 4096)
+    k = 5
+    verdicts = []
+
+    def compare(title, ours, theirs):
+        t = alternate({"ours": ours, **theirs}, reps)
+        best = min(theirs, key=lambda n: np.median(t[n]))
+        mo, mt = np.median(t["ours"]), np.median(t[best])
+        spread = max(np.max(t["ours"]) - np.min(t["ours"]), np.max(t[best]) - np.min(t[best]))
+        print("%s" % title)
+        for name, ms in t.items():
+            print("    %-28s %s" % (name, _stat(ms)))
+        ok = mo <= mt + spread
+        verdicts.append((title, ok))
+        print("    -> ours / best torch = %.3f  (%s)" % (mo / mt, "not slower" if ok else "SLOWER beyond the spread"), flush=True)
+        return mo
+
+    # k-NN throughput
+    nodes, queries = big[:65536].contiguous(), big[1 << 20:].contiguous()
+    N, Q = nodes.shape[0], queries.shape[0]
+    i0, d0 = c.nearest_k_batch(nodes, queries, k)
+    ref = torch_knn_diff(nodes, queries, k)
+    print("agreement with torch (exact-difference form): %d of %d neighbour slots equal" % (int((i0.long() == ref[1]).sum()), Q * k))
+    print(_lib.describe(ctx.handle, _lib.CALL_KNN, Q))
+    ms = compare("k-NN  N=%d Q=%d k=%d" % (N, Q, k), lambda: c.nearest_k_batch(nodes, queries, k),
+                 {"torch mm + topk": lambda: torch_knn_mm(nodes, queries, k), "torch cdist(exact) + topk": lambda: torch_knn_diff(nodes, queries, k)})
+    flops = 42.0 * Q * N / (ms * 1e-3)
+    print("    achieved %.2f TFLOP/s FP64 (42 Q N flop per call) = %.1f %% of the 78.6 TFLOP/s vector peak" % (flops / 1e12, 100 * flops / 78.6e12))
+    # single-query latency
+    for Nn in (65536, 1 << 20):
+        nd, q1 = big[:Nn].contiguous(), queries[:1].contiguous()
+        print(_lib.describe(ctx.handle, _lib.CALL_KNN, 1))
+        compare("k-NN  N=%d Q=1 k=%d" % (Nn, k), lambda: c.nearest_k_batch(nd, q1, k),
+                {"torch diff + topk": lambda: torch.topk(((nd - q1) ** 2).sum(1), k, largest=False), "torch mv + topk": lambda: torch_knn_mm(nd, q1, k)})
+    # connect
+    nodes, queries = big[:16384].contiguous(), big[1 << 20: (1 << 20) + 3277].contiguous()
+    for mode in (0, 1):
+        c.setJacobianMode(mode)
+        idx, _ = c.nearest_k_batch(nodes, queries, k)
+        frm = nodes[idx.reshape(-1).long()].contiguous()
+        to = queries.repeat_interleave(k, dim=0).contiguous()
+
+        def parent():
+            _, i = torch_knn_mm(nodes, queries, k)
+            f = nodes[i.reshape(-1)]
+            t_ = queries.repeat_interleave(k, dim=0)
+            return c.discrete_geodesic_batch(f, t_, 16, check_target=True, want_carry=True, round_budget=128)
+
+        t = alternate({"traversal alone": lambda: c.discrete_geodesic_batch(frm, to, 16, check_target=True, want_carry=True, round_budget=128)}, reps)
+        print("connect (%s)  N=%d Q=%d k=%d: %d edges, lists of 16, round budget 128" % ("analytic" if mode else "FD", nodes.shape[0], queries.shape[0], k, frm.shape[0]))
+        print("    %-28s %s" % ("traversal alone", _stat(t["traversal alone"])))
+        mo = compare("  connect call against torch k-NN + gather + ccmp_geodesic_batch_ex",
+                     lambda: c.connect_batch(nodes, queries, k, check_target=True, max_states=16, round_budget=128), {"torch k-NN + gather + ex": parent})
+        print("    choosing the pairs costs %.4f ms (connect call - traversal alone, medians)" % (mo - np.median(t["traversal alone"])))
+    c.setJacobianMode(0)
+    print("VERDICT " + ("all not slower" if all(ok for _, ok in verdicts) else "SLOWER: " + "; ".join(t for t, ok in verdicts if not ok)))
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -578,7 +696,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, run)}
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
     cmds[sys.argv[1]](sys.argv[2:])
