@@ -13,4 +13,6 @@ from .space import (check_motion, format_graphml, format_graphviz, format_path_m
 
 from .scene import ProxyScene, ProxyValidityChecker, default_allowed, skeleton_spheres  # noqa: F401
 
+from .roadmap import Roadmap, pose_distance, pose_from_t_wo  # noqa: F401
+
 __version__ = "0.6.0"

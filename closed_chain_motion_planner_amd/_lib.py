@@ -73,6 +73,10 @@ EXPORTS = [
     "ccmp_scene_create", "ccmp_scene_destroy", "ccmp_scene_num_pairs", "ccmp_clearance_batch", "ccmp_clearance_host",
     "ccmp_geodesic_scene_batch", "ccmp_geodesic_scene_host",
     "ccmp_knn_batch", "ccmp_knn_host", "ccmp_connect_batch", "ccmp_connect_host",
+    "ccmp_pose_distance", "ccmp_pose_from_t_wo",
+    "ccmp_roadmap_create", "ccmp_roadmap_destroy", "ccmp_roadmap_size", "ccmp_roadmap_reserve", "ccmp_roadmap_append", "ccmp_roadmap_set_joints",
+    "ccmp_roadmap_truncate", "ccmp_roadmap_read", "ccmp_roadmap_knn", "ccmp_roadmap_connect",
+    "ccmp_roadmap_append_host", "ccmp_roadmap_set_joints_host", "ccmp_roadmap_read_host", "ccmp_roadmap_knn_host", "ccmp_roadmap_connect_host",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -175,6 +179,25 @@ def lib():
                                 vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "ccmp_connect_host": ([vp, pp, vp, C.c_double, dp, C.c_size_t, dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int32), u8p, dp], C.c_int),
+        "ccmp_pose_distance": ([dp, dp], C.c_double),
+        "ccmp_pose_from_t_wo": ([dp, dp], None),
+        "ccmp_roadmap_create": ([vp, C.c_size_t], vp),
+        "ccmp_roadmap_destroy": ([vp], None),
+        "ccmp_roadmap_size": ([vp], C.c_size_t),
+        "ccmp_roadmap_reserve": ([vp, C.c_size_t], C.c_int),
+        "ccmp_roadmap_append": ([vp, pp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp], C.c_int),
+        "ccmp_roadmap_set_joints": ([vp, C.c_size_t, vp, vp], C.c_int),
+        "ccmp_roadmap_truncate": ([vp, C.c_size_t], C.c_int),
+        "ccmp_roadmap_read": ([vp, C.c_size_t, C.c_size_t, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_knn": ([vp, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_connect": ([vp, pp, vp, C.c_double, C.c_int, vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                  vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_append_host": ([vp, pp, dp, dp, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_roadmap_set_joints_host": ([vp, C.c_size_t, dp], C.c_int),
+        "ccmp_roadmap_read_host": ([vp, C.c_size_t, C.c_size_t, dp, dp], C.c_int),
+        "ccmp_roadmap_knn_host": ([vp, C.c_int, dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int32), dp], C.c_int),
+        "ccmp_roadmap_connect_host": ([vp, pp, vp, C.c_double, C.c_int, dp, dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int32), u8p, dp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -204,6 +227,8 @@ def lib():
 
 CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GEODESIC_BUDGET, CALL_GEODESIC_ANALYTIC = range(6)  # ccmp.h: CCMP_CALL_*
 CALL_GEODESIC_SCENE, CALL_KNN, CALL_CONNECT = 6, 7, 8
+CALL_ROADMAP_KNN, CALL_ROADMAP_CONNECT = 10, 11  # (9 is not assigned)
+METRIC_JOINT, METRIC_OBJECT = 0, 1  # ccmp.h: CCMP_METRIC_*
 KNN_ALL, KNN_NOT_SELF, KNN_EARLIER = 0, 1, 2  # ccmp.h: CCMP_KNN_*
 KNN_MAX_K = 16
 

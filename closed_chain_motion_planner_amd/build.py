@@ -22,7 +22,9 @@ Translation units with deliberately different flags:
   ccmp_kernels_scout.hip -ffast-math                        FP32 iteration-count predictor + ordering (never touches results)
   ccmp_kernels_scene.hip -ffp-contract=off -DCCMP_USE_FMA   proxy-geometry clearance (pre-filter ahead of the host's MoveIt test)
   ccmp_scene.cpp                                            proxy scenes: validation, pair list, launches
-  ccmp_kernels_knn.hip   -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the connection step: FP64 brute-force k nearest neighbours, the gather of ccmp_connect_batch
+  ccmp_kernels_knn.hip   -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the connection step: FP64 brute-force k nearest neighbours on the joint metric and on the
+                         object metric (ccmp_pose.h), the gather of ccmp_connect_batch, the roadmap store's pose_from_joints_kernel
+  ccmp_roadmap.cpp       -ffp-contract=off -DCCMP_USE_FMA   the device-resident roadmap store; ccmp_pose_distance / ccmp_pose_from_t_wo on the host (same bits as the kernels)
 """
 import os
 import shutil
@@ -79,8 +81,10 @@ _UNITS = [
     # the connection step (k nearest neighbours, gather): the scene unit's flags; its lists live in registers and LDS, never in scratch
     ("ccmp_kernels_knn.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     ("ccmp_scene.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # the roadmap store and the host side of the object metric (ccmp_pose.h in the rounding model of the kernels)
+    ("ccmp_roadmap.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():

@@ -269,7 +269,9 @@ int ccmp_function_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *q, d
 
 // workspaces owned by the context: below n units (*cap) *buf is replaced by `bytes` new bytes.  They grow outside any stream
 // capture (the first call at a size is never captured) and after a resident service kernel has left (hipFree waits for it)
-static int grow(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes)
+extern "C++" {
+namespace ccmp_host {
+int grow_buffer(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes)
 {
   if (*cap >= n) return CCMP_OK;
   ccmp_host::quiesce(ctx);
@@ -280,6 +282,9 @@ static int grow(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes)
   *cap = n;
   return CCMP_OK;
 }
+}  // namespace ccmp_host
+}  // extern "C++"
+static int grow(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes) { return ccmp_host::grow_buffer(ctx, buf, cap, n, bytes); }
 static int ensure_pool(ccmp_ctx *ctx, size_t records) { return grow(ctx, (void **)&ctx->pool, &ctx->pool_cap, records, records * kPoolEntry * sizeof(double)); }
 static int ensure_lpt_buffers(ccmp_ctx *ctx, size_t B) // pred u16 | hist 1024 x u32 | order u32 | flags u8 (bulk checkMotion)
 {
@@ -634,8 +639,47 @@ int ccmp_knn_batch(ccmp_ctx *ctx, const double *nodes, size_t N, const double *q
   return knn_launches(ctx, KnnCall{nodes, N, queries, Q, k, mode, self_base, nbr_idx, nbr_dist}, s, (hipStream_t)hip_stream);
 }
 
-// k-NN, gather, the traversal the caller would have run on the gathered pairs (geodesic_common, or the scene variant's entry point,
-// both unchanged), then the empty slots' values.  One stream, no host synchronisation; both workspaces of its own have their size
+// What a connect call (ccmp_connect_batch, ccmp_roadmap_connect) checks besides its k-NN arguments, before anything is launched: the
+// problem, the scene, and the traversal's own arguments (geodesic_args on the workspace's endpoints, which are never NULL).
+extern "C++" {
+namespace ccmp_host {
+int problem_ok(const ccmp_problem *p) { return check_problem(p); }
+int connect_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, int max_states, double *states, int32_t *n_states,
+                   uint8_t *ok, double *carry_out, int round_budget, int check_target)
+{
+  { const int rc = check_problem(p); if (rc != CCMP_OK) return rc; }
+  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  static const double endpoint = 0.0; // stands for the gathered endpoints
+  return geodesic_args(p, &endpoint, &endpoint, max_states, states, n_states, ok, nullptr, carry_out, round_budget, check_target);
+}
+
+// The edges of a connect call whose neighbours are in nbr_idx (on the stream, behind the k-NN): gather into ctx->connect_ws (grown by
+// the caller to E edges before its first launch), the traversal the caller would have run on the gathered pairs (geodesic_common, or
+// the scene variant's entry point, both unchanged), then the empty slots' values.
+int connect_edges(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, const double *queries, size_t Q, int k,
+                  int check_target, int max_states, int round_budget, const int32_t *nbr_idx, double *states, int32_t *n_states, uint8_t *ok,
+                  int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream)
+{
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t E = Q * (size_t)k;
+  double *from = ctx->connect_ws, *to = ctx->connect_ws + E * 14;
+  HIP_TRY(ccmp_launch::connect_gather(nodes, queries, nbr_idx, E, k, from, to, st));
+  int rc;
+  if (scene)
+    rc = ccmp_geodesic_scene_batch(ctx, p, scene, margin, from, to, E, max_states, states, n_states, ok, newton_iters, blocked, nullptr, nullptr,
+                                   carry_out, round_budget, check_target, hip_stream);
+  else {
+    rc = geodesic_common(ctx, p, from, to, E, max_states, states, n_states, ok, newton_iters, nullptr, carry_out, round_budget, check_target, hip_stream);
+    if (rc == CCMP_OK && blocked) HIP_TRY(hipMemsetAsync(blocked, 0, E, st)); // no scene refuses anything
+  }
+  if (rc != CCMP_OK) return rc;
+  HIP_TRY(ccmp_launch::connect_fix(nbr_idx, E, n_states, ok, newton_iters, blocked, carry_out, st));
+  return CCMP_OK;
+}
+}  // namespace ccmp_host
+}  // extern "C++"
+
+// k-NN, then ccmp_host::connect_edges.  One stream, no host synchronisation; both workspaces of its own have their size
 // before the first launch.
 int ccmp_connect_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, size_t N,
                        const double *queries, size_t Q, int k, int mode, size_t self_base, int check_target, int max_states, int round_budget,
@@ -655,21 +699,10 @@ int ccmp_connect_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *s
   const KnnShape s = ccmp_host::plan_knn(ctx, Q, N, k);
   { const int rc = grow(ctx, &ctx->knn_ws, &ctx->knn_ws_cap, s.workspace_bytes, s.workspace_bytes); if (rc != CCMP_OK) return rc; }
   { const int rc = grow(ctx, (void **)&ctx->connect_ws, &ctx->connect_ws_cap, E, E * 28 * sizeof(double)); if (rc != CCMP_OK) return rc; }
-  double *from = ctx->connect_ws, *to = ctx->connect_ws + E * 14;
-  { const int rc = geodesic_args(p, from, to, max_states, states, n_states, ok, nullptr, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; }
+  { const int rc = geodesic_args(p, ctx->connect_ws, ctx->connect_ws + E * 14, max_states, states, n_states, ok, nullptr, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; }
   { const int rc = knn_launches(ctx, KnnCall{nodes, N, queries, Q, k, mode, self_base, nbr_idx, nbr_dist}, s, st); if (rc != CCMP_OK) return rc; }
-  HIP_TRY(ccmp_launch::connect_gather(nodes, queries, nbr_idx, E, k, from, to, st));
-  int rc;
-  if (scene)
-    rc = ccmp_geodesic_scene_batch(ctx, p, scene, margin, from, to, E, max_states, states, n_states, ok, newton_iters, blocked, nullptr, nullptr,
-                                   carry_out, round_budget, check_target, hip_stream);
-  else {
-    rc = geodesic_common(ctx, p, from, to, E, max_states, states, n_states, ok, newton_iters, nullptr, carry_out, round_budget, check_target, hip_stream);
-    if (rc == CCMP_OK && blocked) HIP_TRY(hipMemsetAsync(blocked, 0, E, st)); // no scene refuses anything
-  }
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(ccmp_launch::connect_fix(nbr_idx, E, n_states, ok, newton_iters, blocked, carry_out, st));
-  return CCMP_OK;
+  return ccmp_host::connect_edges(ctx, p, scene, margin, nodes, queries, Q, k, check_target, max_states, round_budget, nbr_idx, states, n_states, ok,
+                                  newton_iters, blocked, carry_out, hip_stream);
 }
 
 int ccmp_is_satisfied_batch(ccmp_ctx *ctx, const ccmp_problem *p, const double *q, uint8_t *ok, size_t B, void *hip_stream)

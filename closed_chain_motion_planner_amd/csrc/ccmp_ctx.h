@@ -150,6 +150,17 @@ inline unsigned int *arm_done_word(ccmp_ctx *ctx, size_t B)
   ctx->done_armed = true;
   return (unsigned int *)((char *)ctx->pin_dev + kPinData);
 }
+/* a workspace of the context (or of an object on it) at `n` units / `bytes` before anything that uses it is in flight: stops a resident
+ * service kernel first (hipFree waits for the whole device), frees and reallocates; a no-op while *cap >= n (ccmp_api.cpp) */
+int grow_buffer(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes);
+/* check_problem of ccmp_api.cpp; what a connect call checks before its first launch; its gather -> traversal -> fix chain on the
+ * neighbours in nbr_idx (ctx->connect_ws holds Q * k edges by then) — shared by ccmp_connect_batch and ccmp_roadmap_connect */
+int problem_ok(const ccmp_problem *p);
+int connect_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, int max_states, double *states, int32_t *n_states,
+                   uint8_t *ok, double *carry_out, int round_budget, int check_target);
+int connect_edges(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, const double *queries, size_t Q, int k,
+                  int check_target, int max_states, int round_budget, const int32_t *nbr_idx, double *states, int32_t *n_states, uint8_t *ok,
+                  int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream);
 /* device staging of the *_host conveniences, grown on demand */
 int ensure_stage(ccmp_ctx *ctx, size_t bytes);
 /* the device-visible alias of a caller's host range if all of it is page-locked and mapped (hipHostMalloc,

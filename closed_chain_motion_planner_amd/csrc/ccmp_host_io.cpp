@@ -522,7 +522,7 @@ int ccmp_geodesic_scene_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sc
   return io.finish();
 }
 
-// the connection step on host buffers: nodes and queries are uploaded per call (there is no device-resident node store)
+// the connection step on host buffers: nodes and queries are uploaded per call (the device-resident store: ccmp_roadmap.cpp)
 int ccmp_knn_host(ccmp_ctx *ctx, const double *nodes, size_t N, const double *queries, size_t Q, int k, int mode, size_t self_base,
                   int32_t *nbr_idx, double *nbr_dist)
 {

@@ -24,10 +24,22 @@
 //                     is one partition (the scan kernels then write the result themselves).
 //   connect_gather_kernel / connect_fix_kernel   edge e = q * k + r: from = nodes[nbr_idx[q][r]], to = queries[q]; an empty
 //                     slot gets from = to (a traversal that ends before its first Newton round) and is overwritten afterwards.
+//
+// The same two layouts on the reference's own tree metric, the SE3 distance between object poses (ccmp_pose.h; the roadmap store of
+// ccmp_roadmap.cpp keeps one 64-byte pose row per node):
+//   knn_pose_many_kernel  one query per thread, LDS tiles of 512 poses (32 KB).  distance = |dp| + rot with rot >= 0, so
+//                         |dp|^2 < the list's bound is still a necessary condition for entry: a node costs two ds_read_b128 (x y | z qx),
+//                         three subtractions and three FMAs; only a candidate reads the other half of its row and pays for the square
+//                         root, the quaternion dot product and the atan.
+//   knn_pose_few_kernel   one block per (partition, query), four 16-byte global loads per node.
+//   knn_merge_kernel      unchanged: its lists do not depend on the metric.
+//   pose_from_joints_kernel / pose_store_kernel / joints_fill_nan_kernel   what an append to the store runs (derived poses; given
+//                         poses with the pad zeroed; the NaN joint rows of a pose-only vertex).
 #include <hip/hip_runtime.h>
 
 #include "ccmp_detmath.h"
 #include "ccmp_launch.h"
+#include "ccmp_pose.h"
 
 namespace {
 
@@ -292,6 +304,148 @@ hipError_t knn_launch(const ccmp_launch::KnnCall &c, const ccmp_launch::KnnShape
   return hipGetLastError();
 }
 
+// ---- the object metric (ccmp_pose.h) --------------------------------------------------------------------------------------------
+constexpr int kPoseTile = ccmp_launch::kKnnPoseTile;
+static_assert(kPoseTile % kRows == 0, "knn_pose_many_kernel reads its tile kRows rows at a time");
+
+// one node whose squared translation d2 passed no test yet, scanned in increasing index; lo = (z, qx), and row[2], row[3] = the
+// rest of its quaternion.  fl(|dp| + rot) >= |dp| (rot >= 0, rounding is monotone), so List::bound filters on d2 as it does for the
+// joint metric; a NaN d2 fails both tests, a NaN in the quaternions gives a NaN distance, which is below nothing.
+template <int KC>
+__device__ __forceinline__ void offer_pose(List<KC> &L, double d2, int idx, const double (&x)[7], double qx, const double2 *row)
+{
+  if (d2 < L.bound || d2 == __builtin_inf()) {
+    const double2 v2 = row[2], v3 = row[3];
+    const double dist = ccmp_sqrt(d2) + ccmp_pose_rot(x[3], x[4], x[5], x[6], qx, v2.x, v2.y, v3.x);
+    if (key_less(dist, idx, L.d[KC - 1], L.i[KC - 1])) L.insert(dist, idx);
+  }
+}
+
+template <int KC>
+__global__ __launch_bounds__(kThreads) void knn_pose_many_kernel(const double *__restrict__ nodes, unsigned int N, const double *__restrict__ queries,
+                                                                 unsigned long long Q, int mode, unsigned long long self_base, unsigned int part,
+                                                                 KnnOut o)
+{
+  __shared__ __attribute__((aligned(16))) double tile[kPoseTile * 8];
+  const int t = threadIdx.x, p = blockIdx.y;
+  const unsigned long long q = (unsigned long long)blockIdx.x * kThreads + t;
+  const bool live = q < Q;
+  double x[7];
+#pragma unroll
+  for (int c = 0; c < 7; c++) x[c] = live ? queries[q * 8 + c] : 0.0;
+  unsigned int lim, excl;
+  eligibility(mode, self_base + q, N, lim, excl);
+  if (!live) lim = 0;
+  List<KC> L;
+  L.clear();
+  const unsigned int lo = (unsigned int)p * part, hi = lo + part < N ? lo + part : N;
+  if (lim > hi) lim = hi;
+  for (unsigned int base = lo; base < hi; base += kPoseTile) {
+    const unsigned int n = hi - base < (unsigned int)kPoseTile ? hi - base : (unsigned int)kPoseTile;
+    __syncthreads(); // the previous tile has been read by everyone
+    {
+      const double2 *src = reinterpret_cast<const double2 *>(nodes) + (size_t)base * 4; // the store's rows: 64 bytes, 16-byte aligned
+      double2 *dst = reinterpret_cast<double2 *>(tile);
+      for (unsigned int w = t; w < n * 4; w += kThreads) dst[w] = src[w]; // n <= kPoseTile: inside the tile; base + n <= N: inside the store
+    }
+    __syncthreads();
+    // rows past n (the range's last tile) hold stale or unwritten LDS words, inside the array, and are never offered: lim <= hi
+    for (unsigned int r = 0; r < n; r += kRows) {
+      double d2[kRows], qx[kRows];
+#pragma unroll
+      for (int u = 0; u < kRows; u++) {
+        const double2 *row = reinterpret_cast<const double2 *>(tile + (r + u) * 8);
+        const double2 v0 = row[0], v1 = row[1];
+        d2[u] = ccmp_pose_d2(x[0], x[1], x[2], v0.x, v0.y, v1.x);
+        qx[u] = v1.y;
+      }
+#pragma unroll
+      for (int u = 0; u < kRows; u++) {
+        const unsigned int j = base + r + u;
+        if (j < lim && j != excl) offer_pose<KC>(L, d2[u], (int)j, x, qx[u], reinterpret_cast<const double2 *>(tile + (r + u) * 8));
+      }
+    }
+  }
+  if (live) emit<KC>(o, q, p, L.d, L.i);
+}
+
+template <int KC>
+__global__ __launch_bounds__(kThreads) void knn_pose_few_kernel(const double *__restrict__ nodes, unsigned int N, const double *__restrict__ queries,
+                                                                int mode, unsigned long long self_base, unsigned int part, KnnOut o)
+{
+  __shared__ double ld[kThreads * KC];
+  __shared__ int li[kThreads * KC];
+  const int t = threadIdx.x, p = blockIdx.x;
+  const unsigned long long q = blockIdx.y;
+  double x[7];
+#pragma unroll
+  for (int c = 0; c < 7; c++) x[c] = queries[q * 8 + c];
+  unsigned int lim, excl;
+  eligibility(mode, self_base + q, N, lim, excl);
+  List<KC> L;
+  L.clear();
+  const unsigned int lo = (unsigned int)p * part, hi = lo + part < N ? lo + part : N;
+  for (unsigned int j = lo + t; j < hi; j += kThreads) {
+    const double2 *row = reinterpret_cast<const double2 *>(nodes) + (size_t)j * 4;
+    const double2 v0 = row[0], v1 = row[1];
+    const double d2 = ccmp_pose_d2(x[0], x[1], x[2], v0.x, v0.y, v1.x);
+    if (j < lim && j != excl) offer_pose<KC>(L, d2, (int)j, x, v1.y, row);
+  }
+#pragma unroll
+  for (int s = 0; s < KC; s++) { ld[t * KC + s] = L.d[s]; li[t * KC + s] = L.i[s]; }
+  block_merge<KC, kThreads>(ld, li, t, L.d, L.i);
+  if (t == 0) emit<KC>(o, q, p, L.d, L.i);
+}
+
+// the pose of a joint state: compute_t_wo of the left arm (t_wo_kernel's arithmetic), then Eigen's Quaterniond(Matrix3d)
+__global__ __launch_bounds__(64) void pose_from_joints_kernel(const ccmp_consts K, const double *__restrict__ joints, double *__restrict__ poses, size_t n)
+{
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double x[7], Rw[9], pw[3], T[12], pose[8];
+#pragma unroll
+  for (int e = 0; e < 7; e++) x[e] = joints[i * 14 + e];
+  ccmp::fk_arm(K, 0, x, Rw, pw);
+  ccmp::mul33(Rw, K.t_o7i_R, T);
+  T[9] = pw[0]; T[10] = pw[1]; T[11] = pw[2];
+  ccmp::mulvec_acc(Rw, K.t_o7i_p, T + 9);
+  ccmp_pose_of_t_wo(T, pose);
+#pragma unroll
+  for (int c = 0; c < 8; c++) poses[i * 8 + c] = pose[c];
+}
+
+// the caller's poses into the store: seven values and a zero pad
+__global__ __launch_bounds__(256) void pose_store_kernel(const double *__restrict__ src, double *__restrict__ dst, size_t n)
+{
+  const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (w >= n * 8) return;
+  dst[w] = (w & 7) == 7 ? 0.0 : src[w];
+}
+
+// the joint rows of pose-only vertices: NaN, never a neighbour under the joint metric
+__global__ __launch_bounds__(256) void joints_fill_nan_kernel(double *__restrict__ dst, size_t words)
+{
+  const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (w < words) dst[w] = __builtin_nan("");
+}
+
+template <int KC>
+hipError_t knn_pose_launch(const ccmp_launch::KnnCall &c, const ccmp_launch::KnnShape &s, double *ws_d, int32_t *ws_i, hipStream_t st)
+{
+  const KnnOut o{c.nbr_idx, c.nbr_dist, ws_d, ws_i, c.k, (int)s.partitions};
+  if (s.few)
+    hipLaunchKernelGGL(knn_pose_few_kernel<KC>, dim3(s.partitions, (unsigned int)c.Q), dim3(kThreads), 0, st, c.nodes, (unsigned int)c.N, c.queries, c.mode,
+                       (unsigned long long)c.self_base, s.part, o);
+  else
+    hipLaunchKernelGGL(knn_pose_many_kernel<KC>, dim3(s.groups, s.partitions), dim3(kThreads), 0, st, c.nodes, (unsigned int)c.N, c.queries,
+                       (unsigned long long)c.Q, c.mode, (unsigned long long)c.self_base, s.part, o);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || s.partitions == 1) return e;
+  if (s.partitions <= 64) hipLaunchKernelGGL((knn_merge_kernel<KC, 64>), dim3((unsigned int)c.Q), dim3(64), 0, st, o);
+  else hipLaunchKernelGGL((knn_merge_kernel<KC, 256>), dim3((unsigned int)c.Q), dim3(256), 0, st, o);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 namespace ccmp_launch {
@@ -308,6 +462,37 @@ hipError_t knn(const KnnCall &c, const KnnShape &s, void *workspace, hipStream_t
     case 16: return knn_launch<16>(c, s, ws_d, ws_i, st);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t knn_pose(const KnnCall &c, const KnnShape &s, void *workspace, hipStream_t st)
+{
+  double *ws_d = (double *)workspace; // as knn(): distances [Q][P][KC], then indices
+  int32_t *ws_i = (int32_t *)(ws_d + c.Q * (size_t)s.partitions * (size_t)s.kc);
+  switch (s.kc) {
+    case 1: return knn_pose_launch<1>(c, s, ws_d, ws_i, st);
+    case 4: return knn_pose_launch<4>(c, s, ws_d, ws_i, st);
+    case 8: return knn_pose_launch<8>(c, s, ws_d, ws_i, st);
+    case 16: return knn_pose_launch<16>(c, s, ws_d, ws_i, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t pose_from_joints(const ccmp_consts *K, const double *joints, double *poses, size_t n, hipStream_t st)
+{
+  hipLaunchKernelGGL(pose_from_joints_kernel, dim3((unsigned int)((n + 63) / 64)), dim3(64), 0, st, *K, joints, poses, n);
+  return hipGetLastError();
+}
+
+hipError_t pose_store(const double *src, double *dst, size_t n, hipStream_t st)
+{
+  hipLaunchKernelGGL(pose_store_kernel, dim3((unsigned int)((n * 8 + 255) / 256)), dim3(256), 0, st, src, dst, n);
+  return hipGetLastError();
+}
+
+hipError_t joints_fill_nan(double *dst, size_t n, hipStream_t st)
+{
+  hipLaunchKernelGGL(joints_fill_nan_kernel, dim3((unsigned int)((n * 14 + 255) / 256)), dim3(256), 0, st, dst, n * 14);
+  return hipGetLastError();
 }
 
 hipError_t connect_gather(const double *nodes, const double *queries, const int32_t *nbr_idx, size_t E, int k, double *from, double *to, hipStream_t st)

@@ -121,6 +121,7 @@ struct KnnCall {
 constexpr int kKnnThreads = 256; // threads per block of every k-NN kernel; queries per block of the many-query kernel
 constexpr int kKnnTile = 256;    // nodes per LDS tile of the many-query kernel (28 KB)
 constexpr int kKnnMaxPartitions = 256; // the merge kernel holds one partition's list per thread
+constexpr int kKnnPoseTile = 512; // poses per LDS tile of the many-query kernel of the object metric (64-byte rows: 32 KB)
 struct KnnShape {
   bool few = false;            // knn_few_kernel: one block per (partition, query), else knn_many_kernel: one query per thread
   unsigned int groups = 0;     // many-query kernel: blocks of kKnnThreads queries
@@ -132,6 +133,13 @@ struct KnnShape {
 
 #pragma GCC visibility push(hidden)
 hipError_t knn(const KnnCall &c, const KnnShape &s, void *workspace, hipStream_t st);
+/* the same call on the object metric: nodes = the store's pose rows [N][8], queries [Q][8]; shape from plan_knn_pose (part a multiple of kKnnPoseTile) */
+hipError_t knn_pose(const KnnCall &c, const KnnShape &s, void *workspace, hipStream_t st);
+/* what an append to the roadmap store runs: poses[i] = pose of joints[i] (t_wo_kernel's arithmetic, then Quaterniond(Matrix3d)); the caller's
+ * poses with the pad zeroed; NaN joint rows */
+hipError_t pose_from_joints(const ccmp_consts *K, const double *joints, double *poses, size_t n, hipStream_t st);
+hipError_t pose_store(const double *src, double *dst, size_t n, hipStream_t st);
+hipError_t joints_fill_nan(double *dst, size_t n, hipStream_t st);
 hipError_t connect_gather(const double *nodes, const double *queries, const int32_t *nbr_idx, size_t E, int k, double *from, double *to, hipStream_t st);
 hipError_t connect_fix(const int32_t *nbr_idx, size_t E, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out,
                        hipStream_t st);

@@ -287,7 +287,7 @@ GeoPlan plan_geodesic(const ccmp_ctx *ctx, size_t E, int round_budget, bool cont
 // 256 per block, the partition's nodes through LDS tiles.  Either way the node range is cut so that the call has about two blocks
 // per CU, into at most kKnnMaxPartitions partitions of at least kKnnMinPart nodes; with more than one partition the lists go through
 // the context's workspace and knn_merge_kernel.  The (distance, index) key makes the result the same for every cut.
-ccmp_launch::KnnShape plan_knn(const ccmp_ctx *ctx, size_t Q, size_t N, int k)
+static ccmp_launch::KnnShape plan_knn_tiled(const ccmp_ctx *ctx, size_t Q, size_t N, int k, size_t tile, size_t min_part)
 {
   ccmp_launch::KnnShape s;
   s.kc = k <= 1 ? 1 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16));
@@ -298,12 +298,21 @@ ccmp_launch::KnnShape plan_knn(const ccmp_ctx *ctx, size_t Q, size_t N, int k)
   if (want < 1) want = 1;
   if (want > (size_t)ccmp_launch::kKnnMaxPartitions) want = ccmp_launch::kKnnMaxPartitions;
   size_t part = (N + want - 1) / want;
-  part = (part + ccmp_launch::kKnnTile - 1) / ccmp_launch::kKnnTile * ccmp_launch::kKnnTile;
-  if (part < kKnnMinPart) part = kKnnMinPart;
+  part = (part + tile - 1) / tile * tile;
+  if (part < min_part) part = min_part;
   s.part = (unsigned int)part;
   s.partitions = N ? (unsigned int)((N + part - 1) / part) : 1u;
   s.workspace_bytes = s.partitions > 1 ? Q * (size_t)s.partitions * (size_t)s.kc * (sizeof(double) + sizeof(int32_t)) : 0;
   return s;
+}
+
+ccmp_launch::KnnShape plan_knn(const ccmp_ctx *ctx, size_t Q, size_t N, int k) { return plan_knn_tiled(ctx, Q, N, k, ccmp_launch::kKnnTile, kKnnMinPart); }
+
+// The same rule for the object metric over a roadmap store's 64-byte pose rows: the kernels are knn_pose_few_kernel / knn_pose_many_kernel,
+// the many-query kernel's tile is kKnnPoseTile poses (the same 32 KB class of LDS as the joint kernel's 28 KB), a partition at least two tiles.
+ccmp_launch::KnnShape plan_knn_pose(const ccmp_ctx *ctx, size_t Q, size_t N, int k)
+{
+  return plan_knn_tiled(ctx, Q, N, k, ccmp_launch::kKnnPoseTile, kKnnPoseMinPart);
 }
 
 }  // namespace ccmp_host
@@ -476,6 +485,34 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
         }
         L.add("; connect_fix_kernel (empty slots)");
         return (int)L.len; // (the traversal's line already says whether a context was given)
+      }
+      break;
+    }
+    case CCMP_CALL_ROADMAP_KNN:
+    case CCMP_CALL_ROADMAP_CONNECT: {
+      // as CCMP_CALL_KNN: n = the queries, a store of kKnnDescribeNodes nodes and the reference's five neighbours assumed; the object
+      // metric (the joint metric over a store runs CCMP_CALL_KNN's plan on the store's joint rows)
+      constexpr size_t kKnnDescribeNodes = 65536;
+      const ccmp_launch::KnnShape s = plan_knn_pose(ctx, n, kKnnDescribeNodes, kConnectDescribeK);
+      L.add("%s Q=%zu, object metric (N=%zu, k=%d assumed): ", call_kind == CCMP_CALL_ROADMAP_KNN ? "roadmap_knn" : "roadmap_connect", n, kKnnDescribeNodes,
+            kConnectDescribeK);
+      if (s.few)
+        L.add("partitioned form: knn_pose_few_kernel x %zu blocks (one per partition and query, %d threads striding over %u poses)",
+              (size_t)s.partitions * s.groups, ccmp_launch::kKnnThreads, s.part);
+      else
+        L.add("knn_pose_many_kernel x %zu blocks (one query per thread, %d per block; LDS tiles of %d poses)", (size_t)s.partitions * s.groups,
+              ccmp_launch::kKnnThreads, ccmp_launch::kKnnPoseTile);
+      L.add(", %u partitions of %u poses", s.partitions, s.part);
+      if (s.partitions > 1) L.add(", then knn_merge_kernel x %zu blocks (workspace %zu bytes)", n, s.workspace_bytes);
+      L.add(", lists of %d [few_queries<=%zu min_partition=%u max_partitions=%d]; joint metric: the knn line on the store's joint rows", s.kc, kKnnFewMax,
+            kKnnPoseMinPart, ccmp_launch::kKnnMaxPartitions);
+      if (call_kind == CCMP_CALL_ROADMAP_CONNECT) {
+        L.add("; pose_from_joints_kernel where the query poses are derived; connect_gather_kernel; then, for %zu edges, ", n * kConnectDescribeK);
+        char sub[2048];
+        if (ccmp_ctx_describe(ctx_in, CCMP_CALL_GEODESIC, n * kConnectDescribeK, sub, sizeof sub) > 0)
+          for (size_t at = 0, len = strlen(sub); at < len; at += 256) L.add("%.256s", sub + at);
+        L.add("; connect_fix_kernel (empty slots)");
+        return (int)L.len;
       }
       break;
     }

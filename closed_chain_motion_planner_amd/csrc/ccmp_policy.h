@@ -71,6 +71,10 @@ int plan_geodesic_scene(const ccmp_ctx *ctx, size_t E, bool analytic);
 constexpr size_t kKnnFewMax = 8;          // up to this many queries: one block per (partition, query)
 constexpr unsigned int kKnnMinPart = 1024; // nodes per partition at least (four tiles)
 ccmp_launch::KnnShape plan_knn(const ccmp_ctx *ctx, size_t Q, size_t N, int k);
+/* the same on the object metric over a roadmap store's pose rows (ccmp_roadmap_knn / ccmp_roadmap_connect with CCMP_METRIC_OBJECT):
+ * the same rule on tiles of kKnnPoseTile poses.  A function of Q, N, k and the CU count alone. */
+constexpr unsigned int kKnnPoseMinPart = 1024; // poses per partition at least (two tiles)
+ccmp_launch::KnnShape plan_knn_pose(const ccmp_ctx *ctx, size_t Q, size_t N, int k);
 constexpr int kConnectDescribeK = 5;      // ccmp_ctx_describe(CCMP_CALL_CONNECT): the reference's DEFAULT_NEAREST_NEIGHBORS
 
 /* ccmp_ctx_set_option behind the options ccmp_api.cpp handles itself ("resident"): the option table */

@@ -252,7 +252,10 @@ enum {
   CCMP_CALL_GEODESIC_ANALYTIC = 5, /* ccmp_geodesic_batch / _ex with CCMP_JAC_ANALYTIC */
   CCMP_CALL_GEODESIC_SCENE = 6,    /* ccmp_geodesic_scene_batch, both Jacobian modes    */
   CCMP_CALL_KNN = 7,               /* ccmp_knn_batch: n = the queries; 65536 nodes and k = 5 assumed (the shape follows Q, N and the CU count) */
-  CCMP_CALL_CONNECT = 8            /* ccmp_connect_batch: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
+  CCMP_CALL_CONNECT = 8,           /* ccmp_connect_batch: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
+  /* (9 is not assigned: it stays an unknown kind) */
+  CCMP_CALL_ROADMAP_KNN = 10,      /* ccmp_roadmap_knn with CCMP_METRIC_OBJECT: n = the queries; a store of 65536 nodes and k = 5 assumed */
+  CCMP_CALL_ROADMAP_CONNECT = 11   /* ccmp_roadmap_connect with CCMP_METRIC_OBJECT: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
 };
 int ccmp_ctx_describe(const ccmp_ctx *ctx, int call_kind, size_t n, char *buf, size_t cap);
 int ccmp_ctx_device(const ccmp_ctx *ctx);
@@ -508,8 +511,8 @@ int ccmp_geodesic_scene_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sc
  * startgoalMilestone (:392-409, :458-475) or discreteGeodesic(neighbour, new) in growTree (:307-351).
  * Distance: RealVectorStateSpace::distance over the 14 joints exactly as oracle/ccmp_oracle.c: orc_distance states it — the chain
  * dist = fma(diff_i, diff_i, dist), i = 0..13, diff_i = a[i] - b[i], then the correctly rounded square root; not wrap-aware.  THE
- * JOINT TERM ONLY: the reference's tree metric is the compound space's, this distance plus the object's SE3 distance
- * (ConstrainedPlanningCommon.cpp:66-67); the SE3 term is not part of this library.
+ * JOINT TERM ONLY.  The metric the reference's tree actually ranks on is the SE3 distance between the vertices' object poses
+ * (stefanBiPRM.h:194-201): CCMP_METRIC_OBJECT of the roadmap store below.
  * Ranking of the eligible nodes of a query: ascending by (distance as returned, i.e. after the square root; node index) — equal
  * distances go to the lower index, also where two different squared sums round to one distance.  Eligible: a node whose distance
  * to the query is not NaN (a NaN on either side: never a neighbour), and by mode
@@ -520,9 +523,9 @@ int ccmp_geodesic_scene_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sc
  * nbr_idx[q][r] / nbr_dist[q][r] (nullable), r = 0..k-1: the r-th neighbour; fewer than k eligible nodes leave the remaining slots
  * idx = -1, dist = +inf.  1 <= k <= CCMP_KNN_MAX_K, N < 2^31 (N == 0 is allowed: every slot empty), Q < 2^31; Q == 0 returns CCMP_OK and
  * touches nothing.  The result is a function of the arguments alone: the launch shape (csrc/ccmp_policy.cpp: plan_knn, from Q, N and
- * the CU count; no option) never changes it.  `nodes` is read per call: there is no device-resident, appendable node store, and the
- * host form uploads the nodes every time.  Device pointers, asynchronous on hip_stream, capturable (after one eager call at that
- * size); the resident service does not serve these calls. */
+ * the CU count; no option) never changes it.  `nodes` is read per call and the host form uploads the nodes every time; a roadmap that
+ * grows by one vertex per query belongs in the device-resident store below (ccmp_roadmap_*).  Device pointers, asynchronous on
+ * hip_stream, capturable (after one eager call at that size); the resident service does not serve these calls. */
 #define CCMP_KNN_MAX_K 16
 enum { CCMP_KNN_ALL = 0, CCMP_KNN_NOT_SELF = 1, CCMP_KNN_EARLIER = 2 };
 int ccmp_knn_batch(ccmp_ctx *ctx, const double *nodes, size_t N, const double *queries, size_t Q, int k, int mode, size_t self_base,
@@ -549,6 +552,80 @@ int ccmp_connect_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *sc
                       const double *queries, size_t Q, int k, int mode, size_t self_base, int check_target, int max_states, int round_budget,
                       int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
                       double *carry_out);
+
+/* ---- the device-resident roadmap store, and the planner's own tree metric ------------------------------------------------------------ */
+/* The reference's tree_ ranks on obj_space_->distance(components[1], components[1]) (stefanBiPRM.h:194-201; the joint-space line above it
+ * is commented out): OMPL's SE3StateSpace::distance between the OBJECT POSES of two vertices, with the default weights 1 and 1,
+ *     d(a, b) = |dp| + rot(a, b),   rot = 0 if |qa . qb| > 1 - 1e-9 (SO3StateSpace's MAX_QUATERNION_NORM_ERROR), else acos(|qa . qb|),
+ * in the rounding model of the rest of the library (csrc/ccmp_pose.h: FMA chains over x, y, z and over qx, qy, qz, qw, the correctly
+ * rounded square root, acos(dq) = atan2(sqrt(1 - dq^2), dq)); quaternions are not normalised, a NaN anywhere gives NaN.
+ * A pose is 8 doubles: x y z qx qy qz qw pad; public pose arrays are [n][8]; the pad is written as 0 and never read.
+ * The pose of a joint state (stefanBiPRM.cpp:338, utils.h:37-46) = ccmp_compute_t_wo_batch of the left arm, then Eigen's
+ * Quaterniond(Matrix3d) (the trace / largest-diagonal branches of oracle/ccmp_oracle.c: R_to_quat, bit for bit).
+ * The two functions below are pure host code: no device, never CCMP_ENODEV (the planner's single-pair distances,
+ * stefanBiPRM.cpp:340-341,635). */
+double ccmp_pose_distance(const double a[8], const double b[8]);
+void ccmp_pose_from_t_wo(const double t_wo[12], double pose[8]);
+
+/* The store: the joints [14] and the object pose [8] of every roadmap vertex, resident on the context's device, so that a planner that
+ * appends one vertex and queries uploads one vertex.  Indices are positions: an append takes size .. size + Q - 1.  ONLY THE TAIL CAN BE
+ * REMOVED (ccmp_roadmap_truncate: the reference's remove_vertex(t) of the vertex just appended, stefanBiPRM.cpp:353-359); interior
+ * vertices cannot.  The size is host state of the handle: every call below takes effect, for later calls ON THE SAME STREAM, in call
+ * order; calls on different streams are the caller's to order.  One store belongs to one context and to one thread at a time.
+ *   create    capacity_hint = rows allocated up front (0: a small default).  Returns NULL on any failure (ctx NULL, no memory); a store
+ *             needs a context, so where ccmp_ctx_create answers CCMP_ENODEV there is no store.  Every entry below answers a NULL store
+ *             with CCMP_ENODEV on a machine without a HIP device and with CCMP_EINVAL otherwise.
+ *   destroy   quiesces the context first, as scenes do; the context must outlive the store or be destroyed first with its service off.
+ *   reserve   room for n vertices in all, now (synchronous: it waits for the device when it has to move the rows); after it, appends up to n
+ *             never grow.
+ *   append    joints [Q][14] and / or poses [Q][8], device pointers.  poses == NULL: derived on the device from the joints and `p`
+ *             (pose_from_joints_kernel).  joints == NULL (poses given): growTree's pose-only vertex (stefanBiPRM.cpp:283-292) — its joint
+ *             row is NaN, so no joint-metric query ever returns it, until ccmp_roadmap_set_joints fills it in.  Both NULL: CCMP_EINVAL.
+ *             p may be NULL when poses are given.  *first_index (nullable) = the first new index.  Asynchronous on hip_stream and
+ *             capturable WHILE THE CAPACITY HOLDS; an append beyond it grows the store: a new allocation of at least twice the size, a
+ *             device-to-device copy and ONE synchronisation of hip_stream before the old block is freed — the only non-asynchronous case
+ *             (never under capture: reserve first).
+ *   set_joints  joints[14] (device pointer) into row `index` < size, asynchronous on hip_stream; the pose row is not touched.
+ *             ccmp_roadmap_set_joints_host takes a host pointer (growTree hands over the result of its IK) and is synchronous.
+ *   truncate  size = n <= size; keeps the capacity.
+ *   read      rows first .. first + count - 1 into joints_out [count][14] / poses_out [count][8] (device pointers, either may be NULL).
+ *   knn       the k nearest vertices of each query.  CCMP_METRIC_JOINT: queries [Q][14], the kernels of ccmp_knn_batch over the store's
+ *             joint rows — bit-identical to ccmp_knn_batch on the same rows.  CCMP_METRIC_OBJECT: queries [Q][8] poses, the distance
+ *             above (knn_pose_few_kernel / knn_pose_many_kernel; shape: csrc/ccmp_policy.cpp: plan_knn_pose, from Q, N and the CU count
+ *             only).  Everything else as ccmp_knn_batch: modes and self_base, ranking by (distance, index), NaN never a neighbour,
+ *             idx = -1 / dist = +inf in empty slots, 1 <= k <= CCMP_KNN_MAX_K, a result that no launch shape changes.
+ *   connect   neighbours from the store by `metric`, then edge e = q * k + r from the store's JOINTS at nbr_idx[q][r] to query_joints[q]
+ *             through the unchanged gather -> traversal -> fix chain of ccmp_connect_batch: outputs, empty slots and continuation rules
+ *             as documented there.  CCMP_METRIC_OBJECT ranks on query_poses [Q][8], or with query_poses == NULL on the poses derived
+ *             from query_joints.  A neighbour chosen by the object metric whose joint row is still NaN (a pose-only vertex) gives an
+ *             edge from NaN joints: fill the joints in first.
+ * The *_host forms take host pointers, are synchronous on the context's own stream and upload only what is new. */
+enum { CCMP_METRIC_JOINT = 0, CCMP_METRIC_OBJECT = 1 };
+typedef struct ccmp_roadmap ccmp_roadmap;
+ccmp_roadmap *ccmp_roadmap_create(ccmp_ctx *ctx, size_t capacity_hint);
+void ccmp_roadmap_destroy(ccmp_roadmap *rm);
+size_t ccmp_roadmap_size(const ccmp_roadmap *rm);
+int ccmp_roadmap_reserve(ccmp_roadmap *rm, size_t n);
+int ccmp_roadmap_append(ccmp_roadmap *rm, const ccmp_problem *p, const double *joints, const double *poses, size_t Q, size_t *first_index,
+                        void *hip_stream);
+int ccmp_roadmap_set_joints(ccmp_roadmap *rm, size_t index, const double *joints, void *hip_stream);
+int ccmp_roadmap_truncate(ccmp_roadmap *rm, size_t n);
+int ccmp_roadmap_read(ccmp_roadmap *rm, size_t first, size_t count, double *joints_out, double *poses_out, void *hip_stream);
+int ccmp_roadmap_knn(ccmp_roadmap *rm, int metric, const double *queries, size_t Q, int k, int mode, size_t self_base, int32_t *nbr_idx,
+                     double *nbr_dist, void *hip_stream);
+int ccmp_roadmap_connect(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, int metric, const double *query_joints,
+                         const double *query_poses, size_t Q, int k, int mode, size_t self_base, int check_target, int max_states, int round_budget,
+                         int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked,
+                         double *carry_out, void *hip_stream);
+int ccmp_roadmap_append_host(ccmp_roadmap *rm, const ccmp_problem *p, const double *joints, const double *poses, size_t Q, size_t *first_index);
+int ccmp_roadmap_set_joints_host(ccmp_roadmap *rm, size_t index, const double *joints);
+int ccmp_roadmap_read_host(ccmp_roadmap *rm, size_t first, size_t count, double *joints_out, double *poses_out);
+int ccmp_roadmap_knn_host(ccmp_roadmap *rm, int metric, const double *queries, size_t Q, int k, int mode, size_t self_base, int32_t *nbr_idx,
+                          double *nbr_dist);
+int ccmp_roadmap_connect_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, int metric,
+                              const double *query_joints, const double *query_poses, size_t Q, int k, int mode, size_t self_base, int check_target,
+                              int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok,
+                              int32_t *newton_iters, uint8_t *blocked, double *carry_out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

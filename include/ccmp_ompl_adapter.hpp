@@ -377,14 +377,149 @@ inline bool discreteGeodesic(const Projector &proj, const double *from14, const 
 
 // The reference's connectionStrategy_(m) — a KStrategy over tree_ (src/planner/stefanBiPRM.cpp:292,390,457) — on the joint distance
 // (ccmp_knn_host): the k nearest of N host states for one state, nearest first, ties to the lower index; idx has k entries, -1
-// where fewer than k nodes exist.  The joint term only: the compound space's SE3 term is not part of it.  The
-// nodes are uploaded with every call.
+// where fewer than k nodes exist.  The joint term only, and the nodes are uploaded with every call: ccmp::Roadmap below keeps them on
+// the device and ranks on the reference's own metric, the object's SE3 distance.
 inline void nearestK(const Projector &proj, const double *nodes, size_t N, const double *q14, unsigned k, std::vector<int32_t> *idx)
 {
   idx->assign(k, -1);
   std::lock_guard<std::mutex> hold(proj.mutex());
   check(ccmp_knn_host(proj.ctx(), nodes, N, q14, 1, (int)k, CCMP_KNN_ALL, 0, idx->data(), nullptr), "ccmp_knn_host");
 }
+
+// ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
+// The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
+// rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
+template <class SE3State>
+inline void poseOf(const SE3State &s, double pose[8])
+{
+  pose[0] = s.getX();
+  pose[1] = s.getY();
+  pose[2] = s.getZ();
+  pose[3] = s.rotation().x;
+  pose[4] = s.rotation().y;
+  pose[5] = s.rotation().z;
+  pose[6] = s.rotation().w;
+  pose[7] = 0.0;
+}
+// obj_space_->distance(a, b) of the reference's tree metric (stefanBiPRM.h:194-201) on two such states: host arithmetic, no device
+template <class SE3State>
+inline double poseDistance(const SE3State &a, const SE3State &b)
+{
+  double pa[8], pb[8];
+  poseOf(a, pa);
+  poseOf(b, pb);
+  return ccmp_pose_distance(pa, pb);
+}
+
+// The planner's tree_ on the device: joints and object pose of every vertex, appended one at a time, ranked on the reference's own
+// metric (CCMP_METRIC_OBJECT) or on the joint distance (CCMP_METRIC_JOINT).  Replaces tree_->add (append), tree_->remove of the vertex
+// just added (truncate: ONLY the tail can go) and connectionStrategy_ (nearestK).  The reference queries BEFORE it adds — tree_->add(m)
+// follows the neighbour loop and only on success (stefanBiPRM.cpp:410,476; growTree :361) — so a query never sees the new vertex; a
+// caller that appends first passes mode = CCMP_KNN_NOT_SELF and self_base = the new index, or the vertex is its own nearest neighbour.  Never throws: every verb returns false when it
+// failed and the FIRST failure stays in lastError() / lastErrorMessage() until clearError().  Host pointers throughout; the calls
+// take the Projector's mutex and upload only what is new.  The Projector must outlive the Roadmap.
+class Roadmap {
+public:
+  explicit Roadmap(const Projector &proj, size_t capacity_hint = 0) noexcept : proj_(proj)
+  {
+    std::lock_guard<std::mutex> hold(proj_.mutex());
+    rm_ = ccmp_roadmap_create(proj_.ctx(), capacity_hint);
+    if (!rm_) record(CCMP_EHIP, "ccmp_roadmap_create");
+  }
+  ~Roadmap()
+  {
+    if (!rm_) return;
+    std::lock_guard<std::mutex> hold(proj_.mutex());
+    ccmp_roadmap_destroy(rm_);
+  }
+  Roadmap(const Roadmap &) = delete;
+  Roadmap &operator=(const Roadmap &) = delete;
+
+  size_t size() const noexcept { return ccmp_roadmap_size(rm_); }
+  bool reserve(size_t n) noexcept { return call([&] { return ccmp_roadmap_reserve(rm_, n); }, "ccmp_roadmap_reserve"); }
+  // n vertices: joints [n][14] and / or poses [n][8].  poses == nullptr: derived on the device from the joints; joints == nullptr:
+  // growTree's pose-only vertices (stefanBiPRM.cpp:283-292), no joint-metric neighbour of anything until setJoints.  *first = index of the first
+  bool append(const double *joints, const double *poses, size_t n = 1, size_t *first = nullptr) noexcept
+  {
+    return call([&] { return ccmp_roadmap_append_host(rm_, &proj_.problem(), joints, poses, n, first); }, "ccmp_roadmap_append_host");
+  }
+  bool setJoints(size_t index, const double *joints14) noexcept
+  {
+    return call([&] { return ccmp_roadmap_set_joints_host(rm_, index, joints14); }, "ccmp_roadmap_set_joints_host");
+  }
+  // remove_vertex(t) of the vertex just appended (stefanBiPRM.cpp:353-359): drops the vertices from index n on
+  bool truncate(size_t n) noexcept { return call([&] { return ccmp_roadmap_truncate(rm_, n); }, "ccmp_roadmap_truncate"); }
+  bool read(size_t first, size_t count, double *joints, double *poses) const noexcept
+  {
+    return call([&] { return ccmp_roadmap_read_host(rm_, first, count, joints, poses); }, "ccmp_roadmap_read_host");
+  }
+  // connectionStrategy_(m): the k nearest vertices of ONE query (a pose [8] under CCMP_METRIC_OBJECT, joints [14] under
+  // CCMP_METRIC_JOINT), nearest first, ties to the lower index; idx / dist (nullable) get k entries, -1 / +inf where fewer exist
+  bool nearestK(int metric, const double *query, unsigned k, std::vector<int32_t> *idx, std::vector<double> *dist = nullptr, int mode = CCMP_KNN_ALL,
+                size_t self_base = 0) const noexcept
+  {
+    try {
+      idx->assign(k, -1);
+      if (dist) dist->assign(k, 0.0);
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::nearestK");
+      return false;
+    }
+    return call([&] { return ccmp_roadmap_knn_host(rm_, metric, query, 1, (int)k, mode, self_base, idx->data(), dist ? dist->data() : nullptr); },
+                "ccmp_roadmap_knn_host");
+  }
+  // neighbours and checkMotion (check_target) / discreteGeodesic of all of them towards ONE query in one call (ccmp_roadmap_connect_host):
+  // the raw outputs of ccmp_connect_host for k edges — n_states, ok [k], states [k][max_states][14].  query_pose may be nullptr (derived).
+  bool connect(int metric, const double *query_joints, const double *query_pose, unsigned k, bool check_target, int max_states, std::vector<int32_t> *idx,
+               std::vector<int32_t> *n_states, std::vector<uint8_t> *ok, std::vector<double> *states, const ccmp_scene *scene = nullptr,
+               double margin = 0.0, int mode = CCMP_KNN_ALL, size_t self_base = 0) const noexcept
+  {
+    try {
+      idx->assign(k, -1);
+      n_states->assign(k, 0);
+      ok->assign(k, 0);
+      states->assign((size_t)k * (size_t)(max_states > 0 ? max_states : 0) * 14, 0.0);
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::connect");
+      return false;
+    }
+    return call([&] {
+      return ccmp_roadmap_connect_host(rm_, &proj_.problem(), scene, margin, metric, query_joints, query_pose, 1, (int)k, mode, self_base, check_target ? 1 : 0,
+                                       max_states, 0, idx->data(), nullptr, states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr);
+    }, "ccmp_roadmap_connect_host");
+  }
+
+  int lastError() const noexcept { return err_code_; }
+  std::string lastErrorMessage() const { return err_what_; }
+  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
+  ccmp_roadmap *handle() const noexcept { return rm_; }
+
+private:
+  template <class F>
+  bool call(F &&body, const char *what) const noexcept
+  {
+    if (!rm_) { record(CCMP_EINVAL, what); return false; }
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(proj_.mutex());
+      rc = body();
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) record(rc, what);
+    return rc == CCMP_OK;
+  }
+  void record(int code, const char *what) const noexcept
+  {
+    if (err_code_ != CCMP_OK) return;
+    err_code_ = code;
+    try { err_what_ = std::string(what) + ": " + ccmp_strerror(code); } catch (...) {}
+  }
+  const Projector &proj_;
+  ccmp_roadmap *rm_ = nullptr;
+  mutable int err_code_ = CCMP_OK;
+  mutable std::string err_what_;
+};
 
 // One planner process, several GPUs (the reference's shape: src/main.cpp is one process): one context per device and an
 // RCCL communicator over them.  sampleProjectSharded / projectSharded spread a batch over the GPUs in contiguous shards,
@@ -923,7 +1058,7 @@ public:
 
   // connectionStrategy_(m) of the reference's planner (a KStrategy over tree_, src/planner/stefanBiPRM.cpp:292,390,457) on the joint
   // distance: the indices into `nodes` of the k nearest to s, nearest first, ties to the lower index; fewer when there are fewer
-  // nodes.  The compound space's SE3 term is not part of the ranking.  false (and *out empty) when the GPU call
+  // nodes.  (The reference's own metric, the object's SE3 distance: the ccmp::Roadmap overloads below.)  false (and *out empty) when the GPU call
   // failed: KinematicChainConstraint::lastError().
   bool nearestK(const std::vector<const ompl::base::State *> &nodes, const ompl::base::State *s, unsigned k, std::vector<unsigned> *out) const
   {
@@ -956,6 +1091,50 @@ public:
     std::vector<const ompl::base::State *> from;
     for (unsigned j : *neighbours) from.push_back(nodes[j]);
     traverseMany(from, s, false, geodesics, reached, true);
+  }
+
+  // The same two on a device-resident ccmp::Roadmap instead of a node vector: only `s` goes up.  pose8 != nullptr ranks on the reference's
+  // own tree metric, the SE3 distance between object poses (ccmp::poseOf of components[1]); pose8 == nullptr on the joint distance of s.
+  // *out = indices into the roadmap.  false when the call failed: Roadmap::lastError().  The reference's order is query, then add
+  // (stefanBiPRM.cpp:390-410): with s already appended at index i pass mode = CCMP_KNN_NOT_SELF, self_base = i, or s is its own neighbour.
+  bool nearestK(ccmp::Roadmap &rm, const ompl::base::State *s, const double *pose8, unsigned k, std::vector<unsigned> *out, int mode = CCMP_KNN_ALL,
+                size_t self_base = 0) const
+  {
+    out->clear();
+    if (k == 0 || rm.size() == 0) return true;
+    double b[14];
+    const auto &sb = *s->as<StateType>();
+    for (int i = 0; i < 14; ++i) b[i] = sb[i];
+    std::vector<int32_t> idx;
+    if (!rm.nearestK(pose8 ? CCMP_METRIC_OBJECT : CCMP_METRIC_JOINT, pose8 ? pose8 : b, k, &idx, nullptr, mode, self_base)) return false;
+    for (int32_t j : idx)
+      if (j >= 0) out->push_back((unsigned)j);
+    return true;
+  }
+  // One k-NN call, then the neighbours' joints come back from the store (k one-row reads), then the traversals and the checker's questions
+  // of connectMilestone above (all neighbours in one launch).  Neighbours and raw traversals in ONE call: ccmp::Roadmap::connect.
+  void connectMilestone(ccmp::Roadmap &rm, const ompl::base::State *s, const double *pose8, unsigned k, std::vector<unsigned> *neighbours,
+                        std::vector<char> *reached, std::vector<std::vector<ompl::base::State *>> *geodesics, int mode = CCMP_KNN_ALL,
+                        size_t self_base = 0) const
+  {
+    if (reached) reached->clear();
+    if (geodesics) geodesics->clear();
+    if (!nearestK(rm, s, pose8, k, neighbours, mode, self_base)) return;
+    std::vector<ompl::base::State *> own;
+    std::vector<const ompl::base::State *> from;
+    bool ok = true;
+    for (unsigned j : *neighbours) {
+      double row[14];
+      if (!(ok = rm.read(j, 1, row, nullptr))) break;
+      ompl::base::State *n = allocState();
+      auto &x = *n->as<StateType>();
+      for (int i = 0; i < 14; ++i) x[i] = row[i];
+      own.push_back(n);
+      from.push_back(n);
+    }
+    if (ok) traverseMany(from, s, false, geodesics, reached, true);
+    else neighbours->clear();
+    for (ompl::base::State *n : own) freeState(n);
   }
 
 private:

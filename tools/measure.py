@@ -17,6 +17,8 @@
     python tools/measure.py soak_resident [N] [--analytic]  N states as single calls through the resident service kernel against the batched kernels
                                                             (--analytic: analytic mode, and five checkMotion edges per request instead of one)
     python tools/measure.py scout                           FP32 scout's predictions against the true iteration counts
+    python tools/measure.py roadmap [reps]                  the device-resident roadmap store: host-form single-query k-NN against ccmp_knn_host, the object
+                                                           metric's many-query kernel against the joint metric's (k = 5 and 16), appends, pose derivation
     python tools/measure.py connect [reps]                  the connection step: ccmp_knn_batch against FP64 torch distances + torch.topk (throughput shape and
                                                            single queries), ccmp_connect_batch against torch k-NN + gather + ccmp_geodesic_batch_ex, both
                                                            contenders alternating in one process, device events, medians with their spread
@@ -626,6 +628,112 @@ def connect(argv):
     print("VERDICT " + ("all not slower" if all(ok for _, ok in verdicts) else "SLOWER: " + "; ".join(t for t, ok in verdicts if not ok)))
 
 
+def roadmap(argv):
+    """the device-resident roadmap store: host-form single-query k-NN against ccmp_knn_host (which uploads the nodes per call), the
+    object metric's many-query kernel against the joint metric's, appends and pose derivation.  Contenders alternate in one process,
+    `reps` rounds behind warm-ups; device events around device forms, the wall clock around host forms; every line states the spread"""
+    from closed_chain_motion_planner_amd import Roadmap
+    from closed_chain_motion_planner_amd._lib import METRIC_JOINT, METRIC_OBJECT
+
+    reps = max(20, int(argv[0])) if argv else 20
+    ctx = Context(0)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    big = valid_states(c, 65536 + 16384)
+    k = 5
+
+    def wall(fns):
+        for fn in fns.values():
+            for _ in range(3):
+                fn()
+        out = {name: [] for name in fns}
+        for _ in range(reps):
+            for name, fn in fns.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                out[name].append((time.perf_counter() - t0) * 1e3)
+        return out
+
+    def show(title, t):
+        print(title)
+        for name, ms in t.items():
+            print("    %-44s %s" % (name, _stat(ms)))
+        sys.stdout.flush()
+
+    # 1. the planner's query: one state, host pointers, k = 5
+    verdict = []
+    L, dp, ip = _lib.lib(), C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    for N in (4096, 65536):
+        nodes = big[:N].contiguous()
+        nodes_h, q_h = nodes.cpu().numpy(), big[65536:65537].cpu().numpy()
+        rm = Roadmap(c, N)
+        rm.append(nodes)
+        qp_h = Roadmap(c, 4)
+        qp_h.append(big[65536:65537].contiguous())
+        qpose = qp_h.read(host=True)[1]
+        idx, dist = np.zeros((1, k), np.int32), np.zeros((1, k))
+        t = wall({
+            "ccmp_knn_host (uploads the nodes)": lambda: _lib.check(L.ccmp_knn_host(ctx.handle, nodes_h.ctypes.data_as(dp), N, q_h.ctypes.data_as(dp), 1, k, 0, 0,
+                                                                                    idx.ctypes.data_as(ip), dist.ctypes.data_as(dp)), "ccmp_knn_host"),
+            "ccmp_roadmap_knn_host, joint metric": lambda: rm.nearest_k(q_h, k, METRIC_JOINT),
+            "ccmp_roadmap_knn_host, object metric": lambda: rm.nearest_k(qpose, k, METRIC_OBJECT),
+        })
+        show("host-form single-query k-NN  N=%d k=%d (wall clock)" % (N, k), t)
+        names = list(t)
+        base, spread = np.median(t[names[0]]), np.max(t[names[0]]) - np.min(t[names[0]])
+        for n in names[1:]:
+            ok = np.median(t[n]) <= base + spread
+            verdict.append(ok)
+            print("    -> %s / ccmp_knn_host = %.3f (%s)" % (n, np.median(t[n]) / base, "not slower" if ok else "SLOWER beyond the spread"))
+    # 2. the many-query kernels, both metrics, k = 5 and k = 16 (does the cheap pre-filter hold up with long lists?)
+    N, Q = 65536, 16384
+    nodes, queries = big[:N].contiguous(), big[65536:].contiguous()
+    rm = Roadmap(c, N)
+    rm.append(nodes)
+    qrm = Roadmap(c, Q)
+    qrm.append(queries)
+    qposes = qrm.read()[1]
+    print(_lib.describe(ctx.handle, _lib.CALL_ROADMAP_KNN, Q))
+    print(_lib.describe(ctx.handle, _lib.CALL_KNN, Q))
+    for kk in (5, 16):
+        t = alternate({"knn_pose_many (object metric)": lambda: rm.nearest_k(qposes, kk, METRIC_OBJECT),
+                       "knn_many (joint metric, same store)": lambda: rm.nearest_k(queries, kk, METRIC_JOINT),
+                       "ccmp_knn_batch (joint metric, caller's nodes)": lambda: c.nearest_k_batch(nodes, queries, kk)}, reps)
+        show("k-NN  N=%d Q=%d k=%d (device events, scan + merge)" % (N, Q, kk), t)
+        mo, mj = np.median(t["knn_pose_many (object metric)"]), np.median(t["knn_many (joint metric, same store)"])
+        print("    -> object / joint = %.3f; object metric: %.1f G pairs/s, %.2f TFLOP/s FP64 on the 12 flop of the pre-filter alone" %
+              (mo / mj, Q * N / (mo * 1e-3) / 1e9, 12.0 * Q * N / (mo * 1e-3) / 1e12))
+    # 3. appends
+    row = big[:1].contiguous()
+    small = Roadmap(c, 1 << 16)
+    small.append(big[:4096].contiguous())
+
+    def append_no_growth():
+        small.truncate(4096)
+        small.append(row)
+
+    def append_growth():
+        g = Roadmap(c, 4096)
+        g.append(big[:4096].contiguous())
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        g.append(row)  # 4096 -> 8192 rows: allocation, device-to-device copy, one stream synchronisation
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) * 1e3
+        g.close()
+        return dt
+
+    t = wall({"append of 1 row, capacity holds (host time, incl. sync)": lambda: (append_no_growth(), torch.cuda.synchronize())})
+    show("append (wall clock)", t)
+    grow = [append_growth() for _ in range(reps + 3)][3:]
+    print("    %-44s %s" % ("append of 1 row that doubles 4096 rows", _stat(grow)))
+    many = valid_states(c, 262144, seed=0x77)
+    bulk = Roadmap(c, 262144)
+    t = alternate({"append of 262144 rows (copy + pose_from_joints)": lambda: (bulk.truncate(0), bulk.append(many))}, reps)
+    show("pose derivation (device events)", t)
+    print("VERDICT host-form k-NN on the resident store: " + ("not slower" if all(verdict) else "SLOWER in at least one case"))
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -696,7 +804,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, run)}
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
     cmds[sys.argv[1]](sys.argv[2:])
