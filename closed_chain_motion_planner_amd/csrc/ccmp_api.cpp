@@ -359,7 +359,7 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
       // the scout — profiles/r06_head_start_ab.log.)
       if (pl.latency_order) { // longest-predicted-first on the latency kernel alone
         const ScoutBuffers sb(ctx);
-        HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, ctx->queue + kQScout, ctx->num_cus, scout_pair_blocks, nullptr, st));
+        HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, ctx->queue + kQScout, ctx->num_cus * kScoutBlocksPerCu, scout_pair_blocks, nullptr, st));
         lat_order = sb.order;
       }
       HIP_TRY(ccmp_launch::project_flat(c, {.blocks = pl.latency_blocks, .queue = pl.latency_static ? nullptr : q_latency, .pool = ctx->pool,
@@ -375,10 +375,12 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
   ForkJoin fj(ctx, st);
   if (pl.scout) { // FP32 scout pass -> predicted iteration counts -> descending counting sort -> processing order
     const ScoutBuffers sb(ctx);
-    // one 256-thread block per CU, 4 samples per lane at 262144: more lanes only lengthen the per-wave maximum
+    // up to two 256-thread blocks per CU (kScoutBlocksPerCu): a wavefront owns a contiguous slice of the batch — 128 samples at
+    // 262144 — and its lanes refill from it, so a second wavefront per SIMD no longer lengthens the launch by its unluckiest lane;
+    // it halves the drain at the end of the slices (262144 samples: 0.362 ms at one block per CU, 0.336 at two, 0.387 at three)
     // (a split launch's cut of the order — fd_split_kernel's rule — is decided by the sort's own kernel: ccmp_launch.h, ccmp_split_req)
     const ccmp_split_req cut{ctx->queue, 1, pl.shape.pred, 0, 0, pl.shape.samples, 0};
-    HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, ctx->queue + kQScout, ctx->num_cus, scout_pair_blocks, pl.split ? &cut : nullptr, st));
+    HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, ctx->queue + kQScout, ctx->num_cus * kScoutBlocksPerCu, scout_pair_blocks, pl.split ? &cut : nullptr, st));
     order = sb.order;
     // hand-over in two classes (scout's prediction minus the iterations done): the pool is filled from both ends and the
     // latency kernel takes the long samples first

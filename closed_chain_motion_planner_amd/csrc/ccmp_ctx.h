@@ -58,6 +58,7 @@ constexpr size_t kNoHandoverFrom = 131072;         // ordered batches of this si
 // fixed since round 6 (no option sets them any more)
 constexpr int kPoolLongRemaining = 24;             // two-class hand-over: samples with at least this many predicted iterations left go first
 constexpr int kLatencyBlocksPerCu = 8;             // the projector's latency kernel (and the extend step's throughput flavour): blocks per CU
+constexpr int kScoutBlocksPerCu = 2;               // scout_kernel: 256-lane blocks per CU at most (two wavefronts per SIMD; its lanes refill from their wavefront's slice)
 constexpr int kScoutPairBlocksPerCu = 1;           // the scout's two-lanes-per-sample form while every sample gets its pair at once
 constexpr size_t kScoutPairMaxEdges = 131072;      // extend step: the scout's two-lanes-per-edge form up to this many edges
 constexpr int kGeoBlocksPerCu = 4;                 // the extend step's latency flavour: blocks per CU

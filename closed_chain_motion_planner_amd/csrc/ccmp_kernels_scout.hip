@@ -253,6 +253,13 @@ __device__ __forceinline__ bool scout_round(const consts_f &K, float *x, bool ac
   return cont;
 }
 
+// One sample per lane, and a lane that finishes takes the next one of ITS WAVE's slice: every wavefront owns a contiguous slice
+// of [0, B) (slices differ by at most one sample; the last ones are empty when there are more wavefronts than samples) and keeps
+// a wave-uniform cursor into it; at the top of a round the idle lanes take cursor + their rank among the idle lanes.  No shared
+// word and no atomic (262144 single-lane dequeues on one word cost more than the whole scout; wave-level queues in memory were
+// measured slower too, DESIGN_experiments.md §5.6) — and the wave no longer ends on its unluckiest lane's fixed list of samples:
+// only the last sample of each lane, at most the cap's 96 rounds, is a tail.  A prediction depends on its sample alone, so pred[]
+// does not depend on the grid, on the slices or on which lane took a sample.
 template <int MODE, bool STOCK>
 __global__ __launch_bounds__(256) void scout_kernel(const consts_f K, const ccmp_consts KD, const double *__restrict__ q_in,
                                                     uint16_t *__restrict__ pred, unsigned long long B,
@@ -260,22 +267,31 @@ __global__ __launch_bounds__(256) void scout_kernel(const consts_f K, const ccmp
                                                     unsigned long long first_index)
 {
   float x[14];
-  unsigned long long idx = 0, next = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  int iter = 0;
-  bool active = false, drained = false;
   (void)queue;
+  const unsigned long long waves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
+  const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned long long per = B / waves, extra = B % waves;
+  // wave-uniform: the slice [cursor, end)
+  unsigned long long cursor = wave * per + (wave < extra ? wave : extra);
+  const unsigned long long end = cursor + per + (wave < extra ? 1ull : 0ull);
+  unsigned long long idx = 0;
+  int iter = 0;
+  bool active = false;
   for (;;) {
-    if (!active && !drained) {
-      // static striding instead of a shared queue head: 262144 single-lane dequeues on one word cost more than
-      // the whole scout (one word saturates at ~88 dequeues/us); the imbalance of a few samples per lane is small
-      const unsigned long long t = next;
-      next += (unsigned long long)gridDim.x * blockDim.x;
-      if (t < B) {
-        idx = t; active = true; iter = 0;
+    if (cursor < end) {
+      const unsigned long long idle = __builtin_amdgcn_ballot_w64(!active);
+      if (idle != 0ull) {
+        const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)idle, 0u));
+        const unsigned long long t = cursor + rank;
+        if (!active && t < end) {
+          idx = t; active = true; iter = 0;
 #pragma unroll
-        for (int e = 0; e < 14; e++)
-          x[e] = (float)(MODE == 0 ? q_in[idx * 14 + e] : ccmp::ambient_uniform(KD, seed, first_index + idx, e));
-      } else drained = true;
+          for (int e = 0; e < 14; e++)
+            x[e] = (float)(MODE == 0 ? q_in[idx * 14 + e] : ccmp::ambient_uniform(KD, seed, first_index + idx, e));
+        }
+        const unsigned long long left = end - cursor, n = (unsigned long long)__builtin_popcountll(idle);
+        cursor += n < left ? n : left;
+      }
     }
     if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
     bool resid;
@@ -954,8 +970,12 @@ hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist,
     e = clear_words(hist, kBins, st);
     if (e != hipSuccess) return e;
   }
+  // `blocks` is the most the chip is given; a batch too small to hand every lane of that grid a first sample gets no more wavefronts
+  // than it fills (a half-empty wavefront refills nothing and only shares its SIMD: 65 536 samples 0.152 ms on 1 024 wavefronts, 0.230 on 2 048)
+  const size_t full_blocks = (B + 255) / 256;
+  const unsigned scout_blocks = (unsigned)(full_blocks < (size_t)blocks ? full_blocks : (size_t)blocks);
 #define CCMP_LAUNCH_SCOUT(MODE, STOCK) \
-  hipLaunchKernelGGL((scout_kernel<MODE, STOCK>), dim3(blocks), dim3(256), 0, st, F, *K, c.q_in, pred, (unsigned long long)B, queue, c.seed, c.first)
+  hipLaunchKernelGGL((scout_kernel<MODE, STOCK>), dim3(scout_blocks), dim3(256), 0, st, F, *K, c.q_in, pred, (unsigned long long)B, queue, c.seed, c.first)
   // two lanes per sample while every sample still gets its pair at once (pair_max_blocks blocks of 128 pairs); larger batches
   // keep one lane per sample, several samples per lane
   const size_t pair_blocks = (2 * B + 255) / 256;
