@@ -15,4 +15,6 @@ from .scene import ProxyScene, ProxyValidityChecker, default_allowed, skeleton_s
 
 from .roadmap import Roadmap, pose_distance, pose_from_t_wo  # noqa: F401
 
+from .ik import ik_options, pose_ik_ref  # noqa: F401
+
 __version__ = "0.6.0"

@@ -48,6 +48,12 @@ class CcmpProblem(C.Structure):
         return CcmpProblem.from_buffer_copy(bytes(self))
 
 
+class CcmpIkOpts(C.Structure):
+    """ccmp_ik_opts of include/ccmp.h"""
+    _fields_ = [("restarts", C.c_int32), ("max_rounds", C.c_int32), ("eps", C.c_double), ("lambda_", C.c_double), ("err_clamp", C.c_double),
+                ("sigma", C.c_double)]
+
+
 class CcmpSphere(C.Structure):
     """ccmp_sphere of include/ccmp.h"""
     _fields_ = [("frame", C.c_int32), ("group", C.c_int32), ("c", C.c_double * 3), ("r", C.c_double)]
@@ -77,6 +83,7 @@ EXPORTS = [
     "ccmp_roadmap_create", "ccmp_roadmap_destroy", "ccmp_roadmap_size", "ccmp_roadmap_reserve", "ccmp_roadmap_append", "ccmp_roadmap_set_joints",
     "ccmp_roadmap_truncate", "ccmp_roadmap_read", "ccmp_roadmap_knn", "ccmp_roadmap_connect",
     "ccmp_roadmap_append_host", "ccmp_roadmap_set_joints_host", "ccmp_roadmap_read_host", "ccmp_roadmap_knn_host", "ccmp_roadmap_connect_host",
+    "ccmp_ik_opts_default", "ccmp_pose_ik_batch", "ccmp_pose_ik_host", "ccmp_pose_ik_ref", "ccmp_roadmap_grow", "ccmp_roadmap_grow_host",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -198,6 +205,17 @@ def lib():
         "ccmp_roadmap_knn_host": ([vp, C.c_int, dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int32), dp], C.c_int),
         "ccmp_roadmap_connect_host": ([vp, pp, vp, C.c_double, C.c_int, dp, dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int32), u8p, dp], C.c_int),
+        "ccmp_ik_opts_default": ([C.POINTER(CcmpIkOpts)], None),
+        "ccmp_pose_ik_batch": ([vp, pp, C.POINTER(CcmpIkOpts), vp, vp, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_pose_ik_host": ([vp, pp, C.POINTER(CcmpIkOpts), dp, dp, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, dp, u8p, C.POINTER(C.c_int32), dp,
+                               C.POINTER(C.c_int32)], C.c_int),
+        "ccmp_pose_ik_ref": ([pp, C.POINTER(CcmpIkOpts), dp, dp, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, dp, u8p, C.POINTER(C.c_int32), dp,
+                              C.POINTER(C.c_int32)], C.c_int),
+        "ccmp_roadmap_grow": ([vp, pp, vp, C.c_double, C.POINTER(CcmpIkOpts), vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.c_int,
+                               C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_grow_host": ([vp, pp, vp, C.c_double, C.POINTER(CcmpIkOpts), dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64,
+                                    C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, u8p, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32), u8p,
+                                    C.POINTER(C.c_int32), u8p, dp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -228,6 +246,8 @@ def lib():
 CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GEODESIC_BUDGET, CALL_GEODESIC_ANALYTIC = range(6)  # ccmp.h: CCMP_CALL_*
 CALL_GEODESIC_SCENE, CALL_KNN, CALL_CONNECT = 6, 7, 8
 CALL_ROADMAP_KNN, CALL_ROADMAP_CONNECT = 10, 11  # (9 is not assigned)
+CALL_POSE_IK = 13  # (12 is not assigned)
+IK_MAX_SEEDS, IK_MAX_RESTARTS, IK_MAX_ROUNDS = 16, 31, 256  # ccmp.h: CCMP_IK_MAX_*
 METRIC_JOINT, METRIC_OBJECT = 0, 1  # ccmp.h: CCMP_METRIC_*
 KNN_ALL, KNN_NOT_SELF, KNN_EARLIER = 0, 1, 2  # ccmp.h: CCMP_KNN_*
 KNN_MAX_K = 16

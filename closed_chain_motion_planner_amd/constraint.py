@@ -446,6 +446,18 @@ class KinematicChainConstraint:
                                             out["blocked"].data_ptr(), out["carry"].data_ptr(), _stream_handle(stream)), "ccmp_connect_batch")
         return out
 
+    def pose_ik_batch(self, target_poses, seeds, rng_seed=0, first_index=0, opts=None, want_candidates=False, stream=None):
+        """growTree's sampleCalibGoal for T object poses (ccmp_pose_ik_batch / _host): target_poses (T,8) in the roadmap store's format,
+        seeds (T,S,14) tried in order — per arm the slot's own joints first, then `opts.restarts` Gaussian restarts of which the
+        converged one closest to the seed is kept; the first slot on which both arms succeed gives the state.  Returns a dict: q
+        (T,14; NaN rows on failure), ok (T,), which (T,; the slot, -1 on failure) and with want_candidates cand_q (T,S,2,1+R,7) and
+        cand_rounds (T,S,2,1+R).  Device tensors run asynchronously on `stream`, numpy arrays through the synchronous host form;
+        `ik.pose_ik_ref` is the same solver on the host.  opts: `ik.ik_options(...)`."""
+        from .ik import pose_ik
+
+        self._need_problem()
+        return pose_ik(self.ctx.handle, self.problem, target_poses, seeds, rng_seed, first_index, opts, want_candidates, stream)
+
     def continue_geodesics(self, to, states, n, ok, its, carry, max_states, round_budget=0, max_calls=1 << 20, cont_states=None,
                            scene=None, margin=None):
         """Finishes the edges of a `discrete_geodesic_batch(..., want_carry=True)` result that did not reach their end

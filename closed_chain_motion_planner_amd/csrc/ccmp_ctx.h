@@ -9,6 +9,8 @@
 
 #include "../../include/ccmp.h"
 
+namespace ccmp { struct ik_params; }
+
 namespace ccmp_host {
 
 /* text of the last HIP / RCCL failure on this thread (ccmp_last_hip_error) */
@@ -88,6 +90,8 @@ struct ccmp_ctx {
   size_t knn_ws_cap = 0;               // in bytes
   double *connect_ws = nullptr;        // ccmp_connect_batch: the gathered endpoints, from [E][14] then to [E][14]
   size_t connect_ws_cap = 0;           // in edges
+  void *ik_ws = nullptr;               // ccmp_pose_ik_batch: the candidates' records, q [C][7] | d2 [C] | rounds [C] (ccmp_launch.h: IkCall)
+  size_t ik_ws_cap = 0;                // in candidates
   void *stage = nullptr;               // device staging of the *_host conveniences
   size_t stage_cap = 0;
   void *pin = nullptr;                 // pinned, device-mapped host block for small *_host calls (single states of the reference signature)
@@ -162,6 +166,13 @@ int connect_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene 
 int connect_edges(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *nodes, const double *queries, size_t Q, int k,
                   int check_target, int max_states, int round_budget, const int32_t *nbr_idx, double *states, int32_t *n_states, uint8_t *ok,
                   int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream);
+/* pose-targeted IK (ccmp_ik.cpp), shared with ccmp_roadmap_grow: the checks of a call (problem, options, S, the candidate count) and the
+ * options as the kernels take them; the candidate count; the context's record workspace at that size; the launches of a checked call */
+int ik_checks(const ccmp_problem *p, const ccmp_ik_opts *opts, size_t T, int S, ccmp::ik_params *P);
+size_t ik_candidates(size_t T, int S, const ccmp::ik_params &P);
+int ik_reserve(ccmp_ctx *ctx, size_t candidates);
+int ik_launches(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp::ik_params &P, const double *poses, const double *seeds, size_t T, int S, uint64_t rng_seed,
+                uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds, hipStream_t st);
 /* device staging of the *_host conveniences, grown on demand */
 int ensure_stage(ccmp_ctx *ctx, size_t bytes);
 /* the device-visible alias of a caller's host range if all of it is page-locked and mapped (hipHostMalloc,

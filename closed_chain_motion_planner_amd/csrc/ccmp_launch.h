@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; }
+namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -131,7 +131,30 @@ struct KnnShape {
   size_t workspace_bytes = 0;  // Q * partitions * kc * 12, 0 with one partition
 };
 
+/* one pose-targeted IK call (ccmp_pose_ik_batch; csrc/ccmp_ik.h): T targets x S seed slots x 2 arms x (1 + restarts) candidates, their
+ * records in the context's workspace at candidate index ((t S + s) 2 + a) (1 + restarts) + r */
+struct IkCall {
+  const ccmp_consts *K;
+  const ccmp::ik_arms *arms;
+  const ccmp::ik_params *P;
+  const double *poses;  // [T][8]
+  const double *seeds;  // [T][S][14]
+  size_t T; int S;
+  unsigned long long rng_seed, first_index;
+  double *rec_q;        // [candidates][7]
+  int32_t *rec_rounds;  // [candidates]
+  double *rec_d2;       // [candidates]
+};
+
 #pragma GCC visibility push(hidden)
+hipError_t ik_solve(const IkCall &c, hipStream_t st);
+hipError_t ik_select(const IkCall &c, double *q_out, uint8_t *ok, int32_t *which, hipStream_t st);
+/* ccmp_roadmap_grow: seeds[q][r] = the store's joint row nbr_idx[q][r] (NaN for an empty slot) */
+hipError_t ik_gather_seeds(const double *joints, const int32_t *nbr_idx, size_t slots, double *seeds, hipStream_t st);
+/* ccmp_roadmap_grow: what the traversal sees — masked[q][r] = nbr_idx[q][r] where target q has a state and the neighbour's joint row is
+ * finite, else -1 (an empty slot); q_trav[q] = q_new[q], or zeros for a target without a state (no NaN endpoint reaches a traversal) */
+hipError_t ik_grow_prepare(const double *joints, const int32_t *nbr_idx, const uint8_t *ik_ok, const double *q_new, size_t Q, int k, int32_t *masked,
+                           double *q_trav, hipStream_t st);
 hipError_t knn(const KnnCall &c, const KnnShape &s, void *workspace, hipStream_t st);
 /* the same call on the object metric: nodes = the store's pose rows [N][8], queries [Q][8]; shape from plan_knn_pose (part a multiple of kKnnPoseTile) */
 hipError_t knn_pose(const KnnCall &c, const KnnShape &s, void *workspace, hipStream_t st);

@@ -516,6 +516,17 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
       }
       break;
     }
+    case CCMP_CALL_POSE_IK: {
+      // n = the targets; the reference's five neighbours as seed slots and the default options assumed.  The shape is fixed: one
+      // candidate per lane, one wavefront per block, the arm as the grid's second dimension.
+      ccmp_ik_opts o;
+      ccmp_ik_opts_default(&o);
+      const size_t lanes = n * (size_t)kConnectDescribeK * (size_t)(1 + o.restarts);
+      L.add("pose_ik T=%zu (S=%d seed slots, %d restarts, at most %d rounds assumed): ik_solve_kernel x %zu blocks (one candidate per lane, 64 per block, "
+            "x 2 arms; %zu candidates, records of 68 bytes in the context's workspace), then ik_select_kernel x %zu blocks (one target per thread)",
+            n, kConnectDescribeK, o.restarts, o.max_rounds, 2 * ((lanes + 63) / 64), 2 * lanes, (n + 63) / 64);
+      break;
+    }
     default: return CCMP_EINVAL;
   }
   // without a context the plan is the built-in policy on an ASSUMED device: say so (block counts and the thresholds that mark

@@ -14,6 +14,7 @@
 #include "../../include/ccmp.h"
 #include "ccmp_ctx.h"
 #include "ccmp_host.h"
+#include "ccmp_ik.h"
 #include "ccmp_launch.h"
 #include "ccmp_policy.h"
 #include "ccmp_pose.h"
@@ -30,6 +31,8 @@ struct ccmp_roadmap {
   size_t size = 0, cap = 0;
   double *qpose = nullptr;  // ccmp_roadmap_connect: the derived query poses [qpose_cap][8]
   size_t qpose_cap = 0;
+  void *grow_ws = nullptr;  // ccmp_roadmap_grow: seeds [E][14] | the traversal's targets [Q][14] | its neighbours [E] (int32)
+  size_t grow_ws_cap = 0;   // in edges
 };
 
 namespace {
@@ -130,6 +133,7 @@ void ccmp_roadmap_destroy(ccmp_roadmap *rm)
     if (rm->joints) (void)hipFree(rm->joints);
     if (rm->poses) (void)hipFree(rm->poses);
     if (rm->qpose) (void)hipFree(rm->qpose);
+    if (rm->grow_ws) (void)hipFree(rm->grow_ws);
   }
   delete rm;
 }
@@ -260,6 +264,44 @@ int ccmp_roadmap_connect(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_sce
                        newton_iters, blocked, carry_out, hip_stream);
 }
 
+// growTree's device part: the object-metric k-NN, the neighbours' joint rows as seed slots, the IK, then ccmp_roadmap_connect's own chain
+// from each neighbour to the new state.  Every check runs and every workspace has its size before the first launch; one stream, no
+// host synchronisation.  The traversal reads a copy of the neighbours in which a target without a state, and a neighbour without
+// joints, are empty slots, and a copy of the new states in which a missing one is a row of zeros (never an endpoint: all its slots
+// are empty): no NaN reaches a traversal kernel.
+int ccmp_roadmap_grow(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts, const double *query_poses,
+                      size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index, int check_target, int max_states,
+                      int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok, int32_t *ik_which, double *states,
+                      int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream)
+{
+  { const int rc = knn_checks(rm, CCMP_METRIC_OBJECT, query_poses, Q, k, mode, nbr_idx); if (rc != CCMP_OK) return rc; }
+  ccmp_ctx *ctx = rm->ctx;
+  if (!p || k > CCMP_IK_MAX_SEEDS) return CCMP_EINVAL;
+  ccmp::ik_params P;
+  { const int rc = ik_checks(p, opts, Q, k, &P); if (rc != CCMP_OK) return rc; }
+  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  if (Q == 0) return CCMP_OK;
+  if (!q_new || !ik_ok || !ik_which) return CCMP_EINVAL;
+  { const int rc = connect_checks(ctx, p, scene, margin, max_states, states, n_states, ok, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; }
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t E = Q * (size_t)k;
+  const ccmp_launch::KnnShape s = plan_knn_pose(ctx, Q, rm->size, k);
+  { const int rc = grow_buffer(ctx, &ctx->knn_ws, &ctx->knn_ws_cap, s.workspace_bytes, s.workspace_bytes); if (rc != CCMP_OK) return rc; }
+  { const int rc = grow_buffer(ctx, (void **)&ctx->connect_ws, &ctx->connect_ws_cap, E, E * 28 * sizeof(double)); if (rc != CCMP_OK) return rc; }
+  { const int rc = grow_buffer(ctx, &rm->grow_ws, &rm->grow_ws_cap, E, E * (28 * sizeof(double) + sizeof(int32_t))); if (rc != CCMP_OK) return rc; }
+  { const int rc = ik_reserve(ctx, ik_candidates(Q, k, P)); if (rc != CCMP_OK) return rc; }
+  double *seeds = (double *)rm->grow_ws, *q_trav = seeds + E * 14; // Q <= E rows
+  int32_t *masked = (int32_t *)(seeds + E * 28);
+  { const int rc = knn_object(rm, query_poses, Q, k, mode, self_base, nbr_idx, nbr_dist, st); if (rc != CCMP_OK) return rc; }
+  HIP_TRY(ccmp_launch::ik_gather_seeds(rm->joints, nbr_idx, E, seeds, st));
+  { const int rc = ik_launches(ctx, p, P, query_poses, seeds, Q, k, rng_seed, first_index, q_new, ik_ok, ik_which, nullptr, nullptr, st); if (rc != CCMP_OK) return rc; }
+  HIP_TRY(ccmp_launch::ik_grow_prepare(rm->joints, nbr_idx, ik_ok, q_new, Q, k, masked, q_trav, st));
+  return connect_edges(ctx, p, scene, margin, rm->joints, q_trav, Q, k, check_target, max_states, round_budget, masked, states, n_states, ok, newton_iters,
+                       blocked, carry_out, hip_stream);
+}
+
 // the host form of set_joints (growTree hands over the result of its IK): synchronous on the context's stream
 int ccmp_roadmap_set_joints_host(ccmp_roadmap *rm, size_t index, const double *joints)
 {
@@ -385,6 +427,55 @@ int ccmp_roadmap_connect_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccm
   if (rc == CCMP_OK) {
     down(nbr_idx, off_i, E * sizeof(int32_t));
     down(nbr_dist, off_d, E * sizeof(double));
+    down(states, off_st, sb);
+    down(n_states, off_n, E * sizeof(int32_t));
+    down(ok, off_ok, E);
+    down(newton_iters, off_it, E * sizeof(int32_t));
+    down(blocked, off_bl, E);
+    down(carry_out, off_co, E * 2 * sizeof(double));
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  if (rc != CCMP_OK) return rc;
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                           const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
+                           int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
+                           int32_t *ik_which, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out)
+{
+  { const int rc = knn_checks(rm, CCMP_METRIC_OBJECT, query_poses, Q, k, mode, nbr_idx); if (rc != CCMP_OK) return rc; }
+  if (!p || k > CCMP_IK_MAX_SEEDS) return CCMP_EINVAL;
+  { ccmp::ik_params P; const int rc = ik_checks(p, opts, Q, k, &P); if (rc != CCMP_OK) return rc; }
+  if (Q == 0) return CCMP_OK;
+  if (!q_new || !ik_ok || !ik_which) return CCMP_EINVAL;
+  { const int rc = connect_checks(rm->ctx, p, scene, margin, max_states, states, n_states, ok, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; } // before any buffer is touched
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  ccmp_ctx *ctx = rm->ctx;
+  hipStream_t st = ctx->stream;
+  const size_t E = Q * (size_t)k, pb = Q * 8 * sizeof(double), sb = E * (size_t)max_states * 14 * sizeof(double);
+  Stage sg(ctx);
+  const size_t off_p = sg.add(pb), off_i = sg.add(E * sizeof(int32_t)), off_d = sg.add(E * sizeof(double)), off_q = sg.add(Q * 14 * sizeof(double)),
+               off_io = sg.add(Q), off_iw = sg.add(Q * sizeof(int32_t)), off_st = sg.add(sb), off_n = sg.add(E * sizeof(int32_t)), off_ok = sg.add(E),
+               off_it = sg.add(E * sizeof(int32_t)), off_bl = sg.add(E), off_co = sg.add(E * 2 * sizeof(double));
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
+  HIP_TRY(hipMemcpyAsync(sg.at(off_p), query_poses, pb, hipMemcpyHostToDevice, st));
+  const int rc = ccmp_roadmap_grow(rm, p, scene, margin, opts, (const double *)sg.at(off_p), Q, k, mode, self_base, rng_seed, first_index, check_target, max_states,
+                                   round_budget, (int32_t *)sg.at(off_i), nbr_dist ? (double *)sg.at(off_d) : nullptr, (double *)sg.at(off_q),
+                                   (uint8_t *)sg.at(off_io), (int32_t *)sg.at(off_iw), (double *)sg.at(off_st), (int32_t *)sg.at(off_n), (uint8_t *)sg.at(off_ok),
+                                   newton_iters ? (int32_t *)sg.at(off_it) : nullptr, blocked ? (uint8_t *)sg.at(off_bl) : nullptr,
+                                   carry_out ? (double *)sg.at(off_co) : nullptr, st);
+  hipError_t e = hipSuccess;
+  auto down = [&](void *dst, size_t off, size_t n) { if (dst && e == hipSuccess) e = hipMemcpyAsync(dst, sg.at(off), n, hipMemcpyDeviceToHost, st); };
+  if (rc == CCMP_OK) {
+    down(nbr_idx, off_i, E * sizeof(int32_t));
+    down(nbr_dist, off_d, E * sizeof(double));
+    down(q_new, off_q, Q * 14 * sizeof(double));
+    down(ik_ok, off_io, Q);
+    down(ik_which, off_iw, Q * sizeof(int32_t));
     down(states, off_st, sb);
     down(n_states, off_n, E * sizeof(int32_t));
     down(ok, off_ok, E);

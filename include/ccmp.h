@@ -255,7 +255,9 @@ enum {
   CCMP_CALL_CONNECT = 8,           /* ccmp_connect_batch: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
   /* (9 is not assigned: it stays an unknown kind) */
   CCMP_CALL_ROADMAP_KNN = 10,      /* ccmp_roadmap_knn with CCMP_METRIC_OBJECT: n = the queries; a store of 65536 nodes and k = 5 assumed */
-  CCMP_CALL_ROADMAP_CONNECT = 11   /* ccmp_roadmap_connect with CCMP_METRIC_OBJECT: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
+  CCMP_CALL_ROADMAP_CONNECT = 11,  /* ccmp_roadmap_connect with CCMP_METRIC_OBJECT: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
+  /* (12 is not assigned: it stays an unknown kind) */
+  CCMP_CALL_POSE_IK = 13           /* ccmp_pose_ik_batch: n = the targets; 5 seed slots and the default options (14 restarts) assumed */
 };
 int ccmp_ctx_describe(const ccmp_ctx *ctx, int call_kind, size_t n, char *buf, size_t cap);
 int ccmp_ctx_device(const ccmp_ctx *ctx);
@@ -586,7 +588,7 @@ void ccmp_pose_from_t_wo(const double t_wo[12], double pose[8]);
  *             device-to-device copy and ONE synchronisation of hip_stream before the old block is freed — the only non-asynchronous case
  *             (never under capture: reserve first).
  *   set_joints  joints[14] (device pointer) into row `index` < size, asynchronous on hip_stream; the pose row is not touched.
- *             ccmp_roadmap_set_joints_host takes a host pointer (growTree hands over the result of its IK) and is synchronous.
+ *             ccmp_roadmap_set_joints_host takes a host pointer (growTree hands over the result of its IK: ccmp_pose_ik_* / ccmp_roadmap_grow below) and is synchronous.
  *   truncate  size = n <= size; keeps the capacity.
  *   read      rows first .. first + count - 1 into joints_out [count][14] / poses_out [count][8] (device pointers, either may be NULL).
  *   knn       the k nearest vertices of each query.  CCMP_METRIC_JOINT: queries [Q][14], the kernels of ccmp_knn_batch over the store's
@@ -626,6 +628,73 @@ int ccmp_roadmap_connect_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccm
                               const double *query_joints, const double *query_poses, size_t Q, int k, int mode, size_t self_base, int check_target,
                               int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *states, int32_t *n_states, uint8_t *ok,
                               int32_t *newton_iters, uint8_t *blocked, double *carry_out);
+
+/* ---- pose-targeted IK: growTree's sampleCalibGoal step ----------------------------------------------------------------------------- */
+/* The reference's growTree creates a vertex that has only an object pose, ranks its neighbours on the object metric and calls
+ * sampleCalibGoal(obj_state, neighbour joints, new joints) per neighbour until one succeeds (stefanBiPRM.cpp:283-302,
+ * jy_ConstrainedValidStateSampler.h:147-189); the same call produces every start and goal state (stefanBiPRM.cpp:722,744,760).  Per arm
+ * a the hand target is T_obj * t_o7[a] (ik_task.cpp:16-28); TRAC-IK solves from the neighbour's seven joints and, where that fails, from
+ * 14 Gaussian configurations around mid-range (sigma 0.3, clamped to the limits: panda_tracik.cpp:62-78), keeping the converged one
+ * closest to the seed; both arms must succeed; the first neighbour that succeeds wins.
+ * WHAT IS AND IS NOT RESTATED: TRAC-IK (KDL + NLopt, time-bounded, two racing threads) is not reproducible and is not part of this
+ * library.  These calls restate the RULE AROUND IT and put a deterministic damped-least-squares Newton solver of this project's own where
+ * the reference calls CartToJnt, on the projector's own forward kinematics (csrc/ccmp_ik.h states target, error, test, step and rule in
+ * full): a state they return satisfies the constraint by construction — both hands meet T_obj * t_o7 within eps per twist component.
+ * The reference's IKValid and si_->isValid(result) (MoveIt) stay host calls on the returned state; the proxy pre-filter is one
+ * ccmp_clearance_* call on it.
+ *   target_poses [T][8]   object poses in the store's format (x y z qx qy qz qw pad); the quaternion is NOT normalised (utils.h:22)
+ *   seeds [T][S][14]      S seed slots per target in the order to try them, 1 <= S <= CCMP_IK_MAX_SEEDS; a slot with a non-finite entry
+ *                         is skipped
+ *   rng_seed, first_index the restarts' stream: restart r = 1..R of (target t, slot s, arm a) starts from ccmp::ambient_gaussian at index
+ *                         ((first_index + t) S + s) R + (r - 1), dimension 7 a + i, mean (lb_i + ub_i) / 2 — a call over T targets equals
+ *                         T calls over one with the matching first_index
+ *   q_out [T][14], ok [T], which [T]   the state, 1 / 0, and the slot that gave it; on failure a NaN row, ok = 0, which = -1
+ *   cand_q [T][S][2][1 + R][7], cand_rounds [T][S][2][1 + R]   (nullable) every candidate's last iterate and the rounds it took, -1 = not
+ *                         converged within max_rounds, -2 = its slot was skipped (the iterate is NaN)
+ * Start configurations and every iterate are clamped into [lb + joint_eps, ub - joint_eps] (a value on the bound passes jointValid).
+ * The result is a function of the arguments alone: no launch shape changes it, and ccmp_pose_ik_ref gives the same bits.
+ * ccmp_pose_ik_batch: device pointers, asynchronous on hip_stream, capturable after one eager call at that size (the candidates'
+ * records live in a workspace of the context).  ccmp_pose_ik_host: host pointers, synchronous on the context's stream.  Both answer a
+ * NULL context with CCMP_ENODEV on a machine without a HIP device and with CCMP_EINVAL otherwise; every check runs before the first
+ * launch.  ccmp_pose_ik_ref: THE SAME TEXT COMPILED FOR THE HOST on host pointers, one thread, no device, never CCMP_ENODEV — the
+ * checker of the GPU tests and the CPU contender of tools/measure.py ik, as ccmp_pose_distance is for the metric.
+ * CCMP_EINVAL: an invalid problem, options out of range, S out of range, T * S * 2 * (1 + restarts) >= 2^31, a NULL array with T > 0.
+ * T == 0 returns CCMP_OK and touches nothing.  opts == NULL: the defaults. */
+#define CCMP_IK_MAX_SEEDS 16
+#define CCMP_IK_MAX_RESTARTS 31
+#define CCMP_IK_MAX_ROUNDS 256
+typedef struct ccmp_ik_opts {
+  int32_t restarts;   /* 14   Gaussian restarts per (slot, arm) behind the seeded solve, 0..CCMP_IK_MAX_RESTARTS (jy_ConstrainedValidStateSampler.h:160) */
+  int32_t max_rounds; /* 64   Newton steps per candidate at most, 1..CCMP_IK_MAX_ROUNDS */
+  double eps;         /* 1e-5 per twist component, strictly below (TRAC-IK's default eps) */
+  double lambda;      /* 0.05 damping */
+  double err_clamp;   /* 0.5  the error vector's norm is clamped to this before a step */
+  double sigma;       /* 0.3  standard deviation of the restarts (panda_tracik.cpp:70) */
+} ccmp_ik_opts;
+void ccmp_ik_opts_default(ccmp_ik_opts *opts);
+int ccmp_pose_ik_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
+                       uint64_t rng_seed, uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds,
+                       void *hip_stream);
+int ccmp_pose_ik_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
+                      uint64_t rng_seed, uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds);
+int ccmp_pose_ik_ref(const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S, uint64_t rng_seed,
+                     uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds);
+/* growTree's device part for Q poses in ONE call on one stream (stefanBiPRM.cpp:283-351), in this order: the object-metric k-NN of
+ * query_poses [Q][8] on the store (k, mode, self_base as ccmp_roadmap_knn; k <= CCMP_IK_MAX_SEEDS); the neighbours' joint rows as seed
+ * slots in rank order (an empty slot or a pose-only neighbour is a skipped slot); ccmp_pose_ik_batch on them; then edge e = q * k + r
+ * from neighbour r to the new state through ccmp_roadmap_connect's own gather -> traversal -> fix chain, with its traversal arguments
+ * and outputs unchanged in meaning (check_target = 0 is growTree's discreteGeodesic).  A target without a state makes all its slots
+ * empty slots (ok = 0, n_states = 0, ...), as does a neighbour without joints: no NaN endpoint reaches a traversal kernel.
+ * Additional outputs: q_new [Q][14], ik_ok [Q], ik_which [Q] (ccmp_pose_ik_batch's q_out, ok, which).  IT DOES NOT APPEND: the reference
+ * adds the vertex only after an edge succeeded (stefanBiPRM.cpp:361) — the caller does, with ccmp_roadmap_append or set_joints. */
+int ccmp_roadmap_grow(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts, const double *query_poses,
+                      size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index, int check_target, int max_states,
+                      int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok, int32_t *ik_which, double *states,
+                      int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream);
+int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                           const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
+                           int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
+                           int32_t *ik_which, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

@@ -82,7 +82,12 @@ inline uint64_t next_sampler_seed()
 // a ~100 us launch.  The problem is passed by value into every launch and may be changed between calls.
 class Projector {
 public:
-  explicit Projector(int device = 0) { check(ccmp_ctx_create(device, &ctx_), "ccmp_ctx_create"); std::memset(&problem_, 0, sizeof problem_); }
+  explicit Projector(int device = 0)
+  {
+    check(ccmp_ctx_create(device, &ctx_), "ccmp_ctx_create");
+    std::memset(&problem_, 0, sizeof problem_);
+    ccmp_ik_opts_default(&ik_opts_);
+  }
   Projector(const std::string &yaml_path, int device = 0) : Projector(device) { loadConfig(yaml_path); }
   ~Projector() { ccmp_ctx_destroy(ctx_); }
   Projector(const Projector &) = delete;
@@ -171,6 +176,54 @@ public:
     std::lock_guard<std::mutex> hold(mu_);
     check(ccmp_project_host(ctx_, &problem_, q_in, q_out, ok, iters, B), "ccmp_project_host");
   }
+  // ---- growTree's IK: bool jy_ValidStateSampler::sampleCalibGoal(obj_state, start, result) (jy_ConstrainedValidStateSampler.h:147-189) ----
+  // pose8 = the object pose (x y z qx qy qz qw pad: poseOf), start14 = the neighbour's joints, result14 = the new joints.  Per arm the
+  // hand target is T_obj * t_o7; the seeded solve first, else the closest converged one of ikOptions().restarts Gaussian restarts; both
+  // arms must succeed (ccmp_pose_ik_host; the solver is this library's own, not TRAC-IK: include/ccmp.h).  The multi-seed form tries
+  // `S` seeds [S][14] in order in ONE call — the reference's loop over the neighbours (stefanBiPRM.cpp:294-302) — and reports the slot
+  // that won in *which (-1: none).  The reference's IKValid / si_->isValid(result) stay the caller's, on the returned state.
+  // Never throw: false when no state was found OR the call failed; a failed call also leaves the FIRST error in lastError() /
+  // lastErrorMessage() until clearError().  Whenever false is returned result14 is NaN-filled.
+  // The restarts draw from the stream (ikSeed(), running index): one index per call; setIkStream makes runs reproducible.
+  bool sampleCalibGoal(const double *pose8, const double *start14, double *result14) const noexcept { return sampleCalibGoal(pose8, start14, 1, result14, nullptr); }
+  bool sampleCalibGoal(const double *pose8, const double *seeds, int S, double *result14, int *which) const noexcept
+  {
+    uint8_t ok = 0;
+    int32_t slot = -1;
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(mu_);
+      rc = ccmp_pose_ik_host(ctx_, &problem_, &ik_opts_, pose8, seeds, 1, S, ikSeed(), ik_index_, result14, &ok, &slot, nullptr, nullptr);
+      if (rc == CCMP_OK) ik_index_++;
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) {
+      record(rc, "ccmp_pose_ik_host");
+      ok = 0;
+      slot = -1;
+      if (result14)
+        for (int i = 0; i < 14; i++) result14[i] = std::numeric_limits<double>::quiet_NaN();
+    }
+    if (which) *which = slot;
+    return ok != 0;
+  }
+  ccmp_ik_opts &ikOptions() noexcept { return ik_opts_; }
+  const ccmp_ik_opts &ikOptions() const noexcept { return ik_opts_; }
+  void setIkStream(uint64_t seed, uint64_t next_index = 0) noexcept { ik_seed_ = seed; ik_index_ = next_index; ik_seeded_ = true; }
+  // (drawn from the process-wide source at first use, not at construction: the samplers' seeds keep their order)
+  uint64_t ikSeed() const noexcept
+  {
+    if (!ik_seeded_) { ik_seed_ = next_sampler_seed(); ik_seeded_ = true; }
+    return ik_seed_;
+  }
+  uint64_t ikNextIndex() const noexcept { return ik_index_; }
+  // for ccmp::Roadmap::grow, under mutex(): the index of the next call's restarts
+  uint64_t takeIkIndex() const noexcept { return ik_index_++; }
+  int lastError() const noexcept { return err_code_; }
+  std::string lastErrorMessage() const { return err_what_; }
+  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
+
   unsigned getCoDimension() const { return 2; }
   unsigned getAmbientDimension() const { return 14; }
   const ccmp_problem &problem() const { return problem_; }
@@ -180,10 +233,22 @@ public:
   std::mutex &mutex() const { return mu_; }
 
 private:
+  void record(int code, const char *what) const noexcept
+  {
+    if (err_code_ != CCMP_OK) return;
+    err_code_ = code;
+    try { err_what_ = std::string(what) + ": " + ccmp_strerror(code); } catch (...) {}
+  }
   mutable std::mutex mu_;
   ccmp_ctx *ctx_ = nullptr;
   ccmp_problem problem_;
   bool configured_ = false;
+  ccmp_ik_opts ik_opts_;
+  mutable uint64_t ik_seed_ = 0;
+  mutable bool ik_seeded_ = false;
+  mutable uint64_t ik_index_ = 0;
+  mutable int err_code_ = CCMP_OK; // the IK verbs' sticky error (the other verbs throw)
+  mutable std::string err_what_;
 };
 
 // jy_ProjectedStateSampler::sampleUniform served from a buffer that ONE launch of `batch` fused
@@ -487,6 +552,47 @@ public:
       return ccmp_roadmap_connect_host(rm_, &proj_.problem(), scene, margin, metric, query_joints, query_pose, 1, (int)k, mode, self_base, check_target ? 1 : 0,
                                        max_states, 0, idx->data(), nullptr, states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr);
     }, "ccmp_roadmap_connect_host");
+  }
+
+  // growTree's device part for ONE object pose in one call (ccmp_roadmap_grow_host; stefanBiPRM.cpp:283-351): the k pose-nearest
+  // vertices, Projector::sampleCalibGoal's rule over their joints as seeds in rank order, then discreteGeodesic (check_target:
+  // checkMotion) from every neighbour to the new state.  idx [k], q_new14 [14], *ik_which (nullable) = the neighbour slot whose joints
+  // seeded the state, n_states / ok [k], states [k][max_states][14] as connect() reports them; a pose without a state gives NaN joints,
+  // *ik_which = -1 and empty slots.  Returns true when the call ran AND a state was found; a failed call leaves q_new14 NaN-filled and
+  // the error in lastError().  It does not append: the reference adds the vertex only after an edge succeeded (:361).  The restarts'
+  // stream is the Projector's (setIkStream).
+  bool grow(const double *pose8, unsigned k, int max_states, std::vector<int32_t> *idx, double *q_new14, int *ik_which, std::vector<int32_t> *n_states,
+            std::vector<uint8_t> *ok, std::vector<double> *states, bool check_target = false, const ccmp_scene *scene = nullptr, double margin = 0.0,
+            int mode = CCMP_KNN_ALL, size_t self_base = 0) const noexcept
+  {
+    uint8_t ik_ok = 0;
+    int32_t slot = -1;
+    if (q_new14)
+      for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
+    if (ik_which) *ik_which = -1;
+    try {
+      idx->assign(k, -1);
+      n_states->assign(k, 0);
+      ok->assign(k, 0);
+      states->assign((size_t)k * (size_t)(max_states > 0 ? max_states : 0) * 14, 0.0);
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::grow");
+      return false;
+    }
+    const bool ran = call([&] {
+      const int rc = ccmp_roadmap_grow_host(rm_, &proj_.problem(), scene, margin, &proj_.ikOptions(), pose8, 1, (int)k, mode, self_base, proj_.ikSeed(),
+                                            proj_.ikNextIndex(), check_target ? 1 : 0, max_states, 0, idx->data(), nullptr, q_new14, &ik_ok, &slot,
+                                            states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr);
+      if (rc == CCMP_OK) (void)proj_.takeIkIndex();
+      return rc;
+    }, "ccmp_roadmap_grow_host");
+    if (!ran) {
+      if (q_new14)
+        for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
+      return false;
+    }
+    if (ik_which) *ik_which = slot;
+    return ik_ok != 0;
   }
 
   int lastError() const noexcept { return err_code_; }

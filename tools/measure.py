@@ -22,6 +22,9 @@
     python tools/measure.py connect [reps]                  the connection step: ccmp_knn_batch against FP64 torch distances + torch.topk (throughput shape and
                                                            single queries), ccmp_connect_batch against torch k-NN + gather + ccmp_geodesic_batch_ex, both
                                                            contenders alternating in one process, device events, medians with their spread
+    python tools/measure.py ik [reps_a] [reps_b] [T_b]      pose-targeted IK (growTree's sampleCalibGoal): (a) one pose x 5 seeds x 14 restarts through the host
+                                                           form, (b) T_b = 4096 poses x 5 x 14 through the device form, each against ccmp_pose_ik_ref on one
+                                                           thread on the same inputs, alternating in one process; histogram of rounds, idle lane-rounds
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -734,6 +737,91 @@ def roadmap(argv):
     print("VERDICT host-form k-NN on the resident store: " + ("not slower" if all(verdict) else "SLOWER in at least one case"))
 
 
+def ik(argv):
+    """ccmp_pose_ik_host / ccmp_pose_ik_batch against ccmp_pose_ik_ref (the same text on one host thread) on the same inputs; the outputs are
+    compared bit for bit while they are timed.  Targets: poses of valid projected states; seeds: their five pose-nearest other states."""
+    from closed_chain_motion_planner_amd import Roadmap, pose_ik_ref
+
+    reps_a = int(argv[0]) if len(argv) > 0 else 30
+    reps_b = int(argv[1]) if len(argv) > 1 else 2
+    Tb = int(argv[2]) if len(argv) > 2 else 4096
+    S, R = 5, 14
+    ctx = Context(0)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    q, ok, _, _ = c.sample_project_batch(0x1C, 0, 16 * Tb + 4096, want_iters=False)
+    states = q[(ok != 0) & (c.joint_valid_batch(q) != 0)][:Tb + 1024].contiguous()
+    rm = Roadmap(c, states.shape[0])
+    rm.append(joints=states)
+    poses = rm.read()[1]
+    T = min(Tb, states.shape[0])
+    idx, _ = rm.nearest_k(poses[:T].contiguous(), S, mode=_lib.KNN_NOT_SELF)
+    seeds = states[idx.long()].contiguous()
+    tp, sd = poses[:T].contiguous(), seeds
+    tph, sdh = tp.cpu().numpy(), sd.cpu().numpy()
+    print("%d valid states; %d targets x %d seeds x %d restarts" % (states.shape[0], T, S, R))
+
+    def same(a, b):
+        return all(np.array_equal(np.asarray(a[k]).view(np.uint8), np.asarray(b[k]).view(np.uint8)) for k in ("q", "ok", "which"))
+
+    # (a) the planner's shape: one pose per call, host pointers, host clock around the synchronous calls
+    ta = {"host form (device)": [], "ccmp_pose_ik_ref (one thread)": []}
+    agree = True
+    for i in range(reps_a + 3):
+        t = i % T
+        t0 = time.perf_counter()
+        dev = c.pose_ik_batch(tph[t:t + 1], sdh[t:t + 1], rng_seed=0x1C, first_index=t)
+        t1 = time.perf_counter()
+        ref = pose_ik_ref(c.problem, tph[t:t + 1], sdh[t:t + 1], rng_seed=0x1C, first_index=t)
+        t2 = time.perf_counter()
+        agree = agree and same(dev, ref)
+        if i >= 3:
+            ta["host form (device)"].append((t1 - t0) * 1e3)
+            ta["ccmp_pose_ik_ref (one thread)"].append((t2 - t1) * 1e3)
+    print("(a) 1 pose x %d x %d, host form, wall clock; outputs identical: %s" % (S, R, agree))
+    for name, ms in ta.items():
+        print("    %-34s %s" % (name, _stat(ms)))
+
+    # (b) the batch: device pointers, device events; the contender once per round on the host clock
+    tb = {"device form": [], "ccmp_pose_ik_ref (one thread)": []}
+    out = c.pose_ik_batch(tp, sd, rng_seed=0x1C, want_candidates=True)
+    torch.cuda.synchronize()
+    for _ in range(reps_b):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dev = c.pose_ik_batch(tp, sd, rng_seed=0x1C)
+        e1.record()
+        torch.cuda.synchronize()
+        tb["device form"].append(e0.elapsed_time(e1))
+        t0 = time.perf_counter()
+        ref = pose_ik_ref(c.problem, tph, sdh, rng_seed=0x1C)
+        tb["ccmp_pose_ik_ref (one thread)"].append((time.perf_counter() - t0) * 1e3)
+        agree = agree and same({k: v.cpu().numpy() for k, v in dev.items()}, ref)
+    print("(b) %d poses x %d x %d, device form, device events; outputs identical: %s" % (T, S, R, agree))
+    for name, ms in tb.items():
+        print("    %-34s %s" % (name, _stat(ms)))
+    print("    solved %d of %d; by the first slot %d" % (int(out["ok"].sum()), T, int((out["which"] == 0).sum())))
+    # rounds and idle lanes: lane n of an arm is candidate (n // (1 + R), n % (1 + R)); a wavefront is 64 consecutive lanes and runs as
+    # many loop passes as its slowest lane (a converged lane took rounds + 1 passes, an unconverged one max_rounds + 1)
+    rounds = out["cand_rounds"].cpu().numpy()
+    conv = rounds[rounds >= 0]
+    hist, edges = np.histogram(conv, bins=[0, 1, 2, 4, 8, 16, 32, 48, 65])
+    print("    rounds of the converged candidates (%.1f %% of all; %.1f %% did not converge): median %d, 95th percentile %d"
+          % (100.0 * len(conv) / rounds.size, 100.0 * (rounds == -1).mean(), np.median(conv), np.percentile(conv, 95)))
+    print("    histogram " + ", ".join("[%d,%d): %d" % (edges[i], edges[i + 1], hist[i]) for i in range(len(hist))))
+    passes = np.where(rounds >= 0, rounds + 1, np.where(rounds == -1, 65, 0))  # (T, S, 2, 1 + R)
+    busy = wave = 0
+    for a in (0, 1):
+        lanes = passes[:, :, a, :].reshape(-1)
+        pad = (-len(lanes)) % 64
+        w = np.concatenate([lanes, np.zeros(pad, dtype=lanes.dtype)]).reshape(-1, 64)
+        busy += int(w.sum())
+        wave += 64 * int(w.max(axis=1).sum())
+    print("    lane-passes spent idle (a finished lane waiting for its wavefront's slowest): %.1f %% of %d" % (100.0 * (1.0 - busy / wave), wave))
+    print("VERDICT pose_ik device forms against one host thread: (a) %.2fx, (b) %.1fx"
+          % (np.median(ta["ccmp_pose_ik_ref (one thread)"]) / np.median(ta["host form (device)"]),
+             np.median(tb["ccmp_pose_ik_ref (one thread)"]) / np.median(tb["device form"])))
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -804,7 +892,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, run)}
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
     cmds[sys.argv[1]](sys.argv[2:])
