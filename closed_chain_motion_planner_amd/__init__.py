@@ -17,4 +17,6 @@ from .roadmap import Roadmap, pose_distance, pose_from_t_wo  # noqa: F401
 
 from .ik import ik_options, pose_ik_ref  # noqa: F401
 
+from .object import ObjectChecker, object_propose_ref, object_valid_ref, pose_interpolate  # noqa: F401
+
 __version__ = "0.6.0"

@@ -84,6 +84,8 @@ EXPORTS = [
     "ccmp_roadmap_truncate", "ccmp_roadmap_read", "ccmp_roadmap_knn", "ccmp_roadmap_connect",
     "ccmp_roadmap_append_host", "ccmp_roadmap_set_joints_host", "ccmp_roadmap_read_host", "ccmp_roadmap_knn_host", "ccmp_roadmap_connect_host",
     "ccmp_ik_opts_default", "ccmp_pose_ik_batch", "ccmp_pose_ik_host", "ccmp_pose_ik_ref", "ccmp_roadmap_grow", "ccmp_roadmap_grow_host",
+    "ccmp_pose_interpolate", "ccmp_object_create", "ccmp_object_destroy", "ccmp_object_num_triangles",
+    "ccmp_object_valid_batch", "ccmp_object_valid_host", "ccmp_object_valid_ref", "ccmp_object_propose_batch", "ccmp_object_propose_host", "ccmp_object_propose_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -216,6 +218,19 @@ def lib():
         "ccmp_roadmap_grow_host": ([vp, pp, vp, C.c_double, C.POINTER(CcmpIkOpts), dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64,
                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, u8p, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32), u8p,
                                     C.POINTER(C.c_int32), u8p, dp], C.c_int),
+        "ccmp_pose_interpolate": ([dp, dp, C.c_double, dp], None),
+        "ccmp_object_create": ([vp, dp, C.c_int, C.POINTER(CcmpBox), C.c_int, C.POINTER(vp)], C.c_int),
+        "ccmp_object_destroy": ([vp], None),
+        "ccmp_object_num_triangles": ([vp], C.c_int),
+        "ccmp_object_valid_batch": ([vp, vp, vp, C.c_size_t, C.c_double, vp, vp, vp], C.c_int),
+        "ccmp_object_valid_host": ([vp, vp, dp, C.c_size_t, C.c_double, u8p, C.POINTER(C.c_uint32)], C.c_int),
+        "ccmp_object_valid_ref": ([dp, C.c_int, C.POINTER(CcmpBox), C.c_int, dp, C.c_size_t, C.c_double, C.c_int, u8p, C.POINTER(C.c_uint32)], C.c_int),
+        "ccmp_object_propose_batch": ([vp, vp, vp, vp, C.c_int, C.c_size_t, C.c_double, C.c_double, dp, dp, C.c_int, C.c_uint64, C.c_uint64, C.c_double,
+                                       vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_object_propose_host": ([vp, vp, dp, dp, C.c_int, C.c_size_t, C.c_double, C.c_double, dp, dp, C.c_int, C.c_uint64, C.c_uint64, C.c_double,
+                                      dp, C.POINTER(C.c_int32), dp, u8p], C.c_int),
+        "ccmp_object_propose_ref": ([dp, C.c_int, C.POINTER(CcmpBox), C.c_int, dp, dp, C.c_int, C.c_size_t, C.c_double, C.c_double, dp, dp, C.c_int, C.c_uint64,
+                                     C.c_uint64, C.c_double, dp, C.POINTER(C.c_int32), dp, u8p], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -247,6 +262,8 @@ CALL_PROJECT, CALL_SAMPLE_PROJECT, CALL_PROJECT_ANALYTIC, CALL_GEODESIC, CALL_GE
 CALL_GEODESIC_SCENE, CALL_KNN, CALL_CONNECT = 6, 7, 8
 CALL_ROADMAP_KNN, CALL_ROADMAP_CONNECT = 10, 11  # (9 is not assigned)
 CALL_POSE_IK = 13  # (12 is not assigned)
+CALL_OBJECT_PROPOSE = 15  # (14 is not assigned)
+OBJECT_MAX_TRIANGLES, OBJECT_MAX_ATTEMPTS, MAX_BOXES = 16384, 16, 8  # ccmp.h: CCMP_OBJECT_MAX_*, CCMP_MAX_BOXES
 IK_MAX_SEEDS, IK_MAX_RESTARTS, IK_MAX_ROUNDS = 16, 31, 256  # ccmp.h: CCMP_IK_MAX_*
 METRIC_JOINT, METRIC_OBJECT = 0, 1  # ccmp.h: CCMP_METRIC_*
 KNN_ALL, KNN_NOT_SELF, KNN_EARLIER = 0, 1, 2  # ccmp.h: CCMP_KNN_*

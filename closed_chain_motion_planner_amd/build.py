@@ -28,6 +28,9 @@ Translation units with deliberately different flags:
   ccmp_kernels_ik.hip    -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   growTree's sampleCalibGoal step: pose-targeted IK (ccmp_ik.h), one candidate per lane, and its selection rule;
                          without machine LICM (two wavefronts per SIMD instead of one)
   ccmp_ik.cpp            -ffp-contract=off -DCCMP_USE_FMA   ccmp_pose_ik_*: checks, launches, and the same solver text on the host (ccmp_pose_ik_ref, same bits as the kernels)
+  ccmp_kernels_object.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the head of growTree: object-pose proposal (interpolate, SE3 Gaussian draw) and the
+                         mesh-against-workspace test (ccmp_object.h), one 256-lane block per pose, the triangles strided over the lanes
+  ccmp_object.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_object_*: checks, launches, and the same text on the host (the *_ref forms, same bits as the kernels)
 """
 import os
 import shutil
@@ -87,13 +90,17 @@ _UNITS = [
     # literals of sincos / atan would be held in registers across the round loop: 256 + 65 registers, one wavefront per SIMD, instead
     # of 190 and two); registers only, never scratch
     ("ccmp_kernels_ik.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-mllvm", "-disable-machine-licm"]),
+    # the head of growTree (ccmp_object.h): one block per pose, one triangle per lane and chunk; the k-NN unit's flags; registers only, never scratch
+    ("ccmp_kernels_object.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     ("ccmp_scene.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
     # the roadmap store and the host side of the object metric (ccmp_pose.h in the rounding model of the kernels)
     ("ccmp_roadmap.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
     # ccmp_pose_ik_*: the checks and launches, and ccmp_ik.h compiled for the host (ccmp_pose_ik_ref: the kernels' bits without a device)
     ("ccmp_ik.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # ccmp_object_*: the checks and launches, and ccmp_object.h compiled for the host (the *_ref forms: the kernels' bits without a device)
+    ("ccmp_object.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -136,6 +143,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"geodesic_row16_(scene_)?kernel", 0),  # analytic mode's extend step and its scene variant, both instantiations (diagonal and general base frames)
     (r"knn_|connect_(gather|fix)_kernel", 0),  # the connection step: per-thread lists of up to 16 (distance, index) pairs in registers, every instantiation
     (r"ik_", 0),  # pose-targeted IK: the 6x6 system, the kept sines and cosines and the iterate live in registers, both instantiations
+    (r"object_", 0),  # the head of growTree: a lane's triangle, the pose's frame and one box at a time live in registers, every kernel of the unit
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; }
+namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -146,7 +146,25 @@ struct IkCall {
   double *rec_d2;       // [candidates]
 };
 
+/* one call on an object checker (ccmp_object_*; csrc/ccmp_object.h): the mesh as nine planes of `plane` doubles on the device, the boxes
+ * and the bounding sphere as the kernels take them by value */
+constexpr int kObjectThreads = 256; // lanes per block of the object kernels: one block per pose / grow index, the triangles strided over them
+struct ObjectCall {
+  const ccmp::object_boxes *boxes;
+  const ccmp::object_sphere *sphere;
+  const double *tri; // [9][plane]
+  int M; size_t plane;
+  int n_boxes;
+};
+
 #pragma GCC visibility push(hidden)
+/* ccmp_object_create: rows [M][9] -> planes [9][plane] */
+hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
+/* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */
+hipError_t object_valid(const ObjectCall &c, const double *poses, size_t T, double inflate, uint8_t *valid, uint32_t *hit_mask, hipStream_t st);
+/* one block per grow index: interpolate, draw, test, attempt by attempt */
+hipError_t object_propose(const ObjectCall &c, const ccmp::object_draw &D, const double *from_poses, const double *to_poses, size_t G, double *pose_out,
+                          int32_t *which, double *cand_pose, uint8_t *cand_valid, hipStream_t st);
 hipError_t ik_solve(const IkCall &c, hipStream_t st);
 hipError_t ik_select(const IkCall &c, double *q_out, uint8_t *ok, int32_t *which, hipStream_t st);
 /* ccmp_roadmap_grow: seeds[q][r] = the store's joint row nbr_idx[q][r] (NaN for an empty slot) */

@@ -527,6 +527,14 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
             n, kConnectDescribeK, o.restarts, o.max_rounds, 2 * ((lanes + 63) / 64), 2 * lanes, (n + 63) / 64);
       break;
     }
+    case CCMP_CALL_OBJECT_PROPOSE:
+      // n = the grow indices; the reference's two attempts and a mesh of 1024 triangles assumed.  The shape is fixed: one 256-lane
+      // block per grow index, the triangles strided over its lanes; no workspace.
+      L.add("object_propose G=%zu (2 attempts, 1024 triangles assumed): object_propose_kernel x %zu blocks of %d lanes (one grow index per block, attempt by "
+            "attempt: interpolate, draw, then the mesh test in %d chunks of %d triangles, leaving at the first chunk with a hit); object_valid_kernel "
+            "takes the same shape, one pose per block",
+            n, n, ccmp_launch::kObjectThreads, 1024 / ccmp_launch::kObjectThreads, ccmp_launch::kObjectThreads);
+      break;
     default: return CCMP_EINVAL;
   }
   // without a context the plan is the built-in policy on an ASSUMED device: say so (block counts and the thresholds that mark

@@ -198,6 +198,30 @@ class Roadmap:
         check(_lib.lib().ccmp_roadmap_grow(*head, qp.data_ptr(), *tail, *[out[n].data_ptr() for n in order], _stream_handle(stream)), "ccmp_roadmap_grow")
         return out
 
+    def grow_toward(self, checker, from_poses, goal_pose, k, t=0.3, sigma=0.2, lo=None, hi=None, attempts=2, rng_seed=0, first_index=0, inflate=0.0,
+                    **grow_args):
+        """The whole of growTree's device part (stefanBiPRM.cpp:255-351): `checker.propose` (an `ObjectChecker`: interpolate from_poses[g]
+        towards goal_pose, draw, test the mesh, `attempts` times), then `grow` on the poses that were found.  Indices without a valid
+        candidate (which = -1: the reference's TRAPPED) never reach `grow`.  The flags make one small host read in between — growTree
+        needs that decision on the host anyway.  Returns `grow`'s dict over the kept poses plus "which" (G,), "rows" (the grow index g of
+        every row of the other entries) and "poses" (the kept poses); rng_seed and first_index serve both the draw and the IK restarts
+        (row r of `grow` uses first_index + r); grow_args go to `grow`."""
+        from .object import DEFAULT_HI, DEFAULT_LO
+
+        prop = checker.propose(from_poses, goal_pose, t=t, sigma=sigma, lo=DEFAULT_LO if lo is None else lo, hi=DEFAULT_HI if hi is None else hi,
+                               attempts=attempts, rng_seed=rng_seed, first_index=first_index, inflate=inflate)
+        which = prop["which"]
+        if isinstance(which, np.ndarray):
+            rows = np.flatnonzero(which >= 0)
+            kept = np.ascontiguousarray(prop["pose"][rows])
+        else:
+            rows_t = (which >= 0).nonzero().reshape(-1)  # the host read: the flags decide what grows
+            kept = prop["pose"][rows_t].contiguous()
+            rows = rows_t.cpu().numpy()
+        out = self.grow(kept, k, rng_seed=rng_seed, first_index=first_index, **grow_args)
+        out.update(which=which, rows=rows, poses=kept)
+        return out
+
     def close(self):
         if self._h:
             _lib.lib().ccmp_roadmap_destroy(self._h)

@@ -257,7 +257,9 @@ enum {
   CCMP_CALL_ROADMAP_KNN = 10,      /* ccmp_roadmap_knn with CCMP_METRIC_OBJECT: n = the queries; a store of 65536 nodes and k = 5 assumed */
   CCMP_CALL_ROADMAP_CONNECT = 11,  /* ccmp_roadmap_connect with CCMP_METRIC_OBJECT: the k-NN part as above, then the CCMP_CALL_GEODESIC line for 5 n edges */
   /* (12 is not assigned: it stays an unknown kind) */
-  CCMP_CALL_POSE_IK = 13           /* ccmp_pose_ik_batch: n = the targets; 5 seed slots and the default options (14 restarts) assumed */
+  CCMP_CALL_POSE_IK = 13,          /* ccmp_pose_ik_batch: n = the targets; 5 seed slots and the default options (14 restarts) assumed */
+  /* (14 is not assigned: it stays an unknown kind) */
+  CCMP_CALL_OBJECT_PROPOSE = 15    /* ccmp_object_propose_batch: n = the grow indices; 2 attempts and a mesh of 1024 triangles assumed */
 };
 int ccmp_ctx_describe(const ccmp_ctx *ctx, int call_kind, size_t n, char *buf, size_t cap);
 int ccmp_ctx_device(const ccmp_ctx *ctx);
@@ -695,6 +697,73 @@ int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_s
                            const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
                            int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
                            int32_t *ik_which, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out);
+
+/* ---- the head of growTree: object-pose proposal and the mesh-against-workspace test ------------------------------------------------ */
+/* What the reference does before it grows (stefanBiPRM.cpp:255-276): interpolate the object pose 30 % from the nearest vertex towards the
+ * goal, draw an SE(3) Gaussian sample around that (sigma 0.2, two attempts), ask stefan_checker_->isValid, and only then call
+ * growTree(obj_state_); checkForSolution (:733-752) walks nine interpolated poses 0.1 i towards the goal and stops at the first pose the
+ * checker refuses; stefanFCL::isFeasible (stefanFCL.h:115-138) tests the object's triangle mesh, moved by the pose, against six static
+ * workspace boxes and answers "no" at the first that collides.  These calls close the loop (nearest pose, goal pose) -> vetted candidate
+ * poses -> ccmp_roadmap_grow.
+ * WHAT IS AND IS NOT RESTATED (csrc/ccmp_object.h states every term order): OMPL's SE3StateSpace::interpolate and its compound
+ * sampleGaussian are restated from their published definitions in the rounding model of the rest of the library.  OMPL's random numbers
+ * are not: the six unit deviates of a draw are Box-Muller on counter-based uniforms as the library's joint-space Gaussian sampler forms
+ * them, counters rng_seed ^ (index 12 + 2 j) and rng_seed ^ (index 12 + 2 j + 1).  Nor is OMPL's uniform fall-back for wide rotations:
+ * a sigma with 2 sigma / sqrt(3) > 1.44 is CCMP_EINVAL.  FCL's BVH and GJK code is not restated either: the mesh test is an exact
+ * 13-axis separating-axis test of a triangle against an oriented box (unnormalised axes, no division, no square root; separated only by
+ * a strict >, so touching is a hit; a degenerate triangle answers as the segment or point it is).  It answers the same geometric question
+ * as FCL and is not comparable with it beyond that, as the proxy scene is not comparable with MoveIt.
+ * MESHES ARE THE CALLER'S: triangles as numbers, [M][9] = x0 y0 z0 x1 y1 z1 x2 y2 z2 in the object frame, 1 <= M <=
+ * CCMP_OBJECT_MAX_TRIANGLES.  The library hard-codes no workspace: 1 <= n_boxes <= CCMP_MAX_BOXES boxes of type ccmp_box, whose group is
+ * ignored (half extents, not fcl::Box's side lengths).  Non-finite input: CCMP_EINVAL.
+ * The pose rule: R from the quaternion by Eigen's toRotationMatrix arithmetic, not normalised (utils.h:22); world vertex = R v + p;
+ * hit_mask bit b set iff any triangle hits box b with its half extents enlarged by inflate (finite, >= 0); valid = (hit_mask == 0).  A pose
+ * with a non-finite component gives valid = 0, hit_mask = 0: nothing was tested.  A broad phase (the mesh's bounding sphere, computed at
+ * creation with a slack that rounding cannot eat, against each box) skips boxes a pose cannot reach; it never changes an answer.
+ *   create / destroy   the object lives on the context's device, remembers its context and follows the life-cycle rules of scenes: destroy
+ *                      quiesces the context first; the context must outlive the object or be destroyed first with its service off.  Argument
+ *                      checks come first; a NULL context then answers CCMP_ENODEV on a machine without a HIP device, CCMP_EINVAL otherwise.
+ *   valid_batch        poses [T][8] -> valid [T] (uint8), hit_mask [T] (uint32, nullable).  One 256-lane block per pose.  With hit_mask
+ *                      the mask is complete; without it a block leaves after the first 256 triangles among which one hit (the reference's
+ *                      early return) — valid is the same either way.  Device pointers, asynchronous on hip_stream, capturable.
+ *   propose_batch      grow index g, attempt a = 0 .. attempts - 1 (1 <= attempts <= CCMP_OBJECT_MAX_ATTEMPTS): the candidate is the
+ *                      interpolation from from_poses[g] towards to_poses[g] (to_stride 8) or to_poses[0] (to_stride 0) at t, then the
+ *                      Gaussian draw of index (first_index + g) attempts + a around it with sigma, its position clamped into [lo, hi];
+ *                      sigma == 0 makes the candidate the interpolated pose itself.  pose_out [G][8] = the first valid candidate and
+ *                      which [G] = its attempt, or a NaN row (pad 0) and -1.  cand_pose [G][attempts][8] and cand_valid [G][attempts]
+ *                      (both nullable): every attempt, and all of them then run.  A total order over attempts: no launch shape changes the
+ *                      result, and a call over G indices equals G calls over one with the matching first_index.
+ *   *_host             the same calls on host buffers, synchronous on the context's stream.
+ *   *_ref              THE SAME TEXT COMPILED FOR THE HOST: raw triangles and boxes instead of a handle, one thread, no device, never
+ *                      CCMP_ENODEV.  The valid form takes broad_phase (0 switches it off: the answers must not change).
+ * The device and host forms answer a NULL context with CCMP_ENODEV on a machine without a HIP device and with CCMP_EINVAL otherwise;
+ * every check runs before the first launch.  CCMP_EINVAL: M or n_boxes out of range, non-finite mesh, box, inflate, t or sigma, a
+ * negative inflate or sigma, the rotation limit above, lo > hi or NaN bounds, attempts out of range, to_stride not 0 or 8, T or G >= 2^31,
+ * an object of another device than the context's, a NULL array with T or G > 0.  T == 0 / G == 0 returns CCMP_OK and touches nothing.
+ * Where a result is NaN (a candidate of a non-finite pose, the row of a grow index without a valid attempt) it is some NaN: its sign and
+ * payload are not specified.
+ * ccmp_pose_interpolate is pure host code beside ccmp_pose_distance and gives the same bits as the kernels. */
+#define CCMP_OBJECT_MAX_TRIANGLES 16384
+#define CCMP_OBJECT_MAX_ATTEMPTS 16
+typedef struct ccmp_object ccmp_object;
+void ccmp_pose_interpolate(const double a[8], const double b[8], double t, double out[8]);
+int ccmp_object_create(ccmp_ctx *ctx, const double *tri, int M, const ccmp_box *boxes, int n_boxes, ccmp_object **out);
+void ccmp_object_destroy(ccmp_object *obj);
+int ccmp_object_num_triangles(const ccmp_object *obj);
+int ccmp_object_valid_batch(ccmp_ctx *ctx, const ccmp_object *obj, const double *poses, size_t T, double inflate, uint8_t *valid, uint32_t *hit_mask,
+                            void *hip_stream);
+int ccmp_object_valid_host(ccmp_ctx *ctx, const ccmp_object *obj, const double *poses, size_t T, double inflate, uint8_t *valid, uint32_t *hit_mask);
+int ccmp_object_valid_ref(const double *tri, int M, const ccmp_box *boxes, int n_boxes, const double *poses, size_t T, double inflate, int broad_phase,
+                          uint8_t *valid, uint32_t *hit_mask);
+int ccmp_object_propose_batch(ccmp_ctx *ctx, const ccmp_object *obj, const double *from_poses, const double *to_poses, int to_stride, size_t G, double t,
+                              double sigma, const double lo[3], const double hi[3], int attempts, uint64_t rng_seed, uint64_t first_index, double inflate,
+                              double *pose_out, int32_t *which, double *cand_pose, uint8_t *cand_valid, void *hip_stream);
+int ccmp_object_propose_host(ccmp_ctx *ctx, const ccmp_object *obj, const double *from_poses, const double *to_poses, int to_stride, size_t G, double t,
+                             double sigma, const double lo[3], const double hi[3], int attempts, uint64_t rng_seed, uint64_t first_index, double inflate,
+                             double *pose_out, int32_t *which, double *cand_pose, uint8_t *cand_valid);
+int ccmp_object_propose_ref(const double *tri, int M, const ccmp_box *boxes, int n_boxes, const double *from_poses, const double *to_poses, int to_stride,
+                            size_t G, double t, double sigma, const double lo[3], const double hi[3], int attempts, uint64_t rng_seed, uint64_t first_index,
+                            double inflate, double *pose_out, int32_t *which, double *cand_pose, uint8_t *cand_valid);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

@@ -627,6 +627,173 @@ private:
   mutable std::string err_what_;
 };
 
+// ---- the head of growTree (include/ccmp.h: ccmp_object_*) ---------------------------------------------------------------------------
+// stefan_checker_ (stefanFCL: the object's triangle mesh against the static workspace boxes) with its questions, and the two places the
+// planner asks them from: the head of growTree() (stefanBiPRM.cpp:255-276: interpolate 30 % towards the goal, draw around that, ask, two
+// attempts — propose) and checkForSolution's ladder (:733-752 — ladder).  The mesh ([M][9], object frame) and the boxes (half extents) are
+// the caller's.  The mesh test is this library's exact separating-axis test, not FCL; the draw is its counter-based Gaussian, not OMPL's
+// RNG (csrc/ccmp_object.h).  Never throws: every question answers "no" (false / 0) when the call failed, and the FIRST failure stays in
+// lastError() / lastErrorMessage() until clearError(), as Projector::sampleCalibGoal does.  Host pointers throughout.  Built on a
+// Projector (its context and its mutex; it must outlive the checker) or on a bare context.
+class ObjectChecker {
+public:
+  ObjectChecker(const Projector &proj, const double *tri, int M, const ccmp_box *boxes, int n_boxes) noexcept : ctx_(proj.ctx()), mu_(&proj.mutex())
+  {
+    create(tri, M, boxes, n_boxes);
+  }
+  ObjectChecker(ccmp_ctx *ctx, const double *tri, int M, const ccmp_box *boxes, int n_boxes) noexcept : ctx_(ctx), mu_(&own_mu_)
+  {
+    create(tri, M, boxes, n_boxes);
+  }
+  ~ObjectChecker()
+  {
+    if (!obj_) return;
+    std::lock_guard<std::mutex> hold(*mu_);
+    ccmp_object_destroy(obj_);
+  }
+  ObjectChecker(const ObjectChecker &) = delete;
+  ObjectChecker &operator=(const ObjectChecker &) = delete;
+
+  // the half extents of every box grow by this much in every question (0 by default)
+  void setInflate(double inflate) noexcept { inflate_ = inflate; }
+  // position bounds of propose's draw (the planner's object space bounds; unbounded by default)
+  void setBounds(const double lo[3], const double hi[3]) noexcept
+  {
+    for (int i = 0; i < 3; i++) { lo_[i] = lo[i]; hi_[i] = hi[i]; }
+  }
+  // the draws' stream: propose number n of this checker uses index first_index + n (as every OMPL sampler owns its RNG)
+  void setStream(uint64_t seed, uint64_t first_index = 0) noexcept { seed_ = seed; next_ = first_index; }
+  uint64_t nextIndex() const noexcept { return next_; }
+
+  // stefanFCL::isValid on a pose row (x y z qx qy qz qw pad)
+  bool isValidPose(const double pose8[8]) const noexcept
+  {
+    uint8_t valid = 0;
+    const bool ran = call([&] { return ccmp_object_valid_host(ctx_, obj_, pose8, 1, inflate_, &valid, nullptr); }, "ccmp_object_valid_host");
+    return ran && valid != 0;
+  }
+  // stefanFCL::isValid(Eigen::Isometry3d): any type with linear()(r, c) and translation()(i).  The rotation goes through Eigen's
+  // Quaterniond(Matrix3d) arithmetic (ccmp_pose_from_t_wo), the inverse of the StateToIsometry that produced it (utils.h:22)
+  template <class Isometry>
+  bool isValid(const Isometry &T) const noexcept
+  {
+    double t_wo[12], pose[8];
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) t_wo[3 * r + c] = T.linear()(r, c);
+      t_wo[9 + r] = T.translation()(r);
+    }
+    ccmp_pose_from_t_wo(t_wo, pose);
+    return isValidPose(pose);
+  }
+  // stefanFCL::isValid(ob::State *): state->as<ob::SE3StateSpace::StateType>(), read by the adapter's poseOf
+  template <class SE3State>
+  bool isValid(const SE3State *state) const noexcept
+  {
+    double pose[8];
+    poseOf(*state, pose);
+    return isValidPose(pose);
+  }
+  template <class SE3State>
+  bool isValid(SE3State *state) const noexcept { return isValid(static_cast<const SE3State *>(state)); }
+  // stefanFCL::is_Valid(pos, quat): quat as x y z w
+  bool is_Valid(const double pos[3], const double quat_xyzw[4]) const noexcept
+  {
+    const double pose[8] = {pos[0], pos[1], pos[2], quat_xyzw[0], quat_xyzw[1], quat_xyzw[2], quat_xyzw[3], 0.0};
+    return isValidPose(pose);
+  }
+  // The head of growTree() for one nearest pose: out8 = the first of `attempts` candidates (interpolate from8 -> goal8 at t, then the
+  // SE(3) Gaussian draw with sigma) whose mesh is free; *which (nullable) = its attempt.  false = TRAPPED (out8 NaN-filled, *which = -1)
+  // or a failed call (the error in lastError()).  One index of the stream per call that ran.
+  bool propose(const double from8[8], const double goal8[8], double out8[8], int *which = nullptr, double t = 0.3, double sigma = 0.2,
+               int attempts = 2) noexcept
+  {
+    int32_t w = -1;
+    for (int i = 0; i < 7; i++) out8[i] = std::numeric_limits<double>::quiet_NaN();
+    out8[7] = 0.0;
+    if (which) *which = -1;
+    const bool ran = call([&] {
+      const int rc = ccmp_object_propose_host(ctx_, obj_, from8, goal8, 0, 1, t, sigma, lo_, hi_, attempts, seed_, next_, inflate_, out8, &w, nullptr, nullptr);
+      if (rc == CCMP_OK) next_++;
+      return rc;
+    }, "ccmp_object_propose_host");
+    if (!ran) {
+      for (int i = 0; i < 7; i++) out8[i] = std::numeric_limits<double>::quiet_NaN();
+      return false;
+    }
+    if (which) *which = w;
+    return w >= 0;
+  }
+  // checkForSolution's ladder: poses [steps][8] (nullable) = the interpolation from8 -> goal8 at 0.1 i, i = 1..steps; returns how many of
+  // them are valid before the first one refused (0 also when the call failed)
+  int ladder(const double from8[8], const double goal8[8], std::vector<double> *poses = nullptr, int steps = 9) const noexcept
+  {
+    if (steps < 1) return 0;
+    std::vector<double> own;
+    std::vector<uint8_t> valid;
+    std::vector<double> *rows = poses ? poses : &own;
+    try {
+      rows->assign((size_t)steps * 8, 0.0);
+      valid.assign((size_t)steps, 0);
+    } catch (...) {
+      record(CCMP_ENOMEM, "ObjectChecker::ladder");
+      return 0;
+    }
+    for (int i = 1; i <= steps; i++) ccmp_pose_interpolate(from8, goal8, 0.1 * i, rows->data() + (size_t)(i - 1) * 8);
+    if (!call([&] { return ccmp_object_valid_host(ctx_, obj_, rows->data(), (size_t)steps, inflate_, valid.data(), nullptr); }, "ccmp_object_valid_host")) return 0;
+    int n = 0;
+    while (n < steps && valid[(size_t)n]) n++;
+    return n;
+  }
+
+  int numTriangles() const noexcept { return ccmp_object_num_triangles(obj_); }
+  int lastError() const noexcept { return err_code_; }
+  std::string lastErrorMessage() const { return err_what_; }
+  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
+  ccmp_object *handle() const noexcept { return obj_; }
+
+private:
+  void create(const double *tri, int M, const ccmp_box *boxes, int n_boxes) noexcept
+  {
+    for (int i = 0; i < 3; i++) { lo_[i] = -1e30; hi_[i] = 1e30; }
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(*mu_);
+      rc = ccmp_object_create(ctx_, tri, M, boxes, n_boxes, &obj_);
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) { obj_ = nullptr; record(rc, "ccmp_object_create"); }
+  }
+  template <class F>
+  bool call(F &&body, const char *what) const noexcept
+  {
+    if (!obj_) { record(CCMP_EINVAL, what); return false; }
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(*mu_);
+      rc = body();
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) record(rc, what);
+    return rc == CCMP_OK;
+  }
+  void record(int code, const char *what) const noexcept
+  {
+    if (err_code_ != CCMP_OK) return;
+    err_code_ = code;
+    try { err_what_ = std::string(what) + ": " + ccmp_strerror(code); } catch (...) {}
+  }
+  ccmp_ctx *ctx_ = nullptr;
+  std::mutex *mu_ = nullptr;
+  mutable std::mutex own_mu_;
+  ccmp_object *obj_ = nullptr;
+  double inflate_ = 0.0, lo_[3], hi_[3];
+  uint64_t seed_ = 0, next_ = 0;
+  mutable int err_code_ = CCMP_OK;
+  mutable std::string err_what_;
+};
+
 // One planner process, several GPUs (the reference's shape: src/main.cpp is one process): one context per device and an
 // RCCL communicator over them.  sampleProjectSharded / projectSharded spread a batch over the GPUs in contiguous shards,
 // every GPU compacts its valid states into a fixed-capacity block and ONE all-gather brings them together; the valid

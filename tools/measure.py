@@ -25,6 +25,9 @@
     python tools/measure.py ik [reps_a] [reps_b] [T_b]      pose-targeted IK (growTree's sampleCalibGoal): (a) one pose x 5 seeds x 14 restarts through the host
                                                            form, (b) T_b = 4096 poses x 5 x 14 through the device form, each against ccmp_pose_ik_ref on one
                                                            thread on the same inputs, alternating in one process; histogram of rounds, idle lane-rounds
+    python tools/measure.py object [reps_a] [reps_b] [G_b]  the head of growTree (object-pose proposal + mesh test): (a) propose with G = 1, 2 attempts, a dumbbell of
+                                                           ~1 000 triangles against the six fixture boxes through the host form, (b) G_b = 4096 through the device form,
+                                                           (c) valid on 4096 poses of a ~8 600-triangle sphere, each against the *_ref form on one thread on the same inputs
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -822,6 +825,93 @@ def ik(argv):
              np.median(tb["ccmp_pose_ik_ref (one thread)"]) / np.median(tb["device form"])))
 
 
+def object_(argv):
+    """ccmp_object_propose_host / _batch and ccmp_object_valid_batch against the *_ref forms (the same text on one host thread) on the same
+    inputs; the outputs are compared bit for bit while they are timed.  Meshes are procedural (tests/object_cases.py), the workspace is
+    the fixture tests/golden/object_workspace.json."""
+    sys.path.insert(0, "tests")
+    from object_cases import big_sphere, dumbbell, random_poses, workspace
+
+    from closed_chain_motion_planner_amd import ObjectChecker, object_propose_ref, object_valid_ref
+
+    reps_a = int(argv[0]) if len(argv) > 0 else 30
+    reps_b = int(argv[1]) if len(argv) > 1 else 3
+    Gb = int(argv[2]) if len(argv) > 2 else 4096
+    ctx = Context(0)
+    boxes, mesh, big = workspace(), dumbbell(), big_sphere()
+    chk, chk_big = ObjectChecker(ctx, mesh, boxes), ObjectChecker(ctx, big, boxes)
+    rng = np.random.default_rng(0x0B)
+    lo, hi = (0.1, -0.5, 1.25), (1.2, 0.5, 1.8)
+    frm = random_poses(rng, Gb, lo=(0.2, -0.45, 1.25), hi=(1.1, 0.45, 1.8))
+    goal = random_poses(rng, 1, lo=(0.4, -0.2, 1.4), hi=(0.9, 0.2, 1.7))
+    kw = dict(t=0.3, sigma=0.2, lo=lo, hi=hi, attempts=2, rng_seed=0x0B)
+    print("meshes: %d and %d triangles; %d boxes" % (len(mesh), len(big), len(boxes)))
+
+    def same(a, b, keys):
+        return all(np.array_equal(np.asarray(a[k]).view(np.uint8), np.asarray(b[k]).view(np.uint8)) for k in keys)
+
+    # (a) the planner's shape: one nearest pose per call, host pointers, host clock around the synchronous calls
+    ta = {"host form (device)": [], "ccmp_object_propose_ref (one thread)": []}
+    agree = True
+    for i in range(reps_a + 3):
+        g = i % Gb
+        t0 = time.perf_counter()
+        dev = chk.propose(frm[g:g + 1], goal, first_index=g, **kw)
+        t1 = time.perf_counter()
+        ref = object_propose_ref(mesh, boxes, frm[g:g + 1], goal, first_index=g, **kw)
+        t2 = time.perf_counter()
+        agree = agree and same(dev, ref, ("pose", "which"))
+        if i >= 3:
+            ta["host form (device)"].append((t1 - t0) * 1e3)
+            ta["ccmp_object_propose_ref (one thread)"].append((t2 - t1) * 1e3)
+    print("(a) propose G = 1, 2 attempts, %d triangles, host form, wall clock; outputs identical: %s" % (len(mesh), agree))
+    for name, ms in ta.items():
+        print("    %-40s %s" % (name, _stat(ms)))
+
+    # (b) the batch, (c) valid on the large mesh: device pointers, device events; the contender once per round on the host clock
+    frm_d, goal_d = torch.from_numpy(frm).cuda(), torch.from_numpy(goal).cuda()
+    poses = random_poses(rng, 4096)
+    poses_d = torch.from_numpy(poses).cuda()
+    tb = {"device form": [], "ccmp_object_propose_ref (one thread)": []}
+    tc = {"device form, mask": [], "device form, early exit": [], "ccmp_object_valid_ref (one thread)": []}
+    chk.propose(frm_d, goal_d, **kw), chk_big.valid(poses_d, want_mask=True), chk_big.valid(poses_d)
+    torch.cuda.synchronize()
+    for _ in range(reps_b):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record()
+        dev = chk.propose(frm_d, goal_d, **kw)
+        e[1].record()
+        dv = chk_big.valid(poses_d, want_mask=True)
+        e[2].record()
+        dq = chk_big.valid(poses_d)
+        e[3].record()
+        torch.cuda.synchronize()
+        tb["device form"].append(e[0].elapsed_time(e[1]))
+        tc["device form, mask"].append(e[1].elapsed_time(e[2]))
+        tc["device form, early exit"].append(e[2].elapsed_time(e[3]))
+        t0 = time.perf_counter()
+        ref = object_propose_ref(mesh, boxes, frm, goal, **kw)
+        t1 = time.perf_counter()
+        rv = object_valid_ref(big, boxes, poses, want_mask=True)
+        t2 = time.perf_counter()
+        tb["ccmp_object_propose_ref (one thread)"].append((t1 - t0) * 1e3)
+        tc["ccmp_object_valid_ref (one thread)"].append((t2 - t1) * 1e3)
+        agree = agree and same({k: v.cpu().numpy() for k, v in dev.items()}, ref, ("pose", "which"))
+        agree = agree and np.array_equal(dv[0].cpu().numpy(), rv[0]) and np.array_equal(dv[1].cpu().numpy().view(np.uint32), rv[1]) and np.array_equal(dq.cpu().numpy(), rv[0])
+    print("(b) propose G = %d, 2 attempts, %d triangles, device form, device events; outputs identical: %s" % (Gb, len(mesh), agree))
+    for name, ms in tb.items():
+        print("    %-40s %s" % (name, _stat(ms)))
+    print("    found %d of %d; by the first attempt %d" % (int((ref["which"] >= 0).sum()), Gb, int((ref["which"] == 0).sum())))
+    print("(c) valid on 4096 poses, %d triangles; %d valid" % (len(big), int(rv[0].sum())))
+    for name, ms in tc.items():
+        print("    %-40s %s" % (name, _stat(ms)))
+    print("VERDICT object device forms against one host thread: (a) %.2fx, (b) %.1fx, (c) %.1fx with the mask, %.1fx with the early exit"
+          % (np.median(ta["ccmp_object_propose_ref (one thread)"]) / np.median(ta["host form (device)"]),
+             np.median(tb["ccmp_object_propose_ref (one thread)"]) / np.median(tb["device form"]),
+             np.median(tc["ccmp_object_valid_ref (one thread)"]) / np.median(tc["device form, mask"]),
+             np.median(tc["ccmp_object_valid_ref (one thread)"]) / np.median(tc["device form, early exit"])))
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -893,6 +983,7 @@ def run(argv):
 
 if __name__ == "__main__":
     cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, run)}
+    cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
     cmds[sys.argv[1]](sys.argv[2:])
