@@ -156,3 +156,194 @@ def test_graph_capture(world):
         nd, qs = torch.as_tensor(nodes).cuda(), torch.as_tensor(queries[:Q]).cuda()
         ref = _capture_and_replay(lambda: c.nearest_k_batch(nd, qs, 5))
         _same((ref[0].cpu().numpy(), ref[1].cpu().numpy()), table.rank(5, n_queries=Q))
+
+
+# ---- every list size, merge width, node order and tie pattern -----------------------------------------------------------------------
+# KC is the instantiation >= k (1, 4, 8, 16): k = 2..4 runs List<4> / block_merge<4, .>, k = 8 fills List<8>, k = 9..15 leaves slots of
+# List<16> unused.  Above 64 partitions the lists merge in knn_merge_kernel<KC, 256>; the plan is restated in knn_reference.plan from the
+# constants the describe line prints, and every test asserts the partition count it is meant to reach before it compares.
+from knn_reference import MERGE_NARROW, described_shape, nodes_for_partitions, plan, plan_constants  # noqa: E402
+
+K_SIZES = (2, 3, 4, 6, 8, 9, 15)
+
+
+def _plan(c, Q, N):
+    """(few form?, nodes per partition, partitions) of a call on this chip"""
+    return plan(c.ctx.num_cus, Q, N, TILE, *plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_KNN, Q)))
+
+
+def test_plan_restated(world):
+    c = world[0]
+    assert plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_KNN, 1)) == (FEW_QUERIES, MIN_PARTITION, 256)
+    for Q in (1, FEW_QUERIES, FEW_QUERIES + 1, Q_MAX, 5000):  # the describe line assumes 65 536 nodes
+        line = _lib.describe(c.ctx.handle, _lib.CALL_KNN, Q)
+        few, part, partitions = _plan(c, Q, 65536)
+        assert described_shape(line) == (partitions, part) and few == ("knn_few_kernel" in line), line
+    assert _plan(c, 1, N_MAX)[2] == _plan(c, Q_MAX, N_MAX)[2] == 5 and _plan(c, 37, 1000)[2] == 1
+
+
+@pytest.mark.parametrize("N", [3, 1000, N_MAX])
+@pytest.mark.parametrize("Q", [1, 37, Q_MAX])
+def test_every_list_size(world, N, Q):
+    c, nodes, queries, table = world
+    assert _plan(c, Q, N)[::2] == (Q <= FEW_QUERIES, 5 if N == N_MAX else 1)
+    for k in K_SIZES:
+        got = _knn(c, nodes[:N], queries[:Q], k)
+        _same(got, table.rank(k, n_nodes=N, n_queries=Q))
+        assert (got[0] >= 0).sum() == Q * min(k, N) and np.all(np.isinf(got[1][got[0] < 0]))
+
+
+@pytest.fixture(scope="module")
+def self_table(world, oracle_det):
+    """rows 1030 .. 1069 of the first 1 300 nodes as queries: query q is node 1030 + q, in the second partition"""
+    nd = world[1][:1300]
+    return nd, DistanceTable(oracle_det, nd[1030:1070], nd)
+
+
+@pytest.mark.parametrize("mode", [KNN_NOT_SELF, KNN_EARLIER])
+def test_modes_in_the_second_partition(world, self_table, mode):
+    c, _, queries, table = world
+    nd, own = self_table
+    assert _plan(c, 5, 1300)[1:] == _plan(c, 40, 1300)[1:] == (1024, 2)
+    for Q in (5, 40):
+        for k in K_SIZES:
+            got = _knn(c, nd, nd[1030: 1030 + Q], k, mode, 1030)
+            _same(got, own.rank(k, mode, 1030, n_queries=Q))
+            if mode == KNN_NOT_SELF:
+                assert not np.any(got[0] == (1030 + np.arange(Q))[:, None]) and np.all(got[1] > 0)
+            else:
+                assert np.all(got[0] < (1030 + np.arange(Q))[:, None]) and np.all(got[0] >= 0)
+    # self_base + q >= N: the mode excludes nothing (from q = 5 on with self_base = N - 5, for every q with self_base = N)
+    for s in (1295, 1300):
+        for Q, k in ((5, 3), (40, 8), (40, 15)):
+            got = _knn(c, nd, queries[:Q], k, mode, s)
+            _same(got, table.rank(k, mode, s, n_nodes=1300, n_queries=Q))
+            _same((got[0][max(0, 1300 - s):], got[1][max(0, 1300 - s):]), tuple(a[max(0, 1300 - s):] for a in table.rank(k, n_nodes=1300, n_queries=Q)))
+
+
+# Random rows alone would leave most partitions' lists out of the result (16 places, up to 256 lists): query 0's nearest nodes are
+# planted — the last node of each node count first (a partition of one node at 65 537; partition 255; the last partition past the
+# clamp), then the first node, both sides of a partition boundary and indices across the range — so the lists that must reach the
+# result come from the highest merge threads as well as the lowest.
+PLANTED = (262144, 262143, 65536, 204800, 0, 1023, 1024, 32773, 40000, 66000, 100000, 131072, 200000, 230000, 250000, 261000)
+
+
+@pytest.fixture(scope="module")
+def big(world, oracle_det):
+    """random rows inside the joint bounds (k-NN does not need the manifold) and tables over them, made on demand and shared: a table
+    over fewer nodes or queries is a slice of one that exists"""
+    c = world[0]
+    rng = np.random.default_rng(0xB16)
+    lb, ub = np.array(list(c.problem.lb) * 2), np.array(list(c.problem.ub) * 2)
+    state = {"nodes": np.empty((0, 14)), "tables": []}
+    queries = np.ascontiguousarray(rng.uniform(lb, ub, size=(9, 14)))
+
+    def get(Q, N):
+        if N > len(state["nodes"]):  # (only on another CU count: the first request is the largest here)
+            state["nodes"] = np.ascontiguousarray(np.concatenate([state["nodes"], np.random.default_rng(N).uniform(lb, ub, size=(N - len(state["nodes"]), 14))]))
+            state["tables"] = []
+            for r, j in enumerate(PLANTED):  # query 0's nearest nodes, nearest first, whatever the node count
+                if j < len(state["nodes"]):
+                    state["nodes"][j] = queries[0]
+                    state["nodes"][j, 0] += 1e-3 * (1 + r)
+        for t in state["tables"]:
+            if t.D.shape[0] >= Q and t.D.shape[1] >= N:
+                return state["nodes"][:N], queries[:Q], t
+        state["tables"].append(DistanceTable(oracle_det, queries[:Q], state["nodes"][:N]))
+        return state["nodes"][:N], queries[:Q], state["tables"][-1]
+
+    return get
+
+
+# on 256 CUs: 262 145 nodes are past the clamp at 256 partitions (partitions of 1 280), 262 144 are 256 partitions, 65 537 are 65
+@pytest.mark.parametrize("want,N256,Q", [(205, 262145, 1), (256, 262144, 1), (65, 65537, 9), (65, 65537, 1)])
+def test_wide_merge(world, big, want, N256, Q):
+    c = world[0]
+    consts = plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_KNN, Q))
+    N = nodes_for_partitions(c.ctx.num_cus, Q, TILE, consts, want, N256)
+    few, part, partitions = _plan(c, Q, N)
+    assert partitions == want > MERGE_NARROW and few == (Q == 1) and partitions <= consts[2]
+    assert (part > consts[1]) == (want == 205)  # past the clamp the partitions grow beyond their least size
+    nodes, queries, table = big(Q, N)
+    for k in (3, 16):
+        want_idx, want_dist = table.rank(k, n_nodes=N, n_queries=Q)
+        if c.ctx.num_cus == 256:  # the planted nodes are query 0's list: from the last partition down
+            planted = [j for j in PLANTED if j < N][:k]
+            assert list(want_idx[0, :len(planted)]) == planted and planted[0] // part == partitions - 1 and len(planted) >= min(k, 6)
+        _same(_knn(c, nodes, queries, k), (want_idx, want_dist))
+
+
+@pytest.mark.parametrize("order", ["descending", "ascending"])
+def test_sorted_node_orders(world, order):
+    """the nodes by decreasing reference distance to query 0: every node enters query 0's list and its bound shrinks at every insert;
+    by increasing distance: the list is final after k nodes and the pre-filter refuses all others, ties included"""
+    c, nodes, queries, table = world
+    d = table.D[0]
+    perm = np.lexsort((np.arange(N_MAX), -d if order == "descending" else d))
+    t = table.take(perm)
+    assert np.all(np.diff(t.D[0]) <= 0 if order == "descending" else np.diff(t.D[0]) >= 0)
+    for Q in (1, 9):
+        for k in (4, 16):
+            _same(_knn(c, t.nodes, queries[:Q], k), t.rank(k, n_queries=Q))
+
+
+def _lattice():
+    """4 099 rows whose first nine coordinates are the base-3 digits of j times 0.25, in an order drawn from a fixed seed with three
+    rows of the largest tie class moved into the last partition (three nodes); queries: the zero row, the all-0.25 row, and the
+    half-step row (0.125 in the nine coordinates).  Every difference and every squared sum is exact in binary64, so a few dozen
+    distinct distances remain.  The half-step row is at the same distance from all 256 rows whose digits are 0 or 1: the first 256
+    places of its ranking are one tie, decided by the index alone.  (From the lattice points themselves the ties at the first places
+    are small — 1, 8, 28 rows at the three nearest distances — so those two queries alone would not put 50 rows at the k-th place.)"""
+    j = np.arange(N_MAX)
+    rows = np.zeros((N_MAX, 14))
+    for c in range(9):
+        rows[:, c] = 0.25 * ((j // 3 ** c) % 3)
+    perm = np.random.default_rng(0x7135).permutation(N_MAX)
+    rows = rows[perm]
+    tied = np.flatnonzero((rows[:, :9] <= 0.25).all(axis=1))
+    assert len(tied) == 256
+    last = np.arange(4 * MIN_PARTITION, N_MAX)
+    swap = tied[tied < 4 * MIN_PARTITION][:len(last)]
+    rows[np.concatenate([last, swap])] = rows[np.concatenate([swap, last])]
+    queries = np.zeros((3, 14))
+    queries[1] = 0.25
+    queries[2, :9] = 0.125
+    return np.ascontiguousarray(rows), queries
+
+
+@pytest.fixture(scope="module")
+def lattice(oracle_det):
+    rows, queries = _lattice()
+    return rows, queries, DistanceTable(oracle_det, queries, rows)
+
+
+def test_lattice_ties(world, lattice):
+    c = world[0]
+    rows, queries, table = lattice
+    assert len(np.unique(table.D)) <= 64  # a handful of distinct distances over 3 x 4 099 pairs
+    part = _plan(c, 1, N_MAX)[1]
+    assert _plan(c, 1, N_MAX)[2] == _plan(c, 9, N_MAX)[2] == 5
+    for k in (1, 4, 8, 16):
+        ties = table.ties_at(k, q=2)
+        assert len(ties) >= 50 and set(ties // part) == set(range(5)), (k, len(ties))  # at the k-th place, in every partition
+        for qs in (queries, np.concatenate([queries] * 3)):  # 3 queries: the partitioned form; 9: one query per thread
+            got = _knn(c, rows, qs, k)
+            want = table.rank(k)
+            _same(got, tuple(np.concatenate([a] * (len(qs) // 3)) for a in want))
+            assert np.all(got[1][2] == got[1][2, 0])  # the half-step row's k nearest are one distance: the lowest indices of the tie
+    print("ties at the k-th place, k = 1, 4, 8, 16, per query:", [[len(table.ties_at(k, q)) for k in (1, 4, 8, 16)] for q in range(3)])
+
+
+def test_lattice_ties_through_the_wide_merge(world, lattice):
+    """the lattice tiled to 65 537 rows (row j = lattice row j mod 4 099: sixteen copies of every tie), the three queries in the
+    partitioned form: 65 lists per query meet in knn_merge_kernel<KC, 256>"""
+    c = world[0]
+    rows, queries, table = lattice
+    consts = plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_KNN, 3))
+    N = nodes_for_partitions(c.ctx.num_cus, 3, TILE, consts, 65, 65537)
+    cols = np.arange(N) % N_MAX
+    t = table.take(cols)
+    assert _plan(c, 3, N)[2] == 65 > MERGE_NARROW and _plan(c, 3, N)[0]
+    for k in (4, 16):
+        assert len(t.ties_at(k, 2)) >= 50 * 15
+        _same(_knn(c, t.nodes, queries, k), t.rank(k))

@@ -355,3 +355,225 @@ def test_python_host_forms(world, gpu_ctx):
                                  None, None, None)
     assert L.ccmp_roadmap_connect_host(*args(c.problem, 32)) == -1 and L.ccmp_roadmap_connect_host(*args(bad, 0)) == -1
     assert L.ccmp_roadmap_connect_host(*args(c.problem, 0)) == 0
+
+
+# ---- every list size, merge width, node order and tie pattern under the object metric (tests/test_gpu_knn.py has the joint metric's) --
+from knn_reference import MERGE_NARROW, described_shape, nodes_for_partitions, plan, plan_constants  # noqa: E402
+
+K_SIZES = (2, 3, 4, 6, 8, 9, 15)
+Q0 = np.array([0.5, 0.5, 0.5, 0.5])  # a unit quaternion whose products are exact
+Q_OTHER = np.array([0.0, 0.0, 0.0, 1.0])
+
+
+def _plan(c, Q, N):
+    """(few form?, poses per partition, partitions) of an object-metric call on this chip"""
+    return plan(c.ctx.num_cus, Q, N, TILE, *plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_ROADMAP_KNN, Q)))
+
+
+def _random_poses(rng, n):
+    p = np.zeros((n, 8))
+    p[:, :3] = rng.uniform(-1.0, 1.0, size=(n, 3))
+    q = rng.normal(size=(n, 4))
+    p[:, 3:7] = q / np.linalg.norm(q, axis=1)[:, None]
+    return p
+
+
+def test_plan_restated(world):
+    c = world["c"]
+    assert plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_ROADMAP_KNN, 1)) == (FEW_QUERIES, MIN_PARTITION, 256)
+    for Q in (1, FEW_QUERIES, FEW_QUERIES + 1, Q_MAX, 5000):  # the describe line assumes 65 536 poses
+        line = _lib.describe(c.ctx.handle, _lib.CALL_ROADMAP_KNN, Q)
+        few, part, partitions = _plan(c, Q, 65536)
+        assert described_shape(line) == (partitions, part) and few == ("knn_pose_few_kernel" in line), line
+    assert _plan(c, 1, N_MAX)[2] == _plan(c, Q_MAX, N_MAX)[2] == 5 and _plan(c, 37, 1000)[2] == 1
+
+
+@pytest.mark.parametrize("N", [3, 1000, N_MAX])
+@pytest.mark.parametrize("Q", [1, 37, Q_MAX])
+def test_every_list_size(world, N, Q):
+    c = world["c"]
+    rm = _rm(c, world["nj"][:N], world["np"][:N])
+    assert _plan(c, Q, N)[::2] == (Q <= FEW_QUERIES, 5 if N == N_MAX else 1)
+    for k in K_SIZES:
+        got = _knn(rm, world["qp"][:Q], k)
+        _same(got, world["table"].rank(k, n_nodes=N, n_queries=Q))
+        assert (got[0] >= 0).sum() == Q * min(k, N) and np.all(np.isinf(got[1][got[0] < 0]))
+
+
+@pytest.mark.parametrize("mode", [KNN_NOT_SELF, KNN_EARLIER])
+def test_modes_in_the_second_partition(world, mode):
+    """queries = rows 1030 .. of 1 300 vertices (self_base in the second partition), and self_base + q >= N, where the mode excludes
+    nothing"""
+    c = world["c"]
+    nd = world["np"][:1300]
+    rm = _rm(c, world["nj"][:1300], nd)
+    own = PoseDistanceTable(nd[1030:1070], nd)
+    assert _plan(c, 5, 1300)[1:] == _plan(c, 40, 1300)[1:] == (1024, 2)
+    for Q in (5, 40):
+        for k in K_SIZES:
+            got = _knn(rm, nd[1030: 1030 + Q], k, mode, 1030)
+            _same(got, own.rank(k, mode, 1030, n_queries=Q))
+            if mode == KNN_NOT_SELF:
+                assert not np.any(got[0] == (1030 + np.arange(Q))[:, None])
+            else:
+                assert np.all(got[0] < (1030 + np.arange(Q))[:, None]) and np.all(got[0] >= 0)
+    for s in (1295, 1300):
+        for Q, k in ((5, 3), (40, 8), (40, 15)):
+            got = _knn(rm, world["qp"][:Q], k, mode, s)
+            _same(got, world["table"].rank(k, mode, s, n_nodes=1300, n_queries=Q))
+            _same((got[0][max(0, 1300 - s):], got[1][max(0, 1300 - s):]),
+                  tuple(a[max(0, 1300 - s):] for a in world["table"].rank(k, n_nodes=1300, n_queries=Q)))
+
+
+# query 0's nearest poses are planted as in tests/test_gpu_knn.py: the last pose of each node count first, then the first, both sides of
+# a partition boundary and indices across the range, so the lists that reach the result come from the highest merge threads too
+PLANTED = (262144, 262143, 65536, 204800, 0, 1023, 1024, 32773, 40000, 66000, 100000, 131072, 200000, 230000, 250000, 261000)
+
+
+@pytest.fixture(scope="module")
+def big():
+    """random positions with unit quaternions (k-NN does not need the manifold) and tables over them, made on demand and shared: a
+    table over fewer poses or queries is a slice of one that exists"""
+    state = {"nodes": np.empty((0, 8)), "tables": []}
+    queries = _random_poses(np.random.default_rng(0xB16), 9)
+
+    def get(Q, N):
+        if N > len(state["nodes"]):  # (only on another CU count: the first request is the largest here)
+            state["nodes"] = np.ascontiguousarray(np.concatenate([state["nodes"], _random_poses(np.random.default_rng(N), N - len(state["nodes"]))]))
+            state["tables"] = []
+            for r, j in enumerate(PLANTED):  # query 0's nearest poses, nearest first, whatever the node count: its rotation, 1e-3 apart in x
+                if j < len(state["nodes"]):
+                    state["nodes"][j] = queries[0]
+                    state["nodes"][j, 0] += 1e-3 * (1 + r)
+        for t in state["tables"]:
+            if t.D.shape[0] >= Q and t.D.shape[1] >= N:
+                return state["nodes"][:N], queries[:Q], t
+        state["tables"].append(PoseDistanceTable(queries[:Q], state["nodes"][:N]))
+        return state["nodes"][:N], queries[:Q], state["tables"][-1]
+
+    return get
+
+
+# on 256 CUs: 262 145 poses are past the clamp at 256 partitions (partitions of 1 536), 262 144 are 256 partitions, 65 537 are 65
+@pytest.mark.parametrize("want,N256,Q", [(171, 262145, 1), (256, 262144, 1), (65, 65537, 9), (65, 65537, 1)])
+def test_wide_merge(world, big, want, N256, Q):
+    c = world["c"]
+    consts = plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_ROADMAP_KNN, Q))
+    N = nodes_for_partitions(c.ctx.num_cus, Q, TILE, consts, want, N256)
+    few, part, partitions = _plan(c, Q, N)
+    assert partitions == want > MERGE_NARROW and few == (Q == 1) and partitions <= consts[2]
+    assert (part > consts[1]) == (want == 171)  # past the clamp the partitions grow beyond their least size
+    nodes, queries, table = big(Q, N)
+    rm = _rm(c, None, nodes)
+    for k in (3, 16):
+        want_idx, want_dist = table.rank(k, n_nodes=N, n_queries=Q)
+        if c.ctx.num_cus == 256:  # the planted poses are query 0's list: from the last partition down
+            planted = [j for j in PLANTED if j < N][:k]
+            assert list(want_idx[0, :len(planted)]) == planted and planted[0] // part == partitions - 1 and len(planted) >= min(k, 6)
+        _same(_knn(rm, queries, k), (want_idx, want_dist))
+    rm.close()
+
+
+@pytest.mark.parametrize("order", ["descending", "ascending"])
+def test_sorted_node_orders(world, order):
+    """the vertices by decreasing reference distance to query 0: every one enters query 0's list and its bound shrinks at every insert;
+    by increasing distance: the list is final after k vertices and the pre-filter on |dp| refuses what it can"""
+    d = world["table"].D[0]
+    perm = np.lexsort((np.arange(N_MAX), -d if order == "descending" else d))
+    t = world["table"].take(perm)
+    assert np.all(np.diff(t.D[0]) <= 0 if order == "descending" else np.diff(t.D[0]) >= 0)
+    rm = _rm(world["c"], None, t.nodes)
+    for Q in (1, 9):
+        for k in (4, 16):
+            _same(_knn(rm, world["qp"][:Q], k), t.rank(k, n_queries=Q))
+
+
+def _pose_lattice(side):
+    """4 099 poses on a side^3 lattice of step 0.125 (position index j mod side^3, so positions repeat), quaternions cycling through q0,
+    -q0 (the same rotation) and one other with the next digit of j, in an order drawn from a fixed seed with three poses of the tie
+    class of query 2 moved into the last partition (three poses).  Queries, all with q0: the zero position, 0.25 on every axis, 0.125
+    on every axis.  Every |dp|^2 and every quaternion product is exact, so the distances are a few dozen values.  side = 16: all but
+    three positions are distinct and the first places hold small ties; side = 3: about a hundred poses share each query's position
+    and rotation — distance 0, ranked by the index alone."""
+    j = np.arange(N_MAX)
+    cell = j % side ** 3
+    p = np.zeros((N_MAX, 8))
+    for a in range(3):
+        p[:, a] = 0.125 * ((cell // side ** a) % side)
+    p[:, 3:7] = np.array([Q0, -Q0, Q_OTHER])[(j // side ** 3) % 3 if side == 3 else j % 3]
+    p = p[np.random.default_rng(0x7135 + side).permutation(N_MAX)]
+    queries = np.zeros((3, 8))
+    queries[:, 3:7] = Q0
+    queries[1, :3], queries[2, :3] = 0.25, 0.125
+    tied = np.flatnonzero((p[:, :3] == 0.125).all(axis=1) & (np.abs(p[:, 3:7] @ Q0) == 1.0))
+    last = np.arange(4 * MIN_PARTITION, N_MAX)
+    swap = tied[tied < 4 * MIN_PARTITION][:len(last)]  # (side = 16: one pose; side = 3: three)
+    last = last[:len(swap)]
+    p[np.concatenate([last, swap])] = p[np.concatenate([swap, last])]
+    return np.ascontiguousarray(p), queries
+
+
+@pytest.fixture(scope="module")
+def pose_lattices():
+    out = {}
+    for side in (16, 3):
+        p, queries = _pose_lattice(side)
+        out[side] = (p, queries, PoseDistanceTable(queries, p))
+    return out
+
+
+@pytest.mark.parametrize("side", [16, 3])
+def test_lattice_ties(world, pose_lattices, side):
+    c = world["c"]
+    p, queries, table = pose_lattices[side]
+    assert side != 3 or len(np.unique(table.D)) <= 96  # a few dozen distinct distances over 3 x 4 099 pairs
+    part = _plan(c, 1, N_MAX)[1]
+    assert _plan(c, 3, N_MAX)[2] == _plan(c, 9, N_MAX)[2] == 5
+    rm = _rm(c, None, p)
+    for k in (1, 4, 8, 16):
+        if side == 3:  # at the k-th place, in every partition, for every query
+            for q in range(3):
+                ties = table.ties_at(k, q)
+                assert len(ties) >= 50 and (q != 2 or set(ties // part) == set(range(5))), (k, q, len(ties))
+                assert set(ties // part) >= set(range(4))
+        for qs in (queries, np.concatenate([queries] * 3)):  # 3 queries: the partitioned form; 9: one query per thread
+            got = _knn(rm, qs, k)
+            _same(got, tuple(np.concatenate([a] * (len(qs) // 3)) for a in table.rank(k)))
+            assert side != 3 or not got[1].any()  # the coarse lattice: k poses at distance 0 for every query
+    print("side %d: ties at the k-th place, k = 1, 4, 8, 16, per query:" % side, [[len(table.ties_at(k, q)) for k in (1, 4, 8, 16)] for q in range(3)])
+
+
+def test_lattice_ties_through_the_wide_merge(world, pose_lattices):
+    """the coarse lattice tiled to 65 537 poses (pose j = lattice pose j mod 4 099), the three queries in the partitioned form: 65
+    lists per query meet in knn_merge_kernel<KC, 256>"""
+    c = world["c"]
+    p, queries, table = pose_lattices[3]
+    consts = plan_constants(_lib.describe(c.ctx.handle, _lib.CALL_ROADMAP_KNN, 3))
+    N = nodes_for_partitions(c.ctx.num_cus, 3, TILE, consts, 65, 65537)
+    t = table.take(np.arange(N) % N_MAX)
+    assert _plan(c, 3, N)[2] == 65 > MERGE_NARROW and _plan(c, 3, N)[0]
+    rm = _rm(c, None, t.nodes)
+    for k in (4, 16):
+        assert all(len(t.ties_at(k, q)) >= 50 * 15 for q in range(3))
+        _same(_knn(rm, queries, k), t.rank(k))
+    rm.close()
+
+
+@pytest.mark.parametrize("term", ["rotation", "translation", "interleaved"])
+def test_one_term_at_a_time(world, term):
+    """every vertex at query 0's position with random rotations (d2 = 0 always passes the pre-filter: the rank is by rot alone); every
+    vertex with query 0's quaternion (rot = 0: by |dp| alone); the two kinds alternating.  1 300 vertices, two partitions."""
+    rng = np.random.default_rng({"rotation": 1, "translation": 2, "interleaved": 3}[term])
+    queries = _random_poses(rng, 9)
+    nodes = _random_poses(rng, 1300)
+    same_place = np.ones(1300, bool) if term == "rotation" else np.zeros(1300, bool) if term == "translation" else np.arange(1300) % 2 == 0
+    nodes[same_place, :3] = queries[0, :3]
+    nodes[~same_place, 3:7] = queries[0, 3:7]
+    table = PoseDistanceTable(queries, nodes)
+    if term != "translation":  # the distances of the vertices at the query's position are their rotations: distinct, and not 0
+        assert len(np.unique(table.D[0, same_place])) > 1000 * same_place.mean() and table.D[0, same_place].min() > 0
+    rm = _rm(world["c"], None, nodes)
+    assert _plan(world["c"], 1, 1300)[2] == 2
+    for Q in (1, 9):
+        for k in (1, 4, 16):
+            _same(_knn(rm, queries[:Q], k), table.rank(k, n_queries=Q))
