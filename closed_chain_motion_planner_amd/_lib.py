@@ -86,6 +86,9 @@ EXPORTS = [
     "ccmp_ik_opts_default", "ccmp_pose_ik_batch", "ccmp_pose_ik_host", "ccmp_pose_ik_ref", "ccmp_roadmap_grow", "ccmp_roadmap_grow_host",
     "ccmp_pose_interpolate", "ccmp_object_create", "ccmp_object_destroy", "ccmp_object_num_triangles",
     "ccmp_object_valid_batch", "ccmp_object_valid_host", "ccmp_object_valid_ref", "ccmp_object_propose_batch", "ccmp_object_propose_host", "ccmp_object_propose_ref",
+    "ccmp_joint_distance", "ccmp_graph_labels_ref", "ccmp_roadmap_commit", "ccmp_roadmap_commit_host", "ccmp_roadmap_commit_ref",
+    "ccmp_roadmap_add_edges", "ccmp_roadmap_add_edges_host", "ccmp_roadmap_num_edges", "ccmp_roadmap_read_edges", "ccmp_roadmap_read_edges_host",
+    "ccmp_roadmap_read_labels", "ccmp_roadmap_read_labels_host", "ccmp_roadmap_closest", "ccmp_roadmap_closest_host", "ccmp_roadmap_closest_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -116,7 +119,7 @@ def lib():
         pass
     L = C.CDLL(LIBPATH)
     dp, u8p, u16p, vp = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_void_p
-    pp = C.POINTER(CcmpProblem)
+    pp, i32p = C.POINTER(CcmpProblem), C.POINTER(C.c_int32)
     sig = {
         "ccmp_problem_from_yaml": ([C.c_char_p, pp], C.c_int),
         "ccmp_problem_init": ([pp, C.c_char_p, C.c_int, C.c_char_p, C.c_int, dp, dp, dp, dp, dp], C.c_int),
@@ -231,6 +234,24 @@ def lib():
                                       dp, C.POINTER(C.c_int32), dp, u8p], C.c_int),
         "ccmp_object_propose_ref": ([dp, C.c_int, C.POINTER(CcmpBox), C.c_int, dp, dp, C.c_int, C.c_size_t, C.c_double, C.c_double, dp, dp, C.c_int, C.c_uint64,
                                      C.c_uint64, C.c_double, dp, C.POINTER(C.c_int32), dp, u8p], C.c_int),
+        "ccmp_joint_distance": ([dp, dp], C.c_double),
+        "ccmp_graph_labels_ref": ([i32p, C.c_size_t, C.c_size_t, i32p], C.c_int),
+        "ccmp_roadmap_commit": ([vp, pp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_size_t, C.c_int, dp, i32p, C.c_int, C.c_uint, vp, vp, vp,
+                                 C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), vp], C.c_int),
+        "ccmp_roadmap_commit_host": ([vp, pp, i32p, u8p, i32p, dp, C.c_int, dp, dp, u8p, C.c_size_t, C.c_int, dp, i32p, C.c_int, C.c_uint, i32p, i32p, i32p,
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_roadmap_commit_ref": ([pp, dp, dp, i32p, C.c_size_t, i32p, u8p, i32p, dp, C.c_int, dp, dp, u8p, C.c_size_t, C.c_int, dp, i32p, C.c_int, C.c_uint,
+                                     i32p, i32p, i32p, dp, dp, i32p, dp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_roadmap_add_edges": ([vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp], C.c_int),
+        "ccmp_roadmap_add_edges_host": ([vp, i32p, C.c_size_t], C.c_int),
+        "ccmp_roadmap_num_edges": ([vp], C.c_size_t),
+        "ccmp_roadmap_read_edges": ([vp, C.c_size_t, C.c_size_t, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_read_edges_host": ([vp, C.c_size_t, C.c_size_t, i32p, dp], C.c_int),
+        "ccmp_roadmap_read_labels": ([vp, C.c_size_t, C.c_size_t, vp, vp], C.c_int),
+        "ccmp_roadmap_read_labels_host": ([vp, C.c_size_t, C.c_size_t, i32p], C.c_int),
+        "ccmp_roadmap_closest": ([vp, vp, C.c_size_t, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_closest_host": ([vp, i32p, C.c_size_t, dp, i32p, dp, dp], C.c_int),
+        "ccmp_roadmap_closest_ref": ([dp, i32p, C.c_size_t, i32p, C.c_size_t, dp, i32p, dp, dp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -268,6 +289,9 @@ IK_MAX_SEEDS, IK_MAX_RESTARTS, IK_MAX_ROUNDS = 16, 31, 256  # ccmp.h: CCMP_IK_MA
 METRIC_JOINT, METRIC_OBJECT = 0, 1  # ccmp.h: CCMP_METRIC_*
 KNN_ALL, KNN_NOT_SELF, KNN_EARLIER = 0, 1, 2  # ccmp.h: CCMP_KNN_*
 KNN_MAX_K = 16
+GROW_TRAPPED, GROW_SREACHED, GROW_GREACHED, GROW_UNSETTLED = range(4)  # ccmp.h: CCMP_GROW_*
+COMMIT_KEEP_ISOLATED = 1  # ccmp.h: CCMP_COMMIT_*
+GRAPH_MAX_ROOTS, CLOSEST_MAX_FROM = 32, 64  # ccmp.h: CCMP_GRAPH_MAX_ROOTS, CCMP_CLOSEST_MAX_FROM
 
 
 def option_table():

@@ -30,6 +30,8 @@ Translation units with deliberately different flags:
   ccmp_ik.cpp            -ffp-contract=off -DCCMP_USE_FMA   ccmp_pose_ik_*: checks, launches, and the same solver text on the host (ccmp_pose_ik_ref, same bits as the kernels)
   ccmp_kernels_object.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the head of growTree: object-pose proposal (interpolate, SE3 Gaussian draw) and the
                          mesh-against-workspace test (ccmp_object.h), one 256-lane block per pose, the triangles strided over the lanes
+  ccmp_kernels_graph.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the roadmap graph (ccmp_graph.h): growTree's tail (commit), explicit edges, the component labels
+                         (hooking rounds in one block, then a compress launch) and closestFromGoal's vertex scan; ccmp_roadmap.cpp compiles the same header for the *_ref forms
   ccmp_object.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_object_*: checks, launches, and the same text on the host (the *_ref forms, same bits as the kernels)
 """
 import os
@@ -92,6 +94,8 @@ _UNITS = [
     ("ccmp_kernels_ik.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-mllvm", "-disable-machine-licm"]),
     # the head of growTree (ccmp_object.h): one block per pose, one triangle per lane and chunk; the k-NN unit's flags; registers only, never scratch
     ("ccmp_kernels_object.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # the roadmap graph (ccmp_graph.h): commit, explicit edges, component labels, closest; the k-NN unit's flags; registers and LDS only
+    ("ccmp_kernels_graph.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     ("ccmp_scene.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
     # the roadmap store and the host side of the object metric (ccmp_pose.h in the rounding model of the kernels)
     ("ccmp_roadmap.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
@@ -100,7 +104,7 @@ _UNITS = [
     # ccmp_object_*: the checks and launches, and ccmp_object.h compiled for the host (the *_ref forms: the kernels' bits without a device)
     ("ccmp_object.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -144,6 +148,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"knn_|connect_(gather|fix)_kernel", 0),  # the connection step: per-thread lists of up to 16 (distance, index) pairs in registers, every instantiation
     (r"ik_", 0),  # pose-targeted IK: the 6x6 system, the kept sines and cosines and the iterate live in registers, both instantiations
     (r"object_", 0),  # the head of growTree: a lane's triangle, the pose's frame and one box at a time live in registers, every kernel of the unit
+    (r"graph_", 0),  # the roadmap graph: a slot's FK and distances, a lane's best candidate and the scan's sums live in registers and LDS, every kernel of the unit
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; }
+namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -157,7 +157,51 @@ struct ObjectCall {
   int n_boxes;
 };
 
+/* one call on the roadmap graph (ccmp_roadmap_commit / _add_edges / _closest; csrc/ccmp_graph.h): the store's arrays and the call's
+ * workspace.  Per slot (S = Q k of a commit): flags, label, weight, mid_pose; per item of the scan (a commit's queries, add_edges'
+ * edges): the decision's masks, the counts and the bases; totals = {vertices added, edges added, new edge floor}. */
+constexpr int kGraphThreads = 256;          // lanes per block of the graph kernels; the hooking rounds and the scan run in ONE such block
+constexpr int kClosestMaxPartitions = 256;  // cuts of the vertex range of a closest call: its merge holds one partition's best per lane
+struct GraphStore {
+  double *joints, *poses; // [cap][14], [cap][8]
+  int32_t *labels;        // [cap]
+  int32_t *uv;            // [cap_e][2]
+  double *w;              // [cap_e]
+  size_t N, E, floor;     // size, edge count and edge floor at call entry
+};
+struct GraphWork {
+  uint32_t *flags;   // [S]
+  int32_t *label;    // [S]
+  double *weight;    // [S]
+  double *mid_pose;  // [S][8]
+  uint32_t *masks;   // [n]: reached | mid << 16
+  int32_t *cnt_v, *cnt_e, *hi, *base_v, *base_e; // [n] each
+  int32_t *totals;   // [4]
+};
+struct GraphCommit {
+  const ccmp_consts *K; // nullable: no mid-stones
+  const int32_t *nbr_idx; const uint8_t *edge_ok; const int32_t *n_states; const double *states; int max_states;
+  const double *new_joints, *new_poses; const uint8_t *vertex_ok;
+  size_t Q; int k;
+  double goal[8]; int has_goal; // the goal pose, by value; has_goal == 0: no mid-stones
+  const ccmp::graph_roots *roots;
+  int keep_isolated;
+  int32_t *new_index, *mid_index, *grow_state;
+};
+
 #pragma GCC visibility push(hidden)
+/* label[first + i] = first + i (an append) */
+hipError_t graph_iota(int32_t *labels, size_t first, size_t n, hipStream_t st);
+/* slots -> decisions -> scan -> scatter (rows, edges, labels, the caller's index arrays); totals are on the device afterwards */
+hipError_t graph_commit(const GraphStore &s, const GraphWork &w, const GraphCommit &c, hipStream_t st);
+/* explicit edges: validity and scan, then the weights and the scatter */
+hipError_t graph_add_edges(const GraphStore &s, const GraphWork &w, const int32_t *uv, size_t E, hipStream_t st);
+/* the call's new edges (uv[E .. E + totals[1])) into the labels: hooking rounds in one block, then label[i] = root(label[i]) over the
+ * s.N + totals[0] labels that exist (at most n_after: the grid) as a launch of its own; max_new bounds every loop */
+hipError_t graph_components(const GraphStore &s, const int32_t *totals, size_t n_after, size_t max_new, hipStream_t st);
+/* blocks over (partition, from), bests of one, then the exact merge (partitions > 1: ws_d [F][P], ws_i [F][P]) */
+hipError_t graph_closest(const GraphStore &s, const int32_t *from_idx, size_t F, const double *target, unsigned int part, unsigned int partitions,
+                         double *ws_d, int32_t *ws_i, int32_t *idx, double *dist, double *from_dist, hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

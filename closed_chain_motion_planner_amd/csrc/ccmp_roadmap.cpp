@@ -4,6 +4,9 @@
 // ccmp_pose.h (metric, pose of a t_wo) and ccmp_kernels_knn.hip (the k-NN kernels of both metrics, pose_from_joints_kernel); the
 // checks and the gather -> traversal -> fix chain behind ccmp_roadmap_connect are ccmp_connect_batch's own (ccmp_api.cpp:
 // ccmp_host::connect_checks / connect_edges), as is the workspace rule (ccmp_host::grow_buffer).
+// The store also keeps the planner's graph: an edge list with weights and one component label per vertex, with the edge count and the
+// edge floor as host state; growTree's tail (ccmp_roadmap_commit), explicit edges and closestFromGoal's scan are launches of
+// ccmp_kernels_graph.hip, and their *_ref forms compile the same rule text here (ccmp_graph.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,6 +16,7 @@
 
 #include "../../include/ccmp.h"
 #include "ccmp_ctx.h"
+#include "ccmp_graph.h"
 #include "ccmp_host.h"
 #include "ccmp_ik.h"
 #include "ccmp_launch.h"
@@ -33,6 +37,15 @@ struct ccmp_roadmap {
   size_t qpose_cap = 0;
   void *grow_ws = nullptr;  // ccmp_roadmap_grow: seeds [E][14] | the traversal's targets [Q][14] | its neighbours [E] (int32)
   size_t grow_ws_cap = 0;   // in edges
+  // the graph (ccmp_graph.h): one label per vertex (allocated and moved with the rows), the edge list, and as host state the edge count
+  // and the edge floor (1 + the largest endpoint of any edge: truncate never goes below it)
+  int32_t *labels = nullptr; // [cap]
+  int32_t *uv = nullptr;     // [cap_e][2]
+  double *w = nullptr;       // [cap_e]
+  size_t n_edges = 0, cap_e = 0, floor = 0;
+  void *graph_ws = nullptr;  // commit / add_edges: ccmp_launch::GraphWork for graph_ws_cap slots
+  size_t graph_ws_cap = 0;
+  void *closest_ws = nullptr; // closest: the partitions' bests, distances [64][256] then indices (allocated with the store)
 };
 
 namespace {
@@ -57,22 +70,144 @@ int regrow(ccmp_roadmap *rm, size_t new_cap, hipStream_t st, bool sync_device)
   ccmp_host::quiesce(rm->ctx);
   if (sync_device) HIP_TRY(hipDeviceSynchronize());
   double *nj = nullptr, *np = nullptr;
+  int32_t *nl = nullptr;
   hipError_t e = hipMalloc((void **)&nj, new_cap * 14 * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void **)&np, new_cap * 8 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void **)&nl, new_cap * sizeof(int32_t));
+  if (e == hipSuccess && rm->size) e = hipMemcpyAsync(nl, rm->labels, rm->size * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && rm->size) e = hipMemcpyAsync(nj, rm->joints, rm->size * 14 * sizeof(double), hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && rm->size) e = hipMemcpyAsync(np, rm->poses, rm->size * 8 * sizeof(double), hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
     if (nj) (void)hipFree(nj);
     if (np) (void)hipFree(np);
+    if (nl) (void)hipFree(nl);
     return e == hipErrorOutOfMemory ? CCMP_ENOMEM : hip_fail(e, "ccmp_roadmap: growth");
   }
   if (rm->joints) (void)hipFree(rm->joints);
   if (rm->poses) (void)hipFree(rm->poses);
+  if (rm->labels) (void)hipFree(rm->labels);
   rm->joints = nj;
   rm->poses = np;
+  rm->labels = nl;
   rm->cap = new_cap;
   return CCMP_OK;
+}
+
+// the same for the edge block
+int regrow_edges(ccmp_roadmap *rm, size_t new_cap, hipStream_t st)
+{
+  if (new_cap > kMaxNodes) return CCMP_EINVAL;
+  ccmp_host::quiesce(rm->ctx);
+  int32_t *nuv = nullptr;
+  double *nw = nullptr;
+  hipError_t e = hipMalloc((void **)&nuv, new_cap * 2 * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void **)&nw, new_cap * sizeof(double));
+  if (e == hipSuccess && rm->n_edges) e = hipMemcpyAsync(nuv, rm->uv, rm->n_edges * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && rm->n_edges) e = hipMemcpyAsync(nw, rm->w, rm->n_edges * sizeof(double), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    if (nuv) (void)hipFree(nuv);
+    if (nw) (void)hipFree(nw);
+    return e == hipErrorOutOfMemory ? CCMP_ENOMEM : hip_fail(e, "ccmp_roadmap: edge growth");
+  }
+  if (rm->uv) (void)hipFree(rm->uv);
+  if (rm->w) (void)hipFree(rm->w);
+  rm->uv = nuv;
+  rm->w = nw;
+  rm->cap_e = new_cap;
+  return CCMP_OK;
+}
+
+// room for `rows` vertices and `edges` edges in all, before a graph call's first launch (at least doubling, as an append grows)
+int graph_reserve(ccmp_roadmap *rm, size_t rows, size_t edges, hipStream_t st)
+{
+  if (rows > kMaxNodes || edges > kMaxNodes) return CCMP_EINVAL;
+  if (rows > rm->cap) {
+    const int rc = regrow(rm, rows > 2 * rm->cap ? rows : 2 * rm->cap > kMaxNodes ? kMaxNodes : 2 * rm->cap, st, false);
+    if (rc != CCMP_OK) return rc;
+  }
+  if (edges > rm->cap_e) {
+    const size_t twice = 2 * rm->cap_e > kMaxNodes ? kMaxNodes : 2 * rm->cap_e;
+    const int rc = regrow_edges(rm, edges > twice ? edges : twice, st);
+    if (rc != CCMP_OK) return rc;
+  }
+  return CCMP_OK;
+}
+
+ccmp_launch::GraphStore graph_store(const ccmp_roadmap *rm) { return ccmp_launch::GraphStore{rm->joints, rm->poses, rm->labels, rm->uv, rm->w, rm->size, rm->n_edges, rm->floor}; }
+
+// the call's workspace for S slots (S >= the scan's items), cut out of rm->graph_ws
+constexpr size_t kGraphSlotBytes = 8 + 64 + 4 + 4 + 6 * 4; // weight, mid_pose, flags, label, and masks .. base_e
+int graph_work(ccmp_roadmap *rm, size_t S, ccmp_launch::GraphWork *w)
+{
+  const int rc = grow_buffer(rm->ctx, &rm->graph_ws, &rm->graph_ws_cap, S, S * kGraphSlotBytes + 64);
+  if (rc != CCMP_OK) return rc;
+  double *d = (double *)rm->graph_ws;
+  w->weight = d;
+  w->mid_pose = d + S;
+  int32_t *i = (int32_t *)(d + 9 * S);
+  w->flags = (uint32_t *)i;
+  w->label = i + S;
+  w->masks = (uint32_t *)(i + 2 * S);
+  w->cnt_v = i + 3 * S;
+  w->cnt_e = i + 4 * S;
+  w->hi = i + 5 * S;
+  w->base_v = i + 6 * S;
+  w->base_e = i + 7 * S;
+  w->totals = i + 8 * S; // 16 bytes of the 64 behind the arrays
+  return CCMP_OK;
+}
+
+// what a commit checks before anything else (the store is there)
+int commit_checks(size_t N, const int32_t *nbr_idx, const uint8_t *edge_ok, const int32_t *n_states, int max_states, const double *new_joints,
+                  const double *new_poses, size_t Q, int k, const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index,
+                  int32_t *grow_state)
+{
+  if (k < 1 || k > CCMP_KNN_MAX_K || n_roots < 0 || n_roots > CCMP_GRAPH_MAX_ROOTS || (flags & ~(unsigned int)CCMP_COMMIT_KEEP_ISOLATED)) return CCMP_EINVAL;
+  if (n_roots > 0 && !roots) return CCMP_EINVAL;
+  for (int i = 0; i < n_roots; i++)
+    if (roots[i] < 0 || (size_t)roots[i] >= N) return CCMP_EINVAL;
+  if (Q == 0) return CCMP_OK;
+  if (max_states < 1 || !nbr_idx || !edge_ok || !n_states || !new_joints || !new_poses || !new_index || !mid_index || !grow_state) return CCMP_EINVAL;
+  if (Q > kMaxNodes / (size_t)(k + 1) || N > kMaxNodes - Q * (size_t)(k + 1)) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+ccmp::graph_roots roots_of(const int32_t *roots, int n_roots)
+{
+  ccmp::graph_roots R{};
+  for (int i = 0; i < n_roots; i++) R.v[i] = roots[i];
+  R.n = n_roots;
+  return R;
+}
+
+// the read-back that ends commit and add_edges: {vertices, edges, floor}
+int graph_finish(ccmp_roadmap *rm, const int32_t *totals, hipStream_t st, size_t *vertices_added, size_t *edges_added)
+{
+  int32_t t[4] = {0, 0, 0, 0};
+  const hipError_t e = hipMemcpyAsync(t, totals, sizeof t, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  rm->size += (size_t)t[0];
+  rm->n_edges += (size_t)t[1];
+  rm->floor = (size_t)t[2];
+  if (vertices_added) *vertices_added = (size_t)t[0];
+  if (edges_added) *edges_added = (size_t)t[1];
+  return CCMP_OK;
+}
+
+// cuts of the vertex range of a closest call: from N alone
+void plan_closest(size_t N, unsigned int *part, unsigned int *partitions)
+{
+  size_t pt = 2048;
+  if ((N + pt - 1) / pt > (size_t)ccmp_launch::kClosestMaxPartitions) {
+    pt = (N + ccmp_launch::kClosestMaxPartitions - 1) / ccmp_launch::kClosestMaxPartitions;
+    pt = (pt + 255) / 256 * 256;
+  }
+  *part = (unsigned int)pt;
+  *partitions = N ? (unsigned int)((N + pt - 1) / pt) : 1;
 }
 
 int knn_checks(const ccmp_roadmap *rm, int metric, const void *queries, size_t Q, int k, int mode, const int32_t *nbr_idx)
@@ -121,6 +256,12 @@ ccmp_roadmap *ccmp_roadmap_create(ccmp_ctx *ctx, size_t capacity_hint)
   rm->ctx = ctx;
   rm->device = ctx->device;
   if (regrow(rm, capacity_hint ? capacity_hint : kDefaultCapacity, ctx->stream, false) != CCMP_OK) { delete rm; return nullptr; }
+  if (regrow_edges(rm, capacity_hint ? capacity_hint : kDefaultCapacity, ctx->stream) != CCMP_OK ||
+      hipMalloc(&rm->closest_ws, (size_t)CCMP_CLOSEST_MAX_FROM * ccmp_launch::kClosestMaxPartitions * (sizeof(double) + sizeof(int32_t))) != hipSuccess) {
+    (void)hipGetLastError();
+    ccmp_roadmap_destroy(rm);
+    return nullptr;
+  }
   return rm;
 }
 
@@ -134,6 +275,11 @@ void ccmp_roadmap_destroy(ccmp_roadmap *rm)
     if (rm->poses) (void)hipFree(rm->poses);
     if (rm->qpose) (void)hipFree(rm->qpose);
     if (rm->grow_ws) (void)hipFree(rm->grow_ws);
+    if (rm->labels) (void)hipFree(rm->labels);
+    if (rm->uv) (void)hipFree(rm->uv);
+    if (rm->w) (void)hipFree(rm->w);
+    if (rm->graph_ws) (void)hipFree(rm->graph_ws);
+    if (rm->closest_ws) (void)hipFree(rm->closest_ws);
   }
   delete rm;
 }
@@ -175,6 +321,7 @@ int ccmp_roadmap_append(ccmp_roadmap *rm, const ccmp_problem *p, const double *j
     ccmp_host::make_consts(*p, K);
     HIP_TRY(ccmp_launch::pose_from_joints(&K, jrow, prow, Q, st));
   }
+  HIP_TRY(ccmp_launch::graph_iota(rm->labels, rm->size, Q, st)); // a new vertex is its own component
   rm->size = need;
   return CCMP_OK;
 }
@@ -192,7 +339,7 @@ int ccmp_roadmap_set_joints(ccmp_roadmap *rm, size_t index, const double *joints
 int ccmp_roadmap_truncate(ccmp_roadmap *rm, size_t n)
 {
   if (!rm) return no_store();
-  if (n > rm->size) return CCMP_EINVAL;
+  if (n > rm->size || n < rm->floor) return CCMP_EINVAL; // a vertex with an edge stays (the reference removes only vertices without one)
   rm->size = n;
   return CCMP_OK;
 }
@@ -482,6 +629,349 @@ int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_s
     down(newton_iters, off_it, E * sizeof(int32_t));
     down(blocked, off_bl, E);
     down(carry_out, off_co, E * 2 * sizeof(double));
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  if (rc != CCMP_OK) return rc;
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+// ---- the graph: edges, components, growTree's tail, closestFromGoal's scan (ccmp_graph.h) ------------------------------------------------
+double ccmp_joint_distance(const double a[14], const double b[14]) { return ccmp::graph_joint_dist(a, b); }
+
+int ccmp_graph_labels_ref(const int32_t *uv, size_t E, size_t N, int32_t *labels)
+{
+  if (N > kMaxNodes || (N > 0 && !labels) || (E > 0 && !uv)) return CCMP_EINVAL;
+  for (size_t e = 0; e < E; e++) // what ccmp_roadmap_add_edges_host refuses: an endpoint that is no vertex, a loop
+    if (uv[2 * e] < 0 || (size_t)uv[2 * e] >= N || uv[2 * e + 1] < 0 || (size_t)uv[2 * e + 1] >= N || uv[2 * e] == uv[2 * e + 1]) return CCMP_EINVAL;
+  for (size_t i = 0; i < N; i++) labels[i] = (int32_t)i;
+  auto find = [&](int32_t x) { while (labels[x] != x) { labels[x] = labels[labels[x]]; x = labels[x]; } return x; };
+  for (size_t e = 0; e < E; e++) {
+    const int32_t a = find(uv[2 * e]), b = find(uv[2 * e + 1]);
+    if (a != b) labels[a > b ? a : b] = a > b ? b : a; // the smaller root stays: a root is the smallest index of its tree
+  }
+  for (size_t i = 0; i < N; i++) labels[i] = find((int32_t)i);
+  return CCMP_OK;
+}
+
+size_t ccmp_roadmap_num_edges(const ccmp_roadmap *rm) { return rm ? rm->n_edges : 0; }
+
+int ccmp_roadmap_commit(ccmp_roadmap *rm, const ccmp_problem *p, const int32_t *nbr_idx, const uint8_t *edge_ok, const int32_t *n_states,
+                        const double *states, int max_states, const double *new_joints, const double *new_poses, const uint8_t *vertex_ok, size_t Q, int k,
+                        const double *goal_pose, const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index,
+                        int32_t *grow_state, size_t *vertices_added, size_t *edges_added, void *hip_stream)
+{
+  if (!rm) return no_store();
+  if (vertices_added) *vertices_added = 0;
+  if (edges_added) *edges_added = 0;
+  { const int rc = commit_checks(rm->size, nbr_idx, edge_ok, n_states, max_states, new_joints, new_poses, Q, k, roots, n_roots, flags, new_index, mid_index, grow_state); if (rc != CCMP_OK) return rc; }
+  const bool mids = states && goal_pose;
+  if (mids) { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
+  if (Q == 0) return CCMP_OK;
+  const size_t S = Q * (size_t)k;
+  if (rm->n_edges > kMaxNodes - S) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  { const int rc = graph_reserve(rm, rm->size + Q + S, rm->n_edges + S, st); if (rc != CCMP_OK) return rc; } // the worst case, before the first launch
+  ccmp_launch::GraphWork w;
+  { const int rc = graph_work(rm, S, &w); if (rc != CCMP_OK) return rc; }
+  ccmp_consts K{};
+  if (mids) ccmp_host::make_consts(*p, K);
+  const ccmp::graph_roots R = roots_of(roots, n_roots);
+  ccmp_launch::GraphCommit c{mids ? &K : nullptr, nbr_idx, edge_ok, n_states, states, max_states, new_joints, new_poses, vertex_ok, Q, k, {0, 0, 0, 0, 0, 0, 0, 0},
+                             mids ? 1 : 0, &R, (flags & CCMP_COMMIT_KEEP_ISOLATED) ? 1 : 0, new_index, mid_index, grow_state};
+  if (mids) memcpy(c.goal, goal_pose, 7 * sizeof(double));
+  const ccmp_launch::GraphStore gs = graph_store(rm);
+  HIP_TRY(ccmp_launch::graph_commit(gs, w, c, st));
+  HIP_TRY(ccmp_launch::graph_components(gs, w.totals, rm->size + Q + S, S, st));
+  return graph_finish(rm, w.totals, st, vertices_added, edges_added);
+}
+
+int ccmp_roadmap_commit_ref(const ccmp_problem *p, const double *store_joints, const double *store_poses, const int32_t *labels, size_t N,
+                            const int32_t *nbr_idx, const uint8_t *edge_ok, const int32_t *n_states, const double *states, int max_states,
+                            const double *new_joints, const double *new_poses, const uint8_t *vertex_ok, size_t Q, int k, const double *goal_pose,
+                            const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index, int32_t *grow_state,
+                            double *rows_joints, double *rows_poses, int32_t *edges_uv, double *edges_w, size_t *vertices_added, size_t *edges_added)
+{
+  if (vertices_added) *vertices_added = 0;
+  if (edges_added) *edges_added = 0;
+  if (N > 0 && (!store_joints || !store_poses || !labels)) return CCMP_EINVAL;
+  { const int rc = commit_checks(N, nbr_idx, edge_ok, n_states, max_states, new_joints, new_poses, Q, k, roots, n_roots, flags, new_index, mid_index, grow_state); if (rc != CCMP_OK) return rc; }
+  const bool mids = states && goal_pose;
+  if (mids) { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
+  if (Q == 0) return CCMP_OK;
+  if (!rows_joints || !rows_poses || !edges_uv || !edges_w) return CCMP_EINVAL;
+  ccmp_consts K{};
+  if (mids) ccmp_host::make_consts(*p, K);
+  const ccmp::graph_roots R = roots_of(roots, n_roots);
+  double goal[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (mids) memcpy(goal, goal_pose, 7 * sizeof(double));
+  size_t nv = 0, ne = 0;
+  for (size_t q = 0; q < Q; q++) {
+    uint32_t f[CCMP_KNN_MAX_K];
+    int32_t lab[CCMP_KNN_MAX_K];
+    double wgt[CCMP_KNN_MAX_K], mid[CCMP_KNN_MAX_K][8];
+    for (int r = 0; r < k; r++) {
+      const size_t e = q * (size_t)k + (size_t)r;
+      lab[r] = 0;
+      wgt[r] = 0.0;
+      f[r] = ccmp::graph_slot_eval(K, mids, store_joints, store_poses, labels, (uint32_t)N, R, nbr_idx[e], edge_ok[e], n_states[e], max_states,
+                                   states ? states + e * (size_t)max_states * 14 : nullptr, new_joints + q * 14, goal, &lab[r], &wgt[r], mid[r]);
+    }
+    const ccmp::graph_decision d = ccmp::graph_decide(f, lab, k, vertex_ok ? vertex_ok[q] != 0 : 1, (flags & CCMP_COMMIT_KEEP_ISOLATED) ? 1 : 0);
+    grow_state[q] = d.state;
+    const size_t t = N + nv;
+    new_index[q] = d.keep ? (int32_t)t : -1;
+    if (d.keep) {
+      memcpy(rows_joints + nv * 14, new_joints + q * 14, 14 * sizeof(double));
+      memcpy(rows_poses + nv * 8, new_poses + q * 8, 7 * sizeof(double));
+      rows_poses[nv * 8 + 7] = 0.0;
+      nv++;
+    }
+    for (int r = 0; r < k; r++)
+      if (d.reached >> r & 1u) {
+        edges_uv[2 * ne] = nbr_idx[q * (size_t)k + r];
+        edges_uv[2 * ne + 1] = (int32_t)t;
+        edges_w[ne++] = wgt[r];
+      }
+    for (int r = 0; r < k; r++) {
+      const size_t e = q * (size_t)k + (size_t)r;
+      mid_index[e] = -1;
+      if (!(d.mid >> r & 1u)) continue;
+      memcpy(rows_joints + nv * 14, states + (e * (size_t)max_states + (size_t)(n_states[e] - 1)) * 14, 14 * sizeof(double));
+      memcpy(rows_poses + nv * 8, mid[r], 8 * sizeof(double));
+      mid_index[e] = (int32_t)(N + nv);
+      edges_uv[2 * ne] = nbr_idx[e];
+      edges_uv[2 * ne + 1] = (int32_t)(N + nv);
+      edges_w[ne++] = wgt[r];
+      nv++;
+    }
+  }
+  if (vertices_added) *vertices_added = nv;
+  if (edges_added) *edges_added = ne;
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_add_edges(ccmp_roadmap *rm, const int32_t *uv, size_t E, size_t *rejected, void *hip_stream)
+{
+  if (!rm) return no_store();
+  if (rejected) *rejected = 0;
+  if (E == 0) return CCMP_OK;
+  if (!uv || E > kMaxNodes || rm->n_edges > kMaxNodes - E) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  { const int rc = graph_reserve(rm, rm->size, rm->n_edges + E, st); if (rc != CCMP_OK) return rc; }
+  ccmp_launch::GraphWork w;
+  { const int rc = graph_work(rm, E, &w); if (rc != CCMP_OK) return rc; }
+  const ccmp_launch::GraphStore gs = graph_store(rm);
+  HIP_TRY(ccmp_launch::graph_add_edges(gs, w, uv, E, st));
+  HIP_TRY(ccmp_launch::graph_components(gs, w.totals, rm->size, E, st));
+  size_t added = 0;
+  { const int rc = graph_finish(rm, w.totals, st, nullptr, &added); if (rc != CCMP_OK) return rc; }
+  if (rejected) *rejected = E - added;
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_read_edges(ccmp_roadmap *rm, size_t first, size_t count, int32_t *uv_out, double *w_out, void *hip_stream)
+{
+  if (!rm) return no_store();
+  if (first > rm->n_edges || count > rm->n_edges - first) return CCMP_EINVAL;
+  if (count == 0) return CCMP_OK;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (uv_out) HIP_TRY(hipMemcpyAsync(uv_out, rm->uv + first * 2, count * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  if (w_out) HIP_TRY(hipMemcpyAsync(w_out, rm->w + first, count * sizeof(double), hipMemcpyDeviceToDevice, st));
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_read_labels(ccmp_roadmap *rm, size_t first, size_t count, int32_t *labels_out, void *hip_stream)
+{
+  if (!rm) return no_store();
+  if (first > rm->size || count > rm->size - first) return CCMP_EINVAL;
+  if (count == 0) return CCMP_OK;
+  if (!labels_out) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  HIP_TRY(hipMemcpyAsync(labels_out, rm->labels + first, count * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_closest(ccmp_roadmap *rm, const int32_t *from_idx, size_t F, const double *target_pose, int32_t *idx, double *dist, double *from_dist,
+                         void *hip_stream)
+{
+  if (!rm) return no_store();
+  if (F == 0) return CCMP_OK;
+  if (F > CCMP_CLOSEST_MAX_FROM || !from_idx || !target_pose || !idx || !dist || !from_dist) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  unsigned int part, partitions;
+  plan_closest(rm->size, &part, &partitions);
+  double *ws_d = (double *)rm->closest_ws;
+  int32_t *ws_i = (int32_t *)(ws_d + (size_t)CCMP_CLOSEST_MAX_FROM * ccmp_launch::kClosestMaxPartitions);
+  HIP_TRY(ccmp_launch::graph_closest(graph_store(rm), from_idx, F, target_pose, part, partitions, ws_d, ws_i, idx, dist, from_dist, (hipStream_t)hip_stream));
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_closest_ref(const double *store_poses, const int32_t *labels, size_t N, const int32_t *from_idx, size_t F, const double *target_pose,
+                             int32_t *idx, double *dist, double *from_dist)
+{
+  if (F == 0) return CCMP_OK;
+  if (F > CCMP_CLOSEST_MAX_FROM || N > kMaxNodes || !store_poses || !labels || !from_idx || !target_pose || !idx || !dist || !from_dist) return CCMP_EINVAL;
+  for (size_t f = 0; f < F; f++)
+    if (from_idx[f] < 0 || (size_t)from_idx[f] >= N) return CCMP_EINVAL;
+  double x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  memcpy(x, target_pose, 7 * sizeof(double));
+  for (size_t f = 0; f < F; f++) {
+    const int32_t lab = labels[from_idx[f]];
+    double bd = __builtin_inf();
+    int32_t bi = 0x7fffffff;
+    for (size_t j = 0; j < N; j++) {
+      if (labels[j] != lab) continue;
+      const double d = ccmp_pose_dist(store_poses + j * 8, x);
+      if (ccmp::graph_closer(d, (int32_t)j, bd, bi)) { bd = d; bi = (int32_t)j; }
+    }
+    idx[f] = bi == 0x7fffffff ? -1 : bi;
+    dist[f] = bd;
+    from_dist[f] = ccmp_pose_dist(store_poses + (size_t)from_idx[f] * 8, x);
+  }
+  return CCMP_OK;
+}
+
+// ---- host forms of the graph's entries: synchronous on the context's stream --------------------------------------------------------------
+int ccmp_roadmap_commit_host(ccmp_roadmap *rm, const ccmp_problem *p, const int32_t *nbr_idx, const uint8_t *edge_ok, const int32_t *n_states,
+                             const double *states, int max_states, const double *new_joints, const double *new_poses, const uint8_t *vertex_ok, size_t Q,
+                             int k, const double *goal_pose, const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index,
+                             int32_t *grow_state, size_t *vertices_added, size_t *edges_added)
+{
+  if (!rm) return no_store();
+  if (vertices_added) *vertices_added = 0;
+  if (edges_added) *edges_added = 0;
+  { const int rc = commit_checks(rm->size, nbr_idx, edge_ok, n_states, max_states, new_joints, new_poses, Q, k, roots, n_roots, flags, new_index, mid_index, grow_state); if (rc != CCMP_OK) return rc; }
+  if (states && goal_pose) { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
+  if (Q == 0) return CCMP_OK;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  ccmp_ctx *ctx = rm->ctx;
+  hipStream_t st = ctx->stream;
+  const size_t S = Q * (size_t)k, sb = states ? S * (size_t)max_states * 14 * sizeof(double) : 0;
+  Stage sg(ctx);
+  const size_t off_i = sg.add(S * sizeof(int32_t)), off_ok = sg.add(S), off_n = sg.add(S * sizeof(int32_t)), off_st = sg.add(sb), off_j = sg.add(Q * 14 * sizeof(double)),
+               off_p = sg.add(Q * 8 * sizeof(double)), off_v = sg.add(vertex_ok ? Q : 0), off_ni = sg.add(Q * sizeof(int32_t)), off_mi = sg.add(S * sizeof(int32_t)),
+               off_gs = sg.add(Q * sizeof(int32_t));
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
+  hipError_t e = hipSuccess;
+  auto up = [&](size_t off, const void *src, size_t n) { if (src && n && e == hipSuccess) e = hipMemcpyAsync(sg.at(off), src, n, hipMemcpyHostToDevice, st); };
+  up(off_i, nbr_idx, S * sizeof(int32_t));
+  up(off_ok, edge_ok, S);
+  up(off_n, n_states, S * sizeof(int32_t));
+  up(off_st, states, sb);
+  up(off_j, new_joints, Q * 14 * sizeof(double));
+  up(off_p, new_poses, Q * 8 * sizeof(double));
+  up(off_v, vertex_ok, Q);
+  int rc = CCMP_OK;
+  if (e == hipSuccess)
+    rc = ccmp_roadmap_commit(rm, p, (const int32_t *)sg.at(off_i), (const uint8_t *)sg.at(off_ok), (const int32_t *)sg.at(off_n),
+                             states ? (const double *)sg.at(off_st) : nullptr, max_states, (const double *)sg.at(off_j), (const double *)sg.at(off_p),
+                             vertex_ok ? (const uint8_t *)sg.at(off_v) : nullptr, Q, k, goal_pose, roots, n_roots, flags, (int32_t *)sg.at(off_ni),
+                             (int32_t *)sg.at(off_mi), (int32_t *)sg.at(off_gs), vertices_added, edges_added, st);
+  if (rc == CCMP_OK && e == hipSuccess) {
+    e = hipMemcpyAsync(new_index, sg.at(off_ni), Q * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(mid_index, sg.at(off_mi), S * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(grow_state, sg.at(off_gs), Q * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  if (rc != CCMP_OK) return rc;
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_add_edges_host(ccmp_roadmap *rm, const int32_t *uv, size_t E)
+{
+  if (!rm) return no_store();
+  if (E == 0) return CCMP_OK;
+  if (!uv || E > kMaxNodes || rm->n_edges > kMaxNodes - E) return CCMP_EINVAL;
+  for (size_t e = 0; e < E; e++)
+    if (uv[2 * e] < 0 || uv[2 * e + 1] < 0 || (size_t)uv[2 * e] >= rm->size || (size_t)uv[2 * e + 1] >= rm->size || uv[2 * e] == uv[2 * e + 1]) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  ccmp_ctx *ctx = rm->ctx;
+  Stage sg(ctx);
+  const size_t off = sg.add(E * 2 * sizeof(int32_t));
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
+  const hipError_t e = hipMemcpyAsync(sg.at(off), uv, E * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+  int rc = CCMP_OK;
+  if (e == hipSuccess) rc = ccmp_roadmap_add_edges(rm, (const int32_t *)sg.at(off), E, nullptr, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (rc != CCMP_OK) return rc;
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_read_edges_host(ccmp_roadmap *rm, size_t first, size_t count, int32_t *uv_out, double *w_out)
+{
+  if (!rm) return no_store();
+  if (first > rm->n_edges || count > rm->n_edges - first) return CCMP_EINVAL;
+  if (count == 0) return CCMP_OK;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = rm->ctx->stream;
+  hipError_t e = hipSuccess;
+  if (uv_out) e = hipMemcpyAsync(uv_out, rm->uv + first * 2, count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && w_out) e = hipMemcpyAsync(w_out, rm->w + first, count * sizeof(double), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_read_labels_host(ccmp_roadmap *rm, size_t first, size_t count, int32_t *labels_out)
+{
+  if (!rm) return no_store();
+  if (first > rm->size || count > rm->size - first) return CCMP_EINVAL;
+  if (count == 0) return CCMP_OK;
+  if (!labels_out) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = rm->ctx->stream;
+  const hipError_t e = hipMemcpyAsync(labels_out, rm->labels + first, count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_closest_host(ccmp_roadmap *rm, const int32_t *from_idx, size_t F, const double *target_pose, int32_t *idx, double *dist,
+                              double *from_dist)
+{
+  if (!rm) return no_store();
+  if (F == 0) return CCMP_OK;
+  if (F > CCMP_CLOSEST_MAX_FROM || !from_idx || !target_pose || !idx || !dist || !from_dist) return CCMP_EINVAL;
+  for (size_t f = 0; f < F; f++)
+    if (from_idx[f] < 0 || (size_t)from_idx[f] >= rm->size) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  ccmp_ctx *ctx = rm->ctx;
+  hipStream_t st = ctx->stream;
+  Stage sg(ctx);
+  const size_t off_f = sg.add(F * sizeof(int32_t)), off_t = sg.add(8 * sizeof(double)), off_i = sg.add(F * sizeof(int32_t)), off_d = sg.add(F * sizeof(double)),
+               off_fd = sg.add(F * sizeof(double));
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
+  hipError_t e = hipMemcpyAsync(sg.at(off_f), from_idx, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(sg.at(off_t), target_pose, 7 * sizeof(double), hipMemcpyHostToDevice, st);
+  int rc = CCMP_OK;
+  if (e == hipSuccess)
+    rc = ccmp_roadmap_closest(rm, (const int32_t *)sg.at(off_f), F, (const double *)sg.at(off_t), (int32_t *)sg.at(off_i), (double *)sg.at(off_d),
+                              (double *)sg.at(off_fd), st);
+  if (rc == CCMP_OK && e == hipSuccess) {
+    e = hipMemcpyAsync(idx, sg.at(off_i), F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dist, sg.at(off_d), F * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(from_dist, sg.at(off_fd), F * sizeof(double), hipMemcpyDeviceToHost, st);
   }
   const hipError_t es = hipStreamSynchronize(st);
   if (rc != CCMP_OK) return rc;

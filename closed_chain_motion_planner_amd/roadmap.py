@@ -13,12 +13,24 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import METRIC_JOINT, METRIC_OBJECT, check
+from ._lib import COMMIT_KEEP_ISOLATED, GROW_GREACHED, GROW_SREACHED, GROW_TRAPPED, GROW_UNSETTLED, METRIC_JOINT, METRIC_OBJECT, check
 from .constraint import _stream_handle, _torch
 
-__all__ = ["Roadmap", "pose_distance", "pose_from_t_wo", "METRIC_JOINT", "METRIC_OBJECT"]
+__all__ = ["Roadmap", "pose_distance", "pose_from_t_wo", "joint_distance", "graph_labels_ref", "commit_ref", "closest_ref", "METRIC_JOINT", "METRIC_OBJECT",
+           "GROW_TRAPPED", "GROW_SREACHED", "GROW_GREACHED", "GROW_UNSETTLED", "COMMIT_KEEP_ISOLATED"]
 
 _dp = C.POINTER(C.c_double)
+_i32p = C.POINTER(C.c_int32)
+_u8p = C.POINTER(C.c_uint8)
+
+
+def _np(a, dtype, shape=None):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a if shape is None else a.reshape(shape)
+
+
+def _ptr(a, typ):
+    return a.ctypes.data_as(typ) if a is not None else None
 
 
 def _host(a, cols):
@@ -51,6 +63,73 @@ def pose_from_t_wo(t_wo):
     for i in range(flat.shape[0]):
         fn(flat[i].ctypes.data_as(_dp), out[i].ctypes.data_as(_dp))
     return out.reshape(t.shape[:-1] + (8,))
+
+
+def joint_distance(a, b):
+    """ccmp_joint_distance: the weight of an edge between two joint states (RealVectorStateSpace::distance over the 14 joints in the
+    k-NN's rounding); host only"""
+    a, b = _np(a, np.float64, 14), _np(b, np.float64, 14)
+    return float(_lib.lib().ccmp_joint_distance(_ptr(a, _dp), _ptr(b, _dp)))
+
+
+def graph_labels_ref(uv, n):
+    """ccmp_graph_labels_ref: labels (n,) int32, label[v] = the smallest index of v's component under the edges uv (E,2); host only"""
+    uv = _np(uv, np.int32).reshape(-1, 2)
+    labels = np.empty(int(n), dtype=np.int32)
+    check(_lib.lib().ccmp_graph_labels_ref(_ptr(uv, _i32p), len(uv), int(n), _ptr(labels, _i32p)), "ccmp_graph_labels_ref")
+    return labels
+
+
+_NO_LIMIT = 2**31 - 1  # max_states of a commit without state lists and without a stated limit: no slot is unsettled by its length
+
+
+def _commit_inputs(nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots):
+    nbr = _np(nbr_idx, np.int32)
+    if nbr.ndim != 2:
+        raise ValueError("nbr_idx is (Q, k)")
+    Q, k = nbr.shape
+    S = Q * k
+    st = None if states is None or S == 0 else _np(states, np.float64).reshape(S, -1, 14)
+    goal = None
+    if goal_pose is not None:
+        goal = np.zeros(8)
+        goal[:7] = np.asarray(goal_pose, dtype=np.float64).reshape(-1)[:7]
+    return (nbr, _np(edge_ok, np.uint8, S), _np(n_states, np.int32, S), st, _np(new_joints, np.float64, (Q, 14)), _np(new_poses, np.float64, (Q, 8)),
+            None if vertex_ok is None else _np(vertex_ok, np.uint8, Q), goal, _np(list(roots), np.int32, -1), Q, k)
+
+
+def commit_ref(problem, store_joints, store_poses, labels, nbr_idx, edge_ok, n_states, new_joints, new_poses, states=None, vertex_ok=None, goal_pose=None,
+               roots=(), flags=0, max_states=None):
+    """ccmp_roadmap_commit_ref: `Roadmap.commit`'s rule (csrc/ccmp_graph.h compiled for the host: the kernels' bits) on the store's raw
+    arrays — joints (N,14), poses (N,8), labels (N,) — without a device.  Returns new_index (Q,), mid_index (Q,k), grow_state (Q,) and
+    the appended rows and edges in index order: rows_joints (V,14), rows_poses (V,8), edges_uv (E,2), edges_w (E,).  `problem`: a
+    `CcmpProblem` (needed for mid-stones only).  max_states: the traversal's list length (n_states beyond it = unsettled); taken from
+    `states` when those are given."""
+    sj, sp, lab = _np(store_joints, np.float64).reshape(-1, 14), _np(store_poses, np.float64).reshape(-1, 8), _np(labels, np.int32, -1)
+    nbr, ok, ns, st, nj, npo, vok, goal, rt, Q, k = _commit_inputs(nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots)
+    S = Q * k
+    out = {"new_index": np.empty(Q, dtype=np.int32), "mid_index": np.empty((Q, k), dtype=np.int32), "grow_state": np.empty(Q, dtype=np.int32)}
+    rj, rp, euv, ew = np.empty((Q + S, 14)), np.empty((Q + S, 8)), np.empty((S, 2), dtype=np.int32), np.empty(S)
+    nv, ne = C.c_size_t(), C.c_size_t()
+    check(_lib.lib().ccmp_roadmap_commit_ref(C.byref(problem) if problem is not None else None, _ptr(sj, _dp), _ptr(sp, _dp), _ptr(lab, _i32p), len(sj),
+                                             _ptr(nbr, _i32p), _ptr(ok, _u8p), _ptr(ns, _i32p), _ptr(st, _dp),
+                                             st.shape[1] if st is not None else _NO_LIMIT if max_states is None else int(max_states),
+                                             _ptr(nj, _dp), _ptr(npo, _dp), _ptr(vok, _u8p), Q, k, _ptr(goal, _dp), _ptr(rt, _i32p), len(rt), int(flags),
+                                             _ptr(out["new_index"], _i32p), _ptr(out["mid_index"], _i32p), _ptr(out["grow_state"], _i32p), _ptr(rj, _dp),
+                                             _ptr(rp, _dp), _ptr(euv, _i32p), _ptr(ew, _dp), C.byref(nv), C.byref(ne)), "ccmp_roadmap_commit_ref")
+    out.update(rows_joints=rj[:nv.value].copy(), rows_poses=rp[:nv.value].copy(), edges_uv=euv[:ne.value].copy(), edges_w=ew[:ne.value].copy())
+    return out
+
+
+def closest_ref(store_poses, labels, froms, target_pose):
+    """ccmp_roadmap_closest_ref: `Roadmap.closest` on host arrays, no device: (idx (F,), dist (F,), from_dist (F,))"""
+    sp, lab, fr = _np(store_poses, np.float64).reshape(-1, 8), _np(labels, np.int32, -1), _np(froms, np.int32, -1)
+    tgt = np.zeros(8)
+    tgt[:7] = np.asarray(target_pose, dtype=np.float64).reshape(-1)[:7]
+    idx, dist, fd = np.empty(len(fr), dtype=np.int32), np.empty(len(fr)), np.empty(len(fr))
+    check(_lib.lib().ccmp_roadmap_closest_ref(_ptr(sp, _dp), _ptr(lab, _i32p), len(sp), _ptr(fr, _i32p), len(fr), _ptr(tgt, _dp), _ptr(idx, _i32p),
+                                              _ptr(dist, _dp), _ptr(fd, _dp)), "ccmp_roadmap_closest_ref")
+    return idx, dist, fd
 
 
 class Roadmap:
@@ -221,6 +300,155 @@ class Roadmap:
         out = self.grow(kept, k, rng_seed=rng_seed, first_index=first_index, **grow_args)
         out.update(which=which, rows=rows, poses=kept)
         return out
+
+    # ---- the graph: edges, component labels, growTree's tail, closestFromGoal (include/ccmp.h; csrc/ccmp_graph.h) ---------------------
+    def commit(self, nbr_idx, edge_ok, n_states, new_joints, new_poses, states=None, vertex_ok=None, goal_pose=None, roots=(), flags=0, max_states=None,
+               stream=None):
+        """What follows the traversals in growTree (stefanBiPRM.cpp:303-372, milestonesToAdd), addMilestone and, with
+        COMMIT_KEEP_ISOLATED, startgoalMilestone, on the device (ccmp_roadmap_commit): `grow`'s / `connect`'s nbr_idx (Q,k), ok, n_states
+        and states go in unchanged with the new states' joints (Q,14) and poses (Q,8).  Per query: the new vertex stays if an edge
+        reached it (or with COMMIT_KEEP_ISOLATED), every reached slot gives an edge weighted by the joint distance, and — with
+        `goal_pose` and `states` — a failed slot whose neighbour is in a root's component (`roots`: the planner's start vertices) and
+        whose last state is strictly closer to the goal than the neighbour gives a mid-stone vertex and its edge.  The labels are
+        updated.  Returns new_index (Q,) (-1: not kept), mid_index (Q,k) (-1: none), grow_state (Q,) (GROW_*), and the counts
+        vertices_added / edges_added (ints).  The queries of one call do not see each other.  Synchronous at its end (one small
+        read-back), not capturable.  max_states: the traversal's list length (n_states beyond it = unsettled); taken from `states` when
+        those are given."""
+        nv, ne = C.c_size_t(), C.c_size_t()
+        no_states = _NO_LIMIT if max_states is None else int(max_states)
+        goal = None
+        if goal_pose is not None:
+            goal = np.zeros(8)
+            goal[:7] = np.asarray(goal_pose.cpu() if hasattr(goal_pose, "cpu") else goal_pose, dtype=np.float64).reshape(-1)[:7]
+        rt = _np(list(roots), np.int32, -1)
+        if isinstance(nbr_idx, np.ndarray):
+            nbr, ok, ns, st, nj, npo, vok, goal, rt, Q, k = _commit_inputs(nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots)
+            out = {"new_index": np.empty(Q, dtype=np.int32), "mid_index": np.empty((Q, k), dtype=np.int32), "grow_state": np.empty(Q, dtype=np.int32)}
+            check(_lib.lib().ccmp_roadmap_commit_host(self._h, self._problem() if (st is not None and goal is not None) else None, _ptr(nbr, _i32p), _ptr(ok, _u8p),
+                                                      _ptr(ns, _i32p), _ptr(st, _dp), st.shape[1] if st is not None else no_states, _ptr(nj, _dp), _ptr(npo, _dp),
+                                                      _ptr(vok, _u8p), Q, k, _ptr(goal, _dp), _ptr(rt, _i32p), len(rt), int(flags), _ptr(out["new_index"], _i32p),
+                                                      _ptr(out["mid_index"], _i32p), _ptr(out["grow_state"], _i32p), C.byref(nv), C.byref(ne)),
+                  "ccmp_roadmap_commit_host")
+        else:
+            torch = _torch()
+            if nbr_idx.dim() != 2 or nbr_idx.dtype != torch.int32 or not nbr_idx.is_contiguous():
+                raise ValueError("nbr_idx: a contiguous (Q, k) int32 tensor")
+            Q, k = nbr_idx.shape
+            S = Q * k
+
+            def dev(t, dtype, numel):
+                if t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or t.numel() != numel:
+                    raise ValueError("expected a contiguous %s tensor of %d elements on the device" % (dtype, numel))
+                return t
+
+            ok, ns = dev(edge_ok, torch.uint8, S), dev(n_states, torch.int32, S)
+            ms = no_states
+            if states is not None:
+                ms = states.numel() // (S * 14) if S else 1
+                dev(states, torch.float64, S * ms * 14)
+            nj, npo = _dev(new_joints, 14), _dev(new_poses, 8)
+            if vertex_ok is not None:
+                dev(vertex_ok, torch.uint8, Q)
+            out = {"new_index": torch.empty(Q, dtype=torch.int32, device=nbr_idx.device), "mid_index": torch.empty((Q, k), dtype=torch.int32, device=nbr_idx.device),
+                   "grow_state": torch.empty(Q, dtype=torch.int32, device=nbr_idx.device)}
+            check(_lib.lib().ccmp_roadmap_commit(self._h, self._problem() if (states is not None and goal is not None) else None, nbr_idx.data_ptr(), ok.data_ptr(),
+                                                 ns.data_ptr(), states.data_ptr() if states is not None else None, ms, nj.data_ptr(), npo.data_ptr(),
+                                                 vertex_ok.data_ptr() if vertex_ok is not None else None, Q, k, _ptr(goal, _dp), _ptr(rt, _i32p), len(rt), int(flags),
+                                                 out["new_index"].data_ptr(), out["mid_index"].data_ptr(), out["grow_state"].data_ptr(), C.byref(nv), C.byref(ne),
+                                                 _stream_handle(stream)), "ccmp_roadmap_commit")
+        out.update(vertices_added=int(nv.value), edges_added=int(ne.value))
+        return out
+
+    def add_edges(self, uv, stream=None):
+        """Explicit edges uv (E,2) int32 between existing vertices; the weights (joint distance) are computed on the device and the labels
+        updated.  numpy: an endpoint out of range or u == v raises (CCMP_EINVAL), returns 0; a device tensor: such edges are skipped and
+        their number is returned."""
+        if isinstance(uv, np.ndarray):
+            a = _np(uv, np.int32).reshape(-1, 2)
+            check(_lib.lib().ccmp_roadmap_add_edges_host(self._h, _ptr(a, _i32p), len(a)), "ccmp_roadmap_add_edges_host")
+            return 0
+        torch = _torch()
+        if uv.dtype != torch.int32 or uv.dim() != 2 or uv.shape[1] != 2 or not uv.is_contiguous() or not uv.is_cuda:
+            raise ValueError("expected a contiguous (E, 2) int32 tensor on the device")
+        rej = C.c_size_t()
+        check(_lib.lib().ccmp_roadmap_add_edges(self._h, uv.data_ptr(), uv.shape[0], C.byref(rej), _stream_handle(stream)), "ccmp_roadmap_add_edges")
+        return int(rej.value)
+
+    @property
+    def num_edges(self):
+        return int(_lib.lib().ccmp_roadmap_num_edges(self._h))
+
+    def edges(self, first=0, count=None, host=False, stream=None):
+        """(uv (count,2) int32, w (count,) float64) of the edges first ... in insertion order — what a graph library needs for the path
+        search; device tensors, or numpy arrays with host=True"""
+        count = self.num_edges - int(first) if count is None else int(count)
+        if host:
+            uv, w = np.empty((count, 2), dtype=np.int32), np.empty(count)
+            check(_lib.lib().ccmp_roadmap_read_edges_host(self._h, int(first), count, _ptr(uv, _i32p), _ptr(w, _dp)), "ccmp_roadmap_read_edges_host")
+            return uv, w
+        torch = _torch()
+        dev = torch.device("cuda", self.ctx.device)
+        uv, w = torch.empty((count, 2), dtype=torch.int32, device=dev), torch.empty(count, dtype=torch.float64, device=dev)
+        check(_lib.lib().ccmp_roadmap_read_edges(self._h, int(first), count, uv.data_ptr(), w.data_ptr(), _stream_handle(stream)), "ccmp_roadmap_read_edges")
+        return uv, w
+
+    def labels(self, first=0, count=None, host=False, stream=None):
+        """labels (count,) int32: label[v] = the smallest vertex index of v's connected component"""
+        count = len(self) - int(first) if count is None else int(count)
+        if host:
+            lab = np.empty(count, dtype=np.int32)
+            check(_lib.lib().ccmp_roadmap_read_labels_host(self._h, int(first), count, _ptr(lab, _i32p)), "ccmp_roadmap_read_labels_host")
+            return lab
+        torch = _torch()
+        lab = torch.empty(count, dtype=torch.int32, device=torch.device("cuda", self.ctx.device))
+        check(_lib.lib().ccmp_roadmap_read_labels(self._h, int(first), count, lab.data_ptr(), _stream_handle(stream)), "ccmp_roadmap_read_labels")
+        return lab
+
+    def closest(self, froms, target_pose, stream=None):
+        """closestFromGoal's vertex scan (ccmp_roadmap_closest): for each of froms (F,) int32, F <= 64, the vertex of from's component
+        with the smallest (pose distance to target_pose, index): (idx (F,), dist (F,), from_dist (F,)), from_dist = the distance of
+        `from` itself.  A NaN distance is never a candidate.  numpy in, numpy out (synchronous); device tensors in (target_pose (8,)),
+        device tensors out, asynchronous and capturable."""
+        if isinstance(froms, np.ndarray):
+            fr = _np(froms, np.int32, -1)
+            tgt = np.zeros(8)
+            tgt[:7] = np.asarray(target_pose, dtype=np.float64).reshape(-1)[:7]
+            idx, dist, fd = np.empty(len(fr), dtype=np.int32), np.empty(len(fr)), np.empty(len(fr))
+            check(_lib.lib().ccmp_roadmap_closest_host(self._h, _ptr(fr, _i32p), len(fr), _ptr(tgt, _dp), _ptr(idx, _i32p), _ptr(dist, _dp), _ptr(fd, _dp)),
+                  "ccmp_roadmap_closest_host")
+            return idx, dist, fd
+        torch = _torch()
+        if froms.dtype != torch.int32 or froms.dim() != 1 or not froms.is_contiguous() or not froms.is_cuda:
+            raise ValueError("expected a contiguous (F,) int32 tensor on the device")
+        if target_pose.dtype != torch.float64 or target_pose.numel() < 7 or not target_pose.is_contiguous() or not target_pose.is_cuda:
+            raise ValueError("expected a contiguous float64 pose on the device")
+        F = froms.shape[0]
+        idx = torch.empty(F, dtype=torch.int32, device=froms.device)
+        dist, fd = torch.empty(F, dtype=torch.float64, device=froms.device), torch.empty(F, dtype=torch.float64, device=froms.device)
+        check(_lib.lib().ccmp_roadmap_closest(self._h, froms.data_ptr(), F, target_pose.data_ptr(), idx.data_ptr(), dist.data_ptr(), fd.data_ptr(),
+                                              _stream_handle(stream)), "ccmp_roadmap_closest")
+        return idx, dist, fd
+
+    def closest_from_goal(self, froms, to):
+        """The reference's closestFromGoal(froms, {to}, closest) (stefanBiPRM.cpp:641-690) from `closest`'s per-from answers: closestVal
+        is carried across `froms`, each from first offers its own distance, `closest` = the best vertex of the LAST from's component if
+        it is strictly better than closestVal, else that from; only tos[0] is used.  Returns (closest, closestVal); (None, inf) for no
+        froms.  The one difference: the reference scans the vertices its A* sweep has ranked, and the sweep stops when it reaches `to` —
+        so this equals closestFromGoal whenever `to` is not in the component; when it is, both answer distance 0 (the vertex `to`, or a
+        lower-indexed vertex with the same pose)."""
+        froms = [int(f) for f in froms]
+        if not froms:
+            return None, float("inf")
+        _, pose = self.read(int(to), 1, host=True)
+        idx, dist, fd = self.closest(np.array(froms, dtype=np.int32), pose[0])
+        closest, val = None, float("inf")
+        for f, i, d, h in zip(froms, idx, dist, fd):
+            if h < val:
+                val = float(h)
+            closest = f
+            if i >= 0 and d < val:
+                closest, val = int(i), float(d)
+        return closest, val
 
     def close(self):
         if self._h:

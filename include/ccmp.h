@@ -591,7 +591,7 @@ void ccmp_pose_from_t_wo(const double t_wo[12], double pose[8]);
  *             (never under capture: reserve first).
  *   set_joints  joints[14] (device pointer) into row `index` < size, asynchronous on hip_stream; the pose row is not touched.
  *             ccmp_roadmap_set_joints_host takes a host pointer (growTree hands over the result of its IK: ccmp_pose_ik_* / ccmp_roadmap_grow below) and is synchronous.
- *   truncate  size = n <= size; keeps the capacity.
+ *   truncate  size = n <= size; keeps the capacity.  CCMP_EINVAL for n below the edge floor of a store with edges (see the graph section below).
  *   read      rows first .. first + count - 1 into joints_out [count][14] / poses_out [count][8] (device pointers, either may be NULL).
  *   knn       the k nearest vertices of each query.  CCMP_METRIC_JOINT: queries [Q][14], the kernels of ccmp_knn_batch over the store's
  *             joint rows — bit-identical to ccmp_knn_batch on the same rows.  CCMP_METRIC_OBJECT: queries [Q][8] poses, the distance
@@ -764,6 +764,95 @@ int ccmp_object_propose_host(ccmp_ctx *ctx, const ccmp_object *obj, const double
 int ccmp_object_propose_ref(const double *tri, int M, const ccmp_box *boxes, int n_boxes, const double *from_poses, const double *to_poses, int to_stride,
                             size_t G, double t, double sigma, const double lo[3], const double hi[3], int attempts, uint64_t rng_seed, uint64_t first_index,
                             double inflate, double *pose_out, int32_t *which, double *cand_pose, uint8_t *cand_valid);
+
+/* ---- the roadmap graph on the device: edges, components and growTree's tail ------------------------------------------------------------ */
+/* The store also keeps the graph: a device edge list uv [E][2] (int32) with weights w [E] (double), and one int32 LABEL per vertex,
+ *     label[v] = the smallest vertex index in v's connected component
+ * — a function of the edge set alone, fully compressed between calls; an append writes label[i] = i.  The handle keeps the edge count
+ * and an EDGE FLOOR (1 + the largest endpoint of any edge) as host state: ccmp_roadmap_truncate(n) with n below the floor answers
+ * CCMP_EINVAL (the reference only ever removes a vertex without an edge, stefanBiPRM.cpp:353-359, :375-378).
+ *
+ * ccmp_roadmap_commit is what follows the traversals in growTree (stefanBiPRM.cpp:303-372, milestonesToAdd :420-445), addMilestone and,
+ * with CCMP_COMMIT_KEEP_ISOLATED, startgoalMilestone; the outputs of ccmp_roadmap_grow / ccmp_roadmap_connect go in unchanged.  For query
+ * q and slot r < k (N = the store's size at entry) the slot is
+ *     empty      nbr_idx < 0 (or >= N)
+ *     unsettled  edge_ok == 2 or n_states > max_states: a continuation is still due
+ *     reached    edge_ok == 1
+ *     failed     otherwise
+ * and, with L = the labels at call entry and root(l) = l is the label of one of roots[0 .. n_roots) (the planner's startM_):
+ *     vertex_ok[q] == 0            -> TRAPPED, nothing committed
+ *     any slot unsettled           -> UNSETTLED, nothing committed for q
+ *     joined = {}, joined_start = false
+ *     for r = 0 .. k-1:
+ *       reached: edge (nbr, t), weight = joint distance; joined += L[nbr]; joined_start |= root(L[nbr])
+ *       failed, a goal pose given, n_states > 1, and (root(L[nbr]) or (L[nbr] in joined and joined_start)):
+ *           m = pose of states[q][r][n_states-1]
+ *           if dist(m, goal) < dist(pose[nbr], goal)  (strict; a NaN never passes):
+ *               mid-stone r = vertex (that state, m) + edge (nbr, mid)
+ *     added = any slot reached;  t is kept iff added or KEEP_ISOLATED
+ *     state = !added ? TRAPPED : joined_start ? SREACHED : GREACHED
+ * (the second arm of the component test is the reference's: sameComponent_start(n) is asked inside the neighbour loop, after the earlier
+ * successful edges of the same vertex have been united).  New indices are taken in a total order: for ascending q, t if kept, then its
+ * mid-stones in r order; edges likewise: the reached edges of q in r order, then its mid-stone edges, each as (neighbour, new vertex).
+ * The queries of one call do not see each other; with Q == 1 the rule is the reference's.  Weights are the joint distance of the k-NN
+ * (FMA chain over the 14 differences, correctly rounded root); the pose of a state is what an append derives; distances are
+ * ccmp_pose_distance.  csrc/ccmp_graph.h states all of it once, for the kernels and for the *_ref forms.
+ *   commit      inputs (device pointers): nbr_idx [Q][k], edge_ok [Q k], n_states [Q k], states [Q k][max_states][14] (NULL: no
+ *               mid-stones), new_joints [Q][14], new_poses [Q][8], vertex_ok [Q] (NULL: all 1).  Host arguments: p (may be NULL when states
+ *               or goal_pose is), goal_pose[8] (NULL: no mid-stones), roots[n_roots] (0 <= n_roots <= CCMP_GRAPH_MAX_ROOTS, each < size),
+ *               flags.  Outputs (device pointers): new_index [Q] (-1: not kept), mid_index [Q][k] (-1: none), grow_state [Q]; host:
+ *               *vertices_added, *edges_added (nullable).  The worst case (Q (1 + k) rows, Q k edges) is reserved before the first launch;
+ *               the call ends with one small read-back (the counts and the new edge floor): IT IS SYNCHRONOUS AT ITS END AND NOT CAPTURABLE.
+ *   add_edges   explicit uv [E][2]; the weights (joint distance) are computed on the device.  An endpoint outside [0, size) or u == v:
+ *               CCMP_EINVAL from the _host form (checked on the host); the device form skips such an edge and counts it in *rejected
+ *               (nullable).  Synchronous at its end like commit.
+ *   num_edges / read_edges (uv_out [count][2], w_out [count], either may be NULL) / read_labels (labels_out [count])   as read.
+ *   closest     closestFromGoal's vertex scan (stefanBiPRM.cpp:675-684): for each of from_idx [F], 1 <= F <= CCMP_CLOSEST_MAX_FROM, the
+ *               vertex with the smallest (ccmp_pose_distance(pose[i], target_pose), i) among those with label[i] == label[from]: idx [F],
+ *               dist [F]; from_dist [F] = the distance of `from` itself.  A NaN distance is never a candidate (none at all: idx -1, dist
+ *               +inf).  target_pose[8] is a device pointer in the device form.  Asynchronous and capturable.  A `from` outside [0, size):
+ *               CCMP_EINVAL from the _host and _ref forms; the device form answers idx -1, dist +inf, from_dist NaN.
+ *   *_ref       the same text on host arrays, one thread, no device, never CCMP_ENODEV.  commit_ref takes the store's raw arrays (joints
+ *               [N][14], poses [N][8], labels [N]) and returns the appended rows (rows_joints [Q (1 + k)][14], rows_poses [..][8]) and edges
+ *               (edges_uv [Q k][2], edges_w [Q k]), of which the first *vertices_added / *edges_added are written.
+ *   ccmp_graph_labels_ref   plain host union-find: uv [E][2] over N vertices -> labels [N]; CCMP_EINVAL for an endpoint outside [0, N) or
+ *               u == v, as add_edges_host.
+ *   ccmp_joint_distance     the edge weight of two joint states; pure host code beside ccmp_pose_distance.
+ * Conventions as the store's other entries: every check runs before the first launch; a NULL store answers CCMP_ENODEV without a device
+ * and CCMP_EINVAL with one; zero counts return CCMP_OK and touch nothing.  The path search itself (A*) stays with the caller's graph
+ * library: read_edges hands it the graph. */
+#define CCMP_GRAPH_MAX_ROOTS 32
+#define CCMP_CLOSEST_MAX_FROM 64
+enum { CCMP_GROW_TRAPPED = 0, CCMP_GROW_SREACHED = 1, CCMP_GROW_GREACHED = 2, CCMP_GROW_UNSETTLED = 3 };
+enum { CCMP_COMMIT_KEEP_ISOLATED = 1 };
+double ccmp_joint_distance(const double a[14], const double b[14]);
+int ccmp_graph_labels_ref(const int32_t *uv, size_t E, size_t N, int32_t *labels);
+int ccmp_roadmap_commit(ccmp_roadmap *rm, const ccmp_problem *p, const int32_t *nbr_idx, const uint8_t *edge_ok, const int32_t *n_states,
+                        const double *states, int max_states, const double *new_joints, const double *new_poses, const uint8_t *vertex_ok, size_t Q, int k,
+                        const double *goal_pose, const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index,
+                        int32_t *grow_state, size_t *vertices_added, size_t *edges_added, void *hip_stream);
+int ccmp_roadmap_commit_host(ccmp_roadmap *rm, const ccmp_problem *p, const int32_t *nbr_idx, const uint8_t *edge_ok, const int32_t *n_states,
+                             const double *states, int max_states, const double *new_joints, const double *new_poses, const uint8_t *vertex_ok, size_t Q,
+                             int k, const double *goal_pose, const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index,
+                             int32_t *grow_state, size_t *vertices_added, size_t *edges_added);
+int ccmp_roadmap_commit_ref(const ccmp_problem *p, const double *store_joints, const double *store_poses, const int32_t *labels, size_t N,
+                            const int32_t *nbr_idx, const uint8_t *edge_ok, const int32_t *n_states, const double *states, int max_states,
+                            const double *new_joints, const double *new_poses, const uint8_t *vertex_ok, size_t Q, int k, const double *goal_pose,
+                            const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index, int32_t *grow_state,
+                            double *rows_joints, double *rows_poses, int32_t *edges_uv, double *edges_w, size_t *vertices_added, size_t *edges_added);
+int ccmp_roadmap_add_edges(ccmp_roadmap *rm, const int32_t *uv, size_t E, size_t *rejected, void *hip_stream);
+int ccmp_roadmap_add_edges_host(ccmp_roadmap *rm, const int32_t *uv, size_t E);
+size_t ccmp_roadmap_num_edges(const ccmp_roadmap *rm);
+int ccmp_roadmap_read_edges(ccmp_roadmap *rm, size_t first, size_t count, int32_t *uv_out, double *w_out, void *hip_stream);
+int ccmp_roadmap_read_edges_host(ccmp_roadmap *rm, size_t first, size_t count, int32_t *uv_out, double *w_out);
+int ccmp_roadmap_read_labels(ccmp_roadmap *rm, size_t first, size_t count, int32_t *labels_out, void *hip_stream);
+int ccmp_roadmap_read_labels_host(ccmp_roadmap *rm, size_t first, size_t count, int32_t *labels_out);
+int ccmp_roadmap_closest(ccmp_roadmap *rm, const int32_t *from_idx, size_t F, const double *target_pose, int32_t *idx, double *dist, double *from_dist,
+                         void *hip_stream);
+int ccmp_roadmap_closest_host(ccmp_roadmap *rm, const int32_t *from_idx, size_t F, const double *target_pose, int32_t *idx, double *dist,
+                              double *from_dist);
+int ccmp_roadmap_closest_ref(const double *store_poses, const int32_t *labels, size_t N, const int32_t *from_idx, size_t F, const double *target_pose,
+                             int32_t *idx, double *dist, double *from_dist);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

@@ -595,6 +595,74 @@ public:
     return ik_ok != 0;
   }
 
+  // ---- the graph (include/ccmp.h: ccmp_roadmap_commit / _add_edges / _closest) --------------------------------------------------------
+  // What growTree does with grow()'s outputs (stefanBiPRM.cpp:303-372 and milestonesToAdd), for ONE pose: idx / ok / n_states / states
+  // as grow() or connect() left them, the new state's joints and pose, the planner's goal pose (nullptr: no mid-stones) and startM_
+  // (roots).  Returns the GrowState (CCMP_GROW_*); CCMP_GROW_TRAPPED when the call failed (the error in lastError()).  *new_index
+  // (nullable): the new vertex or -1; *mid_index (nullable): k entries, the mid-stone of every slot or -1.  keep_isolated:
+  // startgoalMilestone's vertex, which stays without an edge.  have_state = false: the IK found no state (vertex_ok = 0).
+  int commit(const std::vector<int32_t> &idx, const std::vector<uint8_t> &ok, const std::vector<int32_t> &n_states, const std::vector<double> *states,
+             int max_states, const double *q_new14, const double *pose8, const double *goal_pose8, const std::vector<int32_t> &roots,
+             int32_t *new_index = nullptr, std::vector<int32_t> *mid_index = nullptr, bool keep_isolated = false, bool have_state = true) noexcept
+  {
+    const size_t k = idx.size();
+    int32_t t = -1, state = CCMP_GROW_TRAPPED;
+    std::vector<int32_t> mids;
+    if (new_index) *new_index = -1;
+    try {
+      mids.assign(k, -1);
+      if (mid_index) mid_index->assign(k, -1);
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::commit");
+      return CCMP_GROW_TRAPPED;
+    }
+    if (ok.size() != k || n_states.size() != k || (states && states->size() < k * (size_t)(max_states > 0 ? max_states : 0) * 14)) {
+      record(CCMP_EINVAL, "Roadmap::commit");
+      return CCMP_GROW_TRAPPED;
+    }
+    const uint8_t vertex_ok = have_state ? 1 : 0;
+    const bool ran = call([&] {
+      return ccmp_roadmap_commit_host(rm_, &proj_.problem(), idx.data(), ok.data(), n_states.data(), states ? states->data() : nullptr, max_states, q_new14,
+                                      pose8, &vertex_ok, 1, (int)k, goal_pose8, roots.data(), (int)roots.size(),
+                                      keep_isolated ? (unsigned int)CCMP_COMMIT_KEEP_ISOLATED : 0u, &t, mids.data(), &state, nullptr, nullptr);
+    }, "ccmp_roadmap_commit_host");
+    if (!ran) return CCMP_GROW_TRAPPED;
+    if (new_index) *new_index = t;
+    if (mid_index) mid_index->swap(mids);
+    return state;
+  }
+  // explicit edges uv [n][2] between existing vertices, weighted by the joint distance on the device
+  bool addEdges(const int32_t *uv, size_t n = 1) noexcept { return call([&] { return ccmp_roadmap_add_edges_host(rm_, uv, n); }, "ccmp_roadmap_add_edges_host"); }
+  size_t numEdges() const noexcept { return ccmp_roadmap_num_edges(rm_); }
+  bool readEdges(size_t first, size_t count, int32_t *uv, double *w) const noexcept
+  {
+    return call([&] { return ccmp_roadmap_read_edges_host(rm_, first, count, uv, w); }, "ccmp_roadmap_read_edges_host");
+  }
+  bool readLabels(size_t first, size_t count, int32_t *labels) const noexcept
+  {
+    return call([&] { return ccmp_roadmap_read_labels_host(rm_, first, count, labels); }, "ccmp_roadmap_read_labels_host");
+  }
+  // closestFromGoal's vertex scan for every `from` (at most CCMP_CLOSEST_MAX_FROM): the vertex of from's component nearest to
+  // target_pose8 by (distance, index), its distance, and from's own distance (nullable); false and -1 / +inf / NaN when the call failed
+  bool closest(const std::vector<int32_t> &froms, const double *target_pose8, std::vector<int32_t> *idx, std::vector<double> *dist,
+               std::vector<double> *from_dist = nullptr) const noexcept
+  {
+    std::vector<double> fd;
+    try {
+      idx->assign(froms.size(), -1);
+      dist->assign(froms.size(), std::numeric_limits<double>::infinity());
+      fd.assign(froms.size(), std::numeric_limits<double>::quiet_NaN());
+      if (from_dist) *from_dist = fd;
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::closest");
+      return false;
+    }
+    const bool ran = call([&] { return ccmp_roadmap_closest_host(rm_, froms.data(), froms.size(), target_pose8, idx->data(), dist->data(), fd.data()); },
+                          "ccmp_roadmap_closest_host");
+    if (ran && from_dist) from_dist->swap(fd);
+    return ran;
+  }
+
   int lastError() const noexcept { return err_code_; }
   std::string lastErrorMessage() const { return err_what_; }
   void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }

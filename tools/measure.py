@@ -28,6 +28,9 @@
     python tools/measure.py object [reps_a] [reps_b] [G_b]  the head of growTree (object-pose proposal + mesh test): (a) propose with G = 1, 2 attempts, a dumbbell of
                                                            ~1 000 triangles against the six fixture boxes through the host form, (b) G_b = 4096 through the device form,
                                                            (c) valid on 4096 poses of a ~8 600-triangle sphere, each against the *_ref form on one thread on the same inputs
+    python tools/measure.py graph [reps]                    the roadmap graph (growTree's tail, closestFromGoal's scan, labels): (a) commit with Q = 1, k = 5, lists of 64
+                                                           through the host form, (b) Q = 4096 through the device form, (c) closest and (d) a one-edge label update at
+                                                           N = 65 536, each against the *_ref form on one thread on the same inputs; writes profiles/roadmap_graph.md
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -912,6 +915,147 @@ def object_(argv):
              np.median(tc["ccmp_object_valid_ref (one thread)"]) / np.median(tc["device form, early exit"])))
 
 
+def graph(argv):
+    """ccmp_roadmap_commit / _closest / a one-edge label update against their *_ref forms (the same text on one host thread) on the same
+    inputs; outputs compared while they are timed.  Writes profiles/roadmap_graph.md.  Inputs: tests/graph_cases.py."""
+    import os
+
+    sys.path.insert(0, "tests")
+    from graph_cases import Graph, base_store, commit_args, initial_edges, make_case, union_find_labels
+
+    from closed_chain_motion_planner_amd import Roadmap, closest_ref, commit_ref, graph_labels_ref
+
+    reps = int(argv[0]) if len(argv) > 0 else 30
+    ctx = Context(0)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    joints, poses, fresh, fresh_poses, goal = base_store()
+    e0 = initial_edges(len(joints))
+    lines = []
+
+    def store():
+        rm = Roadmap(c, capacity_hint=1 << 17)
+        rm.append(torch.from_numpy(np.array(joints)).cuda(), torch.from_numpy(np.array(poses)).cuda())
+        rm.add_edges(torch.from_numpy(e0).cuda())
+        return rm
+
+    def report(title, times, agree):
+        print("%s; outputs identical: %s" % (title, agree))
+        lines.append("%s; outputs identical: %s" % (title, agree))
+        for name, ms in times.items():
+            print("    %-44s %s" % (name, _stat(ms)))
+            lines.append("    %-44s %s" % (name, _stat(ms)))
+
+    # (a) the planner's shape: Q = 1, k = 5, lists of 64 states, host pointers, wall clock around the synchronous call
+    rm = store()
+    labels = union_find_labels(e0, len(joints))
+    ta = {"ccmp_roadmap_commit_host (device)": [], "ccmp_roadmap_commit_ref (one thread)": []}
+    agree = True
+    for i in range(reps + 3):
+        case = make_case(joints, poses, 1, 5, 900 + i, goal, fresh[i % 40:i % 40 + 1], fresh_poses[i % 40:i % 40 + 1], with_vertex_ok=False)
+        wide = np.zeros((5, 64, 14))
+        wide[:, :case["states"].shape[1]] = case["states"]
+        case["states"], case["max_states"] = wide, 64
+        kw = commit_args(case)
+        n0, ne0 = len(rm), rm.num_edges
+        t0 = time.perf_counter()
+        dev = rm.commit(**kw)
+        t1 = time.perf_counter()
+        ref = commit_ref(c.problem, joints, poses, labels, **kw)
+        t2 = time.perf_counter()
+        agree = agree and all(np.array_equal(dev[k], ref[k]) for k in ("new_index", "mid_index", "grow_state")) and dev["edges_added"] == len(ref["edges_uv"])
+        rm.close()
+        rm = store()  # every call starts from the same store
+        if i >= 3:
+            ta["ccmp_roadmap_commit_host (device)"].append((t1 - t0) * 1e3)
+            ta["ccmp_roadmap_commit_ref (one thread)"].append((t2 - t1) * 1e3)
+    report("(a) commit Q = 1, k = 5, lists of 64, host form, wall clock", ta, agree)
+
+    # (b) Q = 4096, k = 5: device pointers, wall clock to the end of the call (it ends with its own read-back)
+    Q = 4096
+    case = make_case(joints, poses, Q, 5, 77, goal, fresh, fresh_poses)
+    kw = commit_args(case)
+    kd = dict(kw)
+    for name in ("nbr_idx", "edge_ok", "n_states", "new_joints", "new_poses", "states", "vertex_ok"):
+        kd[name] = torch.from_numpy(np.ascontiguousarray(kw[name])).cuda()
+    tb = {"ccmp_roadmap_commit (device)": [], "ccmp_roadmap_commit_ref (one thread)": []}
+    agree = True
+    for i in range(3 + 3):
+        rm.close()
+        rm = store()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dev = rm.commit(**kd)
+        t1 = time.perf_counter()
+        ref = commit_ref(c.problem, joints, poses, labels, **kw)
+        t2 = time.perf_counter()
+        agree = agree and all(np.array_equal(dev[k].cpu().numpy(), ref[k]) for k in ("new_index", "mid_index", "grow_state"))
+        uv, w = rm.edges(len(e0), host=True)
+        agree = agree and np.array_equal(uv, ref["edges_uv"]) and np.array_equal(w.view(np.uint8), ref["edges_w"].view(np.uint8))
+        if i >= 3:
+            tb["ccmp_roadmap_commit (device)"].append((t1 - t0) * 1e3)
+            tb["ccmp_roadmap_commit_ref (one thread)"].append((t2 - t1) * 1e3)
+    report("(b) commit Q = %d, k = 5, device form, wall clock to its read-back; %d vertices and %d edges added" % (Q, dev["vertices_added"], dev["edges_added"]), tb, agree)
+    rm.close()
+
+    # (c) closest and (d) a one-edge label update at N = 65536 (pose-only vertices; random edges: components of every size)
+    N = 65536
+    rng = np.random.default_rng(0x6A)
+    big = np.zeros((N, 8))
+    big[:, :3] = rng.uniform(-1, 1, (N, 3))
+    quat = rng.normal(size=(N, 4))
+    big[:, 3:7] = quat / np.linalg.norm(quat, axis=1, keepdims=True)
+    uv = rng.integers(0, N, size=(N, 2)).astype(np.int32)
+    uv = np.ascontiguousarray(uv[uv[:, 0] != uv[:, 1]])
+    rm = Roadmap(c, capacity_hint=N + 64)
+    rm.append(None, torch.from_numpy(big).cuda())
+    rm.add_edges(torch.from_numpy(uv).cuda())
+    lab = rm.labels(host=True)
+    agree = np.array_equal(lab, graph_labels_ref(uv, N))
+    froms = np.array([int(np.argmax(np.bincount(lab)))], dtype=np.int32)  # a vertex of the largest component (its label is its smallest index)
+    froms_d, tgt_d = torch.from_numpy(froms).cuda(), torch.from_numpy(big[7].copy()).cuda()
+    tc = {"ccmp_roadmap_closest (device, events)": [], "ccmp_roadmap_closest_host (wall clock)": [], "ccmp_roadmap_closest_ref (one thread)": []}
+    for i in range(reps + 3):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        e[0].record()
+        dev = rm.closest(froms_d, tgt_d)
+        e[1].record()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        host = rm.closest(froms, big[7])
+        t1 = time.perf_counter()
+        ref = closest_ref(big, lab, froms, big[7])
+        t2 = time.perf_counter()
+        agree = agree and all(np.array_equal(a.cpu().numpy().view(np.uint8), b.view(np.uint8)) and np.array_equal(h.view(np.uint8), b.view(np.uint8))
+                              for a, h, b in zip(dev, host, ref))
+        if i >= 3:
+            tc["ccmp_roadmap_closest (device, events)"].append(e[0].elapsed_time(e[1]))
+            tc["ccmp_roadmap_closest_host (wall clock)"].append((t1 - t0) * 1e3)
+            tc["ccmp_roadmap_closest_ref (one thread)"].append((t2 - t1) * 1e3)
+    report("(c) closest F = 1 at N = %d (from's component: %d vertices)" % (N, int((lab == lab[froms[0]]).sum())), tc, agree)
+    td = {"ccmp_roadmap_add_edges_host, one edge (device)": [], "ccmp_graph_labels_ref, all edges (one thread)": []}
+    done = uv
+    for i in range(reps + 3):
+        one = rng.integers(0, N, size=(1, 2)).astype(np.int32)
+        if one[0, 0] == one[0, 1]:
+            continue
+        t0 = time.perf_counter()
+        rm.add_edges(one)
+        t1 = time.perf_counter()
+        done = np.concatenate([done, one])
+        want = graph_labels_ref(done, N)
+        t2 = time.perf_counter()
+        agree = agree and np.array_equal(rm.labels(host=True), want)
+        if i >= 3:
+            td["ccmp_roadmap_add_edges_host, one edge (device)"].append((t1 - t0) * 1e3)
+            td["ccmp_graph_labels_ref, all edges (one thread)"].append((t2 - t1) * 1e3)
+    report("(d) one-edge label update at N = %d, %d edges, host form, wall clock (the host contender has no incremental form: it rebuilds)" % (N, len(done)), td, agree)
+    rm.close()
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "roadmap_graph.md"), "w") as f:
+        f.write("# Roadmap graph on the device: `tools/measure.py graph`\n\n1 x MI355X, one run; every device form against its `_ref` form on one host thread on the "
+                "same inputs, the outputs compared while they are timed.  No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -982,7 +1126,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
