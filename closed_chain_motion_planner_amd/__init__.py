@@ -13,7 +13,7 @@ from .space import (check_motion, format_graphml, format_graphviz, format_path_m
 
 from .scene import ProxyScene, ProxyValidityChecker, default_allowed, skeleton_spheres  # noqa: F401
 
-from .roadmap import Roadmap, closest_ref, commit_ref, graph_labels_ref, joint_distance, pose_distance, pose_from_t_wo  # noqa: F401
+from .roadmap import Roadmap, closest_ref, commit_ref, graph_labels_ref, joint_distance, pose_distance, pose_from_t_wo, shortest_paths_ref  # noqa: F401
 
 from .ik import ik_options, pose_ik_ref  # noqa: F401
 

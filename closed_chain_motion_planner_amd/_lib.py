@@ -89,6 +89,7 @@ EXPORTS = [
     "ccmp_joint_distance", "ccmp_graph_labels_ref", "ccmp_roadmap_commit", "ccmp_roadmap_commit_host", "ccmp_roadmap_commit_ref",
     "ccmp_roadmap_add_edges", "ccmp_roadmap_add_edges_host", "ccmp_roadmap_num_edges", "ccmp_roadmap_read_edges", "ccmp_roadmap_read_edges_host",
     "ccmp_roadmap_read_labels", "ccmp_roadmap_read_labels_host", "ccmp_roadmap_closest", "ccmp_roadmap_closest_host", "ccmp_roadmap_closest_ref",
+    "ccmp_roadmap_shortest_paths", "ccmp_roadmap_shortest_paths_host", "ccmp_graph_shortest_paths_ref", "ccmp_roadmap_path_rounds_host",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -252,6 +253,10 @@ def lib():
         "ccmp_roadmap_closest": ([vp, vp, C.c_size_t, vp, vp, vp, vp, vp], C.c_int),
         "ccmp_roadmap_closest_host": ([vp, i32p, C.c_size_t, dp, i32p, dp, dp], C.c_int),
         "ccmp_roadmap_closest_ref": ([dp, i32p, C.c_size_t, i32p, C.c_size_t, dp, i32p, dp, dp], C.c_int),
+        "ccmp_roadmap_shortest_paths": ([vp, vp, vp, C.c_size_t, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_shortest_paths_host": ([vp, i32p, i32p, C.c_size_t, C.c_int, dp, i32p, i32p, dp, dp, dp, i32p], C.c_int),
+        "ccmp_graph_shortest_paths_ref": ([i32p, dp, C.c_size_t, C.c_size_t, i32p, i32p, C.c_size_t, C.c_int, dp, i32p, i32p, dp, i32p], C.c_int),
+        "ccmp_roadmap_path_rounds_host": ([vp, C.c_size_t, i32p], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -292,6 +297,7 @@ KNN_MAX_K = 16
 GROW_TRAPPED, GROW_SREACHED, GROW_GREACHED, GROW_UNSETTLED = range(4)  # ccmp.h: CCMP_GROW_*
 COMMIT_KEEP_ISOLATED = 1  # ccmp.h: CCMP_COMMIT_*
 GRAPH_MAX_ROOTS, CLOSEST_MAX_FROM = 32, 64  # ccmp.h: CCMP_GRAPH_MAX_ROOTS, CCMP_CLOSEST_MAX_FROM
+PATH_MAX_PAIRS = 64  # ccmp.h: CCMP_PATH_MAX_PAIRS
 
 
 def option_table():

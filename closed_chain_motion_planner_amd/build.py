@@ -31,7 +31,8 @@ Translation units with deliberately different flags:
   ccmp_kernels_object.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the head of growTree: object-pose proposal (interpolate, SE3 Gaussian draw) and the
                          mesh-against-workspace test (ccmp_object.h), one 256-lane block per pose, the triangles strided over the lanes
   ccmp_kernels_graph.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the roadmap graph (ccmp_graph.h): growTree's tail (commit), explicit edges, the component labels
-                         (hooking rounds in one block, then a compress launch) and closestFromGoal's vertex scan; ccmp_roadmap.cpp compiles the same header for the *_ref forms
+                         (hooking rounds in one block, then a compress launch) and closestFromGoal's vertex scan; ccmp_roadmap.cpp compiles the same header for the *_ref forms;
+                         and the planner's solution step, shortest paths on that graph (ccmp_path.h: graph_path_*, relaxation and hop rounds in one block per pair)
   ccmp_object.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_object_*: checks, launches, and the same text on the host (the *_ref forms, same bits as the kernels)
 """
 import os
@@ -104,7 +105,7 @@ _UNITS = [
     # ccmp_object_*: the checks and launches, and ccmp_object.h compiled for the host (the *_ref forms: the kernels' bits without a device)
     ("ccmp_object.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():

@@ -25,18 +25,37 @@
 // Closest: graph_closest_kernel, knn_pose_few_kernel's layout with lists of one — blocks over (partition, from), a lane takes the
 // vertices t, t + 256, ... of the partition whose label is from's, the 256 bests are merged in LDS; several partitions leave theirs in the
 // workspace and graph_closest_merge_kernel merges them.  (distance, index) is a total order: no launch shape changes the answer.
+//
+// Shortest paths (ccmp_path.h), three launches, one pair (src[f], dst[f]) per f < F, per-pair arrays d / hops / pred / stamp [F][N]:
+//   graph_path_init_kernel     multi-block: +inf, INT_MAX, -1 and stamp -1 everywhere, the source's entries 0.
+//   graph_path_sssp_kernel     ONE block per pair, up to 1024 lanes striding over the edge list, three phases separated by block barriers
+//                              only.  Relaxation rounds: every edge in both directions, atomicMin on the distance's bits (distances are
+//                              >= +0.0 and never NaN: the order of the bits is theirs); stamp[v] = the last round that lowered d[v], and
+//                              round r skips an edge when neither endpoint was lowered in round r - 1 or later.  A vertex's last move in
+//                              round r keeps stamp == r through the whole of round r + 1, where each of its edges is relaxed with the
+//                              final value: a round without a move ends the phase at the fixed point, after at most N + 1 rounds (after
+//                              round r every vertex whose cheapest path has <= r edges is final).  Hop rounds likewise: round r gives level
+//                              r over tight edges from level r - 1.  Then one pass: atomicMin of u into pred[v] over the tree candidates
+//                              (as unsigned: -1 is "none", above every vertex).  Both round loops carry the bound N + 1.  d, hops and stamp
+//                              are read with agent-scope atomic loads: what an atomic left in L2 is the truth, never an L1 line.
+//   graph_path_extract_kernel  one block per pair: lane 0 walks pred from dst (hops[dst] + 1 steps, the loop's bound) into path[f] front to
+//                              back, then the lanes gather the joint and pose rows.
+// The answer is a function of the edge set: no arrival order of the atomics, no block size changes a bit.
 #include <hip/hip_runtime.h>
 
 #include "ccmp_detmath.h"
 #include "ccmp_graph.h"
 #include "ccmp_launch.h"
+#include "ccmp_path.h"
 
 namespace {
 
 using ccmp_launch::GraphCommit;
+using ccmp_launch::GraphPath;
 using ccmp_launch::GraphStore;
 using ccmp_launch::GraphWork;
 constexpr int kThreads = ccmp_launch::kGraphThreads;
+constexpr int kPathThreads = ccmp_launch::kPathThreads;
 constexpr int kEmptyIdx = 0x7fffffff; // no candidate yet: (+inf, kEmptyIdx), behind every vertex
 
 __global__ __launch_bounds__(kThreads) void graph_iota_kernel(int32_t *__restrict__ labels, unsigned long long first, unsigned long long n)
@@ -291,6 +310,134 @@ __global__ __launch_bounds__(kThreads) void graph_closest_merge_kernel(int P, co
   }
 }
 
+// ---- shortest paths (ccmp_path.h) ---------------------------------------------------------------------------------------------------
+using u64 = unsigned long long;
+__device__ __forceinline__ u64 path_ld64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int32_t path_ld32(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the grid: (blocks over the N vertices, F)
+__global__ __launch_bounds__(kThreads) void graph_path_init_kernel(const GraphPath p, unsigned long long N)
+{
+  const unsigned long long i = (unsigned long long)blockIdx.x * kThreads + threadIdx.x, f = blockIdx.y;
+  if (i >= N) return;
+  const int32_t s = p.src[f];
+  const bool source = s >= 0 && (unsigned long long)s == i; // (i < N: a source outside the store matches no lane, nothing is reached)
+  const unsigned long long o = f * N + i;
+  p.d[o] = source ? 0ull : ccmp::path_bits(__builtin_inf());
+  p.hops[o] = source ? 0 : ccmp::kPathNoHops;
+  p.pred[o] = -1;
+  p.stamp[o] = source ? 0 : -1;
+}
+
+// one direction of one edge in relaxation round r; true: d[v] went down
+__device__ __forceinline__ bool path_relax(u64 *d, int32_t *stamp, int32_t u, int32_t v, double w, int32_t r)
+{
+  double c;
+  if (!ccmp::path_candidate(ccmp::path_from_bits(path_ld64(d + u)), w, &c)) return false;
+  const u64 cb = ccmp::path_bits(c);
+  if (cb >= path_ld64(d + v)) return false;
+  if (atomicMin(d + v, cb) <= cb) return false; // another lane was there first with no more
+  __hip_atomic_store(stamp + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
+}
+
+__global__ __launch_bounds__(kPathThreads) void graph_path_sssp_kernel(const GraphStore s, const GraphPath p)
+{
+  __shared__ int changed;
+  const unsigned int t = threadIdx.x, nt = blockDim.x, N = (unsigned int)s.N, E = (unsigned int)s.E;
+  const size_t f = blockIdx.x;
+  u64 *d = p.d + f * N;
+  int32_t *hops = p.hops + f * N, *pred = p.pred + f * N, *stamp = p.stamp + f * N;
+  const int32_t max_rounds = N < 0x7ffffffeu ? (int32_t)N + 1 : 0x7ffffffe;
+  int32_t relax_rounds = 0, hop_rounds = 0;
+  for (int32_t r = 1; r <= max_rounds; r++) {
+    if (t == 0) changed = 0;
+    __syncthreads();
+    for (unsigned int e = t; e < E; e += nt) {
+      const int32_t u = s.uv[2 * e], v = s.uv[2 * e + 1];
+      if ((unsigned int)u >= N || (unsigned int)v >= N) continue; // (the store's edges are inside it; this keeps every access in bounds)
+      if (path_ld32(stamp + u) < r - 1 && path_ld32(stamp + v) < r - 1) continue;
+      const double w = s.w[e];
+      const bool a = path_relax(d, stamp, u, v, w, r), b = path_relax(d, stamp, v, u, w, r);
+      if (a || b) changed = 1;
+    }
+    __syncthreads(); // the round's atomics are done and visible to the block (one block: workgroup scope is all it takes)
+    const int more = changed;
+    __syncthreads();
+    relax_rounds = r;
+    if (!more) break;
+  }
+  for (int32_t r = 1; r <= max_rounds; r++) {
+    if (t == 0) changed = 0;
+    __syncthreads();
+    for (unsigned int e = t; e < E; e += nt) {
+      const int32_t u = s.uv[2 * e], v = s.uv[2 * e + 1];
+      if ((unsigned int)u >= N || (unsigned int)v >= N) continue;
+      const int32_t hu = path_ld32(hops + u), hv = path_ld32(hops + v);
+      if (hu != r - 1 && hv != r - 1) continue;
+      const double w = s.w[e], du = ccmp::path_from_bits(path_ld64(d + u)), dv = ccmp::path_from_bits(path_ld64(d + v));
+      if (hu == r - 1 && hv > r && ccmp::path_tight(du, w, dv)) { atomicMin(hops + v, r); changed = 1; }
+      if (hv == r - 1 && hu > r && ccmp::path_tight(dv, w, du)) { atomicMin(hops + u, r); changed = 1; }
+    }
+    __syncthreads();
+    const int more = changed;
+    __syncthreads();
+    hop_rounds = r;
+    if (!more) break;
+  }
+  for (unsigned int e = t; e < E; e += nt) {
+    const int32_t u = s.uv[2 * e], v = s.uv[2 * e + 1];
+    if ((unsigned int)u >= N || (unsigned int)v >= N) continue;
+    const int32_t hu = path_ld32(hops + u), hv = path_ld32(hops + v);
+    const double w = s.w[e], du = ccmp::path_from_bits(path_ld64(d + u)), dv = ccmp::path_from_bits(path_ld64(d + v));
+    if (ccmp::path_parent(du, hu, w, dv, hv)) atomicMin((unsigned int *)pred + v, (unsigned int)u);
+    if (ccmp::path_parent(dv, hv, w, du, hu)) atomicMin((unsigned int *)pred + u, (unsigned int)v);
+  }
+  if (t == 0) { p.rounds[2 * f] = relax_rounds; p.rounds[2 * f + 1] = hop_rounds; }
+}
+
+// a launch of its own behind the sssp launch: plain loads see what its atomics left
+__global__ __launch_bounds__(kThreads) void graph_path_extract_kernel(const GraphStore s, const GraphPath p)
+{
+  __shared__ int s_len;
+  const int t = threadIdx.x;
+  const size_t f = blockIdx.x;
+  const unsigned int N = (unsigned int)s.N;
+  int32_t *path = p.path + f * (size_t)p.max_len;
+  if (t == 0) {
+    const int32_t src = p.src[f], dst = p.dst[f];
+    int32_t len = 0;
+    double cost = __builtin_nan("");
+    if (src >= 0 && dst >= 0 && (unsigned int)src < N && (unsigned int)dst < N) {
+      const int32_t h = p.hops[f * N + dst];
+      cost = ccmp::path_from_bits(p.d[f * N + dst]);
+      len = h == ccmp::kPathNoHops ? 0 : h + 1;
+      if (len <= p.max_len) {
+        int32_t v = dst;
+        for (int32_t i = len - 1; i >= 0 && (unsigned int)v < N; i--) { // hops[v] falls by one per step: exactly len steps
+          path[i] = v;
+          v = p.pred[f * N + v];
+        }
+      }
+    }
+    p.cost[f] = cost;
+    p.path_len[f] = len;
+    s_len = len <= p.max_len ? len : 0;
+  }
+  __syncthreads(); // lane 0's path entries are visible to the block
+  const int len = s_len;
+  if (p.path_joints)
+    for (int i = t; i < len * 14; i += kThreads) {
+      const unsigned int v = (unsigned int)path[i / 14];
+      if (v < N) p.path_joints[(f * (size_t)p.max_len + (size_t)(i / 14)) * 14 + (size_t)(i % 14)] = s.joints[(size_t)v * 14 + (size_t)(i % 14)];
+    }
+  if (p.path_poses)
+    for (int i = t; i < len * 8; i += kThreads) {
+      const unsigned int v = (unsigned int)path[i / 8];
+      if (v < N) p.path_poses[(f * (size_t)p.max_len + (size_t)(i / 8)) * 8 + (size_t)(i % 8)] = s.poses[(size_t)v * 8 + (size_t)(i % 8)];
+    }
+}
+
 unsigned int blocks_of(size_t n) { return (unsigned int)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
@@ -350,6 +497,21 @@ hipError_t graph_closest(const GraphStore &s, const int32_t *from_idx, size_t F,
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess || partitions == 1) return e;
   hipLaunchKernelGGL(graph_closest_merge_kernel, dim3((unsigned int)F), dim3(kThreads), 0, st, (int)partitions, ws_d, ws_i, idx, dist);
+  return hipGetLastError();
+}
+
+hipError_t graph_paths(const GraphStore &s, const GraphPath &p, hipStream_t st)
+{
+  hipError_t e = hipSuccess;
+  if (s.N > 0) {
+    hipLaunchKernelGGL(graph_path_init_kernel, dim3(blocks_of(s.N), (unsigned int)p.F), dim3(kThreads), 0, st, p, (unsigned long long)s.N);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    size_t lanes = (s.E + 63) / 64 * 64; // a lane per edge up to the block's 1024
+    lanes = lanes < 64 ? 64 : lanes > (size_t)kPathThreads ? (size_t)kPathThreads : lanes;
+    hipLaunchKernelGGL(graph_path_sssp_kernel, dim3((unsigned int)p.F), dim3((unsigned int)lanes), 0, st, s, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(graph_path_extract_kernel, dim3((unsigned int)p.F), dim3(kThreads), 0, st, s, p);
   return hipGetLastError();
 }
 

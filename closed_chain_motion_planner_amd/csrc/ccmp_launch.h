@@ -189,6 +189,19 @@ struct GraphCommit {
   int32_t *new_index, *mid_index, *grow_state;
 };
 
+/* one shortest-path call (ccmp_roadmap_shortest_paths; csrc/ccmp_path.h): the pairs, the per-pair arrays of the handle's workspace and
+ * the caller's outputs.  d holds the distances' bits. */
+constexpr int kPathThreads = 1024;  // lanes of the ONE block that runs a pair's relaxation and hop rounds
+struct GraphPath {
+  const int32_t *src, *dst; int F; // [F] each
+  unsigned long long *d;           // [F][N]
+  int32_t *hops, *pred, *stamp;    // [F][N] each
+  int32_t *rounds;                 // [F][2]: the relaxation and hop rounds the call took
+  int max_len;
+  double *cost; int32_t *path_len, *path; // [F], [F], [F][max_len]
+  double *path_joints, *path_poses;       // [F][max_len][14], [F][max_len][8]; nullable
+};
+
 #pragma GCC visibility push(hidden)
 /* label[first + i] = first + i (an append) */
 hipError_t graph_iota(int32_t *labels, size_t first, size_t n, hipStream_t st);
@@ -202,6 +215,8 @@ hipError_t graph_components(const GraphStore &s, const int32_t *totals, size_t n
 /* blocks over (partition, from), bests of one, then the exact merge (partitions > 1: ws_d [F][P], ws_i [F][P]) */
 hipError_t graph_closest(const GraphStore &s, const int32_t *from_idx, size_t F, const double *target, unsigned int part, unsigned int partitions,
                          double *ws_d, int32_t *ws_i, int32_t *idx, double *dist, double *from_dist, hipStream_t st);
+/* init -> rounds in one block per pair -> extract (cost, length, path, rows); s.N == 0: the extract alone */
+hipError_t graph_paths(const GraphStore &s, const GraphPath &p, hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

@@ -6,12 +6,16 @@
 // ccmp_host::connect_checks / connect_edges), as is the workspace rule (ccmp_host::grow_buffer).
 // The store also keeps the planner's graph: an edge list with weights and one component label per vertex, with the edge count and the
 // edge floor as host state; growTree's tail (ccmp_roadmap_commit), explicit edges and closestFromGoal's scan are launches of
-// ccmp_kernels_graph.hip, and their *_ref forms compile the same rule text here (ccmp_graph.h).
+// ccmp_kernels_graph.hip, and their *_ref forms compile the same rule text here (ccmp_graph.h).  The planner's solution step, shortest
+// paths on that graph (ccmp_path.h), is three more launches of the unit over a workspace the handle grows on first use; its *_ref form
+// finds the distances by heap Dijkstra and the hops and predecessors from the same rule text.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <queue>
+#include <utility>
 #include <vector>
 
 #include "../../include/ccmp.h"
@@ -20,6 +24,7 @@
 #include "ccmp_host.h"
 #include "ccmp_ik.h"
 #include "ccmp_launch.h"
+#include "ccmp_path.h"
 #include "ccmp_policy.h"
 #include "ccmp_pose.h"
 #include "ccmp_resident.h"
@@ -46,6 +51,9 @@ struct ccmp_roadmap {
   void *graph_ws = nullptr;  // commit / add_edges: ccmp_launch::GraphWork for graph_ws_cap slots
   size_t graph_ws_cap = 0;
   void *closest_ws = nullptr; // closest: the partitions' bests, distances [64][256] then indices (allocated with the store)
+  void *path_ws = nullptr;    // shortest_paths: rounds [64][2] | d [F][N] (64-bit) | hops | pred | stamp [F][N] (int32); grown on first use
+  size_t path_ws_cap = 0;     // in elements of F N, plus one
+  size_t path_F = 0, path_N = 0; // the shape of the last call (what path_rounds and the host form's read-backs address)
 };
 
 namespace {
@@ -210,6 +218,17 @@ void plan_closest(size_t N, unsigned int *part, unsigned int *partitions)
   *partitions = N ? (unsigned int)((N + pt - 1) / pt) : 1;
 }
 
+// what every form of a shortest-path call checks first
+int path_checks(const int32_t *src, const int32_t *dst, size_t F, int max_len, const double *cost, const int32_t *path_len, const int32_t *path)
+{
+  if (F > CCMP_PATH_MAX_PAIRS || max_len < 1 || !src || !dst || !cost || !path_len || !path) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+constexpr size_t kPathHeadBytes = CCMP_PATH_MAX_PAIRS * 2 * sizeof(int32_t); // the rounds, in front of the arrays
+unsigned long long *path_d(const ccmp_roadmap *rm) { return (unsigned long long *)((char *)rm->path_ws + kPathHeadBytes); }
+int32_t *path_pred(const ccmp_roadmap *rm) { return (int32_t *)(path_d(rm) + rm->path_F * rm->path_N) + rm->path_F * rm->path_N; }
+
 int knn_checks(const ccmp_roadmap *rm, int metric, const void *queries, size_t Q, int k, int mode, const int32_t *nbr_idx)
 {
   if (!rm) return no_store();
@@ -280,6 +299,7 @@ void ccmp_roadmap_destroy(ccmp_roadmap *rm)
     if (rm->w) (void)hipFree(rm->w);
     if (rm->graph_ws) (void)hipFree(rm->graph_ws);
     if (rm->closest_ws) (void)hipFree(rm->closest_ws);
+    if (rm->path_ws) (void)hipFree(rm->path_ws);
   }
   delete rm;
 }
@@ -977,6 +997,186 @@ int ccmp_roadmap_closest_host(ccmp_roadmap *rm, const int32_t *from_idx, size_t 
   if (rc != CCMP_OK) return rc;
   HIP_TRY(e);
   HIP_TRY(es);
+  return CCMP_OK;
+}
+
+// ---- shortest paths: the planner's solution step (ccmp_path.h) ---------------------------------------------------------------------------
+int ccmp_roadmap_shortest_paths(ccmp_roadmap *rm, const int32_t *src, const int32_t *dst, size_t F, int max_len, double *cost, int32_t *path_len,
+                                int32_t *path, double *path_joints, double *path_poses, double *dist_out, int32_t *pred_out, void *hip_stream)
+{
+  if (!rm) return no_store();
+  if (F == 0) return CCMP_OK;
+  { const int rc = path_checks(src, dst, F, max_len, cost, path_len, path); if (rc != CCMP_OK) return rc; }
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t N = rm->size, n = F * N;
+  { const int rc = grow_buffer(rm->ctx, &rm->path_ws, &rm->path_ws_cap, n + 1, kPathHeadBytes + n * (sizeof(double) + 3 * sizeof(int32_t))); if (rc != CCMP_OK) return rc; }
+  rm->path_F = F;
+  rm->path_N = N;
+  ccmp_launch::GraphPath gp{};
+  gp.src = src;
+  gp.dst = dst;
+  gp.F = (int)F;
+  gp.rounds = (int32_t *)rm->path_ws;
+  gp.d = path_d(rm);
+  gp.hops = (int32_t *)(gp.d + n);
+  gp.pred = gp.hops + n;
+  gp.stamp = gp.pred + n;
+  gp.max_len = max_len;
+  gp.cost = cost;
+  gp.path_len = path_len;
+  gp.path = path;
+  gp.path_joints = path_joints;
+  gp.path_poses = path_poses;
+  if (N == 0) HIP_TRY(hipMemsetAsync(gp.rounds, 0, kPathHeadBytes, st));
+  HIP_TRY(ccmp_launch::graph_paths(graph_store(rm), gp, st));
+  if (dist_out && n) HIP_TRY(hipMemcpyAsync(dist_out, gp.d, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (pred_out && n) HIP_TRY(hipMemcpyAsync(pred_out, gp.pred, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_path_rounds_host(ccmp_roadmap *rm, size_t F, int32_t *rounds)
+{
+  if (!rm) return no_store();
+  if (F == 0) return CCMP_OK;
+  if (!rounds || !rm->path_ws || F > rm->path_F) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = rm->ctx->stream;
+  const hipError_t e = hipMemcpyAsync(rounds, rm->path_ws, F * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_roadmap_shortest_paths_host(ccmp_roadmap *rm, const int32_t *src, const int32_t *dst, size_t F, int max_len, double *cost, int32_t *path_len,
+                                     int32_t *path, double *path_joints, double *path_poses, double *dist_out, int32_t *pred_out)
+{
+  if (!rm) return no_store();
+  if (F == 0) return CCMP_OK;
+  { const int rc = path_checks(src, dst, F, max_len, cost, path_len, path); if (rc != CCMP_OK) return rc; }
+  for (size_t f = 0; f < F; f++)
+    if (src[f] < 0 || (size_t)src[f] >= rm->size || dst[f] < 0 || (size_t)dst[f] >= rm->size) return CCMP_EINVAL;
+  DeviceGuard guard(rm->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  ccmp_ctx *ctx = rm->ctx;
+  hipStream_t st = ctx->stream;
+  const size_t L = (size_t)max_len;
+  Stage sg(ctx);
+  const size_t off_s = sg.add(F * sizeof(int32_t)), off_d = sg.add(F * sizeof(int32_t)), off_c = sg.add(F * sizeof(double)), off_l = sg.add(F * sizeof(int32_t)),
+               off_p = sg.add(F * L * sizeof(int32_t)), off_j = sg.add(path_joints ? F * L * 14 * sizeof(double) : 0),
+               off_o = sg.add(path_poses ? F * L * 8 * sizeof(double) : 0);
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
+  hipError_t e = hipMemcpyAsync(sg.at(off_s), src, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(sg.at(off_d), dst, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  int rc = CCMP_OK;
+  if (e == hipSuccess)
+    rc = ccmp_roadmap_shortest_paths(rm, (const int32_t *)sg.at(off_s), (const int32_t *)sg.at(off_d), F, max_len, (double *)sg.at(off_c), (int32_t *)sg.at(off_l),
+                                     (int32_t *)sg.at(off_p), path_joints ? (double *)sg.at(off_j) : nullptr, path_poses ? (double *)sg.at(off_o) : nullptr, nullptr,
+                                     nullptr, st);
+  const size_t n = F * rm->size; // the distances and predecessors come straight from the workspace
+  if (rc == CCMP_OK && e == hipSuccess) {
+    e = hipMemcpyAsync(cost, sg.at(off_c), F * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(path_len, sg.at(off_l), F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dist_out && n) e = hipMemcpyAsync(dist_out, path_d(rm), n * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && pred_out && n) e = hipMemcpyAsync(pred_out, path_pred(rm), n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  }
+  hipError_t es = hipStreamSynchronize(st);
+  if (rc != CCMP_OK) return rc;
+  HIP_TRY(e);
+  HIP_TRY(es);
+  for (size_t f = 0; f < F && e == hipSuccess; f++) { // a path that fitted: its entries alone (a longer one leaves the caller's arrays as they were)
+    const size_t len = path_len[f] > 0 && path_len[f] <= max_len ? (size_t)path_len[f] : 0;
+    if (!len) continue;
+    e = hipMemcpyAsync(path + f * L, sg.at(off_p + f * L * sizeof(int32_t)), len * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && path_joints) e = hipMemcpyAsync(path_joints + f * L * 14, sg.at(off_j + f * L * 14 * sizeof(double)), len * 14 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && path_poses) e = hipMemcpyAsync(path_poses + f * L * 8, sg.at(off_o + f * L * 8 * sizeof(double)), len * 8 * sizeof(double), hipMemcpyDeviceToHost, st);
+  }
+  es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_graph_shortest_paths_ref(const int32_t *uv, const double *w, size_t E, size_t N, const int32_t *src, const int32_t *dst, size_t F, int max_len,
+                                  double *cost, int32_t *path_len, int32_t *path, double *dist_out, int32_t *pred_out)
+{
+  if (F == 0) return CCMP_OK;
+  { const int rc = path_checks(src, dst, F, max_len, cost, path_len, path); if (rc != CCMP_OK) return rc; }
+  if (N > kMaxNodes || E > kMaxNodes || (E > 0 && (!uv || !w))) return CCMP_EINVAL;
+  for (size_t e = 0; e < E; e++) // what ccmp_roadmap_add_edges_host refuses
+    if (uv[2 * e] < 0 || (size_t)uv[2 * e] >= N || uv[2 * e + 1] < 0 || (size_t)uv[2 * e + 1] >= N || uv[2 * e] == uv[2 * e + 1]) return CCMP_EINVAL;
+  for (size_t f = 0; f < F; f++)
+    if (src[f] < 0 || (size_t)src[f] >= N || dst[f] < 0 || (size_t)dst[f] >= N) return CCMP_EINVAL;
+  try {
+    // the adjacency: the half-edges of vertex v are adj[first[v] .. first[v + 1])
+    std::vector<size_t> first(N + 1, 0);
+    for (size_t e = 0; e < E; e++) { first[(size_t)uv[2 * e] + 1]++; first[(size_t)uv[2 * e + 1] + 1]++; }
+    for (size_t v = 0; v < N; v++) first[v + 1] += first[v];
+    std::vector<std::pair<int32_t, double>> adj(2 * E);
+    {
+      std::vector<size_t> at(first.begin(), first.end() - 1);
+      for (size_t e = 0; e < E; e++) {
+        adj[at[(size_t)uv[2 * e]]++] = {uv[2 * e + 1], w[e]};
+        adj[at[(size_t)uv[2 * e + 1]]++] = {uv[2 * e], w[e]};
+      }
+    }
+    std::vector<double> d(N);
+    std::vector<int32_t> hops(N), pred(N), level, next;
+    using Item = std::pair<double, int32_t>;
+    for (size_t f = 0; f < F; f++) {
+      const int32_t s = src[f], t = dst[f];
+      // distances: heap Dijkstra with lazy deletion
+      std::fill(d.begin(), d.end(), __builtin_inf());
+      std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
+      d[(size_t)s] = 0.0;
+      heap.push({0.0, s});
+      while (!heap.empty()) {
+        const Item top = heap.top();
+        heap.pop();
+        const size_t u = (size_t)top.second;
+        if (top.first != d[u]) continue;
+        for (size_t h = first[u]; h < first[u + 1]; h++) {
+          double c;
+          const size_t v = (size_t)adj[h].first;
+          if (ccmp::path_candidate(d[u], adj[h].second, &c) && c < d[v]) { d[v] = c; heap.push({c, (int32_t)v}); }
+        }
+      }
+      // hops: breadth first over the tight edges
+      std::fill(hops.begin(), hops.end(), ccmp::kPathNoHops);
+      std::fill(pred.begin(), pred.end(), -1);
+      hops[(size_t)s] = 0;
+      level.assign(1, s);
+      for (int32_t r = 1; !level.empty(); r++) {
+        next.clear();
+        for (const int32_t u : level)
+          for (size_t h = first[(size_t)u]; h < first[(size_t)u + 1]; h++) {
+            const size_t v = (size_t)adj[h].first;
+            if (hops[v] == ccmp::kPathNoHops && ccmp::path_tight(d[(size_t)u], adj[h].second, d[v])) { hops[v] = r; next.push_back((int32_t)v); }
+          }
+        level.swap(next);
+      }
+      // predecessors: the smallest tree candidate
+      for (size_t v = 0; v < N; v++)
+        for (size_t h = first[v]; h < first[v + 1]; h++) {
+          const int32_t u = adj[h].first;
+          if (ccmp::path_parent(d[(size_t)u], hops[(size_t)u], adj[h].second, d[v], hops[v]) && (pred[v] < 0 || u < pred[v])) pred[v] = u;
+        }
+      cost[f] = d[(size_t)t];
+      const int32_t len = hops[(size_t)t] == ccmp::kPathNoHops ? 0 : hops[(size_t)t] + 1;
+      path_len[f] = len;
+      if (len <= max_len) {
+        int32_t v = t;
+        for (int32_t i = len - 1; i >= 0 && v >= 0; i--) { path[f * (size_t)max_len + (size_t)i] = v; v = pred[(size_t)v]; }
+      }
+      if (dist_out) memcpy(dist_out + f * N, d.data(), N * sizeof(double));
+      if (pred_out) memcpy(pred_out + f * N, pred.data(), N * sizeof(int32_t));
+    }
+  } catch (const std::bad_alloc &) {
+    return CCMP_ENOMEM;
+  }
   return CCMP_OK;
 }
 

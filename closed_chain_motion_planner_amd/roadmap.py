@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import COMMIT_KEEP_ISOLATED, GROW_GREACHED, GROW_SREACHED, GROW_TRAPPED, GROW_UNSETTLED, METRIC_JOINT, METRIC_OBJECT, check
 from .constraint import _stream_handle, _torch
 
-__all__ = ["Roadmap", "pose_distance", "pose_from_t_wo", "joint_distance", "graph_labels_ref", "commit_ref", "closest_ref", "METRIC_JOINT", "METRIC_OBJECT",
+__all__ = ["Roadmap", "pose_distance", "pose_from_t_wo", "joint_distance", "graph_labels_ref", "commit_ref", "closest_ref", "shortest_paths_ref", "METRIC_JOINT", "METRIC_OBJECT",
            "GROW_TRAPPED", "GROW_SREACHED", "GROW_GREACHED", "GROW_UNSETTLED", "COMMIT_KEEP_ISOLATED"]
 
 _dp = C.POINTER(C.c_double)
@@ -130,6 +130,24 @@ def closest_ref(store_poses, labels, froms, target_pose):
     check(_lib.lib().ccmp_roadmap_closest_ref(_ptr(sp, _dp), _ptr(lab, _i32p), len(sp), _ptr(fr, _i32p), len(fr), _ptr(tgt, _dp), _ptr(idx, _i32p),
                                               _ptr(dist, _dp), _ptr(fd, _dp)), "ccmp_roadmap_closest_ref")
     return idx, dist, fd
+
+
+def shortest_paths_ref(uv, w, n, src, dst, max_len=None, full=False):
+    """ccmp_graph_shortest_paths_ref: `Roadmap.shortest_paths`' rule (csrc/ccmp_path.h) on host arrays without a device — edges uv (E,2),
+    weights w (E,) over n vertices, pairs src (F,), dst (F,), F <= 64.  Distances by heap Dijkstra, hops and predecessors from the rule
+    text the kernels compile.  Returns (cost (F,), path_len (F,), paths: a list of F int32 arrays; a path longer than max_len, when
+    one is given, is None); full=True adds dist (F,n) and pred (F,n)."""
+    uv, w = _np(uv, np.int32).reshape(-1, 2), _np(w, np.float64, -1)
+    sr, ds = _np(src, np.int32, -1), _np(dst, np.int32, -1)
+    F, n = len(sr), int(n)
+    L = int(max_len) if max_len is not None else max(n, 1)
+    cost, plen, path = np.empty(F), np.empty(F, dtype=np.int32), np.full((F, L), -1, dtype=np.int32)
+    dist = np.empty((F, n)) if full else None
+    pred = np.empty((F, n), dtype=np.int32) if full else None
+    check(_lib.lib().ccmp_graph_shortest_paths_ref(_ptr(uv, _i32p), _ptr(w, _dp), len(uv), n, _ptr(sr, _i32p), _ptr(ds, _i32p), F, L, _ptr(cost, _dp),
+                                                   _ptr(plen, _i32p), _ptr(path, _i32p), _ptr(dist, _dp), _ptr(pred, _i32p)), "ccmp_graph_shortest_paths_ref")
+    paths = [path[f, :plen[f]].copy() if plen[f] <= L else None for f in range(F)]
+    return (cost, plen, paths, dist, pred) if full else (cost, plen, paths)
 
 
 class Roadmap:
@@ -379,8 +397,8 @@ class Roadmap:
         return int(_lib.lib().ccmp_roadmap_num_edges(self._h))
 
     def edges(self, first=0, count=None, host=False, stream=None):
-        """(uv (count,2) int32, w (count,) float64) of the edges first ... in insertion order — what a graph library needs for the path
-        search; device tensors, or numpy arrays with host=True"""
+        """(uv (count,2) int32, w (count,) float64) of the edges first ... in insertion order (the path search itself is `shortest_paths`);
+        device tensors, or numpy arrays with host=True"""
         count = self.num_edges - int(first) if count is None else int(count)
         if host:
             uv, w = np.empty((count, 2), dtype=np.int32), np.empty(count)
@@ -449,6 +467,109 @@ class Roadmap:
             if i >= 0 and d < val:
                 closest, val = int(i), float(d)
         return closest, val
+
+    # ---- shortest paths: the planner's solution step (include/ccmp.h; csrc/ccmp_path.h) ------------------------------------------------
+    def shortest_paths(self, src, dst, max_len=64, host=False, stream=None, full=False):
+        """The cheapest path of every pair (src[f], dst[f]), F <= 64, on the store's graph, on the device (ccmp_roadmap_shortest_paths):
+        distances are the least fixed point of d[v] = min fl(d[u] + w), ties go to the fewest hops and then to the smallest predecessor
+        (csrc/ccmp_path.h) — the cheapest path, not boost's A* under the reference's inadmissible heuristic.  Returns a dict: cost (F,)
+        (+inf: not connected), path_len (F,) (0: not connected), path (F,L) int32 and joints (F,L,14), poses (F,L,8) (the first path_len[f]
+        rows of f are the path, start first), L = the buffer's length: max_len, or the longest path when one did not fit — the call is
+        then made once more with that length.  Device tensors (src / dst may be given as such: int32, on the device), or numpy arrays
+        with host=True (the synchronous host form; an index outside the store raises).  full=True adds dist (F,N) and pred (F,N)."""
+        L = _lib.lib()
+        N = len(self)
+        if host:
+            sr, ds = _np(src.cpu() if hasattr(src, "cpu") else src, np.int32, -1), _np(dst.cpu() if hasattr(dst, "cpu") else dst, np.int32, -1)
+            F = len(sr)
+            for ml in (int(max_len), None):
+                if ml is None:
+                    ml = int(out["path_len"].max())
+                out = {"cost": np.empty(F), "path_len": np.empty(F, dtype=np.int32), "path": np.full((F, ml), -1, dtype=np.int32),
+                       "joints": np.full((F, ml, 14), np.nan), "poses": np.full((F, ml, 8), np.nan)}
+                if full:
+                    out.update(dist=np.empty((F, N)), pred=np.empty((F, N), dtype=np.int32))
+                check(L.ccmp_roadmap_shortest_paths_host(self._h, _ptr(sr, _i32p), _ptr(ds, _i32p), F, ml, _ptr(out["cost"], _dp), _ptr(out["path_len"], _i32p),
+                                                         _ptr(out["path"], _i32p), _ptr(out["joints"], _dp), _ptr(out["poses"], _dp), _ptr(out.get("dist"), _dp),
+                                                         _ptr(out.get("pred"), _i32p)), "ccmp_roadmap_shortest_paths_host")
+                if F == 0 or int(out["path_len"].max()) <= ml:
+                    break
+            return out
+        torch = _torch()
+        dev = torch.device("cuda", self.ctx.device)
+
+        def pairs(a):
+            if isinstance(a, torch.Tensor):
+                if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous() or not a.is_cuda:
+                    raise ValueError("expected a contiguous (F,) int32 tensor on the device")
+                return a
+            return torch.from_numpy(np.array(a, dtype=np.int32).reshape(-1)).to(dev)
+
+        sr, ds = pairs(src), pairs(dst)
+        F = sr.shape[0]
+        if ds.shape[0] != F:
+            raise ValueError("src and dst are (F,) each")
+        for ml in (int(max_len), None):
+            if ml is None:
+                ml = longest
+            out = {"cost": torch.empty(F, dtype=torch.float64, device=dev), "path_len": torch.empty(F, dtype=torch.int32, device=dev),
+                   "path": torch.full((F, ml), -1, dtype=torch.int32, device=dev), "joints": torch.full((F, ml, 14), float("nan"), dtype=torch.float64, device=dev),
+                   "poses": torch.full((F, ml, 8), float("nan"), dtype=torch.float64, device=dev)}
+            if full:
+                out.update(dist=torch.empty((F, N), dtype=torch.float64, device=dev), pred=torch.empty((F, N), dtype=torch.int32, device=dev))
+            check(L.ccmp_roadmap_shortest_paths(self._h, sr.data_ptr(), ds.data_ptr(), F, ml, out["cost"].data_ptr(), out["path_len"].data_ptr(),
+                                                out["path"].data_ptr(), out["joints"].data_ptr(), out["poses"].data_ptr(),
+                                                out["dist"].data_ptr() if full else None, out["pred"].data_ptr() if full else None, _stream_handle(stream)),
+                  "ccmp_roadmap_shortest_paths")
+            longest = int(out["path_len"].max()) if F else 0  # the one host read: did every path fit
+            if longest <= ml:
+                break
+        return out
+
+    def path_rounds(self, F):
+        """(F,2) int32: the relaxation and hop rounds the last `shortest_paths` call took for each of its first F pairs; a diagnostic"""
+        r = np.empty((int(F), 2), dtype=np.int32)
+        check(_lib.lib().ccmp_roadmap_path_rounds_host(self._h, int(F), _ptr(r, _i32p)), "ccmp_roadmap_path_rounds_host")
+        return r
+
+    def solution(self, starts, goals, max_len=64):
+        """maybeConstructSolution (stefanBiPRM.cpp:480-603) on the device: of the pairs (start, goal) whose component labels agree, the
+        cheapest path — one `shortest_paths` call for those pairs (at most 64 of them), the first pair in starts-major order wins a
+        tie.  Returns (cost, indices (len,) int32 numpy, joints (len,14) device tensor), or None when no pair is connected.  The joint
+        rows are what `discrete_geodesic_batch` takes to densify the path (PathGeometric::interpolate)."""
+        starts, goals = [int(s) for s in starts], [int(g) for g in goals]
+        if not starts or not goals:
+            return None
+        lab = self.labels(host=True)
+        pairs = [(s, g) for s in starts for g in goals if lab[s] == lab[g]]
+        if not pairs:
+            return None
+        if len(pairs) > _lib.PATH_MAX_PAIRS:
+            raise ValueError("more than %d connected (start, goal) pairs" % _lib.PATH_MAX_PAIRS)
+        out = self.shortest_paths(np.array([p[0] for p in pairs], dtype=np.int32), np.array([p[1] for p in pairs], dtype=np.int32), max_len=max_len)
+        cost = out["cost"].cpu().numpy()
+        if not np.isfinite(cost).any():  # connected only through edges that cannot be traversed (a pose-only endpoint)
+            return None
+        f = int(np.argmin(np.where(np.isfinite(cost), cost, np.inf)))  # argmin: the first of equal costs
+        n = int(out["path_len"][f])
+        return float(cost[f]), out["path"][f, :n].cpu().numpy(), out["joints"][f, :n].contiguous()
+
+    def approximate_solution(self, starts, goal_pose, max_len=64):
+        """constructApproximateSolution (stefanBiPRM.cpp:161-239) on the device: `closest` gives, per start, the vertex of its component
+        nearest to goal_pose; the path goes from the start whose vertex is nearest (the first start wins a tie) to that vertex.
+        Returns (distance to the goal pose, cost, indices (len,) int32 numpy, joints (len,14) device tensor), or None without starts."""
+        starts = [int(s) for s in starts]
+        if not starts:
+            return None
+        tgt = np.zeros(8)
+        tgt[:7] = np.asarray(goal_pose.cpu() if hasattr(goal_pose, "cpu") else goal_pose, dtype=np.float64).reshape(-1)[:7]
+        idx, dist, _ = self.closest(np.array(starts, dtype=np.int32), tgt)
+        if not (idx >= 0).any():
+            return None
+        i = int(np.argmin(np.where(idx >= 0, dist, np.inf)))
+        out = self.shortest_paths(np.array([starts[i]], dtype=np.int32), np.array([idx[i]], dtype=np.int32), max_len=max_len)
+        n = int(out["path_len"][0])
+        return float(dist[i]), float(out["cost"][0]), out["path"][0, :n].cpu().numpy(), out["joints"][0, :n].contiguous()
 
     def close(self):
         if self._h:

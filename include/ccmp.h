@@ -819,8 +819,8 @@ int ccmp_object_propose_ref(const double *tri, int M, const ccmp_box *boxes, int
  *               u == v, as add_edges_host.
  *   ccmp_joint_distance     the edge weight of two joint states; pure host code beside ccmp_pose_distance.
  * Conventions as the store's other entries: every check runs before the first launch; a NULL store answers CCMP_ENODEV without a device
- * and CCMP_EINVAL with one; zero counts return CCMP_OK and touch nothing.  The path search itself (A*) stays with the caller's graph
- * library: read_edges hands it the graph. */
+ * and CCMP_EINVAL with one; zero counts return CCMP_OK and touch nothing.  The path search runs on the device too (the next section);
+ * read_edges remains for callers that want the graph itself. */
 #define CCMP_GRAPH_MAX_ROOTS 32
 #define CCMP_CLOSEST_MAX_FROM 64
 enum { CCMP_GROW_TRAPPED = 0, CCMP_GROW_SREACHED = 1, CCMP_GROW_GREACHED = 2, CCMP_GROW_UNSETTLED = 3 };
@@ -853,6 +853,51 @@ int ccmp_roadmap_closest_host(ccmp_roadmap *rm, const int32_t *from_idx, size_t 
                               double *from_dist);
 int ccmp_roadmap_closest_ref(const double *store_poses, const int32_t *labels, size_t N, const int32_t *from_idx, size_t F, const double *target_pose,
                              int32_t *idx, double *dist, double *from_dist);
+
+/* ---- shortest paths on the store's graph: the planner's solution step ------------------------------------------------------------ */
+/* constructSolution, maybeConstructSolution and constructApproximateSolution (stefanBiPRM.cpp:161-239, :480-603) need the cheapest path
+ * from a start vertex to a goal vertex as joint states.  One call answers 1 <= F <= CCMP_PATH_MAX_PAIRS pairs (src[f], dst[f]) on the
+ * store's graph as it stands (undirected edges, the stored weights, parallel edges allowed) without taking it off the device.  The rule
+ * (csrc/ccmp_path.h states it once, for the kernels and for the _ref form; fl(a + b) is one IEEE double addition), for one source s:
+ *     candidate   over an edge {u, v} from u: c = fl(d[u] + w); it passes iff d[u] is finite, w >= 0 and c is finite — a NaN never passes
+ *                 (an edge at a pose-only vertex has a NaN weight and is never traversed), nor does a sum that overflowed
+ *     distance    d = the least fixed point of d[s] = +0.0, d[v] = min over the passing candidates into v; unreached: +inf.  The fixed
+ *                 point is unique (fl(a + w) is non-decreasing in a and >= a), so the result is a function of the edge set alone, bit
+ *                 for bit: Dijkstra, Bellman-Ford in any order and atomicMin arriving in any order reach the same values, with zero
+ *                 weights and absorbed weights (fl(d + w) == d) included
+ *     tight edge  u -> v: the candidate from u passes and equals d[v]
+ *     hops        hops[v] = the breadth-first level of v from s in the directed graph of tight edges
+ *     pred        pred[v] = the smallest u with a tight edge u -> v and hops[u] == hops[v] - 1 (-1 for s and for an unreached vertex):
+ *                 acyclic by construction, where a rule on distances or indices would not be
+ *     path        s -> t has hops[t] + 1 vertices (the walk of pred from t, written forwards); its cost d[t] is the left-to-right fl sum
+ *                 of its weights.  s == t: length 1, cost +0.0.  t unreached: length 0, cost +inf.
+ * THIS IS NOT boost's A*: the reference guides its search by the SE3 object distance (costHeuristic) while its weights are joint
+ * distances; that heuristic is not admissible for these weights, so the reference's path need not be the cheapest.  This one is (its
+ * cost is never above the reference's), and ties are broken by the rule above, not by heap order.
+ *   shortest_paths   device pointers: src [F], dst [F]; outputs cost [F], path_len [F], path [F][max_len] (int32, the first path_len[f]
+ *                    entries of row f), and, each nullable, path_joints [F][max_len][14], path_poses [F][max_len][8] (the store's rows at
+ *                    those indices), dist_out [F][N] and pred_out [F][N] (N = the store's size).  A path longer than max_len reports its
+ *                    length and leaves row f of path and of the rows untouched: call again with more room.  A src or dst outside
+ *                    [0, size): length 0, cost NaN.  The per-pair arrays live in a workspace on the handle, grown before the first
+ *                    launch (F N 20 bytes), allocated only when this call is used and freed with the store.  N and the edge count are
+ *                    host state: the call is asynchronous on its stream, and capturable once the workspace holds F N (the first call
+ *                    at a size grows it: never capture that one).
+ *   _host            host pointers, synchronous on the context's stream; a src or dst outside [0, size) is CCMP_EINVAL, checked on the host.
+ *   ccmp_graph_shortest_paths_ref   pure host code on uv [E][2], w [E] over N vertices, one thread, no device, never CCMP_ENODEV: distances
+ *                    by HEAP DIJKSTRA (another algorithm than the kernel's rounds), hops and predecessors from the same rule text.
+ *                    CCMP_EINVAL for an endpoint outside [0, N) or u == v (as add_edges_host) and for a src or dst outside [0, N).
+ *   path_rounds_host   the relaxation and hop rounds ([F][2]) the store's last shortest_paths call took per pair; a diagnostic.
+ * Conventions as above: every check runs before the first launch; a NULL store answers CCMP_ENODEV without a device and CCMP_EINVAL
+ * with one; F == 0 returns CCMP_OK and touches nothing; F > CCMP_PATH_MAX_PAIRS, max_len < 1 or a NULL src, dst, cost, path_len or path
+ * is CCMP_EINVAL.  What remains with the caller is PathGeometric::interpolate, itself ccmp_geodesic_batch over the returned rows. */
+#define CCMP_PATH_MAX_PAIRS 64
+int ccmp_roadmap_shortest_paths(ccmp_roadmap *rm, const int32_t *src, const int32_t *dst, size_t F, int max_len, double *cost, int32_t *path_len,
+                                int32_t *path, double *path_joints, double *path_poses, double *dist_out, int32_t *pred_out, void *hip_stream);
+int ccmp_roadmap_shortest_paths_host(ccmp_roadmap *rm, const int32_t *src, const int32_t *dst, size_t F, int max_len, double *cost, int32_t *path_len,
+                                     int32_t *path, double *path_joints, double *path_poses, double *dist_out, int32_t *pred_out);
+int ccmp_graph_shortest_paths_ref(const int32_t *uv, const double *w, size_t E, size_t N, const int32_t *src, const int32_t *dst, size_t F, int max_len,
+                                  double *cost, int32_t *path_len, int32_t *path, double *dist_out, int32_t *pred_out);
+int ccmp_roadmap_path_rounds_host(ccmp_roadmap *rm, size_t F, int32_t *rounds);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

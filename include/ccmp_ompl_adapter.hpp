@@ -26,6 +26,7 @@
 #define CCMP_OMPL_ADAPTER_HPP
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdint>
@@ -661,6 +662,91 @@ public:
                           "ccmp_roadmap_closest_host");
     if (ran && from_dist) from_dist->swap(fd);
     return ran;
+  }
+  // ---- the solution step (include/ccmp.h: ccmp_roadmap_shortest_paths) ----------------------------------------------------------------
+  // The cheapest path src -> dst on the store's graph, on the device: path = its vertex indices, start first, cost = the sum of its
+  // weights (ties: the fewest hops, then the smallest predecessor — csrc/ccmp_path.h; not boost's A*, whose heuristic here is not
+  // admissible).  states (nullable) = the joint rows of those vertices.  false with an empty path and cost +inf when dst cannot be
+  // reached OR the call failed (the error in lastError()).
+  bool shortestPath(int32_t src, int32_t dst, std::vector<int32_t> &path, double &cost, std::vector<std::array<double, 14>> *states = nullptr) const noexcept
+  {
+    cost = std::numeric_limits<double>::infinity();
+    path.clear();
+    if (states) states->clear();
+    int32_t len = 0;
+    double c = cost;
+    std::vector<double> rows;
+    try {
+      for (int room = 64, tries = 0; tries < 2; tries++) { // a path that did not fit reports its length: once more with that room
+        path.assign((size_t)room, -1);
+        rows.assign(states ? (size_t)room * 14 : 0, 0.0);
+        const bool ran = call([&] { return ccmp_roadmap_shortest_paths_host(rm_, &src, &dst, 1, room, &c, &len, path.data(), states ? rows.data() : nullptr, nullptr, nullptr, nullptr); },
+                              "ccmp_roadmap_shortest_paths_host");
+        if (!ran) { path.clear(); return false; }
+        if (len <= room) break;
+        room = len;
+      }
+      path.resize((size_t)len);
+      if (states) {
+        states->resize((size_t)len);
+        for (size_t i = 0; i < (size_t)len; i++) std::memcpy((*states)[i].data(), rows.data() + i * 14, 14 * sizeof(double));
+      }
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::shortestPath");
+      path.clear();
+      return false;
+    }
+    cost = c;
+    return len > 0;
+  }
+  // maybeConstructSolution (stefanBiPRM.cpp:480-603): of the pairs (start, goal) in one component, the cheapest path's joint states, start
+  // first — what PathGeometric::append takes, and discreteGeodesicBatch over consecutive rows is PathGeometric::interpolate.  The first
+  // pair in starts-major order wins a tie.  false with no states when no pair is connected (at most CCMP_PATH_MAX_PAIRS connected pairs are
+  // considered) OR a call failed (lastError()).  cost / indices (nullable) = the path's cost and vertices.
+  bool constructSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states, double *cost = nullptr,
+                         std::vector<int32_t> *indices = nullptr) const noexcept
+  {
+    states.clear();
+    if (indices) indices->clear();
+    if (cost) *cost = std::numeric_limits<double>::infinity();
+    try {
+      const size_t N = size();
+      std::vector<int32_t> lab(N), src, dst;
+      if (N == 0 || !readLabels(0, N, lab.data())) return false;
+      for (int32_t s : starts)
+        for (int32_t g : goals)
+          if (s >= 0 && g >= 0 && (size_t)s < N && (size_t)g < N && lab[(size_t)s] == lab[(size_t)g] && src.size() < (size_t)CCMP_PATH_MAX_PAIRS) {
+            src.push_back(s);
+            dst.push_back(g);
+          }
+      const size_t F = src.size();
+      if (F == 0) return false;
+      std::vector<double> c(F), rows;
+      std::vector<int32_t> len(F), path;
+      int room = 64;
+      for (int tries = 0; tries < 2; tries++) {
+        path.assign(F * (size_t)room, -1);
+        rows.assign(F * (size_t)room * 14, 0.0);
+        if (!call([&] { return ccmp_roadmap_shortest_paths_host(rm_, src.data(), dst.data(), F, room, c.data(), len.data(), path.data(), rows.data(), nullptr, nullptr, nullptr); },
+                  "ccmp_roadmap_shortest_paths_host")) return false;
+        const int longest = *std::max_element(len.begin(), len.end());
+        if (longest <= room) break;
+        room = longest;
+      }
+      size_t best = F;
+      for (size_t f = 0; f < F; f++)
+        if (len[f] > 0 && (best == F || c[f] < c[best])) best = f;
+      if (best == F) return false;
+      states.resize((size_t)len[best]);
+      for (size_t i = 0; i < states.size(); i++) std::memcpy(states[i].data(), rows.data() + (best * (size_t)room + i) * 14, 14 * sizeof(double));
+      if (indices) indices->assign(path.begin() + (std::ptrdiff_t)(best * (size_t)room), path.begin() + (std::ptrdiff_t)(best * (size_t)room + states.size()));
+      if (cost) *cost = c[best];
+      return true;
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::constructSolution");
+      states.clear();
+      return false;
+    }
   }
 
   int lastError() const noexcept { return err_code_; }

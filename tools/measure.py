@@ -31,6 +31,10 @@
     python tools/measure.py graph [reps]                    the roadmap graph (growTree's tail, closestFromGoal's scan, labels): (a) commit with Q = 1, k = 5, lists of 64
                                                            through the host form, (b) Q = 4096 through the device form, (c) closest and (d) a one-edge label update at
                                                            N = 65 536, each against the *_ref form on one thread on the same inputs; writes profiles/roadmap_graph.md
+    python tools/measure.py path [reps]                     shortest paths on the device roadmap (the solution step): N = 65 536 with ~65 000 edges and N = 2 000 with 5 000,
+                                                           F = 1 and F = 64, the device form (events) and the host form (wall clock) against ccmp_graph_shortest_paths_ref on
+                                                           one thread, the rounds each phase took, and the full round trip (read_edges_host + _ref + re-upload of the rows
+                                                           against shortest_paths with the rows left on the device); writes profiles/roadmap_path.md
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -1056,6 +1060,90 @@ def graph(argv):
                 "same inputs, the outputs compared while they are timed.  No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
 
 
+def path(argv):
+    """ccmp_roadmap_shortest_paths (device form: events; host form: wall clock) against ccmp_graph_shortest_paths_ref (heap Dijkstra, one
+    host thread) on the same inputs; outputs compared while they are timed.  Writes profiles/roadmap_path.md."""
+    import os
+
+    from closed_chain_motion_planner_amd import Roadmap, shortest_paths_ref
+
+    reps = int(argv[0]) if len(argv) > 0 else 15
+    ctx = Context(0)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    lines = []
+
+    def say(text):
+        print(text)
+        lines.append(text)
+
+    def same(a, b):
+        return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+    for N, E in ((65536, 65536), (2000, 5000)):
+        rng = np.random.default_rng(0x9A7 + N)
+        joints = rng.uniform(-2.8, 2.8, (N, 14))
+        poses = np.zeros((N, 8))
+        poses[:, :3] = joints[:, :3]
+        poses[:, 6] = 1.0
+        uv = rng.integers(0, N, size=(E, 2)).astype(np.int32)
+        uv = np.ascontiguousarray(uv[uv[:, 0] != uv[:, 1]])
+        rm = Roadmap(c, capacity_hint=N + 64)
+        rm.append(torch.from_numpy(joints).cuda(), torch.from_numpy(poses).cuda())
+        rm.add_edges(torch.from_numpy(uv).cuda())
+        lab = rm.labels(host=True)
+        comp = np.flatnonzero(lab == np.bincount(lab).argmax())  # the largest component
+        _, w = rm.edges(host=True)
+        for F in (1, 64):
+            pick = rng.choice(comp, size=(F, 2))
+            src, dst = np.ascontiguousarray(pick[:, 0].astype(np.int32)), np.ascontiguousarray(pick[:, 1].astype(np.int32))
+            src_d, dst_d = torch.from_numpy(src).cuda(), torch.from_numpy(dst).cuda()
+            ref = shortest_paths_ref(uv, w, N, src, dst)
+            L = int(ref[1].max())
+            t = {"ccmp_roadmap_shortest_paths (device, events)": [], "ccmp_roadmap_shortest_paths_host (wall clock)": [],
+                 "ccmp_graph_shortest_paths_ref (one thread)": [], "round trip on the host: read_edges_host + _ref + rows re-uploaded": [],
+                 "round trip on the device: shortest_paths, rows stay": []}
+            agree = True
+            for i in range(reps + 3):
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                e[0].record()
+                dev = rm.shortest_paths(src_d, dst_d, max_len=L)
+                e[1].record()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                host = rm.shortest_paths(src, dst, max_len=L, host=True)
+                t1 = time.perf_counter()
+                ref = shortest_paths_ref(uv, w, N, src, dst)
+                t2 = time.perf_counter()
+                # the full round trip, as a caller without this call has it: the edge list down, the search, the chosen rows up again
+                uv_h, w_h = rm.edges(host=True)
+                r2 = shortest_paths_ref(uv_h, w_h, N, src, dst)
+                rows = [torch.from_numpy(joints[p]).cuda() for p in r2[2]]
+                torch.cuda.synchronize()
+                t3 = time.perf_counter()
+                d2 = rm.shortest_paths(src_d, dst_d, max_len=L)
+                torch.cuda.synchronize()
+                t4 = time.perf_counter()
+                dl, dp = dev["path_len"].cpu().numpy(), dev["path"].cpu().numpy()
+                agree = agree and same(dev["cost"].cpu().numpy(), ref[0]) and same(host["cost"], ref[0]) and np.array_equal(dl, ref[1]) and np.array_equal(host["path_len"], ref[1])
+                agree = agree and all(np.array_equal(dp[f, :dl[f]], ref[2][f]) and np.array_equal(host["path"][f, :dl[f]], ref[2][f]) for f in range(F))
+                agree = agree and all(same(d2["joints"][f, :dl[f]].cpu().numpy(), rows[f].cpu().numpy()) for f in range(F))
+                if i >= 3:
+                    for name, ms in zip(t, (e[0].elapsed_time(e[1]), (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3)):
+                        t[name].append(ms)
+            rounds = rm.path_rounds(F)
+            say("N = %d, %d edges, F = %d (largest component: %d vertices; longest path %d vertices); outputs identical: %s" % (N, len(uv), F, len(comp), L, agree))
+            say("    rounds per pair: relaxation %d .. %d (median %d), hops %d .. %d (median %d)"
+                % (rounds[:, 0].min(), rounds[:, 0].max(), int(np.median(rounds[:, 0])), rounds[:, 1].min(), rounds[:, 1].max(), int(np.median(rounds[:, 1]))))
+            for name, ms in t.items():
+                say("    %-68s %s" % (name, _stat(ms)))
+        rm.close()
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "roadmap_path.md"), "w") as f:
+        f.write("# Shortest paths on the device roadmap: `tools/measure.py path`\n\n1 x MI355X, one run; the device forms against `ccmp_graph_shortest_paths_ref` "
+                "(heap Dijkstra on one host thread) on the same inputs, the outputs compared while they are timed.  No speed threshold gates this feature.\n\n```\n"
+                + "\n".join(lines) + "\n```\n")
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -1126,7 +1214,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
