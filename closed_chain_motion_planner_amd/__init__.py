@@ -15,6 +15,8 @@ from .scene import ProxyScene, ProxyValidityChecker, default_allowed, skeleton_s
 
 from .roadmap import Roadmap, closest_ref, commit_ref, graph_labels_ref, joint_distance, pose_distance, pose_from_t_wo, shortest_paths_ref  # noqa: F401
 
+from .dense import DENSE_DISTINCT, dense_arc_ref, dense_layout_ref  # noqa: F401
+
 from .ik import ik_options, pose_ik_ref  # noqa: F401
 
 from .object import ObjectChecker, object_propose_ref, object_valid_ref, pose_interpolate  # noqa: F401

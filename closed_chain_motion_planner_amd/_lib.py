@@ -64,6 +64,11 @@ class CcmpBox(C.Structure):
     _fields_ = [("group", C.c_int32), ("reserved", C.c_int32), ("c", C.c_double * 3), ("R", C.c_double * 9), ("half", C.c_double * 3)]
 
 
+class CcmpDenseOpts(C.Structure):
+    """ccmp_dense_opts of include/ccmp.h"""
+    _fields_ = [("flags", C.c_int), ("chunk_states", C.c_int), ("round_budget", C.c_int), ("max_calls", C.c_int)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -90,6 +95,8 @@ EXPORTS = [
     "ccmp_roadmap_add_edges", "ccmp_roadmap_add_edges_host", "ccmp_roadmap_num_edges", "ccmp_roadmap_read_edges", "ccmp_roadmap_read_edges_host",
     "ccmp_roadmap_read_labels", "ccmp_roadmap_read_labels_host", "ccmp_roadmap_closest", "ccmp_roadmap_closest_host", "ccmp_roadmap_closest_ref",
     "ccmp_roadmap_shortest_paths", "ccmp_roadmap_shortest_paths_host", "ccmp_graph_shortest_paths_ref", "ccmp_roadmap_path_rounds_host",
+    "ccmp_dense_opts_default", "ccmp_path_densify", "ccmp_path_densify_host", "ccmp_dense_paths_info", "ccmp_dense_paths_copy", "ccmp_dense_paths_copy_host",
+    "ccmp_dense_paths_destroy", "ccmp_dense_layout_ref", "ccmp_dense_arc_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -257,6 +264,15 @@ def lib():
         "ccmp_roadmap_shortest_paths_host": ([vp, i32p, i32p, C.c_size_t, C.c_int, dp, i32p, i32p, dp, dp, dp, i32p], C.c_int),
         "ccmp_graph_shortest_paths_ref": ([i32p, dp, C.c_size_t, C.c_size_t, i32p, i32p, C.c_size_t, C.c_int, dp, i32p, i32p, dp, i32p], C.c_int),
         "ccmp_roadmap_path_rounds_host": ([vp, C.c_size_t, i32p], C.c_int),
+        "ccmp_dense_opts_default": ([C.POINTER(CcmpDenseOpts)], None),
+        "ccmp_path_densify": ([vp, pp, vp, C.c_double, vp, vp, C.c_size_t, C.c_int, C.POINTER(CcmpDenseOpts), C.POINTER(vp), vp], C.c_int),
+        "ccmp_path_densify_host": ([vp, pp, vp, C.c_double, dp, i32p, C.c_size_t, C.c_int, C.POINTER(CcmpDenseOpts), C.POINTER(vp)], C.c_int),
+        "ccmp_dense_paths_info": ([vp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)], C.c_int),
+        "ccmp_dense_paths_copy": ([vp] + [vp] * 11 + [vp], C.c_int),
+        "ccmp_dense_paths_copy_host": ([vp, dp, i32p, i32p, u8p, i32p, dp, dp, dp, dp, i32p, i32p], C.c_int),
+        "ccmp_dense_paths_destroy": ([vp], None),
+        "ccmp_dense_layout_ref": ([i32p, C.c_size_t, C.c_int, i32p, C.c_int, i32p, i32p, C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_dense_arc_ref": ([dp, i32p, C.c_size_t, dp, dp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -298,6 +314,7 @@ GROW_TRAPPED, GROW_SREACHED, GROW_GREACHED, GROW_UNSETTLED = range(4)  # ccmp.h:
 COMMIT_KEEP_ISOLATED = 1  # ccmp.h: CCMP_COMMIT_*
 GRAPH_MAX_ROOTS, CLOSEST_MAX_FROM = 32, 64  # ccmp.h: CCMP_GRAPH_MAX_ROOTS, CCMP_CLOSEST_MAX_FROM
 PATH_MAX_PAIRS = 64  # ccmp.h: CCMP_PATH_MAX_PAIRS
+DENSE_DISTINCT = 1  # ccmp.h: CCMP_DENSE_DISTINCT
 
 
 def option_table():

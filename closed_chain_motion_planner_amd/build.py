@@ -34,6 +34,9 @@ Translation units with deliberately different flags:
                          (hooking rounds in one block, then a compress launch) and closestFromGoal's vertex scan; ccmp_roadmap.cpp compiles the same header for the *_ref forms;
                          and the planner's solution step, shortest paths on that graph (ccmp_path.h: graph_path_*, relaxation and hop rounds in one block per pair)
   ccmp_object.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_object_*: checks, launches, and the same text on the host (the *_ref forms, same bits as the kernels)
+  ccmp_kernels_dense.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   dense solution paths (ccmp_dense.h): the endpoint gather of the continuation loop, the pack of the
+                         extend calls' chunks and the waypoint rows, the arc's serial chain (one block per path) and the segmented clearance reduction
+  ccmp_dense.cpp         -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_densify: checks, the continuation loop over ccmp_geodesic_batch_ex, the layout; ccmp_dense_*_ref on the host
 """
 import os
 import shutil
@@ -104,8 +107,12 @@ _UNITS = [
     ("ccmp_ik.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
     # ccmp_object_*: the checks and launches, and ccmp_object.h compiled for the host (the *_ref forms: the kernels' bits without a device)
     ("ccmp_object.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # dense solution paths (ccmp_dense.h): gather, pack, arc and the clearance summary; the k-NN unit's flags; registers and LDS only
+    ("ccmp_kernels_dense.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # ccmp_path_densify: the checks, the continuation loop and the layout rule on the host (ccmp_dense_layout_ref, ccmp_dense_arc_ref)
+    ("ccmp_dense.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -150,6 +157,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"ik_", 0),  # pose-targeted IK: the 6x6 system, the kept sines and cosines and the iterate live in registers, both instantiations
     (r"object_", 0),  # the head of growTree: a lane's triangle, the pose's frame and one box at a time live in registers, every kernel of the unit
     (r"graph_", 0),  # the roadmap graph: a slot's FK and distances, a lane's best candidate and the scan's sums live in registers and LDS, every kernel of the unit
+    (r"dense_", 0),  # dense solution paths: a chunk's descriptor, a lane's distance and a lane's best (value, row) live in registers and LDS, every kernel of the unit
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

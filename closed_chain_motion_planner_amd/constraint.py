@@ -519,6 +519,23 @@ class KinematicChainConstraint:
             raise RuntimeError("continue_geodesics: %d edges unfinished after %d calls (first: %s)" % (len(idx), max_calls, idx[:8]))
         return out
 
+    def densify_paths(self, path_joints, path_len, scene=None, margin=None, distinct=False, chunk_states=16, round_budget=128, max_calls=4096,
+                      stream=None):
+        """`PathGeometric::interpolate` for F solution paths (ccmp_path_densify; csrc/ccmp_dense.h): path_joints (F,max_len,14) and
+        path_len (F,) int32 as `Roadmap.shortest_paths` returns them ("joints", "path_len"), on the device.  Every segment is
+        traversed to its end inside the library, whatever chunk_states / round_budget cut it into; the state lists stay on the
+        device.  Rows per path: w_0, G_0, w_1, G_1, .., w_{L-1} (each w_i before the last twice in a row, as printAsMatrix writes
+        them), or with distinct=True G_0, G_1, .., w_{L-1}; G_i = the list of discreteGeodesic(w_i, w_{i+1}, interpolate = true).
+        Returns a dict of device tensors — joints (rows,14), path_first (F+1,), seg_first / seg_ok / seg_newton (F,max_len-1),
+        arc (rows,), length (F,) and, with a ProxyScene and its margin, clearance (rows,), min_clear / min_row / first_blocked (F,) —
+        plus rows and calls (the extend calls made).  numpy arrays go through the host form and come back as numpy arrays.
+        Synchronous.  max_calls spent with a segment open raises CcmpError (CCMP_EOVERFLOW): a cut list never looks complete."""
+        from .dense import densify
+
+        self._need_problem()
+        return densify(self.ctx, self.problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream, _torch(),
+                       _stream_handle)
+
     def ambient_uniform_batch(self, seed, first_index, B, stream=None):
         self._need_problem()
         torch = _torch()

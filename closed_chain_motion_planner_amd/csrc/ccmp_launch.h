@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; }
+namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -217,6 +217,17 @@ hipError_t graph_closest(const GraphStore &s, const int32_t *from_idx, size_t F,
                          double *ws_d, int32_t *ws_i, int32_t *idx, double *dist, double *from_dist, hipStream_t st);
 /* init -> rounds in one block per pair -> extract (cost, length, path, rows); s.N == 0: the extract alone */
 hipError_t graph_paths(const GraphStore &s, const GraphPath &p, hipStream_t st);
+/* dense solution paths (ccmp_path_densify; csrc/ccmp_dense.h).  Endpoint gather of one extend call's E open segments: from / to [E][14] and,
+ * for a continuation (prev_states, prev_carry given), carry_in [E][2]; waypoints = path_joints seen as rows [F * max_len][14] */
+hipError_t dense_gather(const ccmp::dense_open_seg *open, size_t E, const double *waypoints, const double *prev_states, int chunk_states,
+                        const double *prev_carry, double *from, double *to, double *carry_in, hipStream_t st);
+/* one wavefront per chunk: its rows to their final place (a chunk reaching beyond total_rows is skipped), its Newton count into seg_newton */
+hipError_t dense_pack(const ccmp::dense_chunk *chunks, size_t n, double *rows, size_t total_rows, int32_t *seg_newton, size_t slots, hipStream_t st);
+/* one block per path: the serial arc chain and the path's length */
+hipError_t dense_arc(const double *rows, const int32_t *path_first, size_t F, double *arc, double *length, hipStream_t st);
+/* one block per path: (min clearance, first row attaining it) and the first row below the margin */
+hipError_t dense_clearance_summary(const double *clearance, const int32_t *path_first, size_t F, double margin, double *min_clear, int32_t *min_row,
+                                   int32_t *first_blocked, hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

@@ -536,7 +536,7 @@ class Roadmap:
         """maybeConstructSolution (stefanBiPRM.cpp:480-603) on the device: of the pairs (start, goal) whose component labels agree, the
         cheapest path — one `shortest_paths` call for those pairs (at most 64 of them), the first pair in starts-major order wins a
         tie.  Returns (cost, indices (len,) int32 numpy, joints (len,14) device tensor), or None when no pair is connected.  The joint
-        rows are what `discrete_geodesic_batch` takes to densify the path (PathGeometric::interpolate)."""
+        rows are what `KinematicChainConstraint.densify_paths` takes to densify the path (PathGeometric::interpolate): `dense_solution`."""
         starts, goals = [int(s) for s in starts], [int(g) for g in goals]
         if not starts or not goals:
             return None
@@ -570,6 +570,30 @@ class Roadmap:
         out = self.shortest_paths(np.array([starts[i]], dtype=np.int32), np.array([idx[i]], dtype=np.int32), max_len=max_len)
         n = int(out["path_len"][0])
         return float(dist[i]), float(out["cost"][0]), out["path"][0, :n].cpu().numpy(), out["joints"][0, :n].contiguous()
+
+    @staticmethod
+    def _dense(constraint, joints, kw):
+        """one path's waypoint rows (len,14), on the device, through `KinematicChainConstraint.densify_paths`"""
+        torch = _torch()
+        n = joints.shape[0]
+        plen = torch.full((1,), n, dtype=torch.int32, device=joints.device)
+        return constraint.densify_paths(joints.reshape(1, n, 14).contiguous(), plen, **kw)
+
+    def dense_solution(self, constraint, starts, goals, max_len=64, **kw):
+        """`solution` followed by `constraint.densify_paths` on its joint rows (PathGeometric::interpolate): the path never leaves the
+        device between the two.  Returns (cost, indices, dense) with dense the dict of `densify_paths` (kw: its keyword arguments),
+        or None when no pair is connected.  `space.format_path_matrix(dense["joints"].cpu().numpy())` is the reference's <obj>_path.txt."""
+        sol = self.solution(starts, goals, max_len=max_len)
+        if sol is None:
+            return None
+        return sol[0], sol[1], self._dense(constraint, sol[2], kw)
+
+    def dense_approximate_solution(self, constraint, starts, goal_pose, max_len=64, **kw):
+        """`approximate_solution` followed by `constraint.densify_paths`: (distance to the goal pose, cost, indices, dense), or None"""
+        sol = self.approximate_solution(starts, goal_pose, max_len=max_len)
+        if sol is None:
+            return None
+        return sol[0], sol[1], sol[2], self._dense(constraint, sol[3], kw)
 
     def close(self):
         if self._h:

@@ -889,7 +889,7 @@ int ccmp_roadmap_closest_ref(const double *store_poses, const int32_t *labels, s
  *   path_rounds_host   the relaxation and hop rounds ([F][2]) the store's last shortest_paths call took per pair; a diagnostic.
  * Conventions as above: every check runs before the first launch; a NULL store answers CCMP_ENODEV without a device and CCMP_EINVAL
  * with one; F == 0 returns CCMP_OK and touches nothing; F > CCMP_PATH_MAX_PAIRS, max_len < 1 or a NULL src, dst, cost, path_len or path
- * is CCMP_EINVAL.  What remains with the caller is PathGeometric::interpolate, itself ccmp_geodesic_batch over the returned rows. */
+ * is CCMP_EINVAL.  The step behind it, PathGeometric::interpolate over the returned rows, is ccmp_path_densify below. */
 #define CCMP_PATH_MAX_PAIRS 64
 int ccmp_roadmap_shortest_paths(ccmp_roadmap *rm, const int32_t *src, const int32_t *dst, size_t F, int max_len, double *cost, int32_t *path_len,
                                 int32_t *path, double *path_joints, double *path_poses, double *dist_out, int32_t *pred_out, void *hip_stream);
@@ -898,6 +898,72 @@ int ccmp_roadmap_shortest_paths_host(ccmp_roadmap *rm, const int32_t *src, const
 int ccmp_graph_shortest_paths_ref(const int32_t *uv, const double *w, size_t E, size_t N, const int32_t *src, const int32_t *dst, size_t F, int max_len,
                                   double *cost, int32_t *path_len, int32_t *path, double *dist_out, int32_t *pred_out);
 int ccmp_roadmap_path_rounds_host(ccmp_roadmap *rm, size_t F, int32_t *rounds);
+
+/* ---- dense solution paths: PathGeometric::interpolate on the device --------------------------------------------------------------- */
+/* ConstrainedProblem::solveOnce (ConstrainedPlanningCommon.cpp:207-222) runs PathGeometric::interpolate on the planner's solution and
+ * prints the result as <obj>_path.txt.  One call takes F >= 0 paths as waypoint rows on the device — path_joints [F][max_len][14] and
+ * path_len [F], the shapes ccmp_roadmap_shortest_paths writes — and returns them dense; the state lists never leave the device.  The
+ * rule (csrc/ccmp_dense.h states it once, for the kernels and for the host forms); path f has L = path_len[f] waypoints w_0 .. w_{L-1}:
+ *     segment list   G_i = the state list of ONE uninterrupted discreteGeodesic(w_i, w_{i+1}, interpolate = true)
+ *                    (jy_ProjectedStateSpace.cpp:32-96): n_i >= 1 states, G_i[0] = w_i; seg_ok[i] its return value, seg_newton[i] its Newton
+ *                    total.  The library cuts a traversal into extend calls of chunk_states list entries and round_budget Newton rounds
+ *                    (ccmp_geodesic_batch_ex with carries) and continues every open segment until none is left: lists, flag and count
+ *                    are those of one traversal, bit for bit, whatever the cut.  The problem's Jacobian mode decides the arithmetic.
+ *     reference      flags = 0: w_0, G_0, w_1, G_1, .., w_{L-2}, G_{L-2}, w_{L-1} — sum (1 + n_i) + 1 rows, each w_i with i < L - 1 twice in a
+ *     layout         row, as PathGeometric::interpolate followed by printAsMatrix writes them.  L == 1: one row.  L == 0: none.
+ *     distinct       CCMP_DENSE_DISTINCT: G_0, G_1, .., G_{L-2}, w_{L-1} — sum n_i + 1 rows: the layout for executing the path.
+ *     unreached      a segment with seg_ok = 0 contributes the rows it has and the next waypoint follows: the path has a jump there, as
+ *                    the reference's own output has (Wine_Bottle_path.txt, segment 1).  Not an error.
+ *     offsets        paths are packed one after another: path_first [F + 1] (path_first[F] = the row count), seg_first [F][max_len - 1] =
+ *                    the first row of G_i, -1 for a slot without a segment (seg_ok and seg_newton are 0 there).
+ *     arc            arc[path_first[f]] = +0.0, arc[r] = fl(arc[r-1] + ccmp_joint_distance(row[r-1], row[r])) within a path; length[f] = the
+ *                    arc of the path's last row, +0.0 for an empty path.  A duplicated row adds exactly +0.0: both layouts carry the
+ *                    same arcs at corresponding rows.
+ *     clearance      only with a proxy scene: clearance[r] = ccmp_clearance_batch's value for row r; per path min_clear, min_row (the
+ *     summary        first row attaining it; rows are numbered over the whole result) and first_blocked (the first row with clearance <
+ *                    margin, -1: none).  A NaN never attains the minimum.  Empty path: +inf, -1, -1.  A pre-filter, as every proxy result.
+ *   ccmp_path_densify   device pointers.  SYNCHRONOUS on its stream (it reads 5 bytes per open segment after every extend call to drive
+ *                    the continuation, and path_len once, before any launch): not capturable.  It returns a handle, because the row
+ *                    count is known only afterwards and no caller should pay for the traversal twice.  opts == NULL: the defaults.  With
+ *                    max_calls extend calls spent and a segment still open: CCMP_EOVERFLOW, and no handle — a cut list never looks complete.
+ *   _host            host pointers, on the context's stream.
+ *   ccmp_dense_paths_info / _copy / _copy_host / _destroy   the result: F, max_len, the row count, the extend calls made; copies into
+ *                    device (asynchronous on hip_stream) or host (synchronous) destinations, each nullable: rows_out [rows][14],
+ *                    path_first [F + 1], seg_first / seg_ok / seg_newton [F][max_len - 1], arc [rows], length [F], clearance [rows],
+ *                    min_clear / min_row / first_blocked [F] (the last four: CCMP_EINVAL if asked of a result made without a scene).
+ *   ccmp_dense_layout_ref   the layout alone, pure host code, no device: from path_len and seg_states [F][max_len - 1] (the n_i; entries of
+ *                    slots without a segment are not read) it writes path_first, seg_first (each nullable) and *rows.  CCMP_EINVAL for
+ *                    a path_len outside [0, max_len], an n_i < 1, unknown flags, max_len < 1 or a NULL path_len, seg_states (where a
+ *                    segment exists) or rows; CCMP_EOVERFLOW beyond 2^31 - 1 rows.
+ *   ccmp_dense_arc_ref   the arc rule alone, pure host code: arc [rows] and length [F] (nullable) from rows and path_first.  CCMP_EINVAL for
+ *                    a NULL path_first, a path_first that is negative or decreases, or NULL rows / arc where rows exist.
+ * Conventions as above: every check runs before the first launch; a NULL context answers CCMP_ENODEV without a device and CCMP_EINVAL
+ * with one; F == 0 gives an empty result (0 rows, path_first = {0}).  CCMP_EINVAL: chunk_states < 2, round_budget < 0, max_calls < 1,
+ * unknown flags, max_len < 1, a path_len entry outside [0, max_len] (one that ccmp_roadmap_shortest_paths reported as "did not fit" lands
+ * here), a scene of another device, a NaN margin with a scene, NULL path_joints, path_len or out. */
+#define CCMP_DENSE_DISTINCT 1
+typedef struct ccmp_dense_opts {
+  int flags;        /* 0 or CCMP_DENSE_DISTINCT */
+  int chunk_states; /* list entries per extend call, >= 2 */
+  int round_budget; /* Newton rounds per segment and extend call, 0 = no bound */
+  int max_calls;    /* extend calls at most */
+} ccmp_dense_opts;
+/* 0, 16, 128, 4096: the list length and round budget the extend step's bulk calls settled on */
+void ccmp_dense_opts_default(ccmp_dense_opts *opts);
+typedef struct ccmp_dense_paths ccmp_dense_paths;
+int ccmp_path_densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
+                      size_t F, int max_len, const ccmp_dense_opts *opts, ccmp_dense_paths **out, void *hip_stream);
+int ccmp_path_densify_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints,
+                           const int32_t *path_len, size_t F, int max_len, const ccmp_dense_opts *opts, ccmp_dense_paths **out);
+int ccmp_dense_paths_info(const ccmp_dense_paths *h, size_t *F, int *max_len, size_t *rows, int *calls);
+int ccmp_dense_paths_copy(ccmp_dense_paths *h, double *rows_out, int32_t *path_first, int32_t *seg_first, uint8_t *seg_ok, int32_t *seg_newton, double *arc,
+                          double *length, double *clearance, double *min_clear, int32_t *min_row, int32_t *first_blocked, void *hip_stream);
+int ccmp_dense_paths_copy_host(ccmp_dense_paths *h, double *rows_out, int32_t *path_first, int32_t *seg_first, uint8_t *seg_ok, int32_t *seg_newton,
+                               double *arc, double *length, double *clearance, double *min_clear, int32_t *min_row, int32_t *first_blocked);
+void ccmp_dense_paths_destroy(ccmp_dense_paths *h);
+int ccmp_dense_layout_ref(const int32_t *path_len, size_t F, int max_len, const int32_t *seg_states, int flags, int32_t *path_first, int32_t *seg_first,
+                          size_t *rows);
+int ccmp_dense_arc_ref(const double *rows, const int32_t *path_first, size_t F, double *arc, double *length);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

@@ -452,6 +452,47 @@ inline void nearestK(const Projector &proj, const double *nodes, size_t N, const
   check(ccmp_knn_host(proj.ctx(), nodes, N, q14, 1, (int)k, CCMP_KNN_ALL, 0, idx->data(), nullptr), "ccmp_knn_host");
 }
 
+// PathGeometric::interpolate on a solution path (include/ccmp.h: ccmp_path_densify_host): `states` = the waypoints on entry and the dense
+// path on return — w_0, G_0, w_1, G_1, .., w_{L-1} with every w_i before the last twice in a row, as printAsMatrix then writes them, or
+// with `distinct` G_0, G_1, .., w_{L-1}; G_i = the state list of discreteGeodesic(w_i, w_{i+1}, interpolate = true), traversed to its end
+// inside the library.  seg_ok (nullable) = the return value of each of the L - 1 traversals: a 0 is a segment that stopped short of its
+// target — its rows are there and the path jumps, as the reference's does.  delta / lambda > 0 replace the problem's (the OMPL space's
+// setDelta / setLambda).  Returns the library's code and leaves `states` untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int densifyPathLocked(const Projector &proj, std::vector<std::array<double, 14>> &states, bool distinct, std::vector<uint8_t> *seg_ok,
+                             double delta = 0.0, double lambda = 0.0)
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double), "rows are contiguous");
+  ccmp_problem P = proj.problem();
+  if (delta > 0.0) P.delta = delta;
+  if (lambda > 0.0) P.lambda = lambda;
+  ccmp_dense_opts o;
+  ccmp_dense_opts_default(&o);
+  o.flags = distinct ? CCMP_DENSE_DISTINCT : 0;
+  static const double none[14] = {0};
+  const int32_t len = (int32_t)states.size();
+  ccmp_dense_paths *h = nullptr;
+  int rc = ccmp_path_densify_host(proj.ctx(), &P, nullptr, 0.0, len ? states[0].data() : none, &len, 1, len > 0 ? len : 1, &o, &h);
+  if (rc != CCMP_OK) return rc;
+  size_t rows = 0;
+  std::vector<std::array<double, 14>> dense;
+  std::vector<uint8_t> ok;
+  try {
+    rc = ccmp_dense_paths_info(h, nullptr, nullptr, &rows, nullptr);
+    dense.resize(rows);
+    ok.resize(len > 1 ? (size_t)len - 1 : 0);
+  } catch (...) {
+    rc = CCMP_ENOMEM;
+  }
+  if (rc == CCMP_OK)
+    rc = ccmp_dense_paths_copy_host(h, rows ? dense[0].data() : nullptr, nullptr, nullptr, ok.empty() ? nullptr : ok.data(), nullptr, nullptr, nullptr, nullptr,
+                                    nullptr, nullptr, nullptr);
+  ccmp_dense_paths_destroy(h);
+  if (rc != CCMP_OK) return rc;
+  states.swap(dense);
+  if (seg_ok) seg_ok->swap(ok);
+  return CCMP_OK;
+}
+
 // ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
 // The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
 // rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
@@ -700,7 +741,7 @@ public:
     return len > 0;
   }
   // maybeConstructSolution (stefanBiPRM.cpp:480-603): of the pairs (start, goal) in one component, the cheapest path's joint states, start
-  // first — what PathGeometric::append takes, and discreteGeodesicBatch over consecutive rows is PathGeometric::interpolate.  The first
+  // first — what PathGeometric::append takes; constructDenseSolution below adds PathGeometric::interpolate.  The first
   // pair in starts-major order wins a tie.  false with no states when no pair is connected (at most CCMP_PATH_MAX_PAIRS connected pairs are
   // considered) OR a call failed (lastError()).  cost / indices (nullable) = the path's cost and vertices.
   bool constructSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states, double *cost = nullptr,
@@ -747,6 +788,24 @@ public:
       states.clear();
       return false;
     }
+  }
+  // constructSolution followed by PathGeometric::interpolate (ccmp::densifyPathLocked above): `states` = the dense path, in the layout
+  // ccmp::printAsMatrix writes as the reference's <obj>_path.txt, or with `distinct` without the repeated waypoint rows.  seg_ok (nullable)
+  // = one flag per segment of the waypoint path; delta / lambda > 0 replace the problem's (pass the OMPL space's getDelta() / getLambda()).
+  // false with no states when no pair is connected OR a call failed (lastError()).
+  bool constructDenseSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states,
+                              bool distinct = false, double *cost = nullptr, std::vector<int32_t> *indices = nullptr, std::vector<uint8_t> *seg_ok = nullptr,
+                              double delta = 0.0, double lambda = 0.0) const noexcept
+  {
+    if (seg_ok) seg_ok->clear();
+    if (!constructSolution(starts, goals, states, cost, indices)) return false;
+    const bool ran = call([&] { return densifyPathLocked(proj_, states, distinct, seg_ok, delta, lambda); }, "ccmp_path_densify_host");
+    if (!ran) {
+      states.clear();
+      if (indices) indices->clear();
+      if (cost) *cost = std::numeric_limits<double>::infinity();
+    }
+    return ran;
   }
 
   int lastError() const noexcept { return err_code_; }
@@ -1562,6 +1621,20 @@ public:
     if (ok) traverseMany(from, s, false, geodesics, reached, true);
     else neighbours->clear();
     for (ompl::base::State *n : own) freeState(n);
+  }
+
+  // PathGeometric::interpolate for the solution path of ConstrainedProblem::solveOnce (ConstrainedPlanningCommon.cpp:217), in one call:
+  // `states` = the solution's waypoints on entry, the dense path on return (ccmp::densifyPathLocked: the layout ccmp::printAsMatrix writes
+  // as <obj>_path.txt, or `distinct` for executing it), under this space's delta and lambda.  false = the call failed: `states` is as it
+  // was and the first error stays in KinematicChainConstraint::lastError().  A segment that stops short of its target is not a failure:
+  // seg_ok tells.
+  bool interpolatePath(std::vector<std::array<double, 14>> &states, bool distinct = false, std::vector<uint8_t> *seg_ok = nullptr) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      ccmp::check(ccmp::densifyPathLocked(proj, states, distinct, seg_ok, delta_, lambda_), "ccmp_path_densify_host");
+    });
   }
 
 private:

@@ -35,6 +35,9 @@
                                                            F = 1 and F = 64, the device form (events) and the host form (wall clock) against ccmp_graph_shortest_paths_ref on
                                                            one thread, the rounds each phase took, and the full round trip (read_edges_host + _ref + re-upload of the rows
                                                            against shortest_paths with the rows left on the device); writes profiles/roadmap_path.md
+    python tools/measure.py dense [reps]                    dense solution paths (PathGeometric::interpolate): ccmp_path_densify against discrete_geodesic_batch +
+                                                           continue_geodesics + the host join + the upload of the joined rows, one path and 64 paths of 32 waypoints,
+                                                           both Jacobian modes, the extend calls made and the bytes that crossed to the host; writes profiles/dense_path.md
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -1144,6 +1147,94 @@ def path(argv):
                 + "\n".join(lines) + "\n```\n")
 
 
+def dense(argv):
+    """ccmp_path_densify (KinematicChainConstraint.densify_paths: the continuation loop in the library, the lists stay on the device) against
+    the route a caller had before it on the same waypoints: discrete_geodesic_batch + continue_geodesics (every open list downloaded), the
+    join of the lists on the host by the rule, and the upload of the joined rows.  Near-sampling chains of 32 waypoints, one path and 64
+    paths, both Jacobian modes, lists of 16 and a round budget of 128 on both routes; wall clock around each synchronous route, medians;
+    the outputs compared while they are timed.  Writes profiles/dense_path.md."""
+    import os
+
+    reps = int(argv[0]) if len(argv) > 0 else 15
+    Lw, cs, budget = 32, 16, 128
+    ctx = Context(0)
+    lines = []
+
+    def say(text):
+        print(text)
+        lines.append(text)
+
+    for mode in (0, 1):
+        c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+        cols = [c.sample_project_batch(0xDE5, 0, 64, want_iters=False)[0]]
+        for j in range(1, Lw):
+            cols.append(c.sample_near_project_batch(0xDE5 + j, 0, cols[-1], 0.6, 64, want_iters=False)[0])
+        chains = torch.stack(cols, dim=1).contiguous()  # the FD constraint's samples for both modes
+        c.setJacobianMode(mode)
+        extend_sizes = []  # edges of every extend call the old route makes: what it brings to the host is a function of them
+        plain = c.discrete_geodesic_batch
+
+        def logged(frm, to, *a, **k):
+            extend_sizes.append(frm.shape[0])
+            return plain(frm, to, *a, **k)
+
+        for F in (1, 64):
+            pj = chains[:F].contiguous()
+            pl = torch.full((F,), Lw, dtype=torch.int32, device=pj.device)
+            frm, to = pj[:, :-1].reshape(-1, 14).contiguous(), pj[:, 1:].reshape(-1, 14).contiguous()
+            S = frm.shape[0]
+
+            def old_route():
+                c.discrete_geodesic_batch = logged
+                try:
+                    s, n, ok, its, carry = c.discrete_geodesic_batch(frm, to, cs, want_carry=True, round_budget=budget)
+                    cont = c.continue_geodesics(to, s, n, ok, its, carry, cs, round_budget=budget)
+                finally:
+                    del c.discrete_geodesic_batch
+                s_h, n_h, wp = s.cpu().numpy(), n.cpu().numpy(), pj.cpu().numpy()
+                rows = []
+                for f in range(F):  # the rule, on the host: w_i, G_i, .., the last waypoint
+                    for i in range(Lw - 1):
+                        e = f * (Lw - 1) + i
+                        rows.append(wp[f, i][None])
+                        rows.append(cont[e][0] if e in cont else s_h[e, : n_h[e]])
+                    rows.append(wp[f, Lw - 1][None])
+                joined = np.concatenate(rows, axis=0)
+                up = torch.from_numpy(joined).cuda()  # ... and back up for whatever runs on the dense path next
+                torch.cuda.synchronize()
+                return joined, up
+
+            t_new, t_old, agree, calls = [], [], True, 0
+            for i in range(reps + 3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                new = c.densify_paths(pj, pl, chunk_states=cs, round_budget=budget)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                extend_sizes.clear()
+                joined, up = old_route()
+                t2 = time.perf_counter()
+                calls = new["calls"]
+                agree = agree and np.array_equal(new["joints"].cpu().numpy().view(np.uint64), joined.view(np.uint64)) and len(extend_sizes) == calls
+                if i >= 3:
+                    t_new.append((t1 - t0) * 1e3)
+                    t_old.append((t2 - t1) * 1e3)
+            # bytes to the host.  new: path_len once, then n_states and ok of every open segment of every extend call.  old: the first
+            # call's lists whole with their counts, the open subset's lists again, every continuation call's lists, counts, flags and iterations
+            per_list = cs * 14 * 8
+            new_bytes = 4 * F + 5 * sum(extend_sizes)
+            old_bytes = S * (per_list + 4) + (extend_sizes[1] if len(extend_sizes) > 1 else 0) * (per_list + 8) + sum(extend_sizes[1:]) * (per_list + 9)
+            say("%s mode, F = %d paths x %d waypoints (%d segments, %d dense rows); outputs identical: %s" % ("analytic" if mode else "FD", F, Lw, S, new["rows"], agree))
+            say("    extend calls %d (open segments per call: %s); bytes to the host: densify %d, old route %d" % (calls, extend_sizes[:8] + (["..."] if len(extend_sizes) > 8 else []), new_bytes, old_bytes))
+            say("    %-72s %s" % ("ccmp_path_densify (rows stay on the device)", _stat(t_new)))
+            say("    %-72s %s" % ("discrete_geodesic_batch + continue_geodesics + host join + upload", _stat(t_old)))
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "dense_path.md"), "w") as f:
+        f.write("# Dense solution paths on the device: `tools/measure.py dense`\n\n1 x MI355X, one run; `ccmp_path_densify` against the route a caller had before it "
+                "(extend call, continuation with every open list downloaded, join on the host, upload of the joined rows) on the same waypoints, wall clock around each "
+                "synchronous route, the outputs compared while they are timed.  No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -1214,7 +1305,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, dense, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
