@@ -69,6 +69,11 @@ class CcmpDenseOpts(C.Structure):
     _fields_ = [("flags", C.c_int), ("chunk_states", C.c_int), ("round_budget", C.c_int), ("max_calls", C.c_int)]
 
 
+class CcmpShortcutOpts(C.Structure):
+    """ccmp_shortcut_opts of include/ccmp.h"""
+    _fields_ = [("max_span", C.c_int), ("chunk_states", C.c_int), ("round_budget", C.c_int), ("max_calls", C.c_int), ("tile_edges", C.c_int)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -97,6 +102,8 @@ EXPORTS = [
     "ccmp_roadmap_shortest_paths", "ccmp_roadmap_shortest_paths_host", "ccmp_graph_shortest_paths_ref", "ccmp_roadmap_path_rounds_host",
     "ccmp_dense_opts_default", "ccmp_path_densify", "ccmp_path_densify_host", "ccmp_dense_paths_info", "ccmp_dense_paths_copy", "ccmp_dense_paths_copy_host",
     "ccmp_dense_paths_destroy", "ccmp_dense_layout_ref", "ccmp_dense_arc_ref",
+    "ccmp_shortcut_opts_default", "ccmp_path_shortcut", "ccmp_path_shortcut_host", "ccmp_shortcut_select", "ccmp_shortcut_select_host",
+    "ccmp_shortcut_select_ref", "ccmp_shortcut_pairs_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -273,6 +280,14 @@ def lib():
         "ccmp_dense_paths_destroy": ([vp], None),
         "ccmp_dense_layout_ref": ([i32p, C.c_size_t, C.c_int, i32p, C.c_int, i32p, i32p, C.POINTER(C.c_size_t)], C.c_int),
         "ccmp_dense_arc_ref": ([dp, i32p, C.c_size_t, dp, dp], C.c_int),
+        "ccmp_shortcut_opts_default": ([C.POINTER(CcmpShortcutOpts)], None),
+        "ccmp_path_shortcut": ([vp, pp, vp, C.c_double, vp, vp, C.c_size_t, C.c_int, C.POINTER(CcmpShortcutOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_path_shortcut_host": ([vp, pp, vp, C.c_double, dp, i32p, C.c_size_t, C.c_int, C.POINTER(CcmpShortcutOpts), dp, i32p, i32p, dp, dp, u8p, i32p, i32p],
+                                    C.c_int),
+        "ccmp_shortcut_select": ([vp, vp, vp, C.c_size_t, C.c_int, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_shortcut_select_host": ([vp, dp, i32p, C.c_size_t, C.c_int, u8p, dp, i32p, i32p, dp, dp], C.c_int),
+        "ccmp_shortcut_select_ref": ([dp, i32p, C.c_size_t, C.c_int, u8p, dp, i32p, i32p, dp, dp], C.c_int),
+        "ccmp_shortcut_pairs_ref": ([dp, i32p, C.c_size_t, C.c_int, C.c_int, i32p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -315,6 +330,7 @@ COMMIT_KEEP_ISOLATED = 1  # ccmp.h: CCMP_COMMIT_*
 GRAPH_MAX_ROOTS, CLOSEST_MAX_FROM = 32, 64  # ccmp.h: CCMP_GRAPH_MAX_ROOTS, CCMP_CLOSEST_MAX_FROM
 PATH_MAX_PAIRS = 64  # ccmp.h: CCMP_PATH_MAX_PAIRS
 DENSE_DISTINCT = 1  # ccmp.h: CCMP_DENSE_DISTINCT
+SHORTCUT_MAX_LEN = 1024  # ccmp.h: CCMP_SHORTCUT_MAX_LEN
 
 
 def option_table():

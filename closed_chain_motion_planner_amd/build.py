@@ -37,6 +37,9 @@ Translation units with deliberately different flags:
   ccmp_kernels_dense.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   dense solution paths (ccmp_dense.h): the endpoint gather of the continuation loop, the pack of the
                          extend calls' chunks and the waypoint rows, the arc's serial chain (one block per path) and the segmented clearance reduction
   ccmp_dense.cpp         -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_densify: checks, the continuation loop over ccmp_geodesic_batch_ex, the layout; ccmp_dense_*_ref on the host
+  ccmp_kernels_shortcut.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   shortcut solution paths (ccmp_shortcut.h): the enumeration of a tile of waypoint pairs, the endpoint gather
+                         of a continuation, the scatter of flags and counts into the pair matrices, the DAG search (one block per path) and the gather of the kept rows
+  ccmp_shortcut.cpp      -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_shortcut: checks, the tile and continuation loops over the extend step; ccmp_shortcut_select*, ccmp_shortcut_pairs_ref
 """
 import os
 import shutil
@@ -111,8 +114,12 @@ _UNITS = [
     ("ccmp_kernels_dense.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_path_densify: the checks, the continuation loop and the layout rule on the host (ccmp_dense_layout_ref, ccmp_dense_arc_ref)
     ("ccmp_dense.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # shortcut solution paths (ccmp_shortcut.h): enumerate, regather, scatter, select and the kept rows; the dense unit's flags; registers and LDS only
+    ("ccmp_kernels_shortcut.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # ccmp_path_shortcut: the checks, the tile and continuation loops, and the rule on the host (ccmp_shortcut_select_ref, ccmp_shortcut_pairs_ref)
+    ("ccmp_shortcut.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -158,6 +165,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"object_", 0),  # the head of growTree: a lane's triangle, the pose's frame and one box at a time live in registers, every kernel of the unit
     (r"graph_", 0),  # the roadmap graph: a slot's FK and distances, a lane's best candidate and the scan's sums live in registers and LDS, every kernel of the unit
     (r"dense_", 0),  # dense solution paths: a chunk's descriptor, a lane's distance and a lane's best (value, row) live in registers and LDS, every kernel of the unit
+    (r"shortcut_", 0),  # shortcut solution paths: a slot's decode, a lane's best parent and the search's d / hops / pred live in registers and LDS, every kernel of the unit
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

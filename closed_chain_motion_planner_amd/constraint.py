@@ -536,6 +536,24 @@ class KinematicChainConstraint:
         return densify(self.ctx, self.problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream, _torch(),
                        _stream_handle)
 
+    def shortcut_paths(self, path_joints, path_len, scene=None, margin=None, max_span=0, chunk_states=16, round_budget=128, max_calls=4096,
+                       tile_edges=65536, pairs=False, stream=None):
+        """The removal of interior vertices from F solution paths (ccmp_path_shortcut; csrc/ccmp_shortcut.h): path_joints (F,max_len,14)
+        and path_len (F,) int32 as `Roadmap.shortest_paths` returns them, on the device.  Every pair (i, j) of a path's waypoints with
+        2 <= j - i <= max_span (0: every span) is put to ONE checkMotion(w_i, w_j) — with a ProxyScene and its margin the scene form —
+        all pairs in one batch, continued inside the library whatever tile_edges / chunk_states / round_budget cut it into; then the
+        cheapest path from w_0 to w_{L-1} over the adjacent pairs and the pairs that passed is taken, ties to the fewest hops and the
+        smallest predecessor: deterministic, the optimum any sequence of vertex removals could reach.  Returns a dict of device tensors
+        — joints (F,max_len,14) (the kept rows first; rows behind out_len are the input's), out_len (F,), kept (F,max_len) (-1 behind
+        out_len), cost_in / cost_out (F,) and, with pairs=True, pair_ok / pair_states / pair_newton (F,max_len,max_len).  numpy arrays
+        go through the host form and come back as numpy arrays.  Synchronous.  max_calls spent on a tile with a pair open raises
+        CcmpError (CCMP_EOVERFLOW).  A shortcut leaves the edges the host validated: densify the result and validate the dense rows."""
+        from .shortcut import shortcut
+
+        self._need_problem()
+        return shortcut(self.ctx, self.problem, path_joints, path_len, scene, margin, max_span, chunk_states, round_budget, max_calls, tile_edges, pairs,
+                        stream, _torch(), _stream_handle)
+
     def ambient_uniform_batch(self, seed, first_index, B, stream=None):
         self._need_problem()
         torch = _torch()

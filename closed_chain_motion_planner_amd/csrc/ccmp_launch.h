@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; }
+namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -228,6 +228,26 @@ hipError_t dense_arc(const double *rows, const int32_t *path_first, size_t F, do
 /* one block per path: (min clearance, first row attaining it) and the first row below the margin */
 hipError_t dense_clearance_summary(const double *clearance, const int32_t *path_first, size_t F, double margin, double *min_clear, int32_t *min_row,
                                    int32_t *first_blocked, hipStream_t st);
+/* shortcut solution paths (ccmp_path_shortcut, ccmp_shortcut_select; csrc/ccmp_shortcut.h).  One tile of pair slots [first, first + T) of the
+ * enumeration over all paths (prefix [F + 1] = the slots before each path, from path_len and max_span alone): slot k's matrix entry
+ * cell[k] = (f max_len + i) max_len + j and its endpoint rows from / to [T][14]; a slot with a non-finite row is no candidate: cell -1 and
+ * zero rows (no NaN endpoint reaches a traversal) */
+hipError_t shortcut_enumerate(const double *path_joints, const int32_t *path_len, const long long *prefix, size_t F, int max_len, int max_span,
+                              long long first, size_t T, long long *cell, double *from, double *to, hipStream_t st);
+/* the endpoints of a continuation's E open pairs: from = the last stored row of the previous call's list, to and carry as they were */
+hipError_t shortcut_regather(const ccmp::shortcut_open *open, size_t E, const double *prev_states, int chunk_states, const double *prev_to,
+                             const double *prev_carry, double *from, double *to, double *carry_in, hipStream_t st);
+/* after an extend call over E open pairs (open == nullptr: the tile's first call, pair k = slot k): the states and Newton rounds the call
+ * contributed are added to the pair's matrix entries, and the flag of a pair that is no longer open is written */
+hipError_t shortcut_scatter(const ccmp::shortcut_open *open, size_t E, const long long *cell, const int32_t *n_states, const uint8_t *ok,
+                            const int32_t *newton, const uint8_t *blocked, int chunk_states, size_t cells, uint8_t *pair_ok, int32_t *pair_states,
+                            int32_t *pair_newton, hipStream_t st);
+/* one block per path: the forward sweep over the DAG of admitted edges, the walk of pred, the costs */
+hipError_t shortcut_select(const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok, int32_t *out_len,
+                           int32_t *kept, double *cost_in, double *cost_out, hipStream_t st);
+/* out_joints[f][k] = path_joints[f][kept[f][k]] for k < out_len[f]; rows behind are not written */
+hipError_t shortcut_gather_kept(const double *path_joints, const int32_t *out_len, const int32_t *kept, size_t F, int max_len, double *out_joints,
+                                hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

@@ -1,0 +1,444 @@
+// ccmp_shortcut.cpp — shortcut solution paths of the C ABI (include/ccmp.h: ccmp_path_shortcut, ccmp_shortcut_*): every pair of a path's
+// waypoints is put to one checkMotion, then the cheapest path over the pairs that passed is taken.  The rule is csrc/ccmp_shortcut.h.  The
+// traversals are ccmp_geodesic_batch_ex's (ccmp_geodesic_scene_batch's with a proxy scene), unchanged: this unit owns the loop over tiles of
+// the enumeration and, per tile, the continuation loop — one extend launch over the open pairs, one scatter launch that adds what the call
+// contributed to the pair's matrix entries, one read of n_states / ok (5 bytes per open pair, 6 with a scene), the compaction of the open
+// subset on those bytes, one gather launch for the next call.  Nothing but an open pair's last stored state and carry survives a call: the
+// two list buffers of a tile alternate.  The matrices are filled in a workspace of the call; only when every tile has closed does the
+// selection run and anything reach the caller's outputs, so a call that spends max_calls leaves them untouched.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/ccmp.h"
+#include "ccmp_ctx.h"
+#include "ccmp_launch.h"
+#include "ccmp_resident.h"
+#include "ccmp_scene.h"
+#include "ccmp_shortcut.h"
+
+using namespace ccmp_host;
+using ccmp::shortcut_best;
+using ccmp::shortcut_open;
+
+namespace {
+
+constexpr size_t kMaxCells = (size_t)1 << 40; // F max_len^2 beyond this is an argument error, not an allocation to try
+
+int no_ctx()
+{
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CCMP_ENODEV; }
+  return CCMP_EINVAL;
+}
+
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// the device memory of one call, released when it returns
+struct Scratch {
+  ccmp_ctx *ctx;
+  std::vector<void *> blocks;
+  explicit Scratch(ccmp_ctx *c) : ctx(c) {}
+  Scratch(const Scratch &) = delete;
+  Scratch &operator=(const Scratch &) = delete;
+  void *get(size_t bytes)
+  {
+    void *b = nullptr;
+    ccmp_host::quiesce(ctx);
+    const hipError_t e = hipMalloc(&b, align256(bytes ? bytes : 1));
+    if (e != hipSuccess) { (void)hip_fail(e, "ccmp_path_shortcut: hipMalloc"); return nullptr; }
+    blocks.push_back(b);
+    return b;
+  }
+  ~Scratch()
+  {
+    if (blocks.empty()) return;
+    ccmp_host::quiesce(ctx);
+    for (void *b : blocks) (void)hipFree(b); // waits for whatever still reads it
+  }
+};
+
+bool overlaps(const void *a, size_t na, const void *b, size_t nb)
+{
+  if (!a || !b || !na || !nb) return false;
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+int opts_ok(const ccmp_shortcut_opts &o)
+{
+  if (o.max_span < 0 || o.chunk_states < 2 || o.round_budget < 0 || o.max_calls < 1 || o.tile_edges < 1) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+// the shapes, the required pointers and the overlap of outputs with inputs: shared by every form that has them
+int select_checks(const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok_in, double *out_joints, int32_t *out_len,
+                  int32_t *kept, double *cost_in, double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton)
+{
+  if (max_len < 1 || max_len > CCMP_SHORTCUT_MAX_LEN) return CCMP_EINVAL;
+  if (F == 0) return CCMP_OK;
+  if (F > kMaxCells / ((size_t)max_len * (size_t)max_len)) return CCMP_EINVAL;
+  if (!path_joints || !path_len || !out_joints || !out_len || !kept || !cost_in || !cost_out) return CCMP_EINVAL;
+  const size_t rows = F * (size_t)max_len, cells = rows * (size_t)max_len;
+  const void *in[3] = {path_joints, path_len, pair_ok_in};
+  const size_t in_n[3] = {rows * 14 * sizeof(double), F * sizeof(int32_t), pair_ok_in ? cells : 0};
+  const void *out[8] = {out_joints, out_len, kept, cost_in, cost_out, pair_ok, pair_states, pair_newton};
+  const size_t out_n[8] = {rows * 14 * sizeof(double), F * sizeof(int32_t), rows * sizeof(int32_t), F * sizeof(double), F * sizeof(double),
+                           cells,                      cells * sizeof(int32_t), cells * sizeof(int32_t)};
+  for (int a = 0; a < 8; a++)
+    for (int b = 0; b < 3; b++)
+      if (overlaps(out[a], out_n[a], in[b], in_n[b])) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+int shortcut_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_shortcut_opts &o)
+{
+  { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
+  if (!(p->delta > 0) || !(p->lambda > 0)) return CCMP_EINVAL;
+  { const int rc = opts_ok(o); if (rc != CCMP_OK) return rc; }
+  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+int lens_ok(const int32_t *len, size_t F, int max_len)
+{
+  for (size_t f = 0; f < F; f++)
+    if (len[f] < 0 || len[f] > max_len) return CCMP_EINVAL;
+  return CCMP_OK;
+}
+
+// one extend call's buffers; a tile has two and alternates
+struct CallBufs {
+  double *from = nullptr, *to = nullptr, *states = nullptr, *carry_out = nullptr, *carry_in = nullptr;
+  int32_t *n = nullptr, *its = nullptr;
+  uint8_t *ok = nullptr, *blocked = nullptr;
+  shortcut_open *open = nullptr;
+};
+
+bool make_bufs(Scratch &mem, size_t T, int cs, bool scene, CallBufs *b)
+{
+  b->from = (double *)mem.get(T * 14 * sizeof(double));
+  b->to = (double *)mem.get(T * 14 * sizeof(double));
+  b->states = (double *)mem.get(T * (size_t)cs * 14 * sizeof(double));
+  b->carry_out = (double *)mem.get(T * 2 * sizeof(double));
+  b->carry_in = (double *)mem.get(T * 2 * sizeof(double));
+  b->n = (int32_t *)mem.get(T * sizeof(int32_t));
+  b->its = (int32_t *)mem.get(T * sizeof(int32_t));
+  b->ok = (uint8_t *)mem.get(T);
+  b->blocked = scene ? (uint8_t *)mem.get(T) : nullptr;
+  b->open = (shortcut_open *)mem.get(T * sizeof(shortcut_open));
+  return b->from && b->to && b->states && b->carry_out && b->carry_in && b->n && b->its && b->ok && (!scene || b->blocked) && b->open;
+}
+
+// The body of the device form behind its checks; `len` = path_len as read once from the device.  The outputs are written only after every
+// tile has closed.
+int shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
+             const std::vector<int32_t> &len, size_t F, int max_len, const ccmp_shortcut_opts &o, double *out_joints, int32_t *out_len, int32_t *kept,
+             double *cost_in, double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton, hipStream_t st)
+{
+  const int cs = o.chunk_states;
+  const size_t cells = F * (size_t)max_len * (size_t)max_len;
+  std::vector<long long> prefix(F + 1, 0);
+  for (size_t f = 0; f < F; f++) prefix[f + 1] = prefix[f] + ccmp::shortcut_pair_count(len[f], o.max_span);
+  const long long total = prefix[F];
+  Scratch mem(ctx);
+  // the call's own matrices: the caller's stay untouched until the end
+  uint8_t *w_ok = (uint8_t *)mem.get(cells);
+  int32_t *w_states = pair_states ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr;
+  int32_t *w_newton = pair_newton ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr;
+  if (!w_ok || (pair_states && !w_states) || (pair_newton && !w_newton)) return CCMP_EHIP;
+  HIP_TRY(hipMemsetAsync(w_ok, 0, cells, st));
+  if (w_states) HIP_TRY(hipMemsetAsync(w_states, 0, cells * sizeof(int32_t), st));
+  if (w_newton) HIP_TRY(hipMemsetAsync(w_newton, 0, cells * sizeof(int32_t), st));
+
+  if (total > 0) {
+    const size_t T_max = (size_t)((long long)o.tile_edges < total ? (long long)o.tile_edges : total);
+    long long *d_prefix = (long long *)mem.get((F + 1) * sizeof(long long)), *d_cell = (long long *)mem.get(T_max * sizeof(long long));
+    CallBufs bufs[2];
+    if (!d_prefix || !d_cell || !make_bufs(mem, T_max, cs, scene != nullptr, &bufs[0]) || !make_bufs(mem, T_max, cs, scene != nullptr, &bufs[1])) return CCMP_EHIP;
+    HIP_TRY(hipMemcpyAsync(d_prefix, prefix.data(), (F + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    std::vector<int32_t> n_h(T_max);
+    std::vector<uint8_t> ok_h(T_max), bl_h(T_max, 0);
+    std::vector<shortcut_open> open_h, next_h;
+    std::vector<int32_t> slot_of(T_max); // per pair of the current call: its slot in the tile
+    for (long long first = 0; first < total; first += (long long)T_max) {
+      const size_t T = (size_t)(total - first < (long long)T_max ? total - first : (long long)T_max);
+      size_t E = T;
+      int cur = 0, calls = 0;
+      bool cont = false; // the tile's first call reads its endpoints from the enumeration
+      for (size_t k = 0; k < T; k++) slot_of[k] = (int32_t)k;
+      HIP_TRY(ccmp_launch::shortcut_enumerate(path_joints, path_len, d_prefix, F, max_len, o.max_span, first, T, d_cell, bufs[0].from, bufs[0].to, st));
+      while (E > 0) {
+        if (calls == o.max_calls) { // a cut traversal must never look complete: nothing reaches the outputs
+          (void)hipStreamSynchronize(st);
+          return CCMP_EOVERFLOW;
+        }
+        CallBufs &b = bufs[cur];
+        int rc;
+        if (scene)
+          rc = ccmp_geodesic_scene_batch(ctx, p, scene, margin, b.from, b.to, E, cs, b.states, b.n, b.ok, b.its, b.blocked, nullptr, cont ? b.carry_in : nullptr,
+                                         b.carry_out, o.round_budget, cont ? 0 : 1, st);
+        else
+          rc = ccmp_geodesic_batch_ex(ctx, p, b.from, b.to, E, cs, b.states, b.n, b.ok, b.its, cont ? b.carry_in : nullptr, b.carry_out, o.round_budget,
+                                      cont ? 0 : 1, st);
+        hipError_t e = hipSuccess;
+        if (rc == CCMP_OK)
+          e = ccmp_launch::shortcut_scatter(cont ? b.open : nullptr, E, d_cell, b.n, b.ok, b.its, b.blocked, cs, cells, w_ok, w_states, w_newton, st);
+        if (e == hipSuccess && rc == CCMP_OK) e = hipMemcpyAsync(n_h.data(), b.n, E * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && rc == CCMP_OK) e = hipMemcpyAsync(ok_h.data(), b.ok, E, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && rc == CCMP_OK && scene) e = hipMemcpyAsync(bl_h.data(), b.blocked, E, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (rc != CCMP_OK) return rc;
+        HIP_TRY(e);
+        HIP_TRY(es);
+        calls++;
+        next_h.clear();
+        for (size_t k = 0; k < E; k++) {
+          if (bl_h[k] || !ccmp::dense_open(n_h[k], ok_h[k], cs)) continue;
+          const int32_t stored = ccmp::dense_stored(n_h[k], cs);
+          if (stored < 1) { snprintf(g_hip_err, sizeof g_hip_err, "ccmp_path_shortcut: an extend call stored no state"); return CCMP_EHIP; }
+          next_h.push_back(shortcut_open{(int32_t)k, stored - 1, slot_of[k], 0});
+        }
+        E = next_h.size();
+        if (E == 0) break;
+        open_h.swap(next_h); // kept until the next synchronisation: it backs the upload below
+        for (size_t k = 0; k < E; k++) slot_of[k] = open_h[k].slot;
+        CallBufs &nb = bufs[cur ^ 1];
+        HIP_TRY(hipMemcpyAsync(nb.open, open_h.data(), E * sizeof(shortcut_open), hipMemcpyHostToDevice, st));
+        HIP_TRY(ccmp_launch::shortcut_regather(nb.open, E, b.states, cs, b.to, b.carry_out, nb.from, nb.to, nb.carry_in, st));
+        cur ^= 1;
+        cont = true;
+      }
+    }
+  }
+
+  // every pair is closed: the selection, then the caller's outputs
+  HIP_TRY(ccmp_launch::shortcut_select(path_joints, path_len, F, max_len, w_ok, out_len, kept, cost_in, cost_out, st));
+  HIP_TRY(ccmp_launch::shortcut_gather_kept(path_joints, out_len, kept, F, max_len, out_joints, st));
+  if (pair_ok) HIP_TRY(hipMemcpyAsync(pair_ok, w_ok, cells, hipMemcpyDeviceToDevice, st));
+  if (pair_states) HIP_TRY(hipMemcpyAsync(pair_states, w_states, cells * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  if (pair_newton) HIP_TRY(hipMemcpyAsync(pair_newton, w_newton, cells * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st)); // the call is synchronous: its workspace goes when it returns
+  return CCMP_OK;
+}
+
+// the rule on host pointers, one thread (ccmp_shortcut_select_ref)
+void select_one(const double *rows, int L, int max_len, const uint8_t *okm, double *out_rows, int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out)
+{
+  std::vector<double> d((size_t)(L > 0 ? L : 1));
+  std::vector<int32_t> hops(d.size()), pred(d.size());
+  for (int k = 0; k < max_len; k++) kept[k] = -1;
+  double a = 0.0;
+  for (int j = 1; j < L; j++) a = a + ccmp::graph_joint_dist(rows + (size_t)(j - 1) * 14, rows + (size_t)j * 14);
+  *cost_in = a;
+  if (L == 0) { *out_len = 0; *cost_out = 0.0; return; }
+  d[0] = 0.0; hops[0] = 0; pred[0] = -1;
+  for (int j = 1; j < L; j++) {
+    shortcut_best b = ccmp::shortcut_none();
+    for (int i = 0; i < j; i++) {
+      if (!ccmp::shortcut_admitted(i, j, i + 1 == j ? 1 : okm[(size_t)i * (size_t)max_len + (size_t)j])) continue;
+      ccmp::shortcut_relax(&b, i, d[i], hops[i], ccmp::graph_joint_dist(rows + (size_t)i * 14, rows + (size_t)j * 14));
+    }
+    const bool reached = b.pred != ccmp::kShortcutNoPred;
+    d[j] = reached ? b.d : __builtin_inf();
+    hops[j] = reached ? b.parent_hops + 1 : ccmp::kPathNoHops;
+    pred[j] = reached ? b.pred : -1;
+  }
+  *cost_out = d[L - 1];
+  if (hops[L - 1] == ccmp::kPathNoHops) { // unchanged
+    for (int k = 0; k < L; k++) kept[k] = k;
+    *out_len = L;
+  } else {
+    const int n = hops[L - 1] + 1;
+    int v = L - 1;
+    for (int k = n - 1; k >= 0 && v >= 0; k--) { kept[k] = v; v = pred[v]; }
+    *out_len = n;
+  }
+  for (int k = 0; k < *out_len; k++) memcpy(out_rows + (size_t)k * 14, rows + (size_t)kept[k] * 14, 14 * sizeof(double));
+}
+
+}  // namespace
+
+extern "C" {
+
+void ccmp_shortcut_opts_default(ccmp_shortcut_opts *opts)
+{
+  if (!opts) return;
+  opts->max_span = 0;
+  opts->chunk_states = 16;
+  opts->round_budget = 128;
+  opts->max_calls = 4096;
+  opts->tile_edges = 65536;
+}
+
+int ccmp_path_shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
+                       size_t F, int max_len, const ccmp_shortcut_opts *opts, double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in,
+                       double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton, void *hip_stream)
+{
+  if (!ctx) return no_ctx();
+  ccmp_shortcut_opts o;
+  ccmp_shortcut_opts_default(&o);
+  if (opts) o = *opts;
+  { const int rc = shortcut_checks(ctx, p, scene, margin, o); if (rc != CCMP_OK) return rc; }
+  { const int rc = select_checks(path_joints, path_len, F, max_len, nullptr, out_joints, out_len, kept, cost_in, cost_out, pair_ok, pair_states, pair_newton);
+    if (rc != CCMP_OK) return rc; }
+  if (F == 0) return CCMP_OK;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  std::vector<int32_t> len(F);
+  { // path_len is read once, before any launch
+    const hipError_t e = hipMemcpyAsync(len.data(), path_len, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    HIP_TRY(e);
+    HIP_TRY(es);
+    const int rc = lens_ok(len.data(), F, max_len);
+    if (rc != CCMP_OK) return rc;
+  }
+  return shortcut(ctx, p, scene, margin, path_joints, path_len, len, F, max_len, o, out_joints, out_len, kept, cost_in, cost_out, pair_ok, pair_states,
+                  pair_newton, st);
+}
+
+int ccmp_path_shortcut_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints,
+                            const int32_t *path_len, size_t F, int max_len, const ccmp_shortcut_opts *opts, double *out_joints, int32_t *out_len,
+                            int32_t *kept, double *cost_in, double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton)
+{
+  if (!ctx) return no_ctx();
+  ccmp_shortcut_opts o;
+  ccmp_shortcut_opts_default(&o);
+  if (opts) o = *opts;
+  { const int rc = shortcut_checks(ctx, p, scene, margin, o); if (rc != CCMP_OK) return rc; }
+  { const int rc = select_checks(path_joints, path_len, F, max_len, nullptr, out_joints, out_len, kept, cost_in, cost_out, pair_ok, pair_states, pair_newton);
+    if (rc != CCMP_OK) return rc; }
+  if (F == 0) return CCMP_OK;
+  { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = ctx->stream;
+  const size_t rows = F * (size_t)max_len, cells = rows * (size_t)max_len;
+  Scratch mem(ctx);
+  double *d_in = (double *)mem.get(rows * 14 * sizeof(double)), *d_out = (double *)mem.get(rows * 14 * sizeof(double));
+  double *d_ci = (double *)mem.get(F * sizeof(double)), *d_co = (double *)mem.get(F * sizeof(double));
+  int32_t *d_len = (int32_t *)mem.get(F * sizeof(int32_t)), *d_olen = (int32_t *)mem.get(F * sizeof(int32_t)), *d_kept = (int32_t *)mem.get(rows * sizeof(int32_t));
+  uint8_t *d_ok = pair_ok ? (uint8_t *)mem.get(cells) : nullptr;
+  int32_t *d_ps = pair_states ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr, *d_pn = pair_newton ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr;
+  if (!d_in || !d_out || !d_ci || !d_co || !d_len || !d_olen || !d_kept || (pair_ok && !d_ok) || (pair_states && !d_ps) || (pair_newton && !d_pn)) return CCMP_EHIP;
+  {
+    hipError_t e = hipMemcpyAsync(d_in, path_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_len, path_len, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, out_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st); // rows behind out_len stay the caller's
+    const hipError_t es = hipStreamSynchronize(st);
+    HIP_TRY(e);
+    HIP_TRY(es);
+  }
+  const int rc = shortcut(ctx, p, scene, margin, d_in, d_len, std::vector<int32_t>(path_len, path_len + F), F, max_len, o, d_out, d_olen, d_kept, d_ci, d_co, d_ok,
+                          d_ps, d_pn, st);
+  if (rc != CCMP_OK) return rc;
+  hipError_t e = hipMemcpyAsync(out_joints, d_out, rows * 14 * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_len, d_olen, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(kept, d_kept, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cost_in, d_ci, F * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cost_out, d_co, F * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && pair_ok) e = hipMemcpyAsync(pair_ok, d_ok, cells, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && pair_states) e = hipMemcpyAsync(pair_states, d_ps, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && pair_newton) e = hipMemcpyAsync(pair_newton, d_pn, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_shortcut_select(ccmp_ctx *ctx, const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok,
+                         double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out, void *hip_stream)
+{
+  if (!ctx) return no_ctx();
+  { const int rc = select_checks(path_joints, path_len, F, max_len, pair_ok, out_joints, out_len, kept, cost_in, cost_out, nullptr, nullptr, nullptr);
+    if (rc != CCMP_OK) return rc; }
+  if (F == 0) return CCMP_OK;
+  if (!pair_ok) return CCMP_EINVAL;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(ccmp_launch::shortcut_select(path_joints, path_len, F, max_len, pair_ok, out_len, kept, cost_in, cost_out, st));
+  HIP_TRY(ccmp_launch::shortcut_gather_kept(path_joints, out_len, kept, F, max_len, out_joints, st));
+  return CCMP_OK;
+}
+
+int ccmp_shortcut_select_host(ccmp_ctx *ctx, const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok,
+                              double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out)
+{
+  if (!ctx) return no_ctx();
+  { const int rc = select_checks(path_joints, path_len, F, max_len, pair_ok, out_joints, out_len, kept, cost_in, cost_out, nullptr, nullptr, nullptr);
+    if (rc != CCMP_OK) return rc; }
+  if (F == 0) return CCMP_OK;
+  if (!pair_ok) return CCMP_EINVAL;
+  { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = ctx->stream;
+  const size_t rows = F * (size_t)max_len, cells = rows * (size_t)max_len;
+  Scratch mem(ctx);
+  double *d_in = (double *)mem.get(rows * 14 * sizeof(double)), *d_out = (double *)mem.get(rows * 14 * sizeof(double));
+  double *d_ci = (double *)mem.get(F * sizeof(double)), *d_co = (double *)mem.get(F * sizeof(double));
+  int32_t *d_len = (int32_t *)mem.get(F * sizeof(int32_t)), *d_olen = (int32_t *)mem.get(F * sizeof(int32_t)), *d_kept = (int32_t *)mem.get(rows * sizeof(int32_t));
+  uint8_t *d_ok = (uint8_t *)mem.get(cells);
+  if (!d_in || !d_out || !d_ci || !d_co || !d_len || !d_olen || !d_kept || !d_ok) return CCMP_EHIP;
+  hipError_t e = hipMemcpyAsync(d_in, path_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_len, path_len, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_ok, pair_ok, cells, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_out, out_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st); // rows behind out_len stay the caller's
+  if (e == hipSuccess) e = ccmp_launch::shortcut_select(d_in, d_len, F, max_len, d_ok, d_olen, d_kept, d_ci, d_co, st);
+  if (e == hipSuccess) e = ccmp_launch::shortcut_gather_kept(d_in, d_olen, d_kept, F, max_len, d_out, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_joints, d_out, rows * 14 * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_len, d_olen, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(kept, d_kept, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cost_in, d_ci, F * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cost_out, d_co, F * sizeof(double), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
+int ccmp_shortcut_select_ref(const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok, double *out_joints,
+                             int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out)
+{
+  { const int rc = select_checks(path_joints, path_len, F, max_len, pair_ok, out_joints, out_len, kept, cost_in, cost_out, nullptr, nullptr, nullptr);
+    if (rc != CCMP_OK) return rc; }
+  if (F == 0) return CCMP_OK;
+  if (!pair_ok) return CCMP_EINVAL;
+  { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
+  for (size_t f = 0; f < F; f++)
+    select_one(path_joints + f * (size_t)max_len * 14, path_len[f], max_len, pair_ok + f * (size_t)max_len * (size_t)max_len,
+               out_joints + f * (size_t)max_len * 14, out_len + f, kept + f * (size_t)max_len, cost_in + f, cost_out + f);
+  return CCMP_OK;
+}
+
+int ccmp_shortcut_pairs_ref(const double *path_joints, const int32_t *path_len, size_t F, int max_len, int max_span, int32_t *triples, size_t capacity,
+                            size_t *count)
+{
+  if (!count || max_len < 1 || max_len > CCMP_SHORTCUT_MAX_LEN || max_span < 0) return CCMP_EINVAL;
+  *count = 0;
+  if (F == 0) return CCMP_OK;
+  if (!path_joints || !path_len || F > (size_t)0x7fffffff) return CCMP_EINVAL;
+  { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
+  size_t n = 0;
+  for (size_t f = 0; f < F; f++) {
+    const int L = path_len[f];
+    const double *rows = path_joints + f * (size_t)max_len * 14;
+    const long long slots = ccmp::shortcut_pair_count(L, max_span);
+    for (long long r = 0; r < slots; r++) { // the enumeration the device walks, slot by slot
+      int i, j;
+      ccmp::shortcut_pair_of(L, max_span, r, &i, &j);
+      if (!ccmp::shortcut_row_finite(rows + (size_t)i * 14) || !ccmp::shortcut_row_finite(rows + (size_t)j * 14)) continue;
+      if (triples && n < capacity) { triples[n * 3] = (int32_t)f; triples[n * 3 + 1] = i; triples[n * 3 + 2] = j; }
+      n++;
+    }
+  }
+  *count = n;
+  return (triples && n > capacity) ? CCMP_EOVERFLOW : CCMP_OK;
+}
+
+}  // extern "C"

@@ -595,6 +595,36 @@ class Roadmap:
             return None
         return sol[0], sol[1], sol[2], self._dense(constraint, sol[3], kw)
 
+    _SHORTCUT_KW = ("scene", "margin", "max_span", "chunk_states", "round_budget", "max_calls", "tile_edges", "pairs")
+
+    def shortcut_solution(self, constraint, starts, goals, max_len=64, **kw):
+        """`solution` followed by `constraint.shortcut_paths` on its joint rows (kw: its keyword arguments): interior vertices the
+        constraint's checkMotion can do without are removed, on the device.  Returns (cost of the shortcut path, indices of the kept
+        vertices (len,) int32 numpy, joints (len,14) device tensor, shortcut) with shortcut the dict of `shortcut_paths`, or None when
+        no pair is connected."""
+        torch = _torch()
+        sol = self.solution(starts, goals, max_len=max_len)
+        if sol is None:
+            return None
+        _, idx, joints = sol
+        n = joints.shape[0]
+        plen = torch.full((1,), n, dtype=torch.int32, device=joints.device)
+        sc = constraint.shortcut_paths(joints.reshape(1, n, 14).contiguous(), plen, **kw)
+        m = int(sc["out_len"][0])
+        keep = sc["kept"][0, :m].cpu().numpy()
+        return float(sc["cost_out"][0]), idx[keep], sc["joints"][0, :m].contiguous(), sc
+
+    def dense_shortcut_solution(self, constraint, starts, goals, max_len=64, **kw):
+        """solution -> shortcut -> densify, each step on the device outputs of the one before: `shortcut_solution` (its keyword arguments
+        among kw), then `constraint.densify_paths` on the kept rows (the remaining kw; a scene and its margin go to both).  Returns
+        (cost, indices, dense, shortcut), or None.  The dense rows are what the host's validity test takes next."""
+        skw = {k: v for k, v in kw.items() if k in self._SHORTCUT_KW}
+        dkw = {k: v for k, v in kw.items() if k not in ("max_span", "tile_edges", "pairs")}
+        sol = self.shortcut_solution(constraint, starts, goals, max_len=max_len, **skw)
+        if sol is None:
+            return None
+        return sol[0], sol[1], self._dense(constraint, sol[2], dkw), sol[3]
+
     def close(self):
         if self._h:
             _lib.lib().ccmp_roadmap_destroy(self._h)

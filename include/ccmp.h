@@ -965,6 +965,74 @@ int ccmp_dense_layout_ref(const int32_t *path_len, size_t F, int max_len, const 
                           size_t *rows);
 int ccmp_dense_arc_ref(const double *rows, const int32_t *path_first, size_t F, double *arc, double *length);
 
+/* ---- shortcut solution paths: the removal of interior vertices on the device ------------------------------------------------------- */
+/* What comes out of ccmp_roadmap_shortest_paths is a roadmap path: it visits every milestone the tree happened to grow through.  OMPL
+ * removes interior vertices by trying random pairs, one checkMotion at a time (PathSimplifier::reduceVertices); here every pair of a path
+ * is tested in one batch and the cheapest path over the pairs that passed is taken — the optimum any sequence of vertex removals could
+ * reach, deterministic, a function of the inputs alone, bit for bit.  The rule (csrc/ccmp_shortcut.h states it once, for the kernels, the
+ * host forms and the _ref forms); path f has L = path_len[f] waypoints w_0 .. w_{L-1}, rows of path_joints [F][max_len][14]:
+ *     candidate      a pair (i, j), 0 <= i, j < L, with j - i >= 2, j - i <= max_span (max_span == 0: every span) and both rows finite in all
+ *                    14 coordinates; candidates are enumerated in (f, i, j) order.
+ *     test           ONE uninterrupted checkMotion(w_i, w_j), forwards only: isSatisfied(w_j), then discreteGeodesic(w_i, w_j)
+ *                    (ccmp_geodesic_batch_ex with check_target = 1 on the first call; with a proxy scene ccmp_geodesic_scene_batch and its
+ *                    margin: the traversal breaks at the first refused state).  pair_ok[i][j] = its return value, pair_states[i][j] = its
+ *                    list length, pair_newton[i][j] = its Newton total.  The library cuts traversals into extend calls of chunk_states
+ *                    list entries and round_budget Newton rounds over tiles of at most tile_edges pairs and continues every open pair
+ *                    until none is left: flag, count and total are those of one traversal, bit for bit, whatever the cut.  Only the last
+ *                    stored state and the carry of an open pair are kept: no state lists.  Entries that are no candidates are 0.
+ *     admitted edge  i -> j with j == i + 1 (the roadmap's own edge: never tested) or pair_ok[i][j] == 1.
+ *     weight         w(i, j) = ccmp_joint_distance(w_i, w_j): what commit stores as motionCost.
+ *     selection      the rule of ccmp_roadmap_shortest_paths on this DAG from source 0: d[0] = +0.0, d[j] = min over admitted i < j of
+ *                    fl(d[i] + w(i, j)), a candidate passing iff d[i] is finite, w >= 0 and the sum is finite; hops[j] = the least
+ *                    hops[i] + 1 over tight i; pred[j] = the smallest tight i with hops[i] == hops[j] - 1.  One forward sweep is exact.
+ *     result         kept [F][max_len] = the walk of pred from L - 1 written forwards, -1 behind it; out_len [F] = its length; out_joints
+ *                    [F][max_len][14] = the kept rows, bit for bit (rows behind out_len are untouched); cost_in [F] = the left-to-right fl
+ *                    sum of the adjacent weights; cost_out [F] = d[L - 1].  L == 1: kept {0}, costs +0.0.  L == 0: nothing, costs +0.0.
+ *                    d[L - 1] == +inf (an adjacent weight is NaN or infinite, e.g. a pose-only vertex): the path comes back unchanged —
+ *                    identity kept — with cost_out = +inf.
+ * The result does not depend on tile_edges, chunk_states, round_budget or launch shape.
+ *   ccmp_path_shortcut   device pointers.  pair_ok (uint8), pair_states, pair_newton (int32), each [F][max_len][max_len], are nullable.
+ *                    SYNCHRONOUS on its stream (it reads 5 bytes per open pair after every extend call, and path_len once, before any
+ *                    launch): not capturable.  opts == NULL: the defaults.  max_calls extend calls spent on a tile with a pair still open:
+ *                    CCMP_EOVERFLOW, every output untouched.  A shortcut leaves the edges the host validated: densify the result
+ *                    (ccmp_path_densify) and put the dense rows to the host's validity test.
+ *   _host            host pointers, on the context's stream.
+ *   ccmp_shortcut_select   the selection alone on a caller's pair_ok (any edge test: the host's MoveIt verdicts, say): asynchronous on its
+ *                    stream, capturable; path_len is read on the device, an entry outside [0, max_len] is taken as 0.  _host: host
+ *                    pointers, synchronous; a path_len entry outside [0, max_len] is CCMP_EINVAL.
+ *   ccmp_shortcut_select_ref   the same rule text on host pointers, one thread, no device, never CCMP_ENODEV.
+ *   ccmp_shortcut_pairs_ref    the candidate enumeration, pure host code: triples [capacity][3] = (f, i, j) in order (nullable: count only)
+ *                    and *count; CCMP_EOVERFLOW when capacity is too small (*count is still the number there is).
+ * Conventions as the dense section's: every check runs before the first launch; a NULL context answers CCMP_ENODEV without a device and
+ * CCMP_EINVAL with one; F == 0 returns CCMP_OK and touches nothing.  CCMP_EINVAL: a path_len entry outside [0, max_len], max_len < 1 or
+ * > CCMP_SHORTCUT_MAX_LEN, max_span < 0, tile_edges < 1, chunk_states < 2, round_budget < 0, max_calls < 1, an output overlapping an input,
+ * a NULL path_joints, path_len, out_joints, out_len, kept, cost_in or cost_out (select: pair_ok too), a scene of another device, a NaN
+ * margin with a scene. */
+#define CCMP_SHORTCUT_MAX_LEN 1024
+typedef struct ccmp_shortcut_opts {
+  int max_span;     /* candidates span at most this many waypoints, 0 = every span */
+  int chunk_states; /* list entries per extend call, >= 2 */
+  int round_budget; /* Newton rounds per pair and extend call, 0 = no bound */
+  int max_calls;    /* extend calls at most, per tile */
+  int tile_edges;   /* pairs per tile, >= 1 */
+} ccmp_shortcut_opts;
+/* 0, 16, 128, 4096, 65536 */
+void ccmp_shortcut_opts_default(ccmp_shortcut_opts *opts);
+int ccmp_path_shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
+                       size_t F, int max_len, const ccmp_shortcut_opts *opts, double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in,
+                       double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton, void *hip_stream);
+int ccmp_path_shortcut_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints,
+                            const int32_t *path_len, size_t F, int max_len, const ccmp_shortcut_opts *opts, double *out_joints, int32_t *out_len,
+                            int32_t *kept, double *cost_in, double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton);
+int ccmp_shortcut_select(ccmp_ctx *ctx, const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok,
+                         double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out, void *hip_stream);
+int ccmp_shortcut_select_host(ccmp_ctx *ctx, const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok,
+                              double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out);
+int ccmp_shortcut_select_ref(const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok, double *out_joints,
+                             int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out);
+int ccmp_shortcut_pairs_ref(const double *path_joints, const int32_t *path_len, size_t F, int max_len, int max_span, int32_t *triples, size_t capacity,
+                            size_t *count);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault
  * injection — are not part of this library: include/ccmp_debug.h, lib/libccmp_debug.so) */

@@ -493,6 +493,54 @@ inline int densifyPathLocked(const Projector &proj, std::vector<std::array<doubl
   return CCMP_OK;
 }
 
+// The removal of interior vertices from a solution path (include/ccmp.h: ccmp_path_shortcut_host): `states` = the waypoints on entry and
+// the kept waypoints on return — every pair (i, j) with 2 <= j - i <= max_span (0: every span) is put to one checkMotion(w_i, w_j), all
+// pairs in one batch, and the cheapest path from w_0 to w_{L-1} over the path's own edges and the pairs that passed is taken: the optimum
+// any sequence of PathSimplifier::reduceVertices removals could reach, deterministic.  kept (nullable) = the indices of the kept waypoints
+// in the path as it came in; cost_in / cost_out (nullable) = the joint length before and after.  delta / lambda > 0 replace the problem's.
+// A shortcut leaves the edges the host validated: interpolate the result and put the dense rows to the host's isValid.
+// Returns the library's code and leaves `states` untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int shortcutPathLocked(const Projector &proj, std::vector<std::array<double, 14>> &states, int max_span, std::vector<int32_t> *kept,
+                              double *cost_in, double *cost_out, double delta = 0.0, double lambda = 0.0)
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double), "rows are contiguous");
+  if (states.empty()) {
+    if (kept) kept->clear();
+    if (cost_in) *cost_in = 0.0;
+    if (cost_out) *cost_out = 0.0;
+    return CCMP_OK;
+  }
+  if (states.size() > (size_t)CCMP_SHORTCUT_MAX_LEN) return CCMP_EINVAL;
+  ccmp_problem P = proj.problem();
+  if (delta > 0.0) P.delta = delta;
+  if (lambda > 0.0) P.lambda = lambda;
+  ccmp_shortcut_opts o;
+  ccmp_shortcut_opts_default(&o);
+  o.max_span = max_span;
+  const int32_t len = (int32_t)states.size();
+  int32_t out_len = 0;
+  double ci = 0.0, co = 0.0;
+  std::vector<std::array<double, 14>> rows;
+  std::vector<int32_t> idx;
+  try {
+    rows.resize(states.size());
+    idx.assign(states.size(), -1);
+  } catch (...) {
+    return CCMP_ENOMEM;
+  }
+  const int rc = ccmp_path_shortcut_host(proj.ctx(), &P, nullptr, 0.0, states[0].data(), &len, 1, len, &o, rows[0].data(), &out_len, idx.data(), &ci, &co,
+                                         nullptr, nullptr, nullptr);
+  if (rc != CCMP_OK) return rc;
+  if (out_len < 0 || out_len > len) return CCMP_EHIP;
+  rows.resize((size_t)out_len);
+  idx.resize((size_t)out_len);
+  states.swap(rows);
+  if (kept) kept->swap(idx);
+  if (cost_in) *cost_in = ci;
+  if (cost_out) *cost_out = co;
+  return CCMP_OK;
+}
+
 // ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
 // The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
 // rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
@@ -806,6 +854,36 @@ public:
       if (cost) *cost = std::numeric_limits<double>::infinity();
     }
     return ran;
+  }
+
+  // constructSolution followed by the removal of interior vertices (ccmp::shortcutPathLocked above): `states` = the kept waypoints, cost =
+  // their joint length, indices = their vertices.  On a library error in the shortcut step the answer is the UNCHANGED solution path (true,
+  // with lastError() set): a planner that cannot simplify still has its path.  false with no states when no pair is connected or the
+  // solution step itself failed.  Interpolate the result (ccmp::densifyPathLocked) and validate the dense rows on the host.
+  bool constructShortcutSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states,
+                                 int max_span = 0, double *cost = nullptr, std::vector<int32_t> *indices = nullptr, double delta = 0.0,
+                                 double lambda = 0.0) const noexcept
+  {
+    std::vector<int32_t> path;
+    if (!constructSolution(starts, goals, states, cost, &path)) {
+      if (indices) indices->clear();
+      return false;
+    }
+    try {
+      std::vector<int32_t> kept;
+      double co = 0.0;
+      if (call([&] { return shortcutPathLocked(proj_, states, max_span, &kept, nullptr, &co, delta, lambda); }, "ccmp_path_shortcut_host")) {
+        std::vector<int32_t> idx(kept.size());
+        for (size_t k = 0; k < kept.size(); k++) idx[k] = path[(size_t)kept[k]];
+        path.swap(idx);
+        if (cost) *cost = co;
+      }
+      if (indices) indices->swap(path);
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::constructShortcutSolution");
+      if (indices) indices->clear();
+    }
+    return true;
   }
 
   int lastError() const noexcept { return err_code_; }
@@ -1634,6 +1712,20 @@ public:
       const ccmp::Projector &proj = chain_->impl();
       std::lock_guard<std::mutex> hold(proj.mutex());
       ccmp::check(ccmp::densifyPathLocked(proj, states, distinct, seg_ok, delta_, lambda_), "ccmp_path_densify_host");
+    });
+  }
+
+  // The removal of interior vertices from a solution path (ccmp::shortcutPathLocked: every pair of waypoints put to this space's
+  // checkMotion in one batch, then the cheapest path over the pairs that passed), under this space's delta and lambda: `states` = the
+  // waypoints on entry, the kept ones on return; kept (nullable) = their indices in the path as it came in.  On a library error the answer
+  // is the unchanged path: false, `states` as it was, the first error in KinematicChainConstraint::lastError().  Follow it with
+  // interpolatePath and the host's isValid over the dense rows: a shortcut leaves the edges the host validated.
+  bool shortcutPath(std::vector<std::array<double, 14>> &states, int max_span = 0, std::vector<int32_t> *kept = nullptr) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      ccmp::check(ccmp::shortcutPathLocked(proj, states, max_span, kept, nullptr, nullptr, delta_, lambda_), "ccmp_path_shortcut_host");
     });
   }
 

@@ -38,6 +38,8 @@
     python tools/measure.py dense [reps]                    dense solution paths (PathGeometric::interpolate): ccmp_path_densify against discrete_geodesic_batch +
                                                            continue_geodesics + the host join + the upload of the joined rows, one path and 64 paths of 32 waypoints,
                                                            both Jacobian modes, the extend calls made and the bytes that crossed to the host; writes profiles/dense_path.md
+    python tools/measure.py shortcut [reps]                 shortcut solution paths (vertex removal): ccmp_path_shortcut against check_target extend calls over all pairs, their
+                                                           continuation and the selection in numpy, 1 and 64 paths of 32 waypoints; writes profiles/shortcut.md
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -1235,6 +1237,125 @@ def dense(argv):
                 "synchronous route, the outputs compared while they are timed.  No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
 
 
+def shortcut(argv):
+    """ccmp_path_shortcut (KinematicChainConstraint.shortcut_paths: every pair of a path's waypoints put to checkMotion in one batch inside
+    the library, then the DAG search on the device) against the same work through the calls a caller had before it: the pairs enumerated on
+    the host, discrete_geodesic_batch(check_target=True) + continue_geodesics over all of them, the flags and the waypoints brought to the
+    host, the joint distances and the selection in numpy.  Paths of 32 waypoints out of a roadmap store: 64 chains of near-sampled
+    milestones appended with their chain edges, each path the store's shortest path between a chain's ends (seed 0x5C7); one path and 64
+    paths, both Jacobian modes, lists of 16 and a round budget of 128 on both routes; wall clock around each synchronous route, medians;
+    the outputs compared while they are timed.  Writes profiles/shortcut.md."""
+    import os
+
+    from closed_chain_motion_planner_amd import Roadmap
+
+    reps = int(argv[0]) if len(argv) > 0 else 15
+    Lw, cs, budget, seed = 32, 16, 128, 0x5C7
+    ctx = Context(0)
+    lines = []
+
+    def say(text):
+        print(text)
+        lines.append(text)
+
+    for mode in (0, 1):
+        c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+        cols = [c.sample_project_batch(seed, 0, 64, want_iters=False)[0]]
+        for j in range(1, Lw):
+            cols.append(c.sample_near_project_batch(seed + j, 0, cols[-1], 0.6, 64, want_iters=False)[0])
+        chains = torch.stack(cols, dim=1).contiguous()  # the FD constraint's samples for both modes
+        rm = Roadmap(c, capacity_hint=64 * Lw)
+        rm.append(chains.reshape(-1, 14).contiguous())
+        uv = np.array([(f * Lw + i, f * Lw + i + 1) for f in range(64) for i in range(Lw - 1)], dtype=np.int32)
+        rm.add_edges(torch.from_numpy(uv).cuda())
+        c.setJacobianMode(mode)
+        extend_sizes = []
+        plain = c.discrete_geodesic_batch
+
+        def logged(frm, to, *a, **k):
+            extend_sizes.append(frm.shape[0])
+            return plain(frm, to, *a, **k)
+
+        for F in (1, 64):
+            src = np.arange(F, dtype=np.int32) * Lw
+            sp = rm.shortest_paths(torch.from_numpy(src).cuda(), torch.from_numpy(src + Lw - 1).cuda(), max_len=Lw)
+            pj, pl = sp["joints"].contiguous(), sp["path_len"].contiguous()
+            assert pj.shape[1] == Lw and int(pl.min()) == Lw
+            ii, jj = np.triu_indices(Lw, 2)
+            E = F * len(ii)
+
+            def old_route():
+                wp = pj.cpu().numpy()  # the waypoints cross once: the weights are computed on the host
+                sel_f = np.repeat(np.arange(F), len(ii))
+                frm = pj[torch.from_numpy(sel_f).cuda(), torch.from_numpy(np.tile(ii, F)).cuda()].contiguous()
+                to = pj[torch.from_numpy(sel_f).cuda(), torch.from_numpy(np.tile(jj, F)).cuda()].contiguous()
+                c.discrete_geodesic_batch = logged
+                try:
+                    s, n, ok, its, carry = c.discrete_geodesic_batch(frm, to, cs, check_target=True, want_carry=True, round_budget=budget)
+                    cont = c.continue_geodesics(to, s, n, ok, its, carry, cs, round_budget=budget)
+                finally:
+                    del c.discrete_geodesic_batch
+                flag = ok.cpu().numpy().copy()
+                for e, v in cont.items():
+                    flag[e] = v[1]
+                okm = np.zeros((F, Lw, Lw), dtype=np.uint8)
+                okm[sel_f, np.tile(ii, F), np.tile(jj, F)] = flag
+                kept, cost = [], []
+                for f in range(F):  # the selection in numpy: one forward sweep, (cost, hops, index) lexicographic
+                    W = np.sqrt(((wp[f][:, None, :] - wp[f][None, :, :]) ** 2).sum(-1))
+                    d, h, pr = np.full(Lw, np.inf), np.zeros(Lw, dtype=np.int64), np.full(Lw, -1)
+                    d[0] = 0.0
+                    for j in range(1, Lw):
+                        adm = (okm[f, :j, j] == 1) | (np.arange(j) == j - 1)
+                        cnd = np.where(adm & np.isfinite(d[:j]), d[:j] + W[:j, j], np.inf)
+                        best = cnd.min()
+                        if np.isfinite(best):
+                            t = np.nonzero(cnd == best)[0]
+                            i = t[np.argmin(h[t])]
+                            d[j], h[j], pr[j] = best, h[i] + 1, i
+                    k, v = [], Lw - 1
+                    while v >= 0:
+                        k.append(v)
+                        v = pr[v]
+                    kept.append(k[::-1])
+                    cost.append(d[Lw - 1])
+                return okm, kept, cost
+
+            t_new, t_old, agree = [], [], True
+            for i in range(reps + 3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                new = c.shortcut_paths(pj, pl, chunk_states=cs, round_budget=budget, pairs=True)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                extend_sizes.clear()
+                okm, kept, cost = old_route()
+                t2 = time.perf_counter()
+                nk, nl = new["kept"].cpu().numpy(), new["out_len"].cpu().numpy()
+                agree = agree and np.array_equal(new["pair_ok"].cpu().numpy(), okm) and all(nk[f, : nl[f]].tolist() == kept[f] for f in range(F))
+                if i >= 3:
+                    t_new.append((t1 - t0) * 1e3)
+                    t_old.append((t2 - t1) * 1e3)
+            # bytes to the host.  new: path_len once, then n_states and ok of every open pair of every extend call.  old: the waypoints, the
+            # first call's flags, the open subset's lists, and every continuation call's lists, counts, flags and iterations
+            per_list = cs * 14 * 8
+            new_bytes = 4 * F + 5 * sum(extend_sizes)
+            old_bytes = F * Lw * 14 * 8 + E + (extend_sizes[1] if len(extend_sizes) > 1 else 0) * (per_list + 8) + sum(extend_sizes[1:]) * (per_list + 9)
+            say("%s mode, F = %d paths x %d waypoints (%d pairs tested, %d passed; %.1f waypoints kept per path); pair flags and kept vertices identical: %s"
+                % ("analytic" if mode else "FD", F, Lw, E, int(okm.sum()), float(np.mean([len(k) for k in kept])), agree))
+            say("    extend calls %d (open pairs per call: %s); bytes to the host: shortcut %d, old route %d"
+                % (len(extend_sizes), extend_sizes[:8] + (["..."] if len(extend_sizes) > 8 else []), new_bytes, old_bytes))
+            say("    %-84s %s" % ("ccmp_path_shortcut (pairs, flags and the search stay on the device)", _stat(t_new)))
+            say("    %-84s %s" % ("discrete_geodesic_batch(check_target) + continue_geodesics + selection in numpy", _stat(t_old)))
+        rm.close()
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "shortcut.md"), "w") as f:
+        f.write("# Shortcut solution paths on the device: `tools/measure.py shortcut`\n\n1 x MI355X, one run, seed 0x5C7; `ccmp_path_shortcut` against the same work through "
+                "the calls a caller had before it (pairs enumerated on the host, `discrete_geodesic_batch(check_target=True)` and its continuation over all pairs, "
+                "the selection in numpy) on the same waypoints, wall clock around each synchronous route, the outputs compared while they are timed.  "
+                "No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -1305,7 +1426,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, dense, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, dense, shortcut, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
