@@ -54,9 +54,14 @@ __device__ __forceinline__ double sphere_pair_d2(const double *cen, int lane, un
 }
 // One pair against the running minimum.  The signed distance sqrt(d2) - rsum can only become the minimum (ties keep
 // the earlier pair) if sqrt(d2) < best + rsum; a pair that is further than that by a nanometre is dropped on its
-// squared distance — the margin is 1e6 times the rounding of the four operations involved — and the square root, ten
-// dependent operations, runs only when some lane of the wavefront still needs it: after the first few pairs of a state
-// almost never.  Pairs that do run are computed exactly as before, so the result is unchanged bit for bit.
+// squared distance, and the square root, ten dependent operations, runs only when some lane of the wavefront still needs
+// it: after the first few pairs of a state almost never.  Pairs that do run are computed exactly as before, so the result
+// is unchanged bit for bit — WHILE best + rsum < 2^22 (metres), which ccmp_scene.cpp: clearance_magnitude_bound guarantees for
+// every scene that reaches this kernel (the others take clearance_state_kernel).  Proof: below 2^22 the two roundings of
+// t = fl(fl(best + rsum) + 1e-9) are at most 2^-32 each, 4.7e-10 together, so t > best + rsum exactly (t <= 0 implies
+// best + rsum < 0 <= sqrt(d2) at any magnitude).  And d2 > fl(t t) implies fl(sqrt(d2)) >= fl(sqrt(fl(t t))) = t, so the pair's
+// sqrt(d2) - rsum >= t - rsum > best before rounding and >= best after it: never a new minimum.  From 2^23 on the rounding of
+// best + rsum alone exceeds the nanometre and pairs that would become the minimum are dropped (tests/test_scene_cases.py).
 __device__ __forceinline__ void consider_pair(double d2, double rsum, int p, double &best, int &bestp)
 {
   const double t = (best + rsum) + 1e-9;

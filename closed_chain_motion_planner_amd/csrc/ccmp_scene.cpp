@@ -23,6 +23,38 @@ bool pair_allowed(const uint32_t *allowed, int g, int h)
 {
   return allowed && ((((allowed[g] >> h) & 1u) != 0) || (((allowed[h] >> g) & 1u) != 0));
 }
+double norm_n(const double *v, int n)
+{
+  double s = 0.0;
+  for (int k = 0; k < n; k++) s += v[k] * v[k];
+  return std::sqrt(s);
+}
+
+// The tile kernel drops a pair on its squared distance (ccmp_kernels_scene.hip: consider_pair); that is exact only while
+// best + rsum < 2^22.  An upper bound of that sum over every state: best is +inf (nothing is dropped) or an earlier pair's
+// distance less its radii, so best + rsum <= D + rsum_max, D the largest distance between the centres of two tested proxies.
+// Rotations keep lengths, so a sphere on a body or a hand lies within |base_p| + |base_R|_F (sum |offset_i| + |ee| + |c|) of the
+// origin whatever the joints, one on a base within |base_p| + |base_R|_F |c|, a world sphere within |c|; with `reach` the largest
+// of these D <= 2 reach between spheres and D <= max(1, |R|_F) (reach + |box centre|) to a box (its half extents only shorten the
+// distance).  Rounding along the chain and a rotation's half-ulp departures from an isometry are covered by the factor of two
+// between 2^22 and the 2^23 at which the prune's own argument ends.  +inf or NaN (centres near DBL_MAX) count as beyond.
+constexpr double kPruneLimit = 4194304.0; // 2^22
+double clearance_magnitude_bound(const ccmp_problem &p, const ccmp_scene &sc)
+{
+  double reach = sc.c_world > 0.0 ? sc.c_world : 0.0;
+  for (int arm = 0; arm < 2; arm++) {
+    const double bp = norm_n(p.base_p[arm], 3), gain = norm_n(p.base_R[arm], 9);
+    if (sc.c_base[arm] >= 0.0 && !(bp + gain * sc.c_base[arm] <= reach)) reach = bp + gain * sc.c_base[arm];
+    if (sc.c_moving[arm] >= 0.0) {
+      double chain = norm_n(p.ee[arm], 3) + sc.c_moving[arm];
+      for (int i = 0; i < 7; i++) chain += norm_n(p.offset[arm][i], 3);
+      if (!(bp + gain * chain <= reach)) reach = bp + gain * chain;
+    }
+  }
+  double d = 2.0 * reach;
+  if (sc.host.n_boxes > 0 && !(sc.box_gain * (reach + sc.box_c) <= d)) d = sc.box_gain * (reach + sc.box_c);
+  return d + sc.rsum_max;
+}
 
 }  // namespace
 
@@ -100,6 +132,20 @@ int ccmp_scene_create(ccmp_ctx *ctx, const ccmp_sphere *spheres, int n_spheres, 
       np++;
     }
   H.n_pairs = np;
+  // the scene's share of clearance_magnitude_bound
+  for (int i = 0; i < n_spheres; i++) {
+    const int f = spheres[i].frame;
+    double &m = f < 0 ? sc->c_world : (f % 9 == 8 ? sc->c_base[f / 9] : sc->c_moving[f / 9]);
+    const double c = norm_n(spheres[i].c, 3);
+    if (!(c <= m)) m = c;
+  }
+  for (int k = 0; k < np; k++)
+    if (H.pair_rsum[k] > sc->rsum_max) sc->rsum_max = H.pair_rsum[k];
+  for (int b = 0; b < n_boxes; b++) {
+    const double c = norm_n(boxes[b].c, 3), g = norm_n(boxes[b].R, 9);
+    if (!(c <= sc->box_c)) sc->box_c = c;
+    if (!(g <= sc->box_gain)) sc->box_gain = g;
+  }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) { delete sc; return CCMP_ENODEV; }
   ccmp_host::quiesce(ctx);
@@ -139,7 +185,9 @@ int ccmp_clearance_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene 
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_consts K;
   make_consts(*p, K);
-  if (B <= ctx->clearance_per_state_max) {
+  // beyond the domain of the tile kernel's prune (a wall or a floor modelled as one huge sphere): the one-block kernel, which has none
+  const bool in_prune_domain = clearance_magnitude_bound(*p, *scene) < kPruneLimit;
+  if (B <= ctx->clearance_per_state_max || !in_prune_domain) {
     // small batches: one block per state (the parallelism of a single state; what a validity-checker wrapper calls)
     size_t blocks = B;
     const size_t cap = (size_t)ctx->num_cus * 8;

@@ -38,6 +38,11 @@ struct ccmp_scene {
   ccmp_ctx *ctx = nullptr; // the context the scene was created on: its resident service kernel is stopped before the scene's hipFree (ccmp_resident.h rule 2); the context must outlive the scene or be destroyed first with the service off
   ccmp::scene_dev host;
   ccmp::scene_dev *dev = nullptr;
+  // The scene's share of the bound on `best + rsum` (ccmp_scene.cpp: clearance_magnitude_bound; the tile kernel's prune holds below
+  // 2^22 only): the largest |centre| of the spheres on each kind of frame, in that frame (-1: none there), the largest pair_rsum,
+  // and over the boxes the largest |centre| and the largest max(1, |R|_F)
+  double c_world = -1.0, c_base[2] = {-1.0, -1.0}, c_moving[2] = {-1.0, -1.0};
+  double rsum_max = 0.0, box_c = 0.0, box_gain = 1.0;
 };
 
 #endif /* CCMP_SCENE_H */

@@ -461,7 +461,14 @@ typedef struct ccmp_box { /* static, oriented, in the world frame */
 typedef struct ccmp_scene ccmp_scene;
 /* allowed[g] bit h set = pairs between groups g and h are never tested (either direction counts; NULL = nothing allowed).
  * Never tested either: two proxies on the same frame, and two proxies that are both static (world or an arm's base).
- * Pairs are numbered sphere i < sphere j in the caller's order first, then (sphere i, box b). */
+ * Pairs are numbered sphere i < sphere j in the caller's order first, then (sphere i, box b).
+ * Any finite centre and radius is accepted.  The 64-state tile kernel of ccmp_clearance_batch prunes pairs on their squared
+ * distance, which is exact only while (running minimum + a pair's radii) < 2^22 m: the two roundings of that sum plus the
+ * prune's nanometre stay below the nanometre there, so a pruned pair provably cannot become the minimum.  The host bounds that
+ * sum from the arms' reach (base position, link offsets, tool), the largest sphere centre and radii and the boxes' centres
+ * (ccmp_scene.cpp: clearance_magnitude_bound); a scene whose bound is not below 2^22 — a wall or a floor modelled as one huge
+ * sphere — is served by the one-block-per-state kernel, which does not prune, whatever B and "clearance_per_state_max" say:
+ * the same bits as the oracle, at that kernel's speed. */
 int ccmp_scene_create(ccmp_ctx *ctx, const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes,
                       const uint32_t allowed[32], ccmp_scene **out);
 void ccmp_scene_destroy(ccmp_scene *scene);
