@@ -18,6 +18,7 @@
 #include "ccmp_launch.h"
 #include "ccmp_resident.h"
 #include "ccmp_scene.h"
+#include "ccmp_stage.h"
 
 using namespace ccmp_host;
 using ccmp::dense_chunk;
@@ -38,52 +39,7 @@ struct ccmp_dense_paths {
 namespace {
 
 constexpr size_t kMaxRows = ((size_t)1 << 31) - 1; // rows and slots are int32
-constexpr size_t kArenaBlock = (size_t)4 << 20;
-
-// a context needs a device: without one that is the reason a call has no context (CCMP_ENODEV); with one it is an argument error
-int no_ctx()
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CCMP_ENODEV; }
-  return CCMP_EINVAL;
-}
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// the device memory of one call: every extend call's buffers live until the pack has run, then all of it goes at once
-struct Arena {
-  ccmp_ctx *ctx;
-  std::vector<void *> blocks;
-  char *cur = nullptr;
-  size_t left = 0;
-  explicit Arena(ccmp_ctx *c) : ctx(c) {}
-  Arena(const Arena &) = delete;
-  Arena &operator=(const Arena &) = delete;
-  void *get(size_t bytes)
-  {
-    bytes = align256(bytes ? bytes : 1);
-    if (bytes > left) {
-      const size_t sz = bytes > kArenaBlock ? bytes : kArenaBlock;
-      void *b = nullptr;
-      ccmp_host::quiesce(ctx);
-      const hipError_t e = hipMalloc(&b, sz);
-      if (e != hipSuccess) { (void)hip_fail(e, "ccmp_path_densify: hipMalloc"); return nullptr; }
-      blocks.push_back(b);
-      cur = (char *)b;
-      left = sz;
-    }
-    void *r = cur;
-    cur += bytes;
-    left -= bytes;
-    return r;
-  }
-  ~Arena()
-  {
-    if (blocks.empty()) return;
-    ccmp_host::quiesce(ctx);
-    for (void *b : blocks) (void)hipFree(b); // waits for whatever still reads it
-  }
-};
+constexpr const char *kArenaWhat = "ccmp_path_densify: hipMalloc";
 
 // The layout rule on the host (ccmp_dense.h): what ccmp_dense_layout_ref answers and what the device call lays its result out by.
 int layout(const int32_t *path_len, size_t F, int max_len, const int32_t *seg_states, int distinct, int32_t *path_first, int32_t *seg_first, size_t *rows)
@@ -129,13 +85,6 @@ int densify_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene 
   if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
   if (F > 0 && (!path_joints || !path_len || max_len < 1)) return CCMP_EINVAL;
   if (F > 0 && F > kMaxRows / (size_t)max_len) return CCMP_EINVAL;
-  return CCMP_OK;
-}
-
-int lens_ok(const int32_t *len, size_t F, int max_len)
-{
-  for (size_t f = 0; f < F; f++)
-    if (len[f] < 0 || len[f] > max_len) return CCMP_EINVAL;
   return CCMP_OK;
 }
 
@@ -205,7 +154,7 @@ int densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, doubl
   std::vector<uint8_t> seg_ok(slots, 0);
   std::vector<HostChunk> pieces;
   std::vector<Round> rounds; // kept whole until the end: their host arrays back uploads, their device arrays are the chunks
-  Arena arena(ctx);
+  CallArena arena(ctx, kArenaWhat); // every extend call's buffers live until the pack has run, then all of it goes at once
   int calls = 0;
 
   Round first;
@@ -226,15 +175,15 @@ int densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, doubl
     Round &r = rounds.back();
     const Round *prev = rounds.size() > 1 ? &rounds[rounds.size() - 2] : nullptr;
     const size_t E = r.open.size();
-    dense_open_seg *d_open = (dense_open_seg *)arena.get(E * sizeof(dense_open_seg));
-    double *from = (double *)arena.get(E * 14 * sizeof(double)), *to = (double *)arena.get(E * 14 * sizeof(double));
-    double *carry_in = prev ? (double *)arena.get(E * 2 * sizeof(double)) : nullptr;
-    r.states = (double *)arena.get(E * (size_t)cs * 14 * sizeof(double));
-    r.carry = (double *)arena.get(E * 2 * sizeof(double));
-    r.n = (int32_t *)arena.get(E * sizeof(int32_t));
-    r.its = (int32_t *)arena.get(E * sizeof(int32_t));
-    r.ok = (uint8_t *)arena.get(E);
-    if (!d_open || !from || !to || (prev && !carry_in) || !r.states || !r.carry || !r.n || !r.its || !r.ok) { (void)hipStreamSynchronize(st); return CCMP_EHIP; }
+    dense_open_seg *d_open = arena.array<dense_open_seg>(E);
+    double *from = arena.array<double>(E * 14), *to = arena.array<double>(E * 14);
+    double *carry_in = prev ? arena.array<double>(E * 2) : nullptr;
+    r.states = arena.array<double>(E * (size_t)cs * 14);
+    r.carry = arena.array<double>(E * 2);
+    r.n = arena.array<int32_t>(E);
+    r.its = arena.array<int32_t>(E);
+    r.ok = arena.array<uint8_t>(E);
+    if (!arena.ok()) { (void)hipStreamSynchronize(st); return CCMP_EHIP; }
     hipError_t e = hipMemcpyAsync(d_open, r.open.data(), E * sizeof(dense_open_seg), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = ccmp_launch::dense_gather(d_open, E, path_joints, prev ? prev->states : nullptr, cs, prev ? prev->carry : nullptr, from, to, carry_in, st);
     int rc = CCMP_OK;
@@ -296,7 +245,7 @@ int densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, doubl
   if (e == hipSuccess && slots) e = hipMemcpyAsync(h->seg_ok, seg_ok.data(), slots, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && slots) e = hipMemsetAsync(h->seg_newton, 0, slots * sizeof(int32_t), st);
   if (e == hipSuccess && !chunks.empty()) {
-    dense_chunk *d_chunks = (dense_chunk *)arena.get(chunks.size() * sizeof(dense_chunk));
+    dense_chunk *d_chunks = arena.array<dense_chunk>(chunks.size());
     if (!d_chunks) rc = CCMP_EHIP;
     if (rc == CCMP_OK) e = hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(dense_chunk), hipMemcpyHostToDevice, st);
     if (rc == CCMP_OK && e == hipSuccess) e = ccmp_launch::dense_pack(d_chunks, chunks.size(), h->d_rows, rows, h->seg_newton, slots, st);
@@ -331,7 +280,7 @@ int ccmp_path_densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *sc
                       size_t F, int max_len, const ccmp_dense_opts *opts, ccmp_dense_paths **out, void *hip_stream)
 {
   if (out) *out = nullptr;
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   if (!out) return CCMP_EINVAL;
   ccmp_dense_opts o;
   ccmp_dense_opts_default(&o);
@@ -356,7 +305,7 @@ int ccmp_path_densify_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scen
                            const int32_t *path_len, size_t F, int max_len, const ccmp_dense_opts *opts, ccmp_dense_paths **out)
 {
   if (out) *out = nullptr;
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   if (!out) return CCMP_EINVAL;
   ccmp_dense_opts o;
   ccmp_dense_opts_default(&o);
@@ -365,20 +314,18 @@ int ccmp_path_densify_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scen
   if (F) { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = ctx->stream;
-  Arena up(ctx); // the uploaded waypoints; released when the call returns (the result holds its own rows)
-  const double *d_joints = nullptr;
+  CallArena mem(ctx, kArenaWhat); // the uploaded waypoints; released when the call returns (the result holds its own rows)
+  double *d_joints = nullptr;
   if (F) {
-    const size_t bytes = F * (size_t)max_len * 14 * sizeof(double);
-    void *d = up.get(bytes);
-    if (!d) return CCMP_EHIP;
-    const hipError_t e = hipMemcpyAsync(d, path_joints, bytes, hipMemcpyHostToDevice, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-    d_joints = (const double *)d;
+    const size_t n = F * (size_t)max_len * 14;
+    d_joints = mem.array<double>(n);
+    if (!mem.ok()) return CCMP_EHIP;
+    StagedCall sg(ctx, __func__);
+    sg.up(d_joints, path_joints, n * sizeof(double));
+    const int rc = sg.finish(CCMP_OK);
+    if (rc != CCMP_OK) return rc;
   }
-  return densify(ctx, p, scene, margin, d_joints, std::vector<int32_t>(path_len, path_len + F), F, max_len, o, out, st);
+  return densify(ctx, p, scene, margin, d_joints, std::vector<int32_t>(path_len, path_len + F), F, max_len, o, out, ctx->stream);
 }
 
 int ccmp_dense_paths_info(const ccmp_dense_paths *h, size_t *F, int *max_len, size_t *rows, int *calls)
@@ -412,7 +359,7 @@ static int dense_copy(ccmp_dense_paths *h, double *rows_out, int32_t *path_first
 int ccmp_dense_paths_copy(ccmp_dense_paths *h, double *rows_out, int32_t *path_first, int32_t *seg_first, uint8_t *seg_ok, int32_t *seg_newton, double *arc,
                           double *length, double *clearance, double *min_clear, int32_t *min_row, int32_t *first_blocked, void *hip_stream)
 {
-  if (!h) return no_ctx();
+  if (!h) return no_handle();
   if (!h->has_scene && (clearance || min_clear || min_row || first_blocked)) return CCMP_EINVAL;
   DeviceGuard guard(h->device);
   if (!guard.ok) return CCMP_ENODEV;
@@ -423,18 +370,15 @@ int ccmp_dense_paths_copy(ccmp_dense_paths *h, double *rows_out, int32_t *path_f
 int ccmp_dense_paths_copy_host(ccmp_dense_paths *h, double *rows_out, int32_t *path_first, int32_t *seg_first, uint8_t *seg_ok, int32_t *seg_newton,
                                double *arc, double *length, double *clearance, double *min_clear, int32_t *min_row, int32_t *first_blocked)
 {
-  if (!h) return no_ctx();
+  if (!h) return no_handle();
   if (!h->has_scene && (clearance || min_clear || min_row || first_blocked)) return CCMP_EINVAL;
   if (!ccmp_host::context_alive(h->ctx)) return CCMP_EINVAL;
   DeviceGuard guard(h->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = h->ctx->stream;
+  StagedCall sg(h->ctx, __func__); // nothing staged: the copies (one list for both forms, dense_copy) come straight from the result
   const int rc = dense_copy(h, rows_out, path_first, seg_first, seg_ok, seg_newton, arc, length, clearance, min_clear, min_row, first_blocked,
-                            hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(es);
-  return CCMP_OK;
+                            hipMemcpyDeviceToHost, h->ctx->stream);
+  return sg.finish(rc);
 }
 
 void ccmp_dense_paths_destroy(ccmp_dense_paths *h)

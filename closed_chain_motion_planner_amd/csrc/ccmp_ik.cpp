@@ -14,18 +14,11 @@
 #include "ccmp_host.h"
 #include "ccmp_ik.h"
 #include "ccmp_launch.h"
+#include "ccmp_stage.h"
 
 using namespace ccmp_host;
 
 namespace {
-
-// what an entry point answers when it is given no context: a context needs a device, so on a machine without one that is the reason
-int no_ctx()
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CCMP_ENODEV; }
-  return CCMP_EINVAL;
-}
 
 bool positive(double v) { return std::isfinite(v) && v > 0.0; }
 
@@ -138,7 +131,7 @@ int ccmp_pose_ik_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts 
                        uint64_t rng_seed, uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds,
                        void *hip_stream)
 {
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   ccmp::ik_params P;
   { const int rc = ik_checks(p, opts, T, S, &P); if (rc != CCMP_OK) return rc; }
   if (T == 0) return CCMP_OK;
@@ -153,41 +146,33 @@ int ccmp_pose_ik_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts 
 int ccmp_pose_ik_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
                       uint64_t rng_seed, uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds)
 {
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   ccmp::ik_params P;
   { const int rc = ik_checks(p, opts, T, S, &P); if (rc != CCMP_OK) return rc; }
   if (T == 0) return CCMP_OK;
   if (!target_poses || !seeds || !q_out || !ok || !which) return CCMP_EINVAL;
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = ctx->stream;
-  const size_t C = ik_candidates(T, S, P);
-  const size_t sizes[7] = {T * 8 * sizeof(double), T * (size_t)S * 14 * sizeof(double), T * 14 * sizeof(double), T * sizeof(int32_t), T,
-                           cand_q ? C * 7 * sizeof(double) : 0, cand_rounds ? C * sizeof(int32_t) : 0};
-  size_t off[7], total = 0;
-  for (int i = 0; i < 7; i++) { off[i] = total; total = (total + sizes[i] + 255) & ~(size_t)255; }
-  { const int rc = ensure_stage(ctx, total ? total : 256); if (rc != CCMP_OK) return rc; }
+  const size_t C = ik_candidates(T, S, P), pb = T * 8 * sizeof(double), sb = T * (size_t)S * 14 * sizeof(double);
+  StagedCall sg(ctx, __func__);
+  const size_t off_p = sg.add(pb), off_s = sg.add(sb), off_q = sg.add(T * 14 * sizeof(double)), off_w = sg.add(T * sizeof(int32_t)), off_ok = sg.add(T),
+               off_cq = sg.add(cand_q ? C * 7 * sizeof(double) : 0), off_cr = sg.add(cand_rounds ? C * sizeof(int32_t) : 0);
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; } // the staging block has its size before the candidates' workspace
   { const int rc = ik_reserve(ctx, C); if (rc != CCMP_OK) return rc; }
-  char *sg = (char *)ctx->stage;
-  HIP_TRY(hipMemcpyAsync(sg + off[0], target_poses, sizes[0], hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(sg + off[1], seeds, sizes[1], hipMemcpyHostToDevice, st));
-  const int rc = ik_launches(ctx, p, P, (const double *)(sg + off[0]), (const double *)(sg + off[1]), T, S, rng_seed, first_index, (double *)(sg + off[2]),
-                             (uint8_t *)(sg + off[4]), (int32_t *)(sg + off[3]), cand_q ? (double *)(sg + off[5]) : nullptr,
-                             cand_rounds ? (int32_t *)(sg + off[6]) : nullptr, st);
-  hipError_t e = hipSuccess;
-  auto down = [&](void *dst, int i) { if (dst && e == hipSuccess) e = hipMemcpyAsync(dst, sg + off[i], sizes[i], hipMemcpyDeviceToHost, st); };
+  sg.up(off_p, target_poses, pb);
+  sg.up(off_s, seeds, sb);
+  int rc = CCMP_OK;
+  if (sg.copy_ok())
+    rc = ik_launches(ctx, p, P, sg.at<const double>(off_p), sg.at<const double>(off_s), T, S, rng_seed, first_index, sg.at<double>(off_q), sg.at<uint8_t>(off_ok),
+                     sg.at<int32_t>(off_w), sg.at<double>(off_cq, cand_q), sg.at<int32_t>(off_cr, cand_rounds), ctx->stream);
   if (rc == CCMP_OK) {
-    down(q_out, 2);
-    down(which, 3);
-    down(ok, 4);
-    down(cand_q, 5);
-    down(cand_rounds, 6);
+    sg.down(q_out, off_q, T * 14 * sizeof(double));
+    sg.down(which, off_w, T * sizeof(int32_t));
+    sg.down(ok, off_ok, T);
+    sg.down(cand_q, off_cq, C * 7 * sizeof(double));
+    sg.down(cand_rounds, off_cr, C * sizeof(int32_t));
   }
-  const hipError_t es = hipStreamSynchronize(st); // also on the error path: the staging block must be quiet
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  return sg.finish(rc); // waits on the error path too: the staging block must be quiet
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include "ccmp_launch.h"
 #include "ccmp_object.h"
 #include "ccmp_resident.h"
+#include "ccmp_stage.h"
 
 using namespace ccmp_host;
 
@@ -28,13 +29,6 @@ struct ccmp_object {
 };
 
 namespace {
-
-int no_ctx()
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CCMP_ENODEV; }
-  return CCMP_EINVAL;
-}
 
 // the mesh and the boxes of a create / _ref call -> what the kernels take
 int object_checks(const double *tri, int M, const ccmp_box *boxes, int n_boxes, ccmp::object_boxes *B, ccmp::object_sphere *S)
@@ -107,7 +101,7 @@ ccmp_launch::ObjectCall call_of(const ccmp_object *o) { return ccmp_launch::Obje
 // what every device form checks about its handles; CCMP_OK or the code to return
 int handles_ok(const ccmp_ctx *ctx, const ccmp_object *obj)
 {
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   if (!obj || obj->device != ctx->device) return CCMP_EINVAL;
   return CCMP_OK;
 }
@@ -131,7 +125,7 @@ int ccmp_object_create(ccmp_ctx *ctx, const double *tri, int M, const ccmp_box *
   ccmp_object *o = new (std::nothrow) ccmp_object();
   if (!o) return CCMP_ENOMEM;
   { const int rc = object_checks(tri, M, boxes, n_boxes, &o->boxes, &o->sphere); if (rc != CCMP_OK) { delete o; return rc; } }
-  if (!ctx) { delete o; return no_ctx(); }
+  if (!ctx) { delete o; return no_handle(); }
   o->device = ctx->device;
   o->M = M;
   o->n_boxes = n_boxes;
@@ -211,21 +205,15 @@ int ccmp_object_valid_host(ccmp_ctx *ctx, const ccmp_object *obj, const double *
   if (!poses || !valid) return CCMP_EINVAL;
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = ctx->stream;
-  const size_t sizes[3] = {T * 8 * sizeof(double), hit_mask ? T * sizeof(uint32_t) : 0, T};
-  size_t off[3], total = 0;
-  for (int i = 0; i < 3; i++) { off[i] = total; total = (total + sizes[i] + 255) & ~(size_t)255; }
-  { const int rc = ensure_stage(ctx, total); if (rc != CCMP_OK) return rc; }
-  char *sg = (char *)ctx->stage;
-  HIP_TRY(hipMemcpyAsync(sg + off[0], poses, sizes[0], hipMemcpyHostToDevice, st));
-  hipError_t e = ccmp_launch::object_valid(call_of(obj), (const double *)(sg + off[0]), T, inflate, (uint8_t *)(sg + off[2]),
-                                           hit_mask ? (uint32_t *)(sg + off[1]) : nullptr, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(valid, sg + off[2], sizes[2], hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && hit_mask) e = hipMemcpyAsync(hit_mask, sg + off[1], sizes[1], hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st); // also on the error path: the staging block must be quiet
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  StagedCall sg(ctx, __func__);
+  const size_t off_p = sg.add(T * 8 * sizeof(double)), off_m = sg.add(hit_mask ? T * sizeof(uint32_t) : 0), off_v = sg.add(T);
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
+  sg.up(off_p, poses, T * 8 * sizeof(double));
+  if (sg.copy_ok())
+    sg.note(ccmp_launch::object_valid(call_of(obj), sg.at<const double>(off_p), T, inflate, sg.at<uint8_t>(off_v), sg.at<uint32_t>(off_m, hit_mask), ctx->stream));
+  sg.down(valid, off_v, T);
+  sg.down(hit_mask, off_m, T * sizeof(uint32_t));
+  return sg.finish(CCMP_OK); // waits on the error path too: the staging block must be quiet
 }
 
 int ccmp_object_propose_ref(const double *tri, int M, const ccmp_box *boxes, int n_boxes, const double *from_poses, const double *to_poses, int to_stride,
@@ -293,28 +281,21 @@ int ccmp_object_propose_host(ccmp_ctx *ctx, const ccmp_object *obj, const double
   if (!from_poses || !to_poses || !pose_out || !which) return CCMP_EINVAL;
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = ctx->stream;
-  const size_t C = G * (size_t)attempts;
-  const size_t sizes[6] = {G * 8 * sizeof(double), (to_stride ? G : 1) * 8 * sizeof(double), G * 8 * sizeof(double), G * sizeof(int32_t),
-                           cand_pose ? C * 8 * sizeof(double) : 0, cand_valid ? C : 0};
-  size_t off[6], total = 0;
-  for (int i = 0; i < 6; i++) { off[i] = total; total = (total + sizes[i] + 255) & ~(size_t)255; }
-  { const int rc = ensure_stage(ctx, total); if (rc != CCMP_OK) return rc; }
-  char *sg = (char *)ctx->stage;
-  HIP_TRY(hipMemcpyAsync(sg + off[0], from_poses, sizes[0], hipMemcpyHostToDevice, st));
-  hipError_t e = hipMemcpyAsync(sg + off[1], to_poses, sizes[1], hipMemcpyHostToDevice, st);
-  if (e == hipSuccess)
-    e = ccmp_launch::object_propose(call_of(obj), D, (const double *)(sg + off[0]), (const double *)(sg + off[1]), G, (double *)(sg + off[2]),
-                                    (int32_t *)(sg + off[3]), cand_pose ? (double *)(sg + off[4]) : nullptr, cand_valid ? (uint8_t *)(sg + off[5]) : nullptr, st);
-  auto down = [&](void *dst, int i) { if (dst && e == hipSuccess) e = hipMemcpyAsync(dst, sg + off[i], sizes[i], hipMemcpyDeviceToHost, st); };
-  down(pose_out, 2);
-  down(which, 3);
-  down(cand_pose, 4);
-  down(cand_valid, 5);
-  const hipError_t es = hipStreamSynchronize(st); // also on the error path: the staging block must be quiet
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  const size_t C = G * (size_t)attempts, gb = G * 8 * sizeof(double), tb = (to_stride ? G : 1) * 8 * sizeof(double); // stride 0: one target for all
+  StagedCall sg(ctx, __func__);
+  const size_t off_f = sg.add(gb), off_t = sg.add(tb), off_o = sg.add(gb), off_w = sg.add(G * sizeof(int32_t)), off_cp = sg.add(cand_pose ? C * 8 * sizeof(double) : 0),
+               off_cv = sg.add(cand_valid ? C : 0);
+  { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
+  sg.up(off_f, from_poses, gb);
+  sg.up(off_t, to_poses, tb);
+  if (sg.copy_ok())
+    sg.note(ccmp_launch::object_propose(call_of(obj), D, sg.at<const double>(off_f), sg.at<const double>(off_t), G, sg.at<double>(off_o), sg.at<int32_t>(off_w),
+                                        sg.at<double>(off_cp, cand_pose), sg.at<uint8_t>(off_cv, cand_valid), ctx->stream));
+  sg.down(pose_out, off_o, gb);
+  sg.down(which, off_w, G * sizeof(int32_t));
+  sg.down(cand_pose, off_cp, C * 8 * sizeof(double));
+  sg.down(cand_valid, off_cv, C);
+  return sg.finish(CCMP_OK); // waits on the error path too: the staging block must be quiet
 }
 
 }  // extern "C"

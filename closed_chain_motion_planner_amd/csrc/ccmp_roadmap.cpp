@@ -29,6 +29,7 @@
 #include "ccmp_pose.h"
 #include "ccmp_resident.h"
 #include "ccmp_scene.h"
+#include "ccmp_stage.h"
 
 using namespace ccmp_host;
 
@@ -60,15 +61,6 @@ namespace {
 
 constexpr size_t kDefaultCapacity = 1024;
 constexpr size_t kMaxNodes = ((size_t)1 << 31) - 1; // indices are int32
-
-// what an entry point answers when it is given no store: a store needs a context and a context needs a device, so on a machine
-// without one that is the reason (CCMP_ENODEV); with a device a NULL store is an argument error
-int no_store()
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CCMP_ENODEV; }
-  return CCMP_EINVAL;
-}
 
 // Moves the store into a block of new_cap rows.  st != nullptr-able: the copy is ordered behind what `st` holds and `st` is waited
 // for once before the old block goes; sync_device: the whole device is waited for first instead (ccmp_roadmap_reserve has no stream).
@@ -231,7 +223,7 @@ int32_t *path_pred(const ccmp_roadmap *rm) { return (int32_t *)(path_d(rm) + rm-
 
 int knn_checks(const ccmp_roadmap *rm, int metric, const void *queries, size_t Q, int k, int mode, const int32_t *nbr_idx)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (metric != CCMP_METRIC_JOINT && metric != CCMP_METRIC_OBJECT) return CCMP_EINVAL;
   if (k < 1 || k > CCMP_KNN_MAX_K || mode < CCMP_KNN_ALL || mode > CCMP_KNN_EARLIER || Q >= ((size_t)1 << 31)) return CCMP_EINVAL;
   if (Q > 0 && (!queries || !nbr_idx)) return CCMP_EINVAL;
@@ -247,16 +239,6 @@ int knn_object(ccmp_roadmap *rm, const double *poses, size_t Q, int k, int mode,
   HIP_TRY(ccmp_launch::knn_pose(ccmp_launch::KnnCall{rm->poses, rm->size, poses, Q, k, mode, self_base, nbr_idx, nbr_dist}, s, ctx->knn_ws, st));
   return CCMP_OK;
 }
-
-// a host call's scratch on the device: the context's staging block, cut into 256-byte aligned pieces
-struct Stage {
-  ccmp_ctx *ctx;
-  size_t total = 0;
-  explicit Stage(ccmp_ctx *c) : ctx(c) {}
-  size_t add(size_t bytes) { const size_t off = total; total = (total + bytes + 255) & ~(size_t)255; return off; }
-  int alloc() { return ensure_stage(ctx, total ? total : 256); }
-  char *at(size_t off) const { return (char *)ctx->stage + off; }
-};
 
 }  // namespace
 
@@ -308,7 +290,7 @@ size_t ccmp_roadmap_size(const ccmp_roadmap *rm) { return rm ? rm->size : 0; }
 
 int ccmp_roadmap_reserve(ccmp_roadmap *rm, size_t n)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (n > kMaxNodes) return CCMP_EINVAL;
   if (n <= rm->cap) return CCMP_OK;
   DeviceGuard guard(rm->device);
@@ -319,7 +301,7 @@ int ccmp_roadmap_reserve(ccmp_roadmap *rm, size_t n)
 int ccmp_roadmap_append(ccmp_roadmap *rm, const ccmp_problem *p, const double *joints, const double *poses, size_t Q, size_t *first_index,
                         void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first_index) *first_index = rm->size;
   if (Q == 0) return CCMP_OK;
   if ((!joints && !poses) || Q > kMaxNodes - rm->size) return CCMP_EINVAL;
@@ -348,7 +330,7 @@ int ccmp_roadmap_append(ccmp_roadmap *rm, const ccmp_problem *p, const double *j
 
 int ccmp_roadmap_set_joints(ccmp_roadmap *rm, size_t index, const double *joints, void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (!joints || index >= rm->size) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
@@ -358,7 +340,7 @@ int ccmp_roadmap_set_joints(ccmp_roadmap *rm, size_t index, const double *joints
 
 int ccmp_roadmap_truncate(ccmp_roadmap *rm, size_t n)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (n > rm->size || n < rm->floor) return CCMP_EINVAL; // a vertex with an edge stays (the reference removes only vertices without one)
   rm->size = n;
   return CCMP_OK;
@@ -366,7 +348,7 @@ int ccmp_roadmap_truncate(ccmp_roadmap *rm, size_t n)
 
 int ccmp_roadmap_read(ccmp_roadmap *rm, size_t first, size_t count, double *joints_out, double *poses_out, void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first > rm->size || count > rm->size - first) return CCMP_EINVAL;
   if (count == 0) return CCMP_OK;
   DeviceGuard guard(rm->device);
@@ -472,22 +454,21 @@ int ccmp_roadmap_grow(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene 
 // the host form of set_joints (growTree hands over the result of its IK): synchronous on the context's stream
 int ccmp_roadmap_set_joints_host(ccmp_roadmap *rm, size_t index, const double *joints)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (!joints || index >= rm->size) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = rm->ctx->stream;
-  const hipError_t e = hipMemcpyAsync(rm->joints + index * 14, joints, 14 * sizeof(double), hipMemcpyHostToDevice, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  StagedCall sg(rm->ctx, __func__);
+  sg.up(rm->joints + index * 14, joints, 14 * sizeof(double));
+  return sg.finish(CCMP_OK);
 }
 
-// ---- host forms: synchronous on the context's stream; only the new rows / the queries go up ---------------------------------------
+// ---- host forms: synchronous on the context's stream; only the new rows / the queries go up.  Each one: its checks (before the device
+// guard and before any buffer is touched), the pieces of the staging block, the uploads, the device-pointer form unless an upload
+// failed, the downloads if it succeeded, and StagedCall::finish, which waits for the stream on every path ------------------------------
 int ccmp_roadmap_append_host(ccmp_roadmap *rm, const ccmp_problem *p, const double *joints, const double *poses, size_t Q, size_t *first_index)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first_index) *first_index = rm->size;
   if (Q == 0) return CCMP_OK;
   if ((!joints && !poses) || Q > kMaxNodes - rm->size) return CCMP_EINVAL;
@@ -495,35 +476,28 @@ int ccmp_roadmap_append_host(ccmp_roadmap *rm, const ccmp_problem *p, const doub
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
-  Stage sg(ctx);
+  StagedCall sg(ctx, __func__);
   const size_t jb = Q * 14 * sizeof(double), pb = Q * 8 * sizeof(double);
-  const size_t off_j = sg.add(joints ? jb : 0), off_p = sg.add(poses ? pb : 0);
+  const size_t off_j = sg.add(joints ? jb : 0), off_p = sg.add(poses ? pb : 0); // an absent array is a piece of no bytes
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  if (joints) HIP_TRY(hipMemcpyAsync(sg.at(off_j), joints, jb, hipMemcpyHostToDevice, ctx->stream));
-  if (poses) HIP_TRY(hipMemcpyAsync(sg.at(off_p), poses, pb, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = ccmp_roadmap_append(rm, p, joints ? (const double *)sg.at(off_j) : nullptr, poses ? (const double *)sg.at(off_p) : nullptr, Q, first_index,
-                                     ctx->stream);
-  const hipError_t e = hipStreamSynchronize(ctx->stream); // also on the error path: the staging block must be quiet
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  return CCMP_OK;
+  sg.up(off_j, joints, jb);
+  sg.up(off_p, poses, pb);
+  int rc = CCMP_OK;
+  if (sg.copy_ok()) rc = ccmp_roadmap_append(rm, p, sg.at<const double>(off_j, joints), sg.at<const double>(off_p, poses), Q, first_index, ctx->stream);
+  return sg.finish(rc);
 }
 
 int ccmp_roadmap_read_host(ccmp_roadmap *rm, size_t first, size_t count, double *joints_out, double *poses_out)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first > rm->size || count > rm->size - first) return CCMP_EINVAL;
   if (count == 0) return CCMP_OK;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = rm->ctx->stream;
-  hipError_t e = hipSuccess;
-  if (joints_out) e = hipMemcpyAsync(joints_out, rm->joints + first * 14, count * 14 * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && poses_out) e = hipMemcpyAsync(poses_out, rm->poses + first * 8, count * 8 * sizeof(double), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  StagedCall sg(rm->ctx, __func__);
+  sg.down(joints_out, rm->joints + first * 14, count * 14 * sizeof(double));
+  sg.down(poses_out, rm->poses + first * 8, count * 8 * sizeof(double));
+  return sg.finish(CCMP_OK);
 }
 
 int ccmp_roadmap_knn_host(ccmp_roadmap *rm, int metric, const double *queries, size_t Q, int k, int mode, size_t self_base, int32_t *nbr_idx,
@@ -535,27 +509,26 @@ int ccmp_roadmap_knn_host(ccmp_roadmap *rm, int metric, const double *queries, s
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
   const size_t S = Q * (size_t)k, qb = Q * (metric == CCMP_METRIC_JOINT ? 14 : 8) * sizeof(double);
-  Stage sg(ctx);
-  const size_t off_q = sg.add(qb);
-  const size_t off_d = sg.total; // distances then indices, one block: one download
-  sg.add(S * sizeof(double) + S * sizeof(int32_t));
+  StagedCall sg(ctx, __func__);
+  const size_t off_q = sg.add(qb), off_d = sg.add(S * sizeof(double) + S * sizeof(int32_t)); // distances then indices, one piece
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  HIP_TRY(hipMemcpyAsync(sg.at(off_q), queries, qb, hipMemcpyHostToDevice, ctx->stream));
-  double *d_dev = (double *)sg.at(off_d);
+  sg.up(off_q, queries, qb);
+  double *d_dev = sg.at<double>(off_d);
   int32_t *i_dev = (int32_t *)(d_dev + S);
-  int rc = ccmp_roadmap_knn(rm, metric, (const double *)sg.at(off_q), Q, k, mode, self_base, i_dev, nbr_dist ? d_dev : nullptr, ctx->stream);
-  hipError_t e = hipSuccess;
+  int rc = CCMP_OK;
+  if (sg.copy_ok()) rc = ccmp_roadmap_knn(rm, metric, sg.at<const double>(off_q), Q, k, mode, self_base, i_dev, nbr_dist ? d_dev : nullptr, ctx->stream);
+  // with distances both arrays come down in one copy, into a bounce vector (no room for it: CCMP_ENOMEM, after the wait); without, the
+  // indices alone
   std::vector<char> back;
-  if (rc == CCMP_OK) {
-    if (nbr_dist) {
-      try { back.resize(S * (sizeof(double) + sizeof(int32_t))); } catch (...) { rc = CCMP_ENOMEM; }
-      if (rc == CCMP_OK) e = hipMemcpyAsync(back.data(), d_dev, back.size(), hipMemcpyDeviceToHost, ctx->stream);
-    } else e = hipMemcpyAsync(nbr_idx, i_dev, S * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (rc == CCMP_OK && nbr_dist) {
+    try { back.resize(S * (sizeof(double) + sizeof(int32_t))); } catch (...) { rc = CCMP_ENOMEM; }
   }
-  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (rc == CCMP_OK) {
+    if (nbr_dist) sg.down(back.data(), d_dev, back.size());
+    else sg.down(nbr_idx, i_dev, S * sizeof(int32_t));
+  }
+  rc = sg.finish(rc);
   if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
   if (nbr_dist) {
     memcpy(nbr_dist, back.data(), S * sizeof(double));
     memcpy(nbr_idx, back.data() + S * sizeof(double), S * sizeof(int32_t));
@@ -575,37 +548,31 @@ int ccmp_roadmap_connect_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccm
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
-  hipStream_t st = ctx->stream;
   const size_t E = Q * (size_t)k, jb = Q * 14 * sizeof(double), pb = Q * 8 * sizeof(double), sb = E * (size_t)max_states * 14 * sizeof(double);
-  Stage sg(ctx);
+  StagedCall sg(ctx, __func__);
   const size_t off_j = sg.add(jb), off_p = sg.add(query_poses ? pb : 0), off_i = sg.add(E * sizeof(int32_t)), off_d = sg.add(E * sizeof(double)),
                off_st = sg.add(sb), off_n = sg.add(E * sizeof(int32_t)), off_ok = sg.add(E), off_it = sg.add(E * sizeof(int32_t)), off_bl = sg.add(E),
                off_co = sg.add(E * 2 * sizeof(double));
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  HIP_TRY(hipMemcpyAsync(sg.at(off_j), query_joints, jb, hipMemcpyHostToDevice, st));
-  if (query_poses) HIP_TRY(hipMemcpyAsync(sg.at(off_p), query_poses, pb, hipMemcpyHostToDevice, st));
-  const int rc = ccmp_roadmap_connect(rm, p, scene, margin, metric, (const double *)sg.at(off_j), query_poses ? (const double *)sg.at(off_p) : nullptr, Q, k,
-                                      mode, self_base, check_target, max_states, round_budget, (int32_t *)sg.at(off_i),
-                                      nbr_dist ? (double *)sg.at(off_d) : nullptr, (double *)sg.at(off_st), (int32_t *)sg.at(off_n), (uint8_t *)sg.at(off_ok),
-                                      newton_iters ? (int32_t *)sg.at(off_it) : nullptr, blocked ? (uint8_t *)sg.at(off_bl) : nullptr,
-                                      carry_out ? (double *)sg.at(off_co) : nullptr, st);
-  hipError_t e = hipSuccess;
-  auto down = [&](void *dst, size_t off, size_t n) { if (dst && e == hipSuccess) e = hipMemcpyAsync(dst, sg.at(off), n, hipMemcpyDeviceToHost, st); };
+  sg.up(off_j, query_joints, jb);
+  sg.up(off_p, query_poses, pb);
+  int rc = CCMP_OK;
+  if (sg.copy_ok())
+    rc = ccmp_roadmap_connect(rm, p, scene, margin, metric, sg.at<const double>(off_j), sg.at<const double>(off_p, query_poses), Q, k, mode, self_base,
+                              check_target, max_states, round_budget, sg.at<int32_t>(off_i), sg.at<double>(off_d, nbr_dist), sg.at<double>(off_st),
+                              sg.at<int32_t>(off_n), sg.at<uint8_t>(off_ok), sg.at<int32_t>(off_it, newton_iters), sg.at<uint8_t>(off_bl, blocked),
+                              sg.at<double>(off_co, carry_out), ctx->stream);
   if (rc == CCMP_OK) {
-    down(nbr_idx, off_i, E * sizeof(int32_t));
-    down(nbr_dist, off_d, E * sizeof(double));
-    down(states, off_st, sb);
-    down(n_states, off_n, E * sizeof(int32_t));
-    down(ok, off_ok, E);
-    down(newton_iters, off_it, E * sizeof(int32_t));
-    down(blocked, off_bl, E);
-    down(carry_out, off_co, E * 2 * sizeof(double));
+    sg.down(nbr_idx, off_i, E * sizeof(int32_t));
+    sg.down(nbr_dist, off_d, E * sizeof(double));
+    sg.down(states, off_st, sb);
+    sg.down(n_states, off_n, E * sizeof(int32_t));
+    sg.down(ok, off_ok, E);
+    sg.down(newton_iters, off_it, E * sizeof(int32_t));
+    sg.down(blocked, off_bl, E);
+    sg.down(carry_out, off_co, E * 2 * sizeof(double));
   }
-  const hipError_t es = hipStreamSynchronize(st);
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  return sg.finish(rc);
 }
 
 int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
@@ -622,39 +589,33 @@ int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_s
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
-  hipStream_t st = ctx->stream;
   const size_t E = Q * (size_t)k, pb = Q * 8 * sizeof(double), sb = E * (size_t)max_states * 14 * sizeof(double);
-  Stage sg(ctx);
+  StagedCall sg(ctx, __func__);
   const size_t off_p = sg.add(pb), off_i = sg.add(E * sizeof(int32_t)), off_d = sg.add(E * sizeof(double)), off_q = sg.add(Q * 14 * sizeof(double)),
                off_io = sg.add(Q), off_iw = sg.add(Q * sizeof(int32_t)), off_st = sg.add(sb), off_n = sg.add(E * sizeof(int32_t)), off_ok = sg.add(E),
                off_it = sg.add(E * sizeof(int32_t)), off_bl = sg.add(E), off_co = sg.add(E * 2 * sizeof(double));
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  HIP_TRY(hipMemcpyAsync(sg.at(off_p), query_poses, pb, hipMemcpyHostToDevice, st));
-  const int rc = ccmp_roadmap_grow(rm, p, scene, margin, opts, (const double *)sg.at(off_p), Q, k, mode, self_base, rng_seed, first_index, check_target, max_states,
-                                   round_budget, (int32_t *)sg.at(off_i), nbr_dist ? (double *)sg.at(off_d) : nullptr, (double *)sg.at(off_q),
-                                   (uint8_t *)sg.at(off_io), (int32_t *)sg.at(off_iw), (double *)sg.at(off_st), (int32_t *)sg.at(off_n), (uint8_t *)sg.at(off_ok),
-                                   newton_iters ? (int32_t *)sg.at(off_it) : nullptr, blocked ? (uint8_t *)sg.at(off_bl) : nullptr,
-                                   carry_out ? (double *)sg.at(off_co) : nullptr, st);
-  hipError_t e = hipSuccess;
-  auto down = [&](void *dst, size_t off, size_t n) { if (dst && e == hipSuccess) e = hipMemcpyAsync(dst, sg.at(off), n, hipMemcpyDeviceToHost, st); };
+  sg.up(off_p, query_poses, pb);
+  int rc = CCMP_OK;
+  if (sg.copy_ok())
+    rc = ccmp_roadmap_grow(rm, p, scene, margin, opts, sg.at<const double>(off_p), Q, k, mode, self_base, rng_seed, first_index, check_target, max_states,
+                           round_budget, sg.at<int32_t>(off_i), sg.at<double>(off_d, nbr_dist), sg.at<double>(off_q), sg.at<uint8_t>(off_io),
+                           sg.at<int32_t>(off_iw), sg.at<double>(off_st), sg.at<int32_t>(off_n), sg.at<uint8_t>(off_ok), sg.at<int32_t>(off_it, newton_iters),
+                           sg.at<uint8_t>(off_bl, blocked), sg.at<double>(off_co, carry_out), ctx->stream);
   if (rc == CCMP_OK) {
-    down(nbr_idx, off_i, E * sizeof(int32_t));
-    down(nbr_dist, off_d, E * sizeof(double));
-    down(q_new, off_q, Q * 14 * sizeof(double));
-    down(ik_ok, off_io, Q);
-    down(ik_which, off_iw, Q * sizeof(int32_t));
-    down(states, off_st, sb);
-    down(n_states, off_n, E * sizeof(int32_t));
-    down(ok, off_ok, E);
-    down(newton_iters, off_it, E * sizeof(int32_t));
-    down(blocked, off_bl, E);
-    down(carry_out, off_co, E * 2 * sizeof(double));
+    sg.down(nbr_idx, off_i, E * sizeof(int32_t));
+    sg.down(nbr_dist, off_d, E * sizeof(double));
+    sg.down(q_new, off_q, Q * 14 * sizeof(double));
+    sg.down(ik_ok, off_io, Q);
+    sg.down(ik_which, off_iw, Q * sizeof(int32_t));
+    sg.down(states, off_st, sb);
+    sg.down(n_states, off_n, E * sizeof(int32_t));
+    sg.down(ok, off_ok, E);
+    sg.down(newton_iters, off_it, E * sizeof(int32_t));
+    sg.down(blocked, off_bl, E);
+    sg.down(carry_out, off_co, E * 2 * sizeof(double));
   }
-  const hipError_t es = hipStreamSynchronize(st);
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  return sg.finish(rc);
 }
 
 // ---- the graph: edges, components, growTree's tail, closestFromGoal's scan (ccmp_graph.h) ------------------------------------------------
@@ -682,7 +643,7 @@ int ccmp_roadmap_commit(ccmp_roadmap *rm, const ccmp_problem *p, const int32_t *
                         const double *goal_pose, const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index,
                         int32_t *grow_state, size_t *vertices_added, size_t *edges_added, void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (vertices_added) *vertices_added = 0;
   if (edges_added) *edges_added = 0;
   { const int rc = commit_checks(rm->size, nbr_idx, edge_ok, n_states, max_states, new_joints, new_poses, Q, k, roots, n_roots, flags, new_index, mid_index, grow_state); if (rc != CCMP_OK) return rc; }
@@ -776,7 +737,7 @@ int ccmp_roadmap_commit_ref(const ccmp_problem *p, const double *store_joints, c
 
 int ccmp_roadmap_add_edges(ccmp_roadmap *rm, const int32_t *uv, size_t E, size_t *rejected, void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (rejected) *rejected = 0;
   if (E == 0) return CCMP_OK;
   if (!uv || E > kMaxNodes || rm->n_edges > kMaxNodes - E) return CCMP_EINVAL;
@@ -797,7 +758,7 @@ int ccmp_roadmap_add_edges(ccmp_roadmap *rm, const int32_t *uv, size_t E, size_t
 
 int ccmp_roadmap_read_edges(ccmp_roadmap *rm, size_t first, size_t count, int32_t *uv_out, double *w_out, void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first > rm->n_edges || count > rm->n_edges - first) return CCMP_EINVAL;
   if (count == 0) return CCMP_OK;
   DeviceGuard guard(rm->device);
@@ -810,7 +771,7 @@ int ccmp_roadmap_read_edges(ccmp_roadmap *rm, size_t first, size_t count, int32_
 
 int ccmp_roadmap_read_labels(ccmp_roadmap *rm, size_t first, size_t count, int32_t *labels_out, void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first > rm->size || count > rm->size - first) return CCMP_EINVAL;
   if (count == 0) return CCMP_OK;
   if (!labels_out) return CCMP_EINVAL;
@@ -823,7 +784,7 @@ int ccmp_roadmap_read_labels(ccmp_roadmap *rm, size_t first, size_t count, int32
 int ccmp_roadmap_closest(ccmp_roadmap *rm, const int32_t *from_idx, size_t F, const double *target_pose, int32_t *idx, double *dist, double *from_dist,
                          void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (F == 0) return CCMP_OK;
   if (F > CCMP_CLOSEST_MAX_FROM || !from_idx || !target_pose || !idx || !dist || !from_dist) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
@@ -867,7 +828,7 @@ int ccmp_roadmap_commit_host(ccmp_roadmap *rm, const ccmp_problem *p, const int3
                              int k, const double *goal_pose, const int32_t *roots, int n_roots, unsigned int flags, int32_t *new_index, int32_t *mid_index,
                              int32_t *grow_state, size_t *vertices_added, size_t *edges_added)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (vertices_added) *vertices_added = 0;
   if (edges_added) *edges_added = 0;
   { const int rc = commit_checks(rm->size, nbr_idx, edge_ok, n_states, max_states, new_joints, new_poses, Q, k, roots, n_roots, flags, new_index, mid_index, grow_state); if (rc != CCMP_OK) return rc; }
@@ -876,43 +837,35 @@ int ccmp_roadmap_commit_host(ccmp_roadmap *rm, const ccmp_problem *p, const int3
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
-  hipStream_t st = ctx->stream;
   const size_t S = Q * (size_t)k, sb = states ? S * (size_t)max_states * 14 * sizeof(double) : 0;
-  Stage sg(ctx);
+  StagedCall sg(ctx, __func__);
   const size_t off_i = sg.add(S * sizeof(int32_t)), off_ok = sg.add(S), off_n = sg.add(S * sizeof(int32_t)), off_st = sg.add(sb), off_j = sg.add(Q * 14 * sizeof(double)),
                off_p = sg.add(Q * 8 * sizeof(double)), off_v = sg.add(vertex_ok ? Q : 0), off_ni = sg.add(Q * sizeof(int32_t)), off_mi = sg.add(S * sizeof(int32_t)),
                off_gs = sg.add(Q * sizeof(int32_t));
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  hipError_t e = hipSuccess;
-  auto up = [&](size_t off, const void *src, size_t n) { if (src && n && e == hipSuccess) e = hipMemcpyAsync(sg.at(off), src, n, hipMemcpyHostToDevice, st); };
-  up(off_i, nbr_idx, S * sizeof(int32_t));
-  up(off_ok, edge_ok, S);
-  up(off_n, n_states, S * sizeof(int32_t));
-  up(off_st, states, sb);
-  up(off_j, new_joints, Q * 14 * sizeof(double));
-  up(off_p, new_poses, Q * 8 * sizeof(double));
-  up(off_v, vertex_ok, Q);
+  sg.up(off_i, nbr_idx, S * sizeof(int32_t));
+  sg.up(off_ok, edge_ok, S);
+  sg.up(off_n, n_states, S * sizeof(int32_t));
+  sg.up(off_st, states, sb);
+  sg.up(off_j, new_joints, Q * 14 * sizeof(double));
+  sg.up(off_p, new_poses, Q * 8 * sizeof(double));
+  sg.up(off_v, vertex_ok, Q);
   int rc = CCMP_OK;
-  if (e == hipSuccess)
-    rc = ccmp_roadmap_commit(rm, p, (const int32_t *)sg.at(off_i), (const uint8_t *)sg.at(off_ok), (const int32_t *)sg.at(off_n),
-                             states ? (const double *)sg.at(off_st) : nullptr, max_states, (const double *)sg.at(off_j), (const double *)sg.at(off_p),
-                             vertex_ok ? (const uint8_t *)sg.at(off_v) : nullptr, Q, k, goal_pose, roots, n_roots, flags, (int32_t *)sg.at(off_ni),
-                             (int32_t *)sg.at(off_mi), (int32_t *)sg.at(off_gs), vertices_added, edges_added, st);
-  if (rc == CCMP_OK && e == hipSuccess) {
-    e = hipMemcpyAsync(new_index, sg.at(off_ni), Q * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(mid_index, sg.at(off_mi), S * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(grow_state, sg.at(off_gs), Q * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (sg.copy_ok()) // vertices_added and edges_added (zeroed above, before the checks) are the device form's to fill
+    rc = ccmp_roadmap_commit(rm, p, sg.at<const int32_t>(off_i), sg.at<const uint8_t>(off_ok), sg.at<const int32_t>(off_n), sg.at<const double>(off_st, states),
+                             max_states, sg.at<const double>(off_j), sg.at<const double>(off_p), sg.at<const uint8_t>(off_v, vertex_ok), Q, k, goal_pose, roots,
+                             n_roots, flags, sg.at<int32_t>(off_ni), sg.at<int32_t>(off_mi), sg.at<int32_t>(off_gs), vertices_added, edges_added, ctx->stream);
+  if (rc == CCMP_OK) {
+    sg.down(new_index, off_ni, Q * sizeof(int32_t));
+    sg.down(mid_index, off_mi, S * sizeof(int32_t));
+    sg.down(grow_state, off_gs, Q * sizeof(int32_t));
   }
-  const hipError_t es = hipStreamSynchronize(st);
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  return sg.finish(rc);
 }
 
 int ccmp_roadmap_add_edges_host(ccmp_roadmap *rm, const int32_t *uv, size_t E)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (E == 0) return CCMP_OK;
   if (!uv || E > kMaxNodes || rm->n_edges > kMaxNodes - E) return CCMP_EINVAL;
   for (size_t e = 0; e < E; e++)
@@ -920,56 +873,45 @@ int ccmp_roadmap_add_edges_host(ccmp_roadmap *rm, const int32_t *uv, size_t E)
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
-  Stage sg(ctx);
+  StagedCall sg(ctx, __func__);
   const size_t off = sg.add(E * 2 * sizeof(int32_t));
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  const hipError_t e = hipMemcpyAsync(sg.at(off), uv, E * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+  sg.up(off, uv, E * 2 * sizeof(int32_t));
   int rc = CCMP_OK;
-  if (e == hipSuccess) rc = ccmp_roadmap_add_edges(rm, (const int32_t *)sg.at(off), E, nullptr, ctx->stream);
-  const hipError_t es = hipStreamSynchronize(ctx->stream);
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  if (sg.copy_ok()) rc = ccmp_roadmap_add_edges(rm, sg.at<const int32_t>(off), E, nullptr, ctx->stream);
+  return sg.finish(rc);
 }
 
 int ccmp_roadmap_read_edges_host(ccmp_roadmap *rm, size_t first, size_t count, int32_t *uv_out, double *w_out)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first > rm->n_edges || count > rm->n_edges - first) return CCMP_EINVAL;
   if (count == 0) return CCMP_OK;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = rm->ctx->stream;
-  hipError_t e = hipSuccess;
-  if (uv_out) e = hipMemcpyAsync(uv_out, rm->uv + first * 2, count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && w_out) e = hipMemcpyAsync(w_out, rm->w + first, count * sizeof(double), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  StagedCall sg(rm->ctx, __func__);
+  sg.down(uv_out, rm->uv + first * 2, count * 2 * sizeof(int32_t));
+  sg.down(w_out, rm->w + first, count * sizeof(double));
+  return sg.finish(CCMP_OK);
 }
 
 int ccmp_roadmap_read_labels_host(ccmp_roadmap *rm, size_t first, size_t count, int32_t *labels_out)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (first > rm->size || count > rm->size - first) return CCMP_EINVAL;
   if (count == 0) return CCMP_OK;
   if (!labels_out) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = rm->ctx->stream;
-  const hipError_t e = hipMemcpyAsync(labels_out, rm->labels + first, count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  StagedCall sg(rm->ctx, __func__);
+  sg.down(labels_out, rm->labels + first, count * sizeof(int32_t));
+  return sg.finish(CCMP_OK);
 }
 
 int ccmp_roadmap_closest_host(ccmp_roadmap *rm, const int32_t *from_idx, size_t F, const double *target_pose, int32_t *idx, double *dist,
                               double *from_dist)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (F == 0) return CCMP_OK;
   if (F > CCMP_CLOSEST_MAX_FROM || !from_idx || !target_pose || !idx || !dist || !from_dist) return CCMP_EINVAL;
   for (size_t f = 0; f < F; f++)
@@ -977,34 +919,29 @@ int ccmp_roadmap_closest_host(ccmp_roadmap *rm, const int32_t *from_idx, size_t 
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
-  hipStream_t st = ctx->stream;
-  Stage sg(ctx);
+  StagedCall sg(ctx, __func__);
   const size_t off_f = sg.add(F * sizeof(int32_t)), off_t = sg.add(8 * sizeof(double)), off_i = sg.add(F * sizeof(int32_t)), off_d = sg.add(F * sizeof(double)),
                off_fd = sg.add(F * sizeof(double));
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  hipError_t e = hipMemcpyAsync(sg.at(off_f), from_idx, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(sg.at(off_t), target_pose, 7 * sizeof(double), hipMemcpyHostToDevice, st);
+  sg.up(off_f, from_idx, F * sizeof(int32_t));
+  sg.up(off_t, target_pose, 7 * sizeof(double)); // the target is 7 doubles, its piece a pose row of 8
   int rc = CCMP_OK;
-  if (e == hipSuccess)
-    rc = ccmp_roadmap_closest(rm, (const int32_t *)sg.at(off_f), F, (const double *)sg.at(off_t), (int32_t *)sg.at(off_i), (double *)sg.at(off_d),
-                              (double *)sg.at(off_fd), st);
-  if (rc == CCMP_OK && e == hipSuccess) {
-    e = hipMemcpyAsync(idx, sg.at(off_i), F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dist, sg.at(off_d), F * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(from_dist, sg.at(off_fd), F * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (sg.copy_ok())
+    rc = ccmp_roadmap_closest(rm, sg.at<const int32_t>(off_f), F, sg.at<const double>(off_t), sg.at<int32_t>(off_i), sg.at<double>(off_d), sg.at<double>(off_fd),
+                              ctx->stream);
+  if (rc == CCMP_OK) {
+    sg.down(idx, off_i, F * sizeof(int32_t));
+    sg.down(dist, off_d, F * sizeof(double));
+    sg.down(from_dist, off_fd, F * sizeof(double));
   }
-  const hipError_t es = hipStreamSynchronize(st);
-  if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  return sg.finish(rc);
 }
 
 // ---- shortest paths: the planner's solution step (ccmp_path.h) ---------------------------------------------------------------------------
 int ccmp_roadmap_shortest_paths(ccmp_roadmap *rm, const int32_t *src, const int32_t *dst, size_t F, int max_len, double *cost, int32_t *path_len,
                                 int32_t *path, double *path_joints, double *path_poses, double *dist_out, int32_t *pred_out, void *hip_stream)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (F == 0) return CCMP_OK;
   { const int rc = path_checks(src, dst, F, max_len, cost, path_len, path); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(rm->device);
@@ -1038,23 +975,20 @@ int ccmp_roadmap_shortest_paths(ccmp_roadmap *rm, const int32_t *src, const int3
 
 int ccmp_roadmap_path_rounds_host(ccmp_roadmap *rm, size_t F, int32_t *rounds)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (F == 0) return CCMP_OK;
   if (!rounds || !rm->path_ws || F > rm->path_F) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = rm->ctx->stream;
-  const hipError_t e = hipMemcpyAsync(rounds, rm->path_ws, F * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  StagedCall sg(rm->ctx, __func__);
+  sg.down(rounds, rm->path_ws, F * 2 * sizeof(int32_t));
+  return sg.finish(CCMP_OK);
 }
 
 int ccmp_roadmap_shortest_paths_host(ccmp_roadmap *rm, const int32_t *src, const int32_t *dst, size_t F, int max_len, double *cost, int32_t *path_len,
                                      int32_t *path, double *path_joints, double *path_poses, double *dist_out, int32_t *pred_out)
 {
-  if (!rm) return no_store();
+  if (!rm) return no_handle();
   if (F == 0) return CCMP_OK;
   { const int rc = path_checks(src, dst, F, max_len, cost, path_len, path); if (rc != CCMP_OK) return rc; }
   for (size_t f = 0; f < F; f++)
@@ -1062,42 +996,37 @@ int ccmp_roadmap_shortest_paths_host(ccmp_roadmap *rm, const int32_t *src, const
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
-  hipStream_t st = ctx->stream;
   const size_t L = (size_t)max_len;
-  Stage sg(ctx);
+  StagedCall sg(ctx, __func__);
   const size_t off_s = sg.add(F * sizeof(int32_t)), off_d = sg.add(F * sizeof(int32_t)), off_c = sg.add(F * sizeof(double)), off_l = sg.add(F * sizeof(int32_t)),
                off_p = sg.add(F * L * sizeof(int32_t)), off_j = sg.add(path_joints ? F * L * 14 * sizeof(double) : 0),
                off_o = sg.add(path_poses ? F * L * 8 * sizeof(double) : 0);
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
-  hipError_t e = hipMemcpyAsync(sg.at(off_s), src, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(sg.at(off_d), dst, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  sg.up(off_s, src, F * sizeof(int32_t));
+  sg.up(off_d, dst, F * sizeof(int32_t));
   int rc = CCMP_OK;
-  if (e == hipSuccess)
-    rc = ccmp_roadmap_shortest_paths(rm, (const int32_t *)sg.at(off_s), (const int32_t *)sg.at(off_d), F, max_len, (double *)sg.at(off_c), (int32_t *)sg.at(off_l),
-                                     (int32_t *)sg.at(off_p), path_joints ? (double *)sg.at(off_j) : nullptr, path_poses ? (double *)sg.at(off_o) : nullptr, nullptr,
-                                     nullptr, st);
-  const size_t n = F * rm->size; // the distances and predecessors come straight from the workspace
-  if (rc == CCMP_OK && e == hipSuccess) {
-    e = hipMemcpyAsync(cost, sg.at(off_c), F * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(path_len, sg.at(off_l), F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && dist_out && n) e = hipMemcpyAsync(dist_out, path_d(rm), n * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && pred_out && n) e = hipMemcpyAsync(pred_out, path_pred(rm), n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (sg.copy_ok())
+    rc = ccmp_roadmap_shortest_paths(rm, sg.at<const int32_t>(off_s), sg.at<const int32_t>(off_d), F, max_len, sg.at<double>(off_c), sg.at<int32_t>(off_l),
+                                     sg.at<int32_t>(off_p), sg.at<double>(off_j, path_joints), sg.at<double>(off_o, path_poses), nullptr, nullptr, ctx->stream);
+  // The download has two phases, each ended by a wait: the costs and lengths (and the distances and predecessors, straight from the
+  // workspace), then of every path that fitted its entries alone, chosen by the lengths just read.  A path that did not fit leaves the
+  // caller's arrays as they were.
+  const size_t n = F * rm->size;
+  if (rc == CCMP_OK) {
+    sg.down(cost, off_c, F * sizeof(double));
+    sg.down(path_len, off_l, F * sizeof(int32_t));
+    sg.down(dist_out, path_d(rm), n * sizeof(double));
+    sg.down(pred_out, path_pred(rm), n * sizeof(int32_t));
   }
-  hipError_t es = hipStreamSynchronize(st);
+  rc = sg.finish(rc);
   if (rc != CCMP_OK) return rc;
-  HIP_TRY(e);
-  HIP_TRY(es);
-  for (size_t f = 0; f < F && e == hipSuccess; f++) { // a path that fitted: its entries alone (a longer one leaves the caller's arrays as they were)
+  for (size_t f = 0; f < F; f++) {
     const size_t len = path_len[f] > 0 && path_len[f] <= max_len ? (size_t)path_len[f] : 0;
-    if (!len) continue;
-    e = hipMemcpyAsync(path + f * L, sg.at(off_p + f * L * sizeof(int32_t)), len * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && path_joints) e = hipMemcpyAsync(path_joints + f * L * 14, sg.at(off_j + f * L * 14 * sizeof(double)), len * 14 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && path_poses) e = hipMemcpyAsync(path_poses + f * L * 8, sg.at(off_o + f * L * 8 * sizeof(double)), len * 8 * sizeof(double), hipMemcpyDeviceToHost, st);
+    sg.down(path + f * L, off_p + f * L * sizeof(int32_t), len * sizeof(int32_t));
+    if (path_joints) sg.down(path_joints + f * L * 14, off_j + f * L * 14 * sizeof(double), len * 14 * sizeof(double));
+    if (path_poses) sg.down(path_poses + f * L * 8, off_o + f * L * 8 * sizeof(double), len * 8 * sizeof(double));
   }
-  es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  return sg.finish(CCMP_OK);
 }
 
 int ccmp_graph_shortest_paths_ref(const int32_t *uv, const double *w, size_t E, size_t N, const int32_t *src, const int32_t *dst, size_t F, int max_len,

@@ -18,6 +18,7 @@
 #include "ccmp_resident.h"
 #include "ccmp_scene.h"
 #include "ccmp_shortcut.h"
+#include "ccmp_stage.h"
 
 using namespace ccmp_host;
 using ccmp::shortcut_best;
@@ -27,38 +28,7 @@ namespace {
 
 constexpr size_t kMaxCells = (size_t)1 << 40; // F max_len^2 beyond this is an argument error, not an allocation to try
 
-int no_ctx()
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return CCMP_ENODEV; }
-  return CCMP_EINVAL;
-}
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// the device memory of one call, released when it returns
-struct Scratch {
-  ccmp_ctx *ctx;
-  std::vector<void *> blocks;
-  explicit Scratch(ccmp_ctx *c) : ctx(c) {}
-  Scratch(const Scratch &) = delete;
-  Scratch &operator=(const Scratch &) = delete;
-  void *get(size_t bytes)
-  {
-    void *b = nullptr;
-    ccmp_host::quiesce(ctx);
-    const hipError_t e = hipMalloc(&b, align256(bytes ? bytes : 1));
-    if (e != hipSuccess) { (void)hip_fail(e, "ccmp_path_shortcut: hipMalloc"); return nullptr; }
-    blocks.push_back(b);
-    return b;
-  }
-  ~Scratch()
-  {
-    if (blocks.empty()) return;
-    ccmp_host::quiesce(ctx);
-    for (void *b : blocks) (void)hipFree(b); // waits for whatever still reads it
-  }
-};
+constexpr const char *kArenaWhat = "ccmp_path_shortcut: hipMalloc";
 
 bool overlaps(const void *a, size_t na, const void *b, size_t nb)
 {
@@ -102,13 +72,6 @@ int shortcut_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene
   return CCMP_OK;
 }
 
-int lens_ok(const int32_t *len, size_t F, int max_len)
-{
-  for (size_t f = 0; f < F; f++)
-    if (len[f] < 0 || len[f] > max_len) return CCMP_EINVAL;
-  return CCMP_OK;
-}
-
 // one extend call's buffers; a tile has two and alternates
 struct CallBufs {
   double *from = nullptr, *to = nullptr, *states = nullptr, *carry_out = nullptr, *carry_in = nullptr;
@@ -117,19 +80,18 @@ struct CallBufs {
   shortcut_open *open = nullptr;
 };
 
-bool make_bufs(Scratch &mem, size_t T, int cs, bool scene, CallBufs *b)
+void make_bufs(CallArena &mem, size_t T, int cs, bool scene, CallBufs *b) // (the caller asks mem.ok() once)
 {
-  b->from = (double *)mem.get(T * 14 * sizeof(double));
-  b->to = (double *)mem.get(T * 14 * sizeof(double));
-  b->states = (double *)mem.get(T * (size_t)cs * 14 * sizeof(double));
-  b->carry_out = (double *)mem.get(T * 2 * sizeof(double));
-  b->carry_in = (double *)mem.get(T * 2 * sizeof(double));
-  b->n = (int32_t *)mem.get(T * sizeof(int32_t));
-  b->its = (int32_t *)mem.get(T * sizeof(int32_t));
-  b->ok = (uint8_t *)mem.get(T);
-  b->blocked = scene ? (uint8_t *)mem.get(T) : nullptr;
-  b->open = (shortcut_open *)mem.get(T * sizeof(shortcut_open));
-  return b->from && b->to && b->states && b->carry_out && b->carry_in && b->n && b->its && b->ok && (!scene || b->blocked) && b->open;
+  b->from = mem.array<double>(T * 14);
+  b->to = mem.array<double>(T * 14);
+  b->states = mem.array<double>(T * (size_t)cs * 14);
+  b->carry_out = mem.array<double>(T * 2);
+  b->carry_in = mem.array<double>(T * 2);
+  b->n = mem.array<int32_t>(T);
+  b->its = mem.array<int32_t>(T);
+  b->ok = mem.array<uint8_t>(T);
+  b->blocked = scene ? mem.array<uint8_t>(T) : nullptr;
+  b->open = mem.array<shortcut_open>(T);
 }
 
 // The body of the device form behind its checks; `len` = path_len as read once from the device.  The outputs are written only after every
@@ -143,21 +105,23 @@ int shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, doub
   std::vector<long long> prefix(F + 1, 0);
   for (size_t f = 0; f < F; f++) prefix[f + 1] = prefix[f] + ccmp::shortcut_pair_count(len[f], o.max_span);
   const long long total = prefix[F];
-  Scratch mem(ctx);
+  CallArena mem(ctx, kArenaWhat); // everything below lives until the call returns
   // the call's own matrices: the caller's stay untouched until the end
-  uint8_t *w_ok = (uint8_t *)mem.get(cells);
-  int32_t *w_states = pair_states ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr;
-  int32_t *w_newton = pair_newton ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr;
-  if (!w_ok || (pair_states && !w_states) || (pair_newton && !w_newton)) return CCMP_EHIP;
+  uint8_t *w_ok = mem.array<uint8_t>(cells);
+  int32_t *w_states = pair_states ? mem.array<int32_t>(cells) : nullptr;
+  int32_t *w_newton = pair_newton ? mem.array<int32_t>(cells) : nullptr;
+  if (!mem.ok()) return CCMP_EHIP;
   HIP_TRY(hipMemsetAsync(w_ok, 0, cells, st));
   if (w_states) HIP_TRY(hipMemsetAsync(w_states, 0, cells * sizeof(int32_t), st));
   if (w_newton) HIP_TRY(hipMemsetAsync(w_newton, 0, cells * sizeof(int32_t), st));
 
   if (total > 0) {
     const size_t T_max = (size_t)((long long)o.tile_edges < total ? (long long)o.tile_edges : total);
-    long long *d_prefix = (long long *)mem.get((F + 1) * sizeof(long long)), *d_cell = (long long *)mem.get(T_max * sizeof(long long));
+    long long *d_prefix = mem.array<long long>(F + 1), *d_cell = mem.array<long long>(T_max);
     CallBufs bufs[2];
-    if (!d_prefix || !d_cell || !make_bufs(mem, T_max, cs, scene != nullptr, &bufs[0]) || !make_bufs(mem, T_max, cs, scene != nullptr, &bufs[1])) return CCMP_EHIP;
+    make_bufs(mem, T_max, cs, scene != nullptr, &bufs[0]);
+    make_bufs(mem, T_max, cs, scene != nullptr, &bufs[1]);
+    if (!mem.ok()) return CCMP_EHIP;
     HIP_TRY(hipMemcpyAsync(d_prefix, prefix.data(), (F + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     std::vector<int32_t> n_h(T_max);
     std::vector<uint8_t> ok_h(T_max), bl_h(T_max, 0);
@@ -277,7 +241,7 @@ int ccmp_path_shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *s
                        size_t F, int max_len, const ccmp_shortcut_opts *opts, double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in,
                        double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton, void *hip_stream)
 {
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   ccmp_shortcut_opts o;
   ccmp_shortcut_opts_default(&o);
   if (opts) o = *opts;
@@ -305,7 +269,7 @@ int ccmp_path_shortcut_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sce
                             const int32_t *path_len, size_t F, int max_len, const ccmp_shortcut_opts *opts, double *out_joints, int32_t *out_len,
                             int32_t *kept, double *cost_in, double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton)
 {
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   ccmp_shortcut_opts o;
   ccmp_shortcut_opts_default(&o);
   if (opts) o = *opts;
@@ -316,44 +280,36 @@ int ccmp_path_shortcut_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sce
   { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = ctx->stream;
   const size_t rows = F * (size_t)max_len, cells = rows * (size_t)max_len;
-  Scratch mem(ctx);
-  double *d_in = (double *)mem.get(rows * 14 * sizeof(double)), *d_out = (double *)mem.get(rows * 14 * sizeof(double));
-  double *d_ci = (double *)mem.get(F * sizeof(double)), *d_co = (double *)mem.get(F * sizeof(double));
-  int32_t *d_len = (int32_t *)mem.get(F * sizeof(int32_t)), *d_olen = (int32_t *)mem.get(F * sizeof(int32_t)), *d_kept = (int32_t *)mem.get(rows * sizeof(int32_t));
-  uint8_t *d_ok = pair_ok ? (uint8_t *)mem.get(cells) : nullptr;
-  int32_t *d_ps = pair_states ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr, *d_pn = pair_newton ? (int32_t *)mem.get(cells * sizeof(int32_t)) : nullptr;
-  if (!d_in || !d_out || !d_ci || !d_co || !d_len || !d_olen || !d_kept || (pair_ok && !d_ok) || (pair_states && !d_ps) || (pair_newton && !d_pn)) return CCMP_EHIP;
-  {
-    hipError_t e = hipMemcpyAsync(d_in, path_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_len, path_len, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, out_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st); // rows behind out_len stay the caller's
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-  }
+  CallArena mem(ctx, kArenaWhat); // the staging is memory of this call, not the context's block: it can be hundreds of megabytes
+  double *d_in = mem.array<double>(rows * 14), *d_out = mem.array<double>(rows * 14), *d_ci = mem.array<double>(F), *d_co = mem.array<double>(F);
+  int32_t *d_len = mem.array<int32_t>(F), *d_olen = mem.array<int32_t>(F), *d_kept = mem.array<int32_t>(rows);
+  uint8_t *d_ok = pair_ok ? mem.array<uint8_t>(cells) : nullptr;
+  int32_t *d_ps = pair_states ? mem.array<int32_t>(cells) : nullptr, *d_pn = pair_newton ? mem.array<int32_t>(cells) : nullptr;
+  if (!mem.ok()) return CCMP_EHIP;
+  StagedCall sg(ctx, __func__);
+  sg.up(d_in, path_joints, rows * 14 * sizeof(double));
+  sg.up(d_len, path_len, F * sizeof(int32_t));
+  sg.up(d_out, out_joints, rows * 14 * sizeof(double)); // the caller's out_joints go up first: rows behind out_len stay the caller's
+  { const int rc = sg.finish(CCMP_OK); if (rc != CCMP_OK) return rc; }
   const int rc = shortcut(ctx, p, scene, margin, d_in, d_len, std::vector<int32_t>(path_len, path_len + F), F, max_len, o, d_out, d_olen, d_kept, d_ci, d_co, d_ok,
-                          d_ps, d_pn, st);
-  if (rc != CCMP_OK) return rc;
-  hipError_t e = hipMemcpyAsync(out_joints, d_out, rows * 14 * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_len, d_olen, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(kept, d_kept, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(cost_in, d_ci, F * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(cost_out, d_co, F * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && pair_ok) e = hipMemcpyAsync(pair_ok, d_ok, cells, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && pair_states) e = hipMemcpyAsync(pair_states, d_ps, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && pair_newton) e = hipMemcpyAsync(pair_newton, d_pn, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+                          d_ps, d_pn, ctx->stream);
+  if (rc != CCMP_OK) return rc; // (CCMP_EOVERFLOW at max_calls among them: no output is written; the arena's hipFree waits for what is in flight)
+  sg.down(out_joints, d_out, rows * 14 * sizeof(double));
+  sg.down(out_len, d_olen, F * sizeof(int32_t));
+  sg.down(kept, d_kept, rows * sizeof(int32_t));
+  sg.down(cost_in, d_ci, F * sizeof(double));
+  sg.down(cost_out, d_co, F * sizeof(double));
+  sg.down(pair_ok, d_ok, cells);
+  sg.down(pair_states, d_ps, cells * sizeof(int32_t));
+  sg.down(pair_newton, d_pn, cells * sizeof(int32_t));
+  return sg.finish(CCMP_OK);
 }
 
 int ccmp_shortcut_select(ccmp_ctx *ctx, const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok,
                          double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out, void *hip_stream)
 {
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   { const int rc = select_checks(path_joints, path_len, F, max_len, pair_ok, out_joints, out_len, kept, cost_in, cost_out, nullptr, nullptr, nullptr);
     if (rc != CCMP_OK) return rc; }
   if (F == 0) return CCMP_OK;
@@ -369,7 +325,7 @@ int ccmp_shortcut_select(ccmp_ctx *ctx, const double *path_joints, const int32_t
 int ccmp_shortcut_select_host(ccmp_ctx *ctx, const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok,
                               double *out_joints, int32_t *out_len, int32_t *kept, double *cost_in, double *cost_out)
 {
-  if (!ctx) return no_ctx();
+  if (!ctx) return no_handle();
   { const int rc = select_checks(path_joints, path_len, F, max_len, pair_ok, out_joints, out_len, kept, cost_in, cost_out, nullptr, nullptr, nullptr);
     if (rc != CCMP_OK) return rc; }
   if (F == 0) return CCMP_OK;
@@ -377,29 +333,25 @@ int ccmp_shortcut_select_host(ccmp_ctx *ctx, const double *path_joints, const in
   { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = ctx->stream;
   const size_t rows = F * (size_t)max_len, cells = rows * (size_t)max_len;
-  Scratch mem(ctx);
-  double *d_in = (double *)mem.get(rows * 14 * sizeof(double)), *d_out = (double *)mem.get(rows * 14 * sizeof(double));
-  double *d_ci = (double *)mem.get(F * sizeof(double)), *d_co = (double *)mem.get(F * sizeof(double));
-  int32_t *d_len = (int32_t *)mem.get(F * sizeof(int32_t)), *d_olen = (int32_t *)mem.get(F * sizeof(int32_t)), *d_kept = (int32_t *)mem.get(rows * sizeof(int32_t));
-  uint8_t *d_ok = (uint8_t *)mem.get(cells);
-  if (!d_in || !d_out || !d_ci || !d_co || !d_len || !d_olen || !d_kept || !d_ok) return CCMP_EHIP;
-  hipError_t e = hipMemcpyAsync(d_in, path_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_len, path_len, F * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_ok, pair_ok, cells, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_out, out_joints, rows * 14 * sizeof(double), hipMemcpyHostToDevice, st); // rows behind out_len stay the caller's
-  if (e == hipSuccess) e = ccmp_launch::shortcut_select(d_in, d_len, F, max_len, d_ok, d_olen, d_kept, d_ci, d_co, st);
-  if (e == hipSuccess) e = ccmp_launch::shortcut_gather_kept(d_in, d_olen, d_kept, F, max_len, d_out, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_joints, d_out, rows * 14 * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_len, d_olen, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(kept, d_kept, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(cost_in, d_ci, F * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(cost_out, d_co, F * sizeof(double), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
+  CallArena mem(ctx, kArenaWhat); // memory of this call, as in ccmp_path_shortcut_host
+  double *d_in = mem.array<double>(rows * 14), *d_out = mem.array<double>(rows * 14), *d_ci = mem.array<double>(F), *d_co = mem.array<double>(F);
+  int32_t *d_len = mem.array<int32_t>(F), *d_olen = mem.array<int32_t>(F), *d_kept = mem.array<int32_t>(rows);
+  uint8_t *d_ok = mem.array<uint8_t>(cells);
+  if (!mem.ok()) return CCMP_EHIP;
+  StagedCall sg(ctx, __func__);
+  sg.up(d_in, path_joints, rows * 14 * sizeof(double));
+  sg.up(d_len, path_len, F * sizeof(int32_t));
+  sg.up(d_ok, pair_ok, cells);
+  sg.up(d_out, out_joints, rows * 14 * sizeof(double)); // the caller's out_joints go up first: rows behind out_len stay the caller's
+  if (sg.copy_ok()) sg.note(ccmp_launch::shortcut_select(d_in, d_len, F, max_len, d_ok, d_olen, d_kept, d_ci, d_co, ctx->stream));
+  if (sg.copy_ok()) sg.note(ccmp_launch::shortcut_gather_kept(d_in, d_olen, d_kept, F, max_len, d_out, ctx->stream));
+  sg.down(out_joints, d_out, rows * 14 * sizeof(double));
+  sg.down(out_len, d_olen, F * sizeof(int32_t));
+  sg.down(kept, d_kept, rows * sizeof(int32_t));
+  sg.down(cost_in, d_ci, F * sizeof(double));
+  sg.down(cost_out, d_co, F * sizeof(double));
+  return sg.finish(CCMP_OK);
 }
 
 int ccmp_shortcut_select_ref(const double *path_joints, const int32_t *path_len, size_t F, int max_len, const uint8_t *pair_ok, double *out_joints,
