@@ -8,31 +8,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from arm_model_cases import edges as _edges, tilt as _tilt  # (one text: tests/arm_model_cases.py)
 from conftest import NCPU, ROOT, config_path
 from test_gpu_parity import _constraint, _oracle_problem
 
 pytestmark = pytest.mark.gpu
 
 dp = C.POINTER(C.c_double)
-
-
-def _tilt(c):
-    """stock arms on a tilted base: the general base-frame instantiation (DIAG = false)"""
-    a, b = 0.3, -0.7
-    Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
-    Rz = np.array([[np.cos(b), -np.sin(b), 0], [np.sin(b), np.cos(b), 0], [0, 0, 1]])
-    for k, v in enumerate((Rz @ Rx).reshape(-1)):
-        c.problem.base_R[9 + k] = float(v)
-    c.setInitialPosition(np.array(c.problem.start_joint[:]))
-
-
-def _edges(c, E, seed):
-    """growTree-shaped edges (src/planner/stefanBiPRM.cpp:307-351): a valid projected state -> a projected sampleUniformNear state"""
-    q, okq, _, _ = c.sample_project_batch(seed, 0, 8 * E + 64, want_iters=False)
-    frm = q[okq == 1][:E].contiguous()
-    assert frm.shape[0] == E
-    to, _, _, _ = c.sample_near_project_batch(seed + 1, 0, frm, 0.6, E, want_iters=False)
-    return frm, to
 
 
 def _analytic(gpu_ctx, oracle_det, variant=None):

@@ -17,7 +17,7 @@ dp = C.POINTER(C.c_double)
 VALID_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_void_p)
 
 
-def _random_scene(c, seed=0x5CE1):
+def _random_proxies(seed=0x5CE1):
     """64 spheres on every kind of frame, 8 boxes (turned ones among them), a random allowed-pair matrix (test_gpu_scene.py)"""
     from closed_chain_motion_planner_amd import scene as S
 
@@ -32,7 +32,13 @@ def _random_scene(c, seed=0x5CE1):
         boxes.append((int(rng.integers(0, 32)), tuple(rng.uniform([-0.2, -0.8, 0.6], [0.9, 0.8, 1.8])), np.eye(3) if b < 2 else Q,
                       tuple(rng.uniform(0.0, 0.3, 3))))
     allowed = [int(v) for v in rng.integers(0, 2 ** 32, 32, dtype=np.uint64) & rng.integers(0, 2 ** 32, 32, dtype=np.uint64)]
-    return S.ProxyScene(c, sph, boxes, allowed)
+    return sph, boxes, allowed
+
+
+def _random_scene(c, seed=0x5CE1):
+    from closed_chain_motion_planner_amd import scene as S
+
+    return S.ProxyScene(c, *_random_proxies(seed))
 
 
 class OracleScene:
