@@ -94,6 +94,8 @@ EXPORTS = [
     "ccmp_roadmap_truncate", "ccmp_roadmap_read", "ccmp_roadmap_knn", "ccmp_roadmap_connect",
     "ccmp_roadmap_append_host", "ccmp_roadmap_set_joints_host", "ccmp_roadmap_read_host", "ccmp_roadmap_knn_host", "ccmp_roadmap_connect_host",
     "ccmp_ik_opts_default", "ccmp_pose_ik_batch", "ccmp_pose_ik_host", "ccmp_pose_ik_ref", "ccmp_roadmap_grow", "ccmp_roadmap_grow_host",
+    "ccmp_arm_clearance_batch", "ccmp_arm_clearance_host", "ccmp_arm_clearance_ref", "ccmp_pose_ik_vetted_batch", "ccmp_pose_ik_vetted_host",
+    "ccmp_pose_ik_vetted_ref", "ccmp_roadmap_grow_vetted", "ccmp_roadmap_grow_vetted_host",
     "ccmp_pose_interpolate", "ccmp_object_create", "ccmp_object_destroy", "ccmp_object_num_triangles",
     "ccmp_object_valid_batch", "ccmp_object_valid_host", "ccmp_object_valid_ref", "ccmp_object_propose_batch", "ccmp_object_propose_host", "ccmp_object_propose_ref",
     "ccmp_joint_distance", "ccmp_graph_labels_ref", "ccmp_roadmap_commit", "ccmp_roadmap_commit_host", "ccmp_roadmap_commit_ref",
@@ -236,6 +238,20 @@ def lib():
         "ccmp_roadmap_grow_host": ([vp, pp, vp, C.c_double, C.POINTER(CcmpIkOpts), dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64,
                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, u8p, C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32), u8p,
                                     C.POINTER(C.c_int32), u8p, dp], C.c_int),
+        "ccmp_arm_clearance_batch": ([vp, pp, vp, C.c_int, vp, C.c_size_t, C.c_double, vp, vp, vp], C.c_int),
+        "ccmp_arm_clearance_host": ([vp, pp, vp, C.c_int, dp, C.c_size_t, C.c_double, dp, u8p], C.c_int),
+        "ccmp_arm_clearance_ref": ([pp, C.POINTER(CcmpSphere), C.c_int, C.POINTER(CcmpBox), C.c_int, C.POINTER(C.c_uint32), C.c_int, dp, C.c_size_t, C.c_double,
+                                    dp, u8p], C.c_int),
+        "ccmp_pose_ik_vetted_batch": ([vp, pp, C.POINTER(CcmpIkOpts), vp, vp, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_double, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, vp], C.c_int),
+        "ccmp_pose_ik_vetted_host": ([vp, pp, C.POINTER(CcmpIkOpts), dp, dp, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_double, dp, u8p, i32p, dp, i32p,
+                                      dp, dp, dp], C.c_int),
+        "ccmp_pose_ik_vetted_ref": ([pp, C.POINTER(CcmpIkOpts), dp, dp, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(CcmpSphere), C.c_int,
+                                     C.POINTER(CcmpBox), C.c_int, C.POINTER(C.c_uint32), C.c_double, dp, u8p, i32p, dp, i32p, dp, dp, dp], C.c_int),
+        "ccmp_roadmap_grow_vetted": ([vp, pp, vp, C.c_double, C.POINTER(CcmpIkOpts), vp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64,
+                                      C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_grow_vetted_host": ([vp, pp, vp, C.c_double, C.POINTER(CcmpIkOpts), dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64,
+                                           C.c_int, C.c_int, C.c_int, i32p, dp, dp, u8p, i32p, dp, dp, i32p, u8p, i32p, u8p, dp], C.c_int),
         "ccmp_pose_interpolate": ([dp, dp, C.c_double, dp], None),
         "ccmp_object_create": ([vp, dp, C.c_int, C.POINTER(CcmpBox), C.c_int, C.POINTER(vp)], C.c_int),
         "ccmp_object_destroy": ([vp], None),

@@ -446,17 +446,20 @@ class KinematicChainConstraint:
                                             out["blocked"].data_ptr(), out["carry"].data_ptr(), _stream_handle(stream)), "ccmp_connect_batch")
         return out
 
-    def pose_ik_batch(self, target_poses, seeds, rng_seed=0, first_index=0, opts=None, want_candidates=False, stream=None):
+    def pose_ik_batch(self, target_poses, seeds, rng_seed=0, first_index=0, opts=None, want_candidates=False, stream=None, scene=None, margin=None):
         """growTree's sampleCalibGoal for T object poses (ccmp_pose_ik_batch / _host): target_poses (T,8) in the roadmap store's format,
         seeds (T,S,14) tried in order — per arm the slot's own joints first, then `opts.restarts` Gaussian restarts of which the
         converged one closest to the seed is kept; the first slot on which both arms succeed gives the state.  Returns a dict: q
         (T,14; NaN rows on failure), ok (T,), which (T,; the slot, -1 on failure) and with want_candidates cand_q (T,S,2,1+R,7) and
         cand_rounds (T,S,2,1+R).  Device tensors run asynchronously on `stream`, numpy arrays through the synchronous host form;
-        `ik.pose_ik_ref` is the same solver on the host.  opts: `ik.ik_options(...)`."""
+        `ik.pose_ik_ref` is the same solver on the host.  opts: `ik.ik_options(...)`.
+        scene (a `ProxyScene`) and margin (None = 0): the vetted form (ccmp_pose_ik_vetted_*) — the scene where the reference has IKValid on
+        every candidate and si_->isValid on the assembled state; the dict then also holds clearance (T,) and with want_candidates
+        cand_clear (T,S,2,1+R) and slot_clear (T,S).  Proxies, not MoveIt."""
         from .ik import pose_ik
 
         self._need_problem()
-        return pose_ik(self.ctx.handle, self.problem, target_poses, seeds, rng_seed, first_index, opts, want_candidates, stream)
+        return pose_ik(self.ctx.handle, self.problem, target_poses, seeds, rng_seed, first_index, opts, want_candidates, stream, scene=scene, margin=margin)
 
     def continue_geodesics(self, to, states, n, ok, its, carry, max_states, round_budget=0, max_calls=1 << 20, cont_states=None,
                            scene=None, margin=None):

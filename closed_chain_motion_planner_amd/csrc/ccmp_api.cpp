@@ -174,6 +174,7 @@ void ccmp_ctx_destroy(ccmp_ctx *ctx)
   if (ctx->knn_ws) (void)hipFree(ctx->knn_ws);
   if (ctx->connect_ws) (void)hipFree(ctx->connect_ws);
   if (ctx->ik_ws) (void)hipFree(ctx->ik_ws);
+  if (ctx->ik_vet_ws) (void)hipFree(ctx->ik_vet_ws);
   if (ctx->queue) (void)hipFree(ctx->queue);
   if (ctx->pool) (void)hipFree(ctx->pool);
   if (ctx->lpt_buf) (void)hipFree(ctx->lpt_buf);

@@ -92,6 +92,8 @@ struct ccmp_ctx {
   size_t connect_ws_cap = 0;           // in edges
   void *ik_ws = nullptr;               // ccmp_pose_ik_batch: the candidates' records, q [C][7] | d2 [C] | rounds [C] (ccmp_launch.h: IkCall)
   size_t ik_ws_cap = 0;                // in candidates
+  void *ik_vet_ws = nullptr;           // ccmp_pose_ik_vetted_batch: cand_clear [C] | slot_clear [T S] | slot_q [T S][14] | slot_has [T S] (ccmp_ik.cpp: ik_vetted_launches)
+  size_t ik_vet_ws_cap = 0;            // in bytes
   void *stage = nullptr;               // device staging of the *_host conveniences
   size_t stage_cap = 0;
   void *pin = nullptr;                 // pinned, device-mapped host block for small *_host calls (single states of the reference signature)
@@ -173,6 +175,13 @@ size_t ik_candidates(size_t T, int S, const ccmp::ik_params &P);
 int ik_reserve(ccmp_ctx *ctx, size_t candidates);
 int ik_launches(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp::ik_params &P, const double *poses, const double *seeds, size_t T, int S, uint64_t rng_seed,
                 uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds, hipStream_t st);
+/* the vetted IK (csrc/ccmp_ik_vet.h), shared with ccmp_roadmap_grow_vetted: what a call checks of its scene and margin; both workspaces
+ * at the call's size; the launches of a checked call — ik_solve, ik_vet, ik_assemble, ccmp_clearance_batch on the slots, ik_pick */
+int ik_vet_checks(const ccmp_ctx *ctx, const ccmp_scene *scene, double margin);
+int ik_vetted_reserve(ccmp_ctx *ctx, size_t T, int S, const ccmp::ik_params &P);
+int ik_vetted_launches(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp::ik_params &P, const double *poses, const double *seeds, size_t T, int S,
+                       uint64_t rng_seed, uint64_t first_index, const ccmp_scene *scene, double margin, double *q_out, uint8_t *ok, int32_t *which,
+                       double *cand_q, int32_t *cand_rounds, double *cand_clear, double *slot_clear, double *clearance, hipStream_t st);
 /* device staging of the *_host conveniences, grown on demand */
 int ensure_stage(ccmp_ctx *ctx, size_t bytes);
 /* the device-visible alias of a caller's host range if all of it is page-locked and mapped (hipHostMalloc,

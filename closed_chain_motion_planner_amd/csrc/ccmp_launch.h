@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; }
+namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -257,6 +257,16 @@ hipError_t object_propose(const ObjectCall &c, const ccmp::object_draw &D, const
                           int32_t *which, double *cand_pose, uint8_t *cand_valid, hipStream_t st);
 hipError_t ik_solve(const IkCall &c, hipStream_t st);
 hipError_t ik_select(const IkCall &c, double *q_out, uint8_t *ok, int32_t *which, hipStream_t st);
+/* the vetted IK (csrc/ccmp_ik_vet.h).  ik_vet: the arm clearance of n_rows rows of seven joints for each of the arms arm0 .. arm0 + n_arms - 1
+ * (the grid's second dimension); per > 0: the rows are a pose-IK call's records, row n = ts per + r of an arm at record (2 ts + arm) per + r,
+ * -inf where rounds < 0; per == 0: the caller's own rows (rounds == nullptr).  ik_assemble: the per-arm rule per slot -> slot_q [slots][14]
+ * (zeros without a state), slot_has.  ik_pick: the first slot with a state and a slot clearance > margin */
+hipError_t ik_vet(const ccmp_consts *K, const ccmp::scene_dev *scene, const ccmp::scene_arm_dev *arms, const double *q7, const int32_t *rounds, size_t n_rows,
+                  int per, int arm0, int n_arms, double margin, double *clear, uint8_t *free_out, hipStream_t st);
+hipError_t ik_assemble(const double *rec_q, const int32_t *rec_rounds, const double *rec_d2, const double *cand_clear, size_t slots, int R, double margin,
+                       double *slot_q, uint8_t *slot_has, hipStream_t st);
+hipError_t ik_pick(const double *slot_q, const uint8_t *slot_has, const double *slot_clear, size_t T, int S, double margin, double *q_out, uint8_t *ok,
+                   int32_t *which, double *clearance, double *slot_out, hipStream_t st);
 /* ccmp_roadmap_grow: seeds[q][r] = the store's joint row nbr_idx[q][r] (NaN for an empty slot) */
 hipError_t ik_gather_seeds(const double *joints, const int32_t *nbr_idx, size_t slots, double *seeds, hipStream_t st);
 /* ccmp_roadmap_grow: what the traversal sees — masked[q][r] = nbr_idx[q][r] where target q has a state and the neighbour's joint row is

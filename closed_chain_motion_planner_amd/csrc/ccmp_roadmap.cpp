@@ -418,10 +418,12 @@ int ccmp_roadmap_connect(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_sce
 // host synchronisation.  The traversal reads a copy of the neighbours in which a target without a state, and a neighbour without
 // joints, are empty slots, and a copy of the new states in which a missing one is a row of zeros (never an endpoint: all its slots
 // are empty): no NaN reaches a traversal kernel.
-int ccmp_roadmap_grow(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts, const double *query_poses,
-                      size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index, int check_target, int max_states,
-                      int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok, int32_t *ik_which, double *states,
-                      int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream)
+// vet: the IK is ccmp_pose_ik_vetted_batch's (csrc/ccmp_ik_vet.h) on the call's scene and margin, ik_clearance (nullable) its chosen states' clearances
+static int grow_common(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts, const double *query_poses,
+                       size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index, int check_target, int max_states,
+                       int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok, int32_t *ik_which, double *states,
+                       int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream, bool vet,
+                       double *ik_clearance)
 {
   { const int rc = knn_checks(rm, CCMP_METRIC_OBJECT, query_poses, Q, k, mode, nbr_idx); if (rc != CCMP_OK) return rc; }
   ccmp_ctx *ctx = rm->ctx;
@@ -429,6 +431,7 @@ int ccmp_roadmap_grow(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene 
   ccmp::ik_params P;
   { const int rc = ik_checks(p, opts, Q, k, &P); if (rc != CCMP_OK) return rc; }
   if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  if (vet) { const int rc = ik_vet_checks(ctx, scene, margin); if (rc != CCMP_OK) return rc; }
   if (Q == 0) return CCMP_OK;
   if (!q_new || !ik_ok || !ik_which) return CCMP_EINVAL;
   { const int rc = connect_checks(ctx, p, scene, margin, max_states, states, n_states, ok, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; }
@@ -440,15 +443,40 @@ int ccmp_roadmap_grow(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene 
   { const int rc = grow_buffer(ctx, &ctx->knn_ws, &ctx->knn_ws_cap, s.workspace_bytes, s.workspace_bytes); if (rc != CCMP_OK) return rc; }
   { const int rc = grow_buffer(ctx, (void **)&ctx->connect_ws, &ctx->connect_ws_cap, E, E * 28 * sizeof(double)); if (rc != CCMP_OK) return rc; }
   { const int rc = grow_buffer(ctx, &rm->grow_ws, &rm->grow_ws_cap, E, E * (28 * sizeof(double) + sizeof(int32_t))); if (rc != CCMP_OK) return rc; }
-  { const int rc = ik_reserve(ctx, ik_candidates(Q, k, P)); if (rc != CCMP_OK) return rc; }
+  { const int rc = vet ? ik_vetted_reserve(ctx, Q, k, P) : ik_reserve(ctx, ik_candidates(Q, k, P)); if (rc != CCMP_OK) return rc; }
   double *seeds = (double *)rm->grow_ws, *q_trav = seeds + E * 14; // Q <= E rows
   int32_t *masked = (int32_t *)(seeds + E * 28);
   { const int rc = knn_object(rm, query_poses, Q, k, mode, self_base, nbr_idx, nbr_dist, st); if (rc != CCMP_OK) return rc; }
   HIP_TRY(ccmp_launch::ik_gather_seeds(rm->joints, nbr_idx, E, seeds, st));
-  { const int rc = ik_launches(ctx, p, P, query_poses, seeds, Q, k, rng_seed, first_index, q_new, ik_ok, ik_which, nullptr, nullptr, st); if (rc != CCMP_OK) return rc; }
+  {
+    const int rc = vet ? ik_vetted_launches(ctx, p, P, query_poses, seeds, Q, k, rng_seed, first_index, scene, margin, q_new, ik_ok, ik_which, nullptr, nullptr,
+                                            nullptr, nullptr, ik_clearance, st)
+                       : ik_launches(ctx, p, P, query_poses, seeds, Q, k, rng_seed, first_index, q_new, ik_ok, ik_which, nullptr, nullptr, st);
+    if (rc != CCMP_OK) return rc;
+  }
   HIP_TRY(ccmp_launch::ik_grow_prepare(rm->joints, nbr_idx, ik_ok, q_new, Q, k, masked, q_trav, st));
   return connect_edges(ctx, p, scene, margin, rm->joints, q_trav, Q, k, check_target, max_states, round_budget, masked, states, n_states, ok, newton_iters,
                        blocked, carry_out, hip_stream);
+}
+
+int ccmp_roadmap_grow(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts, const double *query_poses,
+                      size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index, int check_target, int max_states,
+                      int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok, int32_t *ik_which, double *states,
+                      int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out, void *hip_stream)
+{
+  return grow_common(rm, p, scene, margin, opts, query_poses, Q, k, mode, self_base, rng_seed, first_index, check_target, max_states, round_budget, nbr_idx,
+                     nbr_dist, q_new, ik_ok, ik_which, states, n_states, ok, newton_iters, blocked, carry_out, hip_stream, false, nullptr);
+}
+
+// ccmp_roadmap_grow with the vetted IK in place of the plain one: the scene is required and serves the IK and the traversals under the one margin
+int ccmp_roadmap_grow_vetted(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                             const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index, int check_target,
+                             int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok, int32_t *ik_which,
+                             double *ik_clearance, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out,
+                             void *hip_stream)
+{
+  return grow_common(rm, p, scene, margin, opts, query_poses, Q, k, mode, self_base, rng_seed, first_index, check_target, max_states, round_budget, nbr_idx,
+                     nbr_dist, q_new, ik_ok, ik_which, states, n_states, ok, newton_iters, blocked, carry_out, hip_stream, true, ik_clearance);
 }
 
 // the host form of set_joints (growTree hands over the result of its IK): synchronous on the context's stream
@@ -575,14 +603,16 @@ int ccmp_roadmap_connect_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccm
   return sg.finish(rc);
 }
 
-int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
-                           const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
-                           int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
-                           int32_t *ik_which, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out)
+static int grow_host_common(const char *entry, ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                            const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
+                            int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
+                            int32_t *ik_which, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out,
+                            bool vet, double *ik_clearance)
 {
   { const int rc = knn_checks(rm, CCMP_METRIC_OBJECT, query_poses, Q, k, mode, nbr_idx); if (rc != CCMP_OK) return rc; }
   if (!p || k > CCMP_IK_MAX_SEEDS) return CCMP_EINVAL;
   { ccmp::ik_params P; const int rc = ik_checks(p, opts, Q, k, &P); if (rc != CCMP_OK) return rc; }
+  if (vet) { const int rc = ik_vet_checks(rm->ctx, scene, margin); if (rc != CCMP_OK) return rc; }
   if (Q == 0) return CCMP_OK;
   if (!q_new || !ik_ok || !ik_which) return CCMP_EINVAL;
   { const int rc = connect_checks(rm->ctx, p, scene, margin, max_states, states, n_states, ok, carry_out, round_budget, check_target); if (rc != CCMP_OK) return rc; } // before any buffer is touched
@@ -590,18 +620,18 @@ int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_s
   if (!guard.ok) return CCMP_ENODEV;
   ccmp_ctx *ctx = rm->ctx;
   const size_t E = Q * (size_t)k, pb = Q * 8 * sizeof(double), sb = E * (size_t)max_states * 14 * sizeof(double);
-  StagedCall sg(ctx, __func__);
+  StagedCall sg(ctx, entry);
   const size_t off_p = sg.add(pb), off_i = sg.add(E * sizeof(int32_t)), off_d = sg.add(E * sizeof(double)), off_q = sg.add(Q * 14 * sizeof(double)),
                off_io = sg.add(Q), off_iw = sg.add(Q * sizeof(int32_t)), off_st = sg.add(sb), off_n = sg.add(E * sizeof(int32_t)), off_ok = sg.add(E),
-               off_it = sg.add(E * sizeof(int32_t)), off_bl = sg.add(E), off_co = sg.add(E * 2 * sizeof(double));
+               off_it = sg.add(E * sizeof(int32_t)), off_bl = sg.add(E), off_co = sg.add(E * 2 * sizeof(double)), off_ic = sg.add(ik_clearance ? Q * sizeof(double) : 0);
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; }
   sg.up(off_p, query_poses, pb);
   int rc = CCMP_OK;
   if (sg.copy_ok())
-    rc = ccmp_roadmap_grow(rm, p, scene, margin, opts, sg.at<const double>(off_p), Q, k, mode, self_base, rng_seed, first_index, check_target, max_states,
-                           round_budget, sg.at<int32_t>(off_i), sg.at<double>(off_d, nbr_dist), sg.at<double>(off_q), sg.at<uint8_t>(off_io),
-                           sg.at<int32_t>(off_iw), sg.at<double>(off_st), sg.at<int32_t>(off_n), sg.at<uint8_t>(off_ok), sg.at<int32_t>(off_it, newton_iters),
-                           sg.at<uint8_t>(off_bl, blocked), sg.at<double>(off_co, carry_out), ctx->stream);
+    rc = grow_common(rm, p, scene, margin, opts, sg.at<const double>(off_p), Q, k, mode, self_base, rng_seed, first_index, check_target, max_states,
+                     round_budget, sg.at<int32_t>(off_i), sg.at<double>(off_d, nbr_dist), sg.at<double>(off_q), sg.at<uint8_t>(off_io),
+                     sg.at<int32_t>(off_iw), sg.at<double>(off_st), sg.at<int32_t>(off_n), sg.at<uint8_t>(off_ok), sg.at<int32_t>(off_it, newton_iters),
+                     sg.at<uint8_t>(off_bl, blocked), sg.at<double>(off_co, carry_out), ctx->stream, vet, sg.at<double>(off_ic, ik_clearance));
   if (rc == CCMP_OK) {
     sg.down(nbr_idx, off_i, E * sizeof(int32_t));
     sg.down(nbr_dist, off_d, E * sizeof(double));
@@ -614,8 +644,28 @@ int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_s
     sg.down(newton_iters, off_it, E * sizeof(int32_t));
     sg.down(blocked, off_bl, E);
     sg.down(carry_out, off_co, E * 2 * sizeof(double));
+    sg.down(ik_clearance, off_ic, Q * sizeof(double));
   }
   return sg.finish(rc);
+}
+
+int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                           const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
+                           int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
+                           int32_t *ik_which, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out)
+{
+  return grow_host_common(__func__, rm, p, scene, margin, opts, query_poses, Q, k, mode, self_base, rng_seed, first_index, check_target, max_states,
+                          round_budget, nbr_idx, nbr_dist, q_new, ik_ok, ik_which, states, n_states, ok, newton_iters, blocked, carry_out, false, nullptr);
+}
+
+int ccmp_roadmap_grow_vetted_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                                  const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
+                                  int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
+                                  int32_t *ik_which, double *ik_clearance, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters,
+                                  uint8_t *blocked, double *carry_out)
+{
+  return grow_host_common(__func__, rm, p, scene, margin, opts, query_poses, Q, k, mode, self_base, rng_seed, first_index, check_target, max_states,
+                          round_budget, nbr_idx, nbr_dist, q_new, ik_ok, ik_which, states, n_states, ok, newton_iters, blocked, carry_out, true, ik_clearance);
 }
 
 // ---- the graph: edges, components, growTree's tail, closestFromGoal's scan (ccmp_graph.h) ------------------------------------------------

@@ -58,14 +58,12 @@ double clearance_magnitude_bound(const ccmp_problem &p, const ccmp_scene &sc)
 
 }  // namespace
 
-extern "C" {
+namespace ccmp_host {
 
-int ccmp_scene_create(ccmp_ctx *ctx, const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes,
-                      const uint32_t allowed[32], ccmp_scene **out)
+int scene_tables(const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes, const uint32_t allowed[32], scene_dev &H,
+                 ccmp::scene_arm_dev &A)
 {
-  if (!out) return CCMP_EINVAL;
-  *out = nullptr;
-  if (!ctx || n_spheres < 0 || n_spheres > CCMP_MAX_SPHERES || n_boxes < 0 || n_boxes > CCMP_MAX_BOXES) return CCMP_EINVAL;
+  if (n_spheres < 0 || n_spheres > CCMP_MAX_SPHERES || n_boxes < 0 || n_boxes > CCMP_MAX_BOXES) return CCMP_EINVAL;
   if ((n_spheres > 0 && !spheres) || (n_boxes > 0 && !boxes)) return CCMP_EINVAL;
   for (int i = 0; i < n_spheres; i++) {
     const ccmp_sphere &s = spheres[i];
@@ -79,10 +77,6 @@ int ccmp_scene_create(ccmp_ctx *ctx, const ccmp_sphere *spheres, int n_spheres, 
     for (int k = 0; k < 9; k++)
       if (!std::isfinite(x.R[k])) return CCMP_EINVAL;
   }
-  ccmp_scene *sc = new (std::nothrow) ccmp_scene();
-  if (!sc) return CCMP_ENOMEM;
-  sc->device = ctx->device;
-  scene_dev &H = sc->host;
   memset(&H, 0, sizeof H);
   H.n_spheres = n_spheres;
   H.n_boxes = n_boxes;
@@ -132,6 +126,34 @@ int ccmp_scene_create(ccmp_ctx *ctx, const ccmp_sphere *spheres, int n_spheres, 
       np++;
     }
   H.n_pairs = np;
+  // the per-arm lists: a pair belongs to arm a unless one of its spheres moves on the other arm
+  A.n_pairs[0] = A.n_pairs[1] = 0;
+  for (int k = 0; k < np; k++) {
+    const int i = (int)(H.pair_ij[k] & 0xffu), j = (int)(H.pair_ij[k] >> 8);
+    int moves = ccmp::scene_moving_arm(H.slot[i]) >= 0 ? 1 << ccmp::scene_moving_arm(H.slot[i]) : 0;
+    if (j < CCMP_MAX_SPHERES && ccmp::scene_moving_arm(H.slot[j]) >= 0) moves |= 1 << ccmp::scene_moving_arm(H.slot[j]);
+    for (int a = 0; a < 2; a++)
+      if (!(moves & (2 >> a))) A.pair[a][A.n_pairs[a]++] = (uint16_t)k;
+  }
+  return CCMP_OK;
+}
+
+}  // namespace ccmp_host
+
+extern "C" {
+
+int ccmp_scene_create(ccmp_ctx *ctx, const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes,
+                      const uint32_t allowed[32], ccmp_scene **out)
+{
+  if (!out) return CCMP_EINVAL;
+  *out = nullptr;
+  if (!ctx) return CCMP_EINVAL;
+  ccmp_scene *sc = new (std::nothrow) ccmp_scene();
+  if (!sc) return CCMP_ENOMEM;
+  sc->device = ctx->device;
+  scene_dev &H = sc->host;
+  { const int rc = scene_tables(spheres, n_spheres, boxes, n_boxes, allowed, H, sc->arm_host); if (rc != CCMP_OK) { delete sc; return rc; } }
+  const int np = H.n_pairs;
   // the scene's share of clearance_magnitude_bound
   for (int i = 0; i < n_spheres; i++) {
     const int f = spheres[i].frame;
@@ -151,8 +173,11 @@ int ccmp_scene_create(ccmp_ctx *ctx, const ccmp_sphere *spheres, int n_spheres, 
   ccmp_host::quiesce(ctx);
   hipError_t e = hipMalloc((void **)&sc->dev, sizeof(scene_dev));
   if (e == hipSuccess) e = hipMemcpy(sc->dev, &H, sizeof(scene_dev), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void **)&sc->arm_dev, sizeof(ccmp::scene_arm_dev));
+  if (e == hipSuccess) e = hipMemcpy(sc->arm_dev, &sc->arm_host, sizeof(ccmp::scene_arm_dev), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     if (sc->dev) (void)hipFree(sc->dev);
+    if (sc->arm_dev) (void)hipFree(sc->arm_dev);
     delete sc;
     return hip_fail(e, "ccmp_scene_create");
   }
@@ -168,6 +193,7 @@ void ccmp_scene_destroy(ccmp_scene *scene)
     DeviceGuard guard(scene->device);
     if (scene->ctx && ccmp_host::context_alive(scene->ctx)) ccmp_host::quiesce(scene->ctx);
     if (scene->dev) (void)hipFree(scene->dev);
+    if (scene->arm_dev) (void)hipFree(scene->arm_dev);
   }
   delete scene;
 }

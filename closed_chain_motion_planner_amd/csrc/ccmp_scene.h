@@ -31,6 +31,17 @@ struct scene_dev {
   double pair_rsum[kSceneMaxPairs]; /* r_i + r_j (sphere-sphere) or r_i (sphere-box): what is subtracted from the distance */
 };
 
+/* Derived from scene_dev for the vetted IK (csrc/ccmp_ik_vet.h): the tested pairs of ONE arm — those that contain no sphere moving on
+ * the other arm (frame slots 9 a' .. 9 a' + 7) — as positions in scene_dev's pair table, ascending.  The two lists and the cross pairs
+ * (one sphere moving on each arm) partition the table.  A table of its own: scene_dev's layout is what every scene kernel reads. */
+struct scene_arm_dev {
+  int32_t n_pairs[2];
+  uint16_t pair[2][kSceneMaxPairs];
+};
+/* the arm a sphere on frame slot `slot` moves with (slots 9 a .. 9 a + 7: the bodies and the hand), -1 for a static one (a base, the world) */
+constexpr int scene_moving_arm(int slot) { return slot == kSceneSlots - 1 || slot % 9 == 8 ? -1 : slot / 9; }
+static_assert(kSceneMaxPairs < 65536, "scene_arm_dev keeps pair positions in 16 bits");
+
 }  // namespace ccmp
 
 struct ccmp_scene {
@@ -38,11 +49,20 @@ struct ccmp_scene {
   ccmp_ctx *ctx = nullptr; // the context the scene was created on: its resident service kernel is stopped before the scene's hipFree (ccmp_resident.h rule 2); the context must outlive the scene or be destroyed first with the service off
   ccmp::scene_dev host;
   ccmp::scene_dev *dev = nullptr;
+  ccmp::scene_arm_dev arm_host; // the per-arm pair lists (ik_vet_kernel); filled by ccmp_scene_create with the tables above
+  ccmp::scene_arm_dev *arm_dev = nullptr;
   // The scene's share of the bound on `best + rsum` (ccmp_scene.cpp: clearance_magnitude_bound; the tile kernel's prune holds below
   // 2^22 only): the largest |centre| of the spheres on each kind of frame, in that frame (-1: none there), the largest pair_rsum,
   // and over the boxes the largest |centre| and the largest max(1, |R|_F)
   double c_world = -1.0, c_base[2] = {-1.0, -1.0}, c_moving[2] = {-1.0, -1.0};
   double rsum_max = 0.0, box_c = 0.0, box_gain = 1.0;
 };
+
+namespace ccmp_host {
+/* what ccmp_scene_create checks of the caller's arrays and the tables it derives from them (no device): shared with the *_ref forms
+ * that take a scene as the caller's arrays (ccmp_arm_clearance_ref, ccmp_pose_ik_vetted_ref) */
+int scene_tables(const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes, const uint32_t allowed[32], ccmp::scene_dev &H,
+                 ccmp::scene_arm_dev &A);
+}  // namespace ccmp_host
 
 #endif /* CCMP_SCENE_H */

@@ -266,33 +266,42 @@ class Roadmap:
         return out
 
     def grow(self, query_poses, k, mode=0, self_base=0, rng_seed=0, first_index=0, opts=None, check_target=False, max_states=64, round_budget=0,
-             scene=None, margin=None, stream=None):
+             scene=None, margin=None, stream=None, vet=False):
         """growTree's device part for the poses `query_poses` (Q,8) in one call (ccmp_roadmap_grow): the object-metric k-NN on the store,
         the neighbours' joints as seed slots in rank order, `KinematicChainConstraint.pose_ik_batch` on them, then edge e = q * k + r
         from neighbour r to the new state as `connect` runs its edges (check_target False: growTree's discreteGeodesic).  Returns
         `connect`'s dict plus q_new (Q,14), ik_ok (Q,), ik_which (Q,).  A pose without a state (and a neighbour without joints) has
-        empty slots.  Nothing is appended: the reference adds the vertex only after an edge succeeded."""
+        empty slots.  Nothing is appended: the reference adds the vertex only after an edge succeeded.
+        vet=True with a scene: ccmp_roadmap_grow_vetted — the IK vets its candidates and the assembled state against the scene under the
+        same margin as the traversals (IKValid inside sampleCalibGoal, on proxies), and the dict also holds ik_clearance (Q,)."""
         from .ik import ik_options
 
         Q, k, ms = len(query_poses), int(k), int(max_states)
         E = Q * k
         opts = opts if opts is not None else ik_options()
+        vet = bool(vet) and scene is not None
         shapes = {"nbr_idx": ((Q, k), "int32"), "nbr_dist": ((Q, k), "float64"), "q_new": ((Q, 14), "float64"), "ik_ok": ((Q,), "uint8"),
-                  "ik_which": ((Q,), "int32"), "states": ((E, ms, 14), "float64"), "n_states": ((E,), "int32"), "ok": ((E,), "uint8"),
-                  "newton_iters": ((E,), "int32"), "blocked": ((E,), "uint8"), "carry": ((E, 2), "float64")}
+                  "ik_which": ((Q,), "int32")}
+        if vet:
+            shapes["ik_clearance"] = ((Q,), "float64")
+        shapes.update({"states": ((E, ms, 14), "float64"), "n_states": ((E,), "int32"), "ok": ((E,), "uint8"),
+                       "newton_iters": ((E,), "int32"), "blocked": ((E,), "uint8"), "carry": ((E, 2), "float64")})
         order = list(shapes)
+        L = _lib.lib()
+        grow_host, grow_dev = (L.ccmp_roadmap_grow_vetted_host, L.ccmp_roadmap_grow_vetted) if vet else (L.ccmp_roadmap_grow_host, L.ccmp_roadmap_grow)
+        what = "ccmp_roadmap_grow_vetted" if vet else "ccmp_roadmap_grow"
         head = (self._h, self._problem(), scene._h if scene is not None else None, float(margin) if scene is not None else 0.0, C.byref(opts))
         tail = (Q, k, int(mode), int(self_base), int(rng_seed), int(first_index), 1 if check_target else 0, ms, int(round_budget))
         if isinstance(query_poses, np.ndarray):
             qp = _host(query_poses, 8)
             out = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()}
             ptr = lambda n: out[n].ctypes.data_as({"int32": C.POINTER(C.c_int32), "float64": _dp, "uint8": C.POINTER(C.c_uint8)}[shapes[n][1]])
-            check(_lib.lib().ccmp_roadmap_grow_host(*head, qp.ctypes.data_as(_dp), *tail, *[ptr(n) for n in order]), "ccmp_roadmap_grow_host")
+            check(grow_host(*head, qp.ctypes.data_as(_dp), *tail, *[ptr(n) for n in order]), what + "_host")
             return out
         torch = _torch()
         qp = _dev(query_poses, 8)
         out = {n: torch.empty(s, dtype=getattr(torch, d), device=qp.device) for n, (s, d) in shapes.items()}
-        check(_lib.lib().ccmp_roadmap_grow(*head, qp.data_ptr(), *tail, *[out[n].data_ptr() for n in order], _stream_handle(stream)), "ccmp_roadmap_grow")
+        check(grow_dev(*head, qp.data_ptr(), *tail, *[out[n].data_ptr() for n in order], _stream_handle(stream)), what)
         return out
 
     def grow_toward(self, checker, from_poses, goal_pose, k, t=0.3, sigma=0.2, lo=None, hi=None, attempts=2, rng_seed=0, first_index=0, inflate=0.0,

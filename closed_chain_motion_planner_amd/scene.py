@@ -20,7 +20,7 @@ from . import _lib
 from ._lib import CcmpBox, CcmpSphere, check
 
 __all__ = ["FRAME_WORLD", "frame", "ProxyScene", "ProxyValidityChecker", "skeleton_spheres", "default_allowed", "allow",
-           "object_points_to_hand", "decode_pair", "GROUP_OBJECT", "GROUP_ENVIRONMENT"]
+           "object_points_to_hand", "decode_pair", "GROUP_OBJECT", "GROUP_ENVIRONMENT", "scene_arrays", "arm_clearance_ref"]
 
 FRAME_WORLD = -1
 MAX_SPHERES = 64
@@ -118,6 +118,33 @@ def decode_pair(code):
     return (i, ("sphere", j) if j < MAX_SPHERES else ("box", j - MAX_SPHERES))
 
 
+def scene_arrays(spheres, boxes=(), allowed=None):
+    """the caller's scene as the C arrays ccmp_scene_create and the *_ref forms take: (ccmp_sphere[], n, ccmp_box[], n, uint32[32] or None)"""
+    sa = (CcmpSphere * max(1, len(spheres)))()
+    for k, (f, g, c, r) in enumerate(spheres):
+        sa[k] = CcmpSphere(int(f), int(g), (C.c_double * 3)(*[float(v) for v in c]), float(r))
+    ba = (CcmpBox * max(1, len(boxes)))()
+    for k, (g, c, R, h) in enumerate(boxes):
+        ba[k] = CcmpBox(int(g), 0, (C.c_double * 3)(*[float(v) for v in c]), (C.c_double * 9)(*np.asarray(R, dtype=np.float64).reshape(9)),
+                        (C.c_double * 3)(*[float(v) for v in h]))
+    al = None if allowed is None else (C.c_uint32 * 32)(*[int(v) & 0xFFFFFFFF for v in allowed])
+    return sa, len(spheres), ba, len(boxes), al
+
+
+def arm_clearance_ref(problem, spheres, boxes, allowed, arm, q7, margin=0.0):
+    """ccmp_arm_clearance_ref: IKValid(arm, q7) on the proxies, the kernels' text on the host, no device.  q7 (7,) or (B,7) ->
+    (clearance, free) as numpy (scalars for one row)"""
+    q = np.ascontiguousarray(q7, dtype=np.float64)
+    single = q.ndim == 1
+    q = q.reshape(-1, 7)
+    B = q.shape[0]
+    clr, free = np.empty(B), np.empty(B, dtype=np.uint8)
+    dp = C.POINTER(C.c_double)
+    check(_lib.lib().ccmp_arm_clearance_ref(C.byref(problem), *scene_arrays(spheres, boxes, allowed), int(arm), q.ctypes.data_as(dp), B, float(margin),
+                                            clr.ctypes.data_as(dp), free.ctypes.data_as(C.POINTER(C.c_uint8))), "ccmp_arm_clearance_ref")
+    return (float(clr[0]), bool(free[0])) if single else (clr, free)
+
+
 class ProxyScene:
     """ccmp_scene.  spheres: (frame, group, centre(3), radius); boxes: (group, centre(3), R(3x3), half(3))."""
 
@@ -180,6 +207,40 @@ class ProxyScene:
         if single:
             return float(clr[0]), int(pair[0]), bool(free[0])
         return clr, pair, free
+
+    def arm_clearance_batch(self, arm, q7, margin=0.0, stream=None):
+        """IKValid(arm, q7) on the proxies (ccmp_arm_clearance_*): the clearance of arm `arm` alone at seven joints, over the tested pairs
+        that hold no sphere moving on the other arm.  A (B,7) float64 CUDA tensor -> (clearance (B,), free (B,) u8) tensors on `stream`;
+        a numpy array (7,) or (B,7) -> numpy through the host form (scalars for one row)"""
+        c = self.constraint
+        c._need_problem()
+        if isinstance(q7, np.ndarray) or not hasattr(q7, "data_ptr"):
+            q = np.ascontiguousarray(q7, dtype=np.float64)
+            single = q.ndim == 1
+            q = q.reshape(-1, 7)
+            B = q.shape[0]
+            clr, free = np.empty(B), np.empty(B, dtype=np.uint8)
+            dp = C.POINTER(C.c_double)
+            check(_lib.lib().ccmp_arm_clearance_host(c.ctx.handle, C.byref(c.problem), self._h, int(arm), q.ctypes.data_as(dp), B, float(margin),
+                                                     clr.ctypes.data_as(dp), free.ctypes.data_as(C.POINTER(C.c_uint8))), "ccmp_arm_clearance_host")
+            return (float(clr[0]), bool(free[0])) if single else (clr, free)
+        import torch
+
+        from .constraint import _stream_handle
+
+        if not (q7.is_cuda and q7.dtype == torch.float64 and q7.is_contiguous() and q7.ndim == 2 and q7.shape[1] == 7):
+            raise ValueError("q7: expected a contiguous (B, 7) float64 tensor on the device")
+        B = q7.shape[0]
+        clr = torch.empty(B, dtype=torch.float64, device=q7.device)
+        free = torch.empty(B, dtype=torch.uint8, device=q7.device)
+        check(_lib.lib().ccmp_arm_clearance_batch(c.ctx.handle, C.byref(c.problem), self._h, int(arm), q7.data_ptr(), B, float(margin), clr.data_ptr(),
+                                                  free.data_ptr(), _stream_handle(stream)), "ccmp_arm_clearance_batch")
+        return clr, free
+
+    def arm_clearance_ref(self, arm, q7, margin=0.0):
+        """the same on the host, no device (ccmp_arm_clearance_ref on this scene's own arrays)"""
+        self.constraint._need_problem()
+        return arm_clearance_ref(self.constraint.problem, self.spheres, self.boxes, self.allowed, arm, q7, margin)
 
     def close(self):
         if self._h:

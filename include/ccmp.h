@@ -705,6 +705,70 @@ int ccmp_roadmap_grow_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_s
                            int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
                            int32_t *ik_which, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out);
 
+/* ---- pose IK vetted against the proxy scene: IKValid and si_->isValid where the reference has them ---------------------------------- */
+/* The reference gates every IK candidate with a collision test: sampleCalibGoal's _solveCalibIK / _randomsolveCalibIK are
+ * ik_task_->solve(...) && IKvc_->IKValid(arm_idx, solution) (jy_ConstrainedValidStateSampler.h:192-199; IKValid is a collision test of
+ * that one arm, KinematicChain.cpp:129-161, req.group_name = arm), and the function ends in si_->isValid(result) on the assembled
+ * 14-joint state (:188).  Hence a seeded solution that collides loses to a restart that does not; among the restarts only collision-free
+ * ones compete for "closest to the seed"; and growTree tries the next neighbour when the assembled state collides
+ * (stefanBiPRM.cpp:294-302).  ccmp_pose_ik_* restate the rule WITHOUT the gate; these calls restate it WITH the gate, on the PROXY SCENE
+ * (ccmp_scene_create) — this library's stand-in for MoveIt everywhere else, NOT MoveIt: si_->isValid(result) on the state they return
+ * stays a host call.  csrc/ccmp_ik_vet.h states the rule in full:
+ *   arm clearance   of arm a at seven joints: the smallest signed distance over the scene's tested pairs that contain no sphere moving on
+ *                   the OTHER arm (a sphere moves on arm a on CCMP_FRAME(a, 0..7); world and base spheres are static); boxes included;
+ *                   +inf for an empty set, NaN for a non-finite joint.  ccmp_clearance's arithmetic: bit-identical to ccmp_clearance_* on
+ *                   the sub-scene made of the caller's spheres minus those moving on the other arm (whose seven joints are then free).
+ *                   The scene's pairs are arm 0's, arm 1's and the cross pairs: full clearance = min(arm 0, arm 1, cross).
+ *   admissible      a candidate that converged and whose arm clearance > margin (the rule of free_out)
+ *   per arm         candidate 0 if admissible, else the admissible restart closest to the seed (ties to the lowest r), else failure
+ *   slot            assembled when both arms succeed; it succeeds iff the full ccmp_clearance of its 14-joint row > margin (:188 — what
+ *                   catches the cross pairs); the first slot that succeeds is the answer, else a NaN row, ok = 0, which = -1
+ * HOW THIS DIFFERS FROM MoveIt's IKValid: the reference tests the arm against a robot state that still holds whatever the other arm was
+ * last set to; here the arm is tested ALONE, and the pair of arms is tested on the assembled state.
+ * margin = -inf gives ccmp_pose_ik_*'s answer bit for bit, margin = +inf fails every target; wherever the unvetted answer's own full
+ * clearance is > margin the vetted answer is the same row, ok and which: vetting only ever adds solved targets.
+ * ccmp_arm_clearance_*: IKValid(arm_index, sol) as a call of its own — q7 [B][7], clearance [B], free_out [B] (nullable) = clearance >
+ * margin.  ccmp_pose_ik_vetted_*: ccmp_pose_ik_*'s arguments and outputs, plus (all nullable)
+ *   cand_clear [T][S][2][1 + R]   the arm clearance of each converged candidate; -inf for one that did not converge or was skipped
+ *   slot_clear [T][S]             the slot clearance; NaN where the slot was not assembled
+ *   clearance [T]                 the chosen state's full clearance; NaN on failure
+ * The *_batch forms take device pointers and are asynchronous on hip_stream (ccmp_pose_ik_vetted_batch: capturable after one eager call
+ * at that size; candidate clearances and slot states live in a workspace of the context); the *_host forms take host pointers and are
+ * synchronous on the context's stream; the *_ref forms are the same text compiled for the host, take the scene as the caller's arrays
+ * (as ccmp_scene_create does), need no device and never answer CCMP_ENODEV.  Every check runs before the first launch.  CCMP_EINVAL:
+ * what ccmp_pose_ik_* / ccmp_scene_create refuse, a NULL scene, a scene of another device, a NaN margin, arm outside 0..1.  A NULL context
+ * is CCMP_ENODEV on a machine without a HIP device and CCMP_EINVAL otherwise. */
+int ccmp_arm_clearance_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, int arm, const double *q7, size_t B, double margin,
+                             double *clearance, uint8_t *free_out, void *hip_stream);
+int ccmp_arm_clearance_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, int arm, const double *q7, size_t B, double margin,
+                            double *clearance, uint8_t *free_out);
+int ccmp_arm_clearance_ref(const ccmp_problem *p, const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes, const uint32_t allowed[32],
+                           int arm, const double *q7, size_t B, double margin, double *clearance, uint8_t *free_out);
+int ccmp_pose_ik_vetted_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
+                              uint64_t rng_seed, uint64_t first_index, const ccmp_scene *scene, double margin, double *q_out, uint8_t *ok, int32_t *which,
+                              double *cand_q, int32_t *cand_rounds, double *cand_clear, double *slot_clear, double *clearance, void *hip_stream);
+int ccmp_pose_ik_vetted_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
+                             uint64_t rng_seed, uint64_t first_index, const ccmp_scene *scene, double margin, double *q_out, uint8_t *ok, int32_t *which,
+                             double *cand_q, int32_t *cand_rounds, double *cand_clear, double *slot_clear, double *clearance);
+int ccmp_pose_ik_vetted_ref(const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
+                            uint64_t rng_seed, uint64_t first_index, const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes,
+                            const uint32_t allowed[32], double margin, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds,
+                            double *cand_clear, double *slot_clear, double *clearance);
+/* ccmp_roadmap_grow with the vetted IK in place of the plain one (growTree with IKValid inside sampleCalibGoal, stefanBiPRM.cpp:294-302),
+ * plus ik_clearance [Q] (nullable): the new states' full clearances, NaN for a target without a state.  scene is REQUIRED and serves both
+ * the IK and the traversals under the one margin; everything else — the gather, the empty-slot rule, the traversal chain — is
+ * ccmp_roadmap_grow's.  CCMP_EINVAL additionally for a NULL scene or a NaN margin. */
+int ccmp_roadmap_grow_vetted(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                             const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index, int check_target,
+                             int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok, int32_t *ik_which,
+                             double *ik_clearance, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out,
+                             void *hip_stream);
+int ccmp_roadmap_grow_vetted_host(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_ik_opts *opts,
+                                  const double *query_poses, size_t Q, int k, int mode, size_t self_base, uint64_t rng_seed, uint64_t first_index,
+                                  int check_target, int max_states, int round_budget, int32_t *nbr_idx, double *nbr_dist, double *q_new, uint8_t *ik_ok,
+                                  int32_t *ik_which, double *ik_clearance, double *states, int32_t *n_states, uint8_t *ok, int32_t *newton_iters,
+                                  uint8_t *blocked, double *carry_out);
+
 /* ---- the head of growTree: object-pose proposal and the mesh-against-workspace test ------------------------------------------------ */
 /* What the reference does before it grows (stefanBiPRM.cpp:255-276): interpolate the object pose 30 % from the nearest vertex towards the
  * goal, draw an SE(3) Gaussian sample around that (sigma 0.2, two attempts), ask stefan_checker_->isValid, and only then call

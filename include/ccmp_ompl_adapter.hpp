@@ -76,6 +76,8 @@ inline uint64_t next_sampler_seed()
   return splitmix64(process_seed + counter.fetch_add(1, std::memory_order_relaxed));
 }
 
+class ProxyScene; // the proxy pre-filter, below: the vetted sampleCalibGoal takes one
+
 // Owner of one execution context and one problem description.  The drop-in KinematicChainConstraint is touched from
 // more than one thread in the reference (the jy_GoalLazySamples sampling thread; checkForSolution beside
 // constructRoadmap, src/planner/stefanBiPRM.cpp:848) and one ccmp_ctx holds per-call state (pinned I/O block, queue
@@ -209,6 +211,18 @@ public:
     if (which) *which = slot;
     return ok != 0;
   }
+  // The same with the collision gates the reference has INSIDE sampleCalibGoal (jy_ConstrainedValidStateSampler.h:188,192-199), on the
+  // PROXY scene (ccmp_pose_ik_vetted_host): a candidate of an arm counts only if that arm's clearance exceeds `margin` (IKValid), the
+  // assembled state only if its full clearance does (si_->isValid(result)); a seeded solution that collides loses to a restart that does
+  // not, and a refused slot hands over to the next seed.  Proxies, not MoveIt: the exact si_->isValid(result) of the returned state stays
+  // the caller's.  Unlike MoveIt's IKValid, which sees whatever the other arm was last set to, the arm is tested alone and the pair of
+  // arms on the assembled state.  *clearance (nullable): the returned state's clearance, NaN without one.  Same stream, same error rules.
+  bool sampleCalibGoal(const double *pose8, const double *start14, double *result14, const ProxyScene &scene, double margin) const noexcept
+  {
+    return sampleCalibGoal(pose8, start14, 1, result14, nullptr, scene, margin, nullptr);
+  }
+  inline bool sampleCalibGoal(const double *pose8, const double *seeds, int S, double *result14, int *which, const ProxyScene &scene, double margin,
+                              double *clearance = nullptr) const noexcept;
   ccmp_ik_opts &ikOptions() noexcept { return ik_opts_; }
   const ccmp_ik_opts &ikOptions() const noexcept { return ik_opts_; }
   void setIkStream(uint64_t seed, uint64_t next_index = 0) noexcept { ik_seed_ = seed; ik_index_ = next_index; ik_seeded_ = true; }
@@ -679,6 +693,47 @@ public:
     if (!ran) {
       if (q_new14)
         for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
+      return false;
+    }
+    if (ik_which) *ik_which = slot;
+    return ik_ok != 0;
+  }
+
+  // grow() with the vetted IK (ccmp_roadmap_grow_vetted_host): `scene` (required; ProxyScene::handle()) stands where the reference has
+  // IKValid inside sampleCalibGoal and si_->isValid(result) behind it, and serves the traversals too, all under the one `margin`.  With
+  // vet = false this is grow() above with the scene on the traversals alone.  *ik_clearance (nullable): the new state's clearance, NaN
+  // without one.  Proxies, not MoveIt: the caller's exact validity test of the new state stays.  Same outputs, stream and error rules.
+  bool grow(const double *pose8, unsigned k, int max_states, std::vector<int32_t> *idx, double *q_new14, int *ik_which, std::vector<int32_t> *n_states,
+            std::vector<uint8_t> *ok, std::vector<double> *states, const ccmp_scene *scene, double margin, bool vet, double *ik_clearance = nullptr,
+            bool check_target = false, int mode = CCMP_KNN_ALL, size_t self_base = 0) const noexcept
+  {
+    if (ik_clearance) *ik_clearance = std::numeric_limits<double>::quiet_NaN();
+    if (!vet) return grow(pose8, k, max_states, idx, q_new14, ik_which, n_states, ok, states, check_target, scene, margin, mode, self_base);
+    uint8_t ik_ok = 0;
+    int32_t slot = -1;
+    if (q_new14)
+      for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
+    if (ik_which) *ik_which = -1;
+    try {
+      idx->assign(k, -1);
+      n_states->assign(k, 0);
+      ok->assign(k, 0);
+      states->assign((size_t)k * (size_t)(max_states > 0 ? max_states : 0) * 14, 0.0);
+    } catch (...) {
+      record(CCMP_ENOMEM, "Roadmap::grow");
+      return false;
+    }
+    const bool ran = call([&] {
+      const int rc = ccmp_roadmap_grow_vetted_host(rm_, &proj_.problem(), scene, margin, &proj_.ikOptions(), pose8, 1, (int)k, mode, self_base, proj_.ikSeed(),
+                                                   proj_.ikNextIndex(), check_target ? 1 : 0, max_states, 0, idx->data(), nullptr, q_new14, &ik_ok, &slot,
+                                                   ik_clearance, states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr);
+      if (rc == CCMP_OK) (void)proj_.takeIkIndex();
+      return rc;
+    }, "ccmp_roadmap_grow_vetted_host");
+    if (!ran) {
+      if (q_new14)
+        for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
+      if (ik_clearance) *ik_clearance = std::numeric_limits<double>::quiet_NaN();
       return false;
     }
     if (ik_which) *ik_which = slot;
@@ -1194,6 +1249,36 @@ public:
     std::lock_guard<std::mutex> hold(proj_.mutex());
     check(ccmp_clearance_host(proj_.ctx(), &proj_.problem(), scene_, q, B, margin, clearance, pair, free_out), "ccmp_clearance_host");
   }
+  // KinematicChainValidityChecker::IKValid(arm_index, sol) (KinematicChain.cpp:129-161: a collision test of that ONE arm) on the proxies
+  // (ccmp_arm_clearance_host): true when the clearance of arm `arm` alone at the seven joints q7 — over the tested pairs that hold no
+  // sphere moving on the other arm — exceeds `margin`.  Unlike MoveIt's, which sees whatever the other arm was last set to, the other
+  // arm's links are not part of the test.  *clearance (nullable): the value, NaN when the call failed.  Never throws: false on a failed
+  // call, whose FIRST error stays in lastError() / lastErrorMessage() until clearError().
+  bool ikValid(int arm, const double *q7, double margin = 0.0, double *clearance = nullptr) const noexcept
+  {
+    double clr = std::numeric_limits<double>::quiet_NaN();
+    uint8_t free_flag = 0;
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(proj_.mutex());
+      rc = ccmp_arm_clearance_host(proj_.ctx(), &proj_.problem(), scene_, arm, q7, 1, margin, &clr, &free_flag);
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) {
+      if (err_code_ == CCMP_OK) {
+        err_code_ = rc;
+        try { err_what_ = std::string("ccmp_arm_clearance_host: ") + ccmp_strerror(rc); } catch (...) {}
+      }
+      clr = std::numeric_limits<double>::quiet_NaN();
+      free_flag = 0;
+    }
+    if (clearance) *clearance = clr;
+    return free_flag != 0;
+  }
+  int lastError() const noexcept { return err_code_; }
+  std::string lastErrorMessage() const { return err_what_; }
+  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
   const ccmp_scene *handle() const { return scene_; }
   const Projector &projector() const { return proj_; }
 
@@ -1218,7 +1303,37 @@ public:
 private:
   const Projector &proj_;
   ccmp_scene *scene_ = nullptr;
+  mutable int err_code_ = CCMP_OK; // ikValid's sticky error (the other verbs throw)
+  mutable std::string err_what_;
 };
+
+inline bool Projector::sampleCalibGoal(const double *pose8, const double *seeds, int S, double *result14, int *which, const ProxyScene &scene, double margin,
+                                       double *clearance) const noexcept
+{
+  uint8_t ok = 0;
+  int32_t slot = -1;
+  double clr = std::numeric_limits<double>::quiet_NaN();
+  int rc;
+  try {
+    std::lock_guard<std::mutex> hold(mu_);
+    rc = ccmp_pose_ik_vetted_host(ctx_, &problem_, &ik_opts_, pose8, seeds, 1, S, ikSeed(), ik_index_, scene.handle(), margin, result14, &ok, &slot, nullptr,
+                                  nullptr, nullptr, nullptr, &clr);
+    if (rc == CCMP_OK) ik_index_++;
+  } catch (...) {
+    rc = CCMP_EHIP;
+  }
+  if (rc != CCMP_OK) {
+    record(rc, "ccmp_pose_ik_vetted_host");
+    ok = 0;
+    slot = -1;
+    clr = std::numeric_limits<double>::quiet_NaN();
+    if (result14)
+      for (int i = 0; i < 14; i++) result14[i] = std::numeric_limits<double>::quiet_NaN();
+  }
+  if (which) *which = slot;
+  if (clearance) *clearance = clr;
+  return ok != 0;
+}
 
 // discreteGeodesicBatch with the proxy pre-filter ON THE DEVICE (ccmp_geodesic_scene_host): with interpolate == false the
 // traversal itself refuses a state whose clearance in `scene` does not exceed `margin` — before the step test, where the

@@ -25,6 +25,9 @@
     python tools/measure.py ik [reps_a] [reps_b] [T_b]      pose-targeted IK (growTree's sampleCalibGoal): (a) one pose x 5 seeds x 14 restarts through the host
                                                            form, (b) T_b = 4096 poses x 5 x 14 through the device form, each against ccmp_pose_ik_ref on one
                                                            thread on the same inputs, alternating in one process; histogram of rounds, idle lane-rounds
+    python tools/measure.py ik --scene [reps_a] [reps_b] [T_b]  the vetted IK (ccmp_pose_ik_vetted_*) against today's route, ccmp_pose_ik_* plus one ccmp_clearance_*
+                                                           call on the answers, on the default skeleton scene at -0.03, same two shapes: time, targets solved
+                                                           and clear by each route, the vet kernel's share of the call and its registers / LDS / occupancy
     python tools/measure.py object [reps_a] [reps_b] [G_b]  the head of growTree (object-pose proposal + mesh test): (a) propose with G = 1, 2 attempts, a dumbbell of
                                                            ~1 000 triangles against the six fixture boxes through the host form, (b) G_b = 4096 through the device form,
                                                            (c) valid on 4096 poses of a ~8 600-triangle sphere, each against the *_ref form on one thread on the same inputs
@@ -757,6 +760,8 @@ def ik(argv):
     compared bit for bit while they are timed.  Targets: poses of valid projected states; seeds: their five pose-nearest other states."""
     from closed_chain_motion_planner_amd import Roadmap, pose_ik_ref
 
+    if "--scene" in argv:
+        return ik_scene([a for a in argv if a != "--scene"])
     reps_a = int(argv[0]) if len(argv) > 0 else 30
     reps_b = int(argv[1]) if len(argv) > 1 else 2
     Tb = int(argv[2]) if len(argv) > 2 else 4096
@@ -835,6 +840,94 @@ def ik(argv):
     print("VERDICT pose_ik device forms against one host thread: (a) %.2fx, (b) %.1fx"
           % (np.median(ta["ccmp_pose_ik_ref (one thread)"]) / np.median(ta["host form (device)"]),
              np.median(tb["ccmp_pose_ik_ref (one thread)"]) / np.median(tb["device form"])))
+
+
+def ik_scene(argv):
+    """ik --scene: the vetted call (ccmp_pose_ik_vetted_*) against today's route — ccmp_pose_ik_* and one ccmp_clearance_* call on the answers —
+    on the default skeleton scene at -0.03: time, targets solved by each route, the vet kernel's share of the call and its resources."""
+    from closed_chain_motion_planner_amd import ProxyValidityChecker, Roadmap
+    from closed_chain_motion_planner_amd.build import resource_report
+
+    reps_a = int(argv[0]) if len(argv) > 0 else 30
+    reps_b = int(argv[1]) if len(argv) > 1 else 10
+    Tb = int(argv[2]) if len(argv) > 2 else 4096
+    S, R, seed = 5, 14, 0x1C
+    ctx = Context(0)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    chk = ProxyValidityChecker(c)
+    scene, margin = chk.scene, chk.margin
+    q, ok, _, _ = c.sample_project_batch(seed, 0, 16 * Tb + 4096, want_iters=False)
+    states = q[(ok != 0) & (c.joint_valid_batch(q) != 0)][:Tb + 1024].contiguous()
+    rm = Roadmap(c, states.shape[0])
+    rm.append(joints=states)
+    poses = rm.read()[1]
+    T = min(Tb, states.shape[0])
+    idx, _ = rm.nearest_k(poses[:T].contiguous(), S, mode=_lib.KNN_NOT_SELF)
+    tp, sd = poses[:T].contiguous(), states[idx.long()].contiguous()
+    tph, sdh = tp.cpu().numpy(), sd.cpu().numpy()
+    print("seed 0x%X; %d valid states; %d targets x %d seeds x %d restarts; default skeleton scene (%d tested pairs), margin %g"
+          % (seed, states.shape[0], T, S, R, scene.num_pairs, margin))
+
+    def today_host(t):
+        out = c.pose_ik_batch(tph[t:t + 1], sdh[t:t + 1], rng_seed=seed, first_index=t)
+        return bool(out["ok"][0]) and bool(scene.clearance(np.nan_to_num(out["q"]), margin)[2][0])
+
+    def vetted_host(t):
+        return bool(c.pose_ik_batch(tph[t:t + 1], sdh[t:t + 1], rng_seed=seed, first_index=t, scene=scene, margin=margin)["ok"][0])
+
+    # (a) the planner's shape: one pose per call, host pointers, host clock around the synchronous calls
+    ta = {"today: pose_ik_host + clearance_host": [], "ccmp_pose_ik_vetted_host": []}
+    solved = [0, 0]
+    for i in range(reps_a + 3):
+        t = i % T
+        t0 = time.perf_counter()
+        a = today_host(t)
+        t1 = time.perf_counter()
+        b = vetted_host(t)
+        t2 = time.perf_counter()
+        if i >= 3:
+            ta["today: pose_ik_host + clearance_host"].append((t1 - t0) * 1e3)
+            ta["ccmp_pose_ik_vetted_host"].append((t2 - t1) * 1e3)
+            solved[0] += a
+            solved[1] += b
+    print("(a) 1 pose x %d x %d, host forms, wall clock; solved and clear: today %d, vetted %d of %d" % (S, R, solved[0], solved[1], reps_a))
+    for name, ms in ta.items():
+        print("    %-40s %s" % (name, _stat(ms)))
+
+    # (b) the batch: device pointers, device events, the contenders alternating
+    def today():
+        out = c.pose_ik_batch(tp, sd, rng_seed=seed)
+        free = scene.clearance_batch(torch.nan_to_num(out["q"]), margin, ok=out["ok"], want_pair=False)[2]
+        return out, free
+
+    full = c.pose_ik_batch(tp, sd, rng_seed=seed, want_candidates=True, scene=scene, margin=margin)
+    rounds = full["cand_rounds"]
+    conv = rounds >= 0
+    rows = [full["cand_q"][:, :, a].reshape(-1, 7).contiguous() for a in (0, 1)]
+    packed = [full["cand_q"][:, :, a][conv[:, :, a]].contiguous() for a in (0, 1)]
+    tb = alternate({"today: pose_ik_batch + clearance_batch": today,
+                    "ccmp_pose_ik_vetted_batch": lambda: c.pose_ik_batch(tp, sd, rng_seed=seed, scene=scene, margin=margin),
+                    "ccmp_pose_ik_batch alone": lambda: c.pose_ik_batch(tp, sd, rng_seed=seed),
+                    "ik_vet_kernel on every candidate row": lambda: [scene.arm_clearance_batch(a, rows[a], margin) for a in (0, 1)],
+                    "ik_vet_kernel on the converged rows, packed": lambda: [scene.arm_clearance_batch(a, packed[a], margin) for a in (0, 1)]}, reps_b)
+    out, free = today()
+    torch.cuda.synchronize()
+    n_today, n_vet = int((out["ok"].bool() & free.bool()).sum()), int(full["ok"].sum())
+    print("(b) %d poses x %d x %d, device forms, device events" % (T, S, R))
+    for name, ms in tb.items():
+        print("    %-44s %s" % (name, _stat(ms)))
+    print("    targets solved and clear: today's route %d, vetted call %d of %d (%d recovered); plain call solves %d" % (n_today, n_vet, T, n_vet - n_today, int(out["ok"].sum())))
+    med = {k: float(np.median(v)) for k, v in tb.items()}
+    print("    the vet kernel's share of the vetted call: between %.1f %% (converged rows only, packed) and %.1f %% (every row computed); in the call a row that did "
+          "not converge idles: %.1f %% of the rows, what a compaction ahead of the kernel would save"
+          % (100.0 * med["ik_vet_kernel on the converged rows, packed"] / med["ccmp_pose_ik_vetted_batch"],
+             100.0 * med["ik_vet_kernel on every candidate row"] / med["ccmp_pose_ik_vetted_batch"], 100.0 * (1.0 - float(conv.float().mean()))))
+    for k in resource_report().get("ccmp_kernels_ik_vet.hip", []):
+        print("    %-20s %d VGPRs, %d SGPRs, %d B LDS per block, %d B scratch, occupancy %d waves per SIMD"
+              % (k["name"], k.get("vgprs", -1), k.get("sgprs", -1), k.get("lds", -1), k.get("scratch", -1), k.get("occupancy", -1)))
+    print("VERDICT vetted call against today's route: (a) %.2fx the time, (b) %.2fx the time; targets solved and clear %d -> %d"
+          % (np.median(ta["ccmp_pose_ik_vetted_host"]) / np.median(ta["today: pose_ik_host + clearance_host"]),
+             med["ccmp_pose_ik_vetted_batch"] / med["today: pose_ik_batch + clearance_batch"], n_today, n_vet))
 
 
 def object_(argv):
