@@ -20,7 +20,8 @@ Translation units with deliberately different flags:
   ccmp_comm.cpp                                             one process / several GPUs: RCCL communicator and sharded entry points
   ccmp_kernels_fast.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   analytic fast mode (lane-pair and row16 projectors, the row16 extend step, the row16 resident service kernel), bit-identical to the oracle's analytic mode
   ccmp_kernels_scout.hip -ffast-math                        FP32 iteration-count predictor + ordering (never touches results)
-  ccmp_kernels_scene.hip -ffp-contract=off -DCCMP_USE_FMA   proxy-geometry clearance (pre-filter ahead of the host's MoveIt test)
+  ccmp_kernels_scene.hip -ffp-contract=off -DCCMP_USE_FMA   proxy-geometry clearance (pre-filter ahead of the host's MoveIt test); its arithmetic — frames, placement,
+                         pair distance — is ccmp_scene_math.h, one text shared with ccmp_clearance.h (the extend step's scene variants), ccmp_kernels_ik_vet.hip and ccmp_ik.cpp
   ccmp_scene.cpp                                            proxy scenes: validation, pair list, launches
   ccmp_kernels_knn.hip   -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the connection step: FP64 brute-force k nearest neighbours on the joint metric and on the
                          object metric (ccmp_pose.h), the gather of ccmp_connect_batch, the roadmap store's pose_from_joints_kernel
@@ -28,9 +29,9 @@ Translation units with deliberately different flags:
   ccmp_kernels_ik.hip    -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   growTree's sampleCalibGoal step: pose-targeted IK (ccmp_ik.h), one candidate per lane, and its selection rule;
                          without machine LICM (two wavefronts per SIMD instead of one)
   ccmp_ik.cpp            -ffp-contract=off -DCCMP_USE_FMA   ccmp_pose_ik_*: checks, launches, and the same solver text on the host (ccmp_pose_ik_ref, same bits as the kernels);
-                         the vetted forms ccmp_arm_clearance_* / ccmp_pose_ik_vetted_* on ccmp_ik_vet.h
+                         the vetted forms ccmp_arm_clearance_* / ccmp_pose_ik_vetted_* on ccmp_ik_vet.h (the rule) and ccmp_scene_math.h (the clearances)
   ccmp_kernels_ik_vet.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the collision gate of sampleCalibGoal on the proxy scene (ccmp_ik_vet.h): the arm clearance of every
-                         IK candidate, sixteen lanes per candidate (ik_vet_kernel), and the vetted selection (ik_assemble_kernel, ik_pick_kernel)
+                         IK candidate, sixteen lanes per candidate (ik_vet_kernel, on ccmp_scene_math.h), and the vetted selection (ik_assemble_kernel, ik_pick_kernel)
   ccmp_kernels_object.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the head of growTree: object-pose proposal (interpolate, SE3 Gaussian draw) and the
                          mesh-against-workspace test (ccmp_object.h), one 256-lane block per pose, the triangles strided over the lanes
   ccmp_kernels_graph.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the roadmap graph (ccmp_graph.h): growTree's tail (commit), explicit edges, the component labels
@@ -102,7 +103,7 @@ _UNITS = [
     # literals of sincos / atan would be held in registers across the round loop: 256 + 65 registers, one wavefront per SIMD, instead
     # of 190 and two); registers only, never scratch
     ("ccmp_kernels_ik.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-mllvm", "-disable-machine-licm"]),
-    # the collision gate of that step (ccmp_ik_vet.h): sixteen lanes per candidate, frames and centres in LDS; the IK unit's flags; registers and LDS only
+    # the collision gate of that step (ccmp_ik_vet.h, ccmp_scene_math.h): sixteen lanes per candidate, frames and centres in LDS; the IK unit's flags; registers and LDS only
     ("ccmp_kernels_ik_vet.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT", "-mllvm", "-disable-machine-licm"]),
     # the head of growTree (ccmp_object.h): one block per pose, one triangle per lane and chunk; the k-NN unit's flags; registers only, never scratch
     ("ccmp_kernels_object.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
@@ -124,7 +125,7 @@ _UNITS = [
     # ccmp_path_shortcut: the checks, the tile and continuation loops, and the rule on the host (ccmp_shortcut_select_ref, ccmp_shortcut_pairs_ref)
     ("ccmp_shortcut.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():

@@ -15,7 +15,7 @@
 #include "ccmp_ik.h"
 #include "ccmp_ik_vet.h"
 #include "ccmp_launch.h"
-#include "ccmp_scene.h"
+#include "ccmp_scene_math.h"
 #include "ccmp_stage.h"
 
 using namespace ccmp_host;
@@ -55,6 +55,62 @@ int ref_records(const ccmp_problem *p, const ccmp_consts &K, const ccmp::ik_para
       }
     }
   }
+  return CCMP_OK;
+}
+
+// a scene given as the caller's arrays (the *_ref forms, no device): the tables ccmp_scene_create derives, on the heap for the call
+struct RefScene {
+  ccmp::scene_dev *H = new (std::nothrow) ccmp::scene_dev;
+  ccmp::scene_arm_dev *A = new (std::nothrow) ccmp::scene_arm_dev;
+  RefScene() = default;
+  RefScene(const RefScene &) = delete;
+  RefScene &operator=(const RefScene &) = delete;
+  int tables(const ccmp_sphere *spheres, int n_spheres, const ccmp_box *boxes, int n_boxes, const uint32_t allowed[32])
+  {
+    return H && A ? scene_tables(spheres, n_spheres, boxes, n_boxes, allowed, *H, *A) : CCMP_ENOMEM;
+  }
+  ~RefScene() { delete H; delete A; }
+};
+
+// The seven staged pieces of a pose-IK call on host buffers, in the order they take their room: the vetted form adds its own behind them.
+struct IkStaged {
+  size_t T, C, pb, sb, off_p, off_s, off_q, off_w, off_ok, off_cq, off_cr;
+  IkStaged(StagedCall &sg, size_t T_, int S, size_t C_, const double *cand_q, const int32_t *cand_rounds)
+      : T(T_), C(C_), pb(T_ * 8 * sizeof(double)), sb(T_ * (size_t)S * 14 * sizeof(double))
+  {
+    off_p = sg.add(pb);
+    off_s = sg.add(sb);
+    off_q = sg.add(T * 14 * sizeof(double));
+    off_w = sg.add(T * sizeof(int32_t));
+    off_ok = sg.add(T);
+    off_cq = sg.add(cand_q ? C * 7 * sizeof(double) : 0);
+    off_cr = sg.add(cand_rounds ? C * sizeof(int32_t) : 0);
+  }
+  void up(StagedCall &sg, const double *poses, const double *seeds) const
+  {
+    sg.up(off_p, poses, pb);
+    sg.up(off_s, seeds, sb);
+  }
+  void down(StagedCall &sg, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds) const
+  {
+    sg.down(q_out, off_q, T * 14 * sizeof(double));
+    sg.down(which, off_w, T * sizeof(int32_t));
+    sg.down(ok, off_ok, T);
+    sg.down(cand_q, off_cq, C * 7 * sizeof(double));
+    sg.down(cand_rounds, off_cr, C * sizeof(int32_t));
+  }
+};
+
+// What the four device entry points check before the device guard, in this order: the handle, ik_checks, a vetted form's scene and
+// margin, then — T == 0 answers CCMP_OK here and the caller returns it — the five required pointers.
+int ik_prologue(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, size_t T, int S, bool vet, const ccmp_scene *scene, double margin,
+                const double *target_poses, const double *seeds, const double *q_out, const uint8_t *ok, const int32_t *which, ccmp::ik_params *P)
+{
+  if (!ctx) return no_handle();
+  { const int rc = ik_checks(p, opts, T, S, P); if (rc != CCMP_OK) return rc; }
+  if (vet) { const int rc = ik_vet_checks(ctx, scene, margin); if (rc != CCMP_OK) return rc; }
+  if (T == 0) return CCMP_OK;
+  if (!target_poses || !seeds || !q_out || !ok || !which) return CCMP_EINVAL;
   return CCMP_OK;
 }
 
@@ -196,11 +252,8 @@ int ccmp_pose_ik_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts 
                        uint64_t rng_seed, uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds,
                        void *hip_stream)
 {
-  if (!ctx) return no_handle();
   ccmp::ik_params P;
-  { const int rc = ik_checks(p, opts, T, S, &P); if (rc != CCMP_OK) return rc; }
-  if (T == 0) return CCMP_OK;
-  if (!target_poses || !seeds || !q_out || !ok || !which) return CCMP_EINVAL;
+  { const int rc = ik_prologue(ctx, p, opts, T, S, false, nullptr, 0.0, target_poses, seeds, q_out, ok, which, &P); if (rc != CCMP_OK || T == 0) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
   { const int rc = ik_reserve(ctx, ik_candidates(T, S, P)); if (rc != CCMP_OK) return rc; }
@@ -211,32 +264,21 @@ int ccmp_pose_ik_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts 
 int ccmp_pose_ik_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
                       uint64_t rng_seed, uint64_t first_index, double *q_out, uint8_t *ok, int32_t *which, double *cand_q, int32_t *cand_rounds)
 {
-  if (!ctx) return no_handle();
   ccmp::ik_params P;
-  { const int rc = ik_checks(p, opts, T, S, &P); if (rc != CCMP_OK) return rc; }
-  if (T == 0) return CCMP_OK;
-  if (!target_poses || !seeds || !q_out || !ok || !which) return CCMP_EINVAL;
+  { const int rc = ik_prologue(ctx, p, opts, T, S, false, nullptr, 0.0, target_poses, seeds, q_out, ok, which, &P); if (rc != CCMP_OK || T == 0) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  const size_t C = ik_candidates(T, S, P), pb = T * 8 * sizeof(double), sb = T * (size_t)S * 14 * sizeof(double);
+  const size_t C = ik_candidates(T, S, P);
   StagedCall sg(ctx, __func__);
-  const size_t off_p = sg.add(pb), off_s = sg.add(sb), off_q = sg.add(T * 14 * sizeof(double)), off_w = sg.add(T * sizeof(int32_t)), off_ok = sg.add(T),
-               off_cq = sg.add(cand_q ? C * 7 * sizeof(double) : 0), off_cr = sg.add(cand_rounds ? C * sizeof(int32_t) : 0);
+  const IkStaged o(sg, T, S, C, cand_q, cand_rounds);
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; } // the staging block has its size before the candidates' workspace
   { const int rc = ik_reserve(ctx, C); if (rc != CCMP_OK) return rc; }
-  sg.up(off_p, target_poses, pb);
-  sg.up(off_s, seeds, sb);
+  o.up(sg, target_poses, seeds);
   int rc = CCMP_OK;
   if (sg.copy_ok())
-    rc = ik_launches(ctx, p, P, sg.at<const double>(off_p), sg.at<const double>(off_s), T, S, rng_seed, first_index, sg.at<double>(off_q), sg.at<uint8_t>(off_ok),
-                     sg.at<int32_t>(off_w), sg.at<double>(off_cq, cand_q), sg.at<int32_t>(off_cr, cand_rounds), ctx->stream);
-  if (rc == CCMP_OK) {
-    sg.down(q_out, off_q, T * 14 * sizeof(double));
-    sg.down(which, off_w, T * sizeof(int32_t));
-    sg.down(ok, off_ok, T);
-    sg.down(cand_q, off_cq, C * 7 * sizeof(double));
-    sg.down(cand_rounds, off_cr, C * sizeof(int32_t));
-  }
+    rc = ik_launches(ctx, p, P, sg.at<const double>(o.off_p), sg.at<const double>(o.off_s), T, S, rng_seed, first_index, sg.at<double>(o.off_q),
+                     sg.at<uint8_t>(o.off_ok), sg.at<int32_t>(o.off_w), sg.at<double>(o.off_cq, cand_q), sg.at<int32_t>(o.off_cr, cand_rounds), ctx->stream);
+  if (rc == CCMP_OK) o.down(sg, q_out, ok, which, cand_q, cand_rounds);
   return sg.finish(rc); // waits on the error path too: the staging block must be quiet
 }
 
@@ -248,21 +290,16 @@ int ccmp_arm_clearance_ref(const ccmp_problem *p, const ccmp_sphere *spheres, in
 {
   { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
   if (arm < 0 || arm > 1 || std::isnan(margin)) return CCMP_EINVAL;
-  ccmp::scene_dev *H = new (std::nothrow) ccmp::scene_dev;
-  ccmp::scene_arm_dev *A = new (std::nothrow) ccmp::scene_arm_dev;
-  int rc = H && A ? scene_tables(spheres, n_spheres, boxes, n_boxes, allowed, *H, *A) : CCMP_ENOMEM;
-  if (rc == CCMP_OK && B > 0 && (!q7 || !clearance)) rc = CCMP_EINVAL;
-  if (rc == CCMP_OK) {
-    ccmp_consts K;
-    make_consts(*p, K);
-    for (size_t i = 0; i < B; i++) {
-      clearance[i] = ccmp::vet_arm_clearance(K, *H, *A, arm, q7 + i * 7);
-      if (free_out) free_out[i] = (uint8_t)(clearance[i] > margin);
-    }
+  RefScene sc;
+  { const int rc = sc.tables(spheres, n_spheres, boxes, n_boxes, allowed); if (rc != CCMP_OK) return rc; }
+  if (B > 0 && (!q7 || !clearance)) return CCMP_EINVAL;
+  ccmp_consts K;
+  make_consts(*p, K);
+  for (size_t i = 0; i < B; i++) {
+    clearance[i] = ccmp::scene_arm_clearance(K, *sc.H, *sc.A, arm, q7 + i * 7);
+    if (free_out) free_out[i] = (uint8_t)(clearance[i] > margin);
   }
-  delete H;
-  delete A;
-  return rc;
+  return CCMP_OK;
 }
 
 static int arm_clearance_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, int arm, size_t B, double margin)
@@ -319,51 +356,38 @@ int ccmp_pose_ik_vetted_ref(const ccmp_problem *p, const ccmp_ik_opts *opts, con
   ccmp::ik_params P;
   { const int rc = ik_checks(p, opts, T, S, &P); if (rc != CCMP_OK) return rc; }
   if (std::isnan(margin)) return CCMP_EINVAL;
-  ccmp::scene_dev *H = new (std::nothrow) ccmp::scene_dev;
-  ccmp::scene_arm_dev *A = new (std::nothrow) ccmp::scene_arm_dev;
-  int rc = H && A ? scene_tables(spheres, n_spheres, boxes, n_boxes, allowed, *H, *A) : CCMP_ENOMEM;
-  if (rc == CCMP_OK && T > 0 && (!target_poses || !seeds || !q_out || !ok || !which)) rc = CCMP_EINVAL;
-  if (rc == CCMP_OK && T > 0) {
-    ccmp_consts K;
-    make_consts(*p, K);
-    const size_t C = ik_candidates(T, S, P), TS = T * (size_t)S;
-    RefRecords rec;
-    std::vector<double> cc, sq, sc;
-    std::vector<uint8_t> has;
-    rc = ref_records(p, K, P, target_poses, seeds, T, S, rng_seed, first_index, rec);
-    if (rc == CCMP_OK) {
-      try { cc.resize(C); sq.resize(TS * 14); sc.resize(TS); has.resize(TS); } catch (...) { rc = CCMP_ENOMEM; }
-    }
-    if (rc == CCMP_OK) {
-      const size_t per = (size_t)(1 + P.restarts);
-      for (size_t c = 0; c < C; c++)
-        cc[c] = rec.rounds[c] >= 0 ? ccmp::vet_arm_clearance(K, *H, *A, (int)((c / per) % 2), rec.q.data() + c * 7) : -__builtin_inf();
-      for (size_t ts = 0; ts < TS; ts++) {
-        has[ts] = ccmp::ik_vet_assemble(rec.q.data(), rec.rounds.data(), rec.d2.data(), cc.data(), ts, P.restarts, margin, sq.data() + ts * 14) ? 1 : 0;
-        sc[ts] = ccmp::vet_state_clearance(K, *H, sq.data() + ts * 14);
-      }
-      for (size_t t = 0; t < T; t++)
-        ccmp::ik_vet_pick(sq.data(), has.data(), sc.data(), t, S, margin, q_out + t * 14, ok + t, which + t, clearance ? clearance + t : nullptr, slot_clear);
-      if (cand_q) memcpy(cand_q, rec.q.data(), C * 7 * sizeof(double));
-      if (cand_rounds) memcpy(cand_rounds, rec.rounds.data(), C * sizeof(int32_t));
-      if (cand_clear) memcpy(cand_clear, cc.data(), C * sizeof(double));
-    }
+  RefScene scn;
+  { const int rc = scn.tables(spheres, n_spheres, boxes, n_boxes, allowed); if (rc != CCMP_OK) return rc; }
+  if (T == 0) return CCMP_OK;
+  if (!target_poses || !seeds || !q_out || !ok || !which) return CCMP_EINVAL;
+  ccmp_consts K;
+  make_consts(*p, K);
+  const size_t C = ik_candidates(T, S, P), TS = T * (size_t)S, per = (size_t)(1 + P.restarts);
+  RefRecords rec;
+  std::vector<double> cc, sq, sc;
+  std::vector<uint8_t> has;
+  { const int rc = ref_records(p, K, P, target_poses, seeds, T, S, rng_seed, first_index, rec); if (rc != CCMP_OK) return rc; }
+  try { cc.resize(C); sq.resize(TS * 14); sc.resize(TS); has.resize(TS); } catch (...) { return CCMP_ENOMEM; }
+  for (size_t c = 0; c < C; c++)
+    cc[c] = rec.rounds[c] >= 0 ? ccmp::scene_arm_clearance(K, *scn.H, *scn.A, (int)((c / per) % 2), rec.q.data() + c * 7) : -__builtin_inf();
+  for (size_t ts = 0; ts < TS; ts++) {
+    has[ts] = ccmp::ik_vet_assemble(rec.q.data(), rec.rounds.data(), rec.d2.data(), cc.data(), ts, P.restarts, margin, sq.data() + ts * 14) ? 1 : 0;
+    sc[ts] = ccmp::scene_state_clearance(K, *scn.H, sq.data() + ts * 14);
   }
-  delete H;
-  delete A;
-  return rc;
+  for (size_t t = 0; t < T; t++)
+    ccmp::ik_vet_pick(sq.data(), has.data(), sc.data(), t, S, margin, q_out + t * 14, ok + t, which + t, clearance ? clearance + t : nullptr, slot_clear);
+  if (cand_q) memcpy(cand_q, rec.q.data(), C * 7 * sizeof(double));
+  if (cand_rounds) memcpy(cand_rounds, rec.rounds.data(), C * sizeof(int32_t));
+  if (cand_clear) memcpy(cand_clear, cc.data(), C * sizeof(double));
+  return CCMP_OK;
 }
 
 int ccmp_pose_ik_vetted_batch(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik_opts *opts, const double *target_poses, const double *seeds, size_t T, int S,
                               uint64_t rng_seed, uint64_t first_index, const ccmp_scene *scene, double margin, double *q_out, uint8_t *ok, int32_t *which,
                               double *cand_q, int32_t *cand_rounds, double *cand_clear, double *slot_clear, double *clearance, void *hip_stream)
 {
-  if (!ctx) return no_handle();
   ccmp::ik_params P;
-  { const int rc = ik_checks(p, opts, T, S, &P); if (rc != CCMP_OK) return rc; }
-  { const int rc = ik_vet_checks(ctx, scene, margin); if (rc != CCMP_OK) return rc; }
-  if (T == 0) return CCMP_OK;
-  if (!target_poses || !seeds || !q_out || !ok || !which) return CCMP_EINVAL;
+  { const int rc = ik_prologue(ctx, p, opts, T, S, true, scene, margin, target_poses, seeds, q_out, ok, which, &P); if (rc != CCMP_OK || T == 0) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
   { const int rc = ik_vetted_reserve(ctx, T, S, P); if (rc != CCMP_OK) return rc; }
@@ -376,35 +400,26 @@ int ccmp_pose_ik_vetted_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_ik
                              uint64_t rng_seed, uint64_t first_index, const ccmp_scene *scene, double margin, double *q_out, uint8_t *ok, int32_t *which,
                              double *cand_q, int32_t *cand_rounds, double *cand_clear, double *slot_clear, double *clearance)
 {
-  if (!ctx) return no_handle();
   ccmp::ik_params P;
-  { const int rc = ik_checks(p, opts, T, S, &P); if (rc != CCMP_OK) return rc; }
-  { const int rc = ik_vet_checks(ctx, scene, margin); if (rc != CCMP_OK) return rc; }
-  if (T == 0) return CCMP_OK;
-  if (!target_poses || !seeds || !q_out || !ok || !which) return CCMP_EINVAL;
+  { const int rc = ik_prologue(ctx, p, opts, T, S, true, scene, margin, target_poses, seeds, q_out, ok, which, &P); if (rc != CCMP_OK || T == 0) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  const size_t C = ik_candidates(T, S, P), TS = T * (size_t)S, pb = T * 8 * sizeof(double), sb = TS * 14 * sizeof(double);
+  const size_t C = ik_candidates(T, S, P), TS = T * (size_t)S;
   StagedCall sg(ctx, __func__);
-  const size_t off_p = sg.add(pb), off_s = sg.add(sb), off_q = sg.add(T * 14 * sizeof(double)), off_w = sg.add(T * sizeof(int32_t)), off_ok = sg.add(T),
-               off_cq = sg.add(cand_q ? C * 7 * sizeof(double) : 0), off_cr = sg.add(cand_rounds ? C * sizeof(int32_t) : 0),
-               off_cc = sg.add(cand_clear ? C * sizeof(double) : 0), off_sc = sg.add(slot_clear ? TS * sizeof(double) : 0),
+  const IkStaged o(sg, T, S, C, cand_q, cand_rounds);
+  const size_t off_cc = sg.add(cand_clear ? C * sizeof(double) : 0), off_sc = sg.add(slot_clear ? TS * sizeof(double) : 0),
                off_cl = sg.add(clearance ? T * sizeof(double) : 0);
   { const int rc = sg.alloc(); if (rc != CCMP_OK) return rc; } // the staging block has its size before the workspaces
   { const int rc = ik_vetted_reserve(ctx, T, S, P); if (rc != CCMP_OK) return rc; }
-  sg.up(off_p, target_poses, pb);
-  sg.up(off_s, seeds, sb);
+  o.up(sg, target_poses, seeds);
   int rc = CCMP_OK;
   if (sg.copy_ok())
-    rc = ik_vetted_launches(ctx, p, P, sg.at<const double>(off_p), sg.at<const double>(off_s), T, S, rng_seed, first_index, scene, margin, sg.at<double>(off_q),
-                            sg.at<uint8_t>(off_ok), sg.at<int32_t>(off_w), sg.at<double>(off_cq, cand_q), sg.at<int32_t>(off_cr, cand_rounds),
-                            sg.at<double>(off_cc, cand_clear), sg.at<double>(off_sc, slot_clear), sg.at<double>(off_cl, clearance), ctx->stream);
+    rc = ik_vetted_launches(ctx, p, P, sg.at<const double>(o.off_p), sg.at<const double>(o.off_s), T, S, rng_seed, first_index, scene, margin,
+                            sg.at<double>(o.off_q), sg.at<uint8_t>(o.off_ok), sg.at<int32_t>(o.off_w), sg.at<double>(o.off_cq, cand_q),
+                            sg.at<int32_t>(o.off_cr, cand_rounds), sg.at<double>(off_cc, cand_clear), sg.at<double>(off_sc, slot_clear),
+                            sg.at<double>(off_cl, clearance), ctx->stream);
   if (rc == CCMP_OK) {
-    sg.down(q_out, off_q, T * 14 * sizeof(double));
-    sg.down(which, off_w, T * sizeof(int32_t));
-    sg.down(ok, off_ok, T);
-    sg.down(cand_q, off_cq, C * 7 * sizeof(double));
-    sg.down(cand_rounds, off_cr, C * sizeof(int32_t));
+    o.down(sg, q_out, ok, which, cand_q, cand_rounds);
     sg.down(cand_clear, off_cc, C * sizeof(double));
     sg.down(slot_clear, off_sc, TS * sizeof(double));
     sg.down(clearance, off_cl, T * sizeof(double));

@@ -10,10 +10,11 @@
  * Arm clearance.  A sphere is static on the world frame or on either arm's base, moving on arm a on CCMP_FRAME(a, 0..7).  Arm a's pair
  * set is the scene's tested pairs (already filtered by its allowed matrix; boxes included) that contain no sphere moving on the other
  * arm (ccmp_scene.h: scene_arm_dev); arm_clearance(a, q7) is the smallest signed distance over it: +inf for an empty set, NaN when one
- * of the seven joints is not finite.  It reads arm a's seven joints only, and is ccmp_clearance's arithmetic (ccmp_clearance.h: the
- * chain of joint_step, t_wb (o + R c), the distances) on the same operands: the bits of orc_clearance on the sub-scene without the
- * other arm's moving spheres, whatever the work layout (the minimum of a set of doubles is exact).  The scene's pairs are arm 0's set,
- * arm 1's set and the cross pairs (one sphere moving on each arm): full clearance = min(arm 0, arm 1, cross).
+ * of the seven joints is not finite.  It reads arm a's seven joints only, and is ccmp_clearance's arithmetic (ccmp_scene_math.h: the
+ * chain of joint_step, t_wb (o + R c), the distances; scene_arm_clearance on the host, ik_vet_kernel on the device) on the same
+ * operands: the bits of orc_clearance on the sub-scene without the other arm's moving spheres, whatever the work layout (the minimum of
+ * a set of doubles is exact).  The scene's pairs are arm 0's set, arm 1's set and the cross pairs (one sphere moving on each arm): full
+ * clearance = min(arm 0, arm 1, cross).
  *
  * Unlike MoveIt's IKValid, which tests the arm against a robot state that still holds whatever the other arm was last set to, the arm
  * is tested ALONE here; the pair of arms is tested on the assembled state.
@@ -30,115 +31,8 @@
 #ifndef CCMP_IK_VET_H
 #define CCMP_IK_VET_H
 #include "ccmp_ik.h"
-#include "ccmp_scene.h"
 
 namespace ccmp {
-
-constexpr int kVetFrame = 12;                    /* a frame in the arm's base: R (9, row-major), o (3) */
-constexpr int kVetFrames = 8 * kVetFrame;        /* one arm: bodies 0..6 after each joint, the hand */
-constexpr int kVetCentres = CCMP_MAX_SPHERES * 3;
-
-/* world centre of a sphere on frame slot `slot` with centre c in that frame: t_wb (o + R c); fr = the eight frames of the sphere's arm
- * (not read for a base or the world) */
-CCMP_HD void vet_place(const ccmp_consts &K, int slot, const double *c, const double *fr, double *w)
-{
-  if (slot == kSceneSlots - 1) { /* world frame */
-    w[0] = c[0]; w[1] = c[1]; w[2] = c[2];
-    return;
-  }
-  const int arm = slot >= 9 ? 1 : 0, k = slot - 9 * arm;
-  double v[3];
-  if (k == 8) { /* the arm's base: only t_wb applies */
-    v[0] = c[0]; v[1] = c[1]; v[2] = c[2];
-  } else {
-    const double *f = fr + k * kVetFrame;
-    v[0] = f[9]; v[1] = f[10]; v[2] = f[11];
-    mulvec_acc(f, c, v);
-  }
-  w[0] = K.base_p[arm][0]; w[1] = K.base_p[arm][1]; w[2] = K.base_p[arm][2];
-  mulvec_acc(K.base_R[arm], v, w);
-}
-
-/* signed distance of tested pair p of the scene's table; cen = world centres by stored sphere index */
-CCMP_HD double vet_pair_clearance(const scene_dev *S, const double *cen, int p)
-{
-  const unsigned ij = S->pair_ij[p];
-  const int i = (int)(ij & 0xffu), j = (int)(ij >> 8);
-  const double a0 = cen[3 * i], a1 = cen[3 * i + 1], a2 = cen[3 * i + 2];
-  double d2;
-  if (j < CCMP_MAX_SPHERES) {
-    const double d0 = a0 - cen[3 * j], d1 = a1 - cen[3 * j + 1], dz = a2 - cen[3 * j + 2];
-    d2 = dot3(d0, d0, d1, d1, dz, dz);
-  } else {
-    const int b = j - CCMP_MAX_SPHERES;
-    const double d[3] = {a0 - S->box_c[b][0], a1 - S->box_c[b][1], a2 - S->box_c[b][2]};
-    double l[3], e[3];
-    mulTvec(S->box_R[b], d, l); /* into the box's axes */
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const double a = ccmp_abs(l[k]) - S->box_half[b][k];
-      e[k] = a > 0.0 ? a : 0.0;
-    }
-    d2 = dot3(e[0], e[0], e[1], e[1], e[2], e[2]);
-  }
-  return ccmp_sqrt(d2) - S->pair_rsum[p];
-}
-
-CCMP_HD bool vet_finite(double x) { return x - x == 0.0; } /* the oracle's test: false on NaN and on an infinity */
-
-/* ---- host forms (the *_ref entry points): one thread walks what the kernels spread over sixteen lanes ------------------------------ */
-/* PandaModel's chain of one arm (ccmp_kin.h: joint_step, the general form) and the hand frame (getTranslation / getRotation) */
-inline void vet_arm_frames(const ccmp_consts &K, int arm, const double *q7, double *fr)
-{
-  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
-  for (int i = 0; i < 7; i++) {
-    double s, c;
-    ccmp_sincos(q7[i], &s, &c);
-    joint_step(K, arm, i, s, c, R, o);
-    for (int k = 0; k < 9; k++) fr[i * kVetFrame + k] = R[k];
-    for (int k = 0; k < 3; k++) fr[i * kVetFrame + 9 + k] = o[k];
-  }
-  double *f = fr + 7 * kVetFrame;
-  f[9] = o[0]; f[10] = o[1]; f[11] = o[2];
-  mulvec_acc(R, K.ee[arm], f + 9);
-  mul33(R, K.R_tool[arm], f);
-}
-
-inline double vet_arm_clearance(const ccmp_consts &K, const scene_dev &S, const scene_arm_dev &A, int arm, const double *q7)
-{
-  for (int i = 0; i < 7; i++)
-    if (!vet_finite(q7[i])) return __builtin_nan("");
-  double fr[kVetFrames], cen[kVetCentres];
-  vet_arm_frames(K, arm, q7, fr);
-  for (int s = 0; s < S.n_spheres; s++) {
-    const int m = scene_moving_arm(S.slot[s]);
-    if (m >= 0 && m != arm) continue; /* moving on the other arm: in none of this arm's pairs */
-    vet_place(K, S.slot[s], S.c[s], fr, cen + 3 * s);
-  }
-  double best = __builtin_inf();
-  for (int n = 0; n < A.n_pairs[arm]; n++) {
-    const double clr = vet_pair_clearance(&S, cen, A.pair[arm][n]);
-    if (clr < best) best = clr;
-  }
-  return best;
-}
-
-/* ccmp_clearance of a 14-joint state (oracle/ccmp_oracle.c: orc_clearance) */
-inline double vet_state_clearance(const ccmp_consts &K, const scene_dev &S, const double *x)
-{
-  for (int i = 0; i < 14; i++)
-    if (!vet_finite(x[i])) return __builtin_nan("");
-  double fr[2][kVetFrames], cen[kVetCentres];
-  vet_arm_frames(K, 0, x, fr[0]);
-  vet_arm_frames(K, 1, x + 7, fr[1]);
-  for (int s = 0; s < S.n_spheres; s++) vet_place(K, S.slot[s], S.c[s], fr[S.slot[s] >= 9 && S.slot[s] < kSceneSlots - 1 ? 1 : 0], cen + 3 * s);
-  double best = __builtin_inf();
-  for (int p = 0; p < S.n_pairs; p++) {
-    const double clr = vet_pair_clearance(&S, cen, p);
-    if (clr < best) best = clr;
-  }
-  return best;
-}
 
 /* ---- the selection ------------------------------------------------------------------------------------------------------------------- */
 CCMP_HD bool ik_vet_admissible(int32_t rounds, double clear, double margin) { return rounds >= 0 && clear > margin; }

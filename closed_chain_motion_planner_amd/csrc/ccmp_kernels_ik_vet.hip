@@ -1,12 +1,14 @@
-// ccmp_kernels_ik_vet.hip — the collision gate of growTree's sampleCalibGoal on the device (csrc/ccmp_ik_vet.h holds the rule, one text
-// for host and device): ik_vet_kernel, the arm clearance of every candidate record (and of ccmp_arm_clearance_batch's rows), sixteen lanes
-// per candidate; ik_assemble_kernel, one thread per (target, slot); ik_pick_kernel, one thread per target.  Between the last two the
+// ccmp_kernels_ik_vet.hip — the collision gate of growTree's sampleCalibGoal on the device (csrc/ccmp_ik_vet.h holds the rule,
+// csrc/ccmp_scene_math.h the arm clearance's arithmetic, each one text for host and device): ik_vet_kernel, the arm clearance of every
+// candidate record (and of ccmp_arm_clearance_batch's rows), sixteen lanes per candidate; ik_assemble_kernel, one thread per
+// (target, slot); ik_pick_kernel, one thread per target.  Between the last two the
 // slots' full clearances come from ccmp_clearance_batch on the same stream.  Built with the IK unit's flags; no scratch (_SCRATCH_RULES).
 #include <hip/hip_runtime.h>
 
 #include "ccmp_fd_common.h"
 #include "ccmp_ik_vet.h"
 #include "ccmp_launch.h"
+#include "ccmp_scene_math.h"
 
 using namespace ccmp;
 
@@ -18,18 +20,18 @@ constexpr int kThreads = 256;               // of the two per-thread kernels
 // Row `row` of the wavefront works on row n = 4 blockIdx.x + row of arm (arm0 + blockIdx.y): the arm is uniform over the block, so its
 // constants and its pair list stay scalar.  per > 0: the rows are the candidate records of a pose-IK call, n = ts per + r -> record
 // c = (2 ts + arm) per + r, and a record that did not converge or was skipped does no work and gets -inf; per == 0: the rows are the
-// caller's own, c = n.  After ccmp_clearance.h: state_clearance<16> with one arm's chain —
-//   1  lanes 0..6: the rotation of joint `tid` (sine, cosine, rot_sc), into the space the centres take later;
-//   2  lanes 0..2: row tid of the arm's chain, joint_step's operations row by row, the eight frames into LDS;
-//   3  lane s, s + 16, ...: the world centre of stored sphere s unless it moves on the other arm;
-//   4  lane i, i + 16, ...: entry i of the arm's pair list; the minimum over the row by four exchanges.
+// caller's own, c = n.  The work split of ccmp_clearance.h: state_clearance<16> with one arm's chain, on the text of ccmp_scene_math.h —
+//   1  lanes 0..6: the rotation of joint `tid` (scene_joint_rot), into the space the centres take later;
+//   2  lanes 0..2: row tid of the arm's chain (scene_chain_row), the eight frames into LDS;
+//   3  lane s, s + 16, ...: the world centre of stored sphere s (scene_place) unless it moves on the other arm;
+//   4  lane i, i + 16, ...: entry i of the arm's pair list (scene_pair_clearance); the minimum over the row by four exchanges.
 // The rows of a wavefront never wait for each other or for another wavefront: LDS accesses of one wavefront complete in order, so a
 // compiler barrier stands where a block would need __syncthreads.  Every loop is bounded by the scene's sizes.  2.3 KB of LDS per row.
 __global__ __launch_bounds__(64) void ik_vet_kernel(const ccmp_consts K, const scene_dev *__restrict__ S, const scene_arm_dev *__restrict__ A,
                                                     const double *__restrict__ q7, const int32_t *__restrict__ rounds, unsigned long long n_rows, int per,
                                                     int arm0, double margin, double *__restrict__ clear, uint8_t *__restrict__ free_out)
 {
-  __shared__ double lds[kRows][kVetFrames + kVetCentres];
+  __shared__ double lds[kRows][kSceneArmFrames + kSceneCentres];
   const int arm = arm0 + (int)blockIdx.y;
   const int lane = (int)threadIdx.x, row = lane / kRow, tid = lane % kRow;
   const unsigned long long n = (unsigned long long)blockIdx.x * kRows + (unsigned long long)row;
@@ -37,39 +39,16 @@ __global__ __launch_bounds__(64) void ik_vet_kernel(const ccmp_consts K, const s
   unsigned long long c = 0;
   if (mine) c = per > 0 ? ((n / (unsigned long long)per) * 2ull + (unsigned long long)arm) * (unsigned long long)per + n % (unsigned long long)per : n;
   const bool work = mine && (rounds == nullptr || rounds[c] >= 0);
-  double *fr = lds[row], *cen = fr + kVetFrames, *rj = cen; // rj [7][9]: dead once the frames exist
+  double *fr = lds[row], *cen = fr + kSceneArmFrames, *rj = cen; // rj [7][9]: dead once the frames exist
   double best = __builtin_inf();
   bool finite = true;
   if (work) {
     const double *x = q7 + c * 7;
 #pragma unroll
-    for (int i = 0; i < 7; i++) finite = finite && vet_finite(x[i]);
-    if (tid < 7) {
-      double s, cs;
-      ccmp_sincos(x[tid], &s, &cs);
-      rot_sc(K.axis[arm][tid], K.aprod[arm][tid], s, cs, rj + 9 * tid);
-    }
+    for (int i = 0; i < 7; i++) finite = finite && scene_finite(x[i]);
+    if (tid < 7) scene_joint_rot(K, arm, tid, x[tid], rj + 9 * tid);
     asm volatile("" ::: "memory");
-    if (tid < 3) {
-      const int r = tid;
-      double R[3] = {r == 0 ? 1.0 : 0.0, r == 1 ? 1.0 : 0.0, r == 2 ? 1.0 : 0.0}, o = 0.0; // row r of R, component r of o
-      for (int i = 0; i < 7; i++) {
-        const double *Rj = rj + 9 * i, *off = K.offset[arm][i];
-        o = dot3acc(o, R[0], off[0], R[1], off[1], R[2], off[2]); // mulvec_acc(R, offset, o)
-        double Rn[3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) Rn[j] = dot3(R[0], Rj[j], R[1], Rj[3 + j], R[2], Rj[6 + j]); // mul33(R, Rj, Rn)
-        R[0] = Rn[0]; R[1] = Rn[1]; R[2] = Rn[2];
-        double *f = fr + i * kVetFrame;
-        f[3 * r] = R[0]; f[3 * r + 1] = R[1]; f[3 * r + 2] = R[2];
-        f[9 + r] = o;
-      }
-      const double *ee = K.ee[arm], *Rt = K.R_tool[arm]; // hand frame: getTranslation / getRotation
-      double *f = fr + 7 * kVetFrame;
-      f[9 + r] = dot3acc(o, R[0], ee[0], R[1], ee[1], R[2], ee[2]);
-#pragma unroll
-      for (int j = 0; j < 3; j++) f[3 * r + j] = dot3(R[0], Rt[j], R[1], Rt[3 + j], R[2], Rt[6 + j]);
-    }
+    if (tid < 3) scene_chain_row(K, arm, tid, rj, fr);
     asm volatile("" ::: "memory");
     const int ns = S->n_spheres, np = A->n_pairs[arm];
     for (int s = tid; s < ns; s += kRow) {
@@ -77,12 +56,12 @@ __global__ __launch_bounds__(64) void ik_vet_kernel(const ccmp_consts K, const s
       if (m >= 0 && m != arm) continue; // moving on the other arm: in none of this arm's pairs
       const double cs[3] = {S->c[s][0], S->c[s][1], S->c[s][2]};
       double w[3];
-      vet_place(K, slot, cs, fr, w);
+      scene_place(K, slot, cs, fr, w);
       cen[3 * s] = w[0]; cen[3 * s + 1] = w[1]; cen[3 * s + 2] = w[2];
     }
     asm volatile("" ::: "memory");
     for (int i = tid; i < np; i += kRow) {
-      const double clr = vet_pair_clearance(S, cen, (int)A->pair[arm][i]);
+      const double clr = scene_pair_clearance(S, cen, (int)A->pair[arm][i]);
       if (clr < best) best = clr;
     }
   }

@@ -15,7 +15,7 @@
 // HBM traffic: 112 B read + 13 B written per state; the work is the pair loop (one IEEE square root per pair).
 // Small batches: one block per state (clearance_state_kernel below).
 #include "ccmp_fd_common.h"
-#include "ccmp_scene.h"
+#include "ccmp_scene_math.h"
 
 using namespace ccmp;
 
@@ -34,10 +34,9 @@ __device__ __forceinline__ void place_spheres(const ccmp_consts &K, const scene_
   for (int s = b; s < e; s++) {
     if ((s & (kTileWaves / 2 - 1)) != part) continue;
     const double c[3] = {S->c[s][0], S->c[s][1], S->c[s][2]};
-    double v[3] = {o[0], o[1], o[2]};
-    mulvec_acc(R, c, v);
-    double wv[3] = {K.base_p[arm][0], K.base_p[arm][1], K.base_p[arm][2]};
-    mulvec_acc(K.base_R[arm], v, wv);
+    double v[3], wv[3];
+    scene_frame_to_base(R, o, c, v);
+    scene_base_to_world(K, arm, v, wv);
 #pragma unroll
     for (int k = 0; k < 3; k++) cen[(s * 3 + k) * kTile + lane] = wv[k];
   }
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(kTileThreads) void clearance_kernel(const ccmp_cons
 #pragma unroll
       for (int i = 0; i < 7; i++) {
         x[i] = q[src * 14 + arm * 7 + i];
-        if (!(x[i] - x[i] == 0.0)) nonfinite = true;
+        if (!scene_finite(x[i])) nonfinite = true;
       }
       bad[w * kTile + lane] = nonfinite ? 1 : 0;
       double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
@@ -144,8 +143,8 @@ __global__ __launch_bounds__(kTileThreads) void clearance_kernel(const ccmp_cons
         for (int s = S->slot_begin[slot]; s < S->slot_begin[slot + 1]; s++) {
           if ((s & (kTileWaves / 2 - 1)) != part) continue;
           const double c[3] = {S->c[s][0], S->c[s][1], S->c[s][2]};
-          double wv[3] = {K.base_p[arm][0], K.base_p[arm][1], K.base_p[arm][2]};
-          mulvec_acc(K.base_R[arm], c, wv);
+          double wv[3];
+          scene_base_to_world(K, arm, c, wv);
 #pragma unroll
           for (int k = 0; k < 3; k++) cen[(s * 3 + k) * kTile + lane] = wv[k];
         }
@@ -186,16 +185,8 @@ __global__ __launch_bounds__(kTileThreads) void clearance_kernel(const ccmp_cons
       for (; l < end; l++) { // sphere-box pairs
         const unsigned ij = (unsigned)__builtin_amdgcn_readlane((int)my_ij[k], l);
         const int i = (int)(ij & 0xffu), b = (int)(ij >> 8) - CCMP_MAX_SPHERES;
-        const double d[3] = {cen[(i * 3 + 0) * kTile + lane] - S->box_c[b][0], cen[(i * 3 + 1) * kTile + lane] - S->box_c[b][1],
-                             cen[(i * 3 + 2) * kTile + lane] - S->box_c[b][2]};
-        double lb[3], e[3];
-        mulTvec(S->box_R[b], d, lb); // into the box's axes
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-          const double a = ccmp_abs(lb[c]) - S->box_half[b][c];
-          e[c] = a > 0.0 ? a : 0.0;
-        }
-        consider_pair(dot3(e[0], e[0], e[1], e[1], e[2], e[2]), readlane_f64(my_rs[k], l), w + kTileWaves * (base + l), best, bestp);
+        const double d2 = scene_box_d2(S, b, cen + i * 3 * kTile + lane, kTile);
+        consider_pair(d2, readlane_f64(my_rs[k], l), w + kTileWaves * (base + l), best, bestp);
       }
     }
     red[w * kTile + lane] = best;
@@ -252,7 +243,7 @@ __global__ __launch_bounds__(256) void clearance_state_kernel(const ccmp_consts 
     bool nonfinite = false;
     if (tid < 14) {
       const double x = q[st * 14 + tid];
-      nonfinite = !(x - x == 0.0);
+      nonfinite = !scene_finite(x);
       double s, c;
       ccmp_sincos(x, &s, &c);
       sc[2 * tid] = s;
@@ -264,58 +255,30 @@ __global__ __launch_bounds__(256) void clearance_state_kernel(const ccmp_consts 
     }
     __syncthreads();
     if (tid < ns) {
-      const int slot = S->slot[tid];
-      double wv[3];
-      if (slot == kSceneSlots - 1) {
-        wv[0] = S->c[tid][0]; wv[1] = S->c[tid][1]; wv[2] = S->c[tid][2];
-      } else {
-        const int arm = slot >= 9 ? 1 : 0, k = slot - 9 * arm;
-        const double c[3] = {S->c[tid][0], S->c[tid][1], S->c[tid][2]};
-        double v[3];
-        if (k == 8) {
-          v[0] = c[0]; v[1] = c[1]; v[2] = c[2];
-        } else {
-          double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
-          const int last = k < 7 ? k : 6;
-          for (int i = 0; i <= last; i++) joint_step(KL, arm, i, sc[2 * (arm * 7 + i)], sc[2 * (arm * 7 + i) + 1], R, o);
-          if (k == 7) {
-            double Rh[9];
-            mulvec_acc(R, KL.ee[arm], o);
-            mul33(R, KL.R_tool[arm], Rh);
+      const int slot = S->slot[tid], arm = scene_moving_arm(slot);
+      const double c[3] = {S->c[tid][0], S->c[tid][1], S->c[tid][2]};
+      double f[kSceneFrame] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}, wv[3]; // the sphere's own frame (R, o); a static sphere has none
+      if (arm >= 0) {
+        const int k = slot - 9 * arm, last = k < 7 ? k : 6;
+        for (int i = 0; i <= last; i++) joint_step(KL, arm, i, sc[2 * (arm * 7 + i)], sc[2 * (arm * 7 + i) + 1], f, f + 9);
+        if (k == 7) { // hand frame
+          double Rh[9];
+          mulvec_acc(f, KL.ee[arm], f + 9);
+          mul33(f, KL.R_tool[arm], Rh);
 #pragma unroll
-            for (int e = 0; e < 9; e++) R[e] = Rh[e];
-          }
-          v[0] = o[0]; v[1] = o[1]; v[2] = o[2];
-          mulvec_acc(R, c, v);
+          for (int e = 0; e < 9; e++) f[e] = Rh[e];
         }
-        wv[0] = KL.base_p[arm][0]; wv[1] = KL.base_p[arm][1]; wv[2] = KL.base_p[arm][2];
-        mulvec_acc(KL.base_R[arm], v, wv);
       }
+      scene_place_on(KL, slot, c, f, wv);
       cen[3 * tid] = wv[0]; cen[3 * tid + 1] = wv[1]; cen[3 * tid + 2] = wv[2];
     }
     __syncthreads();
     double best = __builtin_inf();
     int bestp = 0x7fffffff;
     for (int p = tid; p < np; p += 256) {
-      const unsigned ij = S->pair_ij[p];
-      const int i = (int)(ij & 0xffu), j = (int)(ij >> 8);
-      const double a0 = cen[3 * i], a1 = cen[3 * i + 1], a2 = cen[3 * i + 2];
-      double clr;
-      if (j < CCMP_MAX_SPHERES) {
-        const double d0 = a0 - cen[3 * j], d1 = a1 - cen[3 * j + 1], d2 = a2 - cen[3 * j + 2];
-        clr = ccmp_sqrt(dot3(d0, d0, d1, d1, d2, d2)) - (S->r[i] + S->r[j]);
-      } else {
-        const int b = j - CCMP_MAX_SPHERES;
-        const double d[3] = {a0 - S->box_c[b][0], a1 - S->box_c[b][1], a2 - S->box_c[b][2]};
-        double l[3], e[3];
-        mulTvec(S->box_R[b], d, l);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const double a = ccmp_abs(l[k]) - S->box_half[b][k];
-          e[k] = a > 0.0 ? a : 0.0;
-        }
-        clr = ccmp_sqrt(dot3(e[0], e[0], e[1], e[1], e[2], e[2])) - S->r[i];
-      }
+      // subtracts pair_rsum[p] like every other form: ccmp_scene.cpp: scene_tables stores it as spheres[i].r + spheres[j].r (or r_i for
+      // a box), the very doubles S->r[] holds, and IEEE addition is commutative — the bits this kernel had from S->r[i] + S->r[j]
+      const double clr = scene_pair_clearance(S, cen, p);
       if (clr < best) { best = clr; bestp = p; }
     }
 #pragma unroll

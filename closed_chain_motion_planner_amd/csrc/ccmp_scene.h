@@ -31,15 +31,18 @@ struct scene_dev {
   double pair_rsum[kSceneMaxPairs]; /* r_i + r_j (sphere-sphere) or r_i (sphere-box): what is subtracted from the distance */
 };
 
-/* Derived from scene_dev for the vetted IK (csrc/ccmp_ik_vet.h): the tested pairs of ONE arm — those that contain no sphere moving on
- * the other arm (frame slots 9 a' .. 9 a' + 7) — as positions in scene_dev's pair table, ascending.  The two lists and the cross pairs
- * (one sphere moving on each arm) partition the table.  A table of its own: scene_dev's layout is what every scene kernel reads. */
+/* Derived from scene_dev for the vetted IK (the rule: csrc/ccmp_ik_vet.h; the arm clearance over it: csrc/ccmp_scene_math.h): the tested
+ * pairs of ONE arm — those that contain no sphere moving on the other arm (frame slots 9 a' .. 9 a' + 7) — as positions in scene_dev's
+ * pair table, ascending.  The two lists and the cross pairs (one sphere moving on each arm) partition the table.  A table of its own:
+ * scene_dev's layout is what every scene kernel reads. */
 struct scene_arm_dev {
   int32_t n_pairs[2];
   uint16_t pair[2][kSceneMaxPairs];
 };
 /* the arm a sphere on frame slot `slot` moves with (slots 9 a .. 9 a + 7: the bodies and the hand), -1 for a static one (a base, the world) */
 constexpr int scene_moving_arm(int slot) { return slot == kSceneSlots - 1 || slot % 9 == 8 ? -1 : slot / 9; }
+/* the arm whose frames and base a slot indexes (slots 9 a .. 9 a + 8); 0 for the world, which has neither */
+constexpr int scene_slot_arm(int slot) { return slot >= 9 && slot < kSceneSlots - 1 ? 1 : 0; }
 static_assert(kSceneMaxPairs < 65536, "scene_arm_dev keeps pair positions in 16 bits");
 
 }  // namespace ccmp
