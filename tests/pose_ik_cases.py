@@ -1,9 +1,17 @@
-"""Inputs and numpy restatements shared by the pose-IK tests (tests/test_pose_ik_host.py, tests/test_gpu_pose_ik.py).
+"""Inputs and numpy restatements shared by the pose-IK tests (tests/test_pose_ik_host.py, tests/test_gpu_pose_ik.py, and on every arm
+model tests/test_pose_ik_models_host.py, tests/test_gpu_pose_ik_models.py).
 
 Targets are object poses of states that exist: the valid states among orc_sample_project_batch(seed 0x4B4E, first 0, 1 500) of the libm
 oracle (both `ok` and orc_joint_valid), their poses ccmp_pose_from_t_wo of orc_compute_t_wo.  The first 40 are targets; the rest
 supply each target's 5 pose-nearest states as seed slots, nearest first (ccmp_pose_distance, ties to the lower index) — what the
-store's object-metric k-NN hands growTree.  Everything is computed once per object and shared."""
+store's object-metric k-NN hands growTree.  Everything is computed once per object and arm model (tests/arm_model_cases.py) and shared:
+on a model other than the stock one the states are sampled on that model's own manifold.
+
+`restated_step` is one step of the solver as csrc/ccmp_ik.h documents it, in plain float64 numpy on the ORACLE's forward kinematics
+alone — no library call, no base frame, no chain walk: the world-frame geometric Jacobian comes from Richardson-extrapolated central
+differences of orc_fk.  `restart_start` is the start of restart candidate r from orc_ambient_gaussian at the documented stream index.
+`step_tolerance` is the bound of a comparison with them, measured on the restatement itself: 200 x the largest difference between two
+difference step sizes (H_FINE, H_COARSE), never above 1e-6."""
 import functools
 
 import numpy as np
@@ -28,12 +36,27 @@ def pose_of(orc, OP, q):
 
 
 @functools.lru_cache(maxsize=None)
-def sampled_case(obj):
-    """(oracle, oracle problem, valid states (n,14), their poses (n,8), targets (40,8), seeds (40,5,14))"""
+def model_problem(obj, model="stock"):
+    """the library's problem struct of `obj` under the arm model (arm_model_cases.MODELS); general_kernels is the stock problem (the
+    model is an option of a device context)"""
+    from arm_model_cases import apply, host_constraint
+
+    c = host_constraint(obj=obj)
+    with apply(c, None, model):
+        pass
+    return c.problem
+
+
+@functools.lru_cache(maxsize=None)
+def sampled_case(obj, model="stock"):
+    """(oracle, oracle problem, valid states (n,14), their poses (n,8), targets (40,8), seeds (40,5,14)) on the arm model: the stock
+    problem by the oracle's own set-up, any other as the bytes of model_problem (test_ik_vet_ref._model)"""
     from closed_chain_motion_planner_amd import pose_distance
 
     orc = _oracle()
-    OP = orc.problem(load_cfg(obj))
+    if model == "general_kernels":
+        return sampled_case(obj)
+    OP = orc.problem(load_cfg(obj)) if model == "stock" else orc.problem_from_bytes(bytes(model_problem(obj, model)))
     q, ok, _ = orc.sample_project_batch(OP, SEED, 0, SAMPLES)
     valid = np.array([x for x, o in zip(q, ok) if o and orc.joint_valid(OP, x)])
     poses = np.array([pose_of(orc, OP, x) for x in valid])
@@ -114,3 +137,82 @@ def select(cand_q, cand_rounds, seeds):
                 ok[t], which[t] = 1, s
                 break
     return q, ok, which
+
+
+# ---- one step of the solver, restated on the oracle's forward kinematics ---------------------------------------------------------------
+H_FINE, H_COARSE = 2e-3, 4e-3  # the two difference step sizes a tolerance is measured with (rad)
+
+
+def rot_vec(R):
+    """the rotation vector of a rotation matrix (twist's rotation part)"""
+    return twist(R, np.zeros(3), np.eye(3), np.zeros(3))[3:]
+
+
+def _central(orc, OP, arm, q, R0, h):
+    J = np.empty((6, 7))
+    for i in range(7):
+        d = np.zeros(7)
+        d[i] = h
+        Rp, pp = orc.fk(OP, arm, q + d)
+        Rm, pm = orc.fk(OP, arm, q - d)
+        J[:3, i] = (pp - pm) / (2 * h)
+        J[3:, i] = (rot_vec(Rp @ R0.T) - rot_vec(Rm @ R0.T)) / (2 * h)
+    return J
+
+
+def fk_jacobian(orc, OP, arm, q7, h):
+    """the world-frame geometric Jacobian (6,7) of the hand at q7 from orc_fk alone: central differences at h and h / 2 (position by
+    difference, rotation by the rotation vector of R(q +- h) R(q)^T), Richardson-extrapolated to O(h^4)"""
+    q = np.asarray(q7, dtype=np.float64)
+    R0 = orc.fk(OP, arm, q)[0]
+    return (4.0 * _central(orc, OP, arm, q, R0, h / 2) - _central(orc, OP, arm, q, R0, h)) / 3.0
+
+
+def joint_box(OP):
+    """[lb + joint_eps, ub - joint_eps]: where every iterate is kept"""
+    return np.array(OP.lb[:]) + OP.joint_eps, np.array(OP.ub[:]) - OP.joint_eps
+
+
+def restated_error(orc, OP, arm, pose, q7, fk_problem=None):
+    """the six error components of arm `arm` at q7 against the hand target of `pose`"""
+    Rt, pt = hand_target(OP, np.asarray(pose, dtype=np.float64), arm)
+    R, p = orc.fk(OP if fk_problem is None else fk_problem, arm, np.asarray(q7, dtype=np.float64))
+    return twist(Rt, pt, R, p)
+
+
+def restated_step(orc, OP, arm, pose, q7, opts, h=H_FINE, fk_problem=None):
+    """One step of csrc/ccmp_ik.h from q7 (inside the joint box): e = twist to hand_target, clamped in norm to err_clamp;
+    dq = J^T (J J^T + lambda^2 I)^-1 e in the world frame; q + dq clamped to the joint box.  -> (the next iterate (7,), the largest
+    |e_i| before the step).  fk_problem: another problem's arm under the same target (what tells the models apart)."""
+    q = np.asarray(q7, dtype=np.float64)
+    F = OP if fk_problem is None else fk_problem
+    e = restated_error(orc, OP, arm, pose, q, F)
+    emax = float(np.abs(e).max())
+    n = float(np.linalg.norm(e))
+    if n > opts.err_clamp:
+        e = e * (opts.err_clamp / n)
+    J = fk_jacobian(orc, F, arm, q, h)
+    dq = J.T @ np.linalg.solve(J @ J.T + opts.lambda_ ** 2 * np.eye(6), e)
+    lo, hi = joint_box(F)
+    return np.clip(q + dq, lo, hi), emax
+
+
+def restart_start(orc, OP, opts, rng_seed, first_index, t, s, S, r):
+    """the 14 start joints of restart candidate r >= 1 of (target t, slot s) in a call of S slots: orc_ambient_gaussian at stream index
+    ((first_index + t) S + s) R + (r - 1) around mid-range with opts.sigma, clamped to the joint box; arm a takes entries 7a..7a+6"""
+    assert 1 <= r <= opts.restarts
+    index = ((int(first_index) + t) * S + s) * int(opts.restarts) + (r - 1)
+    mid = np.tile(0.5 * (np.array(OP.lb[:]) + np.array(OP.ub[:])), 2)
+    v = orc.ambient_ref_batch(OP, "gaussian", int(rng_seed), index, mid, float(opts.sigma), 1)[0]
+    lo, hi = joint_box(OP)
+    return np.clip(v, np.tile(lo, 2), np.tile(hi, 2))
+
+
+def step_tolerance(fine, coarse):
+    """(tolerance, spread) of a step comparison from the restatement at H_FINE and at H_COARSE over all rows of a test: 200 x their
+    largest difference — the factor covers the oracle's libm arithmetic against the library's own and the conditioning
+    (sigma^2 + lambda^2) / lambda^2 <~ 1e4 of the damped solve — and never above 1e-6"""
+    spread = float(np.abs(np.asarray(fine) - np.asarray(coarse)).max())
+    tol = 200.0 * spread
+    assert 0.0 < tol <= 1e-6, (tol, spread)
+    return tol, spread

@@ -4,14 +4,15 @@ ccmp_arm_clearance_ref and ccmp_pose_ik_vetted_ref are the checkers — one text
 output is compared BIT FOR BIT — and the arm clearance is also compared with ccmp_clearance_batch on the sub-scene without the other
 arm's moving spheres.  Batches are ragged against ik_vet_kernel's four rows per wavefront; the scenes are those of
 tests/test_ik_vet_ref.py: per-arm pair counts around the sixteen-lane stride, the largest scene the pair rule admits, the default
-skeleton scene and the scenes built from the plain run's records."""
+skeleton scene and the scenes built from the plain run's records.  The arm clearance runs on every arm model of
+tests/arm_model_cases.py; the vetted rule on the tilted ones is in tests/test_gpu_pose_ik_models.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import ik_vet_cases as V
-from arm_model_cases import default_scene_host
+from arm_model_cases import default_scene_host, tilt
 from test_gpu_pose_ik import _constraint, _inputs
 
 pytestmark = pytest.mark.gpu
@@ -37,13 +38,15 @@ def _same(dev, ref, keys=VET_KEYS):
         assert np.array_equal(_bytes(dev[k]), _bytes(ref[k])), k
 
 
-@pytest.mark.parametrize("calibrated", [False, True], ids=["stock", "calibrated"])
-def test_arm_clearance_bit_for_bit(gpu_ctx, oracle_det, calibrated):
+@pytest.mark.parametrize("model", ["stock", "calibrated", "tilted", "calibrated_tilted"])
+def test_arm_clearance_bit_for_bit(gpu_ctx, oracle_det, model):
     import torch
     from closed_chain_motion_planner_amd import ProxyScene
     from closed_chain_motion_planner_amd.scene import arm_clearance_ref
 
-    c = _constraint(gpu_ctx, calibrated)
+    c = _constraint(gpu_ctx, model in ("calibrated", "calibrated_tilted"))
+    if model in ("tilted", "calibrated_tilted"):
+        tilt(c)  # arm 1 on a rotated base: the world transform of its frames is the general one
     OP = oracle_det.problem_from_bytes(bytes(c.problem))
     n = max(BATCHES)
     q7 = V.candidates(oracle_det, OP, n)
