@@ -46,14 +46,79 @@
 
 namespace ccmp {
 
+namespace detail {
+// the text of every error of this header: "<entry point>: <the library's word for the code>"
+inline std::string describe(int code, const std::string &what) { return what + ": " + ccmp_strerror(code); }
+}  // namespace detail
+
 struct Error : std::runtime_error {
   int code;
-  Error(int c, const std::string &what) : std::runtime_error(what + ": " + ccmp_strerror(c)), code(c) {}
+  Error(int c, const std::string &what) : std::runtime_error(detail::describe(c, what)), code(c) {}
 };
 inline void check(int rc, const char *what)
 {
   if (rc != CCMP_OK) throw Error(rc, what);
 }
+
+namespace detail {
+// The sticky error of the verbs that never throw: the FIRST failure stays until clear().  Not synchronised: the owner's calls are
+// (KinematicChainConstraint, the one class touched from two threads, keeps a mutex of its own around it).
+class ErrorLatch {
+public:
+  void record(int code, const char *what) noexcept
+  {
+    if (code_ != CCMP_OK) return;
+    code_ = code;
+    try { what_ = describe(code, what); } catch (...) {}
+  }
+  // the same rule with the message as given
+  void recordAs(int code, const char *message) noexcept
+  {
+    if (code_ != CCMP_OK) return;
+    code_ = code;
+    try { what_ = message; } catch (...) {}
+  }
+  int code() const noexcept { return code_; }
+  std::string message() const { return what_; }
+  void clear() noexcept { code_ = CCMP_OK; what_.clear(); }
+
+private:
+  int code_ = CCMP_OK;
+  std::string what_;
+};
+// One library call of a verb that never throws: without a handle CCMP_EINVAL; else `body` (returns the library's code) under `mu`, an
+// exception counting as CCMP_EHIP; whatever is not CCMP_OK goes to the latch under the name `what`.  true = the call ran and succeeded.
+template <class F>
+inline bool guardedCall(bool have_handle, std::mutex &mu, ErrorLatch &err, const char *what, F &&body) noexcept
+{
+  if (!have_handle) { err.record(CCMP_EINVAL, what); return false; }
+  int rc;
+  try {
+    std::lock_guard<std::mutex> hold(mu);
+    rc = body();
+  } catch (...) {
+    rc = CCMP_EHIP;
+  }
+  if (rc != CCMP_OK) err.record(rc, what);
+  return rc == CCMP_OK;
+}
+inline void fillNaN(double *x, int n = 14)
+{
+  if (x)
+    for (int i = 0; i < n; i++) x[i] = std::numeric_limits<double>::quiet_NaN();
+}
+// 14 joints between a double[14] and anything indexable (an OMPL StateType, an Eigen::Ref)
+template <class Src>
+inline void load14(double *dst, const Src &src)
+{
+  for (int i = 0; i < 14; ++i) dst[i] = src[i];
+}
+template <class Dst>
+inline void store14(Dst &&dst, const double *src)
+{
+  for (int i = 0; i < 14; ++i) dst[i] = src[i];
+}
+}  // namespace detail
 
 // SplitMix64 (the generator behind the kernels' counter-based samplers) and a process-wide source of sampler seeds:
 // every sampler owns its own stream, as every OMPL StateSampler owns its own ompl::RNG.  CCMP_SEED in the
@@ -193,20 +258,15 @@ public:
   {
     uint8_t ok = 0;
     int32_t slot = -1;
-    int rc;
-    try {
-      std::lock_guard<std::mutex> hold(mu_);
-      rc = ccmp_pose_ik_host(ctx_, &problem_, &ik_opts_, pose8, seeds, 1, S, ikSeed(), ik_index_, result14, &ok, &slot, nullptr, nullptr);
+    const bool ran = detail::guardedCall(true, mu_, err_, "ccmp_pose_ik_host", [&] {
+      const int rc = ccmp_pose_ik_host(ctx_, &problem_, &ik_opts_, pose8, seeds, 1, S, ikSeed(), ik_index_, result14, &ok, &slot, nullptr, nullptr);
       if (rc == CCMP_OK) ik_index_++;
-    } catch (...) {
-      rc = CCMP_EHIP;
-    }
-    if (rc != CCMP_OK) {
-      record(rc, "ccmp_pose_ik_host");
+      return rc;
+    });
+    if (!ran) {
       ok = 0;
       slot = -1;
-      if (result14)
-        for (int i = 0; i < 14; i++) result14[i] = std::numeric_limits<double>::quiet_NaN();
+      detail::fillNaN(result14);
     }
     if (which) *which = slot;
     return ok != 0;
@@ -235,9 +295,9 @@ public:
   uint64_t ikNextIndex() const noexcept { return ik_index_; }
   // for ccmp::Roadmap::grow, under mutex(): the index of the next call's restarts
   uint64_t takeIkIndex() const noexcept { return ik_index_++; }
-  int lastError() const noexcept { return err_code_; }
-  std::string lastErrorMessage() const { return err_what_; }
-  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
+  int lastError() const noexcept { return err_.code(); }
+  std::string lastErrorMessage() const { return err_.message(); }
+  void clearError() noexcept { err_.clear(); }
 
   unsigned getCoDimension() const { return 2; }
   unsigned getAmbientDimension() const { return 14; }
@@ -248,12 +308,6 @@ public:
   std::mutex &mutex() const { return mu_; }
 
 private:
-  void record(int code, const char *what) const noexcept
-  {
-    if (err_code_ != CCMP_OK) return;
-    err_code_ = code;
-    try { err_what_ = std::string(what) + ": " + ccmp_strerror(code); } catch (...) {}
-  }
   mutable std::mutex mu_;
   ccmp_ctx *ctx_ = nullptr;
   ccmp_problem problem_;
@@ -262,9 +316,20 @@ private:
   mutable uint64_t ik_seed_ = 0;
   mutable bool ik_seeded_ = false;
   mutable uint64_t ik_index_ = 0;
-  mutable int err_code_ = CCMP_OK; // the IK verbs' sticky error (the other verbs throw)
-  mutable std::string err_what_;
+  mutable detail::ErrorLatch err_; // the IK verbs' sticky error (the other verbs throw)
 };
+
+namespace detail {
+// the Projector's problem with this delta / lambda where positive (the OMPL space's setDelta / setLambda): a per-call copy, nothing
+// shared is written.  The CALLER holds proj.mutex().
+inline ccmp_problem problemWith(const Projector &proj, double delta, double lambda)
+{
+  ccmp_problem pb = proj.problem();
+  if (delta > 0) pb.delta = delta;
+  if (lambda > 0) pb.lambda = lambda;
+  return pb;
+}
+}  // namespace detail
 
 // jy_ProjectedStateSampler::sampleUniform served from a buffer that ONE launch of `batch` fused
 // sample -> project -> enforceBounds refills when empty (src/base/jy_ProjectedStateSpace.cpp:10-15).
@@ -364,11 +429,26 @@ private:
 // target fails it returns false with only `from` in the list (src/planner/stefanBiPRM.cpp:397-398).
 // delta / lambda > 0 override the problem's values for this call (the space's setDelta / setLambda) through a per-call
 // copy of the problem: nothing shared is written, whichever thread calls.
+namespace detail {
+// The host loop of every discreteGeodesicBatch / discreteGeodesic.  scene != nullptr (never with interpolate): the traversal itself
+// refuses a state whose clearance does not exceed `margin` (ccmp_geodesic_scene_host) and (*blocked)[e] (nullable) = 1 where edge e
+// ended at such a state; else ccmp_geodesic_host_ex — the first pass and the continuations alike.
 template <class ValidFn>
-inline void discreteGeodesicBatch(const Projector &proj, const double *from, const double *to, size_t E, bool interpolate, ValidFn valid,
-                                  std::vector<std::vector<std::vector<double>>> *geodesics, std::vector<char> *reached, int max_states = 64,
-                                  bool check_target = false, double delta = -1.0, double lambda = -1.0)
+inline void traverseBatch(const Projector &proj, const double *from, const double *to, size_t E, bool interpolate, ValidFn valid,
+                          std::vector<std::vector<std::vector<double>>> *geodesics, std::vector<char> *reached, int max_states, bool check_target,
+                          double delta, double lambda, const ccmp_scene *scene, double margin, std::vector<char> *blocked)
 {
+  // one library call, by the caller under proj.mutex(): bl = the edges' blocked bytes (with a scene), carry as ccmp_geodesic_host_ex has it
+  const auto traversal = [&](const ccmp_problem &pb, const double *a, const double *b, size_t edges, int cap, double *st, int32_t *n, uint8_t *ok,
+                             uint8_t *bl, const double *carry_in, double *carry_out, int budget, int target, bool continued) {
+    if (scene)
+      check(ccmp_geodesic_scene_host(proj.ctx(), &pb, scene, margin, a, b, edges, cap, st, n, ok, nullptr, bl, nullptr, carry_in, carry_out, budget, target),
+            continued ? "ccmp_geodesic_scene_host(continue)" : "ccmp_geodesic_scene_host");
+    else
+      check(ccmp_geodesic_host_ex(proj.ctx(), &pb, a, b, edges, cap, st, n, ok, carry_in, carry_out, budget, target),
+            continued ? "ccmp_geodesic_host_ex(continue)" : "ccmp_geodesic_host_ex");
+  };
+  if (blocked) blocked->assign(E, 0);
   if (reached) reached->assign(E, 0);
   if (geodesics) geodesics->assign(E, {});
   if (E == 0) return;
@@ -383,15 +463,11 @@ inline void discreteGeodesicBatch(const Projector &proj, const double *from, con
   ccmp_problem pb;
   std::vector<double> states(E * (size_t)first_cap * 14), carry(E * 2);
   std::vector<int32_t> n(E);
-  std::vector<uint8_t> ok(E);
+  std::vector<uint8_t> ok(E), bl(scene ? E : 0);
   {
     std::lock_guard<std::mutex> hold(proj.mutex());
-    pb = proj.problem();
-    if (delta > 0) pb.delta = delta;
-    if (lambda > 0) pb.lambda = lambda;
-    check(ccmp_geodesic_host_ex(proj.ctx(), &pb, from, to, E, first_cap, states.data(), n.data(), ok.data(), nullptr, carry.data(),
-                                first_budget, check_target ? 1 : 0),
-          "ccmp_geodesic_host_ex");
+    pb = problemWith(proj, delta, lambda);
+    traversal(pb, from, to, E, first_cap, states.data(), n.data(), ok.data(), bl.data(), nullptr, carry.data(), first_budget, check_target ? 1 : 0, false);
   }
   std::vector<double> more((size_t)max_states * 14);
   for (size_t e = 0; e < E; ++e) {
@@ -400,7 +476,7 @@ inline void discreteGeodesicBatch(const Projector &proj, const double *from, con
     const double *to_e = to + 14 * e;
     double cr[2] = {carry[2 * e], carry[2 * e + 1]};
     int32_t ne = n[e];
-    uint8_t oke = ok[e];
+    uint8_t oke = ok[e], ble = scene ? bl[e] : 0;
     bool good = false, cut = false;
     std::vector<double> last(14);
     int first = 0; // a continuation's row 0 repeats the state it started from
@@ -421,14 +497,14 @@ inline void discreteGeodesicBatch(const Projector &proj, const double *from, con
         list.emplace_back(row, row + 14);
       }
       if (cut) break;
-      if (ne <= cap && oke != 2) { good = oke != 0; break; }
+      // the edge ended here: a blocked edge is final too (the traversal's ok is the reference's answer behind the break)
+      if (ne <= cap && oke != 2) { good = oke != 0; if (blocked) (*blocked)[e] = (char)ble; break; }
       // ne == cap + 1: the list was full and the traversal stopped there; ok == 2: it had spent the call's Newton rounds —
       // either way go on from its last state
       double cr_out[2];
       {
         std::lock_guard<std::mutex> hold(proj.mutex());
-        check(ccmp_geodesic_host_ex(proj.ctx(), &pb, last.data(), to_e, 1, max_states, more.data(), &ne, &oke, cr, cr_out, 0, 0),
-              "ccmp_geodesic_host_ex(continue)");
+        traversal(pb, last.data(), to_e, 1, max_states, more.data(), &ne, &oke, &ble, cr, cr_out, 0, 0, true);
       }
       cr[0] = cr_out[0];
       cr[1] = cr_out[1];
@@ -440,6 +516,16 @@ inline void discreteGeodesicBatch(const Projector &proj, const double *from, con
     if (geodesics) (*geodesics)[e] = std::move(list);
   }
 }
+}  // namespace detail
+
+// E edges, as described above
+template <class ValidFn>
+inline void discreteGeodesicBatch(const Projector &proj, const double *from, const double *to, size_t E, bool interpolate, ValidFn valid,
+                                  std::vector<std::vector<std::vector<double>>> *geodesics, std::vector<char> *reached, int max_states = 64,
+                                  bool check_target = false, double delta = -1.0, double lambda = -1.0)
+{
+  detail::traverseBatch(proj, from, to, E, interpolate, valid, geodesics, reached, max_states, check_target, delta, lambda, nullptr, 0.0, nullptr);
+}
 
 // one edge
 template <class ValidFn>
@@ -449,8 +535,8 @@ inline bool discreteGeodesic(const Projector &proj, const double *from14, const 
 {
   std::vector<std::vector<std::vector<double>>> lists;
   std::vector<char> reached;
-  discreteGeodesicBatch(proj, from14, to14, 1, interpolate, valid, geodesic ? &lists : nullptr, &reached, max_states, check_target, delta,
-                        lambda);
+  detail::traverseBatch(proj, from14, to14, 1, interpolate, valid, geodesic ? &lists : nullptr, &reached, max_states, check_target, delta, lambda, nullptr,
+                        0.0, nullptr);
   if (geodesic) *geodesic = std::move(lists[0]);
   return reached[0] != 0;
 }
@@ -476,9 +562,7 @@ inline int densifyPathLocked(const Projector &proj, std::vector<std::array<doubl
                              double delta = 0.0, double lambda = 0.0)
 {
   static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double), "rows are contiguous");
-  ccmp_problem P = proj.problem();
-  if (delta > 0.0) P.delta = delta;
-  if (lambda > 0.0) P.lambda = lambda;
+  const ccmp_problem P = detail::problemWith(proj, delta, lambda);
   ccmp_dense_opts o;
   ccmp_dense_opts_default(&o);
   o.flags = distinct ? CCMP_DENSE_DISTINCT : 0;
@@ -525,9 +609,7 @@ inline int shortcutPathLocked(const Projector &proj, std::vector<std::array<doub
     return CCMP_OK;
   }
   if (states.size() > (size_t)CCMP_SHORTCUT_MAX_LEN) return CCMP_EINVAL;
-  ccmp_problem P = proj.problem();
-  if (delta > 0.0) P.delta = delta;
-  if (lambda > 0.0) P.lambda = lambda;
+  const ccmp_problem P = detail::problemWith(proj, delta, lambda);
   ccmp_shortcut_opts o;
   ccmp_shortcut_opts_default(&o);
   o.max_span = max_span;
@@ -593,7 +675,7 @@ public:
   {
     std::lock_guard<std::mutex> hold(proj_.mutex());
     rm_ = ccmp_roadmap_create(proj_.ctx(), capacity_hint);
-    if (!rm_) record(CCMP_EHIP, "ccmp_roadmap_create");
+    if (!rm_) err_.record(CCMP_EHIP, "ccmp_roadmap_create");
   }
   ~Roadmap()
   {
@@ -631,7 +713,7 @@ public:
       idx->assign(k, -1);
       if (dist) dist->assign(k, 0.0);
     } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::nearestK");
+      err_.record(CCMP_ENOMEM, "Roadmap::nearestK");
       return false;
     }
     return call([&] { return ccmp_roadmap_knn_host(rm_, metric, query, 1, (int)k, mode, self_base, idx->data(), dist ? dist->data() : nullptr); },
@@ -643,15 +725,7 @@ public:
                std::vector<int32_t> *n_states, std::vector<uint8_t> *ok, std::vector<double> *states, const ccmp_scene *scene = nullptr,
                double margin = 0.0, int mode = CCMP_KNN_ALL, size_t self_base = 0) const noexcept
   {
-    try {
-      idx->assign(k, -1);
-      n_states->assign(k, 0);
-      ok->assign(k, 0);
-      states->assign((size_t)k * (size_t)(max_states > 0 ? max_states : 0) * 14, 0.0);
-    } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::connect");
-      return false;
-    }
+    if (!resetSlots("Roadmap::connect", k, max_states, idx, n_states, ok, states)) return false;
     return call([&] {
       return ccmp_roadmap_connect_host(rm_, &proj_.problem(), scene, margin, metric, query_joints, query_pose, 1, (int)k, mode, self_base, check_target ? 1 : 0,
                                        max_states, 0, idx->data(), nullptr, states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr);
@@ -669,34 +743,7 @@ public:
             std::vector<uint8_t> *ok, std::vector<double> *states, bool check_target = false, const ccmp_scene *scene = nullptr, double margin = 0.0,
             int mode = CCMP_KNN_ALL, size_t self_base = 0) const noexcept
   {
-    uint8_t ik_ok = 0;
-    int32_t slot = -1;
-    if (q_new14)
-      for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
-    if (ik_which) *ik_which = -1;
-    try {
-      idx->assign(k, -1);
-      n_states->assign(k, 0);
-      ok->assign(k, 0);
-      states->assign((size_t)k * (size_t)(max_states > 0 ? max_states : 0) * 14, 0.0);
-    } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::grow");
-      return false;
-    }
-    const bool ran = call([&] {
-      const int rc = ccmp_roadmap_grow_host(rm_, &proj_.problem(), scene, margin, &proj_.ikOptions(), pose8, 1, (int)k, mode, self_base, proj_.ikSeed(),
-                                            proj_.ikNextIndex(), check_target ? 1 : 0, max_states, 0, idx->data(), nullptr, q_new14, &ik_ok, &slot,
-                                            states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr);
-      if (rc == CCMP_OK) (void)proj_.takeIkIndex();
-      return rc;
-    }, "ccmp_roadmap_grow_host");
-    if (!ran) {
-      if (q_new14)
-        for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
-      return false;
-    }
-    if (ik_which) *ik_which = slot;
-    return ik_ok != 0;
+    return growWith(false, nullptr, pose8, k, max_states, idx, q_new14, ik_which, n_states, ok, states, check_target, scene, margin, mode, self_base);
   }
 
   // grow() with the vetted IK (ccmp_roadmap_grow_vetted_host): `scene` (required; ProxyScene::handle()) stands where the reference has
@@ -707,37 +754,9 @@ public:
             std::vector<uint8_t> *ok, std::vector<double> *states, const ccmp_scene *scene, double margin, bool vet, double *ik_clearance = nullptr,
             bool check_target = false, int mode = CCMP_KNN_ALL, size_t self_base = 0) const noexcept
   {
-    if (ik_clearance) *ik_clearance = std::numeric_limits<double>::quiet_NaN();
-    if (!vet) return grow(pose8, k, max_states, idx, q_new14, ik_which, n_states, ok, states, check_target, scene, margin, mode, self_base);
-    uint8_t ik_ok = 0;
-    int32_t slot = -1;
-    if (q_new14)
-      for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
-    if (ik_which) *ik_which = -1;
-    try {
-      idx->assign(k, -1);
-      n_states->assign(k, 0);
-      ok->assign(k, 0);
-      states->assign((size_t)k * (size_t)(max_states > 0 ? max_states : 0) * 14, 0.0);
-    } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::grow");
-      return false;
-    }
-    const bool ran = call([&] {
-      const int rc = ccmp_roadmap_grow_vetted_host(rm_, &proj_.problem(), scene, margin, &proj_.ikOptions(), pose8, 1, (int)k, mode, self_base, proj_.ikSeed(),
-                                                   proj_.ikNextIndex(), check_target ? 1 : 0, max_states, 0, idx->data(), nullptr, q_new14, &ik_ok, &slot,
-                                                   ik_clearance, states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr);
-      if (rc == CCMP_OK) (void)proj_.takeIkIndex();
-      return rc;
-    }, "ccmp_roadmap_grow_vetted_host");
-    if (!ran) {
-      if (q_new14)
-        for (int i = 0; i < 14; i++) q_new14[i] = std::numeric_limits<double>::quiet_NaN();
-      if (ik_clearance) *ik_clearance = std::numeric_limits<double>::quiet_NaN();
-      return false;
-    }
-    if (ik_which) *ik_which = slot;
-    return ik_ok != 0;
+    detail::fillNaN(ik_clearance, 1);
+    return growWith(vet, vet ? ik_clearance : nullptr, pose8, k, max_states, idx, q_new14, ik_which, n_states, ok, states, check_target, scene, margin, mode,
+                    self_base);
   }
 
   // ---- the graph (include/ccmp.h: ccmp_roadmap_commit / _add_edges / _closest) --------------------------------------------------------
@@ -758,11 +777,11 @@ public:
       mids.assign(k, -1);
       if (mid_index) mid_index->assign(k, -1);
     } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::commit");
+      err_.record(CCMP_ENOMEM, "Roadmap::commit");
       return CCMP_GROW_TRAPPED;
     }
     if (ok.size() != k || n_states.size() != k || (states && states->size() < k * (size_t)(max_states > 0 ? max_states : 0) * 14)) {
-      record(CCMP_EINVAL, "Roadmap::commit");
+      err_.record(CCMP_EINVAL, "Roadmap::commit");
       return CCMP_GROW_TRAPPED;
     }
     const uint8_t vertex_ok = have_state ? 1 : 0;
@@ -799,7 +818,7 @@ public:
       fd.assign(froms.size(), std::numeric_limits<double>::quiet_NaN());
       if (from_dist) *from_dist = fd;
     } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::closest");
+      err_.record(CCMP_ENOMEM, "Roadmap::closest");
       return false;
     }
     const bool ran = call([&] { return ccmp_roadmap_closest_host(rm_, froms.data(), froms.size(), target_pose8, idx->data(), dist->data(), fd.data()); },
@@ -836,7 +855,7 @@ public:
         for (size_t i = 0; i < (size_t)len; i++) std::memcpy((*states)[i].data(), rows.data() + i * 14, 14 * sizeof(double));
       }
     } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::shortestPath");
+      err_.record(CCMP_ENOMEM, "Roadmap::shortestPath");
       path.clear();
       return false;
     }
@@ -887,7 +906,7 @@ public:
       if (cost) *cost = c[best];
       return true;
     } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::constructSolution");
+      err_.record(CCMP_ENOMEM, "Roadmap::constructSolution");
       states.clear();
       return false;
     }
@@ -935,42 +954,70 @@ public:
       }
       if (indices) indices->swap(path);
     } catch (...) {
-      record(CCMP_ENOMEM, "Roadmap::constructShortcutSolution");
+      err_.record(CCMP_ENOMEM, "Roadmap::constructShortcutSolution");
       if (indices) indices->clear();
     }
     return true;
   }
 
-  int lastError() const noexcept { return err_code_; }
-  std::string lastErrorMessage() const { return err_what_; }
-  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
+  int lastError() const noexcept { return err_.code(); }
+  std::string lastErrorMessage() const { return err_.message(); }
+  void clearError() noexcept { err_.clear(); }
   ccmp_roadmap *handle() const noexcept { return rm_; }
 
 private:
   template <class F>
   bool call(F &&body, const char *what) const noexcept
   {
-    if (!rm_) { record(CCMP_EINVAL, what); return false; }
-    int rc;
-    try {
-      std::lock_guard<std::mutex> hold(proj_.mutex());
-      rc = body();
-    } catch (...) {
-      rc = CCMP_EHIP;
-    }
-    if (rc != CCMP_OK) record(rc, what);
-    return rc == CCMP_OK;
+    return detail::guardedCall(rm_ != nullptr, proj_.mutex(), err_, what, std::forward<F>(body));
   }
-  void record(int code, const char *what) const noexcept
+  // connect's and grow's outputs for k slots, empty; false (CCMP_ENOMEM under the verb's name) when they cannot be had
+  bool resetSlots(const char *verb, unsigned k, int max_states, std::vector<int32_t> *idx, std::vector<int32_t> *n_states, std::vector<uint8_t> *ok,
+                  std::vector<double> *states) const noexcept
   {
-    if (err_code_ != CCMP_OK) return;
-    err_code_ = code;
-    try { err_what_ = std::string(what) + ": " + ccmp_strerror(code); } catch (...) {}
+    try {
+      idx->assign(k, -1);
+      n_states->assign(k, 0);
+      ok->assign(k, 0);
+      states->assign((size_t)k * (size_t)(max_states > 0 ? max_states : 0) * 14, 0.0);
+      return true;
+    } catch (...) {
+      err_.record(CCMP_ENOMEM, verb);
+      return false;
+    }
+  }
+  // both grow() forms: vet chooses ccmp_roadmap_grow_vetted_host, which alone writes *ik_clearance (nullable)
+  bool growWith(bool vet, double *ik_clearance, const double *pose8, unsigned k, int max_states, std::vector<int32_t> *idx, double *q_new14, int *ik_which,
+                std::vector<int32_t> *n_states, std::vector<uint8_t> *ok, std::vector<double> *states, bool check_target, const ccmp_scene *scene,
+                double margin, int mode, size_t self_base) const noexcept
+  {
+    uint8_t ik_ok = 0;
+    int32_t slot = -1;
+    detail::fillNaN(q_new14);
+    if (ik_which) *ik_which = -1;
+    if (!resetSlots("Roadmap::grow", k, max_states, idx, n_states, ok, states)) return false;
+    const bool ran = call([&] {
+      const int target = check_target ? 1 : 0;
+      const int rc = vet ? ccmp_roadmap_grow_vetted_host(rm_, &proj_.problem(), scene, margin, &proj_.ikOptions(), pose8, 1, (int)k, mode, self_base,
+                                                         proj_.ikSeed(), proj_.ikNextIndex(), target, max_states, 0, idx->data(), nullptr, q_new14, &ik_ok,
+                                                         &slot, ik_clearance, states->data(), n_states->data(), ok->data(), nullptr, nullptr, nullptr)
+                         : ccmp_roadmap_grow_host(rm_, &proj_.problem(), scene, margin, &proj_.ikOptions(), pose8, 1, (int)k, mode, self_base, proj_.ikSeed(),
+                                                  proj_.ikNextIndex(), target, max_states, 0, idx->data(), nullptr, q_new14, &ik_ok, &slot, states->data(),
+                                                  n_states->data(), ok->data(), nullptr, nullptr, nullptr);
+      if (rc == CCMP_OK) (void)proj_.takeIkIndex();
+      return rc;
+    }, vet ? "ccmp_roadmap_grow_vetted_host" : "ccmp_roadmap_grow_host");
+    if (!ran) {
+      detail::fillNaN(q_new14);
+      detail::fillNaN(ik_clearance, 1);
+      return false;
+    }
+    if (ik_which) *ik_which = slot;
+    return ik_ok != 0;
   }
   const Projector &proj_;
   ccmp_roadmap *rm_ = nullptr;
-  mutable int err_code_ = CCMP_OK;
-  mutable std::string err_what_;
+  mutable detail::ErrorLatch err_;
 };
 
 // ---- the head of growTree (include/ccmp.h: ccmp_object_*) ---------------------------------------------------------------------------
@@ -1054,7 +1101,7 @@ public:
                int attempts = 2) noexcept
   {
     int32_t w = -1;
-    for (int i = 0; i < 7; i++) out8[i] = std::numeric_limits<double>::quiet_NaN();
+    detail::fillNaN(out8, 7);
     out8[7] = 0.0;
     if (which) *which = -1;
     const bool ran = call([&] {
@@ -1063,7 +1110,7 @@ public:
       return rc;
     }, "ccmp_object_propose_host");
     if (!ran) {
-      for (int i = 0; i < 7; i++) out8[i] = std::numeric_limits<double>::quiet_NaN();
+      detail::fillNaN(out8, 7);
       return false;
     }
     if (which) *which = w;
@@ -1081,7 +1128,7 @@ public:
       rows->assign((size_t)steps * 8, 0.0);
       valid.assign((size_t)steps, 0);
     } catch (...) {
-      record(CCMP_ENOMEM, "ObjectChecker::ladder");
+      err_.record(CCMP_ENOMEM, "ObjectChecker::ladder");
       return 0;
     }
     for (int i = 1; i <= steps; i++) ccmp_pose_interpolate(from8, goal8, 0.1 * i, rows->data() + (size_t)(i - 1) * 8);
@@ -1092,43 +1139,22 @@ public:
   }
 
   int numTriangles() const noexcept { return ccmp_object_num_triangles(obj_); }
-  int lastError() const noexcept { return err_code_; }
-  std::string lastErrorMessage() const { return err_what_; }
-  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
+  int lastError() const noexcept { return err_.code(); }
+  std::string lastErrorMessage() const { return err_.message(); }
+  void clearError() noexcept { err_.clear(); }
   ccmp_object *handle() const noexcept { return obj_; }
 
 private:
   void create(const double *tri, int M, const ccmp_box *boxes, int n_boxes) noexcept
   {
     for (int i = 0; i < 3; i++) { lo_[i] = -1e30; hi_[i] = 1e30; }
-    int rc;
-    try {
-      std::lock_guard<std::mutex> hold(*mu_);
-      rc = ccmp_object_create(ctx_, tri, M, boxes, n_boxes, &obj_);
-    } catch (...) {
-      rc = CCMP_EHIP;
-    }
-    if (rc != CCMP_OK) { obj_ = nullptr; record(rc, "ccmp_object_create"); }
+    // (the library itself answers for a null context)
+    if (!detail::guardedCall(true, *mu_, err_, "ccmp_object_create", [&] { return ccmp_object_create(ctx_, tri, M, boxes, n_boxes, &obj_); })) obj_ = nullptr;
   }
   template <class F>
   bool call(F &&body, const char *what) const noexcept
   {
-    if (!obj_) { record(CCMP_EINVAL, what); return false; }
-    int rc;
-    try {
-      std::lock_guard<std::mutex> hold(*mu_);
-      rc = body();
-    } catch (...) {
-      rc = CCMP_EHIP;
-    }
-    if (rc != CCMP_OK) record(rc, what);
-    return rc == CCMP_OK;
-  }
-  void record(int code, const char *what) const noexcept
-  {
-    if (err_code_ != CCMP_OK) return;
-    err_code_ = code;
-    try { err_what_ = std::string(what) + ": " + ccmp_strerror(code); } catch (...) {}
+    return detail::guardedCall(obj_ != nullptr, *mu_, err_, what, std::forward<F>(body));
   }
   ccmp_ctx *ctx_ = nullptr;
   std::mutex *mu_ = nullptr;
@@ -1136,8 +1162,7 @@ private:
   ccmp_object *obj_ = nullptr;
   double inflate_ = 0.0, lo_[3], hi_[3];
   uint64_t seed_ = 0, next_ = 0;
-  mutable int err_code_ = CCMP_OK;
-  mutable std::string err_what_;
+  mutable detail::ErrorLatch err_;
 };
 
 // One planner process, several GPUs (the reference's shape: src/main.cpp is one process): one context per device and an
@@ -1258,27 +1283,19 @@ public:
   {
     double clr = std::numeric_limits<double>::quiet_NaN();
     uint8_t free_flag = 0;
-    int rc;
-    try {
-      std::lock_guard<std::mutex> hold(proj_.mutex());
-      rc = ccmp_arm_clearance_host(proj_.ctx(), &proj_.problem(), scene_, arm, q7, 1, margin, &clr, &free_flag);
-    } catch (...) {
-      rc = CCMP_EHIP;
-    }
-    if (rc != CCMP_OK) {
-      if (err_code_ == CCMP_OK) {
-        err_code_ = rc;
-        try { err_what_ = std::string("ccmp_arm_clearance_host: ") + ccmp_strerror(rc); } catch (...) {}
-      }
+    const bool ran = detail::guardedCall(true, proj_.mutex(), err_, "ccmp_arm_clearance_host", [&] {
+      return ccmp_arm_clearance_host(proj_.ctx(), &proj_.problem(), scene_, arm, q7, 1, margin, &clr, &free_flag);
+    });
+    if (!ran) {
       clr = std::numeric_limits<double>::quiet_NaN();
       free_flag = 0;
     }
     if (clearance) *clearance = clr;
     return free_flag != 0;
   }
-  int lastError() const noexcept { return err_code_; }
-  std::string lastErrorMessage() const { return err_what_; }
-  void clearError() noexcept { err_code_ = CCMP_OK; err_what_.clear(); }
+  int lastError() const noexcept { return err_.code(); }
+  std::string lastErrorMessage() const { return err_.message(); }
+  void clearError() noexcept { err_.clear(); }
   const ccmp_scene *handle() const { return scene_; }
   const Projector &projector() const { return proj_; }
 
@@ -1303,8 +1320,7 @@ public:
 private:
   const Projector &proj_;
   ccmp_scene *scene_ = nullptr;
-  mutable int err_code_ = CCMP_OK; // ikValid's sticky error (the other verbs throw)
-  mutable std::string err_what_;
+  mutable detail::ErrorLatch err_; // ikValid's sticky error (the other verbs throw)
 };
 
 inline bool Projector::sampleCalibGoal(const double *pose8, const double *seeds, int S, double *result14, int *which, const ProxyScene &scene, double margin,
@@ -1313,22 +1329,17 @@ inline bool Projector::sampleCalibGoal(const double *pose8, const double *seeds,
   uint8_t ok = 0;
   int32_t slot = -1;
   double clr = std::numeric_limits<double>::quiet_NaN();
-  int rc;
-  try {
-    std::lock_guard<std::mutex> hold(mu_);
-    rc = ccmp_pose_ik_vetted_host(ctx_, &problem_, &ik_opts_, pose8, seeds, 1, S, ikSeed(), ik_index_, scene.handle(), margin, result14, &ok, &slot, nullptr,
-                                  nullptr, nullptr, nullptr, &clr);
+  const bool ran = detail::guardedCall(true, mu_, err_, "ccmp_pose_ik_vetted_host", [&] {
+    const int rc = ccmp_pose_ik_vetted_host(ctx_, &problem_, &ik_opts_, pose8, seeds, 1, S, ikSeed(), ik_index_, scene.handle(), margin, result14, &ok, &slot,
+                                            nullptr, nullptr, nullptr, nullptr, &clr);
     if (rc == CCMP_OK) ik_index_++;
-  } catch (...) {
-    rc = CCMP_EHIP;
-  }
-  if (rc != CCMP_OK) {
-    record(rc, "ccmp_pose_ik_vetted_host");
+    return rc;
+  });
+  if (!ran) {
     ok = 0;
     slot = -1;
     clr = std::numeric_limits<double>::quiet_NaN();
-    if (result14)
-      for (int i = 0; i < 14; i++) result14[i] = std::numeric_limits<double>::quiet_NaN();
+    detail::fillNaN(result14);
   }
   if (which) *which = slot;
   if (clearance) *clearance = clr;
@@ -1347,76 +1358,8 @@ inline void discreteGeodesicBatch(const Projector &proj, const double *from, con
                                   bool check_target, double delta, double lambda, const ProxyScene *scene, double margin,
                                   std::vector<char> *blocked = nullptr)
 {
-  if (blocked) blocked->assign(E, 0);
-  if (!scene || interpolate) {
-    discreteGeodesicBatch(proj, from, to, E, interpolate, exact, geodesics, reached, max_states, check_target, delta, lambda);
-    return;
-  }
-  if (reached) reached->assign(E, 0);
-  if (geodesics) geodesics->assign(E, {});
-  if (E == 0) return;
-  if (max_states < 2) max_states = 2;
-  const bool big = E >= 1024; // the first pass's shape as above
-  const int first_cap = big && max_states > 16 ? 16 : max_states;
-  const int first_budget = big ? 128 : 0;
-  ccmp_problem pb;
-  std::vector<double> states(E * (size_t)first_cap * 14), carry(E * 2);
-  std::vector<int32_t> n(E);
-  std::vector<uint8_t> ok(E), bl(E);
-  {
-    std::lock_guard<std::mutex> hold(proj.mutex());
-    pb = proj.problem();
-    if (delta > 0) pb.delta = delta;
-    if (lambda > 0) pb.lambda = lambda;
-    check(ccmp_geodesic_scene_host(proj.ctx(), &pb, scene->handle(), margin, from, to, E, first_cap, states.data(), n.data(), ok.data(), nullptr,
-                                   bl.data(), nullptr, nullptr, carry.data(), first_budget, check_target ? 1 : 0),
-          "ccmp_geodesic_scene_host");
-  }
-  std::vector<double> more((size_t)max_states * 14);
-  for (size_t e = 0; e < E; ++e) {
-    std::vector<std::vector<double>> list;
-    const double *st = &states[e * (size_t)first_cap * 14];
-    const double *to_e = to + 14 * e;
-    double cr[2] = {carry[2 * e], carry[2 * e + 1]};
-    int32_t ne = n[e];
-    uint8_t oke = ok[e], ble = bl[e];
-    bool good = false, cut = false;
-    std::vector<double> last(14);
-    int first = 0;
-    int cap = first_cap;
-    for (;;) {
-      const int have = ne > cap ? cap : ne;
-      for (int k = first; k < have && !cut; ++k) {
-        const double *row = st + (size_t)k * 14;
-        if (!(list.empty() && k == 0) && !exact(row)) {
-          double d = 0;
-          for (int i = 0; i < 14; ++i) { const double df = last[i] - to_e[i]; d += df * df; }
-          good = std::sqrt(d) <= pb.delta;
-          cut = true;
-          break;
-        }
-        last.assign(row, row + 14);
-        list.emplace_back(row, row + 14);
-      }
-      if (cut) break;
-      // a blocked edge is final (the traversal's ok is the reference's answer behind the break); else as above
-      if (ne <= cap && oke != 2) { good = oke != 0; if (blocked) (*blocked)[e] = (char)ble; break; }
-      double cr_out[2];
-      {
-        std::lock_guard<std::mutex> hold(proj.mutex());
-        check(ccmp_geodesic_scene_host(proj.ctx(), &pb, scene->handle(), margin, last.data(), to_e, 1, max_states, more.data(), &ne, &oke, nullptr,
-                                       &ble, nullptr, cr, cr_out, 0, 0),
-              "ccmp_geodesic_scene_host(continue)");
-      }
-      cr[0] = cr_out[0];
-      cr[1] = cr_out[1];
-      st = more.data();
-      cap = max_states;
-      first = 1;
-    }
-    if (reached) (*reached)[e] = good ? 1 : 0;
-    if (geodesics) (*geodesics)[e] = std::move(list);
-  }
+  detail::traverseBatch(proj, from, to, E, interpolate, exact, geodesics, reached, max_states, check_target, delta, lambda,
+                        scene && !interpolate ? scene->handle() : nullptr, margin, blocked);
 }
 
 // ---- dump formats of the reference's planner run ----------------------------------------------------------------------
@@ -1532,16 +1475,17 @@ public:
   bool project(Eigen::Ref<Eigen::VectorXd> x) const override
   {
     double buf[14];
-    for (int i = 0; i < 14; ++i) buf[i] = x[i];
+    ccmp::detail::load14(buf, x);
     bool ok = false;
     if (!guarded([&] { ok = impl_->project(buf); })) return false;  // x untouched
-    for (int i = 0; i < 14; ++i) x[i] = buf[i];
+    ccmp::detail::store14(x, buf);
     return ok;
   }
   void function(const Eigen::Ref<const Eigen::VectorXd> &x, Eigen::Ref<Eigen::VectorXd> out) const override
   {
-    double buf[14], f[2] = {std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::quiet_NaN()};
-    for (int i = 0; i < 14; ++i) buf[i] = x[i];
+    double buf[14], f[2];
+    ccmp::detail::fillNaN(f, 2);
+    ccmp::detail::load14(buf, x);
     guarded([&] { impl_->function(buf, f); });
     out[0] = f[0];
     out[1] = f[1];
@@ -1549,14 +1493,14 @@ public:
   bool isSatisfied(const Eigen::Ref<const Eigen::VectorXd> &x) const override
   {
     double buf[14];
-    for (int i = 0; i < 14; ++i) buf[i] = x[i];
+    ccmp::detail::load14(buf, x);
     bool ok = false;
     return guarded([&] { ok = impl_->isSatisfied(buf); }) && ok;
   }
   bool jointValid(const Eigen::Ref<const Eigen::VectorXd> &q) const
   {
     double buf[14];
-    for (int i = 0; i < 14; ++i) buf[i] = q[i];
+    ccmp::detail::load14(buf, q);
     bool ok = false;
     return guarded([&] { ok = impl_->jointValid(buf); }) && ok;
   }
@@ -1564,18 +1508,17 @@ public:
   int lastError() const
   {
     std::lock_guard<std::mutex> hold(err_mu_);
-    return err_code_;
+    return err_.code();
   }
   std::string lastErrorMessage() const
   {
     std::lock_guard<std::mutex> hold(err_mu_);
-    return err_what_;
+    return err_.message();
   }
   void clearError() const
   {
     std::lock_guard<std::mutex> hold(err_mu_);
-    err_code_ = CCMP_OK;
-    err_what_.clear();
+    err_.clear();
   }
   // runs `body`; an exception of the library (or any other) is recorded, never passed on: false = it failed.  Used by the space and
   // the samplers below for their own GPU calls too.
@@ -1601,14 +1544,13 @@ private:
   {
     try {
       std::lock_guard<std::mutex> hold(err_mu_);
-      if (err_code_ == CCMP_OK) { err_code_ = code; err_what_ = what; }
+      err_.recordAs(code, what);  // the exception's own text
     } catch (...) {
     }
   }
   std::shared_ptr<ccmp::Projector> impl_;
   mutable std::mutex err_mu_;
-  mutable int err_code_ = CCMP_OK;
-  mutable std::string err_what_;
+  mutable ccmp::detail::ErrorLatch err_;
 };
 typedef std::shared_ptr<KinematicChainConstraint> ChainConstraintPtr;
 
@@ -1668,7 +1610,7 @@ public:
     auto &&x = *state->as<ompl::base::ConstrainedStateSpace::StateType>();
     double buf[14];
     if (!constraint_->guarded([&] { buffer_.next(buf); })) return;  // already projected and wrapped by enforceBounds on the GPU; a failed refill leaves the state as it was (lastError() of the constraint)
-    for (int i = 0; i < 14; ++i) x[i] = buf[i];
+    ccmp::detail::store14(x, buf);
   }
   void sampleUniformNear(ompl::base::State *state, const ompl::base::State *near, const double distance) override
   {
@@ -1685,9 +1627,9 @@ protected:
     const auto &r = *ref->as<ompl::base::ConstrainedStateSpace::StateType>();
     auto &&x = *state->as<ompl::base::ConstrainedStateSpace::StateType>();
     double rb[14], out[14];
-    for (int i = 0; i < 14; ++i) rb[i] = r[i];
+    ccmp::detail::load14(rb, r);
     if (!constraint_->guarded([&] { buf.next(out, rb, param); })) return;  // ambient draw, project (result ignored, as the reference does) and enforceBounds on the GPU
-    for (int i = 0; i < 14; ++i) x[i] = out[i];
+    ccmp::detail::store14(x, out);
   }
   const std::shared_ptr<KinematicChainConstraint> constraint_;
   ccmp::SampleBuffer buffer_;
@@ -1732,7 +1674,7 @@ public:
   void discreteGeodesics(const std::vector<const ompl::base::State *> &from, const ompl::base::State *to, bool interpolate,
                          std::vector<std::vector<ompl::base::State *>> *geodesics, std::vector<char> *reached) const
   {
-    traverseMany(from, to, interpolate, geodesics, reached, false);
+    traverse(from, to, interpolate, geodesics, reached, false);
   }
 
   // connectionStrategy_(m) of the reference's planner (a KStrategy over tree_, src/planner/stefanBiPRM.cpp:292,390,457) on the joint
@@ -1745,12 +1687,8 @@ public:
     if (k == 0 || nodes.empty()) return true;
     std::vector<double> a(nodes.size() * 14);
     double b[14];
-    for (size_t j = 0; j < nodes.size(); ++j) {
-      const auto &x = *nodes[j]->as<StateType>();
-      for (int i = 0; i < 14; ++i) a[14 * j + i] = x[i];
-    }
-    const auto &sb = *s->as<StateType>();
-    for (int i = 0; i < 14; ++i) b[i] = sb[i];
+    for (size_t j = 0; j < nodes.size(); ++j) ccmp::detail::load14(&a[14 * j], *nodes[j]->as<StateType>());
+    ccmp::detail::load14(b, *s->as<StateType>());
     std::vector<int32_t> idx;
     if (!chain_->guarded([&] { ccmp::nearestK(chain_->impl(), a.data(), nodes.size(), b, k, &idx); })) return false;
     for (int32_t j : idx)
@@ -1769,7 +1707,7 @@ public:
     if (!nearestK(nodes, s, k, neighbours)) return;
     std::vector<const ompl::base::State *> from;
     for (unsigned j : *neighbours) from.push_back(nodes[j]);
-    traverseMany(from, s, false, geodesics, reached, true);
+    traverse(from, s, false, geodesics, reached, true);
   }
 
   // The same two on a device-resident ccmp::Roadmap instead of a node vector: only `s` goes up.  pose8 != nullptr ranks on the reference's
@@ -1782,8 +1720,7 @@ public:
     out->clear();
     if (k == 0 || rm.size() == 0) return true;
     double b[14];
-    const auto &sb = *s->as<StateType>();
-    for (int i = 0; i < 14; ++i) b[i] = sb[i];
+    ccmp::detail::load14(b, *s->as<StateType>());
     std::vector<int32_t> idx;
     if (!rm.nearestK(pose8 ? CCMP_METRIC_OBJECT : CCMP_METRIC_JOINT, pose8 ? pose8 : b, k, &idx, nullptr, mode, self_base)) return false;
     for (int32_t j : idx)
@@ -1806,12 +1743,11 @@ public:
       double row[14];
       if (!(ok = rm.read(j, 1, row, nullptr))) break;
       ompl::base::State *n = allocState();
-      auto &x = *n->as<StateType>();
-      for (int i = 0; i < 14; ++i) x[i] = row[i];
+      ccmp::detail::store14(*n->as<StateType>(), row);
       own.push_back(n);
       from.push_back(n);
     }
-    if (ok) traverseMany(from, s, false, geodesics, reached, true);
+    if (ok) traverse(from, s, false, geodesics, reached, true);
     else neighbours->clear();
     for (ompl::base::State *n : own) freeState(n);
   }
@@ -1845,40 +1781,30 @@ public:
   }
 
 private:
-  void traverseMany(const std::vector<const ompl::base::State *> &from, const ompl::base::State *to, bool interpolate,
-                    std::vector<std::vector<ompl::base::State *>> *geodesics, std::vector<char> *reached, bool check_target) const
+  // every traversal of this space: edges from[e] -> to, in one call of ccmp::discreteGeodesicBatch
+  void traverse(const std::vector<const ompl::base::State *> &from, const ompl::base::State *to, bool interpolate,
+                std::vector<std::vector<ompl::base::State *>> *geodesics, std::vector<char> *reached, bool check_target) const
   {
     const size_t E = from.size();
     std::vector<double> a(E * 14), b(E * 14);
-    const auto &tb = *to->as<StateType>();
     for (size_t e = 0; e < E; ++e) {
-      const auto &fa = *from[e]->as<StateType>();
-      for (int i = 0; i < 14; ++i) { a[14 * e + i] = fa[i]; b[14 * e + i] = tb[i]; }
+      ccmp::detail::load14(&a[14 * e], *from[e]->as<StateType>());
+      ccmp::detail::load14(&b[14 * e], *to->as<StateType>());
     }
     ccmp::Projector &proj = chain_->impl();
     auto &&svc = si_->getStateValidityChecker();
     std::vector<std::vector<std::vector<double>>> lists;
     ompl::base::State *scratch = allocState();
+    // with a device prefilter: the proxies inside the traversal, the exact checker alone on the listed states
     const PrefilteredValidityChecker *pre = devicePrefilter(svc.get(), interpolate);
     std::vector<char> blocked;
-    const bool done = chain_->guarded([&] {
-      if (pre)  // the proxies inside the traversal, the exact checker on the listed states
-        ccmp::discreteGeodesicBatch(proj, a.data(), b.data(), E, false,
-                                    [&](const double *q) {
-                                      auto &x = *scratch->as<StateType>();
-                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
-                                      return pre->isValidExact(scratch);
-                                    },
-                                    geodesics ? &lists : nullptr, reached, 64, check_target, delta_, lambda_, pre->scene().get(), pre->rejectBelow(),
-                                    &blocked);
-      else
-        ccmp::discreteGeodesicBatch(proj, a.data(), b.data(), E, interpolate,
-                                    [&](const double *q) {
-                                      auto &x = *scratch->as<StateType>();
-                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
-                                      return svc->isValid(scratch);
-                                    },
-                                    geodesics ? &lists : nullptr, reached, 64, check_target, delta_, lambda_); // setDelta / setLambda of the base class
+    const auto valid = [&](const double *q) {
+      ccmp::detail::store14(*scratch->as<StateType>(), q);
+      return pre ? pre->isValidExact(scratch) : svc->isValid(scratch);
+    };
+    const bool done = chain_->guarded([&] {  // delta_ / lambda_: setDelta / setLambda of the base class stay the source of truth
+      ccmp::discreteGeodesicBatch(proj, a.data(), b.data(), E, interpolate, valid, geodesics ? &lists : nullptr, reached, 64, check_target, delta_, lambda_,
+                                  pre ? pre->scene().get() : nullptr, pre ? pre->rejectBelow() : 0.0, pre ? &blocked : nullptr);
     });
     freeState(scratch);
     if (pre && done)
@@ -1894,68 +1820,21 @@ private:
       for (size_t e = 0; e < E; ++e)
         for (const auto &st : lists[e]) {
           ompl::base::State *s = allocState();
-          auto &x = *s->as<StateType>();
-          for (int i = 0; i < 14; ++i) x[i] = st[i];
+          ccmp::detail::store14(*s->as<StateType>(), st.data());
           (*geodesics)[e].push_back(s);
         }
     }
   }
 
+  // the same for one edge: a failed GPU call is "not reached", no states
   bool traverse(const ompl::base::State *from, const ompl::base::State *to, bool interpolate, std::vector<ompl::base::State *> *geodesic,
                 bool check_target) const
   {
-    double a[14], b[14];
-    const auto &fa = *from->as<StateType>();
-    const auto &tb = *to->as<StateType>();
-    for (int i = 0; i < 14; ++i) { a[i] = fa[i]; b[i] = tb[i]; }
-    ccmp::Projector &proj = chain_->impl();
-    auto &&svc = si_->getStateValidityChecker();
-    std::vector<std::vector<double>> states;
-    ompl::base::State *scratch = allocState();
-    bool ok = false;
-    const PrefilteredValidityChecker *pre = devicePrefilter(svc.get(), interpolate);
-    std::vector<char> blocked;
-    const bool done = chain_->guarded([&] {
-      if (pre) {  // the proxies inside the traversal, the exact checker on the listed states
-        std::vector<std::vector<std::vector<double>>> lists;
-        std::vector<char> reached;
-        ccmp::discreteGeodesicBatch(proj, a, b, 1, false,
-                                    [&](const double *q) {
-                                      auto &x = *scratch->as<StateType>();
-                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
-                                      return pre->isValidExact(scratch);
-                                    },
-                                    geodesic ? &lists : nullptr, &reached, 64, check_target, delta_, lambda_, pre->scene().get(),
-                                    pre->rejectBelow(), &blocked);
-        ok = reached[0] != 0;
-        if (geodesic) states = std::move(lists[0]);
-      } else {
-        ok = ccmp::discreteGeodesic(proj, a, b, interpolate,
-                                    [&](const double *q) {
-                                      auto &x = *scratch->as<StateType>();
-                                      for (int i = 0; i < 14; ++i) x[i] = q[i];
-                                      return svc->isValid(scratch);
-                                    },
-                                    geodesic ? &states : nullptr, 64, check_target, delta_,
-                                    lambda_);  // setDelta / setLambda of the base class stay the source of truth
-      }
-    });
-    freeState(scratch);
-    if (pre && done && blocked[0]) pre->countRejected();
-    if (!done) {  // the GPU call failed (KinematicChainConstraint::lastError()): "not reached", no states
-      if (geodesic) geodesic->clear();
-      return false;
-    }
-    if (geodesic) {
-      geodesic->clear();
-      for (const auto &st : states) {
-        ompl::base::State *s = allocState();
-        auto &x = *s->as<StateType>();
-        for (int i = 0; i < 14; ++i) x[i] = st[i];
-        geodesic->push_back(s);
-      }
-    }
-    return ok;
+    std::vector<std::vector<ompl::base::State *>> lists;
+    std::vector<char> reached;
+    traverse({from}, to, interpolate, geodesic ? &lists : nullptr, &reached, check_target);
+    if (geodesic) *geodesic = std::move(lists[0]);
+    return reached[0] != 0;
   }
 
   // the space information's checker when the extend step can run its proxies on the device: a PrefilteredValidityChecker whose
