@@ -19,6 +19,8 @@ from .dense import DENSE_DISTINCT, dense_arc_ref, dense_layout_ref  # noqa: F401
 
 from .shortcut import SHORTCUT_MAX_LEN, shortcut_pairs_ref, shortcut_select, shortcut_select_ref  # noqa: F401
 
+from .smooth import SMOOTH_STATS, SMOOTH_STOP, smooth_len_after, smooth_mid_ref  # noqa: F401
+
 from .ik import ik_options, pose_ik_ref, pose_ik_vetted_ref  # noqa: F401
 
 from .object import ObjectChecker, object_propose_ref, object_valid_ref, pose_interpolate  # noqa: F401

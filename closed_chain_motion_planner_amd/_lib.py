@@ -74,6 +74,12 @@ class CcmpShortcutOpts(C.Structure):
     _fields_ = [("max_span", C.c_int), ("chunk_states", C.c_int), ("round_budget", C.c_int), ("max_calls", C.c_int), ("tile_edges", C.c_int)]
 
 
+class CcmpSmoothOpts(C.Structure):
+    """ccmp_smooth_opts of include/ccmp.h"""
+    _fields_ = [("max_steps", C.c_int), ("min_change", C.c_double), ("chunk_states", C.c_int), ("round_budget", C.c_int), ("max_calls", C.c_int),
+                ("tile_edges", C.c_int)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -106,6 +112,8 @@ EXPORTS = [
     "ccmp_dense_paths_destroy", "ccmp_dense_layout_ref", "ccmp_dense_arc_ref",
     "ccmp_shortcut_opts_default", "ccmp_path_shortcut", "ccmp_path_shortcut_host", "ccmp_shortcut_select", "ccmp_shortcut_select_host",
     "ccmp_shortcut_select_ref", "ccmp_shortcut_pairs_ref",
+    "ccmp_smooth_opts_default", "ccmp_path_smooth", "ccmp_path_smooth_host", "ccmp_smooth_mid_ref", "ccmp_smooth_len_after",
+    "ccmp_smooth_last_counts",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -304,6 +312,13 @@ def lib():
         "ccmp_shortcut_select_host": ([vp, dp, i32p, C.c_size_t, C.c_int, u8p, dp, i32p, i32p, dp, dp], C.c_int),
         "ccmp_shortcut_select_ref": ([dp, i32p, C.c_size_t, C.c_int, u8p, dp, i32p, i32p, dp, dp], C.c_int),
         "ccmp_shortcut_pairs_ref": ([dp, i32p, C.c_size_t, C.c_int, C.c_int, i32p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_smooth_opts_default": ([C.POINTER(CcmpSmoothOpts)], None),
+        "ccmp_path_smooth": ([vp, pp, vp, C.c_double, vp, vp, C.c_size_t, C.c_int, C.POINTER(CcmpSmoothOpts), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_path_smooth_host": ([vp, pp, vp, C.c_double, dp, i32p, C.c_size_t, C.c_int, C.POINTER(CcmpSmoothOpts), C.c_int, dp, i32p, i32p, i32p, i32p, dp, dp,
+                                   i32p], C.c_int),
+        "ccmp_smooth_mid_ref": ([dp, dp, C.c_int, C.POINTER(C.c_int), dp, dp, C.POINTER(C.c_int)], C.c_int),
+        "ccmp_smooth_len_after": ([C.c_int, C.c_int], C.c_int),
+        "ccmp_smooth_last_counts": ([C.POINTER(C.c_longlong)] * 3, None),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),

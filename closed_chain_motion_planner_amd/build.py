@@ -44,6 +44,9 @@ Translation units with deliberately different flags:
   ccmp_kernels_shortcut.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   shortcut solution paths (ccmp_shortcut.h): the enumeration of a tile of waypoint pairs, the endpoint gather
                          of a continuation, the scatter of flags and counts into the pair matrices, the DAG search (one block per path) and the gather of the kept rows
   ccmp_shortcut.cpp      -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_shortcut: checks, the tile and continuation loops over the extend step; ccmp_shortcut_select*, ccmp_shortcut_pairs_ref
+  ccmp_kernels_smooth.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   smooth solution paths (ccmp_smooth.h): the pair gather of a pass's stages, the bracket of half the arc and
+                         the blend, the pick between projected / fallback / degenerate, the accept step into the other path buffer, lengths and the store
+  ccmp_smooth.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_smooth: checks, the pass loop (midpoint steps on the dense unit's loop, the test step on the shortcut unit's); ccmp_smooth_mid_ref
 """
 import os
 import shutil
@@ -124,8 +127,12 @@ _UNITS = [
     ("ccmp_kernels_shortcut.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_path_shortcut: the checks, the tile and continuation loops, and the rule on the host (ccmp_shortcut_select_ref, ccmp_shortcut_pairs_ref)
     ("ccmp_shortcut.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # smooth solution paths (ccmp_smooth.h): load, gather, bracket, pick, accept, length and store; the shortcut unit's flags; registers and LDS only
+    ("ccmp_kernels_smooth.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # ccmp_path_smooth: the checks, the pass loop over the dense and shortcut units' loops, and the rule on the host (ccmp_smooth_mid_ref, ccmp_smooth_len_after)
+    ("ccmp_smooth.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -172,6 +179,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"graph_", 0),  # the roadmap graph: a slot's FK and distances, a lane's best candidate and the scan's sums live in registers and LDS, every kernel of the unit
     (r"dense_", 0),  # dense solution paths: a chunk's descriptor, a lane's distance and a lane's best (value, row) live in registers and LDS, every kernel of the unit
     (r"shortcut_", 0),  # shortcut solution paths: a slot's decode, a lane's best parent and the search's d / hops / pred live in registers and LDS, every kernel of the unit
+    (r"smooth_", 0),  # smooth solution paths: a pair's decode, its bracket and a lane's row element live in registers, the length's 64 distances in LDS, every kernel of the unit
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

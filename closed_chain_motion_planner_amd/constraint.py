@@ -557,6 +557,25 @@ class KinematicChainConstraint:
         return shortcut(self.ctx, self.problem, path_joints, path_len, scene, margin, max_span, chunk_states, round_budget, max_calls, tile_edges, pairs,
                         stream, _torch(), _stream_handle)
 
+    def smooth_paths(self, path_joints, path_len, max_steps=5, min_change=0.005, out_max_len=None, scene=None, margin=None, chunk_states=16,
+                     round_budget=128, max_calls=4096, tile_edges=65536, stats=False, stream=None):
+        """B-spline smoothing passes on the manifold for F solution paths (ccmp_path_smooth; csrc/ccmp_smooth.h): path_joints
+        (F,max_len,14) and path_len (F,) int32, on the device.  A pass subdivides every segment at mid(w_i, w_{i+1}) — the blend at half
+        the arc of the pair's dense list, projected — and moves every original interior vertex to mid(mid(m_{i-1}, w_i), mid(w_i, m_i))
+        when both checkMotion tests from and to its new neighbours pass (with a ProxyScene and its margin the scene form, and the
+        clearances of the vertices) and it moves by more than min_change: L -> 2L - 1 vertices.  A path stops when a pass moves nothing
+        (stop 1), after max_steps passes (2), when the next pass would not fit out_max_len (3; default ccmp_smooth_len_after(max_len,
+        max_steps): never), with L < 3 (0) or a non-finite waypoint (4).  Returns a dict of device tensors — joints (F,out_max_len,14)
+        (rows behind out_len are the input's, zeros behind those), out_len, passes, moved, stop (F,) int32, length_in / length_out (F,)
+        and, with stats=True, stats (F,5) (SMOOTH_STATS).  numpy arrays go through the host form and come back as numpy arrays.
+        Synchronous.  max_calls spent with a traversal open raises CcmpError (CCMP_EOVERFLOW).  Order of use: shortcut -> smooth ->
+        densify -> the host's validity test over the dense rows."""
+        from .smooth import smooth
+
+        self._need_problem()
+        return smooth(self.ctx, self.problem, path_joints, path_len, max_steps, min_change, out_max_len, scene, margin, chunk_states, round_budget, max_calls,
+                      tile_edges, stats, stream, _torch(), _stream_handle)
+
     def ambient_uniform_batch(self, seed, first_index, B, stream=None):
         self._need_problem()
         torch = _torch()

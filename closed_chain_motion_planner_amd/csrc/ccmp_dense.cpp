@@ -16,6 +16,7 @@
 #include "ccmp_ctx.h"
 #include "ccmp_dense.h"
 #include "ccmp_launch.h"
+#include "ccmp_pair_tests.h"
 #include "ccmp_resident.h"
 #include "ccmp_scene.h"
 #include "ccmp_stage.h"
@@ -24,17 +25,7 @@ using namespace ccmp_host;
 using ccmp::dense_chunk;
 using ccmp::dense_open_seg;
 
-struct ccmp_dense_paths {
-  ccmp_ctx *ctx = nullptr;
-  int device = 0;
-  size_t F = 0, rows = 0, slots = 0; // slots = F (max_len - 1)
-  int max_len = 0, calls = 0;
-  bool has_scene = false;
-  void *block = nullptr; // one allocation; the arrays below point into it
-  double *d_rows = nullptr, *arc = nullptr, *length = nullptr, *clearance = nullptr, *min_clear = nullptr;
-  int32_t *path_first = nullptr, *seg_first = nullptr, *seg_newton = nullptr, *min_row = nullptr, *first_blocked = nullptr;
-  uint8_t *seg_ok = nullptr;
-};
+// (struct ccmp_dense_paths: ccmp_pair_tests.h — the smoothing's midpoint step reads a result's rows and arcs on the device)
 
 namespace {
 
@@ -239,6 +230,7 @@ int densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, doubl
   ccmp_dense_paths *h = nullptr;
   { const int rc = make_handle(ctx, F, F ? max_len : 0, rows, scene != nullptr, &h); if (rc != CCMP_OK) return rc; }
   h->calls = calls;
+  for (const Round &r : rounds) h->read_bytes += r.open.size() * 5;
   int rc = CCMP_OK;
   hipError_t e = hipMemcpyAsync(h->path_first, path_first.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st);
   if (e == hipSuccess && slots) e = hipMemcpyAsync(h->seg_first, seg_first.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, st);
@@ -264,6 +256,12 @@ int densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, doubl
 }
 
 }  // namespace
+
+int ccmp_host::densify_rows(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints,
+                            const std::vector<int32_t> &len, size_t F, int max_len, const ccmp_dense_opts &o, ccmp_dense_paths **out, hipStream_t st)
+{
+  return densify(ctx, p, scene, margin, path_joints, len, F, max_len, o, out, st);
+}
 
 extern "C" {
 

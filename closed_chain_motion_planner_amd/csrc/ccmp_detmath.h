@@ -121,6 +121,23 @@ CCMP_HD double ccmp_div_lean(double n, double d) { return n / d; }
 
 CCMP_HD double ccmp_abs(double x) { return __builtin_fabs(x); }
 
+/* WrapperStateSpace::interpolate through KinematicChainSpace::interpolate (KinematicChain.h:145-171; the oracle's orc_interpolate), one
+ * joint: fr towards tg by the fraction tt, the short way round.  One text for every extend-step kernel and for the smoothing's blend. */
+CCMP_HD double ccmp_joint_interpolate(double fr, double tg, double tt)
+{
+  const double pi = 3.14159265358979323846;
+  double diff = tg - fr, v;
+  if (ccmp_abs(diff) <= pi) v = CCMP_FMA(diff, tt, fr);
+  else {
+    if (diff > 0.0) diff = 2.0 * pi - diff;
+    else diff = -2.0 * pi - diff;
+    v = CCMP_FMA(-diff, tt, fr);
+    if (v > pi) v -= 2.0 * pi;
+    else if (v < -pi) v += 2.0 * pi;
+  }
+  return v;
+}
+
 /* sin(x+y) and cos(x+y), |x| <= pi/4 (+ a hair), y the tail of the reduced argument. */
 CCMP_HD double ccmp_kernel_sin(double x, double y)
 {

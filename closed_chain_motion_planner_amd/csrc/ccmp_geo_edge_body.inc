@@ -73,16 +73,7 @@
         if (tid < 14 && !resume) { // WrapperStateSpace::interpolate(previous, to, delta_ / dist, scratch)
           const double tt = delta / dist;
           const double fr = x_own;
-          double diff = to_own - fr, v;
-          if (ccmp_abs(diff) <= pi) v = CCMP_FMA(diff, tt, fr);
-          else {
-            if (diff > 0.0) diff = 2.0 * pi - diff;
-            else diff = -2.0 * pi - diff;
-            v = CCMP_FMA(-diff, tt, fr);
-            if (v > pi) v -= 2.0 * pi;
-            else if (v < -pi) v += 2.0 * pi;
-          }
-          rec[fX + tid] = v;
+          rec[fX + tid] = ccmp_joint_interpolate(fr, to_own, tt);
           rec[gPrev + tid] = fr; // previous := the accepted state (unchanged on the first pass)
         }
         __syncthreads();

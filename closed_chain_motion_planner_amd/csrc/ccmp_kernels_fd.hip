@@ -524,20 +524,8 @@ constexpr int kGPrev = kRec, kGDist = kRec + 14, kGCnt = kRec + 17, kRecG = kRec
 static_assert(kRecG % 2 == 1, "odd record stride: the ten groups stay on distinct LDS banks");
 
 // WrapperStateSpace::interpolate through KinematicChainSpace::interpolate (KinematicChain.h:145-171), one joint
-__device__ __forceinline__ double geo_interpolate(double fr, double tg, double tt)
-{
-  const double pi = 3.14159265358979323846;
-  double diff = tg - fr, v;
-  if (ccmp_abs(diff) <= pi) v = CCMP_FMA(diff, tt, fr);
-  else {
-    if (diff > 0.0) diff = 2.0 * pi - diff;
-    else diff = -2.0 * pi - diff;
-    v = CCMP_FMA(-diff, tt, fr);
-    if (v > pi) v -= 2.0 * pi;
-    else if (v < -pi) v += 2.0 * pi;
-  }
-  return v;
-}
+// (ccmp_detmath.h: ccmp_joint_interpolate, the one text)
+__device__ __forceinline__ double geo_interpolate(double fr, double tg, double tt) { return ccmp_joint_interpolate(fr, tg, tt); }
 
 #ifndef CCMP_GEO_GROUP_WAVES_PER_SIMD
 #define CCMP_GEO_GROUP_WAVES_PER_SIMD CCMP_FD_WAVES_PER_SIMD

@@ -9,6 +9,7 @@
 //                               to and the carry as they were.
 //   shortcut_scatter_kernel     one lane per pair of an extend call: states and Newton rounds the call contributed are added to the pair's
 //                               cells (integer additions; one lane owns a cell in any one call), the flag once the pair is no longer open.
+//                               Without a cell array (explicit pairs: the smoothing's test step) slot k's cell is cell_base + k.
 //   shortcut_select_kernel      one 256-lane block per path: d, hops, pred and the adjacent weights live in LDS; for each j the lanes fold
 //                               the parents i = lane, lane + 256, .. < j, then a tree in LDS takes the lexicographic minimum — a total
 //                               order, so no block shape changes the answer.  Lane 0 sums cost_in and walks pred.
@@ -81,14 +82,15 @@ __global__ __launch_bounds__(kThreads) void shortcut_regather_kernel(const short
 }
 
 __global__ __launch_bounds__(kThreads) void shortcut_scatter_kernel(const shortcut_open *__restrict__ open, unsigned int E, const long long *__restrict__ cell,
-                                                                   const int32_t *__restrict__ n_states, const uint8_t *__restrict__ ok,
+                                                                   long long cell_base, const int32_t *__restrict__ n_states, const uint8_t *__restrict__ ok,
                                                                    const int32_t *__restrict__ newton, const uint8_t *__restrict__ blocked,
                                                                    int chunk_states, unsigned long long cells, uint8_t *__restrict__ pair_ok,
                                                                    int32_t *__restrict__ pair_states, int32_t *__restrict__ pair_newton)
 {
   const unsigned long long k = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
   if (k >= E) return;
-  const long long m = cell[open ? open[k].slot : (long long)k];
+  const long long slot = open ? open[k].slot : (long long)k;
+  const long long m = cell ? cell[slot] : cell_base + slot; // a tile of explicit pairs has no cell array: its entries are consecutive
   if (m < 0 || (unsigned long long)m >= cells) return; // no candidate
   const int32_t stored = ccmp::dense_stored(n_states[k], chunk_states);
   const int32_t add = open ? (stored > 0 ? stored - 1 : 0) : stored; // a continuation's row 0 repeats the state it started from
@@ -194,11 +196,11 @@ hipError_t shortcut_regather(const ccmp::shortcut_open *open, size_t E, const do
   return hipGetLastError();
 }
 
-hipError_t shortcut_scatter(const ccmp::shortcut_open *open, size_t E, const long long *cell, const int32_t *n_states, const uint8_t *ok,
+hipError_t shortcut_scatter(const ccmp::shortcut_open *open, size_t E, const long long *cell, long long cell_base, const int32_t *n_states, const uint8_t *ok,
                             const int32_t *newton, const uint8_t *blocked, int chunk_states, size_t cells, uint8_t *pair_ok, int32_t *pair_states,
                             int32_t *pair_newton, hipStream_t st)
 {
-  hipLaunchKernelGGL(shortcut_scatter_kernel, dim3(blocks_of(E, kThreads)), dim3(kThreads), 0, st, open, (unsigned int)E, cell, n_states, ok, newton, blocked,
+  hipLaunchKernelGGL(shortcut_scatter_kernel, dim3(blocks_of(E, kThreads)), dim3(kThreads), 0, st, open, (unsigned int)E, cell, cell_base, n_states, ok, newton, blocked,
                      chunk_states, (unsigned long long)cells, pair_ok, pair_states, pair_newton);
   return hipGetLastError();
 }

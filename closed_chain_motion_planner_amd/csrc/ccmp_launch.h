@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; }
+namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -238,8 +238,9 @@ hipError_t shortcut_enumerate(const double *path_joints, const int32_t *path_len
 hipError_t shortcut_regather(const ccmp::shortcut_open *open, size_t E, const double *prev_states, int chunk_states, const double *prev_to,
                              const double *prev_carry, double *from, double *to, double *carry_in, hipStream_t st);
 /* after an extend call over E open pairs (open == nullptr: the tile's first call, pair k = slot k): the states and Newton rounds the call
- * contributed are added to the pair's matrix entries, and the flag of a pair that is no longer open is written */
-hipError_t shortcut_scatter(const ccmp::shortcut_open *open, size_t E, const long long *cell, const int32_t *n_states, const uint8_t *ok,
+ * contributed are added to the pair's matrix entries, and the flag of a pair that is no longer open is written; cell == nullptr (a tile of
+ * explicit pairs): slot k's entry is cell_base + k */
+hipError_t shortcut_scatter(const ccmp::shortcut_open *open, size_t E, const long long *cell, long long cell_base, const int32_t *n_states, const uint8_t *ok,
                             const int32_t *newton, const uint8_t *blocked, int chunk_states, size_t cells, uint8_t *pair_ok, int32_t *pair_states,
                             int32_t *pair_newton, hipStream_t st);
 /* one block per path: the forward sweep over the DAG of admitted edges, the walk of pred, the costs */
@@ -248,6 +249,30 @@ hipError_t shortcut_select(const double *path_joints, const int32_t *path_len, s
 /* out_joints[f][k] = path_joints[f][kept[f][k]] for k < out_len[f]; rows behind are not written */
 hipError_t shortcut_gather_kept(const double *path_joints, const int32_t *out_len, const int32_t *kept, size_t F, int max_len, double *out_joints,
                                 hipStream_t st);
+/* smooth solution paths (ccmp_path_smooth; csrc/ccmp_smooth.h).  The caller's rows k < path_len[f] into buf [F][cap][14]; bad[f] = 1 where one
+ * of them is not finite */
+hipError_t smooth_load(const double *path_joints, const int32_t *path_len, size_t F, int max_len, int cap, double *buf, uint8_t *bad, hipStream_t st);
+/* the E pairs of one stage of a pass over the nA active paths (cur = the current path buffer [F][cap][14]): stage 0 (w_i, w_{i+1}) per
+ * segment, 1 (m_{i-1}, w_i), (w_i, m_i) per interior vertex, 2 (t1, t2) — into pairs [E][2][14], pair_path [E] = the pair's path — and 3 the two
+ * tests (m_{i-1}, c_i), (c_i, m_i) into from / to [E][14] */
+hipError_t smooth_gather(int stage, const ccmp::smooth_path *paths, size_t nA, size_t E, const double *cur, int cap, const double *m, const double *t12,
+                         const double *cand, double *pairs, double *from, double *to, int32_t *pair_path, hipStream_t st);
+/* per pair e with the dense rows [path_first[e], path_first[e + 1]) and their arcs: x[e] = the blend at half the arc (row 0 for a degenerate
+ * list), choice[e] = the fallback row, -1 for a degenerate list */
+hipError_t smooth_bracket(const double *rows, const double *arc, const int32_t *path_first, size_t E, size_t total_rows, double *x, int32_t *choice,
+                          hipStream_t st);
+/* mid[e] = degenerate: row 0; ok[e]: y[e]; else the fallback row; the kind is counted in stats [F][5] of the pair's path */
+hipError_t smooth_pick(const double *rows, const int32_t *path_first, const int32_t *choice, const double *y, const uint8_t *ok, const int32_t *pair_path,
+                       size_t E, size_t total_rows, size_t F, double *mid, int32_t *stats, hipStream_t st);
+/* the subdivided paths of the active paths into `next`: items = their vertices; moved [F] and stats [F][5] are added to */
+hipError_t smooth_accept(const ccmp::smooth_path *paths, size_t nA, size_t items, const double *cur, int cap, const double *m, const double *cand,
+                         const uint8_t *test_ok, const double *clear_m, const double *clear_c, double margin, double min_change, double *next,
+                         int32_t *moved, int32_t *stats, hipStream_t st);
+/* length[f] = the left-to-right sum of the adjacent joint distances of path f's first len[f] rows in buf0 (where[f] != 0: buf1) */
+hipError_t smooth_length(const double *buf0, const double *buf1, const uint8_t *where, const int32_t *len, size_t F, int cap, double *length, hipStream_t st);
+/* out_joints[f][k] = the path's row k for k < len[f]; rows behind are not written */
+hipError_t smooth_store(const double *buf0, const double *buf1, const uint8_t *where, const int32_t *len, size_t F, int cap, double *out_joints,
+                        hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

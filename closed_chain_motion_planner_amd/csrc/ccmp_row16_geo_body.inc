@@ -169,16 +169,7 @@
       }
       if (stage == kNext) { // WrapperStateSpace::interpolate(previous, to, delta_ / dist, scratch) (KinematicChain.h:145-171; orc_interpolate)
         const double tt = delta / dist;
-        double diff = tgt - prv, v;
-        if (ccmp_abs(diff) <= pi) v = CCMP_FMA(diff, tt, prv);
-        else {
-          if (diff > 0.0) diff = 2.0 * pi - diff;
-          else diff = -2.0 * pi - diff;
-          v = CCMP_FMA(-diff, tt, prv);
-          if (v > pi) v -= 2.0 * pi;
-          else if (v < -pi) v += 2.0 * pi;
-        }
-        x = v;
+        x = ccmp_joint_interpolate(prv, tgt, tt);
         iter = 0; updates = 0; norm1 = 0.0; norm2 = 0.0;
         stage = kProject;
       }

@@ -15,6 +15,7 @@
 #include "../../include/ccmp.h"
 #include "ccmp_ctx.h"
 #include "ccmp_launch.h"
+#include "ccmp_pair_tests.h"
 #include "ccmp_resident.h"
 #include "ccmp_scene.h"
 #include "ccmp_shortcut.h"
@@ -94,13 +95,93 @@ void make_bufs(CallArena &mem, size_t T, int cs, bool scene, CallBufs *b) // (th
   b->open = mem.array<shortcut_open>(T);
 }
 
+}  // namespace
+
+// The tile and continuation loop (ccmp_pair_tests.h), shared with the smoothing's test step: only where a tile's endpoints come from differs.
+int ccmp_host::pair_tests(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const PairLoopOpts &o, long long total,
+                          const PairSource &src, size_t cells, uint8_t *w_ok, int32_t *w_states, int32_t *w_newton, CallArena &mem, hipStream_t st,
+                          const char *what, PairLoopCounts *counts)
+{
+  if (total <= 0) return CCMP_OK;
+  const int cs = o.chunk_states;
+  const bool enumerated = src.from == nullptr;
+  const size_t T_max = (size_t)((long long)o.tile_edges < total ? (long long)o.tile_edges : total);
+  long long *d_cell = enumerated ? mem.array<long long>(T_max) : nullptr;
+  CallBufs bufs[2];
+  make_bufs(mem, T_max, cs, scene != nullptr, &bufs[0]);
+  make_bufs(mem, T_max, cs, scene != nullptr, &bufs[1]);
+  if (!mem.ok()) return CCMP_EHIP;
+  std::vector<int32_t> n_h(T_max);
+  std::vector<uint8_t> ok_h(T_max), bl_h(T_max, 0);
+  std::vector<shortcut_open> open_h, next_h;
+  std::vector<int32_t> slot_of(T_max); // per pair of the current call: its slot in the tile
+  for (long long first = 0; first < total; first += (long long)T_max) {
+    const size_t T = (size_t)(total - first < (long long)T_max ? total - first : (long long)T_max);
+    size_t E = T;
+    int cur = 0, calls = 0;
+    bool cont = false; // the tile's first call reads its endpoints from the source
+    for (size_t k = 0; k < T; k++) slot_of[k] = (int32_t)k;
+    if (enumerated) {
+      HIP_TRY(ccmp_launch::shortcut_enumerate(src.path_joints, src.path_len, src.d_prefix, src.F, src.max_len, src.max_span, first, T, d_cell, bufs[0].from,
+                                              bufs[0].to, st));
+    } else {
+      HIP_TRY(hipMemcpyAsync(bufs[0].from, src.from + (size_t)first * 14, T * 14 * sizeof(double), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(bufs[0].to, src.to + (size_t)first * 14, T * 14 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    while (E > 0) {
+      if (calls == o.max_calls) { // a cut traversal must never look complete: nothing reaches the outputs
+        (void)hipStreamSynchronize(st);
+        return CCMP_EOVERFLOW;
+      }
+      CallBufs &b = bufs[cur];
+      int rc;
+      if (scene)
+        rc = ccmp_geodesic_scene_batch(ctx, p, scene, margin, b.from, b.to, E, cs, b.states, b.n, b.ok, b.its, b.blocked, nullptr, cont ? b.carry_in : nullptr,
+                                       b.carry_out, o.round_budget, cont ? 0 : 1, st);
+      else
+        rc = ccmp_geodesic_batch_ex(ctx, p, b.from, b.to, E, cs, b.states, b.n, b.ok, b.its, cont ? b.carry_in : nullptr, b.carry_out, o.round_budget,
+                                    cont ? 0 : 1, st);
+      hipError_t e = hipSuccess;
+      if (rc == CCMP_OK)
+        e = ccmp_launch::shortcut_scatter(cont ? b.open : nullptr, E, d_cell, first, b.n, b.ok, b.its, b.blocked, cs, cells, w_ok, w_states, w_newton, st);
+      if (e == hipSuccess && rc == CCMP_OK) e = hipMemcpyAsync(n_h.data(), b.n, E * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && rc == CCMP_OK) e = hipMemcpyAsync(ok_h.data(), b.ok, E, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && rc == CCMP_OK && scene) e = hipMemcpyAsync(bl_h.data(), b.blocked, E, hipMemcpyDeviceToHost, st);
+      const hipError_t es = hipStreamSynchronize(st);
+      if (rc != CCMP_OK) return rc;
+      HIP_TRY(e);
+      HIP_TRY(es);
+      calls++;
+      if (counts) { counts->calls++; counts->read_bytes += (long long)E * (scene ? 6 : 5); }
+      next_h.clear();
+      for (size_t k = 0; k < E; k++) {
+        if (bl_h[k] || !ccmp::dense_open(n_h[k], ok_h[k], cs)) continue;
+        const int32_t stored = ccmp::dense_stored(n_h[k], cs);
+        if (stored < 1) { snprintf(g_hip_err, sizeof g_hip_err, "%s: an extend call stored no state", what); return CCMP_EHIP; }
+        next_h.push_back(shortcut_open{(int32_t)k, stored - 1, slot_of[k], 0});
+      }
+      E = next_h.size();
+      if (E == 0) break;
+      open_h.swap(next_h); // kept until the next synchronisation: it backs the upload below
+      for (size_t k = 0; k < E; k++) slot_of[k] = open_h[k].slot;
+      CallBufs &nb = bufs[cur ^ 1];
+      HIP_TRY(hipMemcpyAsync(nb.open, open_h.data(), E * sizeof(shortcut_open), hipMemcpyHostToDevice, st));
+      HIP_TRY(ccmp_launch::shortcut_regather(nb.open, E, b.states, cs, b.to, b.carry_out, nb.from, nb.to, nb.carry_in, st));
+      cur ^= 1;
+      cont = true;
+    }
+  }
+  return CCMP_OK;
+}
+
+namespace {
+
 // The body of the device form behind its checks; `len` = path_len as read once from the device.  The outputs are written only after every
 // tile has closed.
 int shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
              const std::vector<int32_t> &len, size_t F, int max_len, const ccmp_shortcut_opts &o, double *out_joints, int32_t *out_len, int32_t *kept,
              double *cost_in, double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton, hipStream_t st)
 {
-  const int cs = o.chunk_states;
   const size_t cells = F * (size_t)max_len * (size_t)max_len;
   std::vector<long long> prefix(F + 1, 0);
   for (size_t f = 0; f < F; f++) prefix[f + 1] = prefix[f] + ccmp::shortcut_pair_count(len[f], o.max_span);
@@ -116,66 +197,14 @@ int shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, doub
   if (w_newton) HIP_TRY(hipMemsetAsync(w_newton, 0, cells * sizeof(int32_t), st));
 
   if (total > 0) {
-    const size_t T_max = (size_t)((long long)o.tile_edges < total ? (long long)o.tile_edges : total);
-    long long *d_prefix = mem.array<long long>(F + 1), *d_cell = mem.array<long long>(T_max);
-    CallBufs bufs[2];
-    make_bufs(mem, T_max, cs, scene != nullptr, &bufs[0]);
-    make_bufs(mem, T_max, cs, scene != nullptr, &bufs[1]);
+    long long *d_prefix = mem.array<long long>(F + 1);
     if (!mem.ok()) return CCMP_EHIP;
     HIP_TRY(hipMemcpyAsync(d_prefix, prefix.data(), (F + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    std::vector<int32_t> n_h(T_max);
-    std::vector<uint8_t> ok_h(T_max), bl_h(T_max, 0);
-    std::vector<shortcut_open> open_h, next_h;
-    std::vector<int32_t> slot_of(T_max); // per pair of the current call: its slot in the tile
-    for (long long first = 0; first < total; first += (long long)T_max) {
-      const size_t T = (size_t)(total - first < (long long)T_max ? total - first : (long long)T_max);
-      size_t E = T;
-      int cur = 0, calls = 0;
-      bool cont = false; // the tile's first call reads its endpoints from the enumeration
-      for (size_t k = 0; k < T; k++) slot_of[k] = (int32_t)k;
-      HIP_TRY(ccmp_launch::shortcut_enumerate(path_joints, path_len, d_prefix, F, max_len, o.max_span, first, T, d_cell, bufs[0].from, bufs[0].to, st));
-      while (E > 0) {
-        if (calls == o.max_calls) { // a cut traversal must never look complete: nothing reaches the outputs
-          (void)hipStreamSynchronize(st);
-          return CCMP_EOVERFLOW;
-        }
-        CallBufs &b = bufs[cur];
-        int rc;
-        if (scene)
-          rc = ccmp_geodesic_scene_batch(ctx, p, scene, margin, b.from, b.to, E, cs, b.states, b.n, b.ok, b.its, b.blocked, nullptr, cont ? b.carry_in : nullptr,
-                                         b.carry_out, o.round_budget, cont ? 0 : 1, st);
-        else
-          rc = ccmp_geodesic_batch_ex(ctx, p, b.from, b.to, E, cs, b.states, b.n, b.ok, b.its, cont ? b.carry_in : nullptr, b.carry_out, o.round_budget,
-                                      cont ? 0 : 1, st);
-        hipError_t e = hipSuccess;
-        if (rc == CCMP_OK)
-          e = ccmp_launch::shortcut_scatter(cont ? b.open : nullptr, E, d_cell, b.n, b.ok, b.its, b.blocked, cs, cells, w_ok, w_states, w_newton, st);
-        if (e == hipSuccess && rc == CCMP_OK) e = hipMemcpyAsync(n_h.data(), b.n, E * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && rc == CCMP_OK) e = hipMemcpyAsync(ok_h.data(), b.ok, E, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && rc == CCMP_OK && scene) e = hipMemcpyAsync(bl_h.data(), b.blocked, E, hipMemcpyDeviceToHost, st);
-        const hipError_t es = hipStreamSynchronize(st);
-        if (rc != CCMP_OK) return rc;
-        HIP_TRY(e);
-        HIP_TRY(es);
-        calls++;
-        next_h.clear();
-        for (size_t k = 0; k < E; k++) {
-          if (bl_h[k] || !ccmp::dense_open(n_h[k], ok_h[k], cs)) continue;
-          const int32_t stored = ccmp::dense_stored(n_h[k], cs);
-          if (stored < 1) { snprintf(g_hip_err, sizeof g_hip_err, "ccmp_path_shortcut: an extend call stored no state"); return CCMP_EHIP; }
-          next_h.push_back(shortcut_open{(int32_t)k, stored - 1, slot_of[k], 0});
-        }
-        E = next_h.size();
-        if (E == 0) break;
-        open_h.swap(next_h); // kept until the next synchronisation: it backs the upload below
-        for (size_t k = 0; k < E; k++) slot_of[k] = open_h[k].slot;
-        CallBufs &nb = bufs[cur ^ 1];
-        HIP_TRY(hipMemcpyAsync(nb.open, open_h.data(), E * sizeof(shortcut_open), hipMemcpyHostToDevice, st));
-        HIP_TRY(ccmp_launch::shortcut_regather(nb.open, E, b.states, cs, b.to, b.carry_out, nb.from, nb.to, nb.carry_in, st));
-        cur ^= 1;
-        cont = true;
-      }
-    }
+    PairSource src;
+    src.path_joints = path_joints; src.path_len = path_len; src.d_prefix = d_prefix; src.F = F; src.max_len = max_len; src.max_span = o.max_span;
+    const int rc = pair_tests(ctx, p, scene, margin, PairLoopOpts{o.chunk_states, o.round_budget, o.max_calls, o.tile_edges}, total, src, cells, w_ok, w_states,
+                              w_newton, mem, st, "ccmp_path_shortcut");
+    if (rc != CCMP_OK) return rc;
   }
 
   // every pair is closed: the selection, then the caller's outputs

@@ -634,6 +634,38 @@ class Roadmap:
             return None
         return sol[0], sol[1], self._dense(constraint, sol[2], dkw), sol[3]
 
+    _SMOOTH_KW = ("max_steps", "min_change", "out_max_len", "stats")
+
+    def smooth_solution(self, constraint, starts, goals, max_len=64, **kw):
+        """solution -> shortcut -> smooth, each step on the device outputs of the one before: `shortcut_solution` (its keyword arguments
+        among kw), then `constraint.smooth_paths` on the kept rows (max_steps, min_change, out_max_len, stats among kw; a scene and its
+        margin, chunk_states, round_budget, max_calls and tile_edges go to both).  Returns (length of the smoothed path, indices of the
+        vertices the shortcut kept, joints (len,14) device tensor, smooth, shortcut) with smooth the dict of `smooth_paths`, or None when
+        no pair is connected.  The smoothed vertices other than the first and the last are not roadmap vertices."""
+        torch = _torch()
+        skw = {k: v for k, v in kw.items() if k in self._SHORTCUT_KW}
+        mkw = {k: v for k, v in kw.items() if k in self._SMOOTH_KW or k in ("scene", "margin", "chunk_states", "round_budget", "max_calls", "tile_edges")}
+        sol = self.shortcut_solution(constraint, starts, goals, max_len=max_len, **skw)
+        if sol is None:
+            return None
+        _, idx, joints, sc = sol
+        n = joints.shape[0]
+        plen = torch.full((1,), n, dtype=torch.int32, device=joints.device)
+        sm = constraint.smooth_paths(joints.reshape(1, n, 14).contiguous(), plen, **mkw)
+        m = int(sm["out_len"][0])
+        return float(sm["length_out"][0]), idx, sm["joints"][0, :m].contiguous(), sm, sc
+
+    def dense_smooth_solution(self, constraint, starts, goals, max_len=64, **kw):
+        """solution -> shortcut -> smooth -> densify: `smooth_solution`, then `constraint.densify_paths` on the smoothed rows (the
+        remaining kw, `distinct` for one; a scene and its margin go to all three).  Returns (length, indices, dense, smooth, shortcut), or
+        None.  The dense rows are what the host's validity test takes next."""
+        own = ("max_span", "tile_edges", "pairs") + self._SMOOTH_KW
+        dkw = {k: v for k, v in kw.items() if k not in own}
+        sol = self.smooth_solution(constraint, starts, goals, max_len=max_len, **{k: v for k, v in kw.items() if k != "distinct"})
+        if sol is None:
+            return None
+        return sol[0], sol[1], self._dense(constraint, sol[2], dkw), sol[3], sol[4]
+
     def close(self):
         if self._h:
             _lib.lib().ccmp_roadmap_destroy(self._h)

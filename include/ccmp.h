@@ -1104,6 +1104,78 @@ int ccmp_shortcut_select_ref(const double *path_joints, const int32_t *path_len,
 int ccmp_shortcut_pairs_ref(const double *path_joints, const int32_t *path_len, size_t F, int max_len, int max_span, int32_t *triples, size_t capacity,
                             size_t *count);
 
+/* ---- smooth solution paths: B-spline passes on the manifold ----------------------------------------------------------------------- */
+/* A roadmap path, shortcut or not, is a polygon with a corner at every kept vertex, and the corners are what the arms execute.  This is
+ * the structure of OMPL's PathSimplifier::smoothBSpline — subdivide, then move every original vertex towards the middle of its two new
+ * neighbours — with this project's midpoint, not OMPL's arithmetic.  A pass is data-parallel as written (only the original vertices move,
+ * each reads only its two new neighbours, no pass moves a new neighbour), so every segment and every interior vertex of every path goes
+ * into one batch per stage.  The rule (csrc/ccmp_smooth.h states it once, for the kernels, the host forms and the _ref forms); path f has
+ * L = path_len[f] waypoints w_0 .. w_{L-1}, rows of path_joints [F][max_len][14]:
+ *     closed list    of a pair (a, b): the distinct dense rows of the two-waypoint path [a, b] (the dense section): G = the list of ONE
+ *                    uninterrupted discreteGeodesic(a, b, interpolate = true), then b; n >= 2 rows, arcs s_0 = +0.0,
+ *                    s_k = fl(s_{k-1} + ccmp_joint_distance(row_{k-1}, row_k)).
+ *     midpoint       mid(a, b): T = s_{n-1}, h = 0.5 T.  Not T > 0: mid = a (degenerate).  Otherwise k = the smallest k >= 1 with s_k >= h,
+ *                    t = (h - s_{k-1}) / (s_k - s_{k-1}) (IEEE division, the denominator positive by construction), x =
+ *                    WrapperStateSpace::interpolate(row_{k-1}, row_k, t) (the extend step's), (y, ok) = project(x); ok: mid = y
+ *                    (projected); not ok: mid = row_{k-1} when (h - s_{k-1}) <= (s_k - h), else row_k (fallback).  The midpoint is the
+ *                    blend at half the arc put back on the manifold and not the list state nearest to it: lists have one to seven states at
+ *                    the planner's delta, so list-state midpoints coincide with waypoints after one pass.
+ *     one pass       (L >= 3) m_i = mid(w_i, w_{i+1}) per segment; per interior i: t1 = mid(m_{i-1}, w_i), t2 = mid(w_i, m_i), c_i =
+ *                    mid(t1, t2).  c_i is accepted iff checkMotion(m_{i-1}, c_i) and checkMotion(c_i, m_i) pass (each isSatisfied(target),
+ *                    then one uninterrupted discreteGeodesic, forwards, as the shortcut section's test; with a proxy scene
+ *                    ccmp_geodesic_scene_batch with the margin, and also clearance(m_{i-1}) >= margin and clearance(c_i) >= margin, a NaN
+ *                    refusing) — otherwise it is refused — and then ccmp_joint_distance(w_i, c_i) > min_change — otherwise it is below
+ *                    min_change.  The new path is w_0, m_0, w_1', m_1, .., m_{L-2}, w_{L-1}: 2L - 1 vertices, w_i' = c_i if accepted, else
+ *                    w_i; u = the accepted vertices.
+ *     loop           per path; stop [F] is the reason it ended, decided in this order: 4 a waypoint among the first L is not finite in all
+ *                    14 coordinates (copied unchanged, nothing traversed); 0 L < 3 (copied); then, before every pass, 2 max_steps passes
+ *                    have run, 3 the next pass would not fit (2L - 1 > out_max_len); after a pass 1 it moved nothing (u == 0; that pass's
+ *                    subdivision is kept, as OMPL keeps it).  A path that has stopped takes no part in later passes: its result equals that
+ *                    of the path run alone.
+ *     result         out_joints [F][out_max_len][14] (rows behind out_len are untouched), out_len, passes, moved (the sum of u), stop [F]
+ *                    int32; length_in, length_out [F] = the left-to-right fl sum of adjacent joint distances (a NaN row makes it NaN);
+ *                    stats (nullable) [F][5] int32: midpoints projected, fallen back, degenerate, candidates refused (checkMotion or
+ *                    clearance), candidates below min_change.
+ * The result does not depend on launch shape, list length (chunk_states), round_budget or tile_edges.
+ *   ccmp_path_smooth     device pointers.  SYNCHRONOUS on its stream and not capturable: it reads what the continuation loops of the dense
+ *                    and shortcut sections read, path_len and F flags once, and F counts per pass.  opts == NULL: the defaults.  The
+ *                    whole result is built in a workspace of the call and copied out only at the end: on any error (CCMP_EOVERFLOW when
+ *                    max_calls extend calls are spent with a traversal still open among them) every output is untouched.
+ *   _host            host pointers, on the context's stream.
+ *   ccmp_smooth_mid_ref  the bracket and the blend of ONE pair, pure host code: rows [n][14] and arcs [n] of its closed list -> *k, *t, blend
+ *                    [14] (before projection) and *fallback = the row a failed projection would take.  A degenerate list answers k = 0,
+ *                    t = 0, blend = row 0, fallback = 0.  No projection, no device, never CCMP_ENODEV.  CCMP_EINVAL: n < 2, a NULL pointer.
+ *   ccmp_smooth_len_after(L, passes)   the vertices of a path of L waypoints after that many passes (L < 3: L), saturating at INT32_MAX;
+ *                    out_max_len = ccmp_smooth_len_after(max_len, max_steps) never stops a path on capacity.
+ *   ccmp_smooth_last_counts   what the calling thread's last ccmp_path_smooth / _host did, for measurements (each pointer nullable): the
+ *                    extend calls it made, the projector calls (one per midpoint step), and the bytes it read on the host (path_len and
+ *                    the flags once, the continuation loops' 5 or 6 bytes per open traversal and extend call, F counts per pass).
+ * Conventions as the dense and shortcut sections': every check runs before the first launch; a NULL context answers CCMP_ENODEV without a
+ * device and CCMP_EINVAL with one; F == 0 returns CCMP_OK and touches nothing.  CCMP_EINVAL: max_steps < 0, a negative or NaN min_change
+ * (+inf is allowed), max_len < 1, out_max_len < max_len, a path_len entry outside [0, max_len], chunk_states < 2, round_budget < 0,
+ * max_calls < 1, tile_edges < 1, a scene of another device, a NaN margin with a scene, an output overlapping an input, a NULL path_joints,
+ * path_len, out_joints, out_len, passes, moved, stop, length_in or length_out.  Order of use: shortcut -> smooth -> densify -> the host's
+ * validity test over the dense rows. */
+typedef struct ccmp_smooth_opts {
+  int max_steps;     /* passes at most, >= 0 */
+  double min_change; /* a vertex moves only by more than this */
+  int chunk_states;  /* list entries per extend call, >= 2 */
+  int round_budget;  /* Newton rounds per traversal and extend call, 0 = no bound */
+  int max_calls;     /* extend calls at most, per midpoint step and per tile of the test step */
+  int tile_edges;    /* checkMotion tests per tile, >= 1 */
+} ccmp_smooth_opts;
+/* 5, 0.005, 16, 128, 4096, 65536 */
+void ccmp_smooth_opts_default(ccmp_smooth_opts *opts);
+int ccmp_path_smooth(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
+                     size_t F, int max_len, const ccmp_smooth_opts *opts, int out_max_len, double *out_joints, int32_t *out_len, int32_t *passes,
+                     int32_t *moved, int32_t *stop, double *length_in, double *length_out, int32_t *stats, void *hip_stream);
+int ccmp_path_smooth_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints,
+                          const int32_t *path_len, size_t F, int max_len, const ccmp_smooth_opts *opts, int out_max_len, double *out_joints,
+                          int32_t *out_len, int32_t *passes, int32_t *moved, int32_t *stop, double *length_in, double *length_out, int32_t *stats);
+int ccmp_smooth_mid_ref(const double *rows, const double *arcs, int n, int *k, double *t, double *blend, int *fallback);
+int ccmp_smooth_len_after(int L, int passes);
+void ccmp_smooth_last_counts(long long *extend_calls, long long *project_calls, long long *bytes_read);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault
  * injection — are not part of this library: include/ccmp_debug.h, lib/libccmp_debug.so) */

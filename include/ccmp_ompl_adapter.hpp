@@ -637,6 +637,56 @@ inline int shortcutPathLocked(const Projector &proj, std::vector<std::array<doub
   return CCMP_OK;
 }
 
+// B-spline smoothing passes on the manifold (include/ccmp.h: ccmp_path_smooth_host; the structure of PathSimplifier::smoothBSpline with
+// the library's midpoint): `states` = the waypoints on entry and the smoothed path on return — at most max_steps passes, each L -> 2L - 1
+// vertices, a vertex moving only by more than min_change and only when both checkMotions to its new neighbours pass.  passes / moved /
+// stop / length_in / length_out (nullable) as the library reports them.  delta / lambda > 0 replace the problem's.  Order of use:
+// shortcut -> smooth -> interpolate -> the host's isValid over the dense rows.  Returns the library's code and leaves
+// `states` untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int smoothPathLocked(const Projector &proj, std::vector<std::array<double, 14>> &states, int max_steps, double min_change, int *passes = nullptr,
+                            int *moved = nullptr, int *stop = nullptr, double *length_in = nullptr, double *length_out = nullptr, double delta = 0.0,
+                            double lambda = 0.0)
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double), "rows are contiguous");
+  const ccmp_problem P = detail::problemWith(proj, delta, lambda);
+  ccmp_smooth_opts o;
+  ccmp_smooth_opts_default(&o);
+  o.max_steps = max_steps;
+  o.min_change = min_change;
+  if (states.empty()) {
+    if (passes) *passes = 0;
+    if (moved) *moved = 0;
+    if (stop) *stop = 0;
+    if (length_in) *length_in = 0.0;
+    if (length_out) *length_out = 0.0;
+    return (max_steps < 0 || !(min_change >= 0.0)) ? CCMP_EINVAL : CCMP_OK;
+  }
+  if (states.size() > (size_t)0x3fffffff) return CCMP_EINVAL;
+  const int32_t len = (int32_t)states.size();
+  const int cap = ccmp_smooth_len_after(len, max_steps < 0 ? 0 : max_steps);
+  if (cap == 0x7fffffff) return CCMP_EINVAL; // the result would not fit any buffer
+  int32_t out_len = 0, n_pass = 0, n_moved = 0, why = 0;
+  double li = 0.0, lo = 0.0;
+  std::vector<std::array<double, 14>> rows;
+  try {
+    rows.resize((size_t)cap);
+  } catch (...) {
+    return CCMP_ENOMEM;
+  }
+  const int rc = ccmp_path_smooth_host(proj.ctx(), &P, nullptr, 0.0, states[0].data(), &len, 1, len, &o, cap, rows[0].data(), &out_len, &n_pass, &n_moved, &why,
+                                       &li, &lo, nullptr);
+  if (rc != CCMP_OK) return rc;
+  if (out_len < 0 || out_len > cap) return CCMP_EHIP;
+  rows.resize((size_t)out_len);
+  states.swap(rows);
+  if (passes) *passes = n_pass;
+  if (moved) *moved = n_moved;
+  if (stop) *stop = why;
+  if (length_in) *length_in = li;
+  if (length_out) *length_out = lo;
+  return CCMP_OK;
+}
+
 // ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
 // The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
 // rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
@@ -956,6 +1006,23 @@ public:
     } catch (...) {
       err_.record(CCMP_ENOMEM, "Roadmap::constructShortcutSolution");
       if (indices) indices->clear();
+    }
+    return true;
+  }
+
+  // constructShortcutSolution followed by smoothing passes (ccmp::smoothPathLocked above): `states` = the smoothed path, cost = its joint
+  // length, indices = the vertices the shortcut kept (the smoothed vertices between the first and the last are not roadmap vertices).  On
+  // a library error in the smoothing step the answer is the UNCHANGED shortcut path (true, with lastError() set).  false with no states
+  // when no pair is connected or the solution step itself failed.  Interpolate the result and validate the dense rows on the host.
+  bool constructSmoothSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states,
+                               int max_steps = 5, double min_change = 0.005, int max_span = 0, double *cost = nullptr,
+                               std::vector<int32_t> *indices = nullptr, double delta = 0.0, double lambda = 0.0) const noexcept
+  {
+    if (!constructShortcutSolution(starts, goals, states, max_span, cost, indices, delta, lambda)) return false;
+    double lo = 0.0;
+    if (call([&] { return smoothPathLocked(proj_, states, max_steps, min_change, nullptr, nullptr, nullptr, nullptr, &lo, delta, lambda); },
+             "ccmp_path_smooth_host")) {
+      if (cost) *cost = lo;
     }
     return true;
   }
@@ -1777,6 +1844,20 @@ public:
       const ccmp::Projector &proj = chain_->impl();
       std::lock_guard<std::mutex> hold(proj.mutex());
       ccmp::check(ccmp::shortcutPathLocked(proj, states, max_span, kept, nullptr, nullptr, delta_, lambda_), "ccmp_path_shortcut_host");
+    });
+  }
+
+  // B-spline smoothing passes on the manifold (ccmp::smoothPathLocked: PathSimplifier::smoothBSpline's structure with the library's
+  // midpoint), under this space's delta and lambda: `states` = the waypoints on entry, the smoothed path on return (up to
+  // 2^max_steps (L - 1) + 1 states).  On a library error the answer is the unchanged path: false, `states` as it was, the first error in
+  // KinematicChainConstraint::lastError().  Use it behind shortcutPath and follow it with interpolatePath and the host's isValid.
+  bool smoothPath(std::vector<std::array<double, 14>> &states, int max_steps = 5, double min_change = 0.005, int *passes = nullptr,
+                  int *moved = nullptr) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      ccmp::check(ccmp::smoothPathLocked(proj, states, max_steps, min_change, passes, moved, nullptr, nullptr, nullptr, delta_, lambda_), "ccmp_path_smooth_host");
     });
   }
 

@@ -1,0 +1,143 @@
+"""Smooth solution paths without a device: ccmp_smooth_mid_ref and ccmp_smooth_len_after (csrc/ccmp_smooth.h compiled for the host)
+against the plain-Python restatement of tests/smooth_cases.py, the argument checks that are decided before a device is needed, and the
+restatement alone on the recorded waypoints (what the feature was proposed on).  On grid rows (multiples of 2^-3) every difference,
+square and sum of a joint distance is exact, so only the square root, the arc sums and the division round."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from shortcut_cases import collinear, grid_rows, recorded_waypoints
+from smooth_cases import Restatement, arcs_of, bits, bracket_py, same_f64
+
+EINVAL, ENODEV = -1, -5
+
+
+@pytest.fixture(scope="module")
+def api(ccmp_built):
+    import closed_chain_motion_planner_amd as pkg
+
+    return pkg
+
+
+def _check(api, O, rows, what):
+    """ccmp_smooth_mid_ref against the restatement's linear scan and the oracle's interpolate; returns (k, t, fallback)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    arcs = arcs_of(rows)
+    k, t, blend, fb = api.smooth_mid_ref(rows, arcs)
+    want = bracket_py(rows, arcs)
+    if want is None:
+        assert (k, t, fb) == (0, 0.0, 0) and same_f64(blend, rows[0]), what
+        return None
+    wk, wt, wfb = want
+    assert (k, fb) == (wk, wfb) and bits(np.array([t]))[0] == bits(np.array([wt]))[0], (what, k, t, fb, want)
+    assert arcs[k] > arcs[k - 1]  # a +0.0 step is never the bracket
+    assert same_f64(blend, O.interpolate(rows[k - 1], rows[k], t)), what
+    return k, t, fb
+
+
+def test_two_rows_and_the_tie(api, oracle_det):
+    """n = 2: the bracket is the only step, t = 0.5 exactly, and the fallback tie (h - s_0 == s_1 - h) goes to row k - 1"""
+    rng = np.random.default_rng(2)
+    for f in range(8):
+        rows = grid_rows(rng, 1, 2)[0]
+        assert _check(api, oracle_det, rows, f) == (1, 0.5, 0)
+
+
+def test_half_the_arc_falls_on_a_state(api, oracle_det):
+    """collinear rows at equal steps, an odd number of them: h is exactly s_k and t = 1"""
+    for n in (3, 5, 9):
+        rows = collinear(n)[0]
+        k, t, fb = _check(api, oracle_det, rows, n)
+        assert (k, t) == ((n - 1) // 2, 1.0) and fb == k  # above = +0.0 < below
+
+
+def test_duplicated_rows(api, oracle_det):
+    rng = np.random.default_rng(3)
+    a, b = grid_rows(rng, 1, 2)[0]
+    k, t, fb = _check(api, oracle_det, [a, a, b, b], "a a b b")
+    assert (k, t, fb) == (2, 0.5, 1)
+    k, t, fb = _check(api, oracle_det, [a, a, a, b], "a a a b")
+    assert (k, t, fb) == (3, 0.5, 2)
+    rows = collinear(4)[0]
+    rows[2] = rows[1]  # 0, 1, 1, 3 eighths: h = 1.5 eighths lies in the step behind the duplicate
+    k, t, fb = _check(api, oracle_det, rows, "dup inside")
+    assert (k, t, fb) == (3, 0.25, 2)
+
+
+def test_degenerate(api, oracle_det):
+    rng = np.random.default_rng(4)
+    a = grid_rows(rng, 1, 1)[0, 0]
+    assert _check(api, oracle_det, [a, a], "a a") is None
+    assert _check(api, oracle_det, [a, a, a, a], "a a a a") is None
+    bad = np.array([a, a])
+    bad[1, 3] = np.nan  # a NaN arc is not > 0
+    k, t, blend, fb = api.smooth_mid_ref(bad, np.array([0.0, np.nan]))
+    assert (k, t, fb) == (0, 0.0, 0) and same_f64(blend, a)
+
+
+@pytest.mark.parametrize("n", [2, 3, 4, 7, 8, 9, 33])
+def test_random_grid_lists(api, oracle_det, n):
+    rng = np.random.default_rng(100 + n)
+    rows = grid_rows(rng, 16, n)
+    rows[:, :, 2] = np.where(rng.random((16, n)) < 0.3, 4.0, rows[:, :, 2])  # some differences beyond pi: the blend wraps
+    for f in range(16):
+        r = rows[f].copy()
+        if f % 4 == 1:
+            r[n // 2] = r[n // 2 - 1]  # a duplicate somewhere
+        _check(api, oracle_det, r, (n, f))
+
+
+def test_len_after(api):
+    for L in range(0, 12):
+        n = L
+        for s in range(0, 6):
+            assert api.smooth_len_after(L, s) == n, (L, s)
+            n = n if L < 3 else 2 * n - 1
+    assert api.smooth_len_after(5, 3) == 33 and api.smooth_len_after(10, 1) == 19 and api.smooth_len_after(32, 3) == 249
+    assert api.smooth_len_after(3, 40) == 2 ** 31 - 1 and api.smooth_len_after(-4, 2) == 0
+
+
+def test_argument_errors(api):
+    from closed_chain_motion_planner_amd import _lib
+
+    L = _lib.lib()
+    dp = C.POINTER(C.c_double)
+    rows, arcs, blend = np.zeros((3, 14)), np.array([0.0, 1.0, 2.0]), np.zeros(14)
+    k, fb, t = C.c_int(0), C.c_int(0), C.c_double(0.0)
+    ptr = lambda a: a.ctypes.data_as(dp)
+    good = [ptr(rows), ptr(arcs), 3, C.byref(k), C.byref(t), ptr(blend), C.byref(fb)]
+    assert L.ccmp_smooth_mid_ref(*good) == 0 and (k.value, t.value, fb.value) == (1, 1.0, 1)
+    for i in (0, 1, 3, 4, 5, 6):  # a NULL required pointer
+        bad = list(good)
+        bad[i] = None
+        assert L.ccmp_smooth_mid_ref(*bad) == EINVAL, i
+    for n in (1, 0, -1):
+        assert L.ccmp_smooth_mid_ref(*(good[:2] + [n] + good[3:])) == EINVAL, n
+    o = _lib.CcmpSmoothOpts()
+    L.ccmp_smooth_opts_default(C.byref(o))
+    assert (o.max_steps, o.min_change, o.chunk_states, o.round_budget, o.max_calls, o.tile_edges) == (5, 0.005, 16, 128, 4096, 65536)
+    L.ccmp_smooth_opts_default(None)
+    # without a context nothing else is decided: a context needs a device
+    import torch
+
+    want = EINVAL if torch.cuda.is_available() else ENODEV
+    assert L.ccmp_path_smooth(None, None, None, 0.0, None, None, 1, 5, None, 33, *([None] * 9)) == want
+    assert L.ccmp_path_smooth_host(None, None, None, 0.0, None, None, 1, 5, None, 33, *([None] * 8)) == want
+    with pytest.raises(ValueError):
+        api.smooth_mid_ref(np.zeros((3, 13)), arcs)
+
+
+@pytest.mark.parametrize("obj,mode", [("Wine_Bottle", 0), ("Wine_Bottle", 1), ("dumbbell", 0)])
+def test_the_restatement_on_the_recorded_waypoints(oracle_det, obj, mode):
+    """One pass of the rule on the recorded waypoints, projected by the oracle: every interior vertex moves, every midpoint is a
+    projection, every new vertex is on the manifold and the path gets shorter."""
+    P, pj, pl = recorded_waypoints(oracle_det, obj, mode, True)
+    L = int(pl[0])
+    R = Restatement(oracle_det, P)
+    r = R.smooth(pj[0, :L], 1, 0.005, 2 * L - 1)
+    assert r["passes"] == 1 and r["moved"] == L - 2 and r["stop"] == 2 and len(r["rows"]) == 2 * L - 1
+    assert r["stats"] == [(L - 1) + 3 * (L - 2), 0, 0, 0, 0]
+    assert r["length_out"] < r["length_in"]
+    assert all(oracle_det.is_satisfied(P, q) for q in r["rows"])
+    assert same_f64(r["rows"][0], pj[0, 0]) and same_f64(r["rows"][-1], pj[0, L - 1])

@@ -43,6 +43,9 @@
                                                            both Jacobian modes, the extend calls made and the bytes that crossed to the host; writes profiles/dense_path.md
     python tools/measure.py shortcut [reps]                 shortcut solution paths (vertex removal): ccmp_path_shortcut against check_target extend calls over all pairs, their
                                                            continuation and the selection in numpy, 1 and 64 paths of 32 waypoints; writes profiles/shortcut.md
+    python tools/measure.py smooth [reps] [file.npz]        smooth solution paths (B-spline passes on the manifold): ccmp_path_smooth, three passes on 1 and 64 paths of 32
+                                                           waypoints, both Jacobian modes, the extend calls made and the bytes read on the host; writes profiles/smooth.md
+    python tools/measure.py smooth_restate <file.npz> [n]   the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -1449,6 +1452,93 @@ def shortcut(argv):
                 "No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
 
 
+def _smooth_paths(c, F, Lw, seed):
+    """F chains of Lw near-sampled milestones (the shortcut measurement's chains): (F,Lw,14) and (F,) int32 on the device"""
+    cols = [c.sample_project_batch(seed, 0, F, want_iters=False)[0]]
+    for j in range(1, Lw):
+        cols.append(c.sample_near_project_batch(seed + j, 0, cols[-1], 0.6, F, want_iters=False)[0])
+    return torch.stack(cols, dim=1).contiguous(), torch.full((F,), Lw, dtype=torch.int32, device="cuda")
+
+
+def smooth(argv):
+    """ccmp_path_smooth (KinematicChainConstraint.smooth_paths): three passes on 1 and 64 paths of 32 waypoints (chains of near-sampled
+    milestones of the FD constraint, seed 0x5C7), both Jacobian modes, lists of 16 and a round budget of 128; wall clock around the
+    synchronous call, medians; the extend calls, projector calls and bytes read on the host as the library counts them
+    (ccmp_smooth_last_counts).  With a second argument the inputs and results are written there (.npz) for `smooth_restate`.  Writes
+    profiles/smooth.md."""
+    import os
+
+    reps = int(argv[0]) if len(argv) > 0 else 9
+    dump = argv[1] if len(argv) > 1 else None
+    Lw, seed, steps = 32, 0x5C7, 3
+    ctx = Context(0)
+    lines, saved = [], {}
+
+    def say(text):
+        print(text)
+        lines.append(text)
+
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    pj, pl = _smooth_paths(c, 64, Lw, seed)  # the FD constraint's samples for both modes
+    saved["path_joints"] = pj.cpu().numpy()
+    for mode in (0, 1):
+        c.setJacobianMode(mode)
+        for F in (1, 64):
+            a, b = pj[:F].contiguous(), pl[:F].contiguous()
+            t = []
+            for i in range(reps + 2):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = c.smooth_paths(a, b, max_steps=steps, stats=True)
+                torch.cuda.synchronize()
+                if i >= 2:
+                    t.append((time.perf_counter() - t0) * 1e3)
+            calls, projects, nbytes = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+            _lib.lib().ccmp_smooth_last_counts(C.byref(calls), C.byref(projects), C.byref(nbytes))
+            o = {k: v.cpu().numpy() for k, v in out.items()}
+            for k, v in o.items():
+                saved["mode%d_F%d_%s" % (mode, F, k)] = v
+            say("%s mode, F = %d paths x %d waypoints, %d passes: %d -> %d vertices, moved %d, length %.3f -> %.3f per path, stop %s, stats (projected, fallback, "
+                "degenerate, refused, below) %s" % ("analytic" if mode else "FD", F, Lw, steps, F * Lw, int(o["out_len"].sum()), int(o["moved"].sum()),
+                                                  float(o["length_in"].mean()), float(o["length_out"].mean()), sorted(set(o["stop"].tolist())), o["stats"].sum(0).tolist()))
+            say("    extend calls %d, projector calls %d, bytes read on the host %d" % (calls.value, projects.value, nbytes.value))
+            say("    %-84s %s" % ("ccmp_path_smooth (every state stays on the device)", _stat(t)))
+    if dump:
+        np.savez(dump, **saved)
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "smooth.md"), "w") as f:
+        f.write("# Smooth solution paths on the device: `tools/measure.py smooth`\n\n1 x MI355X, one run, seed 0x5C7; `ccmp_path_smooth`, three passes, lists of 16, round "
+                "budget 128, wall clock around the synchronous call.  No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
+
+
+def smooth_restate(argv):
+    """the plain-Python restatement of the smoothing rule (tests/smooth_cases.py on the det oracle) on one host core, on the inputs `smooth`
+    wrote, compared bit for bit with the results it wrote: python tools/measure.py smooth_restate <file.npz> [paths]"""
+    sys.path.insert(0, "tests")
+    from conftest import load_cfg
+    from oracle_binding import Oracle
+    from smooth_cases import Restatement, bits
+
+    d = np.load(argv[0])
+    n_max = int(argv[1]) if len(argv) > 1 else 64
+    O = Oracle("det")
+    pj = d["path_joints"]
+    for mode in (0, 1):
+        P = O.problem(load_cfg("Wine_Bottle"))  # the oracle's own set-up: byte for byte the product's problem (tests/test_gpu_parity.py)
+        P.jacobian_mode = mode
+        for F in (1, 64):
+            F = min(F, n_max)
+            t0 = time.perf_counter()
+            same = True
+            for f in range(F):
+                r = Restatement(O, P).smooth(pj[f], 3, 0.005, 249)
+                n = len(r["rows"])
+                same = same and n == int(d["mode%d_F%d_out_len" % (mode, F)][f]) and np.array_equal(bits(r["rows"]), bits(d["mode%d_F%d_joints" % (mode, F)][f, :n])) \
+                    and r["stats"] == d["mode%d_F%d_stats" % (mode, F)][f].tolist()
+            print("%s mode, F = %d: restatement on one host core %.1f ms; rows, lengths and stats identical to the device's: %s"
+                  % ("analytic" if mode else "FD", F, (time.perf_counter() - t0) * 1e3, same))
+
+
 def run(argv):
     """fixed workloads for the profiler: one kernel family each, `reps` launches"""
     what = argv[0]
@@ -1519,7 +1609,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, dense, shortcut, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, dense, shortcut, smooth, smooth_restate, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
