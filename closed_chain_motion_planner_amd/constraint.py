@@ -11,15 +11,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._arrays import _stream_handle, _torch
 from ._lib import CCMP_JAC_ANALYTIC, CCMP_JAC_FD, CcmpError, CcmpProblem, check
 
 __all__ = ["Context", "Communicator", "KinematicChainConstraint", "ArmModel", "load_config", "CCMP_JAC_FD", "CCMP_JAC_ANALYTIC"]
-
-
-def _torch():
-    import torch  # deferred: importing the package must not need a GPU
-
-    return torch
 
 
 _SIZE_DEFAULT = C.c_size_t(-1).value  # CCMP_DEFAULT
@@ -137,14 +132,6 @@ def load_config(yaml_path):
 
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _stream_handle(stream):
-    if stream is None:
-        return C.c_void_p(_torch().cuda.current_stream().cuda_stream)
-    if isinstance(stream, int):
-        return C.c_void_p(stream)
-    return C.c_void_p(stream.cuda_stream)
 
 
 class KinematicChainConstraint:
@@ -536,8 +523,7 @@ class KinematicChainConstraint:
         from .dense import densify
 
         self._need_problem()
-        return densify(self.ctx, self.problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream, _torch(),
-                       _stream_handle)
+        return densify(self.ctx, self.problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream)
 
     def shortcut_paths(self, path_joints, path_len, scene=None, margin=None, max_span=0, chunk_states=16, round_budget=128, max_calls=4096,
                        tile_edges=65536, pairs=False, stream=None):
@@ -554,8 +540,7 @@ class KinematicChainConstraint:
         from .shortcut import shortcut
 
         self._need_problem()
-        return shortcut(self.ctx, self.problem, path_joints, path_len, scene, margin, max_span, chunk_states, round_budget, max_calls, tile_edges, pairs,
-                        stream, _torch(), _stream_handle)
+        return shortcut(self.ctx, self.problem, path_joints, path_len, scene, margin, max_span, chunk_states, round_budget, max_calls, tile_edges, pairs, stream)
 
     def smooth_paths(self, path_joints, path_len, max_steps=5, min_change=0.005, out_max_len=None, scene=None, margin=None, chunk_states=16,
                      round_budget=128, max_calls=4096, tile_edges=65536, stats=False, stream=None):
@@ -574,7 +559,7 @@ class KinematicChainConstraint:
 
         self._need_problem()
         return smooth(self.ctx, self.problem, path_joints, path_len, max_steps, min_change, out_max_len, scene, margin, chunk_states, round_budget, max_calls,
-                      tile_edges, stats, stream, _torch(), _stream_handle)
+                      tile_edges, stats, stream)
 
     def ambient_uniform_batch(self, seed, first_index, B, stream=None):
         self._need_problem()

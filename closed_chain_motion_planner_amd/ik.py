@@ -15,11 +15,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CcmpIkOpts, check
+from ._arrays import kind_of
+from ._lib import CcmpIkOpts
+from .scene import scene_arrays
 
 __all__ = ["ik_options", "pose_ik_ref", "pose_ik", "pose_ik_vetted_ref"]
-
-_dp, _i32p, _u8p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 
 
 def ik_options(**kw):
@@ -36,60 +36,26 @@ def ik_options(**kw):
     return o
 
 
-def _shape(target_poses, seeds):
-    if target_poses.ndim != 2 or target_poses.shape[1] != 8:
-        raise ValueError("target_poses: expected (T, 8), got %s" % (tuple(target_poses.shape),))
-    T = target_poses.shape[0]
-    if seeds.ndim != 3 or seeds.shape[0] != T or seeds.shape[2] != 14:
-        raise ValueError("seeds: expected (T, S, 14) with T = %d, got %s" % (T, tuple(seeds.shape)))
-    return T, int(seeds.shape[1])
+def _inputs(K, target_poses, seeds):
+    tp = K.expect(target_poses, "float64", (None, 8), "target_poses (T, 8)")
+    sd = K.expect(seeds, "float64", (len(tp), None, 14), "seeds (T, S, 14)")
+    return tp, sd, len(tp), int(sd.shape[1])
 
 
 def _vetted(ctx_handle, problem, target_poses, seeds, rng_seed, first_index, opts, want_candidates, stream, scene, margin):
     """ccmp_pose_ik_vetted_host / _batch / _ref; scene: a ProxyScene, or for the host reference (ctx_handle None) the caller's arrays as a
     tuple (spheres, boxes, allowed)"""
-    L = _lib.lib()
+    ref = isinstance(scene, tuple)
     R1 = 1 + int(opts.restarts)
-    margin = 0.0 if margin is None else float(margin)
-    head = (int(rng_seed), int(first_index))
-    if isinstance(target_poses, np.ndarray):
-        tp = np.ascontiguousarray(target_poses, dtype=np.float64)
-        sd = np.ascontiguousarray(seeds, dtype=np.float64)
-        T, S = _shape(tp, sd)
-        out = {"q": np.empty((T, 14)), "ok": np.empty(T, dtype=np.uint8), "which": np.empty(T, dtype=np.int32), "clearance": np.empty(T)}
-        if want_candidates:
-            out.update(cand_q=np.empty((T, S, 2, R1, 7)), cand_rounds=np.empty((T, S, 2, R1), dtype=np.int32), cand_clear=np.empty((T, S, 2, R1)),
-                       slot_clear=np.empty((T, S)))
-        ptr = lambda n, t: out[n].ctypes.data_as(t) if n in out else None  # noqa: E731
-        outs = (ptr("q", _dp), ptr("ok", _u8p), ptr("which", _i32p), ptr("cand_q", _dp), ptr("cand_rounds", _i32p), ptr("cand_clear", _dp),
-                ptr("slot_clear", _dp), ptr("clearance", _dp))
-        args = (C.byref(problem), C.byref(opts), tp.ctypes.data_as(_dp), sd.ctypes.data_as(_dp), T, S) + head
-        if isinstance(scene, tuple):
-            from .scene import scene_arrays
-
-            check(L.ccmp_pose_ik_vetted_ref(*args, *scene_arrays(*scene), margin, *outs), "ccmp_pose_ik_vetted_ref")
-        else:
-            check(L.ccmp_pose_ik_vetted_host(ctx_handle, *args, scene._h, margin, *outs), "ccmp_pose_ik_vetted_host")
-        return out
-    from .constraint import _stream_handle, _torch
-
-    torch = _torch()
-    for t in (target_poses, seeds):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError("expected contiguous float64 tensors on the device")
-    T, S = _shape(target_poses, seeds)
-    dev = target_poses.device
-    out = {"q": torch.empty((T, 14), dtype=torch.float64, device=dev), "ok": torch.empty(T, dtype=torch.uint8, device=dev),
-           "which": torch.empty(T, dtype=torch.int32, device=dev), "clearance": torch.empty(T, dtype=torch.float64, device=dev)}
-    if want_candidates:
-        out["cand_q"] = torch.empty((T, S, 2, R1, 7), dtype=torch.float64, device=dev)
-        out["cand_rounds"] = torch.empty((T, S, 2, R1), dtype=torch.int32, device=dev)
-        out["cand_clear"] = torch.empty((T, S, 2, R1), dtype=torch.float64, device=dev)
-        out["slot_clear"] = torch.empty((T, S), dtype=torch.float64, device=dev)
-    ptr = lambda n: out[n].data_ptr() if n in out else None  # noqa: E731
-    check(L.ccmp_pose_ik_vetted_batch(ctx_handle, C.byref(problem), C.byref(opts), target_poses.data_ptr(), seeds.data_ptr(), T, S, *head, scene._h, margin,
-                                      ptr("q"), ptr("ok"), ptr("which"), ptr("cand_q"), ptr("cand_rounds"), ptr("cand_clear"), ptr("slot_clear"),
-                                      ptr("clearance"), _stream_handle(stream)), "ccmp_pose_ik_vetted_batch")
+    K = kind_of(target_poses)
+    tp, sd, T, S = _inputs(K, target_poses, seeds)
+    out = {"q": K.empty((T, 14), "float64"), "ok": K.empty(T, "uint8"), "which": K.empty(T, "int32"), "clearance": K.empty(T, "float64"),
+           **({"cand_q": K.empty((T, S, 2, R1, 7), "float64"), "cand_rounds": K.empty((T, S, 2, R1), "int32"), "cand_clear": K.empty((T, S, 2, R1), "float64"),
+               "slot_clear": K.empty((T, S), "float64")} if want_candidates else {})}
+    K.call("ccmp_pose_ik_vetted_batch", "ccmp_pose_ik_vetted_ref" if ref else "ccmp_pose_ik_vetted_host", *(() if ref else (ctx_handle,)), C.byref(problem),
+           C.byref(opts), K.arg(tp), K.arg(sd), T, S, int(rng_seed), int(first_index), *(scene_arrays(*scene) if ref else (scene._h,)),
+           0.0 if margin is None else float(margin),
+           *[K.arg(out.get(n)) for n in ("q", "ok", "which", "cand_q", "cand_rounds", "cand_clear", "slot_clear", "clearance")], stream=stream)
     return out
 
 
@@ -100,44 +66,16 @@ def pose_ik(ctx_handle, problem, target_poses, seeds, rng_seed=0, first_index=0,
     want_candidates, cand_q (T,S,2,1+R,7) and cand_rounds (T,S,2,1+R) int32.
     scene (a ProxyScene) and margin (None = 0): the vetted forms, ccmp_pose_ik_vetted_* — the dict also holds clearance (T,) and, with
     want_candidates, cand_clear (T,S,2,1+R) and slot_clear (T,S).  Without a scene the call is the plain one, as before."""
-    L = _lib.lib()
     opts = opts if opts is not None else ik_options()
     if scene is not None:
         return _vetted(ctx_handle, problem, target_poses, seeds, rng_seed, first_index, opts, want_candidates, stream, scene, margin)
     R1 = 1 + int(opts.restarts)
-    if isinstance(target_poses, np.ndarray):
-        tp = np.ascontiguousarray(target_poses, dtype=np.float64)
-        sd = np.ascontiguousarray(seeds, dtype=np.float64)
-        T, S = _shape(tp, sd)
-        out = {"q": np.empty((T, 14)), "ok": np.empty(T, dtype=np.uint8), "which": np.empty(T, dtype=np.int32)}
-        if want_candidates:
-            out["cand_q"] = np.empty((T, S, 2, R1, 7))
-            out["cand_rounds"] = np.empty((T, S, 2, R1), dtype=np.int32)
-        tail = (tp.ctypes.data_as(_dp), sd.ctypes.data_as(_dp), T, S, int(rng_seed), int(first_index), out["q"].ctypes.data_as(_dp),
-                out["ok"].ctypes.data_as(_u8p), out["which"].ctypes.data_as(_i32p),
-                out["cand_q"].ctypes.data_as(_dp) if want_candidates else None, out["cand_rounds"].ctypes.data_as(_i32p) if want_candidates else None)
-        if ref:
-            check(L.ccmp_pose_ik_ref(C.byref(problem), C.byref(opts), *tail), "ccmp_pose_ik_ref")
-        else:
-            check(L.ccmp_pose_ik_host(ctx_handle, C.byref(problem), C.byref(opts), *tail), "ccmp_pose_ik_host")
-        return out
-    from .constraint import _stream_handle, _torch
-
-    torch = _torch()
-    for t in (target_poses, seeds):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError("expected contiguous float64 tensors on the device")
-    T, S = _shape(target_poses, seeds)
-    dev = target_poses.device
-    out = {"q": torch.empty((T, 14), dtype=torch.float64, device=dev), "ok": torch.empty(T, dtype=torch.uint8, device=dev),
-           "which": torch.empty(T, dtype=torch.int32, device=dev)}
-    if want_candidates:
-        out["cand_q"] = torch.empty((T, S, 2, R1, 7), dtype=torch.float64, device=dev)
-        out["cand_rounds"] = torch.empty((T, S, 2, R1), dtype=torch.int32, device=dev)
-    check(L.ccmp_pose_ik_batch(ctx_handle, C.byref(problem), C.byref(opts), target_poses.data_ptr(), seeds.data_ptr(), T, S, int(rng_seed), int(first_index),
-                               out["q"].data_ptr(), out["ok"].data_ptr(), out["which"].data_ptr(),
-                               out["cand_q"].data_ptr() if want_candidates else None, out["cand_rounds"].data_ptr() if want_candidates else None,
-                               _stream_handle(stream)), "ccmp_pose_ik_batch")
+    K = kind_of(target_poses)
+    tp, sd, T, S = _inputs(K, target_poses, seeds)
+    out = {"q": K.empty((T, 14), "float64"), "ok": K.empty(T, "uint8"), "which": K.empty(T, "int32"),
+           **({"cand_q": K.empty((T, S, 2, R1, 7), "float64"), "cand_rounds": K.empty((T, S, 2, R1), "int32")} if want_candidates else {})}
+    K.call("ccmp_pose_ik_batch", "ccmp_pose_ik_ref" if ref else "ccmp_pose_ik_host", *(() if ref else (ctx_handle,)), C.byref(problem), C.byref(opts), K.arg(tp),
+           K.arg(sd), T, S, int(rng_seed), int(first_index), *[K.arg(out.get(n)) for n in ("q", "ok", "which", "cand_q", "cand_rounds")], stream=stream)
     return out
 
 

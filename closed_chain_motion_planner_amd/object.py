@@ -16,11 +16,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._arrays import HOST, kind_of
 from ._lib import CcmpBox, check
 
 __all__ = ["ObjectChecker", "object_valid_ref", "object_propose_ref", "pose_interpolate", "boxes_from", "DEFAULT_LO", "DEFAULT_HI"]
 
-_dp, _i32p, _u8p, _u32p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
 # position bounds of the draw when the caller gives none: effectively unbounded (the planner passes its object space's bounds)
 DEFAULT_LO, DEFAULT_HI = (-1e30,) * 3, (1e30,) * 3
 
@@ -39,17 +39,14 @@ def boxes_from(boxes):
 
 
 def _tri(triangles):
-    t = np.ascontiguousarray(triangles, dtype=np.float64).reshape(-1, 9)
-    return t
+    return HOST.expect(triangles, "float64", -1, "triangles").reshape(-1, 9)
 
 
-def _poses(a, name="poses"):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.ndim == 1:
-        a = a.reshape(1, -1)
-    if a.ndim != 2 or a.shape[1] != 8:
-        raise ValueError("%s: expected (n, 8), got %s" % (name, (a.shape,)))
-    return a
+def _poses(K, a, name="poses"):
+    """pose rows (n, 8) of kind K; the host kind also takes one pose (8,)"""
+    if K is HOST and np.ndim(a) == 1:
+        a = np.reshape(a, (1, -1))
+    return K.expect(a, "float64", (None, 8), name)
 
 
 def _vec3(v):
@@ -60,47 +57,39 @@ def pose_interpolate(a, b, t):
     """ccmp_pose_interpolate: OMPL's SE3StateSpace::interpolate on pose rows (x y z qx qy qz qw [pad]); host only, the kernels' bits"""
     a8, b8, out = np.zeros(8), np.zeros(8), np.empty(8)
     a8[:7], b8[:7] = np.asarray(a, dtype=np.float64)[:7], np.asarray(b, dtype=np.float64)[:7]
-    _lib.lib().ccmp_pose_interpolate(a8.ctypes.data_as(_dp), b8.ctypes.data_as(_dp), float(t), out.ctypes.data_as(_dp))
+    _lib.lib().ccmp_pose_interpolate(HOST.arg(a8), HOST.arg(b8), float(t), HOST.arg(out))
     return out
 
 
 def object_valid_ref(triangles, boxes, poses, inflate=0.0, want_mask=False, broad_phase=True):
     """ccmp_object_valid_ref: valid (T,) uint8 and, with want_mask, hit_mask (T,) uint32 — no device"""
-    tri, bx, ps = _tri(triangles), boxes_from(boxes), _poses(poses)
-    valid, mask = np.empty(len(ps), dtype=np.uint8), np.empty(len(ps), dtype=np.uint32)
-    check(_lib.lib().ccmp_object_valid_ref(tri.ctypes.data_as(_dp), len(tri), bx, len(bx), ps.ctypes.data_as(_dp), len(ps), float(inflate),
-                                           1 if broad_phase else 0, valid.ctypes.data_as(_u8p), mask.ctypes.data_as(_u32p) if want_mask else None),
-          "ccmp_object_valid_ref")
+    tri, bx, ps = _tri(triangles), boxes_from(boxes), _poses(HOST, poses)
+    valid, mask = HOST.empty(len(ps), "uint8"), HOST.empty(len(ps), "uint32") if want_mask else None
+    check(_lib.lib().ccmp_object_valid_ref(HOST.arg(tri), len(tri), bx, len(bx), HOST.arg(ps), len(ps), float(inflate), 1 if broad_phase else 0, HOST.arg(valid),
+                                           HOST.arg(mask)), "ccmp_object_valid_ref")
     return (valid, mask) if want_mask else valid
 
 
-def _propose_out_host(G, A, want_candidates):
-    out = {"pose": np.empty((G, 8)), "which": np.empty(G, dtype=np.int32)}
-    if want_candidates:
-        out["cand_pose"] = np.empty((G, A, 8))
-        out["cand_valid"] = np.empty((G, A), dtype=np.uint8)
-    return out
+def _propose_out(K, G, A, want_candidates):
+    return {"pose": K.empty((G, 8), "float64"), "which": K.empty(G, "int32"),
+            **({"cand_pose": K.empty((G, A, 8), "float64"), "cand_valid": K.empty((G, A), "uint8")} if want_candidates else {})}
 
 
-def _to_stride(frm, to):
-    if to.shape[0] == 1:
-        return 0
-    if to.shape[0] != frm.shape[0]:
+def _propose_args(K, frm, to, t, sigma, lo, hi, attempts, rng_seed, first_index, inflate, out):
+    """ccmp_object_propose_*'s arguments behind the mesh and the boxes"""
+    if to.shape[0] not in (1, frm.shape[0]):
         raise ValueError("to_poses: one goal pose or one per from pose")
-    return 8
+    return (K.arg(frm), K.arg(to), 0 if to.shape[0] == 1 else 8, len(frm), float(t), float(sigma), _vec3(lo), _vec3(hi), int(attempts), int(rng_seed),
+            int(first_index), float(inflate), *[K.arg(out.get(n)) for n in ("pose", "which", "cand_pose", "cand_valid")])
 
 
 def object_propose_ref(triangles, boxes, from_poses, to_poses, t=0.3, sigma=0.2, lo=DEFAULT_LO, hi=DEFAULT_HI, attempts=2, rng_seed=0, first_index=0,
                        inflate=0.0, want_candidates=False):
     """ccmp_object_propose_ref: the dict of `ObjectChecker.propose` — no device"""
-    tri, bx, frm, to = _tri(triangles), boxes_from(boxes), _poses(from_poses, "from_poses"), _poses(to_poses, "to_poses")
-    G, A = len(frm), int(attempts)
-    out = _propose_out_host(G, max(A, 0), want_candidates)
-    check(_lib.lib().ccmp_object_propose_ref(tri.ctypes.data_as(_dp), len(tri), bx, len(bx), frm.ctypes.data_as(_dp), to.ctypes.data_as(_dp), _to_stride(frm, to),
-                                             G, float(t), float(sigma), _vec3(lo), _vec3(hi), A, int(rng_seed), int(first_index), float(inflate),
-                                             out["pose"].ctypes.data_as(_dp), out["which"].ctypes.data_as(_i32p),
-                                             out["cand_pose"].ctypes.data_as(_dp) if want_candidates else None,
-                                             out["cand_valid"].ctypes.data_as(_u8p) if want_candidates else None), "ccmp_object_propose_ref")
+    tri, bx, frm, to = _tri(triangles), boxes_from(boxes), _poses(HOST, from_poses, "from_poses"), _poses(HOST, to_poses, "to_poses")
+    out = _propose_out(HOST, len(frm), max(int(attempts), 0), want_candidates)
+    check(_lib.lib().ccmp_object_propose_ref(HOST.arg(tri), len(tri), bx, len(bx),
+                                             *_propose_args(HOST, frm, to, t, sigma, lo, hi, attempts, rng_seed, first_index, inflate, out)), "ccmp_object_propose_ref")
     return out
 
 
@@ -112,37 +101,19 @@ class ObjectChecker:
         self.ctx = getattr(constraint_or_ctx, "ctx", constraint_or_ctx)
         tri, bx = _tri(triangles), boxes_from(boxes)
         self._h = C.c_void_p()
-        check(_lib.lib().ccmp_object_create(self.ctx.handle, tri.ctypes.data_as(_dp), len(tri), bx, len(bx), C.byref(self._h)), "ccmp_object_create")
+        check(_lib.lib().ccmp_object_create(self.ctx.handle, HOST.arg(tri), len(tri), bx, len(bx), C.byref(self._h)), "ccmp_object_create")
 
     def __len__(self):
         return int(_lib.lib().ccmp_object_num_triangles(self._h))
 
-    def _dev(self, t, name):
-        from .constraint import _torch
-
-        torch = _torch()
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 8):
-            raise ValueError("%s: expected a contiguous (n, 8) float64 tensor on the device" % name)
-        return t
-
     def valid(self, poses, inflate=0.0, want_mask=False, stream=None):
         """valid (T,) uint8 — the pose's mesh touches no box — and with want_mask hit_mask (T,) uint32 (torch: int32 with the same bits),
         bit b = box b is hit.  Without the mask a block leaves at its first hit; `valid` is the same."""
-        L = _lib.lib()
-        if isinstance(poses, np.ndarray):
-            ps = _poses(poses)
-            valid, mask = np.empty(len(ps), dtype=np.uint8), np.empty(len(ps), dtype=np.uint32)
-            check(L.ccmp_object_valid_host(self.ctx.handle, self._h, ps.ctypes.data_as(_dp), len(ps), float(inflate), valid.ctypes.data_as(_u8p),
-                                           mask.ctypes.data_as(_u32p) if want_mask else None), "ccmp_object_valid_host")
-            return (valid, mask) if want_mask else valid
-        from .constraint import _stream_handle, _torch
-
-        torch = _torch()
-        ps = self._dev(poses, "poses")
-        valid = torch.empty(ps.shape[0], dtype=torch.uint8, device=ps.device)
-        mask = torch.empty(ps.shape[0], dtype=torch.int32, device=ps.device) if want_mask else None
-        check(L.ccmp_object_valid_batch(self.ctx.handle, self._h, ps.data_ptr(), ps.shape[0], float(inflate), valid.data_ptr(),
-                                        mask.data_ptr() if want_mask else None, _stream_handle(stream)), "ccmp_object_valid_batch")
+        K = kind_of(poses)
+        ps = _poses(K, poses)
+        valid, mask = K.empty(len(ps), "uint8"), K.empty(len(ps), "uint32") if want_mask else None
+        K.call("ccmp_object_valid_batch", "ccmp_object_valid_host", self.ctx.handle, self._h, K.arg(ps), len(ps), float(inflate), K.arg(valid), K.arg(mask),
+               stream=stream)
         return (valid, mask) if want_mask else valid
 
     def propose(self, from_poses, to_poses, t=0.3, sigma=0.2, lo=DEFAULT_LO, hi=DEFAULT_HI, attempts=2, rng_seed=0, first_index=0, inflate=0.0,
@@ -151,31 +122,12 @@ class ObjectChecker:
         (or the one goal pose) at t, then the SE(3) Gaussian draw of index (first_index + g) * attempts + a — whose mesh is free.  Returns a
         dict: pose (G, 8) (a NaN row where none was), which (G,) int32 (-1 where none was) and, with want_candidates, cand_pose (G, A, 8)
         and cand_valid (G, A) of every attempt."""
-        L = _lib.lib()
-        A = int(attempts)
-        if isinstance(from_poses, np.ndarray):
-            frm, to = _poses(from_poses, "from_poses"), _poses(to_poses, "to_poses")
-            out = _propose_out_host(len(frm), max(A, 0), want_candidates)
-            check(L.ccmp_object_propose_host(self.ctx.handle, self._h, frm.ctypes.data_as(_dp), to.ctypes.data_as(_dp), _to_stride(frm, to), len(frm), float(t),
-                                             float(sigma), _vec3(lo), _vec3(hi), A, int(rng_seed), int(first_index), float(inflate),
-                                             out["pose"].ctypes.data_as(_dp), out["which"].ctypes.data_as(_i32p),
-                                             out["cand_pose"].ctypes.data_as(_dp) if want_candidates else None,
-                                             out["cand_valid"].ctypes.data_as(_u8p) if want_candidates else None), "ccmp_object_propose_host")
-            return out
-        from .constraint import _stream_handle, _torch
-
-        torch = _torch()
-        frm = self._dev(from_poses, "from_poses")
-        to = self._dev(to_poses.reshape(1, 8) if to_poses.dim() == 1 else to_poses, "to_poses")
-        G, dev = frm.shape[0], frm.device
-        out = {"pose": torch.empty((G, 8), dtype=torch.float64, device=dev), "which": torch.empty(G, dtype=torch.int32, device=dev)}
-        if want_candidates:
-            out["cand_pose"] = torch.empty((G, max(A, 0), 8), dtype=torch.float64, device=dev)
-            out["cand_valid"] = torch.empty((G, max(A, 0)), dtype=torch.uint8, device=dev)
-        check(L.ccmp_object_propose_batch(self.ctx.handle, self._h, frm.data_ptr(), to.data_ptr(), _to_stride(frm, to), G, float(t), float(sigma), _vec3(lo),
-                                          _vec3(hi), A, int(rng_seed), int(first_index), float(inflate), out["pose"].data_ptr(), out["which"].data_ptr(),
-                                          out["cand_pose"].data_ptr() if want_candidates else None, out["cand_valid"].data_ptr() if want_candidates else None,
-                                          _stream_handle(stream)), "ccmp_object_propose_batch")
+        K = kind_of(from_poses)
+        frm = _poses(K, from_poses, "from_poses")
+        to = _poses(K, to_poses.reshape(1, 8) if K is not HOST and to_poses.dim() == 1 else to_poses, "to_poses")
+        out = _propose_out(K, len(frm), max(int(attempts), 0), want_candidates)
+        K.call("ccmp_object_propose_batch", "ccmp_object_propose_host", self.ctx.handle, self._h,
+               *_propose_args(K, frm, to, t, sigma, lo, hi, attempts, rng_seed, first_index, inflate, out), stream=stream)
         return out
 
     def ladder(self, from_pose, goal_pose, steps=9, inflate=0.0):

@@ -13,45 +13,29 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._arrays import HOST, _stream_handle, _torch, kind_of, kind_on
 from ._lib import COMMIT_KEEP_ISOLATED, GROW_GREACHED, GROW_SREACHED, GROW_TRAPPED, GROW_UNSETTLED, METRIC_JOINT, METRIC_OBJECT, check
-from .constraint import _stream_handle, _torch
+from .ik import ik_options
+from .object import DEFAULT_HI, DEFAULT_LO
 
 __all__ = ["Roadmap", "pose_distance", "pose_from_t_wo", "joint_distance", "graph_labels_ref", "commit_ref", "closest_ref", "shortest_paths_ref", "METRIC_JOINT", "METRIC_OBJECT",
            "GROW_TRAPPED", "GROW_SREACHED", "GROW_GREACHED", "GROW_UNSETTLED", "COMMIT_KEEP_ISOLATED"]
 
-_dp = C.POINTER(C.c_double)
-_i32p = C.POINTER(C.c_int32)
-_u8p = C.POINTER(C.c_uint8)
+_arg = HOST.arg
 
 
-def _np(a, dtype, shape=None):
-    a = np.ascontiguousarray(a, dtype=dtype)
-    return a if shape is None else a.reshape(shape)
-
-
-def _ptr(a, typ):
-    return a.ctypes.data_as(typ) if a is not None else None
-
-
-def _host(a, cols):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.ndim != 2 or a.shape[1] != cols:
-        raise ValueError("expected an (n, %d) float64 array, got %s" % (cols, (a.shape,)))
-    return a
-
-
-def _dev(t, cols):
-    torch = _torch()
-    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous() or not t.is_cuda:
-        raise ValueError("expected a contiguous (n, %d) float64 tensor on the device" % cols)
-    return t
+def _pose8(pose):
+    """a pose (x y z qx qy qz qw [pad]) from the host or the device as the padded host row the library takes"""
+    p8 = np.zeros(8)
+    p8[:7] = np.asarray(pose.cpu() if hasattr(pose, "cpu") else pose, dtype=np.float64).reshape(-1)[:7]
+    return p8
 
 
 def pose_distance(a, b):
     """ccmp_pose_distance: OMPL's SE3StateSpace::distance (weights 1 and 1) between two poses (x y z qx qy qz qw [pad]); host only"""
     a8, b8 = np.zeros(8), np.zeros(8)
     a8[:7], b8[:7] = np.asarray(a, dtype=np.float64)[:7], np.asarray(b, dtype=np.float64)[:7]
-    return float(_lib.lib().ccmp_pose_distance(a8.ctypes.data_as(_dp), b8.ctypes.data_as(_dp)))
+    return float(_lib.lib().ccmp_pose_distance(_arg(a8), _arg(b8)))
 
 
 def pose_from_t_wo(t_wo):
@@ -61,41 +45,41 @@ def pose_from_t_wo(t_wo):
     out = np.empty((flat.shape[0], 8))
     fn = _lib.lib().ccmp_pose_from_t_wo
     for i in range(flat.shape[0]):
-        fn(flat[i].ctypes.data_as(_dp), out[i].ctypes.data_as(_dp))
+        fn(_arg(flat[i]), _arg(out[i]))
     return out.reshape(t.shape[:-1] + (8,))
 
 
 def joint_distance(a, b):
     """ccmp_joint_distance: the weight of an edge between two joint states (RealVectorStateSpace::distance over the 14 joints in the
     k-NN's rounding); host only"""
-    a, b = _np(a, np.float64, 14), _np(b, np.float64, 14)
-    return float(_lib.lib().ccmp_joint_distance(_ptr(a, _dp), _ptr(b, _dp)))
+    return float(_lib.lib().ccmp_joint_distance(_arg(HOST.expect(a, "float64", 14, "a")), _arg(HOST.expect(b, "float64", 14, "b"))))
 
 
 def graph_labels_ref(uv, n):
     """ccmp_graph_labels_ref: labels (n,) int32, label[v] = the smallest index of v's component under the edges uv (E,2); host only"""
-    uv = _np(uv, np.int32).reshape(-1, 2)
+    uv = HOST.expect(uv, "int32", -1, "uv").reshape(-1, 2)
     labels = np.empty(int(n), dtype=np.int32)
-    check(_lib.lib().ccmp_graph_labels_ref(_ptr(uv, _i32p), len(uv), int(n), _ptr(labels, _i32p)), "ccmp_graph_labels_ref")
+    check(_lib.lib().ccmp_graph_labels_ref(_arg(uv), len(uv), int(n), _arg(labels)), "ccmp_graph_labels_ref")
     return labels
 
 
 _NO_LIMIT = 2**31 - 1  # max_states of a commit without state lists and without a stated limit: no slot is unsettled by its length
 
 
-def _commit_inputs(nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots):
-    nbr = _np(nbr_idx, np.int32)
-    if nbr.ndim != 2:
-        raise ValueError("nbr_idx is (Q, k)")
+def _commit_inputs(K, nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots, max_states):
+    """the inputs of `Roadmap.commit` / `commit_ref` as kind K takes them (goal and roots: host arrays in both), then max_states, Q and k.
+    The host kind reshapes what it is given; the device kind takes new_joints (n,14) / new_poses (n,8) as they are."""
+    nbr = K.expect(nbr_idx, "int32", (None, None), "nbr_idx (Q, k)")
     Q, k = nbr.shape
     S = Q * k
-    st = None if states is None or S == 0 else _np(states, np.float64).reshape(S, -1, 14)
-    goal = None
-    if goal_pose is not None:
-        goal = np.zeros(8)
-        goal[:7] = np.asarray(goal_pose, dtype=np.float64).reshape(-1)[:7]
-    return (nbr, _np(edge_ok, np.uint8, S), _np(n_states, np.int32, S), st, _np(new_joints, np.float64, (Q, 14)), _np(new_poses, np.float64, (Q, 8)),
-            None if vertex_ok is None else _np(vertex_ok, np.uint8, Q), goal, _np(list(roots), np.int32, -1), Q, k)
+    st, ms = None, _NO_LIMIT if max_states is None else int(max_states)
+    if states is not None and S:
+        ms = int(np.prod(np.shape(states))) // (S * 14)  # the traversal's list length
+        st = K.expect(states, "float64", S * ms * 14, "states (Q * k, max_states, 14)")
+    rows = (lambda c: Q * c) if K is HOST else (lambda c: (None, c))
+    return (nbr, K.expect(edge_ok, "uint8", S, "edge_ok"), K.expect(n_states, "int32", S, "n_states"), st, K.expect(new_joints, "float64", rows(14), "new_joints"),
+            K.expect(new_poses, "float64", rows(8), "new_poses"), None if vertex_ok is None else K.expect(vertex_ok, "uint8", Q, "vertex_ok"),
+            None if goal_pose is None else _pose8(goal_pose), HOST.expect(list(roots), "int32", -1, "roots"), ms, Q, k)
 
 
 def commit_ref(problem, store_joints, store_poses, labels, nbr_idx, edge_ok, n_states, new_joints, new_poses, states=None, vertex_ok=None, goal_pose=None,
@@ -105,30 +89,29 @@ def commit_ref(problem, store_joints, store_poses, labels, nbr_idx, edge_ok, n_s
     the appended rows and edges in index order: rows_joints (V,14), rows_poses (V,8), edges_uv (E,2), edges_w (E,).  `problem`: a
     `CcmpProblem` (needed for mid-stones only).  max_states: the traversal's list length (n_states beyond it = unsettled); taken from
     `states` when those are given."""
-    sj, sp, lab = _np(store_joints, np.float64).reshape(-1, 14), _np(store_poses, np.float64).reshape(-1, 8), _np(labels, np.int32, -1)
-    nbr, ok, ns, st, nj, npo, vok, goal, rt, Q, k = _commit_inputs(nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots)
+    sj, sp = HOST.expect(store_joints, "float64", -1, "store_joints").reshape(-1, 14), HOST.expect(store_poses, "float64", -1, "store_poses").reshape(-1, 8)
+    lab = HOST.expect(labels, "int32", -1, "labels")
+    nbr, ok, ns, st, nj, npo, vok, goal, rt, ms, Q, k = _commit_inputs(HOST, nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots,
+                                                                       max_states)
     S = Q * k
     out = {"new_index": np.empty(Q, dtype=np.int32), "mid_index": np.empty((Q, k), dtype=np.int32), "grow_state": np.empty(Q, dtype=np.int32)}
     rj, rp, euv, ew = np.empty((Q + S, 14)), np.empty((Q + S, 8)), np.empty((S, 2), dtype=np.int32), np.empty(S)
     nv, ne = C.c_size_t(), C.c_size_t()
-    check(_lib.lib().ccmp_roadmap_commit_ref(C.byref(problem) if problem is not None else None, _ptr(sj, _dp), _ptr(sp, _dp), _ptr(lab, _i32p), len(sj),
-                                             _ptr(nbr, _i32p), _ptr(ok, _u8p), _ptr(ns, _i32p), _ptr(st, _dp),
-                                             st.shape[1] if st is not None else _NO_LIMIT if max_states is None else int(max_states),
-                                             _ptr(nj, _dp), _ptr(npo, _dp), _ptr(vok, _u8p), Q, k, _ptr(goal, _dp), _ptr(rt, _i32p), len(rt), int(flags),
-                                             _ptr(out["new_index"], _i32p), _ptr(out["mid_index"], _i32p), _ptr(out["grow_state"], _i32p), _ptr(rj, _dp),
-                                             _ptr(rp, _dp), _ptr(euv, _i32p), _ptr(ew, _dp), C.byref(nv), C.byref(ne)), "ccmp_roadmap_commit_ref")
+    check(_lib.lib().ccmp_roadmap_commit_ref(C.byref(problem) if problem is not None else None, _arg(sj), _arg(sp), _arg(lab), len(sj), _arg(nbr), _arg(ok),
+                                             _arg(ns), _arg(st), ms, _arg(nj), _arg(npo), _arg(vok), Q, k, _arg(goal), _arg(rt), len(rt), int(flags),
+                                             _arg(out["new_index"]), _arg(out["mid_index"]), _arg(out["grow_state"]), _arg(rj), _arg(rp), _arg(euv), _arg(ew),
+                                             C.byref(nv), C.byref(ne)), "ccmp_roadmap_commit_ref")
     out.update(rows_joints=rj[:nv.value].copy(), rows_poses=rp[:nv.value].copy(), edges_uv=euv[:ne.value].copy(), edges_w=ew[:ne.value].copy())
     return out
 
 
 def closest_ref(store_poses, labels, froms, target_pose):
     """ccmp_roadmap_closest_ref: `Roadmap.closest` on host arrays, no device: (idx (F,), dist (F,), from_dist (F,))"""
-    sp, lab, fr = _np(store_poses, np.float64).reshape(-1, 8), _np(labels, np.int32, -1), _np(froms, np.int32, -1)
-    tgt = np.zeros(8)
-    tgt[:7] = np.asarray(target_pose, dtype=np.float64).reshape(-1)[:7]
+    sp = HOST.expect(store_poses, "float64", -1, "store_poses").reshape(-1, 8)
+    lab, fr = HOST.expect(labels, "int32", -1, "labels"), HOST.expect(froms, "int32", -1, "froms")
     idx, dist, fd = np.empty(len(fr), dtype=np.int32), np.empty(len(fr)), np.empty(len(fr))
-    check(_lib.lib().ccmp_roadmap_closest_ref(_ptr(sp, _dp), _ptr(lab, _i32p), len(sp), _ptr(fr, _i32p), len(fr), _ptr(tgt, _dp), _ptr(idx, _i32p),
-                                              _ptr(dist, _dp), _ptr(fd, _dp)), "ccmp_roadmap_closest_ref")
+    check(_lib.lib().ccmp_roadmap_closest_ref(_arg(sp), _arg(lab), len(sp), _arg(fr), len(fr), _arg(_pose8(target_pose)), _arg(idx), _arg(dist), _arg(fd)),
+          "ccmp_roadmap_closest_ref")
     return idx, dist, fd
 
 
@@ -137,17 +120,23 @@ def shortest_paths_ref(uv, w, n, src, dst, max_len=None, full=False):
     weights w (E,) over n vertices, pairs src (F,), dst (F,), F <= 64.  Distances by heap Dijkstra, hops and predecessors from the rule
     text the kernels compile.  Returns (cost (F,), path_len (F,), paths: a list of F int32 arrays; a path longer than max_len, when
     one is given, is None); full=True adds dist (F,n) and pred (F,n)."""
-    uv, w = _np(uv, np.int32).reshape(-1, 2), _np(w, np.float64, -1)
-    sr, ds = _np(src, np.int32, -1), _np(dst, np.int32, -1)
+    uv, w = HOST.expect(uv, "int32", -1, "uv").reshape(-1, 2), HOST.expect(w, "float64", -1, "w")
+    sr, ds = HOST.expect(src, "int32", -1, "src"), HOST.expect(dst, "int32", -1, "dst")
     F, n = len(sr), int(n)
     L = int(max_len) if max_len is not None else max(n, 1)
     cost, plen, path = np.empty(F), np.empty(F, dtype=np.int32), np.full((F, L), -1, dtype=np.int32)
     dist = np.empty((F, n)) if full else None
     pred = np.empty((F, n), dtype=np.int32) if full else None
-    check(_lib.lib().ccmp_graph_shortest_paths_ref(_ptr(uv, _i32p), _ptr(w, _dp), len(uv), n, _ptr(sr, _i32p), _ptr(ds, _i32p), F, L, _ptr(cost, _dp),
-                                                   _ptr(plen, _i32p), _ptr(path, _i32p), _ptr(dist, _dp), _ptr(pred, _i32p)), "ccmp_graph_shortest_paths_ref")
+    check(_lib.lib().ccmp_graph_shortest_paths_ref(_arg(uv), _arg(w), len(uv), n, _arg(sr), _arg(ds), F, L, _arg(cost), _arg(plen), _arg(path), _arg(dist),
+                                                   _arg(pred)), "ccmp_graph_shortest_paths_ref")
     paths = [path[f, :plen[f]].copy() if plen[f] <= L else None for f in range(F)]
     return (cost, plen, paths, dist, pred) if full else (cost, plen, paths)
+
+
+def _edge_outputs(K, E, ms):
+    """what the traversals of E edges leave, as `connect` and `grow` end their argument lists"""
+    return {"states": K.empty((E, ms, 14), "float64"), "n_states": K.empty((E,), "int32"), "ok": K.empty((E,), "uint8"), "newton_iters": K.empty((E,), "int32"),
+            "blocked": K.empty((E,), "uint8"), "carry": K.empty((E, 2), "float64")}
 
 
 class Roadmap:
@@ -178,28 +167,18 @@ class Roadmap:
         given = joints if joints is not None else poses
         if given is None:
             raise ValueError("joints, poses or both")
-        if isinstance(given, np.ndarray):
-            j = _host(joints, 14) if joints is not None else None
-            p = _host(poses, 8) if poses is not None else None
-            check(_lib.lib().ccmp_roadmap_append_host(self._h, self._problem() if p is None else None, j.ctypes.data_as(_dp) if j is not None else None,
-                                                      p.ctypes.data_as(_dp) if p is not None else None, len(given), C.byref(first)),
-                  "ccmp_roadmap_append_host")
-        else:
-            j = _dev(joints, 14) if joints is not None else None
-            p = _dev(poses, 8) if poses is not None else None
-            check(_lib.lib().ccmp_roadmap_append(self._h, self._problem() if p is None else None, j.data_ptr() if j is not None else None,
-                                                 p.data_ptr() if p is not None else None, given.shape[0], C.byref(first), _stream_handle(stream)),
-                  "ccmp_roadmap_append")
+        K = kind_of(given)
+        j = K.expect(joints, "float64", (None, 14), "joints") if joints is not None else None
+        p = K.expect(poses, "float64", (None, 8), "poses") if poses is not None else None
+        K.call("ccmp_roadmap_append", "ccmp_roadmap_append_host", self._h, self._problem() if p is None else None, K.arg(j), K.arg(p), len(given),
+               C.byref(first), stream=stream)
         return int(first.value)
 
     def set_joints(self, index, joints, stream=None):
         """the joints of vertex `index` (growTree: after the IK of a pose-only vertex); its pose row stays"""
-        if isinstance(joints, np.ndarray):
-            j = np.ascontiguousarray(joints, dtype=np.float64).reshape(14)
-            check(_lib.lib().ccmp_roadmap_set_joints_host(self._h, int(index), j.ctypes.data_as(_dp)), "ccmp_roadmap_set_joints_host")
-        else:
-            j = joints.reshape(1, 14)
-            check(_lib.lib().ccmp_roadmap_set_joints(self._h, int(index), _dev(j, 14).data_ptr(), _stream_handle(stream)), "ccmp_roadmap_set_joints")
+        K = kind_of(joints)
+        j = K.expect(joints.reshape(1, 14), "float64", (1, 14), "joints")
+        K.call("ccmp_roadmap_set_joints", "ccmp_roadmap_set_joints_host", self._h, int(index), K.arg(j), stream=stream)
 
     def truncate(self, n):
         """drops the vertices from index n on (the reference's remove_vertex of the vertex just appended)"""
@@ -208,33 +187,20 @@ class Roadmap:
     def read(self, first=0, count=None, host=False, stream=None):
         """(joints (count,14), poses (count,8)) of the vertices first ... — device tensors, or numpy arrays with host=True"""
         count = len(self) - int(first) if count is None else int(count)
-        if host:
-            j, p = np.empty((count, 14)), np.empty((count, 8))
-            check(_lib.lib().ccmp_roadmap_read_host(self._h, int(first), count, j.ctypes.data_as(_dp), p.ctypes.data_as(_dp)), "ccmp_roadmap_read_host")
-            return j, p
-        torch = _torch()
-        dev = torch.device("cuda", self.ctx.device)
-        j = torch.empty((count, 14), dtype=torch.float64, device=dev)
-        p = torch.empty((count, 8), dtype=torch.float64, device=dev)
-        check(_lib.lib().ccmp_roadmap_read(self._h, int(first), count, j.data_ptr(), p.data_ptr(), _stream_handle(stream)), "ccmp_roadmap_read")
+        K = kind_on(self.ctx, host)
+        j, p = K.empty((count, 14), "float64"), K.empty((count, 8), "float64")
+        K.call("ccmp_roadmap_read", "ccmp_roadmap_read_host", self._h, int(first), count, K.arg(j), K.arg(p), stream=stream)
         return j, p
 
     def nearest_k(self, queries, k, metric=METRIC_OBJECT, mode=0, self_base=0, stream=None):
         """The k nearest vertices of every query: (Q,8) poses under METRIC_OBJECT, (Q,14) joints under METRIC_JOINT; modes, ranking
         and empty slots as `KinematicChainConstraint.nearest_k_batch`.  Returns (nbr_idx (Q,k) int32, nbr_dist (Q,k) float64)."""
         cols, k = (14 if metric == METRIC_JOINT else 8), int(k)
-        if isinstance(queries, np.ndarray):
-            q = _host(queries, cols)
-            idx, dist = np.empty((len(q), k), dtype=np.int32), np.empty((len(q), k))
-            check(_lib.lib().ccmp_roadmap_knn_host(self._h, int(metric), q.ctypes.data_as(_dp), len(q), k, int(mode), int(self_base),
-                                                   idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(_dp)), "ccmp_roadmap_knn_host")
-            return idx, dist
-        torch = _torch()
-        q = _dev(queries, cols)
-        idx = torch.empty((q.shape[0], k), dtype=torch.int32, device=q.device)
-        dist = torch.empty((q.shape[0], k), dtype=torch.float64, device=q.device)
-        check(_lib.lib().ccmp_roadmap_knn(self._h, int(metric), q.data_ptr(), q.shape[0], k, int(mode), int(self_base), idx.data_ptr(), dist.data_ptr(),
-                                          _stream_handle(stream)), "ccmp_roadmap_knn")
+        K = kind_of(queries)
+        q = K.expect(queries, "float64", (None, cols), "queries")
+        idx, dist = K.empty((len(q), k), "int32"), K.empty((len(q), k), "float64")
+        K.call("ccmp_roadmap_knn", "ccmp_roadmap_knn_host", self._h, int(metric), K.arg(q), len(q), k, int(mode), int(self_base), K.arg(idx), K.arg(dist),
+               stream=stream)
         return idx, dist
 
     def connect(self, query_joints, k, metric=METRIC_OBJECT, query_poses=None, mode=0, self_base=0, check_target=True, max_states=64,
@@ -243,26 +209,13 @@ class Roadmap:
         query_joints[q], exactly as `KinematicChainConstraint.connect_batch` runs its edges; the same dict comes back.
         METRIC_OBJECT ranks on `query_poses`, or on the poses derived from `query_joints` when they are None."""
         Q, k, ms = len(query_joints), int(k), int(max_states)
-        E = Q * k
-        shapes = {"nbr_idx": ((Q, k), "int32"), "nbr_dist": ((Q, k), "float64"), "states": ((E, ms, 14), "float64"), "n_states": ((E,), "int32"),
-                  "ok": ((E,), "uint8"), "newton_iters": ((E,), "int32"), "blocked": ((E,), "uint8"), "carry": ((E, 2), "float64")}
-        order = ["nbr_idx", "nbr_dist", "states", "n_states", "ok", "newton_iters", "blocked", "carry"]
-        head = (self._h, self._problem(), scene._h if scene is not None else None, float(margin) if scene is not None else 0.0, int(metric))
-        tail = (Q, k, int(mode), int(self_base), 1 if check_target else 0, ms, int(round_budget))
-        if isinstance(query_joints, np.ndarray):
-            qj = _host(query_joints, 14)
-            qp = _host(query_poses, 8) if query_poses is not None else None
-            out = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()}
-            ptr = lambda n: out[n].ctypes.data_as({"int32": C.POINTER(C.c_int32), "float64": _dp, "uint8": C.POINTER(C.c_uint8)}[shapes[n][1]])
-            check(_lib.lib().ccmp_roadmap_connect_host(*head, qj.ctypes.data_as(_dp), qp.ctypes.data_as(_dp) if qp is not None else None, *tail,
-                                                       *[ptr(n) for n in order]), "ccmp_roadmap_connect_host")
-            return out
-        torch = _torch()
-        qj = _dev(query_joints, 14)
-        qp = _dev(query_poses, 8) if query_poses is not None else None
-        out = {n: torch.empty(s, dtype=getattr(torch, d), device=qj.device) for n, (s, d) in shapes.items()}
-        check(_lib.lib().ccmp_roadmap_connect(*head, qj.data_ptr(), qp.data_ptr() if qp is not None else None, *tail,
-                                              *[out[n].data_ptr() for n in order], _stream_handle(stream)), "ccmp_roadmap_connect")
+        K = kind_of(query_joints)
+        qj = K.expect(query_joints, "float64", (None, 14), "query_joints")
+        qp = K.expect(query_poses, "float64", (None, 8), "query_poses") if query_poses is not None else None
+        out = {"nbr_idx": K.empty((Q, k), "int32"), "nbr_dist": K.empty((Q, k), "float64"), **_edge_outputs(K, Q * k, ms)}  # in the order the library takes them
+        K.call("ccmp_roadmap_connect", "ccmp_roadmap_connect_host", self._h, self._problem(), scene._h if scene is not None else None,
+               float(margin) if scene is not None else 0.0, int(metric), K.arg(qj), K.arg(qp), Q, k, int(mode), int(self_base), 1 if check_target else 0, ms,
+               int(round_budget), *[K.arg(a) for a in out.values()], stream=stream)
         return out
 
     def grow(self, query_poses, k, mode=0, self_base=0, rng_seed=0, first_index=0, opts=None, check_target=False, max_states=64, round_budget=0,
@@ -274,34 +227,18 @@ class Roadmap:
         empty slots.  Nothing is appended: the reference adds the vertex only after an edge succeeded.
         vet=True with a scene: ccmp_roadmap_grow_vetted — the IK vets its candidates and the assembled state against the scene under the
         same margin as the traversals (IKValid inside sampleCalibGoal, on proxies), and the dict also holds ik_clearance (Q,)."""
-        from .ik import ik_options
-
         Q, k, ms = len(query_poses), int(k), int(max_states)
-        E = Q * k
         opts = opts if opts is not None else ik_options()
         vet = bool(vet) and scene is not None
-        shapes = {"nbr_idx": ((Q, k), "int32"), "nbr_dist": ((Q, k), "float64"), "q_new": ((Q, 14), "float64"), "ik_ok": ((Q,), "uint8"),
-                  "ik_which": ((Q,), "int32")}
-        if vet:
-            shapes["ik_clearance"] = ((Q,), "float64")
-        shapes.update({"states": ((E, ms, 14), "float64"), "n_states": ((E,), "int32"), "ok": ((E,), "uint8"),
-                       "newton_iters": ((E,), "int32"), "blocked": ((E,), "uint8"), "carry": ((E, 2), "float64")})
-        order = list(shapes)
-        L = _lib.lib()
-        grow_host, grow_dev = (L.ccmp_roadmap_grow_vetted_host, L.ccmp_roadmap_grow_vetted) if vet else (L.ccmp_roadmap_grow_host, L.ccmp_roadmap_grow)
-        what = "ccmp_roadmap_grow_vetted" if vet else "ccmp_roadmap_grow"
-        head = (self._h, self._problem(), scene._h if scene is not None else None, float(margin) if scene is not None else 0.0, C.byref(opts))
-        tail = (Q, k, int(mode), int(self_base), int(rng_seed), int(first_index), 1 if check_target else 0, ms, int(round_budget))
-        if isinstance(query_poses, np.ndarray):
-            qp = _host(query_poses, 8)
-            out = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()}
-            ptr = lambda n: out[n].ctypes.data_as({"int32": C.POINTER(C.c_int32), "float64": _dp, "uint8": C.POINTER(C.c_uint8)}[shapes[n][1]])
-            check(grow_host(*head, qp.ctypes.data_as(_dp), *tail, *[ptr(n) for n in order]), what + "_host")
-            return out
-        torch = _torch()
-        qp = _dev(query_poses, 8)
-        out = {n: torch.empty(s, dtype=getattr(torch, d), device=qp.device) for n, (s, d) in shapes.items()}
-        check(grow_dev(*head, qp.data_ptr(), *tail, *[out[n].data_ptr() for n in order], _stream_handle(stream)), what)
+        K = kind_of(query_poses)
+        qp = K.expect(query_poses, "float64", (None, 8), "query_poses")
+        out = {"nbr_idx": K.empty((Q, k), "int32"), "nbr_dist": K.empty((Q, k), "float64"), "q_new": K.empty((Q, 14), "float64"), "ik_ok": K.empty((Q,), "uint8"),
+               "ik_which": K.empty((Q,), "int32"), **({"ik_clearance": K.empty((Q,), "float64")} if vet else {}),
+               **_edge_outputs(K, Q * k, ms)}  # in the order the library takes them
+        entries = ("ccmp_roadmap_grow_vetted", "ccmp_roadmap_grow_vetted_host") if vet else ("ccmp_roadmap_grow", "ccmp_roadmap_grow_host")
+        K.call(*entries, self._h, self._problem(), scene._h if scene is not None else None, float(margin) if scene is not None else 0.0, C.byref(opts),
+               K.arg(qp), Q, k, int(mode), int(self_base), int(rng_seed), int(first_index), 1 if check_target else 0, ms, int(round_budget),
+               *[K.arg(a) for a in out.values()], stream=stream)
         return out
 
     def grow_toward(self, checker, from_poses, goal_pose, k, t=0.3, sigma=0.2, lo=None, hi=None, attempts=2, rng_seed=0, first_index=0, inflate=0.0,
@@ -312,8 +249,6 @@ class Roadmap:
         needs that decision on the host anyway.  Returns `grow`'s dict over the kept poses plus "which" (G,), "rows" (the grow index g of
         every row of the other entries) and "poses" (the kept poses); rng_seed and first_index serve both the draw and the IK restarts
         (row r of `grow` uses first_index + r); grow_args go to `grow`."""
-        from .object import DEFAULT_HI, DEFAULT_LO
-
         prop = checker.propose(from_poses, goal_pose, t=t, sigma=sigma, lo=DEFAULT_LO if lo is None else lo, hi=DEFAULT_HI if hi is None else hi,
                                attempts=attempts, rng_seed=rng_seed, first_index=first_index, inflate=inflate)
         which = prop["which"]
@@ -342,47 +277,13 @@ class Roadmap:
         read-back), not capturable.  max_states: the traversal's list length (n_states beyond it = unsettled); taken from `states` when
         those are given."""
         nv, ne = C.c_size_t(), C.c_size_t()
-        no_states = _NO_LIMIT if max_states is None else int(max_states)
-        goal = None
-        if goal_pose is not None:
-            goal = np.zeros(8)
-            goal[:7] = np.asarray(goal_pose.cpu() if hasattr(goal_pose, "cpu") else goal_pose, dtype=np.float64).reshape(-1)[:7]
-        rt = _np(list(roots), np.int32, -1)
-        if isinstance(nbr_idx, np.ndarray):
-            nbr, ok, ns, st, nj, npo, vok, goal, rt, Q, k = _commit_inputs(nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots)
-            out = {"new_index": np.empty(Q, dtype=np.int32), "mid_index": np.empty((Q, k), dtype=np.int32), "grow_state": np.empty(Q, dtype=np.int32)}
-            check(_lib.lib().ccmp_roadmap_commit_host(self._h, self._problem() if (st is not None and goal is not None) else None, _ptr(nbr, _i32p), _ptr(ok, _u8p),
-                                                      _ptr(ns, _i32p), _ptr(st, _dp), st.shape[1] if st is not None else no_states, _ptr(nj, _dp), _ptr(npo, _dp),
-                                                      _ptr(vok, _u8p), Q, k, _ptr(goal, _dp), _ptr(rt, _i32p), len(rt), int(flags), _ptr(out["new_index"], _i32p),
-                                                      _ptr(out["mid_index"], _i32p), _ptr(out["grow_state"], _i32p), C.byref(nv), C.byref(ne)),
-                  "ccmp_roadmap_commit_host")
-        else:
-            torch = _torch()
-            if nbr_idx.dim() != 2 or nbr_idx.dtype != torch.int32 or not nbr_idx.is_contiguous():
-                raise ValueError("nbr_idx: a contiguous (Q, k) int32 tensor")
-            Q, k = nbr_idx.shape
-            S = Q * k
-
-            def dev(t, dtype, numel):
-                if t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or t.numel() != numel:
-                    raise ValueError("expected a contiguous %s tensor of %d elements on the device" % (dtype, numel))
-                return t
-
-            ok, ns = dev(edge_ok, torch.uint8, S), dev(n_states, torch.int32, S)
-            ms = no_states
-            if states is not None:
-                ms = states.numel() // (S * 14) if S else 1
-                dev(states, torch.float64, S * ms * 14)
-            nj, npo = _dev(new_joints, 14), _dev(new_poses, 8)
-            if vertex_ok is not None:
-                dev(vertex_ok, torch.uint8, Q)
-            out = {"new_index": torch.empty(Q, dtype=torch.int32, device=nbr_idx.device), "mid_index": torch.empty((Q, k), dtype=torch.int32, device=nbr_idx.device),
-                   "grow_state": torch.empty(Q, dtype=torch.int32, device=nbr_idx.device)}
-            check(_lib.lib().ccmp_roadmap_commit(self._h, self._problem() if (states is not None and goal is not None) else None, nbr_idx.data_ptr(), ok.data_ptr(),
-                                                 ns.data_ptr(), states.data_ptr() if states is not None else None, ms, nj.data_ptr(), npo.data_ptr(),
-                                                 vertex_ok.data_ptr() if vertex_ok is not None else None, Q, k, _ptr(goal, _dp), _ptr(rt, _i32p), len(rt), int(flags),
-                                                 out["new_index"].data_ptr(), out["mid_index"].data_ptr(), out["grow_state"].data_ptr(), C.byref(nv), C.byref(ne),
-                                                 _stream_handle(stream)), "ccmp_roadmap_commit")
+        K = kind_of(nbr_idx)
+        nbr, ok, ns, st, nj, npo, vok, goal, rt, ms, Q, k = _commit_inputs(K, nbr_idx, edge_ok, n_states, new_joints, new_poses, states, vertex_ok, goal_pose, roots,
+                                                                           max_states)
+        out = {"new_index": K.empty(Q, "int32"), "mid_index": K.empty((Q, k), "int32"), "grow_state": K.empty(Q, "int32")}
+        K.call("ccmp_roadmap_commit", "ccmp_roadmap_commit_host", self._h, self._problem() if (st is not None and goal is not None) else None, K.arg(nbr), K.arg(ok),
+               K.arg(ns), K.arg(st), ms, K.arg(nj), K.arg(npo), K.arg(vok), Q, k, _arg(goal), _arg(rt), len(rt), int(flags), *[K.arg(a) for a in out.values()],
+               C.byref(nv), C.byref(ne), stream=stream)
         out.update(vertices_added=int(nv.value), edges_added=int(ne.value))
         return out
 
@@ -391,12 +292,10 @@ class Roadmap:
         updated.  numpy: an endpoint out of range or u == v raises (CCMP_EINVAL), returns 0; a device tensor: such edges are skipped and
         their number is returned."""
         if isinstance(uv, np.ndarray):
-            a = _np(uv, np.int32).reshape(-1, 2)
-            check(_lib.lib().ccmp_roadmap_add_edges_host(self._h, _ptr(a, _i32p), len(a)), "ccmp_roadmap_add_edges_host")
+            a = HOST.expect(uv, "int32", -1, "uv").reshape(-1, 2)
+            check(_lib.lib().ccmp_roadmap_add_edges_host(self._h, _arg(a), len(a)), "ccmp_roadmap_add_edges_host")
             return 0
-        torch = _torch()
-        if uv.dtype != torch.int32 or uv.dim() != 2 or uv.shape[1] != 2 or not uv.is_contiguous() or not uv.is_cuda:
-            raise ValueError("expected a contiguous (E, 2) int32 tensor on the device")
+        uv = kind_of(uv).expect(uv, "int32", (None, 2), "uv")
         rej = C.c_size_t()
         check(_lib.lib().ccmp_roadmap_add_edges(self._h, uv.data_ptr(), uv.shape[0], C.byref(rej), _stream_handle(stream)), "ccmp_roadmap_add_edges")
         return int(rej.value)
@@ -409,26 +308,17 @@ class Roadmap:
         """(uv (count,2) int32, w (count,) float64) of the edges first ... in insertion order (the path search itself is `shortest_paths`);
         device tensors, or numpy arrays with host=True"""
         count = self.num_edges - int(first) if count is None else int(count)
-        if host:
-            uv, w = np.empty((count, 2), dtype=np.int32), np.empty(count)
-            check(_lib.lib().ccmp_roadmap_read_edges_host(self._h, int(first), count, _ptr(uv, _i32p), _ptr(w, _dp)), "ccmp_roadmap_read_edges_host")
-            return uv, w
-        torch = _torch()
-        dev = torch.device("cuda", self.ctx.device)
-        uv, w = torch.empty((count, 2), dtype=torch.int32, device=dev), torch.empty(count, dtype=torch.float64, device=dev)
-        check(_lib.lib().ccmp_roadmap_read_edges(self._h, int(first), count, uv.data_ptr(), w.data_ptr(), _stream_handle(stream)), "ccmp_roadmap_read_edges")
+        K = kind_on(self.ctx, host)
+        uv, w = K.empty((count, 2), "int32"), K.empty(count, "float64")
+        K.call("ccmp_roadmap_read_edges", "ccmp_roadmap_read_edges_host", self._h, int(first), count, K.arg(uv), K.arg(w), stream=stream)
         return uv, w
 
     def labels(self, first=0, count=None, host=False, stream=None):
         """labels (count,) int32: label[v] = the smallest vertex index of v's connected component"""
         count = len(self) - int(first) if count is None else int(count)
-        if host:
-            lab = np.empty(count, dtype=np.int32)
-            check(_lib.lib().ccmp_roadmap_read_labels_host(self._h, int(first), count, _ptr(lab, _i32p)), "ccmp_roadmap_read_labels_host")
-            return lab
-        torch = _torch()
-        lab = torch.empty(count, dtype=torch.int32, device=torch.device("cuda", self.ctx.device))
-        check(_lib.lib().ccmp_roadmap_read_labels(self._h, int(first), count, lab.data_ptr(), _stream_handle(stream)), "ccmp_roadmap_read_labels")
+        K = kind_on(self.ctx, host)
+        lab = K.empty(count, "int32")
+        K.call("ccmp_roadmap_read_labels", "ccmp_roadmap_read_labels_host", self._h, int(first), count, K.arg(lab), stream=stream)
         return lab
 
     def closest(self, froms, target_pose, stream=None):
@@ -436,24 +326,16 @@ class Roadmap:
         with the smallest (pose distance to target_pose, index): (idx (F,), dist (F,), from_dist (F,)), from_dist = the distance of
         `from` itself.  A NaN distance is never a candidate.  numpy in, numpy out (synchronous); device tensors in (target_pose (8,)),
         device tensors out, asynchronous and capturable."""
-        if isinstance(froms, np.ndarray):
-            fr = _np(froms, np.int32, -1)
-            tgt = np.zeros(8)
-            tgt[:7] = np.asarray(target_pose, dtype=np.float64).reshape(-1)[:7]
-            idx, dist, fd = np.empty(len(fr), dtype=np.int32), np.empty(len(fr)), np.empty(len(fr))
-            check(_lib.lib().ccmp_roadmap_closest_host(self._h, _ptr(fr, _i32p), len(fr), _ptr(tgt, _dp), _ptr(idx, _i32p), _ptr(dist, _dp), _ptr(fd, _dp)),
-                  "ccmp_roadmap_closest_host")
-            return idx, dist, fd
-        torch = _torch()
-        if froms.dtype != torch.int32 or froms.dim() != 1 or not froms.is_contiguous() or not froms.is_cuda:
-            raise ValueError("expected a contiguous (F,) int32 tensor on the device")
-        if target_pose.dtype != torch.float64 or target_pose.numel() < 7 or not target_pose.is_contiguous() or not target_pose.is_cuda:
-            raise ValueError("expected a contiguous float64 pose on the device")
-        F = froms.shape[0]
-        idx = torch.empty(F, dtype=torch.int32, device=froms.device)
-        dist, fd = torch.empty(F, dtype=torch.float64, device=froms.device), torch.empty(F, dtype=torch.float64, device=froms.device)
-        check(_lib.lib().ccmp_roadmap_closest(self._h, froms.data_ptr(), F, target_pose.data_ptr(), idx.data_ptr(), dist.data_ptr(), fd.data_ptr(),
-                                              _stream_handle(stream)), "ccmp_roadmap_closest")
+        K = kind_of(froms)
+        if K is HOST:  # any shape of indices and any pose of seven numbers or more, padded here
+            fr, tgt = K.expect(froms, "int32", -1, "froms"), _pose8(target_pose)
+        else:
+            fr, tgt = K.expect(froms, "int32", (None,), "froms"), K.expect(target_pose, "float64", -1, "target_pose")
+            if tgt.numel() < 7:
+                raise ValueError("target_pose: a pose of seven numbers or more")
+        F = len(fr)
+        idx, dist, fd = K.empty(F, "int32"), K.empty(F, "float64"), K.empty(F, "float64")
+        K.call("ccmp_roadmap_closest", "ccmp_roadmap_closest_host", self._h, K.arg(fr), F, K.arg(tgt), K.arg(idx), K.arg(dist), K.arg(fd), stream=stream)
         return idx, dist, fd
 
     def closest_from_goal(self, froms, to):
@@ -486,51 +368,29 @@ class Roadmap:
         rows of f are the path, start first), L = the buffer's length: max_len, or the longest path when one did not fit — the call is
         then made once more with that length.  Device tensors (src / dst may be given as such: int32, on the device), or numpy arrays
         with host=True (the synchronous host form; an index outside the store raises).  full=True adds dist (F,N) and pred (F,N)."""
-        L = _lib.lib()
         N = len(self)
-        if host:
-            sr, ds = _np(src.cpu() if hasattr(src, "cpu") else src, np.int32, -1), _np(dst.cpu() if hasattr(dst, "cpu") else dst, np.int32, -1)
-            F = len(sr)
-            for ml in (int(max_len), None):
-                if ml is None:
-                    ml = int(out["path_len"].max())
-                out = {"cost": np.empty(F), "path_len": np.empty(F, dtype=np.int32), "path": np.full((F, ml), -1, dtype=np.int32),
-                       "joints": np.full((F, ml, 14), np.nan), "poses": np.full((F, ml, 8), np.nan)}
-                if full:
-                    out.update(dist=np.empty((F, N)), pred=np.empty((F, N), dtype=np.int32))
-                check(L.ccmp_roadmap_shortest_paths_host(self._h, _ptr(sr, _i32p), _ptr(ds, _i32p), F, ml, _ptr(out["cost"], _dp), _ptr(out["path_len"], _i32p),
-                                                         _ptr(out["path"], _i32p), _ptr(out["joints"], _dp), _ptr(out["poses"], _dp), _ptr(out.get("dist"), _dp),
-                                                         _ptr(out.get("pred"), _i32p)), "ccmp_roadmap_shortest_paths_host")
-                if F == 0 or int(out["path_len"].max()) <= ml:
-                    break
-            return out
-        torch = _torch()
-        dev = torch.device("cuda", self.ctx.device)
+        K = kind_on(self.ctx, host)
 
         def pairs(a):
-            if isinstance(a, torch.Tensor):
-                if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous() or not a.is_cuda:
-                    raise ValueError("expected a contiguous (F,) int32 tensor on the device")
-                return a
-            return torch.from_numpy(np.array(a, dtype=np.int32).reshape(-1)).to(dev)
+            if host:  # from wherever they are
+                return K.expect(a.cpu() if hasattr(a, "cpu") else a, "int32", -1, "src / dst")
+            if not hasattr(a, "data_ptr"):
+                a = _torch().from_numpy(np.array(a, dtype=np.int32).reshape(-1)).to(K.device)
+            return K.expect(a, "int32", (None,), "src / dst")
 
         sr, ds = pairs(src), pairs(dst)
-        F = sr.shape[0]
-        if ds.shape[0] != F:
+        F = len(sr)
+        if not host and len(ds) != F:
             raise ValueError("src and dst are (F,) each")
+        nan = float("nan")
         for ml in (int(max_len), None):
             if ml is None:
                 ml = longest
-            out = {"cost": torch.empty(F, dtype=torch.float64, device=dev), "path_len": torch.empty(F, dtype=torch.int32, device=dev),
-                   "path": torch.full((F, ml), -1, dtype=torch.int32, device=dev), "joints": torch.full((F, ml, 14), float("nan"), dtype=torch.float64, device=dev),
-                   "poses": torch.full((F, ml, 8), float("nan"), dtype=torch.float64, device=dev)}
-            if full:
-                out.update(dist=torch.empty((F, N), dtype=torch.float64, device=dev), pred=torch.empty((F, N), dtype=torch.int32, device=dev))
-            check(L.ccmp_roadmap_shortest_paths(self._h, sr.data_ptr(), ds.data_ptr(), F, ml, out["cost"].data_ptr(), out["path_len"].data_ptr(),
-                                                out["path"].data_ptr(), out["joints"].data_ptr(), out["poses"].data_ptr(),
-                                                out["dist"].data_ptr() if full else None, out["pred"].data_ptr() if full else None, _stream_handle(stream)),
-                  "ccmp_roadmap_shortest_paths")
-            longest = int(out["path_len"].max()) if F else 0  # the one host read: did every path fit
+            out = {"cost": K.empty(F, "float64"), "path_len": K.empty(F, "int32"), "path": K.full((F, ml), "int32", -1), "joints": K.full((F, ml, 14), "float64", nan),
+                   "poses": K.full((F, ml, 8), "float64", nan), **({"dist": K.empty((F, N), "float64"), "pred": K.empty((F, N), "int32")} if full else {})}
+            K.call("ccmp_roadmap_shortest_paths", "ccmp_roadmap_shortest_paths_host", self._h, K.arg(sr), K.arg(ds), F, ml,
+                   *[K.arg(out.get(n)) for n in ("cost", "path_len", "path", "joints", "poses", "dist", "pred")], stream=stream)
+            longest = int(out["path_len"].max()) if F else 0  # the device form's one host read: did every path fit
             if longest <= ml:
                 break
         return out
@@ -538,7 +398,7 @@ class Roadmap:
     def path_rounds(self, F):
         """(F,2) int32: the relaxation and hop rounds the last `shortest_paths` call took for each of its first F pairs; a diagnostic"""
         r = np.empty((int(F), 2), dtype=np.int32)
-        check(_lib.lib().ccmp_roadmap_path_rounds_host(self._h, int(F), _ptr(r, _i32p)), "ccmp_roadmap_path_rounds_host")
+        check(_lib.lib().ccmp_roadmap_path_rounds_host(self._h, int(F), _arg(r)), "ccmp_roadmap_path_rounds_host")
         return r
 
     def solution(self, starts, goals, max_len=64):
@@ -570,9 +430,7 @@ class Roadmap:
         starts = [int(s) for s in starts]
         if not starts:
             return None
-        tgt = np.zeros(8)
-        tgt[:7] = np.asarray(goal_pose.cpu() if hasattr(goal_pose, "cpu") else goal_pose, dtype=np.float64).reshape(-1)[:7]
-        idx, dist, _ = self.closest(np.array(starts, dtype=np.int32), tgt)
+        idx, dist, _ = self.closest(np.array(starts, dtype=np.int32), _pose8(goal_pose))
         if not (idx >= 0).any():
             return None
         i = int(np.argmin(np.where(idx >= 0, dist, np.inf)))

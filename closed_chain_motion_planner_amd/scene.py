@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._arrays import HOST, _stream_handle, kind_of
 from ._lib import CcmpBox, CcmpSphere, check
 
 __all__ = ["FRAME_WORLD", "frame", "ProxyScene", "ProxyValidityChecker", "skeleton_spheres", "default_allowed", "allow",
@@ -139,9 +140,8 @@ def arm_clearance_ref(problem, spheres, boxes, allowed, arm, q7, margin=0.0):
     q = q.reshape(-1, 7)
     B = q.shape[0]
     clr, free = np.empty(B), np.empty(B, dtype=np.uint8)
-    dp = C.POINTER(C.c_double)
-    check(_lib.lib().ccmp_arm_clearance_ref(C.byref(problem), *scene_arrays(spheres, boxes, allowed), int(arm), q.ctypes.data_as(dp), B, float(margin),
-                                            clr.ctypes.data_as(dp), free.ctypes.data_as(C.POINTER(C.c_uint8))), "ccmp_arm_clearance_ref")
+    check(_lib.lib().ccmp_arm_clearance_ref(C.byref(problem), *scene_arrays(spheres, boxes, allowed), int(arm), HOST.arg(q), B, float(margin), HOST.arg(clr),
+                                            HOST.arg(free)), "ccmp_arm_clearance_ref")
     return (float(clr[0]), bool(free[0])) if single else (clr, free)
 
 
@@ -174,8 +174,6 @@ class ProxyScene:
         free = (ok is None or ok) & (clearance > margin): feed it to compact_valid behind a projection"""
         import torch
 
-        from .constraint import _stream_handle
-
         c = self.constraint
         c._need_problem()
         c._check_q(q)
@@ -200,10 +198,8 @@ class ProxyScene:
         clr = np.empty(B)
         pair = np.empty(B, dtype=np.int32)
         free = np.empty(B, dtype=np.uint8)
-        check(_lib.lib().ccmp_clearance_host(c.ctx.handle, C.byref(c.problem), self._h, q.ctypes.data_as(C.POINTER(C.c_double)), B,
-                                             float(margin), clr.ctypes.data_as(C.POINTER(C.c_double)),
-                                             pair.ctypes.data_as(C.POINTER(C.c_int32)), free.ctypes.data_as(C.POINTER(C.c_uint8))),
-              "ccmp_clearance_host")
+        check(_lib.lib().ccmp_clearance_host(c.ctx.handle, C.byref(c.problem), self._h, HOST.arg(q), B, float(margin), HOST.arg(clr), HOST.arg(pair),
+                                             HOST.arg(free)), "ccmp_clearance_host")
         if single:
             return float(clr[0]), int(pair[0]), bool(free[0])
         return clr, pair, free
@@ -214,28 +210,14 @@ class ProxyScene:
         a numpy array (7,) or (B,7) -> numpy through the host form (scalars for one row)"""
         c = self.constraint
         c._need_problem()
-        if isinstance(q7, np.ndarray) or not hasattr(q7, "data_ptr"):
-            q = np.ascontiguousarray(q7, dtype=np.float64)
-            single = q.ndim == 1
-            q = q.reshape(-1, 7)
-            B = q.shape[0]
-            clr, free = np.empty(B), np.empty(B, dtype=np.uint8)
-            dp = C.POINTER(C.c_double)
-            check(_lib.lib().ccmp_arm_clearance_host(c.ctx.handle, C.byref(c.problem), self._h, int(arm), q.ctypes.data_as(dp), B, float(margin),
-                                                     clr.ctypes.data_as(dp), free.ctypes.data_as(C.POINTER(C.c_uint8))), "ccmp_arm_clearance_host")
-            return (float(clr[0]), bool(free[0])) if single else (clr, free)
-        import torch
-
-        from .constraint import _stream_handle
-
-        if not (q7.is_cuda and q7.dtype == torch.float64 and q7.is_contiguous() and q7.ndim == 2 and q7.shape[1] == 7):
-            raise ValueError("q7: expected a contiguous (B, 7) float64 tensor on the device")
-        B = q7.shape[0]
-        clr = torch.empty(B, dtype=torch.float64, device=q7.device)
-        free = torch.empty(B, dtype=torch.uint8, device=q7.device)
-        check(_lib.lib().ccmp_arm_clearance_batch(c.ctx.handle, C.byref(c.problem), self._h, int(arm), q7.data_ptr(), B, float(margin), clr.data_ptr(),
-                                                  free.data_ptr(), _stream_handle(stream)), "ccmp_arm_clearance_batch")
-        return clr, free
+        K = kind_of(q7) if hasattr(q7, "data_ptr") else HOST  # anything that is no tensor is the host's
+        single = K is HOST and np.ndim(q7) == 1
+        q = K.expect(q7, "float64", -1, "q7").reshape(-1, 7) if K is HOST else K.expect(q7, "float64", (None, 7), "q7 (B, 7)")
+        B = len(q)
+        clr, free = K.empty(B, "float64"), K.empty(B, "uint8")
+        K.call("ccmp_arm_clearance_batch", "ccmp_arm_clearance_host", c.ctx.handle, C.byref(c.problem), self._h, int(arm), K.arg(q), B, float(margin), K.arg(clr),
+               K.arg(free), stream=stream)
+        return (float(clr[0]), bool(free[0])) if single else (clr, free)
 
     def arm_clearance_ref(self, arm, q7, margin=0.0):
         """the same on the host, no device (ccmp_arm_clearance_ref on this scene's own arrays)"""

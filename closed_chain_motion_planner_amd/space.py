@@ -9,14 +9,10 @@ import threading
 
 import numpy as np
 
+from ._arrays import _torch
+
 __all__ = ["jy_ProjectedStateSampler", "jy_ProjectedStateSpace", "check_motion", "geodesic_interpolate", "format_path_matrix",
            "parse_path_matrix", "format_graphml", "parse_graphml", "format_graphviz", "splitmix64", "next_sampler_seed"]
-
-
-def _torch():
-    import torch
-
-    return torch
 
 
 _M64 = (1 << 64) - 1

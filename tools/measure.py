@@ -19,6 +19,8 @@
     python tools/measure.py scout                           FP32 scout's predictions against the true iteration counts
     python tools/measure.py roadmap [reps]                  the device-resident roadmap store: host-form single-query k-NN against ccmp_knn_host, the object
                                                            metric's many-query kernel against the joint metric's (k = 5 and 16), appends, pose derivation
+    python tools/measure.py mirror [calls] [warm]           host wall time of the Python mirror's own wrappers in the planner's per-vertex loop (numpy append,
+                                                           nearest_k and read, device connect) on a store of 1 024 vertices: median of `calls` calls, one JSON line
     python tools/measure.py connect [reps]                  the connection step: ccmp_knn_batch against FP64 torch distances + torch.topk (throughput shape and
                                                            single queries), ccmp_connect_batch against torch k-NN + gather + ccmp_geodesic_batch_ex, both
                                                            contenders alternating in one process, device events, medians with their spread
@@ -756,6 +758,48 @@ def roadmap(argv):
     t = alternate({"append of 262144 rows (copy + pose_from_joints)": lambda: (bulk.truncate(0), bulk.append(many))}, reps)
     show("pose derivation (device events)", t)
     print("VERDICT host-form k-NN on the resident store: " + ("not slower" if all(verdict) else "SLOWER in at least one case"))
+
+
+def mirror(argv):
+    """host wall time per call of the mirror's own wrappers in the planner's per-vertex loop, on a store of 1 024 vertices: the numpy
+    forms of append (one vertex, truncated again outside the clock), nearest_k (Q = 1, k = 5) and read (one row), the device form of
+    connect (Q = 1, k = 5; the clock stops when the call returns, the stream is drained outside it).  `warm` rounds of all four, then the
+    median of `calls` calls each, one JSON line.  Run from the root of the tree to be measured; CCMP_LIBRARY names the library."""
+    import json
+
+    from closed_chain_motion_planner_amd import Roadmap
+
+    calls, warm = (int(argv[0]) if argv else 2000), (int(argv[1]) if len(argv) > 1 else 200)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=Context(0))
+    q = valid_states(c, 1024 + 1)
+    rm = Roadmap(c, 2048)
+    rm.append(q[:1024])
+    one_d = q[1024:].contiguous()
+    one = one_d.cpu().numpy()
+    pose = rm.read(5, 1, host=True)[1]
+
+    def append():
+        rm.append(one)
+
+    fns = {"append (numpy, 1 vertex)": (append, lambda: rm.truncate(1024)), "nearest_k (numpy, Q=1, k=5)": (lambda: rm.nearest_k(pose, 5), None),
+           "read (host=True, 1 row)": (lambda: rm.read(7, 1, host=True), None),
+           "connect (device, Q=1, k=5)": (lambda: rm.connect(one_d, 5, max_states=16), torch.cuda.synchronize)}
+    for _ in range(warm):
+        for fn, after in fns.values():
+            fn()
+            if after:
+                after()
+    out = {}
+    for name, (fn, after) in fns.items():
+        us = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            fn()
+            us.append((time.perf_counter() - t0) * 1e6)
+            if after:
+                after()
+        out[name] = round(float(np.median(us)), 2)
+    print("MIRROR_US " + json.dumps({"calls": calls, "warmup_rounds": warm, "median_us": out}))
 
 
 def ik(argv):
@@ -1609,7 +1653,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, ik, graph, path, dense, shortcut, smooth, smooth_restate, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
