@@ -33,6 +33,11 @@ CLEAR_SEED = 0xA2C0
 PLAIN_SEED = 0xA2D0
 EXTEND_SEED = {(m, j): 0xA2E0 for m in MODELS for j in (0, 1)}
 PATH_SEED = {("tilted", 0): 0xB600, ("tilted", 1): 0xB600, ("calibrated", 0): 0xB0B8, ("calibrated", 1): 0xB0B8}
+# smoothing (test_gpu_arm_models_planner.test_smooth): the paths of waypoint_paths(.., F_PATHS, L_PATHS, SMOOTH_SEED), SMOOTH_STEPS passes,
+# a result of ccmp_smooth_len_after(L_PATHS, SMOOTH_STEPS) = 21 vertices per path
+# (PATH_SEED's paths do not serve: on them no candidate is refused or below min_change without a scene)
+SMOOTH_SEED = {("tilted", 0): 0xBA88, ("tilted", 1): 0xBA88, ("calibrated", 0): 0xB708, ("calibrated", 1): 0xB708}
+SMOOTH_STEPS, SMOOTH_CAP = 2, 21
 
 
 def tilt(c):

@@ -8,6 +8,8 @@ import arm_model_cases as A
 from conftest import NCPU, load_cfg
 from dense_path_cases import oracle_segments
 from shortcut_cases import oracle_pairs, pairs_py
+from smooth_cases import BELOW, PROJECTED, REFUSED, Restatement, mirror_fill, same_f64, scene_restatement
+from smooth_cases import expect as smooth_expect
 from test_gpu_geodesic_scene import OracleScene, _random_proxies
 from test_gpu_parity import _oracle_problem
 from test_gpu_scene import _states
@@ -149,3 +151,32 @@ def test_path_seed_gives_both_outcomes(oracle_det, model, mode):
         print("%s mode %d scene %d: seg_ok 1 / 0 = %d / %d, pair_ok 1 / 0 = %d / %d (blocked by the scene: %d), unreached behind a stored state: %d"
               % (model, mode, scene, seg[0], seg[1], pair[0], pair[1], blocked, zero_row))
         assert min(seg) >= 1 and min(pair) >= 1 and zero_row >= 1
+
+
+def smooth_facts(O, c, P, model, mode):
+    """(path_joints, path_len, margin, {scene: the restated result of the smooth test}, the restatement of the same input on the stock problem)"""
+    pj, pl = A.waypoint_paths(c, O, P, A.F_PATHS, A.L_PATHS, A.SMOOTH_SEED[(model, mode)])
+    sc = A.default_scene_host(c.problem)
+    margin = A.oracle_pick_margin(O, P, sc, *A.oracle_edges(O, P, A.E_SCENE, A.EXTEND_SEED[(model, mode)]), A.MS_SCENE)
+    fill = mirror_fill(pj, A.SMOOTH_CAP)
+    want = {scene: smooth_expect(scene_restatement(O, P, sc, margin) if scene else Restatement(O, P), pj, pl, A.SMOOTH_STEPS, 0.005, A.SMOOTH_CAP, fill)
+            for scene in (False, True)}
+    stock = smooth_expect(Restatement(O, _model(O, "stock", mode)[1]), pj, pl, A.SMOOTH_STEPS, 0.005, A.SMOOTH_CAP, fill)
+    return pj, pl, margin, want, stock
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("model", ["tilted", "calibrated"])
+def test_smooth_seed_gives_every_outcome(oracle_det, model, mode):
+    """without and with the default scene: a vertex moves, one is refused or below min_change, a midpoint is projected; the result is
+    not the stock problem's on the same input, and the scene changes it"""
+    c, P = _model(oracle_det, model, mode)
+    pj, pl, margin, want, stock = smooth_facts(oracle_det, c, P, model, mode)
+    assert pl.tolist() == [2, 3, A.L_PATHS, 1] and A.SMOOTH_CAP == 2 ** A.SMOOTH_STEPS * (A.L_PATHS - 1) + 1
+    for scene, w in want.items():
+        s = w["stats"].sum(axis=0)
+        print("%s mode %d scene %d (margin %.6f): moved %d, stats (projected, fallback, degenerate, refused, below) %s, stop %s, out_len %s"
+              % (model, mode, scene, margin, w["moved"].sum(), s.tolist(), w["stop"].tolist(), w["out_len"].tolist()))
+        assert w["moved"].sum() >= 1 and s[REFUSED] + s[BELOW] >= 1 and s[PROJECTED] >= 1
+        assert not same_f64(w["joints"], stock["joints"])
+    assert not same_f64(want[True]["joints"], want[False]["joints"])

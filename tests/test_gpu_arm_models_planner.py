@@ -1,6 +1,6 @@
-"""The planner-side steps — the plain analytic extend step, connect, grow and the store's poses, densify and shortcut (with and without a
-scene) — on arms that are not the stock model (tests/arm_model_cases.py: tilted, calibrated, calibrated_tilted).  Their own suites
-(test_gpu_connect.py, test_gpu_grow_store.py, test_gpu_pose_ik.py, test_gpu_dense.py, test_gpu_shortcut.py) run Wine_Bottle and the
+"""The planner-side steps — the plain analytic extend step, connect, grow and the store's poses, densify, shortcut and smooth (with and
+without a scene) — on arms that are not the stock model (tests/arm_model_cases.py: tilted, calibrated, calibrated_tilted).  Their own suites
+(test_gpu_connect.py, test_gpu_grow_store.py, test_gpu_pose_ik.py, test_gpu_dense.py, test_gpu_shortcut.py, test_gpu_smooth.py) run Wine_Bottle and the
 recorded files, which is the stock model; the continuation loops of these calls hand carry and round_budget to whichever extend kernel
 the model selects.  Bit for bit against the det oracle and against the composition of the entry points, uint64 views, NaN equal to NaN,
 no tolerance; sizes and seeds from arm_model_cases (the seeds chosen in tests/test_arm_model_cases.py on the oracle alone).  The table
@@ -16,7 +16,25 @@ Mutation check (the builds and the run are described there; none faulted or hung
                                                                    Newton totals of its eleven pairs stay)
   ccmp_kernels_scene.hip: likewise in clearance_kernel and         test_densify_and_shortcut[0-tilted-scene], [1-tilted-scene] (the margin and the
   clearance_state_kernel                                           clearance summary come from clearance_batch)
-The plain analytic extend step, grow and the store's poses run no code these mutations touch (ccmp_ik.cpp is out of their scope)."""
+The plain analytic extend step, grow and the store's poses run no code these mutations touch (ccmp_ik.cpp is out of their scope).
+
+test_smooth (smooth_paths, added after the units above): eight cases, 0.03 to 0.11 s each on the MI355X, 0.5 s together, of which the
+restatement takes 0.01 to 0.04 s per case.  Mutation check of test_smooth alone, scratch builds, one run each, all wrong answers, none a
+fault or a hang.  The world transform of the last two rows above is one text now (ccmp_scene_math.h: scene_base_to_world), so they are
+one mutant:
+  ccmp_kernels_geo_scene.hip: the launcher always takes            test_smooth[0-calibrated-scene]
+  CCMP_LAUNCH_GEO_SCENE(true)
+  ccmp_kernels_fast.hip: CCMP_LAUNCH_GEO_ROW16_SCENE always        test_smooth[1-tilted-scene]
+  takes DIAG = true
+  ccmp_scene_math.h: scene_base_to_world takes K.base_R[0]         test_smooth[0-tilted-scene], [1-tilted-scene]
+  for both arms
+  (test_smooth[*-plain] runs no scene kernel.)  The six mutants of csrc/ccmp_kernels_smooth.hip listed in tests/test_gpu_smooth_shapes.py:
+  the bracket's fallback row, the gather's pair_path and the dropped guard of the length sum fail all eight cases; where[0] for where[f]
+  in smooth_store_kernel or smooth_length_kernel fails the four scene cases (without a scene every active path of these four runs both
+  passes, so all lie in the same buffer); clear_m at the wrong segment fails none of them (tests/test_gpu_smooth_shapes.py::
+  test_scene_reads_the_incoming_midpoint holds that one)."""
+import time
+
 import numpy as np
 import pytest
 
@@ -25,6 +43,8 @@ from conftest import NCPU
 from dense_path_cases import bits, join, oracle_segments, same_paths
 from pose_ik_cases import pose_of
 from shortcut_cases import expect, oracle_pairs, pairs_py, same_selection
+from smooth_cases import BELOW, PROJECTED, REFUSED, Restatement, mirror_fill, same_result, scene_restatement
+from smooth_cases import expect as smooth_expect
 from test_gpu_analytic_extend import _same_lists
 from test_gpu_connect import _check_edges, _gathered, _np, _same_bits
 from test_gpu_geodesic_scene import OracleScene, _pick_margin
@@ -250,3 +270,34 @@ def test_densify_and_shortcut(gpu_ctx, oracle_det, mode, model, with_scene):
 
 def _np_all(out):
     return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("with_scene", [False, True], ids=["plain", "scene"])
+@pytest.mark.parametrize("model", ["tilted", "calibrated"])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_smooth(gpu_ctx, oracle_det, mode, model, with_scene):
+    """smooth_paths on the four synthetic paths of the model's own manifold, two passes for a result of 21 vertices: the pass loop hands
+    its own option struct to densify, the projector, the pair tests and clearance_batch, each of which chooses its kernel by the model.
+    The device form at the defaults and with lists of 2 at one state per call, and the host form, equal the restatement on the oracle
+    (with a scene: checkMotion behind the oracle's validity callback and the oracle's clearance of the midpoints and candidates)"""
+    from closed_chain_motion_planner_amd import smooth_len_after
+
+    assert smooth_len_after(A.L_PATHS, A.SMOOTH_STEPS) == A.SMOOTH_CAP
+    c = _constraint(A.OBJ, gpu_ctx, mode=mode)
+    with A.apply(c, gpu_ctx, model):
+        P = _oracle_problem(oracle_det, c)
+        pj, pl = A.waypoint_paths(c, oracle_det, P, A.F_PATHS, A.L_PATHS, A.SMOOTH_SEED[(model, mode)])
+        pj_d, pl_d = _dev(pj), _dev(pl)
+        sc, margin = _scene_and_margin(c, model, mode) if with_scene else (None, None)
+        kw = dict(max_steps=A.SMOOTH_STEPS, out_max_len=A.SMOOTH_CAP, scene=sc, margin=margin, stats=True)
+        got = [(c.smooth_paths(pj_d, pl_d, **kw), "device form"), (c.smooth_paths(pj_d, pl_d, chunk_states=2, round_budget=1, **kw), "lists of 2, one state per call"),
+               (c.smooth_paths(pj, pl, **kw), "host form")]
+    t = time.perf_counter()
+    R = scene_restatement(oracle_det, P, sc, margin) if with_scene else Restatement(oracle_det, P)
+    want = smooth_expect(R, pj, pl, A.SMOOTH_STEPS, 0.005, A.SMOOTH_CAP, mirror_fill(pj, A.SMOOTH_CAP))
+    s = want["stats"].sum(axis=0)
+    print("%s mode %d scene %d: moved %d, stats (projected, fallback, degenerate, refused, below) %s, stop %s; restated in %.2f s"
+          % (model, mode, with_scene, want["moved"].sum(), s.tolist(), want["stop"].tolist(), time.perf_counter() - t))
+    assert want["moved"].sum() >= 1 and s[REFUSED] + s[BELOW] >= 1 and s[PROJECTED] >= 1
+    for g, what in got:
+        same_result(g, want, (model, mode, with_scene, what))

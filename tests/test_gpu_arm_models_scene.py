@@ -20,6 +20,9 @@ What ran on no model but stock before, and the test that runs it now (planner: t
   connect_batch(scene=), Roadmap.connect / grow, densify_paths,        planner: test_connect_equals_its_parts_and_the_oracle,
   shortcut_paths on a non-stock model                                  test_grow_and_the_store, test_densify_and_shortcut
   analytic extend step (geodesic_row16_kernel) on calibrated arms      planner: test_plain_analytic_extend_on_calibrated_arms
+  smooth_paths on a non-stock model: the pass loop's own option        planner: test_smooth (tilted and calibrated, both modes, with and
+  struct handed to densify, the projector, the pair tests and          without a scene; the seeds: arm_model_cases.SMOOTH_SEED)
+  clearance_batch
 
 Mutation check: changes of arithmetic only (no barrier, loop bound or index depends on them) on scratch builds, one run of this module
 and of tests/test_gpu_arm_models_planner.py each; all gave wrong answers, none a fault or a hang.  What failed here (the planner
