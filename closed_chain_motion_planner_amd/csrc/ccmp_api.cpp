@@ -157,6 +157,7 @@ int ccmp_ctx_create(int device, ccmp_ctx **out)
   }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->join, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->gate, hipEventDisableTiming);
   if (e != hipSuccess) { ccmp_ctx_destroy(ctx); return hip_fail(e, "side stream / events"); }
   live_contexts(ctx, +1);
   *out = ctx;
@@ -177,6 +178,7 @@ void ccmp_ctx_destroy(ccmp_ctx *ctx)
   if (ctx->ik_vet_ws) (void)hipFree(ctx->ik_vet_ws);
   if (ctx->queue) (void)hipFree(ctx->queue);
   if (ctx->pool) (void)hipFree(ctx->pool);
+  if (ctx->fd_state) (void)hipFree(ctx->fd_state);
   if (ctx->lpt_buf) (void)hipFree(ctx->lpt_buf);
   if (ctx->scan) (void)hipFree(ctx->scan);
   if (ctx->stage) (void)hipFree(ctx->stage);
@@ -184,6 +186,7 @@ void ccmp_ctx_destroy(ccmp_ctx *ctx)
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
   if (ctx->fork) (void)hipEventDestroy(ctx->fork);
   if (ctx->join) (void)hipEventDestroy(ctx->join);
+  if (ctx->gate) (void)hipEventDestroy(ctx->gate);
   if (ctx->ev_shard) (void)hipEventDestroy(ctx->ev_shard);
   (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -288,6 +291,7 @@ int grow_buffer(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes)
 }  // extern "C++"
 static int grow(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes) { return ccmp_host::grow_buffer(ctx, buf, cap, n, bytes); }
 static int ensure_pool(ccmp_ctx *ctx, size_t records) { return grow(ctx, (void **)&ctx->pool, &ctx->pool_cap, records, records * kPoolEntry * sizeof(double)); }
+static int ensure_fd_state(ccmp_ctx *ctx, size_t B) { return grow(ctx, (void **)&ctx->fd_state, &ctx->fd_state_cap, B, B * kPoolEntry * sizeof(double)); }
 static int ensure_lpt_buffers(ccmp_ctx *ctx, size_t B) // pred u16 | hist 1024 x u32 | order u32 | flags u8 (bulk checkMotion)
 {
   return grow(ctx, &ctx->lpt_buf, &ctx->lpt_cap, B, ((B * 2 + 255) & ~(size_t)255) + 4096 + B * 4 + B);
@@ -348,6 +352,10 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
     int rc = ensure_pool(ctx, (size_t)pl.group_blocks * 10);
     if (rc != CCMP_OK) return rc;
   }
+  if (pl.head_rounds > 0) {
+    int rc = ensure_fd_state(ctx, B);
+    if (rc != CCMP_OK) return rc;
+  }
   unsigned long long *const q_pool_count = ctx->queue + kQPool, *const q_latency = ctx->queue + kQLatency;
   if (!pl.latency_static) HIP_TRY(ccmp_launch::clear_words(ctx->queue, 16, st)); // the projector's eight queue words
 
@@ -375,6 +383,44 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
   const unsigned int *order = ctx->order;
   const uint16_t *pred = nullptr;
   ForkJoin fj(ctx, st);
+  // Head and resume (ccmp_kernels_fd.hip: FdPart): every sample's first rounds, ten samples of one age per wavefront in index order,
+  // then the persistent kernel on the rows those left in ctx->fd_state.  The scout pass reads q_in alone and runs beside the head.  The
+  // head's workgroups keep every wavefront slot of the chip taken until its last generation, and a kernel dispatched behind them waits
+  // for wavefronts to retire one by one (the scout pass then ends 0.23 ms after the head; the sort's small kernels took 3 ms).  So the
+  // scout pass must be dispatched FIRST: it goes to the side stream, and the head waits for an event that the side stream records in
+  // front of the scout pass (`gate`) — one signal further away than the scout pass itself.  The scout takes two wavefronts per SIMD for
+  // its 0.34 ms and leaves the head the rest; the sort runs once both are done, in front of the resume launch.  (The orders this one
+  // was measured against — scout and sort in front, an ungated side stream, a side stream of lowest priority: DESIGN_experiments.md §5.6.)
+  // A call IN PLACE (q_out on q_in, include/ccmp.h) keeps the scout in front: the head writes back the samples that end within its
+  // rounds, and beside it the scout pass would read rows that are being overwritten — the order would still be a permutation and the
+  // results the same bits, but the schedule would differ from run to run.
+  if (pl.head_rounds > 0) {
+    const int head_blocks = (int)((B + 9) / 10);
+    const bool in_place = mode == 0 && q_in < q_out + B * 14 && q_out < q_in + B * 14;
+    if (pl.scout) {
+      const ScoutBuffers sb(ctx);
+      const int scout_blocks = ctx->num_cus * kScoutBlocksPerCu;
+      unsigned long long *const q_scout = ctx->queue + kQScout;
+      order = sb.order;
+      if (in_place) {
+        HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, q_scout, scout_blocks, scout_pair_blocks, nullptr, st));
+        HIP_TRY(ccmp_launch::project_group(c, head_blocks, ctx->queue, nullptr, pl.dump_threshold, nullptr, nullptr, 0, 0, st, kFdHead, ctx->fd_state, pl.head_rounds));
+      } else {
+        HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, q_scout, scout_blocks, scout_pair_blocks, nullptr, st, kScoutClear));
+        fj.fork();
+        FJ_STEP(fj, hipEventRecord(ctx->gate, ctx->side));
+        FJ_STEP(fj, ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, q_scout, scout_blocks, scout_pair_blocks, nullptr, ctx->side, kScoutPass));
+        FJ_STEP(fj, hipStreamWaitEvent(st, ctx->gate, 0));
+        FJ_STEP(fj, ccmp_launch::project_group(c, head_blocks, ctx->queue, nullptr, pl.dump_threshold, nullptr, nullptr, 0, 0, st, kFdHead, ctx->fd_state, pl.head_rounds));
+        const int rc = fj.join();
+        if (rc != CCMP_OK) return rc;
+        HIP_TRY(ccmp_launch::scout_order(c, sb.pred, sb.hist, sb.order, q_scout, scout_blocks, scout_pair_blocks, nullptr, st, kScoutSort));
+      }
+    } else
+      HIP_TRY(ccmp_launch::project_group(c, head_blocks, ctx->queue, nullptr, pl.dump_threshold, nullptr, nullptr, 0, 0, st, kFdHead, ctx->fd_state, pl.head_rounds));
+    HIP_TRY(ccmp_launch::project_group(c, pl.group_blocks, ctx->queue, nullptr, pl.dump_threshold, order, nullptr, 0, 0, st, kFdResume, ctx->fd_state, pl.head_rounds));
+    return CCMP_OK;
+  }
   if (pl.scout) { // FP32 scout pass -> predicted iteration counts -> descending counting sort -> processing order
     const ScoutBuffers sb(ctx);
     // up to two 256-thread blocks per CU (kScoutBlocksPerCu): a wavefront owns a contiguous slice of the batch — 128 samples at

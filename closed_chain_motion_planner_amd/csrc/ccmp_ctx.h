@@ -58,6 +58,8 @@ constexpr size_t kOccupancyHandoverBelow = 53248;  // below: the throughput kern
 constexpr int kOccupancyHandoverValue = 10 + 70;   // "handover_threshold" encoding of that rule: 10 + per cent of the group slots (70 %)
 constexpr size_t kNoHandoverFrom = 131072;         // ordered batches of this size or more end on their shortest samples: no hand-over
 // fixed since round 6 (no option sets them any more)
+constexpr int kDefaultFdHeadRounds = 5;            // from fd_head_min_batch samples on: every sample's first rounds in a launch of their own (0 = one launch; DESIGN_experiments.md §5.6, tools/head_rounds_model.py)
+constexpr size_t kDefaultFdHeadMinBatch = 262144;  // ... from here on: the call must be bound by the chip's turnover of rounds, not by its longest sample's chain of them — a sample's first rounds end only with the whole head launch (131 584 samples: +16 %, 196 608: -1.7 %, 262 144: -1.7 %)
 constexpr int kPoolLongRemaining = 24;             // two-class hand-over: samples with at least this many predicted iterations left go first
 constexpr int kLatencyBlocksPerCu = 8;             // the projector's latency kernel (and the extend step's throughput flavour): blocks per CU
 constexpr int kScoutBlocksPerCu = 2;               // scout_kernel: 256-lane blocks per CU at most (two wavefronts per SIMD; its lanes refill from their wavefront's slice)
@@ -77,9 +79,12 @@ struct ccmp_ctx {
   hipStream_t stream = nullptr;        // internal stream of the *_host entry points
   hipStream_t side = nullptr;          // side stream of split launches (highest priority: a hardware queue of its own)
   hipEvent_t fork = nullptr, join = nullptr;
+  hipEvent_t gate = nullptr;           // head launch of a large projector batch: holds the head back until the side stream has reached the scout pass
   unsigned long long *queue = nullptr; // work-queue words: ccmp_launch.h (QueueWord)
   double *pool = nullptr;              // straggler hand-over records (throughput kernel -> latency kernel)
   size_t pool_cap = 0;                 // in records
+  double *fd_state = nullptr;          // head -> resume launch of a large projector batch: one hand-over record per sample, row = sample
+  size_t fd_state_cap = 0;             // in records
   void *lpt_buf = nullptr;             // pred (u16 x B) | hist (u32 x 1024) | order (u32 x B) | flags (u8 x B, bulk checkMotion)
   size_t lpt_cap = 0;                  // in samples
   double *geo_pool = nullptr;          // bulk extend hand-over: kGeoPoolEntry doubles per edge
@@ -126,6 +131,8 @@ struct ccmp_ctx {
   size_t fd_split_min = 0, fd_split_max = 90112;
   int fd_split_pred = -1, fd_split_front = -1, fd_split_group_cut = -1;
   long long fd_split_samples = -1;
+  int fd_head_rounds = kDefaultFdHeadRounds;
+  size_t fd_head_min_batch = kDefaultFdHeadMinBatch;
   size_t analytic_small_batch = 8192;  // analytic mode: at or below, the sixteen-lanes-per-sample latency kernel alone
   int analytic_waves_per_cu = 12;      // ... persistent wavefronts of the lane-pair kernel per CU (142 registers, 13 KB of LDS: three per SIMD)
   int analytic_handover = 8;           // ... one of them hands over to the latency kernel once its tickets are gone and it holds at most this many samples (0: never)

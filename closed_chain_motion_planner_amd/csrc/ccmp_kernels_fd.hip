@@ -325,14 +325,70 @@ __device__ __forceinline__ void stencil_combine(double *rec, int r, bool live)
 }
 
 // MODE 0: project q_in -> q_out.  MODE 1: sampleUniform = ambient sample -> project -> enforceBounds.
-template <int MODE, bool STOCK>
+// PART (ccmp_launch.h: FdPart) — which part of a call the launch is:
+//   whole   the persistent, queue-fed kernel from a sample's first round to its last (every regime but the one below)
+//   head    large batches without hand-over: the first head_rounds Newton rounds of EVERY sample, non-persistent: workgroup w takes
+//           samples 10 w .. 10 w + 9 in index order, so the ten samples of a wavefront are of one age — far from the manifold all
+//           together, for four or five rounds, and done with it; at the loop top of round head_rounds each sample still iterating
+//           leaves its hand-over record (kPoolEntry doubles: x, index, counters) in row idx of `state`; one that ends earlier is
+//           written back as ever and its row is marked finished (index -1)
+//   resume  the persistent kernel again, whose refill takes x and the four counters from that row instead of q_in and zeros, and
+//           draws again (kResumeDraws times, then waits a round) where the row is marked finished.  Its wavefronts hold samples of
+//           all ages, none of them far from the manifold: ccmp_atan's wave-uniform first interval (ccmp_detmath.h) holds in nearly
+//           every round, where one young sample among the ten defeated it in two rounds of three.
+// The operations on a sample are the same ones in the same order whichever launches perform them: same bits.
+// VARIANT = MODE + 2 * PART in ONE integer: the kernels' names keep the form project_fd_kernel<n, stock> (build.py: _SCRATCH_RULES).
+using ccmp_launch::FdPart;
+using ccmp_launch::kFdHead;
+using ccmp_launch::kFdResume;
+using ccmp_launch::kFdWhole;
+constexpr int kResumeDraws = 4;
+// A sample's iterate into its group's record.  From a row of 14 doubles (q_in, or the row the head left) as seven 16-B pieces: lanes
+// 0..5 of the group take 96 contiguous bytes in ONE instruction, lane 0 the last piece (14 single-lane 8-B loads before: same data,
+// 7x the requests).  MODE 1, head launch: the ambient draw, every lane its entries (the refill of a whole call keeps its own copy of
+// these lines: through this function project_fd_kernel<1, true> came out with another register allocation).
+__device__ __forceinline__ void iterate_from_row(double *rec, int r, const double *__restrict__ src)
+{
+  const double2 *row = reinterpret_cast<const double2 *>(src);
+  const double2 a = row[r];
+  rec[kX + 2 * r] = a.x;
+  rec[kX + 2 * r + 1] = a.y;
+  if (r == 0) {
+    const double2 b = row[6];
+    rec[kX + 12] = b.x;
+    rec[kX + 13] = b.y;
+  }
+}
+__device__ __forceinline__ void iterate_from_draw(const ccmp_consts &K, double *rec, int r, unsigned long long seed, unsigned long long first_index,
+                                                  unsigned long long idx, double *q_ambient)
+{
+#pragma unroll
+  for (int e = 0; e < 14; e++) {
+    if (e % kGroup == r) { // e is a compile-time constant here: bounds come from SGPRs
+      const double v = ambient_uniform(K, seed, first_index + idx, e);
+      if (q_ambient) q_ambient[idx * 14 + e] = v;
+      rec[kX + e] = v;
+    }
+  }
+}
+// head: the sample of group g of this workgroup.  It never changes, but it is NOT held across the Newton loop, and neither are the
+// four row addresses that follow from it: formed where it is used, from a group index the optimiser cannot see through (as the
+// lane's slots in ccmp_fd_newton_phase2.inc) — hoisted, they were the registers that the head's instantiations spilled.
+__device__ __forceinline__ unsigned long long head_sample(int g)
+{
+  asm volatile("" : "+v"(g));
+  return (unsigned long long)blockIdx.x * kGroupsPerWave + (unsigned long long)g;
+}
+template <int VARIANT, bool STOCK>
 __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
     const ccmp_consts K, const double *__restrict__ q_in, double *__restrict__ q_out, uint8_t *__restrict__ ok_out,
     uint16_t *__restrict__ iters_out, double *__restrict__ q_ambient, unsigned long long B, unsigned long long *queue,
     unsigned long long seed, unsigned long long first_index, double *__restrict__ pool, unsigned long long *pool_count,
     int dump_threshold, const unsigned int *__restrict__ order, const uint16_t *__restrict__ pred, int long_remaining,
-    unsigned long long pool_records)
+    unsigned long long pool_records, double *__restrict__ state, int head_rounds)
 {
+  constexpr int MODE = VARIANT & 1, PART = VARIANT >> 1;
+  if constexpr (PART != kFdWhole) pool = nullptr; // neither part hands over (ccmp_policy.cpp): the text below that does folds away
   __shared__ double lds[kGroupsPerWave * kRec];
   const int lane = threadIdx.x;
   const int g = lane / kGroup;                // 0..10; lanes 60..63 form the idle "group 10"
@@ -358,10 +414,41 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
   int iter = 0, updates = 0;
   double norm1 = 0.0, norm2 = 0.0;
   bool active = false, drained = false;
+  int round = 0; // head: Newton rounds done, the same for all ten samples
+  if constexpr (PART == kFdHead) { // the group's one sample, taken in front of the loop: nothing of the draw is live across it
+    idx = head_sample(g);
+    if (live && idx < B) {
+      active = true;
+      if (MODE == 0) iterate_from_row(rec, r, q_in + idx * 14);
+      else iterate_from_draw(K, rec, r, seed, first_index, idx, q_ambient);
+    }
+  }
 
   for (;;) {
     // ---- refill: groups without a sample pull the next index from the global queue ----------
-    {
+    if constexpr (PART == kFdResume) {
+      // the same tickets, the sample's state from its row of `state`: x in 16-B pieces as below, the index and the counters by
+      // every lane of the group for itself (one address: a broadcast)
+      for (int draw = 0; draw < kResumeDraws; draw++) {
+        const bool want = live && !active && !drained;
+        if (__builtin_amdgcn_ballot_w64(want) == 0ull) break;
+        unsigned long long t = 0;
+        if (want && r == 0) t = atomicAdd(queue, 1ull);
+        t = shfl_u64(t, leader);
+        if (want) {
+          if (t < B) {
+            idx = order ? (unsigned long long)order[t] : t;
+            const double2 *row = reinterpret_cast<const double2 *>(state + idx * kPoolEntry);
+            const double2 tag = row[7], nrm = row[8];
+            if (__double_as_longlong(tag.x) >= 0) { // (a row marked finished: the head has written the sample back)
+              active = true;
+              iter = __double2loint(tag.y); updates = __double2hiint(tag.y); norm1 = nrm.x; norm2 = nrm.y;
+              iterate_from_row(rec, r, state + idx * kPoolEntry);
+            }
+          } else drained = true;
+        }
+      }
+    } else if constexpr (PART == kFdWhole) {
       const bool want = live && !active && !drained;
       unsigned long long t = 0;
       if (want && r == 0) t = atomicAdd(queue, 1ull);
@@ -370,19 +457,8 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
         if (t < B) {
           idx = order ? (unsigned long long)order[t] : t; // ticket -> sample: longest-predicted-first when scheduled
           active = true; iter = 0; updates = 0; norm1 = 0.0; norm2 = 0.0;
-          if (MODE == 0) {
-            // the 112-B row as seven 16-B pieces: lanes 0..5 of the group take 96 contiguous bytes in ONE
-            // instruction, lane 0 the last piece (14 single-lane 8-B loads before: same data, 7x the requests)
-            const double2 *row = reinterpret_cast<const double2 *>(q_in + idx * 14);
-            const double2 a = row[r];
-            rec[kX + 2 * r] = a.x;
-            rec[kX + 2 * r + 1] = a.y;
-            if (r == 0) {
-              const double2 b = row[6];
-              rec[kX + 12] = b.x;
-              rec[kX + 13] = b.y;
-            }
-          } else {
+          if (MODE == 0) iterate_from_row(rec, r, q_in + idx * 14);
+          else {
 #pragma unroll
             for (int e = 0; e < 14; e++) {
               if (e % kGroup == r) { // e is a compile-time constant here: bounds come from SGPRs
@@ -395,8 +471,31 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
         } else drained = true;
       }
     }
-    if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
+    if (__builtin_amdgcn_ballot_w64(active) == 0ull) {
+      // (resume: ten finished rows in a row leave the groups without a sample and the queue not yet dry — draw again)
+      if (PART == kFdResume && __builtin_amdgcn_ballot_w64(live && !drained) != 0ull) continue;
+      break;
+    }
     __syncthreads();
+    // ---- head: the loop top of round head_rounds, where the next thing that happens to a sample is function(x) + the loop test —
+    // the samples still iterating leave their records (the hand-over's, in row idx) and the wavefront retires
+    if constexpr (PART == kFdHead) {
+      if (round == head_rounds) {
+        idx = head_sample(g);
+        if (active) {
+          double *ent = state + idx * kPoolEntry;
+          for (int e = r; e < 14; e += kGroup) ent[e] = rec[kX + e];
+          if (r == 0) {
+            ent[14] = __longlong_as_double((long long)idx);
+            ent[15] = __hiloint2double(updates, iter);
+            ent[16] = norm1;
+            ent[17] = norm2;
+          }
+        }
+        break;
+      }
+      round++;
+    }
     // ---- hand-over: once the queue is empty the samples still in flight go to the straggler pool
     // (x, index, counters — everything else is recomputed from x) and the wave retires; the
     // wave-per-sample kernel finishes them.  State is dumped at the loop top, where the next thing
@@ -461,6 +560,7 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
     {
       const bool fin = active && !cont;
       bool bad = false;
+      if constexpr (PART == kFdHead) idx = head_sample(g);
       if (fin) {
 #pragma unroll
         for (int e = 0; e < 14; e++) {
@@ -491,6 +591,7 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
         ok_out[idx] = (uint8_t)((!gbad) && (norm1 < K.tol_pos) && (norm2 < K.tol_rot));
         if (iters_out) iters_out[idx] = (uint16_t)updates;
         if (pool != nullptr && dump_threshold > 10) atomicAdd(queue + 3, 1ull); // finished count of the occupancy-driven hand-over
+        if constexpr (PART == kFdHead) state[idx * kPoolEntry + 14] = __longlong_as_double(-1ll); // nothing left for the resume launch
       }
       if (fin) active = false;
     }
@@ -955,20 +1056,32 @@ hipError_t clear_words(void *words, size_t n_u32, hipStream_t st)
 }
 
 // queue: the projector's block of queue words (kQTicket: this kernel's samples, kQPool: the pool's fill count)
+// part: the whole call (the default), or one of the two launches of a large batch — a head launch is one one-wavefront workgroup
+// per ten samples: `blocks` must say so; state: the call's B rows of kPoolEntry doubles between head and resume
 hipError_t project_group(const ProjectCall &c, int blocks, unsigned long long *queue, double *pool, int dump_threshold,
-                         const unsigned int *order, const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st)
+                         const unsigned int *order, const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st,
+                         FdPart part, double *state, int head_rounds)
 {
-#define CCMP_LAUNCH_GROUP(MODE, STOCK)                                                                                                    \
-  hipLaunchKernelGGL((project_fd_kernel<MODE, STOCK>), dim3(blocks), dim3(64), 0, st, *c.K, c.q_in, c.q_out, c.ok, c.iters, c.q_ambient, \
-                     (unsigned long long)c.B, queue + kQTicket, c.seed, c.first, pool, queue + kQPool, dump_threshold, order, pred,       \
-                     long_remaining, (unsigned long long)pool_records)
+  if (part != kFdWhole && (state == nullptr || head_rounds <= 0)) return hipErrorInvalidValue;
+  if (blocks <= 0 || (part == kFdHead && (size_t)blocks != (c.B + kGroupsPerWave - 1) / kGroupsPerWave)) return hipErrorInvalidValue;
+#define CCMP_LAUNCH_GROUP(VARIANT, STOCK)                                                                                                    \
+  hipLaunchKernelGGL((project_fd_kernel<VARIANT, STOCK>), dim3(blocks), dim3(64), 0, st, *c.K, c.q_in, c.q_out, c.ok, c.iters, c.q_ambient, \
+                     (unsigned long long)c.B, queue + kQTicket, c.seed, c.first, pool, queue + kQPool, dump_threshold, order, pred,          \
+                     long_remaining, (unsigned long long)pool_records, state, head_rounds)
+#define CCMP_LAUNCH_PART(MODE, STOCK)                                              \
+  do {                                                                             \
+    if (part == kFdHead) CCMP_LAUNCH_GROUP(MODE + 2 * kFdHead, STOCK);             \
+    else if (part == kFdResume) CCMP_LAUNCH_GROUP(MODE + 2 * kFdResume, STOCK);    \
+    else CCMP_LAUNCH_GROUP(MODE, STOCK);                                           \
+  } while (0)
   if (c.mode == 0) {
-    if (c.K->stock && c.K->twin_arms) CCMP_LAUNCH_GROUP(0, true);
-    else CCMP_LAUNCH_GROUP(0, false);
+    if (c.K->stock && c.K->twin_arms) CCMP_LAUNCH_PART(0, true);
+    else CCMP_LAUNCH_PART(0, false);
   } else {
     if (!(c.K->stock && c.K->twin_arms)) return hipErrorInvalidValue; // the fused sampler exists for the stock structure only (ccmp_api.cpp: project_common)
-    CCMP_LAUNCH_GROUP(1, true);
+    CCMP_LAUNCH_PART(1, true);
   }
+#undef CCMP_LAUNCH_PART
 #undef CCMP_LAUNCH_GROUP
   return hipGetLastError();
 }

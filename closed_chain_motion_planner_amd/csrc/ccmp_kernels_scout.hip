@@ -955,8 +955,9 @@ hipError_t fd_split(const unsigned int *hist, int pred_min, unsigned int limit, 
   return hipGetLastError();
 }
 
+// steps: which of the sequence's launches this call makes (ScoutStep; all of them unless a caller puts other work between them)
 hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist, unsigned int *order, unsigned long long *queue, int blocks,
-                       int pair_max_blocks, const ccmp_split_req *split, hipStream_t st)
+                       int pair_max_blocks, const ccmp_split_req *split, hipStream_t st, int steps)
 {
   const ccmp_consts *K = c.K;
   const size_t B = c.B;
@@ -966,10 +967,11 @@ hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist,
   make_consts_f(K, F, &stock);
   const bool fused = B <= (size_t)kSortFusedMax; // the fused sort writes every bin itself: nothing to clear
   hipError_t e = hipSuccess;
-  if (!fused) {
+  if (!fused && (steps & kScoutClear)) {
     e = clear_words(hist, kBins, st);
     if (e != hipSuccess) return e;
   }
+  if (steps & kScoutPass) {
   // `blocks` is the most the chip is given; a batch too small to hand every lane of that grid a first sample gets no more wavefronts
   // than it fills (a half-empty wavefront refills nothing and only shares its SIMD: 65 536 samples 0.152 ms on 1 024 wavefronts, 0.230 on 2 048)
   const size_t full_blocks = (B + 255) / 256;
@@ -991,6 +993,8 @@ hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist,
     else CCMP_LAUNCH_SCOUT(1, false);
   }
 #undef CCMP_LAUNCH_SCOUT
+  }
+  if (!(steps & kScoutSort)) return hipGetLastError();
   if (fused) {
     hipLaunchKernelGGL(sort_fused_kernel, dim3(1), dim3(1024), 0, st, pred, (unsigned int)B, hist, order, sr);
     return hipGetLastError();

@@ -310,14 +310,20 @@ hipError_t connect_gather(const double *nodes, const double *queries, const int3
 hipError_t connect_fix(const int32_t *nbr_idx, size_t E, int32_t *n_states, uint8_t *ok, int32_t *newton_iters, uint8_t *blocked, double *carry_out,
                        hipStream_t st);
 hipError_t clear_words(void *words, size_t n_u32, hipStream_t st);
+/* which part of a projector call a launch of project_fd_kernel is (ccmp_kernels_fd.hip): all of it, or — large batches without
+ * hand-over — every sample's first rounds in index order (head), then the persistent kernel on the rows the head left (resume) */
+enum FdPart : int { kFdWhole = 0, kFdHead = 1, kFdResume = 2 };
 hipError_t project_group(const ProjectCall &c, int blocks, unsigned long long *queue, double *pool, int dump_threshold, const unsigned int *order,
-                         const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st);
+                         const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st, FdPart part = kFdWhole,
+                         double *state = nullptr, int head_rounds = 0);
 hipError_t project_wave(const ProjectCall &c, bool from_pool, int blocks, unsigned long long *queue, const double *pool,
                         const unsigned long long *pool_count, hipStream_t st);
 hipError_t project_flat(const ProjectCall &c, const FlatLaunch &l, hipStream_t st);
 hipError_t project_analytic(const ProjectCall &c, int pair_blocks, int dump_below, int latency_blocks, double *pool, unsigned long long *queue, hipStream_t st);
+/* the launches of scout_order: the histogram's clear, the scout pass (-> pred), the counting sort (pred -> order) */
+enum ScoutStep : int { kScoutClear = 1, kScoutPass = 2, kScoutSort = 4, kScoutAll = 7 };
 hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist, unsigned int *order, unsigned long long *queue, int blocks,
-                       int pair_max_blocks, const ccmp_split_req *split, hipStream_t st);
+                       int pair_max_blocks, const ccmp_split_req *split, hipStream_t st, int steps = kScoutAll);
 hipError_t fd_split(const unsigned int *hist, int pred_min, unsigned int limit, unsigned long long *queue, hipStream_t st);
 hipError_t geo_split(const unsigned int *hist, int p_min, int p_max, int permille, unsigned long long *queue, hipStream_t st);
 hipError_t geodesic(const GeoCall &g, const GeoLaunch &l, hipStream_t st);

@@ -45,6 +45,8 @@ const OptionDesc kOptions[] = {
     OPT("fd_split_front", fd_split_front, kInt, -1, 4096, 0, "latency blocks of the front (-1: two per CU up to 24576 samples, one above; 0 = no split)"),
     OPT("fd_split_samples", fd_split_samples, kLongLong, -1, 0x7fffffffl, 0, "samples of the front at most (-1: four per CU up to 24576 samples, three to four above; 0 = one per block)"),
     OPT("fd_split_group_cut", fd_split_group_cut, kInt, -1, 8, 0, "throughput wavefronts per CU left out for the front's blocks (-1: 3 up to 24576 samples, 2 above)"),
+    OPT("fd_head_rounds", fd_head_rounds, kInt, 0, 65535, 0, "throughput kernel alone (no split, no hand-over) from fd_head_min_batch samples on: the first this many Newton rounds of every sample in a launch of their own, ten samples of one age per wavefront, and the persistent kernel resumes them (0 = one launch)"),
+    OPT("fd_head_min_batch", fd_head_min_batch, kSize, 0, LONG_MAX, 0, "... from this many samples on"),
     // projector, analytic mode
     OPT("analytic_small_batch", analytic_small_batch, kSize, 0, LONG_MAX, 0, "analytic mode: at or below, the sixteen-lanes-per-sample latency kernel alone"),
     OPT("analytic_waves_per_cu", analytic_waves_per_cu, kInt, 1, 12, 0, "analytic mode: persistent wavefronts of the lane-pair kernel per CU"),
@@ -154,6 +156,8 @@ static SplitShape split_shape(const ccmp_ctx *ctx, size_t B)
 //   scout + longest-first order     from lpt_min_batch on (and wherever the split launch applies); from kNoHandoverFrom samples
 //                                   on without hand-over
 //   split launch                    small_batch < B <= fd_split_max: the front of the order on latency blocks beside it
+//   head launch                     throughput kernel alone (no split, no hand-over) from fd_head_min_batch samples on: every sample's
+//                                   first fd_head_rounds rounds in a launch of their own, the throughput kernel resumes them
 FdPlan plan_fd_batch(const ccmp_ctx *ctx, size_t B, bool external_order)
 {
   FdPlan pl;
@@ -198,6 +202,10 @@ FdPlan plan_fd_batch(const ccmp_ctx *ctx, size_t B, bool external_order)
       if (pl.group_blocks > room) pl.group_blocks = room;
     }
   }
+  // Head launch: where the call is the throughput kernel alone.  A persistent wavefront mixes ten samples of all ages and takes atan's
+  // wave-uniform first interval (ccmp_detmath.h) only while none of them is in its first four or five rounds, far from the manifold — a
+  // third of its rounds; with those rounds in a launch of their own, ten samples of one age per wavefront, nearly all of them.
+  if (ctx->fd_head_rounds > 0 && !pl.handover && !pl.split && B >= ctx->fd_head_min_batch && B < 0xffffffffull) pl.head_rounds = ctx->fd_head_rounds;
   return pl;
 }
 
@@ -414,8 +422,12 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
         L.add(" to %d %s blocks", pl.latency_blocks, ctx->flat_kernel ? "project_fd_flat_kernel" : "project_fd_wave_kernel");
         if (pl.two_class_pool) L.add(" in two classes (>= %d predicted iterations left first)", kPoolLongRemaining);
       } else L.add("; no hand-over");
-      L.add(" [small_batch=%zu lpt_min_batch=%zu fd_split=%d:%zu..%zu wide<=%zu occupancy_rule<%zu no_handover>=%zu]", ctx->small_batch,
-            ctx->lpt_min_batch, ctx->fd_split, ctx->fd_split_min, ctx->fd_split_max, kSplitWideMax, kOccupancyHandoverBelow, kNoHandoverFrom);
+      if (pl.head_rounds > 0)
+        L.add("; in front of it the first %d Newton rounds of every sample on project_fd_kernel (head) x %zu one-wavefront workgroups in index order%s",
+              pl.head_rounds, (n + 9) / 10, pl.scout ? ", the scout pass beside them on the side stream (in front of them where the call is in place)" : "");
+      L.add(" [small_batch=%zu lpt_min_batch=%zu fd_split=%d:%zu..%zu wide<=%zu occupancy_rule<%zu no_handover>=%zu fd_head=%d:%zu..]", ctx->small_batch,
+            ctx->lpt_min_batch, ctx->fd_split, ctx->fd_split_min, ctx->fd_split_max, kSplitWideMax, kOccupancyHandoverBelow, kNoHandoverFrom,
+            ctx->fd_head_rounds, ctx->fd_head_min_batch);
       break;
     }
     case CCMP_CALL_PROJECT_ANALYTIC: {

@@ -28,6 +28,8 @@ struct FdPlan {
   bool two_class_pool = false; // hand-over in two classes by the scout's remaining prediction
   bool split = false;          // split launch: the front on latency blocks on the side stream, beside the throughput kernel
   SplitShape shape;
+  int head_rounds = 0;         // > 0: every sample's first head_rounds Newton rounds ten to a one-wavefront workgroup in index order, then
+                               // the throughput kernel on the records those left
 };
 FdPlan plan_fd_batch(const ccmp_ctx *ctx, size_t B, bool external_order);
 

@@ -179,6 +179,10 @@ int ccmp_ctx_option_info(int index, const char **name, long *dflt, long *lo, lon
  *                                                            0 = one per block)
  *   "fd_split_group_cut"            -1        -1..8         throughput wavefronts per CU left out for the front's blocks (-1: 3 up to 24576 samples,
  *                                                           2 above)
+ *   "fd_head_rounds"                5         0..65535      throughput kernel alone (no split, no hand-over) from fd_head_min_batch samples on: the
+ *                                                           first this many Newton rounds of every sample in a launch of their own, ten samples of
+ *                                                           one age per wavefront, and the persistent kernel resumes them (0 = one launch)
+ *   "fd_head_min_batch"             262144    0..max        ... from this many samples on
  *   "analytic_small_batch"          8192      0..max        analytic mode: at or below, the sixteen-lanes-per-sample latency kernel alone
  *   "analytic_waves_per_cu"         12        1..12         analytic mode: persistent wavefronts of the lane-pair kernel per CU
  *   "analytic_handover"             8         0..32         analytic mode: a wavefront of the lane-pair kernel whose tickets are gone hands over to

@@ -68,6 +68,16 @@ def profiled_rows(rows, key, warm_frac):
     return rows[int(round(len(rows) * warm_frac)):]
 
 
+def instantiation(ks, kernel_name):
+    """`ks<template arguments>` of a dispatch's kernel name (ks itself where the kernel is no template)"""
+    m = re.search(re.escape(ks) + r"<[^>]*>", kernel_name)
+    return m.group(0) if m else ks
+
+
+def ms(row):
+    return (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e6
+
+
 def counters(d, kernel_subs, warm_frac):
     """mean per call = sum over the call's kernels of (mean per profiled dispatch x dispatches per call)"""
     per = {ks: collections.defaultdict(list) for ks in kernel_subs}
@@ -77,9 +87,11 @@ def counters(d, kernel_subs, warm_frac):
             for ks in kernel_subs:
                 if ks in r["Kernel_Name"]:
                     per[ks][r["Counter_Name"]].append((int(r.get("Dispatch_Id", 0)), float(r["Counter_Value"])))
-                    meta[ks] = {k: r[k] for k in ("Grid_Size", "Workgroup_Size", "LDS_Block_Size", "Scratch_Size",
-                                                  "VGPR_Count", "Accum_VGPR_Count", "SGPR_Count")}
+                    meta.setdefault(ks, {})[instantiation(ks, r["Kernel_Name"])] = {
+                        k: r[k] for k in ("Grid_Size", "Workgroup_Size", "LDS_Block_Size", "Scratch_Size", "VGPR_Count", "Accum_VGPR_Count", "SGPR_Count")}
                     break
+    # the launch record of a kernel: under the kernel's name while one instantiation of it runs, under each instantiation's otherwise
+    meta = {(ks if len(v) == 1 else name): rec for ks, v in meta.items() for name, rec in v.items()}
     out, n = collections.defaultdict(float), {}
     return per, out, n, meta
 
@@ -115,9 +127,20 @@ def main():
                     by[ks].append(r)
                     break
         for ks, rows in by.items():
-            rows = profiled_rows(rows, lambda r: int(r["Start_Timestamp"]), warm_frac)
-            d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]
-            per_kernel[ks] = dict(quartiles(d), per_call=len(d) / float(n_calls))
+            # the projector's head and resume launches: several instantiations of one kernel, each dispatched once per call.  The
+            # kernel's figure is then the call's SUM — what the one dispatch was before, and what bench.py's roofline prices — with
+            # each instantiation's own dispatches listed beside it.  Each instantiation is trimmed of its own warm-up dispatches and
+            # its i-th profiled dispatch belongs to the i-th profiled call, whatever the order of the launches within a call.
+            parts = collections.defaultdict(list)
+            for r in rows:
+                parts[instantiation(ks, r["Kernel_Name"])].append(r)
+            parts = {name: [ms(r) for r in profiled_rows(v, lambda r: int(r["Start_Timestamp"]), warm_frac)] for name, v in parts.items()}
+            if len(parts) > 1 and all(len(v) == n_calls for v in parts.values()):
+                per_kernel[ks] = dict(quartiles([sum(v[i] for v in parts.values()) for i in range(n_calls)]), per_call=1.0, dispatches_per_call=len(parts))
+                per_kernel[ks]["parts"] = {name: dict(quartiles(v), per_call=1.0) for name, v in parts.items()}
+            else:
+                d = [ms(r) for r in profiled_rows(rows, lambda r: int(r["Start_Timestamp"]), warm_frac)]
+                per_kernel[ks] = dict(quartiles(d), per_call=len(d) / float(n_calls))
     dominant = max(per_kernel, key=lambda k: per_kernel[k]["median"] * per_kernel[k]["per_call"]) if per_kernel else None
     call_q = quartiles(calls_ms) if calls_ms else None
     # the call's wall time: what the workload measured around it; for the headline (bench.py steps overlap nothing) that is the
@@ -166,8 +189,12 @@ def main():
         w("| the same under `--pmc` (counter collection serialises the dispatches) | %.3f ms | %.3f – %.3f | %.3f – %.3f | %d |"
           % (pmc_q["median"], pmc_q["q1"], pmc_q["q3"], pmc_q["min"], pmc_q["max"], pmc_q["n"]))
     for ks, v in sorted(per_kernel.items(), key=lambda kv: -kv[1]["median"] * kv[1]["per_call"]):
-        w("| kernel `%s` (%.3g per call) | %.3f ms | %.3f – %.3f | %.3f – %.3f | %d |"
-          % (ks[-60:], v["per_call"], v["median"], v["q1"], v["q3"], v["min"], v["max"], v["n"]))
+        w("| kernel `%s` (%s) | %.3f ms | %.3f – %.3f | %.3f – %.3f | %d |"
+          % (ks[-60:], "%d dispatches per call, summed" % v["dispatches_per_call"] if "parts" in v else "%.3g per call" % v["per_call"],
+             v["median"], v["q1"], v["q3"], v["min"], v["max"], v["n"]))
+        for name, pv in sorted(v.get("parts", {}).items(), key=lambda kv: -kv[1]["median"]):
+            w("| ... of which `%s` (%.3g per call) | %.3f ms | %.3f – %.3f | %.3f – %.3f | %d |"
+              % (name[-60:], pv["per_call"], pv["median"], pv["q1"], pv["q3"], pv["min"], pv["max"], pv["n"]))
     w("")
     w("| quantity | value |\n|---|---|")
     w("| units/s at the call's median | %.3e |" % summary["units_per_s"])
