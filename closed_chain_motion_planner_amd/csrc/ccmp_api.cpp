@@ -846,6 +846,77 @@ int ccmp_detmath_div_probe(ccmp_ctx *ctx, const double *n_dev, const double *d_d
   HIP_TRY(ccmp_launch::div_probe(n_dev, d_dev, out_dev, count, st));
   return CCMP_OK;
 }
+
+// what the scout's order, histogram and the context's queue words hold behind the last call (ScoutBuffers; ccmp_launch.h: QueueWord)
+int ccmp_ctx_debug_lpt_order(ccmp_ctx *ctx, unsigned int *order_host, size_t n, unsigned int *hist_host, unsigned long long *queue_host, size_t queue_words)
+{
+  if (!ctx || !order_host || !hist_host || !queue_host || !ctx->lpt_buf || n > ctx->lpt_cap || queue_words != (size_t)kQueueWords) return CCMP_EINVAL;
+  DeviceGuard guard(ctx->device);
+  ccmp_host::quiesce(ctx);
+  HIP_TRY(hipDeviceSynchronize());
+  const ScoutBuffers sb(ctx);
+  HIP_TRY(hipMemcpy(order_host, sb.order, n * sizeof(unsigned int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hist_host, sb.hist, 1024 * sizeof(unsigned int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(queue_host, ctx->queue, kQueueWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return CCMP_OK;
+}
+
+// every index a split rule forms stays inside the 1024 bins (the kernels clamp p_high / p_max / kind 1's p_low from above only)
+static bool split_args_ok(int kind, int p_low, int p_high, int permille, int clear)
+{
+  if (kind == 0) return true;
+  if (kind != 1 && kind != 2) return false;
+  if (p_low < 0 || p_high < 0 || permille < 0 || permille > 1000 || clear < 0 || clear > 16) return false;
+  return kind == 1 || p_low <= 1023;
+}
+
+int ccmp_debug_sort_probe(ccmp_ctx *ctx, const uint16_t *keys_dev, size_t n, int nbins, int hist_blocks, int clear_first, unsigned int *order_dev,
+                          unsigned int *hist_dev, unsigned long long *queue_dev, int kind, int p_low, int p_high, int permille, unsigned int limit,
+                          int clear, void *hip_stream)
+{
+  if (!ctx || !keys_dev || !order_dev || !hist_dev || n == 0 || n > (1u << 24) || nbins < 1 || nbins > 1024 || hist_blocks < 1 || hist_blocks > 1024)
+    return CCMP_EINVAL;
+  if (!split_args_ok(kind, p_low, p_high, permille, clear) || (kind != 0 && !queue_dev)) return CCMP_EINVAL;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (ccmp_launch::sort_needs_clear(n)) {
+    // the three-kernel form scans nbins bins only: a key beyond them would be scattered from an unscanned cursor, past the end of order
+    uint16_t *keys = (uint16_t *)malloc(n * sizeof(uint16_t));
+    if (!keys) return CCMP_ENOMEM;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(keys, keys_dev, n * sizeof(uint16_t), hipMemcpyDeviceToHost);
+    bool inside = true;
+    for (size_t i = 0; e == hipSuccess && i < n; i++) inside = inside && (keys[i] < 1024 ? keys[i] : 1023) < nbins;
+    free(keys);
+    HIP_TRY(e);
+    if (!inside) return CCMP_EINVAL;
+    if (clear_first) HIP_TRY(ccmp_launch::clear_words(hist_dev, 1024, st));
+    else { // the histogram kernel ADDS: on anything but zeros the scan's bases would leave order too
+      unsigned int h[1024];
+      HIP_TRY(hipMemcpy(h, hist_dev, sizeof h, hipMemcpyDeviceToHost));
+      for (int k = 0; k < 1024; k++)
+        if (h[k]) return CCMP_EINVAL;
+    }
+  }
+  const ccmp_split_req req{kind ? queue_dev : nullptr, kind, p_low, p_high, permille, limit, clear};
+  HIP_TRY(ccmp_launch::sort_desc(keys_dev, n, nbins, hist_blocks, hist_dev, order_dev, req, st));
+  return CCMP_OK;
+}
+
+int ccmp_debug_split_probe(ccmp_ctx *ctx, int kernel, const unsigned int *hist_dev, int p_min, int p_max, int permille, unsigned int limit,
+                           unsigned long long *queue_dev, void *hip_stream)
+{
+  if (!ctx || !hist_dev || !queue_dev || p_min < 0) return CCMP_EINVAL;
+  if (kernel == 2 && (p_min > 1023 || p_max < p_min || permille < 0 || permille > 1000)) return CCMP_EINVAL; // (P walks down to p_min: never below bin 0)
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (kernel == 1) HIP_TRY(ccmp_launch::fd_split(hist_dev, p_min, limit, queue_dev, st));
+  else if (kernel == 2) HIP_TRY(ccmp_launch::geo_split(hist_dev, p_min, p_max, permille, queue_dev, st));
+  else return CCMP_EINVAL;
+  return CCMP_OK;
+}
 #endif
 
 } // extern "C"

@@ -955,6 +955,26 @@ hipError_t fd_split(const unsigned int *hist, int pred_min, unsigned int limit, 
   return hipGetLastError();
 }
 
+// the fused sort writes every bin itself: only the three-kernel form, whose histogram ADDS to what hist holds, needs it cleared
+bool sort_needs_clear(size_t n) { return n > (size_t)kSortFusedMax; }
+
+// The descending counting sort of n keys (pred -> order; hist[k] = keys >= k behind it) and, where split.queue is set, the cut of the
+// order: one launch up to kSortFusedMax keys, else histogram (hist_blocks blocks), scan over nbins bins (keys < nbins), scatter.
+// The callers clear all kBins words of hist in front of their scout pass where sort_needs_clear(n).
+hipError_t sort_desc(const uint16_t *pred, size_t n, int nbins, int hist_blocks, unsigned int *hist, unsigned int *order, const ccmp_split_req &split,
+                     hipStream_t st)
+{
+  if (n <= (size_t)kSortFusedMax) {
+    hipLaunchKernelGGL(sort_fused_kernel, dim3(1), dim3(1024), 0, st, pred, (unsigned int)n, hist, order, split);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(hist_kernel, dim3((unsigned)hist_blocks), dim3(256), 0, st, pred, (unsigned long long)n, hist);
+  hipLaunchKernelGGL(scan_desc_kernel, dim3(1), dim3(64), 0, st, hist, nbins, split);
+  hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((n + 256 * kScatterPerThread - 1) / (256 * kScatterPerThread))), dim3(256), 0, st, pred,
+                     (unsigned long long)n, hist, order);
+  return hipGetLastError();
+}
+
 // steps: which of the sequence's launches this call makes (ScoutStep; all of them unless a caller puts other work between them)
 hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist, unsigned int *order, unsigned long long *queue, int blocks,
                        int pair_max_blocks, const ccmp_split_req *split, hipStream_t st, int steps)
@@ -965,9 +985,8 @@ hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist,
   consts_f F;
   bool stock;
   make_consts_f(K, F, &stock);
-  const bool fused = B <= (size_t)kSortFusedMax; // the fused sort writes every bin itself: nothing to clear
   hipError_t e = hipSuccess;
-  if (!fused && (steps & kScoutClear)) {
+  if (sort_needs_clear(B) && (steps & kScoutClear)) {
     e = clear_words(hist, kBins, st);
     if (e != hipSuccess) return e;
   }
@@ -995,15 +1014,7 @@ hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist,
 #undef CCMP_LAUNCH_SCOUT
   }
   if (!(steps & kScoutSort)) return hipGetLastError();
-  if (fused) {
-    hipLaunchKernelGGL(sort_fused_kernel, dim3(1), dim3(1024), 0, st, pred, (unsigned int)B, hist, order, sr);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(hist_kernel, dim3(256), dim3(256), 0, st, pred, (unsigned long long)B, hist);
-  hipLaunchKernelGGL(scan_desc_kernel, dim3(1), dim3(64), 0, st, hist, kBins, sr);
-  hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((B + 256 * kScatterPerThread - 1) / (256 * kScatterPerThread))), dim3(256), 0, st, pred,
-                     (unsigned long long)B, hist, order);
-  return hipGetLastError();
+  return sort_desc(pred, B, kBins, 256, hist, order, sr, st);
 }
 
 // extend-step order: FP32 scout of every edge (rounds capped at round_cap < 1024), then the descending counting sort
@@ -1019,9 +1030,8 @@ hipError_t geodesic_scout_order(const GeoCall &g, int round_cap, uint16_t *pred,
   if (round_cap > kBins - 1) round_cap = kBins - 1;
   F.max_iter = K->max_iter < round_cap ? K->max_iter : round_cap;
   const int nbins = round_cap + 1;
-  const bool fused = E <= (size_t)kSortFusedMax;
   hipError_t e = hipSuccess;
-  if (!fused) {
+  if (sort_needs_clear(E)) {
     // every bin, not only the nbins this sort fills: the split rules sum the histogram over all kBins, and the bins above were
     // whatever the context's last sort left there (a projector batch's counts up to its cap of 96: a cut decided on them)
     e = clear_words(hist, (size_t)kBins, st);
@@ -1037,15 +1047,7 @@ hipError_t geodesic_scout_order(const GeoCall &g, int round_cap, uint16_t *pred,
   else
     hipLaunchKernelGGL(scout_geodesic_kernel<false>, dim3(blocks), dim3(64), 0, st, F, g.from, g.to, (unsigned long long)E, (float)g.delta,
                        (float)g.lambda, g.max_states, round_cap, pred);
-  if (fused) {
-    hipLaunchKernelGGL(sort_fused_kernel, dim3(1), dim3(1024), 0, st, pred, (unsigned int)E, hist, order, sr);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(hist_kernel, dim3(64), dim3(256), 0, st, pred, (unsigned long long)E, hist);
-  hipLaunchKernelGGL(scan_desc_kernel, dim3(1), dim3(64), 0, st, hist, nbins, sr);
-  hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((E + 256 * kScatterPerThread - 1) / (256 * kScatterPerThread))), dim3(256), 0, st, pred,
-                     (unsigned long long)E, hist, order);
-  return hipGetLastError();
+  return sort_desc(pred, E, nbins, 64, hist, order, sr, st);
 }
 
 }  // namespace ccmp_launch

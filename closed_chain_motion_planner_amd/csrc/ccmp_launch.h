@@ -16,7 +16,8 @@ namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct 
 struct ccmp_split_req {
   unsigned long long *queue; /* the block of queue words; nullptr: no split */
   int kind;                  /* 1: the units predicted >= p_low, at most `limit` (projector: fd_split_kernel's rule);
-                                2: >= p_high where those carry permille / 1000 of the predicted work, else >= p_low (extend step: geo_split2_kernel's) */
+                                2: >= p_high where those carry permille / 1000 of the predicted work, else >= p_low (extend step: apply_split's
+                                   second rule, ccmp_kernels_scout.hip) */
   int p_low, p_high, permille;
   unsigned int limit;
   int clear;                 /* this many 64-bit words from queue[0] on are zeroed first (the others of the launch's block) */
@@ -324,6 +325,12 @@ hipError_t project_analytic(const ProjectCall &c, int pair_blocks, int dump_belo
 enum ScoutStep : int { kScoutClear = 1, kScoutPass = 2, kScoutSort = 4, kScoutAll = 7 };
 hipError_t scout_order(const ProjectCall &c, uint16_t *pred, unsigned int *hist, unsigned int *order, unsigned long long *queue, int blocks,
                        int pair_max_blocks, const ccmp_split_req *split, hipStream_t st, int steps = kScoutAll);
+/* the counting sort both scout orders end with: n keys (pred, clamped to 1023) -> order, descending; hist[k] = the keys >= k afterwards;
+ * split.queue != nullptr: the cut of the order too.  One launch where !sort_needs_clear(n); else histogram (hist_blocks blocks), scan over
+ * nbins bins (every key < nbins), scatter — on a hist whose 1024 words the caller has cleared */
+bool sort_needs_clear(size_t n);
+hipError_t sort_desc(const uint16_t *pred, size_t n, int nbins, int hist_blocks, unsigned int *hist, unsigned int *order, const ccmp_split_req &split,
+                     hipStream_t st);
 hipError_t fd_split(const unsigned int *hist, int pred_min, unsigned int limit, unsigned long long *queue, hipStream_t st);
 hipError_t geo_split(const unsigned int *hist, int p_min, int p_max, int permille, unsigned long long *queue, hipStream_t st);
 hipError_t geodesic(const GeoCall &g, const GeoLaunch &l, hipStream_t st);

@@ -3,8 +3,8 @@
  * The default library (lib/libccmp.so) exports none of these symbols and does not know the options named here; the same sources
  * built with -DCCMP_DEBUG_HOOKS (closed_chain_motion_planner_amd/build.py links them as lib/libccmp_debug.so beside the default
  * library — every kernel object is shared, only ccmp_api.cpp and ccmp_policy.cpp are compiled twice) do.  The GPU suite runs the
- * two tests that need a hook in a process of their own against the debug library (tests/test_gpu_debug_hooks.py); tools/ that
- * read the scout's predictions select it through CCMP_LIBRARY.
+ * tests that need a hook in processes of their own against the debug library (tests/test_gpu_debug_hooks.py, test_gpu_scout_slices.py,
+ * test_gpu_scout_sort.py); tools/ that read the scout's predictions select it through CCMP_LIBRARY.
  *
  * The reference has no counterpart for any of this (no tracing, no fault injection). */
 #ifndef CCMP_DEBUG_H
@@ -26,6 +26,25 @@ int ccmp_detmath_div_probe(ccmp_ctx *ctx, const double *n_dev, const double *d_d
 int ccmp_ctx_set_order_experimental(ccmp_ctx *ctx, const unsigned int *order_dev);
 /* a copy of the FP32 scout's predicted iteration counts of the last call that ran one */
 int ccmp_ctx_debug_lpt_pred(ccmp_ctx *ctx, uint16_t *host_out, size_t B);
+/* beside it: the processing order the counting sort made of those predictions (order_host[n]), the sort's histogram (hist_host[1024]: at k
+ * the number of keys >= k) and the context's queue words (queue_host[queue_words]; queue_words must be the library's count, 83) as the
+ * last call left them */
+int ccmp_ctx_debug_lpt_order(ccmp_ctx *ctx, unsigned int *order_host, size_t n, unsigned int *hist_host, unsigned long long *queue_host,
+                             size_t queue_words);
+/* the scouts' descending counting sort on the caller's device buffers: keys_dev[n] (uint16, clamped to 1023) -> order_dev[n], hist_dev[1024],
+ * and — kind 1 or 2 — the cut of the order into queue_dev (a block of 16 64-bit words: 0, 3, 4 = the front's length, the other words
+ * below `clear` zeroed, the rest untouched).  Above 16 384 keys (the three-kernel form) every key must be below nbins, the histogram runs on
+ * hist_blocks blocks, and clear_first != 0 clears hist_dev first as the library's callers do (0: it must hold zeros already); at or
+ * below, one launch that ignores all three.  What would make a kernel leave the buffers is refused with CCMP_EINVAL.  kind 1: the keys >= p_low, at most limit; kind 2: >= p_high where those carry permille / 1000 of the sum of the keys, else
+ * >= p_low; kind 0: no cut, queue_dev is not touched */
+int ccmp_debug_sort_probe(ccmp_ctx *ctx, const uint16_t *keys_dev, size_t n, int nbins, int hist_blocks, int clear_first, unsigned int *order_dev,
+                          unsigned int *hist_dev, unsigned long long *queue_dev, int kind, int p_low, int p_high, int permille, unsigned int limit,
+                          int clear, void *hip_stream);
+/* the two stand-alone cut kernels on a caller-supplied histogram hist_dev[1024] (at k: keys >= k); they write words 0, 3 and 4 of queue_dev.
+ * kernel 1: the keys >= p_min, at most limit; kernel 2: the largest cut P in (p_min, p_max] whose front carries permille / 1000 of the sum
+ * of the keys, else p_min */
+int ccmp_debug_split_probe(ccmp_ctx *ctx, int kernel, const unsigned int *hist_dev, int p_min, int p_max, int permille, unsigned int limit,
+                           unsigned long long *queue_dev, void *hip_stream);
 /* fault injection: the next n compute entry points of this context return CCMP_EHIP before anything is launched */
 int ccmp_debug_fail_calls(ccmp_ctx *ctx, int n);
 /* option "fail_after_fork" (ccmp_ctx_set_option; listed by ccmp_ctx_option_info of the debug library only): 1 / 2 = the split
