@@ -80,6 +80,11 @@ class CcmpSmoothOpts(C.Structure):
                 ("tile_edges", C.c_int)]
 
 
+class CcmpResampleOpts(C.Structure):
+    """ccmp_resample_opts of include/ccmp.h"""
+    _fields_ = [("count", C.c_int), ("spacing", C.c_double), ("max_rows", C.c_int)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -114,6 +119,9 @@ EXPORTS = [
     "ccmp_shortcut_select_ref", "ccmp_shortcut_pairs_ref",
     "ccmp_smooth_opts_default", "ccmp_path_smooth", "ccmp_path_smooth_host", "ccmp_smooth_mid_ref", "ccmp_smooth_len_after",
     "ccmp_smooth_last_counts",
+    "ccmp_resample_opts_default", "ccmp_path_resample", "ccmp_sampled_paths_info", "ccmp_sampled_paths_copy", "ccmp_sampled_paths_copy_host",
+    "ccmp_sampled_paths_destroy", "ccmp_path_timestamps", "ccmp_path_timestamps_host", "ccmp_path_timestamps_ref", "ccmp_arc_bracket_ref",
+    "ccmp_resample_targets_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -320,6 +328,17 @@ def lib():
         "ccmp_smooth_mid_ref": ([dp, dp, C.c_int, C.POINTER(C.c_int), dp, dp, C.POINTER(C.c_int)], C.c_int),
         "ccmp_smooth_len_after": ([C.c_int, C.c_int], C.c_int),
         "ccmp_smooth_last_counts": ([C.POINTER(C.c_longlong)] * 3, None),
+        "ccmp_resample_opts_default": ([pp, C.POINTER(CcmpResampleOpts)], None),
+        "ccmp_path_resample": ([vp, pp, vp, C.POINTER(CcmpResampleOpts), C.POINTER(vp), vp], C.c_int),
+        "ccmp_sampled_paths_info": ([vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_sampled_paths_copy": ([vp] + [vp] * 7 + [vp], C.c_int),
+        "ccmp_sampled_paths_copy_host": ([vp, dp, i32p, dp, dp, u8p, i32p, i32p], C.c_int),
+        "ccmp_sampled_paths_destroy": ([vp], None),
+        "ccmp_path_timestamps": ([vp, vp, vp, C.c_size_t, C.c_size_t, dp, dp, C.c_double, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ccmp_path_timestamps_host": ([vp, dp, i32p, C.c_size_t, C.c_size_t, dp, dp, C.c_double, dp, dp, dp, dp, i32p], C.c_int),
+        "ccmp_path_timestamps_ref": ([dp, i32p, C.c_size_t, C.c_size_t, dp, dp, C.c_double, dp, dp, dp, dp, i32p], C.c_int),
+        "ccmp_arc_bracket_ref": ([dp, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)], C.c_int),
+        "ccmp_resample_targets_ref": ([C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), dp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -366,6 +385,8 @@ GRAPH_MAX_ROOTS, CLOSEST_MAX_FROM = 32, 64  # ccmp.h: CCMP_GRAPH_MAX_ROOTS, CCMP
 PATH_MAX_PAIRS = 64  # ccmp.h: CCMP_PATH_MAX_PAIRS
 DENSE_DISTINCT = 1  # ccmp.h: CCMP_DENSE_DISTINCT
 SHORTCUT_MAX_LEN = 1024  # ccmp.h: CCMP_SHORTCUT_MAX_LEN
+RETIME_OK, RETIME_EMPTY, RETIME_BROKEN, RETIME_NONFINITE, RETIME_POINT, RETIME_FULL = range(6)  # ccmp.h: CCMP_RETIME_*
+SAMPLE_PROJECTED, SAMPLE_FALLBACK, SAMPLE_DEGENERATE, SAMPLE_COPIED = range(4)  # ccmp.h: CCMP_SAMPLE_*
 
 
 def option_table():

@@ -510,7 +510,7 @@ class KinematicChainConstraint:
         return out
 
     def densify_paths(self, path_joints, path_len, scene=None, margin=None, distinct=False, chunk_states=16, round_budget=128, max_calls=4096,
-                      stream=None):
+                      stream=None, keep_handle=False):
         """`PathGeometric::interpolate` for F solution paths (ccmp_path_densify; csrc/ccmp_dense.h): path_joints (F,max_len,14) and
         path_len (F,) int32 as `Roadmap.shortest_paths` returns them ("joints", "path_len"), on the device.  Every segment is
         traversed to its end inside the library, whatever chunk_states / round_budget cut it into; the state lists stay on the
@@ -519,11 +519,38 @@ class KinematicChainConstraint:
         Returns a dict of device tensors — joints (rows,14), path_first (F+1,), seg_first / seg_ok / seg_newton (F,max_len-1),
         arc (rows,), length (F,) and, with a ProxyScene and its margin, clearance (rows,), min_clear / min_row / first_blocked (F,) —
         plus rows and calls (the extend calls made).  numpy arrays go through the host form and come back as numpy arrays.
-        Synchronous.  max_calls spent with a segment open raises CcmpError (CCMP_EOVERFLOW): a cut list never looks complete."""
+        Synchronous.  max_calls spent with a segment open raises CcmpError (CCMP_EOVERFLOW): a cut list never looks complete.
+        keep_handle=True adds "handle", the result as the library keeps it (`dense.DenseHandle`): what `resample_paths` reads."""
         from .dense import densify
 
         self._need_problem()
-        return densify(self.ctx, self.problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream)
+        return densify(self.ctx, self.problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream, keep_handle)
+
+    def resample_paths(self, dense, count=None, spacing=None, max_rows=65536, stream=None):
+        """`PathGeometric::interpolate(count)` with this project's blend (ccmp_path_resample; csrc/ccmp_retime.h): every path of a dense
+        result — the dict of `densify_paths(..., keep_handle=True)` — resampled at even arc, count rows per path or, by default, one row
+        every `spacing` of arc (default: the problem's delta).  The first and last rows are copied; every other row is the blend at its
+        target arc put back on the manifold by ONE projector call for all paths, or, where the projection fails, the nearer dense row.
+        Returns a dict in the kind of the dense result's arrays (device tensors, or numpy) — joints (rows,14), path_first (F+1,), arc
+        (rows,), length (F,), kind (rows,) uint8 (SAMPLE_KINDS), status (F,) (RETIME_STATUS: a path that is empty, broken — a segment with
+        seg_ok == 0 —, not finite or over max_rows gets no rows; one without length one row), counts (F,4) — plus rows.  Synchronous.
+        Resampled rows are new states: they go to the host's validity test before use."""
+        from .retime import resample
+
+        self._need_problem()
+        return resample(self.ctx, self.problem, dense, count, spacing, max_rows, stream)
+
+    def timestamp_paths(self, rows, path_first, vmax, amax, beta=0.5, profile=False, stream=None):
+        """Time stamps for packed rows under joint velocity and acceleration limits (ccmp_path_timestamps; csrc/ccmp_retime.h): rows
+        (R,14) and path_first (F+1,) int32 as `resample_paths` or `densify_paths` return them, vmax / amax 14 numbers each (the limits
+        of both arms, e.g. PANDA_VELOCITY_LIMITS * 2), beta in (0, 1) the share of the acceleration budget given to curvature.  Every
+        path starts and ends at rest.  Returns a dict — time (R,), duration (F,), status (F,) and, with profile=True, ceiling and
+        envelope (R,) — of device tensors, asynchronous on the stream, or of numpy arrays through the host form.  The limits hold for
+        the speed profile at the rows (every interval's mean speed is within vmax); they are not a bound on finite differences of the
+        sampled trajectory."""
+        from .retime import timestamps
+
+        return timestamps(self.ctx, rows, path_first, vmax, amax, beta, profile, stream)
 
     def shortcut_paths(self, path_joints, path_len, scene=None, margin=None, max_span=0, chunk_states=16, round_budget=128, max_calls=4096,
                        tile_edges=65536, pairs=False, stream=None):

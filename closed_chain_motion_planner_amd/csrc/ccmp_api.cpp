@@ -173,6 +173,7 @@ void ccmp_ctx_destroy(ccmp_ctx *ctx)
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->geo_pool) (void)hipFree(ctx->geo_pool);
   if (ctx->knn_ws) (void)hipFree(ctx->knn_ws);
+  if (ctx->retime_ws) (void)hipFree(ctx->retime_ws);
   if (ctx->connect_ws) (void)hipFree(ctx->connect_ws);
   if (ctx->ik_ws) (void)hipFree(ctx->ik_ws);
   if (ctx->ik_vet_ws) (void)hipFree(ctx->ik_vet_ws);

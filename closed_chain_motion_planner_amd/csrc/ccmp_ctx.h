@@ -93,6 +93,8 @@ struct ccmp_ctx {
   size_t scan_cap = 0;
   void *knn_ws = nullptr;              // k-NN: the partitions' lists (ccmp_launch.h: KnnShape)
   size_t knn_ws_cap = 0;               // in bytes
+  void *retime_ws = nullptr;           // ccmp_path_timestamps: status-independent scratch, A bits [F] | ceiling [rows] | envelope [rows] (ccmp_retime.cpp)
+  size_t retime_ws_cap = 0;            // in bytes
   double *connect_ws = nullptr;        // ccmp_connect_batch: the gathered endpoints, from [E][14] then to [E][14]
   size_t connect_ws_cap = 0;           // in edges
   void *ik_ws = nullptr;               // ccmp_pose_ik_batch: the candidates' records, q [C][7] | d2 [C] | rounds [C] (ccmp_launch.h: IkCall)

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; }
+namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; struct retime_limits; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -274,6 +274,25 @@ hipError_t smooth_length(const double *buf0, const double *buf1, const uint8_t *
 /* out_joints[f][k] = the path's row k for k < len[f]; rows behind are not written */
 hipError_t smooth_store(const double *buf0, const double *buf1, const uint8_t *where, const int32_t *len, size_t F, int cap, double *out_joints,
                         hipStream_t st);
+/* resample and time stamps (ccmp_path_resample, ccmp_path_timestamps; csrc/ccmp_retime.h).  status [F] of the packed rows' paths: EMPTY (also a
+ * range that is negative, decreasing or beyond total_rows), NONFINITE, else OK; a_bits [F] (nullable) reset to "no interval yet" */
+hipError_t retime_status(const double *rows, const int32_t *path_first, size_t F, size_t total_rows, int32_t *status, unsigned long long *a_bits, hipStream_t st);
+/* per output row g < M of the paths' output ranges out_first [F + 1]: x[g] = the blend at h_j (a copied or degenerate row: its source row),
+ * choice[g] = the fallback (or source) dense row, kind[g] = the kind so far (kRetimePending: the projector's flag decides) */
+hipError_t resample_bracket(const double *rows, const double *arc, const int32_t *path_first, const int32_t *status, const int32_t *out_first, size_t F, size_t M,
+                            size_t total_rows, double *x, int32_t *choice, uint8_t *kind, hipStream_t st);
+/* out_rows[g] = y[g] (projected) or the dense row choice[g]; kind [M] final; counts [F][4] are added to */
+hipError_t resample_pick(const double *rows, const int32_t *out_first, size_t F, size_t M, size_t total_rows, const int32_t *choice, const uint8_t *kind_so_far,
+                         const double *y, const uint8_t *ok, double *out_rows, uint8_t *kind, int32_t *counts, hipStream_t st);
+/* ceiling[r] = x_i of every row of an OK path; a_bits[f] = the bits of the path's minimum of A */
+hipError_t retime_ceiling(const double *rows, const int32_t *path_first, size_t F, size_t total_rows, const int32_t *status, const ccmp::retime_limits &lim,
+                          double *ceiling, unsigned long long *a_bits, hipStream_t st);
+/* envelope[r] = y_i */
+hipError_t retime_envelope(const double *ceiling, const int32_t *path_first, size_t F, size_t total_rows, const int32_t *status, const unsigned long long *a_bits,
+                           double *envelope, hipStream_t st);
+/* time[r] and duration[f]; rows of a path that is not OK are not written, its duration is +0.0 (EMPTY) or NaN (NONFINITE) */
+hipError_t retime_stamp(const double *rows, const double *envelope, const int32_t *path_first, const int32_t *status, const unsigned long long *a_bits,
+                        const ccmp::retime_limits &lim, size_t F, double *time, double *duration, hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

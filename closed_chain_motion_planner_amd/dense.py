@@ -7,9 +7,34 @@ from . import _lib
 from ._arrays import HOST, _torch, kind_of
 from ._lib import CcmpDenseOpts, check
 
-__all__ = ["dense_layout_ref", "dense_arc_ref", "DENSE_DISTINCT"]
+__all__ = ["dense_layout_ref", "dense_arc_ref", "DENSE_DISTINCT", "DenseHandle"]
 
 DENSE_DISTINCT = _lib.DENSE_DISTINCT
+
+
+class DenseHandle:
+    """A dense result kept where the library made it (ccmp_dense_paths), for `KinematicChainConstraint.resample_paths`: what
+    `densify_paths(..., keep_handle=True)` returns under "handle".  close() (or the garbage collector) releases it."""
+
+    def __init__(self, h):
+        self._h = h
+
+    def close(self):
+        if self._h:
+            _lib.lib().ccmp_dense_paths_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _path_inputs(ctx, path_joints, path_len, K=None):
@@ -51,7 +76,7 @@ def dense_arc_ref(rows, path_first):
     return arc, length
 
 
-def densify(ctx, problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream):
+def densify(ctx, problem, path_joints, path_len, scene, margin, distinct, chunk_states, round_budget, max_calls, stream, keep_handle=False):
     """the body of `KinematicChainConstraint.densify_paths`"""
     opts = CcmpDenseOpts(DENSE_DISTINCT if distinct else 0, int(chunk_states), int(round_budget), int(max_calls))
     if scene is not None and margin is None:
@@ -76,6 +101,9 @@ def densify(ctx, problem, path_joints, path_len, scene, margin, distinct, chunk_
             (torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(stream) if isinstance(stream, int) else stream).synchronize()
         out["rows"] = R
         out["calls"] = int(calls.value)
+        if keep_handle:
+            out["handle"], h = DenseHandle(h), None  # the result stays with the caller
         return out
     finally:
-        _lib.lib().ccmp_dense_paths_destroy(h)
+        if h is not None:
+            _lib.lib().ccmp_dense_paths_destroy(h)

@@ -524,6 +524,23 @@ class Roadmap:
             return None
         return sol[0], sol[1], self._dense(constraint, sol[2], dkw), sol[3], sol[4]
 
+    def timed_solution(self, constraint, starts, goals, vmax, amax, beta=0.5, count=None, spacing=None, max_rows=65536, max_len=64, **kw):
+        """solution -> shortcut -> smooth -> densify -> resample -> time stamps on device tensors: `dense_smooth_solution` (kw: its keyword
+        arguments), then `constraint.resample_paths` on the dense result where the library keeps it and `constraint.timestamp_paths` on
+        the new rows.  Returns (duration, indices, sampled, stamps, dense, smooth, shortcut) with sampled and stamps the dicts of the two
+        calls, or None when no pair is connected.  The resampled rows are new states: put sampled["joints"] to the host's validity test
+        before the times are used."""
+        sol = self.dense_smooth_solution(constraint, starts, goals, max_len=max_len, keep_handle=True, **kw)
+        if sol is None:
+            return None
+        _, idx, dense, sm, sc = sol
+        try:
+            sampled = constraint.resample_paths(dense, count=count, spacing=spacing, max_rows=max_rows)
+        finally:
+            dense.pop("handle").close()  # the dense arrays stay; the library's copy goes
+        stamps = constraint.timestamp_paths(sampled["joints"], sampled["path_first"], vmax, amax, beta=beta)
+        return float(stamps["duration"][0]), idx, sampled, stamps, dense, sm, sc
+
     def close(self):
         if self._h:
             _lib.lib().ccmp_roadmap_destroy(self._h)

@@ -1180,6 +1180,82 @@ int ccmp_smooth_mid_ref(const double *rows, const double *arcs, int n, int *k, d
 int ccmp_smooth_len_after(int L, int passes);
 void ccmp_smooth_last_counts(long long *extend_calls, long long *project_calls, long long *bytes_read);
 
+/* ---- executing a path: resample at even arc, then time stamps under joint limits --------------------------------------------------- */
+/* The reference executes its path by giving every printed row the same time slice (scripts/execute_path.py:105-108, 2.5 s in all); dense
+ * rows are not evenly spaced and nothing relates that time to what the joints can do.  Two steps close the gap; the rule of both is
+ * csrc/ccmp_retime.h, stated once for the kernels, the host forms and the _ref forms, bit for bit against each other.
+ *     resample       PathGeometric::interpolate(count) with this project's blend.  A dense path (either layout) has rows r_0 .. r_{R-1} and
+ *                    arcs s, T = s_{R-1}.  status [F], tested in this order: CCMP_RETIME_EMPTY R == 0; _BROKEN a segment of the path has
+ *                    seg_ok == 0 (the path has a jump); _NONFINITE a row is not finite in all 14 coordinates; _POINT not T > 0 (one row out:
+ *                    r_0); _FULL N > max_rows; else _OK, N rows out.  N = count when count >= 2, else 1 + (int64)ceil(T / spacing) in IEEE
+ *                    double (beyond INT32_MAX: _FULL).  Row 0 = r_0 and row N-1 = r_{R-1} (CCMP_SAMPLE_COPIED); for 0 < j < N-1:
+ *                    h_j = fl(fl((double)j / (double)(N-1)) * T); not h_j > 0: r_0 (_DEGENERATE); else k = the smallest k >= 1 with
+ *                    s_k >= h_j, t = (h_j - s_{k-1}) / (s_k - s_{k-1}), x = the extend step's interpolate(r_{k-1}, r_k, t), (y, ok) =
+ *                    project(x) in the problem's Jacobian mode; ok: y (_PROJECTED); else r_{k-1} when (h_j - s_{k-1}) <= (s_k - h_j), else r_k
+ *                    (_FALLBACK).  The result carries its own path_first [F + 1], arc [rows] and length [F] (the dense arc rule on the new
+ *                    rows), kind [rows] (uint8), status [F] and counts [F][4] (int32, indexed by kind).  Resampled rows are NEW states: they
+ *                    go to the host's validity test before use.
+ *     time stamps    on any packed rows [total_rows][14] with path_first [F + 1]; the path parameter is the row index.  vmax[14], amax[14]
+ *                    (HOST arrays in every form: checked before the first launch, handed to the kernels by value) finite and > 0;
+ *                    0 < beta < 1 = the share of the acceleration budget given to curvature.  status [F]: _EMPTY, _NONFINITE, else _OK.
+ *                    One row: t_0 = +0.0.  Otherwise d_i[c] = r_{i+1}[c] - r_i[c] (the plain difference, not interpolate's wrap),
+ *                    V_i = min_c vmax_c / |d_i[c]|; ceilings on z = (index speed)^2: x_0 = x_{R-1} = +0.0, interior x_i = min(V_{i-1}^2,
+ *                    V_i^2, min_c fl(beta amax_c) / |d_i[c] - d_{i-1}[c]|); A = min_{i,c} fl((1 - beta) amax_c) / |d_i[c]|, g = 2 A;
+ *                    envelope y_i = min_k e(i, k), e(i, i) = x_i, e(i, k) = fl(x_k + fl(g |i - k|)); R >= 3: dt_i = 2 / (sqrt(y_i) +
+ *                    sqrt(y_{i+1})); R == 2: dt_0 = 2 / sqrt(min(V_0^2, fl(0.5 g))); t_0 = +0.0, t_{i+1} = fl(t_i + dt_i); duration [F]
+ *                    = t_{R-1} (+0.0 for _EMPTY, NaN for _NONFINITE, whose time / ceiling / envelope rows are not written).
+ *                    By construction y_i <= x_i, 1 / dt_i <= V_i (the velocity limit on every interval) and |y_{i+1} - y_i| <= g up to
+ *                    rounding: at the grid rows |q''| z <= beta amax and |q'| |z'| / 2 <= (1 - beta) amax.  That bounds the PROFILE; it is
+ *                    NOT a bound on finite differences of the sampled trajectory.
+ *   ccmp_path_resample   reads a dense result where it lies.  SYNCHRONOUS on its stream (it reads path_first, the F lengths, seg_first /
+ *                    seg_ok and F status words to size the result): not capturable.  The blends of all paths go through the projector in
+ *                    ONE ccmp_project_batch call.  opts == NULL: the defaults.  On any error no handle and no partial output.
+ *   ccmp_resample_opts_default   count 0, spacing = the problem's delta (0 for a NULL problem), max_rows 65 536.
+ *   ccmp_sampled_paths_info / _copy / _copy_host / _destroy   the result: F and the row count; copies into device (asynchronous on
+ *                    hip_stream) or host (synchronous) destinations, each nullable: rows_out [rows][14], path_first [F + 1], arc [rows],
+ *                    length [F], kind [rows], status [F], counts [F][4].
+ *   ccmp_path_timestamps   device pointers (rows, path_first, time [total_rows], duration [F], status [F]; ceiling, envelope [total_rows]
+ *                    nullable), asynchronous on hip_stream, no host read: capturable once the context's workspace holds the call (A per
+ *                    path, and a ceiling / envelope array where the caller gave none: the first call at a size grows it — never capture
+ *                    that one).  total_rows is what the caller sized `time` by.  path_first cannot be checked on the host here: a path
+ *                    whose range is negative, decreasing or beyond total_rows is never read and answers _EMPTY.
+ *   _host            host pointers, synchronous on the context's stream; rows of time / ceiling / envelope that the rule does not write
+ *                    keep the caller's values.
+ *   ccmp_path_timestamps_ref   the same rule text as pure host code, one thread, no device, never CCMP_ENODEV.
+ *   ccmp_arc_bracket_ref   the bracket alone: arcs [n], n >= 2, 0 < h <= arcs[n-1] (else CCMP_EINVAL) -> *k, *t, *lower.
+ *   ccmp_resample_targets_ref   the count and the targets alone: *N = the rows out (1 when not T > 0, 0 for _FULL), h_out [*N] (nullable) =
+ *                    +0.0, the h_j, T.
+ * Conventions as everywhere: every check runs before the first launch; a NULL context answers CCMP_ENODEV without a device and CCMP_EINVAL
+ * with one; F == 0 gives an empty result / touches nothing.  CCMP_EINVAL: count == 1 or < 0, count 0 with spacing not > 0, max_rows < 2, a
+ * limit that is not finite and positive, beta outside (0, 1), (host and _ref forms) a path_first that is negative, decreases or ends beyond
+ * total_rows, a dense result of another device, a NULL dense, out, vmax, amax, path_first, duration or status, NULL rows or time with
+ * total_rows > 0.  Order of use: shortcut -> smooth -> densify -> resample -> the host's validity test over the new rows -> time stamps. */
+enum { CCMP_RETIME_OK = 0, CCMP_RETIME_EMPTY = 1, CCMP_RETIME_BROKEN = 2, CCMP_RETIME_NONFINITE = 3, CCMP_RETIME_POINT = 4, CCMP_RETIME_FULL = 5 };
+enum { CCMP_SAMPLE_PROJECTED = 0, CCMP_SAMPLE_FALLBACK = 1, CCMP_SAMPLE_DEGENERATE = 2, CCMP_SAMPLE_COPIED = 3 };
+typedef struct ccmp_resample_opts {
+  int count;      /* rows out per path, >= 2; 0 = by spacing */
+  double spacing; /* arc between rows when count == 0, > 0 */
+  int max_rows;   /* a path that would get more rows is CCMP_RETIME_FULL, >= 2 */
+} ccmp_resample_opts;
+void ccmp_resample_opts_default(const ccmp_problem *p, ccmp_resample_opts *opts);
+typedef struct ccmp_sampled_paths ccmp_sampled_paths;
+int ccmp_path_resample(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_dense_paths *dense, const ccmp_resample_opts *opts, ccmp_sampled_paths **out,
+                       void *hip_stream);
+int ccmp_sampled_paths_info(const ccmp_sampled_paths *h, size_t *F, size_t *rows);
+int ccmp_sampled_paths_copy(ccmp_sampled_paths *h, double *rows_out, int32_t *path_first, double *arc, double *length, uint8_t *kind, int32_t *status,
+                            int32_t *counts, void *hip_stream);
+int ccmp_sampled_paths_copy_host(ccmp_sampled_paths *h, double *rows_out, int32_t *path_first, double *arc, double *length, uint8_t *kind, int32_t *status,
+                                 int32_t *counts);
+void ccmp_sampled_paths_destroy(ccmp_sampled_paths *h);
+int ccmp_path_timestamps(ccmp_ctx *ctx, const double *rows, const int32_t *path_first, size_t F, size_t total_rows, const double *vmax, const double *amax,
+                         double beta, double *time, double *duration, double *ceiling, double *envelope, int32_t *status, void *hip_stream);
+int ccmp_path_timestamps_host(ccmp_ctx *ctx, const double *rows, const int32_t *path_first, size_t F, size_t total_rows, const double *vmax,
+                              const double *amax, double beta, double *time, double *duration, double *ceiling, double *envelope, int32_t *status);
+int ccmp_path_timestamps_ref(const double *rows, const int32_t *path_first, size_t F, size_t total_rows, const double *vmax, const double *amax, double beta,
+                             double *time, double *duration, double *ceiling, double *envelope, int32_t *status);
+int ccmp_arc_bracket_ref(const double *arcs, int n, double h, int *k, double *t, int *lower);
+int ccmp_resample_targets_ref(double T, int count, double spacing, int max_rows, int *N, double *h_out);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault
  * injection — are not part of this library: include/ccmp_debug.h, lib/libccmp_debug.so) */

@@ -687,6 +687,87 @@ inline int smoothPathLocked(const Projector &proj, std::vector<std::array<double
   return CCMP_OK;
 }
 
+// A solution path resampled at even arc (include/ccmp.h: ccmp_path_densify_host, then ccmp_path_resample on the dense result where the
+// library keeps it — PathGeometric::interpolate(count) with the library's blend): `states` = the waypoints on entry (the smoothed path,
+// say) and the resampled rows on return: `count` rows, or with count == 0 one every `spacing` of arc (spacing <= 0: the problem's delta).
+// The first and the last row are the path's own; every other row is a NEW state — the blend at its arc put back on the manifold, or the
+// nearer dense row where that fails — and goes to the host's isValid before use.  status (nullable) = CCMP_RETIME_*;
+// kinds (nullable) = CCMP_SAMPLE_* per row.  A path that is empty, broken (a segment that stopped short), not finite or over 65 536 rows
+// comes back as it was, with CCMP_OK and its status.  delta / lambda > 0 replace the problem's.  Returns the library's code and leaves
+// `states` untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int resamplePathLocked(const Projector &proj, std::vector<std::array<double, 14>> &states, int count, double spacing, int *status = nullptr,
+                              std::vector<uint8_t> *kinds = nullptr, double delta = 0.0, double lambda = 0.0)
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double), "rows are contiguous");
+  const ccmp_problem P = detail::problemWith(proj, delta, lambda);
+  ccmp_resample_opts ro;
+  ccmp_resample_opts_default(&P, &ro);
+  ro.count = count;
+  if (spacing > 0.0) ro.spacing = spacing;
+  ccmp_dense_opts o;
+  ccmp_dense_opts_default(&o);
+  o.flags = CCMP_DENSE_DISTINCT;
+  static const double none[14] = {0};
+  const int32_t len = (int32_t)states.size();
+  ccmp_dense_paths *dense = nullptr;
+  int rc = ccmp_path_densify_host(proj.ctx(), &P, nullptr, 0.0, len ? states[0].data() : none, &len, 1, len > 0 ? len : 1, &o, &dense);
+  if (rc != CCMP_OK) return rc;
+  ccmp_sampled_paths *h = nullptr;
+  rc = ccmp_path_resample(proj.ctx(), &P, dense, &ro, &h, nullptr);
+  ccmp_dense_paths_destroy(dense);
+  if (rc != CCMP_OK) return rc;
+  size_t rows = 0;
+  int32_t st = CCMP_RETIME_EMPTY;
+  std::vector<std::array<double, 14>> out;
+  std::vector<uint8_t> kd;
+  try {
+    rc = ccmp_sampled_paths_info(h, nullptr, &rows);
+    out.resize(rows);
+    kd.resize(rows);
+  } catch (...) {
+    rc = CCMP_ENOMEM;
+  }
+  if (rc == CCMP_OK) rc = ccmp_sampled_paths_copy_host(h, rows ? out[0].data() : nullptr, nullptr, nullptr, nullptr, rows ? kd.data() : nullptr, &st, nullptr);
+  ccmp_sampled_paths_destroy(h);
+  if (rc != CCMP_OK) return rc;
+  if (status) *status = st;
+  if (st == CCMP_RETIME_OK || st == CCMP_RETIME_POINT) {
+    states.swap(out);
+    if (kinds) kinds->swap(kd);
+  } else if (kinds) {
+    kinds->clear();
+  }
+  return CCMP_OK;
+}
+
+// Time stamps for a path's rows under joint velocity and acceleration limits (include/ccmp.h: ccmp_path_timestamps_host; the path starts
+// and ends at rest): vmax / amax = 14 numbers each, beta in (0, 1) the share of the acceleration budget given to curvature.  times = one
+// per row, times[0] = 0; duration (nullable) = the last.  The limits bound the speed profile at the rows; they are not a bound on finite
+// differences of the sampled trajectory.  A row that is not finite is CCMP_EINVAL.  Returns the library's code and leaves `times`
+// untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int timestampPath(const Projector &proj, const std::vector<std::array<double, 14>> &states, const double *vmax, const double *amax, double beta,
+                         std::vector<double> *times, double *duration = nullptr)
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double), "rows are contiguous");
+  if (!times || states.size() > (size_t)0x7fffffff) return CCMP_EINVAL;
+  const int32_t first[2] = {0, (int32_t)states.size()};
+  std::vector<double> t;
+  try {
+    t.assign(states.size(), 0.0);
+  } catch (...) {
+    return CCMP_ENOMEM;
+  }
+  double total = 0.0;
+  int32_t st = CCMP_RETIME_EMPTY;
+  const int rc = ccmp_path_timestamps_host(proj.ctx(), states.empty() ? nullptr : states[0].data(), first, 1, states.size(), vmax, amax, beta,
+                                           t.empty() ? nullptr : t.data(), &total, nullptr, nullptr, &st);
+  if (rc != CCMP_OK) return rc;
+  if (st == CCMP_RETIME_NONFINITE) return CCMP_EINVAL;
+  times->swap(t);
+  if (duration) *duration = total;
+  return CCMP_OK;
+}
+
 // ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
 // The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
 // rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
@@ -1023,6 +1104,36 @@ public:
     if (call([&] { return smoothPathLocked(proj_, states, max_steps, min_change, nullptr, nullptr, nullptr, nullptr, &lo, delta, lambda); },
              "ccmp_path_smooth_host")) {
       if (cost) *cost = lo;
+    }
+    return true;
+  }
+
+  // constructSmoothSolution followed by the resampling at even arc and the time stamps (ccmp::resamplePathLocked, ccmp::timestampPath
+  // above): `states` = the resampled rows, `times` = one per row, cost = the duration.  On a library error in either step — or a path the
+  // resampling gives no rows for — the answer FALLS BACK to the smooth solution without times (true, `times` empty, cost = the smoothed
+  // length, lastError() set on an error).  false with no states when no pair is connected or the solution step itself failed.  The
+  // resampled rows are new states: validate them on the host before the times are used.
+  bool constructTimedSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states,
+                              std::vector<double> &times, const double *vmax, const double *amax, double beta = 0.5, int count = 0, double spacing = 0.0,
+                              int max_steps = 5, double min_change = 0.005, int max_span = 0, double *cost = nullptr,
+                              std::vector<int32_t> *indices = nullptr, double delta = 0.0, double lambda = 0.0) const noexcept
+  {
+    times.clear();
+    if (!constructSmoothSolution(starts, goals, states, max_steps, min_change, max_span, cost, indices, delta, lambda)) return false;
+    try {
+      std::vector<std::array<double, 14>> rows(states);
+      std::vector<double> t;
+      int status = CCMP_RETIME_EMPTY;
+      double total = 0.0;
+      if (call([&] { return resamplePathLocked(proj_, rows, count, spacing, &status, nullptr, delta, lambda); }, "ccmp_path_resample") &&
+          (status == CCMP_RETIME_OK || status == CCMP_RETIME_POINT) &&
+          call([&] { return timestampPath(proj_, rows, vmax, amax, beta, &t, &total); }, "ccmp_path_timestamps_host")) {
+        states.swap(rows);
+        times.swap(t);
+        if (cost) *cost = total;
+      }
+    } catch (...) {
+      err_.record(CCMP_ENOMEM, "Roadmap::constructTimedSolution");
     }
     return true;
   }
@@ -1444,6 +1555,19 @@ inline void printAsMatrix(std::ostream &out, const double *states, size_t n_stat
   out.flush();
 }
 
+// A time-stamped path: printAsMatrix's row — the reals of one state, each followed by a space — with the row's time as one more column,
+// and the empty line after the last row.  The first `dim` columns of every line are printAsMatrix's, character for character.
+inline void printTrajectory(std::ostream &out, const double *states, const double *times, size_t n_states, size_t dim = 14)
+{
+  for (size_t i = 0; i < n_states; ++i) {
+    for (size_t j = 0; j < dim; ++j) out << states[i * dim + j] << ' ';
+    out << times[i] << ' ';
+    out << '\n';
+  }
+  out << '\n';
+  out.flush();
+}
+
 // PlannerData::printGraphML as ConstrainedProblem::dumpGraph writes `<obj>_node_info.graphml`
 // (include/closed_chain_motion_planner/base/constraints/ConstrainedPlanningCommon.h:73-87): node data = the reals of
 // the milestone joined by commas, directed edges in insertion order with their weight (nullptr = 1 each).
@@ -1858,6 +1982,34 @@ public:
       const ccmp::Projector &proj = chain_->impl();
       std::lock_guard<std::mutex> hold(proj.mutex());
       ccmp::check(ccmp::smoothPathLocked(proj, states, max_steps, min_change, passes, moved, nullptr, nullptr, nullptr, delta_, lambda_), "ccmp_path_smooth_host");
+    });
+  }
+
+  // The path resampled at even arc for execution (ccmp::resamplePathLocked: PathGeometric::interpolate(count) with the library's blend),
+  // under this space's delta and lambda: `states` = the waypoints on entry (behind smoothPath), count rows on return, or with
+  // count_or_0 == 0 one every `spacing` of arc (spacing <= 0: this space's delta).  On a library error, or for a path that cannot be
+  // resampled (a segment that stops short, a non-finite row), the answer is the unchanged path: false, `states` as it was, an error in
+  // KinematicChainConstraint::lastError().  The rows between the first and the last are new states: the host's isValid comes next.
+  bool resamplePath(std::vector<std::array<double, 14>> &states, int count_or_0 = 0, double spacing = 0.0, std::vector<uint8_t> *kinds = nullptr) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      int status = CCMP_RETIME_EMPTY;
+      ccmp::check(ccmp::resamplePathLocked(proj, states, count_or_0, spacing, &status, kinds, delta_, lambda_), "ccmp_path_resample");
+      if (status != CCMP_RETIME_OK && status != CCMP_RETIME_POINT && !states.empty()) ccmp::check(CCMP_EINVAL, "ccmp_path_resample: the path cannot be resampled");
+    });
+  }
+
+  // Time stamps for the rows of a path (ccmp::timestampPath): vmax / amax = 14 joint velocity and acceleration limits, the path starting
+  // and ending at rest.  false with `times` untouched when the call failed (KinematicChainConstraint::lastError()).
+  bool timePath(const std::vector<std::array<double, 14>> &states, const double *vmax, const double *amax, std::vector<double> *times, double beta = 0.5,
+                double *duration = nullptr) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      ccmp::check(ccmp::timestampPath(proj, states, vmax, amax, beta, times, duration), "ccmp_path_timestamps_host");
     });
   }
 

@@ -47,6 +47,8 @@
                                                            continuation and the selection in numpy, 1 and 64 paths of 32 waypoints; writes profiles/shortcut.md
     python tools/measure.py smooth [reps] [file.npz]        smooth solution paths (B-spline passes on the manifold): ccmp_path_smooth, three passes on 1 and 64 paths of 32
                                                            waypoints, both Jacobian modes, the extend calls made and the bytes read on the host; writes profiles/smooth.md
+    python tools/measure.py retime [reps]                   resample and time stamps: ccmp_path_resample and ccmp_path_timestamps on the smooth measurement's inputs,
+                                                           continued (1 and 64 paths), the kind counts; the recorded paths' durations on the CPU; writes profiles/retime.md
     python tools/measure.py smooth_restate <file.npz> [n]   the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
@@ -1555,6 +1557,76 @@ def smooth(argv):
                 "budget 128, wall clock around the synchronous call.  No speed threshold gates this feature.\n\n```\n" + "\n".join(lines) + "\n```\n")
 
 
+def retime(argv):
+    """ccmp_path_resample and ccmp_path_timestamps (KinematicChainConstraint.resample_paths / timestamp_paths) on the smooth measurement's
+    inputs, continued: 1 and 64 paths of 32 waypoints, three smoothing passes, densified, then resampled at the problem's delta and stamped
+    under the Panda's limits, both Jacobian modes; wall clock around each call (resample is synchronous; the stamps are followed by a
+    synchronize), medians; the kind counts.  Then, on the CPU _ref form, the reference's two recorded path files: the duration under the
+    Panda's limits beside the 2.5 s of scripts/execute_path.py, and the largest finite-difference joint acceleration of the stamped
+    trajectory as a multiple of amax (reported, not asserted: the rule bounds the profile, not finite differences).  Writes
+    profiles/retime.md."""
+    import os
+
+    from closed_chain_motion_planner_amd import PANDA_ACCELERATION_LIMITS, PANDA_VELOCITY_LIMITS, RETIME_STATUS, timestamps_ref
+
+    reps = int(argv[0]) if len(argv) > 0 else 9
+    Lw, seed, steps = 32, 0x5C7, 3
+    vmax, amax = PANDA_VELOCITY_LIMITS * 2, PANDA_ACCELERATION_LIMITS * 2
+    ctx = Context(0)
+    lines = []
+
+    def say(text):
+        print(text)
+        lines.append(text)
+
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    pj, pl = _smooth_paths(c, 64, Lw, seed)  # the FD constraint's samples for both modes
+    for mode in (0, 1):
+        c.setJacobianMode(mode)
+        for F in (1, 64):
+            sm = c.smooth_paths(pj[:F].contiguous(), pl[:F].contiguous(), max_steps=steps)
+            dense = c.densify_paths(sm["joints"], sm["out_len"], distinct=True, keep_handle=True)
+            t_rs, t_ts = [], []
+            for i in range(reps + 2):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                rs = c.resample_paths(dense)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                ts = c.timestamp_paths(rs["joints"], rs["path_first"], vmax, amax)
+                torch.cuda.synchronize()
+                if i >= 2:
+                    t_rs.append((t1 - t0) * 1e3)
+                    t_ts.append((time.perf_counter() - t1) * 1e3)
+            dense["handle"].close()
+            status = rs["status"].cpu().numpy()
+            dur = ts["duration"].cpu().numpy()[status == 0]
+            say("%s mode, F = %d smoothed paths, %d dense rows -> %d rows at spacing %.3g; status %s; kinds (projected, fallback, degenerate, copied) %s; "
+                "duration %.2f s per path (median over the OK paths)"
+                % ("analytic" if mode else "FD", F, dense["rows"], rs["rows"], c.problem.delta, {RETIME_STATUS[k]: int((status == k).sum()) for k in sorted(set(status.tolist()))},
+                   rs["counts"].sum(0).cpu().tolist(), float(np.median(dur)) if len(dur) else float("nan")))
+            say("    %-84s %s" % ("ccmp_path_resample (one projector call for all paths; the mirror's copy-out included)", _stat(t_rs)))
+            say("    %-84s %s" % ("ccmp_path_timestamps (four launches, no host read)", _stat(t_ts)))
+    say("")
+    say("the reference's recorded paths, stamped on the CPU (ccmp_path_timestamps_ref) under the Panda's limits, beta 0.5:")
+    for obj in ("Wine_Bottle", "dumbbell"):
+        rows = np.loadtxt(os.path.join("tests", "golden", "paths", obj + "_path.txt"))
+        out = timestamps_ref(rows, np.array([0, len(rows)], dtype=np.int32), vmax, amax)
+        t = out["time"]
+        keep = np.concatenate([[True], np.diff(t) > 0])  # a repeated waypoint row at the same time is one sample
+        q, tt = rows[keep], t[keep]
+        v = np.diff(q, axis=0) / np.diff(tt)[:, None]
+        acc = np.diff(v, axis=0) / (0.5 * (tt[2:] - tt[:-2]))[:, None]
+        say("    %-12s %2d rows: duration %.3f s (scripts/execute_path.py: 2.5 s for every path); largest finite-difference speed %.2f x vmax, acceleration %.2f x amax"
+            % (obj, len(rows), float(out["duration"][0]), float((np.abs(v) / np.array(vmax)).max()), float((np.abs(acc) / np.array(amax)).max())))
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "retime.md"), "w") as f:
+        f.write("# Resample and time stamps on the device: `tools/measure.py retime`\n\n1 x MI355X, one run, seed 0x5C7; the smooth measurement's inputs, continued: "
+                "three smoothing passes, densified (distinct layout), `ccmp_path_resample` at the problem's delta, `ccmp_path_timestamps` under the Panda's data-sheet "
+                "limits; wall clock around each call, no GPU time measured.  No speed threshold gates this feature.  The finite-difference figures are reported, not "
+                "asserted: the rule bounds the speed profile at the rows, not finite differences of the sampled trajectory.\n\n```\n" + "\n".join(lines) + "\n```\n")
+
+
 def smooth_restate(argv):
     """the plain-Python restatement of the smoothing rule (tests/smooth_cases.py on the det oracle) on one host core, on the inputs `smooth`
     wrote, compared bit for bit with the results it wrote: python tools/measure.py smooth_restate <file.npz> [paths]"""
@@ -1653,7 +1725,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
