@@ -848,6 +848,17 @@ int ccmp_detmath_div_probe(ccmp_ctx *ctx, const double *n_dev, const double *d_d
   return CCMP_OK;
 }
 
+int ccmp_detmath_round_facts_probe(ccmp_ctx *ctx, const double *m_dev, const double *y_dev, const unsigned char *store_dev, double *out_dev, size_t n,
+                                   void *hip_stream)
+{
+  if (!ctx || !m_dev || !y_dev || !store_dev || !out_dev || n == 0 || n % 64 != 0) return CCMP_EINVAL;
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return CCMP_ENODEV;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(ccmp_launch::round_facts_probe(m_dev, y_dev, store_dev, out_dev, n, st));
+  return CCMP_OK;
+}
+
 // what the scout's order, histogram and the context's queue words hold behind the last call (ScoutBuffers; ccmp_launch.h: QueueWord)
 int ccmp_ctx_debug_lpt_order(ccmp_ctx *ctx, unsigned int *order_host, size_t n, unsigned int *hist_host, unsigned long long *queue_host, size_t queue_words)
 {

@@ -60,6 +60,25 @@
  * only at an exact zero.  CCMP_LEAN_SQRT runs the same nine steps directly when NO lane of the wavefront holds such an
  * argument (wave-uniform test on the exponent field: 2 instructions) — without the scaling the steps are the very same
  * operations on the very same values, hence the same bits — and the compiler's full expansion otherwise. */
+#if defined(__HIP_DEVICE_COMPILE__) && defined(CCMP_USE_FMA)
+/* the nine steps alone, for a caller that KNOWS its argument lies in 2^-767 <= x < inf (ccmp_kin.h: the quaternion's radicand in an
+ * in-range round of the throughput kernels); anything else gives garbage or NaN, never a trap */
+static __device__ __forceinline__ double ccmp_sqrt_steps(double x)
+{
+  const double y = __builtin_amdgcn_rsq(x);
+  double g = x * y;
+  double h = y * 0.5;
+  const double r = CCMP_FMA(-h, g, 0.5);
+  g = CCMP_FMA(g, r, g);
+  h = CCMP_FMA(h, r, h);
+  double d = CCMP_FMA(-g, g, x);
+  g = CCMP_FMA(d, h, g);
+  d = CCMP_FMA(-g, g, x);
+  return CCMP_FMA(d, h, g);
+}
+#else
+CCMP_HD double ccmp_sqrt_steps(double x) { return __builtin_sqrt(x); }
+#endif
 #if defined(__HIP_DEVICE_COMPILE__) && defined(CCMP_LEAN_SQRT)
 static __device__ __forceinline__ double ccmp_sqrt(double x)
 {
@@ -90,8 +109,9 @@ CCMP_HD double ccmp_sqrt(double x) { return __builtin_sqrt(x); }
  * v_div_fixup returns its input unless an operand is zero, infinite or NaN or the quotient leaves the range.  With both
  * operands in 2^-300 <= |v| < 2^300 none of this happens: ccmp_div_steps runs the remaining operations on the same values, hence
  * the same bits.  CCMP_LEAN_DIV: ccmp_div_lean takes that sequence when every lane of the wavefront qualifies (wave-uniform test),
- * the compiler's expansion otherwise; without it (and on the host) both are n / d. */
-#if defined(__HIP_DEVICE_COMPILE__) && defined(CCMP_LEAN_DIV) && defined(CCMP_USE_FMA)
+ * the compiler's expansion otherwise; without it (and on the host) it is n / d.  ccmp_div_steps itself exists in every device unit
+ * of the rounding model, for a caller that KNOWS its operands qualify (ccmp_kin.h: 0.5 / t with t in [1, 2]); on the host it is n / d. */
+#if defined(__HIP_DEVICE_COMPILE__) && defined(CCMP_USE_FMA)
 static __device__ __forceinline__ double ccmp_div_steps(double n, double d)
 {
   const double r0 = __builtin_amdgcn_rcp(d);
@@ -103,6 +123,10 @@ static __device__ __forceinline__ double ccmp_div_steps(double n, double d)
   const double rem = CCMP_FMA(-d, m, n);
   return CCMP_FMA(rem, r2, m);
 }
+#else
+CCMP_HD double ccmp_div_steps(double n, double d) { return n / d; }
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && defined(CCMP_LEAN_DIV) && defined(CCMP_USE_FMA)
 static __device__ __forceinline__ bool ccmp_div_operand_plain(double v)
 {
   /* 2^-300 <= |v| < 2^300  <=>  0x2d300000 <= high dword without its sign < 0x52b00000 */
@@ -115,7 +139,6 @@ static __device__ __forceinline__ double ccmp_div_lean(double n, double d)
   return n / d;
 }
 #else
-CCMP_HD double ccmp_div_steps(double n, double d) { return n / d; }
 CCMP_HD double ccmp_div_lean(double n, double d) { return n / d; }
 #endif
 
@@ -175,8 +198,10 @@ CCMP_HD double ccmp_kernel_cos(double x, double y)
   return w1 + (((1.0 - w1) - hz) + CCMP_FMA(z, r, -(x * y)));
 }
 
-/* Simultaneous sine and cosine.  NaN for non-finite or |x| >= CCMP_SINCOS_MAX. */
-CCMP_HD void ccmp_sincos(double x, double *s_out, double *c_out)
+/* Simultaneous sine and cosine, both forms in one text.  INR = 0: ccmp_sincos.  INR = 1 (a literal at the call: the tests on it
+ * fold away): for a caller that KNOWS |x| < CCMP_SINCOS_MAX — no range test, no replacement, no NaN region, the same operations on
+ * the same values otherwise, hence ccmp_sincos's bits. */
+CCMP_HD void ccmp_sincos_form(const int INR, double x, double *s_out, double *c_out)
 {
   const double invpio2 = CCMP_K(0, 6.36619772367581382433e-01);
   const double pio2_1 = CCMP_K(1, 1.57079632673412561417e+00);  /* first 33 bits of pi/2 */
@@ -185,7 +210,7 @@ CCMP_HD void ccmp_sincos(double x, double *s_out, double *c_out)
   double t = ccmp_abs(x);
   /* out of range (or not finite): the reduction below runs on zero instead and its result is replaced at the end —
    * one rarely-taken region instead of an if/else around the whole function */
-  const int bad = !(t < CCMP_SINCOS_MAX);
+  const int bad = !INR && !(t < CCMP_SINCOS_MAX);
   if (bad) t = 0.0;
   /* n = nearest multiple of pi/2; fn*pio2_1 is exact (33 + 20 bits) */
   int n = (int)CCMP_FMA(t, invpio2, 0.5);
@@ -203,7 +228,7 @@ CCMP_HD void ccmp_sincos(double x, double *s_out, double *c_out)
   double s = (n & 1) ? kc : ks;
   double c = (n & 1) ? ks : kc;
   if (n & 2) s = -s;
-  if ((n + 1) & 2) c = -c;
+  if (((unsigned)n + 1u) & 2u) c = -c; /* unsigned: with INR a lane without a sample may have saturated n; the same bit for every n */
   s = x < 0.0 ? -s : s;
   if (bad) {
     double nan = (x - x) / (x - x); /* NaN for inf, NaN and out-of-range finite x alike */
@@ -213,6 +238,12 @@ CCMP_HD void ccmp_sincos(double x, double *s_out, double *c_out)
   *s_out = s;
   *c_out = c;
 }
+/* NaN for non-finite or |x| >= CCMP_SINCOS_MAX. */
+CCMP_HD void ccmp_sincos(double x, double *s_out, double *c_out) { ccmp_sincos_form(0, x, s_out, c_out); }
+/* The in-range form.  The throughput kernels' stencil points in an in-range round (ccmp_kin.h: rot_x0_round_ok, |x_j| <= 512, so
+ * |y| <= 512 + 3 h < 513) are such arguments.  One that is out of range after all — a lane whose group holds no sample — gets
+ * garbage or NaN: the conversion saturates, nothing traps, nothing loops. */
+CCMP_HD void ccmp_sincos_inr(double x, double *s_out, double *c_out) { ccmp_sincos_form(1, x, s_out, c_out); }
 
 /* atan(x) for any double (NaN propagates). */
 CCMP_HD double ccmp_atan(double x)

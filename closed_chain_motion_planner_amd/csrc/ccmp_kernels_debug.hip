@@ -3,7 +3,7 @@
 // probe reports is what project_fd_kernel computes with.
 #include <hip/hip_runtime.h>
 
-#include "ccmp_detmath.h"
+#include "ccmp_kin.h"
 #include "ccmp_launch.h"
 
 namespace {
@@ -32,7 +32,40 @@ __global__ void div_probe_kernel(const double *__restrict__ num, const double *_
   out[3 * i + 2] = num[i] / den[i];
 }
 
+// The forms an in-range round of the throughput kernels runs (ccmp_kin.h: quat_of_t<true>, ccmp_detmath.h: ccmp_sincos_inr)
+// beside the forms they stand in for, one matrix (9 doubles) and one angle per lane, one wavefront per block so that a block of 64
+// inputs is exactly what one wavefront's case test sees.  out[i] = {quat_of_t<true> (4), quat_of (4), ccmp_sincos_inr (2),
+// ccmp_sincos (2), the path the wavefront took AS quat_of_t REPORTS IT from inside its branch: case 0..3, or 4 for the branch-free text}; a lane with store[i] == 0
+// computes on whatever it was given — NaN, garbage — and writes nothing, as a lane without a live sample does in the kernels.
+__global__ __launch_bounds__(64) void round_facts_probe_kernel(const double *__restrict__ m, const double *__restrict__ y,
+                                                               const unsigned char *__restrict__ store, double *__restrict__ out)
+{
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  double a[9], qt[4], qf[4], s1, c1, s0, c0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) a[k] = m[9 * i + k];
+  int path = -1; // reported by quat_of_t itself, from inside the branch it took
+  ccmp::quat_of_t<true>(a, qt, &path);
+  ccmp::quat_of(a, qf);
+  ccmp_sincos_inr(y[i], &s1, &c1);
+  ccmp_sincos(y[i], &s0, &c0);
+  if (store[i]) {
+    double *o = out + 13 * i;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { o[k] = qt[k]; o[4 + k] = qf[k]; }
+    o[8] = s1; o[9] = c1; o[10] = s0; o[11] = c0;
+    o[12] = (double)path;
+  }
+}
+
 } // namespace
+
+hipError_t ccmp_launch::round_facts_probe(const double *m, const double *y, const unsigned char *store, double *out, size_t n, hipStream_t st)
+{
+  if (n == 0 || n % 64 != 0) return hipErrorInvalidValue; // whole wavefronts only: every lane of a block reads its own input
+  hipLaunchKernelGGL(round_facts_probe_kernel, dim3((unsigned)(n / 64)), dim3(64), 0, st, m, y, store, out);
+  return hipGetLastError();
+}
 
 hipError_t ccmp_launch::detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st)
 {

@@ -217,7 +217,8 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
     for (int k = 0; k < 9; k++) R[k] = rec[kPre + j * 12 + k];
 #pragma unroll
     for (int k = 0; k < 3; k++) o[k] = rec[kPre + j * 12 + 9 + k];
-    ccmp_sincos(y, &s, &c);
+    if constexpr (X0) ccmp_sincos_inr(y, &s, &c); // an in-range round: |y| <= 512 + 3 h, no range test (ccmp_detmath.h)
+    else ccmp_sincos(y, &s, &c);
     const double *sc = rec + kSC + 2 * ARM * 7;
     if constexpr (STOCK) {
       // twin arms: arm 0's constants serve both.  Joint indices are wave-uniform scalars; the branches are scalar.
@@ -284,7 +285,10 @@ __device__ __forceinline__ void jacobian_columns(const ccmp_consts &K, double *r
     double Tw[12], t[2];
     if constexpr (STOCK) tool_pose_fold<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
     else tool_pose_t<STOCK>(K, ARM, R, o, &Tw[0], &Tw[9]);
-    if (ARM == 0) chain_residual_ti(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
+    if constexpr (X0) { // ... and the quaternion's root and quotient without their guards, its case once per wavefront (ccmp_kin.h: quat_of_t)
+      if (ARM == 0) chain_residual_t<true, true>(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
+      else chain_residual_t<false, true>(K, &To[0], &To[9], &Tw[0], &Tw[9], t, nullptr, nullptr);
+    } else if (ARM == 0) chain_residual_ti(K, &Tw[0], &Tw[9], &To[0], &To[9], t, nullptr, nullptr);
     else chain_residual(K, &To[0], &To[9], &Tw[0], &Tw[9], t, nullptr, nullptr);
     // park this evaluation in the prefix slot the group has just consumed (12 doubles = 6 lanes x (f0, f1));
     // the stencil is combined after the arm's 7 columns (stencil_combine) instead of through two dependent

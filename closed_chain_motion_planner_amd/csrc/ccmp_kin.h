@@ -321,11 +321,115 @@ CCMP_HD void quat_of(const double *m, double *q)
   q[3] = kase == 3 ? h : (kase == 0 ? d1 : (kase == 1 ? d2 : d3));
 }
 
+/* ---- quat_of in an in-range round of the throughput kernels (INR) --------------------------------------------------------------
+ * The STOCK kernels enter jacobian_columns<., true, X0 = true> only when phase 1 has established rot_x0_round_ok for every joint of
+ * every live sample of the wavefront: |x_j| <= 512, finite sines and cosines at x and at the six stencil points.  The matrix m
+ * handed to quat_of is then a product of finite rotation factors, orthogonal to a few ulp, and three of quat_of's guards have
+ * nothing left to guard:
+ *   the radicand   In exact arithmetic, for ANY 3x3 matrix, the selected radicand is tr + 1 > 1 when tr > 0; otherwise it is
+ *                  1 + 2 m_ii - tr with m_ii the largest diagonal entry, m_ii >= tr / 3, so 1 + 2 m_ii - tr >= 1 - tr / 3 >= 1.
+ *                  The sums are rounded (three operations, entries of magnitude <= 1 + a few ulp): the radicand lies within a few
+ *                  ulp of [1, 4] — nowhere near 2^-767, zero or infinity — and ccmp_sqrt_steps runs the nine steps that
+ *                  ccmp_sqrt's wave-uniform test would have chosen, and the compiler's expansion performs, on the same values.
+ *   the quotient   t = sqrt(radicand) lies in [1, 2] up to rounding and the numerator is 0.5: both in 2^-300 <= |v| < 2^300, where
+ *                  ccmp_div_steps gives the compiler's division's bits (ccmp_detmath.h).
+ *   the selects    quat_case<KASE> is ONE branch of Eigen's Quaterniond(Matrix3d): that case's radicand by quat_of's three
+ *                  operations, its root, h, the quotient and the three products the case uses — the same operations on the same
+ *                  operands in the same order as quat_of performs for that case (the other nine sums and products of quat_of are
+ *                  computed there and thrown away by the selects), hence the same bits:
+ *                    case 3 (tr > 0)          arg = tr + 1                          q = (d1, d2, d3, h)
+ *                    case 0 (m00 largest)     arg = ((m00 - m11) - m22) + 1         q = (h, s1, s2, d1)
+ *                    case 1 (m11 largest)     arg = ((m11 - m22) - m00) + 1         q = (s1, h, s3, d2)
+ *                    case 2 (m22 largest)     arg = ((m22 - m00) - m11) + 1         q = (s2, s3, h, d3)
+ *                  with d1 = (m21 - m12) k, d2 = (m02 - m20) k, d3 = (m10 - m01) k, s1 = (m10 + m01) k, s2 = (m20 + m02) k,
+ *                  s3 = (m21 + m12) k, k = 0.5 / t, h = 0.5 t.  tests/test_quat_case_host.py compares the four bodies with quat_of.
+ * quat_of_t<true> forms kase per lane as quat_of does and enters ONE case body behind a scalar branch when the whole wavefront
+ * agrees on it (near the manifold the relative rotation of a fixture sits in one case, and all six stencil points of all ten
+ * samples with it); otherwise it runs quat_of's branch-free text with the two lean operations.  A lane whose group holds no
+ * sample may carry anything: it can make the wavefront take the branch-free text, and its own results — garbage, NaN — are
+ * never stored; neither path traps or loops on them.  The branch exists in this form ONLY: in every copy of the residual it
+ * spilled (DESIGN_experiments.md §5.6). */
+CCMP_HD int quat_kase(const double *m, double tr)
+{
+  int i = (m[4] > m[0]) ? 1 : 0;
+  const double mii = i ? m[4] : m[0];
+  if (m[8] > mii) i = 2;
+  return (tr > 0.0) ? 3 : i;
+}
+template <int KASE>
+CCMP_HD void quat_case(const double *m, double tr, double *q)
+{
+  double arg;
+  if (KASE == 3) arg = tr + 1.0;
+  else if (KASE == 0) arg = ((m[0] - m[4]) - m[8]) + 1.0;
+  else if (KASE == 1) arg = ((m[4] - m[8]) - m[0]) + 1.0;
+  else arg = ((m[8] - m[0]) - m[4]) + 1.0;
+  const double t = ccmp_sqrt_steps(arg);
+  const double h = 0.5 * t;
+  const double k = ccmp_div_steps(0.5, t);
+  if (KASE == 3) { q[0] = (m[7] - m[5]) * k; q[1] = (m[2] - m[6]) * k; q[2] = (m[3] - m[1]) * k; q[3] = h; }
+  else if (KASE == 0) { q[0] = h; q[1] = (m[3] + m[1]) * k; q[2] = (m[6] + m[2]) * k; q[3] = (m[7] - m[5]) * k; }
+  else if (KASE == 1) { q[0] = (m[3] + m[1]) * k; q[1] = h; q[2] = (m[7] + m[5]) * k; q[3] = (m[2] - m[6]) * k; }
+  else { q[0] = (m[6] + m[2]) * k; q[1] = (m[7] + m[5]) * k; q[2] = h; q[3] = (m[3] - m[1]) * k; }
+}
+/* the radicand quat_of selects for m (the lemma above: >= 1 up to rounding) */
+CCMP_HD double quat_radicand(const double *m)
+{
+  const double tr = (m[0] + m[4]) + m[8];
+  const int kase = quat_kase(m, tr);
+  return kase == 3 ? tr + 1.0
+                   : (kase == 0 ? ((m[0] - m[4]) - m[8]) + 1.0 : (kase == 1 ? ((m[4] - m[8]) - m[0]) + 1.0 : ((m[8] - m[0]) - m[4]) + 1.0));
+}
+/* one case body chosen by a run-time case (host: what the device's scalar branch enters) */
+CCMP_HD void quat_case_rt(int kase, const double *m, double *q)
+{
+  const double tr = (m[0] + m[4]) + m[8];
+  if (kase == 3) quat_case<3>(m, tr, q);
+  else if (kase == 0) quat_case<0>(m, tr, q);
+  else if (kase == 1) quat_case<1>(m, tr, q);
+  else quat_case<2>(m, tr, q);
+}
+/* INR: the form above; quat_of_t<false> is quat_of.  (The case branch WITHOUT the lean root and quotient spilled 56-76 B per lane in
+ * every stock kernel and was never run; the lean operations alone are about half the gain: DESIGN_experiments.md §5.6.) */
+template <bool INR>
+CCMP_HD void quat_of_t(const double *m, double *q, int *path = nullptr) /* path (nullable, the debug probe's): the case body entered, 4 = the branch-free text */
+{
+  if constexpr (!INR) { quat_of(m, q); return; }
+  const double tr = (m[0] + m[4]) + m[8];
+  const int kase = quat_kase(m, tr);
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int k0 = __builtin_amdgcn_readfirstlane(kase);
+  if (__builtin_amdgcn_ballot_w64(kase != k0) == 0ull) {
+    if (k0 == 3) quat_case<3>(m, tr, q);
+    else if (k0 == 0) quat_case<0>(m, tr, q);
+    else if (k0 == 1) quat_case<1>(m, tr, q);
+    else quat_case<2>(m, tr, q);
+    if (path) *path = k0;
+    return;
+  }
+#endif
+  if (path) *path = 4;
+  const double a3 = tr + 1.0;
+  const double a0 = ((m[0] - m[4]) - m[8]) + 1.0;
+  const double a1 = ((m[4] - m[8]) - m[0]) + 1.0;
+  const double a2 = ((m[8] - m[0]) - m[4]) + 1.0;
+  const double arg = kase == 3 ? a3 : (kase == 0 ? a0 : (kase == 1 ? a1 : a2));
+  const double t = ccmp_sqrt_steps(arg);
+  const double h = 0.5 * t;
+  const double k = ccmp_div_steps(0.5, t);
+  const double d1 = (m[7] - m[5]) * k, d2 = (m[2] - m[6]) * k, d3 = (m[3] - m[1]) * k;
+  const double s1 = (m[3] + m[1]) * k, s2 = (m[6] + m[2]) * k, s3 = (m[7] + m[5]) * k;
+  q[0] = kase == 3 ? d1 : (kase == 0 ? h : (kase == 1 ? s1 : s2));
+  q[1] = kase == 3 ? d2 : (kase == 0 ? s1 : (kase == 1 ? h : s3));
+  q[2] = kase == 3 ? d3 : (kase == 0 ? s2 : (kase == 1 ? s3 : h));
+  q[3] = kase == 3 ? h : (kase == 0 ? d1 : (kase == 1 ? d2 : d3));
+}
+
 /* current_chain = t_w72.inverse() * t_w71, then (|dp|, angularDistance) against init_chain_
  * (ConstraintFunction.h:92-101).  dq (nullable) receives q_c * conj(q_0) as (x,y,z,w) and pc
  * (nullable) the chain translation — the analytic Jacobian needs both.  chain_residual_ti takes ti = R2^T p2 from the caller
  * (a term of arm 1 alone: arm 0's Jacobian columns compute it once per round instead of once per stencil point). */
-template <bool TI>
+template <bool TI, bool INR = false> /* INR: quat_of_t's, for the callers named there */
 CCMP_HD void chain_residual_t(const ccmp_consts &K, const double *R1, const double *p1, const double *R2,
                               const double *p2_or_ti, double *f, double *dq, double *pc_out)
 {
@@ -336,7 +440,8 @@ CCMP_HD void chain_residual_t(const ccmp_consts &K, const double *R1, const doub
   mulTvec(R2, p1, pc);
 #pragma unroll
   for (int k = 0; k < 3; k++) pc[k] = pc[k] + (-ti[k]);
-  quat_of(Rc, qc);
+  if constexpr (INR) quat_of_t<true>(Rc, qc);
+  else quat_of(Rc, qc);
   double ax = qc[0], ay = qc[1], az = qc[2], aw = qc[3];
   double bx = -K.init_q[0], by = -K.init_q[1], bz = -K.init_q[2], bw = K.init_q[3];
   double dw = CCMP_FMA(-az, bz, CCMP_FMA(-ay, by, CCMP_FMA(-ax, bx, aw * bw)));

@@ -380,6 +380,7 @@ hipError_t resident_row16(int diag, void *box_dev, unsigned long long last_tag, 
 // lib/libccmp_debug.so only (ccmp_kernels_debug.hip)
 hipError_t detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
 hipError_t div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);
+hipError_t round_facts_probe(const double *m, const double *y, const unsigned char *store, double *out, size_t n, hipStream_t st);
 #pragma GCC visibility pop
 
 }  // namespace ccmp_launch

@@ -22,6 +22,13 @@ int ccmp_detmath_probe(ccmp_ctx *ctx, const double *x_dev, const double *y_dev, 
  * choice), the compiler's n / d} — the lean sequence must equal n / d wherever both operands are in 2^-300 <= |v| < 2^300, and
  * ccmp_div_lean everywhere */
 int ccmp_detmath_div_probe(ccmp_ctx *ctx, const double *n_dev, const double *d_dev, double *out_dev, size_t count, void *hip_stream);
+/* the forms an in-range Newton round of the throughput kernels runs, beside the forms they stand in for, one wavefront per 64 inputs
+ * (n a multiple of 64; anything else is refused with CCMP_EINVAL): m_dev[n][9] row-major matrices, y_dev[n] angles, store_dev[n] flags.
+ * out_dev[i][13] = {quat_of_t<true> (x, y, z, w), quat_of (x, y, z, w), ccmp_sincos_inr (sin, cos), ccmp_sincos (sin, cos), the path
+ * lane i's wavefront took through the quaternion, written by quat_of_t<true> itself inside the branch it took: case 0..3 (one case
+ * body behind the scalar branch) or 4 (the branch-free text)}; where store_dev[i] == 0 the lane computes on its input all the same and row i is left untouched */
+int ccmp_detmath_round_facts_probe(ccmp_ctx *ctx, const double *m_dev, const double *y_dev, const unsigned char *store_dev, double *out_dev, size_t n,
+                                   void *hip_stream);
 /* an externally supplied processing order for the reference-arithmetic projector (device array of B sample indices, NULL = none) */
 int ccmp_ctx_set_order_experimental(ccmp_ctx *ctx, const unsigned int *order_dev);
 /* a copy of the FP32 scout's predicted iteration counts of the last call that ran one */
