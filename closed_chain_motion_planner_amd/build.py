@@ -47,7 +47,7 @@ Translation units with deliberately different flags:
   ccmp_kernels_smooth.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   smooth solution paths (ccmp_smooth.h): the pair gather of a pass's stages, the bracket of half the arc and
                          the blend, the pick between projected / fallback / degenerate, the accept step into the other path buffer, lengths and the store
   ccmp_smooth.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_smooth: checks, the pass loop (midpoint steps on the dense unit's loop, the test step on the shortcut unit's); ccmp_smooth_mid_ref
-  ccmp_kernels_retime.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   resample and time stamps (ccmp_retime.h): the status scan, the bracket of a target arc and the blend, the pick,
+  ccmp_kernels_retime.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   resample and time stamps (ccmp_retime.h): the status scan, the bracket of a target arc (ccmp_dense.h: arc_bracket, the smooth unit's too) and the blend, the pick,
                          the ceilings and the minimum of A, the envelope and the stamps' serial sum (one wavefront per path)
   ccmp_retime.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_resample, ccmp_sampled_paths_*, ccmp_path_timestamps*: checks, launches; ccmp_path_timestamps_ref, ccmp_arc_bracket_ref, ccmp_resample_targets_ref
 """

@@ -7,7 +7,6 @@
 // and one block per path reduces it.  The loop is bounded by max_calls; spent with a segment open, the call creates nothing.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -29,7 +28,6 @@ using ccmp::dense_open_seg;
 
 namespace {
 
-constexpr size_t kMaxRows = ((size_t)1 << 31) - 1; // rows and slots are int32
 constexpr const char *kArenaWhat = "ccmp_path_densify: hipMalloc";
 
 // The layout rule on the host (ccmp_dense.h): what ccmp_dense_layout_ref answers and what the device call lays its result out by.
@@ -70,10 +68,7 @@ int opts_ok(const ccmp_dense_opts &o)
 int densify_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
                    size_t F, int max_len, const ccmp_dense_opts &o)
 {
-  { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
-  if (!(p->delta > 0) || !(p->lambda > 0)) return CCMP_EINVAL;
-  { const int rc = opts_ok(o); if (rc != CCMP_OK) return rc; }
-  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  { const int rc = traversal_checks(ctx, p, scene, margin, opts_ok(o)); if (rc != CCMP_OK) return rc; }
   if (F > 0 && (!path_joints || !path_len || max_len < 1)) return CCMP_EINVAL;
   if (F > 0 && F > kMaxRows / (size_t)max_len) return CCMP_EINVAL;
   return CCMP_OK;
@@ -100,36 +95,30 @@ int make_handle(ccmp_ctx *ctx, size_t F, int max_len, size_t rows, bool has_scen
 {
   ccmp_dense_paths *h = new (std::nothrow) ccmp_dense_paths();
   if (!h) return CCMP_ENOMEM;
-  h->ctx = ctx;
-  h->device = ctx->device;
   h->F = F;
   h->max_len = max_len;
   h->rows = rows;
   h->slots = F * (size_t)(max_len > 0 ? max_len - 1 : 0);
   h->has_scene = has_scene;
   const size_t R = rows ? rows : 1, S = h->slots ? h->slots : 1, P = F + 1;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-  const size_t o_rows = take(R * 14 * sizeof(double)), o_arc = take(R * sizeof(double)), o_len = take(P * sizeof(double)),
-               o_clr = take(has_scene ? R * sizeof(double) : 0), o_minc = take(has_scene ? P * sizeof(double) : 0), o_pf = take(P * sizeof(int32_t)),
-               o_sf = take(S * sizeof(int32_t)), o_sn = take(S * sizeof(int32_t)), o_minr = take(has_scene ? P * sizeof(int32_t) : 0),
-               o_fb = take(has_scene ? P * sizeof(int32_t) : 0), o_ok = take(S);
-  ccmp_host::quiesce(ctx);
-  const hipError_t e = hipMalloc(&h->block, off);
-  if (e != hipSuccess) { delete h; return hip_fail(e, "ccmp_path_densify: hipMalloc"); }
-  char *b = (char *)h->block;
-  h->d_rows = (double *)(b + o_rows);
-  h->arc = (double *)(b + o_arc);
-  h->length = (double *)(b + o_len);
-  h->path_first = (int32_t *)(b + o_pf);
-  h->seg_first = (int32_t *)(b + o_sf);
-  h->seg_newton = (int32_t *)(b + o_sn);
-  h->seg_ok = (uint8_t *)(b + o_ok);
+  ResultBlock b;
+  const size_t o_rows = b.take(R * 14 * sizeof(double)), o_arc = b.take(R * sizeof(double)), o_len = b.take(P * sizeof(double)),
+               o_clr = b.take(has_scene ? R * sizeof(double) : 0), o_minc = b.take(has_scene ? P * sizeof(double) : 0), o_pf = b.take(P * sizeof(int32_t)),
+               o_sf = b.take(S * sizeof(int32_t)), o_sn = b.take(S * sizeof(int32_t)), o_minr = b.take(has_scene ? P * sizeof(int32_t) : 0),
+               o_fb = b.take(has_scene ? P * sizeof(int32_t) : 0), o_ok = b.take(S);
+  { const int rc = b.alloc(h, ctx, kArenaWhat); if (rc != CCMP_OK) { delete h; return rc; } }
+  h->d_rows = b.at<double>(o_rows);
+  h->arc = b.at<double>(o_arc);
+  h->length = b.at<double>(o_len);
+  h->path_first = b.at<int32_t>(o_pf);
+  h->seg_first = b.at<int32_t>(o_sf);
+  h->seg_newton = b.at<int32_t>(o_sn);
+  h->seg_ok = b.at<uint8_t>(o_ok);
   if (has_scene) {
-    h->clearance = (double *)(b + o_clr);
-    h->min_clear = (double *)(b + o_minc);
-    h->min_row = (int32_t *)(b + o_minr);
-    h->first_blocked = (int32_t *)(b + o_fb);
+    h->clearance = b.at<double>(o_clr);
+    h->min_clear = b.at<double>(o_minc);
+    h->min_row = b.at<int32_t>(o_minr);
+    h->first_blocked = b.at<int32_t>(o_fb);
   }
   *out = h;
   return CCMP_OK;
@@ -280,22 +269,13 @@ int ccmp_path_densify(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *sc
   if (out) *out = nullptr;
   if (!ctx) return no_handle();
   if (!out) return CCMP_EINVAL;
-  ccmp_dense_opts o;
-  ccmp_dense_opts_default(&o);
-  if (opts) o = *opts;
+  const ccmp_dense_opts o = opts_or(opts, ccmp_dense_opts_default);
   { const int rc = densify_checks(ctx, p, scene, margin, path_joints, path_len, F, max_len, o); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
-  std::vector<int32_t> len(F);
-  if (F) { // path_len is read once, before any launch
-    const hipError_t e = hipMemcpyAsync(len.data(), path_len, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-    const int rc = lens_ok(len.data(), F, max_len);
-    if (rc != CCMP_OK) return rc;
-  }
+  std::vector<int32_t> len;
+  { const int rc = read_lens(path_len, F, max_len, st, &len); if (rc != CCMP_OK) return rc; }
   return densify(ctx, p, scene, margin, path_joints, len, F, max_len, o, out, st);
 }
 
@@ -305,9 +285,7 @@ int ccmp_path_densify_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scen
   if (out) *out = nullptr;
   if (!ctx) return no_handle();
   if (!out) return CCMP_EINVAL;
-  ccmp_dense_opts o;
-  ccmp_dense_opts_default(&o);
-  if (opts) o = *opts;
+  const ccmp_dense_opts o = opts_or(opts, ccmp_dense_opts_default);
   { const int rc = densify_checks(ctx, p, scene, margin, path_joints, path_len, F, max_len, o); if (rc != CCMP_OK) return rc; }
   if (F) { const int rc = lens_ok(path_len, F, max_len); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(ctx->device);
@@ -379,16 +357,7 @@ int ccmp_dense_paths_copy_host(ccmp_dense_paths *h, double *rows_out, int32_t *p
   return sg.finish(rc);
 }
 
-void ccmp_dense_paths_destroy(ccmp_dense_paths *h)
-{
-  if (!h) return;
-  {
-    DeviceGuard guard(h->device);
-    if (h->ctx && ccmp_host::context_alive(h->ctx)) ccmp_host::quiesce(h->ctx);
-    if (h->block) (void)hipFree(h->block);
-  }
-  delete h;
-}
+void ccmp_dense_paths_destroy(ccmp_dense_paths *h) { result_destroy(h); }
 
 int ccmp_dense_layout_ref(const int32_t *path_len, size_t F, int max_len, const int32_t *seg_states, int flags, int32_t *path_first, int32_t *seg_first,
                           size_t *rows)

@@ -22,6 +22,7 @@
 
 namespace {
 
+using ccmp::blocks_of;
 using ccmp::dense_chunk;
 using ccmp::dense_open_seg;
 constexpr int kThreads = 256;
@@ -115,8 +116,6 @@ __global__ __launch_bounds__(kThreads) void dense_clear_kernel(const double *__r
     first_blocked[f] = s_b[0] == kNoRow ? -1 : s_b[0];
   }
 }
-
-unsigned int blocks_of(size_t n, size_t per_block) { return (unsigned int)((n + per_block - 1) / per_block); }
 
 }  // namespace
 

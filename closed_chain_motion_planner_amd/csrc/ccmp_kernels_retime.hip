@@ -24,21 +24,12 @@
 
 namespace {
 
+using ccmp::blocks_of;
+using ccmp::path_of; // (ccmp_dense.h: the path of a packed row)
 using ccmp::retime_limits;
 constexpr int kThreads = 256;
 constexpr int kWave = 64;
 constexpr unsigned long long kNoA = ~0ull; // above the bits of every double >= 0, +inf included: no interval has contributed
-
-// the path whose range holds item g: first[a] ascending over a < F; the last a with first[a] <= g (0 when there is none)
-__device__ __forceinline__ unsigned int path_of(const int32_t *__restrict__ first, unsigned int F, long long g)
-{
-  unsigned int lo = 0, hi = F - 1;
-  while (lo < hi) {
-    const unsigned int mid = lo + (hi - lo + 1) / 2;
-    if ((long long)first[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // the minimum over the sixteen lanes of a row's group (finite values or +inf: the order cannot change a bit)
 __device__ __forceinline__ double min16(double v)
@@ -90,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void resample_bracket_kernel(const double
       const double h = ccmp::retime_target(j, N, arc[first + R - 1]);
       what = ccmp::kRetimeDegenerate;
       if (h > 0.0 && R >= 2 && h <= arc[first + R - 1]) {
-        ccmp::retime_bracket(arc + first, (int)R, h, &k, &tt, &lower);
+        ccmp::arc_bracket(arc + first, (int)R, h, &k, &tt, &lower);
         what = ccmp::kRetimePending;
       }
     }
@@ -230,8 +221,6 @@ __global__ __launch_bounds__(kWave) void retime_stamp_kernel(const double *__res
   }
   if (lane == 0) duration[f] = a;
 }
-
-unsigned int blocks_of(size_t n, size_t per_block) { return (unsigned int)((n + per_block - 1) / per_block); }
 
 }  // namespace
 

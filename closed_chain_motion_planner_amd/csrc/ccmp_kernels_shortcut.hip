@@ -23,6 +23,7 @@
 
 namespace {
 
+using ccmp::blocks_of;
 using ccmp::shortcut_best;
 using ccmp::shortcut_open;
 constexpr int kThreads = 256;
@@ -173,8 +174,6 @@ __global__ __launch_bounds__(kThreads) void shortcut_kept_kernel(const double *_
   if (v < 0 || v >= max_len) return;
   out_joints[s * 14 + c] = path_joints[(f * (unsigned long long)max_len + (unsigned long long)v) * 14 + c];
 }
-
-unsigned int blocks_of(size_t n, size_t per_block) { return (unsigned int)((n + per_block - 1) / per_block); }
 
 }  // namespace
 

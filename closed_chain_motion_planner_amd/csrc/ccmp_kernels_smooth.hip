@@ -22,19 +22,10 @@
 
 namespace {
 
+using ccmp::blocks_of;
+using ccmp::path_of; // (ccmp_dense.h: the active path of an item, by its key)
 using ccmp::smooth_path;
 constexpr int kThreads = 256;
-
-// the active path whose range holds item g: key(a) = its first item, ascending; the last a with key(a) <= g
-template <class Key> __device__ __forceinline__ unsigned int path_of(unsigned int nA, long long g, Key key)
-{
-  unsigned int lo = 0, hi = nA - 1;
-  while (lo < hi) {
-    const unsigned int mid = lo + (hi - lo + 1) / 2;
-    if (key(mid) <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 __global__ __launch_bounds__(kThreads) void smooth_load_kernel(const double *__restrict__ path_joints, const int32_t *__restrict__ path_len,
                                                               unsigned long long slots, int max_len, int cap, double *__restrict__ buf,
@@ -205,8 +196,6 @@ __global__ __launch_bounds__(kThreads) void smooth_store_kernel(const double *__
   if (k >= len[f]) return;
   out_joints[s * 14 + c] = (where[f] ? buf1 : buf0)[s * 14 + c];
 }
-
-unsigned int blocks_of(size_t n, size_t per_block) { return (unsigned int)((n + per_block - 1) / per_block); }
 
 }  // namespace
 

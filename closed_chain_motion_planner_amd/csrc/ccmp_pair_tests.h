@@ -1,15 +1,17 @@
-/* ccmp_pair_tests.h — what the path units share on the host (ccmp_shortcut.cpp, ccmp_dense.cpp, ccmp_smooth.cpp): the tile and
- * continuation loop of checkMotion tests over pairs of rows, and the dense form of a batch of paths as the library keeps it.  Host only,
- * C++ linkage, hidden: nothing here is exported. */
+/* ccmp_pair_tests.h — what the path units share on the host (ccmp_shortcut.cpp, ccmp_dense.cpp, ccmp_smooth.cpp, ccmp_retime.cpp): the
+ * checks every traversing entry point begins with, the tile and continuation loop of checkMotion tests over pairs of rows, and the
+ * dense form of a batch of paths as the library keeps it.  Host only, C++ linkage, hidden: nothing here is exported. */
 #ifndef CCMP_PAIR_TESTS_H
 #define CCMP_PAIR_TESTS_H
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/ccmp.h"
+#include "ccmp_scene.h"
 #include "ccmp_stage.h"
 
 /* the result of ccmp_path_densify: one allocation, the arrays point into it */
@@ -49,6 +51,17 @@ struct PairLoopOpts {
 struct PairLoopCounts {
   long long calls = 0, read_bytes = 0;
 };
+
+/* what every entry point that traverses checks first of all, in this order (problem_ok can answer more than CCMP_EINVAL): its problem,
+ * its options — opts_rc = what the unit's own opts_ok answered — and its scene */
+inline int traversal_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, int opts_rc)
+{
+  { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
+  if (!(p->delta > 0) || !(p->lambda > 0)) return CCMP_EINVAL;
+  if (opts_rc != CCMP_OK) return opts_rc;
+  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  return CCMP_OK;
+}
 
 /* `total` pair slots in tiles of at most tile_edges, each tile continued until no pair is open: ONE uninterrupted checkMotion per pair
  * (ccmp_geodesic_batch_ex, with a scene ccmp_geodesic_scene_batch), its flag, list length and Newton total into w_ok / w_states /

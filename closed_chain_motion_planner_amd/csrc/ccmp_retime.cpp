@@ -34,7 +34,6 @@ struct ccmp_sampled_paths {
 
 namespace {
 
-constexpr size_t kMaxRows = ((size_t)1 << 31) - 1; // rows are int32
 constexpr const char *kArenaWhat = "ccmp_path_resample: hipMalloc";
 
 bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
@@ -78,26 +77,20 @@ int make_handle(ccmp_ctx *ctx, size_t F, size_t rows, ccmp_sampled_paths **out)
 {
   ccmp_sampled_paths *h = new (std::nothrow) ccmp_sampled_paths();
   if (!h) return CCMP_ENOMEM;
-  h->ctx = ctx;
-  h->device = ctx->device;
   h->F = F;
   h->rows = rows;
   const size_t R = rows ? rows : 1, P = F + 1;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-  const size_t o_rows = take(R * 14 * sizeof(double)), o_arc = take(R * sizeof(double)), o_len = take(P * sizeof(double)), o_pf = take(P * sizeof(int32_t)),
-               o_st = take(P * sizeof(int32_t)), o_cnt = take(P * ccmp::kRetimeKinds * sizeof(int32_t)), o_kind = take(R);
-  ccmp_host::quiesce(ctx);
-  const hipError_t e = hipMalloc(&h->block, off);
-  if (e != hipSuccess) { delete h; return hip_fail(e, kArenaWhat); }
-  char *b = (char *)h->block;
-  h->d_rows = (double *)(b + o_rows);
-  h->arc = (double *)(b + o_arc);
-  h->length = (double *)(b + o_len);
-  h->path_first = (int32_t *)(b + o_pf);
-  h->status = (int32_t *)(b + o_st);
-  h->counts = (int32_t *)(b + o_cnt);
-  h->kind = (uint8_t *)(b + o_kind);
+  ResultBlock b;
+  const size_t o_rows = b.take(R * 14 * sizeof(double)), o_arc = b.take(R * sizeof(double)), o_len = b.take(P * sizeof(double)),
+               o_pf = b.take(P * sizeof(int32_t)), o_st = b.take(P * sizeof(int32_t)), o_cnt = b.take(P * ccmp::kRetimeKinds * sizeof(int32_t)), o_kind = b.take(R);
+  { const int rc = b.alloc(h, ctx, kArenaWhat); if (rc != CCMP_OK) { delete h; return rc; } }
+  h->d_rows = b.at<double>(o_rows);
+  h->arc = b.at<double>(o_arc);
+  h->length = b.at<double>(o_len);
+  h->path_first = b.at<int32_t>(o_pf);
+  h->status = b.at<int32_t>(o_st);
+  h->counts = b.at<int32_t>(o_cnt);
+  h->kind = b.at<uint8_t>(o_kind);
   *out = h;
   return CCMP_OK;
 }
@@ -264,16 +257,7 @@ int ccmp_sampled_paths_copy_host(ccmp_sampled_paths *h, double *rows_out, int32_
   return sg.finish(rc);
 }
 
-void ccmp_sampled_paths_destroy(ccmp_sampled_paths *h)
-{
-  if (!h) return;
-  {
-    DeviceGuard guard(h->device);
-    if (h->ctx && ccmp_host::context_alive(h->ctx)) ccmp_host::quiesce(h->ctx);
-    if (h->block) (void)hipFree(h->block);
-  }
-  delete h;
-}
+void ccmp_sampled_paths_destroy(ccmp_sampled_paths *h) { result_destroy(h); }
 
 int ccmp_path_timestamps(ccmp_ctx *ctx, const double *rows, const int32_t *path_first, size_t F, size_t total_rows, const double *vmax, const double *amax,
                          double beta, double *time, double *duration, double *ceiling, double *envelope, int32_t *status, void *hip_stream)
@@ -387,7 +371,7 @@ int ccmp_arc_bracket_ref(const double *arcs, int n, double h, int *k, double *t,
 {
   if (!arcs || n < 2 || !k || !t || !lower || !(h > 0.0) || !(h <= arcs[n - 1])) return CCMP_EINVAL;
   bool lo;
-  ccmp::retime_bracket(arcs, n, h, k, t, &lo);
+  ccmp::arc_bracket(arcs, n, h, k, t, &lo);
   *lower = lo ? 1 : 0;
   return CCMP_OK;
 }

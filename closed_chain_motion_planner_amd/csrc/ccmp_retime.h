@@ -5,10 +5,8 @@
  * both compile it with -ffp-contract=off -DCCMP_USE_FMA: the only fused operations are the ones written with CCMP_FMA (the blend's and
  * the joint distance's), and they cannot differ in a bit.
  *
- *   arc bracket    arcs s[0 .. n), monotone, n >= 2, and a target 0 < h <= s[n-1]: k = the smallest k >= 1 with s[k] >= h, by bisection;
- *                  t = (h - s[k-1]) / (s[k] - s[k-1]), one IEEE division; lower = (h - s[k-1]) <= (s[k] - h).  s[k] > s[k-1] always holds
- *                  (s[k-1] < h <= s[k]), so a +0.0 step — a duplicated row — is never the bracket.  This is smooth_bracket of ccmp_smooth.h
- *                  with the target as an argument.
+ *   arc bracket    (k, t, lower) of a target arc 0 < h <= s[n-1] on monotone arcs s[0 .. n), n >= 2: ccmp_dense.h states it and
+ *                  arc_bracket there is its text, shared with the smoothing's midpoint; ccmp_arc_bracket_ref answers it on the host.
  *
  *   resample       a dense path (ccmp_dense.h, either layout) has rows r_0 .. r_{R-1} and arcs s, T = s[R-1].  Status, tested in this order:
  *                  EMPTY R == 0 (no row out); BROKEN a segment of the path has seg_ok == 0 (none); NONFINITE a row is not finite in all
@@ -43,6 +41,7 @@
 #include <stdint.h>
 
 #include "../../include/ccmp.h"
+#include "ccmp_dense.h"
 #include "ccmp_detmath.h"
 
 namespace ccmp {
@@ -56,20 +55,6 @@ enum : int { kRetimeOk = CCMP_RETIME_OK, kRetimeEmpty = CCMP_RETIME_EMPTY, kReti
 struct retime_limits {
   double vmax[14], amax[14], beta;
 };
-
-/* The bracket of the target arc h on s[0 .. n): defined for n >= 2 and 0 < h <= s[n-1] */
-CCMP_HD void retime_bracket(const double *s, int n, double h, int *k_out, double *t_out, bool *lower)
-{
-  int lo = 1, hi = n - 1; /* s[hi] >= h */
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (s[mid] >= h) hi = mid; else lo = mid + 1;
-  }
-  const double below = h - s[lo - 1], above = s[lo] - h;
-  *k_out = lo;
-  *t_out = below / (s[lo] - s[lo - 1]);
-  *lower = below <= above;
-}
 
 /* The row count of an OK path with T > 0: count mode or spacing mode; -1 beyond INT32_MAX (FULL).  Host only: the count sizes the result. */
 static inline int64_t retime_count(double T, int count, double spacing)

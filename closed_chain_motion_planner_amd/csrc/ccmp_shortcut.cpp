@@ -8,7 +8,6 @@
 // selection run and anything reach the caller's outputs, so a call that spends max_calls leaves them untouched.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -30,13 +29,6 @@ namespace {
 constexpr size_t kMaxCells = (size_t)1 << 40; // F max_len^2 beyond this is an argument error, not an allocation to try
 
 constexpr const char *kArenaWhat = "ccmp_path_shortcut: hipMalloc";
-
-bool overlaps(const void *a, size_t na, const void *b, size_t nb)
-{
-  if (!a || !b || !na || !nb) return false;
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
 
 int opts_ok(const ccmp_shortcut_opts &o)
 {
@@ -61,15 +53,6 @@ int select_checks(const double *path_joints, const int32_t *path_len, size_t F, 
   for (int a = 0; a < 8; a++)
     for (int b = 0; b < 3; b++)
       if (overlaps(out[a], out_n[a], in[b], in_n[b])) return CCMP_EINVAL;
-  return CCMP_OK;
-}
-
-int shortcut_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_shortcut_opts &o)
-{
-  { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
-  if (!(p->delta > 0) || !(p->lambda > 0)) return CCMP_EINVAL;
-  { const int rc = opts_ok(o); if (rc != CCMP_OK) return rc; }
-  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
   return CCMP_OK;
 }
 
@@ -271,25 +254,16 @@ int ccmp_path_shortcut(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *s
                        double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton, void *hip_stream)
 {
   if (!ctx) return no_handle();
-  ccmp_shortcut_opts o;
-  ccmp_shortcut_opts_default(&o);
-  if (opts) o = *opts;
-  { const int rc = shortcut_checks(ctx, p, scene, margin, o); if (rc != CCMP_OK) return rc; }
+  const ccmp_shortcut_opts o = opts_or(opts, ccmp_shortcut_opts_default);
+  { const int rc = traversal_checks(ctx, p, scene, margin, opts_ok(o)); if (rc != CCMP_OK) return rc; }
   { const int rc = select_checks(path_joints, path_len, F, max_len, nullptr, out_joints, out_len, kept, cost_in, cost_out, pair_ok, pair_states, pair_newton);
     if (rc != CCMP_OK) return rc; }
   if (F == 0) return CCMP_OK;
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
-  std::vector<int32_t> len(F);
-  { // path_len is read once, before any launch
-    const hipError_t e = hipMemcpyAsync(len.data(), path_len, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-    const int rc = lens_ok(len.data(), F, max_len);
-    if (rc != CCMP_OK) return rc;
-  }
+  std::vector<int32_t> len;
+  { const int rc = read_lens(path_len, F, max_len, st, &len); if (rc != CCMP_OK) return rc; }
   return shortcut(ctx, p, scene, margin, path_joints, path_len, len, F, max_len, o, out_joints, out_len, kept, cost_in, cost_out, pair_ok, pair_states,
                   pair_newton, st);
 }
@@ -299,10 +273,8 @@ int ccmp_path_shortcut_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sce
                             int32_t *kept, double *cost_in, double *cost_out, uint8_t *pair_ok, int32_t *pair_states, int32_t *pair_newton)
 {
   if (!ctx) return no_handle();
-  ccmp_shortcut_opts o;
-  ccmp_shortcut_opts_default(&o);
-  if (opts) o = *opts;
-  { const int rc = shortcut_checks(ctx, p, scene, margin, o); if (rc != CCMP_OK) return rc; }
+  const ccmp_shortcut_opts o = opts_or(opts, ccmp_shortcut_opts_default);
+  { const int rc = traversal_checks(ctx, p, scene, margin, opts_ok(o)); if (rc != CCMP_OK) return rc; }
   { const int rc = select_checks(path_joints, path_len, F, max_len, nullptr, out_joints, out_len, kept, cost_in, cost_out, pair_ok, pair_states, pair_newton);
     if (rc != CCMP_OK) return rc; }
   if (F == 0) return CCMP_OK;

@@ -8,7 +8,6 @@
 // max_calls leaves them untouched.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -26,15 +25,7 @@ using ccmp::smooth_path;
 
 namespace {
 
-constexpr size_t kMaxRows = ((size_t)1 << 31) - 1; // F out_max_len beyond this is an argument error
 constexpr const char *kArenaWhat = "ccmp_path_smooth: hipMalloc";
-
-bool overlaps(const void *a, size_t na, const void *b, size_t nb)
-{
-  if (!a || !b || !na || !nb) return false;
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
 
 int opts_ok(const ccmp_smooth_opts &o)
 {
@@ -58,10 +49,7 @@ struct Outputs {
 int smooth_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *path_joints, const int32_t *path_len,
                   size_t F, int max_len, int out_max_len, const ccmp_smooth_opts &o, const Outputs &out)
 {
-  { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
-  if (!(p->delta > 0) || !(p->lambda > 0)) return CCMP_EINVAL;
-  { const int rc = opts_ok(o); if (rc != CCMP_OK) return rc; }
-  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
+  { const int rc = traversal_checks(ctx, p, scene, margin, opts_ok(o)); if (rc != CCMP_OK) return rc; }
   if (max_len < 1 || out_max_len < max_len) return CCMP_EINVAL;
   if (F == 0) return CCMP_OK;
   if (F > kMaxRows / (size_t)out_max_len) return CCMP_EINVAL;
@@ -256,24 +244,15 @@ int ccmp_path_smooth(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *sce
                      int32_t *moved, int32_t *stop, double *length_in, double *length_out, int32_t *stats, void *hip_stream)
 {
   if (!ctx) return no_handle();
-  ccmp_smooth_opts o;
-  ccmp_smooth_opts_default(&o);
-  if (opts) o = *opts;
+  const ccmp_smooth_opts o = opts_or(opts, ccmp_smooth_opts_default);
   const Outputs out{out_joints, out_len, passes, moved, stop, length_in, length_out, stats};
   { const int rc = smooth_checks(ctx, p, scene, margin, path_joints, path_len, F, max_len, out_max_len, o, out); if (rc != CCMP_OK) return rc; }
   if (F == 0) return CCMP_OK;
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
-  std::vector<int32_t> len(F);
-  { // path_len is read once, before any launch
-    const hipError_t e = hipMemcpyAsync(len.data(), path_len, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-    const int rc = lens_ok(len.data(), F, max_len);
-    if (rc != CCMP_OK) return rc;
-  }
+  std::vector<int32_t> len;
+  { const int rc = read_lens(path_len, F, max_len, st, &len); if (rc != CCMP_OK) return rc; }
   return smooth(ctx, p, scene, margin, path_joints, path_len, len, F, max_len, out_max_len, o, out, st);
 }
 
@@ -282,9 +261,7 @@ int ccmp_path_smooth_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene
                           int32_t *moved, int32_t *stop, double *length_in, double *length_out, int32_t *stats)
 {
   if (!ctx) return no_handle();
-  ccmp_smooth_opts o;
-  ccmp_smooth_opts_default(&o);
-  if (opts) o = *opts;
+  const ccmp_smooth_opts o = opts_or(opts, ccmp_smooth_opts_default);
   const Outputs out{out_joints, out_len, passes, moved, stop, length_in, length_out, stats};
   { const int rc = smooth_checks(ctx, p, scene, margin, path_joints, path_len, F, max_len, out_max_len, o, out); if (rc != CCMP_OK) return rc; }
   if (F == 0) return CCMP_OK;

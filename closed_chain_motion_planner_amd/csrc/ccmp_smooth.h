@@ -9,10 +9,10 @@
  *   closed list    of a pair (a, b): the distinct dense rows of the two-waypoint path [a, b] (ccmp_dense.h): G = the list of ONE
  *                  uninterrupted discreteGeodesic(a, b, interpolate = true), then b; n >= 2 rows; arcs s_0 = +0.0,
  *                  s_k = fl(s_{k-1} + joint distance(row_{k-1}, row_k)).
- *   midpoint       mid(a, b): T = s_{n-1}, h = 0.5 T.  Not T > 0: mid = a (DEGENERATE).  Otherwise k = the smallest k >= 1 with
- *                  s_k >= h (so s_k > s_{k-1}: a +0.0 step is never the bracket), t = (h - s_{k-1}) / (s_k - s_{k-1}) (IEEE division),
+ *   midpoint       mid(a, b): T = s_{n-1}, h = 0.5 T.  Not T > 0: mid = a (DEGENERATE).  Otherwise (k, t, lower) = the arc bracket of h
+ *                  (ccmp_dense.h states it, once, for this unit and for ccmp_retime.h: a +0.0 step is never the bracket),
  *                  x = WrapperStateSpace::interpolate(row_{k-1}, row_k, t) (smooth_interpolate: the extend step's text), (y, ok) =
- *                  project(x).  ok: mid = y (PROJECTED).  Not ok: mid = row_{k-1} when (h - s_{k-1}) <= (s_k - h), else row_k (FALLBACK).
+ *                  project(x).  ok: mid = y (PROJECTED).  Not ok: mid = row_{k-1} when lower, else row_k (FALLBACK).
  *                  The midpoint is the blend at exactly half the arc put back on the manifold, not the list state nearest to it: at the
  *                  planner's delta a list has one to seven states, so after one pass most list-state midpoints coincide with a waypoint
  *                  and later passes move the same vertices back and forth.
@@ -55,25 +55,13 @@ CCMP_HD int32_t smooth_len_after(int32_t L, int passes)
   return n > 0x7fffffffLL ? 0x7fffffff : (int32_t)n;
 }
 
-/* The bracket of a closed list's half arc: arcs s[0 .. n), monotone.  Returns false for a degenerate list (not T > 0).  Otherwise *k_out =
- * the smallest k >= 1 with s[k] >= h, by bisection (no serial chain), *t_out the blend parameter and *lower true when the fallback is
- * row k - 1. */
+/* The bracket of a closed list's half arc: arcs s[0 .. n), monotone.  Returns false for a degenerate list (not T > 0).  Otherwise the arc
+ * bracket (ccmp_dense.h) of h = 0.5 T: *k_out, the blend parameter *t_out, and *lower true when the fallback is row k - 1. */
 CCMP_HD bool smooth_bracket(const double *s, int n, int *k_out, double *t_out, bool *lower)
 {
   *k_out = 0; *t_out = 0.0; *lower = true;
-  if (n < 2) return false;
-  const double T = s[n - 1];
-  if (!(T > 0.0)) return false;
-  const double h = 0.5 * T;
-  int lo = 1, hi = n - 1; /* s[hi] = T >= h */
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (s[mid] >= h) hi = mid; else lo = mid + 1;
-  }
-  const double below = h - s[lo - 1], above = s[lo] - h;
-  *k_out = lo;
-  *t_out = below / (s[lo] - s[lo - 1]);
-  *lower = below <= above;
+  if (n < 2 || !(s[n - 1] > 0.0)) return false;
+  arc_bracket(s, n, 0.5 * s[n - 1], k_out, t_out, lower);
   return true;
 }
 

@@ -1,8 +1,9 @@
 /* ccmp_stage.h — what the planner-side *_host entry points share (ccmp_roadmap.cpp, ccmp_object.cpp, ccmp_ik.cpp, ccmp_shortcut.cpp,
- * ccmp_dense.cpp): the answer to a missing handle, two small checks, the synchronous staged call on the context's stream and the
- * device memory of one call.  Host only, C++ linkage, nothing exported.  The projector's host path (ccmp_host_io.cpp: HostIO, the
- * sharded calls) has other requirements and does not use this.  Argument checks stay with the entry points: they run before the
- * device guard and before anything here is constructed. */
+ * ccmp_dense.cpp, ccmp_smooth.cpp, ccmp_retime.cpp): the answer to a missing handle, two small checks, the synchronous staged call on
+ * the context's stream, the device memory of one call and, for the path units, the pieces of an entry point's prologue (the read of
+ * path_len, the overlap test, the row bound, the options) and the one allocation of a result handle.  Host only, C++ linkage, nothing
+ * of the C ABI.  The projector's host path (ccmp_host_io.cpp: HostIO, the sharded calls) has other requirements and does not use
+ * this.  Argument checks stay with the entry points: they run before the device guard and before anything here is constructed. */
 #ifndef CCMP_STAGE_H
 #define CCMP_STAGE_H
 #include <hip/hip_runtime.h>
@@ -122,6 +123,66 @@ class CallArena {
     for (void *b : blocks) (void)hipFree(b); // waits for whatever still reads it
   }
 };
+
+/* The path units' share.  Hidden, as ccmp_pair_tests.h is: the inline functions above come out of the library as weak symbols and
+ * stay so, because the list of the library's dynamic symbols is kept as it is; what is added here adds nothing to it. */
+#pragma GCC visibility push(hidden)
+
+/* the device form's one read of path_len [F] (device memory), before any launch: copied, waited for, checked */
+inline int read_lens(const int32_t *path_len, size_t F, int max_len, hipStream_t st, std::vector<int32_t> *len)
+{
+  len->resize(F);
+  if (F == 0) return CCMP_OK;
+  const hipError_t e = hipMemcpyAsync(len->data(), path_len, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return lens_ok(len->data(), F, max_len);
+}
+
+constexpr size_t kMaxRows = ((size_t)1 << 31) - 1; // rows and slots are int32: a batch beyond this is an argument error
+
+/* do two byte ranges share a byte?  (a range without a pointer or a length shares none) */
+inline bool overlaps(const void *a, size_t na, const void *b, size_t nb)
+{
+  if (!a || !b || !na || !nb) return false;
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+/* the caller's options, or the defaults where it gave none */
+template <class O> O opts_or(const O *given, void (*defaults)(O *)) { O o; defaults(&o); return given ? *given : o; }
+
+/* The one allocation of a result handle H (ccmp_dense_paths, ccmp_sampled_paths: fields ctx, device, block): take() the pieces, then
+ * alloc(), then the handle's arrays at<T>() their offsets.  result_destroy is the whole of the handle's *_destroy. */
+struct ResultBlock {
+  size_t total = 0;
+  char *base = nullptr;
+  size_t take(size_t bytes) { const size_t off = total; total += align256(bytes); return off; }
+  template <class T> T *at(size_t off) const { return (T *)(base + off); }
+  template <class H> int alloc(H *h, ccmp_ctx *ctx, const char *what)
+  {
+    h->ctx = ctx;
+    h->device = ctx->device;
+    quiesce(ctx);
+    const hipError_t e = hipMalloc(&h->block, total);
+    base = (char *)h->block;
+    return e == hipSuccess ? CCMP_OK : hip_fail(e, what);
+  }
+};
+
+template <class H> void result_destroy(H *h)
+{
+  if (!h) return;
+  {
+    DeviceGuard guard(h->device);
+    if (h->ctx && context_alive(h->ctx)) quiesce(h->ctx);
+    if (h->block) (void)hipFree(h->block);
+  }
+  delete h;
+}
+
+#pragma GCC visibility pop
 
 }  // namespace ccmp_host
 

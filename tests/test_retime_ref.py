@@ -4,7 +4,7 @@ every batch of that module and on the reference's two recorded path files; then 
 every argument error.
 
 Mutation check (each made in the sources, the library rebuilt, this file run; the unmutated sources turn every test green again):
-  * csrc/ccmp_retime.h, the bracket's bisection with `s[mid] > h` instead of `>=`
+  * csrc/ccmp_dense.h (arc_bracket), the bracket's bisection with `s[mid] > h` instead of `>=`
         -> test_arc_bracket_matches_the_linear_scan (the targets that ARE a dense arc) and test_argument_errors (its two spot values) red
   * csrc/ccmp_retime.h, h_j as (j * T) / (N - 1) instead of (j / (N - 1)) * T
         -> test_targets_match red

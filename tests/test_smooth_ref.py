@@ -88,6 +88,34 @@ def test_random_grid_lists(api, oracle_det, n):
         _check(api, oracle_det, r, (n, f))
 
 
+def test_the_midpoint_is_the_arc_bracket_of_half_the_arc(api):
+    """One bracket rule for both units: on arc arrays with T > 0 and 0.5 T > 0, ccmp_smooth_mid_ref and ccmp_arc_bracket_ref at
+    h = 0.5 T give the same k and the same bits of t, and the fallback row is k - 1 when `lower`, else k.  (The arc-bracket form
+    refuses h <= 0, so a T whose half rounds to +0.0 has no counterpart and is left out.)"""
+    rng = np.random.default_rng(0xA5C)
+    long = np.concatenate([[0.0], np.cumsum(np.where(rng.random(199) < 0.2, 0.0, rng.random(199)))])
+    lists = {
+        "n = 2": [0.0, 0.75],
+        "a +0.0 step before the half arc": [0.0, 0.25, 0.25, 1.0, 2.0],
+        "a +0.0 step after the half arc": [0.0, 0.25, 1.5, 1.5, 2.0],
+        "s_k equal to the half arc": [0.0, 0.5, 1.0, 1.25, 2.0],
+        "s_k equal to the half arc, then a +0.0 step": [0.0, 1.0, 1.0, 2.0],
+        "long": long,
+    }
+    for name, arcs in lists.items():
+        s = np.asarray(arcs, dtype=np.float64)
+        h = 0.5 * s[-1]
+        assert s[-1] > 0.0 and h > 0.0 and np.all(np.diff(s) >= 0.0), name
+        rows = np.zeros((len(s), 14))
+        rows[:, 0] = s  # the blend is not compared: any rows do
+        k, t, _, fb = api.smooth_mid_ref(rows, s)
+        bk, bt, lower = api.arc_bracket_ref(s, h)
+        assert (k, bits(np.array([t]))[0]) == (bk, bits(np.array([bt]))[0]), (name, k, t, bk, bt)
+        assert fb == (k - 1 if lower else k), (name, k, fb, lower)
+        assert s[k] >= h > s[k - 1], name
+    assert len(long) == 200 and np.any(np.diff(long) == 0.0)
+
+
 def test_len_after(api):
     for L in range(0, 12):
         n = L
