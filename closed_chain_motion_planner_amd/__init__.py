@@ -24,6 +24,8 @@ from .smooth import SMOOTH_STATS, SMOOTH_STOP, smooth_len_after, smooth_mid_ref 
 from .retime import (PANDA_ACCELERATION_LIMITS, PANDA_VELOCITY_LIMITS, RETIME_STATUS, SAMPLE_KINDS, arc_bracket_ref, resample_targets_ref,  # noqa: F401
                      timestamps_ref)
 
+from .setpoints import SETPOINT_PEAKS, SETPOINT_STATUS, setpoint_tangents_ref, setpoints_ref  # noqa: F401
+
 from .ik import ik_options, pose_ik_ref, pose_ik_vetted_ref  # noqa: F401
 
 from .object import ObjectChecker, object_propose_ref, object_valid_ref, pose_interpolate  # noqa: F401

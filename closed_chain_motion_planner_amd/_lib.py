@@ -85,6 +85,11 @@ class CcmpResampleOpts(C.Structure):
     _fields_ = [("count", C.c_int), ("spacing", C.c_double), ("max_rows", C.c_int)]
 
 
+class CcmpSetpointOpts(C.Structure):
+    """ccmp_setpoint_opts of include/ccmp.h"""
+    _fields_ = [("period", C.c_double), ("max_ticks", C.c_int)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -122,6 +127,8 @@ EXPORTS = [
     "ccmp_resample_opts_default", "ccmp_path_resample", "ccmp_sampled_paths_info", "ccmp_sampled_paths_copy", "ccmp_sampled_paths_copy_host",
     "ccmp_sampled_paths_destroy", "ccmp_path_timestamps", "ccmp_path_timestamps_host", "ccmp_path_timestamps_ref", "ccmp_arc_bracket_ref",
     "ccmp_resample_targets_ref",
+    "ccmp_setpoint_opts_default", "ccmp_path_setpoints", "ccmp_path_setpoints_host", "ccmp_setpoints_info", "ccmp_setpoints_copy", "ccmp_setpoints_copy_host",
+    "ccmp_setpoints_destroy", "ccmp_setpoints_ref", "ccmp_setpoint_tangents_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -339,6 +346,15 @@ def lib():
         "ccmp_path_timestamps_ref": ([dp, i32p, C.c_size_t, C.c_size_t, dp, dp, C.c_double, dp, dp, dp, dp, i32p], C.c_int),
         "ccmp_arc_bracket_ref": ([dp, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)], C.c_int),
         "ccmp_resample_targets_ref": ([C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), dp], C.c_int),
+        "ccmp_setpoint_opts_default": ([C.POINTER(CcmpSetpointOpts)], None),
+        "ccmp_path_setpoints": ([vp, pp, vp, C.c_double, vp, vp, vp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(CcmpSetpointOpts), C.POINTER(vp), vp], C.c_int),
+        "ccmp_path_setpoints_host": ([vp, pp, vp, C.c_double, dp, i32p, dp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(CcmpSetpointOpts), C.POINTER(vp)], C.c_int),
+        "ccmp_setpoints_info": ([vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_setpoints_copy": ([vp] + [vp] * 12 + [vp], C.c_int),
+        "ccmp_setpoints_copy_host": ([vp, dp, dp, dp, i32p, dp, u8p, dp, i32p, dp, i32p, i32p, dp], C.c_int),
+        "ccmp_setpoints_destroy": ([vp], None),
+        "ccmp_setpoints_ref": ([dp, i32p, dp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(CcmpSetpointOpts), i32p, i32p, dp, dp, dp, dp, i32p, dp], C.c_int),
+        "ccmp_setpoint_tangents_ref": ([dp, dp, C.c_size_t, dp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -388,6 +404,7 @@ DENSE_DISTINCT = 1  # ccmp.h: CCMP_DENSE_DISTINCT
 SHORTCUT_MAX_LEN = 1024  # ccmp.h: CCMP_SHORTCUT_MAX_LEN
 RETIME_OK, RETIME_EMPTY, RETIME_BROKEN, RETIME_NONFINITE, RETIME_POINT, RETIME_FULL = range(6)  # ccmp.h: CCMP_RETIME_*
 SAMPLE_PROJECTED, SAMPLE_FALLBACK, SAMPLE_DEGENERATE, SAMPLE_COPIED = range(4)  # ccmp.h: CCMP_SAMPLE_*
+SETPOINTS_OK, SETPOINTS_EMPTY, SETPOINTS_NONFINITE, SETPOINTS_UNORDERED, SETPOINTS_POINT, SETPOINTS_FULL = range(6)  # ccmp.h: CCMP_SETPOINTS_*
 
 
 def option_table():

@@ -50,6 +50,9 @@ Translation units with deliberately different flags:
   ccmp_kernels_retime.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   resample and time stamps (ccmp_retime.h): the status scan, the bracket of a target arc (ccmp_dense.h: arc_bracket, the smooth unit's too) and the blend, the pick,
                          the ceilings and the minimum of A, the envelope and the stamps' serial sum (one wavefront per path)
   ccmp_retime.cpp        -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_resample, ccmp_sampled_paths_*, ccmp_path_timestamps*: checks, launches; ccmp_path_timestamps_ref, ccmp_arc_bracket_ref, ccmp_resample_targets_ref
+  ccmp_kernels_setpoints.hip -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   controller-rate setpoints and the execution audit (ccmp_setpoints.h, which holds no fused operation): the status scan, the row
+                         tangents, the bracket of a tick on the stamps and the cubic's q and qd, the per-path peaks (one block per path)
+  ccmp_setpoints.cpp     -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_setpoints*, ccmp_setpoints_*: checks, launches, the function / is-satisfied / clearance calls over all ticks; ccmp_setpoints_ref, ccmp_setpoint_tangents_ref
 """
 import os
 import shutil
@@ -138,8 +141,12 @@ _UNITS = [
     ("ccmp_kernels_retime.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_path_resample / ccmp_path_timestamps: the checks, the launches and the rule on the host (the *_ref forms)
     ("ccmp_retime.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # controller-rate setpoints and the execution audit (ccmp_setpoints.h): status, tangent, sample and peak; the retime unit's flags; registers and LDS only
+    ("ccmp_kernels_setpoints.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # ccmp_path_setpoints: the checks, the launches and the rule on the host (ccmp_setpoints_ref, ccmp_setpoint_tangents_ref)
+    ("ccmp_setpoints.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_setpoints.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -188,6 +195,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"shortcut_", 0),  # shortcut solution paths: a slot's decode, a lane's best parent and the search's d / hops / pred live in registers and LDS, every kernel of the unit
     (r"smooth_", 0),  # smooth solution paths: a pair's decode, its bracket and a lane's row element live in registers, the length's 64 distances in LDS, every kernel of the unit
     (r"resample_|retime_", 0),  # resample and time stamps: a row's bracket, a lane's joint quotients and the limits (kernel arguments) live in registers, the stamps' 64 intervals in LDS
+    (r"setpoints_", 0),  # setpoints and audit: a tick's bracket, a lane's joint and a lane's five peaks live in registers, the block's fold of the peaks in LDS
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

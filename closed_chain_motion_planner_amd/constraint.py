@@ -552,6 +552,22 @@ class KinematicChainConstraint:
 
         return timestamps(self.ctx, rows, path_first, vmax, amax, beta, profile, stream)
 
+    def setpoint_paths(self, rows, path_first, time, vmax, amax, period=0.001, max_ticks=65536, scene=None, margin=0.0, stream=None):
+        """Controller-rate setpoints and an execution audit for timed paths (ccmp_path_setpoints; csrc/ccmp_setpoints.h): rows (R,14),
+        path_first (F+1,) int32 and time (R,) as `timestamp_paths` or any caller stamps them, vmax / amax 14 numbers each, period the
+        controller's (seconds).  Every path gets N = 1 + ceil(duration / period) ticks: positions q and velocities qd from a C1 piecewise
+        cubic through the rows with PCHIP tangents — it cannot overshoot its rows and is at rest at both ends — and tick times tau; per
+        tick the constraint gap f = (|dp|, angle), `isSatisfied` and, with a ProxyScene, the clearance; per path the audit: peak (F,5)
+        and peak_tick (F,5) in the order SETPOINT_PEAKS (speed and acceleration as ratios of the limits, measured at the controller's
+        rate), counts (F,2) = ticks off the manifold's tolerance and ticks below margin, stretch (F,) = the factor on all stamps that
+        would bring the measured peaks to the limits (a report, not a guarantee for the stretched grid), status (F,) (SETPOINT_STATUS).
+        Setpoints are NOT projected: the gap is what the resample spacing leaves, and the audit reports it.  Returns a dict of device
+        tensors, or of numpy arrays through the host form, plus ticks.  Synchronous."""
+        from .setpoints import setpoints
+
+        self._need_problem()
+        return setpoints(self.ctx, self.problem, rows, path_first, time, vmax, amax, period, max_ticks, scene, margin, stream)
+
     def shortcut_paths(self, path_joints, path_len, scene=None, margin=None, max_span=0, chunk_states=16, round_budget=128, max_calls=4096,
                        tile_edges=65536, pairs=False, stream=None):
         """The removal of interior vertices from F solution paths (ccmp_path_shortcut; csrc/ccmp_shortcut.h): path_joints (F,max_len,14)

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; struct retime_limits; }
+namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; struct retime_limits; struct setpoint_limits; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -293,6 +293,21 @@ hipError_t retime_envelope(const double *ceiling, const int32_t *path_first, siz
 /* time[r] and duration[f]; rows of a path that is not OK are not written, its duration is +0.0 (EMPTY) or NaN (NONFINITE) */
 hipError_t retime_stamp(const double *rows, const double *envelope, const int32_t *path_first, const int32_t *status, const unsigned long long *a_bits,
                         const ccmp::retime_limits &lim, size_t F, double *time, double *duration, hipStream_t st);
+/* controller-rate setpoints and the execution audit (ccmp_path_setpoints; csrc/ccmp_setpoints.h).  status [F] and ticks [F] of the packed rows'
+ * paths under their stamps: EMPTY (also a range that is negative, decreasing or beyond total_rows), NONFINITE, UNORDERED, POINT (one tick), FULL, OK */
+hipError_t setpoints_status(const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows, double period, int max_ticks,
+                            int32_t *status, int32_t *ticks, hipStream_t st);
+/* tangent [total_rows][14] = w_i of every row of an OK path */
+hipError_t setpoints_tangent(const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows, const int32_t *status,
+                             double *tangent, hipStream_t st);
+/* per tick g < M of the paths' tick ranges tick_first [F + 1]: q, qd [M][14], tau [M]; clearance [M] = NaN (a scene's answer replaces it) */
+hipError_t setpoints_sample(const double *rows, const int32_t *path_first, const double *time, const double *tangent, const int32_t *status,
+                            const int32_t *tick_first, size_t F, size_t M, size_t total_rows, double period, double *q, double *qd, double *tau,
+                            double *clearance, hipStream_t st);
+/* one block per path: peak, peak_tick [F][5], counts [F][2], stretch [F] */
+hipError_t setpoints_peak(const double *qd, const double *tau, const double *f, const uint8_t *satisfied, const double *clearance, const int32_t *tick_first,
+                          size_t F, size_t M, const ccmp::setpoint_limits &lim, double margin, double *peak, int32_t *peak_tick, int32_t *counts,
+                          double *stretch, hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

@@ -1256,6 +1256,73 @@ int ccmp_path_timestamps_ref(const double *rows, const int32_t *path_first, size
 int ccmp_arc_bracket_ref(const double *arcs, int n, double h, int *k, double *t, int *lower);
 int ccmp_resample_targets_ref(double T, int count, double spacing, int max_rows, int *N, double *h_out);
 
+/* ---- executing a path: controller-rate setpoints and an execution audit ------------------------------------------------------------- */
+/* Time stamps end at packed rows with one time per row; a robot is commanded at a fixed period (a Panda: 1 kHz).  ccmp_path_setpoints turns
+ * (rows, stamps, period) into what is commanded at every controller tick and says what that motion does between the rows.  The rule is
+ * csrc/ccmp_setpoints.h, stated once for the kernels and the _ref forms (no fused operation), bit for bit against each other.
+ *     status         [F], tested in this order: CCMP_SETPOINTS_EMPTY R == 0 (device form: also a range that is negative, decreasing or
+ *                    beyond total_rows, never read); _NONFINITE a row coordinate or a stamp is not finite; _UNORDERED t_0 != 0, some
+ *                    t_{i+1} < t_i, or t_{i+1} == t_i while rows i and i + 1 differ; _POINT R == 1 or D = t_{R-1} not > 0 (one tick: q = r_0,
+ *                    qd = 0, tau = +0.0); _FULL N > max_ticks or beyond INT32_MAX (no tick); else _OK, N ticks.
+ *     ticks          N = 1 + (int64)ceil(D / period), at least 2; tau_0 = +0.0, tau_{N-1} = D, else tau_j = min(fl((double)j period), D).
+ *     setpoints      q, qd [ticks][14], tau [ticks]: a C1 piecewise cubic through the rows at their stamps with PCHIP (Fritsch-Butland)
+ *                    tangents, at rest at both ends: it cannot overshoot its rows.  Tangents, bracket and the operation order of q and qd:
+ *                    csrc/ccmp_setpoints.h.  Setpoints are NOT projected, deliberately: a projection moves a point by up to the
+ *                    projector's tolerance, differently from tick to tick — divided by dt^2 = 1e-6 that is acceleration noise of order
+ *                    1e3 rad/s^2.  The knob for the gap is the resample spacing; the audit says whether it is fine enough.
+ *     per tick       f [ticks][2] = ccmp_function_batch's (|dp|, angle) of q, satisfied [ticks] = ccmp_is_satisfied_batch's, clearance
+ *                    [ticks] = ccmp_clearance_batch's with a scene, NaN without: those launchers, unchanged, once each over all ticks.
+ *     audit          per path: peak [F][5] and peak_tick [F][5] in the order speed ratio max |qd| / vmax, acceleration ratio max (|qd_{j+1} -
+ *                    qd_j| / (tau_{j+1} - tau_j)) / amax over intervals of positive width (at the left tick), max |dp|, max angle, min
+ *                    clearance; ties go to the smallest tick, a NaN never contributes, a peak without contributor is +0.0 (clearance
+ *                    +inf) at tick -1.  counts [F][2] = ticks isSatisfied refuses, ticks with clearance < margin.  stretch [F] = max(1,
+ *                    speed ratio, sqrt(acceleration ratio)): the factor on all stamps that would scale the measured peaks to the limits
+ *                    — a report; the stretched call has another tick grid and nothing is claimed for it.  The acceleration figure is
+ *                    the mean acceleration over a tick interval of the interpolant's exact derivative, not a second difference of
+ *                    positions.  The time stamps bound their profile at the rows; THIS is where the executed motion is measured.
+ *   ccmp_path_setpoints   device pointers; vmax, amax HOST arrays.  SYNCHRONOUS on its stream (it reads F status words and F tick counts
+ *                    to size the result): not capturable.  scene nullable.  opts == NULL: the defaults.  On any error no handle and no
+ *                    partial output.
+ *   ccmp_setpoint_opts_default   period 0.001, max_ticks 65 536.
+ *   _host            host pointers (rows, path_first, time), synchronous on the context's stream.
+ *   ccmp_setpoints_info / _copy / _copy_host / _destroy   the result: F and the tick count; copies into device (asynchronous on hip_stream)
+ *                    or host (synchronous) destinations, each nullable: q, qd [ticks][14], tau [ticks], tick_first [F + 1], f [ticks][2],
+ *                    satisfied [ticks] (uint8), clearance [ticks], status [F], peak [F][5], peak_tick [F][5] (int32), counts [F][2],
+ *                    stretch [F].
+ *   ccmp_setpoints_ref   the interpolation and the speed and acceleration audit as pure host code, one thread, no device, never
+ *                    CCMP_ENODEV: tick_first [F + 1] and status [F] always; q, qd, tau, peak [F][2] (speed, acceleration), peak_tick [F][2],
+ *                    stretch [F] where given (two-call sizing: NULL arrays first).  f and the clearance are other units' rules.
+ *   ccmp_setpoint_tangents_ref   the tangents of ONE path alone: rows [R][14], time [R] -> w_out [R][14].
+ * CCMP_EINVAL: a period that is not finite and > 0, max_ticks < 2, a limit that is not finite and positive, a NULL out, problem, vmax, amax,
+ * path_first, tick_first or status, NULL rows or time with total_rows > 0, (host and _ref forms) a path_first that is negative, decreases
+ * or ends beyond total_rows, a scene of another device or a NaN margin with one.  CCMP_EOVERFLOW: more than INT32_MAX ticks in all.
+ * Order of use: shortcut -> smooth -> densify -> resample -> the host's validity test over the new rows -> time stamps -> setpoints and
+ * audit -> execute. */
+enum { CCMP_SETPOINTS_OK = 0, CCMP_SETPOINTS_EMPTY = 1, CCMP_SETPOINTS_NONFINITE = 2, CCMP_SETPOINTS_UNORDERED = 3, CCMP_SETPOINTS_POINT = 4,
+       CCMP_SETPOINTS_FULL = 5 };
+typedef struct ccmp_setpoint_opts {
+  double period; /* the controller's period, seconds, finite and > 0 */
+  int max_ticks; /* a path that would get more ticks is CCMP_SETPOINTS_FULL, >= 2 */
+} ccmp_setpoint_opts;
+void ccmp_setpoint_opts_default(ccmp_setpoint_opts *opts);
+typedef struct ccmp_setpoints ccmp_setpoints;
+int ccmp_path_setpoints(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *rows, const int32_t *path_first,
+                        const double *time, size_t F, size_t total_rows, const double *vmax, const double *amax, const ccmp_setpoint_opts *opts,
+                        ccmp_setpoints **out, void *hip_stream);
+int ccmp_path_setpoints_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *rows, const int32_t *path_first,
+                             const double *time, size_t F, size_t total_rows, const double *vmax, const double *amax, const ccmp_setpoint_opts *opts,
+                             ccmp_setpoints **out);
+int ccmp_setpoints_info(const ccmp_setpoints *h, size_t *F, size_t *ticks);
+int ccmp_setpoints_copy(ccmp_setpoints *h, double *q, double *qd, double *tau, int32_t *tick_first, double *f, uint8_t *satisfied, double *clearance,
+                        int32_t *status, double *peak, int32_t *peak_tick, int32_t *counts, double *stretch, void *hip_stream);
+int ccmp_setpoints_copy_host(ccmp_setpoints *h, double *q, double *qd, double *tau, int32_t *tick_first, double *f, uint8_t *satisfied, double *clearance,
+                             int32_t *status, double *peak, int32_t *peak_tick, int32_t *counts, double *stretch);
+void ccmp_setpoints_destroy(ccmp_setpoints *h);
+int ccmp_setpoints_ref(const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows, const double *vmax, const double *amax,
+                       const ccmp_setpoint_opts *opts, int32_t *tick_first, int32_t *status, double *q, double *qd, double *tau, double *peak,
+                       int32_t *peak_tick, double *stretch);
+int ccmp_setpoint_tangents_ref(const double *rows, const double *time, size_t R, double *w_out);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault
  * injection — are not part of this library: include/ccmp_debug.h, lib/libccmp_debug.so) */

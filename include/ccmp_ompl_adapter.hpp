@@ -768,6 +768,67 @@ inline int timestampPath(const Projector &proj, const std::vector<std::array<dou
   return CCMP_OK;
 }
 
+// What a controller is commanded at every tick of its period along a timed path, and the audit of that motion (include/ccmp.h:
+// ccmp_path_setpoints_host): q, qd = one row of 14 per tick, tau = the tick times (tau[0] = 0, the last = the duration); f = the
+// constraint gap (|dp|, angle) per tick, satisfied = isSatisfied, clearance = against `scene` (NaN without one); peak / peak_tick in the
+// order speed ratio, acceleration ratio, |dp|, angle, clearance; n_off / n_below = ticks isSatisfied refuses / with clearance < margin;
+// stretch = the factor on all stamps that would bring the measured peaks to the limits (a report).  status = CCMP_SETPOINTS_*.
+struct Setpoints {
+  std::vector<std::array<double, 14>> q, qd;
+  std::vector<double> tau, clearance;
+  std::vector<std::array<double, 2>> f;
+  std::vector<uint8_t> satisfied;
+  int32_t status = CCMP_SETPOINTS_EMPTY;
+  double peak[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  int32_t peak_tick[5] = {-1, -1, -1, -1, -1};
+  int32_t n_off = 0, n_below = 0;
+  double stretch = 1.0;
+};
+
+// The setpoints of ONE path: states and times as ccmp::timestampPath leaves them (any stamps that start at 0 and do not decrease), vmax /
+// amax = 14 numbers each, period > 0 the controller's, max_ticks >= 2; scene (nullable) and margin for the ticks' clearance.  The
+// setpoints are NOT projected: between rows they leave the manifold by what the resample spacing allows, and out->peak says by how much.
+// A path that is empty, not finite, out of order or over max_ticks comes back with CCMP_OK, its status and no tick.  Returns the library's
+// code and leaves *out untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int setpointPath(const Projector &proj, const std::vector<std::array<double, 14>> &states, const std::vector<double> &times, const double *vmax,
+                        const double *amax, Setpoints *out, double period = 0.001, int max_ticks = 65536, const ccmp_scene *scene = nullptr,
+                        double margin = 0.0)
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double) && sizeof(std::array<double, 2>) == 2 * sizeof(double), "rows are contiguous");
+  if (!out || states.size() != times.size() || states.size() > (size_t)0x7fffffff) return CCMP_EINVAL;
+  const ccmp_problem P = detail::problemWith(proj, 0.0, 0.0);
+  const int32_t first[2] = {0, (int32_t)states.size()};
+  const ccmp_setpoint_opts o = {period, max_ticks};
+  ccmp_setpoints *h = nullptr;
+  int rc = ccmp_path_setpoints_host(proj.ctx(), &P, scene, margin, states.empty() ? nullptr : states[0].data(), first, times.empty() ? nullptr : times.data(), 1,
+                                    states.size(), vmax, amax, &o, &h);
+  if (rc != CCMP_OK) return rc;
+  Setpoints s;
+  size_t ticks = 0;
+  try {
+    rc = ccmp_setpoints_info(h, nullptr, &ticks);
+    s.q.resize(ticks);
+    s.qd.resize(ticks);
+    s.tau.resize(ticks);
+    s.clearance.resize(ticks);
+    s.f.resize(ticks);
+    s.satisfied.resize(ticks);
+  } catch (...) {
+    rc = CCMP_ENOMEM;
+  }
+  int32_t counts[2] = {0, 0};
+  if (rc == CCMP_OK)
+    rc = ccmp_setpoints_copy_host(h, ticks ? s.q[0].data() : nullptr, ticks ? s.qd[0].data() : nullptr, ticks ? s.tau.data() : nullptr, nullptr,
+                                  ticks ? s.f[0].data() : nullptr, ticks ? s.satisfied.data() : nullptr, ticks ? s.clearance.data() : nullptr, &s.status, s.peak,
+                                  s.peak_tick, counts, &s.stretch);
+  ccmp_setpoints_destroy(h);
+  if (rc != CCMP_OK) return rc;
+  s.n_off = counts[0];
+  s.n_below = counts[1];
+  *out = std::move(s);
+  return CCMP_OK;
+}
+
 // ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
 // The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
 // rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
@@ -1135,6 +1196,24 @@ public:
     } catch (...) {
       err_.record(CCMP_ENOMEM, "Roadmap::constructTimedSolution");
     }
+    return true;
+  }
+
+  // constructTimedSolution followed by the setpoints of its rows at the controller's period and their audit (ccmp::setpointPath above):
+  // what is executed, and what that motion does between the rows.  On a library error in that step — or a solution that came back
+  // without times — the answer FALLS BACK to the timed solution with `setpoints` empty (true, status CCMP_SETPOINTS_EMPTY, lastError() set
+  // on an error).  false with no states when no pair is connected or the solution step itself failed.
+  bool constructExecutableSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states,
+                                   std::vector<double> &times, Setpoints &setpoints, const double *vmax, const double *amax, double period = 0.001,
+                                   int max_ticks = 65536, const ccmp_scene *scene = nullptr, double margin = 0.0, double beta = 0.5, int count = 0,
+                                   double spacing = 0.0, int max_steps = 5, double min_change = 0.005, int max_span = 0, double *cost = nullptr,
+                                   std::vector<int32_t> *indices = nullptr, double delta = 0.0, double lambda = 0.0) const noexcept
+  {
+    setpoints = Setpoints();  // (empty vectors: nothing is allocated)
+    if (!constructTimedSolution(starts, goals, states, times, vmax, amax, beta, count, spacing, max_steps, min_change, max_span, cost, indices, delta, lambda))
+      return false;
+    if (times.size() == states.size() && !states.empty())
+      call([&] { return setpointPath(proj_, states, times, vmax, amax, &setpoints, period, max_ticks, scene, margin); }, "ccmp_path_setpoints_host");
     return true;
   }
 
@@ -1566,6 +1645,24 @@ inline void printTrajectory(std::ostream &out, const double *states, const doubl
   }
   out << '\n';
   out.flush();
+}
+
+// The setpoints of a path (ccmp::Setpoints): one controller tick per line — tau, the positions, the velocities, each followed by a space —
+// and the empty line after the last tick.
+inline void printSetpoints(std::ostream &out, const double *tau, const double *q, const double *qd, size_t n_ticks, size_t dim = 14)
+{
+  for (size_t i = 0; i < n_ticks; ++i) {
+    out << tau[i] << ' ';
+    for (size_t j = 0; j < dim; ++j) out << q[i * dim + j] << ' ';
+    for (size_t j = 0; j < dim; ++j) out << qd[i * dim + j] << ' ';
+    out << '\n';
+  }
+  out << '\n';
+  out.flush();
+}
+inline void printSetpoints(std::ostream &out, const Setpoints &s)
+{
+  printSetpoints(out, s.tau.data(), s.q.empty() ? nullptr : s.q[0].data(), s.qd.empty() ? nullptr : s.qd[0].data(), s.tau.size());
 }
 
 // PlannerData::printGraphML as ConstrainedProblem::dumpGraph writes `<obj>_node_info.graphml`
@@ -2010,6 +2107,21 @@ public:
       const ccmp::Projector &proj = chain_->impl();
       std::lock_guard<std::mutex> hold(proj.mutex());
       ccmp::check(ccmp::timestampPath(proj, states, vmax, amax, beta, times, duration), "ccmp_path_timestamps_host");
+    });
+  }
+
+  // What a controller is commanded at every tick of `period` along the timed path, and the audit of that motion (ccmp::setpointPath):
+  // states and times as timePath leaves them; scene (nullable) and margin for the ticks' clearance.  The setpoints are not projected; the
+  // audit's peaks say how far the motion between the rows leaves the manifold and how it stands against the limits at the controller's
+  // rate.  false with *out untouched when the call failed (KinematicChainConstraint::lastError()); a path the rule gives no ticks for
+  // (out of order, not finite, over max_ticks) is true with its status in out->status.
+  bool setpointPath(const std::vector<std::array<double, 14>> &states, const std::vector<double> &times, const double *vmax, const double *amax,
+                    ccmp::Setpoints *out, double period = 0.001, int max_ticks = 65536, const ccmp_scene *scene = nullptr, double margin = 0.0) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      ccmp::check(ccmp::setpointPath(proj, states, times, vmax, amax, out, period, max_ticks, scene, margin), "ccmp_path_setpoints_host");
     });
   }
 

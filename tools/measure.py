@@ -49,7 +49,9 @@
                                                            waypoints, both Jacobian modes, the extend calls made and the bytes read on the host; writes profiles/smooth.md
     python tools/measure.py retime [reps]                   resample and time stamps: ccmp_path_resample and ccmp_path_timestamps on the smooth measurement's inputs,
                                                            continued (1 and 64 paths), the kind counts; the recorded paths' durations on the CPU; writes profiles/retime.md
-    python tools/measure.py smooth_restate <file.npz> [n]   the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
+    python tools/measure.py setpoints [reps]                setpoints and the execution audit: ccmp_path_setpoints at 1 ms on the retime measurement's inputs, continued
+                                                           (1 and 64 paths); the recorded paths' five peaks and stretch from the library; writes profiles/setpoints.md
+    python tools/measure.py smooth_restate <file.npz> [n]  the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
                                                            stefan_tight | calibrated | clearance
@@ -1627,6 +1629,78 @@ def retime(argv):
                 "asserted: the rule bounds the speed profile at the rows, not finite differences of the sampled trajectory.\n\n```\n" + "\n".join(lines) + "\n```\n")
 
 
+def setpoints(argv):
+    """ccmp_path_setpoints (KinematicChainConstraint.setpoint_paths) on the retime measurement's inputs, continued: 1 and 64 paths of 32
+    waypoints, three smoothing passes, densified, resampled at the problem's delta and stamped under the Panda's limits, then the
+    setpoints at 1 ms with their audit; wall clock around the synchronous call (the mirror's copy-out included), medians; the ticks, the
+    statuses and the medians of the peaks.  Then the reference's two recorded path files, stamped on the CPU (ccmp_path_timestamps_ref)
+    and put through the device call at 1 ms: the audit's five peaks, where they occur, and the stretch — the library's own figures for
+    what the time stamps leave open.  Writes profiles/setpoints.md."""
+    import os
+
+    from closed_chain_motion_planner_amd import PANDA_ACCELERATION_LIMITS, PANDA_VELOCITY_LIMITS, SETPOINT_STATUS, timestamps_ref
+
+    reps = int(argv[0]) if len(argv) > 0 else 9
+    Lw, seed, steps = 32, 0x5C7, 3
+    vmax, amax = PANDA_VELOCITY_LIMITS * 2, PANDA_ACCELERATION_LIMITS * 2
+    ctx = Context(0)
+    lines = []
+
+    def say(text):
+        print(text)
+        lines.append(text)
+
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    pj, pl = _smooth_paths(c, 64, Lw, seed)
+    c.setJacobianMode(1)  # the setpoints do not depend on the mode; the path that feeds them is made in analytic mode
+    for F in (1, 64):
+        sm = c.smooth_paths(pj[:F].contiguous(), pl[:F].contiguous(), max_steps=steps)
+        dense = c.densify_paths(sm["joints"], sm["out_len"], distinct=True, keep_handle=True)
+        rs = c.resample_paths(dense)
+        dense["handle"].close()
+        ts = c.timestamp_paths(rs["joints"], rs["path_first"], vmax, amax)
+        t_sp = []
+        for i in range(reps + 2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sp = c.setpoint_paths(rs["joints"], rs["path_first"], ts["time"], vmax, amax)
+            torch.cuda.synchronize()
+            if i >= 2:
+                t_sp.append((time.perf_counter() - t0) * 1e3)
+        status = sp["status"].cpu().numpy()
+        ok = status == 0
+        peak = sp["peak"].cpu().numpy()[ok]
+        say("F = %d paths, %d rows at spacing %.3g -> %d ticks at 1 ms; status %s; medians over the OK paths: speed %.2f x vmax, acceleration %.2f x amax, "
+            "max |dp| %.2e m, max angle %.2e rad, stretch %.2f; %d of the ticks refused by isSatisfied"
+            % (F, rs["rows"], c.problem.delta, sp["ticks"], {SETPOINT_STATUS[k]: int((status == k).sum()) for k in sorted(set(status.tolist()))},
+               *([float(np.median(peak[:, k])) for k in range(4)] if len(peak) else [float("nan")] * 4),
+               float(np.median(sp["stretch"].cpu().numpy()[ok])) if ok.any() else float("nan"), int(sp["counts"][:, 0].sum())))
+        say("    %-84s %s" % ("ccmp_path_setpoints (status read, four launches, function + isSatisfied over all ticks; copy-out included)", _stat(t_sp)))
+    say("")
+    say("the reference's recorded paths, stamped on the CPU (ccmp_path_timestamps_ref) under the Panda's limits, beta 0.5, then ccmp_path_setpoints at 1 ms:")
+    for obj in ("Wine_Bottle", "dumbbell"):
+        rows = np.loadtxt(os.path.join("tests", "golden", "paths", obj + "_path.txt"))
+        first = np.array([0, len(rows)], dtype=np.int32)
+        t = timestamps_ref(rows, first, vmax, amax)["time"]
+        c2 = KinematicChainConstraint.from_yaml(CFG % obj, ctx=ctx)
+        sp = c2.setpoint_paths(rows, first, t, vmax, amax)
+        p, j = sp["peak"][0], sp["peak_tick"][0]
+        say("    %-12s %2d rows, %.3f s, status %s: %d ticks; speed %.3f x vmax at tick %d; mean tick-interval acceleration %.3f x amax at tick %d; max |dp| %.3e m at "
+            "tick %d; max angle %.3e rad at tick %d; clearance %s (no scene); %d ticks refused by isSatisfied; stretch %.3f"
+            % (obj, len(rows), float(t[-1]), SETPOINT_STATUS[int(sp["status"][0])], sp["ticks"], p[0], j[0], p[1], j[1], p[2], j[2], p[3], j[3], p[4], int(sp["counts"][0, 0]),
+               float(sp["stretch"][0])))
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "setpoints.md"), "w") as f:
+        f.write("# Setpoints and the execution audit on the device: `tools/measure.py setpoints`\n\n1 x MI355X, one run, seed 0x5C7; the retime measurement's inputs, "
+                "continued: three smoothing passes, densified (distinct layout), resampled at the problem's delta, stamped under the Panda's data-sheet limits, then "
+                "`ccmp_path_setpoints` at a period of 1 ms; wall clock around the synchronous call, no GPU time measured.  No speed threshold gates this feature.  "
+                "The audit's figures are measurements of the executed motion, not bounds: the time stamps bound their profile at the rows, and these are what the "
+                "commanded trajectory does between them.  The setpoints are not projected; `max |dp|` and `max angle` are the gap that leaves (the projector's "
+                "tolerances are 1e-3 m and 5e-3 rad: at a spacing of the problem's delta most ticks are outside them, which is what the audit is for).  A path "
+                "the resampling refused (`profiles/retime.md`: 59 of the 64 are broken, a segment that stops short) arrives without rows and answers EMPTY.\n\n```\n"
+                + "\n".join(lines) + "\n```\n")
+
+
 def smooth_restate(argv):
     """the plain-Python restatement of the smoothing rule (tests/smooth_cases.py on the det oracle) on one host core, on the inputs `smooth`
     wrote, compared bit for bit with the results it wrote: python tools/measure.py smooth_restate <file.npz> [paths]"""
@@ -1725,7 +1799,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
