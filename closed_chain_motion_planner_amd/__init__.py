@@ -26,6 +26,8 @@ from .retime import (PANDA_ACCELERATION_LIMITS, PANDA_VELOCITY_LIMITS, RETIME_ST
 
 from .setpoints import SETPOINT_PEAKS, SETPOINT_STATUS, setpoint_tangents_ref, setpoints_ref  # noqa: F401
 
+from .fit import FIT_STATUS, fit_timestamps_ref  # noqa: F401
+
 from .ik import ik_options, pose_ik_ref, pose_ik_vetted_ref  # noqa: F401
 
 from .object import ObjectChecker, object_propose_ref, object_valid_ref, pose_interpolate  # noqa: F401

@@ -552,6 +552,20 @@ class KinematicChainConstraint:
 
         return timestamps(self.ctx, rows, path_first, vmax, amax, beta, profile, stream)
 
+    def fit_timestamps(self, rows, path_first, time, vmax, amax, period=0.001, max_ticks=65536, aim=0.95, max_passes=8, stream=None):
+        """Time stamps fitted to the limits at the controller's rate (ccmp_path_fit_timestamps; csrc/ccmp_fit.h), the step between
+        `timestamp_paths` and `setpoint_paths`: rows (R,14), path_first (F+1,) int32, time (R,), vmax / amax 14 numbers each.  Per path the
+        commanded motion is measured at the ticks of `period` (the ticks of `setpoint_paths`, never materialised), the row intervals in
+        which it exceeds a limit are dilated to `aim` of it, and the measurement repeats — at most max_passes dilations.  Returns
+        dict(time (R,) the fitted stamps, status (F,) (FIT_STATUS: fitted, the setpoints' reasons, passes), passes (F,), peak (F,2) the
+        speed and acceleration ratios of the last measurement — what `setpoint_paths` on `time` reports, bit for bit —, duration (F,),
+        factor (R,) the dilation of each row interval at its right row) of device tensors, or of numpy arrays through the host form.  A
+        path that is done is never touched again; durations never shrink.  Not TOPP-RA, no jerk limit, a bound only at the ticks of this
+        period; convergence is observed, not proven (status says).  Synchronous."""
+        from .fit import fit
+
+        return fit(self.ctx, rows, path_first, time, vmax, amax, period, max_ticks, aim, max_passes, stream)
+
     def setpoint_paths(self, rows, path_first, time, vmax, amax, period=0.001, max_ticks=65536, scene=None, margin=0.0, stream=None):
         """Controller-rate setpoints and an execution audit for timed paths (ccmp_path_setpoints; csrc/ccmp_setpoints.h): rows (R,14),
         path_first (F+1,) int32 and time (R,) as `timestamp_paths` or any caller stamps them, vmax / amax 14 numbers each, period the

@@ -308,6 +308,21 @@ hipError_t setpoints_sample(const double *rows, const int32_t *path_first, const
 hipError_t setpoints_peak(const double *qd, const double *tau, const double *f, const uint8_t *satisfied, const double *clearance, const int32_t *tick_first,
                           size_t F, size_t M, const ccmp::setpoint_limits &lim, double margin, double *peak, int32_t *peak_tick, int32_t *counts,
                           double *stretch, hipStream_t st);
+/* time stamps fitted to the limits at the controller's rate (ccmp_path_fit_timestamps; csrc/ccmp_fit.h).  time_out = time over every path's
+ * checked range; status [F] = open, passes [F] = 0, peak [F][2] and duration [F] = +0.0 */
+hipError_t fit_begin(const int32_t *path_first, const double *time, size_t F, size_t total_rows, double *time_out, int32_t *status, int32_t *passes,
+                     double *peak, double *duration, hipStream_t st);
+/* per tick interval g < M of the paths' ranges tick_first [F + 1] (N - 1 intervals for a path that is measured, none for any other): s_j and
+ * a_j folded into S and A [total_rows] (bit patterns, cleared before) at the rows of the interval's brackets */
+hipError_t fit_measure(const double *rows, const int32_t *path_first, const double *time, const double *tangent, const int32_t *tick_first, size_t F,
+                       size_t M, size_t total_rows, double period, const ccmp::setpoint_limits &lim, unsigned long long *S, unsigned long long *A,
+                       hipStream_t st);
+/* one wavefront per open path: sp_status (this pass's setpoints status) ends it, or the done test does, or its stamps are dilated in place
+ * and its S and A cleared */
+hipError_t fit_dilate(const int32_t *path_first, const int32_t *sp_status, size_t F, double aim, int max_passes, double *time, unsigned long long *S,
+                      unsigned long long *A, int32_t *status, int32_t *passes, double *peak, double *duration, hipStream_t st);
+/* factor[r] = time_out's interval over time's at its right row; row 0 of a path and intervals without positive input width: 1.0 */
+hipError_t fit_factor(const int32_t *path_first, size_t F, size_t total_rows, const double *time, const double *time_out, double *factor, hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

@@ -541,20 +541,29 @@ class Roadmap:
         stamps = constraint.timestamp_paths(sampled["joints"], sampled["path_first"], vmax, amax, beta=beta)
         return float(stamps["duration"][0]), idx, sampled, stamps, dense, sm, sc
 
-    def executable_solution(self, constraint, starts, goals, vmax, amax, period=0.001, max_ticks=65536, audit_scene=None, audit_margin=0.0, **kw):
-        """solution -> shortcut -> smooth -> densify -> resample -> time stamps -> setpoints and audit: `timed_solution` (kw: its keyword
-        arguments), then `constraint.setpoint_paths` on its rows and stamps; audit_scene / audit_margin: the proxy scene the ticks' clearance is
-        taken against.  Returns (setpoints, duration, indices, sampled, stamps, dense, smooth, shortcut) with setpoints the dict of
-        `setpoint_paths`, or None when no pair is connected.  The resampled rows are new states: they go to the host's validity test first."""
+    def executable_solution(self, constraint, starts, goals, vmax, amax, period=0.001, max_ticks=65536, audit_scene=None, audit_margin=0.0, fit=False,
+                            fit_aim=0.95, fit_max_passes=8, **kw):
+        """solution -> shortcut -> smooth -> densify -> resample -> time stamps -> [fit ->] setpoints and audit: `timed_solution` (kw: its
+        keyword arguments), then `constraint.setpoint_paths` on its rows and stamps; audit_scene / audit_margin: the proxy scene the ticks'
+        clearance is taken against.  Returns (setpoints, duration, indices, sampled, stamps, dense, smooth, shortcut) with setpoints the dict
+        of `setpoint_paths`, or None when no pair is connected.  fit=True: the stamps go through `constraint.fit_timestamps` (period,
+        max_ticks, fit_aim, fit_max_passes) first, the setpoints are those of the fitted stamps, and the fit's dict is appended to the
+        tuple (duration and stamps stay the time-stamp rule's; the fitted ones are the dict's).  The resampled rows are new states: they
+        go to the host's validity test first."""
         sol = self.timed_solution(constraint, starts, goals, vmax, amax, **kw)
         if sol is None:
             return None
         sampled, stamps = sol[2], sol[3]
         if audit_scene is None and kw.get("scene") is not None:  # the scene the path was made against audits it too
             audit_scene, audit_margin = kw["scene"], kw.get("margin", audit_margin)
-        sp = constraint.setpoint_paths(sampled["joints"], sampled["path_first"], stamps["time"], vmax, amax, period=period, max_ticks=max_ticks,
+        time, fitted = stamps["time"], ()
+        if fit:
+            fitted = (constraint.fit_timestamps(sampled["joints"], sampled["path_first"], time, vmax, amax, period=period, max_ticks=max_ticks, aim=fit_aim,
+                                                max_passes=fit_max_passes),)
+            time = fitted[0]["time"]
+        sp = constraint.setpoint_paths(sampled["joints"], sampled["path_first"], time, vmax, amax, period=period, max_ticks=max_ticks,
                                        scene=audit_scene, margin=audit_margin)
-        return (sp,) + tuple(sol)
+        return (sp,) + tuple(sol) + fitted
 
     def close(self):
         if self._h:

@@ -1296,8 +1296,8 @@ int ccmp_resample_targets_ref(double T, int count, double spacing, int max_rows,
  * CCMP_EINVAL: a period that is not finite and > 0, max_ticks < 2, a limit that is not finite and positive, a NULL out, problem, vmax, amax,
  * path_first, tick_first or status, NULL rows or time with total_rows > 0, (host and _ref forms) a path_first that is negative, decreases
  * or ends beyond total_rows, a scene of another device or a NaN margin with one.  CCMP_EOVERFLOW: more than INT32_MAX ticks in all.
- * Order of use: shortcut -> smooth -> densify -> resample -> the host's validity test over the new rows -> time stamps -> setpoints and
- * audit -> execute. */
+ * Order of use: shortcut -> smooth -> densify -> resample -> the host's validity test over the new rows -> time stamps -> fit (below) ->
+ * setpoints and audit -> execute. */
 enum { CCMP_SETPOINTS_OK = 0, CCMP_SETPOINTS_EMPTY = 1, CCMP_SETPOINTS_NONFINITE = 2, CCMP_SETPOINTS_UNORDERED = 3, CCMP_SETPOINTS_POINT = 4,
        CCMP_SETPOINTS_FULL = 5 };
 typedef struct ccmp_setpoint_opts {
@@ -1322,6 +1322,63 @@ int ccmp_setpoints_ref(const double *rows, const int32_t *path_first, const doub
                        const ccmp_setpoint_opts *opts, int32_t *tick_first, int32_t *status, double *q, double *qd, double *tau, double *peak,
                        int32_t *peak_tick, double *stretch);
 int ccmp_setpoint_tangents_ref(const double *rows, const double *time, size_t R, double *w_out);
+
+/* ---- executing a path: time stamps fitted to the limits at the controller's rate ---------------------------------------------------- */
+/* The time stamps bound their profile at the rows; the setpoints' audit measures what is commanded between them, and on the recorded paths
+ * it measures up to 1.1 x vmax and 3.5 x amax at 1 ms.  ccmp_path_fit_timestamps is the step between the two: it measures the commanded
+ * motion at the ticks of the stated period, dilates ONLY the row intervals in which it exceeds a limit, measures again and repeats until the
+ * audit passes.  The rule is csrc/ccmp_fit.h, stated once for the kernels and the _ref form (no fused operation), bit for bit against each
+ * other; status, ticks, tangents and qd are the setpoints rule's, unchanged.  Per path, with stamps t (the input's at pass 0), passes = 0:
+ *     status         the setpoints status of (rows, t).  _EMPTY, _NONFINITE, _UNORDERED, _POINT and _FULL end the path with that value and the
+ *                    stamps it was found on (at pass 0: the input's; a device range that is never read is never written); _FULL can arise
+ *                    after a dilation.  peak then holds the last measurement made, +0.0 without one.
+ *     measurement    over the ticks of the setpoints rule, never materialised: k_j the bracket of tau_j (k_0 = k_1), s_j = max_c |qd_j[c]| /
+ *                    vmax_c, a_j = max_c (|qd_{j+1}[c] - qd_j[c]| / (tau_{j+1} - tau_j)) / amax_c over intervals of positive width; per row
+ *                    interval k = 1 .. R-1: S_k = max{ s_j : k_j = k }, A_k = max{ a_j : k_j <= k <= k_{j+1} }, +0.0 for an empty set; a NaN
+ *                    never contributes.  P_s = max_k S_k, P_a = max_k A_k: the speed and acceleration peaks ccmp_path_setpoints' audit
+ *                    reports for the same stamps, bit for bit.
+ *     done           P_s <= 1 and P_a <= 1: CCMP_FIT_FITTED (0), stamps untouched; else passes == max_passes: CCMP_FIT_PASSES, stamps as
+ *                    measured.
+ *     dilation       f_k = max(1, S_k / aim, sqrt(A_k / aim)), h'_k = (t_k - t_{k-1}) f_k, t'_0 = +0.0, t'_k = t'_{k-1} + h'_k left to right;
+ *                    passes += 1; again.
+ *   outputs          time_out [total_rows]; status [F]; passes [F] the dilations applied; peak [F][2] = (P_s, P_a) of the last measurement;
+ *                    duration [F] the last stamp of time_out (+0.0 _EMPTY, NaN _NONFINITE); factor [total_rows], nullable: time_out's
+ *                    interval over the input's at the interval's right row, 1.0 at row 0 and for intervals without positive input width.
+ *                    f_k >= 1: stamps stay ordered, an interval without width keeps none, and no interval or duration shrinks by more than
+ *                    the rounding of the stamps' sum (a factor can read one spacing of its stamp below 1); a path that is done is never
+ *                    touched again, whatever its batch neighbours do; the result is a function of the inputs alone.
+ *   what it is NOT   not TOPP-RA: no optimality, only the audit's figures; no jerk limit; a bound only at the ticks of the stated period (another
+ *                    period is another grid); convergence is observed on the recorded inputs (profiles/fit.md), not proven — with aim = 1 the
+ *                    peaks are observed to creep towards 1 from above without reaching it, hence aim < 1 and hence CCMP_FIT_PASSES is a status.
+ *   ccmp_path_fit_timestamps   device pointers; vmax, amax HOST arrays.  SYNCHRONOUS on its stream: per pass one status launch, one read of F
+ *                    status words and F tick counts (they size the measure launch and tell when no path is open), then tangent ->
+ *                    measure -> dilate; nothing else is read on the host and no allocation is sized by the ticks.  time_out must not overlap
+ *                    time.  opts == NULL: the defaults.
+ *   ccmp_fit_opts_default   period 0.001, max_ticks 65 536, aim 0.95, max_passes 8.
+ *   _host            host pointers throughout, synchronous on the context's stream.
+ *   _ref             pure host code, one thread, no device, never CCMP_ENODEV.
+ * CCMP_EINVAL: a period that is not finite and > 0, max_ticks < 2, aim outside (0, 1], max_passes < 0, a limit that is not finite and
+ * positive, a NULL vmax, amax, path_first, status, passes, peak or duration with F > 0, NULL rows, time or time_out with total_rows > 0, a
+ * time_out that overlaps time, (host and _ref forms) a path_first that is negative, decreases or ends beyond total_rows.  CCMP_EOVERFLOW: more
+ * than INT32_MAX tick intervals in one pass.
+ * Order of use: ... -> time stamps -> fit -> setpoints and audit -> execute. */
+enum { CCMP_FIT_FITTED = 0, CCMP_FIT_PASSES = 6 }; /* 1 .. 5: CCMP_SETPOINTS_EMPTY .. CCMP_SETPOINTS_FULL */
+typedef struct ccmp_fit_opts {
+  double period;  /* the controller's period, seconds, finite and > 0 */
+  int max_ticks;  /* a path that would get more ticks is CCMP_SETPOINTS_FULL, >= 2 */
+  double aim;     /* the share of a limit an interval in excess is dilated to, 0 < aim <= 1 */
+  int max_passes; /* dilations per path at most, >= 0 */
+} ccmp_fit_opts;
+void ccmp_fit_opts_default(ccmp_fit_opts *opts);
+int ccmp_path_fit_timestamps(ccmp_ctx *ctx, const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows,
+                             const double *vmax, const double *amax, const ccmp_fit_opts *opts, double *time_out, int32_t *status, int32_t *passes,
+                             double *peak, double *duration, double *factor, void *hip_stream);
+int ccmp_path_fit_timestamps_host(ccmp_ctx *ctx, const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows,
+                                  const double *vmax, const double *amax, const ccmp_fit_opts *opts, double *time_out, int32_t *status, int32_t *passes,
+                                  double *peak, double *duration, double *factor);
+int ccmp_path_fit_timestamps_ref(const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows, const double *vmax,
+                                 const double *amax, const ccmp_fit_opts *opts, double *time_out, int32_t *status, int32_t *passes, double *peak,
+                                 double *duration, double *factor);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault

@@ -829,6 +829,53 @@ inline int setpointPath(const Projector &proj, const std::vector<std::array<doub
   return CCMP_OK;
 }
 
+// Time stamps fitted to the limits at the controller's rate (include/ccmp.h: ccmp_path_fit_timestamps_host), the step between
+// timestampPath and setpointPath: times = the fitted stamps, factor = the dilation of each row interval at its right row, status =
+// CCMP_FIT_FITTED, CCMP_FIT_PASSES or the setpoints status that ended the path, passes = the dilations applied, peak = the speed and
+// acceleration ratios of the last measurement (what setpointPath's audit reports for `times`), duration = the last stamp.
+struct FittedTimes {
+  std::vector<double> times, factor;
+  int32_t status = CCMP_SETPOINTS_EMPTY, passes = 0;
+  double peak[2] = {0.0, 0.0};
+  double duration = 0.0;
+};
+
+// The options of a fit: the controller's period and tick bound as setpointPath takes them, the share `aim` of a limit an interval in
+// excess is dilated to (0 < aim <= 1) and the dilations at most.
+struct FitOptions {
+  double period = 0.001;
+  int max_ticks = 65536;
+  double aim = 0.95;
+  int max_passes = 8;
+};
+
+// The fit of ONE path: states and times as ccmp::timestampPath leaves them.  Only the row intervals in which the commanded motion exceeds
+// a limit are dilated; a path already within the limits comes back bit for bit.  It is not TOPP-RA, has no jerk limit, bounds the motion
+// only at the ticks of the stated period, and its convergence is observed, not proven: out->status says whether the audit passes.  A path
+// that is empty, not finite, out of order or over max_ticks comes back with CCMP_OK, that status and its stamps.  Returns the library's
+// code and leaves *out untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int fitPath(const Projector &proj, const std::vector<std::array<double, 14>> &states, const std::vector<double> &times, const double *vmax,
+                   const double *amax, FittedTimes *out, const FitOptions &opts = FitOptions())
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double), "rows are contiguous");
+  if (!out || states.size() != times.size() || states.size() > (size_t)0x7fffffff) return CCMP_EINVAL;
+  const int32_t first[2] = {0, (int32_t)states.size()};
+  const ccmp_fit_opts o = {opts.period, opts.max_ticks, opts.aim, opts.max_passes};
+  FittedTimes r;
+  try {
+    r.times.assign(times.size(), 0.0);
+    r.factor.assign(times.size(), 1.0);
+  } catch (...) {
+    return CCMP_ENOMEM;
+  }
+  const int rc = ccmp_path_fit_timestamps_host(proj.ctx(), states.empty() ? nullptr : states[0].data(), first, times.empty() ? nullptr : times.data(), 1,
+                                               states.size(), vmax, amax, &o, r.times.empty() ? nullptr : r.times.data(), &r.status, &r.passes, r.peak,
+                                               &r.duration, r.factor.empty() ? nullptr : r.factor.data());
+  if (rc != CCMP_OK) return rc;
+  *out = std::move(r);
+  return CCMP_OK;
+}
+
 // ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
 // The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
 // rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
@@ -1214,6 +1261,29 @@ public:
       return false;
     if (times.size() == states.size() && !states.empty())
       call([&] { return setpointPath(proj_, states, times, vmax, amax, &setpoints, period, max_ticks, scene, margin); }, "ccmp_path_setpoints_host");
+    return true;
+  }
+
+  // The same with the fit between the time stamps and the setpoints (ccmp::fitPath above): `times` = the FITTED stamps, `fitted` = the
+  // fit's answer, the setpoints those of the fitted stamps (period and max_ticks are the fit options').  On a library error in the fit the
+  // answer FALLS BACK to the time-stamp rule's stamps and their setpoints (`fitted` as constructed, lastError() set).
+  bool constructExecutableSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states,
+                                   std::vector<double> &times, Setpoints &setpoints, FittedTimes &fitted, const FitOptions &fit, const double *vmax,
+                                   const double *amax, const ccmp_scene *scene = nullptr, double margin = 0.0, double beta = 0.5, int count = 0,
+                                   double spacing = 0.0, int max_steps = 5, double min_change = 0.005, int max_span = 0, double *cost = nullptr,
+                                   std::vector<int32_t> *indices = nullptr, double delta = 0.0, double lambda = 0.0) const noexcept
+  {
+    setpoints = Setpoints();
+    fitted = FittedTimes();
+    if (!constructTimedSolution(starts, goals, states, times, vmax, amax, beta, count, spacing, max_steps, min_change, max_span, cost, indices, delta, lambda))
+      return false;
+    if (times.size() == states.size() && !states.empty()) {
+      if (call([&] { return fitPath(proj_, states, times, vmax, amax, &fitted, fit); }, "ccmp_path_fit_timestamps_host") && fitted.times.size() == times.size()) {
+        times = fitted.times;  // (same size: no allocation)
+        if (cost) *cost = fitted.duration;
+      }
+      call([&] { return setpointPath(proj_, states, times, vmax, amax, &setpoints, fit.period, fit.max_ticks, scene, margin); }, "ccmp_path_setpoints_host");
+    }
     return true;
   }
 
@@ -2122,6 +2192,20 @@ public:
       const ccmp::Projector &proj = chain_->impl();
       std::lock_guard<std::mutex> hold(proj.mutex());
       ccmp::check(ccmp::setpointPath(proj, states, times, vmax, amax, out, period, max_ticks, scene, margin), "ccmp_path_setpoints_host");
+    });
+  }
+
+  // Time stamps fitted to the limits at the controller's rate (ccmp::fitPath), between timePath and setpointPath: only the row intervals in
+  // which the commanded motion exceeds a limit are dilated, until the audit of setpointPath passes at the ticks of opts.period or
+  // opts.max_passes dilations are spent (out->status).  false with *out untouched when the call failed
+  // (KinematicChainConstraint::lastError()).
+  bool fitPath(const std::vector<std::array<double, 14>> &states, const std::vector<double> &times, const double *vmax, const double *amax,
+               ccmp::FittedTimes *out, const ccmp::FitOptions &opts = ccmp::FitOptions()) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      ccmp::check(ccmp::fitPath(proj, states, times, vmax, amax, out, opts), "ccmp_path_fit_timestamps_host");
     });
   }
 

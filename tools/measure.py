@@ -51,6 +51,10 @@
                                                            continued (1 and 64 paths), the kind counts; the recorded paths' durations on the CPU; writes profiles/retime.md
     python tools/measure.py setpoints [reps]                setpoints and the execution audit: ccmp_path_setpoints at 1 ms on the retime measurement's inputs, continued
                                                            (1 and 64 paths); the recorded paths' five peaks and stretch from the library; writes profiles/setpoints.md
+    python tools/measure.py fit [reps]                      time stamps fitted to the limits at the controller's rate: ccmp_path_fit_timestamps at 1 ms on the retime
+                                                           measurement's inputs, continued (1 and 64 paths), beside the loop a caller would write without it
+                                                           (ccmp_path_setpoints, copy qd out, dilate on the host, repeat), the same stamps bit for bit; the recorded
+                                                           paths' passes and durations beside the uniform stretch; writes profiles/fit.md
     python tools/measure.py smooth_restate <file.npz> [n]  the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
@@ -1701,6 +1705,135 @@ def setpoints(argv):
                 + "\n".join(lines) + "\n```\n")
 
 
+def _fit_by_hand(c, rows, first, time_dev, vmax, amax, period=0.001, max_ticks=65536, aim=0.95, max_passes=8):
+    """the loop a caller would write without ccmp_path_fit_timestamps, on the rule of csrc/ccmp_fit.h: ccmp_path_setpoints per trial (it
+    materialises every tick and runs the gap and isSatisfied over them: that is the call there is), qd, tau, tick_first and status copied to
+    the host, S and A per row interval and the dilation in numpy, the stamps uploaded again.  -> (stamps (R,) numpy, passes [F], status [F])"""
+    pf = first.cpu().numpy()
+    F = len(pf) - 1
+    t = time_dev.cpu().numpy().copy()
+    v, a = np.array(vmax), np.array(amax)
+    passes, status, open_ = [0] * F, [-1] * F, set(range(F))
+    while open_:
+        sp = c.setpoint_paths(rows, first, torch.from_numpy(t).cuda(), vmax, amax, period=period, max_ticks=max_ticks)
+        qd, tau, tf, st = (sp[k].cpu().numpy() for k in ("qd", "tau", "tick_first", "status"))
+        for f in sorted(open_):
+            if st[f] != 0:
+                status[f] = int(st[f])
+                open_.discard(f)
+                continue
+            r0, r1, g0, g1 = pf[f], pf[f + 1], tf[f], tf[f + 1]
+            tt, ta, w = t[r0:r1], tau[g0:g1], qd[g0:g1]
+            k = np.searchsorted(tt, ta, side="left")  # the smallest k with t_k >= tau (>= 1 for tau > 0)
+            k[0] = k[1]
+            S, A = np.zeros(r1 - r0), np.zeros(r1 - r0)
+            np.maximum.at(S, k, (np.abs(w) / v).max(axis=1))
+            width = ta[1:] - ta[:-1]
+            with np.errstate(all="ignore"):  # (an interval of no width is masked below)
+                acc = ((np.abs(w[1:] - w[:-1]) / width[:, None]) / a).max(axis=1)
+            for span in range(int((k[1:] - k[:-1]).max()) + 1):  # a tick interval owns every row interval from k_j to k_{j+1}
+                on = (k[1:] - k[:-1] >= span) & (width > 0.0)
+                np.maximum.at(A, k[:-1][on] + span, acc[on])
+            if S[1:].max() <= 1.0 and A[1:].max() <= 1.0:
+                status[f] = 0
+                open_.discard(f)
+            elif passes[f] == max_passes:
+                status[f] = 6
+                open_.discard(f)
+            else:
+                fk = np.maximum(1.0, np.maximum(S[1:] / aim, np.sqrt(A[1:] / aim)))
+                t[r0] = 0.0
+                t[r0 + 1:r1] = np.cumsum((tt[1:] - tt[:-1]) * fk)
+                passes[f] += 1
+    return t, passes, status
+
+
+def fit(argv):
+    """ccmp_path_fit_timestamps (KinematicChainConstraint.fit_timestamps) at 1 ms on the retime measurement's inputs, continued: 1 and 64 paths
+    of 32 waypoints, three smoothing passes, densified, resampled at the problem's delta and stamped under the Panda's limits; beside it the
+    loop a caller would write today (_fit_by_hand).  The two must give the same stamps bit for bit before either is timed; wall clock around
+    each, medians.  Then the reference's two recorded path files, stamped on the CPU (ccmp_path_timestamps_ref): passes, the duration
+    before and after, and the duration a uniform stretch by ccmp_path_setpoints' factor would give, at 1 ms and 4 ms.  Writes
+    profiles/fit.md."""
+    import os
+
+    from closed_chain_motion_planner_amd import FIT_STATUS, PANDA_ACCELERATION_LIMITS, PANDA_VELOCITY_LIMITS, timestamps_ref
+
+    reps = int(argv[0]) if len(argv) > 0 else 9
+    Lw, seed, steps = 32, 0x5C7, 3
+    vmax, amax = PANDA_VELOCITY_LIMITS * 2, PANDA_ACCELERATION_LIMITS * 2
+    ctx = Context(0)
+    lines = []
+
+    def say(text):
+        print(text)
+        lines.append(text)
+
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    pj, pl = _smooth_paths(c, 64, Lw, seed)
+    c.setJacobianMode(1)  # the fit does not depend on the mode; the path that feeds it is made in analytic mode
+    for F in (1, 64):
+        sm = c.smooth_paths(pj[:F].contiguous(), pl[:F].contiguous(), max_steps=steps)
+        dense = c.densify_paths(sm["joints"], sm["out_len"], distinct=True, keep_handle=True)
+        rs = c.resample_paths(dense)
+        dense["handle"].close()
+        ts = c.timestamp_paths(rs["joints"], rs["path_first"], vmax, amax)
+        out = c.fit_timestamps(rs["joints"], rs["path_first"], ts["time"], vmax, amax)
+        by_hand, hand_passes, hand_status = _fit_by_hand(c, rs["joints"], rs["path_first"], ts["time"], vmax, amax)
+        got = out["time"].cpu().numpy()
+        same = np.array_equal(got.view(np.uint64), by_hand.view(np.uint64)) and out["passes"].cpu().tolist() == hand_passes and out["status"].cpu().tolist() == hand_status
+        if not same:
+            raise SystemExit("the fused call and the loop by hand disagree: nothing is timed")
+        t_fit, t_hand = [], []
+        for i in range(reps + 2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c.fit_timestamps(rs["joints"], rs["path_first"], ts["time"], vmax, amax)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            _fit_by_hand(c, rs["joints"], rs["path_first"], ts["time"], vmax, amax)
+            torch.cuda.synchronize()
+            if i >= 2:
+                t_fit.append((t1 - t0) * 1e3)
+                t_hand.append((time.perf_counter() - t1) * 1e3)
+        status, passes = out["status"].cpu().numpy(), out["passes"].cpu().numpy()
+        ran = np.isin(status, (0, 6))
+        d0, d1 = ts["duration"].cpu().numpy()[ran], out["duration"].cpu().numpy()[ran]
+        sp = c.setpoint_paths(rs["joints"], rs["path_first"], ts["time"], vmax, amax)
+        stretch = sp["stretch"].cpu().numpy()[ran]
+        say("F = %d paths, %d rows at spacing %.3g, %d ticks at 1 ms before the fit; status %s; dilations %s; durations %s -> %s s (a uniform stretch: %s s); the stamps of "
+            "both ways agree bit for bit" % (F, rs["rows"], c.problem.delta, sp["ticks"], {FIT_STATUS[k]: int((status == k).sum()) for k in sorted(set(status.tolist()))},
+                                            passes[ran].tolist(), np.round(d0, 3).tolist(), np.round(d1, 3).tolist(), np.round(stretch * d0, 3).tolist()))
+        say("    %-100s %s" % ("ccmp_path_fit_timestamps (per pass: status read, tangent, measure, dilate; no tick array)", _stat(t_fit)))
+        say("    %-100s %s" % ("the loop by hand (per pass: ccmp_path_setpoints, qd / tau / tick_first / status copied out, numpy, stamps uploaded)", _stat(t_hand)))
+    say("")
+    say("the reference's recorded paths, stamped on the CPU (ccmp_path_timestamps_ref) under the Panda's limits, beta 0.5, then ccmp_path_fit_timestamps, aim 0.95, 8 passes:")
+    for obj in ("Wine_Bottle", "dumbbell"):
+        rows = np.loadtxt(os.path.join("tests", "golden", "paths", obj + "_path.txt"))
+        first = np.array([0, len(rows)], dtype=np.int32)
+        t = timestamps_ref(rows, first, vmax, amax)["time"]
+        c2 = KinematicChainConstraint.from_yaml(CFG % obj, ctx=ctx)
+        for period in (0.001, 0.004):
+            before = c2.setpoint_paths(rows, first, t, vmax, amax, period=period)
+            out = c2.fit_timestamps(rows, first, t, vmax, amax, period=period)
+            after = c2.setpoint_paths(rows, first, out["time"], vmax, amax, period=period)
+            say("    %-12s %2d rows at %g ms: %s after %d dilations; %.3f -> %.3f s (uniform stretch %.3f: %.3f s); peaks %.3f x vmax, %.3f x amax -> %.4f, %.4f (the audit of "
+                "the fitted stamps: %.4f, %.4f); largest factor %.2f, %d of %d intervals dilated"
+                % (obj, len(rows), period * 1e3, FIT_STATUS[int(out["status"][0])], int(out["passes"][0]), float(t[-1]), float(out["duration"][0]), float(before["stretch"][0]),
+                   float(before["stretch"][0]) * float(t[-1]), before["peak"][0, 0], before["peak"][0, 1], out["peak"][0, 0], out["peak"][0, 1], after["peak"][0, 0],
+                   after["peak"][0, 1], float(out["factor"].max()), int((out["factor"] > 1.0).sum()), len(rows) - 1))
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "fit.md"), "w") as f:
+        f.write("# Time stamps fitted to the limits at the controller's rate: `tools/measure.py fit`\n\n1 x MI355X, one run, seed 0x5C7; the retime measurement's inputs, "
+                "continued: three smoothing passes, densified (distinct layout), resampled at the problem's delta, stamped under the Panda's data-sheet limits, then "
+                "`ccmp_path_fit_timestamps` at a period of 1 ms, aim 0.95, at most 8 dilations; wall clock around the synchronous call, no GPU time measured.  No speed "
+                "threshold gates this feature.  Beside it the loop a caller had to write before: `ccmp_path_setpoints` per trial (which materialises every tick and runs "
+                "the constraint gap and isSatisfied over them), `qd`, `tau`, `tick_first` and `status` copied to the host, the rule of `csrc/ccmp_fit.h` in numpy, the "
+                "stamps uploaded again; the two give the same stamps bit for bit before either is timed.  A path the resampling refused (`profiles/retime.md`) arrives "
+                "without rows and answers EMPTY.  What the step is not: it is not TOPP-RA, it has no jerk limit, it bounds the motion only at the ticks of the stated "
+                "period, and its convergence is observed on these inputs, not proven; with aim = 1 it is observed not to terminate.\n\n```\n" + "\n".join(lines) + "\n```\n")
+
+
 def smooth_restate(argv):
     """the plain-Python restatement of the smoothing rule (tests/smooth_cases.py on the det oracle) on one host core, on the inputs `smooth`
     wrote, compared bit for bit with the results it wrote: python tools/measure.py smooth_restate <file.npz> [paths]"""
@@ -1799,7 +1932,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, fit, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
