@@ -21,12 +21,14 @@ from .shortcut import SHORTCUT_MAX_LEN, shortcut_pairs_ref, shortcut_select, sho
 
 from .smooth import SMOOTH_STATS, SMOOTH_STOP, smooth_len_after, smooth_mid_ref  # noqa: F401
 
-from .retime import (PANDA_ACCELERATION_LIMITS, PANDA_VELOCITY_LIMITS, RETIME_STATUS, SAMPLE_KINDS, arc_bracket_ref, resample_targets_ref,  # noqa: F401
+from .retime import (PANDA_ACCELERATION_LIMITS, PANDA_JERK_LIMITS, PANDA_VELOCITY_LIMITS, RETIME_STATUS, SAMPLE_KINDS, arc_bracket_ref, resample_targets_ref,  # noqa: F401
                      timestamps_ref)
 
 from .setpoints import SETPOINT_PEAKS, SETPOINT_STATUS, setpoint_tangents_ref, setpoints_ref  # noqa: F401
 
 from .fit import FIT_STATUS, fit_timestamps_ref  # noqa: F401
+
+from .jerk import JERK_PEAKS, JERK_STATUS, jerk_next_window_ref, jerk_setpoints_ref  # noqa: F401
 
 from .ik import ik_options, pose_ik_ref, pose_ik_vetted_ref  # noqa: F401
 

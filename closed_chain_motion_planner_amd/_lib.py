@@ -95,6 +95,11 @@ class CcmpFitOpts(C.Structure):
     _fields_ = [("period", C.c_double), ("max_ticks", C.c_int), ("aim", C.c_double), ("max_passes", C.c_int)]
 
 
+class CcmpJerkOpts(C.Structure):
+    """ccmp_jerk_opts of include/ccmp.h"""
+    _fields_ = [("period", C.c_double), ("max_ticks", C.c_int), ("window", C.c_int), ("max_window", C.c_int), ("aim", C.c_double), ("tile_ticks", C.c_int)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -135,6 +140,8 @@ EXPORTS = [
     "ccmp_setpoint_opts_default", "ccmp_path_setpoints", "ccmp_path_setpoints_host", "ccmp_setpoints_info", "ccmp_setpoints_copy", "ccmp_setpoints_copy_host",
     "ccmp_setpoints_destroy", "ccmp_setpoints_ref", "ccmp_setpoint_tangents_ref",
     "ccmp_fit_opts_default", "ccmp_path_fit_timestamps", "ccmp_path_fit_timestamps_host", "ccmp_path_fit_timestamps_ref",
+    "ccmp_jerk_opts_default", "ccmp_path_jerk_setpoints", "ccmp_path_jerk_setpoints_host", "ccmp_jerk_setpoints_info", "ccmp_jerk_setpoints_copy",
+    "ccmp_jerk_setpoints_copy_host", "ccmp_jerk_setpoints_destroy", "ccmp_jerk_setpoints_ref", "ccmp_jerk_next_window_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -365,6 +372,15 @@ def lib():
         "ccmp_path_fit_timestamps": ([vp, vp, vp, vp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(CcmpFitOpts), vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "ccmp_path_fit_timestamps_host": ([vp, dp, i32p, dp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(CcmpFitOpts), dp, i32p, i32p, dp, dp, dp], C.c_int),
         "ccmp_path_fit_timestamps_ref": ([dp, i32p, dp, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(CcmpFitOpts), dp, i32p, i32p, dp, dp, dp], C.c_int),
+        "ccmp_jerk_opts_default": ([C.POINTER(CcmpJerkOpts)], None),
+        "ccmp_path_jerk_setpoints": ([vp, pp, vp, C.c_double, vp, vp, vp, C.c_size_t, C.c_size_t, dp, dp, dp, C.POINTER(CcmpJerkOpts), C.POINTER(vp), vp], C.c_int),
+        "ccmp_path_jerk_setpoints_host": ([vp, pp, vp, C.c_double, dp, i32p, dp, C.c_size_t, C.c_size_t, dp, dp, dp, C.POINTER(CcmpJerkOpts), C.POINTER(vp)], C.c_int),
+        "ccmp_jerk_setpoints_info": ([vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)], C.c_int),
+        "ccmp_jerk_setpoints_copy": ([vp] + [vp] * 13 + [vp], C.c_int),
+        "ccmp_jerk_setpoints_copy_host": ([vp, dp, dp, dp, i32p, dp, u8p, dp, i32p, i32p, i32p, dp, i32p, i32p], C.c_int),
+        "ccmp_jerk_setpoints_destroy": ([vp], None),
+        "ccmp_jerk_next_window_ref": ([C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "ccmp_jerk_setpoints_ref": ([dp, i32p, dp, C.c_size_t, C.c_size_t, dp, dp, dp, C.POINTER(CcmpJerkOpts), i32p, i32p, i32p, i32p, dp, dp, dp, dp, i32p], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -415,6 +431,7 @@ SHORTCUT_MAX_LEN = 1024  # ccmp.h: CCMP_SHORTCUT_MAX_LEN
 RETIME_OK, RETIME_EMPTY, RETIME_BROKEN, RETIME_NONFINITE, RETIME_POINT, RETIME_FULL = range(6)  # ccmp.h: CCMP_RETIME_*
 SAMPLE_PROJECTED, SAMPLE_FALLBACK, SAMPLE_DEGENERATE, SAMPLE_COPIED = range(4)  # ccmp.h: CCMP_SAMPLE_*
 SETPOINTS_OK, SETPOINTS_EMPTY, SETPOINTS_NONFINITE, SETPOINTS_UNORDERED, SETPOINTS_POINT, SETPOINTS_FULL = range(6)  # ccmp.h: CCMP_SETPOINTS_*
+JERK_OK, JERK_FULL, JERK_WINDOW = 0, 5, 6  # ccmp.h: CCMP_JERK_* (1 .. 4: the setpoints values)
 FIT_FITTED, FIT_PASSES = 0, 6  # ccmp.h: CCMP_FIT_* (1 .. 5: the setpoints values)
 
 

@@ -56,6 +56,9 @@ Translation units with deliberately different flags:
   ccmp_kernels_fit.hip   -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   time stamps fitted to the limits at the controller's rate (ccmp_fit.h, which holds no fused operation): the measure kernel (sixteen lanes
                          per tick interval, no tick array, atomic maxima per row interval), the dilation's serial sum (one wavefront per path), the factors
   ccmp_fit.cpp           -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_fit_timestamps*: checks, the pass loop over the setpoints unit's status and tangent launches and this unit's; ccmp_path_fit_timestamps_ref
+  ccmp_kernels_jerk.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   jerk-bounded setpoints (ccmp_jerk.h, which holds no fused operation): the window search's measure kernel (one block per tile of
+                         ticks, the inputs staged in LDS, no tick array, one atomic maximum per block), its decide kernel, the sample kernel and the per-path peaks
+  ccmp_jerk.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_jerk_setpoints*, ccmp_jerk_setpoints_*: checks, the window search's pass loop, the launches; ccmp_jerk_setpoints_ref
 """
 import os
 import shutil
@@ -152,8 +155,12 @@ _UNITS = [
     ("ccmp_kernels_fit.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_path_fit_timestamps: the checks, the pass loop and the rule on the host (ccmp_path_fit_timestamps_ref)
     ("ccmp_fit.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # jerk-bounded setpoints (ccmp_jerk.h): measure, decide, sample and peak; the setpoints unit's flags; registers and LDS only
+    ("ccmp_kernels_jerk.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # ccmp_path_jerk_setpoints: the checks, the window search's pass loop and the rule on the host (ccmp_jerk_setpoints_ref)
+    ("ccmp_jerk.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_setpoints.h", "ccmp_fit.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_setpoints.h", "ccmp_fit.h", "ccmp_jerk.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -204,6 +211,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"resample_|retime_", 0),  # resample and time stamps: a row's bracket, a lane's joint quotients and the limits (kernel arguments) live in registers, the stamps' 64 intervals in LDS
     (r"setpoints_", 0),  # setpoints and audit: a tick's bracket, a lane's joint and a lane's five peaks live in registers, the block's fold of the peaks in LDS
     (r"fit_", 0),  # fitted time stamps: a tick interval's two brackets, a lane's joint at both ticks and the merged maxima live in registers, the dilation's 64 widths in LDS
+    (r"jerk_", 0),  # jerk-bounded setpoints: a tick's bracket, a lane's joint, its window's sum and its six peaks live in registers, the staged inputs and the folds in LDS
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

@@ -582,6 +582,26 @@ class KinematicChainConstraint:
         self._need_problem()
         return setpoints(self.ctx, self.problem, rows, path_first, time, vmax, amax, period, max_ticks, scene, margin, stream)
 
+    def jerk_setpoint_paths(self, rows, path_first, time, vmax, amax, jmax, period=0.001, max_ticks=65536, window=0, max_window=64, aim=0.95, scene=None,
+                            margin=0.0, stream=None, tile_ticks=0):
+        """Jerk-bounded setpoints (ccmp_path_jerk_setpoints; csrc/ccmp_jerk.h), the unit beside `setpoint_paths` for a controller that limits
+        jerk: rows (R,14), path_first (F+1,) int32, time (R,), vmax / amax / jmax 14 numbers each.  `setpoint_paths` commands a C1 cubic
+        whose acceleration jumps at every row; this call delivers a moving average of `window` consecutive ticks of that interpolant (the
+        arrival on the grid at n = ceil(duration / period) periods, M = n + window ticks, both ends copies of the end rows at rest) and
+        audits it: peak (F,6) and peak_tick (F,6) in the order JERK_PEAKS — speed, acceleration, jerk as ratios of the limits, then |dp|,
+        angle and clearance of the FILTERED positions —, counts (F,2), status (F,) (JERK_STATUS), window (F,), passes (F,).  window=0
+        chooses per path: W = 1, then W <- min(max_window, max(W + 1, ceil(W P / aim))) while the jerk ratio P > 1; `window` stays the
+        status when max_window does not reach it.  The speed and acceleration peaks cannot rise above `setpoint_paths`' and the jerk is
+        at most 2 A / (W period) by construction; the filtered ticks lag by (W - 1) / 2 ticks and cut corners — f, satisfied and clearance
+        say whether that matters.  Not a jerk-optimal profile; a bound at the ticks of this period only.  tile_ticks moves the tile edges
+        of the search's launch (the result does not depend on it).  Returns a dict of device tensors, or of numpy arrays through the
+        host form, plus ticks.  Synchronous."""
+        from .jerk import jerk_setpoints
+
+        self._need_problem()
+        return jerk_setpoints(self.ctx, self.problem, rows, path_first, time, vmax, amax, jmax, period, max_ticks, window, max_window, aim, tile_ticks, scene,
+                              margin, stream)
+
     def shortcut_paths(self, path_joints, path_len, scene=None, margin=None, max_span=0, chunk_states=16, round_budget=128, max_calls=4096,
                        tile_edges=65536, pairs=False, stream=None):
         """The removal of interior vertices from F solution paths (ccmp_path_shortcut; csrc/ccmp_shortcut.h): path_joints (F,max_len,14)

@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
-namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; struct retime_limits; struct setpoint_limits; }
+namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; struct retime_limits; struct setpoint_limits; struct jerk_limits; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
  * (front) and the throughput layout (rest), decided by the sort's own kernel from its histogram and left in words 0, 3 and 4 of
@@ -323,6 +323,25 @@ hipError_t fit_dilate(const int32_t *path_first, const int32_t *sp_status, size_
                       unsigned long long *A, int32_t *status, int32_t *passes, double *peak, double *duration, hipStream_t st);
 /* factor[r] = time_out's interval over time's at its right row; row 0 of a path and intervals without positive input width: 1.0 */
 hipError_t fit_factor(const int32_t *path_first, size_t F, size_t total_rows, const double *time, const double *time_out, double *factor, hipStream_t st);
+/* jerk-bounded setpoints (ccmp_path_jerk_setpoints; csrc/ccmp_jerk.h).  The tile lengths of the two staging kernels, whose static LDS they size */
+constexpr int kJerkTile = 128, kJerkSampleTile = 32;
+/* one block per tile < tiles of tile_ticks output ticks of the open paths (tile_first [F + 1]; word [f] = M, window [f] = W, sp_ticks [f] = n + 1): the
+ * path's jerk peak for W folded into P [f] (bit patterns, cleared before) */
+hipError_t jerk_measure(const double *rows, const int32_t *path_first, const double *time, const double *tangent, const int32_t *tile_first, size_t tiles,
+                        const int32_t *word, const int32_t *window, const int32_t *sp_ticks, size_t F, size_t total_rows, double period, int tile_ticks,
+                        const ccmp::jerk_limits &lim, unsigned long long *P, hipStream_t st);
+/* one lane per path.  begin: the setpoints status ends a path or it opens with its first window; else an open path's P [f] is read and cleared
+ * and the path ends OK / WINDOW / FULL or goes on with the next window.  word [f] = M of an open path, -1 - M of a closed one */
+hipError_t jerk_decide(const int32_t *sp_status, const int32_t *sp_ticks, size_t F, bool begin, int fixed_window, int max_window, double aim, int max_ticks,
+                       unsigned long long *P, int32_t *status, int32_t *window, int32_t *passes, int32_t *word, hipStream_t st);
+/* one block per tile < tiles of tile_ticks ticks of the delivered paths (tile_first [F + 1] over tick_first [F + 1]): q, qd [total_ticks][14], tau
+ * [total_ticks]; clearance [total_ticks] = NaN (a scene's answer replaces it) */
+hipError_t jerk_sample(const double *rows, const int32_t *path_first, const double *time, const double *tangent, const int32_t *tile_first, size_t tiles,
+                       const int32_t *tick_first, const int32_t *status, const int32_t *window, const int32_t *sp_ticks, size_t F, size_t total_ticks,
+                       size_t total_rows, double period, int tile_ticks, double *q, double *qd, double *tau, double *clearance, hipStream_t st);
+/* one block per path: peak, peak_tick [F][6], counts [F][2] */
+hipError_t jerk_peak(const double *qd, const double *f, const uint8_t *satisfied, const double *clearance, const int32_t *tick_first, size_t F, size_t total_ticks,
+                     double period, const ccmp::jerk_limits &lim, double margin, double *peak, int32_t *peak_tick, int32_t *counts, hipStream_t st);
 /* ccmp_object_create: rows [M][9] -> planes [9][plane] */
 hipError_t object_planes(const double *rows, int M, size_t plane, double *planes, hipStream_t st);
 /* one block per pose; hit_mask == nullptr: the form that leaves at the first chunk with a hit (the same `valid`) */

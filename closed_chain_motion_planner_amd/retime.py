@@ -11,14 +11,15 @@ from ._lib import CcmpResampleOpts, check
 from .shortcut import _args
 
 __all__ = ["timestamps_ref", "arc_bracket_ref", "resample_targets_ref", "RETIME_STATUS", "SAMPLE_KINDS", "PANDA_VELOCITY_LIMITS",
-           "PANDA_ACCELERATION_LIMITS"]
+           "PANDA_ACCELERATION_LIMITS", "PANDA_JERK_LIMITS"]
 
 RETIME_STATUS = ("ok", "empty", "broken", "non_finite", "point", "full")  # the values of status
 SAMPLE_KINDS = ("projected", "fallback", "degenerate", "copied")  # the values of kind, the columns of counts
 
-# the robot's data sheet; the reference holds no limits.  Per arm, rad/s and rad/s^2; a call takes 14 numbers: the tuple twice
+# the robot's data sheet; the reference holds no limits.  Per arm, rad/s, rad/s^2 and rad/s^3; a call takes 14 numbers: the tuple twice
 PANDA_VELOCITY_LIMITS = (2.175,) * 4 + (2.61,) * 3
 PANDA_ACCELERATION_LIMITS = (15.0, 7.5, 10.0, 12.5, 15.0, 20.0, 20.0)
+PANDA_JERK_LIMITS = (7500.0, 3750.0, 5000.0, 6250.0, 7500.0, 10000.0, 10000.0)
 
 
 def _limits(vmax, amax):

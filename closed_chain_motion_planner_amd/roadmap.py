@@ -542,14 +542,15 @@ class Roadmap:
         return float(stamps["duration"][0]), idx, sampled, stamps, dense, sm, sc
 
     def executable_solution(self, constraint, starts, goals, vmax, amax, period=0.001, max_ticks=65536, audit_scene=None, audit_margin=0.0, fit=False,
-                            fit_aim=0.95, fit_max_passes=8, **kw):
+                            fit_aim=0.95, fit_max_passes=8, jmax=None, jerk_window=0, jerk_max_window=64, **kw):
         """solution -> shortcut -> smooth -> densify -> resample -> time stamps -> [fit ->] setpoints and audit: `timed_solution` (kw: its
         keyword arguments), then `constraint.setpoint_paths` on its rows and stamps; audit_scene / audit_margin: the proxy scene the ticks'
         clearance is taken against.  Returns (setpoints, duration, indices, sampled, stamps, dense, smooth, shortcut) with setpoints the dict
         of `setpoint_paths`, or None when no pair is connected.  fit=True: the stamps go through `constraint.fit_timestamps` (period,
         max_ticks, fit_aim, fit_max_passes) first, the setpoints are those of the fitted stamps, and the fit's dict is appended to the
-        tuple (duration and stamps stay the time-stamp rule's; the fitted ones are the dict's).  The resampled rows are new states: they
-        go to the host's validity test first."""
+        tuple (duration and stamps stay the time-stamp rule's; the fitted ones are the dict's).  jmax (14 numbers): the setpoints are
+        `constraint.jerk_setpoint_paths`' (jerk_window, jerk_max_window), after the fit when fit=True — the dict then has window, passes
+        and six peaks and no stretch.  The resampled rows are new states: they go to the host's validity test first."""
         sol = self.timed_solution(constraint, starts, goals, vmax, amax, **kw)
         if sol is None:
             return None
@@ -561,8 +562,12 @@ class Roadmap:
             fitted = (constraint.fit_timestamps(sampled["joints"], sampled["path_first"], time, vmax, amax, period=period, max_ticks=max_ticks, aim=fit_aim,
                                                 max_passes=fit_max_passes),)
             time = fitted[0]["time"]
-        sp = constraint.setpoint_paths(sampled["joints"], sampled["path_first"], time, vmax, amax, period=period, max_ticks=max_ticks,
-                                       scene=audit_scene, margin=audit_margin)
+        if jmax is not None:
+            sp = constraint.jerk_setpoint_paths(sampled["joints"], sampled["path_first"], time, vmax, amax, jmax, period=period, max_ticks=max_ticks,
+                                                window=jerk_window, max_window=jerk_max_window, scene=audit_scene, margin=audit_margin)
+        else:
+            sp = constraint.setpoint_paths(sampled["joints"], sampled["path_first"], time, vmax, amax, period=period, max_ticks=max_ticks,
+                                           scene=audit_scene, margin=audit_margin)
         return (sp,) + tuple(sol) + fitted
 
     def close(self):

@@ -1380,6 +1380,89 @@ int ccmp_path_fit_timestamps_ref(const double *rows, const int32_t *path_first, 
                                  const double *amax, const ccmp_fit_opts *opts, double *time_out, int32_t *status, int32_t *passes, double *peak,
                                  double *duration, double *factor);
 
+/* ---- executing a path: jerk-bounded setpoints ----------------------------------------------------------------------------------------- */
+/* ccmp_path_setpoints commands a C1 piecewise cubic: its acceleration jumps at every row, and a robot that limits jerk (a Panda: 7500 ..
+ * 10000 rad/s^3 and a 1 kHz interface that refuses a discontinuous acceleration) refuses it however the stamps were fitted.
+ * ccmp_path_jerk_setpoints delivers the setpoints of a moving average of W consecutive ticks of that interpolant, measures jerk, and
+ * chooses W per path.  The rule is csrc/ccmp_jerk.h, stated once for the kernels and the _ref form (no fused operation), bit for bit
+ * against each other; status, tangents, q, qd and the bracket are the setpoints rule's, unchanged.
+ *     status         [F]: CCMP_JERK_EMPTY, _NONFINITE, _UNORDERED, _POINT as the setpoints rule tests them (a _POINT path: one tick, q = r_0,
+ *                    qd = +0.0, tau = +0.0, window 0); _FULL the ticks of the window do not fit max_ticks (no tick); _WINDOW the jerk peak of
+ *                    the delivered window is still above 1; else _OK.
+ *     input          n = (int64)ceil(D / period), D the last stamp.  x_i = (r_0, 0) for i <= 0, (r_{R-1}, 0) for i >= n, else (q, qd) of the
+ *                    setpoints rule's interior tick at min(fl(i period), D): the arrival sits on the grid at n period, not at D.
+ *     output for W   M = n + W ticks, tau_j = fl(j period); ticks 0 and M - 1 are copies of r_0 and r_{R-1} with qd = +0.0; else q_j[c] =
+ *                    (x_{j-W+1}[c] + ... + x_j[c]) / W summed from the oldest term to the newest, then one division, and qd_j[c] the same
+ *                    over the qd parts.
+ *     per tick       f, satisfied, clearance: ccmp_function_batch's, ccmp_is_satisfied_batch's and (with a scene) ccmp_clearance_batch's
+ *                    of the FILTERED q, those launchers unchanged, once each over all ticks.
+ *     audit          peak [F][6] and peak_tick [F][6] in the order speed, acceleration, jerk, |dp|, angle, clearance, under the setpoints
+ *                    audit's order (ties to the smallest tick, a NaN never contributes, none: +0.0 — clearance +inf — at tick -1).  Jerk:
+ *                    a_j[c] = (qd_{j+1}[c] - qd_j[c]) / (tau_{j+1} - tau_j), signed; jerk_j[c] = (|a_{j+1}[c] - a_j[c]| / (0.5 (tau_{j+2} - tau_j))) /
+ *                    jmax_c for 0 <= j <= M - 3, at the middle tick j + 1.  counts [F][2] as in the setpoints unit.
+ *     the window     opts.window > 0: that W for every path, one measurement, passes = 0, _OK or _WINDOW by jerk peak <= 1.  0: per path
+ *                    W = 1; measure the jerk peak P; P <= 1: _OK; else W == max_window: _WINDOW (ticks and audit of max_window are
+ *                    delivered); else W <- min(max_window, max(W + 1, (int)ceil(W P / aim))), passes += 1, again.  A W whose ticks do
+ *                    not fit ends the path _FULL; window and passes then name that W.
+ *   by construction  a mean cannot exceed the largest of its terms: the speed and acceleration peaks do not rise above those of W = 1 and
+ *                    q stays in the hull of its window's inputs (both up to the rounding of W - 1 additions and a division); the jerk of
+ *                    joint c is at most 2 A_c / (W period), A_c its acceleration peak at W = 1 in rad/s^2, so every W >= W* = ceil(max_c 2 A_c /
+ *                    (period jmax_c)) passes and the search ends _OK whenever W* <= max_window, within max_window passes.  The motion
+ *                    grows by W - 1 ticks.
+ *   what it is NOT   a bound at the ticks of the stated period on the qd sequence, as the setpoints audit is, not a third difference of
+ *                    positions (two rows with D <= period: n = 1, every qd zero, whatever the rows).  The filtered ticks no longer pass
+ *                    through the rows: they lag by (W - 1) / 2 ticks and cut corners by the order of a (W period)^2 / 24; f, satisfied and
+ *                    clearance of this call tell whether that matters.  Not a jerk-optimal profile.
+ *   ccmp_path_jerk_setpoints   device pointers; vmax, amax, jmax HOST arrays.  SYNCHRONOUS on its stream (per pass of the search it reads F
+ *                    words that size the next launch and tell when no path is open): not capturable.  scene nullable.  opts == NULL: the
+ *                    defaults.  On any error no handle and no partial output.
+ *   ccmp_jerk_opts_default   period 0.001, max_ticks 65 536, window 0, max_window 64, aim 0.95, tile_ticks 0.
+ *   _host            host pointers (rows, path_first, time), synchronous on the context's stream.
+ *   ccmp_jerk_setpoints_info / _copy / _copy_host / _destroy   the result: F and the tick count; copies into device (asynchronous on
+ *                    hip_stream) or host (synchronous) destinations, each nullable: q, qd [ticks][14], tau [ticks], tick_first [F + 1],
+ *                    f [ticks][2], satisfied [ticks] (uint8), clearance [ticks], status [F], window [F], passes [F], peak [F][6],
+ *                    peak_tick [F][6] (int32), counts [F][2].
+ *   ccmp_jerk_setpoints_ref   the rule and the speed, acceleration and jerk audit as pure host code, one thread, no device, never
+ *                    CCMP_ENODEV: tick_first [F + 1], status [F], window [F], passes [F] always; q, qd, tau, peak [F][3], peak_tick [F][3]
+ *                    where given (two-call sizing: NULL arrays first).
+ *   ccmp_jerk_next_window_ref   the search's update alone: *next = min(max_window, max(W + 1, (int)ceil(W P / aim))) for 1 <= W < max_window
+ *                    <= 256, any P that is no NaN, 0 < aim <= 1 (else CCMP_EINVAL).  Inside the search P > 1 and aim <= 1 make the
+ *                    ceiling at least W + 1 by themselves; the W + 1 term is what makes the growth unconditional.
+ * CCMP_EINVAL: what ccmp_path_setpoints refuses; a jmax that is NULL or not finite and positive; window outside 0 .. max_window; max_window
+ * outside 1 .. 256; aim outside (0, 1]; a negative tile_ticks; a NULL window or passes (_ref form).  CCMP_EOVERFLOW: more than INT32_MAX ticks
+ * in all.  Order of use: ... -> time stamps -> fit -> jerk-bounded setpoints and audit -> execute. */
+enum { CCMP_JERK_OK = 0, CCMP_JERK_EMPTY = 1, CCMP_JERK_NONFINITE = 2, CCMP_JERK_UNORDERED = 3, CCMP_JERK_POINT = 4, CCMP_JERK_FULL = 5,
+       CCMP_JERK_WINDOW = 6 }; /* 0 .. 5: the values of CCMP_SETPOINTS_* */
+typedef struct ccmp_jerk_opts {
+  double period;  /* the controller's period, seconds, finite and > 0 */
+  int max_ticks;  /* a path whose window would give more ticks is CCMP_JERK_FULL, >= 2 */
+  int window;     /* 0: chosen per path; else 1 .. max_window, the same for every path */
+  int max_window; /* the largest window the search tries, 1 .. 256 */
+  double aim;     /* the share of jmax the next window of the search aims at, 0 < aim <= 1 */
+  int tile_ticks; /* output ticks per block of the search's measure launch; 0 or beyond the default (128): the default.  The result
+                     does not depend on it */
+} ccmp_jerk_opts;
+void ccmp_jerk_opts_default(ccmp_jerk_opts *opts);
+typedef struct ccmp_jerk_setpoints ccmp_jerk_setpoints;
+int ccmp_path_jerk_setpoints(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *rows, const int32_t *path_first,
+                             const double *time, size_t F, size_t total_rows, const double *vmax, const double *amax, const double *jmax,
+                             const ccmp_jerk_opts *opts, ccmp_jerk_setpoints **out, void *hip_stream);
+int ccmp_path_jerk_setpoints_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin, const double *rows,
+                                  const int32_t *path_first, const double *time, size_t F, size_t total_rows, const double *vmax, const double *amax,
+                                  const double *jmax, const ccmp_jerk_opts *opts, ccmp_jerk_setpoints **out);
+int ccmp_jerk_setpoints_info(const ccmp_jerk_setpoints *h, size_t *F, size_t *ticks);
+int ccmp_jerk_setpoints_copy(ccmp_jerk_setpoints *h, double *q, double *qd, double *tau, int32_t *tick_first, double *f, uint8_t *satisfied,
+                             double *clearance, int32_t *status, int32_t *window, int32_t *passes, double *peak, int32_t *peak_tick, int32_t *counts,
+                             void *hip_stream);
+int ccmp_jerk_setpoints_copy_host(ccmp_jerk_setpoints *h, double *q, double *qd, double *tau, int32_t *tick_first, double *f, uint8_t *satisfied,
+                                  double *clearance, int32_t *status, int32_t *window, int32_t *passes, double *peak, int32_t *peak_tick,
+                                  int32_t *counts);
+void ccmp_jerk_setpoints_destroy(ccmp_jerk_setpoints *h);
+int ccmp_jerk_setpoints_ref(const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows, const double *vmax,
+                            const double *amax, const double *jmax, const ccmp_jerk_opts *opts, int32_t *tick_first, int32_t *status, int32_t *window,
+                            int32_t *passes, double *q, double *qd, double *tau, double *peak, int32_t *peak_tick);
+int ccmp_jerk_next_window_ref(int W, double P, double aim, int max_window, int *next);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault
  * injection — are not part of this library: include/ccmp_debug.h, lib/libccmp_debug.so) */

@@ -876,6 +876,76 @@ inline int fitPath(const Projector &proj, const std::vector<std::array<double, 1
   return CCMP_OK;
 }
 
+// Jerk-bounded setpoints (include/ccmp.h: ccmp_path_jerk_setpoints_host), the unit beside setpointPath for a controller that limits jerk:
+// Setpoints' per-tick arrays for the moving average of `window` consecutive ticks of the interpolant, plus the window the search chose, its
+// passes and SIX peaks in the order speed ratio, acceleration ratio, jerk ratio, |dp|, angle, clearance — the last three of the FILTERED
+// positions.  status = CCMP_JERK_*.  There is no stretch.
+struct JerkSetpoints {
+  std::vector<std::array<double, 14>> q, qd;
+  std::vector<double> tau, clearance;
+  std::vector<std::array<double, 2>> f;
+  std::vector<uint8_t> satisfied;
+  int32_t status = CCMP_JERK_EMPTY, window = 0, passes = 0;
+  double peak[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int32_t peak_tick[6] = {-1, -1, -1, -1, -1, -1};
+  int32_t n_off = 0, n_below = 0;
+};
+
+// The options of the call: the controller's period and tick bound as setpointPath takes them, window (0: chosen per path, else 1 ..
+// max_window), max_window (1 .. 256) and the share `aim` of the jerk limit the next window of the search aims at (0 < aim <= 1).
+struct JerkOptions {
+  double period = 0.001;
+  int max_ticks = 65536;
+  int window = 0;
+  int max_window = 64;
+  double aim = 0.95;
+};
+
+// The jerk-bounded setpoints of ONE path: states and times as ccmp::timestampPath or ccmp::fitPath leave them, vmax / amax / jmax = 14
+// numbers each.  By construction the speed and acceleration peaks do not rise above setpointPath's and the jerk is at most 2 A / (W period);
+// it is a bound at the ticks of the stated period on the qd sequence, not a third difference of positions; the filtered ticks lag by
+// (W - 1) / 2 ticks and cut corners — out->f, satisfied and clearance say whether that matters; it is not a jerk-optimal profile.  A path
+// that is empty, not finite, out of order or over max_ticks comes back with CCMP_OK, its status and no tick; CCMP_JERK_WINDOW still delivers
+// the ticks of max_window.  Returns the library's code and leaves *out untouched unless it is CCMP_OK.  The CALLER holds proj.mutex().
+inline int jerkSetpointPath(const Projector &proj, const std::vector<std::array<double, 14>> &states, const std::vector<double> &times, const double *vmax,
+                            const double *amax, const double *jmax, JerkSetpoints *out, const JerkOptions &opts = JerkOptions(),
+                            const ccmp_scene *scene = nullptr, double margin = 0.0)
+{
+  static_assert(sizeof(std::array<double, 14>) == 14 * sizeof(double) && sizeof(std::array<double, 2>) == 2 * sizeof(double), "rows are contiguous");
+  if (!out || states.size() != times.size() || states.size() > (size_t)0x7fffffff) return CCMP_EINVAL;
+  const ccmp_problem P = detail::problemWith(proj, 0.0, 0.0);
+  const int32_t first[2] = {0, (int32_t)states.size()};
+  const ccmp_jerk_opts o = {opts.period, opts.max_ticks, opts.window, opts.max_window, opts.aim, 0};
+  ccmp_jerk_setpoints *h = nullptr;
+  int rc = ccmp_path_jerk_setpoints_host(proj.ctx(), &P, scene, margin, states.empty() ? nullptr : states[0].data(), first, times.empty() ? nullptr : times.data(),
+                                         1, states.size(), vmax, amax, jmax, &o, &h);
+  if (rc != CCMP_OK) return rc;
+  JerkSetpoints s;
+  size_t ticks = 0;
+  try {
+    rc = ccmp_jerk_setpoints_info(h, nullptr, &ticks);
+    s.q.resize(ticks);
+    s.qd.resize(ticks);
+    s.tau.resize(ticks);
+    s.clearance.resize(ticks);
+    s.f.resize(ticks);
+    s.satisfied.resize(ticks);
+  } catch (...) {
+    rc = CCMP_ENOMEM;
+  }
+  int32_t counts[2] = {0, 0};
+  if (rc == CCMP_OK)
+    rc = ccmp_jerk_setpoints_copy_host(h, ticks ? s.q[0].data() : nullptr, ticks ? s.qd[0].data() : nullptr, ticks ? s.tau.data() : nullptr, nullptr,
+                                       ticks ? s.f[0].data() : nullptr, ticks ? s.satisfied.data() : nullptr, ticks ? s.clearance.data() : nullptr, &s.status,
+                                       &s.window, &s.passes, s.peak, s.peak_tick, counts);
+  ccmp_jerk_setpoints_destroy(h);
+  if (rc != CCMP_OK) return rc;
+  s.n_off = counts[0];
+  s.n_below = counts[1];
+  *out = std::move(s);
+  return CCMP_OK;
+}
+
 // ---- the device-resident roadmap (include/ccmp.h: ccmp_roadmap_*) ------------------------------------------------------------------
 // The object pose of a vertex as the store keeps it (x y z qx qy qz qw pad) from any state type that offers getX / getY / getZ and
 // rotation().x / y / z / w — ompl::base::SE3StateSpace::StateType, i.e. components[1] of the reference's compound states.
@@ -1283,6 +1353,36 @@ public:
         if (cost) *cost = fitted.duration;
       }
       call([&] { return setpointPath(proj_, states, times, vmax, amax, &setpoints, fit.period, fit.max_ticks, scene, margin); }, "ccmp_path_setpoints_host");
+    }
+    return true;
+  }
+
+  // constructTimedSolution followed by the JERK-BOUNDED setpoints of its rows (ccmp::jerkSetpointPath above) for a controller that limits
+  // jerk: jmax = 14 numbers, the period, tick bound and window search are the JerkOptions'.  `fit` non-null: the stamps go through the
+  // fit first (its period and max_ticks should be the JerkOptions'), `times` = the fitted stamps and *fitted (nullable) = the fit's answer;
+  // on a library error in the fit the answer falls back to the time-stamp rule's stamps.  On a library error in the setpoints step the
+  // answer FALLS BACK to the timed solution with `setpoints` empty (true, status CCMP_JERK_EMPTY, lastError() set).
+  bool constructExecutableSolution(const std::vector<int32_t> &starts, const std::vector<int32_t> &goals, std::vector<std::array<double, 14>> &states,
+                                   std::vector<double> &times, JerkSetpoints &setpoints, const double *vmax, const double *amax, const double *jmax,
+                                   const JerkOptions &jerk = JerkOptions(), const FitOptions *fit = nullptr, FittedTimes *fitted = nullptr,
+                                   const ccmp_scene *scene = nullptr, double margin = 0.0, double beta = 0.5, int count = 0, double spacing = 0.0,
+                                   int max_steps = 5, double min_change = 0.005, int max_span = 0, double *cost = nullptr,
+                                   std::vector<int32_t> *indices = nullptr, double delta = 0.0, double lambda = 0.0) const noexcept
+  {
+    setpoints = JerkSetpoints();
+    if (fitted) *fitted = FittedTimes();
+    if (!constructTimedSolution(starts, goals, states, times, vmax, amax, beta, count, spacing, max_steps, min_change, max_span, cost, indices, delta, lambda))
+      return false;
+    if (times.size() == states.size() && !states.empty()) {
+      if (fit) {
+        FittedTimes answer;
+        if (call([&] { return fitPath(proj_, states, times, vmax, amax, &answer, *fit); }, "ccmp_path_fit_timestamps_host") && answer.times.size() == times.size()) {
+          times = answer.times;  // (same size: no allocation)
+          if (cost) *cost = answer.duration;
+          if (fitted) *fitted = std::move(answer);
+        }
+      }
+      call([&] { return jerkSetpointPath(proj_, states, times, vmax, amax, jmax, &setpoints, jerk, scene, margin); }, "ccmp_path_jerk_setpoints_host");
     }
     return true;
   }
@@ -1731,6 +1831,10 @@ inline void printSetpoints(std::ostream &out, const double *tau, const double *q
   out.flush();
 }
 inline void printSetpoints(std::ostream &out, const Setpoints &s)
+{
+  printSetpoints(out, s.tau.data(), s.q.empty() ? nullptr : s.q[0].data(), s.qd.empty() ? nullptr : s.qd[0].data(), s.tau.size());
+}
+inline void printSetpoints(std::ostream &out, const JerkSetpoints &s)
 {
   printSetpoints(out, s.tau.data(), s.q.empty() ? nullptr : s.q[0].data(), s.qd.empty() ? nullptr : s.qd[0].data(), s.tau.size());
 }
@@ -2206,6 +2310,20 @@ public:
       const ccmp::Projector &proj = chain_->impl();
       std::lock_guard<std::mutex> hold(proj.mutex());
       ccmp::check(ccmp::fitPath(proj, states, times, vmax, amax, out, opts), "ccmp_path_fit_timestamps_host");
+    });
+  }
+
+  // Jerk-bounded setpoints (ccmp::jerkSetpointPath), beside setpointPath for a controller that limits jerk: a moving average of the
+  // interpolant's ticks whose window is chosen until the jerk ratio at the ticks of opts.period is within 1 (out->status, out->window).
+  // false with *out untouched when the call failed (KinematicChainConstraint::lastError()).
+  bool jerkSetpointPath(const std::vector<std::array<double, 14>> &states, const std::vector<double> &times, const double *vmax, const double *amax,
+                        const double *jmax, ccmp::JerkSetpoints *out, const ccmp::JerkOptions &opts = ccmp::JerkOptions(), const ccmp_scene *scene = nullptr,
+                        double margin = 0.0) const noexcept
+  {
+    return chain_->guarded([&] {
+      const ccmp::Projector &proj = chain_->impl();
+      std::lock_guard<std::mutex> hold(proj.mutex());
+      ccmp::check(ccmp::jerkSetpointPath(proj, states, times, vmax, amax, jmax, out, opts, scene, margin), "ccmp_path_jerk_setpoints_host");
     });
   }
 

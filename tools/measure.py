@@ -55,6 +55,10 @@
                                                            measurement's inputs, continued (1 and 64 paths), beside the loop a caller would write without it
                                                            (ccmp_path_setpoints, copy qd out, dilate on the host, repeat), the same stamps bit for bit; the recorded
                                                            paths' passes and durations beside the uniform stretch; writes profiles/fit.md
+    python tools/measure.py jerk [reps]                     jerk-bounded setpoints: first, on one host core, the plain-Python restatement on the recorded paths (the unfiltered
+                                                           jerk ratio, the chosen windows at 1 and 4 ms); then ccmp_path_jerk_setpoints at 1 ms on the setpoints measurement's
+                                                           inputs (1 and 64 paths) beside the loop a caller would write without it (ccmp_path_setpoints, copy qd out, numpy
+                                                           windows); the recorded paths' windows and six peaks, without and behind the fit; writes profiles/jerk.md
     python tools/measure.py smooth_restate <file.npz> [n]  the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
@@ -1834,6 +1838,140 @@ def fit(argv):
                 "period, and its convergence is observed on these inputs, not proven; with aim = 1 it is observed not to terminate.\n\n```\n" + "\n".join(lines) + "\n```\n")
 
 
+def _jerk_by_hand(c, rows, first, time_dev, vmax, amax, jmax, period=0.001, max_window=64, aim=0.95):
+    """the loop a caller would write without ccmp_path_jerk_setpoints: ccmp_path_setpoints once, qd, tau and tick_first copied to the host, a
+    numpy moving window over every OK path's ticks (held at both ends) and the jerk ratio, the window grown by the update of
+    csrc/ccmp_jerk.h until it passes.  The velocities only: the positions, the gap and the clearance of the filtered ticks would be one more
+    upload and three more calls.  numpy's sums are not the rule's rounding sequence and the last tick of ccmp_path_setpoints sits at D, not
+    on the grid: the windows agree with the library's, the last digits need not.  -> windows of the OK paths"""
+    sp = c.setpoint_paths(rows, first, time_dev, vmax, amax, period=period)
+    qd, tf, status = sp["qd"].cpu().numpy(), sp["tick_first"].cpu().numpy(), sp["status"].cpu().numpy()
+    j = np.asarray(jmax)
+    windows = []
+    for f in np.flatnonzero(status == 0):
+        v = qd[tf[f]:tf[f + 1]]
+        W = 1
+        while True:
+            pad = np.vstack([np.zeros((W - 1, 14)), v, np.zeros((W - 1, 14))]) if W > 1 else v
+            filt = np.lib.stride_tricks.sliding_window_view(pad, W, axis=0).mean(axis=2) if W > 1 else v
+            P = float((np.abs(np.diff(filt, 2, axis=0)) / (period * period) / j).max()) if len(filt) > 2 else 0.0
+            if P <= 1.0 or W >= max_window:
+                break
+            W = min(max_window, max(W + 1, int(np.ceil(W * P / aim))))
+        windows.append(W)
+    return windows
+
+
+def jerk(argv):
+    """ccmp_path_jerk_setpoints (KinematicChainConstraint.jerk_setpoint_paths) at 1 ms.  First, on one host core and without a device, the
+    figures the unit was asked for with: the plain-Python restatement (tests/jerk_cases.py on tests/setpoint_cases.py and the stamp rule
+    of tests/retime_cases.py) on the two recorded paths with repeated rows dropped — the unfiltered jerk ratio, the chosen window and the
+    ratio behind it at 1 ms and 4 ms, and dumbbell under doubled stamps.  Then on the device: the setpoints measurement's inputs (1 and 64
+    paths) through the call, beside the loop a caller would write today (_jerk_by_hand), wall clock around each, medians; and the two
+    recorded paths through the call, stamped by ccmp_path_timestamps_ref, without and behind the fit.  Writes profiles/jerk.md."""
+    import os
+
+    from closed_chain_motion_planner_amd import JERK_STATUS, PANDA_ACCELERATION_LIMITS, PANDA_JERK_LIMITS, PANDA_VELOCITY_LIMITS, timestamps_ref
+
+    sys.path.insert(0, "tests")
+    import jerk_cases as jc
+    import setpoint_cases as sc
+    from retime_cases import stamp_path_py
+
+    reps = int(argv[0]) if len(argv) > 0 else 9
+    Lw, seed, steps = 32, 0x5C7, 3
+    vmax, amax, jmax = PANDA_VELOCITY_LIMITS * 2, PANDA_ACCELERATION_LIMITS * 2, PANDA_JERK_LIMITS * 2
+    cpu, lines = [], []
+
+    def say(text, to=None):
+        print(text)
+        (lines if to is None else to).append(text)
+
+    for obj, scale in (("Wine_Bottle", 1.0), ("dumbbell", 1.0), ("dumbbell", 2.0)):
+        g = np.loadtxt(os.path.join("tests", "golden", "paths", obj + "_path.txt"))
+        g = g[np.concatenate([[True], (np.diff(g, axis=0) != 0.0).any(axis=1)])]  # repeated rows dropped
+        t = [v * scale for v in stamp_path_py(g, vmax, amax, 0.5)[0]]
+        for period in ((0.001, 0.004) if scale == 1.0 else (0.001,)):
+            n, xq, xd = jc.inputs_py(g, t, period)
+            st, W, passes, trace = jc.search_py(xd, n, jmax, period, 65536, 0, 64, 0.95)
+            q, qd, tau = jc.window_py(xq, xd, n, W, period)
+            q1, qd1, tau1 = jc.window_py(xq, xd, n, 1, period)
+            nan, one = np.full((len(tau), 2), np.nan), np.ones(len(tau), dtype=np.uint8)
+            pk = jc.audit_py(qd, tau, nan, one, nan[:, 0], vmax, amax, jmax, period, 0.0)[0]
+            pk1 = jc.audit_py(qd1, tau1, nan[:len(tau1)], one[:len(tau1)], nan[:len(tau1), 0], vmax, amax, jmax, period, 0.0)[0]
+            say("    %-12s %2d rows%s at %g ms: %s, W = %d after %d passes, %d -> %d ticks; jerk ratio %.2f -> %.2f; speed %.4f -> %.4f x vmax, acceleration %.4f -> %.4f x amax"
+                % (obj, len(g), "" if scale == 1.0 else ", stamps x %g" % scale, period * 1e3, JERK_STATUS[st], W, passes, n + 1, n + W, trace[0][1], trace[-1][1], pk1[0],
+                   pk[0], pk1[1], pk[1]), cpu)
+
+    ctx = Context(0)
+    c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+    pj, pl = _smooth_paths(c, 64, Lw, seed)
+    c.setJacobianMode(1)  # the setpoints do not depend on the mode; the path that feeds them is made in analytic mode
+    for F in (1, 64):
+        sm = c.smooth_paths(pj[:F].contiguous(), pl[:F].contiguous(), max_steps=steps)
+        dense = c.densify_paths(sm["joints"], sm["out_len"], distinct=True, keep_handle=True)
+        rs = c.resample_paths(dense)
+        dense["handle"].close()
+        ts = c.timestamp_paths(rs["joints"], rs["path_first"], vmax, amax)
+        out = c.jerk_setpoint_paths(rs["joints"], rs["path_first"], ts["time"], vmax, amax, jmax)
+        status, window, passes = (out[k].cpu().numpy() for k in ("status", "window", "passes"))
+        ran = np.isin(status, (0, 6))
+        by_hand = _jerk_by_hand(c, rs["joints"], rs["path_first"], ts["time"], vmax, amax, jmax)
+        t_call, t_hand = [], []
+        for i in range(reps + 2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c.jerk_setpoint_paths(rs["joints"], rs["path_first"], ts["time"], vmax, amax, jmax)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            _jerk_by_hand(c, rs["joints"], rs["path_first"], ts["time"], vmax, amax, jmax)
+            torch.cuda.synchronize()
+            if i >= 2:
+                t_call.append((t1 - t0) * 1e3)
+                t_hand.append((time.perf_counter() - t1) * 1e3)
+        peak = out["peak"].cpu().numpy()[ran]
+        say("F = %d paths, %d rows at spacing %.3g -> %d ticks at 1 ms; status %s; windows %s after %s passes (the loop by hand: %s); speed / acceleration / jerk ratios "
+            "of the delivered ticks, medians: %s; %d of the ticks refused by isSatisfied"
+            % (F, rs["rows"], c.problem.delta, out["ticks"], {JERK_STATUS[k]: int((status == k).sum()) for k in sorted(set(status.tolist()))}, window[ran].tolist(),
+               passes[ran].tolist(), by_hand, np.round(np.median(peak[:, :3], axis=0), 3).tolist() if len(peak) else [], int(out["counts"][:, 0].sum())))
+        say("    %-110s %s" % ("ccmp_path_jerk_setpoints (status, tangents, per pass measure + decide + one read; sample, function + isSatisfied, peak; copy-out)", _stat(t_call)))
+        say("    %-110s %s" % ("the loop by hand (ccmp_path_setpoints, qd / tick_first / status copied out, numpy windows of the velocities alone)", _stat(t_hand)))
+    say("")
+    say("the reference's recorded paths, stamped on the CPU (ccmp_path_timestamps_ref) under the Panda's limits, beta 0.5, then ccmp_path_jerk_setpoints at 1 ms, "
+        "without and behind ccmp_path_fit_timestamps:")
+    for obj in ("Wine_Bottle", "dumbbell"):
+        rows = np.loadtxt(os.path.join("tests", "golden", "paths", obj + "_path.txt"))
+        first = np.array([0, len(rows)], dtype=np.int32)
+        t = timestamps_ref(rows, first, vmax, amax)["time"]
+        c2 = KinematicChainConstraint.from_yaml(CFG % obj, ctx=ctx)
+        fitted = c2.fit_timestamps(rows, first, t, vmax, amax)["time"]
+        for what, stamps in (("as stamped", t), ("fitted", fitted)):
+            plain = c2.jerk_setpoint_paths(rows, first, stamps, vmax, amax, jmax, window=1)
+            out = c2.jerk_setpoint_paths(rows, first, stamps, vmax, amax, jmax)
+            p0, p = plain["peak"][0], out["peak"][0]
+            say("    %-12s %2d rows, %s, %.3f s: %s, W = %d after %d passes, %d -> %d ticks; speed %.4f -> %.4f x vmax, acceleration %.4f -> %.4f x amax, jerk %.3f -> %.3f x "
+                "jmax at tick %d; max |dp| %.3e -> %.3e m, max angle %.3e -> %.3e rad; %d -> %d ticks refused by isSatisfied"
+                % (obj, len(rows), what, float(stamps[-1]), JERK_STATUS[int(out["status"][0])], int(out["window"][0]), int(out["passes"][0]), plain["ticks"], out["ticks"], p0[0],
+                   p[0], p0[1], p[1], p0[2], p[2], int(out["peak_tick"][0, 2]), p0[3], p[3], p0[4], p[4], int(plain["counts"][0, 0]), int(out["counts"][0, 0])))
+    os.makedirs("profiles", exist_ok=True)
+    with open(os.path.join("profiles", "jerk.md"), "w") as f:
+        f.write("# Jerk-bounded setpoints on the device: `tools/measure.py jerk`\n\n1 x MI355X, one run, seed 0x5C7; the setpoints measurement's inputs: three smoothing "
+                "passes, densified (distinct layout), resampled at the problem's delta, stamped under the Panda's data-sheet limits, then `ccmp_path_jerk_setpoints` at a "
+                "period of 1 ms, max_window 64, aim 0.95, under the data-sheet jerk limits.  Wall clock only, around the synchronous call (the mirror's copy-out "
+                "included): no GPU time was measured and no speed threshold gates this feature.  Beside it the loop a caller has to write today: `ccmp_path_setpoints`, "
+                "`qd`, `tick_first` and `status` copied to the host, numpy windows over the velocities and the same update of the window — the velocities alone; the "
+                "filtered positions, their gap and their clearance would be one more upload and three more calls.  numpy's sums are another rounding sequence and "
+                "`ccmp_path_setpoints` ends at D, not on the grid, so only the windows are compared.  A path the resampling refused (`profiles/retime.md`) arrives "
+                "without rows and answers EMPTY.  What the unit is not: a bound at the ticks of the stated period on the qd sequence, not a third difference of "
+                "positions; the filtered ticks lag by (W - 1) / 2 ticks and cut corners (the gap and isSatisfied columns below say by how much); it is not a "
+                "jerk-optimal profile.  The paths as stamped exceed amax between their rows (`profiles/fit.md`); the window leaves that as it is, which is why the "
+                "order of use is time stamps -> fit -> jerk-bounded setpoints.\n\n```\n" + "\n".join(lines) + "\n```\n\n"
+                "## The gap the unit closes, on one host core\n\nNot a GPU measurement: the plain-Python restatement of the rule (`tests/jerk_cases.py` on "
+                "`tests/setpoint_cases.py: path_py` and `tests/retime_cases.py: stamp_path_py`) on the two recorded paths with repeated rows dropped, stamped under the "
+                "Panda's limits with beta 0.5.  The jerk ratio is taken from the `qd` sequence as the audit takes acceleration.  A path whose stamps pass speed and "
+                "acceleration can still command more than jmax (dumbbell under doubled stamps).\n\n```\n" + "\n".join(cpu) + "\n```\n")
+
+
 def smooth_restate(argv):
     """the plain-Python restatement of the smoothing rule (tests/smooth_cases.py on the det oracle) on one host core, on the inputs `smooth`
     wrote, compared bit for bit with the results it wrote: python tools/measure.py smooth_restate <file.npz> [paths]"""
@@ -1932,7 +2070,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, fit, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, fit, jerk, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
