@@ -2,7 +2,9 @@
 // ccmp_fit_opts_default).  The rule is csrc/ccmp_fit.h.  A call is one begin launch, then per pass: the setpoints unit's status launch on the
 // current stamps, ONE read of F status words and F tick counts (they size the measure launch and tell when no path is open), the setpoints
 // unit's tangent launch, the measure and the dilate launches; it stops at the first pass with no open path.  Nothing else is read on the
-// host and no allocation is sized by the ticks.  The _ref form runs the same rule text in plain loops, path by path.
+// host and no allocation is sized by the ticks.  The _ref form runs the same rule text in plain loops, path by path.  The argument checks,
+// the staging of the _host form, the tick ranges and the _ref form's tick and per-tick figures are csrc/ccmp_timed.h's, shared with the
+// setpoints and jerk units; the pass loop is this unit's own.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -13,6 +15,7 @@
 #include "ccmp_fit.h"
 #include "ccmp_launch.h"
 #include "ccmp_stage.h"
+#include "ccmp_timed.h"
 
 using namespace ccmp_host;
 using ccmp::setpoint_limits;
@@ -21,19 +24,9 @@ namespace {
 
 constexpr const char *kArenaWhat = "ccmp_path_fit_timestamps: hipMalloc";
 
-bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
-
 int opts_ok(const ccmp_fit_opts &o)
 {
   return finite_positive(o.period) && o.max_ticks >= 2 && o.aim > 0.0 && o.aim <= 1.0 && o.max_passes >= 0 ? CCMP_OK : CCMP_EINVAL;
-}
-
-int path_first_ok(const int32_t *path_first, size_t F, size_t total_rows)
-{
-  if (path_first[0] < 0) return CCMP_EINVAL;
-  for (size_t f = 0; f < F; f++)
-    if (path_first[f + 1] < path_first[f]) return CCMP_EINVAL;
-  return (size_t)path_first[F] <= total_rows ? CCMP_OK : CCMP_EINVAL;
 }
 
 // what every form checks of its arguments (the host and _ref forms check path_first too)
@@ -42,12 +35,7 @@ int input_checks(const double *rows, const int32_t *path_first, const double *ti
                  setpoint_limits *lim)
 {
   { const int rc = opts_ok(o); if (rc != CCMP_OK) return rc; }
-  if (!vmax || !amax) return CCMP_EINVAL;
-  for (int c = 0; c < 14; c++) {
-    if (!finite_positive(vmax[c]) || !finite_positive(amax[c])) return CCMP_EINVAL;
-    lim->vmax[c] = vmax[c];
-    lim->amax[c] = amax[c];
-  }
+  { const int rc = limits_ok(vmax, amax, lim->vmax, lim->amax); if (rc != CCMP_OK) return rc; }
   if (total_rows > kMaxRows || F > kMaxRows) return CCMP_EINVAL;
   if (F && (!path_first || !status || !passes || !peak || !duration || (total_rows && (!rows || !time || !time_out)))) return CCMP_EINVAL;
   if (overlaps(time, total_rows * sizeof(double), time_out, total_rows * sizeof(double))) return CCMP_EINVAL;
@@ -78,17 +66,9 @@ int fit(ccmp_ctx *ctx, const double *rows, const int32_t *path_first, const doub
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) break;
     bool open = false;
-    int64_t M = 0;
-    for (size_t f = 0; f < F; f++) {
-      first[f] = (int32_t)M;
-      if (state[f] != ccmp::kFitOpen) continue;
-      open = true;
-      const int32_t n = ticks[f];
-      if (n < 0 || n > o.max_ticks) { rc = CCMP_EHIP; break; } // (never: the kernel's count obeys the rule)
-      if (n >= 2) M += n - 1; // an OK path: its tick intervals
-      if ((uint64_t)M > kMaxRows) { rc = CCMP_EOVERFLOW; break; }
-    }
-    first[F] = (int32_t)M;
+    for (size_t f = 0; f < F; f++) open = open || state[f] == ccmp::kFitOpen;
+    int64_t M = 0; // the tick intervals of the open paths: N - 1 of an OK path, none of a path this pass's status ends
+    rc = tick_ranges(F, o.max_ticks, 1, [&](size_t f) { return (int64_t)(state[f] == ccmp::kFitOpen ? ticks[f] : 0); }, &first, &M);
     if (rc != CCMP_OK || !open) break;
     if (M) {
       e = hipMemcpyAsync(d_first, first.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st);
@@ -128,35 +108,21 @@ void fit_path_ref(const double *r, double *t, size_t R, const setpoint_limits &l
     (void)ccmp_setpoint_tangents_ref(r, t, R, w.data());
     S.assign(R, 0.0);
     A.assign(R, 0.0);
-    double v0[14], v1[14], tau0 = 0.0;
+    double v0[14], v1[14], x[14], tau0 = 0.0; // (x: the position half, never used)
     int k0 = 0;
     for (int c = 0; c < 14; c++) v0[c] = 0.0;
     for (int64_t j = 0; j + 1 < N; j++) { // the tick interval (j, j + 1)
-      int k1;
-      double u1;
-      const double tau1 = ccmp::fit_tick(t, (int)R, j + 1, N, o.period, D, &k1, &u1);
+      double tau1;
+      const int k1 = ref_tick(r, w.data(), t, R, j + 1, N, o.period, D, &tau1, x, v1);
+      if (j + 1 == N - 1)
+        for (int c = 0; c < 14; c++) v1[c] = 0.0; // the last tick is at rest: only its bracket counts
       if (j == 0) k0 = k1;
-      for (int c = 0; c < 14; c++) {
-        const size_t ia = (size_t)(k1 - 1) * 14 + c, ib = ia + 14;
-        v1[c] = j + 1 < N - 1 ? ccmp::setpoint_qd(r[ia], r[ib], w[ia], w[ib], t[k1] - t[k1 - 1], u1) : 0.0;
-      }
       const double width = tau1 - tau0;
-      double s = 0.0, a = 0.0;
-      bool s_nan = false, a_nan = false;
-      for (int c = 0; c < 14; c++) {
-        const double sc = ccmp::setpoint_speed(v0[c], lim.vmax[c]);
-        s_nan = s_nan || sc != sc;
-        if (sc > s) s = sc;
-        if (width > 0.0) {
-          const double ac = ccmp::setpoint_acc(v0[c], v1[c], width, lim.amax[c]);
-          a_nan = a_nan || ac != ac;
-          if (ac > a) a = ac;
-        }
-      }
-      if (!s_nan && s > S[k0]) S[k0] = s;
-      if (width > 0.0 && !a_nan)
+      const TickFigures g = tick_figures(v0, v1, width, lim.vmax, lim.amax);
+      if (!g.speed_nan && g.speed > S[k0]) S[k0] = g.speed;
+      if (width > 0.0 && !g.acc_nan)
         for (int k = k0; k <= k1; k++)
-          if (a > A[k]) A[k] = a;
+          if (g.acc > A[k]) A[k] = g.acc;
       for (int c = 0; c < 14; c++) v0[c] = v1[c];
       tau0 = tau1;
       k0 = k1;
@@ -227,18 +193,16 @@ int ccmp_path_fit_timestamps_host(ccmp_ctx *ctx, const double *rows, const int32
   if (!guard.ok) return CCMP_ENODEV;
   const size_t R = total_rows ? total_rows : 1;
   CallArena mem(ctx, "ccmp_path_fit_timestamps_host: hipMalloc"); // the staging is memory of this call
-  double *d_rows = mem.array<double>(R * 14), *d_time = mem.array<double>(R), *d_out = mem.array<double>(R), *d_factor = mem.array<double>(R),
-         *d_peak = mem.array<double>(F * 2), *d_dur = mem.array<double>(F);
-  int32_t *d_pf = mem.array<int32_t>(F + 1), *d_status = mem.array<int32_t>(F), *d_passes = mem.array<int32_t>(F);
+  const PathStage d(mem, F, total_rows);
+  double *d_out = mem.array<double>(R), *d_factor = mem.array<double>(R), *d_peak = mem.array<double>(F * 2), *d_dur = mem.array<double>(F);
+  int32_t *d_status = mem.array<int32_t>(F), *d_passes = mem.array<int32_t>(F);
   if (!mem.ok()) return CCMP_EHIP;
   StagedCall sg(ctx, __func__);
-  sg.up(d_rows, rows, total_rows * 14 * sizeof(double));
-  sg.up(d_pf, path_first, (F + 1) * sizeof(int32_t));
-  sg.up(d_time, time, total_rows * sizeof(double));
+  d.up(sg, rows, time, path_first, F, total_rows);
   sg.up(d_out, time_out, total_rows * sizeof(double)); // the caller's values go up first: rows outside every path stay the caller's
   sg.up(d_factor, factor, total_rows * sizeof(double));
   { const int rc = sg.finish(CCMP_OK); if (rc != CCMP_OK) return rc; }
-  { const int rc = fit(ctx, d_rows, d_pf, d_time, F, total_rows, lim, o, d_out, d_status, d_passes, d_peak, d_dur, factor ? d_factor : nullptr, ctx->stream);
+  { const int rc = fit(ctx, d.rows, d.path_first, d.time, F, total_rows, lim, o, d_out, d_status, d_passes, d_peak, d_dur, factor ? d_factor : nullptr, ctx->stream);
     if (rc != CCMP_OK) return sg.finish(rc); }
   sg.down(time_out, d_out, total_rows * sizeof(double));
   sg.down(factor, d_factor, total_rows * sizeof(double));

@@ -40,14 +40,7 @@ namespace ccmp {
 
 enum : int { kFitOpen = -1, kFitFitted = CCMP_FIT_FITTED, kFitPasses = CCMP_FIT_PASSES };
 
-/* The right tick j1 (1 <= j1 <= N-1) of a tick interval: its tau and its bracket k (u: the bracket's parameter, of use for an interior tick) */
-CCMP_HD double fit_tick(const double *t, int R, int64_t j1, int64_t N, double period, double D, int *k, double *u)
-{
-  const double tau = j1 == N - 1 ? D : setpoint_tau(j1, period, D);
-  bool lower;
-  arc_bracket(t, R, tau, k, u, &lower);
-  return tau;
-}
+/* (the tick of step 2, its tau and its bracket, is setpoint_bracket of ccmp_setpoints.h: the last tick's bracket is what this rule asks of it) */
 
 /* step 5 */
 CCMP_HD bool fit_done(double Ps, double Pa) { return Ps <= 1.0 && Pa <= 1.0; }

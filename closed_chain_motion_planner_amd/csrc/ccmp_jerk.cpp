@@ -4,10 +4,11 @@
 // pass of the window search: ONE read of F words (they size the measure launch and tell when no path is open), one measure launch over the
 // open paths' tiles and one decide launch; then the sample launch, the function, is-satisfied and — with a scene — clearance entry points
 // ONCE each over all ticks of all paths, and the peak launch.  No allocation inside the search is sized by the ticks.  The _ref form runs
-// the same rule text in plain loops, path by path.
+// the same rule text in plain loops, path by path.  The argument checks, the staging of the _host form, the tick ranges, the delivery tail
+// (deliver: this unit hands it its sample launch and, with the window and passes copies, its peak launch) and the _ref form's tick and
+// speed and acceleration peaks are csrc/ccmp_timed.h's, shared with the setpoints and fit units; the window search is this unit's own.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -17,8 +18,8 @@
 #include "ccmp_jerk.h"
 #include "ccmp_launch.h"
 #include "ccmp_resident.h"
-#include "ccmp_scene.h"
 #include "ccmp_stage.h"
+#include "ccmp_timed.h"
 
 using namespace ccmp_host;
 using ccmp::jerk_limits;
@@ -38,8 +39,6 @@ namespace {
 
 constexpr const char *kArenaWhat = "ccmp_path_jerk_setpoints: hipMalloc";
 
-bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
-
 int opts_ok(const ccmp_jerk_opts &o)
 {
   return finite_positive(o.period) && o.max_ticks >= 2 && o.max_window >= 1 && o.max_window <= ccmp::kJerkMaxWindow && o.window >= 0 && o.window <= o.max_window &&
@@ -48,35 +47,14 @@ int opts_ok(const ccmp_jerk_opts &o)
              : CCMP_EINVAL;
 }
 
-int path_first_ok(const int32_t *path_first, size_t F, size_t total_rows)
-{
-  if (path_first[0] < 0) return CCMP_EINVAL;
-  for (size_t f = 0; f < F; f++)
-    if (path_first[f + 1] < path_first[f]) return CCMP_EINVAL;
-  return (size_t)path_first[F] <= total_rows ? CCMP_OK : CCMP_EINVAL;
-}
-
 // what every form checks of its arguments (the host and _ref forms check path_first too)
 int input_checks(const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows, const double *vmax, const double *amax,
                  const double *jmax, const ccmp_jerk_opts &o, jerk_limits *lim)
 {
   { const int rc = opts_ok(o); if (rc != CCMP_OK) return rc; }
-  if (!vmax || !amax || !jmax) return CCMP_EINVAL;
-  for (int c = 0; c < 14; c++) {
-    if (!finite_positive(vmax[c]) || !finite_positive(amax[c]) || !finite_positive(jmax[c])) return CCMP_EINVAL;
-    lim->vmax[c] = vmax[c];
-    lim->amax[c] = amax[c];
-    lim->jmax[c] = jmax[c];
-  }
+  { const int rc = limits_ok(vmax, amax, lim->vmax, lim->amax, jmax, lim->jmax); if (rc != CCMP_OK) return rc; }
   if (total_rows > kMaxRows || F > kMaxRows) return CCMP_EINVAL;
   if (F && (!path_first || (total_rows && (!rows || !time)))) return CCMP_EINVAL;
-  return CCMP_OK;
-}
-
-int device_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin)
-{
-  { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
-  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
   return CCMP_OK;
 }
 
@@ -162,46 +140,32 @@ int jerk(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double m
   if (rc == CCMP_OK && e != hipSuccess) rc = hip_fail(e, "ccmp_path_jerk_setpoints");
   if (rc != CCMP_OK) { (void)hipStreamSynchronize(st); return rc; }
 
-  int64_t M = 0, tiles = 0;
+  int64_t M = 0, tiles = 0; // every path is closed: word [f] = -1 - its ticks
+  { const int r = tick_ranges(F, o.max_ticks, 0, [&](size_t f) { return -1 - (int64_t)word[f]; }, &tick_first, &M); if (r != CCMP_OK) return r; }
   for (size_t f = 0; f < F; f++) {
-    tick_first[f] = (int32_t)M;
     tile_first[f] = (int32_t)tiles;
-    const int64_t n = -1 - (int64_t)word[f]; // every path is closed
-    if (n < 0 || n > o.max_ticks) return CCMP_EHIP; // (never)
-    M += n;
-    tiles += (n + Ts - 1) / Ts;
-    if ((uint64_t)M > kMaxRows) return CCMP_EOVERFLOW;
+    tiles += (tick_first[f + 1] - tick_first[f] + Ts - 1) / Ts;
   }
-  tick_first[F] = (int32_t)M;
   tile_first[F] = (int32_t)tiles;
 
   ccmp_jerk_setpoints *h = nullptr;
   { const int r = make_handle(ctx, F, (size_t)M, &h); if (r != CCMP_OK) return r; }
-  e = hipMemcpyAsync(h->tick_first, tick_first.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && F) e = hipMemcpyAsync(h->status, d_status, F * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess && F) e = hipMemcpyAsync(h->window, d_window, F * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess && F) e = hipMemcpyAsync(h->passes, d_passes, F * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess && M) {
-    const size_t m = (size_t)M;
-    e = hipMemsetAsync(h->q, 0, m * 14 * sizeof(double), st); // a tick the sample kernel refuses to trust stays zero
-    if (e == hipSuccess) e = hipMemsetAsync(h->qd, 0, m * 14 * sizeof(double), st);
-    if (e == hipSuccess) e = hipMemsetAsync(h->tau, 0, m * sizeof(double), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tiles, tile_first.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-      e = ccmp_launch::jerk_sample(rows, path_first, time, tangent, d_tiles, (size_t)tiles, h->tick_first, d_status, d_window, d_ticks, F, m, total_rows, o.period, Ts,
-                                   h->q, h->qd, h->tau, h->clearance, st);
-    if (e == hipSuccess) rc = ccmp_function_batch(ctx, p, h->q, h->f, m, st); // ONE call each for all ticks of all paths
-    if (rc == CCMP_OK && e == hipSuccess) rc = ccmp_is_satisfied_batch(ctx, p, h->q, h->satisfied, m, st);
-    if (rc == CCMP_OK && e == hipSuccess && scene) rc = ccmp_clearance_batch(ctx, p, scene, h->q, nullptr, m, margin, h->clearance, nullptr, nullptr, st);
-  }
-  if (rc == CCMP_OK && e == hipSuccess && F)
-    e = ccmp_launch::jerk_peak(h->qd, h->f, h->satisfied, h->clearance, h->tick_first, F, (size_t)M, o.period, lim, margin, h->peak, h->peak_tick, h->counts, st);
-  const hipError_t es = hipStreamSynchronize(st); // the call is synchronous: the host arrays above and the arena go when it returns
-  if (rc == CCMP_OK && e != hipSuccess) rc = hip_fail(e, "ccmp_path_jerk_setpoints");
-  if (rc == CCMP_OK && es != hipSuccess) rc = hip_fail(es, "ccmp_path_jerk_setpoints: hipStreamSynchronize");
-  if (rc != CCMP_OK) { ccmp_jerk_setpoints_destroy(h); return rc; }
-  *out = h;
-  return CCMP_OK;
+  return deliver(
+      ctx, p, scene, margin, h, tick_first, d_status, "ccmp_path_jerk_setpoints", st,
+      [&] {
+        const hipError_t eu = hipMemcpyAsync(d_tiles, tile_first.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        return eu != hipSuccess ? eu
+                                : ccmp_launch::jerk_sample(rows, path_first, time, tangent, d_tiles, (size_t)tiles, h->tick_first, d_status, d_window, d_ticks, F, h->ticks,
+                                                           total_rows, o.period, Ts, h->q, h->qd, h->tau, h->clearance, st);
+      },
+      [&] { // the window and the passes of every path, then the audit
+        hipError_t ef = hipMemcpyAsync(h->window, d_window, F * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+        if (ef == hipSuccess) ef = hipMemcpyAsync(h->passes, d_passes, F * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+        return ef != hipSuccess ? ef
+                                : ccmp_launch::jerk_peak(h->qd, h->f, h->satisfied, h->clearance, h->tick_first, F, h->ticks, o.period, lim, margin, h->peak, h->peak_tick,
+                                                         h->counts, st);
+      },
+      out);
 }
 
 int result_copy(ccmp_jerk_setpoints *h, double *q, double *qd, double *tau, int32_t *tick_first, double *f, uint8_t *satisfied, double *clearance, int32_t *status,
@@ -309,17 +273,13 @@ int ccmp_path_jerk_setpoints_host(ccmp_ctx *ctx, const ccmp_problem *p, const cc
   if (F) { const int rc = path_first_ok(path_first, F, total_rows); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  const size_t R = total_rows ? total_rows : 1;
   CallArena mem(ctx, "ccmp_path_jerk_setpoints_host: hipMalloc"); // the staging is memory of this call
-  double *d_rows = mem.array<double>(R * 14), *d_time = mem.array<double>(R);
-  int32_t *d_pf = mem.array<int32_t>(F + 1);
+  const PathStage d(mem, F, total_rows);
   if (!mem.ok()) return CCMP_EHIP;
   StagedCall sg(ctx, __func__);
-  sg.up(d_rows, rows, total_rows * 14 * sizeof(double));
-  sg.up(d_time, time, total_rows * sizeof(double));
-  if (F) sg.up(d_pf, path_first, (F + 1) * sizeof(int32_t));
+  d.up(sg, rows, time, path_first, F, total_rows);
   { const int rc = sg.finish(CCMP_OK); if (rc != CCMP_OK) return rc; }
-  return jerk(ctx, p, scene, margin, d_rows, d_pf, d_time, F, total_rows, lim, o, out, ctx->stream);
+  return jerk(ctx, p, scene, margin, d.rows, d.path_first, d.time, F, total_rows, lim, o, out, ctx->stream);
 }
 
 int ccmp_jerk_setpoints_info(const ccmp_jerk_setpoints *h, size_t *F, size_t *ticks)
@@ -398,19 +358,8 @@ int ccmp_jerk_setpoints_ref(const double *rows, const int32_t *path_first, const
         p.xd.assign((size_t)(n + 1) * 14, 0.0);
         memcpy(p.xq.data(), r, 14 * sizeof(double));
         memcpy(p.xq.data() + (size_t)n * 14, r + (R - 1) * 14, 14 * sizeof(double));
-        for (int64_t i = 1; i < n; i++) {
-          const double at = ccmp::setpoint_tau(i, o.period, D);
-          int k;
-          double u;
-          bool lower;
-          ccmp::arc_bracket(t, (int)R, at, &k, &u, &lower);
-          const double h = t[k] - t[k - 1];
-          for (int c = 0; c < 14; c++) {
-            const size_t ia = (size_t)(k - 1) * 14 + c, ib = ia + 14;
-            p.xq[(size_t)i * 14 + c] = ccmp::setpoint_q(r[ia], r[ib], w[ia], w[ib], h, u);
-            p.xd[(size_t)i * 14 + c] = ccmp::setpoint_qd(r[ia], r[ib], w[ia], w[ib], h, u);
-          }
-        }
+        double at; // (the input's own tau: the output's grid is jerk_tau)
+        for (int64_t i = 1; i < n; i++) (void)ref_tick(r, w.data(), t, R, i, n + 1, o.period, D, &at, &p.xq[(size_t)i * 14], &p.xd[(size_t)i * 14]);
       }
       while (st[f] == ccmp::kJerkOpen) {
         double pv;
@@ -461,24 +410,7 @@ int ccmp_jerk_setpoints_ref(const double *rows, const int32_t *path_first, const
         if (tau) tau[g0 + (size_t)j] = ccmp::jerk_tau(j, o.period);
       }
       if (qd) memcpy(qd + g0 * 14, v.data(), (size_t)M * 14 * sizeof(double));
-      // the speed and acceleration peaks: ticks in order, so the first tick of a tie stays
-      for (int64_t j = 0; j < M; j++) {
-        const double width = j + 1 < M ? ccmp::jerk_tau(j + 1, o.period) - ccmp::jerk_tau(j, o.period) : 0.0;
-        double speed = 0.0, acc = 0.0;
-        bool speed_nan = false, acc_nan = false;
-        for (int c = 0; c < 14; c++) {
-          const double s = ccmp::setpoint_speed(v[(size_t)j * 14 + c], lim.vmax[c]);
-          speed_nan = speed_nan || s != s;
-          if (s > speed) speed = s;
-          if (width > 0.0) {
-            const double ac = ccmp::setpoint_acc(v[(size_t)j * 14 + c], v[(size_t)(j + 1) * 14 + c], width, lim.amax[c]);
-            acc_nan = acc_nan || ac != ac;
-            if (ac > acc) acc = ac;
-          }
-        }
-        if (!speed_nan && ccmp::setpoint_higher(speed, (int32_t)j, pv[0], pj[0])) { pv[0] = speed; pj[0] = (int32_t)j; }
-        if (width > 0.0 && !acc_nan && ccmp::setpoint_higher(acc, (int32_t)j, pv[1], pj[1])) { pv[1] = acc; pj[1] = (int32_t)j; }
-      }
+      speed_acc_peaks(v.data(), M, [&](int64_t j) { return ccmp::jerk_tau(j + 1, o.period) - ccmp::jerk_tau(j, o.period); }, lim.vmax, lim.amax, pv, pj);
       jerk_peak_ref(v, M, o.period, lim, &pv[2], &pj[2]);
     }
     if (peak) for (int k = 0; k < 3; k++) peak[f * 3 + k] = pv[k];

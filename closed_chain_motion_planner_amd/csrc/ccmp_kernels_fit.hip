@@ -5,8 +5,9 @@
 //   fit_begin_kernel     one 256-lane block per path: the path's range checked (a range that is negative, decreasing or beyond the rows is
 //                        never read and never written), the input stamps copied to time_out, the path's result words reset to "open".
 //   fit_measure_kernel   the hot path.  Sixteen lanes per tick interval j, lanes 0 .. 13 one joint each.  The interval's path by bisection on
-//                        tick_first; the brackets of tau_j and tau_{j+1}; qd at both from rows, stamps and tangents; s_j and a_j folded across
-//                        the sixteen lanes with DPP row rotations; neighbouring groups of a wavefront with the same brackets merged; then a
+//                        tick_first; the brackets of tau_j and tau_{j+1} (setpoint_bracket) and qd at both (setpoint_joint: the setpoints
+//                        rule's tick, as in its sample kernel); s_j and a_j folded across the sixteen lanes with the DPP row folds of
+//                        ccmp_lanes.h; neighbouring groups of a wavefront with the same brackets merged; then a
 //                        64-bit unsigned atomic maximum on the bit pattern (non-negative doubles order as their bits) into S[k_j] and
 //                        A[k_j .. k_{j+1}], the sixteen lanes striding that range.
 //   fit_dilate_kernel    one wavefront per path: P_s and P_a folded, FITTED / PASSES / open decided; an open path's h' 64 at a time, lane 0's
@@ -18,6 +19,7 @@
 
 #include "ccmp_detmath.h"
 #include "ccmp_fit.h"
+#include "ccmp_lanes.h"
 #include "ccmp_launch.h"
 
 namespace {
@@ -27,36 +29,11 @@ using ccmp::path_of;
 using ccmp::setpoint_limits;
 constexpr int kThreads = 256;
 constexpr int kWave = 64;
-typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 bits_of(double v) { return (u64)__double_as_longlong(v); }
-__device__ __forceinline__ double value_of(u64 b) { return __longlong_as_double((long long)b); }
-
-// a DPP row operation on one 32-bit half
-template <int kCtrl> __device__ __forceinline__ int dpp32(int v) { return __builtin_amdgcn_update_dpp(v, v, kCtrl, 0xf, 0xf, false); }
-template <int kCtrl> __device__ __forceinline__ double dpp64(double v)
-{
-  return __hiloint2double(dpp32<kCtrl>(__double2hiint(v)), dpp32<kCtrl>(__double2loint(v)));
-}
-// The maximum over the sixteen lanes of a DPP row of non-negative doubles without a NaN, in every lane of the row: rotations by 8, 4, 2, 1
-// (row_ror:n is 0x120 + n).  The whole row is active wherever this is called.
-__device__ __forceinline__ double row_max(double v)
-{
-  double o;
-  o = dpp64<0x128>(v); v = o > v ? o : v;
-  o = dpp64<0x124>(v); v = o > v ? o : v;
-  o = dpp64<0x122>(v); v = o > v ? o : v;
-  o = dpp64<0x121>(v); v = o > v ? o : v;
-  return v;
-}
-__device__ __forceinline__ int row_or(int v)
-{
-  v |= dpp32<0x128>(v);
-  v |= dpp32<0x124>(v);
-  v |= dpp32<0x122>(v);
-  v |= dpp32<0x121>(v);
-  return v;
-}
+using ccmp_lanes::bits_of;
+using ccmp_lanes::row_max;
+using ccmp_lanes::row_or;
+using ccmp_lanes::u64;
+using ccmp_lanes::value_of;
 
 __global__ __launch_bounds__(kThreads) void fit_begin_kernel(const int32_t *__restrict__ path_first, const double *__restrict__ time, long long total_rows,
                                                             double *__restrict__ time_out, int32_t *__restrict__ status, int32_t *__restrict__ passes,
@@ -92,27 +69,19 @@ __global__ __launch_bounds__(kThreads) void fit_measure_kernel(const double *__r
     if (j >= 0 && j < n && first >= 0 && R >= 2 && first + R <= total_rows) { // never trusted
       const double *tp = time + first;
       const double D = tp[R - 1];
-      const double tau0 = j == 0 ? 0.0 : ccmp::setpoint_tau(j, period, D);
-      const double tau1p = j + 1 == n ? D : ccmp::setpoint_tau(j + 1, period, D);
-      // (the rule's own precondition of the bracket; an OK path meets it)
-      if (tau1p > 0.0 && tau1p <= D && (j == 0 || (tau0 > 0.0 && tau0 <= D))) {
-        int k0 = 0, k1 = 0;
-        double u0 = 0.0, u1 = 0.0;
-        const double tau1 = ccmp::fit_tick(tp, (int)R, j + 1, n + 1, period, D, &k1, &u1);
-        if (j == 0) k0 = k1; else (void)ccmp::fit_tick(tp, (int)R, j, n + 1, period, D, &k0, &u0);
+      int k0, k1;
+      double tau0, tau1, u0, u1;
+      // (false: the rule's own precondition of a bracket; an OK path meets it)
+      if (ccmp::setpoint_bracket(tp, (int)R, j + 1, n + 1, period, D, &tau1, &k1, &u1) && ccmp::setpoint_bracket(tp, (int)R, j, n + 1, period, D, &tau0, &k0, &u0)) {
+        if (j == 0) k0 = k1;
         if (k0 >= 1 && k0 <= k1 && k1 < R) {
           const double width = tau1 - tau0;
           int nan = 0;
           if (c < 14) {
-            double v0 = 0.0, v1 = 0.0;
-            if (j > 0) {
-              const size_t ia = (size_t)(first + k0 - 1) * 14 + c, ib = ia + 14;
-              v0 = ccmp::setpoint_qd(rows[ia], rows[ib], tangent[ia], tangent[ib], tp[k0] - tp[k0 - 1], u0);
-            }
-            if (j + 1 < n) {
-              const size_t ia = (size_t)(first + k1 - 1) * 14 + c, ib = ia + 14;
-              v1 = ccmp::setpoint_qd(rows[ia], rows[ib], tangent[ia], tangent[ib], tp[k1] - tp[k1 - 1], u1);
-            }
+            const double *r = rows + (size_t)first * 14 + c, *w = tangent + (size_t)first * 14 + c;
+            double v0 = 0.0, v1 = 0.0, x; // (x: the position half, never used)
+            if (j > 0) ccmp::setpoint_joint(r, w, tp, k0, u0, &x, &v0);
+            if (j + 1 < n) ccmp::setpoint_joint(r, w, tp, k1, u1, &x, &v1);
             s = ccmp::setpoint_speed(v0, lim.vmax[c]);
             if (s != s) { nan |= 1; s = 0.0; }
             if (width > 0.0) {

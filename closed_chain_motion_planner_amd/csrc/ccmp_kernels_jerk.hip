@@ -13,15 +13,17 @@
 //                         reads and clears P[f] and decides OK / WINDOW / FULL / the next W.  word[f] = M of an open path, -1 - M of a closed.
 //   jerk_sample_kernel    one block per tile of a delivered path's ticks: both parts of x staged the same way, q, qd, tau of every tick
 //                         with the path's final W, the copies at both ends, the NaN a clearance holds until a scene has answered.
-//   jerk_peak_kernel      one 256-lane block per path: six (value, tick) peaks and two counts per lane, folded in LDS under the same total
-//                         order, the shape of setpoints_peak_kernel.  Its jerk peak is the P the last measurement saw: the same functions
+//   jerk_peak_kernel      one 256-lane block per path: audit_fold of ccmp_lanes.h (setpoints_peak_kernel's too) with six columns, the
+//                         widths from the rule's grid and no stretch.  Its jerk peak is the P the last measurement saw: the same functions
 //                         on the same bits.
+// A tick of the interpolant (input_of) is the setpoints rule's setpoint_bracket and setpoint_joint; the DPP row folds are ccmp_lanes.h's.
 // No grid barrier, no spin; every loop is bounded by its data or by a constant; lanes beyond the data are masked; every offset read from
 // memory is range-checked before use.
 #include <hip/hip_runtime.h>
 
 #include "ccmp_detmath.h"
 #include "ccmp_jerk.h"
+#include "ccmp_lanes.h"
 #include "ccmp_launch.h"
 
 namespace {
@@ -34,39 +36,15 @@ constexpr int kWave = 64;
 constexpr int kTile = ccmp_launch::kJerkTile;             // output ticks per block of the measure kernel at most
 constexpr int kSampleTile = ccmp_launch::kJerkSampleTile; // ... of the sample kernel, which stages both parts of x
 constexpr int kMaxW = ccmp::kJerkMaxWindow;
-typedef unsigned long long u64;
+using ccmp_lanes::bits_of;
+using ccmp_lanes::row_max;
+using ccmp_lanes::row_or;
+using ccmp_lanes::u64;
+using ccmp_lanes::value_of;
 
 // static LDS of the two staging kernels: both within the 64 KB a block may have
 static_assert(((kTile + kMaxW + 1) + (kTile + 2)) * 14 * sizeof(double) + 64 <= 65536, "jerk_measure_kernel: LDS");
 static_assert((kSampleTile + kMaxW - 1) * 28 * sizeof(double) <= 65536, "jerk_sample_kernel: LDS");
-
-__device__ __forceinline__ u64 bits_of(double v) { return (u64)__double_as_longlong(v); }
-__device__ __forceinline__ double value_of(u64 b) { return __longlong_as_double((long long)b); }
-
-template <int kCtrl> __device__ __forceinline__ int dpp32(int v) { return __builtin_amdgcn_update_dpp(v, v, kCtrl, 0xf, 0xf, false); }
-template <int kCtrl> __device__ __forceinline__ double dpp64(double v)
-{
-  return __hiloint2double(dpp32<kCtrl>(__double2hiint(v)), dpp32<kCtrl>(__double2loint(v)));
-}
-// The maximum over the sixteen lanes of a DPP row of non-negative doubles without a NaN, in every lane of the row (row_ror:n is 0x120 + n).
-// The whole row is active wherever this is called.
-__device__ __forceinline__ double row_max(double v)
-{
-  double o;
-  o = dpp64<0x128>(v); v = o > v ? o : v;
-  o = dpp64<0x124>(v); v = o > v ? o : v;
-  o = dpp64<0x122>(v); v = o > v ? o : v;
-  o = dpp64<0x121>(v); v = o > v ? o : v;
-  return v;
-}
-__device__ __forceinline__ int row_or(int v)
-{
-  v |= dpp32<0x128>(v);
-  v |= dpp32<0x124>(v);
-  v |= dpp32<0x122>(v);
-  v |= dpp32<0x121>(v);
-  return v;
-}
 
 // One path as the staging kernels see it, range-checked: rows r, stamps t, tangents w of its R >= 2 rows, n tick intervals
 struct PathView {
@@ -80,16 +58,12 @@ __device__ __forceinline__ double input_of(const PathView &p, long long i, int c
 {
   if (i <= 0) { *xq = p.r[c]; return 0.0; }
   if (i >= p.n) { *xq = p.r[(size_t)(p.R - 1) * 14 + c]; return 0.0; }
-  const double at = ccmp::setpoint_tau(i, period, p.D);
-  if (!(at > 0.0) || !(at <= p.D)) { *xq = p.r[c]; return 0.0; } // (the rule's own precondition of the bracket; an OK path meets it)
   int k;
-  double u;
-  bool lower;
-  ccmp::arc_bracket(p.t, (int)p.R, at, &k, &u, &lower);
-  const double h = p.t[k] - p.t[k - 1];
-  const size_t a = (size_t)(k - 1) * 14 + c, b = a + 14;
-  *xq = ccmp::setpoint_q(p.r[a], p.r[b], p.w[a], p.w[b], h, u);
-  return ccmp::setpoint_qd(p.r[a], p.r[b], p.w[a], p.w[b], h, u);
+  double at, u, xd;
+  // (false: the rule's own precondition of the bracket; an OK path meets it)
+  if (!ccmp::setpoint_bracket(p.t, (int)p.R, i, p.n + 1, period, p.D, &at, &k, &u)) { *xq = p.r[c]; return 0.0; }
+  ccmp::setpoint_joint(p.r + c, p.w + c, p.t, k, u, xq, &xd);
+  return xd;
 }
 
 __global__ __launch_bounds__(kThreads) void jerk_measure_kernel(const double *__restrict__ rows, const int32_t *__restrict__ path_first,
@@ -268,90 +242,27 @@ __global__ __launch_bounds__(kThreads) void jerk_sample_kernel(const double *__r
   }
 }
 
-// one lane's or one block's six peaks
-struct Peaks {
-  double v[ccmp::kJerkPeaks];
-  int32_t j[ccmp::kJerkPeaks];
+// the audit's trait (ccmp_lanes.h: audit_fold): six columns, the widths from the rule's own grid, the jerk share at the middle tick, no stretch
+struct JerkAudit {
+  static constexpr int kCols = ccmp::kJerkPeaks, kSpeed = ccmp::kJerkPeakSpeed, kAcc = ccmp::kJerkPeakAcc, kJerk = ccmp::kJerkPeakJerk, kDp = ccmp::kJerkPeakDp,
+                       kAngle = ccmp::kJerkPeakAngle, kClearance = ccmp::kJerkPeakClearance;
+  static constexpr bool kStretch = false;
+  double period;
+  const double *jmax;
+  __device__ double width(size_t, long long j) const { return ccmp::jerk_tau(j + 1, period) - ccmp::jerk_tau(j, period); }
+  __device__ double jerk(const double *qd, size_t g, long long j, int c) const
+  {
+    return ccmp::jerk_share(qd[(g - 1) * 14 + c], qd[g * 14 + c], qd[(g + 1) * 14 + c], j - 1, period, jmax[c]);
+  }
 };
-
-__device__ __forceinline__ void offer(Peaks &p, int which, double v, int32_t j)
-{
-  const bool better = which == ccmp::kJerkPeakClearance ? ccmp::setpoint_lower(v, j, p.v[which], p.j[which]) : ccmp::setpoint_higher(v, j, p.v[which], p.j[which]);
-  if (better) { p.v[which] = v; p.j[which] = j; }
-}
 
 __global__ __launch_bounds__(kThreads) void jerk_peak_kernel(const double *__restrict__ qd, const double *__restrict__ fgap, const uint8_t *__restrict__ satisfied,
                                                             const double *__restrict__ clearance, const int32_t *__restrict__ tick_first, long long total_ticks,
                                                             double period, jerk_limits lim, double margin, double *__restrict__ peak,
                                                             int32_t *__restrict__ peak_tick, int32_t *__restrict__ counts)
 {
-  __shared__ double s_v[ccmp::kJerkPeaks][kThreads];
-  __shared__ int32_t s_j[ccmp::kJerkPeaks][kThreads];
-  __shared__ int32_t s_n[2][kThreads];
-  const int f = blockIdx.x, t = threadIdx.x;
-  long long first = tick_first[f], M = (long long)tick_first[f + 1] - first;
-  if (first < 0 || M < 0 || first + M > total_ticks) M = 0; // block-uniform: never trusted, a path without ticks
-  Peaks p;
-#pragma unroll
-  for (int w = 0; w < ccmp::kJerkPeaks; w++) { p.v[w] = w == ccmp::kJerkPeakClearance ? __builtin_inf() : 0.0; p.j[w] = -1; }
-  int32_t n_off = 0, n_below = 0;
-  for (long long j = t; j < M; j += kThreads) {
-    const size_t g = (size_t)(first + j);
-    const bool has_next = j + 1 < M, has_prev = j > 0;
-    const double width = has_next ? ccmp::jerk_tau(j + 1, period) - ccmp::jerk_tau(j, period) : 0.0;
-    double speed = 0.0, acc = 0.0, jerk = 0.0; // (the maxima over the joints: finite values, any order)
-    bool speed_nan = false, acc_nan = false, jerk_nan = false;
-    for (int c = 0; c < 14; c++) {
-      const double v = qd[g * 14 + c];
-      const double s = ccmp::setpoint_speed(v, lim.vmax[c]);
-      speed_nan = speed_nan || s != s;
-      if (s > speed) speed = s;
-      if (width > 0.0) {
-        const double a = ccmp::setpoint_acc(v, qd[(g + 1) * 14 + c], width, lim.amax[c]);
-        acc_nan = acc_nan || a != a;
-        if (a > acc) acc = a;
-      }
-      if (has_next && has_prev) { // this tick is the middle one of j - 1, j, j + 1
-        const double k = ccmp::jerk_share(qd[(g - 1) * 14 + c], v, qd[(g + 1) * 14 + c], j - 1, period, lim.jmax[c]);
-        jerk_nan = jerk_nan || k != k;
-        if (k > jerk) jerk = k;
-      }
-    }
-    if (!speed_nan) offer(p, ccmp::kJerkPeakSpeed, speed, (int32_t)j);
-    if (width > 0.0 && !acc_nan) offer(p, ccmp::kJerkPeakAcc, acc, (int32_t)j);
-    if (has_next && has_prev && !jerk_nan) offer(p, ccmp::kJerkPeakJerk, jerk, (int32_t)j);
-    offer(p, ccmp::kJerkPeakDp, fgap[g * 2], (int32_t)j);
-    offer(p, ccmp::kJerkPeakAngle, fgap[g * 2 + 1], (int32_t)j);
-    const double cl = clearance[g];
-    offer(p, ccmp::kJerkPeakClearance, cl, (int32_t)j);
-    n_off += satisfied[g] ? 0 : 1;
-    n_below += cl < margin ? 1 : 0;
-  }
-#pragma unroll
-  for (int w = 0; w < ccmp::kJerkPeaks; w++) { s_v[w][t] = p.v[w]; s_j[w][t] = p.j[w]; }
-  s_n[0][t] = n_off;
-  s_n[1][t] = n_below;
-  __syncthreads();
-  for (int m = kThreads / 2; m > 0; m >>= 1) { // block-uniform: every lane meets every barrier
-    if (t < m) {
-#pragma unroll
-      for (int w = 0; w < ccmp::kJerkPeaks; w++) {
-        const double v = s_v[w][t + m], bv = s_v[w][t];
-        const int32_t j = s_j[w][t + m], bj = s_j[w][t];
-        const bool better = j >= 0 && (w == ccmp::kJerkPeakClearance ? ccmp::setpoint_lower(v, j, bv, bj) : ccmp::setpoint_higher(v, j, bv, bj));
-        if (better) { s_v[w][t] = v; s_j[w][t] = j; }
-      }
-      s_n[0][t] += s_n[0][t + m];
-      s_n[1][t] += s_n[1][t + m];
-    }
-    __syncthreads();
-  }
-  if (t < ccmp::kJerkPeaks) {
-    peak[(size_t)f * ccmp::kJerkPeaks + t] = s_v[t][0];
-    peak_tick[(size_t)f * ccmp::kJerkPeaks + t] = s_j[t][0];
-  } else if (t < ccmp::kJerkPeaks + 2) {
-    counts[(size_t)f * 2 + (t - ccmp::kJerkPeaks)] = s_n[t - ccmp::kJerkPeaks][0];
-  }
+  ccmp_lanes::audit_fold<JerkAudit, kThreads>(JerkAudit{period, lim.jmax}, lim.vmax, lim.amax, qd, fgap, satisfied, clearance, tick_first, total_ticks, margin, peak,
+                                              peak_tick, counts, nullptr);
 }
 
 }  // namespace

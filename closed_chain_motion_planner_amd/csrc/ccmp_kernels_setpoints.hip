@@ -6,16 +6,17 @@
 //                             decreasing or beyond the rows is never trusted: the path counts as EMPTY), every coordinate and stamp tested
 //                             for finiteness, every interval for its order; writes status[f] and the path's tick count.
 //   setpoints_tangent_kernel  sixteen lanes per row, lanes 0 .. 13 one joint each: the two slopes and the row's tangent.
-//   setpoints_sample_kernel   sixteen lanes per tick.  The tick's path by bisection on tick_first; the bracket of tau_j on the path's stamps;
-//                             lanes 0 .. 13 q and qd of one joint each, lane 14 writes tau, lane 15 the NaN a clearance holds until a scene
-//                             has answered.
-//   setpoints_peak_kernel     one 256-lane block per path: every lane folds its ticks into five (value, tick) peaks and two counts, the
-//                             block folds the lanes in LDS under the same total order — the answer is a function of the inputs alone.
+//   setpoints_sample_kernel   sixteen lanes per tick.  The tick's path by bisection on tick_first; the tick by the rule's setpoint_bracket
+//                             and setpoint_joint (the fit and jerk units' too); lanes 0 .. 13 q and qd of one joint each, lane 14 writes
+//                             tau, lane 15 the NaN a clearance holds until a scene has answered.
+//   setpoints_peak_kernel     one 256-lane block per path: audit_fold of ccmp_lanes.h (the jerk unit's too) with five columns, the widths
+//                             from tau, and stretch.
 // No grid barrier, no spin; every loop is bounded by its data; lanes beyond the data are masked; every offset read from memory is
 // range-checked before use.
 #include <hip/hip_runtime.h>
 
 #include "ccmp_detmath.h"
+#include "ccmp_lanes.h"
 #include "ccmp_launch.h"
 #include "ccmp_setpoints.h"
 
@@ -98,28 +99,18 @@ __global__ __launch_bounds__(kThreads) void setpoints_sample_kernel(const double
   const int st = status[f];
   if (j < 0 || j >= N || first < 0 || R < 1 || first + R > total_rows || (st != ccmp::kSetpointsOk && st != ccmp::kSetpointsPoint)) return; // never trusted
   long long src = first; // the row a copied tick is
-  double at = 0.0, u = 0.0, h = 0.0;
+  double at = 0.0, u = 0.0;
   int k = 0; // > 0: an interior tick in the bracket (k - 1, k)
   if (st == ccmp::kSetpointsOk && j > 0) {
-    const double D = time[first + R - 1];
-    if (j == N - 1) {
+    if (!ccmp::setpoint_bracket(time + first, (int)R, j, N, period, time[first + R - 1], &at, &k, &u)) return; // (an OK path meets the precondition)
+    if (j == N - 1) { // a copy, whatever its bracket
       src = first + R - 1;
-      at = D;
-    } else {
-      at = ccmp::setpoint_tau(j, period, D);
-      if (!(at > 0.0) || !(at <= D) || R < 2) return; // (the rule's own precondition of the bracket; an OK path meets it)
-      bool lower;
-      ccmp::arc_bracket(time + first, (int)R, at, &k, &u, &lower);
-      h = time[first + k] - time[first + k - 1];
+      k = 0;
     }
   }
   if (c < 14) {
     double x = rows[(size_t)src * 14 + c], xd = 0.0;
-    if (k > 0) {
-      const size_t a = (size_t)(first + k - 1) * 14 + c, b = a + 14;
-      x = ccmp::setpoint_q(rows[a], rows[b], tangent[a], tangent[b], h, u);
-      xd = ccmp::setpoint_qd(rows[a], rows[b], tangent[a], tangent[b], h, u);
-    }
+    if (k > 0) ccmp::setpoint_joint(rows + (size_t)first * 14 + c, tangent + (size_t)first * 14 + c, time + first, k, u, &x, &xd);
     q[g * 14 + c] = x;
     qd[g * 14 + c] = xd;
   } else if (c == 14) {
@@ -129,17 +120,14 @@ __global__ __launch_bounds__(kThreads) void setpoints_sample_kernel(const double
   }
 }
 
-// one lane's or one block's five peaks and two counts
-struct Peaks {
-  double v[ccmp::kPeaks];
-  int32_t j[ccmp::kPeaks];
+// the audit's trait (ccmp_lanes.h: audit_fold): five columns, the widths from the tau the sample kernel wrote, stretch
+struct SetpointsAudit {
+  static constexpr int kCols = ccmp::kPeaks, kSpeed = ccmp::kPeakSpeed, kAcc = ccmp::kPeakAcc, kJerk = -1, kDp = ccmp::kPeakDp, kAngle = ccmp::kPeakAngle,
+                       kClearance = ccmp::kPeakClearance;
+  static constexpr bool kStretch = true;
+  const double *tau;
+  __device__ double width(size_t g, long long) const { return tau[g + 1] - tau[g]; }
 };
-
-__device__ __forceinline__ void offer(Peaks &p, int which, double v, int32_t j)
-{
-  const bool better = which == ccmp::kPeakClearance ? ccmp::setpoint_lower(v, j, p.v[which], p.j[which]) : ccmp::setpoint_higher(v, j, p.v[which], p.j[which]);
-  if (better) { p.v[which] = v; p.j[which] = j; }
-}
 
 __global__ __launch_bounds__(kThreads) void setpoints_peak_kernel(const double *__restrict__ qd, const double *__restrict__ tau, const double *__restrict__ fgap,
                                                                  const uint8_t *__restrict__ satisfied, const double *__restrict__ clearance,
@@ -147,69 +135,8 @@ __global__ __launch_bounds__(kThreads) void setpoints_peak_kernel(const double *
                                                                  double *__restrict__ peak, int32_t *__restrict__ peak_tick, int32_t *__restrict__ counts,
                                                                  double *__restrict__ stretch)
 {
-  __shared__ double s_v[ccmp::kPeaks][kThreads];
-  __shared__ int32_t s_j[ccmp::kPeaks][kThreads];
-  __shared__ int32_t s_n[2][kThreads];
-  const int f = blockIdx.x, t = threadIdx.x;
-  long long first = tick_first[f], N = (long long)tick_first[f + 1] - first;
-  if (first < 0 || N < 0 || first + N > M) N = 0; // block-uniform: never trusted, a path without ticks
-  Peaks p;
-#pragma unroll
-  for (int w = 0; w < ccmp::kPeaks; w++) { p.v[w] = w == ccmp::kPeakClearance ? __builtin_inf() : 0.0; p.j[w] = -1; }
-  int32_t n_off = 0, n_below = 0;
-  for (long long j = t; j < N; j += kThreads) {
-    const size_t g = (size_t)(first + j);
-    const bool has_next = j + 1 < N;
-    const double width = has_next ? tau[g + 1] - tau[g] : 0.0;
-    double speed = 0.0, acc = 0.0; // (the maxima over the joints: finite values, any order)
-    bool speed_nan = false, acc_nan = false;
-    for (int c = 0; c < 14; c++) {
-      const double v = qd[g * 14 + c];
-      const double s = ccmp::setpoint_speed(v, lim.vmax[c]);
-      speed_nan = speed_nan || s != s;
-      if (s > speed) speed = s;
-      if (width > 0.0) {
-        const double a = ccmp::setpoint_acc(v, qd[(g + 1) * 14 + c], width, lim.amax[c]);
-        acc_nan = acc_nan || a != a;
-        if (a > acc) acc = a;
-      }
-    }
-    if (!speed_nan) offer(p, ccmp::kPeakSpeed, speed, (int32_t)j);
-    if (width > 0.0 && !acc_nan) offer(p, ccmp::kPeakAcc, acc, (int32_t)j);
-    offer(p, ccmp::kPeakDp, fgap[g * 2], (int32_t)j);
-    offer(p, ccmp::kPeakAngle, fgap[g * 2 + 1], (int32_t)j);
-    const double cl = clearance[g];
-    offer(p, ccmp::kPeakClearance, cl, (int32_t)j);
-    n_off += satisfied[g] ? 0 : 1;
-    n_below += cl < margin ? 1 : 0;
-  }
-#pragma unroll
-  for (int w = 0; w < ccmp::kPeaks; w++) { s_v[w][t] = p.v[w]; s_j[w][t] = p.j[w]; }
-  s_n[0][t] = n_off;
-  s_n[1][t] = n_below;
-  __syncthreads();
-  for (int m = kThreads / 2; m > 0; m >>= 1) { // block-uniform: every lane meets every barrier
-    if (t < m) {
-#pragma unroll
-      for (int w = 0; w < ccmp::kPeaks; w++) {
-        const double v = s_v[w][t + m], bv = s_v[w][t];
-        const int32_t j = s_j[w][t + m], bj = s_j[w][t];
-        const bool better = j >= 0 && (w == ccmp::kPeakClearance ? ccmp::setpoint_lower(v, j, bv, bj) : ccmp::setpoint_higher(v, j, bv, bj));
-        if (better) { s_v[w][t] = v; s_j[w][t] = j; }
-      }
-      s_n[0][t] += s_n[0][t + m];
-      s_n[1][t] += s_n[1][t + m];
-    }
-    __syncthreads();
-  }
-  if (t < ccmp::kPeaks) {
-    peak[(size_t)f * ccmp::kPeaks + t] = s_v[t][0];
-    peak_tick[(size_t)f * ccmp::kPeaks + t] = s_j[t][0];
-  } else if (t < ccmp::kPeaks + 2) {
-    counts[(size_t)f * 2 + (t - ccmp::kPeaks)] = s_n[t - ccmp::kPeaks][0];
-  } else if (t == ccmp::kPeaks + 2) {
-    stretch[f] = ccmp::setpoint_stretch(s_v[ccmp::kPeakSpeed][0], s_v[ccmp::kPeakAcc][0]);
-  }
+  ccmp_lanes::audit_fold<SetpointsAudit, kThreads>(SetpointsAudit{tau}, lim.vmax, lim.amax, qd, fgap, satisfied, clearance, tick_first, M, margin, peak, peak_tick,
+                                                   counts, stretch);
 }
 
 }  // namespace

@@ -17,6 +17,7 @@
 #include "ccmp_resident.h"
 #include "ccmp_retime.h"
 #include "ccmp_stage.h"
+#include "ccmp_timed.h"
 
 using namespace ccmp_host;
 using ccmp::retime_limits;
@@ -36,34 +37,12 @@ namespace {
 
 constexpr const char *kArenaWhat = "ccmp_path_resample: hipMalloc";
 
-bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
-
 int resample_opts_ok(const ccmp_resample_opts &o)
 {
   if (o.count == 1 || o.count < 0) return CCMP_EINVAL;
   if (o.count == 0 && !(o.spacing > 0.0)) return CCMP_EINVAL; // a NaN spacing fails the comparison
   if (o.max_rows < 2) return CCMP_EINVAL;
   return CCMP_OK;
-}
-
-int limits_ok(const double *vmax, const double *amax, double beta, retime_limits *lim)
-{
-  if (!vmax || !amax || !(beta > 0.0 && beta < 1.0)) return CCMP_EINVAL;
-  for (int c = 0; c < 14; c++) {
-    if (!finite_positive(vmax[c]) || !finite_positive(amax[c])) return CCMP_EINVAL;
-    lim->vmax[c] = vmax[c];
-    lim->amax[c] = amax[c];
-  }
-  lim->beta = beta;
-  return CCMP_OK;
-}
-
-int path_first_ok(const int32_t *path_first, size_t F, size_t total_rows)
-{
-  if (path_first[0] < 0) return CCMP_EINVAL;
-  for (size_t f = 0; f < F; f++)
-    if (path_first[f + 1] < path_first[f]) return CCMP_EINVAL;
-  return (size_t)path_first[F] <= total_rows ? CCMP_OK : CCMP_EINVAL;
 }
 
 // rows out of a path with T > 0, or -1: FULL
@@ -179,7 +158,9 @@ int sampled_copy(ccmp_sampled_paths *h, double *rows_out, int32_t *path_first, d
 int stamps_checks(const double *rows, const int32_t *path_first, size_t F, size_t total_rows, const double *vmax, const double *amax, double beta,
                   const double *time, const double *duration, const int32_t *status, retime_limits *lim)
 {
-  { const int rc = limits_ok(vmax, amax, beta, lim); if (rc != CCMP_OK) return rc; }
+  if (!(beta > 0.0 && beta < 1.0)) return CCMP_EINVAL;
+  { const int rc = limits_ok(vmax, amax, lim->vmax, lim->amax); if (rc != CCMP_OK) return rc; }
+  lim->beta = beta;
   if (total_rows > kMaxRows || F > kMaxRows) return CCMP_EINVAL;
   if (F == 0) return CCMP_OK;
   if (!path_first || !duration || !status || (total_rows && (!rows || !time))) return CCMP_EINVAL;

@@ -2,9 +2,10 @@
 // ccmp_setpoints_ref, ccmp_setpoint_tangents_ref).  The rule is csrc/ccmp_setpoints.h.  A call is one status launch, one read of F status
 // words and F tick counts (they size the result), then the tangent and sample launches, the function, is-satisfied and — with a scene —
 // clearance entry points ONCE each over all ticks of all paths, and the peak launch.  The _ref forms run the same rule text in plain loops.
+// What this unit has in common with the fit and jerk units' host code is csrc/ccmp_timed.h: the argument checks, the staging of the _host
+// form, the tick ranges, the delivery tail (deliver: this unit hands it its tangent + sample and its peak launches) and the _ref loops.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -13,9 +14,9 @@
 #include "ccmp_ctx.h"
 #include "ccmp_launch.h"
 #include "ccmp_resident.h"
-#include "ccmp_scene.h"
 #include "ccmp_setpoints.h"
 #include "ccmp_stage.h"
+#include "ccmp_timed.h"
 
 using namespace ccmp_host;
 using ccmp::setpoint_limits;
@@ -35,44 +36,16 @@ namespace {
 
 constexpr const char *kArenaWhat = "ccmp_path_setpoints: hipMalloc";
 
-bool finite_positive(double v) { return v > 0.0 && v - v == 0.0; }
-
 int opts_ok(const ccmp_setpoint_opts &o) { return finite_positive(o.period) && o.max_ticks >= 2 ? CCMP_OK : CCMP_EINVAL; }
-
-int limits_ok(const double *vmax, const double *amax, setpoint_limits *lim)
-{
-  if (!vmax || !amax) return CCMP_EINVAL;
-  for (int c = 0; c < 14; c++) {
-    if (!finite_positive(vmax[c]) || !finite_positive(amax[c])) return CCMP_EINVAL;
-    lim->vmax[c] = vmax[c];
-    lim->amax[c] = amax[c];
-  }
-  return CCMP_OK;
-}
-
-int path_first_ok(const int32_t *path_first, size_t F, size_t total_rows)
-{
-  if (path_first[0] < 0) return CCMP_EINVAL;
-  for (size_t f = 0; f < F; f++)
-    if (path_first[f + 1] < path_first[f]) return CCMP_EINVAL;
-  return (size_t)path_first[F] <= total_rows ? CCMP_OK : CCMP_EINVAL;
-}
 
 // what every form checks of its arguments (the host and _ref forms check path_first too)
 int input_checks(const double *rows, const int32_t *path_first, const double *time, size_t F, size_t total_rows, const double *vmax, const double *amax,
                  const ccmp_setpoint_opts &o, setpoint_limits *lim)
 {
   { const int rc = opts_ok(o); if (rc != CCMP_OK) return rc; }
-  { const int rc = limits_ok(vmax, amax, lim); if (rc != CCMP_OK) return rc; }
+  { const int rc = limits_ok(vmax, amax, lim->vmax, lim->amax); if (rc != CCMP_OK) return rc; }
   if (total_rows > kMaxRows || F > kMaxRows) return CCMP_EINVAL;
   if (F && (!path_first || (total_rows && (!rows || !time)))) return CCMP_EINVAL;
-  return CCMP_OK;
-}
-
-int device_checks(const ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double margin)
-{
-  { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
-  if (scene && (scene->device != ctx->device || std::isnan(margin))) return CCMP_EINVAL;
   return CCMP_OK;
 }
 
@@ -124,44 +97,25 @@ int setpoints(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, dou
     HIP_TRY(es);
   }
   int64_t M = 0;
-  for (size_t f = 0; f < F; f++) {
-    tick_first[f] = (int32_t)M;
-    const int32_t n = ticks[f];
-    if (n < 0 || n > o.max_ticks) return CCMP_EHIP; // (never: the kernel's count obeys the rule)
-    M += n;
-    if ((uint64_t)M > kMaxRows) return CCMP_EOVERFLOW;
-  }
-  tick_first[F] = (int32_t)M;
+  { const int rc = tick_ranges(F, o.max_ticks, 0, [&](size_t f) { return (int64_t)ticks[f]; }, &tick_first, &M); if (rc != CCMP_OK) return rc; }
+  double *tangent = M ? mem.array<double>((total_rows ? total_rows : 1) * 14) : nullptr;
+  if (!mem.ok()) return CCMP_EHIP;
 
   ccmp_setpoints *h = nullptr;
   { const int rc = make_handle(ctx, F, (size_t)M, &h); if (rc != CCMP_OK) return rc; }
-  int rc = CCMP_OK;
-  hipError_t e = hipMemcpyAsync(h->tick_first, tick_first.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && F) e = hipMemcpyAsync(h->status, d_status, F * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess && M) {
-    const size_t m = (size_t)M;
-    double *tangent = mem.array<double>((total_rows ? total_rows : 1) * 14);
-    if (!mem.ok()) rc = CCMP_EHIP;
-    if (rc == CCMP_OK) e = hipMemsetAsync(h->q, 0, m * 14 * sizeof(double), st); // a tick the sample kernel refuses to trust stays zero
-    if (rc == CCMP_OK && e == hipSuccess) e = hipMemsetAsync(h->qd, 0, m * 14 * sizeof(double), st);
-    if (rc == CCMP_OK && e == hipSuccess) e = hipMemsetAsync(h->tau, 0, m * sizeof(double), st);
-    if (rc == CCMP_OK && e == hipSuccess) e = ccmp_launch::setpoints_tangent(rows, path_first, time, F, total_rows, d_status, tangent, st);
-    if (rc == CCMP_OK && e == hipSuccess)
-      e = ccmp_launch::setpoints_sample(rows, path_first, time, tangent, d_status, h->tick_first, F, m, total_rows, o.period, h->q, h->qd, h->tau,
-                                        h->clearance, st);
-    if (rc == CCMP_OK && e == hipSuccess) rc = ccmp_function_batch(ctx, p, h->q, h->f, m, st); // ONE call each for all ticks of all paths
-    if (rc == CCMP_OK && e == hipSuccess) rc = ccmp_is_satisfied_batch(ctx, p, h->q, h->satisfied, m, st);
-    if (rc == CCMP_OK && e == hipSuccess && scene) rc = ccmp_clearance_batch(ctx, p, scene, h->q, nullptr, m, margin, h->clearance, nullptr, nullptr, st);
-  }
-  if (rc == CCMP_OK && e == hipSuccess && F)
-    e = ccmp_launch::setpoints_peak(h->qd, h->tau, h->f, h->satisfied, h->clearance, h->tick_first, F, (size_t)M, lim, margin, h->peak, h->peak_tick, h->counts,
-                                    h->stretch, st);
-  const hipError_t es = hipStreamSynchronize(st); // the call is synchronous: the host arrays above and the arena go when it returns
-  if (rc == CCMP_OK && e != hipSuccess) rc = hip_fail(e, "ccmp_path_setpoints");
-  if (rc == CCMP_OK && es != hipSuccess) rc = hip_fail(es, "ccmp_path_setpoints: hipStreamSynchronize");
-  if (rc != CCMP_OK) { ccmp_setpoints_destroy(h); return rc; }
-  *out = h;
-  return CCMP_OK;
+  return deliver(
+      ctx, p, scene, margin, h, tick_first, d_status, "ccmp_path_setpoints", st,
+      [&] {
+        const hipError_t e = ccmp_launch::setpoints_tangent(rows, path_first, time, F, total_rows, d_status, tangent, st);
+        return e != hipSuccess ? e
+                               : ccmp_launch::setpoints_sample(rows, path_first, time, tangent, d_status, h->tick_first, F, h->ticks, total_rows, o.period, h->q, h->qd,
+                                                               h->tau, h->clearance, st);
+      },
+      [&] {
+        return ccmp_launch::setpoints_peak(h->qd, h->tau, h->f, h->satisfied, h->clearance, h->tick_first, F, h->ticks, lim, margin, h->peak, h->peak_tick, h->counts,
+                                           h->stretch, st);
+      },
+      out);
 }
 
 int result_copy(ccmp_setpoints *h, double *q, double *qd, double *tau, int32_t *tick_first, double *f, uint8_t *satisfied, double *clearance, int32_t *status,
@@ -238,17 +192,13 @@ int ccmp_path_setpoints_host(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_sc
   if (F) { const int rc = path_first_ok(path_first, F, total_rows); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return CCMP_ENODEV;
-  const size_t R = total_rows ? total_rows : 1;
   CallArena mem(ctx, "ccmp_path_setpoints_host: hipMalloc"); // the staging is memory of this call
-  double *d_rows = mem.array<double>(R * 14), *d_time = mem.array<double>(R);
-  int32_t *d_pf = mem.array<int32_t>(F + 1);
+  const PathStage d(mem, F, total_rows);
   if (!mem.ok()) return CCMP_EHIP;
   StagedCall sg(ctx, __func__);
-  sg.up(d_rows, rows, total_rows * 14 * sizeof(double));
-  sg.up(d_time, time, total_rows * sizeof(double));
-  if (F) sg.up(d_pf, path_first, (F + 1) * sizeof(int32_t));
+  d.up(sg, rows, time, path_first, F, total_rows);
   { const int rc = sg.finish(CCMP_OK); if (rc != CCMP_OK) return rc; }
-  return setpoints(ctx, p, scene, margin, d_rows, d_pf, d_time, F, total_rows, lim, o, out, ctx->stream);
+  return setpoints(ctx, p, scene, margin, d.rows, d.path_first, d.time, F, total_rows, lim, o, out, ctx->stream);
 }
 
 int ccmp_setpoints_info(const ccmp_setpoints *h, size_t *F, size_t *ticks)
@@ -337,40 +287,11 @@ int ccmp_setpoints_ref(const double *rows, const int32_t *path_first, const doub
       memcpy(x.data(), r, 14 * sizeof(double));
       memcpy(x.data() + (N - 1) * 14, r + (R - 1) * 14, 14 * sizeof(double));
       at[N - 1] = D;
-      for (size_t j = 1; j + 1 < N; j++) {
-        at[j] = ccmp::setpoint_tau((int64_t)j, o.period, D);
-        int k;
-        double u;
-        bool lower;
-        ccmp::arc_bracket(t, (int)R, at[j], &k, &u, &lower);
-        const double h = t[k] - t[k - 1];
-        for (int c = 0; c < 14; c++) {
-          const size_t ia = (size_t)(k - 1) * 14 + c, ib = ia + 14;
-          x[j * 14 + c] = ccmp::setpoint_q(r[ia], r[ib], w[ia], w[ib], h, u);
-          xd[j * 14 + c] = ccmp::setpoint_qd(r[ia], r[ib], w[ia], w[ib], h, u);
-        }
-      }
+      for (size_t j = 1; j + 1 < N; j++) (void)ref_tick(r, w.data(), t, R, (int64_t)j, (int64_t)N, o.period, D, &at[j], &x[j * 14], &xd[j * 14]);
     }
-    // the speed and acceleration peaks: ticks in order, so the first tick of a tie stays
     double pv[2] = {0.0, 0.0};
     int32_t pj[2] = {-1, -1};
-    for (size_t j = 0; j < N; j++) {
-      const double width = j + 1 < N ? at[j + 1] - at[j] : 0.0;
-      double speed = 0.0, acc = 0.0;
-      bool speed_nan = false, acc_nan = false;
-      for (int c = 0; c < 14; c++) {
-        const double s = ccmp::setpoint_speed(xd[j * 14 + c], lim.vmax[c]);
-        speed_nan = speed_nan || s != s;
-        if (s > speed) speed = s;
-        if (width > 0.0) {
-          const double ac = ccmp::setpoint_acc(xd[j * 14 + c], xd[(j + 1) * 14 + c], width, lim.amax[c]);
-          acc_nan = acc_nan || ac != ac;
-          if (ac > acc) acc = ac;
-        }
-      }
-      if (!speed_nan && ccmp::setpoint_higher(speed, (int32_t)j, pv[0], pj[0])) { pv[0] = speed; pj[0] = (int32_t)j; }
-      if (width > 0.0 && !acc_nan && ccmp::setpoint_higher(acc, (int32_t)j, pv[1], pj[1])) { pv[1] = acc; pj[1] = (int32_t)j; }
-    }
+    speed_acc_peaks(xd.data(), (int64_t)N, [&](int64_t j) { return at[j + 1] - at[j]; }, lim.vmax, lim.amax, pv, pj);
     if (q && N) memcpy(q + g0 * 14, x.data(), N * 14 * sizeof(double));
     if (qd && N) memcpy(qd + g0 * 14, xd.data(), N * 14 * sizeof(double));
     if (tau && N) memcpy(tau + g0, at.data(), N * sizeof(double));

@@ -146,6 +146,34 @@ CCMP_HD double setpoint_qd(double ra, double rb, double wa, double wb, double h,
   return t12 + t3;
 }
 
+/* Tick j of the N of an OK path on its stamps t [R], D = t[R-1]: *tau, and for j >= 1 the bracket (*k - 1, *k) of tau with its parameter *u.
+ * Tick 0 has tau = +0.0 and no bracket (*k = 0); the last tick has tau = D and the bracket D lies in, for a caller that folds by row
+ * interval.  False: the rule's own precondition of the bracket fails (an OK path meets it) and no stamp has been read.  The one text of
+ * "a tick of the interpolant" for the setpoints, fit and jerk units, on the device and in their _ref forms. */
+CCMP_HD bool setpoint_bracket(const double *t, int R, int64_t j, int64_t N, double period, double D, double *tau, int *k, double *u)
+{
+  *tau = 0.0;
+  *k = 0;
+  *u = 0.0;
+  if (j <= 0) return true;
+  const double at = j >= N - 1 ? D : setpoint_tau(j, period, D);
+  *tau = at;
+  if (!(at > 0.0) || !(at <= D) || R < 2) return false;
+  bool lower;
+  arc_bracket(t, R, at, k, u, &lower);
+  return true;
+}
+
+/* one joint's q and qd at the parameter u of the bracket (k - 1, k): r and w are the path's rows and tangents from that joint's element of
+ * row 0 on, t the path's stamps.  A caller that needs one of the two hands the other a dummy: the text is inlined and the dead half goes. */
+CCMP_HD void setpoint_joint(const double *r, const double *w, const double *t, int k, double u, double *q, double *qd)
+{
+  const double h = t[k] - t[k - 1];
+  const size_t a = (size_t)(k - 1) * 14, b = a + 14;
+  *q = setpoint_q(r[a], r[b], w[a], w[b], h, u);
+  *qd = setpoint_qd(r[a], r[b], w[a], w[b], h, u);
+}
+
 /* one joint's shares of the speed and acceleration ratios; width = tau_{j+1} - tau_j > 0 */
 CCMP_HD double setpoint_speed(double qd, double vmax) { return ccmp_abs(qd) / vmax; }
 CCMP_HD double setpoint_acc(double qd_a, double qd_b, double width, double amax)

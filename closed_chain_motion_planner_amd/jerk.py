@@ -8,10 +8,10 @@ clearance figures of the same call say whether that matters); it is not a jerk-o
 import ctypes as C
 
 from . import _lib
-from ._arrays import HOST, _torch, kind_of
+from ._arrays import HOST, kind_of
 from ._lib import CcmpJerkOpts, check
 from .retime import _limits
-from .setpoints import _inputs
+from .setpoints import _collect, _inputs
 from .shortcut import _args
 
 __all__ = ["jerk_setpoints_ref", "jerk_next_window_ref", "JERK_STATUS", "JERK_PEAKS"]
@@ -55,9 +55,6 @@ def jerk_next_window_ref(W, P, aim=0.95, max_window=64):
     return nxt.value
 
 
-_COPY_ORDER = ("q", "qd", "tau", "tick_first", "f", "satisfied", "clearance", "status", "window", "passes", "peak", "peak_tick", "counts")
-
-
 def jerk_setpoints(ctx, problem, rows, path_first, time, vmax, amax, jmax, period, max_ticks, window, max_window, aim, tile_ticks, scene, margin, stream):
     """the body of `KinematicChainConstraint.jerk_setpoint_paths`"""
     K = kind_of(rows)
@@ -69,19 +66,7 @@ def jerk_setpoints(ctx, problem, rows, path_first, time, vmax, amax, jmax, perio
     K.call("ccmp_path_jerk_setpoints", "ccmp_path_jerk_setpoints_host", ctx.handle, C.byref(problem), scene._h if scene is not None else None, float(margin),
            K.arg(r, empty_is_null=True), K.arg(pf), K.arg(t, empty_is_null=True), F, R, HOST.arg(v), HOST.arg(a), HOST.arg(j), C.byref(o), C.byref(h),
            stream=stream)
-    try:
-        nF, ticks = C.c_size_t(0), C.c_size_t(0)
-        check(_lib.lib().ccmp_jerk_setpoints_info(h, C.byref(nF), C.byref(ticks)), "ccmp_jerk_setpoints_info")
-        M = int(ticks.value)
-        out = {"q": K.empty((M, 14), "float64"), "qd": K.empty((M, 14), "float64"), "tau": K.empty((M,), "float64"), "tick_first": K.empty((F + 1,), "int32"),
-               "f": K.empty((M, 2), "float64"), "satisfied": K.empty((M,), "uint8"), "clearance": K.empty((M,), "float64"), "status": K.empty((F,), "int32"),
-               "window": K.empty((F,), "int32"), "passes": K.empty((F,), "int32"), "peak": K.empty((F, 6), "float64"), "peak_tick": K.empty((F, 6), "int32"),
-               "counts": K.empty((F, 2), "int32")}
-        K.call("ccmp_jerk_setpoints_copy", "ccmp_jerk_setpoints_copy_host", h, *_args(K, *[out[n] for n in _COPY_ORDER]), stream=stream)
-        if K is not HOST:  # the handle goes below: its arrays must have left it first
-            torch = _torch()
-            (torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(stream) if isinstance(stream, int) else stream).synchronize()
-        out["ticks"] = M
-        return out
-    finally:
-        _lib.lib().ccmp_jerk_setpoints_destroy(h)
+    return _collect(K, h, "ccmp_jerk_setpoints", lambda M: {
+        "q": ((M, 14), "float64"), "qd": ((M, 14), "float64"), "tau": ((M,), "float64"), "tick_first": ((F + 1,), "int32"), "f": ((M, 2), "float64"),
+        "satisfied": ((M,), "uint8"), "clearance": ((M,), "float64"), "status": ((F,), "int32"), "window": ((F,), "int32"), "passes": ((F,), "int32"),
+        "peak": ((F, 6), "float64"), "peak_tick": ((F, 6), "int32"), "counts": ((F, 2), "int32")}, stream)

@@ -58,7 +58,23 @@ def setpoints_ref(rows, path_first, time, vmax, amax, period=0.001, max_ticks=65
     return out
 
 
-_COPY_ORDER = ("q", "qd", "tau", "tick_first", "f", "satisfied", "clearance", "status", "peak", "peak_tick", "counts", "stretch")
+def _collect(K, h, prefix, arrays, stream):
+    """what follows a call that answered with the result handle h of the C type `prefix` (this unit's and the jerk unit's): its info, the
+    arrays allocated by name — arrays(ticks) -> {name: (shape, dtype)} in the order `prefix`_copy takes them —, copied, the stream waited
+    for, and the handle destroyed whatever happened"""
+    try:
+        nF, ticks = C.c_size_t(0), C.c_size_t(0)
+        check(getattr(_lib.lib(), prefix + "_info")(h, C.byref(nF), C.byref(ticks)), prefix + "_info")
+        M = int(ticks.value)
+        out = {n: K.empty(shape, dtype) for n, (shape, dtype) in arrays(M).items()}
+        K.call(prefix + "_copy", prefix + "_copy_host", h, *_args(K, *out.values()), stream=stream)
+        if K is not HOST:  # the handle goes below: its arrays must have left it first
+            torch = _torch()
+            (torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(stream) if isinstance(stream, int) else stream).synchronize()
+        out["ticks"] = M
+        return out
+    finally:
+        getattr(_lib.lib(), prefix + "_destroy")(h)
 
 
 def setpoints(ctx, problem, rows, path_first, time, vmax, amax, period, max_ticks, scene, margin, stream):
@@ -70,18 +86,7 @@ def setpoints(ctx, problem, rows, path_first, time, vmax, amax, period, max_tick
     h = C.c_void_p()
     K.call("ccmp_path_setpoints", "ccmp_path_setpoints_host", ctx.handle, C.byref(problem), scene._h if scene is not None else None, float(margin),
            K.arg(r, empty_is_null=True), K.arg(pf), K.arg(t, empty_is_null=True), F, R, HOST.arg(v), HOST.arg(a), C.byref(o), C.byref(h), stream=stream)
-    try:
-        nF, ticks = C.c_size_t(0), C.c_size_t(0)
-        check(_lib.lib().ccmp_setpoints_info(h, C.byref(nF), C.byref(ticks)), "ccmp_setpoints_info")
-        M = int(ticks.value)
-        out = {"q": K.empty((M, 14), "float64"), "qd": K.empty((M, 14), "float64"), "tau": K.empty((M,), "float64"), "tick_first": K.empty((F + 1,), "int32"),
-               "f": K.empty((M, 2), "float64"), "satisfied": K.empty((M,), "uint8"), "clearance": K.empty((M,), "float64"), "status": K.empty((F,), "int32"),
-               "peak": K.empty((F, 5), "float64"), "peak_tick": K.empty((F, 5), "int32"), "counts": K.empty((F, 2), "int32"), "stretch": K.empty((F,), "float64")}
-        K.call("ccmp_setpoints_copy", "ccmp_setpoints_copy_host", h, *_args(K, *[out[n] for n in _COPY_ORDER]), stream=stream)
-        if K is not HOST:  # the handle goes below: its arrays must have left it first
-            torch = _torch()
-            (torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(stream) if isinstance(stream, int) else stream).synchronize()
-        out["ticks"] = M
-        return out
-    finally:
-        _lib.lib().ccmp_setpoints_destroy(h)
+    return _collect(K, h, "ccmp_setpoints", lambda M: {
+        "q": ((M, 14), "float64"), "qd": ((M, 14), "float64"), "tau": ((M,), "float64"), "tick_first": ((F + 1,), "int32"), "f": ((M, 2), "float64"),
+        "satisfied": ((M,), "uint8"), "clearance": ((M,), "float64"), "status": ((F,), "int32"), "peak": ((F, 5), "float64"), "peak_tick": ((F, 5), "int32"),
+        "counts": ((F, 2), "int32"), "stretch": ((F,), "float64")}, stream)
