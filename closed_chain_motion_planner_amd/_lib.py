@@ -100,6 +100,33 @@ class CcmpJerkOpts(C.Structure):
     _fields_ = [("period", C.c_double), ("max_ticks", C.c_int), ("window", C.c_int), ("max_window", C.c_int), ("aim", C.c_double), ("tile_ticks", C.c_int)]
 
 
+class CcmpPlanOpts(C.Structure):
+    """ccmp_plan_opts of include/ccmp.h"""
+    _fields_ = [("width", C.c_int32), ("k", C.c_int32), ("attempts", C.c_int32), ("max_states", C.c_int32), ("t", C.c_double), ("sigma", C.c_double),
+                ("inflate", C.c_double), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("max_vertices", C.c_uint64)]
+
+
+class CcmpPlanCounters(C.Structure):
+    """ccmp_plan_counters of include/ccmp.h"""
+    _fields_ = [(n, C.c_int32) for n in ("proposals", "valid_proposals", "ik_successes", "vertices_kept", "mid_stones", "unsettled", "checks", "goal_pushes",
+                                         "start_pushes", "ladder_vertices", "push_refused", "reserved")]
+
+
+class CcmpPlanState(C.Structure):
+    """ccmp_plan_state of include/ccmp.h"""
+    _fields_ = [("n_starts", C.c_int32), ("n_goals", C.c_int32), ("starts", C.c_int32 * 8), ("goals", C.c_int32 * 8), ("nearest", C.c_int32),
+                ("sprevious", C.c_int32), ("status", C.c_int32), ("cycle", C.c_int32), ("solved_start", C.c_int32), ("solved_goal", C.c_int32),
+                ("size_at_check", C.c_int32), ("reserved", C.c_int32), ("next_index", C.c_uint64), ("nearest_pose", C.c_double * 8),
+                ("prev_from_goal", C.c_double), ("prev_from_start", C.c_double), ("counters", CcmpPlanCounters)]
+
+
+class CcmpPlanReport(C.Structure):
+    """ccmp_plan_report of include/ccmp.h"""
+    _fields_ = [("status", C.c_int32), ("cycles_run", C.c_int32), ("cycles_total", C.c_int32), ("reserved", C.c_int32), ("size", C.c_uint64),
+                ("edges", C.c_uint64), ("solved_start", C.c_int32), ("solved_goal", C.c_int32), ("nearest", C.c_int32), ("reserved2", C.c_int32),
+                ("prev_from_goal", C.c_double), ("prev_from_start", C.c_double), ("counters", CcmpPlanCounters)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -142,6 +169,8 @@ EXPORTS = [
     "ccmp_fit_opts_default", "ccmp_path_fit_timestamps", "ccmp_path_fit_timestamps_host", "ccmp_path_fit_timestamps_ref",
     "ccmp_jerk_opts_default", "ccmp_path_jerk_setpoints", "ccmp_path_jerk_setpoints_host", "ccmp_jerk_setpoints_info", "ccmp_jerk_setpoints_copy",
     "ccmp_jerk_setpoints_copy_host", "ccmp_jerk_setpoints_destroy", "ccmp_jerk_setpoints_ref", "ccmp_jerk_next_window_ref",
+    "ccmp_plan_default_opts", "ccmp_plan_create", "ccmp_plan_run", "ccmp_plan_state_read", "ccmp_plan_destroy", "ccmp_plan_check_ref", "ccmp_plan_prefix_ref",
+    "ccmp_plan_connected_ref",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -381,6 +410,14 @@ def lib():
         "ccmp_jerk_setpoints_destroy": ([vp], None),
         "ccmp_jerk_next_window_ref": ([C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "ccmp_jerk_setpoints_ref": ([dp, i32p, dp, C.c_size_t, C.c_size_t, dp, dp, dp, C.POINTER(CcmpJerkOpts), i32p, i32p, i32p, i32p, dp, dp, dp, dp, i32p], C.c_int),
+        "ccmp_plan_default_opts": ([C.POINTER(CcmpPlanOpts)], None),
+        "ccmp_plan_create": ([vp, pp, vp, vp, C.c_double, C.POINTER(CcmpIkOpts), C.POINTER(CcmpPlanOpts), dp, C.c_uint64, C.c_uint64, C.POINTER(vp)], C.c_int),
+        "ccmp_plan_run": ([vp, C.c_int, C.POINTER(CcmpPlanReport)], C.c_int),
+        "ccmp_plan_state_read": ([vp, C.POINTER(CcmpPlanState)], C.c_int),
+        "ccmp_plan_destroy": ([vp], None),
+        "ccmp_plan_check_ref": ([C.POINTER(CcmpPlanState), C.c_size_t, i32p, dp, dp, i32p, dp, dp, dp, i32p], C.c_int),
+        "ccmp_plan_prefix_ref": ([u8p, u8p, u8p, i32p], C.c_int),
+        "ccmp_plan_connected_ref": ([i32p, C.c_size_t, C.POINTER(CcmpPlanState)], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -426,6 +463,8 @@ GROW_TRAPPED, GROW_SREACHED, GROW_GREACHED, GROW_UNSETTLED = range(4)  # ccmp.h:
 COMMIT_KEEP_ISOLATED = 1  # ccmp.h: CCMP_COMMIT_*
 GRAPH_MAX_ROOTS, CLOSEST_MAX_FROM = 32, 64  # ccmp.h: CCMP_GRAPH_MAX_ROOTS, CCMP_CLOSEST_MAX_FROM
 PATH_MAX_PAIRS = 64  # ccmp.h: CCMP_PATH_MAX_PAIRS
+PLAN_OPEN, PLAN_SOLVED, PLAN_BUDGET, PLAN_FULL, PLAN_INVALID_GOAL = range(5)  # ccmp.h: CCMP_PLAN_*
+PLAN_MAX_STARTS, PLAN_MAX_GOALS, PLAN_MAX_WIDTH, PLAN_LADDER = 8, 8, 256, 9  # ccmp.h: CCMP_PLAN_MAX_*, CCMP_PLAN_LADDER
 DENSE_DISTINCT = 1  # ccmp.h: CCMP_DENSE_DISTINCT
 SHORTCUT_MAX_LEN = 1024  # ccmp.h: CCMP_SHORTCUT_MAX_LEN
 RETIME_OK, RETIME_EMPTY, RETIME_BROKEN, RETIME_NONFINITE, RETIME_POINT, RETIME_FULL = range(6)  # ccmp.h: CCMP_RETIME_*

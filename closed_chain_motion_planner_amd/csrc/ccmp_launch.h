@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 struct ccmp_consts;
+struct ccmp_plan_state;
 namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; struct retime_limits; struct setpoint_limits; struct jerk_limits; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
@@ -201,6 +202,17 @@ struct GraphPath {
   int max_len;
   double *cost; int32_t *path_len, *path; // [F], [F], [F][max_len]
   double *path_joints, *path_poses;       // [F][max_len][14], [F][max_len][8]; nullable
+};
+
+/* one check of the planner's loop (csrc/ccmp_plan.h): ccmp_roadmap_closest's arrays of both sides (a: from starts towards goals[0], b: from
+ * goals towards starts[0]), the goal and start poses by value, and what the kernel writes for the IK call that follows */
+struct PlanCheck {
+  const int32_t *a_idx; const double *a_dist, *a_from;
+  const int32_t *b_idx; const double *b_dist, *b_from;
+  double goal[8], start[8];
+  double *targets; // [11][8]: goal, ladder 1 .. 9, start; a NaN row where the branch did not fire
+  double *seeds;   // [11][14]
+  int32_t *trig;   // [4]
 };
 
 #pragma GCC visibility push(hidden)
@@ -426,6 +438,18 @@ hipError_t clearance(const ccmp_consts *K, const ccmp::scene_dev *scene, int n_s
                      unsigned int done_seq, hipStream_t st);
 hipError_t resident(int stock, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st);
 hipError_t resident_row16(int diag, void *box_dev, unsigned long long last_tag, unsigned long long idle_ticks, hipStream_t st);
+/* the planner's loop (ccmp_plan_*; csrc/ccmp_plan.h, ccmp_kernels_plan.hip): one block each, on the state block of the handle */
+hipError_t plan_front(const ccmp_plan_state *state, double *from, size_t W, hipStream_t st);
+/* a growth step's outputs (ladder == 0: all counters, proposals += W, next_index += W) or a ladder's new_index [W] (ladder == 1) */
+hipError_t plan_tally(ccmp_plan_state *state, const int32_t *which, const uint8_t *ik_ok, const int32_t *new_index, const int32_t *mid_index,
+                      const int32_t *grow_state, size_t W, int k, int ladder, hipStream_t st);
+hipError_t plan_check(const GraphStore &s, ccmp_plan_state *state, const PlanCheck &c, hipStream_t st);
+/* valid [9], ik_ok [11] (goal, ladder, start) -> vertex_ok [9], summary [4] = {prefix length, goal solved, start solved, the check ran} */
+hipError_t plan_prefix(const ccmp_plan_state *state, const int32_t *trig, const uint8_t *valid, const uint8_t *ik_ok, uint8_t *vertex_ok, int32_t *summary,
+                       hipStream_t st);
+hipError_t plan_push(ccmp_plan_state *state, int which, const int32_t *new_index, hipStream_t st);
+/* cycle += bump_cycle, then the solution test on the store's labels */
+hipError_t plan_connected(const GraphStore &s, ccmp_plan_state *state, int bump_cycle, hipStream_t st);
 // lib/libccmp_debug.so only (ccmp_kernels_debug.hip)
 hipError_t detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
 hipError_t div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);

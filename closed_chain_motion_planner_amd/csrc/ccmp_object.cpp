@@ -13,6 +13,7 @@
 #include "ccmp_ctx.h"
 #include "ccmp_launch.h"
 #include "ccmp_object.h"
+#include "ccmp_plan.h"
 #include "ccmp_resident.h"
 #include "ccmp_stage.h"
 
@@ -299,3 +300,8 @@ int ccmp_object_propose_host(ccmp_ctx *ctx, const ccmp_object *obj, const double
 }
 
 }  // extern "C"
+
+// what the planner's loop (ccmp_plan.cpp; declared in ccmp_plan.h) checks of an object before its first launch
+namespace ccmp_host {
+int object_device(const ccmp_object *obj) { return obj->device; }
+}  // namespace ccmp_host

@@ -25,6 +25,7 @@
 #include "ccmp_ik.h"
 #include "ccmp_launch.h"
 #include "ccmp_path.h"
+#include "ccmp_plan.h"
 #include "ccmp_policy.h"
 #include "ccmp_pose.h"
 #include "ccmp_resident.h"
@@ -1160,3 +1161,9 @@ int ccmp_graph_shortest_paths_ref(const int32_t *uv, const double *w, size_t E, 
 }
 
 }  // extern "C"
+
+// what the planner's loop (ccmp_plan.cpp; declared in ccmp_plan.h) needs of a store: its arrays as they stand, and its context
+namespace ccmp_host {
+void roadmap_arrays(const ccmp_roadmap *rm, ccmp_launch::GraphStore *out) { *out = graph_store(rm); }
+ccmp_ctx *roadmap_ctx(const ccmp_roadmap *rm) { return rm->ctx; }
+}  // namespace ccmp_host

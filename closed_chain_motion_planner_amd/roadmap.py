@@ -19,7 +19,8 @@ from .ik import ik_options
 from .object import DEFAULT_HI, DEFAULT_LO
 
 __all__ = ["Roadmap", "pose_distance", "pose_from_t_wo", "joint_distance", "graph_labels_ref", "commit_ref", "closest_ref", "shortest_paths_ref", "METRIC_JOINT", "METRIC_OBJECT",
-           "GROW_TRAPPED", "GROW_SREACHED", "GROW_GREACHED", "GROW_UNSETTLED", "COMMIT_KEEP_ISOLATED"]
+           "GROW_TRAPPED", "GROW_SREACHED", "GROW_GREACHED", "GROW_UNSETTLED", "COMMIT_KEEP_ISOLATED", "Plan", "PLAN_STATUS", "plan_options", "plan_check_ref",
+           "plan_prefix_ref", "plan_connected_ref"]
 
 _arg = HOST.arg
 
@@ -137,6 +138,123 @@ def _edge_outputs(K, E, ms):
     """what the traversals of E edges leave, as `connect` and `grow` end their argument lists"""
     return {"states": K.empty((E, ms, 14), "float64"), "n_states": K.empty((E,), "int32"), "ok": K.empty((E,), "uint8"), "newton_iters": K.empty((E,), "int32"),
             "blocked": K.empty((E,), "uint8"), "carry": K.empty((E, 2), "float64")}
+
+
+# ---- the planner's loop on the store (include/ccmp.h: ccmp_plan_*; the rule: csrc/ccmp_plan.h) -------------------------------------------
+PLAN_STATUS = {_lib.PLAN_OPEN: "OPEN", _lib.PLAN_SOLVED: "SOLVED", _lib.PLAN_BUDGET: "BUDGET", _lib.PLAN_FULL: "FULL", _lib.PLAN_INVALID_GOAL: "INVALID_GOAL"}
+_PLAN_COUNTERS = [n for n, _ in _lib.CcmpPlanCounters._fields_ if n != "reserved"]
+
+
+def plan_options(**kw):
+    """ccmp_plan_opts with the library's defaults (width 32, k 5, attempts 2, max_states 64, t 0.3, sigma 0.2, inflate 0, lo / hi
+    -1e30 / 1e30, max_vertices 2^31 - 1), fields overridden by keyword"""
+    o = _lib.CcmpPlanOpts()
+    _lib.lib().ccmp_plan_default_opts(C.byref(o))
+    for name, v in kw.items():
+        if name not in dict(_lib.CcmpPlanOpts._fields_):
+            raise TypeError("ccmp_plan_opts has no field %r" % name)
+        if name in ("lo", "hi"):
+            getattr(o, name)[:] = [float(x) for x in v]
+        else:
+            setattr(o, name, v)
+    return o
+
+
+def _plan_state_dict(s):
+    """a ccmp_plan_state as a dict of plain values (starts / goals cut to their lengths)"""
+    d = {n: getattr(s, n) for n in ("nearest", "sprevious", "status", "cycle", "solved_start", "solved_goal", "size_at_check", "next_index", "prev_from_goal",
+                                     "prev_from_start")}
+    d.update(starts=list(s.starts[:s.n_starts]), goals=list(s.goals[:s.n_goals]), nearest_pose=list(s.nearest_pose),
+             counters={n: getattr(s.counters, n) for n in _PLAN_COUNTERS})
+    return d
+
+
+def _plan_state_struct(d):
+    s = _lib.CcmpPlanState()
+    for n in ("nearest", "sprevious", "status", "cycle", "solved_start", "solved_goal", "size_at_check", "next_index", "prev_from_goal", "prev_from_start"):
+        setattr(s, n, d[n])
+    s.n_starts, s.n_goals = len(d["starts"]), len(d["goals"])
+    s.starts[:s.n_starts], s.goals[:s.n_goals] = [int(v) for v in d["starts"]], [int(v) for v in d["goals"]]
+    s.nearest_pose[:] = [float(v) for v in d["nearest_pose"]]
+    for n in _PLAN_COUNTERS:
+        setattr(s.counters, n, int(d["counters"].get(n, 0)))
+    return s
+
+
+def _closest3(a, n):
+    if a is None:
+        return (None, None, None) if n == 0 else (np.full(n, -1, dtype=np.int32), np.full(n, np.inf), np.full(n, np.nan))
+    return HOST.expect(a[0], "int32", n, "idx"), HOST.expect(a[1], "float64", n, "dist"), HOST.expect(a[2], "float64", n, "from_dist")
+
+
+def plan_check_ref(state, size, a, b, store_poses=None):
+    """ccmp_plan_check_ref: the check of the planner's loop (the gate, the carry rule of both sides, the thresholds, the state update) on
+    a state dict as `Plan.state` returns it — a = `closest`'s (idx, dist, from_dist) for starts towards goals[0], b = the same for goals
+    towards starts[0]; store_poses (size, 8): nearest_pose follows.  Returns (the new state, triggers [ran, goal side fired, start side
+    fired, the goal side's vertex or -1]); host only."""
+    s = _plan_state_struct(state)
+    ai, ad, af = _closest3(a, s.n_starts)
+    bi, bd, bf = _closest3(b, s.n_goals)
+    sp = None if store_poses is None else HOST.expect(store_poses, "float64", int(size) * 8, "store_poses")
+    trig = np.zeros(4, dtype=np.int32)
+    check(_lib.lib().ccmp_plan_check_ref(C.byref(s), int(size), _arg(ai), _arg(ad), _arg(af), _arg(bi), _arg(bd), _arg(bf), _arg(sp), _arg(trig)), "ccmp_plan_check_ref")
+    return _plan_state_dict(s), [int(t) for t in trig]
+
+
+def plan_prefix_ref(valid, ik_ok):
+    """ccmp_plan_prefix_ref: the ladder's prefix — (vertex_ok (9,) uint8, its length) from valid (9,) and ik_ok (9,); host only"""
+    v, k = HOST.expect(valid, "uint8", 9, "valid"), HOST.expect(ik_ok, "uint8", 9, "ik_ok")
+    out, n = np.zeros(9, dtype=np.uint8), C.c_int32()
+    check(_lib.lib().ccmp_plan_prefix_ref(_arg(v), _arg(k), _arg(out), C.byref(n)), "ccmp_plan_prefix_ref")
+    return out, int(n.value)
+
+
+def plan_connected_ref(labels, state):
+    """ccmp_plan_connected_ref: the solution test — the first pair (s, g), start-major, whose labels agree makes the state SOLVED with
+    that pair.  Returns the new state; host only."""
+    lab = HOST.expect(labels, "int32", -1, "labels")
+    s = _plan_state_struct(state)
+    check(_lib.lib().ccmp_plan_connected_ref(_arg(lab), len(lab), C.byref(s)), "ccmp_plan_connected_ref")
+    return _plan_state_dict(s)
+
+
+class Plan:
+    """ccmp_plan: the planner's loop on a `Roadmap` (`Roadmap.plan` opens one).  `run(max_cycles)` runs cycles until the status is SOLVED,
+    FULL or the cycles are spent (BUDGET: run again to resume) and returns the report, also kept as `.report`: a dict with status (a
+    PLAN_STATUS key; `status_name` its text), cycles_run, cycles_total, size, edges, solved (start vertex, goal vertex) or None, nearest,
+    prev_from_goal, prev_from_start and counters.  The path of a SOLVED plan is `Roadmap.shortest_paths([s], [g])` on that pair."""
+
+    def __init__(self, roadmap, checker, scene, handle):
+        self.roadmap, self.checker, self.scene, self._h = roadmap, checker, scene, handle  # the store, the object and the scene outlive the handle
+        self.report = None
+        self.run(0)
+
+    def run(self, max_cycles):
+        r = _lib.CcmpPlanReport()
+        check(_lib.lib().ccmp_plan_run(self._h, int(max_cycles), C.byref(r)), "ccmp_plan_run")
+        self.report = {"status": r.status, "status_name": PLAN_STATUS.get(r.status, "?"), "cycles_run": r.cycles_run, "cycles_total": r.cycles_total,
+                       "size": int(r.size), "edges": int(r.edges), "solved": (r.solved_start, r.solved_goal) if r.status == _lib.PLAN_SOLVED else None,
+                       "nearest": r.nearest, "prev_from_goal": r.prev_from_goal, "prev_from_start": r.prev_from_start,
+                       "counters": {n: getattr(r.counters, n) for n in _PLAN_COUNTERS}}
+        return self.report
+
+    def state(self):
+        """the planner's state block (ccmp_plan_state) as a dict: starts, goals, nearest, nearest_pose, sprevious, prev_from_goal,
+        prev_from_start, size_at_check, next_index, cycle, status, solved_start, solved_goal, counters"""
+        s = _lib.CcmpPlanState()
+        check(_lib.lib().ccmp_plan_state_read(self._h, C.byref(s)), "ccmp_plan_state_read")
+        return _plan_state_dict(s)
+
+    def close(self):
+        if self._h:
+            _lib.lib().ccmp_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Roadmap:
@@ -569,6 +687,27 @@ class Roadmap:
             sp = constraint.setpoint_paths(sampled["joints"], sampled["path_first"], time, vmax, amax, period=period, max_ticks=max_ticks,
                                            scene=audit_scene, margin=audit_margin)
         return (sp,) + tuple(sol) + fitted
+
+    def plan(self, constraint, checker, goal_joints=None, scene=None, margin=0.0, width=32, k=5, max_cycles=0, rng_seed=0, first_index=0, ik_opts=None,
+             **opts):
+        """The planner's loop on this store (ccmp_plan_create: stefanBiPRM::solve as include/ccmp.h states it): opens a `Plan` from
+        `constraint`'s problem — start state problem.start_joint, start and goal object poses obj_start_* / obj_goal_* — and `checker` (an
+        `ObjectChecker`); goal_joints (14,): the goal state, else the pose IK towards the goal pose seeded from the start state; scene /
+        margin: the proxy scene the IK vets against and the traversals test (the vetted forms).  width candidates per growth step, k
+        neighbours; opts: the other fields of ccmp_plan_opts (attempts, max_states, t, sigma, inflate, lo, hi, max_vertices).  Runs
+        max_cycles cycles (0: open only) and returns the `Plan`; `Plan.run` resumes it."""
+        constraint._need_problem()
+        o = plan_options(width=int(width), k=int(k), **opts)
+        gj = None if goal_joints is None else HOST.expect(np.asarray(goal_joints.cpu() if hasattr(goal_joints, "cpu") else goal_joints, dtype=np.float64), "float64", 14,
+                                                         "goal_joints")
+        h = C.c_void_p()
+        check(_lib.lib().ccmp_plan_create(self._h, C.byref(constraint.problem), checker._h, scene._h if scene is not None else None, float(margin),
+                                          C.byref(ik_opts) if ik_opts is not None else None, C.byref(o), _arg(gj), int(rng_seed), int(first_index), C.byref(h)),
+              "ccmp_plan_create")
+        pl = Plan(self, checker, scene, h)
+        if max_cycles:
+            pl.run(max_cycles)
+        return pl
 
     def close(self):
         if self._h:

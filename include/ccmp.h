@@ -1463,6 +1463,117 @@ int ccmp_jerk_setpoints_ref(const double *rows, const int32_t *path_first, const
                             int32_t *passes, double *q, double *qd, double *tau, double *peak, int32_t *peak_tick);
 int ccmp_jerk_next_window_ref(int W, double P, double aim, int max_window, int *next);
 
+/* ---- the planner's loop on the store: stefanBiPRM::solve as one resumable object ------------------------------------------------------- */
+/* stefanBiPRM::solve / constructRoadmap / checkForSolution (stefanBiPRM.cpp:692-899) and the start and goal set-up of
+ * ConstrainedPlanningCommon.cpp:147-207 over the calls above: a ccmp_plan takes (the problem's start state, its goal object pose) and
+ * grows the store until a start vertex and a goal vertex share a component.  The reference runs constructRoadmap and checkForSolution
+ * as two racing threads; this unit states their STRUCTURE as one deterministic sequence, not their interleaving: the result is a
+ * function of the arguments and rng_seed alone.  csrc/ccmp_plan.h states the rule once, for the kernels of ccmp_kernels_plan.hip and
+ * for the *_ref forms.  The planner's state (ccmp_plan_state) lives on the device; a cycle costs the host one read of it, the commits'
+ * own read-backs, and one 16-byte read in a cycle whose check ran.
+ *   open (ccmp_plan_create)   the start vertex (p->start_joint, the pose of p->obj_start_*) goes through startgoalMilestone:
+ *       ccmp_roadmap_connect on the object metric with check_target = 1 (k neighbours, checkMotion from each), then ccmp_roadmap_commit
+ *       with CCMP_COMMIT_KEEP_ISOLATED (no states: no mid-stones, no slot unsettled by its length).  The goal vertex is goal_joints[14]
+ *       or, when that is NULL, ccmp_pose_ik_* (the vetted form when a scene is given) towards the pose of p->obj_goal_* seeded from the
+ *       start state (one seed slot, draw index next_index); no solution: status CCMP_PLAN_INVALID_GOAL and nothing more is appended.  It
+ *       goes through startgoalMilestone too, with the goal pose as its pose row.  next_index = first_index + 1 afterwards, in both cases.
+ *       prev_from_goal = prev_from_start = ccmp_pose_distance(start pose, goal pose); nearest = starts[0], nearest_pose = the start
+ *       pose; sprevious = goals[0]; size_at_check = the size after open; then the solution test.
+ *   one cycle (ccmp_plan_run runs up to max_cycles of them)
+ *     0. FULL       size + width (1 + k) + 11 > max_vertices: status CCMP_PLAN_FULL, nothing runs.
+ *     1. growth     ccmp_object_propose_batch from nearest_pose (width rows) towards the goal pose with t, sigma, lo, hi, attempts,
+ *                   inflate, draw indices next_index .. next_index + width - 1; ccmp_roadmap_grow (the vetted form with a scene) on ALL
+ *                   width rows (a row without a valid candidate is NaN: a target without a state) with k, check_target 0, max_states,
+ *                   the same first_index; ccmp_roadmap_commit with vertex_ok = ik_ok, the states, the goal pose and roots = starts.
+ *                   next_index += width.  A query that is UNSETTLED is not continued: it is left out and counted.
+ *     2. check      only if size > size_at_check + 3 (strict).  With (c, d) = closestFromGoal(starts, goals[0]) and (s, d2) =
+ *                   closestFromGoal(goals, starts[0]) — both from ccmp_roadmap_closest on the store as the growth left it, folded by the
+ *                   carry rule: val = +inf; per from f in order: val = min(val, from_dist) (strict <), closest = f, and if idx >= 0 and
+ *                   dist < val (strict) then (closest, val) = (idx, dist) —
+ *                     goal side    d < prev_from_goal - 0.1 (strict; a NaN never passes): nearest = c, nearest_pose = pose[c],
+ *                                  prev_from_goal = d; the goal IK target is the goal pose seeded from joints[c] (with n_goals == 8 it is not
+ *                                  tried and push_refused counts it); the ladder targets are ccmp_pose_interpolate(pose[c], goal, 0.1 i), i =
+ *                                  1 .. 9, seeded from joints[c].
+ *                     start side   sprevious = s; d2 < prev_from_start - 0.1: prev_from_start = d2; the start IK target is the start pose
+ *                                  seeded from joints[s] (n_starts == 8: not tried, counted).
+ *                   size_at_check = size; next_index += 11 (the eleven IK targets take indices next_index .. + 10 in the order goal,
+ *                   ladder 1 .. 9, start, whether or not their branch fired).  Then ccmp_object_valid_batch on the ladder, ONE IK call over
+ *                   the eleven targets (one seed slot each), the ladder's PREFIX = the longest run from i = 1 in which every pose is valid
+ *                   and solved, and in this order: the goal vertex through startgoalMilestone and onto goals; the prefix through addMilestone
+ *                   (ccmp_roadmap_connect with check_target 1, commit without KEEP_ISOLATED) as ONE batch; the start vertex through
+ *                   startgoalMilestone and onto starts.  With n_goals == 0 neither side fires.
+ *     3. cycle += 1, then the solution test: the first pair (s, g), start-major and goal-minor, with label[starts[s]] == label[goals[g]]
+ *                   gives status CCMP_PLAN_SOLVED and the pair (the reference's cost threshold is infinite: the first connected pair is
+ *                   the answer).  The path itself is ccmp_roadmap_shortest_paths' on that pair.
+ *   TWO STATED DIFFERENCES from the reference: a cycle grows width candidates that do not see each other and adds the ladder's prefix as
+ *   one batch (the reference adds one candidate per cycle and the nine ladder poses one after the other); and an UNSETTLED query is
+ *   skipped, not continued.  With width == 1 a growth step is the reference's growTree.
+ * ccmp_plan_create runs open; it remembers the store, the object and the scene, which must outlive it (their life-cycle rules are the
+ * handle's).  ccmp_plan_run is synchronous and not capturable; it waits for the device at entry, so appends made on any stream before it
+ * are seen.  After CCMP_PLAN_SOLVED or CCMP_PLAN_INVALID_GOAL a run returns at once with the same report.  On an error the store is as the
+ * last completed call inside the cycle left it.  Every check comes before the first launch; a NULL store / handle answers CCMP_ENODEV on
+ * a machine without a HIP device and CCMP_EINVAL otherwise.  CCMP_EINVAL: width outside 1 .. CCMP_PLAN_MAX_WIDTH, k outside 1 ..
+ * CCMP_IK_MAX_SEEDS, attempts or max_states out of ccmp_object_propose_batch's / ccmp_roadmap_grow's range, a non-finite option (t, sigma,
+ * inflate, lo, hi) or a NaN margin, max_vertices below the store's size + 2 at open, an object or a scene of another device
+ * than the store's, a NULL problem, object, opts or out, an invalid problem or IK options.
+ * The *_ref forms are the rule's pure parts on host memory: no device, never CCMP_ENODEV.
+ *   ccmp_plan_check_ref      step 2's decisions: state in and out; size; the closest arrays of both sides (a_* [n_starts], b_* [n_goals]);
+ *                            store_poses [size][8] (nullable: nearest_pose is then left alone); triggers[4] = {the check ran, the goal side
+ *                            fired, the start side fired, the vertex c whose joints seed the goal side or -1}.
+ *   ccmp_plan_prefix_ref     valid[9], ik_ok[9] -> vertex_ok[9] (1 on the prefix), returns nothing else; *prefix_len its length.
+ *   ccmp_plan_connected_ref  labels [N], state -> state (status, solved pair); an index outside [0, N) never matches. */
+#define CCMP_PLAN_MAX_STARTS 8
+#define CCMP_PLAN_MAX_GOALS 8
+#define CCMP_PLAN_MAX_WIDTH 256
+#define CCMP_PLAN_LADDER 9
+enum { CCMP_PLAN_OPEN = 0, CCMP_PLAN_SOLVED = 1, CCMP_PLAN_BUDGET = 2, CCMP_PLAN_FULL = 3, CCMP_PLAN_INVALID_GOAL = 4 };
+typedef struct ccmp_plan_opts {
+  int32_t width;         /* 32     candidates per growth step */
+  int32_t k;             /* 5      DEFAULT_NEAREST_NEIGHBORS */
+  int32_t attempts;      /* 2      draws per candidate (stefanBiPRM.cpp:262) */
+  int32_t max_states;    /* 64     the traversals' list length */
+  double t;              /* 0.3    the interpolation towards the goal pose */
+  double sigma;          /* 0.2    the draw's standard deviation */
+  double inflate;        /* 0      the mesh test's box inflation */
+  double lo[3], hi[3];   /* -1e30, 1e30: the draw's position bounds */
+  uint64_t max_vertices; /* 2^31 - 1 */
+} ccmp_plan_opts;
+typedef struct ccmp_plan_counters {
+  int32_t proposals, valid_proposals, ik_successes, vertices_kept, mid_stones, unsettled, checks, goal_pushes, start_pushes, ladder_vertices,
+      push_refused, reserved;
+} ccmp_plan_counters;
+typedef struct ccmp_plan_state {
+  int32_t n_starts, n_goals;
+  int32_t starts[CCMP_PLAN_MAX_STARTS], goals[CCMP_PLAN_MAX_GOALS];
+  int32_t nearest, sprevious;
+  int32_t status, cycle;
+  int32_t solved_start, solved_goal; /* vertices; -1 until SOLVED */
+  int32_t size_at_check, reserved;
+  uint64_t next_index;
+  double nearest_pose[8];
+  double prev_from_goal, prev_from_start;
+  ccmp_plan_counters counters;
+} ccmp_plan_state;
+typedef struct ccmp_plan_report {
+  int32_t status, cycles_run, cycles_total, reserved;
+  uint64_t size, edges;
+  int32_t solved_start, solved_goal, nearest, reserved2;
+  double prev_from_goal, prev_from_start;
+  ccmp_plan_counters counters;
+} ccmp_plan_report;
+typedef struct ccmp_plan ccmp_plan;
+void ccmp_plan_default_opts(ccmp_plan_opts *opts);
+int ccmp_plan_create(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_object *object, const ccmp_scene *scene, double margin,
+                     const ccmp_ik_opts *ik_opts, const ccmp_plan_opts *opts, const double *goal_joints, uint64_t rng_seed, uint64_t first_index,
+                     ccmp_plan **out);
+int ccmp_plan_run(ccmp_plan *plan, int max_cycles, ccmp_plan_report *out);
+int ccmp_plan_state_read(ccmp_plan *plan, ccmp_plan_state *out);
+void ccmp_plan_destroy(ccmp_plan *plan);
+int ccmp_plan_check_ref(ccmp_plan_state *state, size_t size, const int32_t *a_idx, const double *a_dist, const double *a_from, const int32_t *b_idx,
+                        const double *b_dist, const double *b_from, const double *store_poses, int32_t triggers[4]);
+int ccmp_plan_prefix_ref(const uint8_t valid[9], const uint8_t ik_ok[9], uint8_t vertex_ok[9], int32_t *prefix_len);
+int ccmp_plan_connected_ref(const int32_t *labels, size_t N, ccmp_plan_state *state);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault
  * injection — are not part of this library: include/ccmp_debug.h, lib/libccmp_debug.so) */

@@ -1387,10 +1387,19 @@ public:
     return true;
   }
 
+  // stefanBiPRM::solve on this store in one call (ccmp::Planner below: open, then up to max_cycles cycles): the status (CCMP_PLAN_*) and,
+  // when it is CCMP_PLAN_SOLVED, the connected (start vertex, goal vertex) in *start / *goal — the path is shortestPaths' on that pair.
+  // object: ObjectChecker::handle(); scene: ProxyScene::handle() or nullptr; goal_joints14: the goal state, or nullptr for the pose IK
+  // towards the problem's goal pose.  -1 when a call failed (the error in lastError()).
+  int solve(const ccmp_object *object, int max_cycles, int32_t *start = nullptr, int32_t *goal = nullptr, const ccmp_plan_opts *opts = nullptr,
+            const ccmp_scene *scene = nullptr, double margin = 0.0, const double *goal_joints14 = nullptr, uint64_t rng_seed = 0,
+            ccmp_plan_report *report = nullptr) noexcept;
+
   int lastError() const noexcept { return err_.code(); }
   std::string lastErrorMessage() const { return err_.message(); }
   void clearError() noexcept { err_.clear(); }
   ccmp_roadmap *handle() const noexcept { return rm_; }
+  const Projector &projector() const noexcept { return proj_; }
 
 private:
   template <class F>
@@ -1749,6 +1758,102 @@ private:
   ccmp_scene *scene_ = nullptr;
   mutable detail::ErrorLatch err_; // ikValid's sticky error (the other verbs throw)
 };
+
+// ---- the planner's loop on the store (include/ccmp.h: ccmp_plan_*) ------------------------------------------------------------------
+// stefanBiPRM::solve / constructRoadmap / checkForSolution as one resumable object: open (start and goal vertex through
+// startgoalMilestone), then cycles of growth (width candidates where the reference has one), check (closestFromGoal both ways, goal and
+// start IK, the nine-pose ladder as one batch) and the solution test, with the bookkeeping on the device.  A restatement of the
+// reference's STRUCTURE, not of the interleaving of its two threads; an unsettled query is skipped, not continued.
+struct PlanOptions : ccmp_plan_opts {
+  PlanOptions() noexcept { ccmp_plan_default_opts(this); }
+};
+
+// Never throws: a Planner that could not be opened answers "no" to every verb and keeps the FIRST failure in lastError() /
+// lastErrorMessage() until clearError(), as ccmp::Roadmap does.  The store, the object and the scene must outlive it.
+class Planner {
+public:
+  Planner(Roadmap &roadmap, const ccmp_object *object, const PlanOptions &opts = PlanOptions(), const ccmp_scene *scene = nullptr, double margin = 0.0,
+          const double *goal_joints14 = nullptr, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept : mu_(&roadmap.projector().mutex())
+  {
+    open(roadmap.handle(), &roadmap.projector().problem(), object, scene, margin, &roadmap.projector().ikOptions(), opts, goal_joints14, rng_seed, first_index);
+  }
+  // the same on the C handles (a caller without a Projector); serialised by a mutex of its own
+  Planner(ccmp_roadmap *roadmap, const ccmp_problem &problem, const ccmp_object *object, const PlanOptions &opts = PlanOptions(), const ccmp_scene *scene = nullptr,
+          double margin = 0.0, const double *goal_joints14 = nullptr, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept : mu_(&own_mu_)
+  {
+    open(roadmap, &problem, object, scene, margin, nullptr, opts, goal_joints14, rng_seed, first_index);
+  }
+  ~Planner()
+  {
+    if (!plan_) return;
+    std::lock_guard<std::mutex> hold(*mu_);
+    ccmp_plan_destroy(plan_);
+  }
+  Planner(const Planner &) = delete;
+  Planner &operator=(const Planner &) = delete;
+
+  bool create() const noexcept { return plan_ != nullptr; } // was it opened
+  // up to max_cycles more cycles; true = the call ran (report() has the verdict), false = it failed or there is no planner
+  bool run(int max_cycles) noexcept
+  {
+    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_plan_run", [&] { return ccmp_plan_run(plan_, max_cycles, &report_); });
+  }
+  const ccmp_plan_report &report() const noexcept { return report_; }
+  int status() const noexcept { return plan_ ? report_.status : -1; }
+  bool solved() const noexcept { return plan_ && report_.status == CCMP_PLAN_SOLVED; }
+  bool state(ccmp_plan_state *out) const noexcept
+  {
+    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_plan_state_read", [&] { return ccmp_plan_state_read(plan_, out); });
+  }
+  int lastError() const noexcept { return err_.code(); }
+  std::string lastErrorMessage() const { return err_.message(); }
+  void clearError() noexcept { err_.clear(); }
+  ccmp_plan *handle() const noexcept { return plan_; }
+
+private:
+  void open(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_object *object, const ccmp_scene *scene, double margin, const ccmp_ik_opts *ik,
+            const ccmp_plan_opts &opts, const double *goal_joints14, uint64_t rng_seed, uint64_t first_index) noexcept
+  {
+    std::memset(&report_, 0, sizeof report_);
+    report_.status = -1;
+    report_.solved_start = report_.solved_goal = report_.nearest = -1;
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(*mu_);
+      rc = ccmp_plan_create(rm, p, object, scene, margin, ik, &opts, goal_joints14, rng_seed, first_index, &plan_); // a NULL store: the library's own answer
+      if (rc == CCMP_OK) rc = ccmp_plan_run(plan_, 0, &report_);
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) err_.record(rc, "ccmp_plan_create");
+  }
+  std::mutex own_mu_;
+  std::mutex *mu_;
+  ccmp_plan *plan_ = nullptr;
+  ccmp_plan_report report_;
+  mutable detail::ErrorLatch err_;
+};
+
+inline int Roadmap::solve(const ccmp_object *object, int max_cycles, int32_t *start, int32_t *goal, const ccmp_plan_opts *opts, const ccmp_scene *scene,
+                          double margin, const double *goal_joints14, uint64_t rng_seed, ccmp_plan_report *report) noexcept
+{
+  PlanOptions o;
+  if (opts) static_cast<ccmp_plan_opts &>(o) = *opts;
+  if (start) *start = -1;
+  if (goal) *goal = -1;
+  Planner planner(*this, object, o, scene, margin, goal_joints14, rng_seed);
+  if (planner.create() && max_cycles > 0) planner.run(max_cycles);
+  if (report) *report = planner.report();
+  if (planner.lastError() != CCMP_OK) {
+    err_.recordAs(planner.lastError(), planner.lastErrorMessage().c_str());
+    return -1;
+  }
+  if (planner.solved()) {
+    if (start) *start = planner.report().solved_start;
+    if (goal) *goal = planner.report().solved_goal;
+  }
+  return planner.status();
+}
 
 inline bool Projector::sampleCalibGoal(const double *pose8, const double *seeds, int S, double *result14, int *which, const ProxyScene &scene, double margin,
                                        double *clearance) const noexcept

@@ -59,6 +59,11 @@
                                                            jerk ratio, the chosen windows at 1 and 4 ms); then ccmp_path_jerk_setpoints at 1 ms on the setpoints measurement's
                                                            inputs (1 and 64 paths) beside the loop a caller would write without it (ccmp_path_setpoints, copy qd out, numpy
                                                            windows); the recorded paths' windows and six peaks, without and behind the fit; writes profiles/jerk.md
+    python tools/measure.py plan [cycles]                   the planner's loop on the store (ccmp_plan_*): the three shipped configs at width 1, 8, 32 and 128 for `cycles`
+                                                           (64) cycles each — status, cycles, vertices, edges, the counters and wall time —, the same towards a goal that one
+                                                           motion does not reach, beside the same cycles BY HAND over the mirror's calls (tests/plan_cases.py: HandPlan, what a
+                                                           caller can write without the unit) with its host reads, and which branches six cycles reach at width 1, 5, 64 and 65;
+                                                           writes profiles/plan.md
     python tools/measure.py smooth_restate <file.npz> [n]  the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
@@ -1972,6 +1977,101 @@ def jerk(argv):
                 "acceleration can still command more than jmax (dumbbell under doubled stamps).\n\n```\n" + "\n".join(cpu) + "\n```\n")
 
 
+def plan(argv):
+    """the planner's loop (ccmp_plan_*): python tools/measure.py plan [cycles]; writes profiles/plan.md"""
+    sys.path.insert(0, "tests")
+    from arm_model_cases import default_scene_host
+    from object_cases import box_mesh, workspace
+    from plan_cases import HandPlan, state_bits
+    from closed_chain_motion_planner_amd import PLAN_STATUS, ObjectChecker, ProxyScene, Roadmap
+
+    cycles = int(argv[0]) if argv else 64
+    ctx = Context(0)
+    MS, MARGIN = 16, -0.03
+    names = ("proposals", "valid_proposals", "ik_successes", "vertices_kept", "mid_stones", "unsettled", "checks", "goal_pushes", "start_pushes", "ladder_vertices",
+             "push_refused")
+
+    def world(obj, scene, far=False, mode=0):
+        c = KinematicChainConstraint.from_yaml(CFG % obj, ctx=ctx)
+        c.setJacobianMode(mode)
+        chk = ObjectChecker(c, box_mesh(0.04, 0.04, 0.1), workspace())
+        sc = None
+        if scene:
+            hs = default_scene_host(c.problem)
+            sc = ProxyScene(c, hs.spheres, hs.boxes, hs.allowed)
+        return c, chk, sc, (far_goal_state(c, chk, MS) if far else None)
+
+    def line(tag, r, ms, extra=""):
+        return "%-34s %-12s cycles %3d  V %5d  E %5d  d_goal %.4f  d_start %.4f  %s  %8.1f ms%s" % (
+            tag, PLAN_STATUS[r["status"]] + ("" if r["solved"] is None else " %s" % (r["solved"],)), r["cycles_total"], r["size"], r["edges"], r["prev_from_goal"],
+            r["prev_from_start"], " ".join("%s %d" % (n[:3] + n[-2:], r["counters"][n]) for n in names), ms, extra)
+
+    from plan_cases import far_goal_state
+
+    def store(c, far):
+        return Roadmap(c)
+
+    rows, hard, hand, cover = [], [], [], []
+    for far, out in ((False, rows), (True, hard)):
+        for obj in ("Wine_Bottle", "dumbbell", "stefan"):
+            c, chk, _, gj = world(obj, False, far)
+            for W in (1, 8, 32, 128):
+                rm = store(c, far)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                pl = rm.plan(c, chk, goal_joints=gj, width=W, k=5, max_states=MS, rng_seed=0x91A)
+                r = pl.run(cycles)
+                ms = (time.perf_counter() - t0) * 1e3
+                out.append(line("%s width %d" % (obj, W), r, ms, "  (%.2f ms / cycle)" % (ms / max(r["cycles_total"], 1))))
+                print(out[-1], flush=True)
+                final = pl.state()
+                pl.close()
+                rm.close()
+                if W == 32 and far:  # the same cycles by hand: the same bits, and what they cost a caller
+                    rm = store(c, far)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    hp = HandPlan(rm, c, chk, goal_joints=gj, width=W, k=5, max_states=MS, rng_seed=0x91A)
+                    n = hp.run(cycles)
+                    hms = (time.perf_counter() - t0) * 1e3
+                    hand.append("%-12s by hand: %3d cycles %8.1f ms (%.2f ms / cycle), %d mirror calls, %d host reads (%.1f / cycle); Plan.run: %.2f ms / cycle; same state bits: %s"
+                                % (obj, n, hms, hms / max(n, 1), hp.calls, hp.reads, hp.reads / max(n, 1), ms / max(r["cycles_total"], 1), state_bits(hp.state) == state_bits(final)))
+                    print(hand[-1], flush=True)
+                    rm.close()
+    for scene in (False, True):
+        for mode in (0, 1):
+            c, chk, sc, gj = world("Wine_Bottle", scene, True, mode)
+            for W in (1, 5, 64, 65):
+                rm = store(c, True)
+                pl = rm.plan(c, chk, goal_joints=gj, scene=sc, margin=MARGIN, width=W, k=5, max_states=MS, rng_seed=0x91A)
+                r = pl.run(6)
+                cover.append(line("width %d%s%s, 6 cycles" % (W, " scene" if scene else "", " analytic" if mode else ""), r, 0.0))
+                print(cover[-1], flush=True)
+                pl.close()
+                rm.close()
+    with open("profiles/plan.md", "w") as f:
+        f.write("# The planner's loop on the store (`ccmp_plan_*`, `Roadmap.plan`)\n\nWritten by `python tools/measure.py plan`.  One MI355X, one process.  "
+                "**Wall clock only, measured on one card**: `time.perf_counter` around open plus `Plan.run(%d)`; no GPU time was measured and no speed threshold gates "
+                "this feature.  Object: a box mesh (0.04, 0.04, 0.1) against the fixture workspace; k = 5, lists of 16 states, rng_seed 0x91A, no scene unless "
+                "stated.  Whether and when a config solves is a measurement, not a property the unit promises.\n\n"
+                "Counter columns: proposals, valid proposals, IK successes, vertices kept, mid-stones, unsettled queries, checks run, goal pushes, start pushes, "
+                "ladder vertices, pushes refused at the cap.\n\n## The shipped problems, %d cycles\n\n```\n" % (cycles, cycles) + "\n".join(rows) + "\n```\n\n"
+                "On all three shipped configs checkMotion reaches the goal state from the start state: open connects them and no cycle runs.  That is the "
+                "finding for these problems at every width; the rule was not tuned.\n\n## Towards a goal that one motion does not reach\n\nThe same runs with "
+                "another goal (`tests/plan_cases.py: far_goal_state`): of 2 048 sampled states the one nearest to the start pose whose mesh is free and which "
+                "checkMotion from the start does not reach within 16 states; its object pose is the goal pose, the state itself `goal_joints`.\n\n```\n"
+                + "\n".join(hard) + "\n```\n\n"
+                "## The same cycles by hand (width 32, towards that goal)\n\n`tests/plan_cases.py: HandPlan` runs the loop over the mirror's calls that exist without the unit (propose, grow, "
+                "commit, closest, valid, pose_ik_batch, connect, labels), every decision on the host.  That is what a caller could do on the parent commit.  The first by-hand run of a process also pays the one-time growth of the library's workspaces (Wine_Bottle's single cycle below), so only the rows with more than one cycle compare the two routes; what the unit removes for certain is the count of host reads per cycle.\n\n```\n"
+                + "\n".join(hand) + "\n```\n\n## What a cycle of `Plan.run` costs the host\n\nBranches that did not fire are SKIPPED after a read, not launched on NaN "
+                "rows (the rows are NaN on the device either way, so the bits are the same).  A cycle without a check: 3 launches of the plan unit (front, tally, "
+                "solution test) between 3 calls of the store's entries (propose, grow, commit), and 2 host reads (the commit's own 16-byte count read-back and the "
+                "240-byte state block).  A cycle whose check ran adds 2 closest calls, the check kernel, the mesh test of the nine ladder poses, one IK call over the "
+                "eleven targets, the prefix kernel and one 16-byte read; each branch that has a vertex to add (goal, ladder prefix, start) adds one connect, one commit "
+                "(with its read-back) and one push or tally launch.  The store, the edge list, the labels and the state lists never cross to the host.\n\n"
+                "## Which branches six cycles reach (Wine_Bottle towards that goal; FD and analytic mode, without and with the skeleton scene at -0.03)\n\n```\n" + "\n".join(cover) + "\n```\n")
+
+
 def smooth_restate(argv):
     """the plain-Python restatement of the smoothing rule (tests/smooth_cases.py on the det oracle) on one host core, on the inputs `smooth`
     wrote, compared bit for bit with the results it wrote: python tools/measure.py smooth_restate <file.npz> [paths]"""
@@ -2070,7 +2170,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, fit, jerk, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, fit, jerk, plan, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
