@@ -14,6 +14,7 @@ from .space import (check_motion, format_graphml, format_graphviz, format_path_m
 from .scene import ProxyScene, ProxyValidityChecker, default_allowed, skeleton_spheres  # noqa: F401
 
 from .roadmap import PLAN_STATUS, Plan, plan_check_ref, plan_connected_ref, plan_options, plan_prefix_ref  # noqa: F401
+from .roadmap import RRTC_STATUS, RRTConnect, nearest_in_tree_ref, rrtc_connected_ref, rrtc_nearest_shape, rrtc_options, rrtc_pick, rrtc_pick_ref  # noqa: F401
 from .roadmap import Roadmap, closest_ref, commit_ref, graph_labels_ref, joint_distance, pose_distance, pose_from_t_wo, shortest_paths_ref  # noqa: F401
 
 from .dense import DENSE_DISTINCT, dense_arc_ref, dense_layout_ref  # noqa: F401

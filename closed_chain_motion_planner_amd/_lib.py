@@ -127,6 +127,32 @@ class CcmpPlanReport(C.Structure):
                 ("prev_from_goal", C.c_double), ("prev_from_start", C.c_double), ("counters", CcmpPlanCounters)]
 
 
+class CcmpRrtcOpts(C.Structure):
+    """ccmp_rrtc_opts of include/ccmp.h"""
+    _fields_ = [("width", C.c_int32), ("max_states", C.c_int32), ("round_budget", C.c_int32), ("reserved", C.c_int32), ("range", C.c_double),
+                ("max_vertices", C.c_uint64)]
+
+
+class CcmpRrtcCounters(C.Structure):
+    """ccmp_rrtc_counters of include/ccmp.h"""
+    _fields_ = [(n, C.c_int32) for n in ("samples", "projected", "trapped", "advanced", "reached", "unsettled", "connect_reached", "connect_added",
+                                         "connect_nothing", "vertices", "edges", "reserved")]
+
+
+class CcmpRrtcState(C.Structure):
+    """ccmp_rrtc_state of include/ccmp.h"""
+    _fields_ = [("n_starts", C.c_int32), ("n_goals", C.c_int32), ("starts", C.c_int32 * 8), ("goals", C.c_int32 * 8), ("status", C.c_int32), ("cycle", C.c_int32),
+                ("next_index", C.c_uint64), ("solved_start", C.c_int32), ("solved_goal", C.c_int32), ("best_a", C.c_int32), ("best_b", C.c_int32),
+                ("best_gap", C.c_double), ("counters", CcmpRrtcCounters)]
+
+
+class CcmpRrtcReport(C.Structure):
+    """ccmp_rrtc_report of include/ccmp.h"""
+    _fields_ = [("status", C.c_int32), ("cycles_run", C.c_int32), ("cycles_total", C.c_int32), ("reserved", C.c_int32), ("size", C.c_uint64),
+                ("edges", C.c_uint64), ("solved_start", C.c_int32), ("solved_goal", C.c_int32), ("best_a", C.c_int32), ("best_b", C.c_int32),
+                ("best_gap", C.c_double), ("counters", CcmpRrtcCounters)]
+
+
 CCMP_JAC_FD = 0
 CCMP_JAC_ANALYTIC = 1
 
@@ -171,6 +197,9 @@ EXPORTS = [
     "ccmp_jerk_setpoints_copy_host", "ccmp_jerk_setpoints_destroy", "ccmp_jerk_setpoints_ref", "ccmp_jerk_next_window_ref",
     "ccmp_plan_default_opts", "ccmp_plan_create", "ccmp_plan_run", "ccmp_plan_state_read", "ccmp_plan_destroy", "ccmp_plan_check_ref", "ccmp_plan_prefix_ref",
     "ccmp_plan_connected_ref",
+    "ccmp_rrtc_default_opts", "ccmp_rrtc_create", "ccmp_rrtc_run", "ccmp_rrtc_state_read", "ccmp_rrtc_destroy", "ccmp_roadmap_nearest_in_tree",
+    "ccmp_roadmap_nearest_in_tree_host", "ccmp_roadmap_nearest_in_tree_ref", "ccmp_rrtc_nearest_shape", "ccmp_rrtc_pick_ref", "ccmp_rrtc_connected_ref",
+    "ccmp_rrtc_pick_batch",
     "ccmp_strerror",
     "ccmp_last_hip_error", "ccmp_version", "ccmp_problem_sizeof",
 ]
@@ -418,6 +447,18 @@ def lib():
         "ccmp_plan_check_ref": ([C.POINTER(CcmpPlanState), C.c_size_t, i32p, dp, dp, i32p, dp, dp, dp, i32p], C.c_int),
         "ccmp_plan_prefix_ref": ([u8p, u8p, u8p, i32p], C.c_int),
         "ccmp_plan_connected_ref": ([i32p, C.c_size_t, C.POINTER(CcmpPlanState)], C.c_int),
+        "ccmp_rrtc_default_opts": ([C.POINTER(CcmpRrtcOpts)], None),
+        "ccmp_rrtc_create": ([vp, pp, vp, C.c_double, C.POINTER(CcmpRrtcOpts), i32p, C.c_int, i32p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)], C.c_int),
+        "ccmp_rrtc_run": ([vp, C.c_int, C.POINTER(CcmpRrtcReport)], C.c_int),
+        "ccmp_rrtc_state_read": ([vp, C.POINTER(CcmpRrtcState)], C.c_int),
+        "ccmp_rrtc_destroy": ([vp], None),
+        "ccmp_roadmap_nearest_in_tree": ([vp, vp, C.c_int, vp, C.c_size_t, vp, vp, vp], C.c_int),
+        "ccmp_roadmap_nearest_in_tree_host": ([vp, i32p, C.c_int, dp, C.c_size_t, i32p, dp], C.c_int),
+        "ccmp_roadmap_nearest_in_tree_ref": ([dp, i32p, C.c_size_t, i32p, C.c_int, dp, C.c_size_t, i32p, dp], C.c_int),
+        "ccmp_rrtc_nearest_shape": ([vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], C.c_int),
+        "ccmp_rrtc_pick_ref": ([C.c_int, dp, i32p, u8p, u8p, dp, dp, C.c_size_t, C.c_int, C.c_double, i32p, i32p, dp, dp], C.c_int),
+        "ccmp_rrtc_connected_ref": ([i32p, C.c_size_t, C.POINTER(CcmpRrtcState)], C.c_int),
+        "ccmp_rrtc_pick_batch": ([vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, C.c_double, vp, vp, vp, vp, vp], C.c_int),
         "ccmp_strerror": ([C.c_int], C.c_char_p),
         "ccmp_last_hip_error": ([], C.c_char_p),
         "ccmp_version": ([], C.c_int),
@@ -465,6 +506,10 @@ GRAPH_MAX_ROOTS, CLOSEST_MAX_FROM = 32, 64  # ccmp.h: CCMP_GRAPH_MAX_ROOTS, CCMP
 PATH_MAX_PAIRS = 64  # ccmp.h: CCMP_PATH_MAX_PAIRS
 PLAN_OPEN, PLAN_SOLVED, PLAN_BUDGET, PLAN_FULL, PLAN_INVALID_GOAL = range(5)  # ccmp.h: CCMP_PLAN_*
 PLAN_MAX_STARTS, PLAN_MAX_GOALS, PLAN_MAX_WIDTH, PLAN_LADDER = 8, 8, 256, 9  # ccmp.h: CCMP_PLAN_MAX_*, CCMP_PLAN_LADDER
+RRTC_OPEN, RRTC_SOLVED, RRTC_BUDGET, RRTC_FULL = range(4)  # ccmp.h: CCMP_RRTC_* (statuses)
+RRTC_NONE, RRTC_TRAPPED, RRTC_ADVANCED, RRTC_REACHED, RRTC_UNSETTLED = -1, 0, 1, 2, 3  # ccmp.h: CCMP_RRTC_* (step 2's outcomes)
+RRTC_CONNECT_NOTHING, RRTC_CONNECT_ADDED, RRTC_CONNECT_JOINED = range(3)  # ccmp.h: CCMP_RRTC_CONNECT_*
+RRTC_MAX_ROOTS = 8  # ccmp.h: CCMP_RRTC_MAX_ROOTS
 DENSE_DISTINCT = 1  # ccmp.h: CCMP_DENSE_DISTINCT
 SHORTCUT_MAX_LEN = 1024  # ccmp.h: CCMP_SHORTCUT_MAX_LEN
 RETIME_OK, RETIME_EMPTY, RETIME_BROKEN, RETIME_NONFINITE, RETIME_POINT, RETIME_FULL = range(6)  # ccmp.h: CCMP_RETIME_*

@@ -62,6 +62,10 @@ Translation units with deliberately different flags:
   ccmp_kernels_plan.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the planner's loop on the store (ccmp_plan.h): the front's broadcast, the tally of a growth step, the check
                          (one wavefront: the carry rule's serial fold, the thresholds, the IK targets of the ladder), the prefix, the push and the solution test (a ballot over the pairs)
   ccmp_plan.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_plan_*: checks, open, the cycle over the store's own entry points; ccmp_plan_check_ref / _prefix_ref / _connected_ref
+  ccmp_kernels_rrtc.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   RRT-Connect on the store (ccmp_rrtc.h): nearest vertex within a tree (blocks over (partition, query), a
+                         (distance, index) pair reduction), the traversal's endpoints, the pick (sixteen lanes per edge, the arc's serial fold), the commit (one block: a scan
+                         gives the total order) and the solution test
+  ccmp_rrtc.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_rrtc_*, ccmp_roadmap_nearest_in_tree*: checks, the cycle over the library's own entry points; the *_ref forms
   (the three units ccmp_kernels_setpoints / _fit / _jerk share ccmp_lanes.h on the device — the DPP row folds and the audit fold of the two peak kernels — and ccmp_timed.h on the
   host — the checks, the _host staging, the tick ranges, the delivery tail and the _ref loops; a tick of the interpolant is setpoint_bracket and
   setpoint_joint of ccmp_setpoints.h everywhere)
@@ -169,8 +173,12 @@ _UNITS = [
     ("ccmp_kernels_plan.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_plan_*: the checks, open and the cycle over the store's entry points, and the rule on the host (ccmp_plan_check_ref, _prefix_ref, _connected_ref)
     ("ccmp_plan.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
+    # RRT-Connect on the store (ccmp_rrtc.h): nearest-in-tree, edges, pick, commit and the solution test; the graph unit's flags; registers and LDS only
+    ("ccmp_kernels_rrtc.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
+    # ccmp_rrtc_*, ccmp_roadmap_nearest_in_tree*: the checks and the cycle over the library's entry points, and the rule on the host (the *_ref forms)
+    ("ccmp_rrtc.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_setpoints.h", "ccmp_fit.h", "ccmp_jerk.h", "ccmp_plan.h", "ccmp_lanes.h", "ccmp_timed.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_setpoints.h", "ccmp_fit.h", "ccmp_jerk.h", "ccmp_plan.h", "ccmp_rrtc.h", "ccmp_lanes.h", "ccmp_timed.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():
@@ -223,6 +231,7 @@ _SCRATCH_RULES = [  # (regex on the demangled name, bound); first match wins
     (r"fit_", 0),  # fitted time stamps: a tick interval's two brackets, a lane's joint at both ticks and the merged maxima live in registers, the dilation's 64 widths in LDS
     (r"jerk_", 0),  # jerk-bounded setpoints: a tick's bracket, a lane's joint, its window's sum and its six peaks live in registers, the staged inputs and the folds in LDS
     (r"plan_", 0),  # the planner's loop: the state block's fields, a lane's ladder pose and a lane's counts live in registers, the check's triggers in LDS
+    (r"rrtc_", 0),  # RRT-Connect: a query row and the eight root labels live in scalar registers, a lane's best pair and a group's arc in registers, the folds and the scan in LDS
     (r"scout_|clearance", 400),
     (r".", 64),
 ]

@@ -9,6 +9,7 @@
 
 struct ccmp_consts;
 struct ccmp_plan_state;
+struct ccmp_rrtc_state;
 namespace ccmp { struct scene_dev; struct scene_arm_dev; struct ik_arms; struct ik_params; struct object_boxes; struct object_sphere; struct object_draw; struct graph_roots; struct dense_chunk; struct dense_open_seg; struct shortcut_open; struct smooth_path; struct retime_limits; struct setpoint_limits; struct jerk_limits; }
 
 /* What a split launch asks of the counting sort that precedes it: the cut of the descending order between the latency blocks
@@ -213,6 +214,28 @@ struct PlanCheck {
   double *targets; // [11][8]: goal, ladder 1 .. 9, start; a NaN row where the branch did not fire
   double *seeds;   // [11][14]
   int32_t *trig;   // [4]
+};
+
+/* RRT-Connect on the store (csrc/ccmp_rrtc.h).  One pick over E traversal lists: mode 0 = step 2 (d: the nearest distances), 1 = step 3
+ * (gap out); use [E] (nullable: all 1) as rrtc_edges wrote it; nearest [E] (nullable) -> parent [E] (nullable) where an edge results */
+constexpr int kRrtcThreads = 256;          // lanes per block of the RRT-Connect kernels; the commit kernel's ONE block bounds the width
+constexpr int kRrtcMaxPartitions = 256;    // cuts of the vertex range of a nearest-in-tree call: its merge holds one partition's best per lane
+struct RrtcPick {
+  int mode;
+  const double *states; const int32_t *n_states; const uint8_t *ok; const uint8_t *use;
+  const double *to, *d; const int32_t *nearest;
+  size_t E; int max_states; double range;
+  int32_t *outcome, *row_index; double *row; // [E], [E], [E][14]
+  int32_t *parent; uint8_t *made; double *gap; // nullable, [E] each
+};
+/* one commit of a cycle of width W <= kRrtcThreads: step 2's (A) and step 3's (B) picks -> rows [2 W][14], uv [2 W][2], counts [4] =
+ * {vertices, edges, step 2's vertices, step 3's vertices} */
+struct RrtcCommit {
+  int W, a_is_start;
+  const uint8_t *useA;
+  const int32_t *outA, *parA; const double *rowA;
+  const int32_t *outB, *parB, *idxB; const double *rowB, *gapB;
+  double *rows; int32_t *uv, *counts;
 };
 
 #pragma GCC visibility push(hidden)
@@ -450,6 +473,18 @@ hipError_t plan_prefix(const ccmp_plan_state *state, const int32_t *trig, const 
 hipError_t plan_push(ccmp_plan_state *state, int which, const int32_t *new_index, hipStream_t st);
 /* cycle += bump_cycle, then the solution test on the store's labels */
 hipError_t plan_connected(const GraphStore &s, ccmp_plan_state *state, int bump_cycle, hipStream_t st);
+/* RRT-Connect on the store (ccmp_rrtc_*, ccmp_roadmap_nearest_in_tree; csrc/ccmp_rrtc.h, ccmp_kernels_rrtc.hip).  Blocks over (partition,
+ * query), then the exact merge (partitions > 1: ws_d [Q][P], ws_i [Q][P]); roots [n_roots] is device memory */
+hipError_t rrtc_nearest(const GraphStore &s, const int32_t *roots, int n_roots, const double *queries, size_t Q, unsigned int part, unsigned int partitions,
+                        double *ws_d, int32_t *ws_i, int32_t *idx, double *dist, hipStream_t st);
+/* from [E][14] = the store's joints at idx [E], to = rows [E][14]; use [E] = 0 where one of the (nullable) flag arrays is 0, 2 without a nearest
+ * vertex, else 1; an edge that is not used runs from a zero row to a zero row */
+hipError_t rrtc_edges(const GraphStore &s, const int32_t *idx, const double *rows, const uint8_t *f0, const uint8_t *f1, const uint8_t *f2, size_t E,
+                      double *from, double *to, uint8_t *use, hipStream_t st);
+hipError_t rrtc_pick(const RrtcPick &c, hipStream_t st);
+hipError_t rrtc_commit(const GraphStore &s, ccmp_rrtc_state *state, const RrtcCommit &c, hipStream_t st);
+/* cycle += bump_cycle, then the solution test on the store's labels */
+hipError_t rrtc_connected(const GraphStore &s, ccmp_rrtc_state *state, int bump_cycle, hipStream_t st);
 // lib/libccmp_debug.so only (ccmp_kernels_debug.hip)
 hipError_t detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
 hipError_t div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);

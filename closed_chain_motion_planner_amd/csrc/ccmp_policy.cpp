@@ -323,6 +323,19 @@ ccmp_launch::KnnShape plan_knn_pose(const ccmp_ctx *ctx, size_t Q, size_t N, int
   return plan_knn_tiled(ctx, Q, N, k, ccmp_launch::kKnnPoseTile, kKnnPoseMinPart);
 }
 
+// Nearest-in-tree: Q blocks per partition; the partitions fill about four blocks per CU, none shorter than kRrtcMinPart rows.
+void plan_rrtc_nearest(const ccmp_ctx *ctx, size_t Q, size_t N, unsigned int *part, unsigned int *partitions)
+{
+  size_t want = Q ? ((size_t)ctx->num_cus * 4 + Q - 1) / Q : 1;
+  if (want < 1) want = 1;
+  if (want > (size_t)ccmp_launch::kRrtcMaxPartitions) want = ccmp_launch::kRrtcMaxPartitions;
+  size_t pt = (N + want - 1) / want;
+  pt = (pt + ccmp_launch::kRrtcThreads - 1) / ccmp_launch::kRrtcThreads * ccmp_launch::kRrtcThreads;
+  if (pt < kRrtcMinPart) pt = kRrtcMinPart;
+  *part = (unsigned int)pt;
+  *partitions = N ? (unsigned int)((N + pt - 1) / pt) : 1u;
+}
+
 }  // namespace ccmp_host
 
 namespace {

@@ -77,7 +77,12 @@ ccmp_launch::KnnShape plan_knn(const ccmp_ctx *ctx, size_t Q, size_t N, int k);
  * the same rule on tiles of kKnnPoseTile poses.  A function of Q, N, k and the CU count alone. */
 constexpr unsigned int kKnnPoseMinPart = 1024; // poses per partition at least (two tiles)
 ccmp_launch::KnnShape plan_knn_pose(const ccmp_ctx *ctx, size_t Q, size_t N, int k);
-constexpr int kConnectDescribeK = 5;      // ccmp_ctx_describe(CCMP_CALL_CONNECT): the reference's DEFAULT_NEAREST_NEIGHBORS
+/* the nearest vertex of a tree for Q queries among N store rows (ccmp_roadmap_nearest_in_tree; rrtc_nearest_kernel: one block per
+ * (partition, query)): about four blocks per CU, partitions of at least kRrtcMinPart rows (a multiple of the block's 256 lanes), at most
+ * kRrtcMaxPartitions of them.  A function of Q, N and the CU count alone; the (distance, index) key makes the result the same for every cut. */
+constexpr unsigned int kRrtcMinPart = 256;
+void plan_rrtc_nearest(const ccmp_ctx *ctx, size_t Q, size_t N, unsigned int *part, unsigned int *partitions);
+constexpr int kConnectDescribeK = 5;     // ccmp_ctx_describe(CCMP_CALL_CONNECT): the reference's DEFAULT_NEAREST_NEIGHBORS
 
 /* ccmp_ctx_set_option behind the options ccmp_api.cpp handles itself ("resident"): the option table */
 __attribute__((visibility("hidden"))) int policy_set_option(ccmp_ctx *ctx, const char *name, long value);

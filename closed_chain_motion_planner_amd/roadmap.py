@@ -20,7 +20,8 @@ from .object import DEFAULT_HI, DEFAULT_LO
 
 __all__ = ["Roadmap", "pose_distance", "pose_from_t_wo", "joint_distance", "graph_labels_ref", "commit_ref", "closest_ref", "shortest_paths_ref", "METRIC_JOINT", "METRIC_OBJECT",
            "GROW_TRAPPED", "GROW_SREACHED", "GROW_GREACHED", "GROW_UNSETTLED", "COMMIT_KEEP_ISOLATED", "Plan", "PLAN_STATUS", "plan_options", "plan_check_ref",
-           "plan_prefix_ref", "plan_connected_ref"]
+           "plan_prefix_ref", "plan_connected_ref", "RRTConnect", "RRTC_STATUS", "rrtc_options", "rrtc_pick_ref", "rrtc_pick", "rrtc_connected_ref", "nearest_in_tree_ref",
+           "rrtc_nearest_shape"]
 
 _arg = HOST.arg
 
@@ -248,6 +249,147 @@ class Plan:
     def close(self):
         if self._h:
             _lib.lib().ccmp_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- RRT-Connect on the store (include/ccmp.h: ccmp_rrtc_*; the rule: csrc/ccmp_rrtc.h) --------------------------------------------------
+RRTC_STATUS = {_lib.RRTC_OPEN: "OPEN", _lib.RRTC_SOLVED: "SOLVED", _lib.RRTC_BUDGET: "BUDGET", _lib.RRTC_FULL: "FULL"}
+_RRTC_COUNTERS = [n for n, _ in _lib.CcmpRrtcCounters._fields_ if n != "reserved"]
+_RRTC_SCALARS = ("status", "cycle", "next_index", "solved_start", "solved_goal", "best_a", "best_b", "best_gap")
+
+
+def rrtc_options(**kw):
+    """ccmp_rrtc_opts with the library's defaults (width 32, max_states 64, round_budget 0, range 0.1, max_vertices 2^31 - 1), fields
+    overridden by keyword"""
+    o = _lib.CcmpRrtcOpts()
+    _lib.lib().ccmp_rrtc_default_opts(C.byref(o))
+    for name, v in kw.items():
+        if name not in dict(_lib.CcmpRrtcOpts._fields_) or name == "reserved":
+            raise TypeError("ccmp_rrtc_opts has no field %r" % name)
+        setattr(o, name, v)
+    return o
+
+
+def _rrtc_state_dict(s):
+    """a ccmp_rrtc_state as a dict of plain values (starts / goals cut to their lengths)"""
+    d = {n: getattr(s, n) for n in _RRTC_SCALARS}
+    d.update(starts=list(s.starts[:s.n_starts]), goals=list(s.goals[:s.n_goals]), counters={n: getattr(s.counters, n) for n in _RRTC_COUNTERS})
+    return d
+
+
+def _rrtc_state_struct(d):
+    s = _lib.CcmpRrtcState()
+    for n in _RRTC_SCALARS:
+        setattr(s, n, d[n])
+    s.n_starts, s.n_goals = len(d["starts"]), len(d["goals"])
+    s.starts[:], s.goals[:] = [-1] * 8, [-1] * 8
+    s.starts[:s.n_starts], s.goals[:s.n_goals] = [int(v) for v in d["starts"]], [int(v) for v in d["goals"]]
+    for n in _RRTC_COUNTERS:
+        setattr(s.counters, n, int(d["counters"].get(n, 0)))
+    return s
+
+
+def rrtc_pick_ref(states, n_states, ok, to, d=None, use=None, range=0.1, mode=0):
+    """ccmp_rrtc_pick_ref: the pick of a cycle's step 2 (mode 0: TRAPPED / ADVANCED / REACHED / UNSETTLED from the list, the nearest
+    distance d and the range) or step 3 (mode 1: NOTHING / ADDED / JOINED) on host arrays — states (E,max_states,14), n_states (E,), ok
+    (E,), to (E,14) the sample rows (mode 1: the vertices v), use (E,) uint8 or None (0: outcome NONE, 2: no nearest vertex).  Returns a
+    dict: outcome (E,) int32, row_index (E,) int32 (the listed state that becomes the vertex; -1: the target row or none), row (E,14)
+    (zeros without a vertex), gap (E,) (mode 1: the distance of the last stored state to v; NaN without one).  Host only."""
+    st = np.ascontiguousarray(states, dtype=np.float64)
+    E, ms = st.shape[0], st.shape[1]
+    ns, k = HOST.expect(n_states, "int32", E, "n_states"), HOST.expect(ok, "uint8", E, "ok")
+    t = HOST.expect(to, "float64", E * 14, "to")
+    dd = None if d is None else HOST.expect(d, "float64", E, "d")
+    u = None if use is None else HOST.expect(use, "uint8", E, "use")
+    out = {"outcome": np.empty(E, dtype=np.int32), "row_index": np.empty(E, dtype=np.int32), "row": np.empty((E, 14)), "gap": np.empty(E)}
+    check(_lib.lib().ccmp_rrtc_pick_ref(int(mode), _arg(st.reshape(-1)), _arg(ns), _arg(k), _arg(u), _arg(t), _arg(dd), E, int(ms), float(range),
+                                        _arg(out["outcome"]), _arg(out["row_index"]), _arg(out["row"]), _arg(out["gap"])), "ccmp_rrtc_pick_ref")
+    return out
+
+
+def rrtc_pick(ctx, states, n_states, ok, to, d=None, use=None, range=0.1, mode=0, stream=None):
+    """ccmp_rrtc_pick_batch: `rrtc_pick_ref` on device tensors (the pick kernel of a cycle on its own) on the `Context` ctx; the same dict,
+    as device tensors; asynchronous on the stream"""
+    K = kind_of(states)
+    st = K.expect(states, "float64", (None, None, 14), "states")
+    E, ms = st.shape[0], st.shape[1]
+    ns, k, t = K.expect(n_states, "int32", (E,), "n_states"), K.expect(ok, "uint8", (E,), "ok"), K.expect(to, "float64", (E, 14), "to")
+    dd = None if d is None else K.expect(d, "float64", (E,), "d")
+    u = None if use is None else K.expect(use, "uint8", (E,), "use")
+    out = {"outcome": K.empty(E, "int32"), "row_index": K.empty(E, "int32"), "row": K.empty((E, 14), "float64"), "gap": K.empty(E, "float64")}
+    check(_lib.lib().ccmp_rrtc_pick_batch(ctx.handle, int(mode), K.arg(st), K.arg(ns), K.arg(k), K.arg(u), K.arg(t), K.arg(dd), E, int(ms), float(range),
+                                          *[K.arg(a) for a in out.values()], _stream_handle(stream)), "ccmp_rrtc_pick_batch")
+    return out
+
+
+def rrtc_connected_ref(labels, state):
+    """ccmp_rrtc_connected_ref: the solution test on a state dict as `RRTConnect.state` returns it; returns the new state; host only"""
+    lab = HOST.expect(labels, "int32", -1, "labels")
+    s = _rrtc_state_struct(state)
+    check(_lib.lib().ccmp_rrtc_connected_ref(_arg(lab), len(lab), C.byref(s)), "ccmp_rrtc_connected_ref")
+    return _rrtc_state_dict(s)
+
+
+def nearest_in_tree_ref(store_joints, labels, roots, queries):
+    """ccmp_roadmap_nearest_in_tree_ref: `Roadmap.nearest_in_tree` on host arrays, no device: (idx (Q,), dist (Q,))"""
+    sj, lab = HOST.expect(store_joints, "float64", -1, "store_joints").reshape(-1, 14), HOST.expect(labels, "int32", -1, "labels")
+    rt, q = HOST.expect(list(roots), "int32", -1, "roots"), HOST.expect(queries, "float64", -1, "queries").reshape(-1, 14)
+    idx, dist = np.empty(len(q), dtype=np.int32), np.empty(len(q))
+    check(_lib.lib().ccmp_roadmap_nearest_in_tree_ref(_arg(sj, True), _arg(lab, True), len(sj), _arg(rt, True), len(rt), _arg(q, True), len(q), _arg(idx, True),
+                                                      _arg(dist, True)), "ccmp_roadmap_nearest_in_tree_ref")
+    return idx, dist
+
+
+def rrtc_nearest_shape(ctx_handle, Q, N):
+    """ccmp_rrtc_nearest_shape: (rows per partition, partitions) of a nearest-in-tree call of Q queries on N rows; ctx_handle None: a
+    256-CU device.  No result depends on it."""
+    part, parts = C.c_uint(), C.c_uint()
+    check(_lib.lib().ccmp_rrtc_nearest_shape(ctx_handle, int(Q), int(N), C.byref(part), C.byref(parts)), "ccmp_rrtc_nearest_shape")
+    return int(part.value), int(parts.value)
+
+
+class RRTConnect:
+    """ccmp_rrtc: RRT-Connect on a `Roadmap` (`Roadmap.rrt_connect` opens one).  `run(max_cycles)` runs cycles until the status is SOLVED,
+    FULL or the cycles are spent (BUDGET: run again to resume) and returns the report, also kept as `.report`: a dict with status (an
+    RRTC_STATUS key; `status_name` its text), cycles_run, cycles_total, size, edges, solved (start vertex, goal vertex) or None, best_gap
+    and best (its pair, start side first) and counters."""
+
+    def __init__(self, roadmap, scene, handle):
+        self.roadmap, self.scene, self._h = roadmap, scene, handle  # the store and the scene outlive the handle
+        self.report = None
+        self.run(0)
+
+    def run(self, max_cycles):
+        r = _lib.CcmpRrtcReport()
+        check(_lib.lib().ccmp_rrtc_run(self._h, int(max_cycles), C.byref(r)), "ccmp_rrtc_run")
+        self.report = {"status": r.status, "status_name": RRTC_STATUS.get(r.status, "?"), "cycles_run": r.cycles_run, "cycles_total": r.cycles_total,
+                       "size": int(r.size), "edges": int(r.edges), "solved": (r.solved_start, r.solved_goal) if r.status == _lib.RRTC_SOLVED else None,
+                       "best_gap": r.best_gap, "best": (r.best_a, r.best_b), "counters": {n: getattr(r.counters, n) for n in _RRTC_COUNTERS}}
+        return self.report
+
+    def state(self):
+        """the state block (ccmp_rrtc_state) as a dict: starts, goals, status, cycle, next_index, solved_start, solved_goal, best_gap,
+        best_a, best_b, counters"""
+        s = _lib.CcmpRrtcState()
+        check(_lib.lib().ccmp_rrtc_state_read(self._h, C.byref(s)), "ccmp_rrtc_state_read")
+        return _rrtc_state_dict(s)
+
+    def solution(self, max_len=64, host=False):
+        """`Roadmap.shortest_paths` on the solved pair (its dict, one pair), or None while the status is not SOLVED"""
+        if self.report is None or self.report["solved"] is None:
+            return None
+        s, g = self.report["solved"]
+        return self.roadmap.shortest_paths(np.array([s], dtype=np.int32), np.array([g], dtype=np.int32), max_len=max_len, host=host)
+
+    def close(self):
+        if self._h:
+            _lib.lib().ccmp_rrtc_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -705,6 +847,55 @@ class Roadmap:
                                           C.byref(ik_opts) if ik_opts is not None else None, C.byref(o), _arg(gj), int(rng_seed), int(first_index), C.byref(h)),
               "ccmp_plan_create")
         pl = Plan(self, checker, scene, h)
+        if max_cycles:
+            pl.run(max_cycles)
+        return pl
+
+    def nearest_in_tree(self, roots, queries, stream=None):
+        """The nearest vertex, under the joint distance, of each of queries (Q,14) among the vertices whose label is the label of one of
+        roots (at most 8 indices): (idx (Q,) int32, dist (Q,) float64), ranked by (distance, index); idx -1 / dist +inf for an empty tree;
+        NaN (pose-only) vertices are never an answer (ccmp_roadmap_nearest_in_tree).  numpy queries: the synchronous host form (a root
+        outside the store raises); a device tensor: asynchronous, roots a device int32 tensor or a sequence (uploaded)."""
+        K = kind_of(queries)
+        q = K.expect(queries, "float64", (None, 14), "queries")
+        if K is HOST:
+            rt = HOST.expect(list(roots) if not isinstance(roots, np.ndarray) else roots, "int32", -1, "roots")
+        elif hasattr(roots, "data_ptr"):
+            rt = K.expect(roots, "int32", (None,), "roots")
+        else:
+            rt = _torch().from_numpy(np.array(list(roots), dtype=np.int32).reshape(-1)).to(K.device)
+        Q = len(q)
+        idx, dist = K.empty(Q, "int32"), K.empty(Q, "float64")
+        K.call("ccmp_roadmap_nearest_in_tree", "ccmp_roadmap_nearest_in_tree_host", self._h, K.arg(rt, True), len(rt), K.arg(q), Q, K.arg(idx), K.arg(dist),
+               stream=stream)
+        return idx, dist
+
+    def rrt_connect(self, constraint, start_joints=None, goal_joints=None, starts=None, goals=None, scene=None, margin=0.0, width=32, range=0.1,
+                    max_cycles=0, rng_seed=0, first_index=0, **opts):
+        """RRT-Connect on this store (ccmp_rrtc_create: the cycle include/ccmp.h states, and its differences from OMPL's RRTConnect): two
+        trees in joint space grown from `constraint`'s projected sampler, the traversal and — with `scene` / `margin` — the proxy scene's
+        validity test; no object checker, no IK.  starts / goals: indices of vertices already in the store (at most 8 each); or
+        start_joints / goal_joints, joint rows (14,) or (n,14), which are appended here.  width samples per cycle, extensions clipped at
+        `range`; opts: the other fields of ccmp_rrtc_opts (max_states, round_budget, max_vertices).  Runs max_cycles cycles (0: open
+        only) and returns the `RRTConnect`; its `run` resumes it, its `solution()` is `shortest_paths` on the solved pair."""
+        constraint._need_problem()
+
+        def side(idx, joints, what):
+            if (idx is None) == (joints is None):
+                raise ValueError("%s: vertex indices or joint rows, one of the two" % what)
+            if idx is not None:
+                return [int(v) for v in idx]
+            rows = np.ascontiguousarray(np.asarray(joints.cpu() if hasattr(joints, "cpu") else joints, dtype=np.float64).reshape(-1, 14))
+            first = self.append(joints=rows)
+            return list(np.arange(first, first + len(rows)))
+
+        s, g = side(starts, start_joints, "starts"), side(goals, goal_joints, "goals")
+        o = rrtc_options(width=int(width), range=float(range), **opts)
+        sa, ga = np.array(s, dtype=np.int32), np.array(g, dtype=np.int32)
+        h = C.c_void_p()
+        check(_lib.lib().ccmp_rrtc_create(self._h, C.byref(constraint.problem), scene._h if scene is not None else None, float(margin), C.byref(o), _arg(sa, True),
+                                          len(sa), _arg(ga, True), len(ga), int(rng_seed), int(first_index), C.byref(h)), "ccmp_rrtc_create")
+        pl = RRTConnect(self, scene, h)
         if max_cycles:
             pl.run(max_cycles)
         return pl

@@ -1574,6 +1574,136 @@ int ccmp_plan_check_ref(ccmp_plan_state *state, size_t size, const int32_t *a_id
 int ccmp_plan_prefix_ref(const uint8_t valid[9], const uint8_t ik_ok[9], uint8_t vertex_ok[9], int32_t *prefix_len);
 int ccmp_plan_connected_ref(const int32_t *labels, size_t N, ccmp_plan_state *state);
 
+/* ---- RRT-Connect on the store: the reference's other planner ------------------------------------------------------------------------------ */
+/* The reference offers RRT, RRTConnect and StefanBiPRM behind ConstrainedProblem::setPlanner (ConstrainedPlanningCommon.h:141-157, the
+ * commented switch at src/main.cpp:46-47); ccmp_plan_* above is the third, this is the second: two trees in JOINT space, grown from
+ * nothing but the constraint, the projected sampler and a validity test — no object checker, no IK.  A ccmp_rrtc is a resumable
+ * sibling of ccmp_plan on a roadmap store; csrc/ccmp_rrtc.h states its rule once, for the kernels of ccmp_kernels_rrtc.hip and for the
+ * *_ref forms.  The caller has appended up to CCMP_PLAN_MAX_STARTS start vertices and CCMP_PLAN_MAX_GOALS goal vertices and hands over
+ * their indices (host arrays).  A side's TREE is every vertex v whose label[v] equals the label of one of that side's roots: no
+ * per-vertex array is kept, vertices of other components are ignored, pose-only vertices (NaN joints) are never a nearest neighbour.
+ *   nearest_in_tree   for each of queries [Q][14]: the vertex with the smallest (ccmp_joint_distance(joints[v], query), v) among the
+ *       vertices of the tree of roots [n_roots], 0 <= n_roots <= 8 — the arithmetic of ccmp_knn_batch (the FMA chain, then the correctly
+ *       rounded square root), so with every vertex in the tree the answer is ccmp_roadmap_knn's with CCMP_METRIC_JOINT and k = 1.  A NaN
+ *       distance is never a candidate; no candidate: idx -1, dist +inf.  roots is a device pointer in the device form; a root outside
+ *       [0, size) is CCMP_EINVAL from the _host and _ref forms and contributes no label in the device form.  Asynchronous and capturable
+ *       (after one eager call at that size: the partitions' bests go through the context's k-NN workspace).  The result is a function of
+ *       the arguments alone: (distance, index) is a total order and the reduction compares pairs, so the launch shape
+ *       (csrc/ccmp_policy.cpp: plan_rrtc_nearest, from Q, N and the CU count; no option) never changes it.  ccmp_rrtc_nearest_shape
+ *       reports that shape (ctx NULL: a 256-CU device), for tests and tools.
+ *   one cycle (ccmp_rrtc_run runs up to max_cycles of them)
+ *     0. FULL      size + 2 width > max_vertices: status CCMP_RRTC_FULL, nothing runs.
+ *     1. samples   width rows of ccmp_sample_project_batch at draw indices next_index .. next_index + width - 1; next_index += width.  A
+ *                  row whose projection failed or which is not jointValid (ccmp_joint_valid_batch) is no sample and is counted
+ *                  (samples - projected); with a scene neither is a row whose clearance (ccmp_clearance_batch) is not above the margin.
+ *     2. extend    tree A = the start side in even cycles, the goal side in odd ones.  n = nearest_in_tree(A, sample), d its distance;
+ *                  ONE traversal n -> sample through ccmp_geodesic_scene_batch (with a scene) or ccmp_geodesic_batch_ex, with max_states,
+ *                  round_budget and check_target = 0.  With m = min(n_states, max_states) listed states, s_0 = 0, s_j = fl(s_{j-1} +
+ *                  ccmp_joint_distance(state_{j-1}, state_j)) and cut = (n_states > max_states or ok == 2), the pick decides (rrtc_extend of
+ *                  csrc/ccmp_rrtc.h; on its own: ccmp_rrtc_pick_ref / ccmp_rrtc_pick_batch):
+ *                    d <= range   ok == 1: REACHED, the new vertex is the sample row itself; else cut: UNSETTLED; else TRAPPED.
+ *                    d > range    m < 2: TRAPPED.  Else j = the largest listed index with s_j <= range, but at least 1.  cut, j == m - 1
+ *                                 and s_j <= range: UNSETTLED (the arc was not used up inside the list).  Otherwise ADVANCED, the new
+ *                                 vertex is listed state j.
+ *                    a NaN in d, in range or in any s_j, or no nearest vertex: TRAPPED.
+ *                  An UNSETTLED sample is skipped and counted, as ccmp_plan does.
+ *     3. connect   for every vertex v that step 2 produced: u = nearest_in_tree(B, v) with B the OTHER side as of cycle entry, ONE traversal
+ *                  u -> v with the same list length: ok == 1: the edge (u, v), the trees are joined (JOINED); else with two or more
+ *                  listed states the last stored state becomes a vertex of B with the edge (u, that state) (ADDED: a cut list and a
+ *                  blocked list count here too — every listed state passed the validity test, so this is valid progress); else NOTHING.
+ *                  gap = ccmp_joint_distance(last stored state, v); the smallest gap seen so far (strict <, samples in ascending order)
+ *                  is kept as best_gap with its pair (best_a on the start side, best_b on the goal side): the approximate solution's pair.
+ *     4. commit    new indices in a total order: step 2's vertices in ascending sample order, then step 3's in ascending sample order;
+ *                  the edges likewise, each (tree vertex, new vertex).  The rows go through ccmp_roadmap_append, the fixed-size uv array
+ *                  (an entry of a sample without an edge is (-1, -1)) through ccmp_roadmap_add_edges: weights and labels are that call's.
+ *     5. cycle += 1, then the solution test: the first pair (s, g), start-major and goal-minor, whose labels agree gives
+ *                  CCMP_RRTC_SOLVED and the pair.  The path is ccmp_roadmap_shortest_paths' on that pair.
+ *   The samples of a cycle do not see each other; with width == 1 a cycle is one iteration of the sequential algorithm.
+ *
+ *   STATED DIFFERENCES FROM OMPL'S RRTConnect
+ *   (a) One traversal per extension, clipped at range.  OMPL runs interpolate(n, sample, range / d) and then a fresh checkMotion(n,
+ *       dstate); its constrained interpolate returns the listed state NEARER to the fraction of the achieved length.  Here one traversal
+ *       is clipped at an absolute arc, with at least one step of progress.  With the reference's own values, range 0.1
+ *       (ConstrainedPlanningCommon.cpp:124) and delta 0.25 (:118), the nearer-state rule returns `from` itself whenever the first listed
+ *       step is longer than 2 range, and OMPL then answers TRAPPED (DESIGN.md §5.22 records the share).
+ *   (b) The connect phase is one traversal and adds its end state; OMPL adds a chain of range-spaced vertices.
+ *   (c) UNSETTLED is skipped, not continued.
+ *   (d) Both trees extend from the tree vertex towards the target; OMPL checks the goal tree's motion in the other direction.
+ *   (e) The random numbers are the library's counter-based draws, not OMPL's RNG.
+ *   (f) Validity is the proxy scene's, not MoveIt's; isValid over the dense rows of a solution stays a host call.
+ *   What follows from (a) and (d): an edge (parent, child) was validated as a PREFIX of a traversal towards something else.
+ *   ccmp_path_densify runs a fresh traversal parent -> child, and child -> parent where the path uses the edge reversed; that traversal
+ *   is expected to arrive, it is not guaranteed to (its seg_ok says).
+ *
+ * ccmp_rrtc_create checks, uploads the state and runs the solution test once (roots that already share a component: SOLVED, cycle 0);
+ * it remembers the store and the scene, which must outlive it.  ccmp_rrtc_run is synchronous and not capturable; it waits for the device
+ * at entry.  Per cycle the host reads 16 bytes of counts after the commit kernel and the state block at the end, besides the read-back
+ * of ccmp_roadmap_add_edges.  After CCMP_RRTC_SOLVED a run returns at once with the same report.  Every check comes before the first
+ * launch; a NULL store / handle answers CCMP_ENODEV on a machine without a HIP device and CCMP_EINVAL otherwise.  CCMP_EINVAL: a root
+ * outside [0, size), n_starts or n_goals of 0 or above the caps, width outside 1 .. CCMP_PLAN_MAX_WIDTH, a non-finite or non-positive
+ * range, a NaN margin, max_states < 2, round_budget < 0, max_vertices beyond 2^31 - 1, a scene of another device than the store's, a NULL
+ * or invalid problem, NULL opts, starts, goals or out.
+ * The *_ref forms are the rule on host memory: no device, never CCMP_ENODEV.
+ *   ccmp_rrtc_pick_ref        mode 0 (extend) / 1 (connect) on E lists: states [E][max_states][14], n_states [E], ok [E], use [E]
+ *                             (nullable; 0: no sample / no vertex -> outcome CCMP_RRTC_NONE, 2: no nearest vertex -> TRAPPED / NOTHING),
+ *                             to [E][14] (the sample / v), d [E] (mode 0: the nearest distance) -> outcome [E], row_index [E] (the listed
+ *                             state that becomes the vertex, -1: the target row or none), row [E][14] (zeros without a vertex), gap [E]
+ *                             (nullable; mode 1, NaN without a listed state).
+ *   ccmp_rrtc_connected_ref   labels [N], state -> state (status, solved pair); an index outside [0, N) never matches. */
+enum { CCMP_RRTC_OPEN = 0, CCMP_RRTC_SOLVED = 1, CCMP_RRTC_BUDGET = 2, CCMP_RRTC_FULL = 3 };
+enum { CCMP_RRTC_NONE = -1, CCMP_RRTC_TRAPPED = 0, CCMP_RRTC_ADVANCED = 1, CCMP_RRTC_REACHED = 2, CCMP_RRTC_UNSETTLED = 3 };
+enum { CCMP_RRTC_CONNECT_NOTHING = 0, CCMP_RRTC_CONNECT_ADDED = 1, CCMP_RRTC_CONNECT_JOINED = 2 };
+#define CCMP_RRTC_MAX_ROOTS 8
+typedef struct ccmp_rrtc_opts {
+  int32_t width;         /* 32     samples per cycle */
+  int32_t max_states;    /* 64     the traversals' list length */
+  int32_t round_budget;  /* 0      the traversals' Newton-round bound (0: none) */
+  int32_t reserved;
+  double range;          /* 0.1    the reference's (ConstrainedPlanningCommon.cpp:124) */
+  uint64_t max_vertices; /* 2^31 - 1 */
+} ccmp_rrtc_opts;
+typedef struct ccmp_rrtc_counters {
+  int32_t samples, projected, trapped, advanced, reached, unsettled, connect_reached, connect_added, connect_nothing, vertices, edges, reserved;
+} ccmp_rrtc_counters;
+typedef struct ccmp_rrtc_state {
+  int32_t n_starts, n_goals;
+  int32_t starts[CCMP_PLAN_MAX_STARTS], goals[CCMP_PLAN_MAX_GOALS];
+  int32_t status, cycle;
+  uint64_t next_index;
+  int32_t solved_start, solved_goal; /* vertices; -1 until SOLVED */
+  int32_t best_a, best_b;            /* the pair of best_gap: a start-side and a goal-side vertex; -1 until a connect traversal ran */
+  double best_gap;                   /* +inf until then */
+  ccmp_rrtc_counters counters;
+} ccmp_rrtc_state;
+typedef struct ccmp_rrtc_report {
+  int32_t status, cycles_run, cycles_total, reserved;
+  uint64_t size, edges;
+  int32_t solved_start, solved_goal, best_a, best_b;
+  double best_gap;
+  ccmp_rrtc_counters counters;
+} ccmp_rrtc_report;
+typedef struct ccmp_rrtc ccmp_rrtc;
+void ccmp_rrtc_default_opts(ccmp_rrtc_opts *opts);
+int ccmp_rrtc_create(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_rrtc_opts *opts, const int32_t *starts,
+                     int n_starts, const int32_t *goals, int n_goals, uint64_t rng_seed, uint64_t first_index, ccmp_rrtc **out);
+int ccmp_rrtc_run(ccmp_rrtc *plan, int max_cycles, ccmp_rrtc_report *out);
+int ccmp_rrtc_state_read(ccmp_rrtc *plan, ccmp_rrtc_state *out);
+void ccmp_rrtc_destroy(ccmp_rrtc *plan);
+int ccmp_roadmap_nearest_in_tree(ccmp_roadmap *rm, const int32_t *roots, int n_roots, const double *queries, size_t Q, int32_t *idx, double *dist,
+                                 void *hip_stream);
+int ccmp_roadmap_nearest_in_tree_host(ccmp_roadmap *rm, const int32_t *roots, int n_roots, const double *queries, size_t Q, int32_t *idx, double *dist);
+int ccmp_roadmap_nearest_in_tree_ref(const double *store_joints, const int32_t *labels, size_t N, const int32_t *roots, int n_roots, const double *queries,
+                                     size_t Q, int32_t *idx, double *dist);
+int ccmp_rrtc_nearest_shape(const ccmp_ctx *ctx, size_t Q, size_t N, unsigned int *part, unsigned int *partitions);
+int ccmp_rrtc_pick_ref(int mode, const double *states, const int32_t *n_states, const uint8_t *ok, const uint8_t *use, const double *to, const double *d,
+                       size_t E, int max_states, double range, int32_t *outcome, int32_t *row_index, double *row, double *gap);
+int ccmp_rrtc_connected_ref(const int32_t *labels, size_t N, ccmp_rrtc_state *state);
+/* ccmp_rrtc_pick_ref's arguments as device pointers: the pick kernel of a cycle on its own (rrtc_pick_kernel, sixteen lanes per list),
+ * asynchronous on hip_stream and capturable; the same bits as the _ref form */
+int ccmp_rrtc_pick_batch(ccmp_ctx *ctx, int mode, const double *states, const int32_t *n_states, const uint8_t *ok, const uint8_t *use, const double *to,
+                         const double *d, size_t E, int max_states, double range, int32_t *outcome, int32_t *row_index, double *row, double *gap,
+                         void *hip_stream);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 /* (test and tool hooks — the device probe of ccmp_detmath.h, an externally supplied processing order, the scout's predictions, fault
  * injection — are not part of this library: include/ccmp_debug.h, lib/libccmp_debug.so) */

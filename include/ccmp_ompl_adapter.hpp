@@ -1395,6 +1395,13 @@ public:
             const ccmp_scene *scene = nullptr, double margin = 0.0, const double *goal_joints14 = nullptr, uint64_t rng_seed = 0,
             ccmp_plan_report *report = nullptr) noexcept;
 
+  // RRT-Connect on this store in one call (ccmp::RRTConnectPlanner below: open on the given start and goal vertices, then up to
+  // max_cycles cycles): the status (CCMP_RRTC_*) and, when it is CCMP_RRTC_SOLVED, the connected pair in *start / *goal — the path is
+  // shortestPaths' on that pair.  No object checker and no IK; scene: ProxyScene::handle() or nullptr.  -1 when a call failed.
+  int solveRRTConnect(const int32_t *starts, int n_starts, const int32_t *goals, int n_goals, int max_cycles, int32_t *start = nullptr, int32_t *goal = nullptr,
+                      const ccmp_rrtc_opts *opts = nullptr, const ccmp_scene *scene = nullptr, double margin = 0.0, uint64_t rng_seed = 0,
+                      ccmp_rrtc_report *report = nullptr) noexcept;
+
   int lastError() const noexcept { return err_.code(); }
   std::string lastErrorMessage() const { return err_.message(); }
   void clearError() noexcept { err_.clear(); }
@@ -1842,6 +1849,105 @@ inline int Roadmap::solve(const ccmp_object *object, int max_cycles, int32_t *st
   if (start) *start = -1;
   if (goal) *goal = -1;
   Planner planner(*this, object, o, scene, margin, goal_joints14, rng_seed);
+  if (planner.create() && max_cycles > 0) planner.run(max_cycles);
+  if (report) *report = planner.report();
+  if (planner.lastError() != CCMP_OK) {
+    err_.recordAs(planner.lastError(), planner.lastErrorMessage().c_str());
+    return -1;
+  }
+  if (planner.solved()) {
+    if (start) *start = planner.report().solved_start;
+    if (goal) *goal = planner.report().solved_goal;
+  }
+  return planner.status();
+}
+
+// ---- RRT-Connect on the store (include/ccmp.h: ccmp_rrtc_*) ---------------------------------------------------------------------------
+// The reference's other planner (ConstrainedProblem::setPlanner(RRTConnect)) as one resumable object: two trees in joint space over the
+// store's component labels, width samples per cycle, one traversal per extension clipped at `range`, one traversal per connection.  NOT
+// OMPL's RRTConnect step for step: include/ccmp.h lists the stated differences (one clipped traversal, a one-traversal connect phase,
+// unsettled extensions skipped, both trees extend from the tree vertex, counter-based draws, the proxy scene's validity).
+struct RRTConnectOptions : ccmp_rrtc_opts {
+  RRTConnectOptions() noexcept { ccmp_rrtc_default_opts(this); }
+};
+
+// Never throws: a planner that could not be opened answers "no" to every verb and keeps the FIRST failure in lastError() /
+// lastErrorMessage() until clearError(), as ccmp::Planner does.  The store and the scene must outlive it.
+class RRTConnectPlanner {
+public:
+  RRTConnectPlanner(Roadmap &roadmap, const int32_t *starts, int n_starts, const int32_t *goals, int n_goals, const RRTConnectOptions &opts = RRTConnectOptions(),
+                    const ccmp_scene *scene = nullptr, double margin = 0.0, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept
+      : mu_(&roadmap.projector().mutex())
+  {
+    open(roadmap.handle(), &roadmap.projector().problem(), scene, margin, opts, starts, n_starts, goals, n_goals, rng_seed, first_index);
+  }
+  // the same on the C handles (a caller without a Projector); serialised by a mutex of its own
+  RRTConnectPlanner(ccmp_roadmap *roadmap, const ccmp_problem &problem, const int32_t *starts, int n_starts, const int32_t *goals, int n_goals,
+                    const RRTConnectOptions &opts = RRTConnectOptions(), const ccmp_scene *scene = nullptr, double margin = 0.0, uint64_t rng_seed = 0,
+                    uint64_t first_index = 0) noexcept
+      : mu_(&own_mu_)
+  {
+    open(roadmap, &problem, scene, margin, opts, starts, n_starts, goals, n_goals, rng_seed, first_index);
+  }
+  ~RRTConnectPlanner()
+  {
+    if (!plan_) return;
+    std::lock_guard<std::mutex> hold(*mu_);
+    ccmp_rrtc_destroy(plan_);
+  }
+  RRTConnectPlanner(const RRTConnectPlanner &) = delete;
+  RRTConnectPlanner &operator=(const RRTConnectPlanner &) = delete;
+
+  bool create() const noexcept { return plan_ != nullptr; } // was it opened
+  // up to max_cycles more cycles; true = the call ran (report() has the verdict), false = it failed or there is no planner
+  bool run(int max_cycles) noexcept
+  {
+    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_rrtc_run", [&] { return ccmp_rrtc_run(plan_, max_cycles, &report_); });
+  }
+  const ccmp_rrtc_report &report() const noexcept { return report_; }
+  int status() const noexcept { return plan_ ? report_.status : -1; }
+  bool solved() const noexcept { return plan_ && report_.status == CCMP_RRTC_SOLVED; }
+  bool state(ccmp_rrtc_state *out) const noexcept
+  {
+    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_rrtc_state_read", [&] { return ccmp_rrtc_state_read(plan_, out); });
+  }
+  int lastError() const noexcept { return err_.code(); }
+  std::string lastErrorMessage() const { return err_.message(); }
+  void clearError() noexcept { err_.clear(); }
+  ccmp_rrtc *handle() const noexcept { return plan_; }
+
+private:
+  void open(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_rrtc_opts &opts, const int32_t *starts, int n_starts,
+            const int32_t *goals, int n_goals, uint64_t rng_seed, uint64_t first_index) noexcept
+  {
+    std::memset(&report_, 0, sizeof report_);
+    report_.status = -1;
+    report_.solved_start = report_.solved_goal = report_.best_a = report_.best_b = -1;
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(*mu_);
+      rc = ccmp_rrtc_create(rm, p, scene, margin, &opts, starts, n_starts, goals, n_goals, rng_seed, first_index, &plan_); // a NULL store: the library's own answer
+      if (rc == CCMP_OK) rc = ccmp_rrtc_run(plan_, 0, &report_);
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) err_.record(rc, "ccmp_rrtc_create");
+  }
+  std::mutex own_mu_;
+  std::mutex *mu_;
+  ccmp_rrtc *plan_ = nullptr;
+  ccmp_rrtc_report report_;
+  mutable detail::ErrorLatch err_;
+};
+
+inline int Roadmap::solveRRTConnect(const int32_t *starts, int n_starts, const int32_t *goals, int n_goals, int max_cycles, int32_t *start, int32_t *goal,
+                                    const ccmp_rrtc_opts *opts, const ccmp_scene *scene, double margin, uint64_t rng_seed, ccmp_rrtc_report *report) noexcept
+{
+  RRTConnectOptions o;
+  if (opts) static_cast<ccmp_rrtc_opts &>(o) = *opts;
+  if (start) *start = -1;
+  if (goal) *goal = -1;
+  RRTConnectPlanner planner(*this, starts, n_starts, goals, n_goals, o, scene, margin, rng_seed);
   if (planner.create() && max_cycles > 0) planner.run(max_cycles);
   if (report) *report = planner.report();
   if (planner.lastError() != CCMP_OK) {

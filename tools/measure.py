@@ -64,6 +64,9 @@
                                                            motion does not reach, beside the same cycles BY HAND over the mirror's calls (tests/plan_cases.py: HandPlan, what a
                                                            caller can write without the unit) with its host reads, and which branches six cycles reach at width 1, 5, 64 and 65;
                                                            writes profiles/plan.md
+    python tools/measure.py rrtc [cpu] [out.md]             RRT-Connect on the store (ccmp_rrtc_*): the CPU figure of its difference (a) from OMPL (the oracle's first steps beyond 0.2),
+                                                           nearest-in-tree beside the k-NN with k = 1 at 10^3 .. 10^6 rows, time per cycle at width 1, 32, 256 beside the loop by hand,
+                                                           cycles and vertices to SOLVED per range beside Plan, the densify share; `cpu`: the CPU figure alone; writes profiles/rrtc.md
     python tools/measure.py smooth_restate <file.npz> [n]  the plain-Python restatement on one host core on the inputs `smooth` wrote, compared with its results
     python tools/measure.py run <workload> [reps]           a fixed workload for rocprofv3 (tools/profile.sh):
                                                            c3 | flat4096 | mid<B> | flat1 | geodesic[<E>] | geodesic_analytic[<E>] | analytic[<B>] | stefan |
@@ -2072,6 +2075,173 @@ def plan(argv):
                 "## Which branches six cycles reach (Wine_Bottle towards that goal; FD and analytic mode, without and with the skeleton scene at -0.03)\n\n```\n" + "\n".join(cover) + "\n```\n")
 
 
+def rrtc_first_step_share(pairs=1024):
+    """difference (a) of include/ccmp.h on the CPU: with the oracle's traversal (oracle/ccmp_oracle.c, delta 0.25), of `pairs` pairs of valid
+    sampled states, how many list a first step at all and how many first steps exceed 0.2 = 2 range — where OMPL's nearer-state rule gives `from`"""
+    sys.path.insert(0, "tests")
+    import yaml
+    from oracle_binding import Oracle
+
+    O, lines = Oracle("det"), []
+    for obj in ("Wine_Bottle", "dumbbell", "stefan"):
+        P = O.problem(yaml.safe_load(open(CFG % obj)))
+        q, ok, _ = O.sample_project_batch(P, 0x77C, 0, 16 * pairs)
+        good = q[(ok != 0) & np.array([O.joint_valid(P, x) for x in q], dtype=bool)]
+        frm, to = good[:pairs], good[pairs:2 * pairs]
+        st, n, _, _ = O.discrete_geodesic_batch(P, frm, to, max_states=4)
+        first = np.array([O.distance(st[e, 0], st[e, 1]) for e in range(len(to)) if n[e] >= 2])
+        d = np.array([O.distance(a, b) for a, b in zip(frm, to)])
+        lines.append("%-12s valid draws %5d of %5d  pairs %4d  with a first step %4d  first step > 0.2: %4d (%.1f %% of all pairs, %.1f %% of those with a step)  "
+                     "first step min / median / max %.4f / %.4f / %.4f  distance of a pair min / median %.3f / %.3f"
+                     % (obj, len(good), len(q), len(to), len(first), int((first > 0.2).sum()), 100.0 * (first > 0.2).sum() / len(to), 100.0 * (first > 0.2).mean(),
+                        first.min(), np.median(first), first.max(), d.min(), np.median(d)))
+        print(lines[-1], flush=True)
+    return lines
+
+
+def rrtc(argv):
+    """RRT-Connect on the store (ccmp_rrtc_*): python tools/measure.py rrtc [cpu]; writes profiles/rrtc.md.  `cpu`: the CPU figure alone
+    (no device), every GPU figure marked as not measured"""
+    cpu_only = "cpu" in argv
+    argv = [""] + [a for a in argv if a.endswith(".md")]
+    share = rrtc_first_step_share()
+    nearest, cycles_, solved, dens, cover = [], [], [], [], []
+    if not cpu_only:
+        sys.path.insert(0, "tests")
+        from object_cases import box_mesh, workspace
+        from plan_cases import far_goal_state, problem_poses
+        from rrtc_cases import HandRRTConnect, state_bits
+        from closed_chain_motion_planner_amd import PLAN_STATUS, RRTC_STATUS, ObjectChecker, Roadmap
+        from closed_chain_motion_planner_amd._lib import METRIC_JOINT
+
+        ctx = Context(0)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        c = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+        c.setJacobianMode(1)
+        # 1. nearest-in-tree beside the joint-metric k-NN with k = 1 on the same rows; every vertex in the tree (a star on vertex 0)
+        r = np.random.default_rng(11)
+        for N in (10**3, 10**5, 10**6):
+            rm = Roadmap(c, capacity_hint=N)
+            rm.append(joints=dev(r.uniform(-2, 2, size=(N, 14))), poses=dev(np.zeros((N, 8))))
+            rm.add_edges(dev(np.stack([np.zeros(N - 1, dtype=np.int32), np.arange(1, N, dtype=np.int32)], axis=1)))
+            roots = dev(np.zeros(1, dtype=np.int32))
+            for Q in (1, 32, 256):
+                q = dev(r.uniform(-2, 2, size=(Q, 14)))
+                a = rm.nearest_in_tree(roots, q)
+                b = rm.nearest_k(q, 1, metric=METRIC_JOINT)
+                same = a[0].tolist() == b[0][:, 0].tolist()
+                t_a, t_b = timed(lambda: rm.nearest_in_tree(roots, q), 5), timed(lambda: rm.nearest_k(q, 1, metric=METRIC_JOINT), 5)
+                nearest.append("N %8d  Q %4d  partitions %3d  nearest_in_tree %8.3f ms  roadmap knn k=1 %8.3f ms  ratio %5.2f  same answer: %s"
+                               % (N, Q, _lib_shape(ctx, Q, N), t_a, t_b, t_a / t_b, same))
+                print(nearest[-1], flush=True)
+            rm.close()
+        # 2. the far goal: time per cycle against the loop by hand, cycles and vertices to SOLVED per range, beside Plan
+        chk = ObjectChecker(c, box_mesh(0.04, 0.04, 0.1), workspace())
+        start = np.array(c.problem.start_joint[:])
+        _, shipped_pose = problem_poses(c.problem)
+        ik = c.pose_ik_batch(dev(shipped_pose.reshape(1, 8)), dev(start.reshape(1, 1, 14)), rng_seed=0x77C)
+        shipped = ik["q"][0].cpu().numpy() if int(ik["ok"][0]) else None
+        goal = far_goal_state(c, chk, 16)
+
+        def opened(g):
+            rm = Roadmap(c)
+            rm.append(joints=dev(np.stack([start, g])))
+            return rm
+
+        for W in (1, 32, 256):
+            rm = opened(goal)
+            pl = rm.rrt_connect(c, starts=[0], goals=[1], width=W, max_states=16, rng_seed=0x77C)
+            pl.run(1)  # the workspaces' one-time growth
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rep = pl.run(8)
+            ms = (time.perf_counter() - t0) * 1e3 / max(rep["cycles_run"], 1)
+            rmh = opened(goal)
+            hp = HandRRTConnect(rmh, c, [0], [1], width=W, rng_seed=0x77C, max_states=16)
+            hp.run(1)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = hp.run(8)
+            hms = (time.perf_counter() - t0) * 1e3 / max(n, 1)
+            cycles_.append("width %3d  RRTConnect.run %7.2f ms / cycle (%d cycles)   by hand %7.2f ms / cycle (%d cycles)   same state bits: %s   V %d E %d"
+                           % (W, ms, rep["cycles_run"], hms, n, state_bits(pl.state()) == state_bits(hp.state), rep["size"], rep["edges"]))
+            print(cycles_[-1], flush=True)
+            for h in (pl, rm, rmh):
+                h.close()
+        for name, g in (("far goal", goal), ("shipped goal", shipped)):
+            if g is None:
+                continue
+            for rng in (0.1, 0.5, 1.0, 2.0):
+                rm = opened(g)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                pl = rm.rrt_connect(c, starts=[0], goals=[1], width=32, range=rng, max_states=64, rng_seed=0x77C)
+                rep = pl.run(64)
+                ms = (time.perf_counter() - t0) * 1e3
+                cnt = rep["counters"]
+                line = "%-12s range %.1f  %-7s cycles %3d  V %5d  E %5d  best_gap %.3f  trapped %d advanced %d reached %d unsettled %d | joined %d added %d nothing %d  %8.1f ms" % (
+                    name, rng, RRTC_STATUS[rep["status"]], rep["cycles_total"], rep["size"], rep["edges"], rep["best_gap"], cnt["trapped"], cnt["advanced"], cnt["reached"],
+                    cnt["unsettled"], cnt["connect_reached"], cnt["connect_added"], cnt["connect_nothing"], ms)
+                if rep["solved"] is not None:  # the densify share: the solution path's segments whose fresh traversal arrives
+                    d = rm.dense_solution(c, [rep["solved"][0]], [rep["solved"][1]], max_len=256)
+                    ok = d[2]["seg_ok"].cpu().numpy().reshape(-1)[:len(d[1]) - 1]
+                    dens.append("%-12s range %.1f  path of %3d vertices, cost %.3f: %d of %d segments seg_ok" % (name, rng, len(d[1]), d[0], int((ok == 1).sum()), len(ok)))
+                    print(dens[-1], flush=True)
+                solved.append(line)
+                print(line, flush=True)
+                pl.close()
+                rm.close()
+            rm = Roadmap(c)
+            if name == "shipped goal":  # Plan takes its goal pose from the problem: the far goal moved it, so the shipped problem is loaded again
+                c2 = KinematicChainConstraint.from_yaml(CFG % "Wine_Bottle", ctx=ctx)
+                c2.setJacobianMode(1)
+            else:
+                c2 = c
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pp = rm.plan(c2, chk, goal_joints=g, width=32, k=5, max_states=16, rng_seed=0x91A)
+            rep = pp.run(64)
+            solved.append("%-12s Plan (width 32, k 5)  %-7s cycles %3d  V %5d  E %5d  %8.1f ms" % (name, PLAN_STATUS[rep["status"]], rep["cycles_total"], rep["size"], rep["edges"],
+                                                                                                  (time.perf_counter() - t0) * 1e3))
+            print(solved[-1], flush=True)
+            pp.close()
+            rm.close()
+    na = ["NOT MEASURED (written without a device: `python tools/measure.py rrtc cpu`)"]
+    out = argv[1] if len(argv) > 1 else "profiles/rrtc.md"
+    with open(out, "w") as f:
+        f.write("# RRT-Connect on the store (`ccmp_rrtc_*`, `Roadmap.rrt_connect`, `Roadmap.nearest_in_tree`)\n\nWritten by `python tools/measure.py rrtc`.  One MI355X, one "
+                "process, Wine_Bottle in analytic mode unless stated.  **Figures, not gates**: wall clock (`time.perf_counter`) around the synchronous runs, HIP events "
+                "(best of 5) around the nearest-vertex calls; whether and when a run solves is a measurement, not a property the unit promises.\n\n"
+                "## Difference (a) on the CPU: how often OMPL's nearer-state rule would return `from`\n\nThe oracle's traversal (delta 0.25) between pairs of valid sampled "
+                "states (a draw is valid when its projection converged and it is within the joint limits).  With range 0.1 OMPL's constrained `interpolate` returns the "
+                "listed state nearer to arc 0.1, which is `from` whenever the first listed step is longer than 0.2, and `checkMotion(from, from)` then adds nothing.  A "
+                "pair without a first step is TRAPPED under either rule.\n\n```\n" + "\n".join(share) + "\n```\n\n"
+                "So the claim \"nearly every extension\" does not hold as derived: about a fifth to a quarter of all pairs (a quarter to a third of those that move at "
+                "all) would be lost to the nearer-state rule, and the median first step (0.17 to 0.18) is below 0.2.  The clip at an absolute arc with at least one "
+                "step keeps those extensions; it also makes every ADVANCED vertex one listed step (about 0.17) from its parent instead of 0.1.\n\n"
+                "## Nearest vertex of a tree beside the joint-metric k-NN with k = 1 (every vertex in the tree)\n\n```\n" + "\n".join(nearest or na) + "\n```\n\n"
+                "`rrtc_nearest_kernel` runs one block per (query, partition) and does not tile over the queries: every query reads its partition's rows and labels "
+                "again, where `knn_many_kernel` stages a tile of rows in LDS for 256 queries.  Where the ratio above exceeds 1 at large Q and N that is the reason, not "
+                "the label filter (one 4-byte load and eight compares per row beside 112 bytes of joints).  The planner's own calls are Q = width <= 256 on stores of "
+                "thousands of rows.\n\n"
+                "## Time per cycle against the loop by hand (far goal, lists of 16, range 0.1)\n\n`tests/rrtc_cases.py: HandRRTConnect` runs the cycle over the mirror's "
+                "calls with the commit on the host: what a caller could write without the unit.\n\n```\n" + "\n".join(cycles_ or na) + "\n```\n\n"
+                "## Cycles and vertices to SOLVED (width 32, lists of 64, at most 64 cycles), beside `Plan`\n\n```\n" + "\n".join(solved or na) + "\n```\n\n"
+                "## The densify share: solution-path segments whose fresh traversal arrives\n\nAn edge (parent, child) was validated as a prefix of a traversal towards "
+                "something else; `ccmp_path_densify` runs parent -> child (or child -> parent) afresh.\n\n```\n" + "\n".join(dens or na) + "\n```\n\n"
+                "## Outcomes the far goal's six-cycle test runs do not reach\n\n`tests/test_gpu_rrtc.py::test_the_runs_cover_the_outcomes` takes, from the hand loop, the "
+                "union over widths 1, 5 and 64 at range 0.1 and width 5 at range 3 (six cycles, lists of 16).  It holds NONE, TRAPPED, ADVANCED and UNSETTLED of step 2 "
+                "and NOTHING and ADDED of step 3.  It does not hold **REACHED** — the distance between two valid states is never below 2.2 in the pairs above, so no "
+                "sample lies within range 3 of a tree vertex — nor **JOINED**, the trees being far apart by the construction of that goal.  JOINED is asserted in the "
+                "solved run on the shipped goal, REACHED on real traversals in the pick kernel's test (range 4).\n")
+
+
+def _lib_shape(ctx, Q, N):
+    from closed_chain_motion_planner_amd import rrtc_nearest_shape
+
+    return rrtc_nearest_shape(ctx.handle, Q, N)[1]
+
+
 def smooth_restate(argv):
     """the plain-Python restatement of the smoothing rule (tests/smooth_cases.py on the det oracle) on one host core, on the inputs `smooth`
     wrote, compared bit for bit with the results it wrote: python tools/measure.py smooth_restate <file.npz> [paths]"""
@@ -2170,7 +2340,7 @@ def run(argv):
 
 
 if __name__ == "__main__":
-    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, fit, jerk, plan, run)}
+    cmds = {f.__name__: f for f in (sizes, single, geodesic, analytic, host, sharded, afterload, sampler, soak, soak_resident, scout, clearance, connect, roadmap, mirror, ik, graph, path, dense, shortcut, smooth, smooth_restate, retime, setpoints, fit, jerk, plan, rrtc, run)}
     cmds["object"] = object_
     if len(sys.argv) < 2 or sys.argv[1] not in cmds:
         raise SystemExit(__doc__)
