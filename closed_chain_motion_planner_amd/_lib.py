@@ -207,7 +207,7 @@ EXPORTS = [
 _lib = None
 # include/ccmp_debug.h: exported by lib/libccmp_debug.so only (the same sources with -DCCMP_DEBUG_HOOKS; select it with CCMP_LIBRARY)
 DEBUG_EXPORTS = ["ccmp_detmath_probe", "ccmp_detmath_div_probe", "ccmp_ctx_set_order_experimental", "ccmp_ctx_debug_lpt_pred", "ccmp_debug_fail_calls",
-                 "ccmp_ctx_debug_lpt_order", "ccmp_debug_sort_probe", "ccmp_debug_split_probe", "ccmp_detmath_round_facts_probe"]
+                 "ccmp_ctx_debug_lpt_order", "ccmp_debug_sort_probe", "ccmp_debug_split_probe", "ccmp_detmath_round_facts_probe", "ccmp_ctx_debug_fd_state"]
 DEBUG_LIBPATH = os.path.join(os.path.dirname(LIBPATH), "libccmp_debug.so")
 
 
@@ -476,6 +476,7 @@ def lib():
         "ccmp_detmath_round_facts_probe": ([vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
         "ccmp_debug_fail_calls": ([vp, C.c_int], C.c_int),
         "ccmp_ctx_debug_lpt_order": ([vp, vp, C.c_size_t, vp, vp, C.c_size_t], C.c_int),
+        "ccmp_ctx_debug_fd_state": ([vp, vp, C.c_size_t, vp], C.c_int),
         "ccmp_debug_sort_probe": ([vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, vp], C.c_int),
         "ccmp_debug_split_probe": ([vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_uint, vp, vp], C.c_int),
     }

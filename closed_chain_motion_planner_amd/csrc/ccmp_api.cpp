@@ -292,7 +292,25 @@ int grow_buffer(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes)
 }  // extern "C++"
 static int grow(ccmp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t bytes) { return ccmp_host::grow_buffer(ctx, buf, cap, n, bytes); }
 static int ensure_pool(ccmp_ctx *ctx, size_t records) { return grow(ctx, (void **)&ctx->pool, &ctx->pool_cap, records, records * kPoolEntry * sizeof(double)); }
-static int ensure_fd_state(ccmp_ctx *ctx, size_t B) { return grow(ctx, (void **)&ctx->fd_state, &ctx->fd_state_cap, B, B * kPoolEntry * sizeof(double)); }
+// head -> resume workspace: one row per sample — a staged record on stock twin arms (ccmp_launch.h: kStagedRow doubles, 1.26 KB: 331 MB at
+// 262 144 samples), the hand-over's record otherwise (kPoolEntry).  false: the device has no room for it — the caller runs the call as
+// the one-launch whole kernel, which needs none
+static bool ensure_fd_state(ccmp_ctx *ctx, size_t B, int row_doubles)
+{
+  const size_t doubles = B * (size_t)row_doubles;
+  if (ctx->fd_state_cap >= doubles) return true;
+  ccmp_host::quiesce(ctx);
+  if (ctx->fd_state) (void)hipFree(ctx->fd_state);
+  ctx->fd_state = nullptr;
+  ctx->fd_state_cap = 0;
+  if (hipMalloc((void **)&ctx->fd_state, doubles * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError(); // out of memory is this function's answer, not the call's error
+    ctx->fd_state = nullptr;
+    return false;
+  }
+  ctx->fd_state_cap = doubles;
+  return true;
+}
 static int ensure_lpt_buffers(ccmp_ctx *ctx, size_t B) // pred u16 | hist 1024 x u32 | order u32 | flags u8 (bulk checkMotion)
 {
   return grow(ctx, &ctx->lpt_buf, &ctx->lpt_cap, B, ((B * 2 + 255) & ~(size_t)255) + 4096 + B * 4 + B);
@@ -343,7 +361,7 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
     return CCMP_OK;
   }
   // the plan is ccmp_policy.cpp's plan_fd_batch (what ccmp_ctx_describe prints)
-  const FdPlan pl = ccmp_host::plan_fd_batch(ctx, B, ctx->order != nullptr);
+  FdPlan pl = ccmp_host::plan_fd_batch(ctx, B, ctx->order != nullptr);
   // every workspace of the call is sized before anything of it is in flight
   if (pl.scout || pl.latency_order) {
     int rc = ensure_lpt_buffers(ctx, B);
@@ -353,10 +371,7 @@ static int project_common(ccmp_ctx *ctx, const ccmp_problem *p, int mode, const 
     int rc = ensure_pool(ctx, (size_t)pl.group_blocks * 10);
     if (rc != CCMP_OK) return rc;
   }
-  if (pl.head_rounds > 0) {
-    int rc = ensure_fd_state(ctx, B);
-    if (rc != CCMP_OK) return rc;
-  }
+  if (pl.head_rounds > 0 && !ensure_fd_state(ctx, B, K.stock && K.twin_arms ? ccmp_launch::kStagedRow : kPoolEntry)) pl.head_rounds = 0; // no room for the staged records: one launch, the same bits
   unsigned long long *const q_pool_count = ctx->queue + kQPool, *const q_latency = ctx->queue + kQLatency;
   if (!pl.latency_static) HIP_TRY(ccmp_launch::clear_words(ctx->queue, 16, st)); // the projector's eight queue words
 
@@ -870,6 +885,20 @@ int ccmp_ctx_debug_lpt_order(ccmp_ctx *ctx, unsigned int *order_host, size_t n, 
   HIP_TRY(hipMemcpy(order_host, sb.order, n * sizeof(unsigned int), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(hist_host, sb.hist, 1024 * sizeof(unsigned int), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(queue_host, ctx->queue, kQueueWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return CCMP_OK;
+}
+
+// the rows between the head and the resume launch as the last call that ran both ON STOCK TWIN ARMS left them (ccmp_launch.h: kStagedRow)
+int ccmp_ctx_debug_fd_state(ccmp_ctx *ctx, double *rows_host, size_t n, int *row_doubles_out)
+{
+  if (!ctx || !row_doubles_out) return CCMP_EINVAL;
+  *row_doubles_out = ccmp_launch::kStagedRow;
+  if (!rows_host) return CCMP_OK;
+  if (!ctx->fd_state || n * (size_t)ccmp_launch::kStagedRow > ctx->fd_state_cap) return CCMP_EINVAL;
+  DeviceGuard guard(ctx->device);
+  ccmp_host::quiesce(ctx);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(rows_host, ctx->fd_state, n * ccmp_launch::kStagedRow * sizeof(double), hipMemcpyDeviceToHost));
   return CCMP_OK;
 }
 

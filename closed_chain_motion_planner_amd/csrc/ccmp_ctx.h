@@ -83,8 +83,8 @@ struct ccmp_ctx {
   unsigned long long *queue = nullptr; // work-queue words: ccmp_launch.h (QueueWord)
   double *pool = nullptr;              // straggler hand-over records (throughput kernel -> latency kernel)
   size_t pool_cap = 0;                 // in records
-  double *fd_state = nullptr;          // head -> resume launch of a large projector batch: one hand-over record per sample, row = sample
-  size_t fd_state_cap = 0;             // in records
+  double *fd_state = nullptr;          // head -> resume launch of a large projector batch: one row per sample (ccmp_launch.h: kStagedRow doubles on stock twin arms, kPoolEntry otherwise)
+  size_t fd_state_cap = 0;             // in doubles
   void *lpt_buf = nullptr;             // pred (u16 x B) | hist (u32 x 1024) | order (u32 x B) | flags (u8 x B, bulk checkMotion)
   size_t lpt_cap = 0;                  // in samples
   double *geo_pool = nullptr;          // bulk extend hand-over: kGeoPoolEntry doubles per edge

@@ -333,13 +333,19 @@ __device__ __forceinline__ void stencil_combine(double *rec, int r, bool live)
 //   whole   the persistent, queue-fed kernel from a sample's first round to its last (every regime but the one below)
 //   head    large batches without hand-over: the first head_rounds Newton rounds of EVERY sample, non-persistent: workgroup w takes
 //           samples 10 w .. 10 w + 9 in index order, so the ten samples of a wavefront are of one age — far from the manifold all
-//           together, for four or five rounds, and done with it; at the loop top of round head_rounds each sample still iterating
-//           leaves its hand-over record (kPoolEntry doubles: x, index, counters) in row idx of `state`; one that ends earlier is
-//           written back as ever and its row is marked finished (index -1)
-//   resume  the persistent kernel again, whose refill takes x and the four counters from that row instead of q_in and zeros, and
-//           draws again (kResumeDraws times, then waits a round) where the row is marked finished.  Its wavefronts hold samples of
-//           all ages, none of them far from the manifold: ccmp_atan's wave-uniform first interval (ccmp_detmath.h) holds in nearly
-//           every round, where one young sample among the ten defeated it in two rounds of three.
+//           together, for four or five rounds, and done with it; it stops BEHIND phase 1 of round head_rounds: each sample still
+//           iterating there leaves its staged record (kStagedRow doubles, ccmp_launch.h: what that phase 1 computed, index, counters)
+//           in row idx of `state`; one that ends earlier, or in that phase 1, is written back as ever and its row is marked finished
+//           (index -1)
+//   resume  the persistent kernel again, in a loop of its own that admits BEHIND the finish block: a group takes the staged record of
+//           its next sample into LDS and registers and goes straight into phase 2 of the round its predecessor ended in — no group
+//           sits out a phase 2 because its sample is new; it draws again (kResumeDraws times, then waits a round) where the row is
+//           marked finished.  Its wavefronts hold samples of all ages, none of them far from the manifold: ccmp_atan's wave-uniform
+//           first interval (ccmp_detmath.h) holds in nearly every round, where one young sample among the ten defeated it in two
+//           rounds of three.
+//   (STOCK instantiations.  The general ones — calibrated arms, tilted bases — keep the form the two launches had before: the head
+//   dumps at the loop top of round head_rounds the hand-over's record, kPoolEntry doubles, and the resume launch refills from it at its
+//   loop top, in the whole kernel's loop; their register allocation is pinned by tests/test_gpu_fd_round_facts.py.)
 // The operations on a sample are the same ones in the same order whichever launches perform them: same bits.
 // VARIANT = MODE + 2 * PART in ONE integer: the kernels' names keep the form project_fd_kernel<n, stock> (build.py: _SCRATCH_RULES).
 using ccmp_launch::FdPart;
@@ -383,6 +389,63 @@ __device__ __forceinline__ unsigned long long head_sample(int g)
   asm volatile("" : "+v"(g));
   return (unsigned long long)blockIdx.x * kGroupsPerWave + (unsigned long long)g;
 }
+// head -> resume: a group's staged record (ccmp_launch.h: kStagedRow) to and from its row of `state`.  The LDS part is 75 pieces of 16 B:
+// lane r of the group moves pieces r, r + 6, ... — 96 contiguous bytes per group and instruction, as iterate_from_row's; the four pieces
+// behind it (residual pair, index and counters, norms, the group's say in x0) are written by lane 0 and read by every lane for itself.
+using ccmp_launch::kStagedF;
+using ccmp_launch::kStagedLds;
+using ccmp_launch::kStagedNorm;
+using ccmp_launch::kStagedRow;
+using ccmp_launch::kStagedTag;
+using ccmp_launch::kStagedX0;
+static_assert(kStagedLds == kJ0 && kX == 0, "the staged part of a record is everything in front of the Jacobian's slots");
+constexpr int kStagedPieces = kStagedLds / 2;
+__device__ __forceinline__ void stage_to_row(const double *rec, int r, double *__restrict__ dst, unsigned long long idx, double f0, double f1,
+                                             int iter, int updates, double norm1, double norm2, bool x0_off)
+{
+  double2 *row = reinterpret_cast<double2 *>(dst);
+  for (int p = r; p < kStagedPieces; p += kGroup) {
+    double2 a;
+    a.x = rec[2 * p];
+    a.y = rec[2 * p + 1];
+    row[p] = a;
+  }
+  if (r == 0) {
+    double2 f, tag, nrm, flag;
+    f.x = f0; f.y = f1;
+    tag.x = __longlong_as_double((long long)idx); tag.y = __hiloint2double(updates, iter);
+    nrm.x = norm1; nrm.y = norm2;
+    flag.x = x0_off ? 1.0 : 0.0; flag.y = 0.0;
+    row[kStagedF / 2] = f;
+    row[kStagedTag / 2] = tag;
+    row[kStagedNorm / 2] = nrm;
+    row[kStagedX0 / 2] = flag;
+  }
+}
+__device__ __forceinline__ void stage_from_row(double *rec, int r, const double *__restrict__ src)
+{
+  // (the lane's piece index goes through a value the optimiser cannot see through, as head_sample's group index: the thirteen LDS
+  // offsets that follow from it were otherwise formed once, in front of the resume loop, and held across it — registers the kernel does
+  // not have.  From one base the pieces are immediate offsets.)
+  asm volatile("" : "+v"(r));
+  const double2 *row = reinterpret_cast<const double2 *>(src) + r;
+  double *dst = rec + 2 * r;
+  constexpr int kFull = kStagedPieces / kGroup; // 12 pieces that every lane has, one more for the first kStagedPieces % kGroup lanes
+  double2 a[kFull + 1];
+#pragma unroll
+  for (int k = 0; k < kFull; k++) a[k] = row[kGroup * k];
+  const bool last = r < kStagedPieces - kGroup * kFull;
+  if (last) a[kFull] = row[kGroup * kFull];
+#pragma unroll
+  for (int k = 0; k < kFull; k++) {
+    dst[2 * kGroup * k] = a[k].x;
+    dst[2 * kGroup * k + 1] = a[k].y;
+  }
+  if (last) {
+    dst[2 * kGroup * kFull] = a[kFull].x;
+    dst[2 * kGroup * kFull + 1] = a[kFull].y;
+  }
+}
 template <int VARIANT, bool STOCK>
 __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
     const ccmp_consts K, const double *__restrict__ q_in, double *__restrict__ q_out, uint8_t *__restrict__ ok_out,
@@ -392,6 +455,8 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
     unsigned long long pool_records, double *__restrict__ state, int head_rounds)
 {
   constexpr int MODE = VARIANT & 1, PART = VARIANT >> 1;
+  // rows of `state`: staged records between the STOCK head and resume, the hand-over's record between the general ones
+  constexpr int kStateRow = STOCK ? kStagedRow : kPoolEntry, kStateTag = STOCK ? kStagedTag : 14;
   if constexpr (PART != kFdWhole) pool = nullptr; // neither part hands over (ccmp_policy.cpp): the text below that does folds away
   __shared__ double lds[kGroupsPerWave * kRec];
   const int lane = threadIdx.x;
@@ -428,11 +493,71 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
     }
   }
 
+#define CCMP_FD_BP bp_lane
+#define CCMP_FD_X0_ROWS 1
+  // ---- resume: admit -> phase 2 -> phase 1 -> finish -> admit -> ...  Every row it admits holds a sample behind ITS phase 1, so a
+  // group whose sample ends in phase 1 of a round is written back and its successor runs phase 2 of that same round (refilled at the
+  // loop top, as the whole kernel does, the group sat out the four fifths of a round that phase 2 is)
+  if constexpr (PART == kFdResume && STOCK) {
+    double f0c = 0.0, f1c = 0.0;       // the group's residual pair, from phase 1 (or the row) into phase 2
+    bool x0c = K.rot_x0 != 0; // phase 1's x0 over the groups that go on, for phase 2
+    for (;;) {
+      // ---- admission: the whole kernel's tickets; a row marked finished (the head has written the sample back) costs a draw, and
+      // after kResumeDraws of them the group waits a round
+      bool admitted = false;
+      for (int draw = 0; draw < kResumeDraws; draw++) {
+        const bool want = live && !active && !drained;
+        if (__builtin_amdgcn_ballot_w64(want) == 0ull) break;
+        unsigned long long t = 0;
+        if (want && r == 0) t = atomicAdd(queue, 1ull);
+        t = shfl_u64(t, leader);
+        if (want) {
+          if (t < B) {
+            idx = order ? (unsigned long long)order[t] : t;
+            const double2 tag = reinterpret_cast<const double2 *>(state + idx * kStagedRow)[kStagedTag / 2];
+            if (__double_as_longlong(tag.x) >= 0) {
+              active = true; admitted = true;
+              iter = __double2loint(tag.y); updates = __double2hiint(tag.y);
+            }
+          } else drained = true;
+        }
+      }
+      bool adm_off = false;
+      if (admitted) { // the record into the group's LDS, the rest into the lanes' registers (one address per group: a broadcast)
+        const double *src = state + idx * kStagedRow;
+        const double2 *row = reinterpret_cast<const double2 *>(src);
+        const double2 f = row[kStagedF / 2], nrm = row[kStagedNorm / 2];
+        f0c = f.x; f1c = f.y; norm1 = nrm.x; norm2 = nrm.y;
+        adm_off = src[kStagedX0] != 0.0;
+        stage_from_row(rec, r, src);
+      }
+      // the round's x0 covers the samples admitted into it: the flags that THEIR phase 1 computed, in the head
+      x0c = x0c && __builtin_amdgcn_ballot_w64(adm_off) == 0ull;
+      if (__builtin_amdgcn_ballot_w64(active) == 0ull) {
+        // (finished rows only leave the groups without a sample and the queue not yet dry — draw again)
+        if (__builtin_amdgcn_ballot_w64(live && !drained) != 0ull) continue;
+        break;
+      }
+      __syncthreads();
+      {
+        const bool x0 = x0c, cont = active; // every sample a group holds here is behind a loop test that said go on
+        const double f0 = f0c, f1 = f1c;
+#include "ccmp_fd_newton_phase2.inc"
+      }
+#include "ccmp_fd_newton_phase1.inc"
+#include "ccmp_fd_project_finish.inc"
+      f0c = f0; f1c = f1;
+      x0c = K.rot_x0 != 0 && __builtin_amdgcn_ballot_w64(cont && x0_off) == 0ull;
+      __syncthreads(); // the write-back has read the records that the admission overwrites
+    }
+    return;
+  }
+
   for (;;) {
     // ---- refill: groups without a sample pull the next index from the global queue ----------
     if constexpr (PART == kFdResume) {
-      // the same tickets, the sample's state from its row of `state`: x in 16-B pieces as below, the index and the counters by
-      // every lane of the group for itself (one address: a broadcast)
+      // (general instantiation) the same tickets, the sample's state from its row of `state`: x in 16-B pieces as below, the index and
+      // the counters by every lane of the group for itself (one address: a broadcast)
       for (int draw = 0; draw < kResumeDraws; draw++) {
         const bool want = live && !active && !drained;
         if (__builtin_amdgcn_ballot_w64(want) == 0ull) break;
@@ -481,9 +606,9 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
       break;
     }
     __syncthreads();
-    // ---- head: the loop top of round head_rounds, where the next thing that happens to a sample is function(x) + the loop test —
-    // the samples still iterating leave their records (the hand-over's, in row idx) and the wavefront retires
-    if constexpr (PART == kFdHead) {
+    // ---- head, general instantiation: the loop top of round head_rounds, where the next thing that happens to a sample is function(x)
+    // + the loop test — the samples still iterating leave their records (the hand-over's, in row idx) and the wavefront retires
+    if constexpr (PART == kFdHead && !STOCK) {
       if (round == head_rounds) {
         idx = head_sample(g);
         if (active) {
@@ -557,47 +682,18 @@ __global__ __launch_bounds__(64, CCMP_FD_WAVES_PER_SIMD) void project_fd_kernel(
       break;
     }
 
-#define CCMP_FD_BP bp_lane
-#define CCMP_FD_X0_ROWS 1
 #include "ccmp_fd_newton_phase1.inc"
-    // ---- finished groups: jointValid, write-back --------------------------------------------
-    {
-      const bool fin = active && !cont;
-      bool bad = false;
-      if constexpr (PART == kFdHead) idx = head_sample(g);
-      if (fin) {
-#pragma unroll
-        for (int e = 0; e < 14; e++) {
-          if (e % kGroup == r) { // e is a compile-time constant here: limits come from SGPRs
-            const double v = rec[kX + e];
-            if (v < K.lbe[e % 7]) bad = true;
-            if (v > K.ube[e % 7]) bad = true;
-          }
-        }
-        // row write-back in 16-B pieces: 96 contiguous bytes per group in one instruction + the last piece
-        double2 *row = reinterpret_cast<double2 *>(q_out + idx * 14);
-        double2 a;
-        a.x = rec[kX + 2 * r];
-        a.y = rec[kX + 2 * r + 1];
-        if (MODE == 1) { a.x = wrap_pi(a.x); a.y = wrap_pi(a.y); }
-        row[r] = a;
-        if (r == 0) {
-          double2 b;
-          b.x = rec[kX + 12];
-          b.y = rec[kX + 13];
-          if (MODE == 1) { b.x = wrap_pi(b.x); b.y = wrap_pi(b.y); }
-          row[6] = b;
-        }
+#include "ccmp_fd_project_finish.inc"
+    // ---- head, STOCK: behind function(x) + the loop test of round head_rounds the samples still iterating leave their staged records —
+    // what phase 1 has just computed of them, and the counters behind the loop test's increment — in row idx, and the wavefront retires
+    if constexpr (PART == kFdHead && STOCK) {
+      if (round == head_rounds) {
+        const bool off = ((__builtin_amdgcn_ballot_w64(x0_off) >> leader) & 0x3Full) != 0ull; // the group's say in phase 1's x0
+        idx = head_sample(g);
+        if (cont) stage_to_row(rec, r, state + idx * kStagedRow, idx, f0, f1, iter, updates, norm1, norm2, off);
+        break;
       }
-      const unsigned long long badmask = __builtin_amdgcn_ballot_w64(bad);
-      if (fin && r == 0) {
-        const bool gbad = ((badmask >> leader) & 0x3Full) != 0ull;
-        ok_out[idx] = (uint8_t)((!gbad) && (norm1 < K.tol_pos) && (norm2 < K.tol_rot));
-        if (iters_out) iters_out[idx] = (uint16_t)updates;
-        if (pool != nullptr && dump_threshold > 10) atomicAdd(queue + 3, 1ull); // finished count of the occupancy-driven hand-over
-        if constexpr (PART == kFdHead) state[idx * kPoolEntry + 14] = __longlong_as_double(-1ll); // nothing left for the resume launch
-      }
-      if (fin) active = false;
+      round++;
     }
     if (__builtin_amdgcn_ballot_w64(cont) == 0ull) continue; // nobody iterates: straight to refill
     __syncthreads(); // prefix frames / tool poses written by the writer lane are visible to the group
@@ -1061,7 +1157,7 @@ hipError_t clear_words(void *words, size_t n_u32, hipStream_t st)
 
 // queue: the projector's block of queue words (kQTicket: this kernel's samples, kQPool: the pool's fill count)
 // part: the whole call (the default), or one of the two launches of a large batch — a head launch is one one-wavefront workgroup
-// per ten samples: `blocks` must say so; state: the call's B rows of kPoolEntry doubles between head and resume
+// per ten samples: `blocks` must say so; state: the call's B rows between head and resume, kStagedRow doubles each (general instantiations: kPoolEntry)
 hipError_t project_group(const ProjectCall &c, int blocks, unsigned long long *queue, double *pool, int dump_threshold,
                          const unsigned int *order, const uint16_t *pred, int long_remaining, size_t pool_records, hipStream_t st,
                          FdPart part, double *state, int head_rounds)

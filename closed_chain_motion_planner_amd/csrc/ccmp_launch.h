@@ -28,6 +28,17 @@ struct ccmp_split_req {
 namespace ccmp_launch {
 
 constexpr int kPoolEntry = 18;    // projector hand-over record, in doubles: x[14], idx, (iter, updates), norm1, norm2
+// head -> resume launch of a large projector batch (ccmp_kernels_fd.hip: FdPart): one row per sample, in doubles.  A sample that is
+// still iterating behind the head's last function(x) leaves what that evaluation computed — the first kStagedLds doubles of its
+// group's LDS record (x 14, sin / cos 28, arm 0's prefix frames 84, both tool poses 24) and the residual pair — with the hand-over
+// record's index and counters, so the resume launch takes it up at the Jacobian.  16-byte pieces: the stride is even.
+constexpr int kStagedLds = 150;
+constexpr int kStagedF = kStagedLds;        // f0, f1
+constexpr int kStagedTag = kStagedLds + 2;  // index (-1: the head has written the sample back), (iter, updates) behind the loop test's increment
+constexpr int kStagedNorm = kStagedLds + 4; // norm1, norm2
+constexpr int kStagedX0 = kStagedLds + 6;   // 1.0: some joint of x failed rot_x0_round_ok in that evaluation (ccmp_kin.h), else 0.0; pad
+constexpr int kStagedRow = kStagedLds + 8;
+static_assert(kStagedRow % 2 == 0 && kStagedLds % 2 == 0, "rows and their parts are moved in 16-byte pieces");
 constexpr int kGeoPoolEntry = 40; // extend-step hand-over of an edge in the middle of a projection: x[14], previous[14], dist, total,
                                   // maxd, edge, (n, its), (rounds, iter), updates, norm1, norm2 (geodesic_group_kernel -> geodesic_flat_kernel)
 constexpr int kFastQueues = 64;   // ticket words of the analytic mode's lane-pair kernel: one per lane of a wavefront

@@ -436,8 +436,8 @@ int ccmp_ctx_describe(const ccmp_ctx *ctx_in, int call_kind, size_t n, char *buf
         if (pl.two_class_pool) L.add(" in two classes (>= %d predicted iterations left first)", kPoolLongRemaining);
       } else L.add("; no hand-over");
       if (pl.head_rounds > 0)
-        L.add("; in front of it the first %d Newton rounds of every sample on project_fd_kernel (head) x %zu one-wavefront workgroups in index order%s",
-              pl.head_rounds, (n + 9) / 10, pl.scout ? ", the scout pass beside them on the side stream (in front of them where the call is in place)" : "");
+        L.add("; in front of it the first %d Newton rounds of every sample on project_fd_kernel (head) x %zu one-wavefront workgroups in index order, which on stock twin arms stop behind the next function(x) and stage it for the resume launch (%zu MB of workspace; one launch where the device has no room for it)%s",
+              pl.head_rounds, (n + 9) / 10, (n * ccmp_launch::kStagedRow * sizeof(double) + (1u << 20) - 1) >> 20, pl.scout ? ", the scout pass beside them on the side stream (in front of them where the call is in place)" : "");
       L.add(" [small_batch=%zu lpt_min_batch=%zu fd_split=%d:%zu..%zu wide<=%zu occupancy_rule<%zu no_handover>=%zu fd_head=%d:%zu..]", ctx->small_batch,
             ctx->lpt_min_batch, ctx->fd_split, ctx->fd_split_min, ctx->fd_split_max, kSplitWideMax, kOccupancyHandoverBelow, kNoHandoverFrom,
             ctx->fd_head_rounds, ctx->fd_head_min_batch);

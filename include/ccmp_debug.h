@@ -38,6 +38,12 @@ int ccmp_ctx_debug_lpt_pred(ccmp_ctx *ctx, uint16_t *host_out, size_t B);
  * last call left them */
 int ccmp_ctx_debug_lpt_order(ccmp_ctx *ctx, unsigned int *order_host, size_t n, unsigned int *hist_host, unsigned long long *queue_host,
                              size_t queue_words);
+/* the first n rows of the workspace between the head and the resume launch of a large reference-arithmetic projector batch on stock twin
+ * arms (calibrated arms leave the shorter hand-over record: not this layout), as the last such call left them: row i = sample i, row_doubles doubles each (the library's count, returned in *row_doubles_out: ccmp_launch.h, kStagedRow) —
+ * the first 150 of a row what the head's last function(x) left in the group's record (x 14, sin / cos 28, arm 0's frames 84, tool poses 24),
+ * then f0, f1, the index as a 64-bit integer (-1: the head has written the sample back), (iter | updates << 32), norm1, norm2, and 1.0 where some
+ * joint of x failed rot_x0_round_ok in that evaluation, else 0.0; one pad.  rows_host NULL: the count alone */
+int ccmp_ctx_debug_fd_state(ccmp_ctx *ctx, double *rows_host, size_t n, int *row_doubles_out);
 /* the scouts' descending counting sort on the caller's device buffers: keys_dev[n] (uint16, clamped to 1023) -> order_dev[n], hist_dev[1024],
  * and — kind 1 or 2 — the cut of the order into queue_dev (a block of 16 64-bit words: 0, 3, 4 = the front's length, the other words
  * below `clear` zeroed, the rest untouched).  Above 16 384 keys (the three-kernel form) every key must be below nbins, the histogram runs on
