@@ -60,12 +60,15 @@ Translation units with deliberately different flags:
                          ticks, the inputs staged in LDS, no tick array, one atomic maximum per block), its decide kernel, the sample kernel and the per-path peaks
   ccmp_jerk.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_path_jerk_setpoints*, ccmp_jerk_setpoints_*: checks, the window search's pass loop, the launches; ccmp_jerk_setpoints_ref
   ccmp_kernels_plan.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   the planner's loop on the store (ccmp_plan.h): the front's broadcast, the tally of a growth step, the check
-                         (one wavefront: the carry rule's serial fold, the thresholds, the IK targets of the ladder), the prefix, the push and the solution test (a ballot over the pairs)
-  ccmp_plan.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_plan_*: checks, open, the cycle over the store's own entry points; ccmp_plan_check_ref / _prefix_ref / _connected_ref
+                         (one wavefront: the carry rule's serial fold, the thresholds, the IK targets of the ladder), the prefix, the push and the solution test (a ballot over the
+                         pairs; a template over the state type, instantiated for ccmp_plan_state and for ccmp_rrtc_state: both under the plan_ line of _SCRATCH_RULES)
+  ccmp_plan.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_plan_*: checks, open, the cycle's body over the store's own entry points; ccmp_plan_check_ref / _prefix_ref / _connected_ref
   ccmp_kernels_rrtc.hip  -ffp-contract=off -DCCMP_USE_FMA -DCCMP_LEAN_SQRT   RRT-Connect on the store (ccmp_rrtc.h): nearest vertex within a tree (blocks over (partition, query), a
                          (distance, index) pair reduction), the traversal's endpoints, the pick (sixteen lanes per edge, the arc's serial fold), the commit (one block: a scan
-                         gives the total order) and the solution test
-  ccmp_rrtc.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_rrtc_*, ccmp_roadmap_nearest_in_tree*: checks, the cycle over the library's own entry points; the *_ref forms
+                         gives the total order); its solution test is the plan unit's kernel
+  ccmp_rrtc.cpp          -ffp-contract=off -DCCMP_USE_FMA   ccmp_rrtc_*, ccmp_roadmap_nearest_in_tree*: checks, the cycle's body over the library's own entry points; the *_ref forms
+  (ccmp_plan.cpp and ccmp_rrtc.cpp share ccmp_planner.h on the host — the state block's reads, open's upload, the run loop with the solution test, the report's head — and
+  ccmp_plan.h's solution test on host and device)
   (the three units ccmp_kernels_setpoints / _fit / _jerk share ccmp_lanes.h on the device — the DPP row folds and the audit fold of the two peak kernels — and ccmp_timed.h on the
   host — the checks, the _host staging, the tick ranges, the delivery tail and the _ref loops; a tick of the interpolant is setpoint_bracket and
   setpoint_joint of ccmp_setpoints.h everywhere)
@@ -169,16 +172,16 @@ _UNITS = [
     ("ccmp_kernels_jerk.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_path_jerk_setpoints: the checks, the window search's pass loop and the rule on the host (ccmp_jerk_setpoints_ref)
     ("ccmp_jerk.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
-    # the planner's loop on the store (ccmp_plan.h): front, tally, check, prefix, push and the solution test; the graph unit's flags; registers and LDS only
+    # the planner's loop on the store (ccmp_plan.h): front, tally, check, prefix, push and the solution test (both planners' instantiations); the graph unit's flags; registers and LDS only
     ("ccmp_kernels_plan.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_plan_*: the checks, open and the cycle over the store's entry points, and the rule on the host (ccmp_plan_check_ref, _prefix_ref, _connected_ref)
     ("ccmp_plan.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
-    # RRT-Connect on the store (ccmp_rrtc.h): nearest-in-tree, edges, pick, commit and the solution test; the graph unit's flags; registers and LDS only
+    # RRT-Connect on the store (ccmp_rrtc.h): nearest-in-tree, edges, pick and commit (its solution test is the plan unit's kernel); the graph unit's flags; registers and LDS only
     ("ccmp_kernels_rrtc.hip", ["-O3", "-ffp-contract=off", "-DCCMP_USE_FMA", "-DCCMP_LEAN_SQRT"]),
     # ccmp_rrtc_*, ccmp_roadmap_nearest_in_tree*: the checks and the cycle over the library's entry points, and the rule on the host (the *_ref forms)
     ("ccmp_rrtc.cpp", ["-O2", "-ffp-contract=off", "-DCCMP_USE_FMA", "-x", "hip"]),
 ]
-_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_fd_project_finish.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_setpoints.h", "ccmp_fit.h", "ccmp_jerk.h", "ccmp_plan.h", "ccmp_rrtc.h", "ccmp_lanes.h", "ccmp_timed.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
+_HEADERS = ["ccmp_detmath.h", "ccmp_kin.h", "ccmp_solve.h", "ccmp_fd_common.h", "ccmp_flat_newton.h", "ccmp_host.h", "ccmp_ctx.h", "ccmp_launch.h", "ccmp_policy.h", "ccmp_resident.h", "ccmp_resident_proto.h", "ccmp_fd_newton_phase1.inc", "ccmp_fd_newton_phase2.inc", "ccmp_fd_project_finish.inc", "ccmp_geo_edge.h", "ccmp_geo_edge_body.inc", "ccmp_scene.h", "ccmp_scene_math.h", "ccmp_clearance.h", "ccmp_pose.h", "ccmp_ik.h", "ccmp_ik_vet.h", "ccmp_object.h", "ccmp_graph.h", "ccmp_path.h", "ccmp_dense.h", "ccmp_shortcut.h", "ccmp_smooth.h", "ccmp_retime.h", "ccmp_setpoints.h", "ccmp_fit.h", "ccmp_jerk.h", "ccmp_plan.h", "ccmp_rrtc.h", "ccmp_planner.h", "ccmp_lanes.h", "ccmp_timed.h", "ccmp_pair_tests.h", "ccmp_stage.h", "ccmp_row16_eval.inc", "ccmp_row16_step.inc", "ccmp_row16_geo_body.inc", os.path.join("..", "..", "include", "ccmp.h")]
 
 
 def hipcc_path():

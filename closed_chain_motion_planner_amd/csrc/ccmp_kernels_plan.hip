@@ -12,7 +12,8 @@
 //   plan_prefix_kernel     the ladder's prefix mask from valid[9] and ik_ok[9] (ccmp::plan_prefix) and the 16-byte summary the host reads:
 //                          {prefix length, goal vertex solved, start vertex solved, the check ran}
 //   plan_push_kernel       a committed new_index onto starts or goals under the cap (ccmp::plan_push)
-//   plan_connected_kernel  one wavefront, lane l = pair (l / G, l % G) of the <= 8 x 8 pairs: the label compare, a ballot, and the lowest set
+//   plan_connected_kernel  the solution test of EVERY planner on the store, a template over the state type (ccmp_plan_state, ccmp_rrtc_state):
+//                          one wavefront, lane l = pair (l / G, l % G) of the <= 8 x 8 pairs: the label compare, a ballot, and the lowest set
 //                          bit is the first connected pair in start-major order — no race decides it
 #include <hip/hip_runtime.h>
 
@@ -124,21 +125,26 @@ __global__ __launch_bounds__(kWave) void plan_push_kernel(ccmp_plan_state *state
   if (threadIdx.x == 0) ccmp::plan_push(state, which, new_index[0]);
 }
 
-__global__ __launch_bounds__(kWave) void plan_connected_kernel(const GraphStore s, ccmp_plan_state *state, int bump_cycle)
+template <class S> __global__ __launch_bounds__(kWave) void plan_connected_kernel(const GraphStore s, S *state, int bump_cycle)
 {
   const int lane = threadIdx.x;
-  const int S = state->n_starts < 0 ? 0 : state->n_starts > CCMP_PLAN_MAX_STARTS ? CCMP_PLAN_MAX_STARTS : state->n_starts;
-  const int G = state->n_goals < 0 ? 0 : state->n_goals > CCMP_PLAN_MAX_GOALS ? CCMP_PLAN_MAX_GOALS : state->n_goals;
+  const int n_s = ccmp::planner_clamp(state->n_starts), G = ccmp::planner_clamp(state->n_goals);
   const bool solved = state->status == CCMP_PLAN_SOLVED;
   bool hit = false;
-  if (!solved && G > 0 && lane < S * G) hit = ccmp::plan_pair_connected(state, lane / G, lane % G, s.labels, s.N);
+  if (!solved && G > 0 && lane < n_s * G) hit = ccmp::pair_connected(state, lane / G, lane % G, s.labels, s.N);
   const unsigned long long mask = __ballot(hit);
   if (lane != 0) return;
   if (bump_cycle) state->cycle += 1;
   if (mask) {
     const int first = __ffsll((long long)mask) - 1;
-    ccmp::plan_solved(state, first / G, first % G);
+    ccmp::solved(state, first / G, first % G);
   }
+}
+
+template <class S> hipError_t launch_connected(const GraphStore &s, S *state, int bump_cycle, hipStream_t st)
+{
+  hipLaunchKernelGGL(plan_connected_kernel<S>, dim3(1), dim3(kWave), 0, st, s, state, bump_cycle);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -178,10 +184,7 @@ hipError_t plan_push(ccmp_plan_state *state, int which, const int32_t *new_index
   return hipGetLastError();
 }
 
-hipError_t plan_connected(const GraphStore &s, ccmp_plan_state *state, int bump_cycle, hipStream_t st)
-{
-  hipLaunchKernelGGL(plan_connected_kernel, dim3(1), dim3(kWave), 0, st, s, state, bump_cycle);
-  return hipGetLastError();
-}
+hipError_t plan_connected(const GraphStore &s, ccmp_plan_state *state, int bump_cycle, hipStream_t st) { return launch_connected(s, state, bump_cycle, st); }
+hipError_t plan_connected(const GraphStore &s, ccmp_rrtc_state *state, int bump_cycle, hipStream_t st) { return launch_connected(s, state, bump_cycle, st); }
 
 }  // namespace ccmp_launch

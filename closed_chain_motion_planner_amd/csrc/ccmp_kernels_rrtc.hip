@@ -15,7 +15,7 @@
 //                              fed by shuffles within the group.  Writes the outcome, the new row and its parent.
 //   rrtc_commit_kernel         ONE block, width <= 256: an exclusive scan over the keep flags gives step 4's total order; writes the compact
 //                              rows, the uv entries, the counts the host reads, the tallies and the state update (next_index, best_gap)
-//   rrtc_connected_kernel      as plan_connected_kernel: the label compare, a ballot, the lowest set bit
+// The cycle's solution test is ccmp_kernels_plan.hip's plan_connected_kernel, instantiated there for ccmp_rrtc_state.
 #include <hip/hip_runtime.h>
 
 #include "ccmp_detmath.h"
@@ -255,23 +255,6 @@ __global__ __launch_bounds__(kThreads) void rrtc_commit_kernel(const GraphStore 
   c.counts[3] = nB;
 }
 
-__global__ __launch_bounds__(kWave) void rrtc_connected_kernel(const GraphStore s, ccmp_rrtc_state *state, int bump_cycle)
-{
-  const int lane = threadIdx.x;
-  const int S = state->n_starts < 0 ? 0 : state->n_starts > CCMP_PLAN_MAX_STARTS ? CCMP_PLAN_MAX_STARTS : state->n_starts;
-  const int G = state->n_goals < 0 ? 0 : state->n_goals > CCMP_PLAN_MAX_GOALS ? CCMP_PLAN_MAX_GOALS : state->n_goals;
-  const bool solved = state->status == CCMP_RRTC_SOLVED;
-  bool hit = false;
-  if (!solved && G > 0 && lane < S * G) hit = ccmp::rrtc_pair_connected(state, lane / G, lane % G, s.labels, s.N);
-  const unsigned long long mask = __ballot(hit);
-  if (lane != 0) return;
-  if (bump_cycle) state->cycle += 1;
-  if (mask) {
-    const int first = __ffsll((long long)mask) - 1;
-    ccmp::rrtc_solved(state, first / G, first % G);
-  }
-}
-
 }  // namespace
 
 namespace ccmp_launch {
@@ -305,12 +288,6 @@ hipError_t rrtc_pick(const RrtcPick &c, hipStream_t st)
 hipError_t rrtc_commit(const GraphStore &s, ccmp_rrtc_state *state, const RrtcCommit &c, hipStream_t st)
 {
   hipLaunchKernelGGL(rrtc_commit_kernel, dim3(1), dim3(kThreads), 0, st, s, state, c);
-  return hipGetLastError();
-}
-
-hipError_t rrtc_connected(const GraphStore &s, ccmp_rrtc_state *state, int bump_cycle, hipStream_t st)
-{
-  hipLaunchKernelGGL(rrtc_connected_kernel, dim3(1), dim3(kWave), 0, st, s, state, bump_cycle);
   return hipGetLastError();
 }
 

@@ -482,8 +482,9 @@ hipError_t plan_check(const GraphStore &s, ccmp_plan_state *state, const PlanChe
 hipError_t plan_prefix(const ccmp_plan_state *state, const int32_t *trig, const uint8_t *valid, const uint8_t *ik_ok, uint8_t *vertex_ok, int32_t *summary,
                        hipStream_t st);
 hipError_t plan_push(ccmp_plan_state *state, int which, const int32_t *new_index, hipStream_t st);
-/* cycle += bump_cycle, then the solution test on the store's labels */
+/* cycle += bump_cycle, then the solution test on the store's labels: one kernel text for both planners' state blocks */
 hipError_t plan_connected(const GraphStore &s, ccmp_plan_state *state, int bump_cycle, hipStream_t st);
+hipError_t plan_connected(const GraphStore &s, ccmp_rrtc_state *state, int bump_cycle, hipStream_t st);
 /* RRT-Connect on the store (ccmp_rrtc_*, ccmp_roadmap_nearest_in_tree; csrc/ccmp_rrtc.h, ccmp_kernels_rrtc.hip).  Blocks over (partition,
  * query), then the exact merge (partitions > 1: ws_d [Q][P], ws_i [Q][P]); roots [n_roots] is device memory */
 hipError_t rrtc_nearest(const GraphStore &s, const int32_t *roots, int n_roots, const double *queries, size_t Q, unsigned int part, unsigned int partitions,
@@ -494,8 +495,6 @@ hipError_t rrtc_edges(const GraphStore &s, const int32_t *idx, const double *row
                       double *from, double *to, uint8_t *use, hipStream_t st);
 hipError_t rrtc_pick(const RrtcPick &c, hipStream_t st);
 hipError_t rrtc_commit(const GraphStore &s, ccmp_rrtc_state *state, const RrtcCommit &c, hipStream_t st);
-/* cycle += bump_cycle, then the solution test on the store's labels */
-hipError_t rrtc_connected(const GraphStore &s, ccmp_rrtc_state *state, int bump_cycle, hipStream_t st);
 // lib/libccmp_debug.so only (ccmp_kernels_debug.hip)
 hipError_t detmath_probe(const double *x, const double *y, double *out, size_t n, hipStream_t st);
 hipError_t div_probe(const double *num, const double *den, double *out, size_t n, hipStream_t st);

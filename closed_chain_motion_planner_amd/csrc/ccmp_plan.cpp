@@ -5,7 +5,9 @@
 // ccmp_roadmap_connect) on the context's stream, with the kernels of ccmp_kernels_plan.hip between them: the store, the edge list, the
 // labels and the candidates' arrays never cross to the host.  What the host reads: the commits' own counts, 16 bytes after the IK of a
 // check that ran (which of the three branches have a vertex to add: the branches that do not are not launched), and the state block
-// once at the end of a cycle.  The *_ref forms at the end compile the rule text of ccmp_plan.h for the host.
+// once at the end of a cycle.  What every planner handle on the store does alike — the state block's reads, open's upload, the run loop,
+// the solution test, the head of the report — is ccmp_planner.h's, shared with ccmp_rrtc.cpp; the handle and the list of its arrays are
+// there too.  The *_ref forms at the end compile the rule text of ccmp_plan.h for the host.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -20,6 +22,7 @@
 #include "ccmp_ik.h"
 #include "ccmp_launch.h"
 #include "ccmp_plan.h"
+#include "ccmp_planner.h"
 #include "ccmp_pose.h"
 #include "ccmp_resident.h"
 #include "ccmp_scene.h"
@@ -30,85 +33,36 @@ using namespace ccmp_host;
 // the layouts the Python binding restates (closed_chain_motion_planner_amd/_lib.py)
 static_assert(sizeof(ccmp_plan_opts) == 96 && sizeof(ccmp_plan_counters) == 48 && sizeof(ccmp_plan_state) == 240 && sizeof(ccmp_plan_report) == 112, "ccmp_plan_* layout");
 
-struct ccmp_plan {
-  ccmp_roadmap *rm = nullptr;
-  ccmp_ctx *ctx = nullptr;
-  int device = 0;
-  ccmp_problem p;
-  const ccmp_object *obj = nullptr;
-  const ccmp_scene *scene = nullptr;
-  double margin = 0.0;
-  ccmp_ik_opts ik;
-  ccmp_plan_opts o;
-  uint64_t seed = 0;
-  double start_pose[8], goal_pose[8];
-  ccmp_plan_state host; // the state block as last read
-  void *block = nullptr;
-  // the pieces of `block`
-  ccmp_plan_state *state;
-  double *d_start_pose, *d_goal_pose, *d_start_joint, *d_goal_joint;
-  double *from, *prop, *nbr_dist, *q_new, *ik_clear, *states, *carry;
-  int32_t *which, *nbr_idx, *ik_which, *n_states, *iters, *new_index, *mid_index, *grow_state;
-  uint8_t *ik_ok, *ok, *blocked;
-  int32_t *a_idx, *b_idx, *trig, *summary, *ik11_which;
-  double *a_dist, *a_from, *b_dist, *b_from, *targets, *seeds, *ikq, *ik11_clear;
-  uint8_t *valid, *vertex_ok, *ik11_ok;
-};
-
 namespace {
 
-void report_of(const ccmp_plan *pl, int cycles_run, ccmp_plan_report *out)
-{
-  if (!out) return;
-  const ccmp_plan_state &s = pl->host;
-  memset(out, 0, sizeof *out);
-  out->status = s.status;
-  out->cycles_run = cycles_run;
-  out->cycles_total = s.cycle;
-  out->size = ccmp_roadmap_size(pl->rm);
-  out->edges = ccmp_roadmap_num_edges(pl->rm);
-  out->solved_start = s.solved_start;
-  out->solved_goal = s.solved_goal;
-  out->nearest = s.nearest;
-  out->prev_from_goal = s.prev_from_goal;
-  out->prev_from_start = s.prev_from_start;
-  out->counters = s.counters;
-}
-
-int read_state(ccmp_plan *pl)
-{
-  const hipError_t e = hipMemcpyAsync(&pl->host, pl->state, sizeof(ccmp_plan_state), hipMemcpyDeviceToHost, pl->ctx->stream);
-  const hipError_t es = hipStreamSynchronize(pl->ctx->stream);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
-}
-
-int write_state(ccmp_plan *pl)
-{
-  HIP_TRY(hipMemcpyAsync(pl->state, &pl->host, sizeof(ccmp_plan_state), hipMemcpyHostToDevice, pl->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(pl->ctx->stream));
-  return CCMP_OK;
-}
-
-// startgoalMilestone of one vertex (joints [14], pose [8], device rows): the object-metric k-NN and checkMotion from every neighbour,
-// the commit that keeps it even without an edge, and the push onto starts (which == 0) or goals (1).  On an empty store the slots are
-// empty without a launch of the k-NN.
-int milestone(ccmp_plan *pl, const double *joints, const double *pose, int which)
+// addMilestone of Q rows (joints [Q][14], pose [Q][8], device rows): the object-metric k-NN and checkMotion from every neighbour (knn;
+// without it the caller has emptied the slots), then the commit under `flags`
+int connect_commit(ccmp_plan *pl, const double *joints, const double *pose, size_t Q, int flags, bool knn = true)
 {
   hipStream_t st = pl->ctx->stream;
   const int k = pl->o.k;
-  if (ccmp_roadmap_size(pl->rm) == 0) {
-    HIP_TRY(hipMemsetAsync(pl->nbr_idx, 0xff, (size_t)k * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(pl->ok, 0, (size_t)k, st));
-    HIP_TRY(hipMemsetAsync(pl->n_states, 0, (size_t)k * sizeof(int32_t), st));
-  } else {
-    const int rc = ccmp_roadmap_connect(pl->rm, &pl->p, pl->scene, pl->scene ? pl->margin : 0.0, CCMP_METRIC_OBJECT, joints, pose, 1, k, CCMP_KNN_ALL, 0, 1,
+  if (knn) {
+    const int rc = ccmp_roadmap_connect(pl->rm, &pl->p, pl->scene, pl->scene ? pl->margin : 0.0, CCMP_METRIC_OBJECT, joints, pose, Q, k, CCMP_KNN_ALL, 0, 1,
                                         pl->o.max_states, 0, pl->nbr_idx, pl->nbr_dist, pl->states, pl->n_states, pl->ok, pl->iters, pl->blocked, pl->carry, st);
     if (rc != CCMP_OK) return rc;
   }
-  const int rc = ccmp_roadmap_commit(pl->rm, nullptr, pl->nbr_idx, pl->ok, pl->n_states, nullptr, INT_MAX, joints, pose, nullptr, 1, k, nullptr, nullptr, 0,
-                                     CCMP_COMMIT_KEEP_ISOLATED, pl->new_index, pl->mid_index, pl->grow_state, nullptr, nullptr, st);
+  return ccmp_roadmap_commit(pl->rm, nullptr, pl->nbr_idx, pl->ok, pl->n_states, nullptr, INT_MAX, joints, pose, nullptr, Q, k, nullptr, nullptr, 0, flags,
+                             pl->new_index, pl->mid_index, pl->grow_state, nullptr, nullptr, st);
+}
+
+// startgoalMilestone of one vertex (joints [14], pose [8], device rows): connect_commit, which keeps it even without an edge, and the
+// push onto starts (which == 0) or goals (1).  On an empty store the slots are empty without a launch of the k-NN.
+int milestone(ccmp_plan *pl, const double *joints, const double *pose, int which)
+{
+  hipStream_t st = pl->ctx->stream;
+  const size_t k = (size_t)pl->o.k;
+  const bool empty = ccmp_roadmap_size(pl->rm) == 0;
+  if (empty) {
+    HIP_TRY(hipMemsetAsync(pl->nbr_idx, 0xff, k * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(pl->ok, 0, k, st));
+    HIP_TRY(hipMemsetAsync(pl->n_states, 0, k * sizeof(int32_t), st));
+  }
+  const int rc = connect_commit(pl, joints, pose, 1, CCMP_COMMIT_KEEP_ISOLATED, !empty);
   if (rc != CCMP_OK) return rc;
   HIP_TRY(ccmp_launch::plan_push(pl->state, which, pl->new_index, st));
   return CCMP_OK;
@@ -159,11 +113,9 @@ int check(ccmp_plan *pl)
   const uint64_t first = h.next_index; // growth has advanced the device's copy and this one alike (run())
   ccmp_launch::GraphStore gs;
   roadmap_arrays(pl->rm, &gs);
-  int32_t *d_starts = (int32_t *)((char *)pl->state + offsetof(ccmp_plan_state, starts));
-  int32_t *d_goals = (int32_t *)((char *)pl->state + offsetof(ccmp_plan_state, goals));
-  int rc = ccmp_roadmap_closest(pl->rm, d_starts, (size_t)h.n_starts, gs.poses + (size_t)h.goals[0] * 8, pl->a_idx, pl->a_dist, pl->a_from, st);
+  int rc = ccmp_roadmap_closest(pl->rm, dev_starts(pl->state), (size_t)h.n_starts, gs.poses + (size_t)h.goals[0] * 8, pl->a_idx, pl->a_dist, pl->a_from, st);
   if (rc != CCMP_OK) return rc;
-  rc = ccmp_roadmap_closest(pl->rm, d_goals, (size_t)h.n_goals, gs.poses + (size_t)h.starts[0] * 8, pl->b_idx, pl->b_dist, pl->b_from, st);
+  rc = ccmp_roadmap_closest(pl->rm, dev_goals(pl->state), (size_t)h.n_goals, gs.poses + (size_t)h.starts[0] * 8, pl->b_idx, pl->b_dist, pl->b_from, st);
   if (rc != CCMP_OK) return rc;
   ccmp_launch::PlanCheck c{pl->a_idx, pl->a_dist, pl->a_from, pl->b_idx, pl->b_dist, pl->b_from, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0},
                            pl->targets, pl->seeds, pl->trig};
@@ -176,22 +128,12 @@ int check(ccmp_plan *pl)
   if (rc != CCMP_OK) return rc;
   HIP_TRY(ccmp_launch::plan_prefix(pl->state, pl->trig, pl->valid, pl->ik11_ok, pl->vertex_ok, pl->summary, st));
   int32_t sum[4] = {0, 0, 0, 0};
-  {
-    const hipError_t e = hipMemcpyAsync(sum, pl->summary, sizeof sum, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-  }
+  if ((rc = read_back(sum, pl->summary, sizeof sum, st)) != CCMP_OK) return rc;
   if (sum[1]) { rc = milestone(pl, pl->ikq + 14 * ccmp::kPlanGoalRow, pl->d_goal_pose, 1); if (rc != CCMP_OK) return rc; }
   if (sum[0] > 0 && sum[0] <= CCMP_PLAN_LADDER) { // addMilestone of the prefix, one batch
     const size_t L = (size_t)sum[0];
     const double *lj = pl->ikq + 14 * ccmp::kPlanLadderRow, *lp = pl->targets + 8 * ccmp::kPlanLadderRow;
-    rc = ccmp_roadmap_connect(pl->rm, &pl->p, pl->scene, pl->scene ? pl->margin : 0.0, CCMP_METRIC_OBJECT, lj, lp, L, o.k, CCMP_KNN_ALL, 0, 1, o.max_states, 0,
-                              pl->nbr_idx, pl->nbr_dist, pl->states, pl->n_states, pl->ok, pl->iters, pl->blocked, pl->carry, st);
-    if (rc != CCMP_OK) return rc;
-    rc = ccmp_roadmap_commit(pl->rm, nullptr, pl->nbr_idx, pl->ok, pl->n_states, nullptr, INT_MAX, lj, lp, nullptr, L, o.k, nullptr, nullptr, 0, 0, pl->new_index,
-                             pl->mid_index, pl->grow_state, nullptr, nullptr, st);
-    if (rc != CCMP_OK) return rc;
+    if ((rc = connect_commit(pl, lj, lp, L, 0)) != CCMP_OK) return rc;
     HIP_TRY(ccmp_launch::plan_tally(pl->state, nullptr, nullptr, pl->new_index, nullptr, nullptr, L, o.k, 1, st));
   }
   if (sum[2]) { rc = milestone(pl, pl->ikq + 14 * ccmp::kPlanStartRow, pl->d_start_pose, 0); if (rc != CCMP_OK) return rc; }
@@ -211,6 +153,28 @@ int opts_ok(const ccmp_plan_opts *o)
   if (o->max_vertices > (uint64_t)INT32_MAX) return CCMP_EINVAL;
   return CCMP_OK;
 }
+
+// ccmp_planner.h's run loop on this planner: a cycle is growth then check, the solution test is the loop's
+struct PlanLoop {
+  static bool terminal(int status) { return status == CCMP_PLAN_SOLVED || status == CCMP_PLAN_INVALID_GOAL; }
+  static bool full(const ccmp_plan *pl) { return ccmp::plan_full(ccmp_roadmap_size(pl->rm), pl->o.width, pl->o.k, pl->o.max_vertices); }
+  static int cycle(ccmp_plan *pl)
+  {
+    const int rc = growth(pl);
+    if (rc != CCMP_OK) return rc;
+    pl->host.next_index += (uint64_t)pl->o.width; // what plan_tally_kernel did to the device's copy
+    return check(pl);
+  }
+  static void report(const ccmp_plan *pl, int cycles_run, ccmp_plan_report *out)
+  {
+    if (!report_head(pl, cycles_run, out)) return;
+    const ccmp_plan_state &s = pl->host;
+    out->nearest = s.nearest;
+    out->prev_from_goal = s.prev_from_goal;
+    out->prev_from_start = s.prev_from_start;
+    out->counters = s.counters;
+  }
+};
 
 }  // namespace
 
@@ -275,30 +239,8 @@ int ccmp_plan_create(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_object 
     ccmp_pose_of_t_wo(t, pl->goal_pose);
     pl->start_pose[7] = pl->goal_pose[7] = 0.0;
   }
-  // the one block: the state, the fixed rows, the growth step's arrays for Qm queries, the check's
-  const size_t W = (size_t)opts->width, k = (size_t)opts->k, ms = (size_t)opts->max_states;
-  const size_t Qm = W > (size_t)ccmp::kPlanTargets ? W : (size_t)ccmp::kPlanTargets, E = Qm * k;
-  ResultBlock rb;
-  const size_t o_state = rb.take(sizeof(ccmp_plan_state)), o_sp = rb.take(64), o_gp = rb.take(64), o_sj = rb.take(112), o_gj = rb.take(112),
-               o_from = rb.take(Qm * 64), o_prop = rb.take(Qm * 64), o_which = rb.take(Qm * 4), o_ni = rb.take(E * 4), o_nd = rb.take(E * 8),
-               o_qn = rb.take(Qm * 112), o_io = rb.take(Qm), o_iw = rb.take(Qm * 4), o_ic = rb.take(Qm * 8), o_st = rb.take(E * ms * 112), o_ns = rb.take(E * 4),
-               o_ok = rb.take(E), o_it = rb.take(E * 4), o_bl = rb.take(E), o_ca = rb.take(E * 16), o_new = rb.take(Qm * 4), o_mid = rb.take(E * 4),
-               o_gs = rb.take(Qm * 4), o_ai = rb.take(32), o_ad = rb.take(64), o_af = rb.take(64), o_bi = rb.take(32), o_bd = rb.take(64), o_bf = rb.take(64),
-               o_tg = rb.take(ccmp::kPlanTargets * 64), o_sd = rb.take(ccmp::kPlanTargets * 112), o_tr = rb.take(16), o_su = rb.take(16), o_va = rb.take(16),
-               o_vo = rb.take(16), o_iq = rb.take(ccmp::kPlanTargets * 112), o_i11 = rb.take(16), o_w11 = rb.take(ccmp::kPlanTargets * 4),
-               o_c11 = rb.take(ccmp::kPlanTargets * 8);
-  { const int rc = rb.alloc(pl, ctx, __func__); if (rc != CCMP_OK) { delete pl; return rc; } }
-  pl->state = rb.at<ccmp_plan_state>(o_state);
-  pl->d_start_pose = rb.at<double>(o_sp); pl->d_goal_pose = rb.at<double>(o_gp); pl->d_start_joint = rb.at<double>(o_sj); pl->d_goal_joint = rb.at<double>(o_gj);
-  pl->from = rb.at<double>(o_from); pl->prop = rb.at<double>(o_prop); pl->which = rb.at<int32_t>(o_which); pl->nbr_idx = rb.at<int32_t>(o_ni);
-  pl->nbr_dist = rb.at<double>(o_nd); pl->q_new = rb.at<double>(o_qn); pl->ik_ok = rb.at<uint8_t>(o_io); pl->ik_which = rb.at<int32_t>(o_iw);
-  pl->ik_clear = rb.at<double>(o_ic); pl->states = rb.at<double>(o_st); pl->n_states = rb.at<int32_t>(o_ns); pl->ok = rb.at<uint8_t>(o_ok);
-  pl->iters = rb.at<int32_t>(o_it); pl->blocked = rb.at<uint8_t>(o_bl); pl->carry = rb.at<double>(o_ca); pl->new_index = rb.at<int32_t>(o_new);
-  pl->mid_index = rb.at<int32_t>(o_mid); pl->grow_state = rb.at<int32_t>(o_gs); pl->a_idx = rb.at<int32_t>(o_ai); pl->a_dist = rb.at<double>(o_ad);
-  pl->a_from = rb.at<double>(o_af); pl->b_idx = rb.at<int32_t>(o_bi); pl->b_dist = rb.at<double>(o_bd); pl->b_from = rb.at<double>(o_bf);
-  pl->targets = rb.at<double>(o_tg); pl->seeds = rb.at<double>(o_sd); pl->trig = rb.at<int32_t>(o_tr); pl->summary = rb.at<int32_t>(o_su);
-  pl->valid = rb.at<uint8_t>(o_va); pl->vertex_ok = rb.at<uint8_t>(o_vo); pl->ikq = rb.at<double>(o_iq); pl->ik11_ok = rb.at<uint8_t>(o_i11);
-  pl->ik11_which = rb.at<int32_t>(o_w11); pl->ik11_clear = rb.at<double>(o_c11);
+  ResultBlock rb; // the one block: ccmp_planner.h's list
+  { const int rc = rb.alloc_pieces(pl, ctx, __func__); if (rc != CCMP_OK) { delete pl; return rc; } }
 
   hipStream_t st = ctx->stream;
   ccmp_plan_state &h = pl->host;
@@ -310,17 +252,9 @@ int ccmp_plan_create(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_object 
   memcpy(h.nearest_pose, pl->start_pose, sizeof h.nearest_pose);
   int rc = CCMP_OK;
   auto fail = [&](int code) { ccmp_plan_destroy(pl); return code; };
-  quiesce(ctx);
-  {
-    hipError_t e = hipDeviceSynchronize(); // appends on any stream before this call are seen
-    if (e == hipSuccess) e = hipMemcpyAsync(pl->state, &h, sizeof h, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(pl->d_start_pose, pl->start_pose, 64, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(pl->d_goal_pose, pl->goal_pose, 64, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(pl->d_start_joint, p->start_joint, 112, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && goal_joints) e = hipMemcpyAsync(pl->d_goal_joint, goal_joints, 112, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(hip_fail(e, __func__));
-  }
+  rc = planner_upload(pl, {{pl->d_start_pose, pl->start_pose, 64}, {pl->d_goal_pose, pl->goal_pose, 64}, {pl->d_start_joint, p->start_joint, 112},
+                           {pl->d_goal_joint, goal_joints, 112}}, __func__);
+  if (rc != CCMP_OK) return fail(rc);
   if ((rc = milestone(pl, pl->d_start_joint, pl->d_start_pose, 0)) != CCMP_OK) return fail(rc);
   bool have_goal = true;
   if (!goal_joints) { // sampleCalibGoal(t_wo_goal) seeded from the start state
@@ -340,60 +274,14 @@ int ccmp_plan_create(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_object 
   h.size_at_check = (int32_t)ccmp_roadmap_size(rm);
   if (!have_goal) h.status = CCMP_PLAN_INVALID_GOAL;
   if ((rc = write_state(pl)) != CCMP_OK) return fail(rc);
-  if (have_goal) {
-    ccmp_launch::GraphStore gs;
-    roadmap_arrays(rm, &gs);
-    const hipError_t e = ccmp_launch::plan_connected(gs, pl->state, 0, st);
-    if (e != hipSuccess) return fail(hip_fail(e, __func__));
-    if ((rc = read_state(pl)) != CCMP_OK) return fail(rc);
-  }
+  if (have_goal && (rc = solution_test(pl, 0)) != CCMP_OK) return fail(rc);
   *out = pl;
   return CCMP_OK;
 }
 
-int ccmp_plan_run(ccmp_plan *pl, int max_cycles, ccmp_plan_report *out)
-{
-  if (!pl) return no_handle();
-  if (max_cycles < 0) return CCMP_EINVAL;
-  ccmp_plan_state &h = pl->host;
-  if (h.status == CCMP_PLAN_SOLVED || h.status == CCMP_PLAN_INVALID_GOAL || max_cycles == 0) { report_of(pl, 0, out); return CCMP_OK; } // no cycle: the report as it stands
-  DeviceGuard guard(pl->device);
-  if (!guard.ok) return CCMP_ENODEV;
-  hipStream_t st = pl->ctx->stream;
-  quiesce(pl->ctx);
-  HIP_TRY(hipDeviceSynchronize());
-  int ran = 0, status = CCMP_PLAN_BUDGET;
-  for (; ran < max_cycles; ran++) {
-    if (ccmp::plan_full(ccmp_roadmap_size(pl->rm), pl->o.width, pl->o.k, pl->o.max_vertices)) { status = CCMP_PLAN_FULL; break; }
-    { const int rc = growth(pl); if (rc != CCMP_OK) return rc; }
-    h.next_index += (uint64_t)pl->o.width; // what plan_tally_kernel did to the device's copy
-    { const int rc = check(pl); if (rc != CCMP_OK) return rc; }
-    ccmp_launch::GraphStore gs;
-    roadmap_arrays(pl->rm, &gs);
-    HIP_TRY(ccmp_launch::plan_connected(gs, pl->state, 1, st));
-    { const int rc = read_state(pl); if (rc != CCMP_OK) return rc; }
-    if (h.status == CCMP_PLAN_SOLVED) { status = CCMP_PLAN_SOLVED; ran++; break; }
-  }
-  if (h.status != status) { // BUDGET / FULL: the loop's own verdicts, kept in the block too
-    h.status = status;
-    const int rc = write_state(pl);
-    if (rc != CCMP_OK) return rc;
-  }
-  report_of(pl, ran, out);
-  return CCMP_OK;
-}
+int ccmp_plan_run(ccmp_plan *pl, int max_cycles, ccmp_plan_report *out) { return planner_run<PlanLoop>(pl, max_cycles, out); }
 
-int ccmp_plan_state_read(ccmp_plan *pl, ccmp_plan_state *out)
-{
-  if (!pl) return no_handle();
-  if (!out) return CCMP_EINVAL;
-  DeviceGuard guard(pl->device);
-  if (!guard.ok) return CCMP_ENODEV;
-  const int rc = read_state(pl);
-  if (rc != CCMP_OK) return rc;
-  *out = pl->host;
-  return CCMP_OK;
-}
+int ccmp_plan_state_read(ccmp_plan *pl, ccmp_plan_state *out) { return planner_state_read(pl, out); }
 
 void ccmp_plan_destroy(ccmp_plan *pl) { result_destroy(pl); }
 
@@ -423,10 +311,7 @@ int ccmp_plan_connected_ref(const int32_t *labels, size_t N, ccmp_plan_state *st
   if (!state || (N > 0 && !labels) || state->n_starts < 0 || state->n_starts > CCMP_PLAN_MAX_STARTS || state->n_goals < 0 ||
       state->n_goals > CCMP_PLAN_MAX_GOALS)
     return CCMP_EINVAL;
-  if (state->status == CCMP_PLAN_SOLVED) return CCMP_OK;
-  for (int s = 0; s < state->n_starts; s++)
-    for (int g = 0; g < state->n_goals; g++)
-      if (ccmp::plan_pair_connected(state, s, g, labels, N)) { ccmp::plan_solved(state, s, g); return CCMP_OK; }
+  ccmp::first_connected(state, labels, N);
   return CCMP_OK;
 }
 

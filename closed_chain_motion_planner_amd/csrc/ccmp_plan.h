@@ -12,7 +12,8 @@
  *   the caps        a side that fires with its list full (8) does not try its IK; counters.push_refused counts it
  *   the indices     a check that ran advances next_index by 11: goal, ladder 1 .. 9, start, in that order, fired or not
  *   the prefix      the longest run from the ladder's first pose in which valid and ik_ok are both non-zero
- *   the solution    the first pair (s, g), s major and g minor, whose labels agree
+ *   the solution    the first pair (s, g), s major and g minor, whose labels agree — stated as templates over the state type: RRT-Connect's
+ *                   state block (ccmp_rrtc.h) takes the same test, in the same kernel text and the same host fold
  *
  * No arithmetic here rounds differently on host and device: comparisons, one subtraction of two doubles, integer sums. */
 #ifndef CCMP_PLAN_H
@@ -25,6 +26,15 @@ namespace ccmp {
 constexpr int kPlanTargets = 2 + CCMP_PLAN_LADDER; /* the IK targets of a check: goal, ladder 1 .. 9, start */
 constexpr int kPlanGoalRow = 0, kPlanLadderRow = 1, kPlanStartRow = 1 + CCMP_PLAN_LADDER;
 constexpr double kPlanImprove = 0.1;               /* checkForSolution's `dist < previous - 0.1` */
+
+/* ---- what the planners on the store share.  ccmp_plan_state and ccmp_rrtc_state both hold n_starts, n_goals, starts, goals, status, cycle,
+ * solved_start and solved_goal (at different offsets: the shared text below is a template over the state type S, no overlay), and both
+ * spell their status values and caps alike; the shared text names them as ccmp_plan does. */
+static_assert((int)CCMP_PLAN_OPEN == (int)CCMP_RRTC_OPEN && (int)CCMP_PLAN_SOLVED == (int)CCMP_RRTC_SOLVED && (int)CCMP_PLAN_BUDGET == (int)CCMP_RRTC_BUDGET &&
+                  (int)CCMP_PLAN_FULL == (int)CCMP_RRTC_FULL && CCMP_PLAN_MAX_STARTS == CCMP_RRTC_MAX_ROOTS && CCMP_PLAN_MAX_GOALS == CCMP_RRTC_MAX_ROOTS,
+              "one status and one cap for every planner");
+
+CCMP_HD int planner_clamp(int n) { return n < 0 ? 0 : n > CCMP_PLAN_MAX_STARTS ? CCMP_PLAN_MAX_STARTS : n; } /* a list's length as it is used */
 
 CCMP_HD bool plan_gate(unsigned long long size, int32_t size_at_check) { return size_at_check >= 0 && size > (unsigned long long)size_at_check + 3ull; }
 
@@ -62,8 +72,7 @@ CCMP_HD void plan_check(ccmp_plan_state *s, unsigned long long size, const int32
   if (!plan_gate(size, s->size_at_check)) return;
   trig[0] = 1;
   s->counters.checks += 1;
-  const int S = s->n_starts < 0 ? 0 : s->n_starts > CCMP_PLAN_MAX_STARTS ? CCMP_PLAN_MAX_STARTS : s->n_starts;
-  const int G = s->n_goals < 0 ? 0 : s->n_goals > CCMP_PLAN_MAX_GOALS ? CCMP_PLAN_MAX_GOALS : s->n_goals;
+  const int S = planner_clamp(s->n_starts), G = planner_clamp(s->n_goals);
   if (G > 0 && S > 0) {
     int32_t c, p;
     double d, d2;
@@ -97,19 +106,28 @@ CCMP_HD int plan_prefix(const uint8_t *valid, const uint8_t *ik_ok, uint8_t *ver
   return n;
 }
 
-/* pair (si, gi) of the state's lists is connected under `labels` [N] */
-CCMP_HD bool plan_pair_connected(const ccmp_plan_state *s, int si, int gi, const int32_t *labels, unsigned long long N)
+/* the solution test: pair (si, gi) of the state's lists is connected under `labels` [N] */
+template <class S> CCMP_HD bool pair_connected(const S *s, int si, int gi, const int32_t *labels, unsigned long long N)
 {
   const int32_t a = s->starts[si], b = s->goals[gi];
   if (a < 0 || b < 0 || (unsigned long long)a >= N || (unsigned long long)b >= N) return false;
   return labels[a] == labels[b];
 }
 
-CCMP_HD void plan_solved(ccmp_plan_state *s, int si, int gi)
+template <class S> CCMP_HD void solved(S *s, int si, int gi)
 {
   s->status = CCMP_PLAN_SOLVED;
   s->solved_start = s->starts[si];
   s->solved_goal = s->goals[gi];
+}
+
+/* the host's fold: the first connected pair, start-major; a state that is SOLVED stays as it is */
+template <class S> CCMP_HD void first_connected(S *s, const int32_t *labels, unsigned long long N)
+{
+  if (s->status == CCMP_PLAN_SOLVED) return;
+  for (int si = 0; si < s->n_starts; si++)
+    for (int gi = 0; gi < s->n_goals; gi++)
+      if (pair_connected(s, si, gi, labels, N)) { solved(s, si, gi); return; }
 }
 
 /* a committed vertex onto starts (which == 0) or goals (1), under the cap; new_index < 0: nothing was committed */
@@ -130,6 +148,7 @@ CCMP_HD void plan_push(ccmp_plan_state *s, int which, int32_t new_index)
 }  // namespace ccmp
 
 struct ccmp_ctx;
+
 namespace ccmp_launch { struct GraphStore; }
 namespace ccmp_host {
 #pragma GCC visibility push(hidden)

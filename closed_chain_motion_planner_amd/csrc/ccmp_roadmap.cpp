@@ -61,13 +61,12 @@ struct ccmp_roadmap {
 namespace {
 
 constexpr size_t kDefaultCapacity = 1024;
-constexpr size_t kMaxNodes = ((size_t)1 << 31) - 1; // indices are int32
 
 // Moves the store into a block of new_cap rows.  st != nullptr-able: the copy is ordered behind what `st` holds and `st` is waited
 // for once before the old block goes; sync_device: the whole device is waited for first instead (ccmp_roadmap_reserve has no stream).
 int regrow(ccmp_roadmap *rm, size_t new_cap, hipStream_t st, bool sync_device)
 {
-  if (new_cap > kMaxNodes) return CCMP_EINVAL;
+  if (new_cap > kMaxRows) return CCMP_EINVAL;
   ccmp_host::quiesce(rm->ctx);
   if (sync_device) HIP_TRY(hipDeviceSynchronize());
   double *nj = nullptr, *np = nullptr;
@@ -98,7 +97,7 @@ int regrow(ccmp_roadmap *rm, size_t new_cap, hipStream_t st, bool sync_device)
 // the same for the edge block
 int regrow_edges(ccmp_roadmap *rm, size_t new_cap, hipStream_t st)
 {
-  if (new_cap > kMaxNodes) return CCMP_EINVAL;
+  if (new_cap > kMaxRows) return CCMP_EINVAL;
   ccmp_host::quiesce(rm->ctx);
   int32_t *nuv = nullptr;
   double *nw = nullptr;
@@ -123,13 +122,13 @@ int regrow_edges(ccmp_roadmap *rm, size_t new_cap, hipStream_t st)
 // room for `rows` vertices and `edges` edges in all, before a graph call's first launch (at least doubling, as an append grows)
 int graph_reserve(ccmp_roadmap *rm, size_t rows, size_t edges, hipStream_t st)
 {
-  if (rows > kMaxNodes || edges > kMaxNodes) return CCMP_EINVAL;
+  if (rows > kMaxRows || edges > kMaxRows) return CCMP_EINVAL;
   if (rows > rm->cap) {
-    const int rc = regrow(rm, rows > 2 * rm->cap ? rows : 2 * rm->cap > kMaxNodes ? kMaxNodes : 2 * rm->cap, st, false);
+    const int rc = regrow(rm, rows > 2 * rm->cap ? rows : 2 * rm->cap > kMaxRows ? kMaxRows : 2 * rm->cap, st, false);
     if (rc != CCMP_OK) return rc;
   }
   if (edges > rm->cap_e) {
-    const size_t twice = 2 * rm->cap_e > kMaxNodes ? kMaxNodes : 2 * rm->cap_e;
+    const size_t twice = 2 * rm->cap_e > kMaxRows ? kMaxRows : 2 * rm->cap_e;
     const int rc = regrow_edges(rm, edges > twice ? edges : twice, st);
     if (rc != CCMP_OK) return rc;
   }
@@ -171,7 +170,7 @@ int commit_checks(size_t N, const int32_t *nbr_idx, const uint8_t *edge_ok, cons
     if (roots[i] < 0 || (size_t)roots[i] >= N) return CCMP_EINVAL;
   if (Q == 0) return CCMP_OK;
   if (max_states < 1 || !nbr_idx || !edge_ok || !n_states || !new_joints || !new_poses || !new_index || !mid_index || !grow_state) return CCMP_EINVAL;
-  if (Q > kMaxNodes / (size_t)(k + 1) || N > kMaxNodes - Q * (size_t)(k + 1)) return CCMP_EINVAL;
+  if (Q > kMaxRows / (size_t)(k + 1) || N > kMaxRows - Q * (size_t)(k + 1)) return CCMP_EINVAL;
   return CCMP_OK;
 }
 
@@ -187,10 +186,7 @@ ccmp::graph_roots roots_of(const int32_t *roots, int n_roots)
 int graph_finish(ccmp_roadmap *rm, const int32_t *totals, hipStream_t st, size_t *vertices_added, size_t *edges_added)
 {
   int32_t t[4] = {0, 0, 0, 0};
-  const hipError_t e = hipMemcpyAsync(t, totals, sizeof t, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
+  { const int rc = read_back(t, totals, sizeof t, st); if (rc != CCMP_OK) return rc; }
   rm->size += (size_t)t[0];
   rm->n_edges += (size_t)t[1];
   rm->floor = (size_t)t[2];
@@ -250,7 +246,7 @@ void ccmp_pose_from_t_wo(const double t_wo[12], double pose[8]) { ccmp_pose_of_t
 
 ccmp_roadmap *ccmp_roadmap_create(ccmp_ctx *ctx, size_t capacity_hint)
 {
-  if (!ctx || capacity_hint > kMaxNodes) return nullptr;
+  if (!ctx || capacity_hint > kMaxRows) return nullptr;
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return nullptr;
   ccmp_roadmap *rm = new (std::nothrow) ccmp_roadmap();
@@ -292,7 +288,7 @@ size_t ccmp_roadmap_size(const ccmp_roadmap *rm) { return rm ? rm->size : 0; }
 int ccmp_roadmap_reserve(ccmp_roadmap *rm, size_t n)
 {
   if (!rm) return no_handle();
-  if (n > kMaxNodes) return CCMP_EINVAL;
+  if (n > kMaxRows) return CCMP_EINVAL;
   if (n <= rm->cap) return CCMP_OK;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
@@ -305,14 +301,14 @@ int ccmp_roadmap_append(ccmp_roadmap *rm, const ccmp_problem *p, const double *j
   if (!rm) return no_handle();
   if (first_index) *first_index = rm->size;
   if (Q == 0) return CCMP_OK;
-  if ((!joints && !poses) || Q > kMaxNodes - rm->size) return CCMP_EINVAL;
+  if ((!joints && !poses) || Q > kMaxRows - rm->size) return CCMP_EINVAL;
   if (!poses) { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; } // the poses are derived from the joints and the problem
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
   const size_t need = rm->size + Q;
   if (need > rm->cap) {
-    const int rc = regrow(rm, need > 2 * rm->cap ? need : 2 * rm->cap > kMaxNodes ? kMaxNodes : 2 * rm->cap, st, false);
+    const int rc = regrow(rm, need > 2 * rm->cap ? need : 2 * rm->cap > kMaxRows ? kMaxRows : 2 * rm->cap, st, false);
     if (rc != CCMP_OK) return rc;
   }
   double *jrow = rm->joints + rm->size * 14, *prow = rm->poses + rm->size * 8; // rows size .. size + Q - 1 <= cap - 1
@@ -500,7 +496,7 @@ int ccmp_roadmap_append_host(ccmp_roadmap *rm, const ccmp_problem *p, const doub
   if (!rm) return no_handle();
   if (first_index) *first_index = rm->size;
   if (Q == 0) return CCMP_OK;
-  if ((!joints && !poses) || Q > kMaxNodes - rm->size) return CCMP_EINVAL;
+  if ((!joints && !poses) || Q > kMaxRows - rm->size) return CCMP_EINVAL;
   if (!poses) { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
@@ -674,7 +670,7 @@ double ccmp_joint_distance(const double a[14], const double b[14]) { return ccmp
 
 int ccmp_graph_labels_ref(const int32_t *uv, size_t E, size_t N, int32_t *labels)
 {
-  if (N > kMaxNodes || (N > 0 && !labels) || (E > 0 && !uv)) return CCMP_EINVAL;
+  if (N > kMaxRows || (N > 0 && !labels) || (E > 0 && !uv)) return CCMP_EINVAL;
   for (size_t e = 0; e < E; e++) // what ccmp_roadmap_add_edges_host refuses: an endpoint that is no vertex, a loop
     if (uv[2 * e] < 0 || (size_t)uv[2 * e] >= N || uv[2 * e + 1] < 0 || (size_t)uv[2 * e + 1] >= N || uv[2 * e] == uv[2 * e + 1]) return CCMP_EINVAL;
   for (size_t i = 0; i < N; i++) labels[i] = (int32_t)i;
@@ -702,7 +698,7 @@ int ccmp_roadmap_commit(ccmp_roadmap *rm, const ccmp_problem *p, const int32_t *
   if (mids) { const int rc = problem_ok(p); if (rc != CCMP_OK) return rc; }
   if (Q == 0) return CCMP_OK;
   const size_t S = Q * (size_t)k;
-  if (rm->n_edges > kMaxNodes - S) return CCMP_EINVAL;
+  if (rm->n_edges > kMaxRows - S) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
@@ -791,7 +787,7 @@ int ccmp_roadmap_add_edges(ccmp_roadmap *rm, const int32_t *uv, size_t E, size_t
   if (!rm) return no_handle();
   if (rejected) *rejected = 0;
   if (E == 0) return CCMP_OK;
-  if (!uv || E > kMaxNodes || rm->n_edges > kMaxNodes - E) return CCMP_EINVAL;
+  if (!uv || E > kMaxRows || rm->n_edges > kMaxRows - E) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
   if (!guard.ok) return CCMP_ENODEV;
   hipStream_t st = (hipStream_t)hip_stream;
@@ -852,7 +848,7 @@ int ccmp_roadmap_closest_ref(const double *store_poses, const int32_t *labels, s
                              int32_t *idx, double *dist, double *from_dist)
 {
   if (F == 0) return CCMP_OK;
-  if (F > CCMP_CLOSEST_MAX_FROM || N > kMaxNodes || !store_poses || !labels || !from_idx || !target_pose || !idx || !dist || !from_dist) return CCMP_EINVAL;
+  if (F > CCMP_CLOSEST_MAX_FROM || N > kMaxRows || !store_poses || !labels || !from_idx || !target_pose || !idx || !dist || !from_dist) return CCMP_EINVAL;
   for (size_t f = 0; f < F; f++)
     if (from_idx[f] < 0 || (size_t)from_idx[f] >= N) return CCMP_EINVAL;
   double x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -918,7 +914,7 @@ int ccmp_roadmap_add_edges_host(ccmp_roadmap *rm, const int32_t *uv, size_t E)
 {
   if (!rm) return no_handle();
   if (E == 0) return CCMP_OK;
-  if (!uv || E > kMaxNodes || rm->n_edges > kMaxNodes - E) return CCMP_EINVAL;
+  if (!uv || E > kMaxRows || rm->n_edges > kMaxRows - E) return CCMP_EINVAL;
   for (size_t e = 0; e < E; e++)
     if (uv[2 * e] < 0 || uv[2 * e + 1] < 0 || (size_t)uv[2 * e] >= rm->size || (size_t)uv[2 * e + 1] >= rm->size || uv[2 * e] == uv[2 * e + 1]) return CCMP_EINVAL;
   DeviceGuard guard(rm->device);
@@ -1085,7 +1081,7 @@ int ccmp_graph_shortest_paths_ref(const int32_t *uv, const double *w, size_t E, 
 {
   if (F == 0) return CCMP_OK;
   { const int rc = path_checks(src, dst, F, max_len, cost, path_len, path); if (rc != CCMP_OK) return rc; }
-  if (N > kMaxNodes || E > kMaxNodes || (E > 0 && (!uv || !w))) return CCMP_EINVAL;
+  if (N > kMaxRows || E > kMaxRows || (E > 0 && (!uv || !w))) return CCMP_EINVAL;
   for (size_t e = 0; e < E; e++) // what ccmp_roadmap_add_edges_host refuses
     if (uv[2 * e] < 0 || (size_t)uv[2 * e] >= N || uv[2 * e + 1] < 0 || (size_t)uv[2 * e + 1] >= N || uv[2 * e] == uv[2 * e + 1]) return CCMP_EINVAL;
   for (size_t f = 0; f < F; f++)

@@ -4,8 +4,10 @@
 // the library's own entry points (ccmp_sample_project_batch, ccmp_joint_valid_batch, ccmp_clearance_batch, ccmp_geodesic_batch_ex /
 // ccmp_geodesic_scene_batch, ccmp_roadmap_append, ccmp_roadmap_add_edges) on the context's stream, with the kernels of
 // ccmp_kernels_rrtc.hip between them: the samples, the lists and the picks never cross to the host.  What the host reads per cycle: the
-// commit kernel's 16 bytes of counts, add_edges' own read-back and the state block once at the end.  The *_ref forms at the end compile
-// the rule text of ccmp_rrtc.h for the host.
+// commit kernel's 16 bytes of counts, add_edges' own read-back and the state block once at the end.  The state block's reads, open's
+// upload, the run loop with its solution test and the head of the report are ccmp_planner.h's, shared with ccmp_plan.cpp; the handle and
+// the list of its arrays are there too.  The *_ref forms at the end compile the rule text of ccmp_rrtc.h (the solution test:
+// ccmp_plan.h) for the host.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -20,6 +22,7 @@
 #include "ccmp_graph.h"
 #include "ccmp_launch.h"
 #include "ccmp_plan.h"
+#include "ccmp_planner.h"
 #include "ccmp_policy.h"
 #include "ccmp_resident.h"
 #include "ccmp_rrtc.h"
@@ -32,61 +35,7 @@ using namespace ccmp_host;
 static_assert(sizeof(ccmp_rrtc_opts) == 32 && sizeof(ccmp_rrtc_counters) == 48 && sizeof(ccmp_rrtc_state) == 160 && sizeof(ccmp_rrtc_report) == 104,
               "ccmp_rrtc_* layout");
 
-struct ccmp_rrtc {
-  ccmp_roadmap *rm = nullptr;
-  ccmp_ctx *ctx = nullptr;
-  int device = 0;
-  ccmp_problem p;
-  const ccmp_scene *scene = nullptr;
-  double margin = 0.0;
-  ccmp_rrtc_opts o;
-  uint64_t seed = 0;
-  ccmp_rrtc_state host; // the state block as last read
-  void *block = nullptr;
-  // the pieces of `block`
-  ccmp_rrtc_state *state;
-  double *samples, *clear, *dist, *from, *to, *states, *carry, *rowA, *rowB, *gapB, *rows;
-  uint8_t *s_ok, *jv, *free_, *use, *ok, *blocked, *madeA;
-  int32_t *idxA, *idxB, *n_states, *iters, *outA, *outB, *rixA, *rixB, *parA, *parB, *uv, *counts;
-};
-
 namespace {
-
-constexpr size_t kMaxNodes = ((size_t)1 << 31) - 1; // indices are int32
-
-void report_of(const ccmp_rrtc *pl, int cycles_run, ccmp_rrtc_report *out)
-{
-  if (!out) return;
-  const ccmp_rrtc_state &s = pl->host;
-  memset(out, 0, sizeof *out);
-  out->status = s.status;
-  out->cycles_run = cycles_run;
-  out->cycles_total = s.cycle;
-  out->size = ccmp_roadmap_size(pl->rm);
-  out->edges = ccmp_roadmap_num_edges(pl->rm);
-  out->solved_start = s.solved_start;
-  out->solved_goal = s.solved_goal;
-  out->best_a = s.best_a;
-  out->best_b = s.best_b;
-  out->best_gap = s.best_gap;
-  out->counters = s.counters;
-}
-
-int read_state(ccmp_rrtc *pl)
-{
-  const hipError_t e = hipMemcpyAsync(&pl->host, pl->state, sizeof(ccmp_rrtc_state), hipMemcpyDeviceToHost, pl->ctx->stream);
-  const hipError_t es = hipStreamSynchronize(pl->ctx->stream);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return CCMP_OK;
-}
-
-int write_state(ccmp_rrtc *pl)
-{
-  HIP_TRY(hipMemcpyAsync(pl->state, &pl->host, sizeof(ccmp_rrtc_state), hipMemcpyHostToDevice, pl->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(pl->ctx->stream));
-  return CCMP_OK;
-}
 
 // what every form of a nearest-in-tree call checks first
 int nearest_checks(int n_roots, const int32_t *roots, const double *queries, size_t Q, const int32_t *idx, const double *dist)
@@ -124,6 +73,7 @@ int traverse(ccmp_rrtc *pl)
                                 pl->o.round_budget, 0, st);
 }
 
+// steps 1 to 4 of a cycle; step 5, the solution test, is the run loop's
 int cycle(ccmp_rrtc *pl)
 {
   hipStream_t st = pl->ctx->stream;
@@ -131,8 +81,7 @@ int cycle(ccmp_rrtc *pl)
   const ccmp_rrtc_state &h = pl->host;
   const size_t W = (size_t)o.width;
   const bool a_is_start = (h.cycle & 1) == 0;
-  int32_t *d_starts = (int32_t *)((char *)pl->state + offsetof(ccmp_rrtc_state, starts));
-  int32_t *d_goals = (int32_t *)((char *)pl->state + offsetof(ccmp_rrtc_state, goals));
+  int32_t *d_starts = dev_starts(pl->state), *d_goals = dev_goals(pl->state);
   const int32_t *rootsA = a_is_start ? d_starts : d_goals, *rootsB = a_is_start ? d_goals : d_starts;
   const int nA = a_is_start ? h.n_starts : h.n_goals, nB = a_is_start ? h.n_goals : h.n_starts;
   // 1. samples
@@ -163,20 +112,27 @@ int cycle(ccmp_rrtc *pl)
                                                            pl->rowB, pl->gapB, pl->rows, pl->uv, pl->counts},
                                    st));
   int32_t cnt[4] = {0, 0, 0, 0};
-  {
-    const hipError_t e = hipMemcpyAsync(cnt, pl->counts, sizeof cnt, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-  }
+  if ((rc = read_back(cnt, pl->counts, sizeof cnt, st)) != CCMP_OK) return rc;
   if (cnt[0] < 0 || (size_t)cnt[0] > 2 * W || cnt[1] < 0 || (size_t)cnt[1] > 2 * W) return CCMP_EINVAL; // (cannot happen: the kernel counts flags)
   if ((rc = ccmp_roadmap_append(pl->rm, &pl->p, pl->rows, nullptr, (size_t)cnt[0], nullptr, st)) != CCMP_OK) return rc;
   if (cnt[1] > 0 && (rc = ccmp_roadmap_add_edges(pl->rm, pl->uv, 2 * W, nullptr, st)) != CCMP_OK) return rc;
-  // 5. the solution test
-  roadmap_arrays(pl->rm, &gs);
-  HIP_TRY(ccmp_launch::rrtc_connected(gs, pl->state, 1, st));
-  return read_state(pl);
+  return CCMP_OK;
 }
+
+struct RrtcLoop {
+  static bool terminal(int status) { return status == CCMP_RRTC_SOLVED; }
+  static bool full(const ccmp_rrtc *pl) { return ccmp::rrtc_full(ccmp_roadmap_size(pl->rm), pl->o.width, pl->o.max_vertices); }
+  static int cycle(ccmp_rrtc *pl) { return ::cycle(pl); }
+  static void report(const ccmp_rrtc *pl, int cycles_run, ccmp_rrtc_report *out)
+  {
+    if (!report_head(pl, cycles_run, out)) return;
+    const ccmp_rrtc_state &s = pl->host;
+    out->best_a = s.best_a;
+    out->best_b = s.best_b;
+    out->best_gap = s.best_gap;
+    out->counters = s.counters;
+  }
+};
 
 int opts_ok(const ccmp_rrtc_opts *o)
 {
@@ -227,26 +183,9 @@ int ccmp_rrtc_create(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *
   pl->margin = scene ? margin : 0.0;
   pl->o = *opts;
   pl->seed = rng_seed;
-  // the one block: the state, then the cycle's arrays for W rows
-  const size_t W = (size_t)opts->width, ms = (size_t)opts->max_states;
-  ResultBlock rb;
-  const size_t o_state = rb.take(sizeof(ccmp_rrtc_state)), o_sm = rb.take(W * 112), o_cl = rb.take(W * 8), o_di = rb.take(W * 8), o_fr = rb.take(W * 112),
-               o_to = rb.take(W * 112), o_st = rb.take(W * ms * 112), o_ca = rb.take(W * 16), o_ra = rb.take(W * 112), o_rb = rb.take(W * 112),
-               o_gb = rb.take(W * 8), o_rows = rb.take(2 * W * 112), o_so = rb.take(W), o_jv = rb.take(W), o_fe = rb.take(W), o_us = rb.take(W), o_ok = rb.take(W),
-               o_bl = rb.take(W), o_ma = rb.take(W), o_ia = rb.take(W * 4), o_ib = rb.take(W * 4), o_ns = rb.take(W * 4), o_it = rb.take(W * 4),
-               o_oa = rb.take(W * 4), o_ob = rb.take(W * 4), o_xa = rb.take(W * 4), o_xb = rb.take(W * 4), o_pa = rb.take(W * 4), o_pb = rb.take(W * 4),
-               o_uv = rb.take(2 * W * 8), o_cn = rb.take(16);
-  { const int rc = rb.alloc(pl, ctx, __func__); if (rc != CCMP_OK) { delete pl; return rc; } }
-  pl->state = rb.at<ccmp_rrtc_state>(o_state);
-  pl->samples = rb.at<double>(o_sm); pl->clear = rb.at<double>(o_cl); pl->dist = rb.at<double>(o_di); pl->from = rb.at<double>(o_fr); pl->to = rb.at<double>(o_to);
-  pl->states = rb.at<double>(o_st); pl->carry = rb.at<double>(o_ca); pl->rowA = rb.at<double>(o_ra); pl->rowB = rb.at<double>(o_rb); pl->gapB = rb.at<double>(o_gb);
-  pl->rows = rb.at<double>(o_rows); pl->s_ok = rb.at<uint8_t>(o_so); pl->jv = rb.at<uint8_t>(o_jv); pl->free_ = rb.at<uint8_t>(o_fe); pl->use = rb.at<uint8_t>(o_us);
-  pl->ok = rb.at<uint8_t>(o_ok); pl->blocked = rb.at<uint8_t>(o_bl); pl->madeA = rb.at<uint8_t>(o_ma); pl->idxA = rb.at<int32_t>(o_ia); pl->idxB = rb.at<int32_t>(o_ib);
-  pl->n_states = rb.at<int32_t>(o_ns); pl->iters = rb.at<int32_t>(o_it); pl->outA = rb.at<int32_t>(o_oa); pl->outB = rb.at<int32_t>(o_ob);
-  pl->rixA = rb.at<int32_t>(o_xa); pl->rixB = rb.at<int32_t>(o_xb); pl->parA = rb.at<int32_t>(o_pa); pl->parB = rb.at<int32_t>(o_pb); pl->uv = rb.at<int32_t>(o_uv);
-  pl->counts = rb.at<int32_t>(o_cn);
+  ResultBlock rb; // the one block: ccmp_planner.h's list
+  { const int rc = rb.alloc_pieces(pl, ctx, __func__); if (rc != CCMP_OK) { delete pl; return rc; } }
 
-  hipStream_t st = ctx->stream;
   ccmp_rrtc_state &h = pl->host;
   memset(&h, 0, sizeof h);
   h.n_starts = n_starts;
@@ -258,60 +197,15 @@ int ccmp_rrtc_create(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *
   h.solved_start = h.solved_goal = h.best_a = h.best_b = -1;
   h.best_gap = __builtin_inf();
   auto fail = [&](int code) { ccmp_rrtc_destroy(pl); return code; };
-  quiesce(ctx);
-  {
-    hipError_t e = hipDeviceSynchronize(); // appends on any stream before this call are seen
-    if (e == hipSuccess) e = hipMemcpyAsync(pl->state, &h, sizeof h, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(hip_fail(e, __func__));
-  }
-  ccmp_launch::GraphStore gs;
-  roadmap_arrays(rm, &gs);
-  {
-    const hipError_t e = ccmp_launch::rrtc_connected(gs, pl->state, 0, st);
-    if (e != hipSuccess) return fail(hip_fail(e, __func__));
-  }
-  { const int rc = read_state(pl); if (rc != CCMP_OK) return fail(rc); }
+  { const int rc = planner_upload(pl, {}, __func__); if (rc != CCMP_OK) return fail(rc); }
+  { const int rc = solution_test(pl, 0); if (rc != CCMP_OK) return fail(rc); }
   *out = pl;
   return CCMP_OK;
 }
 
-int ccmp_rrtc_run(ccmp_rrtc *pl, int max_cycles, ccmp_rrtc_report *out)
-{
-  if (!pl) return no_handle();
-  if (max_cycles < 0) return CCMP_EINVAL;
-  ccmp_rrtc_state &h = pl->host;
-  if (h.status == CCMP_RRTC_SOLVED || max_cycles == 0) { report_of(pl, 0, out); return CCMP_OK; } // no cycle: the report as it stands
-  DeviceGuard guard(pl->device);
-  if (!guard.ok) return CCMP_ENODEV;
-  quiesce(pl->ctx);
-  HIP_TRY(hipDeviceSynchronize());
-  int ran = 0, status = CCMP_RRTC_BUDGET;
-  for (; ran < max_cycles; ran++) {
-    if (ccmp::rrtc_full(ccmp_roadmap_size(pl->rm), pl->o.width, pl->o.max_vertices)) { status = CCMP_RRTC_FULL; break; }
-    { const int rc = cycle(pl); if (rc != CCMP_OK) return rc; }
-    if (h.status == CCMP_RRTC_SOLVED) { status = CCMP_RRTC_SOLVED; ran++; break; }
-  }
-  if (h.status != status) { // BUDGET / FULL: the loop's own verdicts, kept in the block too
-    h.status = status;
-    const int rc = write_state(pl);
-    if (rc != CCMP_OK) return rc;
-  }
-  report_of(pl, ran, out);
-  return CCMP_OK;
-}
+int ccmp_rrtc_run(ccmp_rrtc *pl, int max_cycles, ccmp_rrtc_report *out) { return planner_run<RrtcLoop>(pl, max_cycles, out); }
 
-int ccmp_rrtc_state_read(ccmp_rrtc *pl, ccmp_rrtc_state *out)
-{
-  if (!pl) return no_handle();
-  if (!out) return CCMP_EINVAL;
-  DeviceGuard guard(pl->device);
-  if (!guard.ok) return CCMP_ENODEV;
-  const int rc = read_state(pl);
-  if (rc != CCMP_OK) return rc;
-  *out = pl->host;
-  return CCMP_OK;
-}
+int ccmp_rrtc_state_read(ccmp_rrtc *pl, ccmp_rrtc_state *out) { return planner_state_read(pl, out); }
 
 void ccmp_rrtc_destroy(ccmp_rrtc *pl) { result_destroy(pl); }
 
@@ -356,7 +250,7 @@ int ccmp_roadmap_nearest_in_tree_ref(const double *store_joints, const int32_t *
                                      size_t Q, int32_t *idx, double *dist)
 {
   { const int rc = nearest_checks(n_roots, roots, queries, Q, idx, dist); if (rc != CCMP_OK) return rc; }
-  if (N > kMaxNodes || (N > 0 && (!store_joints || !labels))) return CCMP_EINVAL;
+  if (N > kMaxRows || (N > 0 && (!store_joints || !labels))) return CCMP_EINVAL;
   for (int i = 0; i < n_roots; i++)
     if (roots[i] < 0 || (size_t)roots[i] >= N) return CCMP_EINVAL;
   int32_t lab[CCMP_RRTC_MAX_ROOTS];
@@ -377,7 +271,7 @@ int ccmp_roadmap_nearest_in_tree_ref(const double *store_joints, const int32_t *
 
 int ccmp_rrtc_nearest_shape(const ccmp_ctx *ctx, size_t Q, size_t N, unsigned int *part, unsigned int *partitions)
 {
-  if (!part || !partitions || Q >= ((size_t)1 << 31) || N > kMaxNodes) return CCMP_EINVAL;
+  if (!part || !partitions || Q >= ((size_t)1 << 31) || N > kMaxRows) return CCMP_EINVAL;
   plan_rrtc_nearest(ctx ? ctx : &default_ctx(), Q, N, part, partitions);
   return CCMP_OK;
 }
@@ -385,7 +279,7 @@ int ccmp_rrtc_nearest_shape(const ccmp_ctx *ctx, size_t Q, size_t N, unsigned in
 int ccmp_rrtc_pick_ref(int mode, const double *states, const int32_t *n_states, const uint8_t *ok, const uint8_t *use, const double *to, const double *d,
                        size_t E, int max_states, double range, int32_t *outcome, int32_t *row_index, double *row, double *gap)
 {
-  if ((mode != 0 && mode != 1) || max_states < 1 || E > kMaxNodes) return CCMP_EINVAL;
+  if ((mode != 0 && mode != 1) || max_states < 1 || E > kMaxRows) return CCMP_EINVAL;
   if (E == 0) return CCMP_OK;
   if (!states || !n_states || !ok || !to || !outcome || !row_index || !row || (mode == 0 && !d)) return CCMP_EINVAL;
   for (size_t e = 0; e < E; e++) {
@@ -418,7 +312,7 @@ int ccmp_rrtc_pick_batch(ccmp_ctx *ctx, int mode, const double *states, const in
                          void *hip_stream)
 {
   if (!ctx) return no_handle();
-  if ((mode != 0 && mode != 1) || max_states < 1 || E > kMaxNodes) return CCMP_EINVAL;
+  if ((mode != 0 && mode != 1) || max_states < 1 || E > kMaxRows) return CCMP_EINVAL;
   if (E == 0) return CCMP_OK;
   if (!states || !n_states || !ok || !to || !outcome || !row_index || !row || (mode == 0 && !d)) return CCMP_EINVAL;
   DeviceGuard guard(ctx->device);
@@ -434,10 +328,7 @@ int ccmp_rrtc_connected_ref(const int32_t *labels, size_t N, ccmp_rrtc_state *st
   if (!state || (N > 0 && !labels) || state->n_starts < 0 || state->n_starts > CCMP_PLAN_MAX_STARTS || state->n_goals < 0 ||
       state->n_goals > CCMP_PLAN_MAX_GOALS)
     return CCMP_EINVAL;
-  if (state->status == CCMP_RRTC_SOLVED) return CCMP_OK;
-  for (int s = 0; s < state->n_starts; s++)
-    for (int g = 0; g < state->n_goals; g++)
-      if (ccmp::rrtc_pair_connected(state, s, g, labels, N)) { ccmp::rrtc_solved(state, s, g); return CCMP_OK; }
+  ccmp::first_connected(state, labels, N);
   return CCMP_OK;
 }
 

@@ -11,7 +11,7 @@
  *   extend       rrtc_extend: TRAPPED / ADVANCED (listed state j, at least 1) / REACHED (the sample row) / UNSETTLED
  *   connect      rrtc_connect: NOTHING / ADDED (the last stored state) / JOINED
  *   FULL         size + 2 width > max_vertices
- *   the solution the first pair (s, g), s major and g minor, whose labels agree
+ *   the solution ccmp_plan.h's, one text for both planners: the first pair (s, g), s major and g minor, whose labels agree
  *
  * No arithmetic here rounds differently on host and device: comparisons, sums of two doubles, integer sums. */
 #ifndef CCMP_RRTC_H
@@ -90,21 +90,6 @@ CCMP_HD int32_t rrtc_connect(int32_t n_states, int max_states, uint8_t ok, doubl
   if (m < 2) return CCMP_RRTC_CONNECT_NOTHING;
   *row = m - 1;
   return CCMP_RRTC_CONNECT_ADDED;
-}
-
-/* pair (si, gi) of the state's lists is connected under `labels` [N] */
-CCMP_HD bool rrtc_pair_connected(const ccmp_rrtc_state *s, int si, int gi, const int32_t *labels, unsigned long long N)
-{
-  const int32_t a = s->starts[si], b = s->goals[gi];
-  if (a < 0 || b < 0 || (unsigned long long)a >= N || (unsigned long long)b >= N) return false;
-  return labels[a] == labels[b];
-}
-
-CCMP_HD void rrtc_solved(ccmp_rrtc_state *s, int si, int gi)
-{
-  s->status = CCMP_RRTC_SOLVED;
-  s->solved_start = s->starts[si];
-  s->solved_goal = s->goals[gi];
 }
 
 }  // namespace ccmp

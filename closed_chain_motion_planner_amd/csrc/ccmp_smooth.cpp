@@ -117,12 +117,7 @@ int smooth(ccmp_ctx *ctx, const ccmp_problem *p, const ccmp_scene *scene, double
   HIP_TRY(hipMemsetAsync(w_moved, 0, F * sizeof(int32_t), st));
   HIP_TRY(ccmp_launch::smooth_load(path_joints, path_len, F, max_len, cap, buf[0], w_bad, st));
   HIP_TRY(ccmp_launch::smooth_length(buf[0], buf[0], nullptr, path_len, F, cap, w_len_in, st));
-  {
-    const hipError_t e = hipMemcpyAsync(bad.data(), w_bad, F, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    HIP_TRY(e);
-    HIP_TRY(es);
-  }
+  { const int rc = read_back(bad.data(), w_bad, F, st); if (rc != CCMP_OK) return rc; }
 
   std::vector<int32_t> len(len0), passes(F, 0), moved(F, 0), stop(F, -1), moved_h(F, 0);
   for (size_t f = 0; f < F; f++) {

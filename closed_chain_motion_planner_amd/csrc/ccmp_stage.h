@@ -1,7 +1,8 @@
 /* ccmp_stage.h — what the planner-side *_host entry points share (ccmp_roadmap.cpp, ccmp_object.cpp, ccmp_ik.cpp, ccmp_shortcut.cpp,
  * ccmp_dense.cpp, ccmp_smooth.cpp, ccmp_retime.cpp): the answer to a missing handle, two small checks, the synchronous staged call on
  * the context's stream, the device memory of one call and, for the path units, the pieces of an entry point's prologue (the read of
- * path_len, the overlap test, the row bound, the options) and the one allocation of a result handle.  Host only, C++ linkage, nothing
+ * path_len, the overlap test, the row bound, the options), the plain synchronous read (read_back) and the one allocation of a result
+ * handle, which the planner handles (ccmp_plan.cpp, ccmp_rrtc.cpp) state as one list of pieces.  Host only, C++ linkage, nothing
  * of the C ABI.  The projector's host path (ccmp_host_io.cpp: HostIO, the sharded calls) has other requirements and does not use
  * this.  Argument checks stay with the entry points: they run before the device guard and before anything here is constructed. */
 #ifndef CCMP_STAGE_H
@@ -128,16 +129,23 @@ class CallArena {
  * stay so, because the list of the library's dynamic symbols is kept as it is; what is added here adds nothing to it. */
 #pragma GCC visibility push(hidden)
 
+/* a synchronous read of device memory on `st`: copied, waited for on every path, then the copy's error before the wait's */
+inline int read_back(void *dst, const void *dev_src, size_t bytes, hipStream_t st)
+{
+  const hipError_t e = hipMemcpyAsync(dst, dev_src, bytes, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return CCMP_OK;
+}
+
 /* the device form's one read of path_len [F] (device memory), before any launch: copied, waited for, checked */
 inline int read_lens(const int32_t *path_len, size_t F, int max_len, hipStream_t st, std::vector<int32_t> *len)
 {
   len->resize(F);
   if (F == 0) return CCMP_OK;
-  const hipError_t e = hipMemcpyAsync(len->data(), path_len, F * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return lens_ok(len->data(), F, max_len);
+  const int rc = read_back(len->data(), path_len, F * sizeof(int32_t), st);
+  return rc != CCMP_OK ? rc : lens_ok(len->data(), F, max_len);
 }
 
 constexpr size_t kMaxRows = ((size_t)1 << 31) - 1; // rows and slots are int32: a batch beyond this is an argument error
@@ -154,12 +162,26 @@ inline bool overlaps(const void *a, size_t na, const void *b, size_t nb)
 template <class O> O opts_or(const O *given, void (*defaults)(O *)) { O o; defaults(&o); return given ? *given : o; }
 
 /* The one allocation of a result handle H (ccmp_dense_paths, ccmp_sampled_paths: fields ctx, device, block): take() the pieces, then
- * alloc(), then the handle's arrays at<T>() their offsets.  result_destroy is the whole of the handle's *_destroy. */
+ * alloc(), then the handle's arrays at<T>() their offsets.  result_destroy is the whole of the handle's *_destroy.
+ * A handle of many arrays (ccmp_plan, ccmp_rrtc) states each ONCE instead, as piece(pointer member, element count) in a function
+ * pieces(ResultBlock &) of its own: alloc_pieces() walks that list twice, to size the block and, after place(), to set the pointers.
+ * The bytes of a piece follow from its pointer's type; the order of the list is the order in the block. */
 struct ResultBlock {
   size_t total = 0;
   char *base = nullptr;
   size_t take(size_t bytes) { const size_t off = total; total += align256(bytes); return off; }
   template <class T> T *at(size_t off) const { return (T *)(base + off); }
+  template <class T> void piece(T *&p, size_t n) { const size_t off = take(n * sizeof(T)); if (base) p = at<T>(off); }
+  void place(void *block) { base = (char *)block; total = 0; } // the second walk starts here
+  template <class H> int alloc_pieces(H *h, ccmp_ctx *ctx, const char *what)
+  {
+    h->pieces(*this);
+    const int rc = alloc(h, ctx, what);
+    if (rc != CCMP_OK) return rc;
+    place(h->block);
+    h->pieces(*this);
+    return CCMP_OK;
+  }
   template <class H> int alloc(H *h, ccmp_ctx *ctx, const char *what)
   {
     h->ctx = ctx;

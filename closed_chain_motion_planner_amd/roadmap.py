@@ -9,6 +9,7 @@ Arguments that are torch tensors are taken as device memory and the calls are as
 arrays go through the synchronous host forms and come back as numpy arrays.  All arithmetic happens in libccmp.so.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -141,45 +142,105 @@ def _edge_outputs(K, E, ms):
             "blocked": K.empty((E,), "uint8"), "carry": K.empty((E, 2), "float64")}
 
 
-# ---- the planner's loop on the store (include/ccmp.h: ccmp_plan_*; the rule: csrc/ccmp_plan.h) -------------------------------------------
-PLAN_STATUS = {_lib.PLAN_OPEN: "OPEN", _lib.PLAN_SOLVED: "SOLVED", _lib.PLAN_BUDGET: "BUDGET", _lib.PLAN_FULL: "FULL", _lib.PLAN_INVALID_GOAL: "INVALID_GOAL"}
-_PLAN_COUNTERS = [n for n, _ in _lib.CcmpPlanCounters._fields_ if n != "reserved"]
-
-
-def plan_options(**kw):
-    """ccmp_plan_opts with the library's defaults (width 32, k 5, attempts 2, max_states 64, t 0.3, sigma 0.2, inflate 0, lo / hi
-    -1e30 / 1e30, max_vertices 2^31 - 1), fields overridden by keyword"""
-    o = _lib.CcmpPlanOpts()
-    _lib.lib().ccmp_plan_default_opts(C.byref(o))
+# ---- what the two planners on the store share: options, the state block as a dict, the handle's wrapper ------------------------------------
+def _options(struct, defaults, what, kw):
+    """`struct` with the library's defaults, fields overridden by keyword (a float sequence into an array field); `reserved` is no field"""
+    o = struct()
+    defaults(C.byref(o))
     for name, v in kw.items():
-        if name not in dict(_lib.CcmpPlanOpts._fields_):
-            raise TypeError("ccmp_plan_opts has no field %r" % name)
-        if name in ("lo", "hi"):
+        if name not in dict(struct._fields_) or name == "reserved":
+            raise TypeError("%s has no field %r" % (what, name))
+        if isinstance(getattr(o, name), C.Array):
             getattr(o, name)[:] = [float(x) for x in v]
         else:
             setattr(o, name, v)
     return o
 
 
-def _plan_state_dict(s):
-    """a ccmp_plan_state as a dict of plain values (starts / goals cut to their lengths)"""
-    d = {n: getattr(s, n) for n in ("nearest", "sprevious", "status", "cycle", "solved_start", "solved_goal", "size_at_check", "next_index", "prev_from_goal",
-                                     "prev_from_start")}
-    d.update(starts=list(s.starts[:s.n_starts]), goals=list(s.goals[:s.n_goals]), nearest_pose=list(s.nearest_pose),
-             counters={n: getattr(s.counters, n) for n in _PLAN_COUNTERS})
+def _state_dict(s, scalars, counters):
+    """a state block as a dict of plain values: its scalars, starts / goals cut to their lengths, nearest_pose where it has one, counters"""
+    d = {n: getattr(s, n) for n in scalars}
+    d.update(starts=list(s.starts[:s.n_starts]), goals=list(s.goals[:s.n_goals]))
+    if hasattr(s, "nearest_pose"):
+        d["nearest_pose"] = list(s.nearest_pose)
+    d["counters"] = {n: getattr(s.counters, n) for n in counters}
     return d
 
 
-def _plan_state_struct(d):
-    s = _lib.CcmpPlanState()
-    for n in ("nearest", "sprevious", "status", "cycle", "solved_start", "solved_goal", "size_at_check", "next_index", "prev_from_goal", "prev_from_start"):
+def _state_struct(struct, d, scalars, counters):
+    s = struct()
+    for n in scalars:
         setattr(s, n, d[n])
     s.n_starts, s.n_goals = len(d["starts"]), len(d["goals"])
+    s.starts[:], s.goals[:] = [-1] * 8, [-1] * 8  # beyond the lengths: read by nothing
     s.starts[:s.n_starts], s.goals[:s.n_goals] = [int(v) for v in d["starts"]], [int(v) for v in d["goals"]]
-    s.nearest_pose[:] = [float(v) for v in d["nearest_pose"]]
-    for n in _PLAN_COUNTERS:
+    if "nearest_pose" in d:
+        s.nearest_pose[:] = [float(v) for v in d["nearest_pose"]]
+    for n in counters:
         setattr(s.counters, n, int(d["counters"].get(n, 0)))
     return s
+
+
+def _connected_ref(name, labels, state, to_struct, to_dict):
+    lab = HOST.expect(labels, "int32", -1, "labels")
+    s = to_struct(state)
+    check(getattr(_lib.lib(), name)(_arg(lab), len(lab), C.byref(s)), name)
+    return to_dict(s)
+
+
+class _PlannerHandle:
+    """what `Plan` and `RRTConnect` share: a handle opened by the `Roadmap`, `run`, `state`, `close`.  A subclass names its C entries'
+    prefix (_ABI), its report and state structs, its status table and SOLVED value, its state helpers and its counters, and adds its own
+    report fields in `_report_more`."""
+
+    def __init__(self, roadmap, scene, handle):
+        self.roadmap, self.scene, self._h = roadmap, scene, handle  # the store and the scene outlive the handle
+        self.report = None
+        self.run(0)
+
+    def _call(self, verb, *args):
+        name = "%s_%s" % (self._ABI, verb)
+        check(getattr(_lib.lib(), name)(self._h, *args), name)
+
+    def run(self, max_cycles):
+        r = self._REPORT()
+        self._call("run", int(max_cycles), C.byref(r))
+        self.report = {"status": r.status, "status_name": self._STATUS.get(r.status, "?"), "cycles_run": r.cycles_run, "cycles_total": r.cycles_total,
+                       "size": int(r.size), "edges": int(r.edges), "solved": (r.solved_start, r.solved_goal) if r.status == self._SOLVED else None}
+        self.report.update(self._report_more(r), counters={n: getattr(r.counters, n) for n in self._COUNTERS})
+        return self.report
+
+    def state(self):
+        s = self._STATE()
+        self._call("state_read", C.byref(s))
+        return self._state_dict(s)
+
+    def close(self):
+        if self._h:
+            getattr(_lib.lib(), self._ABI + "_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- the planner's loop on the store (include/ccmp.h: ccmp_plan_*; the rule: csrc/ccmp_plan.h) -------------------------------------------
+PLAN_STATUS = {_lib.PLAN_OPEN: "OPEN", _lib.PLAN_SOLVED: "SOLVED", _lib.PLAN_BUDGET: "BUDGET", _lib.PLAN_FULL: "FULL", _lib.PLAN_INVALID_GOAL: "INVALID_GOAL"}
+_PLAN_COUNTERS = [n for n, _ in _lib.CcmpPlanCounters._fields_ if n != "reserved"]
+_PLAN_SCALARS = ("nearest", "sprevious", "status", "cycle", "solved_start", "solved_goal", "size_at_check", "next_index", "prev_from_goal", "prev_from_start")
+
+
+def plan_options(**kw):
+    """ccmp_plan_opts with the library's defaults (width 32, k 5, attempts 2, max_states 64, t 0.3, sigma 0.2, inflate 0, lo / hi
+    -1e30 / 1e30, max_vertices 2^31 - 1), fields overridden by keyword"""
+    return _options(_lib.CcmpPlanOpts, _lib.lib().ccmp_plan_default_opts, "ccmp_plan_opts", kw)
+
+
+_plan_state_dict = functools.partial(_state_dict, scalars=_PLAN_SCALARS, counters=_PLAN_COUNTERS)
+_plan_state_struct = functools.partial(_state_struct, _lib.CcmpPlanState, scalars=_PLAN_SCALARS, counters=_PLAN_COUNTERS)
 
 
 def _closest3(a, n):
@@ -213,49 +274,26 @@ def plan_prefix_ref(valid, ik_ok):
 def plan_connected_ref(labels, state):
     """ccmp_plan_connected_ref: the solution test — the first pair (s, g), start-major, whose labels agree makes the state SOLVED with
     that pair.  Returns the new state; host only."""
-    lab = HOST.expect(labels, "int32", -1, "labels")
-    s = _plan_state_struct(state)
-    check(_lib.lib().ccmp_plan_connected_ref(_arg(lab), len(lab), C.byref(s)), "ccmp_plan_connected_ref")
-    return _plan_state_dict(s)
+    return _connected_ref("ccmp_plan_connected_ref", labels, state, _plan_state_struct, _plan_state_dict)
 
 
-class Plan:
+class Plan(_PlannerHandle):
     """ccmp_plan: the planner's loop on a `Roadmap` (`Roadmap.plan` opens one).  `run(max_cycles)` runs cycles until the status is SOLVED,
     FULL or the cycles are spent (BUDGET: run again to resume) and returns the report, also kept as `.report`: a dict with status (a
     PLAN_STATUS key; `status_name` its text), cycles_run, cycles_total, size, edges, solved (start vertex, goal vertex) or None, nearest,
-    prev_from_goal, prev_from_start and counters.  The path of a SOLVED plan is `Roadmap.shortest_paths([s], [g])` on that pair."""
+    prev_from_goal, prev_from_start and counters.  The path of a SOLVED plan is `Roadmap.shortest_paths([s], [g])` on that pair.
+    `state()`: the state block (ccmp_plan_state) as a dict: starts, goals, nearest, nearest_pose, sprevious, prev_from_goal,
+    prev_from_start, size_at_check, next_index, cycle, status, solved_start, solved_goal, counters."""
+    _ABI, _REPORT, _STATE, _STATUS, _SOLVED, _COUNTERS = "ccmp_plan", _lib.CcmpPlanReport, _lib.CcmpPlanState, PLAN_STATUS, _lib.PLAN_SOLVED, _PLAN_COUNTERS
+    _state_dict = staticmethod(_plan_state_dict)
 
     def __init__(self, roadmap, checker, scene, handle):
-        self.roadmap, self.checker, self.scene, self._h = roadmap, checker, scene, handle  # the store, the object and the scene outlive the handle
-        self.report = None
-        self.run(0)
+        self.checker = checker  # the object outlives the handle too
+        super().__init__(roadmap, scene, handle)
 
-    def run(self, max_cycles):
-        r = _lib.CcmpPlanReport()
-        check(_lib.lib().ccmp_plan_run(self._h, int(max_cycles), C.byref(r)), "ccmp_plan_run")
-        self.report = {"status": r.status, "status_name": PLAN_STATUS.get(r.status, "?"), "cycles_run": r.cycles_run, "cycles_total": r.cycles_total,
-                       "size": int(r.size), "edges": int(r.edges), "solved": (r.solved_start, r.solved_goal) if r.status == _lib.PLAN_SOLVED else None,
-                       "nearest": r.nearest, "prev_from_goal": r.prev_from_goal, "prev_from_start": r.prev_from_start,
-                       "counters": {n: getattr(r.counters, n) for n in _PLAN_COUNTERS}}
-        return self.report
-
-    def state(self):
-        """the planner's state block (ccmp_plan_state) as a dict: starts, goals, nearest, nearest_pose, sprevious, prev_from_goal,
-        prev_from_start, size_at_check, next_index, cycle, status, solved_start, solved_goal, counters"""
-        s = _lib.CcmpPlanState()
-        check(_lib.lib().ccmp_plan_state_read(self._h, C.byref(s)), "ccmp_plan_state_read")
-        return _plan_state_dict(s)
-
-    def close(self):
-        if self._h:
-            _lib.lib().ccmp_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @staticmethod
+    def _report_more(r):
+        return {"nearest": r.nearest, "prev_from_goal": r.prev_from_goal, "prev_from_start": r.prev_from_start}
 
 
 # ---- RRT-Connect on the store (include/ccmp.h: ccmp_rrtc_*; the rule: csrc/ccmp_rrtc.h) --------------------------------------------------
@@ -267,32 +305,11 @@ _RRTC_SCALARS = ("status", "cycle", "next_index", "solved_start", "solved_goal",
 def rrtc_options(**kw):
     """ccmp_rrtc_opts with the library's defaults (width 32, max_states 64, round_budget 0, range 0.1, max_vertices 2^31 - 1), fields
     overridden by keyword"""
-    o = _lib.CcmpRrtcOpts()
-    _lib.lib().ccmp_rrtc_default_opts(C.byref(o))
-    for name, v in kw.items():
-        if name not in dict(_lib.CcmpRrtcOpts._fields_) or name == "reserved":
-            raise TypeError("ccmp_rrtc_opts has no field %r" % name)
-        setattr(o, name, v)
-    return o
+    return _options(_lib.CcmpRrtcOpts, _lib.lib().ccmp_rrtc_default_opts, "ccmp_rrtc_opts", kw)
 
 
-def _rrtc_state_dict(s):
-    """a ccmp_rrtc_state as a dict of plain values (starts / goals cut to their lengths)"""
-    d = {n: getattr(s, n) for n in _RRTC_SCALARS}
-    d.update(starts=list(s.starts[:s.n_starts]), goals=list(s.goals[:s.n_goals]), counters={n: getattr(s.counters, n) for n in _RRTC_COUNTERS})
-    return d
-
-
-def _rrtc_state_struct(d):
-    s = _lib.CcmpRrtcState()
-    for n in _RRTC_SCALARS:
-        setattr(s, n, d[n])
-    s.n_starts, s.n_goals = len(d["starts"]), len(d["goals"])
-    s.starts[:], s.goals[:] = [-1] * 8, [-1] * 8
-    s.starts[:s.n_starts], s.goals[:s.n_goals] = [int(v) for v in d["starts"]], [int(v) for v in d["goals"]]
-    for n in _RRTC_COUNTERS:
-        setattr(s.counters, n, int(d["counters"].get(n, 0)))
-    return s
+_rrtc_state_dict = functools.partial(_state_dict, scalars=_RRTC_SCALARS, counters=_RRTC_COUNTERS)
+_rrtc_state_struct = functools.partial(_state_struct, _lib.CcmpRrtcState, scalars=_RRTC_SCALARS, counters=_RRTC_COUNTERS)
 
 
 def rrtc_pick_ref(states, n_states, ok, to, d=None, use=None, range=0.1, mode=0):
@@ -330,10 +347,7 @@ def rrtc_pick(ctx, states, n_states, ok, to, d=None, use=None, range=0.1, mode=0
 
 def rrtc_connected_ref(labels, state):
     """ccmp_rrtc_connected_ref: the solution test on a state dict as `RRTConnect.state` returns it; returns the new state; host only"""
-    lab = HOST.expect(labels, "int32", -1, "labels")
-    s = _rrtc_state_struct(state)
-    check(_lib.lib().ccmp_rrtc_connected_ref(_arg(lab), len(lab), C.byref(s)), "ccmp_rrtc_connected_ref")
-    return _rrtc_state_dict(s)
+    return _connected_ref("ccmp_rrtc_connected_ref", labels, state, _rrtc_state_struct, _rrtc_state_dict)
 
 
 def nearest_in_tree_ref(store_joints, labels, roots, queries):
@@ -354,31 +368,18 @@ def rrtc_nearest_shape(ctx_handle, Q, N):
     return int(part.value), int(parts.value)
 
 
-class RRTConnect:
+class RRTConnect(_PlannerHandle):
     """ccmp_rrtc: RRT-Connect on a `Roadmap` (`Roadmap.rrt_connect` opens one).  `run(max_cycles)` runs cycles until the status is SOLVED,
     FULL or the cycles are spent (BUDGET: run again to resume) and returns the report, also kept as `.report`: a dict with status (an
     RRTC_STATUS key; `status_name` its text), cycles_run, cycles_total, size, edges, solved (start vertex, goal vertex) or None, best_gap
-    and best (its pair, start side first) and counters."""
+    and best (its pair, start side first) and counters.  `state()`: the state block (ccmp_rrtc_state) as a dict: starts, goals, status,
+    cycle, next_index, solved_start, solved_goal, best_gap, best_a, best_b, counters."""
+    _ABI, _REPORT, _STATE, _STATUS, _SOLVED, _COUNTERS = "ccmp_rrtc", _lib.CcmpRrtcReport, _lib.CcmpRrtcState, RRTC_STATUS, _lib.RRTC_SOLVED, _RRTC_COUNTERS
+    _state_dict = staticmethod(_rrtc_state_dict)
 
-    def __init__(self, roadmap, scene, handle):
-        self.roadmap, self.scene, self._h = roadmap, scene, handle  # the store and the scene outlive the handle
-        self.report = None
-        self.run(0)
-
-    def run(self, max_cycles):
-        r = _lib.CcmpRrtcReport()
-        check(_lib.lib().ccmp_rrtc_run(self._h, int(max_cycles), C.byref(r)), "ccmp_rrtc_run")
-        self.report = {"status": r.status, "status_name": RRTC_STATUS.get(r.status, "?"), "cycles_run": r.cycles_run, "cycles_total": r.cycles_total,
-                       "size": int(r.size), "edges": int(r.edges), "solved": (r.solved_start, r.solved_goal) if r.status == _lib.RRTC_SOLVED else None,
-                       "best_gap": r.best_gap, "best": (r.best_a, r.best_b), "counters": {n: getattr(r.counters, n) for n in _RRTC_COUNTERS}}
-        return self.report
-
-    def state(self):
-        """the state block (ccmp_rrtc_state) as a dict: starts, goals, status, cycle, next_index, solved_start, solved_goal, best_gap,
-        best_a, best_b, counters"""
-        s = _lib.CcmpRrtcState()
-        check(_lib.lib().ccmp_rrtc_state_read(self._h, C.byref(s)), "ccmp_rrtc_state_read")
-        return _rrtc_state_dict(s)
+    @staticmethod
+    def _report_more(r):
+        return {"best_gap": r.best_gap, "best": (r.best_a, r.best_b)}
 
     def solution(self, max_len=64, host=False):
         """`Roadmap.shortest_paths` on the solved pair (its dict, one pair), or None while the status is not SOLVED"""
@@ -386,17 +387,6 @@ class RRTConnect:
             return None
         s, g = self.report["solved"]
         return self.roadmap.shortest_paths(np.array([s], dtype=np.int32), np.array([g], dtype=np.int32), max_len=max_len, host=host)
-
-    def close(self):
-        if self._h:
-            _lib.lib().ccmp_rrtc_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Roadmap:

@@ -1766,7 +1766,114 @@ private:
   mutable detail::ErrorLatch err_; // ikValid's sticky error (the other verbs throw)
 };
 
-// ---- the planner's loop on the store (include/ccmp.h: ccmp_plan_*) ------------------------------------------------------------------
+// ---- the planners on the store (include/ccmp.h: ccmp_plan_*, ccmp_rrtc_*) -----------------------------------------------------------
+namespace detail {
+
+// One resumable planner object over the C handle that the traits T name: Handle, Report, State; run / stateRead / destroy (the C entries)
+// with kRun / kState (their texts in an error) and kCreate (the text recorded on a failed open); kSolved; blank(report): the fields
+// beyond status and the solved pair of a planner never opened.  ccmp::Planner and ccmp::RRTConnectPlanner add their constructors.
+// Never throws: a planner that could not be opened answers "no" to every verb and keeps the FIRST failure in lastError() /
+// lastErrorMessage() until clearError(), as ccmp::Roadmap does.  The handle is destroyed under the lock.
+template <class T> class PlannerBase {
+public:
+  ~PlannerBase()
+  {
+    if (!plan_) return;
+    std::lock_guard<std::mutex> hold(*mu_);
+    T::destroy(plan_);
+  }
+  PlannerBase(const PlannerBase &) = delete;
+  PlannerBase &operator=(const PlannerBase &) = delete;
+
+  bool create() const noexcept { return plan_ != nullptr; } // was it opened
+  // up to max_cycles more cycles; true = the call ran (report() has the verdict), false = it failed or there is no planner
+  bool run(int max_cycles) noexcept
+  {
+    return guardedCall(plan_ != nullptr, *mu_, err_, +T::kRun, [&] { return T::run(plan_, max_cycles, &report_); });
+  }
+  const typename T::Report &report() const noexcept { return report_; }
+  int status() const noexcept { return plan_ ? report_.status : -1; }
+  bool solved() const noexcept { return plan_ && report_.status == T::kSolved; }
+  bool state(typename T::State *out) const noexcept
+  {
+    return guardedCall(plan_ != nullptr, *mu_, err_, +T::kState, [&] { return T::stateRead(plan_, out); });
+  }
+  int lastError() const noexcept { return err_.code(); }
+  std::string lastErrorMessage() const { return err_.message(); }
+  void clearError() noexcept { err_.clear(); }
+  typename T::Handle *handle() const noexcept { return plan_; }
+
+protected:
+  // shared: the Projector's mutex, or nullptr for a mutex of the planner's own (a caller on the C handles)
+  explicit PlannerBase(std::mutex *shared) noexcept : mu_(shared ? shared : &own_mu_) {}
+  // create_call(&handle) = the planner's *_create; then a run of no cycles for the report
+  template <class F> void open(F &&create_call) noexcept
+  {
+    std::memset(&report_, 0, sizeof report_);
+    report_.status = -1;
+    report_.solved_start = report_.solved_goal = -1;
+    T::blank(report_);
+    int rc;
+    try {
+      std::lock_guard<std::mutex> hold(*mu_);
+      rc = create_call(&plan_); // a NULL store: the library's own answer
+      if (rc == CCMP_OK) rc = T::run(plan_, 0, &report_);
+    } catch (...) {
+      rc = CCMP_EHIP;
+    }
+    if (rc != CCMP_OK) err_.record(rc, +T::kCreate);
+  }
+
+private:
+  std::mutex own_mu_;
+  std::mutex *mu_;
+  typename T::Handle *plan_ = nullptr;
+  typename T::Report report_;
+  mutable ErrorLatch err_;
+};
+
+struct PlanTraits {
+  using Handle = ccmp_plan;
+  using Report = ccmp_plan_report;
+  using State = ccmp_plan_state;
+  enum { kSolved = CCMP_PLAN_SOLVED };
+  static int run(ccmp_plan *h, int n, ccmp_plan_report *r) { return ccmp_plan_run(h, n, r); }
+  static int stateRead(ccmp_plan *h, ccmp_plan_state *s) { return ccmp_plan_state_read(h, s); }
+  static void destroy(ccmp_plan *h) { ccmp_plan_destroy(h); }
+  static constexpr const char *kRun = "ccmp_plan_run", *kState = "ccmp_plan_state_read", *kCreate = "ccmp_plan_create";
+  static void blank(ccmp_plan_report &r) { r.nearest = -1; }
+};
+
+struct RRTConnectTraits {
+  using Handle = ccmp_rrtc;
+  using Report = ccmp_rrtc_report;
+  using State = ccmp_rrtc_state;
+  enum { kSolved = CCMP_RRTC_SOLVED };
+  static int run(ccmp_rrtc *h, int n, ccmp_rrtc_report *r) { return ccmp_rrtc_run(h, n, r); }
+  static int stateRead(ccmp_rrtc *h, ccmp_rrtc_state *s) { return ccmp_rrtc_state_read(h, s); }
+  static void destroy(ccmp_rrtc *h) { ccmp_rrtc_destroy(h); }
+  static constexpr const char *kRun = "ccmp_rrtc_run", *kState = "ccmp_rrtc_state_read", *kCreate = "ccmp_rrtc_create";
+  static void blank(ccmp_rrtc_report &r) { r.best_a = r.best_b = -1; }
+};
+
+// the tail of Roadmap::solve / solveRRTConnect: the cycles, the report, the planner's error into the store's latch, the solved pair
+template <class P, class R> int solveWith(P &planner, int max_cycles, int32_t *start, int32_t *goal, R *report, ErrorLatch &err) noexcept
+{
+  if (planner.create() && max_cycles > 0) planner.run(max_cycles);
+  if (report) *report = planner.report();
+  if (planner.lastError() != CCMP_OK) {
+    err.recordAs(planner.lastError(), planner.lastErrorMessage().c_str());
+    return -1;
+  }
+  if (planner.solved()) {
+    if (start) *start = planner.report().solved_start;
+    if (goal) *goal = planner.report().solved_goal;
+  }
+  return planner.status();
+}
+
+}  // namespace detail
+
 // stefanBiPRM::solve / constructRoadmap / checkForSolution as one resumable object: open (start and goal vertex through
 // startgoalMilestone), then cycles of growth (width candidates where the reference has one), check (closestFromGoal both ways, goal and
 // start IK, the nine-pose ladder as one batch) and the solution test, with the bookkeeping on the device.  A restatement of the
@@ -1775,70 +1882,23 @@ struct PlanOptions : ccmp_plan_opts {
   PlanOptions() noexcept { ccmp_plan_default_opts(this); }
 };
 
-// Never throws: a Planner that could not be opened answers "no" to every verb and keeps the FIRST failure in lastError() /
-// lastErrorMessage() until clearError(), as ccmp::Roadmap does.  The store, the object and the scene must outlive it.
-class Planner {
+// detail::PlannerBase's verbs and contract.  The store, the object and the scene must outlive it.
+class Planner : public detail::PlannerBase<detail::PlanTraits> {
 public:
   Planner(Roadmap &roadmap, const ccmp_object *object, const PlanOptions &opts = PlanOptions(), const ccmp_scene *scene = nullptr, double margin = 0.0,
-          const double *goal_joints14 = nullptr, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept : mu_(&roadmap.projector().mutex())
+          const double *goal_joints14 = nullptr, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept : PlannerBase(&roadmap.projector().mutex())
   {
-    open(roadmap.handle(), &roadmap.projector().problem(), object, scene, margin, &roadmap.projector().ikOptions(), opts, goal_joints14, rng_seed, first_index);
+    open([&](ccmp_plan **out) {
+      return ccmp_plan_create(roadmap.handle(), &roadmap.projector().problem(), object, scene, margin, &roadmap.projector().ikOptions(), &opts, goal_joints14,
+                              rng_seed, first_index, out);
+    });
   }
   // the same on the C handles (a caller without a Projector); serialised by a mutex of its own
   Planner(ccmp_roadmap *roadmap, const ccmp_problem &problem, const ccmp_object *object, const PlanOptions &opts = PlanOptions(), const ccmp_scene *scene = nullptr,
-          double margin = 0.0, const double *goal_joints14 = nullptr, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept : mu_(&own_mu_)
+          double margin = 0.0, const double *goal_joints14 = nullptr, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept : PlannerBase(nullptr)
   {
-    open(roadmap, &problem, object, scene, margin, nullptr, opts, goal_joints14, rng_seed, first_index);
+    open([&](ccmp_plan **out) { return ccmp_plan_create(roadmap, &problem, object, scene, margin, nullptr, &opts, goal_joints14, rng_seed, first_index, out); });
   }
-  ~Planner()
-  {
-    if (!plan_) return;
-    std::lock_guard<std::mutex> hold(*mu_);
-    ccmp_plan_destroy(plan_);
-  }
-  Planner(const Planner &) = delete;
-  Planner &operator=(const Planner &) = delete;
-
-  bool create() const noexcept { return plan_ != nullptr; } // was it opened
-  // up to max_cycles more cycles; true = the call ran (report() has the verdict), false = it failed or there is no planner
-  bool run(int max_cycles) noexcept
-  {
-    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_plan_run", [&] { return ccmp_plan_run(plan_, max_cycles, &report_); });
-  }
-  const ccmp_plan_report &report() const noexcept { return report_; }
-  int status() const noexcept { return plan_ ? report_.status : -1; }
-  bool solved() const noexcept { return plan_ && report_.status == CCMP_PLAN_SOLVED; }
-  bool state(ccmp_plan_state *out) const noexcept
-  {
-    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_plan_state_read", [&] { return ccmp_plan_state_read(plan_, out); });
-  }
-  int lastError() const noexcept { return err_.code(); }
-  std::string lastErrorMessage() const { return err_.message(); }
-  void clearError() noexcept { err_.clear(); }
-  ccmp_plan *handle() const noexcept { return plan_; }
-
-private:
-  void open(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_object *object, const ccmp_scene *scene, double margin, const ccmp_ik_opts *ik,
-            const ccmp_plan_opts &opts, const double *goal_joints14, uint64_t rng_seed, uint64_t first_index) noexcept
-  {
-    std::memset(&report_, 0, sizeof report_);
-    report_.status = -1;
-    report_.solved_start = report_.solved_goal = report_.nearest = -1;
-    int rc;
-    try {
-      std::lock_guard<std::mutex> hold(*mu_);
-      rc = ccmp_plan_create(rm, p, object, scene, margin, ik, &opts, goal_joints14, rng_seed, first_index, &plan_); // a NULL store: the library's own answer
-      if (rc == CCMP_OK) rc = ccmp_plan_run(plan_, 0, &report_);
-    } catch (...) {
-      rc = CCMP_EHIP;
-    }
-    if (rc != CCMP_OK) err_.record(rc, "ccmp_plan_create");
-  }
-  std::mutex own_mu_;
-  std::mutex *mu_;
-  ccmp_plan *plan_ = nullptr;
-  ccmp_plan_report report_;
-  mutable detail::ErrorLatch err_;
 };
 
 inline int Roadmap::solve(const ccmp_object *object, int max_cycles, int32_t *start, int32_t *goal, const ccmp_plan_opts *opts, const ccmp_scene *scene,
@@ -1849,20 +1909,9 @@ inline int Roadmap::solve(const ccmp_object *object, int max_cycles, int32_t *st
   if (start) *start = -1;
   if (goal) *goal = -1;
   Planner planner(*this, object, o, scene, margin, goal_joints14, rng_seed);
-  if (planner.create() && max_cycles > 0) planner.run(max_cycles);
-  if (report) *report = planner.report();
-  if (planner.lastError() != CCMP_OK) {
-    err_.recordAs(planner.lastError(), planner.lastErrorMessage().c_str());
-    return -1;
-  }
-  if (planner.solved()) {
-    if (start) *start = planner.report().solved_start;
-    if (goal) *goal = planner.report().solved_goal;
-  }
-  return planner.status();
+  return detail::solveWith(planner, max_cycles, start, goal, report, err_);
 }
 
-// ---- RRT-Connect on the store (include/ccmp.h: ccmp_rrtc_*) ---------------------------------------------------------------------------
 // The reference's other planner (ConstrainedProblem::setPlanner(RRTConnect)) as one resumable object: two trees in joint space over the
 // store's component labels, width samples per cycle, one traversal per extension clipped at `range`, one traversal per connection.  NOT
 // OMPL's RRTConnect step for step: include/ccmp.h lists the stated differences (one clipped traversal, a one-traversal connect phase,
@@ -1871,73 +1920,25 @@ struct RRTConnectOptions : ccmp_rrtc_opts {
   RRTConnectOptions() noexcept { ccmp_rrtc_default_opts(this); }
 };
 
-// Never throws: a planner that could not be opened answers "no" to every verb and keeps the FIRST failure in lastError() /
-// lastErrorMessage() until clearError(), as ccmp::Planner does.  The store and the scene must outlive it.
-class RRTConnectPlanner {
+// detail::PlannerBase's verbs and contract.  The store and the scene must outlive it.
+class RRTConnectPlanner : public detail::PlannerBase<detail::RRTConnectTraits> {
 public:
   RRTConnectPlanner(Roadmap &roadmap, const int32_t *starts, int n_starts, const int32_t *goals, int n_goals, const RRTConnectOptions &opts = RRTConnectOptions(),
                     const ccmp_scene *scene = nullptr, double margin = 0.0, uint64_t rng_seed = 0, uint64_t first_index = 0) noexcept
-      : mu_(&roadmap.projector().mutex())
+      : PlannerBase(&roadmap.projector().mutex())
   {
-    open(roadmap.handle(), &roadmap.projector().problem(), scene, margin, opts, starts, n_starts, goals, n_goals, rng_seed, first_index);
+    open([&](ccmp_rrtc **out) {
+      return ccmp_rrtc_create(roadmap.handle(), &roadmap.projector().problem(), scene, margin, &opts, starts, n_starts, goals, n_goals, rng_seed, first_index, out);
+    });
   }
   // the same on the C handles (a caller without a Projector); serialised by a mutex of its own
   RRTConnectPlanner(ccmp_roadmap *roadmap, const ccmp_problem &problem, const int32_t *starts, int n_starts, const int32_t *goals, int n_goals,
                     const RRTConnectOptions &opts = RRTConnectOptions(), const ccmp_scene *scene = nullptr, double margin = 0.0, uint64_t rng_seed = 0,
                     uint64_t first_index = 0) noexcept
-      : mu_(&own_mu_)
+      : PlannerBase(nullptr)
   {
-    open(roadmap, &problem, scene, margin, opts, starts, n_starts, goals, n_goals, rng_seed, first_index);
+    open([&](ccmp_rrtc **out) { return ccmp_rrtc_create(roadmap, &problem, scene, margin, &opts, starts, n_starts, goals, n_goals, rng_seed, first_index, out); });
   }
-  ~RRTConnectPlanner()
-  {
-    if (!plan_) return;
-    std::lock_guard<std::mutex> hold(*mu_);
-    ccmp_rrtc_destroy(plan_);
-  }
-  RRTConnectPlanner(const RRTConnectPlanner &) = delete;
-  RRTConnectPlanner &operator=(const RRTConnectPlanner &) = delete;
-
-  bool create() const noexcept { return plan_ != nullptr; } // was it opened
-  // up to max_cycles more cycles; true = the call ran (report() has the verdict), false = it failed or there is no planner
-  bool run(int max_cycles) noexcept
-  {
-    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_rrtc_run", [&] { return ccmp_rrtc_run(plan_, max_cycles, &report_); });
-  }
-  const ccmp_rrtc_report &report() const noexcept { return report_; }
-  int status() const noexcept { return plan_ ? report_.status : -1; }
-  bool solved() const noexcept { return plan_ && report_.status == CCMP_RRTC_SOLVED; }
-  bool state(ccmp_rrtc_state *out) const noexcept
-  {
-    return detail::guardedCall(plan_ != nullptr, *mu_, err_, "ccmp_rrtc_state_read", [&] { return ccmp_rrtc_state_read(plan_, out); });
-  }
-  int lastError() const noexcept { return err_.code(); }
-  std::string lastErrorMessage() const { return err_.message(); }
-  void clearError() noexcept { err_.clear(); }
-  ccmp_rrtc *handle() const noexcept { return plan_; }
-
-private:
-  void open(ccmp_roadmap *rm, const ccmp_problem *p, const ccmp_scene *scene, double margin, const ccmp_rrtc_opts &opts, const int32_t *starts, int n_starts,
-            const int32_t *goals, int n_goals, uint64_t rng_seed, uint64_t first_index) noexcept
-  {
-    std::memset(&report_, 0, sizeof report_);
-    report_.status = -1;
-    report_.solved_start = report_.solved_goal = report_.best_a = report_.best_b = -1;
-    int rc;
-    try {
-      std::lock_guard<std::mutex> hold(*mu_);
-      rc = ccmp_rrtc_create(rm, p, scene, margin, &opts, starts, n_starts, goals, n_goals, rng_seed, first_index, &plan_); // a NULL store: the library's own answer
-      if (rc == CCMP_OK) rc = ccmp_rrtc_run(plan_, 0, &report_);
-    } catch (...) {
-      rc = CCMP_EHIP;
-    }
-    if (rc != CCMP_OK) err_.record(rc, "ccmp_rrtc_create");
-  }
-  std::mutex own_mu_;
-  std::mutex *mu_;
-  ccmp_rrtc *plan_ = nullptr;
-  ccmp_rrtc_report report_;
-  mutable detail::ErrorLatch err_;
 };
 
 inline int Roadmap::solveRRTConnect(const int32_t *starts, int n_starts, const int32_t *goals, int n_goals, int max_cycles, int32_t *start, int32_t *goal,
@@ -1948,17 +1949,7 @@ inline int Roadmap::solveRRTConnect(const int32_t *starts, int n_starts, const i
   if (start) *start = -1;
   if (goal) *goal = -1;
   RRTConnectPlanner planner(*this, starts, n_starts, goals, n_goals, o, scene, margin, rng_seed);
-  if (planner.create() && max_cycles > 0) planner.run(max_cycles);
-  if (report) *report = planner.report();
-  if (planner.lastError() != CCMP_OK) {
-    err_.recordAs(planner.lastError(), planner.lastErrorMessage().c_str());
-    return -1;
-  }
-  if (planner.solved()) {
-    if (start) *start = planner.report().solved_start;
-    if (goal) *goal = planner.report().solved_goal;
-  }
-  return planner.status();
+  return detail::solveWith(planner, max_cycles, start, goal, report, err_);
 }
 
 inline bool Projector::sampleCalibGoal(const double *pose8, const double *seeds, int S, double *result14, int *which, const ProxyScene &scene, double margin,

@@ -33,6 +33,9 @@ def _pose_store(c, n, capacity_hint=None, seed=0):
     poses[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
     rm = Roadmap(c, capacity_hint=n if capacity_hint is None else capacity_hint)
     rm.append(None, _dev(poses))
+    import torch
+
+    torch.cuda.current_stream().synchronize()  # the append is asynchronous on this stream; the tests' host forms run on the context's own
     return rm, poses
 
 

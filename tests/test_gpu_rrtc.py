@@ -8,7 +8,9 @@ fixture scene, the far goal of tests/plan_cases.py (a goal one motion does not r
 3. `RRTConnect` equals the loop written by hand (tests/rrtc_cases.py: HandRRTConnect) after every one of six cycles — state, store rows,
    edges and labels bit for bit — and `run(2)` three times equals `run(6)` once; then the invariants of the store it grew.
 4. What occurred, from the hand loop, on the union of the runs: see test_the_runs_cover_the_outcomes.
-5. A solved run on the shipped goal: the path and its dense form.  FULL at the stated size, a run after SOLVED, the argument checks."""
+5. A solved run on the shipped goal: the path and its dense form.  FULL at the stated size, a run after SOLVED, the argument checks.
+6. The solution test's kernel, which Plan shares, at open on lists of 1 x 1, 1 x 8, 8 x 1, 8 x 8 and 3 x 5 vertices: no pair, the last
+   pair alone, two pairs whose start-major and goal-major orders differ."""
 import numpy as np
 import pytest
 
@@ -330,6 +332,58 @@ def test_a_solved_run_on_the_shipped_goal(gpu_ctx):
     assert again == dict(r, cycles_run=0) and len(rm) == r["size"]
     for h in (pl, rm, rm_h, chk):
         h.close()
+
+
+# ---- 6. the solution test's kernel (one text for Plan and RRTConnect) at the list shapes where its lane arithmetic can go wrong --------------
+def _pair_lists(S, G, case):
+    """starts [S], goals [G] on a store of 12 vertices in four components (vertex v in component v % 4; a list may repeat a vertex):
+    "none": no pair is connected; "last": only pair (S - 1, G - 1), at 8 x 8 lane 63; "two": pairs (lo, G - 1) and (hi, 0) with lo < hi —
+    start-major order takes the first, goal-major order would take the second wherever S >= 2 and G >= 2"""
+    comp = lambda c, n: [c + 4 * (i % 3) for i in range(n)]
+    if case == "none":
+        return comp(0, S), comp(2, G)
+    if case == "last":
+        return comp(0, S - 1) + [1], comp(2, G - 1) + [5]
+    starts, goals = comp(2, S), comp(3, G)
+    hi = min(2, S - 1)
+    lo = max(hi - 1, 0)
+    if S == 1 or G == 1:  # one list has a single entry: both pairs share it, all four ends in component 0
+        starts[hi], starts[lo], goals[0], goals[G - 1] = 4, 0, 8, 8
+    else:
+        starts[lo], goals[G - 1], starts[hi], goals[0] = 0, 4, 1, 5
+    return starts, goals
+
+
+@pytest.mark.parametrize("S,G", [(1, 1), (1, 8), (8, 1), (8, 8), (3, 5)])
+def test_the_solution_test_at_every_list_shape(gpu_ctx, S, G):
+    """open runs the solution test once (max_cycles = 0).  The expected state is the restatement's (rrtc_cases.new_state + connected) on
+    the labels of graph_labels_ref over the same edges — never the library's _ref form of the test itself."""
+    from closed_chain_motion_planner_amd import KinematicChainConstraint, Roadmap, graph_labels_ref
+
+    c = KinematicChainConstraint.from_yaml(config_path("Wine_Bottle"), ctx=gpu_ctx)
+    rm = Roadmap(c)
+    rm.append(joints=np.random.default_rng(12).uniform(-2.0, 2.0, size=(12, 14)))  # the host forms, both: synchronous on one stream
+    uv = R.tree_edges(12, 4)
+    rm.add_edges(uv)
+    labels = graph_labels_ref(uv, 12)
+    assert labels.tolist() == [v % 4 for v in range(12)]
+    for case in ("none", "last", "two"):
+        starts, goals = _pair_lists(S, G, case)
+        want = R.connected(labels, R.new_state(starts, goals))
+        if case == "none":
+            assert want["status"] == R.OPEN
+        elif case == "last":
+            assert (want["solved_start"], want["solved_goal"]) == (1, 5)
+            assert [(s, g) for s in range(S) for g in range(G) if labels[starts[s]] == labels[goals[g]]] == [(S - 1, G - 1)]
+        elif S >= 2 and G >= 2:  # the orders differ: goal-major would take (starts[hi], goals[0]) = (1, 5)
+            assert (want["solved_start"], want["solved_goal"]) == (0, 4)
+        pl = rm.rrt_connect(c, starts=starts, goals=goals, max_cycles=0)
+        got = pl.state()
+        assert R.state_bits(got) == R.state_bits(want), (case, got, want)
+        assert pl.report["cycles_total"] == 0
+        assert pl.report["solved"] == ((want["solved_start"], want["solved_goal"]) if want["status"] == R.SOLVED else None), (case, pl.report)
+        pl.close()
+    rm.close()
 
 
 def test_full_at_the_stated_size_and_the_argument_checks(gpu_ctx):

@@ -122,3 +122,34 @@ def test_connected_ref_against_the_restatement(ccmp_built):
         hits += got["status"] == R.SOLVED
         assert R.state_bits(rrtc_connected_ref(labels, got)) == R.state_bits(got)
     assert 0 < hits < 40
+
+
+def test_both_connected_refs_are_one_text(ccmp_built):
+    """ccmp_plan_connected_ref and ccmp_rrtc_connected_ref compile one fold (csrc/ccmp_plan.h: first_connected) over their two state
+    types: on the same lists and labels — lengths 0 .. 8, indices -1 .. N (both ends outside the store), N 0 .. 11, labels 0 .. 3 — they
+    return the same (status, solved_start, solved_goal), that of the restatement, and leave every other field as given.  The seed was
+    chosen on the restatement alone: between 1 and 39 of the 40 cases end SOLVED."""
+    import plan_cases as P
+    from closed_chain_motion_planner_amd import plan_connected_ref, rrtc_connected_ref
+
+    r = np.random.default_rng(7)
+    triple = lambda s: (s["status"], s["solved_start"], s["solved_goal"])
+    hits = 0
+    for trial in range(40):
+        N = int(r.integers(0, 12))
+        labels = r.integers(0, 4, size=N).astype(np.int32)
+        starts, goals = r.integers(-1, N + 1, size=int(r.integers(0, 9))), r.integers(-1, N + 1, size=int(r.integers(0, 9)))
+        sr = R.new_state(starts, goals, first_index=trial)
+        sr["best_a"], sr["best_b"], sr["best_gap"], sr["cycle"] = trial, trial + 1, 0.25 * trial, trial
+        sr["counters"] = {n: trial + i for i, n in enumerate(R.COUNTERS)}
+        sp = P.new_state(np.arange(8) + 0.5 * trial, 1.5 * trial, first_index=trial)
+        sp["starts"], sp["goals"] = sr["starts"], sr["goals"]
+        sp["nearest"], sp["sprevious"], sp["size_at_check"], sp["cycle"] = trial, trial + 2, trial + 3, trial
+        sp["counters"] = {n: 2 * trial + i for i, n in enumerate(P.COUNTERS)}
+        want_r, want_p = R.connected(labels, sr), P.connected(labels, sp)
+        assert triple(want_r) == triple(want_p)  # the two restatements agree with each other
+        hits += want_r["status"] == R.SOLVED
+        got_r, got_p = rrtc_connected_ref(labels, sr), plan_connected_ref(labels, sp)
+        assert triple(got_r) == triple(got_p) == triple(want_r), (labels, starts, goals, got_r, got_p, want_r)
+        assert R.state_bits(got_r) == R.state_bits(want_r) and P.state_bits(got_p) == P.state_bits(want_p), (got_r, want_r, got_p, want_p)
+    assert 1 <= hits <= 39, hits
